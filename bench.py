@@ -76,7 +76,41 @@ def parse():
     ap.add_argument("--graph", action="store_true",
                     help="replay each step as one captured HIP graph (for launch-bound small workloads)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU-baseline duration")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to its caller as DIR/<name>.npy (rank 0)")
+    args = ap.parse_args()
+    if args.steps < 0 or args.warmup < 0:
+        ap.error("--steps and --warmup must be >= 0")
+    if args.dump_outputs is not None and args.steps == 0:
+        ap.error("--dump-outputs needs at least one timed step")
+    return args
+
+
+DUMP_MASK_LIMIT = 4 << 20   # mask entries written in full; above it a fixed seeded sample (float32 + float64 index: 48 MB)
+
+
+def dump_outputs(directory: str, out, n: int) -> None:
+    """The outcome of the last timed step — what `ShardedRansac.outcome()` hands its caller — one float32 / float64 .npy per
+    field, so that two builds run with the same arguments (hence the same inputs and seeds) can be compared output for output.
+    No winner: E is NaN, the sample -1 and the mask 0.  More than DUMP_MASK_LIMIT matches: `mask` holds the entries at
+    `mask_index`, a sorted sample drawn with a fixed seed."""
+    os.makedirs(directory, exist_ok=True)
+    found = out.best_h >= 0
+    mask = out.mask if found else np.zeros(n, dtype=np.uint8)
+    arrays = {
+        "best_h": np.array([out.best_h], dtype=np.float64),
+        "error": np.array([out.error], dtype=np.float64),
+        "E": np.asarray(out.E, dtype=np.float64) if found else np.full((3, 3), np.nan),
+        "sample": np.asarray(out.sample if found else np.full(8, -1), dtype=np.float64),
+        "flagged": np.array([out.n_flagged, out.first_flagged], dtype=np.float64),
+    }
+    if n > DUMP_MASK_LIMIT:
+        index = np.sort(np.random.default_rng(0).choice(n, DUMP_MASK_LIMIT, replace=False))
+        arrays["mask_index"] = index.astype(np.float64)
+        mask = mask[index]
+    arrays["mask"] = mask.astype(np.float32)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def cpu_baseline(corr: np.ndarray, seed: int, target_seconds: float):
@@ -724,6 +758,8 @@ def main():
         elapsed = float(tt.cpu()[0])
 
     out = engine.outcome()
+    if rank == 0 and args.dump_outputs is not None:
+        dump_outputs(args.dump_outputs, out, n)
     exact_evals = int(engine.ws.cnt.sum().item()) + 8 * h   # true inliers + sample points of the last step: all must be scored in fp64
     if not args.graph:
         ev = kernel_ev[:args.steps]

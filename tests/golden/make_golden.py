@@ -7,6 +7,7 @@ travels to the GPU box; the committed ``.npz`` files do.
 Harness-side shims (live only in this process, no reference file is touched):
   * ``np.Infinity = np.inf``            (reference ``matching.py:20`` predates NumPy 2)
   * stub ``transforms3d.affines.compose(T, R, Z) -> [[R diag(Z), T], [0, 1]]`` (``transforms.py:30``)
+  * ``numpy.lib.index_tricks`` -> ``numpy.lib._index_tricks_impl`` under NumPy 2 (``middlebury_utils.py:10``)
 OpenCV is absent here, so scenes are projected with a plain pinhole model instead of
 ``cv.projectPoints`` (no distortion, identical geometry).
 Produced under NumPy {np_version}; the reference pins 1.21.2 — differences are LAPACK rounding level.
@@ -38,6 +39,13 @@ def _install_shims():
     t3.affines = aff
     sys.modules["transforms3d"] = t3
     sys.modules["transforms3d.affines"] = aff
+    if "numpy.lib.index_tricks" not in sys.modules:
+        try:
+            import numpy.lib.index_tricks  # noqa: F401
+        except ImportError:   # NumPy 2 made the module private
+            from numpy.lib import _index_tricks_impl
+
+            sys.modules["numpy.lib.index_tricks"] = _index_tricks_impl
     sys.path.insert(0, REFERENCE)
 
 
@@ -666,10 +674,57 @@ def g14_ssd_integer():
     save("g14_ssd_integer", **out)
 
 
+def g15_host_modules():
+    """Known answers of the reference's host-only modules on the inputs of its own unit tests (lib/blur, lib/data_utils,
+    lib/feature_matching matching + util; lib/ransac is g10): what tests/test_reference_suite.py checks the drop-in `lib`
+    against.  The generic matcher is driven by score tables (a[i] x b[j] -> table[i, j])."""
+    import tempfile
+    from pathlib import Path
+    from lib.blur import gaussian
+    from lib.data_utils.middlebury_utils import load_camera_k_r_t
+    from lib.feature_matching import matching, util
+
+    out = {}
+    out["gauss_sizes"] = np.array([5, 3, 7])
+    out["gauss_sigmas"] = np.array([1.0, 0.5, 2.0])
+    for size, sigma in zip(out["gauss_sizes"], out["gauss_sigmas"]):
+        out[f"gauss_{size}"] = gaussian.create_gaussian_kernel(int(size), float(sigma))
+    out["gauss_invalid_sizes"] = np.array([4, 2])
+    for size in out["gauss_invalid_sizes"]:
+        try:
+            gaussian.create_gaussian_kernel(int(size), 1.0)
+            raise AssertionError(f"size {size} accepted")
+        except ValueError:
+            pass
+    par = open(os.path.join(REFERENCE, "lib", "data_utils", "tests", "test_par.txt"), "rb").read()
+    out["par_text"] = np.frombuffer(par, dtype=np.uint8)
+    with tempfile.TemporaryDirectory() as tmp:
+        path = os.path.join(tmp, "par.txt")
+        open(path, "wb").write(par)
+        for i in (1, 2):
+            K, T = load_camera_k_r_t(Path(path), i)
+            out[f"par_K_{i}"], out[f"par_T_{i}"] = np.asarray(K, dtype=np.float64), T.Tmat
+    tables = {"plain": (np.array([[10, 20, 30, 7], [30, 9, 20, 15], [20, 30, 8, 31]], dtype=np.float64), None, 0.8),
+              "ratio": (np.array([[10, 5, 20], [10, 6, 7]], dtype=np.float64), matching.ValidationStrategy.RATIO_TEST, 0.5)}
+    for name, (table, strategy, thr) in tables.items():
+        fa = [Feature(i + 1, i + 1) for i in range(table.shape[0])]
+        fb = [Feature(j + 10, j + 10) for j in range(table.shape[1])]
+        score = lambda a, b: table[fa.index(a), fb.index(b)]  # noqa: E731
+        ms = matching.match_brute_force(fa, fb, score, validation_strategies=strategy, ratio_test_threshold=thr)
+        out[f"match_{name}_table"], out[f"match_{name}_thr"] = table, np.array(thr)
+        out[f"match_{name}_out"] = np.array([[m.a_index, m.b_index, m.match_score] for m in ms], dtype=np.float64).reshape(-1, 3)
+    shape, ws = (100, 200), 5
+    xs, ys = np.meshgrid(np.array([0, 1, 2, 3, 100, 196, 197, 198, 199]), np.array([0, 1, 2, 3, 50, 96, 97, 98, 99]))
+    pts = np.column_stack([xs.ravel(), ys.ravel()]).astype(np.float64)
+    out["bounds_shape"], out["bounds_window"], out["bounds_xy"] = np.array(shape), np.array(ws), pts
+    out["bounds_inside"] = np.array([bool(util.is_within_bounds(Feature(x=int(x), y=int(y)), shape, ws)) for x, y in pts])
+    save("g15_host_modules", **out)
+
+
 if __name__ == "__main__":
     everything = [g1_eight_point_pipeline, g2_ransac_known_answer, g3_per_hypothesis, g4_sed_values, g5_cheirality,
                   g6_triangulate, g7_degenerate, g8_unit_vectors, g9_explicit_table, g10_line_ransac, g11_matching,
-                  g12_harris, g13_refit, g14_ssd_integer]
+                  g12_harris, g13_refit, g14_ssd_integer, g15_host_modules]
     wanted = sys.argv[1:]  # e.g. ``make_golden.py g13`` regenerates one fixture
     for fn in everything:
         if not wanted or fn.__name__.split("_")[0] in wanted:

@@ -597,6 +597,43 @@ def test_bench_roofline_is_a_valu_issue_bound(monkeypatch, tmp_path):
     assert other["frac"] is None and other["counters_stale"] is None
 
 
+def test_bench_dump_outputs(monkeypatch, tmp_path):
+    """bench.py --dump-outputs DIR: the last timed step's outcome as float32 / float64 .npy files (a winner, no winner, and a
+    match count above the limit, where the mask is a fixed seeded sample with its index); it needs a timed step."""
+    import importlib.util
+    import sys
+
+    from structure_from_motion_amd.distributed import ShardedOutcome
+
+    spec = importlib.util.spec_from_file_location("bench_module", os.path.join(REPO, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    n = 1000
+    mask = (np.arange(n) % 3).astype(np.uint8)
+    E = np.arange(9, dtype=np.float64).reshape(3, 3)
+    bench.dump_outputs(str(tmp_path / "a"), ShardedOutcome(17, 0.25, E, np.arange(8) * 5, mask, 0, -1), n)
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert set(got) == {"best_h", "error", "E", "sample", "flagged", "mask"}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert got["best_h"][0] == 17 and got["error"][0] == 0.25 and np.array_equal(got["E"], E)
+    assert np.array_equal(got["sample"], np.arange(8) * 5) and np.array_equal(got["flagged"], [0, -1])
+    assert np.array_equal(got["mask"], mask)
+    bench.dump_outputs(str(tmp_path / "b"), ShardedOutcome(-1, float("inf"), None, None, None, 3, 12), n)
+    assert np.isnan(np.load(tmp_path / "b" / "E.npy")).all() and np.load(tmp_path / "b" / "mask.npy").shape == (n,)
+    monkeypatch.setattr(bench, "DUMP_MASK_LIMIT", 100)
+    for d in ("c", "d"):
+        bench.dump_outputs(str(tmp_path / d), ShardedOutcome(17, 0.25, E, np.arange(8), mask, 0, -1), n)
+    index = np.load(tmp_path / "c" / "mask_index.npy")
+    assert index.shape == (100,) and np.all(np.diff(index) > 0)
+    assert np.array_equal(np.load(tmp_path / "c" / "mask.npy"), mask[index.astype(np.int64)])
+    assert np.array_equal(index, np.load(tmp_path / "d" / "mask_index.npy"))
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0", "--dump-outputs", str(tmp_path / "e")])
+    with pytest.raises(SystemExit):
+        bench.parse()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3", "--dump-outputs", str(tmp_path / "e")])
+    assert bench.parse().dump_outputs == str(tmp_path / "e")
+
+
 def test_sampler_default_is_the_exact_replay_at_every_size(monkeypatch):
     """The drop-in call keeps the reference's sample stream (cumulative random.shuffle, ransac.py:59-64) by default at
     every size — also at BASELINE configs[1] (5 000 x 10 000) and configs[2]; the size switch to the device sampler is
