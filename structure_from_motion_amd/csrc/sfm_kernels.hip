@@ -1027,6 +1027,13 @@ __global__ __launch_bounds__(kWave) void decompose_essential_kernel(const double
     }
 }
 
+// The fit launch of a fused large / batched pass where the matrix-pipe scoring kernel follows: every fit lane also writes its
+// hypothesis' operand rows and sample correction (MatrixPrep); step_blocks blocks behind the fit blocks write the point table.
+MatrixPrep matrix_prep(const sfmhost::ScorePlan& plan, int step_blocks) {
+    if (!plan.ws.matrix) return MatrixPrep{nullptr, 0, 0.0, 0.0, nullptr, nullptr, nullptr, 0};
+    return MatrixPrep{plan.partial, (int)plan.matrix.setup_blocks, plan.a_scale, plan.thr, plan.hyp_table, plan.fix, plan.table, step_blocks};
+}
+
 }  // namespace
 
 // ==================================================================================================
@@ -1126,27 +1133,21 @@ int sfm_ransac_pass_small(uint64_t seed, const uint64_t* seed_dev, int use_philo
         return fail(SFM_EINVAL, "sfm_ransac_pass_small: unknown aggregation");
     if (!corr || !S || !E || !flags || !cnt || !s1 || !s2 || !result || !workspace)
         return fail(SFM_EINVAL, "sfm_ransac_pass_small: null pointer");
-    if (!sfmhost::score_options_valid(options)) return fail(SFM_EINVAL, "sfm_ransac_pass_small: an option is out of range");
-    if (workspace_bytes < sfm_score_workspace_bytes_ex(n, h_count, 1, options))
-        return fail(SFM_EINVAL, "sfm_ransac_pass_small: workspace smaller than sfm_score_workspace_bytes_ex(n, h_count, 1, options)");
-    if ((reinterpret_cast<uintptr_t>(workspace) & 15u) != 0)
-        return fail(SFM_EINVAL, "sfm_ransac_pass_small: workspace must be 16-byte aligned");
+    sfmhost::ScorePlan plan;
+    const int rc_plan = sfmhost::plan_score("sfm_ransac_pass_small", n, h_count, 1, thr, options, workspace, workspace_bytes, &plan);
+    if (rc_plan != SFM_OK) return rc_plan;
     hipStream_t st = (hipStream_t)stream;
     // launch 1: eight-point fits (Philox samples drawn in the kernel, or the caller's table in S) + workspace preparation
-    const int prep_blocks = (int)((n + sfmws::kPrepPoints - 1) / sfmws::kPrepPoints);
     const unsigned fit_blocks = grid_for(h_count, kWave);
-    hipLaunchKernelGGL(fit_eight_point_kernel<false>, dim3(fit_blocks + (unsigned)prep_blocks, 1u), dim3(kWave), 0, st,
+    hipLaunchKernelGGL(fit_eight_point_kernel<false>, dim3(fit_blocks + (unsigned)plan.small.prep_blocks, 1u), dim3(kWave), 0, st,
                        (const Corr*)corr, n, S, h_count, E, flags, (double*)nullptr, (double*)nullptr,
                        PhiloxSource{seed_dev, seed, 0, h_begin, use_philox ? 1 : 0},
-                       SmallPrep{static_cast<unsigned char*>(workspace), sfmhost::small_pass_a_scale(thr), prep_blocks,
-                                 sfmhost::small_pass_order(static_cast<unsigned char*>(workspace), n, h_count)},
+                       SmallPrep{plan.workspace, plan.small.a_scale, plan.small.prep_blocks, plan.small.order},
                        MatrixPrep{nullptr, 0, 0.0, 0.0, nullptr, nullptr, nullptr, 0});
     const int rc = check_launch("fit_eight_point_kernel (fused small pass)");
     if (rc != SFM_OK) return rc;
     // launch 2: SED scoring
-    const int rc2 = sfmhost::launch_small_score(sfmhost::SmallPass{corr, n, E, S, flags, h_count, thr, min_extra, aggregation,
-                                                                   h_offset, cnt, s1, s2, result, mask,
-                                                                   static_cast<unsigned char*>(workspace), st, options});
+    const int rc2 = sfmhost::launch_small_score(plan, sfmhost::ScoreArrays{corr, E, S, cnt, s1, s2, st});
     if (rc2 != SFM_OK) return rc2;
     // launch 3: selection spread over up to 32 blocks x 256 threads x 4 hypotheses, folded by the block that arrives last
     // (a single block needs 14 us at 10 000 and 35 us at 30 000 hypotheses), and — behind them in the same launch — the
@@ -1159,7 +1160,7 @@ int sfm_ransac_pass_small(uint64_t seed, const uint64_t* seed_dev, int use_philo
     }
     const int select_blocks = (int)((h_count + 1023) / 1024);
     const int mask_blocks = mask != nullptr ? (int)((n + 255) / 256) : 0;
-    unsigned char* state = static_cast<unsigned char*>(workspace) + sfmws::ws_points_offset(1) + 16 * n;
+    unsigned char* state = plan.workspace + sfmws::ws_points_offset(1) + 16 * n;
     hipLaunchKernelGGL(select_sharded_kernel, dim3((unsigned)(select_blocks + mask_blocks)), dim3(256), 0, st,
                        (const int32_t*)cnt, (const double*)s1, (const double*)s2, (const int32_t*)flags, h_count, h_offset,
                        min_extra, aggregation, state, result, select_blocks, (const Corr*)corr, n, (const double*)E,
@@ -1179,60 +1180,50 @@ int sfm_ransac_pass_large(uint64_t seed, const uint64_t* seed_dev, int use_philo
         return fail(SFM_EINVAL, "sfm_ransac_pass_large: unknown aggregation");
     if (!corr || !S || !E || !flags || !cnt || !s1 || !s2 || !result || !workspace)
         return fail(SFM_EINVAL, "sfm_ransac_pass_large: null pointer");
-    if (!sfmhost::score_options_valid(options)) return fail(SFM_EINVAL, "sfm_ransac_pass_large: an option is out of range");
-    if (workspace_bytes < sfm_score_workspace_bytes_ex(n, h_count, 1, options))
-        return fail(SFM_EINVAL, "sfm_ransac_pass_large: workspace smaller than sfm_score_workspace_bytes_ex(n, h_count, 1, options)");
-    if ((reinterpret_cast<uintptr_t>(workspace) & 15u) != 0)
-        return fail(SFM_EINVAL, "sfm_ransac_pass_large: workspace must be 16-byte aligned");
-    SFM_REQUIRE_GRID("sfm_ransac_pass_large", h_count, kWave, kWave, 1);
-    SFM_REQUIRE_GRID("sfm_ransac_pass_large (mask)", n, 256, 256);
-    hipStream_t st = (hipStream_t)stream;
-    unsigned char* ws = static_cast<unsigned char*>(workspace);
-    unsigned char* state = ws + sfmws::ws_tail_offset(n, h_count, 1);   // the unused head of the range-split region
-    const bool state_fits = 4 * sfmws::split_padded(h_count) >= sfmws::kFusedPartialOffset + kLargeSelectBlocks * (int64_t)sizeof(PartialSelect);
-    sfmhost::LargePass pass{corr, n, E, S, h_count, thr, cnt, s1, s2, ws, workspace_bytes,
-                            state_fits ? reinterpret_cast<unsigned*>(state) : nullptr, st, options};
-    // launch 1 (where the matrix-pipe scoring kernel will run): partial maxima of the points + every zeroing the pass needs
-    sfmhost::MatrixTables tables;
-    int rc = sfmhost::launch_large_setup(pass, &tables);
+    sfmhost::ScorePlan plan;
+    int rc = sfmhost::plan_score("sfm_ransac_pass_large", n, h_count, 1, thr, options, workspace, workspace_bytes, &plan);
     if (rc != SFM_OK) return rc;
-    // launch 2: the eight-point fits (Philox samples drawn in the kernel, or the caller's table in S); with the matrix-pipe
-    // kernel ahead, every fit lane also writes its hypothesis' operand rows and sample correction, and blocks behind the fit
-    // blocks the point operand table (MatrixPrep)
-    const MatrixPrep prep = tables.matrix ? MatrixPrep{tables.partial, tables.partials, tables.a_scale, thr, tables.hyp_table, tables.fix,
-                                                       tables.table, tables.step_blocks}
-                                          : MatrixPrep{nullptr, 0, 0.0, 0.0, nullptr, nullptr, nullptr, 0};
-    if (!sfmhost::grid_fits((int64_t)grid_for(h_count, kWave) + prep.step_blocks, 1, kWave))
-        return fail(SFM_EINVAL, "sfm_ransac_pass_large: size exceeds what one launch covers");
-    if (tables.matrix)
-        hipLaunchKernelGGL((fit_eight_point_kernel<false, true>), dim3(grid_for(h_count, kWave) + (unsigned)prep.step_blocks, 1u), dim3(kWave),
-                           0, st, (const Corr*)corr, n, S, h_count, E, flags, (double*)nullptr, (double*)nullptr,
-                           PhiloxSource{seed_dev, seed, 0, h_begin, use_philox ? 1 : 0}, SmallPrep{nullptr, 0.0, 0, nullptr}, prep);
+    // with the matrix-pipe kernel ahead, blocks behind the fit blocks write the point operand table, four steps each
+    const int step_blocks = plan.ws.matrix ? plan.matrix.table_blocks : 0;
+    SFM_REQUIRE_GRID("sfm_ransac_pass_large", (int64_t)grid_for(h_count, kWave) + step_blocks, 1, kWave);
+    SFM_REQUIRE_GRID("sfm_ransac_pass_large (mask)", n, 256, 256);
+    unsigned char* state = plan.workspace + sfmws::ws_tail_offset(n, h_count, 1);   // the unused head of the range-split region
+    const bool state_fits = 4 * sfmws::split_padded(h_count) >= sfmws::kFusedPartialOffset + kLargeSelectBlocks * (int64_t)sizeof(PartialSelect);
+    unsigned* select_state = state_fits ? reinterpret_cast<unsigned*>(state) : nullptr;
+    hipStream_t st = (hipStream_t)stream;
+    const sfmhost::ScoreArrays io{corr, E, S, cnt, s1, s2, st};
+    // launch 1 (where the matrix-pipe scoring kernel will run): partial maxima of the points + every zeroing the pass needs
+    rc = sfmhost::launch_large_setup(plan, io, select_state);
+    if (rc != SFM_OK) return rc;
+    // launch 2: the eight-point fits (Philox samples drawn in the kernel, or the caller's table in S), with the matrix-pipe
+    // kernel's operand tables (MatrixPrep)
+    const PhiloxSource source{seed_dev, seed, 0, h_begin, use_philox ? 1 : 0};
+    const dim3 fit_grid(grid_for(h_count, kWave) + (unsigned)step_blocks, 1u);
+    if (plan.ws.matrix)
+        hipLaunchKernelGGL((fit_eight_point_kernel<false, true>), fit_grid, dim3(kWave), 0, st, (const Corr*)corr, n, S, h_count, E, flags,
+                           (double*)nullptr, (double*)nullptr, source, SmallPrep{nullptr, 0.0, 0, nullptr}, matrix_prep(plan, step_blocks));
     else
-        hipLaunchKernelGGL((fit_eight_point_kernel<false, false>), dim3(grid_for(h_count, kWave), 1u), dim3(kWave), 0, st, (const Corr*)corr,
-                           n, S, h_count, E, flags, (double*)nullptr, (double*)nullptr,
-                           PhiloxSource{seed_dev, seed, 0, h_begin, use_philox ? 1 : 0}, SmallPrep{nullptr, 0.0, 0, nullptr}, prep);
+        hipLaunchKernelGGL((fit_eight_point_kernel<false, false>), fit_grid, dim3(kWave), 0, st, (const Corr*)corr, n, S, h_count, E, flags,
+                           (double*)nullptr, (double*)nullptr, source, SmallPrep{nullptr, 0.0, 0, nullptr}, matrix_prep(plan, 0));
     rc = check_launch("fit_eight_point_kernel (fused large pass)");
     if (rc != SFM_OK) return rc;
-    pass.tables_ready = tables.matrix;
     // then sfm_score_sed's launches — cost pre-pass, class count, scan + scatter, the scoring kernel (other sizes: that call's
-    // own preparation first) — with the ranges' partials left unfolded
-    sfmhost::LargeScore folded_later{1, nullptr, nullptr};
-    // (without room for the selection state the scoring call folds its ranges itself — folded_later = NULL —: the separate
-    // selection below reads cnt / s1 / s2.  Round 4 deferred the fold in that case too, and selected from unfolded partials.)
-    rc = sfmhost::launch_large_score(pass, state_fits ? &folded_later : nullptr);
+    // own preparation first) — with the ranges' partials left to the selection launch.  (Without room for the selection state
+    // the scoring launches fold their ranges themselves: the separate selection below reads cnt / s1 / s2.  Round 4 deferred
+    // the fold in that case too, and selected from unfolded partials.)
+    rc = sfmhost::launch_large_score(plan, io, select_state, /*fold_in_selection=*/state_fits);
     if (rc != SFM_OK) return rc;
     if (!state_fits) {   // a few hundred hypotheses: the separate selection and mask launches
         rc = sfm_select_best(cnt, s1, s2, flags, h_count, 1, min_extra, aggregation, h_offset, result, stream);
         if (rc != SFM_OK || mask == nullptr) return rc;
         return sfm_inlier_mask(corr, n, E, S, h_count, 1, result, thr, mask, stream);
     }
-    // launch 8: fold of the ranges + selection over up to 256 blocks + (behind them) the blocks that write the winner's mask
+    // last launch: fold of the ranges + selection over up to 256 blocks + (behind them) the blocks that write the winner's mask
     const int select_blocks = (int)std::min<int64_t>(kLargeSelectBlocks, (h_count + 511) / 512);
     const int mask_blocks = mask != nullptr ? (int)((n + 255) / 256) : 0;
     hipLaunchKernelGGL(select_large_kernel, dim3((unsigned)(select_blocks + mask_blocks)), dim3(256), 0, st, cnt, s1, s2,
                        (const int32_t*)flags, h_count, h_offset, min_extra, aggregation, state, result, select_blocks,
-                       folded_later.units, (const unsigned char*)folded_later.split, folded_later.fix, (const Corr*)corr, n,
+                       plan.deferred_units(), (const unsigned char*)plan.split, (const unsigned char*)plan.fix, (const Corr*)corr, n,
                        (const double*)E, (const int32_t*)S, thr, mask);
     return check_launch("select_large_kernel");
 }
@@ -1249,42 +1240,34 @@ int sfm_ransac_pass_batch(uint64_t seed, const uint64_t* seed_dev, uint64_t seed
     if (batch == 0) return SFM_OK;
     if (!corr || !S || !E || !flags || !cnt || !s1 || !s2 || !result || !workspace)
         return fail(SFM_EINVAL, "sfm_ransac_pass_batch: null pointer");
-    if (!sfmhost::score_options_valid(options)) return fail(SFM_EINVAL, "sfm_ransac_pass_batch: an option is out of range");
-    if (workspace_bytes < sfm_score_workspace_bytes_ex(n, h_count, batch, options))
-        return fail(SFM_EINVAL, "sfm_ransac_pass_batch: workspace smaller than sfm_score_workspace_bytes_ex(n, h_count, batch, options)");
-    if ((reinterpret_cast<uintptr_t>(workspace) & 15u) != 0)
-        return fail(SFM_EINVAL, "sfm_ransac_pass_batch: workspace must be 16-byte aligned");
+    sfmhost::ScorePlan plan;
+    int rc = sfmhost::plan_score("sfm_ransac_pass_batch", n, h_count, batch, thr, options, workspace, workspace_bytes, &plan);
+    if (rc != SFM_OK) return rc;
     SFM_REQUIRE_GRID("sfm_ransac_pass_batch", h_count, kWave, kWave, batch);
     hipStream_t st = (hipStream_t)stream;
-    unsigned char* ws = static_cast<unsigned char*>(workspace);
-    sfmhost::LargePass pass{corr, n, E, S, h_count, thr, cnt, s1, s2, ws, workspace_bytes, nullptr, st, options, batch};
+    const sfmhost::ScoreArrays io{corr, E, S, cnt, s1, s2, st};
     // launches 1-2 (where the matrix-pipe scoring kernel will run): partial maxima + zeroing, the pairs' point operand tables
-    sfmhost::MatrixTables tables;
-    int rc = sfmhost::launch_large_setup(pass, &tables);
+    rc = sfmhost::launch_large_setup(plan, io, nullptr);
     if (rc != SFM_OK) return rc;
     // launch 3: the eight-point fits; with the matrix-pipe kernel ahead every lane also writes its hypothesis' operand rows and
     // sample correction
     const PhiloxSource source{seed_dev, seed, seed_stride, h_begin, use_philox ? 1 : 0};
     const dim3 fit_grid(grid_for(h_count, kWave), (unsigned)batch);
-    if (tables.matrix)
+    if (plan.ws.matrix)
         hipLaunchKernelGGL((fit_eight_point_kernel<false, true>), fit_grid, dim3(kWave), 0, st, (const Corr*)corr, n, S, h_count, E, flags,
-                           (double*)nullptr, (double*)nullptr, source, SmallPrep{nullptr, 0.0, 0, nullptr},
-                           MatrixPrep{tables.partial, tables.partials, tables.a_scale, thr, tables.hyp_table, tables.fix, nullptr, 0});
+                           (double*)nullptr, (double*)nullptr, source, SmallPrep{nullptr, 0.0, 0, nullptr}, matrix_prep(plan, 0));
     else
         hipLaunchKernelGGL((fit_eight_point_kernel<false, false>), fit_grid, dim3(kWave), 0, st, (const Corr*)corr, n, S, h_count, E, flags,
-                           (double*)nullptr, (double*)nullptr, source, SmallPrep{nullptr, 0.0, 0, nullptr},
-                           MatrixPrep{nullptr, 0, 0.0, 0.0, nullptr, nullptr, nullptr, 0});
+                           (double*)nullptr, (double*)nullptr, source, SmallPrep{nullptr, 0.0, 0, nullptr}, matrix_prep(plan, 0));
     rc = check_launch("fit_eight_point_kernel (batched pass)");
     if (rc != SFM_OK) return rc;
-    pass.tables_ready = tables.matrix;
     // sfm_score_sed's launches (matrix-pipe kernel: cost pre-pass, class count, scan + scatter, scoring — the ranges left unfolded)
-    sfmhost::LargeScore folded_later{1, nullptr, nullptr};
-    rc = sfmhost::launch_large_score(pass, &folded_later);
+    rc = sfmhost::launch_large_score(plan, io, nullptr, /*fold_in_selection=*/true);
     if (rc != SFM_OK) return rc;
     // last launch: fold of the ranges + selection + mask, one block per pair
     hipLaunchKernelGGL(select_fold_mask_batch_kernel, dim3((unsigned)batch), dim3(kSelectBlock), 0, st, cnt, s1, s2, (const int32_t*)flags,
-                       h_count, min_extra, aggregation, result, folded_later.units, (const unsigned char*)folded_later.split,
-                       folded_later.fix, (const Corr*)corr, n, (const double*)E, (const int32_t*)S, thr, mask);
+                       h_count, min_extra, aggregation, result, plan.deferred_units(), (const unsigned char*)plan.split,
+                       (const unsigned char*)plan.fix, (const Corr*)corr, n, (const double*)E, (const int32_t*)S, thr, mask);
     return check_launch("select_fold_mask_batch_kernel");
 }
 

@@ -12,9 +12,6 @@
 #include <utility>
 
 #define SFM_DEVICE __device__ __forceinline__
-#ifndef SFM_SED_EXACT_DIVISION
-#define SFM_SED_EXACT_DIVISION 0
-#endif
 
 namespace sfm {
 
@@ -64,10 +61,6 @@ SFM_DEVICE bool sed_inlier(const double e[9], double xa, double ya, double xb, d
     const double da = la0 * la0 + la1 * la1;
     const double db = lb0 * lb0 + lb1 * lb1;
     const double r2 = r * r;
-#if SFM_SED_EXACT_DIVISION   // (A/B builds: tools/r04/fastdiv.sh)
-    sed_out = (1.0 / da + 1.0 / db) * r2;
-    return sed_out <= gate.thr;
-#endif
     const double q = da * db;
     double y = __builtin_amdgcn_rcp(q);
     const double err = fma(-q, y, 1.0);

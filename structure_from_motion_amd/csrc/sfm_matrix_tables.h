@@ -49,10 +49,6 @@ SFM_DEVICE float bf_up(float x) {   // smallest bf16 >= x for x >= 0 (NaN stays 
 SFM_DEVICE void split2(double x, float& hi, float& mid) {
     hi = (float)(_Float16)(float)x;
     mid = (float)(_Float16)(float)(x - (double)hi);
-#if SFM_MATRIX_ABLATE & 16   // measurement build: no fp16 subnormals among the operands (are they slow on the matrix pipe?)
-    if (fabsf(mid) < 6.2e-5f) mid = 0.0f;
-    if (fabsf(hi) < 6.2e-5f) hi = 0.0f;
-#endif
     if (!(fabs(x) < 1e300)) mid = hi;   // inf / NaN: keep the poison in both parts (inf - inf would be NaN anyway)
 }
 // power of two s with s * x in [2^(top-1), 2^top) (x > 0 finite), else 1

@@ -58,9 +58,6 @@ using sfmhost::grid_for;
 using sfmhost::grid_stride;
 
 constexpr int kHypPerWave = 4;
-#ifndef SFM_SCORE_PACKED
-#define SFM_SCORE_PACKED 0   // tier 1 of two hypotheses per instruction in packed fp32 (experiment: profiles/r03/README.md)
-#endif
 #ifndef SFM_WAVE_STAMPS
 #define SFM_WAVE_STAMPS 0   // diagnostic build (tools/wave_timeline.py): per-wave start / end stamps of the filtered kernel
 #endif
@@ -309,77 +306,6 @@ SFM_DEVICE unsigned long long reject_mask_one_sided(const FilterConsts& f, float
     const float r = fmaf(lb0, xa_scaled, fmaf(lb1, ya_scaled, lb2));
     const float dB = fmaf(lb0, lb0, fmaf(lb1, lb1, f.cb));
     return __builtin_amdgcn_ballot_w64(r * r > dB);
-}
-
-// The same test for TWO hypotheses at once in packed fp32 (v_pk_fma_f32: both halves of a 64-bit register pair per
-// instruction): the halves carry hypothesis A and hypothesis B, the point's coordinates are broadcast to both (op_sel
-// picks the dword of the (xa', ya') / (xb, yb) register pair) and the multipliers / addends are packed (A, B) pairs — the
-// four multipliers in SGPR pairs as before.  10 v_pk_fma_f32 + 1 v_pk_mul_f32 + 2 compares per point for two hypotheses
-// instead of 24 instructions; every half is the IEEE fma of the plain form, so the masks are bit for bit the same.
-typedef float float2v __attribute__((ext_vector_type(2)));
-struct PackedConsts {
-    float2v e0, e1, e3, e4;          // multipliers (SGPR pairs)
-    float2v e2, e5, e6, e7, e8, cb;  // the other multipliers and the addends (wave-uniform VGPR pairs)
-};
-SFM_DEVICE float2v sgpr_pair(float a, float b) { return float2v{uniform(a), uniform(b)}; }
-SFM_DEVICE PackedConsts pack_consts(const FilterConsts& a, const FilterConsts& b) {
-    PackedConsts p;
-    p.e0 = sgpr_pair(a.e[0], b.e[0]);
-    p.e1 = sgpr_pair(a.e[1], b.e[1]);
-    p.e3 = sgpr_pair(a.e[3], b.e[3]);
-    p.e4 = sgpr_pair(a.e[4], b.e[4]);
-    p.e2 = float2v{a.e[2], b.e[2]};
-    p.e5 = float2v{a.e[5], b.e[5]};
-    p.e6 = float2v{a.e[6], b.e[6]};
-    p.e7 = float2v{a.e[7], b.e[7]};
-    p.e8 = float2v{a.e[8], b.e[8]};
-    p.cb = float2v{a.cb, b.cb};
-    return p;
-}
-// d = broadcast(coord[SEL]) * mult + add, mult in an SGPR pair / in a VGPR pair
-template <int SEL>
-SFM_DEVICE float2v pk_fma_coord_s(float2v coord, float2v mult, float2v add) {
-    float2v d;
-    if (SEL == 0) asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[0,1,1]" : "=v"(d) : "v"(coord), "s"(mult), "v"(add));
-    else asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,1,1]" : "=v"(d) : "v"(coord), "s"(mult), "v"(add));
-    return d;
-}
-template <int SEL>
-SFM_DEVICE float2v pk_fma_coord_v(float2v coord, float2v mult, float2v add) {
-    float2v d;
-    if (SEL == 0) asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[0,1,1]" : "=v"(d) : "v"(coord), "v"(mult), "v"(add));
-    else asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,1,1]" : "=v"(d) : "v"(coord), "v"(mult), "v"(add));
-    return d;
-}
-// d = value * broadcast(coord[SEL]) + add
-template <int SEL>
-SFM_DEVICE float2v pk_fma_by_coord(float2v value, float2v coord, float2v add) {
-    float2v d;
-    if (SEL == 0) asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[1,0,1]" : "=v"(d) : "v"(value), "v"(coord), "v"(add));
-    else asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[1,1,1]" : "=v"(d) : "v"(value), "v"(coord), "v"(add));
-    return d;
-}
-SFM_DEVICE float2v pk_fma(float2v a, float2v b, float2v c) {
-    float2v d;
-    asm("v_pk_fma_f32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
-    return d;
-}
-SFM_DEVICE float2v pk_mul(float2v a, float2v b) {
-    float2v d;
-    asm("v_pk_mul_f32 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b));
-    return d;
-}
-// lane masks of the pairs hypothesis A / hypothesis B reject; a_xy = (xa', ya'), b_xy = (xb, yb) of the lane's point
-SFM_DEVICE void reject_masks_packed(const PackedConsts& f, float2v a_xy, float2v b_xy, unsigned long long& reject_a,
-                                    unsigned long long& reject_b) {
-    const float2v lb0 = pk_fma_coord_s<0>(b_xy, f.e0, pk_fma_coord_s<1>(b_xy, f.e3, f.e6));
-    const float2v lb1 = pk_fma_coord_s<0>(b_xy, f.e1, pk_fma_coord_s<1>(b_xy, f.e4, f.e7));
-    const float2v lb2 = pk_fma_coord_v<0>(b_xy, f.e2, pk_fma_coord_v<1>(b_xy, f.e5, f.e8));
-    const float2v r = pk_fma_by_coord<0>(lb0, a_xy, pk_fma_by_coord<1>(lb1, a_xy, lb2));
-    const float2v dB = pk_fma(lb0, lb0, pk_fma(lb1, lb1, f.cb));
-    const float2v rr = pk_mul(r, r);
-    reject_a = __builtin_amdgcn_ballot_w64(rr.x > dB.x);
-    reject_b = __builtin_amdgcn_ballot_w64(rr.y > dB.y);
 }
 
 // Turn the constants of the two-sided test into those of reject_mask_one_sided: fold delta into cb (see there), and
@@ -690,11 +616,6 @@ __global__ __launch_bounds__(256, 5) void score_sed_filtered_kernel(
         f[k].e[3] = uniform(f[k].e[3]);
         f[k].e[4] = uniform(f[k].e[4]);
     }
-#if SFM_SCORE_PACKED
-    PackedConsts fp[(HPW + 1) / 2];   // the steady-state loop tests hypotheses two at a time (reject_masks_packed)
-#pragma unroll
-    for (int k = 0; k + 1 < HPW; k += 2) fp[k / 2] = pack_consts(f[k], f[k + 1]);
-#endif
 
     int c[HPW];
     double a1[HPW], a2[HPW];
@@ -765,31 +686,9 @@ __global__ __launch_bounds__(256, 5) void score_sed_filtered_kernel(
     // Steady state: two full 64-point chunks per step (no validity masks), so the scalar bookkeeping and
     // the drain test are paid once per 128 evaluations of a hypothesis.
     auto process_pair = [&](const float4 p0, const float4 p1, int i0, int i1) __attribute__((always_inline)) {
-#if SFM_SCORE_PACKED
-        unsigned long long packed_m0[HPW], packed_m1[HPW];
-        if (ONE_SIDED && HPW % 2 == 0) {
-            const float2v a0 = {p0.x, p0.y}, b0 = {p0.z, p0.w}, a1 = {p1.x, p1.y}, b1 = {p1.z, p1.w};
-#pragma unroll
-            for (int k = 0; k + 1 < HPW; k += 2) {
-                unsigned long long ra, rb;
-                reject_masks_packed(fp[k / 2], a0, b0, ra, rb);
-                packed_m0[k] = ~ra;
-                packed_m0[k + 1] = ~rb;
-                reject_masks_packed(fp[k / 2], a1, b1, ra, rb);
-                packed_m1[k] = ~ra;
-                packed_m1[k + 1] = ~rb;
-            }
-        }
-#endif
 #pragma unroll
         for (int k = 0; k < HPW; ++k) {
             unsigned long long m0, m1;  // survivors of the two chunks
-#if SFM_SCORE_PACKED
-            if (ONE_SIDED && HPW % 2 == 0) {
-                m0 = packed_m0[k];
-                m1 = packed_m1[k];
-            } else
-#endif
             if (ONE_SIDED) {
                 m0 = ~reject_mask_one_sided(f[k], p0.x, p0.y, p0.z, p0.w);
                 m1 = ~reject_mask_one_sided(f[k], p1.x, p1.y, p1.z, p1.w);
@@ -985,80 +884,117 @@ __global__ __launch_bounds__(256, 5) void score_sed_filtered_kernel(
 
 // (The HIP events a benchmark brackets exactly the scoring kernel with travel in the call's sfm_score_options — timing_before /
 // timing_after — since ABI 11; until then they were thread-local state set by sfm_score_set_timing_events.)
-struct FilteredLaunch {
-    const Corr* corr;
-    unsigned char* ws;
-    int n;
-    const double* E;
-    const int32_t* S;
-    int h_count;
-    double thr;
-    bool use_order;
-    int32_t* cnt;
-    double* s1;
-    double* s2;
-    int32_t* buckets;
-    int32_t* order;
-    int64_t batch;
-    hipStream_t st;
-    bool one_sided;
-    double a_scale;
-    int units, chunks_per_unit;   // range split (single pair): 1, 0 = off
-    bool xcd_map = true;          // batches: all blocks of a pair on one XCD (options.xcd_map)
-    bool persistent = true;       // matrix-pipe kernel, single pair: persistent waves (options.persistent)
-    unsigned* select_state = nullptr;          // fused pass: state words of its selection launch, zeroed with everything else
-    sfmhost::LargeScore* deferred = nullptr;   // fused pass: leave the ranges' partials to the selection launch, report them here
-    hipEvent_t event_before = nullptr, event_after = nullptr;   // options.timing_before / _after: recorded around the scoring kernel
-    bool tables_ready = false;    // fused pass: maxima, zeroing and both operand tables of the matrix-pipe kernel are there already
-    WsPlan plan = WsPlan{false, 1, false};   // what the workspace behind the scoring order was sized for
-};
-
 template <int HPW>
-int launch_filtered(const FilteredLaunch& a) {
-    const int64_t waves = (a.h_count + HPW - 1) / HPW;
-    SFM_REQUIRE_GRID("sfm_score_sed", waves, 256 / kWave, 256, a.batch);
-    const dim3 grid(grid_for(waves, 256 / kWave), (unsigned)a.batch);
+int launch_filtered(const sfmhost::ScorePlan& p, const sfmhost::ScoreArrays& io) {
+    const bool one_sided = p.valu.one_sided;
+    const dim3 grid(p.valu.blocks, (unsigned)p.batch);
     const int32_t* order_arg = nullptr;
-    if (a.use_order) {
+    if (p.use_order) {
         // `cnt` doubles as the estimate buffer: it is rewritten by the scoring kernel afterwards
-        if (a.one_sided)
-            hipLaunchKernelGGL((score_estimate_kernel<HPW, true>), grid, dim3(256), 0, a.st, a.ws, a.n, a.E, a.h_count,
-                               a.thr, a.a_scale, a.cnt);
+        if (one_sided)
+            hipLaunchKernelGGL((score_estimate_kernel<HPW, true>), grid, dim3(256), 0, io.stream, p.workspace, (int)p.n, io.E,
+                               (int)p.h_count, p.thr, p.a_scale, io.cnt);
         else
-            hipLaunchKernelGGL((score_estimate_kernel<HPW, false>), grid, dim3(256), 0, a.st, a.ws, a.n, a.E, a.h_count,
-                               a.thr, a.a_scale, a.cnt);
-        SFM_REQUIRE_GRID("sfm_score_sed (ordering pre-pass)", a.h_count, 256, 256, a.batch);
-        const dim3 per_hyp(grid_for(a.h_count, 256), (unsigned)a.batch);
-        hipLaunchKernelGGL(score_class_count_kernel, per_hyp, dim3(256), 0, a.st, a.cnt, a.h_count, a.buckets);
-        hipLaunchKernelGGL(score_class_scan_kernel, dim3((unsigned)a.batch), dim3(256), 0, a.st, a.buckets, a.batch);
-        hipLaunchKernelGGL(score_class_scatter_kernel, per_hyp, dim3(256), 0, a.st, a.cnt, a.h_count, a.buckets, a.order);
+            hipLaunchKernelGGL((score_estimate_kernel<HPW, false>), grid, dim3(256), 0, io.stream, p.workspace, (int)p.n, io.E,
+                               (int)p.h_count, p.thr, p.a_scale, io.cnt);
+        const dim3 per_hyp(grid_for(p.h_count, 256), (unsigned)p.batch);
+        hipLaunchKernelGGL(score_class_count_kernel, per_hyp, dim3(256), 0, io.stream, io.cnt, (int)p.h_count, p.buckets);
+        hipLaunchKernelGGL(score_class_scan_kernel, dim3((unsigned)p.batch), dim3(256), 0, io.stream, p.buckets, p.batch);
+        hipLaunchKernelGGL(score_class_scatter_kernel, per_hyp, dim3(256), 0, io.stream, io.cnt, (int)p.h_count, p.buckets, p.order);
         const int rc = check_launch("score order kernels");
         if (rc != SFM_OK) return rc;
-        order_arg = a.order;
+        order_arg = p.order;
     }
-    const int64_t flat_blocks = (int64_t)grid.x * ((a.batch + 7) / 8 * 8);
-    const bool remap = a.xcd_map && a.batch > 1 && flat_blocks <= 0x7FFFFFFF;  // see the kernel's block -> (pair, block) map
-    const int blocks_per_pair = remap ? (int)grid.x : 0;
-    dim3 flat = remap ? dim3((unsigned)flat_blocks) : grid;
-    unsigned char* split = nullptr;
-    if (a.units > 1) {   // single pair: `units` consecutive blocks per group of waves; their partials are folded behind the launch
-        flat = dim3(grid.x * (unsigned)a.units);   // (sfm_score_sed checked that this grid fits one launch)
-        split = a.ws + ws_tail_offset(a.n, a.h_count, 1);
-    }
-    if (a.event_before) (void)hipEventRecord(a.event_before, a.st);
-    if (a.one_sided)
-        hipLaunchKernelGGL((score_sed_filtered_kernel<HPW, true>), flat, dim3(256), 0, a.st, a.corr, a.ws, a.n, a.E, a.S,
-                           a.h_count, a.thr, a.a_scale, order_arg, a.cnt, a.s1, a.s2, (int)a.batch, blocks_per_pair, 0, 0,
-                           a.units, a.chunks_per_unit, split);
+    if (p.opt.timing_before) (void)hipEventRecord((hipEvent_t)p.opt.timing_before, io.stream);
+    if (one_sided)
+        hipLaunchKernelGGL((score_sed_filtered_kernel<HPW, true>), p.valu.scoring_grid, dim3(256), 0, io.stream, (const Corr*)io.corr,
+                           p.workspace, (int)p.n, io.E, io.S, (int)p.h_count, p.thr, p.a_scale, order_arg, io.cnt, io.s1, io.s2,
+                           (int)p.batch, p.valu.blocks_per_pair, 0, 0, p.ws.units, p.per_unit, p.split);
     else
-        hipLaunchKernelGGL((score_sed_filtered_kernel<HPW, false>), flat, dim3(256), 0, a.st, a.corr, a.ws, a.n, a.E, a.S,
-                           a.h_count, a.thr, a.a_scale, order_arg, a.cnt, a.s1, a.s2, (int)a.batch, blocks_per_pair, 0, 0,
-                           a.units, a.chunks_per_unit, split);
-    if (a.event_after) (void)hipEventRecord(a.event_after, a.st);
-    if (a.units > 1)
-        hipLaunchKernelGGL(matrixscore::matrix_fold_kernel, dim3(grid_stride(a.h_count, 256, 1024), 1), dim3(256), 0, a.st, split,
-                           (const unsigned char*)nullptr, a.units, a.h_count, a.cnt, a.s1, a.s2);
+        hipLaunchKernelGGL((score_sed_filtered_kernel<HPW, false>), p.valu.scoring_grid, dim3(256), 0, io.stream, (const Corr*)io.corr,
+                           p.workspace, (int)p.n, io.E, io.S, (int)p.h_count, p.thr, p.a_scale, order_arg, io.cnt, io.s1, io.s2,
+                           (int)p.batch, p.valu.blocks_per_pair, 0, 0, p.ws.units, p.per_unit, p.split);
+    if (p.opt.timing_after) (void)hipEventRecord((hipEvent_t)p.opt.timing_after, io.stream);
+    if (p.ws.units > 1)   // (one pair) the ranges' partials, folded in range order
+        hipLaunchKernelGGL(matrixscore::matrix_fold_kernel, dim3(grid_stride(p.h_count, 256, 1024), 1), dim3(256), 0, io.stream, p.split,
+                           (const unsigned char*)nullptr, p.ws.units, (int)p.h_count, io.cnt, io.s1, io.s2);
     return check_launch("score_sed_filtered_kernel");
+}
+
+// The VALU filter's launches: workspace preparation, then launch_filtered.  select_state: 16 words a fused pass's selection launch
+// needs zeroed (NULL: none).
+int launch_valu(const sfmhost::ScorePlan& p, const sfmhost::ScoreArrays& io, unsigned* select_state) {
+    // Small point sets are prepared by one block per pair, which stores the maxima itself; the zeroing kernel is then
+    // only needed for the class counters of the ordering pre-pass (a small pass is a chain of ~4 us launches).
+    if (p.use_order || p.valu.prepare_blocks > 1)
+        hipLaunchKernelGGL(score_reset_kernel, dim3((unsigned)p.batch), dim3(256), 0, io.stream, p.workspace, p.buckets);
+    hipLaunchKernelGGL(score_prepare_kernel, dim3(p.valu.prepare_blocks, (unsigned)p.batch), dim3(256), 0, io.stream, (const Corr*)io.corr,
+                       p.n, p.a_scale, p.workspace);
+    const int rc = check_launch("score_prepare_kernel");
+    if (rc != SFM_OK) return rc;
+    if (select_state != nullptr)
+        hipLaunchKernelGGL(score_split_reset_kernel, dim3(1), dim3(256), 0, io.stream, reinterpret_cast<int32_t*>(select_state), (int64_t)16);
+    switch (p.valu.hpw) {
+        case 1: return launch_filtered<1>(p, io);
+        case 2: return launch_filtered<2>(p, io);
+        default: return launch_filtered<4>(p, io);
+    }
+}
+
+// First launch of the matrix-pipe kernel's chain: per-block partial maxima of the points and every zeroing the call needs
+// (select_state: a fused pass's selection state, or NULL).
+void launch_matrix_setup(const sfmhost::ScorePlan& p, const sfmhost::ScoreArrays& io, unsigned* select_state) {
+    hipLaunchKernelGGL(matrixscore::matrix_setup_kernel, dim3(p.matrix.setup_blocks, (unsigned)p.batch), dim3(256), 0, io.stream,
+                       (const Corr*)io.corr, (int)p.n, p.a_scale, p.partial, p.buckets, io.cnt, (int)p.h_count, select_state);
+}
+
+// Scoring launch with tier 1 on the matrix pipe (sfm_score_matrix.h), behind its setup and operand tables — which it launches
+// itself unless a fused pass has (tables_ready: launch_large_setup in front of the pass's fit launch, whose lanes wrote the
+// hypotheses' rows and sample corrections; the point table by blocks of the fit launch for one pair, by a points-only launch of
+// matrix_tables_kernel for a batch).  fold_in_selection: leave the ranges' partials to a fused pass's selection launch.
+int launch_matrix(const sfmhost::ScorePlan& p, const sfmhost::ScoreArrays& io, bool tables_ready, bool fold_in_selection) {
+    using namespace matrixscore;
+    static_assert(kBlocks * 2 * 16 == 96, "sfm_score_ws.h sizes the tables: 3 blocks");
+    const auto& m = p.matrix;
+    const unsigned pairs = (unsigned)p.batch;
+    if (!tables_ready) {
+        launch_matrix_setup(p, io, nullptr);
+        hipLaunchKernelGGL(matrix_tables_kernel, dim3((unsigned)m.table_blocks + grid_for(2 * p.h_count, 256), pairs), dim3(256), 0,
+                           io.stream, (const Corr*)io.corr, (int)p.n, p.a_scale, (const float4*)p.partial, (int)m.setup_blocks, p.table,
+                           m.table_blocks, io.E, (int)p.h_count, p.hyp_table, io.S, p.thr, p.fix);
+    }
+    const int32_t* order_arg = nullptr;
+    if (p.use_order) {
+        // cost pre-pass with this kernel's own tier 1 over the first steps (survivors per 1024 points, in sixteenths, into
+        // `cnt`, which the scoring launch rewrites), then the counting sort by class
+        // (the ranges of the pre-pass add into `cnt`: zeroed by matrix_setup_kernel)
+        hipLaunchKernelGGL((score_sed_matrix_kernel<true, 0, false>), dim3(m.prepass_blocks), dim3(256), 0, io.stream, (const Corr*)io.corr,
+                           (const uint4*)p.hyp_table, (const uint4*)p.table, (int)p.n, io.E, (int)p.h_count, p.thr, (const int32_t*)nullptr,
+                           io.cnt, io.s1, io.s2, m.prepass_units, m.prepass_steps, (unsigned char*)nullptr, (const unsigned char*)nullptr,
+                           (int)p.batch, m.prepass_blocks_per_pair, (int32_t*)nullptr, p.record, p.per_unit, p.ws.units,
+                           (const int32_t*)nullptr, 0);
+        const dim3 per_hyp(grid_for(p.h_count, 256), pairs);
+        hipLaunchKernelGGL(score_class_count_kernel, per_hyp, dim3(256), 0, io.stream, io.cnt, (int)p.h_count, p.buckets);
+        hipLaunchKernelGGL(score_class_scan_scatter_kernel, per_hyp, dim3(256), 0, io.stream, io.cnt, (int)p.h_count, p.buckets, p.order,
+                           m.wide_from_min, m.wide_from_max);
+        const int rc = check_launch("score order kernels");
+        if (rc != SFM_OK) return rc;
+        order_arg = p.order;
+    }
+    if (p.opt.timing_before) (void)hipEventRecord((hipEvent_t)p.opt.timing_before, io.stream);
+    // (the pops of a round that share one execution-mask region: sfm_score_matrix.h, matrix_item's MASK_GROUP)
+    const auto scoring_kernel = m.wide_waves ? score_sed_matrix_kernel<false, SFM_MATRIX_MASK_GROUP_WIDE, true>
+                                : p.batch > 1 ? score_sed_matrix_kernel<false, SFM_MATRIX_MASK_GROUP_BATCH, false>
+                                              : score_sed_matrix_kernel<false, SFM_MATRIX_MASK_GROUP_SINGLE, false>;
+    hipLaunchKernelGGL(scoring_kernel, dim3(m.scoring_blocks), dim3(256), 0, io.stream, (const Corr*)io.corr, (const uint4*)p.hyp_table,
+                       (const uint4*)p.table, (int)p.n, io.E, (int)p.h_count, p.thr, order_arg, io.cnt, io.s1, io.s2, p.ws.units, p.per_unit,
+                       p.split, (const unsigned char*)p.fix, (int)p.batch, m.blocks_per_pair, m.persistent ? p.buckets + kTicketWords : nullptr,
+                       p.record, 0, 0, m.wide_waves ? p.buckets + kWideFromWord : nullptr, m.wide_from_max);
+    if (p.opt.timing_after) (void)hipEventRecord((hipEvent_t)p.opt.timing_after, io.stream);
+    if (!fold_in_selection && p.ws.units > 1)
+        hipLaunchKernelGGL(matrix_fold_kernel, dim3(grid_stride(p.h_count, 256, 1024), pairs), dim3(256), 0, io.stream, p.split,
+                           (const unsigned char*)p.fix, p.ws.units, (int)p.h_count, io.cnt, io.s1, io.s2);
+    return check_launch("score_sed_matrix_kernel");
 }
 
 // Launch options (sfm_score_options, include/sfm_hip.h).  The library never reads the process environment: a call carries its
@@ -1068,15 +1004,24 @@ int launch_filtered(const FilteredLaunch& a) {
 constexpr sfm_score_options kBuiltinOptions = SFM_SCORE_OPTIONS_DEFAULT;
 std::atomic<const sfm_score_options*> g_default_options{&kBuiltinOptions};
 
-sfm_score_options resolve_options(const sfm_score_options* given) {
-    return given ? *given : *g_default_options.load(std::memory_order_acquire);
-}
 bool valid_options(const sfm_score_options& o) {
     return (o.kernel == SFM_SCORE_KERNEL_AUTO || o.kernel == SFM_SCORE_KERNEL_FILTERED || o.kernel == SFM_SCORE_KERNEL_MATRIX) &&
            (o.hyps_per_wave == 0 || o.hyps_per_wave == 1 || o.hyps_per_wave == 2 || o.hyps_per_wave == 4) && o.split >= -1 &&
            o.order >= -1 && o.order <= 1 && o.one_sided >= -1 && o.one_sided <= 1 && o.xcd_map >= -1 && o.xcd_map <= 1 &&
            o.block_sync >= -1 && o.persistent >= -1 && o.persistent <= 1;
 }
+
+// The options of one call, loaded ONCE: the argument, or a single load of the process-wide defaults.  false: a field is out of range.
+bool load_options(const sfm_score_options* given, sfm_score_options* out) {
+    *out = given ? *given : *g_default_options.load(std::memory_order_acquire);
+    return valid_options(*out);
+}
+
+int refuse(const char* fn, const char* what) {
+    snprintf(sfmhost::error_buffer(), sfmhost::kErrorBytes, "%s: %s", fn, what);
+    return SFM_EINVAL;
+}
+constexpr const char* kBeyondOneLaunch = "size exceeds what one launch covers (2^31-1 blocks, 2^32-1 threads in x; 65535 in y/z)";
 
 // The size rule between the two filtered kernels of sfm_score_sed (options.kernel forces the matrix-pipe kernel on where it
 // applies / off).
@@ -1103,17 +1048,14 @@ bool use_matrix_kernel(int64_t n, int64_t h_count, int64_t batch, const sfm_scor
     return matrix_fits && (matrix_env > 0 || (matrix_env < 0 && matrix_pays));
 }
 
-// What a scoring call with a workspace will launch for (n, h_count, batch) under `opt` — decided ONCE, before anything is
-// launched: sfm_score_sed_ex launches from it and sfm_score_workspace_bytes_ex sizes the workspace by it (ScorePlan::ws).
-struct ScorePlan {
-    WsPlan ws;          // matrix-pipe kernel or VALU filter; ranges of the points; recorded pre-pass
-    int hpw;            // VALU filter: hypotheses per wave
-    bool use_order;     // heaviest-first processing order (cost pre-pass + counting sort)
-    bool one_sided;     // VALU filter: one-sided test
-    double a_scale;     // factor the prepared a-side coordinates carry
-    int per_unit;       // VALU filter: 64-point chunks per range; matrix-pipe kernel: steps of 32 points per range
-};
-int plan_score(int64_t n, int64_t h_count, int64_t batch, double thr, const sfm_score_options& opt, ScorePlan* plan) {
+// recording pre-pass, single pair: ranges of the scoring launch one wave of the pre-pass scans (1, 2, 4 or 8 of the 8)
+constexpr int kRecordRangesPerWave = 2;
+
+// The launch rule of a scoring call with a workspace: everything of p->* below the options that does not depend on where the
+// workspace is.  Refuses (SFM_EINVAL) sizes whose launches would not fit one grid each.
+int plan_launches(const char* fn, sfmhost::ScorePlan* p) {
+    const int64_t n = p->n, h_count = p->h_count, batch = p->batch;
+    const sfm_score_options& opt = p->opt;
     // hypotheses per wave: 4 amortises the point loads best, but a launch with fewer waves than the chip holds
     // (5120) leaves SIMDs idle — then fewer hypotheses per wave = more waves wins (options.hyps_per_wave overrides)
     int hpw = kHypPerWave;
@@ -1122,8 +1064,8 @@ int plan_score(int64_t n, int64_t h_count, int64_t batch, double thr, const sfm_
     } else {
         while (hpw > 1 && (h_count + hpw - 1) / hpw * batch < 5120) hpw /= 2;
     }
-    SFM_REQUIRE_GRID("sfm_score_sed", (h_count + hpw - 1) / hpw, 256 / kWave, 256, batch);
-    SFM_REQUIRE_GRID("sfm_score_sed (ordering pre-pass)", h_count, 256, 256, batch);
+    if (!sfmhost::grid_fits((h_count + hpw - 1) / hpw, 256 / kWave, 256, batch)) return refuse(fn, kBeyondOneLaunch);
+    if (!sfmhost::grid_fits(h_count, 256, 256, batch)) return refuse(fn, "the ordering pre-pass exceeds what one launch covers");
     const int64_t waves = (h_count + kHypPerWave - 1) / kHypPerWave;
     // longest-first processing order (cost pre-pass + counting sort); options.order = 0 keeps index order
     // It pays only when the launch has few generations of waves (a long wave starting late then idles the chip at
@@ -1136,10 +1078,20 @@ int plan_score(int64_t n, int64_t h_count, int64_t batch, double thr, const sfm_
     const bool matrix = use_matrix_kernel(n, h_count, batch, opt);
     // options.one_sided = 0 switches tier 1 of the VALU filter back to the two-sided test (ablation)
     const bool one_sided = opt.one_sided != 0;
-    plan->hpw = hpw;
-    plan->one_sided = one_sided;
-    plan->a_scale = matrix ? matrixscore::scale_for(thr) : (one_sided ? one_sided_scale(thr) : 1.0);
+    p->a_scale = matrix ? matrixscore::scale_for(p->thr) : (one_sided ? one_sided_scale(p->thr) : 1.0);
     const int split_env = opt.split;
+    // the fused small pass launches its own scoring kernel (launch_small_score) from the same options
+    // ... its hypotheses per wave: at most 32768 hypotheses are a few generations of waves at best, where two per wave (7
+    // waves per SIMD) beat four (5 per SIMD; measured at 20 000 and 30 000 hypotheses: 80 vs 85 and 186 vs 198 us per
+    // pass) and one per wave wins as long as two would leave the chip short of waves (profiles/r02/small_pass_hpw.log)
+    p->small.hpw = opt.hyps_per_wave != 0 ? opt.hyps_per_wave : (h_count + 1) / 2 >= 5120 ? 2 : 1;
+    p->small.blocks = grid_for((h_count + p->small.hpw - 1) / p->small.hpw, 256 / kWave);   // (at most 32768 hypotheses: 8192 blocks)
+    // block barrier every `sync_every` iterations (three 128-point steps each) of the one-hypothesis-per-wave loop (0 = never): see the kernel
+    // measured (profiles/r03/small_pass/block_barrier.log): every 1..4 iterations alike, -2 % at 5000 x 10000, -5 % at 7000..8000
+    // points (L1 -> L2 requests -41 %), nothing below ~4000 points; options.block_sync overrides
+    p->small.sync_every = opt.block_sync >= 0 ? opt.block_sync : (p->small.hpw == 1 && n >= 4096 ? 2 : 0);
+    p->small.prep_blocks = (int)((n + kPrepPoints - 1) / kPrepPoints);
+    p->small.a_scale = one_sided_scale(p->thr);
     if (!matrix) {
         // Range split: a single-pair launch of 3 to 8 generations of waves (5120 each) is cut into 2 ranges of the points, so
         // that its last generation — a whole wave duration of draining chip — is half as long: 2.233-2.240 ms against
@@ -1162,9 +1114,20 @@ int plan_score(int64_t n, int64_t h_count, int64_t batch, double thr, const sfm_
                 chunks_per_unit = 0;
             }
         }
-        plan->ws = WsPlan{false, units, false};
-        plan->use_order = use_order;
-        plan->per_unit = chunks_per_unit;
+        p->ws = WsPlan{false, units, false};
+        p->use_order = use_order;
+        p->per_unit = chunks_per_unit;
+        auto& v = p->valu;
+        v.hpw = hpw;
+        v.one_sided = one_sided;
+        v.prepare_blocks = n <= 8192 ? 1u : grid_stride(n, 256, 64);
+        v.blocks = grid_for((h_count + hpw - 1) / hpw, 256 / kWave);
+        // batches: all blocks of a pair on one XCD (the kernel's block -> (pair, block) map; options.xcd_map = 0: plain grid);
+        // one pair with ranges: `units` consecutive blocks per group of waves
+        const int64_t flat_blocks = (int64_t)v.blocks * ((batch + 7) / 8 * 8);
+        const bool remap = opt.xcd_map != 0 && batch > 1 && flat_blocks <= 0x7FFFFFFF;
+        v.blocks_per_pair = remap ? (int)v.blocks : 0;
+        v.scoring_grid = units > 1 ? dim3(v.blocks * (unsigned)units) : remap ? dim3((unsigned)flat_blocks) : dim3(v.blocks, (unsigned)batch);
         return SFM_OK;
     }
     // Waves of 32 hypotheses are few (3125 at 100 000 hypotheses, against 12 288 resident ones) and long: the points are cut
@@ -1188,10 +1151,10 @@ int plan_score(int64_t n, int64_t h_count, int64_t batch, double thr, const sfm_
     int m_units = (steps + steps_per_unit - 1) / steps_per_unit;
     const bool must_split = steps > matrixscore::kMaxRangeSteps;   // (a queue entry keeps its step relative to the range in 16 bits)
     if (must_split && (steps_per_unit > matrixscore::kMaxRangeSteps || m_units <= 1 || split_env == 0)) {
-        steps_per_unit = matrixscore::kMaxRangeSteps;   // more than 2 M points per pair: ranges of 2^16 steps, whatever was asked for
+        steps_per_unit = matrixscore::kMaxRangeSteps;   // more than 1 M points per pair: ranges of 2^15 steps, whatever was asked for
         m_units = (steps + steps_per_unit - 1) / steps_per_unit;
         if (!sfmhost::grid_fits((int64_t)grid_for(waves32, 256 / kWave) * (int64_t)m_units * ((batch + 7) / 8 * 8), 1, 256))
-            return fail(SFM_EINVAL, "sfm_score_sed: hypotheses x ranges exceed what one launch covers");
+            return refuse(fn, "hypotheses x ranges exceed what one launch covers");
     } else if (m_units <= 1 || split_env == 0 ||
                !sfmhost::grid_fits((int64_t)grid_for(waves32, 256 / kWave) * (int64_t)m_units * ((batch + 7) / 8 * 8), 1, 256)) {
         m_units = 1;
@@ -1205,15 +1168,42 @@ int plan_score(int64_t n, int64_t h_count, int64_t batch, double thr, const sfm_
     // 20 000 x 40 000 — the larger pre-pass costs 3-8 us more than the replay saves), and for a single pair only: for
     // the 256 pairs of C5 — 9 ranges of 36 steps, so 44 % of all reject words would go through memory, 590 MB written and read —
     // it was measured a loss (2.71 ms per batch against 2.57-2.69, whether a pre-pass wave took one range or all nine).
-    bool record = false;
-#if SFM_MATRIX_REPLAY
     using matrixscore::kReplaySteps;
-    record = matrix_order && batch == 1 && m_units >= 2 && m_units % 2 == 0 && m_units * kReplaySteps == matrixscore::estimate_steps(n) &&
-             steps_per_unit >= kReplaySteps && steps - (m_units - 1) * steps_per_unit >= kReplaySteps;
-#endif
-    plan->ws = WsPlan{true, m_units, record};
-    plan->use_order = matrix_order;
-    plan->per_unit = steps_per_unit;
+    const bool record = matrix_order && batch == 1 && m_units >= 2 && m_units % 2 == 0 && m_units * kReplaySteps == matrixscore::estimate_steps(n) &&
+                        steps_per_unit >= kReplaySteps && steps - (m_units - 1) * steps_per_unit >= kReplaySteps;
+    p->ws = WsPlan{true, m_units, record};
+    p->use_order = matrix_order;
+    p->per_unit = steps_per_unit;
+    auto& m = p->matrix;
+    m.setup_blocks = grid_stride(n, 1024, matrixscore::kSetupBlocks);
+    m.table_blocks = (int)((matrixscore::table_steps(n) + 3) / 4);
+    // one pair, in cost order, many hypotheses: waves of 64 hypotheses behind the heaviest entries of the order (the kernel's
+    // WIDE_WAVES); batches, unordered launches and fewer hypotheses: waves of 32 everywhere
+    m.wide_waves = batch == 1 && matrix_order && h_count >= SFM_MATRIX_WIDE_MIN_HYPOTHESES;
+    // Where the wide waves begin is decided on the device — the sort leaves it in buckets[kWideFromWord]: the first class boundary in
+    // [SFM_MATRIX_WIDE_FROM, kWideFromMax], or 0 —, so the grid covers kWideFromMax entries in waves of 32 and all entries in waves
+    // of 64; waves without entries return.
+    m.wide_from_min = m.wide_waves ? SFM_MATRIX_WIDE_FROM : 0;
+    m.wide_from_max = m.wide_waves ? matrixscore::kWideFromMax : 0;
+    using matrixscore::kHyps;
+    const int64_t scoring_waves = m.wide_waves ? m.wide_from_max / kHyps + (h_count + 2 * kHyps - 1) / (2 * kHyps) : waves32;
+    const unsigned blocks = grid_for(scoring_waves, 256 / kWave);
+    const unsigned blocks_of_32 = grid_for(waves32, 256 / kWave);   // the cost pre-pass: waves of 32 always
+    // batches: flat grid of 8-pair groups (the kernel's block -> (pair, block) map), `units` range blocks per block of a pair; a
+    // single pair: blocks x ranges
+    const unsigned groups = batch > 1 ? (unsigned)((batch + 7) / 8 * 8) : 1u;
+    m.blocks_per_pair = batch > 1 ? (int)blocks * m_units : 0;
+    // a single pair: persistent waves — as many blocks as the chip holds at once, every wave takes (group of 32 hypotheses,
+    // range) items from a per-XCD counter (see the kernel); the counters were zeroed with the class counters
+    m.persistent = batch == 1 && opt.persistent > 0;
+    m.scoring_blocks = blocks * groups * (unsigned)m_units;   // (persistent: capped by plan_score)
+    // The cost pre-pass: a single pair scans four ranges of its steps — or, recording, the first steps of each of the scoring
+    // launch's ranges, kRecordRangesPerWave of them per wave —; a pair of a batch one range, all ranges when recording (see the kernel)
+    const int e_steps = matrixscore::estimate_steps(n);
+    m.prepass_units = record ? (batch == 1 ? std::max(1, m_units / kRecordRangesPerWave) : 1) : (batch == 1 && e_steps >= 128 ? 4 : 1);
+    m.prepass_steps = record ? kReplaySteps : e_steps / m.prepass_units;
+    m.prepass_blocks = blocks_of_32 * groups * (unsigned)m.prepass_units;
+    m.prepass_blocks_per_pair = batch > 1 ? (int)blocks_of_32 * m.prepass_units : 0;
     return SFM_OK;
 }
 
@@ -1230,151 +1220,91 @@ int compute_units() {
     return cus;
 }
 
-// Scoring launch with tier 1 on the matrix pipe (sfm_score_matrix.h): one pair, workspace prepared with that kernel's scale.
-int launch_matrix(const FilteredLaunch& a) {
-    using namespace matrixscore;
-    const unsigned pairs = (unsigned)a.batch;
-    const uint4* table = reinterpret_cast<const uint4*>(a.ws + ws_matrix_offset(a.n, a.h_count, a.batch, a.plan));
-    static_assert(kBlocks * 2 * 16 == 96, "sfm_score_ws.h sizes the tables: 3 blocks");
-    const uint4* hyp_table = reinterpret_cast<const uint4*>(a.ws + ws_matrix_hyp_offset(a.n, a.h_count, a.batch, a.plan));
-    unsigned char* fix = a.ws + ws_matrix_fix_offset(a.n, a.h_count, a.batch, a.plan);   // the sample corrections, per pair
-    // partial maxima (in the workspace's fp32-point region, which this kernel does not use: one float4 per setup block and pair) +
-    // all zeroing, then both tables — unless a fused pass has done all of that already (tables_ready: launch_large_setup in front of
-    // its fit launch, whose lanes wrote the hypotheses' rows and sample corrections; the point table by blocks of the fit launch
-    // for one pair, by a points-only launch of matrix_tables_kernel for a batch)
-    if (!a.tables_ready) {
-        float4* partial = reinterpret_cast<float4*>(a.ws + ws_points_offset(a.batch));
-        const unsigned setup_blocks = grid_stride(a.n, 1024, kSetupBlocks);
-        hipLaunchKernelGGL(matrix_setup_kernel, dim3(setup_blocks, pairs), dim3(256), 0, a.st, a.corr, a.n, a.a_scale, partial, a.buckets,
-                           a.cnt, a.h_count, a.select_state);
-        const int step_blocks = (int)((table_steps(a.n) + 3) / 4);
-        hipLaunchKernelGGL(matrix_tables_kernel, dim3((unsigned)step_blocks + grid_for(2 * (int64_t)a.h_count, 256), pairs), dim3(256), 0, a.st,
-                           a.corr, a.n, a.a_scale, (const float4*)partial, (int)setup_blocks, const_cast<uint4*>(table), step_blocks, a.E,
-                           a.h_count, const_cast<uint4*>(hyp_table), a.S, a.thr, fix);
-    }
-    // a single pair: persistent waves — as many blocks as the chip holds at once, every wave takes (group of 32 hypotheses,
-    // range) items from a per-XCD counter (see the kernel); the counters were zeroed with the class counters
-    const bool persistent = a.batch == 1 && a.persistent;
-    // one pair, in cost order, many hypotheses: waves of 64 hypotheses behind the heaviest entries of the order (the kernel's
-    // WIDE_WAVES); everything else — batches, unordered launches, fewer hypotheses — waves of 32
-    const bool wide_waves = kWideWaves && a.use_order &&
-                            a.h_count >= (a.batch == 1 ? SFM_MATRIX_WIDE_MIN_HYPOTHESES : SFM_MATRIX_WIDE_MIN_HYPOTHESES_BATCH);
-    // entries of a pair's order that stay in waves of 32 at least — one pair: SFM_MATRIX_WIDE_FROM; a pair of a batch: an eighth
-    // of its hypotheses, in whole blocks — and at most (four times that)
-    const int wide_from_min = a.batch == 1 ? SFM_MATRIX_WIDE_FROM : std::max(128, (int)(a.h_count / 8 / 128 * 128));
-    const int wide_from_max = 4 * wide_from_min;
-    // (where the wide waves begin is decided on the device — the sort leaves it in the pair's buckets[kWideFromWord] —, anywhere from
-    // 0 to wide_from_max: the grid covers wide_from_max entries in waves of 32 and all entries in waves of 64; waves without entries return)
-    const int64_t waves = wide_waves ? wide_from_max / kHyps + (a.h_count + 2 * kHyps - 1) / (2 * kHyps) : (a.h_count + kHyps - 1) / kHyps;
-    const unsigned blocks = grid_for(waves, 256 / kWave);
-    const unsigned blocks_of_32 = grid_for((a.h_count + kHyps - 1) / kHyps, 256 / kWave);   // the cost pre-pass: waves of 32 always
-    const unsigned resident_blocks = (unsigned)compute_units() * (unsigned)(wide_waves ? kWideOcc : SFM_MATRIX_OCC);
-    // batches: flat grid of 8-pair groups (the kernel's block -> (pair, block) map), `units` range blocks per block of a pair; a
-    // single pair: blocks x ranges
-    const int blocks_per_pair = a.batch > 1 ? (int)blocks : 0;
-    const unsigned flat = a.batch > 1 ? blocks * (unsigned)((a.batch + 7) / 8 * 8) : blocks;
-    const int32_t* order_arg = nullptr;
-    // (whether the pre-pass records its reject words for the scoring launch: plan_score)
-    using matrixscore::kReplaySteps;
-    uint16_t* record = a.plan.record ? reinterpret_cast<uint16_t*>(a.ws + ws_matrix_record_offset(a.n, a.h_count, a.batch, a.plan)) : nullptr;
-    if (a.use_order) {
-        // cost pre-pass with this kernel's own tier 1 over the first steps (survivors per 1024 points, in sixteenths, into
-        // `cnt`, which the scoring launch rewrites), then the counting sort by class
-        const int e_steps = estimate_steps(a.n);
-        // a single pair: four ranges of the pre-pass's steps — or, recording, the first steps of each of the scoring launch's ranges
-        // (a single pair: half as many units in the launch, each wave takes two of the ranges; a batch: one unit, all ranges — see the kernel)
-#ifndef SFM_MATRIX_RECORD_RANGES_PER_WAVE
-#define SFM_MATRIX_RECORD_RANGES_PER_WAVE 2   // recording pre-pass, single pair: ranges of the scoring launch one wave scans (1, 2, 4 or 8 of the 8)
-#endif
-        const int e_units = record != nullptr ? (a.batch == 1 ? std::max(1, a.units / SFM_MATRIX_RECORD_RANGES_PER_WAVE) : 1)
-                                              : (a.batch == 1 && e_steps >= 128 ? 4 : 1);
-        // (the ranges of the pre-pass add into `cnt`: zeroed by matrix_setup_kernel)
-#ifndef SFM_MATRIX_WIDE_PREPASS
-#define SFM_MATRIX_WIDE_PREPASS 0   // measurement build: the cost pre-pass of one pair in waves of 64 hypotheses as well
-#endif
-        const bool wide_prepass = SFM_MATRIX_WIDE_PREPASS && a.batch == 1;
-        const unsigned blocks_prepass = wide_prepass ? grid_for((a.h_count + 2 * kHyps - 1) / (2 * kHyps), 256 / kWave) : blocks_of_32;
-        const unsigned flat_of_32 = a.batch > 1 ? blocks_of_32 * (unsigned)((a.batch + 7) / 8 * 8) : blocks_prepass;
-        const auto prepass_kernel = wide_prepass ? score_sed_matrix_kernel<true, 0, true> : score_sed_matrix_kernel<true, 0, false>;
-        hipLaunchKernelGGL(prepass_kernel, dim3(flat_of_32 * (unsigned)e_units), dim3(256), 0, a.st, a.corr, hyp_table, table,
-                           a.n, a.E, a.h_count, a.thr, (const int32_t*)nullptr, a.cnt, a.s1, a.s2, e_units,
-                           record != nullptr ? kReplaySteps : e_steps / e_units,
-                           (unsigned char*)nullptr, (const unsigned char*)nullptr, (int)a.batch, (a.batch > 1 ? (int)blocks_of_32 : 0) * e_units, (int32_t*)nullptr,
-                           record, a.chunks_per_unit, a.units, (const int32_t*)nullptr, 0);
-        const dim3 per_hyp(grid_for(a.h_count, 256), pairs);
-        hipLaunchKernelGGL(score_class_count_kernel, per_hyp, dim3(256), 0, a.st, a.cnt, a.h_count, a.buckets);
-        hipLaunchKernelGGL(score_class_scan_scatter_kernel, per_hyp, dim3(256), 0, a.st, a.cnt, a.h_count, a.buckets, a.order,
-                           wide_waves ? wide_from_min : 0, wide_from_max);
-        const int rc = check_launch("score order kernels");
-        if (rc != SFM_OK) return rc;
-        order_arg = a.order;
-    }
-    unsigned char* split = nullptr;   // partials of the ranges: [range][hypothesis], folded by matrix_fold_kernel behind the launch
-    if (a.units > 1) split = a.ws + ws_tail_offset(a.n, a.h_count, a.batch);
-    if (a.event_before) (void)hipEventRecord(a.event_before, a.st);
-    const int64_t item_blocks = (int64_t)flat * a.units;
-    const unsigned grid_blocks = persistent ? (unsigned)std::min<int64_t>(item_blocks, resident_blocks) : (unsigned)item_blocks;
-    // (the pops of a round that share one execution-mask region: sfm_score_matrix.h, matrix_item's MASK_GROUP)
-    const auto scoring_kernel = wide_waves ? score_sed_matrix_kernel<false, SFM_MATRIX_MASK_GROUP_WIDE, true>
-                                : a.batch > 1 ? score_sed_matrix_kernel<false, SFM_MATRIX_MASK_GROUP_BATCH, false>
-                                              : score_sed_matrix_kernel<false, SFM_MATRIX_MASK_GROUP_SINGLE, false>;
-    hipLaunchKernelGGL(scoring_kernel, dim3(grid_blocks), dim3(256), 0, a.st, a.corr, hyp_table, table, a.n,
-                       a.E, a.h_count, a.thr, order_arg, a.cnt, a.s1, a.s2, a.units, a.chunks_per_unit, split, fix,
-                       (int)a.batch, blocks_per_pair * a.units, persistent ? a.buckets + kTicketWords : (int32_t*)nullptr, record, 0, 0,
-                       wide_waves ? a.buckets + kWideFromWord : (const int32_t*)nullptr, wide_from_max);
-    if (a.event_after) (void)hipEventRecord(a.event_after, a.st);
-    if (a.deferred != nullptr) {   // a fused pass folds the ranges inside its selection launch
-        *a.deferred = sfmhost::LargeScore{a.units, split, fix};
-    } else if (a.units > 1) {
-        hipLaunchKernelGGL(matrix_fold_kernel, dim3(grid_stride(a.h_count, 256, 1024), pairs), dim3(256), 0, a.st, split, fix, a.units,
-                           a.h_count, a.cnt, a.s1, a.s2);
-    }
-    return check_launch("score_sed_matrix_kernel");
-}
-
 }  // namespace
 
 namespace sfmhost {
 
-bool score_options_valid(const sfm_score_options* options) { return options == nullptr || valid_options(*options); }
-
-double small_pass_a_scale(double thr) { return one_sided_scale(thr); }
-
-int32_t* small_pass_order(unsigned char* workspace, int64_t n, int64_t h_count) {
-    // with every wave of the scoring launch resident at once (one generation) the order cannot change anything
-    if (h_count <= 4096) return nullptr;
-    return reinterpret_cast<int32_t*>(workspace + ws_order_offset(n, 1));
+int plan_score(const char* fn, int64_t n, int64_t h_count, int64_t batch, double thr, const sfm_score_options* options,
+               void* workspace, int64_t workspace_bytes, ScorePlan* plan) {
+    *plan = ScorePlan{};
+    plan->n = n;
+    plan->h_count = h_count;
+    plan->batch = batch;
+    plan->thr = thr;
+    if (!load_options(options, &plan->opt)) return refuse(fn, "an option is out of range");
+    if (workspace == nullptr) {   // the exact kernel: waves of kHypPerWave hypotheses
+        plan->exact = true;
+        if (!grid_fits((h_count + kHypPerWave - 1) / kHypPerWave, 256 / kWave, 256, batch)) return refuse(fn, kBeyondOneLaunch);
+        return SFM_OK;
+    }
+    const int rc = plan_launches(fn, plan);
+    if (rc != SFM_OK) return rc;
+    if (workspace_bytes < workspace_bytes_for(n, h_count, batch, plan->ws))
+        return refuse(fn, "workspace smaller than sfm_score_workspace_bytes_ex(n, h_count, batch, options)");
+    if ((reinterpret_cast<uintptr_t>(workspace) & 15u) != 0) return refuse(fn, "workspace must be 16-byte aligned");
+    unsigned char* ws = static_cast<unsigned char*>(workspace);
+    plan->workspace = ws;
+    plan->buckets = reinterpret_cast<int32_t*>(ws + ws_buckets_offset(n, batch));
+    plan->order = reinterpret_cast<int32_t*>(ws + ws_order_offset(n, batch));
+    if (plan->ws.units > 1) plan->split = ws + ws_tail_offset(n, h_count, batch);
+    // with every wave of the small pass's scoring launch resident at once (one generation) an order cannot change anything
+    if (batch == 1 && h_count > 4096) plan->small.order = plan->order;
+    if (plan->ws.matrix) {
+        plan->partial = reinterpret_cast<float4*>(ws + ws_points_offset(batch));
+        plan->table = reinterpret_cast<uint4*>(ws + ws_matrix_offset(n, h_count, batch, plan->ws));
+        plan->hyp_table = reinterpret_cast<uint4*>(ws + ws_matrix_hyp_offset(n, h_count, batch, plan->ws));
+        plan->fix = ws + ws_matrix_fix_offset(n, h_count, batch, plan->ws);
+        if (plan->ws.record) plan->record = reinterpret_cast<uint16_t*>(ws + ws_matrix_record_offset(n, h_count, batch, plan->ws));
+        if (plan->matrix.persistent) {   // as many blocks as the chip holds at once
+            const unsigned resident = (unsigned)compute_units() * (unsigned)(plan->matrix.wide_waves ? matrixscore::kWideOcc : SFM_MATRIX_OCC);
+            plan->matrix.scoring_blocks = std::min(plan->matrix.scoring_blocks, resident);
+        }
+    }
+    return SFM_OK;
 }
 
-int launch_small_score(const SmallPass& p) {
-    // hypotheses per wave: at most 32768 hypotheses are a few generations of waves at best, where two per wave (7
-    // waves per SIMD) beat four (5 per SIMD; measured at 20 000 and 30 000 hypotheses: 80 vs 85 and 186 vs 198 us per
-    // pass) and one per wave wins as long as two would leave the chip short of waves (profiles/r02/small_pass_hpw.log)
-    const sfm_score_options opt = resolve_options(p.options);   // (NULL: the process-wide defaults)
-    int hpw = (p.h_count + 1) / 2 >= 5120 ? 2 : 1;
-    if (opt.hyps_per_wave != 0) hpw = opt.hyps_per_wave;
-    const int64_t waves = (p.h_count + hpw - 1) / hpw;
-    const int64_t blocks = (waves + 256 / kWave - 1) / (256 / kWave);
-    SFM_REQUIRE_GRID("sfm_ransac_pass_small", blocks, 1, 256);
-    const int prep_blocks = (int)((p.n + kPrepPoints - 1) / kPrepPoints);
-    const dim3 grid((unsigned)blocks);
-    // block barrier every `sync_every` iterations (three 128-point steps each) of the one-hypothesis-per-wave loop (0 = never): see the kernel
-    // measured (profiles/r03/small_pass/block_barrier.log): every 1..4 iterations alike, -2 % at 5000 x 10000, -5 % at 7000..8000
-    // points (L1 -> L2 requests -41 %), nothing below ~4000 points; options.block_sync overrides
-    const int sync_every = opt.block_sync >= 0 ? opt.block_sync : (hpw == 1 && p.n >= 4096 ? 2 : 0);
-    if (opt.timing_before) (void)hipEventRecord((hipEvent_t)opt.timing_before, p.stream);
-#define SFM_LAUNCH_FUSED(H)                                                                                          \
-    hipLaunchKernelGGL((score_sed_filtered_kernel<H, true, true>), grid, dim3(256), 0, p.stream, (const Corr*)p.corr, \
-                       p.workspace, (int)p.n, p.E, p.S, (int)p.h_count, p.thr, one_sided_scale(p.thr),               \
-                       (const int32_t*)small_pass_order(p.workspace, p.n, p.h_count), p.cnt, p.s1, p.s2, 1, 0, prep_blocks, \
-                       sync_every)
-    switch (hpw) {
+int launch_score(const ScorePlan& p, const ScoreArrays& io) {
+    if (p.exact) {
+        if (p.opt.timing_before) (void)hipEventRecord((hipEvent_t)p.opt.timing_before, io.stream);
+        hipLaunchKernelGGL(score_sed_exact_kernel<kHypPerWave>, dim3(grid_for((p.h_count + kHypPerWave - 1) / kHypPerWave, 256 / kWave),
+                           (unsigned)p.batch), dim3(256), 0, io.stream, (const Corr*)io.corr, (int)p.n, io.E, io.S, (int)p.h_count, p.thr,
+                           io.cnt, io.s1, io.s2);
+        if (p.opt.timing_after) (void)hipEventRecord((hipEvent_t)p.opt.timing_after, io.stream);
+        return check_launch("score_sed_exact_kernel");
+    }
+    // (the matrix-pipe kernel prepares everything itself in two launches — partial maxima + zeroing, then both operand tables —
+    // instead of reset / prepare / point table / hypothesis table / estimate zeroing)
+    return p.ws.matrix ? launch_matrix(p, io, /*tables_ready=*/false, /*fold_in_selection=*/false) : launch_valu(p, io, nullptr);
+}
+
+int launch_large_setup(const ScorePlan& p, const ScoreArrays& io, unsigned* select_state) {
+    if (!p.ws.matrix) return SFM_OK;
+    launch_matrix_setup(p, io, select_state);
+    if (p.batch > 1)   // the point tables of a batch: a launch of their own, four steps per 256-thread block
+        hipLaunchKernelGGL(matrixscore::matrix_tables_kernel, dim3((unsigned)p.matrix.table_blocks, (unsigned)p.batch), dim3(256), 0,
+                           io.stream, (const Corr*)io.corr, (int)p.n, p.a_scale, (const float4*)p.partial, (int)p.matrix.setup_blocks,
+                           p.table, p.matrix.table_blocks, (const double*)nullptr, 0, (uint4*)nullptr, (const int32_t*)nullptr, p.thr,
+                           (unsigned char*)nullptr);
+    return check_launch("matrix_setup_kernel");
+}
+
+int launch_large_score(const ScorePlan& p, const ScoreArrays& io, unsigned* select_state, bool fold_in_selection) {
+    return p.ws.matrix ? launch_matrix(p, io, /*tables_ready=*/true, fold_in_selection) : launch_valu(p, io, select_state);
+}
+
+int launch_small_score(const ScorePlan& p, const ScoreArrays& io) {
+    if (p.opt.timing_before) (void)hipEventRecord((hipEvent_t)p.opt.timing_before, io.stream);
+#define SFM_LAUNCH_FUSED(H)                                                                                                         \
+    hipLaunchKernelGGL((score_sed_filtered_kernel<H, true, true>), dim3(p.small.blocks), dim3(256), 0, io.stream, (const Corr*)io.corr, \
+                       p.workspace, (int)p.n, io.E, io.S, (int)p.h_count, p.thr, p.small.a_scale, (const int32_t*)p.small.order,     \
+                       io.cnt, io.s1, io.s2, 1, 0, p.small.prep_blocks, p.small.sync_every)
+    switch (p.small.hpw) {
         case 1: SFM_LAUNCH_FUSED(1); break;
         case 2: SFM_LAUNCH_FUSED(2); break;
         default: SFM_LAUNCH_FUSED(4); break;
     }
 #undef SFM_LAUNCH_FUSED
-    if (opt.timing_after) (void)hipEventRecord((hipEvent_t)opt.timing_after, p.stream);
+    if (p.opt.timing_after) (void)hipEventRecord((hipEvent_t)p.opt.timing_after, io.stream);
     return check_launch("score_sed_filtered_kernel (fused small pass)");
 }
 
@@ -1401,23 +1331,19 @@ extern "C" int sfm_debug_read_wave_stamps(unsigned long long* out, int64_t waves
 }
 #endif
 
-namespace {
-int score_sed_impl(const double* corr, int64_t n, const double* E, const int32_t* S, int64_t h_count, int64_t batch, double thr,
-                   int32_t* cnt, double* s1, double* s2, void* workspace, int64_t workspace_bytes, void* stream,
-                   const sfm_score_options& opt, unsigned* select_state, sfmhost::LargeScore* deferred, bool tables_ready = false);
-}
-
 extern "C" {
 
 int64_t sfm_score_workspace_bytes_ex(int64_t n, int64_t h_count, int64_t batch, const sfm_score_options* options) {
     if (n < 0 || h_count < 0 || batch < 0 || n > 0x7FFFFFFF || h_count > 0x3FFFFFFF) return -1;
-    const sfm_score_options opt = resolve_options(options);
-    if (!valid_options(opt)) return -1;
-    ScorePlan plan;
-    plan.ws = WsPlan{false, 1, false};
+    sfmhost::ScorePlan plan{};
+    if (!load_options(options, &plan.opt)) return -1;
+    plan.n = n;
+    plan.h_count = h_count;
+    plan.batch = batch;
+    plan.thr = 1.0;
     // (sizes no call accepts — fewer than 8 points, nothing to score, a grid beyond one launch — get the plain layout: the call
     // itself reports the error)
-    if (n >= 8 && h_count >= 1 && batch >= 1 && plan_score(n, h_count, batch, 1.0, opt, &plan) != SFM_OK) plan.ws = WsPlan{false, 1, false};
+    if (n < 8 || h_count < 1 || batch < 1 || plan_launches("sfm_score_workspace_bytes_ex", &plan) != SFM_OK) plan.ws = WsPlan{false, 1, false};
     return workspace_bytes_for(n, h_count, batch, plan.ws);
 }
 
@@ -1427,8 +1353,8 @@ int64_t sfm_score_workspace_bytes(int64_t n, int64_t h_count, int64_t batch) {
 
 int sfm_score_kernel_choice_ex(int64_t n, int64_t h_count, int64_t batch, const sfm_score_options* options) {
     if (n < 0 || h_count < 0 || batch < 0) return -1;
-    const sfm_score_options opt = resolve_options(options);
-    if (!valid_options(opt)) return -1;
+    sfm_score_options opt;
+    if (!load_options(options, &opt)) return -1;
     return use_matrix_kernel(n, h_count, batch, opt) ? SFM_SCORE_KERNEL_MATRIX : SFM_SCORE_KERNEL_FILTERED;
 }
 
@@ -1449,7 +1375,7 @@ int sfm_score_set_default_options(const sfm_score_options* options) {
 
 int sfm_score_get_default_options(sfm_score_options* out) {
     if (!out) return fail(SFM_EINVAL, "sfm_score_get_default_options: null pointer");
-    *out = resolve_options(nullptr);
+    *out = *g_default_options.load(std::memory_order_acquire);
     return SFM_OK;
 }
 
@@ -1493,116 +1419,16 @@ int sfm_score_sed(const double* corr, int64_t n, const double* E, const int32_t*
 int sfm_score_sed_ex(const double* corr, int64_t n, const double* E, const int32_t* S, int64_t h_count,
                      int64_t batch, double thr, int32_t* cnt, double* s1, double* s2, void* workspace,
                      int64_t workspace_bytes, void* stream, const sfm_score_options* options) {
-    const sfm_score_options opt = resolve_options(options);
-    if (!valid_options(opt)) return fail(SFM_EINVAL, "sfm_score_sed_ex: an option is out of range");
-    return score_sed_impl(corr, n, E, S, h_count, batch, thr, cnt, s1, s2, workspace, workspace_bytes, stream, opt, nullptr, nullptr);
-}
-
-}  // extern "C"
-
-namespace {
-
-int score_sed_impl(const double* corr, int64_t n, const double* E, const int32_t* S, int64_t h_count, int64_t batch, double thr,
-                   int32_t* cnt, double* s1, double* s2, void* workspace, int64_t workspace_bytes, void* stream,
-                   const sfm_score_options& opt, unsigned* select_state, sfmhost::LargeScore* deferred, bool tables_ready) {
     if (h_count < 0 || batch < 0 || n < 0) return fail(SFM_EINVAL, "sfm_score_sed: negative size");
     if (n > 0x7FFFFFFF || h_count > 0x3FFFFFFF) return fail(SFM_EINVAL, "sfm_score_sed: size too large");
     if (h_count == 0 || batch == 0) return SFM_OK;
     if (!corr || !E || !S || !cnt || !s1 || !s2) return fail(SFM_EINVAL, "sfm_score_sed: null pointer");
     if (n < 8) return fail(SFM_EINVAL, "sfm_score_sed: need at least 8 correspondences");
-    hipStream_t st = (hipStream_t)stream;
-    const int64_t waves = (h_count + kHypPerWave - 1) / kHypPerWave;
-    SFM_REQUIRE_GRID("sfm_score_sed", waves, 256 / kWave, 256, batch);
-    const dim3 grid(grid_for(waves, 256 / kWave), (unsigned)batch);
-    if (workspace == nullptr) {
-        if (opt.timing_before) (void)hipEventRecord((hipEvent_t)opt.timing_before, st);
-        hipLaunchKernelGGL(score_sed_exact_kernel<kHypPerWave>, grid, dim3(256), 0, st, (const Corr*)corr, (int)n,
-                           E, S, (int)h_count, thr, cnt, s1, s2);
-        if (opt.timing_after) (void)hipEventRecord((hipEvent_t)opt.timing_after, st);
-        return check_launch("score_sed_exact_kernel");
-    }
-    ScorePlan plan;
-    const int rc_plan = plan_score(n, h_count, batch, thr, opt, &plan);   // every size check comes before the first launch: a refused call must not have touched the workspace
-    if (rc_plan != SFM_OK) return rc_plan;
-    if (workspace_bytes < workspace_bytes_for(n, h_count, batch, plan.ws))
-        return fail(SFM_EINVAL, "sfm_score_sed: workspace smaller than sfm_score_workspace_bytes_ex(n, h_count, batch, options)");
-    if ((reinterpret_cast<uintptr_t>(workspace) & 15u) != 0)
-        return fail(SFM_EINVAL, "sfm_score_sed: workspace must be 16-byte aligned");
-    unsigned char* ws = static_cast<unsigned char*>(workspace);
-    int32_t* buckets = reinterpret_cast<int32_t*>(ws + ws_buckets_offset(n, batch));
-    int32_t* order = reinterpret_cast<int32_t*>(ws + ws_order_offset(n, batch));
-    if (plan.ws.matrix) {
-        // (the matrix-pipe kernel: launch_matrix prepares everything itself in two launches — partial maxima + zeroing, then both
-        // operand tables — instead of reset / prepare / point table / hypothesis table / estimate zeroing; batches too since round 5:
-        // until then they went through score_prepare_kernel, which also wrote fp32 points that kernel never reads)
-        const FilteredLaunch margs{(const Corr*)corr, ws, (int)n, E, S, (int)h_count, thr, plan.use_order, cnt, s1, s2,
-                                   buckets, order, batch, st, true, plan.a_scale, plan.ws.units, plan.per_unit, true, opt.persistent > 0,
-                                   select_state, deferred, (hipEvent_t)opt.timing_before, (hipEvent_t)opt.timing_after, tables_ready, plan.ws};
-        return launch_matrix(margs);
-    }
-    // Small point sets are prepared by one block per pair, which stores the maxima itself; the zeroing kernel is then
-    // only needed for the class counters of the ordering pre-pass (a small pass is a chain of ~4 us launches).
-    const unsigned prepare_blocks = n <= 8192 ? 1u : grid_stride(n, 256, 64);
-    if (plan.use_order || prepare_blocks > 1)
-        hipLaunchKernelGGL(score_reset_kernel, dim3((unsigned)batch), dim3(256), 0, st, ws, buckets);
-    hipLaunchKernelGGL(score_prepare_kernel, dim3(prepare_blocks, (unsigned)batch), dim3(256), 0, st, (const Corr*)corr, n, plan.a_scale, ws);
-    const int rc = check_launch("score_prepare_kernel");
+    // every check comes before the first launch: a refused call must not have touched the workspace
+    sfmhost::ScorePlan plan;
+    const int rc = sfmhost::plan_score("sfm_score_sed", n, h_count, batch, thr, options, workspace, workspace_bytes, &plan);
     if (rc != SFM_OK) return rc;
-    if (select_state != nullptr)
-        hipLaunchKernelGGL(score_split_reset_kernel, dim3(1), dim3(256), 0, st, reinterpret_cast<int32_t*>(select_state), (int64_t)16);
-    const FilteredLaunch args{(const Corr*)corr, ws, (int)n, E, S, (int)h_count, thr, plan.use_order, cnt, s1, s2,
-                              buckets, order, batch, st, plan.one_sided, plan.a_scale, plan.ws.units, plan.per_unit, opt.xcd_map != 0, true,
-                              nullptr, nullptr, (hipEvent_t)opt.timing_before, (hipEvent_t)opt.timing_after, false, plan.ws};
-    switch (plan.hpw) {
-        case 1: return launch_filtered<1>(args);
-        case 2: return launch_filtered<2>(args);
-        default: return launch_filtered<4>(args);
-    }
+    return sfmhost::launch_score(plan, sfmhost::ScoreArrays{corr, E, S, cnt, s1, s2, (hipStream_t)stream});
 }
 
-}  // namespace
-
-namespace sfmhost {
-
-int launch_large_score(const LargePass& p, LargeScore* folded_later) {
-    if (folded_later != nullptr)   // (NULL: the scoring launches fold their ranges themselves)
-        *folded_later = LargeScore{1, nullptr, nullptr};   // (stays so unless the matrix-pipe kernel split the points into ranges)
-    const sfm_score_options opt = resolve_options(p.options);
-    if (!valid_options(opt)) return fail(SFM_EINVAL, "sfm_ransac_pass_large: an option is out of range");
-    if (p.h_count < 1 || p.n < 8 || p.n > 0x7FFFFFFF || p.h_count > 0x3FFFFFFF)
-        return fail(SFM_EINVAL, "sfm_ransac_pass_large: sizes out of range");
-    return score_sed_impl(p.corr, p.n, p.E, p.S, p.h_count, p.batch, p.thr, p.cnt, p.s1, p.s2, p.workspace, p.workspace_bytes, p.stream,
-                          opt, p.select_state, folded_later, p.tables_ready);
-}
-
-int launch_large_setup(const LargePass& p, MatrixTables* t) {
-    *t = MatrixTables{false, nullptr, 0, 0.0, nullptr, nullptr, nullptr, 0};
-    const sfm_score_options opt = resolve_options(p.options);
-    if (!valid_options(opt) || p.h_count < 1 || p.batch < 1 || p.n < 8 || p.n > 0x7FFFFFFF || p.h_count > 0x3FFFFFFF)
-        return SFM_OK;   // (the scoring call reports it)
-    ScorePlan plan;
-    if (plan_score(p.n, p.h_count, p.batch, p.thr, opt, &plan) != SFM_OK || !plan.ws.matrix) return SFM_OK;
-    using namespace matrixscore;
-    const unsigned setup_blocks = grid_stride(p.n, 1024, kSetupBlocks);
-    float4* partial = reinterpret_cast<float4*>(p.workspace + ws_points_offset(p.batch));
-    int32_t* buckets = reinterpret_cast<int32_t*>(p.workspace + ws_buckets_offset(p.n, p.batch));
-    t->matrix = true;
-    t->partial = partial;
-    t->partials = (int)setup_blocks;
-    t->a_scale = scale_for(p.thr);
-    t->hyp_table = reinterpret_cast<uint4*>(p.workspace + ws_matrix_hyp_offset(p.n, p.h_count, p.batch, plan.ws));
-    t->fix = p.workspace + ws_matrix_fix_offset(p.n, p.h_count, p.batch, plan.ws);
-    t->table = reinterpret_cast<uint4*>(p.workspace + ws_matrix_offset(p.n, p.h_count, p.batch, plan.ws));
-    t->step_blocks = p.batch == 1 ? (int)((table_steps(p.n) + 3) / 4) : 0;
-    hipLaunchKernelGGL(matrix_setup_kernel, dim3(setup_blocks, (unsigned)p.batch), dim3(256), 0, p.stream, (const Corr*)p.corr, (int)p.n,
-                       t->a_scale, partial, buckets, p.cnt, (int)p.h_count, p.select_state);
-    if (p.batch > 1) {   // the point tables of a batch: a launch of their own, four steps per 256-thread block
-        const int step_blocks = (int)((table_steps(p.n) + 3) / 4);
-        hipLaunchKernelGGL(matrix_tables_kernel, dim3((unsigned)step_blocks, (unsigned)p.batch), dim3(256), 0, p.stream, (const Corr*)p.corr,
-                           (int)p.n, t->a_scale, (const float4*)partial, (int)setup_blocks, t->table, step_blocks, (const double*)nullptr, 0,
-                           (uint4*)nullptr, (const int32_t*)nullptr, p.thr, (unsigned char*)nullptr);
-    }
-    return check_launch("matrix_setup_kernel");
-}
-
-}  // namespace sfmhost
+}  // extern "C"

@@ -79,18 +79,12 @@
 // gets an infinite slack: nothing is rejected and the exact tier decides everything.
 #pragma once
 
-#ifndef SFM_MATRIX_WIDE
-#define SFM_MATRIX_WIDE 1    // large single-pair launches: waves of 64 hypotheses behind the heaviest groups (matrix_item's WIDE; 0: waves of 32 everywhere)
-#endif
 #ifndef SFM_MATRIX_OCC
 #define SFM_MATRIX_OCC 4     // blocks per CU the matrix-pipe kernel is compiled for (32 KiB of queues each); the kernel with wide waves: 3 (163 VGPRs)
 #endif
 #ifndef SFM_MATRIX_POPS
 #define SFM_MATRIX_POPS 4    // points a lane pops per round of the exact tier (2: the same at 50 000 x 100 000, 10-13 % slower at 20 000 x 40 000 and 50 000 x 20 000 where the final drains dominate; 6: a wave less per SIMD; 8: spills)
 #endif
-#ifndef SFM_MATRIX_ABLATE
-#define SFM_MATRIX_ABLATE 0  // measurement builds only (WRONG results; tools/r04/ablate.sh): bit 0 no operand refills, bit 1 one matrix
-#endif                       // instruction instead of three, bit 2 one sign test instead of sixteen, bit 3 no queue push, bit 4 no fp16 subnormal operands
 #ifndef SFM_MATRIX_MASK_GROUP_SINGLE
 #define SFM_MATRIX_MASK_GROUP_SINGLE 4   // pops of an exact-tier round that share one execution-mask region, launches of one pair (0: no masking; A/B builds)
 #endif
@@ -99,10 +93,6 @@
 #endif
 #ifndef SFM_MATRIX_MASK_GROUP_BATCH
 #define SFM_MATRIX_MASK_GROUP_BATCH 2    // ... launches over a batch of pairs
-#endif
-#ifndef SFM_MATRIX_E_IN_REGISTERS
-#define SFM_MATRIX_E_IN_REGISTERS 1   // E held in 18 VGPRs through the tier-1 loop (0: loaded where a burst of rounds starts — better while the
-                                      // loop's registers were the constraint, 2.8 % slower at the bench size on the final kernel)
 #endif
 #ifndef SFM_MATRIX_STATS
 #define SFM_MATRIX_STATS 0   // diagnostic build: rounds of the exact tier, points popped, push-loop iterations (sfm_debug_matrix_stats)
@@ -116,7 +106,7 @@ namespace matrixscore {
 __device__ unsigned long long g_matrix_stats[4];
 #endif
 #ifndef SFM_MATRIX_STAMPS
-#define SFM_MATRIX_STAMPS 0   // diagnostic build (tools/r04/matrix_timeline.py): s_memrealtime stamps of every wave's phases
+#define SFM_MATRIX_STAMPS 0   // diagnostic build (tools/matrix_timeline.py): s_memrealtime stamps of every wave's phases
 #endif
 #if SFM_MATRIX_STAMPS
 __device__ unsigned long long g_matrix_stamps[10 * 65536];   // begin, operands in, loop done, drained, samples fixed, handed off, hw id, wave, exact-tier lane slots | points popped, shader clocks
@@ -132,19 +122,15 @@ __device__ unsigned long long g_matrix_stamps[10 * 65536];   // begin, operands 
 #ifndef SFM_MATRIX_CAP
 #define SFM_MATRIX_CAP 32
 #endif
-constexpr bool kWideWaves = SFM_MATRIX_WIDE != 0;   // the launcher may pick the kernel with wide waves (score_sed_matrix_kernel<.., .., true>)
-constexpr int kWideOcc = 3;
+constexpr int kWideOcc = 3;   // blocks per CU of the kernel with wide waves (score_sed_matrix_kernel<.., .., true>: one pair, in cost order)
 #ifndef SFM_MATRIX_WIDE_MIN_HYPOTHESES
-#define SFM_MATRIX_WIDE_MIN_HYPOTHESES 8192    // ... for one pair with at least this many hypotheses, in cost order (measured down to 200 000 x 10 000: -4 %)
-#endif
-#ifndef SFM_MATRIX_WIDE_MIN_HYPOTHESES_BATCH
-#define SFM_MATRIX_WIDE_MIN_HYPOTHESES_BATCH (1 << 30)   // ... per pair of a batch (measurement builds: 1024)
+#define SFM_MATRIX_WIDE_MIN_HYPOTHESES 8192    // ... for one pair with at least this many hypotheses (measured down to 200 000 x 10 000: -4 %)
 #endif
 #ifndef SFM_MATRIX_WIDE_FROM
-#define SFM_MATRIX_WIDE_FROM 4096              // entries of the heaviest-first order that stay in waves of 32 (a multiple of 128: whole blocks)
+#define SFM_MATRIX_WIDE_FROM 4096              // entries of the heaviest-first order that stay in waves of 32 at least
 #endif
 constexpr int kWideFromMax = 4 * SFM_MATRIX_WIDE_FROM;   // the wide waves begin at the first class boundary in [WIDE_FROM, kWideFromMax] (none: at entry 0)
-static_assert(SFM_MATRIX_WIDE_FROM % 128 == 0, "blocks of four waves of 32 hypotheses");
+static_assert(kWideFromMax % kHyps == 0, "waves of 32 cover the entries [0, kWideFromMax) exactly");
 constexpr int kCap = SFM_MATRIX_CAP;   // entries per lane queue (a power of two: the queue is a ring); an entry is one step's survivors
 constexpr int kHigh = kCap - 4;  // a step pushes at most one entry per lane: rounds start when a queue holds this many (checked once per group of steps) ...
 constexpr int kLow = 8;          // ... and stop when every queue is down to this
@@ -159,23 +145,13 @@ constexpr int kAhead = SFM_MATRIX_AHEAD;   // steps of operand loads in flight b
 #define SFM_MATRIX_ESTIMATE_AHEAD 1   // the same for the cost pre-pass (tier 1 alone: no exact tier competes for its registers); 1 or 3
 #endif
 static_assert(SFM_MATRIX_ESTIMATE_AHEAD == 1 || SFM_MATRIX_ESTIMATE_AHEAD == 3, "the recording pre-pass packs steps in pairs; the table is padded to four steps");
-#ifndef SFM_MATRIX_BUFFER_LOADS
-#define SFM_MATRIX_BUFFER_LOADS 1   // operand refills of the step loop as buffer loads (0: global loads with a 64-bit vector add per step)
-#endif
-#ifndef SFM_MATRIX_MASKED_SUMS
-#define SFM_MATRIX_MASKED_SUMS 0    // 1: the exact tier's count and sums under the execution mask instead of three selects — measured: equal at
-                                    // 50 000 x 100 000, 3-4 % slower at 20 000 x 40 000 and 50 000 x 20 000 (the branch in light waves' drains)
-#endif
-#ifndef SFM_MATRIX_REPLAY
-#define SFM_MATRIX_REPLAY 1         // the scoring launch replays the tier-1 results of the cost pre-pass (MatrixPair::record); 0: computes them again
-#endif
 #ifndef SFM_MATRIX_ESTIMATE_STEPS
 #define SFM_MATRIX_ESTIMATE_STEPS 128
 #endif
 constexpr int kEstimateSteps = SFM_MATRIX_ESTIMATE_STEPS;   // steps of 32 points the cost pre-pass scans at most (4096 points)
 constexpr int64_t kMaxPoints = sfmws::kMatrixMaxPoints;
-constexpr int kMaxRangeSteps = kWideWaves ? 32768 : 65536;   // a queue entry keeps the step RELATIVE TO ITS RANGE (wide waves: 2 x step + half) in 16 bits: at most 2^15 steps (1 M points) per range
-static_assert(kMaxPoints <= (int64_t)sfmws::kSplitMaxUnits * kMaxRangeSteps * kTile, "sixteen ranges of 2^16 steps cover the largest pair");
+constexpr int kMaxRangeSteps = 32768;   // a queue entry keeps the step RELATIVE TO ITS RANGE (wide waves: 2 x step + half) in 16 bits: at most 2^15 steps (1 M points) per range
+static_assert(kMaxPoints <= (int64_t)sfmws::kSplitMaxUnits * kMaxRangeSteps * kTile, "sixteen ranges of 2^15 steps cover the largest pair");
 
 // ... and an eighth of a smaller point set, but no fewer than 1024 points: the pre-pass is tier 1 over that share of the points
 __host__ __device__ inline int estimate_steps(int64_t n) {
@@ -410,8 +386,9 @@ SFM_DEVICE void matrix_item(const MatrixPair& a, int n, int h_count, double thr,
 
     // ---- this lane's hypothesis: exact entries for the exact tier; the B operands of tier 1 come from the table
     // matrix_hypothesis_kernel wrote once per launch (a hypothesis is scored by up to 16 range waves and the cost pre-pass)
-    // (the exact entries are loaded where the exact tier starts — in front of a burst of rounds, and of the final drain — not
-    // kept in 18 VGPRs through the tier-1 loop, which never reads them: the loop's occupancy is what they would cost)
+    // (the exact entries stay in 18 VGPRs through the tier-1 loop, which never reads them: loading them in front of every burst
+    // of rounds instead was better while the loop's registers were the constraint, 2.8 % slower on the final kernel.  The load
+    // stays a lambda: written as a plain block it changes the scheduling of every scoring kernel.)
     double e[9];
     auto load_e = [&]() __attribute__((always_inline)) {
         int64_t first = (int64_t)h * 9;
@@ -419,10 +396,7 @@ SFM_DEVICE void matrix_item(const MatrixPair& a, int n, int h_count, double thr,
 #pragma unroll
         for (int j = 0; j < 9; ++j) e[j] = E[first + j];
     };
-#if !SFM_MATRIX_E_IN_REGISTERS
-    if (ESTIMATE)
-#endif
-        load_e();
+    load_e();
     const uint4* __restrict__ operands = hyp_table + ((int64_t)h_first * 2 + half) * kBlocks;
     const f16x8 B0 = __builtin_bit_cast(f16x8, operands[0]);
     const f16x8 B1 = __builtin_bit_cast(f16x8, operands[1]);
@@ -505,19 +479,10 @@ SFM_DEVICE void matrix_item(const MatrixPair& a, int n, int h_count, double thr,
             for (int k = from; k < to; ++k) {
                 double sed;
                 const bool ok = sfm::sed_inlier(e, p[k].xa, p[k].ya, p[k].xb, p[k].yb, gate, sed) && active[k];
-#if SFM_MATRIX_MASKED_SUMS
-                if (ok) {   // under the execution mask (three instructions for the inlier lanes) instead of three selects + three instructions for all
-                    asm volatile("" : "+v"(c));
-                    c += 1;
-                    a1 += sed;
-                    a2 = fma(sed, sed, a2);
-                }
-#else
                 c += ok ? 1 : 0;
                 const double kept = ok ? sed : 0.0;   // masked once; its square is the masked square
                 a1 += kept;
                 a2 = fma(kept, kept, a2);
-#endif
             }
         };
         if (MASK_GROUP > 0) {
@@ -540,7 +505,7 @@ SFM_DEVICE void matrix_item(const MatrixPair& a, int n, int h_count, double thr,
     unsigned survivors = 0;   // ESTIMATE
     unsigned rec[4] = {0u, 0u, 0u, 0u}, rec_low = 0u;   // ESTIMATE, recording: the reject words of the last eight steps
     unsigned rec_upper[4] = {0u, 0u, 0u, 0u}, rec_upper_low = 0u;   // ... wide waves: of the lane's other half
-    static_assert((kAhead + 1) % 2 == 0 || !SFM_MATRIX_REPLAY, "the recording pre-pass packs the steps of a loop group two to a dword");
+    static_assert((kAhead + 1) % 2 == 0, "the recording pre-pass packs the steps of a loop group two to a dword");
     const int first_step = step_begin + (replaying ? kReplaySteps : 0);   // (the host replays only when every range has that many steps)
     if (step_begin < step_end) {
         const uint4* __restrict__ src = table + lane;
@@ -609,16 +574,14 @@ SFM_DEVICE void matrix_item(const MatrixPair& a, int n, int h_count, double thr,
             const int t = t0 + stage;   // (past the end of the points — at most kStages - 1 steps of the last range — these are the table's pad steps, which keep nothing)
             float16v r = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, d = r;
             r = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, A[stage][0]), B0, r, 0, 0, 0);
-#if !(SFM_MATRIX_ABLATE & 2)
             d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, A[stage][2]), B2, d, 0, 0, 0);
             r = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, A[stage][1]), B1, r, 0, 0, 0);
-#endif
             // rejected bits, register 0 ending up in bit 15: the sign of dB - r^2 (one rounding: the sign is exact, and zero
             // — equality — keeps the point) shifted in with an alignbit.  A NaN with its sign set counts as rejected, which is
             // what the exact tier would decide for it (sed = NaN is not <= thr).
             unsigned rejected = 0;
 #pragma unroll
-            for (int j = 0; j < ((SFM_MATRIX_ABLATE & 4) ? 1 : 16); ++j)
+            for (int j = 0; j < 16; ++j)
                 rejected = __builtin_amdgcn_alignbit(rejected, __float_as_uint(__builtin_fmaf(-r[j], r[j], d[j])), 31);
             unsigned rejected_upper = 0xffffu;   // wide waves: the other half's word of this lane's hypothesis (below)
             if (WIDE) {
@@ -651,17 +614,9 @@ SFM_DEVICE void matrix_item(const MatrixPair& a, int n, int h_count, double thr,
                 // addressing mode — no vector instruction computes an address in this loop; the scalar offset goes through the asm)
                 unsigned step_bytes = (unsigned)min(t + kStages, last_loadable) * (unsigned)(kBlocks * 64 * 16);   // (wave-uniform: a scalar register)
                 asm volatile("" : "+s"(step_bytes), "+v"(rejected), "+v"(rejected_upper));
-#if !(SFM_MATRIX_ABLATE & 1)
-#if SFM_MATRIX_BUFFER_LOADS
 #pragma unroll
                 for (int b = 0; b < kBlocks; ++b)
                     A[stage][b] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(table_rsrc, (int)lane_bytes + b * 1024, (int)step_bytes, 0));
-#else
-                const uint4* nxt = src + step_bytes / 16;
-#pragma unroll
-                for (int b = 0; b < kBlocks; ++b) A[stage][b] = nxt[b * 64];
-#endif
-#endif
             }
             if (ESTIMATE) {
                 survivors += (unsigned)__builtin_popcount(SFM_KEEP_OF(rejected));
@@ -684,9 +639,6 @@ SFM_DEVICE void matrix_item(const MatrixPair& a, int n, int h_count, double thr,
                     }
                 }
             } else {
-#if SFM_MATRIX_ABLATE & 8
-                survivors += (unsigned)__builtin_popcount(SFM_KEEP_OF(rejected));
-#else
                 const unsigned field = WIDE ? 2u * (unsigned)(t - step_begin) : (unsigned)(t - step_begin);   // (wide waves: 2 x step + half)
                 if (rejected != 0xffffu) {   // push: one entry with this step's survivors
                     // (step << 16) | keep  ==  ~(rejected ^ k),  k = (step << 16) ^ 0xffff0000 (wave-uniform): one v_xnor
@@ -697,7 +649,6 @@ SFM_DEVICE void matrix_item(const MatrixPair& a, int n, int h_count, double thr,
                     *ring_slot(tail) = ~(rejected_upper ^ (((field + 1u) << 16) ^ 0xffff0000u));
                     tail += kSlotBytes;
                 }
-#endif
             }
           }
           t0 += kStages;
@@ -714,9 +665,6 @@ SFM_DEVICE void matrix_item(const MatrixPair& a, int n, int h_count, double thr,
          // between two stages it falls back to vmcnt(0) at the top of every group.  A group pushes at most kStages entries per
          // lane: kHigh + kStages - 1 <= kCap.  (When rounds happen does not change any sum: a lane's queue is first-in first-out.)
          if (queue_full) {
-#if !SFM_MATRIX_E_IN_REGISTERS
-             load_e();
-#endif
              __builtin_amdgcn_wave_barrier();
              do round(); while (__builtin_amdgcn_ballot_w64((int)(tail - head) > kLow * (int)kSlotBytes) != 0ull);
          }
@@ -735,15 +683,9 @@ SFM_DEVICE void matrix_item(const MatrixPair& a, int n, int h_count, double thr,
         return;
     }
     SFM_STAMP(2);
-#if !SFM_MATRIX_E_IN_REGISTERS
-    load_e();
-#endif
     __builtin_amdgcn_wave_barrier();
     while (__builtin_amdgcn_ballot_w64(tail != head || cur != 0u) != 0ull) round();
     SFM_STAMP(3);
-#if SFM_MATRIX_ABLATE & 8
-    c += (int)survivors;
-#endif
 #if SFM_MATRIX_STATS
     if (lane == 0) {
         atomicAdd(&g_matrix_stats[0], (unsigned long long)stat_rounds);
@@ -850,7 +792,7 @@ __global__ __launch_bounds__(256) void matrix_fold_kernel(const unsigned char* _
 // The launch.  tickets == nullptr: one item per wave, placed by block index (batches of pairs with their XCD-aware block map).
 // tickets != nullptr (a single pair): PERSISTENT waves — the grid is what the chip holds at once (CUs x SFM_MATRIX_OCC blocks),
 // and every wave takes items from a counter until they run out.  Why: the hardware's workgroup dispatcher does not keep this
-// kernel's slots full.  With one block per 4 items (round 3) the stamps of every wave (tools/r04/matrix_timeline.py,
+// kernel's slots full.  With one block per 4 items (round 3) the stamps of every wave (tools/matrix_timeline.py,
 // profiles/r04) showed, per XCD, ONE shader engine at its 128 waves and the other three at 30-45 for most of the launch while
 // thousands of blocks were waiting — blocks are handed to the engines in turn, and the turn waits for the full one — 2600 of
 // 4096 slots occupied on average, the launch ending when the slowest XCD did.  Waves that fetch their own work do not depend on
@@ -858,12 +800,14 @@ __global__ __launch_bounds__(256) void matrix_fold_kernel(const unsigned char* _
 // Items of XCD x (tickets[16 x]): the ranges u = x (mod 8) of every group when the ranges are a multiple of eight — an XCD then
 // streams only its own eighth of the point operand table through its L2, as the block order of round 3 did; otherwise one
 // counter serves all.  The counters are zeroed by score_reset_kernel (they live behind the class counters).
-// WIDE_WAVES (one pair, in cost order, many hypotheses: launch_matrix): the entries [0, wide_from) of the order — the heaviest
+// WIDE_WAVES (one pair, in cost order, many hypotheses: plan_score, sfm_score.hip): the entries [0, wide_from) of the order — the heaviest
 // hypotheses, whose items are the longest of the launch — go in waves of 32 as everywhere else, the entries behind them in waves
 // of 64 (matrix_item's WIDE): the step's operands are loaded once for 2048 evaluations instead of 1024 — the operand stream keeps
 // a CU's vector L1 ~90 % busy otherwise (profiles/r05/README.md) — and a lane scores all 32 points of a step under its
 // hypothesis.  All of them wide, the heaviest items would take as long as the whole launch (50 000 x 100 000: 888 us median for
-// the first 2048 entries, 1.27 ms the longest, of a 1.27 ms launch).  wide_from is a multiple of 128: whole blocks of either kind.
+// the first 2048 entries, 1.27 ms the longest, of a 1.27 ms launch).  wide_from is the start of a cost class (score_class_scan_scatter_kernel),
+// any entry: the waves of 32 cover [0, wide_max) and those at or behind wide_from return at once; a hypothesis' kind of wave thus depends
+// on its class alone.
 // The kernel with wide waves needs 163 VGPRs: three waves per SIMD.
 template <bool ESTIMATE, int MASK_GROUP = 0, bool WIDE_WAVES = false>
 __global__ __launch_bounds__(256, WIDE_WAVES ? kWideOcc : SFM_MATRIX_OCC) void score_sed_matrix_kernel(
@@ -881,7 +825,7 @@ __global__ __launch_bounds__(256, WIDE_WAVES ? kWideOcc : SFM_MATRIX_OCC) void s
     // 32 over the entries [0, wide_from), the rest waves of 64 behind them
     // (a pair's wave indices [0, wide_max / 32) are waves of 32 — those at or behind wide_from have nothing to do —, the rest waves
     // of 64 from wide_from on; wide_from: what the sort left in the pair's word, anywhere in [0, wide_max])
-    // (wide_word == nullptr: every wave wide — the cost pre-pass of a measurement build)
+    // (wide_word == nullptr: every wave wide; no launch asks for that)
     int wide_from = WIDE_WAVES ? (wide_word != nullptr ? min(*wide_word, h_count) : 0) : h_count;   // (wave-uniform: a scalar load; a batch: set again below, per pair)
     const int narrow_waves = wide_max / kHyps;
     auto item = [&](int wave, int unit, unsigned item_id, int ranges) __attribute__((always_inline)) {

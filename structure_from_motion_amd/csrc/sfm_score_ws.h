@@ -155,3 +155,85 @@ __device__ __forceinline__ void prepare_small_block(const Corr* __restrict__ pts
 }
 
 }  // namespace sfmws
+
+namespace sfmhost {
+
+// Everything the scoring launches of ONE call do, decided before the first of them (plan_score, sfm_score.hip): the options,
+// loaded once; the kernel, ranges, order and launch grids; the workspace regions — after every size check has passed.
+// sfm_score_sed_ex and the fused passes plan once, run their own checks, and only then launch; sfm_score_workspace_bytes_ex
+// sizes the workspace by the same rule.
+struct ScorePlan {
+    int64_t n, h_count, batch;
+    double thr;
+    sfm_score_options opt;   // the call's options: the argument, or the process-wide defaults
+    bool exact;              // no workspace: score_sed_exact_kernel, nothing below applies
+    sfmws::WsPlan ws;        // matrix-pipe kernel or VALU filter; ranges of the points; recorded pre-pass
+    bool use_order;          // heaviest-first processing order (cost pre-pass + counting sort)
+    double a_scale;          // factor the prepared a-side coordinates carry
+    int per_unit;            // VALU filter: 64-point chunks per range; matrix-pipe kernel: steps of 32 points per range
+    // workspace regions (NULL where the plan has none)
+    unsigned char* workspace;
+    int32_t* buckets;
+    int32_t* order;
+    unsigned char* split;    // the ranges' partials (units > 1)
+    float4* partial;         // matrix-pipe kernel: per-block partial maxima of the points (in the fp32-point region it does not use)
+    uint4* table;            // ... the point operand table(s)
+    uint4* hyp_table;        // ... the hypotheses' operand rows
+    unsigned char* fix;      // ... the sample corrections
+    uint16_t* record;        // ... the reject words the cost pre-pass records for the scoring launch (ws.record)
+    struct {                 // VALU filter (ws.matrix == false)
+        int hpw;             // hypotheses per wave
+        bool one_sided;      // one-sided tier-1 test
+        unsigned prepare_blocks;   // score_prepare_kernel blocks per pair (1: that block stores the maxima, no zeroing needed for them)
+        unsigned blocks;     // blocks per pair of the cost pre-pass and (without ranges or block map) of the scoring kernel
+        int blocks_per_pair; // batches: blocks of a pair in the XCD-aware flat grid (0: plain (block, pair) grid)
+        dim3 scoring_grid;
+    } valu;
+    struct {                 // matrix-pipe kernel (ws.matrix)
+        unsigned setup_blocks;     // matrix_setup_kernel blocks per pair: as many partial maxima
+        int table_blocks;          // blocks of four steps that write a pair's point operand table
+        bool wide_waves;           // waves of 64 hypotheses behind the heaviest entries of the order (one pair only)
+        int wide_from_min, wide_from_max;   // where they may begin (0, 0: no wide waves)
+        int prepass_units, prepass_steps;   // cost pre-pass: ranges and steps per range of a wave
+        unsigned prepass_blocks;
+        int prepass_blocks_per_pair;
+        bool persistent;           // one pair: persistent waves (options.persistent)
+        unsigned scoring_blocks;   // (persistent: what the chip holds at once)
+        int blocks_per_pair;       // batches: blocks of a pair in the flat grid, its ranges included (0: one pair)
+    } matrix;
+    struct {                 // the scoring launch of sfm_ransac_pass_small (its own VALU-filter launch, one pair)
+        int hpw, sync_every;
+        unsigned blocks;
+        int prep_blocks;     // blocks of the fit launch that prepare the points (kPrepPoints each)
+        double a_scale;
+        int32_t* order;      // the scoring order the fit launch leaves, or NULL
+    } small;
+    // ranges a fused pass's selection launch folds: the matrix-pipe kernel's (the VALU filter folds its own behind its launch)
+    int deferred_units() const { return ws.matrix ? ws.units : 1; }
+};
+
+// The device arrays of a scoring call.
+struct ScoreArrays {
+    const double* corr;
+    const double* E;
+    const int32_t* S;
+    int32_t* cnt;
+    double* s1;
+    double* s2;
+    hipStream_t stream;
+};
+
+// fn: the entry point the error messages name.  workspace == NULL plans the exact kernel.
+int plan_score(const char* fn, int64_t n, int64_t h_count, int64_t batch, double thr, const sfm_score_options* options,
+               void* workspace, int64_t workspace_bytes, ScorePlan* plan);
+int launch_score(const ScorePlan& plan, const ScoreArrays& io);          // sfm_score_sed_ex
+int launch_small_score(const ScorePlan& plan, const ScoreArrays& io);    // the scoring launch of sfm_ransac_pass_small
+// The fused LARGE / batched passes: launch_large_setup — where the matrix-pipe kernel runs: partial maxima of the points and every
+// zeroing the pass needs (and a batch's point operand tables), in front of the fit launch, which writes the rest of the operand
+// tables (fit_eight_point_kernel's MatrixPrep) —, then launch_large_score: sfm_score_sed's remaining launches.  select_state: 16
+// words of the pass's selection launch the scoring launches zero (NULL: none); fold_in_selection: that launch folds the ranges of
+// the matrix-pipe kernel (plan.split, plan.fix) instead of a fold launch behind the scoring kernel.
+int launch_large_setup(const ScorePlan& plan, const ScoreArrays& io, unsigned* select_state);
+int launch_large_score(const ScorePlan& plan, const ScoreArrays& io, unsigned* select_state, bool fold_in_selection);
+
+}  // 

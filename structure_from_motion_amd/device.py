@@ -303,9 +303,11 @@ def ransac_pass_small(corr, S, E, flags, cnt, s1, s2, result, mask, workspace, t
 
 def ransac_pass_large(corr, S, E, flags, cnt, s1, s2, result, mask, workspace, thr: float, min_extra: float,
                       aggregation: int, h_offset: int = 0, philox=None, options: Optional[ScoreOptions] = None) -> None:
-    """One whole pass of a large problem (one pair) in eight launches instead of eighteen (``sfm_ransac_pass_large``): fit,
-    partial maxima + zeroing, both operand tables, cost pre-pass, class histogram, scan + scatter, the scoring kernel, fold of
-    the point ranges + selection + mask.  Arguments and outputs as ``ransac_pass_small``."""
+    """One whole pass of a large problem (one pair), ``sfm_ransac_pass_large``.  With the matrix-pipe scoring kernel, seven
+    launches: partial maxima + zeroing; the fit, whose lanes also write the hypotheses' operand rows and sample corrections and
+    whose extra blocks write the point operand table; cost pre-pass, class histogram, scan + scatter (these three only in cost
+    order); the scoring kernel; fold of the point ranges + selection + mask.  With the VALU filter: the fit, ``score_sed``'s
+    launches, the selection.  Arguments and outputs as ``ransac_pass_small``."""
     if philox is None:
         seed, seed_dev, use_philox, h_begin = 0, None, False, 0
     else:
@@ -563,7 +565,7 @@ class RansacWorkspace:
                               None if philox is None else (philox[0], philox[1]), options)
             return
         if large_pass_eligible(self.batch, self.n, self.h) and (not with_mask or h_offset == 0):
-            # eight launches instead of eighteen: setup and tables fused, the ranges folded inside the selection launch
+            # seven launches: the operand tables written by the fit launch, the ranges folded inside the selection launch
             ransac_pass_large(corr, self.S, self.E, self.flags, self.cnt, self.s1, self.s2, self.result,
                               self.mask if with_mask else None, self.score_ws, thr, min_extra, aggregation, h_offset,
                               None if philox is None else (philox[0], philox[1]), options)

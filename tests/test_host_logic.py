@@ -182,6 +182,47 @@ def test_argument_validation_without_gpu(native_lib):
     ws = C.c_void_p(0x10000)
     assert native_lib.sfm_score_sed_ex(p, n, p, p, h, 1, 1e-6, p, p, p, ws, small, None, forced) == -1
     assert b"workspace" in native_lib.sfm_last_error()
+    # Every plan — VALU filter with and without ranges; matrix-pipe kernel with one range, several, and the recorded pre-pass; a
+    # batch of either kernel; the small pass — with exactly sfm_score_workspace_bytes_ex bytes gets past every check, one byte fewer
+    # is refused: the size check and the launches use one plan.  Past the checks the call launches, which without a device is
+    # SFM_EHIP (-2); on a GPU box only the refusals run (the pointers are fake).
+    import torch
+
+    launches = not torch.cuda.is_available()
+
+    def sed(n, h, b, opts):
+        return lambda w: native_lib.sfm_score_sed_ex(p, n, p, p, h, b, 1e-6, p, p, p, ws, w, None, opts)
+
+    def large(n, h, opts):
+        return lambda w: native_lib.sfm_ransac_pass_large(1, None, 1, 0, p, n, h, 1e-6, 10.0, 3, 0, p, p, p, p, p, p, p, None, ws, w, None, opts)
+
+    def batched(n, h, b, opts):
+        return lambda w: native_lib.sfm_ransac_pass_batch(1, None, 1, 1, 0, p, n, h, b, 1e-6, 10.0, 3, p, p, p, p, p, p, p, None, ws, w,
+                                                          None, opts)
+
+    def small_pass(n, h, opts):
+        return lambda w: native_lib.sfm_ransac_pass_small(1, None, 1, 0, p, n, h, 1e-6, 10.0, 3, 0, p, p, p, p, p, p, p, None, ws, w, None, opts)
+
+    opt = lambda **kw: C.byref(_native.ScoreOptions(**kw))
+    plans = [(5_000, 10_000, 1, opt(), 1),                        # VALU filter, no ranges
+             (50_000, 100_000, 1, opt(kernel="filtered"), 1),     # VALU filter, 2 ranges
+             (50_000, 100_000, 1, opt(split=0), 2),               # matrix-pipe kernel, one range
+             (20_000, 40_000, 1, opt(), 2),                       # ... 10 ranges
+             (50_000, 100_000, 1, opt(), 2),                      # ... 8 ranges with the recorded pre-pass
+             (50_000, 100_000, 1, opt(persistent=1), 2),          # ... persistent waves
+             (10_000, 2_000, 4, opt(), 1),                        # a batch, VALU filter
+             (10_000, 2_000, 256, opt(), 2)]                      # a batch, matrix-pipe kernel (C5)
+    for n, h, b, opts, kernel in plans:
+        assert native_lib.sfm_score_kernel_choice_ex(n, h, b, opts) == kernel
+        calls = [sed(n, h, b, opts), batched(n, h, b, opts)] + ([large(n, h, opts)] if b == 1 else [])
+        if (n, h) == (5_000, 10_000):
+            calls.append(small_pass(n, h, opts))
+        need = native_lib.sfm_score_workspace_bytes_ex(n, h, b, opts)
+        for call in calls:
+            assert call(need - 1) == -1, (n, h, b)
+            assert b"workspace" in native_lib.sfm_last_error()
+            if launches:
+                assert call(need) == -2, (n, h, b, native_lib.sfm_last_error())
 
 
 def test_sizes_beyond_one_launch_are_refused(native_lib):
@@ -197,6 +238,15 @@ def test_sizes_beyond_one_launch_are_refused(native_lib):
     ws = C.c_void_p(0x10000)
     assert native_lib.sfm_score_sed(p, 50_000, p, p, big_h + 16, 1, 1e-6, p, p, p, ws, ws_bytes, None) == -1
     assert b"one launch" in native_lib.sfm_last_error()
+    # the fused passes plan their scoring launches before their first launch (the fit): 2 M points x 3 x 2^26 hypotheses need
+    # ranges of the points that one launch of the matrix-pipe kernel cannot cover, with any workspace
+    n, h = 2_000_000, 3 << 26
+    assert native_lib.sfm_ransac_pass_large(1, None, 1, 0, p, n, h, 1e-6, 10.0, 3, 0, p, p, p, p, p, p, p, None, ws, 1 << 60, None, None) == -1
+    assert b"one launch" in native_lib.sfm_last_error()
+    for batch in (1, 2):
+        assert native_lib.sfm_ransac_pass_batch(1, None, 1, 1, 0, p, n, h, batch, 1e-6, 10.0, 3, p, p, p, p, p, p, p, None, ws, 1 << 60,
+                                                None, None) == -1
+        assert b"one launch" in native_lib.sfm_last_error()
     assert native_lib.sfm_fit_eight_point(p, 100, p, 1 << 32, 1, p, p, None, None) == -1
     assert b"one launch" in native_lib.sfm_last_error()
     assert native_lib.sfm_sample_fit_philox(1, None, 1, 0, p, 100, 1 << 32, 1, p, p, p, None) == -1
