@@ -1,0 +1,101 @@
+"""Headless three-view structure from motion on synthetic data: the two-view pipeline on views 1 and 2
+(``estimate_essential_mat_with_ransac`` -> ``recover_r_t_from_e`` -> ``triangulate_points``), then view 3 registered against
+the triangulated points with ``estimate_pose_pnp_with_ransac``.  Points are projected directly (no images), a fraction of
+the view-2 and view-3 observations are replaced by random pixels, and the recovered pose of view 3 is compared with ground
+truth in the scale of the two-view reconstruction (|t_2| = 1).
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import random
+
+import numpy as np
+
+from lib.common.feature import Feature
+from lib.epipolar.eight_point import create_trivial_matches, recover_r_t_from_e
+from lib.epipolar.epipolar_ransac import estimate_essential_mat_with_ransac
+from lib.epipolar.triangulation import triangulate_points
+from lib.feature_matching.matching import Match
+from lib.pnp.pnp import estimate_pose_pnp_with_ransac
+from lib.transforms.transforms import Transform3D
+from structure_from_motion_amd import synthetic
+
+
+def three_view_scene(n: int = 400, seed: int = 11, outlier_fraction: float = 0.3, noise_px: float = 0.0):
+    """Points uniform in x, y in [-1, 1], z in [4, 6] (frame of camera 1 = [I | 0]); camera 2 and camera 3 at fixed poses.
+    Returns dict of pixel arrays pa, pb, pc (n, 2), K, and the ground-truth poses R2, t2, R3, t3."""
+    rng = np.random.default_rng(seed)
+    K = synthetic.BENCH_K
+    X = np.column_stack([rng.uniform(-1.0, 1.0, n), rng.uniform(-1.0, 1.0, n), rng.uniform(4.0, 6.0, n)])
+    R2, t2 = synthetic.rotation_xy(-5.0, -10.0), np.array([0.5, 0.05, 0.1])
+    R3, t3 = synthetic.rotation_xy(4.0, 9.0), np.array([-0.45, 0.12, 0.2])
+
+    def project(Xc):
+        uvw = Xc @ K.T
+        return uvw[:, :2] / uvw[:, 2:3] + rng.normal(0.0, noise_px, (len(Xc), 2))
+
+    def corrupt(p):
+        out = rng.random(n) < outlier_fraction
+        rand_px = np.column_stack([rng.uniform(0, 2 * K[0, 2], n), rng.uniform(0, 2 * K[1, 2], n)])
+        return np.where(out[:, None], rand_px, p)
+
+    pa = project(X)
+    pb = corrupt(project(X @ R2.T + t2))
+    pc = corrupt(project(X @ R3.T + t3))
+    return dict(pa=pa, pb=pb, pc=pc, K=K, X=X, R2=R2, t2=t2, R3=R3, t3=t3)
+
+
+def rotation_angle(Ra: np.ndarray, Rb: np.ndarray) -> float:
+    """Angle in radians of Ra Rb^T."""
+    c = (np.trace(Ra @ Rb.T) - 1.0) / 2.0
+    return float(np.arccos(np.clip(c, -1.0, 1.0)))
+
+
+def run(n: int = 400, seed: int = 11, outlier_fraction: float = 0.3, noise_px: float = 0.0, sed_threshold: float = 1.5e-6,
+        reprojection_threshold: float = 4.0, iterations: int = 2000) -> dict:
+    scene = three_view_scene(n, seed, outlier_fraction, noise_px)
+    K = scene["K"]
+    features_a = [Feature(float(x), float(y)) for x, y in scene["pa"]]
+    features_b = [Feature(float(x), float(y)) for x, y in scene["pb"]]
+    features_c = [Feature(float(x), float(y)) for x, y in scene["pc"]]
+    random.seed(seed)
+    # views 1-2: E, pose, triangulation of the cheirality survivors
+    e, inlier_pairs = estimate_essential_mat_with_ransac(
+        K, features_a, features_b, create_trivial_matches(n), sed_inlier_threshold=sed_threshold,
+        min_num_extra_inliers=10, max_iterations=iterations)
+    R2, t2, mask = recover_r_t_from_e(e, K, [p[0] for p in inlier_pairs], [p[1] for p in inlier_pairs])
+    kept = [inlier_pairs[i] for i in mask]
+    points = triangulate_points([p[0] for p in kept], [p[1] for p in kept], K, Transform3D.from_rmat_t(R2, t2))
+    # view 3: its features matched to the triangulated points (the observation of the same scene point)
+    index_of = {(f.x, f.y): i for i, f in enumerate(features_a)}
+    matches = [Match(a_index=k, b_index=index_of[(p[0].x, p[0].y)]) for k, p in enumerate(kept)]
+    R3, t3, inliers = estimate_pose_pnp_with_ransac(K, points, features_c, matches, reprojection_threshold,
+                                                    min_num_extra_inliers=10, max_iterations=iterations)
+    scale = np.linalg.norm(scene["t2"])
+    return {
+        "points": n,
+        "two_view_inliers": len(inlier_pairs),
+        "triangulated": len(kept),
+        "pnp_inliers": len(inliers),
+        "R2_error_rad": rotation_angle(R2, scene["R2"]),
+        "R3_error_rad": rotation_angle(R3, scene["R3"]),
+        "t3_error": float(np.linalg.norm(t3 - scene["t3"] / scale)),
+        "R3": R3.tolist(),
+        "t3": t3.tolist(),
+    }
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--points", type=int, default=400)
+    ap.add_argument("--seed", type=int, default=11)
+    ap.add_argument("--outliers", type=float, default=0.3)
+    ap.add_argument("--noise", type=float, default=0.0, help="pixel noise (standard deviation)")
+    ap.add_argument("--iterations", type=int, default=2000)
+    args = ap.parse_args()
+    print(json.dumps(run(args.points, args.seed, args.outliers, args.noise, iterations=args.iterations)))
+
+
+if __name__ == "__main__":
+    main()

@@ -56,7 +56,7 @@ typedef struct sfm_select_result {
 
 /* Version of this interface: libsfm_hip.so reports the one it was compiled from (sfm_abi_version), the Python binding
  * and the torch op library (sfm_torch_ops_abi_version) refuse a library of another version. */
-#define SFM_ABI_VERSION 12
+#define SFM_ABI_VERSION 13
 
 const char* sfm_last_error(void);
 int sfm_abi_version(void);
@@ -285,6 +285,51 @@ int sfm_fold_select_records_host(const sfm_select_result* gathered, int64_t worl
 int sfm_inlier_mask(const double* corr, int64_t n, const double* E, const int32_t* S, int64_t h_count,
                     int64_t batch, const sfm_select_result* result, double thr, uint8_t* mask,
                     void* stream);
+
+/* ---- RANSAC absolute pose (PnP) of a further view against triangulated points (csrc/sfm_pnp.hip) ----
+ * The reference's fit_with_ransac (ransac.py:55-86) with a six-item sample, a six-point DLT fitter and the squared
+ * reprojection error in pixels as the scorer.  pts: dev [batch,n,5] = {X, Y, Z, u, v}: a 3-D point in the frame of camera 1
+ * and the pixel of its match in the new view.  K: host [9], the camera matrix row-major; row 2 must be (0, 0, 1)
+ * (SFM_EINVAL otherwise).  S: dev int32 [batch,h_count,8], the sample tables of sfm_sample_philox / sfm_pyshuffle_table:
+ * the first 6 entries of each row are the sample (an entry outside [0, n) flags the hypothesis).  model: dev
+ * [batch,h_count,12] = R row-major (9) | t (3), x_cam = R X + t.  flags: dev int32 [batch,h_count], SFM_FIT_DEGENERATE when
+ * sigma_11 / sigma_1 of the conditioned 12 x 12 DLT matrix is below 1e-9 (coplanar or collinear points) or not a number.
+ * n >= 6 in every call. */
+
+/* Six-point DLT fit of every hypothesis: K-normalised 2-D side, 3-D side conditioned per sample (centroid, mean distance
+ * sqrt(3)), null vector by a 12 x 12 one-sided Jacobi SVD, conditioning undone, R = U V^T of M = [P]_{3x3} (sign of P
+ * flipped first if det M < 0), t = p4 / mean(singular values of M). */
+int sfm_pnp_fit(const double* pts, int64_t n, const int32_t* S, int64_t h_count, int64_t batch, const double* K, double* model,
+                int32_t* flags, void* stream);
+
+/* Philox sampling fused into the fit: hypothesis h of entry b uses the first 6 of philox_sample8(seed + b * seed_stride,
+ * h_begin + h), the sampler of sfm_sample_philox; all 8 are stored in S (-1 at positions >= n). */
+int sfm_pnp_sample_fit_philox(uint64_t seed, uint64_t seed_stride, int64_t h_begin, const double* pts, int64_t n,
+                              int64_t h_count, int64_t batch, const double* K, int32_t* S, double* model, int32_t* flags,
+                              void* stream);
+
+/* Scoring of all n items under all hypotheses: e = (p0/c2 - u)^2 + (p1/c2 - v)^2 with c = R X + t, p = K c (operation order
+ * fixed in sfm_pnp.hip), +inf when c2 <= 0.  cnt[b,h] = non-sample items with e <= thr; s1 / s2 = sums of e / e^2 over the
+ * 6 sample items plus those survivors.  All fp64, exact divisions: the values are the host scorer's bit for bit. */
+int sfm_pnp_score(const double* pts, int64_t n, const double* model, const int32_t* S, int64_t h_count, int64_t batch,
+                  const double* K, double thr, int32_t* cnt, double* s1, double* s2, void* stream);
+
+/* sfm_select_best with a six-item sample in the mean and RMS aggregates (count + 6); same record, same rules. */
+int sfm_pnp_select_best(const int32_t* cnt, const double* s1, const double* s2, const int32_t* flags, int64_t h_count,
+                        int64_t batch, double min_extra, int aggregation, int64_t h_offset, sfm_select_result* result,
+                        void* stream);
+
+/* Inlier mask of the selected model: 2 for the 6 sample items, 1 for other items with e <= thr, 0 otherwise (all 0 when the
+ * record holds no model).  `result` as written by sfm_pnp_select_best with h_offset 0.  mask: dev uint8 [batch,n]. */
+int sfm_pnp_inlier_mask(const double* pts, int64_t n, const double* model, const int32_t* S, int64_t h_count, int64_t batch,
+                        const double* K, const sfm_select_result* result, double thr, uint8_t* mask, void* stream);
+
+/* One whole PnP pass: fit (use_philox: sampled in the fit launch as sfm_pnp_sample_fit_philox, else from S), scoring,
+ * selection, and the mask when `mask` is not NULL — four launches, every size checked before the first. */
+int sfm_pnp_ransac_pass(uint64_t seed, uint64_t seed_stride, int use_philox, int64_t h_begin, const double* pts, int64_t n,
+                        int64_t h_count, int64_t batch, const double* K, double thr, double min_extra, int aggregation, int32_t* S,
+                        double* model, int32_t* flags, int32_t* cnt, double* s1, double* s2, sfm_select_result* result,
+                        uint8_t* mask, void* stream);
 
 /* SED of n correspondences under one E (sed.py:7-30).  E: dev [9]; out: dev [n]. */
 int sfm_sed_values(const double* corr, int64_t n, const double* E, double* out, void* stream);

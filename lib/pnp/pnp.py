@@ -1,0 +1,7 @@
+"""``lib.pnp.pnp``: RANSAC absolute pose (structure_from_motion_amd/pnp/pnp.py)."""
+from structure_from_motion_amd.pnp.pnp import (  # noqa: F401
+    PnPCalculationError,
+    calculate_reprojection_score,
+    estimate_pose_pnp_with_ransac,
+    pnp_model_fitter,
+)

@@ -341,8 +341,9 @@ SFM_DEVICE void unnormalise(const double (&fr)[3][3], const Hartley& t1, const H
 }
 
 // ransac.py:96-108 over the 8 sample points plus `count` extra inliers (sum1 = sum e, sum2 = sum e^2)
-SFM_DEVICE double aggregate_error(int aggregation, int count, double sum1, double sum2) {
-    const double nn = (double)(count + 8);
+// sample_size: points per sample (8 for the eight-point fit, 6 for the PnP fit): they enter the mean with the survivors
+SFM_DEVICE double aggregate_error(int aggregation, int count, double sum1, double sum2, int sample_size = 8) {
+    const double nn = (double)(count + sample_size);
     switch (aggregation) {
         case SFM_AGG_SUM: return sum1;
         case SFM_AGG_SQUARE: return sum2;

@@ -17,9 +17,9 @@ namespace sfmsel {
 constexpr uint64_t kNoModelKey = 0x7FFFFFFFFFFFFFFFull;
 
 SFM_DEVICE uint64_t hypothesis_key(const int32_t* cnt, const double* s1, const double* s2, const int32_t* flags,
-                                   int64_t h, double min_extra, int aggregation, bool& flagged) {
+                                   int64_t h, double min_extra, int aggregation, bool& flagged, int sample_size = 8) {
     const int ch = cnt[h];
-    const double err = sfmfit::aggregate_error(aggregation, ch, s1[h], s2[h]);
+    const double err = sfmfit::aggregate_error(aggregation, ch, s1[h], s2[h], sample_size);
     // Hypotheses whose sample was flagged degenerate never compete (the reference aborts on them).
     flagged = flags != nullptr && flags[h] != 0;
     // ransac.py:75 gate and :83 strict compare against an initial +inf: NaN and inf never win.
@@ -124,7 +124,7 @@ __device__ __forceinline__ int64_t block_select(const int32_t* __restrict__ cnt,
                                                 const double* __restrict__ s2, const int32_t* __restrict__ flags,
                                                 int64_t h_count, int64_t h_offset, double min_extra, int aggregation,
                                                 sfm_select_result* __restrict__ record, SelectScratch<THREADS>& sh,
-                                                int64_t* sh_winner) {
+                                                int64_t* sh_winner, int sample_size = 8) {
     uint64_t key = kNoModelKey;
     int64_t best = INT64_MAX, first_flag = INT64_MAX;
     int n_flag = 0;
@@ -136,7 +136,8 @@ __device__ __forceinline__ int64_t block_select(const int32_t* __restrict__ cnt,
         for (int u = 0; u < 4; ++u) {
             const int64_t h = h0 + u * THREADS;
             flagged[u] = false;
-            k[u] = h < h_count ? hypothesis_key(cnt, s1, s2, flags, h, min_extra, aggregation, flagged[u]) : kNoModelKey;
+            k[u] = h < h_count ? hypothesis_key(cnt, s1, s2, flags, h, min_extra, aggregation, flagged[u], sample_size)
+                               : kNoModelKey;
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {

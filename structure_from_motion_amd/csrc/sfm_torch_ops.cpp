@@ -6,7 +6,7 @@
 // select_best, inlier_mask, cheirality, triangulate — each in a functional form (allocates its outputs; has a Meta
 // kernel, so fake-tensor tracing / torch.compile / opcheck work) and, where the engine pre-allocates its buffers
 // (device.RansacWorkspace), an in-place `_`-suffixed form with mutable arguments, plus the fused
-// sample_fit_philox_.  The reference call sites these serve: apps/sfm.py:110-119 (RANSAC-E), :133-138 (pose),
+// sample_fit_philox_; and the PnP ops (sfm_pnp.hip) pnp_fit, pnp_score and the whole pass pnp_ransac_pass_.  The reference call sites these serve: apps/sfm.py:110-119 (RANSAC-E), :133-138 (pose),
 // :181-186 (triangulation).
 //
 // Built by structure_from_motion_amd/build.py into csrc/libsfm_torch_ops.so (host code only: no kernels here).
@@ -395,6 +395,116 @@ Tensor triangulate_meta(const Tensor& corr, const Tensor&, const Tensor&) {
     return at::empty_symint({corr.sym_size(0), 3}, corr.options());
 }
 
+
+// ---- PnP (sfm_pnp.hip): pts [batch, n, 5] = {X, Y, Z, u, v}, K 9 doubles (row-major, row 2 = 0 0 1), S [batch, h, 8],
+// model [batch, h, 12] = R (9) | t (3) ----------------------------------------------------------------------------------
+Dims pnp_dims(const Tensor& pts, const Tensor& S) {
+    TORCH_CHECK(pts.dim() == 3 && pts.size(2) == 5, "sfm_hip: pts must be [batch, n, 5]");
+    TORCH_CHECK(S.dim() == 3 && S.size(0) == pts.size(0) && S.size(2) == 8, "sfm_hip: S must be [batch, h, 8]");
+    return {pts.size(0), pts.size(1), S.size(1)};
+}
+
+void check_K(at::ArrayRef<double> K) { TORCH_CHECK(K.size() == 9, "sfm_hip: K must hold 9 doubles (3 x 3, row-major)"); }
+
+void check_model(const Tensor& model, const Dims& d) {
+    TORCH_CHECK(model.dim() == 3 && model.size(0) == d.batch && model.size(1) == d.h && model.size(2) == 12,
+                "sfm_hip: model must be [batch, h, 12]");
+}
+
+void pnp_fit_out(const Tensor& pts, const Tensor& S, at::ArrayRef<double> K, Tensor& model, Tensor& flags) {
+    const OpDevice scope(pts);
+    need(pts, "pts", at::kDouble);
+    need(S, "S", at::kInt);
+    need(model, "model", at::kDouble);
+    need(flags, "flags", at::kInt);
+    check_K(K);
+    const Dims d = pnp_dims(pts, S);
+    check_model(model, d);
+    TORCH_CHECK(flags.numel() == d.batch * d.h, "sfm_hip: flags must be [batch, h]");
+    ok(sfm_pnp_fit(ptr<double>(pts), d.n, ptr<int32_t>(S), d.h, d.batch, K.data(), ptr<double>(model), ptr<int32_t>(flags),
+                   current_stream()),
+       "sfm_pnp_fit");
+}
+
+std::tuple<Tensor, Tensor> pnp_fit(const Tensor& pts, const Tensor& S, at::ArrayRef<double> K) {
+    const Dims d = pnp_dims(pts, S);
+    Tensor model = at::empty({d.batch, d.h, 12}, like(pts, at::kDouble));
+    Tensor flags = at::empty({d.batch, d.h}, like(pts, at::kInt));
+    pnp_fit_out(pts, S, K, model, flags);
+    return {model, flags};
+}
+
+std::tuple<Tensor, Tensor> pnp_fit_meta(const Tensor& pts, const Tensor& S, at::ArrayRef<double>) {
+    TORCH_CHECK(pts.dim() == 3 && S.dim() == 3, "sfm_hip: pts [batch, n, 5], S [batch, h, 8]");
+    return {at::empty_symint({pts.sym_size(0), S.sym_size(1), 12}, like(pts, at::kDouble)),
+            at::empty_symint({pts.sym_size(0), S.sym_size(1)}, like(pts, at::kInt))};
+}
+
+void pnp_score_out(const Tensor& pts, const Tensor& model, const Tensor& S, at::ArrayRef<double> K, double thr, Tensor& cnt,
+                   Tensor& s1, Tensor& s2) {
+    const OpDevice scope(pts);
+    need(pts, "pts", at::kDouble);
+    need(model, "model", at::kDouble);
+    need(S, "S", at::kInt);
+    need(cnt, "cnt", at::kInt);
+    need(s1, "s1", at::kDouble);
+    need(s2, "s2", at::kDouble);
+    check_K(K);
+    const Dims d = pnp_dims(pts, S);
+    check_model(model, d);
+    TORCH_CHECK(cnt.numel() == d.batch * d.h && s1.numel() == d.batch * d.h && s2.numel() == d.batch * d.h,
+                "sfm_hip: cnt, s1, s2 must be [batch, h]");
+    ok(sfm_pnp_score(ptr<double>(pts), d.n, ptr<double>(model), ptr<int32_t>(S), d.h, d.batch, K.data(), thr, ptr<int32_t>(cnt),
+                     ptr<double>(s1), ptr<double>(s2), current_stream()),
+       "sfm_pnp_score");
+}
+
+std::tuple<Tensor, Tensor, Tensor> pnp_score(const Tensor& pts, const Tensor& model, const Tensor& S, at::ArrayRef<double> K,
+                                             double thr) {
+    const Dims d = pnp_dims(pts, S);
+    Tensor cnt = at::empty({d.batch, d.h}, like(pts, at::kInt));
+    Tensor s1 = at::empty({d.batch, d.h}, like(pts, at::kDouble));
+    Tensor s2 = at::empty({d.batch, d.h}, like(pts, at::kDouble));
+    pnp_score_out(pts, model, S, K, thr, cnt, s1, s2);
+    return {cnt, s1, s2};
+}
+
+std::tuple<Tensor, Tensor, Tensor> pnp_score_meta(const Tensor& pts, const Tensor&, const Tensor& S, at::ArrayRef<double>,
+                                                  double) {
+    TORCH_CHECK(pts.dim() == 3 && S.dim() == 3, "sfm_hip: pts [batch, n, 5], S [batch, h, 8]");
+    return {at::empty_symint({pts.sym_size(0), S.sym_size(1)}, like(pts, at::kInt)),
+            at::empty_symint({pts.sym_size(0), S.sym_size(1)}, like(pts, at::kDouble)),
+            at::empty_symint({pts.sym_size(0), S.sym_size(1)}, like(pts, at::kDouble))};
+}
+
+// the whole pass into the caller's buffers (device.PnPWorkspace); `mask` optional
+void pnp_ransac_pass_out(const Tensor& pts, int64_t seed, int64_t seed_stride, bool use_philox, int64_t h_begin,
+                         at::ArrayRef<double> K, double thr, double min_extra, int64_t aggregation, Tensor& S, Tensor& model,
+                         Tensor& flags, Tensor& cnt, Tensor& s1, Tensor& s2, Tensor& result, const std::optional<Tensor>& mask) {
+    const OpDevice scope(pts);
+    need(pts, "pts", at::kDouble);
+    need(S, "S", at::kInt);
+    need(model, "model", at::kDouble);
+    need(flags, "flags", at::kInt);
+    need(cnt, "cnt", at::kInt);
+    need(s1, "s1", at::kDouble);
+    need(s2, "s2", at::kDouble);
+    need(result, "result", at::kLong);
+    if (mask.has_value()) need(*mask, "mask", at::kByte);
+    check_K(K);
+    const Dims d = pnp_dims(pts, S);
+    check_model(model, d);
+    TORCH_CHECK(flags.numel() == d.batch * d.h && cnt.numel() == d.batch * d.h && s1.numel() == d.batch * d.h &&
+                    s2.numel() == d.batch * d.h,
+                "sfm_hip: flags, cnt, s1, s2 must be [batch, h]");
+    TORCH_CHECK(result.numel() == d.batch * kRecordWords, "sfm_hip: result must be int64 [batch, 5]");
+    TORCH_CHECK(!mask.has_value() || mask->numel() == d.batch * d.n, "sfm_hip: mask must be uint8 [batch, n]");
+    ok(sfm_pnp_ransac_pass((uint64_t)seed, (uint64_t)seed_stride, use_philox ? 1 : 0, h_begin, ptr<double>(pts), d.n, d.h, d.batch,
+                           K.data(), thr, min_extra, (int)aggregation, ptr<int32_t>(S), ptr<double>(model), ptr<int32_t>(flags),
+                           ptr<int32_t>(cnt), ptr<double>(s1), ptr<double>(s2),
+                           reinterpret_cast<sfm_select_result*>(ptr<int64_t>(result)), ptr<uint8_t>(mask), current_stream()),
+       "sfm_pnp_ransac_pass");
+}
 }  // namespace
 
 // the C-ABI version this op library was compiled against (include/sfm_hip.h); ops.load() compares it with the
@@ -426,6 +536,14 @@ TORCH_LIBRARY(sfm_hip, m) {
     m.def("inlier_mask_(Tensor corr, Tensor E, Tensor S, Tensor result, float thr, Tensor(a!) mask) -> ()");
     m.def("cheirality(Tensor corr, Tensor pose_rt, float distance_threshold) -> Tensor");
     m.def("triangulate(Tensor corr, Tensor P1, Tensor P2) -> Tensor");
+    m.def("pnp_fit(Tensor pts, Tensor S, float[] K) -> (Tensor, Tensor)");
+    m.def("pnp_fit_(Tensor pts, Tensor S, float[] K, Tensor(a!) model, Tensor(b!) flags) -> ()");
+    m.def("pnp_score(Tensor pts, Tensor model, Tensor S, float[] K, float thr) -> (Tensor, Tensor, Tensor)");
+    m.def("pnp_score_(Tensor pts, Tensor model, Tensor S, float[] K, float thr, Tensor(a!) cnt, Tensor(b!) s1, "
+          "Tensor(c!) s2) -> ()");
+    m.def("pnp_ransac_pass_(Tensor pts, int seed, int seed_stride, bool use_philox, int h_begin, float[] K, float thr, "
+          "float min_extra, int aggregation, Tensor(a!) S, Tensor(b!) model, Tensor(c!) flags, Tensor(d!) cnt, Tensor(e!) s1, "
+          "Tensor(f!) s2, Tensor(g!) result, Tensor(h!)? mask) -> ()");
 }
 
 // ROCm devices dispatch under torch's "CUDA" key (the name of the dispatch key, not a CUDA code path)
@@ -445,6 +563,11 @@ TORCH_LIBRARY_IMPL(sfm_hip, CUDA, m) {
     m.impl("inlier_mask_", &inlier_mask_out);
     m.impl("cheirality", &cheirality);
     m.impl("triangulate", &triangulate);
+    m.impl("pnp_fit", &pnp_fit);
+    m.impl("pnp_fit_", &pnp_fit_out);
+    m.impl("pnp_score", &pnp_score);
+    m.impl("pnp_score_", &pnp_score_out);
+    m.impl("pnp_ransac_pass_", &pnp_ransac_pass_out);
 }
 
 // sample_philox has no tensor argument to dispatch on: registered for every backend, it checks its device itself
@@ -463,6 +586,10 @@ void ransac_pass_small_out_meta(const Tensor&, int64_t, const std::optional<Tens
 void select_best_out_meta(const Tensor&, const Tensor&, const Tensor&, const std::optional<Tensor>&, double, int64_t,
                           int64_t, Tensor&) {}
 void inlier_mask_out_meta(const Tensor&, const Tensor&, const Tensor&, const Tensor&, double, Tensor&) {}
+void pnp_fit_out_meta(const Tensor&, const Tensor&, at::ArrayRef<double>, Tensor&, Tensor&) {}
+void pnp_score_out_meta(const Tensor&, const Tensor&, const Tensor&, at::ArrayRef<double>, double, Tensor&, Tensor&, Tensor&) {}
+void pnp_ransac_pass_out_meta(const Tensor&, int64_t, int64_t, bool, int64_t, at::ArrayRef<double>, double, double, int64_t, Tensor&,
+                              Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, const std::optional<Tensor>&) {}
 
 TORCH_LIBRARY_IMPL(sfm_hip, Meta, m) {
     m.impl("normalize_coords_", &normalize_coords_out_meta);
@@ -480,4 +607,9 @@ TORCH_LIBRARY_IMPL(sfm_hip, Meta, m) {
     m.impl("inlier_mask", &inlier_mask_meta);
     m.impl("cheirality", &cheirality_meta);
     m.impl("triangulate", &triangulate_meta);
+    m.impl("pnp_fit", &pnp_fit_meta);
+    m.impl("pnp_score", &pnp_score_meta);
+    m.impl("pnp_fit_", &pnp_fit_out_meta);
+    m.impl("pnp_score_", &pnp_score_out_meta);
+    m.impl("pnp_ransac_pass_", &pnp_ransac_pass_out_meta);
 }

@@ -610,3 +610,110 @@ def ransac_essential(corr: torch.Tensor, S, thr: float, min_extra: float, aggreg
     ws.S.copy_(S_t.reshape(1, h, 8))
     ws.run(corr.reshape(1, n, 4), thr, min_extra, aggregation)
     return ws.outcome(0)
+
+
+# ------------------------------------------------------------------------------------------------------
+# RANSAC absolute pose (PnP, csrc/sfm_pnp.hip): pts [B,N,5] = {X, Y, Z, u, v}, K (3,3) with row 2 = (0, 0, 1),
+# S [B,H,8] (first 6 entries used), model [B,H,12] = R (9) | t (3)
+# ------------------------------------------------------------------------------------------------------
+def _camera_list(K) -> List[float]:
+    K = np.asarray(K, dtype=np.float64)
+    if K.shape != (3, 3):
+        raise ValueError(f"camera matrix must be 3x3, got shape {K.shape}")
+    return [float(v) for v in K.reshape(9)]
+
+
+def pnp_fit(pts: torch.Tensor, S: torch.Tensor, K, model=None, flags=None):
+    """Six-point DLT fit of every hypothesis -> model [B,H,12], flags [B,H] (SFM_FIT_DEGENERATE)."""
+    op = ops.load()
+    if model is None and flags is None:
+        return op.pnp_fit(pts, S, _camera_list(K))
+    B, H = S.shape[0], S.shape[1]
+    if model is None:
+        model = torch.empty((B, H, 12), dtype=F64, device=pts.device)
+    if flags is None:
+        flags = torch.empty((B, H), dtype=torch.int32, device=pts.device)
+    op.pnp_fit_(pts, S, _camera_list(K), model, flags)
+    return model, flags
+
+
+def pnp_score(pts: torch.Tensor, model: torch.Tensor, S: torch.Tensor, K, thr: float, cnt=None, s1=None, s2=None):
+    """Per hypothesis (extra-inlier count, sum e, sum e^2) of the squared reprojection error e."""
+    op = ops.load()
+    if cnt is None and s1 is None and s2 is None:
+        return op.pnp_score(pts, model, S, _camera_list(K), float(thr))
+    op.pnp_score_(pts, model, S, _camera_list(K), float(thr), cnt, s1, s2)
+    return cnt, s1, s2
+
+
+def pnp_select_best(cnt, s1, s2, flags, min_extra: float, aggregation: int, h_offset: int = 0, out=None):
+    """sfm_pnp_select_best (six-item samples in the mean) -> int64 tensor [B,5] viewing sfm_select_result records."""
+    lib = _native.load()
+    B, H = cnt.shape
+    if out is None:
+        out = torch.empty((B, SELECT_BYTES // 8), dtype=torch.int64, device=cnt.device)
+    check(lib.sfm_pnp_select_best(_ptr(cnt), _ptr(s1), _ptr(s2), _ptr(flags), H, B, float(min_extra), int(aggregation),
+                                  h_offset, _ptr(out), _stream()), "sfm_pnp_select_best")
+    return out
+
+
+def pnp_inlier_mask(pts, model, S, K, result, thr: float, out=None):
+    """uint8 [B,N]: 2 sample point of the winner, 1 other inlier, 0 outlier."""
+    lib = _native.load()
+    B, N, _ = pts.shape
+    if out is None:
+        out = torch.empty((B, N), dtype=torch.uint8, device=pts.device)
+    Kc = (C.c_double * 9)(*_camera_list(K))
+    check(lib.sfm_pnp_inlier_mask(_ptr(pts), N, _ptr(model), _ptr(S), S.shape[1], B, C.cast(Kc, C.c_void_p), _ptr(result),
+                                  float(thr), _ptr(out), _stream()), "sfm_pnp_inlier_mask")
+    return out
+
+
+@dataclass
+class PnPOutcome:
+    best_h: int                # winning hypothesis, -1 if none
+    error: float               # aggregated inlier error of the winner
+    R: Optional[np.ndarray]    # (3,3) of the winner
+    t: Optional[np.ndarray]    # (3,)
+    sample: Optional[np.ndarray]   # (6,) indices of the winner's sample, in sample order
+    mask: Optional[np.ndarray]     # (N,) uint8: 1 survivor, 2 sample point, 0 outlier
+    n_flagged: int             # hypotheses whose sample was degenerate
+    first_flagged: int         # lowest such hypothesis index, or -1
+    extra_inliers: int
+
+
+class PnPWorkspace:
+    """Pre-allocated device buffers of a PnP pass for B views x H hypotheses x N 2D-3D pairs (as RansacWorkspace)."""
+
+    def __init__(self, batch: int, n: int, h: int, device=None):
+        dev = device or require_gpu()
+        self.batch, self.n, self.h = batch, n, h
+        self.S = torch.empty((batch, h, 8), dtype=torch.int32, device=dev)
+        self.model = torch.empty((batch, h, 12), dtype=F64, device=dev)
+        self.flags = torch.empty((batch, h), dtype=torch.int32, device=dev)
+        self.cnt = torch.empty((batch, h), dtype=torch.int32, device=dev)
+        self.s1 = torch.empty((batch, h), dtype=F64, device=dev)
+        self.s2 = torch.empty((batch, h), dtype=F64, device=dev)
+        self.result = torch.empty((batch, SELECT_BYTES // 8), dtype=torch.int64, device=dev)
+        self.mask = torch.empty((batch, n), dtype=torch.uint8, device=dev)
+
+    def run(self, pts: torch.Tensor, K, thr: float, min_extra: float, aggregation: int, with_mask: bool = True,
+            philox=None) -> None:
+        """fit + score + select (+ mask) in one call (``sfm_pnp_ransac_pass``) for the sample table in ``self.S`` — or, with
+        ``philox=(seed, h_begin, seed_stride)``, for Philox samples drawn inside the fit launch (which also fills ``self.S``)."""
+        seed, h_begin, stride = (0, 0, 1) if philox is None else philox
+        ops.load().pnp_ransac_pass_(pts, _as_int64(seed), _as_int64(stride), philox is not None, h_begin, _camera_list(K),
+                                    float(thr), float(min_extra), int(aggregation), self.S, self.model, self.flags, self.cnt,
+                                    self.s1, self.s2, self.result, self.mask if with_mask else None)
+
+    def outcome(self, b: int = 0) -> PnPOutcome:
+        rec = read_select(self.result)[b]
+        first = -1 if rec.first_flagged == _native.INT64_MAX else int(rec.first_flagged)
+        if rec.best_h < 0:
+            return PnPOutcome(-1, float("inf"), None, None, None, None, int(rec.n_flagged), first, 0)
+        h = int(rec.best_h)
+        m = self.model[b, h].cpu().numpy()
+        sample = self.S[b, h, :6].cpu().numpy().astype(np.int64)
+        mask = checked_mask(self.mask[b].cpu().numpy().copy())
+        return PnPOutcome(h, float(rec.best_err), m[:9].reshape(3, 3).copy(), m[9:].copy(), sample, mask,
+                          int(rec.n_flagged), first, int(rec.best_cnt))

@@ -1,0 +1,71 @@
+"""Device route of fit_with_ransac for PnP items ((X, Feature) pairs): host glue around device.PnPWorkspace."""
+from __future__ import annotations
+
+import copy
+import logging
+import os
+import random
+
+import numpy as np
+
+from .. import device
+from ..epipolar._engine import degenerate_policy, sampler_name
+
+logger = logging.getLogger(__name__)
+
+
+def item_array(data) -> np.ndarray:
+    """(len, 5) float64 {X, Y, Z, u, v} of (X, Feature) items."""
+    n = len(data)
+    out = np.empty((n, 5), dtype=np.float64)
+    if n:
+        out[:, :3] = np.array([np.asarray(item[0], dtype=np.float64).reshape(3) for item in data])
+        out[:, 3] = np.fromiter((item[1].x for item in data), dtype=np.float64, count=n)
+        out[:, 4] = np.fromiter((item[1].y for item in data), dtype=np.float64, count=n)
+    return out
+
+
+def ransac_pnp_items(data, camera_matrix, threshold, min_extra, aggregation, iterations):
+    """Returns ((R, t) or None, inlier items) with the semantics of ransac._host_loop: sample ``pyshuffle`` (default) replays
+    the reference's cumulative ``random.shuffle`` and advances the global ``random`` state; ``philox`` draws on the device
+    (seed ``SFM_SEED`` or 64 bits of ``random``).  Inliers come back as deep copies, the sample first, then the survivors
+    in the order of the shuffled list (``philox``: index order)."""
+    from .pnp import SAMPLE_SIZE, PnPCalculationError, check_camera_matrix
+
+    n = len(data)
+    if iterations <= 0:
+        return None, []
+    if n < SAMPLE_SIZE:
+        raise ValueError("Six 2D-3D pairs are expected.")
+    K = check_camera_matrix(camera_matrix)
+    dev = device.require_gpu()
+    pts = device.to_device(item_array(data)).reshape(1, n, 5)
+    ws = device.PnPWorkspace(1, n, iterations, dev)
+    sampler = sampler_name(n, iterations)
+    table = None
+    if sampler == "pyshuffle":
+        table = device.PyShuffleTable(n, iterations, random, advance=True)
+        ws.S.copy_(device.to_device(table.S, dtype=ws.S.dtype).reshape(1, iterations, 8))
+        ws.run(pts, K, threshold, min_extra, aggregation)
+    else:
+        seed = int(os.environ["SFM_SEED"]) if "SFM_SEED" in os.environ else random.getrandbits(64)
+        ws.run(pts, K, threshold, min_extra, aggregation, philox=(seed, 0, 1))
+    outcome = ws.outcome(0)
+    if outcome.n_flagged and degenerate_policy() == "raise":
+        raise PnPCalculationError(
+            "The six 3-D points of a sample are coplanar or collinear: cannot estimate the pose."
+            f" (hypothesis {outcome.first_flagged}, {outcome.n_flagged} in total)")
+    if logger.isEnabledFor(logging.DEBUG):
+        logger.debug("RANSAC-PnP: %d pairs x %d hypotheses (%s sampler): best hypothesis %d, %d extra inliers, "
+                     "aggregated error %.6g, %d degenerate sample(s)", n, iterations, sampler, outcome.best_h,
+                     outcome.extra_inliers, outcome.error, outcome.n_flagged)
+    if outcome.best_h < 0:
+        return None, []
+    survivors = outcome.mask == 1
+    if sampler == "pyshuffle":
+        perm = table.permutation_after(outcome.best_h)
+        rest = perm[SAMPLE_SIZE:]
+        order = np.concatenate([perm[:SAMPLE_SIZE], rest[survivors[rest]]])
+    else:
+        order = np.concatenate([outcome.sample, np.nonzero(survivors)[0]])
+    return (outcome.R, outcome.t), [copy.deepcopy(data[i]) for i in order.tolist()]

@@ -1,0 +1,139 @@
+"""RANSAC absolute pose (PnP): register a further view against 3-D points that are already triangulated.
+
+Data items are ``(X, f)`` pairs: ``X`` a 3-D point (length-3 float array) in the frame of camera 1, ``f`` the ``Feature`` of
+its match in the new image, in pixels.  The model is ``(R, t)`` with ``x_cam = R X + t`` — the convention of
+``recover_r_t_from_e`` and ``Transform3D.from_rmat_t``.  The RANSAC contract is the reference's ``fit_with_ransac``
+(``lib/ransac/ransac.py``) with a six-item sample: ``estimate_pose_pnp_with_ransac`` passes the tagged fitter / scorer
+below, which ``fit_with_ransac`` routes to the HIP kernels of ``csrc/sfm_pnp.hip``; the same call with untagged callables
+runs on the host.
+"""
+from __future__ import annotations
+
+from functools import partial
+from typing import Sequence, Tuple
+
+import numpy as np
+import numpy.typing as npt
+
+from ..common.feature import Feature
+from ..epipolar import _engine
+from ..feature_matching.matching import Match
+from ..ransac.ransac import ErrorAggregationMethod, fit_with_ransac
+
+PnPItem = Tuple[npt.NDArray, Feature]
+PnPModel = Tuple[npt.NDArray, npt.NDArray]
+
+SAMPLE_SIZE = 6
+# sigma_11 / sigma_1 of the conditioned 12 x 12 DLT matrix below this: the sample is degenerate (coplanar or collinear
+# points have three or more null vectors).  The same floor as kPnPDegenerateFloor of csrc/sfm_pnp.hip.
+DEGENERATE_FLOOR = 1e-9
+
+
+class PnPCalculationError(Exception):
+    """Raised when a sampled six-tuple is degenerate (like EightPointCalculationError for the essential matrix)."""
+
+
+def check_camera_matrix(camera_matrix) -> npt.NDArray:
+    """K as a float64 (3, 3) array; row 2 must be (0, 0, 1) (the scorer's p_2 = c_2)."""
+    K = np.asarray(camera_matrix, dtype=np.float64)
+    if K.shape != (3, 3):
+        raise ValueError(f"camera matrix must be 3x3, got shape {K.shape}")
+    if not np.array_equal(K[2], [0.0, 0.0, 1.0]):
+        raise ValueError("row 2 of the camera matrix must be (0, 0, 1)")
+    return K
+
+
+def pnp_model_fitter(items: Sequence[PnPItem], camera_matrix: npt.NDArray) -> PnPModel:
+    """(R, t) from exactly six 2D-3D pairs by the six-point DLT (the RANSAC model fitter; host form).
+
+    K-normalised 2-D side; the 3-D side conditioned (centroid subtracted, mean distance sqrt(3)); the null vector of the
+    12 x 12 system A p = 0 as P = [M | p4]; conditioning undone; P negated if det(M) < 0; R = U V^T of M = U S V^T;
+    t = p4 / mean(S).  Raises PnPCalculationError for a degenerate sample (see DEGENERATE_FLOOR)."""
+    if len(items) != SAMPLE_SIZE:
+        raise ValueError("Six 2D-3D pairs are expected.")
+    K = np.asarray(camera_matrix, dtype=np.float64)
+    fx, fy, cx, cy = K[0][0], K[1][1], K[0][2], K[1][2]
+    X = np.array([np.asarray(item[0], dtype=np.float64).reshape(3) for item in items])
+    x = np.array([(item[1].x - cx) / fx for item in items])
+    y = np.array([(item[1].y - cy) / fy for item in items])
+    centroid = X.mean(axis=0)
+    scale = np.sqrt(3.0) / np.linalg.norm(X - centroid, axis=1).mean()
+    Xh = np.hstack([(X - centroid) * scale, np.ones((SAMPLE_SIZE, 1))])
+    A = np.zeros((2 * SAMPLE_SIZE, 12))
+    A[0::2, 0:4] = Xh
+    A[0::2, 8:12] = -x[:, None] * Xh
+    A[1::2, 4:8] = Xh
+    A[1::2, 8:12] = -y[:, None] * Xh
+    _, sigma, vt = np.linalg.svd(A)
+    if not sigma[10] / sigma[0] >= DEGENERATE_FLOOR:
+        raise PnPCalculationError("The six 3-D points of the sample are coplanar or collinear: cannot estimate the pose.")
+    P = vt[-1].reshape(3, 4)
+    M = scale * P[:, :3]
+    p4 = P[:, 3] - M @ centroid
+    if np.linalg.det(M) < 0:
+        M, p4 = -M, -p4
+    u, s, wt = np.linalg.svd(M)
+    return u @ wt, p4 / s.mean()
+
+
+def calculate_reprojection_score(model: PnPModel, item: PnPItem, camera_matrix: npt.NDArray) -> float:
+    """Squared reprojection error in pixels of one 2D-3D pair under (R, t) (the RANSAC scorer); +inf for a point behind the
+    camera (c_z <= 0).  Operation order fixed as in csrc/sfm_pnp.hip (pnp_score), so the device value is this one bit for bit."""
+    R, t = model
+    R = np.asarray(R, dtype=np.float64).tolist()
+    t = np.asarray(t, dtype=np.float64).tolist()
+    K = np.asarray(camera_matrix, dtype=np.float64).tolist()
+    X, Y, Z = (float(v) for v in np.asarray(item[0], dtype=np.float64).reshape(3))
+    c0 = ((R[0][0] * X + R[0][1] * Y) + R[0][2] * Z) + t[0]
+    c1 = ((R[1][0] * X + R[1][1] * Y) + R[1][2] * Z) + t[1]
+    c2 = ((R[2][0] * X + R[2][1] * Y) + R[2][2] * Z) + t[2]
+    if c2 <= 0.0:
+        return float("inf")
+    p0 = (K[0][0] * c0 + K[0][1] * c1) + K[0][2] * c2
+    p1 = (K[1][0] * c0 + K[1][1] * c1) + K[1][2] * c2
+    du = p0 / c2 - float(item[1].x)
+    dv = p1 / c2 - float(item[1].y)
+    return du * du + dv * dv
+
+
+# fit_with_ransac recognises partials of these two (with model_fit_data_count == 6) and runs the whole loop on the GPU.
+pnp_model_fitter._sfm_hip_role = "pnp_fitter"
+calculate_reprojection_score._sfm_hip_role = "reprojection_scorer"
+
+
+def estimate_pose_pnp_with_ransac(
+    camera_matrix: npt.NDArray,
+    points_3d: Sequence[npt.NDArray],
+    features: Sequence[Feature],
+    matches: Sequence[Match],
+    reprojection_threshold: float,
+    min_num_extra_inliers: int | None = None,
+    error_aggregation_method: ErrorAggregationMethod | None = None,
+    max_iterations: int | None = None,
+) -> Tuple[npt.NDArray, npt.NDArray, list]:
+    """Pose (R, t) of a further view from 2D-3D matches with RANSAC over six-point DLT hypotheses.
+
+    ``matches[i].a_index`` indexes ``points_3d`` and ``b_index`` indexes ``features`` (pixels of the new view).  A pair is an
+    inlier when its squared reprojection error is at most ``reprojection_threshold`` (pixels squared).  Returns
+    ``(R, t, inlier (X, Feature) pairs)``.  Raises ``ValueError`` for fewer than six matches, a malformed camera matrix or
+    when no hypothesis has enough inliers, and ``PnPCalculationError`` when a sampled six-tuple is degenerate
+    (``SFM_DEGENERATE=skip`` ignores such hypotheses instead)."""
+    K = check_camera_matrix(camera_matrix)
+    if len(matches) < SAMPLE_SIZE:
+        raise ValueError(f"At least six 2D-3D matches are expected, got {len(matches)}.")
+    with _engine.gc_paused():
+        items = [(np.asarray(points_3d[m.a_index], dtype=np.float64).reshape(3), features[m.b_index]) for m in matches]
+        model, inliers = fit_with_ransac(
+            items,
+            model_fit_data_count=SAMPLE_SIZE,
+            model_fitter=partial(pnp_model_fitter, camera_matrix=K),
+            inlier_scorer=partial(calculate_reprojection_score, camera_matrix=K),
+            inlier_threshold=reprojection_threshold,
+            min_num_extra_inliers=min_num_extra_inliers,
+            error_aggregation_method=error_aggregation_method,
+            max_iterations=max_iterations,
+        )
+    if model is None:
+        raise ValueError("Could not estimate the pose with RANSAC.")
+    R, t = model
+    return R, t, inliers

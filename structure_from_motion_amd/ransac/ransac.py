@@ -5,7 +5,8 @@ Two execution routes behind one signature:
 * when ``model_fitter`` / ``inlier_scorer`` are the eight-point fitter and SED scorer of
   ``epipolar_ransac`` (which is what ``estimate_essential_mat_with_ransac`` passes, exactly like the
   reference's ``epipolar_ransac.py:58-67``), the whole loop — fit, H x N scoring, gate, aggregation,
-  selection — runs as HIP kernels on the MI355X (``device.RansacWorkspace``);
+  selection — runs as HIP kernels on the MI355X (``device.RansacWorkspace``); likewise for the six-point PnP fitter
+  and reprojection scorer of ``pnp.pnp`` with ``model_fit_data_count == 6`` (``device.PnPWorkspace``);
 * for arbitrary Python callables (e.g. the 2-point line fitter of the reference's own
   ``test_ransac.py``) the loop is host logic: there is nothing to put on a GPU.
 
@@ -22,7 +23,7 @@ import os
 import random
 from enum import Enum
 from math import inf, sqrt
-from typing import Any, Callable, Optional, Sequence, Tuple
+from typing import Any, Callable, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -65,7 +66,12 @@ def fit_with_ransac(
     min_extra = 0 if min_num_extra_inliers is None else min_num_extra_inliers
 
     spec = _device_spec(model_fitter, inlier_scorer, model_fit_data_count)
-    if spec is not None:
+    if isinstance(spec, PnPDeviceSpec):
+        from ..pnp import _engine as pnp_engine
+
+        model, inliers = pnp_engine.ransac_pnp_items(
+            data, spec.camera_matrix, inlier_threshold, min_extra, aggregation_code(method), iterations)
+    elif spec is not None:
         from ..epipolar import _engine
 
         model, inliers = _engine.ransac_feature_pairs(
@@ -80,11 +86,28 @@ def fit_with_ransac(
     return model, inliers
 
 
+class PnPDeviceSpec(NamedTuple):
+    """Device route of the six-point PnP fitter / reprojection scorer pair."""
+    camera_matrix: np.ndarray
+
+
 def _device_spec(model_fitter, inlier_scorer, model_fit_data_count):
-    """Camera matrix if (fitter, scorer) are partials of the eight-point / SED pair, else None."""
+    """Camera matrix if (fitter, scorer) are partials of the eight-point / SED pair, a PnPDeviceSpec if they are partials
+    of the PnP fitter / reprojection scorer with a six-item sample (and one camera matrix), else None."""
     fit_fn = getattr(model_fitter, "func", None)
     score_fn = getattr(inlier_scorer, "func", None)
-    if fit_fn is None or score_fn is None or model_fit_data_count != 8:
+    if fit_fn is None or score_fn is None:
+        return None
+    if (getattr(fit_fn, "_sfm_hip_role", None) == "pnp_fitter"
+            and getattr(score_fn, "_sfm_hip_role", None) == "reprojection_scorer"):
+        if model_fit_data_count != 6:
+            return None
+        k_fit = model_fitter.keywords.get("camera_matrix") if not model_fitter.args else None
+        k_score = inlier_scorer.keywords.get("camera_matrix") if not inlier_scorer.args else None
+        if k_fit is None or k_score is None or not np.array_equal(np.asarray(k_fit), np.asarray(k_score)):
+            return None
+        return PnPDeviceSpec(np.asarray(k_fit, dtype=np.float64))
+    if model_fit_data_count != 8:
         return None
     if not getattr(fit_fn, "_sfm_hip_role", None) == "eight_point_fitter":
         return None

@@ -1,0 +1,86 @@
+"""PnP pass throughput: milliseconds per whole pass (fit, score, select, mask: ``sfm_pnp_ransac_pass``) and evaluations per
+second (points x hypotheses / time) at 50 000 x 100 000 and 5 000 x 10 000, one JSON line per size.
+
+``--profile DIR`` instead re-runs this script (one size per run, under ``timeout``) below ``rocprofv3 --kernel-trace --stats``
+and prints the per-kernel split of its stats file.  Sizes: ``--sizes 50000x100000,5000x10000``."""
+import argparse
+import csv
+import glob
+import json
+import os
+import subprocess
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+sys.path.insert(0, os.path.join(REPO, "tests"))
+
+SIZES = "50000x100000,5000x10000"
+
+
+def time_pass(n: int, h: int, steps: int, warmup: int) -> dict:
+    import torch
+
+    import pnp_oracle as orc
+    from structure_from_motion_amd import device, synthetic
+    from structure_from_motion_amd._native import AGG_RMS
+
+    dev = device.require_gpu()
+    K = synthetic.BENCH_K
+    pts = device.to_device(orc.scene(n, seed=6, K=K, noise_px=0.02)[0]).reshape(1, n, 5)
+    ws = device.PnPWorkspace(1, n, h, dev)
+    for s in range(warmup):
+        ws.run(pts, K, 4.0, 10, AGG_RMS, philox=(100 + s, 0, 1))
+    torch.cuda.synchronize()
+    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    times = []
+    for s in range(steps):
+        start.record()
+        ws.run(pts, K, 4.0, 10, AGG_RMS, philox=(1000 + s, 0, 1))
+        end.record()
+        end.synchronize()
+        times.append(start.elapsed_time(end))
+    best = ws.outcome(0)
+    ms = sorted(times)[len(times) // 2]
+    return {"n": n, "h": h, "steps": steps, "median_ms": ms, "min_ms": min(times), "evals_per_s": n * h / (ms * 1e-3),
+            "best_h": best.best_h, "extra_inliers": best.extra_inliers}
+
+
+def profile(out_dir: str, n: int, h: int, steps: int, warmup: int, limit: int) -> dict:
+    run_dir = os.path.join(out_dir, f"{n}x{h}")
+    os.makedirs(run_dir, exist_ok=True)
+    cmd = ["timeout", "-k", "10", str(limit), "rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", run_dir, "-o", "pnp", "--",
+           sys.executable, os.path.abspath(__file__), "--sizes", f"{n}x{h}", "--steps", str(steps), "--warmup", str(warmup)]
+    proc = subprocess.run(cmd, capture_output=True, text=True)
+    if proc.returncode != 0:
+        raise SystemExit(f"profiled run failed ({proc.returncode}):\n{proc.stderr[-2000:]}")
+    stats = glob.glob(os.path.join(run_dir, "**", "*kernel_stats.csv"), recursive=True)
+    split = {}
+    if stats:
+        with open(stats[0]) as f:
+            for row in csv.DictReader(f):
+                if "pnp" in row["Name"]:
+                    name = row["Name"].replace("(anonymous namespace)::", "").split("(")[0]
+                    split[name] = {
+                        "calls": int(row["Calls"]), "avg_us": float(row["AverageNs"]) / 1e3, "percent": float(row["Percentage"])}
+    return {"n": n, "h": h, "kernels": split}
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--sizes", default=SIZES)
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--profile", metavar="DIR")
+    ap.add_argument("--limit", type=int, default=300, help="seconds per profiled run")
+    args = ap.parse_args()
+    for size in args.sizes.split(","):
+        n, h = (int(v) for v in size.split("x"))
+        if args.profile:
+            print(json.dumps(profile(args.profile, n, h, args.steps, args.warmup, args.limit)), flush=True)
+        else:
+            print(json.dumps(time_pass(n, h, args.steps, args.warmup)), flush=True)
+
+
+if __name__ == "__main__":
+    main()
