@@ -2,7 +2,8 @@
 (``estimate_essential_mat_with_ransac`` -> ``recover_r_t_from_e`` -> ``triangulate_points``), then view 3 registered against
 the triangulated points with ``estimate_pose_pnp_with_ransac``.  Points are projected directly (no images), a fraction of
 the view-2 and view-3 observations are replaced by random pixels, and the recovered pose of view 3 is compared with ground
-truth in the scale of the two-view reconstruction (|t_2| = 1).
+truth in the scale of the two-view reconstruction (|t_2| = 1).  ``--refine K`` refines the view-3 pose on its inliers
+(``refine_rounds=K``) and also reports the unrefined pose's errors, from the same RANSAC draw, next to the refined ones.
 """
 from __future__ import annotations
 
@@ -53,7 +54,7 @@ def rotation_angle(Ra: np.ndarray, Rb: np.ndarray) -> float:
 
 
 def run(n: int = 400, seed: int = 11, outlier_fraction: float = 0.3, noise_px: float = 0.0, sed_threshold: float = 1.5e-6,
-        reprojection_threshold: float = 4.0, iterations: int = 2000) -> dict:
+        reprojection_threshold: float = 4.0, iterations: int = 2000, refine: int = 0) -> dict:
     scene = three_view_scene(n, seed, outlier_fraction, noise_px)
     K = scene["K"]
     features_a = [Feature(float(x), float(y)) for x, y in scene["pa"]]
@@ -70,9 +71,21 @@ def run(n: int = 400, seed: int = 11, outlier_fraction: float = 0.3, noise_px: f
     # view 3: its features matched to the triangulated points (the observation of the same scene point)
     index_of = {(f.x, f.y): i for i, f in enumerate(features_a)}
     matches = [Match(a_index=k, b_index=index_of[(p[0].x, p[0].y)]) for k, p in enumerate(kept)]
+    state = random.getstate()
     R3, t3, inliers = estimate_pose_pnp_with_ransac(K, points, features_c, matches, reprojection_threshold,
                                                     min_num_extra_inliers=10, max_iterations=iterations)
     scale = np.linalg.norm(scene["t2"])
+    unrefined = {}
+    if refine > 0:
+        unrefined = {
+            "pnp_inliers_unrefined": len(inliers),
+            "R3_error_rad_unrefined": rotation_angle(R3, scene["R3"]),
+            "t3_error_unrefined": float(np.linalg.norm(t3 - scene["t3"] / scale)),
+        }
+        random.setstate(state)   # the same RANSAC draw, now refined
+        R3, t3, inliers = estimate_pose_pnp_with_ransac(K, points, features_c, matches, reprojection_threshold,
+                                                        min_num_extra_inliers=10, max_iterations=iterations,
+                                                        refine_rounds=refine)
     return {
         "points": n,
         "two_view_inliers": len(inlier_pairs),
@@ -83,6 +96,7 @@ def run(n: int = 400, seed: int = 11, outlier_fraction: float = 0.3, noise_px: f
         "t3_error": float(np.linalg.norm(t3 - scene["t3"] / scale)),
         "R3": R3.tolist(),
         "t3": t3.tolist(),
+        **unrefined,
     }
 
 
@@ -93,8 +107,15 @@ def main():
     ap.add_argument("--outliers", type=float, default=0.3)
     ap.add_argument("--noise", type=float, default=0.0, help="pixel noise (standard deviation)")
     ap.add_argument("--iterations", type=int, default=2000)
+    ap.add_argument("--sed-threshold", type=float, default=1.5e-6,
+                    help="two-view SED inlier threshold (the default suits noise-free pixels; about 6e-6 for --noise 0.5)")
+    ap.add_argument("--reprojection-threshold", type=float, default=4.0, help="PnP inlier threshold in pixels squared")
+    ap.add_argument("--refine", type=int, default=0, metavar="K",
+                    help="refine the view-3 pose on its inliers, K rounds (0: off); also reports the unrefined errors")
     args = ap.parse_args()
-    print(json.dumps(run(args.points, args.seed, args.outliers, args.noise, iterations=args.iterations)))
+    print(json.dumps(run(args.points, args.seed, args.outliers, args.noise, sed_threshold=args.sed_threshold,
+                         reprojection_threshold=args.reprojection_threshold, iterations=args.iterations,
+                         refine=args.refine)))
 
 
 if __name__ == "__main__":

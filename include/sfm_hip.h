@@ -56,7 +56,7 @@ typedef struct sfm_select_result {
 
 /* Version of this interface: libsfm_hip.so reports the one it was compiled from (sfm_abi_version), the Python binding
  * and the torch op library (sfm_torch_ops_abi_version) refuse a library of another version. */
-#define SFM_ABI_VERSION 13
+#define SFM_ABI_VERSION 14
 
 const char* sfm_last_error(void);
 int sfm_abi_version(void);
@@ -330,6 +330,30 @@ int sfm_pnp_ransac_pass(uint64_t seed, uint64_t seed_stride, int use_philox, int
                         int64_t h_count, int64_t batch, const double* K, double thr, double min_extra, int aggregation, int32_t* S,
                         double* model, int32_t* flags, int32_t* cnt, double* s1, double* s2, sfm_select_result* result,
                         uint8_t* mask, void* stream);
+
+/* ---- refinement of a PnP winner on its inliers (csrc/sfm_pnp_refine.hip; an extension, off unless asked for) ---- */
+
+typedef struct sfm_pnp_refine_info {
+    double error;     /* aggregated error of the model left in model_out (over its `count` inliers) */
+    int32_t count;    /* inliers of that model (for an unrefined model: non-zero entries of mask_in) */
+    int32_t accepted; /* rounds whose result was kept (0 = model_out is model_in) */
+    int32_t lm_steps; /* Levenberg-Marquardt trial steps over all rounds */
+    int32_t reserved; /* 0 */
+} sfm_pnp_refine_info;
+
+/* Per view, up to `rounds` times: Levenberg-Marquardt on the current inliers I (at most `max_steps` trial steps) minimising
+ * C = sum over I of the squared reprojection error e of sfm_pnp_score (+inf behind the camera), with R <- exp([w]x) R,
+ * t <- t + dt, damping lambda diag(H) from 1e-3 (/10 on an accepted step, *10 otherwise); then every item re-scored
+ * (e <= thr) and the result kept iff it has more inliers, or as many and a lower aggregated error.  A round stops early
+ * when |I| < 6 or when the Gauss-Newton matrix of its start point is rank-deficient (a Cholesky pivot <= 1e-10 of its
+ * diagonal entry).  pts: dev [batch,n,5] as sfm_pnp_score; K: host [9], row 2 (0, 0, 1); model_in: dev [batch,12], R | t
+ * of each view (e.g. model[b, best_h] of a pass); mask_in: dev uint8 [batch,n], non-zero = inlier (as written by
+ * sfm_pnp_inlier_mask); err_in: dev [batch], the aggregated error of model_in (sfm_select_result.best_err);
+ * model_out: dev [batch,12] (may be model_in); mask_out: dev uint8 [batch,n], 1 = inlier, must not alias mask_in;
+ * info: dev [batch].  A view whose mask is all zero keeps its model and reports count 0. */
+int sfm_pnp_refine(const double* pts, int64_t n, int64_t batch, const double* K, const double* model_in, const uint8_t* mask_in,
+                   const double* err_in, double thr, int aggregation, int rounds, int max_steps, double* model_out,
+                   uint8_t* mask_out, sfm_pnp_refine_info* info, void* stream);
 
 /* SED of n correspondences under one E (sed.py:7-30).  E: dev [9]; out: dev [n]. */
 int sfm_sed_values(const double* corr, int64_t n, const double* E, double* out, void* stream);

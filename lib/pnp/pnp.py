@@ -4,4 +4,5 @@ from structure_from_motion_amd.pnp.pnp import (  # noqa: F401
     calculate_reprojection_score,
     estimate_pose_pnp_with_ransac,
     pnp_model_fitter,
+    refine_pose_pnp,
 )

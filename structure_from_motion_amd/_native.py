@@ -16,7 +16,7 @@ FIT_DEGENERATE = 1
 MATCH_NCC, MATCH_SSD = 0, 1
 PATCH_PLAIN, PATCH_MEAN_REMOVED, PATCH_RAW64 = 0, 1, 2
 INT64_MAX = (1 << 63) - 1
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 
 def match_ssd_int(bits: int, signed: bool) -> int:
@@ -161,6 +161,7 @@ SIGNATURES = {
     "sfm_pnp_inlier_mask": [_P, _I64, _P, _P, _I64, _I64, _P, _P, _D, _P, _P],
     "sfm_pnp_ransac_pass": [_U64, _U64, C.c_int, _I64, _P, _I64, _I64, _I64, _P, _D, _D, C.c_int, _P, _P, _P, _P, _P, _P, _P,
                             _P, _P],
+    "sfm_pnp_refine": [_P, _I64, _I64, _P, _P, _P, _P, _D, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P],
 }
 OTHER_SYMBOLS = ["sfm_last_error", "sfm_abi_version", "sfm_score_workspace_bytes", "sfm_score_workspace_bytes_ex",
                  "sfm_fit_trace_doubles", "sfm_match_summary_workspace_bytes"]

@@ -1,0 +1,350 @@
+// Nonlinear refinement of a PnP winner on its inliers: Levenberg-Marquardt on the sum of the PnP scorer's squared
+// reprojection errors, then a re-score of every item and the accept rule of sfm_refine_inliers (more inliers, or as
+// many and a lower aggregated error).  The PnP counterpart of sfm_refine.hip; off unless asked for.
+//
+// One 512-thread block per view runs the whole loop.  The pass over the inliers is latency-bound at one block per view
+// (50 000 items x 40 B are L2-resident), so eight waves keep twice the loads of four in flight; the 28-value reduction
+// costs the same per wave either way.  Each LM step is one fused pass at the trial pose: its cost C and, in the same
+// pass, H = sum J^T J and g = sum J^T r there, so an accepted step already has its next system.  The LM state lives in
+// LDS and only thread 0 changes it: the 6 x 6 damped Cholesky solve, the Rodrigues update, accept / reject.  Every
+// branch that contains a barrier depends only on LDS values published behind a barrier, so it is block-uniform.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "sfm_common.h"
+#include "sfm_math.h"
+#include "sfm_pnp.h"
+
+namespace {
+
+using sfmhost::check_launch;
+using sfmhost::fail;
+using sfmpnp::camera_from;
+using sfmpnp::kPnPFields;
+using sfmpnp::pnp_score;
+using sfmpnp::PnPCamera;
+
+constexpr int kThreads = 512;
+constexpr int kWaves = kThreads / kWave;
+constexpr int kSums = 28;  // H upper triangle (21, row-major) | g (6) | C
+constexpr int kMinItems = 6;
+constexpr double kLambda0 = 1e-3;
+constexpr double kLambdaMax = 1e16;
+constexpr double kMinDecrease = 1e-12;  // stop when an accepted step lowers C by less than this fraction of C
+constexpr double kMinStep = 1e-12;      // stop when |delta| <= kMinStep * (1 + |t|)
+// The undamped H of a round's start point must have full rank: every Cholesky pivot above this fraction of its diagonal
+// entry.  Inliers that pin fewer than six degrees of freedom (all at one 3-D point, say) stop the round.
+constexpr double kRankFloor = 1e-10;
+constexpr int kStop = 0, kEvaluate = 1;
+
+static_assert(sizeof(sfm_pnp_refine_info) == 24, "sfm_pnp_refine_info layout is part of the ABI");
+
+// Block-wide sums of K doubles per thread in a fixed order (the block_sum of sfm_refine.hip): butterfly inside each wave,
+// then the wave partials added in wave order by one thread per value.  Result broadcast through `total`.
+template <int K>
+SFM_DEVICE void block_sum(double (&v)[K], double (*part)[kSums], double* total) {
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const double s = sfm::wave_sum(v[k]);
+        if (lane == 0) part[wave][k] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < K) {
+        double acc = part[0][threadIdx.x];
+        for (int w = 1; w < kWaves; ++w) acc += part[w][threadIdx.x];
+        total[threadIdx.x] = acc;
+    }
+    __syncthreads();
+}
+
+SFM_DEVICE double aggregate_total(int aggregation, double count, double sum1, double sum2) {
+    switch (aggregation) {
+        case SFM_AGG_SUM: return sum1;
+        case SFM_AGG_SQUARE: return sum2;
+        case SFM_AGG_MEAN: return sum1 / count;
+        default: return sqrt(sum2 / count);
+    }
+}
+
+// This thread's share of C, H and g over the items with a non-zero mask, at model m.  e is pnp_score's value; an item
+// behind the camera (c2 <= 0) makes C infinite and adds nothing to H or g.  With c = R X + t, q = K c, r = q01 / c2 - uv:
+//   dr/dc = (1 / c2) [[K00, K01, K02 - q0 / c2], [K10, K11, K12 - q1 / c2]],  dc/domega = -[R X]x,  dc/dt = I,
+// so row k of J is (R X  x  A_k, A_k) with A_k row k of dr/dc.
+SFM_DEVICE void accumulate(const double* __restrict__ P, int n, const uint8_t* __restrict__ mask, const double m[12],
+                           const PnPCamera& k, double (&a)[kSums]) {
+#pragma unroll
+    for (int j = 0; j < kSums; ++j) a[j] = 0.0;
+    for (int i = threadIdx.x; i < n; i += kThreads) {
+        if (!mask[i]) continue;
+        const double* q = P + (int64_t)i * kPnPFields;
+        const double X = q[0], Y = q[1], Z = q[2], u = q[3], v = q[4];
+        a[kSums - 1] += pnp_score(m, k, X, Y, Z, u, v);
+        const double r0 = (m[0] * X + m[1] * Y) + m[2] * Z;
+        const double r1 = (m[3] * X + m[4] * Y) + m[5] * Z;
+        const double r2 = (m[6] * X + m[7] * Y) + m[8] * Z;
+        const double c0 = r0 + m[9], c1 = r1 + m[10], c2 = r2 + m[11];
+        if (!(c2 > 0.0)) continue;
+        const double w0 = ((k.k00 * c0 + k.k01 * c1) + k.k02 * c2) / c2;
+        const double w1 = ((k.k10 * c0 + k.k11 * c1) + k.k12 * c2) / c2;
+        const double du = w0 - u, dv = w1 - v;
+        const double ic = 1.0 / c2;
+        const double A0[3] = {k.k00 * ic, k.k01 * ic, (k.k02 - w0) * ic};
+        const double A1[3] = {k.k10 * ic, k.k11 * ic, (k.k12 - w1) * ic};
+        const double J0[6] = {r1 * A0[2] - r2 * A0[1], r2 * A0[0] - r0 * A0[2], r0 * A0[1] - r1 * A0[0], A0[0], A0[1], A0[2]};
+        const double J1[6] = {r1 * A1[2] - r2 * A1[1], r2 * A1[0] - r0 * A1[2], r0 * A1[1] - r1 * A1[0], A1[0], A1[1], A1[2]};
+        int idx = 0;
+#pragma unroll
+        for (int r = 0; r < 6; ++r)
+#pragma unroll
+            for (int c = r; c < 6; ++c) a[idx++] += J0[r] * J0[c] + J1[r] * J1[c];
+#pragma unroll
+        for (int r = 0; r < 6; ++r) a[21 + r] += J0[r] * du + J1[r] * dv;
+    }
+}
+
+SFM_DEVICE int upper(int r, int c) { return r * 6 - r * (r - 1) / 2 + (c - r); }  // r <= c
+
+// Cholesky factor L of H + lambda diag(H), H the upper triangle sys[0..21).  False when a pivot is not above rel times
+// its diagonal entry (rel = 0: not positive), or not a number.
+SFM_DEVICE bool cholesky6(const double* sys, double lambda, double rel, double (&L)[6][6]) {
+    bool ok = true;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        const double hjj = sys[upper(j, j)];
+        const double mjj = hjj + lambda * hjj;
+        double s = mjj;
+#pragma unroll
+        for (int c = 0; c < j; ++c) s -= L[j][c] * L[j][c];
+        ok = ok && (s > rel * mjj);
+        const double d = sqrt(fmax(s, 0.0));
+        L[j][j] = d;
+#pragma unroll
+        for (int i = j + 1; i < 6; ++i) {
+            double x = sys[upper(j, i)];
+#pragma unroll
+            for (int c = 0; c < j; ++c) x -= L[i][c] * L[j][c];
+            L[i][j] = x / d;
+        }
+    }
+    return ok;
+}
+
+// Solves (H + lambda diag H) delta = -g.  False when the factorisation fails or delta is not finite.
+SFM_DEVICE bool solve6(const double* sys, double lambda, double (&delta)[6]) {
+    double L[6][6];
+    if (!cholesky6(sys, lambda, 0.0, L)) return false;
+    double y[6];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        double x = -sys[21 + j];
+#pragma unroll
+        for (int c = 0; c < j; ++c) x -= L[j][c] * y[c];
+        y[j] = x / L[j][j];
+    }
+    bool finite = true;
+#pragma unroll
+    for (int j = 5; j >= 0; --j) {
+        double x = y[j];
+#pragma unroll
+        for (int r = j + 1; r < 6; ++r) x -= L[r][j] * delta[r];
+        delta[j] = x / L[j][j];
+        finite = finite && isfinite(delta[j]);
+    }
+    return finite;
+}
+
+// out = {exp([omega]x) R | t + dt} for delta = (omega, dt): Rodrigues, exp(W) = I + A W + B W^2 with A = sin(th) / th and
+// B = (1 - cos(th)) / th^2 = 2 sin^2(th / 2) / th^2, their Taylor forms below th = 1e-6.
+SFM_DEVICE void apply_step(const double* pose, const double (&delta)[6], double* out) {
+    const double w0 = delta[0], w1 = delta[1], w2 = delta[2];
+    const double th2 = (w0 * w0 + w1 * w1) + w2 * w2;
+    const double th = sqrt(th2);
+    double A, B;
+    if (th < 1e-6) {
+        A = 1.0 - th2 / 6.0;
+        B = 0.5 - th2 / 24.0;
+    } else {
+        const double s = sin(0.5 * th);
+        A = sin(th) / th;
+        B = 2.0 * s * s / th2;
+    }
+    const double W[3][3] = {{0.0, -w2, w1}, {w2, 0.0, -w0}, {-w1, w0, 0.0}};
+    double E[3][3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const double W2 = (W[r][0] * W[0][c] + W[r][1] * W[1][c]) + W[r][2] * W[2][c];
+            E[r][c] = ((r == c ? 1.0 : 0.0) + A * W[r][c]) + B * W2;
+        }
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) out[3 * r + c] = (E[r][0] * pose[c] + E[r][1] * pose[3 + c]) + E[r][2] * pose[6 + c];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) out[9 + r] = pose[9 + r] + delta[3 + r];
+}
+
+__global__ __launch_bounds__(kThreads) void pnp_refine_kernel(
+    const double* __restrict__ pts, int n, PnPCamera cam, const double* __restrict__ model_in,
+    const uint8_t* __restrict__ mask_in, const double* __restrict__ err_in, double thr, int aggregation, int rounds,
+    int max_steps, double* __restrict__ model_out, uint8_t* __restrict__ mask_out, sfm_pnp_refine_info* __restrict__ info) {
+    __shared__ double part[kWaves][kSums];
+    __shared__ double total[kSums];
+    __shared__ double sys[kSums];  // H | g | C at the LM point (thread 0)
+    __shared__ double best[12];    // the model kept so far
+    __shared__ double pose[12];    // the LM point
+    __shared__ double trial[12];   // the model the next pass evaluates
+    __shared__ int ctl;
+
+    const int64_t b = blockIdx.x;
+    const double* P = pts + b * n * kPnPFields;
+    const uint8_t* min = mask_in + b * n;
+    uint8_t* mout = mask_out + b * n;
+    const int tid = threadIdx.x;
+
+    // start: the input model and its inliers (sample items, marked 2 by sfm_pnp_inlier_mask, count as inliers).  Every
+    // pass maps item i to thread i % kThreads, so a thread only ever reads the mask entries it wrote itself.
+    double v1[1] = {0.0};
+    for (int i = tid; i < n; i += kThreads) {
+        const uint8_t m = min[i] != 0 ? 1 : 0;
+        mout[i] = m;
+        v1[0] += (double)m;
+    }
+    if (tid < 12) {
+        best[tid] = model_in[b * 12 + tid];
+        model_out[b * 12 + tid] = best[tid];
+    }
+    block_sum<1>(v1, part, total);
+    double best_cnt = total[0];
+    double best_err = err_in[b];
+    int accepted = 0;
+    int steps = 0;  // trial steps of every round (thread 0)
+
+    for (int round = 0; round < rounds; ++round) {
+        if (!(best_cnt >= (double)kMinItems)) break;  // block-uniform
+        if (tid < 12) trial[tid] = pose[tid] = best[tid];
+        __syncthreads();
+        double a[kSums];
+        double m[12];
+#pragma unroll
+        for (int k = 0; k < 12; ++k) m[k] = trial[k];
+        accumulate(P, n, mout, m, cam, a);
+        block_sum<kSums>(a, part, total);
+        double lambda = kLambda0;
+        bool stop = false;
+        int round_steps = 0;
+        if (tid == 0) {
+#pragma unroll
+            for (int k = 0; k < kSums; ++k) sys[k] = total[k];
+            double L[6][6];
+            stop = !cholesky6(sys, 0.0, kRankFloor, L);
+        }
+        // LM: thread 0 plans the next trial (or stops), everybody evaluates it, thread 0 accepts or rejects it
+        for (;;) {
+            if (tid == 0) {
+                int next = kStop;
+                while (!stop && round_steps < max_steps && !(lambda > kLambdaMax)) {
+                    ++round_steps;
+                    double delta[6];
+                    if (!solve6(sys, lambda, delta)) {
+                        lambda *= 10.0;
+                        continue;
+                    }
+                    const double dn = sqrt(((delta[0] * delta[0] + delta[1] * delta[1]) + (delta[2] * delta[2] + delta[3] * delta[3])) +
+                                           (delta[4] * delta[4] + delta[5] * delta[5]));
+                    const double tn = sqrt((pose[9] * pose[9] + pose[10] * pose[10]) + pose[11] * pose[11]);
+                    if (dn <= kMinStep * (1.0 + tn)) break;
+                    apply_step(pose, delta, trial);
+                    next = kEvaluate;
+                    break;
+                }
+                ctl = next;
+            }
+            __syncthreads();
+            if (ctl == kStop) break;  // block-uniform
+#pragma unroll
+            for (int k = 0; k < 12; ++k) m[k] = trial[k];
+            accumulate(P, n, mout, m, cam, a);
+            block_sum<kSums>(a, part, total);
+            if (tid == 0) {
+                const double c_new = total[kSums - 1], c_old = sys[kSums - 1];
+                if (isfinite(c_new) && c_new < c_old) {
+#pragma unroll
+                    for (int k = 0; k < kSums; ++k) sys[k] = total[k];
+#pragma unroll
+                    for (int k = 0; k < 12; ++k) pose[k] = trial[k];
+                    lambda /= 10.0;
+                    stop = c_old - c_new < kMinDecrease * c_old;
+                } else {
+                    lambda *= 10.0;
+                }
+            }
+        }
+        steps += round_steps;
+        // re-score every item under the LM result (the pose thread 0 left before the last barrier)
+#pragma unroll
+        for (int k = 0; k < 12; ++k) m[k] = pose[k];
+        double c[3] = {0.0, 0.0, 0.0};
+        for (int i = tid; i < n; i += kThreads) {
+            const double* q = P + (int64_t)i * kPnPFields;
+            const double e = pnp_score(m, cam, q[0], q[1], q[2], q[3], q[4]);
+            if (e <= thr) {
+                c[0] += 1.0;
+                c[1] += e;
+                c[2] += e * e;
+            }
+        }
+        block_sum<3>(c, part, total);
+        const double cnt = total[0];
+        const double err = aggregate_total(aggregation, cnt, total[1], total[2]);
+        const bool better = cnt > best_cnt || (cnt == best_cnt && err < best_err);  // NaN error never wins
+        if (!better) break;
+        for (int i = tid; i < n; i += kThreads) {
+            const double* q = P + (int64_t)i * kPnPFields;
+            mout[i] = pnp_score(m, cam, q[0], q[1], q[2], q[3], q[4]) <= thr ? 1 : 0;
+        }
+        if (tid < 12) {
+            best[tid] = pose[tid];
+            model_out[b * 12 + tid] = pose[tid];
+        }
+        best_cnt = cnt;
+        best_err = err;
+        ++accepted;
+    }
+    if (tid == 0) {
+        info[b].error = best_err;
+        info[b].count = (int32_t)best_cnt;
+        info[b].accepted = accepted;
+        info[b].lm_steps = steps;
+        info[b].reserved = 0;
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int sfm_pnp_refine(const double* pts, int64_t n, int64_t batch, const double* K, const double* model_in, const uint8_t* mask_in,
+                   const double* err_in, double thr, int aggregation, int rounds, int max_steps, double* model_out,
+                   uint8_t* mask_out, sfm_pnp_refine_info* info, void* stream) {
+    // every check before the launch: a refused call has enqueued nothing
+    if (n < 0 || batch < 0 || rounds < 0 || max_steps < 0) return fail(SFM_EINVAL, "sfm_pnp_refine: negative size");
+    if (n > 0x7FFFFFFF) return fail(SFM_EINVAL, "sfm_pnp_refine: n too large");
+    if (batch > 0x7FFFFFFF) return fail(SFM_EINVAL, "sfm_pnp_refine: batch exceeds one launch (2^31-1 blocks)");
+    if (aggregation < SFM_AGG_SUM || aggregation > SFM_AGG_RMS) return fail(SFM_EINVAL, "sfm_pnp_refine: unknown aggregation");
+    PnPCamera cam;
+    const int rc = camera_from(K, cam, "sfm_pnp_refine");
+    if (rc != SFM_OK) return rc;
+    if (batch == 0) return SFM_OK;
+    if (!model_in || !err_in || !model_out || !info || (n > 0 && (!pts || !mask_in || !mask_out)))
+        return fail(SFM_EINVAL, "sfm_pnp_refine: null pointer");
+    if (mask_in != nullptr && mask_in == mask_out) return fail(SFM_EINVAL, "sfm_pnp_refine: mask_out must not alias mask_in");
+    hipLaunchKernelGGL(pnp_refine_kernel, dim3((unsigned)batch), dim3(kThreads), 0, (hipStream_t)stream, pts, (int)n, cam,
+                       model_in, mask_in, err_in, thr, aggregation, rounds, max_steps, model_out, mask_out, info);
+    return check_launch("pnp_refine_kernel");
+}
+
+}  // extern "C"

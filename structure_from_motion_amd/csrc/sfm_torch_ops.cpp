@@ -6,7 +6,8 @@
 // select_best, inlier_mask, cheirality, triangulate — each in a functional form (allocates its outputs; has a Meta
 // kernel, so fake-tensor tracing / torch.compile / opcheck work) and, where the engine pre-allocates its buffers
 // (device.RansacWorkspace), an in-place `_`-suffixed form with mutable arguments, plus the fused
-// sample_fit_philox_; and the PnP ops (sfm_pnp.hip) pnp_fit, pnp_score and the whole pass pnp_ransac_pass_.  The reference call sites these serve: apps/sfm.py:110-119 (RANSAC-E), :133-138 (pose),
+// sample_fit_philox_; and the PnP ops (sfm_pnp.hip) pnp_fit, pnp_score and the whole pass pnp_ransac_pass_, and the
+// refinement of a winner pnp_refine (sfm_pnp_refine.hip).  The reference call sites these serve: apps/sfm.py:110-119 (RANSAC-E), :133-138 (pose),
 // :181-186 (triangulation).
 //
 // Built by structure_from_motion_amd/build.py into csrc/libsfm_torch_ops.so (host code only: no kernels here).
@@ -505,6 +506,53 @@ void pnp_ransac_pass_out(const Tensor& pts, int64_t seed, int64_t seed_stride, b
                            reinterpret_cast<sfm_select_result*>(ptr<int64_t>(result)), ptr<uint8_t>(mask), current_stream()),
        "sfm_pnp_ransac_pass");
 }
+
+// refinement of a winner on its inliers (sfm_pnp_refine.hip): model [batch, 12], mask uint8 [batch, n], err [batch];
+// info int64 [batch, 3] viewing the sfm_pnp_refine_info records
+constexpr int64_t kRefineInfoWords = sizeof(sfm_pnp_refine_info) / 8;
+
+void pnp_refine_out(const Tensor& pts, const Tensor& model, const Tensor& mask, const Tensor& err, at::ArrayRef<double> K,
+                    double thr, int64_t aggregation, int64_t rounds, int64_t max_steps, Tensor& model_out, Tensor& mask_out,
+                    Tensor& info) {
+    const OpDevice scope(pts);
+    need(pts, "pts", at::kDouble);
+    need(model, "model", at::kDouble);
+    need(mask, "mask", at::kByte);
+    need(err, "err", at::kDouble);
+    need(model_out, "model_out", at::kDouble);
+    need(mask_out, "mask_out", at::kByte);
+    need(info, "info", at::kLong);
+    check_K(K);
+    TORCH_CHECK(pts.dim() == 3 && pts.size(2) == 5, "sfm_hip: pts must be [batch, n, 5]");
+    const int64_t batch = pts.size(0), n = pts.size(1);
+    TORCH_CHECK(model.numel() == batch * 12 && model_out.numel() == batch * 12, "sfm_hip: model, model_out must be [batch, 12]");
+    TORCH_CHECK(mask.numel() == batch * n && mask_out.numel() == batch * n, "sfm_hip: mask, mask_out must be uint8 [batch, n]");
+    TORCH_CHECK(err.numel() == batch, "sfm_hip: err must be [batch]");
+    TORCH_CHECK(info.numel() == batch * kRefineInfoWords, "sfm_hip: info must be int64 [batch, 3]");
+    ok(sfm_pnp_refine(ptr<double>(pts), n, batch, K.data(), ptr<double>(model), ptr<uint8_t>(mask), ptr<double>(err), thr,
+                      (int)aggregation, (int)rounds, (int)max_steps, ptr<double>(model_out), ptr<uint8_t>(mask_out),
+                      reinterpret_cast<sfm_pnp_refine_info*>(ptr<int64_t>(info)), current_stream()),
+       "sfm_pnp_refine");
+}
+
+std::tuple<Tensor, Tensor, Tensor> pnp_refine(const Tensor& pts, const Tensor& model, const Tensor& mask, const Tensor& err,
+                                              at::ArrayRef<double> K, double thr, int64_t aggregation, int64_t rounds,
+                                              int64_t max_steps) {
+    TORCH_CHECK(pts.dim() == 3, "sfm_hip: pts must be [batch, n, 5]");
+    Tensor model_out = at::empty({pts.size(0), 12}, like(pts, at::kDouble));
+    Tensor mask_out = at::empty({pts.size(0), pts.size(1)}, like(pts, at::kByte));
+    Tensor info = at::empty({pts.size(0), kRefineInfoWords}, like(pts, at::kLong));
+    pnp_refine_out(pts, model, mask, err, K, thr, aggregation, rounds, max_steps, model_out, mask_out, info);
+    return {model_out, mask_out, info};
+}
+
+std::tuple<Tensor, Tensor, Tensor> pnp_refine_meta(const Tensor& pts, const Tensor&, const Tensor&, const Tensor&,
+                                                   at::ArrayRef<double>, double, int64_t, int64_t, int64_t) {
+    TORCH_CHECK(pts.dim() == 3, "sfm_hip: pts must be [batch, n, 5]");
+    return {at::empty_symint({pts.sym_size(0), 12}, like(pts, at::kDouble)),
+            at::empty_symint({pts.sym_size(0), pts.sym_size(1)}, like(pts, at::kByte)),
+            at::empty_symint({pts.sym_size(0), c10::SymInt(kRefineInfoWords)}, like(pts, at::kLong))};
+}
 }  // namespace
 
 // the C-ABI version this op library was compiled against (include/sfm_hip.h); ops.load() compares it with the
@@ -544,6 +592,10 @@ TORCH_LIBRARY(sfm_hip, m) {
     m.def("pnp_ransac_pass_(Tensor pts, int seed, int seed_stride, bool use_philox, int h_begin, float[] K, float thr, "
           "float min_extra, int aggregation, Tensor(a!) S, Tensor(b!) model, Tensor(c!) flags, Tensor(d!) cnt, Tensor(e!) s1, "
           "Tensor(f!) s2, Tensor(g!) result, Tensor(h!)? mask) -> ()");
+    m.def("pnp_refine(Tensor pts, Tensor model, Tensor mask, Tensor err, float[] K, float thr, int aggregation, int rounds, "
+          "int max_steps) -> (Tensor, Tensor, Tensor)");
+    m.def("pnp_refine_(Tensor pts, Tensor model, Tensor mask, Tensor err, float[] K, float thr, int aggregation, int rounds, "
+          "int max_steps, Tensor(a!) model_out, Tensor(b!) mask_out, Tensor(c!) info) -> ()");
 }
 
 // ROCm devices dispatch under torch's "CUDA" key (the name of the dispatch key, not a CUDA code path)
@@ -568,6 +620,8 @@ TORCH_LIBRARY_IMPL(sfm_hip, CUDA, m) {
     m.impl("pnp_score", &pnp_score);
     m.impl("pnp_score_", &pnp_score_out);
     m.impl("pnp_ransac_pass_", &pnp_ransac_pass_out);
+    m.impl("pnp_refine", &pnp_refine);
+    m.impl("pnp_refine_", &pnp_refine_out);
 }
 
 // sample_philox has no tensor argument to dispatch on: registered for every backend, it checks its device itself
@@ -590,6 +644,8 @@ void pnp_fit_out_meta(const Tensor&, const Tensor&, at::ArrayRef<double>, Tensor
 void pnp_score_out_meta(const Tensor&, const Tensor&, const Tensor&, at::ArrayRef<double>, double, Tensor&, Tensor&, Tensor&) {}
 void pnp_ransac_pass_out_meta(const Tensor&, int64_t, int64_t, bool, int64_t, at::ArrayRef<double>, double, double, int64_t, Tensor&,
                               Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, const std::optional<Tensor>&) {}
+void pnp_refine_out_meta(const Tensor&, const Tensor&, const Tensor&, const Tensor&, at::ArrayRef<double>, double, int64_t, int64_t,
+                         int64_t, Tensor&, Tensor&, Tensor&) {}
 
 TORCH_LIBRARY_IMPL(sfm_hip, Meta, m) {
     m.impl("normalize_coords_", &normalize_coords_out_meta);
@@ -612,4 +668,6 @@ TORCH_LIBRARY_IMPL(sfm_hip, Meta, m) {
     m.impl("pnp_fit_", &pnp_fit_out_meta);
     m.impl("pnp_score_", &pnp_score_out_meta);
     m.impl("pnp_ransac_pass_", &pnp_ransac_pass_out_meta);
+    m.impl("pnp_refine", &pnp_refine_meta);
+    m.impl("pnp_refine_", &pnp_refine_out_meta);
 }

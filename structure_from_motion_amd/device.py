@@ -669,6 +669,31 @@ def pnp_inlier_mask(pts, model, S, K, result, thr: float, out=None):
     return out
 
 
+def pnp_refine(pts, model, mask, err, K, thr: float, aggregation: int, rounds: int = 1, max_steps: int = 20):
+    """Levenberg-Marquardt refinement of one pose per view on its inliers, re-scored and kept only if better
+    (``sfm_pnp_refine``).  pts [B,N,5], model f64 [B,12] (R | t), mask uint8 [B,N] (non-zero = inlier), err f64 [B] (the
+    aggregated error of ``model``) -> (model_out [B,12], mask_out uint8 [B,N] (1 = inlier), info int64 [B,3] viewing
+    sfm_pnp_refine_info records; ``read_pnp_refine_info``).  No host synchronisation."""
+    return ops.load().pnp_refine(pts, model.contiguous(), mask.contiguous(), err.contiguous(), _camera_list(K), float(thr),
+                                 int(aggregation), int(rounds), int(max_steps))
+
+
+@dataclass
+class PnPRefineInfo:
+    error: float     # aggregated error of the model left in model_out, over its `count` inliers
+    count: int       # inliers of that model
+    accepted: int    # rounds whose result was kept (0: model_out is the input model)
+    lm_steps: int    # Levenberg-Marquardt trial steps over all rounds
+
+
+def read_pnp_refine_info(info: torch.Tensor) -> List[PnPRefineInfo]:
+    """Host copy of sfm_pnp_refine_info records (int64 [B,3]) (synchronises)."""
+    raw = info.cpu().numpy()
+    return [PnPRefineInfo(float(raw[i, 0:1].view(np.float64)[0]), int(raw[i, 1:2].view(np.int32)[0]),
+                          int(raw[i, 1:2].view(np.int32)[1]), int(raw[i, 2:3].view(np.int32)[0]))
+            for i in range(raw.shape[0])]
+
+
 @dataclass
 class PnPOutcome:
     best_h: int                # winning hypothesis, -1 if none
@@ -705,6 +730,15 @@ class PnPWorkspace:
         ops.load().pnp_ransac_pass_(pts, _as_int64(seed), _as_int64(stride), philox is not None, h_begin, _camera_list(K),
                                     float(thr), float(min_extra), int(aggregation), self.S, self.model, self.flags, self.cnt,
                                     self.s1, self.s2, self.result, self.mask if with_mask else None)
+
+    def refine(self, pts: torch.Tensor, K, thr: float, aggregation: int, rounds: int = 1, max_steps: int = 20):
+        """``pnp_refine`` of every view's winner, chained on this pass's buffers: model[b, best_h] (row 0 when a view has no
+        winner: its mask is all zero and it keeps that row), the pass's mask and the record's best_err.  Stream-ordered
+        after ``run``: no host round trip.  -> (model_out [B,12], mask_out [B,N], info [B,3])."""
+        best_h = self.result[:, 1].clamp(min=0)
+        model = self.model[torch.arange(self.batch, device=best_h.device), best_h]
+        err = self.result[:, 2].contiguous().view(F64)
+        return pnp_refine(pts, model, self.mask, err, K, thr, aggregation, rounds, max_steps)
 
     def outcome(self, b: int = 0) -> PnPOutcome:
         rec = read_select(self.result)[b]

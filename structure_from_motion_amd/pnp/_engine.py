@@ -25,11 +25,15 @@ def item_array(data) -> np.ndarray:
     return out
 
 
-def ransac_pnp_items(data, camera_matrix, threshold, min_extra, aggregation, iterations):
+def ransac_pnp_items(data, camera_matrix, threshold, min_extra, aggregation, iterations, refine_rounds=0, refine_steps=20):
     """Returns ((R, t) or None, inlier items) with the semantics of ransac._host_loop: sample ``pyshuffle`` (default) replays
     the reference's cumulative ``random.shuffle`` and advances the global ``random`` state; ``philox`` draws on the device
     (seed ``SFM_SEED`` or 64 bits of ``random``).  Inliers come back as deep copies, the sample first, then the survivors
-    in the order of the shuffled list (``philox``: index order)."""
+    in the order of the shuffled list (``philox``: index order).
+
+    ``refine_rounds > 0`` refines the winner on its inliers right after the pass, on the pass's own buffers
+    (``PnPWorkspace.refine``).  When a round is kept, the pose is the refined one and the inliers are the items with
+    e <= threshold under it, in index order; otherwise the return value is the unrefined one."""
     from .pnp import SAMPLE_SIZE, PnPCalculationError, check_camera_matrix
 
     n = len(data)
@@ -50,6 +54,7 @@ def ransac_pnp_items(data, camera_matrix, threshold, min_extra, aggregation, ite
     else:
         seed = int(os.environ["SFM_SEED"]) if "SFM_SEED" in os.environ else random.getrandbits(64)
         ws.run(pts, K, threshold, min_extra, aggregation, philox=(seed, 0, 1))
+    refined = ws.refine(pts, K, threshold, aggregation, refine_rounds, refine_steps) if refine_rounds > 0 else None
     outcome = ws.outcome(0)
     if outcome.n_flagged and degenerate_policy() == "raise":
         raise PnPCalculationError(
@@ -61,6 +66,12 @@ def ransac_pnp_items(data, camera_matrix, threshold, min_extra, aggregation, ite
                      outcome.extra_inliers, outcome.error, outcome.n_flagged)
     if outcome.best_h < 0:
         return None, []
+    if refined is not None:
+        model, mask, info = refined
+        if device.read_pnp_refine_info(info)[0].accepted > 0:
+            m = model[0].cpu().numpy()
+            keep = np.nonzero(mask[0].cpu().numpy())[0]
+            return (m[:9].reshape(3, 3).copy(), m[9:].copy()), [copy.deepcopy(data[i]) for i in keep.tolist()]
     survivors = outcome.mask == 1
     if sampler == "pyshuffle":
         perm = table.permutation_after(outcome.best_h)

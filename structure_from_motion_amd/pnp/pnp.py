@@ -18,7 +18,7 @@ import numpy.typing as npt
 from ..common.feature import Feature
 from ..epipolar import _engine
 from ..feature_matching.matching import Match
-from ..ransac.ransac import ErrorAggregationMethod, fit_with_ransac
+from ..ransac.ransac import DEFAULT_MAX_ITERATIONS, ErrorAggregationMethod, aggregation_code, fit_with_ransac
 
 PnPItem = Tuple[npt.NDArray, Feature]
 PnPModel = Tuple[npt.NDArray, npt.NDArray]
@@ -110,6 +110,7 @@ def estimate_pose_pnp_with_ransac(
     min_num_extra_inliers: int | None = None,
     error_aggregation_method: ErrorAggregationMethod | None = None,
     max_iterations: int | None = None,
+    refine_rounds: int = 0,
 ) -> Tuple[npt.NDArray, npt.NDArray, list]:
     """Pose (R, t) of a further view from 2D-3D matches with RANSAC over six-point DLT hypotheses.
 
@@ -117,10 +118,19 @@ def estimate_pose_pnp_with_ransac(
     inlier when its squared reprojection error is at most ``reprojection_threshold`` (pixels squared).  Returns
     ``(R, t, inlier (X, Feature) pairs)``.  Raises ``ValueError`` for fewer than six matches, a malformed camera matrix or
     when no hypothesis has enough inliers, and ``PnPCalculationError`` when a sampled six-tuple is degenerate
-    (``SFM_DEGENERATE=skip`` ignores such hypotheses instead)."""
+    (``SFM_DEGENERATE=skip`` ignores such hypotheses instead).
+
+    ``refine_rounds > 0`` refines the RANSAC winner on its inliers on the device, right after the pass (see
+    ``refine_pose_pnp``, at most 20 Levenberg-Marquardt steps per round).  If no round is kept the result is exactly the
+    unrefined one; otherwise the inliers are the pairs with an error of at most the threshold under the refined pose, in
+    match order.  0 (the default) runs the unrefined path unchanged."""
     K = check_camera_matrix(camera_matrix)
     if len(matches) < SAMPLE_SIZE:
         raise ValueError(f"At least six 2D-3D matches are expected, got {len(matches)}.")
+    refine_rounds = _non_negative(refine_rounds, "refine_rounds")
+    if refine_rounds > 0:
+        return _ransac_refined(K, points_3d, features, matches, reprojection_threshold, min_num_extra_inliers,
+                               error_aggregation_method, max_iterations, refine_rounds)
     with _engine.gc_paused():
         items = [(np.asarray(points_3d[m.a_index], dtype=np.float64).reshape(3), features[m.b_index]) for m in matches]
         model, inliers = fit_with_ransac(
@@ -137,3 +147,104 @@ def estimate_pose_pnp_with_ransac(
         raise ValueError("Could not estimate the pose with RANSAC.")
     R, t = model
     return R, t, inliers
+
+
+def _non_negative(value, name: str) -> int:
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or value < 0:
+        raise ValueError(f"{name} must be a non-negative integer, got {value!r}")
+    return int(value)
+
+
+def _items(points_3d, features, matches):
+    return [(np.asarray(points_3d[m.a_index], dtype=np.float64).reshape(3), features[m.b_index]) for m in matches]
+
+
+def _ransac_refined(K, points_3d, features, matches, threshold, min_extra, method, max_iterations, rounds):
+    """The device route of fit_with_ransac (the one the tagged pair takes) with the refinement chained after the pass."""
+    from . import _engine as pnp_engine
+
+    iterations = DEFAULT_MAX_ITERATIONS if max_iterations is None else max_iterations
+    method = ErrorAggregationMethod.RMS if method is None else method
+    min_extra = 0 if min_extra is None else min_extra
+    with _engine.gc_paused():
+        items = _items(points_3d, features, matches)
+        model, inliers = pnp_engine.ransac_pnp_items(items, K, threshold, min_extra, aggregation_code(method), iterations,
+                                                     refine_rounds=rounds)
+    if model is None:
+        raise ValueError(f"No model could be found with at least {min_extra + SAMPLE_SIZE} inliers.")
+    R, t = model
+    return R, t, inliers
+
+
+def refine_pose_pnp(
+    camera_matrix: npt.NDArray,
+    points_3d: Sequence[npt.NDArray],
+    features: Sequence[Feature],
+    matches: Sequence[Match],
+    R: npt.NDArray,
+    t: npt.NDArray,
+    reprojection_threshold: float,
+    rounds: int = 1,
+    max_steps: int = 20,
+    error_aggregation_method: ErrorAggregationMethod | None = None,
+) -> Tuple[npt.NDArray, npt.NDArray, list]:
+    """Refine a pose (R, t) on its inliers by Levenberg-Marquardt on the squared reprojection error (``sfm_pnp_refine``).
+
+    The inliers of (R, t) are the pairs with an error of at most ``reprojection_threshold``.  Up to ``rounds`` times,
+    at most ``max_steps`` LM steps minimise the sum of their errors, every pair is re-scored, and the result is kept iff it
+    has more inliers, or as many and a lower aggregated error (``error_aggregation_method``, default RMS).  Returns
+    ``(R, t, inlier (X, Feature) pairs in match order)``; when no round is kept, R and t are the given ones.  Every
+    argument is checked before any device work."""
+    K = check_camera_matrix(camera_matrix)
+    if len(matches) < SAMPLE_SIZE:
+        raise ValueError(f"At least six 2D-3D matches are expected, got {len(matches)}.")
+    R = np.asarray(R, dtype=np.float64)
+    t = np.asarray(t, dtype=np.float64)
+    if R.shape != (3, 3) or t.size != 3:
+        raise ValueError(f"R must be 3x3 and t of length 3, got shapes {R.shape} and {t.shape}")
+    rounds = _non_negative(rounds, "rounds")
+    max_steps = _non_negative(max_steps, "max_steps")
+    method = ErrorAggregationMethod.RMS if error_aggregation_method is None else error_aggregation_method
+    aggregation = aggregation_code(method)
+    from .. import device
+    from . import _engine as pnp_engine
+
+    with _engine.gc_paused():
+        items = _items(points_3d, features, matches)
+    n = len(items)
+    dev = device.require_gpu()
+    pts = device.to_device(pnp_engine.item_array(items)).reshape(1, n, 5)
+    model = np.concatenate([R.reshape(9), t.reshape(3)])
+    mask, err = _score_pose(pts, model, K, reprojection_threshold, aggregation, dev)
+    model_out, mask_out, info = device.pnp_refine(pts, device.to_device(model).reshape(1, 12), mask, err, K,
+                                                  reprojection_threshold, aggregation, rounds, max_steps)
+    if device.read_pnp_refine_info(info)[0].accepted > 0:
+        m = model_out[0].cpu().numpy()
+        R, t, keep = m[:9].reshape(3, 3).copy(), m[9:].copy(), mask_out[0].cpu().numpy()
+    else:
+        R, t, keep = R.copy(), t.reshape(3).copy(), mask[0].cpu().numpy()
+    return R, t, [items[i] for i in np.nonzero(keep)[0].tolist()]
+
+
+def _score_pose(pts, model, K, threshold, aggregation, dev):
+    """(mask uint8 [1,N], err f64 [1]) of one pose by the device scorer: the mask of sfm_pnp_inlier_mask (e <= threshold),
+    and the aggregated error of its inliers from sfm_pnp_score, with six of them standing in as the sample (a sample item
+    with e <= threshold enters the sums like any other inlier)."""
+    import torch
+
+    from .. import device
+
+    n = pts.shape[1]
+    model_d = device.to_device(model).reshape(1, 1, 12)
+    none = torch.full((1, 1, 8), -1, dtype=torch.int32, device=dev)
+    record = torch.zeros((1, 5), dtype=torch.int64, device=dev)   # best_h = 0: the single model
+    mask = device.pnp_inlier_mask(pts, model_d, none, K, record, threshold)
+    inliers = torch.nonzero(mask[0]).flatten()
+    if inliers.numel() < SAMPLE_SIZE:
+        return mask, torch.full((1,), float("inf"), dtype=torch.float64, device=dev)
+    S = torch.full((1, 1, 8), -1, dtype=torch.int32, device=dev)
+    S[0, 0, :SAMPLE_SIZE] = inliers[:SAMPLE_SIZE].to(torch.int32)
+    cnt, s1, s2 = device.pnp_score(pts, model_d, S, K, threshold)
+    count = cnt.to(torch.float64) + SAMPLE_SIZE
+    err = [s1, s2, s1 / count, torch.sqrt(s2 / count)][aggregation]
+    return mask, err.reshape(1).contiguous()

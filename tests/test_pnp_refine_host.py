@@ -1,0 +1,158 @@
+"""Refinement of a PnP winner, host side: the NumPy oracle (tests/pnp_refine_oracle.py), the C-ABI export, the op
+registration with its Meta kernels and the argument checks of refine_pose_pnp (no GPU)."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+import pnp_oracle as po
+import pnp_refine_oracle as ro
+from structure_from_motion_amd import synthetic
+from structure_from_motion_amd.common.feature import Feature
+from structure_from_motion_amd.feature_matching.matching import Match
+from structure_from_motion_amd.pnp import pnp
+
+K = synthetic.BENCH_K
+
+
+def _rotation_error(Ra, Rb):
+    return float(np.arccos(np.clip((np.trace(Ra @ Rb.T) - 1.0) / 2.0, -1.0, 1.0)))
+
+
+def test_oracle_converges_to_ground_truth_without_noise():
+    pts, R, t = po.scene(400, seed=1, K=K, outlier_fraction=0.0, noise_px=0.0)
+    R0, t0 = ro.apply_step(R, t, np.array([0.01, -0.02, 0.005, 0.05, -0.03, 0.02]))
+    e = po.score_values(R0, t0, K, pts)
+    thr = 1e12   # every item is an inlier of the perturbed pose
+    out = ro.refine(pts, R0, t0, K, np.ones(len(pts)), ro.aggregate(ro.RMS, len(pts), e), thr, ro.RMS, rounds=1,
+                    max_steps=50)
+    assert out["accepted"] == 1
+    assert _rotation_error(out["R"], R) <= 1e-9
+    assert np.max(np.abs(out["t"] - t)) <= 1e-9
+
+
+def test_oracle_result_is_stationary_and_gradient_matches_finite_differences():
+    pts, R, t = po.scene(2000, seed=4, K=K, outlier_fraction=0.3, noise_px=0.5)
+    inliers = pts[po.score_values(R, t, K, pts) <= 4.0]
+    R0, t0 = ro.apply_step(R, t, np.array([0.002, -0.001, 0.001, 0.01, 0.0, 0.01]))
+    # g = J^T r is half the gradient of C = sum e: central differences along the LM parametrisation
+    _, g0, _ = ro.system(R0, t0, K, inliers)
+    h = 1e-6
+    fd = np.zeros(6)
+    for k in range(6):
+        d = np.zeros(6)
+        d[k] = h
+        plus = ro.cost(*ro.apply_step(R0, t0, d), K, inliers)
+        d[k] = -h
+        minus = ro.cost(*ro.apply_step(R0, t0, d), K, inliers)
+        fd[k] = (plus - minus) / (4.0 * h)
+    assert np.max(np.abs(fd - g0)) <= 1e-6 * np.max(np.abs(g0))
+    R1, t1, steps = ro.lm(R0, t0, K, inliers, 50)
+    _, g1, C1 = ro.system(R1, t1, K, inliers)
+    assert 0 < steps <= 50
+    assert np.linalg.norm(g1) <= 1e-6 * (1.0 + C1)
+    assert C1 < ro.cost(R0, t0, K, inliers)
+
+
+def test_oracle_keeps_model_of_degenerate_inlier_set():
+    pts, R, t = po.scene(50, seed=7, K=K, outlier_fraction=0.0, noise_px=0.0)
+    pts[:, :3] = pts[0, :3]
+    pts[:, 3:] = pts[0, 3:] + 0.5   # all at one 3-D point, 0.7 px off
+    e = po.score_values(R, t, K, pts)
+    out = ro.refine(pts, R, t, K, np.ones(50), ro.aggregate(ro.RMS, 50, e), 4.0, ro.RMS)
+    assert out["lm_steps"] == 0 and out["accepted"] == 0
+    assert np.array_equal(out["R"], R) and np.array_equal(out["t"], t)
+
+
+def test_refine_symbol_exported_and_abi(native_lib):
+    from structure_from_motion_amd import _native
+
+    assert _native.ABI_VERSION == 14
+    assert native_lib.sfm_abi_version() == 14
+    assert "sfm_pnp_refine" in _native.SIGNATURES
+    assert hasattr(native_lib, "sfm_pnp_refine")
+
+
+def test_refine_rejects_bad_arguments_before_launch(native_lib):
+    """Every refusal happens on the host before the launch (no GPU needed): pointers are never dereferenced."""
+    lib = native_lib
+    Kc = (C.c_double * 9)(*[float(v) for v in K.reshape(9)])
+    Kbad = (C.c_double * 9)(*[float(v) for v in K.reshape(9)])
+    Kbad[8] = 2.0
+    p = C.c_void_p(0x1000)   # never dereferenced: every call below is refused before the launch
+    mask_a, mask_b = C.c_void_p(0x2000), C.c_void_p(0x3000)
+
+    def call(n=100, batch=1, K_=Kc, model=p, mask_in=mask_a, err=p, agg=0, rounds=1, steps=20, mask_out=mask_b, info=p):
+        return lib.sfm_pnp_refine(p, n, batch, C.cast(K_, C.c_void_p) if K_ is not None else None, model, mask_in, err, 4.0,
+                                  agg, rounds, steps, p, mask_out, info, None)
+
+    assert call(n=-1) == -1
+    assert call(batch=-1) == -1
+    assert call(rounds=-1) == -1
+    assert call(steps=-1) == -1
+    assert call(n=1 << 31) == -1
+    assert call(agg=4) == -1
+    assert call(K_=Kbad) == -1 and b"row 2" in lib.sfm_last_error()
+    assert call(K_=None) == -1
+    assert call(model=None) == -1
+    assert call(err=None) == -1
+    assert call(info=None) == -1
+    assert call(mask_out=mask_a) == -1 and b"alias" in lib.sfm_last_error()
+    assert call(batch=0) == 0   # no-op
+
+
+def test_refine_ops_registered_with_meta_kernels(native_lib):
+    from structure_from_motion_amd import ops
+
+    op = ops.load()
+    assert "pnp_refine" in ops.FUNCTIONAL_OPS and "pnp_refine_" in ops.INPLACE_OPS
+    assert "Tensor(a!) model_out" in str(op.pnp_refine_.default._schema)
+    B, n = 3, 50
+    meta = dict(device="meta")
+    model, mask, info = op.pnp_refine(torch.empty((B, n, 5), dtype=torch.float64, **meta),
+                                      torch.empty((B, 12), dtype=torch.float64, **meta),
+                                      torch.empty((B, n), dtype=torch.uint8, **meta),
+                                      torch.empty((B,), dtype=torch.float64, **meta), [float(v) for v in K.reshape(9)],
+                                      4.0, 3, 1, 20)
+    assert model.shape == (B, 12) and model.dtype == torch.float64
+    assert mask.shape == (B, n) and mask.dtype == torch.uint8
+    assert info.shape == (B, 3) and info.dtype == torch.int64
+
+
+def test_refine_pose_pnp_validates_before_device_work(monkeypatch):
+    from structure_from_motion_amd import device
+
+    def no_device(*args, **kwargs):
+        raise AssertionError("device touched")
+
+    monkeypatch.setattr(device, "require_gpu", no_device)
+    monkeypatch.setattr(device, "to_device", no_device)
+    pts, R, t = po.scene(20, seed=5, K=K)
+    points = [row[:3] for row in pts]
+    feats = [Feature(row[3], row[4]) for row in pts]
+    matches = [Match(i, i) for i in range(20)]
+    with pytest.raises(ValueError, match="six"):
+        pnp.refine_pose_pnp(K, points, feats, matches[:5], R, t, 4.0)
+    with pytest.raises(ValueError, match="3x3"):
+        pnp.refine_pose_pnp(K[:2], points, feats, matches, R, t, 4.0)
+    K_bad = K.copy()
+    K_bad[2, 2] = 2.0
+    with pytest.raises(ValueError, match="row 2"):
+        pnp.refine_pose_pnp(K_bad, points, feats, matches, R, t, 4.0)
+    with pytest.raises(ValueError, match="R must be"):
+        pnp.refine_pose_pnp(K, points, feats, matches, R[:2], t, 4.0)
+    with pytest.raises(ValueError, match="R must be"):
+        pnp.refine_pose_pnp(K, points, feats, matches, R, t[:2], 4.0)
+    with pytest.raises(ValueError, match="rounds"):
+        pnp.refine_pose_pnp(K, points, feats, matches, R, t, 4.0, rounds=-1)
+    with pytest.raises(ValueError, match="max_steps"):
+        pnp.refine_pose_pnp(K, points, feats, matches, R, t, 4.0, max_steps=1.5)
+    with pytest.raises(ValueError, match="refine_rounds"):
+        pnp.estimate_pose_pnp_with_ransac(K, points, feats, matches, 4.0, refine_rounds=-2)
+
+
+def test_lib_reexports_refine_pose_pnp():
+    from lib.pnp import pnp as lib_pnp
+
+    assert lib_pnp.refine_pose_pnp is pnp.refine_pose_pnp

@@ -2,7 +2,11 @@
 second (points x hypotheses / time) at 50 000 x 100 000 and 5 000 x 10 000, one JSON line per size.
 
 ``--profile DIR`` instead re-runs this script (one size per run, under ``timeout``) below ``rocprofv3 --kernel-trace --stats``
-and prints the per-kernel split of its stats file.  Sizes: ``--sizes 50000x100000,5000x10000``."""
+and prints the per-kernel split of its stats file.  Sizes: ``--sizes 50000x100000,5000x10000``.
+
+``--refine`` instead times the refinement of the winner (``sfm_pnp_refine``, one round, at most 20 LM steps) at 5 000 and
+50 000 points for one view and a batch of 64 views: HIP events around the call, median of ``--steps`` calls, one JSON line
+per size (``--refine-sizes 5000x1,5000x64,50000x1,50000x64``, points x views)."""
 import argparse
 import csv
 import glob
@@ -16,6 +20,7 @@ sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tests"))
 
 SIZES = "50000x100000,5000x10000"
+REFINE_SIZES = "5000x1,5000x64,50000x1,50000x64"
 
 
 def time_pass(n: int, h: int, steps: int, warmup: int) -> dict:
@@ -46,6 +51,43 @@ def time_pass(n: int, h: int, steps: int, warmup: int) -> dict:
             "best_h": best.best_h, "extra_inliers": best.extra_inliers}
 
 
+def time_refine(n: int, batch: int, steps: int, warmup: int, rounds: int = 1, max_steps: int = 20) -> dict:
+    import numpy as np
+    import torch
+
+    import pnp_oracle as orc
+    from structure_from_motion_amd import device, synthetic
+    from structure_from_motion_amd._native import AGG_RMS
+
+    dev = device.require_gpu()
+    K = synthetic.BENCH_K
+    views = np.stack([orc.scene(n, seed=40 + b, K=K, outlier_fraction=0.3, noise_px=0.5)[0] for b in range(batch)])
+    pts = device.to_device(views).reshape(batch, n, 5)
+    ws = device.PnPWorkspace(batch, n, 256, dev)
+    ws.run(pts, K, 4.0, 10, AGG_RMS, philox=(7, 0, 1000))
+    best_h = ws.result[:, 1].clamp(min=0)
+    model = ws.model[torch.arange(batch, device=dev), best_h].contiguous()
+    err = ws.result[:, 2].contiguous().view(torch.float64)
+    call = lambda: device.pnp_refine(pts, model, ws.mask, err, K, 4.0, AGG_RMS, rounds, max_steps)  # noqa: E731
+    for _ in range(warmup):
+        call()
+    torch.cuda.synchronize()
+    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    times = []
+    for _ in range(steps):
+        start.record()
+        out = call()
+        end.record()
+        end.synchronize()
+        times.append(start.elapsed_time(end))
+    info = device.read_pnp_refine_info(out[2])
+    ms = sorted(times)[len(times) // 2]
+    return {"n": n, "views": batch, "rounds": rounds, "max_steps": max_steps, "steps": steps, "median_ms": ms,
+            "min_ms": min(times), "us_per_view": ms * 1e3 / batch,
+            "lm_steps_mean": float(np.mean([r.lm_steps for r in info])),
+            "accepted": sum(r.accepted > 0 for r in info), "inliers_mean": float(np.mean([r.count for r in info]))}
+
+
 def profile(out_dir: str, n: int, h: int, steps: int, warmup: int, limit: int) -> dict:
     run_dir = os.path.join(out_dir, f"{n}x{h}")
     os.makedirs(run_dir, exist_ok=True)
@@ -73,7 +115,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--profile", metavar="DIR")
     ap.add_argument("--limit", type=int, default=300, help="seconds per profiled run")
+    ap.add_argument("--refine", action="store_true", help="time the refinement of the winner instead of the pass")
+    ap.add_argument("--refine-sizes", default=REFINE_SIZES)
     args = ap.parse_args()
+    if args.refine:
+        for size in args.refine_sizes.split(","):
+            n, batch = (int(v) for v in size.split("x"))
+            print(json.dumps(time_refine(n, batch, args.steps, args.warmup)), flush=True)
+        return
     for size in args.sizes.split(","):
         n, h = (int(v) for v in size.split("x"))
         if args.profile:
