@@ -4,6 +4,9 @@ the triangulated points with ``estimate_pose_pnp_with_ransac``.  Points are proj
 the view-2 and view-3 observations are replaced by random pixels, and the recovered pose of view 3 is compared with ground
 truth in the scale of the two-view reconstruction (|t_2| = 1).  ``--refine K`` refines the view-3 pose on its inliers
 (``refine_rounds=K``) and also reports the unrefined pose's errors, from the same RANSAC draw, next to the refined ones.
+``--bundle-adjust N`` then adjusts all three cameras (camera 1 fixed) and the triangulated points together, at most N
+Levenberg-Marquardt steps, on views 1 and 2 of every triangulated point and view 3 of every PnP inlier, and reports the
+errors and the RMS reprojection error before and after.
 """
 from __future__ import annotations
 
@@ -16,6 +19,7 @@ import numpy as np
 from lib.common.feature import Feature
 from lib.epipolar.eight_point import create_trivial_matches, recover_r_t_from_e
 from lib.epipolar.epipolar_ransac import estimate_essential_mat_with_ransac
+from lib.bundle.bundle import bundle_adjust as adjust_bundle
 from lib.epipolar.triangulation import triangulate_points
 from lib.feature_matching.matching import Match
 from lib.pnp.pnp import estimate_pose_pnp_with_ransac
@@ -54,7 +58,7 @@ def rotation_angle(Ra: np.ndarray, Rb: np.ndarray) -> float:
 
 
 def run(n: int = 400, seed: int = 11, outlier_fraction: float = 0.3, noise_px: float = 0.0, sed_threshold: float = 1.5e-6,
-        reprojection_threshold: float = 4.0, iterations: int = 2000, refine: int = 0) -> dict:
+        reprojection_threshold: float = 4.0, iterations: int = 2000, refine: int = 0, bundle_adjust: int = 0) -> dict:
     scene = three_view_scene(n, seed, outlier_fraction, noise_px)
     K = scene["K"]
     features_a = [Feature(float(x), float(y)) for x, y in scene["pa"]]
@@ -86,6 +90,11 @@ def run(n: int = 400, seed: int = 11, outlier_fraction: float = 0.3, noise_px: f
         R3, t3, inliers = estimate_pose_pnp_with_ransac(K, points, features_c, matches, reprojection_threshold,
                                                         min_num_extra_inliers=10, max_iterations=iterations,
                                                         refine_rounds=refine)
+    adjusted = {}
+    if bundle_adjust > 0:
+        adjusted = _bundle_adjust(scene, K, points, kept, features_c, matches, R2, t2, R3, t3, reprojection_threshold,
+                                  bundle_adjust)
+        R2, t2, R3, t3 = adjusted.pop("R2"), adjusted.pop("t2"), adjusted.pop("R3"), adjusted.pop("t3")
     return {
         "points": n,
         "two_view_inliers": len(inlier_pairs),
@@ -97,6 +106,38 @@ def run(n: int = 400, seed: int = 11, outlier_fraction: float = 0.3, noise_px: f
         "R3": R3.tolist(),
         "t3": t3.tolist(),
         **unrefined,
+        **adjusted,
+    }
+
+
+def _bundle_adjust(scene, K, points, kept, features_c, matches, R2, t2, R3, t3, threshold, max_steps) -> dict:
+    """Bundle adjustment of the three views and the triangulated points (camera 1 fixed): views 1 and 2 of every point,
+    view 3 of every match whose squared reprojection error under (R3, t3) is at most ``threshold`` (the PnP inliers)."""
+    X = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    n = len(X)
+    uv_c = np.array([[features_c[m.b_index].x, features_c[m.b_index].y] for m in matches]).reshape(-1, 2)
+    xc = X @ R3.T + t3
+    with np.errstate(divide="ignore", invalid="ignore"):
+        e = np.sum(((xc @ K.T)[:, :2] / xc[:, 2:3] - uv_c) ** 2, axis=1)
+    inl = np.nonzero((xc[:, 2] > 0) & (e <= threshold))[0]
+    pixels = np.vstack([[[p[0].x, p[0].y] for p in kept], [[p[1].x, p[1].y] for p in kept], uv_c[inl]]).reshape(-1, 2)
+    cams = np.concatenate([np.zeros(n, np.int32), np.ones(n, np.int32), np.full(len(inl), 2, np.int32)])
+    pts = np.concatenate([np.arange(n), np.arange(n), inl]).astype(np.int32)
+    poses = np.array([np.concatenate([np.eye(3).reshape(9), np.zeros(3)]), np.concatenate([R2.reshape(9), t2.reshape(3)]),
+                      np.concatenate([R3.reshape(9), t3.reshape(3)])])
+    out, _, info = adjust_bundle(K, poses, X, cams, pts, pixels, fixed_cameras=(0,), max_steps=max_steps)
+    scale = np.linalg.norm(scene["t2"])
+    return {
+        "R2_error_rad_before_ba": rotation_angle(R2, scene["R2"]),
+        "R3_error_rad_before_ba": rotation_angle(R3, scene["R3"]),
+        "t3_error_before_ba": float(np.linalg.norm(t3 - scene["t3"] / scale)),
+        "rms_px_before_ba": float(np.sqrt(info.initial_cost / len(cams))),
+        "rms_px": float(np.sqrt(info.final_cost / len(cams))),
+        "ba_observations": len(cams),
+        "ba_status": info.status,
+        "ba_steps": info.steps,
+        "ba_accepted": info.accepted,
+        "R2": out[1, :9].reshape(3, 3), "t2": out[1, 9:], "R3": out[2, :9].reshape(3, 3), "t3": out[2, 9:],
     }
 
 
@@ -112,10 +153,13 @@ def main():
     ap.add_argument("--reprojection-threshold", type=float, default=4.0, help="PnP inlier threshold in pixels squared")
     ap.add_argument("--refine", type=int, default=0, metavar="K",
                     help="refine the view-3 pose on its inliers, K rounds (0: off); also reports the unrefined errors")
+    ap.add_argument("--bundle-adjust", type=int, default=0, metavar="N",
+                    help="bundle-adjust the three views and the points, at most N LM steps (0: off); also reports the "
+                         "errors before it")
     args = ap.parse_args()
     print(json.dumps(run(args.points, args.seed, args.outliers, args.noise, sed_threshold=args.sed_threshold,
                          reprojection_threshold=args.reprojection_threshold, iterations=args.iterations,
-                         refine=args.refine)))
+                         refine=args.refine, bundle_adjust=args.bundle_adjust)))
 
 
 if __name__ == "__main__":

@@ -355,6 +355,42 @@ int sfm_pnp_refine(const double* pts, int64_t n, int64_t batch, const double* K,
                    const double* err_in, double thr, int aggregation, int rounds, int max_steps, double* model_out,
                    uint8_t* mask_out, sfm_pnp_refine_info* info, void* stream);
 
+/* ---- bundle adjustment of cameras and points (csrc/sfm_bundle.hip; an extension, off unless asked for) ----
+ * These symbols were added under ABI 14 without a version change: they are new, and nothing an ABI-14 caller uses changed. */
+
+#define SFM_BUNDLE_OK 0
+#define SFM_BUNDLE_BAD_START 1 /* the starting cost is not finite (a point behind a camera, a NaN): output = input */
+#define SFM_BUNDLE_BAD_INDEX 2 /* a camera or point index is out of range: output = input */
+
+typedef struct sfm_bundle_info {
+    double initial_cost; /* cost of the input (NaN for SFM_BUNDLE_BAD_INDEX) */
+    double final_cost;   /* cost of the last accepted trial (= initial_cost when none was accepted) */
+    int32_t steps;       /* Levenberg-Marquardt trial steps */
+    int32_t accepted;    /* accepted steps */
+    int32_t status;      /* SFM_BUNDLE_* */
+    int32_t reserved;    /* 0 */
+} sfm_bundle_info;
+
+/* Bytes of workspace sfm_bundle_adjust needs; -1 for sizes it refuses. */
+int64_t sfm_bundle_workspace_bytes(int64_t cameras, int64_t points, int64_t observations);
+
+/* Levenberg-Marquardt on F = sum over the observations m of e_m, e the squared reprojection error of sfm_pnp_score (+inf
+ * behind the camera), over every camera c with fixed[c] == 0 (R <- exp([w]x) R, t <- t + dt) and every point with at least
+ * two observations (X <- X + dX); the other points and the fixed cameras are held.  Damping lambda diag(H) from 1e-3 (/10 on
+ * an accepted step, *10 otherwise; a damped system that does not factor is a rejected step); at most max_steps trial steps,
+ * stop at lambda > 1e16, on an accepted step that lowers F by less than 1e-12 of F, or on a step |delta| <= 1e-12 (1 + |x|).
+ * With exactly one fixed camera, every accepted step is followed by a similarity about that camera's centre that restores the
+ * input distance from it to the lowest-index free camera's centre: every point and every free camera's centre scale by the
+ * same factor (F does not change).  The whole call is enqueued at once; the LM state stays on the device.
+ * K: host [9], row 2 (0, 0, 1); fixed: host uint8 [cameras], at least one non-zero; poses_in / poses_out: dev [cameras,12]
+ * (R | t, world -> camera); points_in / points_out: dev [points,3] (either may alias its input); camera_index, point_index:
+ * dev int32 [observations]; pixels: dev [observations,2]; info: dev, one record; workspace: dev, 16-byte aligned, at least
+ * sfm_bundle_workspace_bytes.  cameras <= 64; points, observations < 2^31. */
+int sfm_bundle_adjust(const double* K, int64_t cameras, int64_t points, int64_t observations, const uint8_t* fixed,
+                      const double* poses_in, const double* points_in, const int32_t* camera_index,
+                      const int32_t* point_index, const double* pixels, int max_steps, double* poses_out,
+                      double* points_out, sfm_bundle_info* info, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* SED of n correspondences under one E (sed.py:7-30).  E: dev [9]; out: dev [n]. */
 int sfm_sed_values(const double* corr, int64_t n, const double* E, double* out, void* stream);
 

@@ -1,0 +1,83 @@
+"""Bundle adjustment of camera poses and 3-D points on the GPU (``sfm_bundle_adjust``).
+
+Poses are ``R (9) | t (3)`` rows with ``x_cam = R X + t`` — the PnP model layout.  All cameras share one camera matrix
+``K`` whose row 2 is (0, 0, 1); intrinsics are not optimised.  The cost is the sum over the observations of the squared
+reprojection error of the PnP scorer.  Fixed cameras and points with fewer than two observations are held; with exactly
+one fixed camera the scale is held by the distance from it to the lowest-index free camera.
+"""
+from __future__ import annotations
+
+from typing import Sequence, Tuple
+
+import numpy as np
+import numpy.typing as npt
+
+from ..pnp.pnp import check_camera_matrix
+
+MAX_CAMERAS = 64
+_INT32 = 2**31
+
+
+def _array(value, name: str, shape: Tuple[int, ...]) -> npt.NDArray:
+    a = np.asarray(value, dtype=np.float64)
+    if a.ndim != len(shape) or any(want not in (-1, got) for want, got in zip(shape, a.shape)):
+        raise ValueError(f"{name} must have shape {tuple('N' if s < 0 else s for s in shape)}, got {a.shape}")
+    return a
+
+
+def _indices(value, name: str, m: int) -> npt.NDArray:
+    a = np.asarray(value)
+    if a.shape != (m,):
+        raise ValueError(f"{name} must have one entry per pixel ({m}), got shape {a.shape}")
+    if m and not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"{name} must be integers, got {a.dtype}")
+    if m and (a.min() < -_INT32 or a.max() >= _INT32):
+        raise ValueError(f"{name} must fit in 32 bits")
+    return a.astype(np.int32)
+
+
+def bundle_adjust(
+    camera_matrix: npt.NDArray,
+    poses: npt.NDArray,
+    points_3d: npt.NDArray,
+    camera_indices: Sequence[int],
+    point_indices: Sequence[int],
+    pixels: npt.NDArray,
+    fixed_cameras: Sequence[int] = (0,),
+    max_steps: int = 50,
+):
+    """Minimise the summed squared reprojection error over the free cameras' poses and the points.
+
+    ``poses`` (C, 12), ``points_3d`` (P, 3); observation m is pixel ``pixels[m]`` of point ``point_indices[m]`` in camera
+    ``camera_indices[m]``.  At most 64 cameras, at least one of them in ``fixed_cameras``; at most ``max_steps`` LM trial
+    steps.  Returns ``(poses (C, 12), points (P, 3), info)`` with ``info`` a ``device.BundleInfo``.  An input whose cost
+    is not finite (a point behind a camera), or an index out of range, comes back unchanged with ``info.status`` set
+    (``device.BUNDLE_BAD_START`` / ``BUNDLE_BAD_INDEX``).  Every argument is checked before any device work."""
+    K = check_camera_matrix(camera_matrix)
+    poses = _array(poses, "poses", (-1, 12))
+    points = _array(points_3d, "points_3d", (-1, 3))
+    pixels = _array(pixels, "pixels", (-1, 2))
+    m = pixels.shape[0]
+    cams = _indices(camera_indices, "camera_indices", m)
+    pts = _indices(point_indices, "point_indices", m)
+    n_cams = poses.shape[0]
+    if not 1 <= n_cams <= MAX_CAMERAS:
+        raise ValueError(f"between 1 and {MAX_CAMERAS} cameras are supported, got {n_cams}")
+    if points.shape[0] >= _INT32 or m >= _INT32:
+        raise ValueError("points and observations must number fewer than 2^31")
+    fixed = [int(c) for c in fixed_cameras]
+    if not fixed:
+        raise ValueError("at least one camera must be fixed")
+    if any(not 0 <= c < n_cams for c in fixed) or len(set(fixed)) != len(fixed):
+        raise ValueError(f"fixed_cameras must be distinct camera indices in [0, {n_cams}), got {fixed}")
+    if isinstance(max_steps, bool) or not isinstance(max_steps, (int, np.integer)) or max_steps < 0:
+        raise ValueError(f"max_steps must be a non-negative integer, got {max_steps!r}")
+    import torch
+
+    from .. import device
+
+    device.require_gpu()
+    poses_d, points_d, info = device.bundle_adjust(
+        device.to_device(poses), device.to_device(points), device.to_device(cams, dtype=torch.int32),
+        device.to_device(pts, dtype=torch.int32), device.to_device(pixels), K, fixed, int(max_steps))
+    return poses_d.cpu().numpy(), points_d.cpu().numpy(), device.read_bundle_info(info)

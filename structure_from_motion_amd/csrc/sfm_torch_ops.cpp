@@ -7,7 +7,7 @@
 // kernel, so fake-tensor tracing / torch.compile / opcheck work) and, where the engine pre-allocates its buffers
 // (device.RansacWorkspace), an in-place `_`-suffixed form with mutable arguments, plus the fused
 // sample_fit_philox_; and the PnP ops (sfm_pnp.hip) pnp_fit, pnp_score and the whole pass pnp_ransac_pass_, and the
-// refinement of a winner pnp_refine (sfm_pnp_refine.hip).  The reference call sites these serve: apps/sfm.py:110-119 (RANSAC-E), :133-138 (pose),
+// refinement of a winner pnp_refine (sfm_pnp_refine.hip), and bundle_adjust (sfm_bundle.hip).  The reference call sites these serve: apps/sfm.py:110-119 (RANSAC-E), :133-138 (pose),
 // :181-186 (triangulation).
 //
 // Built by structure_from_motion_amd/build.py into csrc/libsfm_torch_ops.so (host code only: no kernels here).
@@ -17,6 +17,7 @@
 #include <torch/library.h>
 
 #include <tuple>
+#include <vector>
 
 #include "../../include/sfm_hip.h"
 
@@ -553,6 +554,74 @@ std::tuple<Tensor, Tensor, Tensor> pnp_refine_meta(const Tensor& pts, const Tens
             at::empty_symint({pts.sym_size(0), pts.sym_size(1)}, like(pts, at::kByte)),
             at::empty_symint({pts.sym_size(0), c10::SymInt(kRefineInfoWords)}, like(pts, at::kLong))};
 }
+
+// bundle adjustment (sfm_bundle.hip): poses [C, 12], points [P, 3], camera / point indices int32 [M], pixels [M, 2];
+// fixed: the indices of the fixed cameras; info int64 [4] viewing the sfm_bundle_info record.  The workspace comes from
+// the caching allocator, stream-ordered like everything else (no host synchronisation).
+constexpr int64_t kBundleInfoWords = sizeof(sfm_bundle_info) / 8;
+
+void bundle_check(const Tensor& poses, const Tensor& points, const Tensor& cam, const Tensor& pt, const Tensor& pixels,
+                  at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed, int64_t max_steps) {
+    check_K(K);
+    TORCH_CHECK(poses.dim() == 2 && poses.size(1) == 12, "sfm_hip: poses must be [C, 12]");
+    TORCH_CHECK(points.dim() == 2 && points.size(1) == 3, "sfm_hip: points must be [P, 3]");
+    TORCH_CHECK(cam.dim() == 1 && pt.dim() == 1 && cam.size(0) == pt.size(0), "sfm_hip: camera and point indices must be [M]");
+    TORCH_CHECK(pixels.dim() == 2 && pixels.size(1) == 2 && pixels.size(0) == cam.size(0), "sfm_hip: pixels must be [M, 2]");
+    TORCH_CHECK(max_steps >= 0 && max_steps <= 0x7FFFFFFF, "sfm_hip: max_steps must be in [0, 2^31)");
+    for (int64_t c : fixed) TORCH_CHECK(c >= 0 && c < poses.size(0), "sfm_hip: fixed camera ", c, " out of range");
+}
+
+void bundle_adjust_out(Tensor& poses, Tensor& points, const Tensor& cam, const Tensor& pt, const Tensor& pixels,
+                       at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed, int64_t max_steps, Tensor& info,
+                       const Tensor& poses_in, const Tensor& points_in) {
+    const OpDevice scope(poses);
+    need(poses, "poses", at::kDouble);
+    need(points, "points", at::kDouble);
+    need(poses_in, "poses", at::kDouble);
+    need(points_in, "points", at::kDouble);
+    need(cam, "camera_indices", at::kInt);
+    need(pt, "point_indices", at::kInt);
+    need(pixels, "pixels", at::kDouble);
+    need(info, "info", at::kLong);
+    bundle_check(poses_in, points_in, cam, pt, pixels, K, fixed, max_steps);
+    TORCH_CHECK(poses.sizes() == poses_in.sizes() && points.sizes() == points_in.sizes(), "sfm_hip: output shapes differ");
+    TORCH_CHECK(info.numel() == kBundleInfoWords, "sfm_hip: info must be int64 [4]");
+    const int64_t C = poses.size(0), P = points.size(0), M = cam.size(0);
+    std::vector<uint8_t> mask((size_t)C, 0);
+    for (int64_t c : fixed) mask[(size_t)c] = 1;
+    const int64_t bytes = sfm_bundle_workspace_bytes(C, P, M);
+    TORCH_CHECK(bytes >= 0, "sfm_hip: bundle_adjust: ", C, " cameras, ", P, " points, ", M,
+                " observations exceed the limits (C <= 64, P and M < 2^31)");
+    Tensor ws = at::empty({bytes}, like(poses, at::kByte));
+    ok(sfm_bundle_adjust(K.data(), C, P, M, mask.data(), ptr<double>(poses_in), ptr<double>(points_in), ptr<int32_t>(cam),
+                         ptr<int32_t>(pt), ptr<double>(pixels), (int)max_steps, ptr<double>(poses), ptr<double>(points),
+                         reinterpret_cast<sfm_bundle_info*>(ptr<int64_t>(info)), ws.data_ptr(), bytes, current_stream()),
+       "sfm_bundle_adjust");
+}
+
+void bundle_adjust_inplace(Tensor& poses, Tensor& points, const Tensor& cam, const Tensor& pt, const Tensor& pixels,
+                           at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed, int64_t max_steps, Tensor& info) {
+    bundle_adjust_out(poses, points, cam, pt, pixels, K, fixed, max_steps, info, poses, points);
+}
+
+std::tuple<Tensor, Tensor, Tensor> bundle_adjust(const Tensor& poses, const Tensor& points, const Tensor& cam, const Tensor& pt,
+                                                 const Tensor& pixels, at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed,
+                                                 int64_t max_steps) {
+    bundle_check(poses, points, cam, pt, pixels, K, fixed, max_steps);
+    Tensor poses_out = at::empty_like(poses);
+    Tensor points_out = at::empty_like(points);
+    Tensor info = at::empty({kBundleInfoWords}, like(poses, at::kLong));
+    bundle_adjust_out(poses_out, points_out, cam, pt, pixels, K, fixed, max_steps, info, poses, points);
+    return {poses_out, points_out, info};
+}
+
+std::tuple<Tensor, Tensor, Tensor> bundle_adjust_meta(const Tensor& poses, const Tensor& points, const Tensor& cam,
+                                                      const Tensor& pt, const Tensor& pixels, at::ArrayRef<double> K,
+                                                      at::ArrayRef<int64_t> fixed, int64_t max_steps) {
+    bundle_check(poses, points, cam, pt, pixels, K, fixed, max_steps);
+    return {at::empty_like(poses), at::empty_like(points),
+            at::empty_symint({c10::SymInt(kBundleInfoWords)}, like(poses, at::kLong))};
+}
 }  // namespace
 
 // the C-ABI version this op library was compiled against (include/sfm_hip.h); ops.load() compares it with the
@@ -596,6 +665,10 @@ TORCH_LIBRARY(sfm_hip, m) {
           "int max_steps) -> (Tensor, Tensor, Tensor)");
     m.def("pnp_refine_(Tensor pts, Tensor model, Tensor mask, Tensor err, float[] K, float thr, int aggregation, int rounds, "
           "int max_steps, Tensor(a!) model_out, Tensor(b!) mask_out, Tensor(c!) info) -> ()");
+    m.def("bundle_adjust(Tensor poses, Tensor points, Tensor camera_indices, Tensor point_indices, Tensor pixels, float[] K, "
+          "int[] fixed, int max_steps) -> (Tensor, Tensor, Tensor)");
+    m.def("bundle_adjust_(Tensor(a!) poses, Tensor(b!) points, Tensor camera_indices, Tensor point_indices, Tensor pixels, "
+          "float[] K, int[] fixed, int max_steps, Tensor(c!) info) -> ()");
 }
 
 // ROCm devices dispatch under torch's "CUDA" key (the name of the dispatch key, not a CUDA code path)
@@ -622,6 +695,8 @@ TORCH_LIBRARY_IMPL(sfm_hip, CUDA, m) {
     m.impl("pnp_ransac_pass_", &pnp_ransac_pass_out);
     m.impl("pnp_refine", &pnp_refine);
     m.impl("pnp_refine_", &pnp_refine_out);
+    m.impl("bundle_adjust", &bundle_adjust);
+    m.impl("bundle_adjust_", &bundle_adjust_inplace);
 }
 
 // sample_philox has no tensor argument to dispatch on: registered for every backend, it checks its device itself
@@ -646,6 +721,8 @@ void pnp_ransac_pass_out_meta(const Tensor&, int64_t, int64_t, bool, int64_t, at
                               Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, const std::optional<Tensor>&) {}
 void pnp_refine_out_meta(const Tensor&, const Tensor&, const Tensor&, const Tensor&, at::ArrayRef<double>, double, int64_t, int64_t,
                          int64_t, Tensor&, Tensor&, Tensor&) {}
+void bundle_adjust_out_meta(Tensor&, Tensor&, const Tensor&, const Tensor&, const Tensor&, at::ArrayRef<double>, at::ArrayRef<int64_t>,
+                            int64_t, Tensor&) {}
 
 TORCH_LIBRARY_IMPL(sfm_hip, Meta, m) {
     m.impl("normalize_coords_", &normalize_coords_out_meta);
@@ -670,4 +747,6 @@ TORCH_LIBRARY_IMPL(sfm_hip, Meta, m) {
     m.impl("pnp_ransac_pass_", &pnp_ransac_pass_out_meta);
     m.impl("pnp_refine", &pnp_refine_meta);
     m.impl("pnp_refine_", &pnp_refine_out_meta);
+    m.impl("bundle_adjust", &bundle_adjust_meta);
+    m.impl("bundle_adjust_", &bundle_adjust_out_meta);
 }

@@ -694,6 +694,44 @@ def read_pnp_refine_info(info: torch.Tensor) -> List[PnPRefineInfo]:
             for i in range(raw.shape[0])]
 
 
+# ------------------------------------------------------------------------------------------------------
+# bundle adjustment (csrc/sfm_bundle.hip): poses [C,12] = R (9) | t (3) world -> camera, points [P,3], observations
+# (camera index, point index) int32 [M] each and pixels [M,2]
+# ------------------------------------------------------------------------------------------------------
+def bundle_adjust(poses, points, camera_indices, point_indices, pixels, K, fixed=(0,), max_steps: int = 50, out=None):
+    """Levenberg-Marquardt over the free cameras and the points seen at least twice (``sfm_bundle_adjust``) ->
+    (poses [C,12], points [P,3], info int64 [4] viewing the sfm_bundle_info record; ``read_bundle_info``).  ``out`` =
+    (poses, points, info) runs the in-place op on those tensors instead (poses and points there are the input).  No host
+    synchronisation: the whole call is enqueued at once."""
+    op = ops.load()
+    args = (camera_indices.contiguous(), point_indices.contiguous(), pixels.contiguous(), _camera_list(K),
+            [int(c) for c in fixed], int(max_steps))
+    if out is None:
+        return op.bundle_adjust(poses.contiguous(), points.contiguous(), *args)
+    op.bundle_adjust_(out[0], out[1], *args, out[2])
+    return out
+
+
+@dataclass
+class BundleInfo:
+    initial_cost: float   # cost of the input (NaN when an index is out of range)
+    final_cost: float     # cost of the last accepted trial (initial_cost when none was accepted)
+    steps: int            # Levenberg-Marquardt trial steps
+    accepted: int         # accepted steps
+    status: int           # BUNDLE_OK, BUNDLE_BAD_START or BUNDLE_BAD_INDEX
+
+
+BUNDLE_OK, BUNDLE_BAD_START, BUNDLE_BAD_INDEX = 0, 1, 2
+
+
+def read_bundle_info(info: torch.Tensor) -> BundleInfo:
+    """Host copy of an sfm_bundle_info record (int64 [4]) (synchronises)."""
+    raw = info.cpu().numpy()
+    costs = raw[0:2].view(np.float64)
+    ints = raw[2:4].view(np.int32)
+    return BundleInfo(float(costs[0]), float(costs[1]), int(ints[0]), int(ints[1]), int(ints[2]))
+
+
 @dataclass
 class PnPOutcome:
     best_h: int                # winning hypothesis, -1 if none

@@ -41,3 +41,45 @@ def two_view_scene(n: int, seed: int = 6, outlier_fraction: float = 0.3, noise_p
     rand_px = np.column_stack([rng.uniform(0, width, n), rng.uniform(0, height, n)])
     pb = np.where(is_out[:, None], rand_px, pb)
     return pa, pb, K, R, t, is_out
+
+
+def _small_rotation(rng, sigma: float) -> np.ndarray:
+    """exp([w]x) for w ~ N(0, sigma^2 I) (Rodrigues)."""
+    w = rng.normal(0.0, sigma, 3)
+    th = float(np.linalg.norm(w))
+    W = np.array([[0.0, -w[2], w[1]], [w[2], 0.0, -w[0]], [-w[1], w[0], 0.0]])
+    if th == 0.0:
+        return np.eye(3)
+    return np.eye(3) + np.sin(th) / th * W + (1.0 - np.cos(th)) / th**2 * (W @ W)
+
+
+def bundle_problem(cameras: int, points: int, per_point: int = 4, seed: int = 0, noise_px: float = 0.5,
+                   rotation_noise: float = 0.003, translation_noise: float = 0.01, point_noise: float = 0.01,
+                   K: np.ndarray = BENCH_K):
+    """A bundle-adjustment input: points uniform in x, y in [-1, 1], z in [4, 6]; camera 0 = [I | 0], the others rotated by
+    up to 5 / 10 degrees about X / Y and shifted by up to 0.5 in x, 0.2 in y and z.  Each point is seen by
+    min(per_point, cameras) distinct cameras, with Gaussian pixel noise; the observations come in random order.  The start
+    perturbs every camera but camera 0 (rotation and translation) and every point.  Returns dict(K, poses (C, 12), points
+    (P, 3), camera_indices, point_indices (M,), pixels (M, 2), poses_true, points_true)."""
+    rng = np.random.default_rng(seed)
+    X = np.column_stack([rng.uniform(-1.0, 1.0, points), rng.uniform(-1.0, 1.0, points), rng.uniform(4.0, 6.0, points)])
+    poses = np.zeros((cameras, 12))
+    poses[0, :9] = np.eye(3).reshape(9)
+    for c in range(1, cameras):
+        poses[c, :9] = rotation_xy(rng.uniform(-5.0, 5.0), rng.uniform(-10.0, 10.0)).reshape(9)
+        poses[c, 9:] = [rng.uniform(-0.5, 0.5), rng.uniform(-0.2, 0.2), rng.uniform(-0.2, 0.2)]
+    k = min(per_point, cameras)
+    cam = np.argsort(rng.random((points, cameras)), axis=1)[:, :k].reshape(-1)
+    pt = np.repeat(np.arange(points), k)
+    order = rng.permutation(len(cam))
+    cam, pt = cam[order], pt[order]
+    R = poses[cam, :9].reshape(-1, 3, 3)
+    xc = np.einsum("mij,mj->mi", R, X[pt]) + poses[cam, 9:]
+    uvw = xc @ K.T
+    pixels = uvw[:, :2] / uvw[:, 2:3] + rng.normal(0.0, noise_px, (len(cam), 2))
+    start = poses.copy()
+    for c in range(1, cameras):
+        start[c, :9] = (_small_rotation(rng, rotation_noise) @ poses[c, :9].reshape(3, 3)).reshape(9)
+        start[c, 9:] += rng.normal(0.0, translation_noise, 3)
+    return dict(K=K, poses=start, points=X + rng.normal(0.0, point_noise, X.shape), camera_indices=cam.astype(np.int32),
+                point_indices=pt.astype(np.int32), pixels=pixels, poses_true=poses, points_true=X)

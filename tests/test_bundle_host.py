@@ -1,0 +1,277 @@
+"""Bundle adjustment, host side: the NumPy oracle of tests/bundle_oracle.py (its two solvers, its gradient, its gauge rules
+and what it does for the three-view scene), the C-ABI export and its refusals before any launch, the op registration with
+its Meta kernels and the argument checks of the public API (no GPU)."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+import bundle_oracle as bo
+import pnp_refine_oracle as ro
+from oracle import sfm_oracle
+from structure_from_motion_amd import synthetic
+
+K = synthetic.BENCH_K
+
+
+def _adjust(pr, **kw):
+    return bo.adjust(pr["K"], pr["poses"], pr["points"], pr["camera_indices"], pr["point_indices"], pr["pixels"], **kw)
+
+
+def _drop_to_one_observation(pr, point):
+    keep = pr["point_indices"] != point
+    keep[np.nonzero(~keep)[0][0]] = True
+    return dict(pr, camera_indices=pr["camera_indices"][keep], point_indices=pr["point_indices"][keep],
+                pixels=pr["pixels"][keep])
+
+
+@pytest.mark.parametrize("C,P,fixed", [(3, 60, (0,)), (5, 120, (1,)), (6, 100, (0, 3)), (4, 80, (0, 1, 2))])
+def test_dense_and_schur_solvers_agree(C, P, fixed):
+    pr = _drop_to_one_observation(synthetic.bundle_problem(C, P, per_point=3, seed=C + P), 5)
+    dense = _adjust(pr, fixed=fixed, max_steps=30, solver="dense")
+    schur = _adjust(pr, fixed=fixed, max_steps=30, solver="schur")
+    assert dense["accepted"] == schur["accepted"] >= 2 and dense["steps"] == schur["steps"]
+    assert abs(dense["final_cost"] - schur["final_cost"]) <= 1e-9 * dense["final_cost"]
+    assert np.max(np.abs(dense["poses"] - schur["poses"])) <= 1e-9
+    assert np.max(np.abs(dense["points"] - schur["points"])) <= 1e-9
+
+
+def test_gradient_matches_finite_differences():
+    """g = J^T r is half the gradient of F = sum e, along the LM parametrisation of a free camera and of a point."""
+    pr = synthetic.bundle_problem(4, 50, per_point=3, seed=3)
+    prob = bo.Problem(K, pr["poses"], pr["points"], pr["camera_indices"], pr["point_indices"], pr["pixels"], (0,))
+    s = prob.system(pr["poses"], pr["points"])
+
+    def F(poses, points):
+        return bo.cost(poses, points, prob.cam, prob.pt, prob.uv, K)
+
+    h = 1e-6
+    for c in (1, 3):
+        fd = np.zeros(6)
+        for k in range(6):
+            vals = []
+            for sign in (1.0, -1.0):
+                d = np.zeros(6)
+                d[k] = sign * h
+                R, t = ro.apply_step(pr["poses"][c, :9].reshape(3, 3), pr["poses"][c, 9:], d)
+                poses = pr["poses"].copy()
+                poses[c] = np.concatenate([R.reshape(9), t])
+                vals.append(F(poses, pr["points"]))
+            fd[k] = (vals[0] - vals[1]) / (4.0 * h)
+        assert np.max(np.abs(fd - s["gc"][c])) <= 1e-5 * np.max(np.abs(s["gc"][c])), c
+    for p in (0, 17):
+        fd = np.zeros(3)
+        for k in range(3):
+            plus, minus = pr["points"].copy(), pr["points"].copy()
+            plus[p, k] += h
+            minus[p, k] -= h
+            fd[k] = (F(pr["poses"], plus) - F(pr["poses"], minus)) / (4.0 * h)
+        assert np.max(np.abs(fd - s["gp"][p])) <= 1e-5 * np.max(np.abs(s["gp"][p])), p
+
+
+def _three_view_start(seed):
+    """The three-view app scene (200 points, 0.5 px, every point in all three views) from a start with R2 and R3 off by
+    the size of error the app reports, t2 and t3 off by 0.01-0.02 and the points re-triangulated from views 1-2."""
+    from apps.sfm_three_view import three_view_scene
+
+    sc = three_view_scene(200, seed, outlier_fraction=0.0, noise_px=0.5)
+    rng = np.random.default_rng(seed)
+    scale = np.linalg.norm(sc["t2"])
+
+    def perturb(R, t, angle):
+        w = rng.normal(size=3)
+        R1, _ = ro.apply_step(R, t, np.concatenate([angle * w / np.linalg.norm(w), np.zeros(3)]))
+        d = rng.normal(size=3)
+        return R1, t / scale + rng.uniform(0.01, 0.02) * d / np.linalg.norm(d)
+
+    R2, t2 = perturb(sc["R2"], sc["t2"], 0.0075)
+    t2 /= np.linalg.norm(t2)
+    R3, t3 = perturb(sc["R3"], sc["t3"], 0.01)
+    T = np.eye(4)
+    T[:3, :3], T[:3, 3] = R2, t2
+    X = sfm_oracle.triangulate_points(sc["pa"], sc["pb"], K, T)
+    n = len(X)
+    poses = np.array([np.concatenate([np.eye(3).reshape(9), np.zeros(3)]), np.concatenate([R2.reshape(9), t2]),
+                      np.concatenate([R3.reshape(9), t3])])
+    cam = np.repeat([0, 1, 2], n)
+    pt = np.tile(np.arange(n), 3)
+    return sc, poses, X, cam, pt, np.vstack([sc["pa"], sc["pb"], sc["pc"]])
+
+
+def _rot_err(Ra, Rb):
+    return float(np.arccos(np.clip((np.trace(Ra @ Rb.T) - 1.0) / 2.0, -1.0, 1.0)))
+
+
+@pytest.mark.parametrize("seed", [11, 12, 13])
+def test_oracle_brings_three_view_scene_to_noise_floor(seed):
+    sc, poses, X, cam, pt, uv = _three_view_start(seed)
+    out = bo.adjust(K, poses, X, cam, pt, uv, fixed=(0,), max_steps=50)
+    scale = np.linalg.norm(sc["t2"])
+    assert out["status"] == bo.OK and out["accepted"] >= 2
+    # 600 observations, 0.5 px: sigma^2 (2M - 3P - 11) = 0.25 * 589 = 147 in expectation
+    assert 100.0 < out["final_cost"] < 200.0, out["final_cost"]
+    for c, R_true in ((1, sc["R2"]), (2, sc["R3"])):
+        before = _rot_err(poses[c, :9].reshape(3, 3), R_true)
+        after = _rot_err(out["poses"][c, :9].reshape(3, 3), R_true)
+        assert after < 0.5 * before and after < 0.003, (c, before, after)
+    t3_before = np.linalg.norm(poses[2, 9:] - sc["t3"] / scale)
+    t3_after = np.linalg.norm(out["poses"][2, 9:] - sc["t3"] / scale)
+    assert t3_after < 0.5 * t3_before and t3_after < 0.01
+
+
+def test_oracle_gauge_rules():
+    pr = _drop_to_one_observation(synthetic.bundle_problem(5, 200, per_point=3, seed=8), 9)
+    out = _adjust(pr, fixed=(3,))
+    assert out["accepted"] >= 2
+    assert np.array_equal(out["poses"][3], pr["poses"][3])
+    c0 = bo.centre(pr["poses"][3])
+    before = np.linalg.norm(bo.centre(pr["poses"][0]) - c0)
+    assert abs(np.linalg.norm(bo.centre(out["poses"][0]) - c0) - before) <= 1e-12 * before
+    two = _adjust(pr, fixed=(0, 3))
+    assert np.array_equal(two["points"][9], pr["points"][9])
+    assert np.array_equal(two["poses"][0], pr["poses"][0]) and np.array_equal(two["poses"][3], pr["poses"][3])
+    none = _adjust(pr, max_steps=0)
+    assert none["steps"] == 0 and np.array_equal(none["poses"], pr["poses"])
+
+
+def test_oracle_bad_start_and_bad_index():
+    pr = synthetic.bundle_problem(3, 40, per_point=3, seed=2)
+    behind = pr["points"].copy()
+    behind[3, 2] = -2.0
+    out = bo.adjust(K, pr["poses"], behind, pr["camera_indices"], pr["point_indices"], pr["pixels"])
+    assert out["status"] == bo.BAD_START and np.array_equal(out["points"], behind)
+    cam = pr["camera_indices"].copy()
+    cam[0] = 3
+    out = bo.adjust(K, pr["poses"], pr["points"], cam, pr["point_indices"], pr["pixels"])
+    assert out["status"] == bo.BAD_INDEX and np.array_equal(out["poses"], pr["poses"])
+
+
+def test_bundle_symbols_exported_and_bound(native_lib):
+    from structure_from_motion_amd import _native
+
+    assert _native.ABI_VERSION == 14 and native_lib.sfm_abi_version() == 14
+    assert "sfm_bundle_adjust" in _native.SIGNATURES and "sfm_bundle_workspace_bytes" in _native.OTHER_SYMBOLS
+    assert hasattr(native_lib, "sfm_bundle_adjust")
+    assert native_lib.sfm_bundle_workspace_bytes(16, 20000, 80000) > 80000 * 18 * 8
+    assert native_lib.sfm_bundle_workspace_bytes(65, 10, 10) == -1
+    assert native_lib.sfm_bundle_workspace_bytes(0, 10, 10) == -1
+    assert native_lib.sfm_bundle_workspace_bytes(4, -1, 10) == -1
+    assert native_lib.sfm_bundle_workspace_bytes(4, 10, 1 << 31) == -1
+
+
+def test_bundle_rejects_bad_arguments_before_launch(native_lib):
+    """Every refusal happens on the host before the launch (no GPU needed): device pointers are never dereferenced."""
+    lib = native_lib
+    Kc = (C.c_double * 9)(*[float(v) for v in K.reshape(9)])
+    Kbad = (C.c_double * 9)(*[float(v) for v in K.reshape(9)])
+    Kbad[7] = 0.5
+    p = C.c_void_p(0x1000)   # never dereferenced: every call below is refused before the launch
+
+    def call(cams=4, pts=100, obs=400, K_=Kc, fixed=(1, 0, 0, 0), steps=10, poses=p, points=p, cam=p, pt=p, pix=p, info=p,
+             ws=p, ws_bytes=1 << 40):
+        fx = (C.c_uint8 * max(1, len(fixed)))(*fixed) if fixed is not None else None
+        return lib.sfm_bundle_adjust(C.cast(K_, C.c_void_p) if K_ is not None else None, cams, pts, obs,
+                                     C.cast(fx, C.c_void_p) if fx is not None else None, poses, points, cam, pt, pix,
+                                     steps, poses, points, info, ws, ws_bytes, None)
+
+    assert call(cams=0) == -1
+    assert call(cams=65, fixed=(1,) * 65) == -1 and b"64" in lib.sfm_last_error()
+    assert call(pts=-1) == -1
+    assert call(obs=-1) == -1
+    assert call(steps=-1) == -1
+    assert call(pts=1 << 31) == -1
+    assert call(obs=1 << 31) == -1
+    assert call(K_=Kbad) == -1 and b"row 2" in lib.sfm_last_error()
+    assert call(K_=None) == -1
+    assert call(fixed=None) == -1
+    assert call(fixed=(0, 0, 0, 0)) == -1 and b"fixed" in lib.sfm_last_error()
+    assert call(poses=None) == -1 and b"null" in lib.sfm_last_error()
+    assert call(points=None) == -1
+    assert call(cam=None) == -1
+    assert call(pt=None) == -1
+    assert call(pix=None) == -1
+    assert call(info=None) == -1
+    assert call(ws=None) == -1
+    assert call(ws_bytes=1000) == -1 and b"workspace" in lib.sfm_last_error()
+    assert call(ws=C.c_void_p(0x1008)) == -1 and b"aligned" in lib.sfm_last_error()
+
+
+def test_bundle_ops_registered_with_meta_kernels(native_lib):
+    from structure_from_motion_amd import ops
+
+    op = ops.load()
+    assert "bundle_adjust" in ops.FUNCTIONAL_OPS and "bundle_adjust_" in ops.INPLACE_OPS
+    assert "Tensor(a!) poses" in str(op.bundle_adjust_.default._schema)
+    meta = dict(device="meta")
+    Cn, P, M = 7, 300, 1200
+    poses, points, info = op.bundle_adjust(torch.empty((Cn, 12), dtype=torch.float64, **meta),
+                                           torch.empty((P, 3), dtype=torch.float64, **meta),
+                                           torch.empty((M,), dtype=torch.int32, **meta),
+                                           torch.empty((M,), dtype=torch.int32, **meta),
+                                           torch.empty((M, 2), dtype=torch.float64, **meta),
+                                           [float(v) for v in K.reshape(9)], [0], 50)
+    assert poses.shape == (Cn, 12) and poses.dtype == torch.float64 and poses.device.type == "meta"
+    assert points.shape == (P, 3) and points.dtype == torch.float64
+    assert info.shape == (4,) and info.dtype == torch.int64
+    with pytest.raises(RuntimeError, match="pixels"):
+        op.bundle_adjust(torch.empty((Cn, 12), dtype=torch.float64, **meta), torch.empty((P, 3), dtype=torch.float64, **meta),
+                         torch.empty((M,), dtype=torch.int32, **meta), torch.empty((M,), dtype=torch.int32, **meta),
+                         torch.empty((M, 3), dtype=torch.float64, **meta), [float(v) for v in K.reshape(9)], [0], 50)
+
+
+def test_bundle_adjust_validates_before_device_work(monkeypatch):
+    from structure_from_motion_amd import device
+    from structure_from_motion_amd.bundle import bundle
+
+    def no_device(*args, **kwargs):
+        raise AssertionError("device touched")
+
+    monkeypatch.setattr(device, "require_gpu", no_device)
+    monkeypatch.setattr(device, "to_device", no_device)
+    pr = synthetic.bundle_problem(3, 20, per_point=3, seed=1)
+    args = [K, pr["poses"], pr["points"], pr["camera_indices"], pr["point_indices"], pr["pixels"]]
+
+    def call(i=None, value=None, **kw):
+        a = list(args)
+        if i is not None:
+            a[i] = value
+        return bundle.bundle_adjust(*a, **kw)
+
+    K_bad = K.copy()
+    K_bad[2, 0] = 1.0
+    with pytest.raises(ValueError, match="row 2"):
+        call(0, K_bad)
+    with pytest.raises(ValueError, match="3x3"):
+        call(0, K[:2])
+    with pytest.raises(ValueError, match="poses"):
+        call(1, pr["poses"][:, :9])
+    with pytest.raises(ValueError, match="points_3d"):
+        call(2, pr["points"][:, :2])
+    with pytest.raises(ValueError, match="camera_indices"):
+        call(3, pr["camera_indices"][:-1])
+    with pytest.raises(ValueError, match="integers"):
+        call(4, pr["point_indices"].astype(np.float64))
+    with pytest.raises(ValueError, match="32 bits"):
+        call(4, pr["point_indices"].astype(np.int64) + (1 << 40))
+    with pytest.raises(ValueError, match="pixels"):
+        call(5, pr["pixels"][:, :1])
+    with pytest.raises(ValueError, match="64 cameras"):
+        call(1, np.zeros((65, 12)))
+    with pytest.raises(ValueError, match="at least one camera"):
+        call(fixed_cameras=())
+    with pytest.raises(ValueError, match="fixed_cameras"):
+        call(fixed_cameras=(3,))
+    with pytest.raises(ValueError, match="fixed_cameras"):
+        call(fixed_cameras=(0, 0))
+    with pytest.raises(ValueError, match="max_steps"):
+        call(max_steps=-1)
+    with pytest.raises(ValueError, match="max_steps"):
+        call(max_steps=2.5)
+
+
+def test_lib_reexports_bundle_adjust():
+    from lib.bundle import bundle as lib_bundle
+    from structure_from_motion_amd.bundle import bundle
+
+    assert lib_bundle.bundle_adjust is bundle.bundle_adjust
