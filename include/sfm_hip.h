@@ -391,6 +391,45 @@ int sfm_bundle_adjust(const double* K, int64_t cameras, int64_t points, int64_t 
                       const int32_t* point_index, const double* pixels, int max_steps, double* poses_out,
                       double* points_out, sfm_bundle_info* info, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- triangulation of multi-view tracks (csrc/sfm_tracks.hip; an extension, off unless asked for) ----
+ * These symbols were added under ABI 14 without a version change: they are new, and nothing an ABI-14 caller uses changed. */
+
+#define SFM_TRACKS_OK 0
+#define SFM_TRACKS_FEW_VIEWS 1   /* fewer than min_views observations: point, angle and errors NaN */
+#define SFM_TRACKS_DEGENERATE 2  /* the unit null vector is not finite or |v3| <= 1e-12: point, angle and errors NaN */
+#define SFM_TRACKS_BEHIND 3      /* behind a camera of one of its observations (the estimate is written) */
+#define SFM_TRACKS_SMALL_ANGLE 4 /* triangulation angle below min_angle (the estimate is written) */
+#define SFM_TRACKS_LARGE_ERROR 5 /* an observation's squared reprojection error above max_error (the estimate is written) */
+#define SFM_TRACKS_BAD_INDEX 6   /* some camera or point index of the call is out of range: every output NaN */
+
+typedef struct sfm_tracks_info {
+    int64_t status;                 /* 0, or 1 when an index is out of range (every point SFM_TRACKS_BAD_INDEX) */
+    int64_t points_ok;              /* points with SFM_TRACKS_OK */
+    int64_t max_refine_steps_taken; /* the most Levenberg-Marquardt trial steps of any point */
+    int64_t reserved;               /* 0 */
+} sfm_tracks_info;
+
+/* Bytes of workspace sfm_triangulate_tracks needs; -1 for sizes it refuses. */
+int64_t sfm_tracks_workspace_bytes(int64_t points, int64_t observations);
+
+/* Every point p from its observations m (point_index[m] == p, in increasing m; any order of the observations): the N-view
+ * DLT of the reference's two-view rows (y P3 - P2, P1 - x P3 with P = K [R | t] of camera camera_index[m], pixels[m] = (x, y)),
+ * X = v[0:3] / v[3] for v the right singular vector of the smallest singular value.  refine_steps > 0: then Levenberg-Marquardt
+ * on the point alone on F = sum of sfm_pnp_score's e over its observations, with the rules of sfm_pnp_refine (a rank-deficient
+ * start or a non-finite F skips it).  At the final X: obs_error[m] = e_m, the cheirality, and the angle
+ * acos(min over pairs i < j of d_i . d_j) of the unit rays d from the camera centres -R^T t; the status is the first failing
+ * rule of SFM_TRACKS_*.  Deterministic, bit for bit, from run to run.
+ * K: host [9], row 2 (0, 0, 1); poses: dev [cameras,12] (R | t, world -> camera); camera_index, point_index: dev int32
+ * [observations]; pixels: dev [observations,2]; min_views >= 2; min_angle (radians) finite and >= 0; max_error (px^2) >= 0,
+ * may be +inf; refine_steps >= 0; points_out: dev [points,3]; status: dev uint8 [points]; obs_error: dev [observations] or
+ * NULL; angle: dev [points] (radians) or NULL; info: dev, one record; workspace: dev, 16-byte aligned, at least
+ * sfm_tracks_workspace_bytes.  cameras, observations < 2^31, points < 2^31 - 1. */
+int sfm_triangulate_tracks(const double* K, int64_t cameras, int64_t points, int64_t observations, const double* poses,
+                           const int32_t* camera_index, const int32_t* point_index, const double* pixels, int min_views,
+                           double min_angle, double max_error, int refine_steps, double* points_out, uint8_t* status,
+                           double* obs_error, double* angle, sfm_tracks_info* info, void* workspace,
+                           int64_t workspace_bytes, void* stream);
+
 /* SED of n correspondences under one E (sed.py:7-30).  E: dev [9]; out: dev [n]. */
 int sfm_sed_values(const double* corr, int64_t n, const double* E, double* out, void* stream);
 

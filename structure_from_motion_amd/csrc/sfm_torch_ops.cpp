@@ -7,7 +7,8 @@
 // kernel, so fake-tensor tracing / torch.compile / opcheck work) and, where the engine pre-allocates its buffers
 // (device.RansacWorkspace), an in-place `_`-suffixed form with mutable arguments, plus the fused
 // sample_fit_philox_; and the PnP ops (sfm_pnp.hip) pnp_fit, pnp_score and the whole pass pnp_ransac_pass_, and the
-// refinement of a winner pnp_refine (sfm_pnp_refine.hip), and bundle_adjust (sfm_bundle.hip).  The reference call sites these serve: apps/sfm.py:110-119 (RANSAC-E), :133-138 (pose),
+// refinement of a winner pnp_refine (sfm_pnp_refine.hip), bundle_adjust (sfm_bundle.hip) and triangulate_tracks
+// (sfm_tracks.hip).  The reference call sites these serve: apps/sfm.py:110-119 (RANSAC-E), :133-138 (pose),
 // :181-186 (triangulation).
 //
 // Built by structure_from_motion_amd/build.py into csrc/libsfm_torch_ops.so (host code only: no kernels here).
@@ -16,6 +17,7 @@
 #include <c10/hip/HIPStream.h>
 #include <torch/library.h>
 
+#include <cmath>
 #include <tuple>
 #include <vector>
 
@@ -622,6 +624,81 @@ std::tuple<Tensor, Tensor, Tensor> bundle_adjust_meta(const Tensor& poses, const
     return {at::empty_like(poses), at::empty_like(points),
             at::empty_symint({c10::SymInt(kBundleInfoWords)}, like(poses, at::kLong))};
 }
+
+// triangulation of multi-view tracks (sfm_tracks.hip): poses [C, 12], camera / point indices int32 [M], pixels [M, 2],
+// `points` the number of points P -> points [P, 3], status uint8 [P], obs_error [M], angle [P] (radians), info int64 [4]
+// viewing the sfm_tracks_info record.  The workspace comes from the caching allocator (stream-ordered, no host sync).
+constexpr int64_t kTracksInfoWords = sizeof(sfm_tracks_info) / 8;
+
+void tracks_check(const Tensor& poses, const Tensor& cam, const Tensor& pt, const Tensor& pixels, int64_t points,
+                  at::ArrayRef<double> K, int64_t min_views, double min_angle, double max_error, int64_t refine_steps) {
+    check_K(K);
+    TORCH_CHECK(poses.dim() == 2 && poses.size(1) == 12, "sfm_hip: poses must be [C, 12]");
+    TORCH_CHECK(cam.dim() == 1 && pt.dim() == 1 && cam.size(0) == pt.size(0), "sfm_hip: camera and point indices must be [M]");
+    TORCH_CHECK(pixels.dim() == 2 && pixels.size(1) == 2 && pixels.size(0) == cam.size(0), "sfm_hip: pixels must be [M, 2]");
+    TORCH_CHECK(points >= 0 && points < 0x7FFFFFFF, "sfm_hip: points must be in [0, 2^31 - 1)");
+    TORCH_CHECK(min_views >= 2 && min_views <= 0x7FFFFFFF, "sfm_hip: min_views must be at least 2");
+    TORCH_CHECK(min_angle >= 0.0 && std::isfinite(min_angle), "sfm_hip: min_angle must be finite and >= 0");
+    TORCH_CHECK(max_error >= 0.0, "sfm_hip: max_error must be >= 0");
+    TORCH_CHECK(refine_steps >= 0 && refine_steps <= 0x7FFFFFFF, "sfm_hip: refine_steps must be in [0, 2^31)");
+}
+
+void triangulate_tracks_out(const Tensor& poses, const Tensor& cam, const Tensor& pt, const Tensor& pixels, int64_t points,
+                            at::ArrayRef<double> K, int64_t min_views, double min_angle, double max_error,
+                            int64_t refine_steps, Tensor& points_out, Tensor& status, Tensor& obs_error, Tensor& angle,
+                            Tensor& info) {
+    const OpDevice scope(poses);
+    need(poses, "poses", at::kDouble);
+    need(cam, "camera_indices", at::kInt);
+    need(pt, "point_indices", at::kInt);
+    need(pixels, "pixels", at::kDouble);
+    need(points_out, "points", at::kDouble);
+    need(status, "status", at::kByte);
+    need(obs_error, "obs_error", at::kDouble);
+    need(angle, "angle", at::kDouble);
+    need(info, "info", at::kLong);
+    tracks_check(poses, cam, pt, pixels, points, K, min_views, min_angle, max_error, refine_steps);
+    const int64_t C = poses.size(0), P = points, M = cam.size(0);
+    TORCH_CHECK(points_out.dim() == 2 && points_out.size(0) == P && points_out.size(1) == 3, "sfm_hip: points must be [P, 3]");
+    TORCH_CHECK(status.numel() == P && angle.numel() == P, "sfm_hip: status and angle must be [P]");
+    TORCH_CHECK(obs_error.numel() == M, "sfm_hip: obs_error must be [M]");
+    TORCH_CHECK(info.numel() == kTracksInfoWords, "sfm_hip: info must be int64 [4]");
+    const int64_t bytes = sfm_tracks_workspace_bytes(P, M);
+    TORCH_CHECK(bytes >= 0, "sfm_hip: triangulate_tracks: ", P, " points, ", M, " observations exceed the limits");
+    Tensor ws = at::empty({bytes}, like(poses, at::kByte));
+    ok(sfm_triangulate_tracks(K.data(), C, P, M, ptr<double>(poses), ptr<int32_t>(cam), ptr<int32_t>(pt), ptr<double>(pixels),
+                              (int)min_views, min_angle, max_error, (int)refine_steps, ptr<double>(points_out),
+                              ptr<uint8_t>(status), ptr<double>(obs_error), ptr<double>(angle),
+                              reinterpret_cast<sfm_tracks_info*>(ptr<int64_t>(info)), ws.data_ptr(), bytes, current_stream()),
+       "sfm_triangulate_tracks");
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> triangulate_tracks(const Tensor& poses, const Tensor& cam, const Tensor& pt,
+                                                                      const Tensor& pixels, int64_t points, at::ArrayRef<double> K,
+                                                                      int64_t min_views, double min_angle, double max_error,
+                                                                      int64_t refine_steps) {
+    tracks_check(poses, cam, pt, pixels, points, K, min_views, min_angle, max_error, refine_steps);
+    Tensor points_out = at::empty({points, 3}, like(poses, at::kDouble));
+    Tensor status = at::empty({points}, like(poses, at::kByte));
+    Tensor obs_error = at::empty({cam.size(0)}, like(poses, at::kDouble));
+    Tensor angle = at::empty({points}, like(poses, at::kDouble));
+    Tensor info = at::empty({kTracksInfoWords}, like(poses, at::kLong));
+    triangulate_tracks_out(poses, cam, pt, pixels, points, K, min_views, min_angle, max_error, refine_steps, points_out, status,
+                           obs_error, angle, info);
+    return {points_out, status, obs_error, angle, info};
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> triangulate_tracks_meta(const Tensor& poses, const Tensor& cam,
+                                                                           const Tensor& pt, const Tensor& pixels,
+                                                                           int64_t points, at::ArrayRef<double> K,
+                                                                           int64_t min_views, double min_angle,
+                                                                           double max_error, int64_t refine_steps) {
+    tracks_check(poses, cam, pt, pixels, points, K, min_views, min_angle, max_error, refine_steps);
+    const c10::SymInt P(points);
+    return {at::empty_symint({P, c10::SymInt(3)}, like(poses, at::kDouble)), at::empty_symint({P}, like(poses, at::kByte)),
+            at::empty_symint({cam.sym_size(0)}, like(poses, at::kDouble)), at::empty_symint({P}, like(poses, at::kDouble)),
+            at::empty_symint({c10::SymInt(kTracksInfoWords)}, like(poses, at::kLong))};
+}
 }  // namespace
 
 // the C-ABI version this op library was compiled against (include/sfm_hip.h); ops.load() compares it with the
@@ -669,6 +746,11 @@ TORCH_LIBRARY(sfm_hip, m) {
           "int[] fixed, int max_steps) -> (Tensor, Tensor, Tensor)");
     m.def("bundle_adjust_(Tensor(a!) poses, Tensor(b!) points, Tensor camera_indices, Tensor point_indices, Tensor pixels, "
           "float[] K, int[] fixed, int max_steps, Tensor(c!) info) -> ()");
+    m.def("triangulate_tracks(Tensor poses, Tensor camera_indices, Tensor point_indices, Tensor pixels, int points, float[] K, "
+          "int min_views, float min_angle, float max_error, int refine_steps) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
+    m.def("triangulate_tracks_(Tensor poses, Tensor camera_indices, Tensor point_indices, Tensor pixels, int points, "
+          "float[] K, int min_views, float min_angle, float max_error, int refine_steps, Tensor(a!) points_out, "
+          "Tensor(b!) status, Tensor(c!) obs_error, Tensor(d!) angle, Tensor(e!) info) -> ()");
 }
 
 // ROCm devices dispatch under torch's "CUDA" key (the name of the dispatch key, not a CUDA code path)
@@ -697,6 +779,8 @@ TORCH_LIBRARY_IMPL(sfm_hip, CUDA, m) {
     m.impl("pnp_refine_", &pnp_refine_out);
     m.impl("bundle_adjust", &bundle_adjust);
     m.impl("bundle_adjust_", &bundle_adjust_inplace);
+    m.impl("triangulate_tracks", &triangulate_tracks);
+    m.impl("triangulate_tracks_", &triangulate_tracks_out);
 }
 
 // sample_philox has no tensor argument to dispatch on: registered for every backend, it checks its device itself
@@ -723,6 +807,8 @@ void pnp_refine_out_meta(const Tensor&, const Tensor&, const Tensor&, const Tens
                          int64_t, Tensor&, Tensor&, Tensor&) {}
 void bundle_adjust_out_meta(Tensor&, Tensor&, const Tensor&, const Tensor&, const Tensor&, at::ArrayRef<double>, at::ArrayRef<int64_t>,
                             int64_t, Tensor&) {}
+void triangulate_tracks_out_meta(const Tensor&, const Tensor&, const Tensor&, const Tensor&, int64_t, at::ArrayRef<double>, int64_t,
+                                 double, double, int64_t, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&) {}
 
 TORCH_LIBRARY_IMPL(sfm_hip, Meta, m) {
     m.impl("normalize_coords_", &normalize_coords_out_meta);
@@ -749,4 +835,6 @@ TORCH_LIBRARY_IMPL(sfm_hip, Meta, m) {
     m.impl("pnp_refine_", &pnp_refine_out_meta);
     m.impl("bundle_adjust", &bundle_adjust_meta);
     m.impl("bundle_adjust_", &bundle_adjust_out_meta);
+    m.impl("triangulate_tracks", &triangulate_tracks_meta);
+    m.impl("triangulate_tracks_", &triangulate_tracks_out_meta);
 }

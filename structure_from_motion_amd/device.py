@@ -732,6 +732,41 @@ def read_bundle_info(info: torch.Tensor) -> BundleInfo:
     return BundleInfo(float(costs[0]), float(costs[1]), int(ints[0]), int(ints[1]), int(ints[2]))
 
 
+# ------------------------------------------------------------------------------------------------------
+# triangulation of multi-view tracks (csrc/sfm_tracks.hip): poses [C,12] = R (9) | t (3) world -> camera, observations
+# (camera index, point index) int32 [M] each and pixels [M,2]
+# ------------------------------------------------------------------------------------------------------
+def triangulate_tracks(poses, camera_indices, point_indices, pixels, points: int, K, min_views: int = 2,
+                       min_angle: float = 0.0, max_error: float = float("inf"), refine_steps: int = 0, out=None):
+    """N-view DLT of every point from its observations, optional per-point LM and the quality checks
+    (``sfm_triangulate_tracks``) -> (points [P,3], status uint8 [P] (TRACKS_*), obs_error [M] (px^2), angle [P]
+    (radians), info int64 [4] viewing the sfm_tracks_info record; ``read_tracks_info``).  ``out`` = those five tensors runs
+    the in-place op on them instead.  No host synchronisation."""
+    op = ops.load()
+    args = (poses.contiguous(), camera_indices.contiguous(), point_indices.contiguous(), pixels.contiguous(), int(points),
+            _camera_list(K), int(min_views), float(min_angle), float(max_error), int(refine_steps))
+    if out is None:
+        return op.triangulate_tracks(*args)
+    op.triangulate_tracks_(*args, *out)
+    return out
+
+
+@dataclass
+class TracksInfo:
+    status: int                  # 0, or 1 when a camera or point index is out of range (every point TRACKS_BAD_INDEX)
+    points_ok: int               # points with TRACKS_OK
+    max_refine_steps_taken: int  # the most LM trial steps of any point
+
+
+TRACKS_OK, TRACKS_FEW_VIEWS, TRACKS_DEGENERATE, TRACKS_BEHIND, TRACKS_SMALL_ANGLE, TRACKS_LARGE_ERROR, TRACKS_BAD_INDEX = range(7)
+
+
+def read_tracks_info(info: torch.Tensor) -> TracksInfo:
+    """Host copy of an sfm_tracks_info record (int64 [4]) (synchronises)."""
+    raw = info.cpu().numpy()
+    return TracksInfo(int(raw[0]), int(raw[1]), int(raw[2]))
+
+
 @dataclass
 class PnPOutcome:
     best_h: int                # winning hypothesis, -1 if none

@@ -83,3 +83,50 @@ def bundle_problem(cameras: int, points: int, per_point: int = 4, seed: int = 0,
         start[c, 9:] += rng.normal(0.0, translation_noise, 3)
     return dict(K=K, poses=start, points=X + rng.normal(0.0, point_noise, X.shape), camera_indices=cam.astype(np.int32),
                 point_indices=pt.astype(np.int32), pixels=pixels, poses_true=poses, points_true=X)
+
+
+def multi_view_scene(views: int = 8, points: int = 2000, seed: int = 21, noise_px: float = 0.5,
+                     outlier_fraction: float = 0.2, step_deg: float = 5.0, K: np.ndarray = BENCH_K):
+    """An N-view scene for incremental reconstruction: points uniform in x, y in [-1, 1], z in [4, 6]; camera 0 = [I | 0]
+    and camera i on an arc about the box centre (0, 0, 5), ``i * step_deg`` degrees about the Y axis, looking at it.  A point
+    is observed by every camera in front of which it projects inside the image (2 cx by 2 cy), with Gaussian pixel noise;
+    only points observed at least twice are kept, so tracks have lengths 2 to ``views``.  A fraction of the observations
+    is replaced by uniform random pixels.  The observations come camera-major, by point inside a camera.  Returns
+    dict(K, camera_indices, point_indices (M,) int32, pixels (M, 2), is_outlier (M,) bool, poses_true (V, 12),
+    points_true (P, 3))."""
+    rng = np.random.default_rng(seed)
+    width, height = 2.0 * K[0, 2], 2.0 * K[1, 2]
+    poses = np.zeros((views, 12))
+    for i in range(views):
+        a = np.radians(i * step_deg)
+        R = np.array([[np.cos(a), 0.0, -np.sin(a)], [0.0, 1.0, 0.0], [np.sin(a), 0.0, np.cos(a)]])
+        centre = np.array([-5.0 * np.sin(a), 0.0, 5.0 - 5.0 * np.cos(a)])
+        poses[i, :9] = R.reshape(9)
+        poses[i, 9:] = -R @ centre
+    poses[0] = np.concatenate([np.eye(3).reshape(9), np.zeros(3)])
+    kept = []
+    while sum(len(x) for x in kept) < points:
+        X = np.column_stack([rng.uniform(-1.0, 1.0, points), rng.uniform(-1.0, 1.0, points), rng.uniform(4.0, 6.0, points)])
+        seen = np.zeros((points, views), dtype=bool)
+        for i in range(views):
+            xc = X @ poses[i, :9].reshape(3, 3).T + poses[i, 9:]
+            uvw = xc @ K.T
+            uv = uvw[:, :2] / uvw[:, 2:3]
+            seen[:, i] = (xc[:, 2] > 0) & (uv[:, 0] >= 0) & (uv[:, 0] < width) & (uv[:, 1] >= 0) & (uv[:, 1] < height)
+        kept.append(X[seen.sum(axis=1) >= 2])
+    X = np.vstack(kept)[:points]
+    cams, pts, pixels = [], [], []
+    for i in range(views):
+        xc = X @ poses[i, :9].reshape(3, 3).T + poses[i, 9:]
+        uvw = xc @ K.T
+        uv = uvw[:, :2] / uvw[:, 2:3]
+        vis = np.nonzero((xc[:, 2] > 0) & (uv[:, 0] >= 0) & (uv[:, 0] < width) & (uv[:, 1] >= 0) & (uv[:, 1] < height))[0]
+        cams.append(np.full(len(vis), i))
+        pts.append(vis)
+        pixels.append(uv[vis] + rng.normal(0.0, noise_px, (len(vis), 2)))
+    cam, pt, pix = np.concatenate(cams), np.concatenate(pts), np.vstack(pixels)
+    is_out = rng.random(len(cam)) < outlier_fraction
+    rand_px = np.column_stack([rng.uniform(0, width, len(cam)), rng.uniform(0, height, len(cam))])
+    pix = np.where(is_out[:, None], rand_px, pix)
+    return dict(K=K, camera_indices=cam.astype(np.int32), point_indices=pt.astype(np.int32), pixels=pix, is_outlier=is_out,
+                poses_true=poses, points_true=X)
