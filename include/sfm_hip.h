@@ -391,6 +391,40 @@ int sfm_bundle_adjust(const double* K, int64_t cameras, int64_t points, int64_t 
                       const int32_t* point_index, const double* pixels, int max_steps, double* poses_out,
                       double* points_out, sfm_bundle_info* info, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- bundle adjustment with an iterative Schur solver (csrc/sfm_bundle_pcg.hip; an extension, off unless asked for) ----
+ * These symbols were added under ABI 14 without a version change: they are new, and nothing an ABI-14 caller uses changed. */
+
+typedef struct sfm_bundle_pcg_info {
+    double initial_cost;   /* cost of the input (NaN for SFM_BUNDLE_BAD_INDEX) */
+    double final_cost;     /* cost of the last accepted trial (= initial_cost when none was accepted) */
+    int32_t steps;         /* Levenberg-Marquardt trial steps */
+    int32_t accepted;      /* accepted steps */
+    int32_t status;        /* SFM_BUNDLE_* */
+    int32_t cg_iterations; /* conjugate-gradient iterations over all trial steps */
+    int32_t cg_max;        /* the most conjugate-gradient iterations of one trial step */
+    int32_t reserved;      /* 0 */
+} sfm_bundle_pcg_info;
+
+/* Bytes of workspace sfm_bundle_adjust_pcg needs; -1 for sizes it refuses (cameras < 1; points or observations < 0;
+ * any of them >= 2^31).  There is no limit on the camera count below that. */
+int64_t sfm_bundle_pcg_workspace_bytes(int64_t cameras, int64_t points, int64_t observations);
+
+/* sfm_bundle_adjust's Levenberg-Marquardt loop (its cost, updates, damping, stops, held points and cameras, gauge rule and
+ * statuses) over any number of cameras, with the damped reduced camera system S* dc = b (S* = U* - W V*^-1 W^T,
+ * b = -g_c + W V*^-1 g_p) solved by conjugate gradients instead of a dense Cholesky factorisation.  S* is applied
+ * matrix-free and never formed; the preconditioner is block Jacobi on S*'s 6 x 6 diagonal blocks, each factored by
+ * Cholesky (a block or a V_p* that does not factor is a rejected step).  CG starts from dc = 0 and stops at the first of
+ * |r_k| <= cg_tolerance |b|, k = max_cg_iterations, or a breakdown (p^T S* p <= 0 or a non-finite scalar: the iterate
+ * reached so far is the step; at k = 0 the step is rejected).  The host reads two flags from the device once per LM step
+ * and once per 10 CG iterations to stop enqueuing work, so the call synchronises `stream`; the result does not depend on
+ * those reads, and a call is bit-reproducible.  Arguments as sfm_bundle_adjust, with no camera limit, plus
+ * max_cg_iterations >= 1 and cg_tolerance finite in (0, 1); the workspace is at least sfm_bundle_pcg_workspace_bytes. */
+int sfm_bundle_adjust_pcg(const double* K, int64_t cameras, int64_t points, int64_t observations, const uint8_t* fixed,
+                          const double* poses_in, const double* points_in, const int32_t* camera_index,
+                          const int32_t* point_index, const double* pixels, int max_steps, int max_cg_iterations,
+                          double cg_tolerance, double* poses_out, double* points_out, sfm_bundle_pcg_info* info,
+                          void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- triangulation of multi-view tracks (csrc/sfm_tracks.hip; an extension, off unless asked for) ----
  * These symbols were added under ABI 14 without a version change: they are new, and nothing an ABI-14 caller uses changed. */
 

@@ -4,6 +4,10 @@ Poses are ``R (9) | t (3)`` rows with ``x_cam = R X + t`` — the PnP model layo
 ``K`` whose row 2 is (0, 0, 1); intrinsics are not optimised.  The cost is the sum over the observations of the squared
 reprojection error of the PnP scorer.  Fixed cameras and points with fewer than two observations are held; with exactly
 one fixed camera the scale is held by the distance from it to the lowest-index free camera.
+
+Two linear solvers sit behind the same LM loop: ``"dense"`` factors the reduced camera system (at most 64 cameras,
+DESIGN.md §6h) and ``"iterative"`` solves it by block-Jacobi preconditioned conjugate gradients without forming it (any
+number of cameras, ``sfm_bundle_adjust_pcg``).
 """
 from __future__ import annotations
 
@@ -14,7 +18,8 @@ import numpy.typing as npt
 
 from ..pnp.pnp import check_camera_matrix
 
-MAX_CAMERAS = 64
+MAX_CAMERAS = 64   # of the dense solver
+LINEAR_SOLVERS = ("dense", "iterative")
 _INT32 = 2**31
 
 
@@ -45,6 +50,9 @@ def bundle_adjust(
     pixels: npt.NDArray,
     fixed_cameras: Sequence[int] = (0,),
     max_steps: int = 50,
+    linear_solver: str = "dense",
+    max_cg_iterations: int = 100,
+    cg_tolerance: float = 0.1,
 ):
     """Minimise the summed squared reprojection error over the free cameras' poses and the points.
 
@@ -52,7 +60,12 @@ def bundle_adjust(
     ``camera_indices[m]``.  At most 64 cameras, at least one of them in ``fixed_cameras``; at most ``max_steps`` LM trial
     steps.  Returns ``(poses (C, 12), points (P, 3), info)`` with ``info`` a ``device.BundleInfo``.  An input whose cost
     is not finite (a point behind a camera), or an index out of range, comes back unchanged with ``info.status`` set
-    (``device.BUNDLE_BAD_START`` / ``BUNDLE_BAD_INDEX``).  Every argument is checked before any device work."""
+    (``device.BUNDLE_BAD_START`` / ``BUNDLE_BAD_INDEX``).  Every argument is checked before any device work.
+
+    ``linear_solver="iterative"`` takes any number of cameras (at least 1) and solves each LM step's reduced camera
+    system by preconditioned conjugate gradients: at most ``max_cg_iterations`` (>= 1) iterations, stopping once the
+    residual is below ``cg_tolerance`` (in (0, 1)) times the right-hand side.  ``info`` is then a
+    ``device.BundlePcgInfo`` (the ``BundleInfo`` fields plus ``cg_iterations`` and ``cg_max``)."""
     K = check_camera_matrix(camera_matrix)
     poses = _array(poses, "poses", (-1, 12))
     points = _array(points_3d, "points_3d", (-1, 3))
@@ -61,7 +74,19 @@ def bundle_adjust(
     cams = _indices(camera_indices, "camera_indices", m)
     pts = _indices(point_indices, "point_indices", m)
     n_cams = poses.shape[0]
-    if not 1 <= n_cams <= MAX_CAMERAS:
+    if linear_solver not in LINEAR_SOLVERS:
+        raise ValueError(f"linear_solver must be one of {LINEAR_SOLVERS}, got {linear_solver!r}")
+    iterative = linear_solver == "iterative"
+    if iterative:
+        if n_cams < 1 or n_cams >= _INT32:
+            raise ValueError(f"the iterative solver needs between 1 and 2^31 - 1 cameras, got {n_cams}")
+        if (isinstance(max_cg_iterations, bool) or not isinstance(max_cg_iterations, (int, np.integer))
+                or not 1 <= max_cg_iterations < _INT32):
+            raise ValueError(f"max_cg_iterations must be a positive integer, got {max_cg_iterations!r}")
+        if (isinstance(cg_tolerance, bool) or not isinstance(cg_tolerance, (int, float, np.floating))
+                or not 0.0 < float(cg_tolerance) < 1.0):
+            raise ValueError(f"cg_tolerance must be a number in (0, 1), got {cg_tolerance!r}")
+    elif not 1 <= n_cams <= MAX_CAMERAS:
         raise ValueError(f"between 1 and {MAX_CAMERAS} cameras are supported, got {n_cams}")
     if points.shape[0] >= _INT32 or m >= _INT32:
         raise ValueError("points and observations must number fewer than 2^31")
@@ -77,6 +102,12 @@ def bundle_adjust(
     from .. import device
 
     device.require_gpu()
+    if iterative:
+        poses_d, points_d, info = device.bundle_adjust_pcg(
+            device.to_device(poses), device.to_device(points), device.to_device(cams, dtype=torch.int32),
+            device.to_device(pts, dtype=torch.int32), device.to_device(pixels), K, fixed, int(max_steps),
+            int(max_cg_iterations), float(cg_tolerance))
+        return poses_d.cpu().numpy(), points_d.cpu().numpy(), device.read_bundle_pcg_info(info)
     poses_d, points_d, info = device.bundle_adjust(
         device.to_device(poses), device.to_device(points), device.to_device(cams, dtype=torch.int32),
         device.to_device(pts, dtype=torch.int32), device.to_device(pixels), K, fixed, int(max_steps))

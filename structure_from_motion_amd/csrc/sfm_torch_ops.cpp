@@ -625,6 +625,77 @@ std::tuple<Tensor, Tensor, Tensor> bundle_adjust_meta(const Tensor& poses, const
             at::empty_symint({c10::SymInt(kBundleInfoWords)}, like(poses, at::kLong))};
 }
 
+// bundle adjustment with the iterative Schur solver (sfm_bundle_pcg.hip): the arguments of bundle_adjust plus
+// max_cg_iterations and cg_tolerance; info int64 [5] viewing the sfm_bundle_pcg_info record.  The call synchronises the
+// stream (the host reads the LM and CG stop flags).
+constexpr int64_t kBundlePcgInfoWords = sizeof(sfm_bundle_pcg_info) / 8;
+
+void bundle_pcg_check(const Tensor& poses, const Tensor& points, const Tensor& cam, const Tensor& pt, const Tensor& pixels,
+                      at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed, int64_t max_steps, int64_t max_cg_iterations,
+                      double cg_tolerance) {
+    bundle_check(poses, points, cam, pt, pixels, K, fixed, max_steps);
+    TORCH_CHECK(max_cg_iterations >= 1 && max_cg_iterations <= 0x7FFFFFFF, "sfm_hip: max_cg_iterations must be in [1, 2^31)");
+    TORCH_CHECK(cg_tolerance > 0.0 && cg_tolerance < 1.0, "sfm_hip: cg_tolerance must be in (0, 1)");
+}
+
+void bundle_adjust_pcg_out(Tensor& poses, Tensor& points, const Tensor& cam, const Tensor& pt, const Tensor& pixels,
+                           at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed, int64_t max_steps, int64_t max_cg_iterations,
+                           double cg_tolerance, Tensor& info, const Tensor& poses_in, const Tensor& points_in) {
+    const OpDevice scope(poses);
+    need(poses, "poses", at::kDouble);
+    need(points, "points", at::kDouble);
+    need(poses_in, "poses", at::kDouble);
+    need(points_in, "points", at::kDouble);
+    need(cam, "camera_indices", at::kInt);
+    need(pt, "point_indices", at::kInt);
+    need(pixels, "pixels", at::kDouble);
+    need(info, "info", at::kLong);
+    bundle_pcg_check(poses_in, points_in, cam, pt, pixels, K, fixed, max_steps, max_cg_iterations, cg_tolerance);
+    TORCH_CHECK(poses.sizes() == poses_in.sizes() && points.sizes() == points_in.sizes(), "sfm_hip: output shapes differ");
+    TORCH_CHECK(info.numel() == kBundlePcgInfoWords, "sfm_hip: info must be int64 [5]");
+    const int64_t C = poses.size(0), P = points.size(0), M = cam.size(0);
+    std::vector<uint8_t> mask((size_t)C, 0);
+    for (int64_t c : fixed) mask[(size_t)c] = 1;
+    const int64_t bytes = sfm_bundle_pcg_workspace_bytes(C, P, M);
+    TORCH_CHECK(bytes >= 0, "sfm_hip: bundle_adjust_pcg: ", C, " cameras, ", P, " points, ", M,
+                " observations exceed the limits (C >= 1; C, P and M < 2^31)");
+    Tensor ws = at::empty({bytes}, like(poses, at::kByte));
+    ok(sfm_bundle_adjust_pcg(K.data(), C, P, M, mask.data(), ptr<double>(poses_in), ptr<double>(points_in), ptr<int32_t>(cam),
+                             ptr<int32_t>(pt), ptr<double>(pixels), (int)max_steps, (int)max_cg_iterations, cg_tolerance,
+                             ptr<double>(poses), ptr<double>(points), reinterpret_cast<sfm_bundle_pcg_info*>(ptr<int64_t>(info)),
+                             ws.data_ptr(), bytes, current_stream()),
+       "sfm_bundle_adjust_pcg");
+}
+
+void bundle_adjust_pcg_inplace(Tensor& poses, Tensor& points, const Tensor& cam, const Tensor& pt, const Tensor& pixels,
+                               at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed, int64_t max_steps,
+                               int64_t max_cg_iterations, double cg_tolerance, Tensor& info) {
+    bundle_adjust_pcg_out(poses, points, cam, pt, pixels, K, fixed, max_steps, max_cg_iterations, cg_tolerance, info, poses,
+                          points);
+}
+
+std::tuple<Tensor, Tensor, Tensor> bundle_adjust_pcg(const Tensor& poses, const Tensor& points, const Tensor& cam,
+                                                     const Tensor& pt, const Tensor& pixels, at::ArrayRef<double> K,
+                                                     at::ArrayRef<int64_t> fixed, int64_t max_steps, int64_t max_cg_iterations,
+                                                     double cg_tolerance) {
+    bundle_pcg_check(poses, points, cam, pt, pixels, K, fixed, max_steps, max_cg_iterations, cg_tolerance);
+    Tensor poses_out = at::empty_like(poses);
+    Tensor points_out = at::empty_like(points);
+    Tensor info = at::empty({kBundlePcgInfoWords}, like(poses, at::kLong));
+    bundle_adjust_pcg_out(poses_out, points_out, cam, pt, pixels, K, fixed, max_steps, max_cg_iterations, cg_tolerance, info,
+                          poses, points);
+    return {poses_out, points_out, info};
+}
+
+std::tuple<Tensor, Tensor, Tensor> bundle_adjust_pcg_meta(const Tensor& poses, const Tensor& points, const Tensor& cam,
+                                                          const Tensor& pt, const Tensor& pixels, at::ArrayRef<double> K,
+                                                          at::ArrayRef<int64_t> fixed, int64_t max_steps,
+                                                          int64_t max_cg_iterations, double cg_tolerance) {
+    bundle_pcg_check(poses, points, cam, pt, pixels, K, fixed, max_steps, max_cg_iterations, cg_tolerance);
+    return {at::empty_like(poses), at::empty_like(points),
+            at::empty_symint({c10::SymInt(kBundlePcgInfoWords)}, like(poses, at::kLong))};
+}
+
 // triangulation of multi-view tracks (sfm_tracks.hip): poses [C, 12], camera / point indices int32 [M], pixels [M, 2],
 // `points` the number of points P -> points [P, 3], status uint8 [P], obs_error [M], angle [P] (radians), info int64 [4]
 // viewing the sfm_tracks_info record.  The workspace comes from the caching allocator (stream-ordered, no host sync).
@@ -746,6 +817,11 @@ TORCH_LIBRARY(sfm_hip, m) {
           "int[] fixed, int max_steps) -> (Tensor, Tensor, Tensor)");
     m.def("bundle_adjust_(Tensor(a!) poses, Tensor(b!) points, Tensor camera_indices, Tensor point_indices, Tensor pixels, "
           "float[] K, int[] fixed, int max_steps, Tensor(c!) info) -> ()");
+    m.def("bundle_adjust_pcg(Tensor poses, Tensor points, Tensor camera_indices, Tensor point_indices, Tensor pixels, "
+          "float[] K, int[] fixed, int max_steps, int max_cg_iterations, float cg_tolerance) -> (Tensor, Tensor, Tensor)");
+    m.def("bundle_adjust_pcg_(Tensor(a!) poses, Tensor(b!) points, Tensor camera_indices, Tensor point_indices, "
+          "Tensor pixels, float[] K, int[] fixed, int max_steps, int max_cg_iterations, float cg_tolerance, "
+          "Tensor(c!) info) -> ()");
     m.def("triangulate_tracks(Tensor poses, Tensor camera_indices, Tensor point_indices, Tensor pixels, int points, float[] K, "
           "int min_views, float min_angle, float max_error, int refine_steps) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
     m.def("triangulate_tracks_(Tensor poses, Tensor camera_indices, Tensor point_indices, Tensor pixels, int points, "
@@ -779,6 +855,8 @@ TORCH_LIBRARY_IMPL(sfm_hip, CUDA, m) {
     m.impl("pnp_refine_", &pnp_refine_out);
     m.impl("bundle_adjust", &bundle_adjust);
     m.impl("bundle_adjust_", &bundle_adjust_inplace);
+    m.impl("bundle_adjust_pcg", &bundle_adjust_pcg);
+    m.impl("bundle_adjust_pcg_", &bundle_adjust_pcg_inplace);
     m.impl("triangulate_tracks", &triangulate_tracks);
     m.impl("triangulate_tracks_", &triangulate_tracks_out);
 }
@@ -807,6 +885,8 @@ void pnp_refine_out_meta(const Tensor&, const Tensor&, const Tensor&, const Tens
                          int64_t, Tensor&, Tensor&, Tensor&) {}
 void bundle_adjust_out_meta(Tensor&, Tensor&, const Tensor&, const Tensor&, const Tensor&, at::ArrayRef<double>, at::ArrayRef<int64_t>,
                             int64_t, Tensor&) {}
+void bundle_adjust_pcg_out_meta(Tensor&, Tensor&, const Tensor&, const Tensor&, const Tensor&, at::ArrayRef<double>,
+                                at::ArrayRef<int64_t>, int64_t, int64_t, double, Tensor&) {}
 void triangulate_tracks_out_meta(const Tensor&, const Tensor&, const Tensor&, const Tensor&, int64_t, at::ArrayRef<double>, int64_t,
                                  double, double, int64_t, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&) {}
 
@@ -835,6 +915,8 @@ TORCH_LIBRARY_IMPL(sfm_hip, Meta, m) {
     m.impl("pnp_refine_", &pnp_refine_out_meta);
     m.impl("bundle_adjust", &bundle_adjust_meta);
     m.impl("bundle_adjust_", &bundle_adjust_out_meta);
+    m.impl("bundle_adjust_pcg", &bundle_adjust_pcg_meta);
+    m.impl("bundle_adjust_pcg_", &bundle_adjust_pcg_out_meta);
     m.impl("triangulate_tracks", &triangulate_tracks_meta);
     m.impl("triangulate_tracks_", &triangulate_tracks_out_meta);
 }

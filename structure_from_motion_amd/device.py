@@ -732,6 +732,41 @@ def read_bundle_info(info: torch.Tensor) -> BundleInfo:
     return BundleInfo(float(costs[0]), float(costs[1]), int(ints[0]), int(ints[1]), int(ints[2]))
 
 
+def bundle_adjust_pcg(poses, points, camera_indices, point_indices, pixels, K, fixed=(0,), max_steps: int = 50,
+                      max_cg_iterations: int = 100, cg_tolerance: float = 0.1, out=None):
+    """``bundle_adjust`` over any number of cameras with the iterative Schur solver (``sfm_bundle_adjust_pcg``,
+    DESIGN.md §6j) -> (poses [C,12], points [P,3], info int64 [5] viewing the sfm_bundle_pcg_info record;
+    ``read_bundle_pcg_info``).  ``out`` = (poses, points, info) runs the in-place op on those tensors instead.  The call
+    synchronises the current stream: the host reads the stop flags between LM steps and CG chunks."""
+    op = ops.load()
+    args = (camera_indices.contiguous(), point_indices.contiguous(), pixels.contiguous(), _camera_list(K),
+            [int(c) for c in fixed], int(max_steps), int(max_cg_iterations), float(cg_tolerance))
+    if out is None:
+        return op.bundle_adjust_pcg(poses.contiguous(), points.contiguous(), *args)
+    op.bundle_adjust_pcg_(out[0], out[1], *args, out[2])
+    return out
+
+
+@dataclass
+class BundlePcgInfo:
+    initial_cost: float   # cost of the input (NaN when an index is out of range)
+    final_cost: float     # cost of the last accepted trial (initial_cost when none was accepted)
+    steps: int            # Levenberg-Marquardt trial steps
+    accepted: int         # accepted steps
+    status: int           # BUNDLE_OK, BUNDLE_BAD_START or BUNDLE_BAD_INDEX
+    cg_iterations: int    # conjugate-gradient iterations over all trial steps
+    cg_max: int           # the most conjugate-gradient iterations of one trial step
+
+
+def read_bundle_pcg_info(info: torch.Tensor) -> BundlePcgInfo:
+    """Host copy of an sfm_bundle_pcg_info record (int64 [5]) (synchronises)."""
+    raw = info.cpu().numpy()
+    costs = raw[0:2].view(np.float64)
+    ints = raw[2:5].view(np.int32)
+    return BundlePcgInfo(float(costs[0]), float(costs[1]), int(ints[0]), int(ints[1]), int(ints[2]), int(ints[3]),
+                         int(ints[4]))
+
+
 # ------------------------------------------------------------------------------------------------------
 # triangulation of multi-view tracks (csrc/sfm_tracks.hip): poses [C,12] = R (9) | t (3) world -> camera, observations
 # (camera index, point index) int32 [M] each and pixels [M,2]

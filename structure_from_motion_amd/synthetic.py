@@ -85,6 +85,45 @@ def bundle_problem(cameras: int, points: int, per_point: int = 4, seed: int = 0,
                 point_indices=pt.astype(np.int32), pixels=pixels, poses_true=poses, points_true=X)
 
 
+def sequence_bundle_problem(cameras: int, points: int, track_length: int = 4, seed: int = 0, noise_px: float = 0.5,
+                            spacing: float = 0.2, rotation_noise: float = 0.003, translation_noise: float = 0.01,
+                            point_noise: float = 0.01, K: np.ndarray = BENCH_K):
+    """A bundle-adjustment input shaped like a video sequence: camera i has its centre at (i * spacing, 0, 0) and is
+    rotated by up to 1 degree about X and Y (camera 0 = [I | 0]).  Each point is seen by a contiguous window of
+    ``min(track_length, cameras)`` neighbouring cameras (the window's first camera uniform), so camera visibility is
+    banded: cameras share points only with neighbours less than ``track_length`` apart.  A point lies in x within 0.55 of
+    every centre of its window, y in [-0.5, 0.5] and z in [4, 6]; pixels carry Gaussian noise and the observations come in
+    random order.  The start perturbs every camera but camera 0 (its rotation about its own centre, and its translation)
+    and every point as ``bundle_problem`` does.  Memory is O(observations).  Returns the dict of ``bundle_problem``."""
+    rng = np.random.default_rng(seed)
+    L = min(track_length, cameras)
+    poses = np.zeros((cameras, 12))
+    poses[0, :9] = np.eye(3).reshape(9)
+    for c in range(1, cameras):
+        R = rotation_xy(rng.uniform(-1.0, 1.0), rng.uniform(-1.0, 1.0))
+        poses[c, :9] = R.reshape(9)
+        poses[c, 9:] = -R @ np.array([c * spacing, 0.0, 0.0])
+    first = rng.integers(0, cameras - L + 1, points)
+    lo = (first + L - 1) * spacing - 0.55
+    hi = first * spacing + 0.55
+    X = np.column_stack([rng.uniform(lo, hi), rng.uniform(-0.5, 0.5, points), rng.uniform(4.0, 6.0, points)])
+    cam = (first[:, None] + np.arange(L)[None, :]).reshape(-1)
+    pt = np.repeat(np.arange(points), L)
+    order = rng.permutation(len(cam))
+    cam, pt = cam[order], pt[order]
+    R = poses[cam, :9].reshape(-1, 3, 3)
+    xc = np.einsum("mij,mj->mi", R, X[pt]) + poses[cam, 9:]
+    uvw = xc @ K.T
+    pixels = uvw[:, :2] / uvw[:, 2:3] + rng.normal(0.0, noise_px, (len(cam), 2))
+    start = poses.copy()
+    for c in range(1, cameras):   # rotated about the camera's own centre, which then moves by the translation noise
+        R = _small_rotation(rng, rotation_noise) @ poses[c, :9].reshape(3, 3)
+        start[c, :9] = R.reshape(9)
+        start[c, 9:] = -R @ np.array([c * spacing, 0.0, 0.0]) + rng.normal(0.0, translation_noise, 3)
+    return dict(K=K, poses=start, points=X + rng.normal(0.0, point_noise, X.shape), camera_indices=cam.astype(np.int32),
+                point_indices=pt.astype(np.int32), pixels=pixels, poses_true=poses, points_true=X)
+
+
 def multi_view_scene(views: int = 8, points: int = 2000, seed: int = 21, noise_px: float = 0.5,
                      outlier_fraction: float = 0.2, step_deg: float = 5.0, K: np.ndarray = BENCH_K):
     """An N-view scene for incremental reconstruction: points uniform in x, y in [-1, 1], z in [4, 6]; camera 0 = [I | 0]
