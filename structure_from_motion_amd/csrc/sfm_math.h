@@ -683,4 +683,24 @@ SFM_DEVICE int wave_sum(int x) {
            __builtin_amdgcn_readlane(x, 48);
 }
 
+// Block-wide sums of K doubles per thread in a fixed order: wave_sum inside each wave, then the wave partials added in
+// wave order.  part: kBlock / 64 * K doubles of LDS.  Valid in `total` (K doubles of LDS) for every thread after the call.
+template <int K, int kBlock>
+SFM_DEVICE void block_sum(double (&v)[K], double* part, double* total) {
+    constexpr int kWaves = kBlock / 64;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x / 64;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const double s = wave_sum(v[k]);
+        if (lane == 0) part[wave * K + k] = s;
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < K; k += kBlock) {
+        double acc = part[k];
+        for (int w = 1; w < kWaves; ++w) acc += part[w * K + k];
+        total[k] = acc;
+    }
+    __syncthreads();
+}
+
 }  // namespace sfm

@@ -20,7 +20,10 @@ namespace {
 
 using sfmhost::check_launch;
 using sfmhost::fail;
+using sfm::block_sum;
+using sfmpnp::apply_step;
 using sfmpnp::camera_from;
+using sfmpnp::jacobians;
 using sfmpnp::kPnPFields;
 using sfmpnp::pnp_score;
 using sfmpnp::PnPCamera;
@@ -40,25 +43,6 @@ constexpr int kStop = 0, kEvaluate = 1;
 
 static_assert(sizeof(sfm_pnp_refine_info) == 24, "sfm_pnp_refine_info layout is part of the ABI");
 
-// Block-wide sums of K doubles per thread in a fixed order (the block_sum of sfm_refine.hip): butterfly inside each wave,
-// then the wave partials added in wave order by one thread per value.  Result broadcast through `total`.
-template <int K>
-SFM_DEVICE void block_sum(double (&v)[K], double (*part)[kSums], double* total) {
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const double s = sfm::wave_sum(v[k]);
-        if (lane == 0) part[wave][k] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < K) {
-        double acc = part[0][threadIdx.x];
-        for (int w = 1; w < kWaves; ++w) acc += part[w][threadIdx.x];
-        total[threadIdx.x] = acc;
-    }
-    __syncthreads();
-}
-
 SFM_DEVICE double aggregate_total(int aggregation, double count, double sum1, double sum2) {
     switch (aggregation) {
         case SFM_AGG_SUM: return sum1;
@@ -69,9 +53,7 @@ SFM_DEVICE double aggregate_total(int aggregation, double count, double sum1, do
 }
 
 // This thread's share of C, H and g over the items with a non-zero mask, at model m.  e is pnp_score's value; an item
-// behind the camera (c2 <= 0) makes C infinite and adds nothing to H or g.  With c = R X + t, q = K c, r = q01 / c2 - uv:
-//   dr/dc = (1 / c2) [[K00, K01, K02 - q0 / c2], [K10, K11, K12 - q1 / c2]],  dc/domega = -[R X]x,  dc/dt = I,
-// so row k of J is (R X  x  A_k, A_k) with A_k row k of dr/dc.
+// behind the camera (c2 <= 0) makes C infinite and adds nothing to H or g.  J: the pose rows of sfmpnp::jacobians.
 SFM_DEVICE void accumulate(const double* __restrict__ P, int n, const uint8_t* __restrict__ mask, const double m[12],
                            const PnPCamera& k, double (&a)[kSums]) {
 #pragma unroll
@@ -81,26 +63,15 @@ SFM_DEVICE void accumulate(const double* __restrict__ P, int n, const uint8_t* _
         const double* q = P + (int64_t)i * kPnPFields;
         const double X = q[0], Y = q[1], Z = q[2], u = q[3], v = q[4];
         a[kSums - 1] += pnp_score(m, k, X, Y, Z, u, v);
-        const double r0 = (m[0] * X + m[1] * Y) + m[2] * Z;
-        const double r1 = (m[3] * X + m[4] * Y) + m[5] * Z;
-        const double r2 = (m[6] * X + m[7] * Y) + m[8] * Z;
-        const double c0 = r0 + m[9], c1 = r1 + m[10], c2 = r2 + m[11];
-        if (!(c2 > 0.0)) continue;
-        const double w0 = ((k.k00 * c0 + k.k01 * c1) + k.k02 * c2) / c2;
-        const double w1 = ((k.k10 * c0 + k.k11 * c1) + k.k12 * c2) / c2;
-        const double du = w0 - u, dv = w1 - v;
-        const double ic = 1.0 / c2;
-        const double A0[3] = {k.k00 * ic, k.k01 * ic, (k.k02 - w0) * ic};
-        const double A1[3] = {k.k10 * ic, k.k11 * ic, (k.k12 - w1) * ic};
-        const double J0[6] = {r1 * A0[2] - r2 * A0[1], r2 * A0[0] - r0 * A0[2], r0 * A0[1] - r1 * A0[0], A0[0], A0[1], A0[2]};
-        const double J1[6] = {r1 * A1[2] - r2 * A1[1], r2 * A1[0] - r0 * A1[2], r0 * A1[1] - r1 * A1[0], A1[0], A1[1], A1[2]};
+        double res[2], J[2][6], Jp[2][3];
+        if (!jacobians(m, k, X, Y, Z, J, Jp, res, u, v)) continue;
         int idx = 0;
 #pragma unroll
         for (int r = 0; r < 6; ++r)
 #pragma unroll
-            for (int c = r; c < 6; ++c) a[idx++] += J0[r] * J0[c] + J1[r] * J1[c];
+            for (int c = r; c < 6; ++c) a[idx++] += J[0][r] * J[0][c] + J[1][r] * J[1][c];
 #pragma unroll
-        for (int r = 0; r < 6; ++r) a[21 + r] += J0[r] * du + J1[r] * dv;
+        for (int r = 0; r < 6; ++r) a[21 + r] += J[0][r] * res[0] + J[1][r] * res[1];
     }
 }
 
@@ -155,43 +126,11 @@ SFM_DEVICE bool solve6(const double* sys, double lambda, double (&delta)[6]) {
     return finite;
 }
 
-// out = {exp([omega]x) R | t + dt} for delta = (omega, dt): Rodrigues, exp(W) = I + A W + B W^2 with A = sin(th) / th and
-// B = (1 - cos(th)) / th^2 = 2 sin^2(th / 2) / th^2, their Taylor forms below th = 1e-6.
-SFM_DEVICE void apply_step(const double* pose, const double (&delta)[6], double* out) {
-    const double w0 = delta[0], w1 = delta[1], w2 = delta[2];
-    const double th2 = (w0 * w0 + w1 * w1) + w2 * w2;
-    const double th = sqrt(th2);
-    double A, B;
-    if (th < 1e-6) {
-        A = 1.0 - th2 / 6.0;
-        B = 0.5 - th2 / 24.0;
-    } else {
-        const double s = sin(0.5 * th);
-        A = sin(th) / th;
-        B = 2.0 * s * s / th2;
-    }
-    const double W[3][3] = {{0.0, -w2, w1}, {w2, 0.0, -w0}, {-w1, w0, 0.0}};
-    double E[3][3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const double W2 = (W[r][0] * W[0][c] + W[r][1] * W[1][c]) + W[r][2] * W[2][c];
-            E[r][c] = ((r == c ? 1.0 : 0.0) + A * W[r][c]) + B * W2;
-        }
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) out[3 * r + c] = (E[r][0] * pose[c] + E[r][1] * pose[3 + c]) + E[r][2] * pose[6 + c];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) out[9 + r] = pose[9 + r] + delta[3 + r];
-}
-
 __global__ __launch_bounds__(kThreads) void pnp_refine_kernel(
     const double* __restrict__ pts, int n, PnPCamera cam, const double* __restrict__ model_in,
     const uint8_t* __restrict__ mask_in, const double* __restrict__ err_in, double thr, int aggregation, int rounds,
     int max_steps, double* __restrict__ model_out, uint8_t* __restrict__ mask_out, sfm_pnp_refine_info* __restrict__ info) {
-    __shared__ double part[kWaves][kSums];
+    __shared__ double part[kWaves * kSums];
     __shared__ double total[kSums];
     __shared__ double sys[kSums];  // H | g | C at the LM point (thread 0)
     __shared__ double best[12];    // the model kept so far
@@ -217,7 +156,7 @@ __global__ __launch_bounds__(kThreads) void pnp_refine_kernel(
         best[tid] = model_in[b * 12 + tid];
         model_out[b * 12 + tid] = best[tid];
     }
-    block_sum<1>(v1, part, total);
+    block_sum<1, kThreads>(v1, part, total);
     double best_cnt = total[0];
     double best_err = err_in[b];
     int accepted = 0;
@@ -232,7 +171,7 @@ __global__ __launch_bounds__(kThreads) void pnp_refine_kernel(
 #pragma unroll
         for (int k = 0; k < 12; ++k) m[k] = trial[k];
         accumulate(P, n, mout, m, cam, a);
-        block_sum<kSums>(a, part, total);
+        block_sum<kSums, kThreads>(a, part, total);
         double lambda = kLambda0;
         bool stop = false;
         int round_steps = 0;
@@ -268,7 +207,7 @@ __global__ __launch_bounds__(kThreads) void pnp_refine_kernel(
 #pragma unroll
             for (int k = 0; k < 12; ++k) m[k] = trial[k];
             accumulate(P, n, mout, m, cam, a);
-            block_sum<kSums>(a, part, total);
+            block_sum<kSums, kThreads>(a, part, total);
             if (tid == 0) {
                 const double c_new = total[kSums - 1], c_old = sys[kSums - 1];
                 if (isfinite(c_new) && c_new < c_old) {
@@ -297,7 +236,7 @@ __global__ __launch_bounds__(kThreads) void pnp_refine_kernel(
                 c[2] += e * e;
             }
         }
-        block_sum<3>(c, part, total);
+        block_sum<3, kThreads>(c, part, total);
         const double cnt = total[0];
         const double err = aggregate_total(aggregation, cnt, total[1], total[2]);
         const bool better = cnt > best_cnt || (cnt == best_cnt && err < best_err);  // NaN error never wins
