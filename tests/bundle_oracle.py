@@ -48,6 +48,56 @@ def cost(poses, points, cam, pt, uv, K):
     return float(np.sum(residuals(poses, points, cam, pt, uv, K)[0]))
 
 
+def inverse3(A):
+    """(A^-1 (n, 3, 3), ok (n,)) of symmetric 3 x 3 blocks as point_kernel computes them: the Cholesky factor L (a pivot
+    <= 0 or not finite fails that block), then A^-1 = L^-T L^-1, in the device's operation order.  A block with a
+    positive pivot is inverted however ill-conditioned it is: a point seen twice by one camera has V_p of rank 2 and V_p*
+    of condition about 1 / lambda, and is still a moving point."""
+    A = np.asarray(A, dtype=np.float64)
+    n = len(A)
+    L = np.zeros((n, 3, 3))
+    ok = np.ones(n, dtype=bool)
+    with np.errstate(all="ignore"):
+        for j in range(3):
+            s = A[:, j, j].copy()
+            for k in range(j):
+                s = s - L[:, j, k] * L[:, j, k]
+            ok &= (s > 0.0) & np.isfinite(s)
+            L[:, j, j] = np.sqrt(np.fmax(s, 0.0))
+            for i in range(j + 1, 3):
+                x = A[:, i, j].copy()
+                for k in range(j):
+                    x = x - L[:, i, k] * L[:, j, k]
+                L[:, i, j] = x / L[:, j, j]
+        Li = np.zeros((n, 3, 3))
+        for c in range(3):
+            for i in range(c, 3):
+                x = np.full(n, 1.0 if i == c else 0.0)
+                for k in range(c, i):
+                    x = x - L[:, i, k] * Li[:, k, c]
+                Li[:, i, c] = x / L[:, i, i]
+        inv = np.zeros((n, 3, 3))
+        for i in range(3):
+            for j in range(i, 3):
+                inv[:, i, j] = inv[:, j, i] = (Li[:, 0, i] * Li[:, 0, j] + Li[:, 1, i] * Li[:, 1, j]) + Li[:, 2, i] * Li[:, 2, j]
+    return inv, ok
+
+
+def damped_point_inverses(V, moving, lam):
+    """V_p*^-1 = (V_p + lam diag V_p)^-1 of every moving point by ``inverse3`` (zero for held points), or None when one of
+    them does not factor: that rejects the step."""
+    V = V.copy()
+    d = V[:, [0, 1, 2], [0, 1, 2]]
+    V[:, [0, 1, 2], [0, 1, 2]] = d + lam * d
+    Vi = np.zeros_like(V)
+    if moving.any():
+        inv, ok = inverse3(V[moving])
+        if not ok.all():
+            return None
+        Vi[moving] = inv
+    return Vi
+
+
 class Problem:
     def __init__(self, K, poses, points, cam, pt, uv, fixed):
         self.K = np.asarray(K, dtype=np.float64).reshape(3, 3)
@@ -77,6 +127,8 @@ class Problem:
 
     def solve_dense(self, s, lam):
         """(dc (C, 6), dX (P, 3)) of the whole damped system, or None when it does not factor or the step is not finite."""
+        if damped_point_inverses(s["V"], self.moving, lam) is None:   # the device's rule: every V_p* must factor
+            return None
         F, mv = len(self.free), np.nonzero(self.moving)[0]
         n = 6 * F + 3 * len(mv)
         pslot = np.full(self.P, -1)
@@ -113,16 +165,9 @@ class Problem:
         """The same step by the Schur complement on the points (vectorised; the device's algorithm)."""
         F, C6 = len(self.free), 6 * len(self.free)
         mv = self.moving
-        V = s["V"].copy()
-        d = V[:, [0, 1, 2], [0, 1, 2]]
-        V[:, [0, 1, 2], [0, 1, 2]] = d + lam * d
-        Vi = np.zeros_like(V)
-        if mv.any():
-            try:
-                np.linalg.cholesky(V[mv])
-            except np.linalg.LinAlgError:
-                return None
-            Vi[mv] = np.linalg.inv(V[mv])
+        Vi = damped_point_inverses(s["V"], mv, lam)
+        if Vi is None:
+            return None
         use = mv[self.pt] & (self.slot[self.cam] >= 0)          # observations that couple a free camera to a moving point
         S = np.zeros((C6, C6))
         rhs = np.zeros(C6)

@@ -21,16 +21,9 @@ class Problem(bo.Problem):
         """(dc (C, 6), dX (P, 3), cg iterations), or (None, cg iterations) for a rejected step."""
         F = len(self.free)
         mv = self.moving
-        V = s["V"].copy()
-        d = V[:, [0, 1, 2], [0, 1, 2]]
-        V[:, [0, 1, 2], [0, 1, 2]] = d + lam * d
-        Vi = np.zeros_like(V)
-        if mv.any():
-            try:
-                np.linalg.cholesky(V[mv])
-            except np.linalg.LinAlgError:
-                return None, 0
-            Vi[mv] = np.linalg.inv(V[mv])
+        Vi = bo.damped_point_inverses(s["V"], mv, lam)
+        if Vi is None:
+            return None, 0
         use = mv[self.pt] & (self.slot[self.cam] >= 0)   # observations that couple a free camera to a moving point
         obs = np.nonzero(use)[0]
         W = s["W"][obs]                                     # (n, 6, 3)
