@@ -125,7 +125,9 @@ class Reconstruction:
 def run(views: int = 8, points: int = 2000, seed: int = 21, noise_px: float = 0.5, outlier_fraction: float = 0.2,
         sed_threshold: float = 6e-6, reprojection_threshold: float = 16.0, iterations: int = 2000, refine_steps: int = 10,
         ba_steps: int = 20, final_ba_steps: int = 50, step_deg: float = 5.0, bundle_solver: str = "dense",
-        details: bool = False) -> dict:
+        details: bool = False, pnp_solver: str = "dlt") -> dict:
+    if pnp_solver not in ("dlt", "p3p"):
+        raise ValueError(f"pnp_solver must be 'dlt' or 'p3p', got {pnp_solver!r}")
     if bundle_solver not in BUNDLE_SOLVERS:
         raise ValueError(f"bundle_solver must be one of {BUNDLE_SOLVERS}, got {bundle_solver!r}")
     limit = DENSE_MAX_VIEWS if bundle_solver == "dense" else MAX_VIEWS
@@ -183,7 +185,7 @@ def run(views: int = 8, points: int = 2000, seed: int = 21, noise_px: float = 0.
         try:
             R, t, inliers = estimate_pose_pnp_with_ransac(K, X, features, matches, reprojection_threshold,
                                                           min_num_extra_inliers=10, max_iterations=iterations,
-                                                          refine_rounds=2)
+                                                          refine_rounds=2, solver=pnp_solver)
         except ValueError:
             break
         if len(inliers) < MIN_PNP_INLIERS:
@@ -240,13 +242,15 @@ def main():
     ap.add_argument("--step-deg", type=float, default=5.0, help="angle between neighbouring views on the arc (degrees)")
     ap.add_argument("--bundle-solver", choices=BUNDLE_SOLVERS, default="auto",
                     help="dense: at most 64 views; auto: the iterative solver above 64 registered cameras")
+    ap.add_argument("--pnp-solver", choices=("dlt", "p3p"), default="dlt",
+                    help="minimal solver that registers each further view: six-point DLT or P3P on four-item samples")
     args = ap.parse_args()
     limit = DENSE_MAX_VIEWS if args.bundle_solver == "dense" else MAX_VIEWS
     if not 2 <= args.views <= limit:
         ap.error(f"--views must be between 2 and {limit} with --bundle-solver {args.bundle_solver}")
     print(json.dumps(run(args.views, args.points, args.seed, args.noise, args.outliers, sed_threshold=args.sed_threshold,
                          reprojection_threshold=args.reprojection_threshold, refine_steps=args.refine_steps,
-                         step_deg=args.step_deg, bundle_solver=args.bundle_solver)))
+                         step_deg=args.step_deg, bundle_solver=args.bundle_solver, pnp_solver=args.pnp_solver)))
 
 
 if __name__ == "__main__":

@@ -58,7 +58,8 @@ def rotation_angle(Ra: np.ndarray, Rb: np.ndarray) -> float:
 
 
 def run(n: int = 400, seed: int = 11, outlier_fraction: float = 0.3, noise_px: float = 0.0, sed_threshold: float = 1.5e-6,
-        reprojection_threshold: float = 4.0, iterations: int = 2000, refine: int = 0, bundle_adjust: int = 0) -> dict:
+        reprojection_threshold: float = 4.0, iterations: int = 2000, refine: int = 0, bundle_adjust: int = 0,
+        pnp_solver: str = "dlt") -> dict:
     scene = three_view_scene(n, seed, outlier_fraction, noise_px)
     K = scene["K"]
     features_a = [Feature(float(x), float(y)) for x, y in scene["pa"]]
@@ -77,7 +78,7 @@ def run(n: int = 400, seed: int = 11, outlier_fraction: float = 0.3, noise_px: f
     matches = [Match(a_index=k, b_index=index_of[(p[0].x, p[0].y)]) for k, p in enumerate(kept)]
     state = random.getstate()
     R3, t3, inliers = estimate_pose_pnp_with_ransac(K, points, features_c, matches, reprojection_threshold,
-                                                    min_num_extra_inliers=10, max_iterations=iterations)
+                                                    min_num_extra_inliers=10, max_iterations=iterations, solver=pnp_solver)
     scale = np.linalg.norm(scene["t2"])
     unrefined = {}
     if refine > 0:
@@ -89,7 +90,7 @@ def run(n: int = 400, seed: int = 11, outlier_fraction: float = 0.3, noise_px: f
         random.setstate(state)   # the same RANSAC draw, now refined
         R3, t3, inliers = estimate_pose_pnp_with_ransac(K, points, features_c, matches, reprojection_threshold,
                                                         min_num_extra_inliers=10, max_iterations=iterations,
-                                                        refine_rounds=refine)
+                                                        refine_rounds=refine, solver=pnp_solver)
     adjusted = {}
     if bundle_adjust > 0:
         adjusted = _bundle_adjust(scene, K, points, kept, features_c, matches, R2, t2, R3, t3, reprojection_threshold,
@@ -156,10 +157,12 @@ def main():
     ap.add_argument("--bundle-adjust", type=int, default=0, metavar="N",
                     help="bundle-adjust the three views and the points, at most N LM steps (0: off); also reports the "
                          "errors before it")
+    ap.add_argument("--pnp-solver", choices=("dlt", "p3p"), default="dlt",
+                    help="minimal solver of the view-3 PnP: six-point DLT or P3P on four-item samples")
     args = ap.parse_args()
     print(json.dumps(run(args.points, args.seed, args.outliers, args.noise, sed_threshold=args.sed_threshold,
                          reprojection_threshold=args.reprojection_threshold, iterations=args.iterations,
-                         refine=args.refine, bundle_adjust=args.bundle_adjust)))
+                         refine=args.refine, bundle_adjust=args.bundle_adjust, pnp_solver=args.pnp_solver)))
 
 
 if __name__ == "__main__":

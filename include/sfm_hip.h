@@ -331,6 +331,41 @@ int sfm_pnp_ransac_pass(uint64_t seed, uint64_t seed_stride, int use_philox, int
                         double* model, int32_t* flags, int32_t* cnt, double* s1, double* s2, sfm_select_result* result,
                         uint8_t* mask, void* stream);
 
+/* ---- P3P: the minimal solver of RANSAC PnP (csrc/sfm_p3p.h, csrc/sfm_pnp.hip; an extension, added under ABI 14) ----
+ * Four-item samples: the first 4 entries of each row of S (the same [batch,h_count,8] tables).  Items 0-2 are solved for
+ * (up to four poses with depths lambda_i > 0 along f_i = normalise(K^-1 (u_i, v_i, 1)) and |lambda_i f_i - lambda_j f_j| =
+ * |X_i - X_j|), item 3 picks the pose with the strictly lowest sfm_pnp_score error, the earliest on ties.  A sample with no
+ * such pose ("no solution") gets a model of 12 NaNs and flag 0: it never gates nor wins.  flags: SFM_FIT_DEGENERATE when
+ * items 0-2 are collinear or coincide (|(X1-X0) x (X2-X0)|^2 <= 1e-18 |X1-X0|^2 |X2-X0|^2) or an index is out of range.
+ * Coplanar samples are not degenerate.  n >= 4. */
+int sfm_p3p_fit(const double* pts, int64_t n, const int32_t* S, int64_t h_count, int64_t batch, const double* K, double* model,
+                int32_t* flags, void* stream);
+
+/* Philox sampling fused into the P3P fit (first 4 of philox_sample8, all 8 stored in S, -1 at positions >= n). */
+int sfm_p3p_sample_fit_philox(uint64_t seed, uint64_t seed_stride, int64_t h_begin, const double* pts, int64_t n,
+                              int64_t h_count, int64_t batch, const double* K, int32_t* S, double* model, int32_t* flags,
+                              void* stream);
+
+/* sfm_pnp_score, sfm_pnp_select_best and sfm_pnp_inlier_mask for a sample of sample_size items (4 or 6; SFM_EINVAL
+ * otherwise): the first sample_size entries of S are the sample, the mean and RMS divide by count + sample_size. */
+int sfm_pnp_score_ex(const double* pts, int64_t n, const double* model, const int32_t* S, int64_t h_count, int64_t batch,
+                     const double* K, double thr, int sample_size, int32_t* cnt, double* s1, double* s2, void* stream);
+int sfm_pnp_select_best_ex(const int32_t* cnt, const double* s1, const double* s2, const int32_t* flags, int64_t h_count,
+                           int64_t batch, double min_extra, int aggregation, int64_t h_offset, int sample_size,
+                           sfm_select_result* result, void* stream);
+int sfm_pnp_inlier_mask_ex(const double* pts, int64_t n, const double* model, const int32_t* S, int64_t h_count, int64_t batch,
+                           const double* K, const sfm_select_result* result, double thr, int sample_size, uint8_t* mask,
+                           void* stream);
+
+#define SFM_PNP_SOLVER_DLT 0 /* six-point DLT, six-item samples (sfm_pnp_ransac_pass) */
+#define SFM_PNP_SOLVER_P3P 1 /* P3P, four-item samples; n >= 4 */
+
+/* sfm_pnp_ransac_pass with the fit of `solver` and the scoring, selection and mask of its sample size. */
+int sfm_pnp_ransac_pass_ex(int solver, uint64_t seed, uint64_t seed_stride, int use_philox, int64_t h_begin, const double* pts,
+                           int64_t n, int64_t h_count, int64_t batch, const double* K, double thr, double min_extra, int aggregation,
+                           int32_t* S, double* model, int32_t* flags, int32_t* cnt, double* s1, double* s2,
+                           sfm_select_result* result, uint8_t* mask, void* stream);
+
 /* ---- refinement of a PnP winner on its inliers (csrc/sfm_pnp_refine.hip; an extension, off unless asked for) ---- */
 
 typedef struct sfm_pnp_refine_info {

@@ -1,7 +1,7 @@
-// RANSAC absolute pose (PnP) of a further view against triangulated points: the six-point DLT fit, squared-reprojection
-// scoring of every hypothesis over every 2D-3D pair, selection and the winner's inlier mask.  The RANSAC semantics are
-// those of the reference's fit_with_ransac (lib/ransac/ransac.py:55-86) with a six-item sample, exactly as for the
-// essential matrix: the sample points enter the aggregate unconditionally, the other points when their score is at most
+// RANSAC absolute pose (PnP) of a further view against triangulated points: the six-point DLT fit or the P3P fit
+// (sfm_p3p.h, four-item samples), squared-reprojection scoring of every hypothesis over every 2D-3D pair, selection and
+// the winner's inlier mask.  The RANSAC semantics are those of the reference's fit_with_ransac
+// (lib/ransac/ransac.py:55-86) with a six- or four-item sample, exactly as for the essential matrix: the sample points enter the aggregate unconditionally, the other points when their score is at most
 // the threshold, the lowest aggregated error among gated hypotheses wins, earliest first, NaN / inf never.
 //
 // Data item i of batch entry b: pts[b, i] = {X, Y, Z, u, v} — a 3-D point in the frame of camera 1 and the pixel of its
@@ -13,6 +13,7 @@
 
 #include "sfm_common.h"
 #include "sfm_math.h"
+#include "sfm_p3p.h"
 #include "sfm_pnp.h"
 #include "sfm_select.h"
 
@@ -28,7 +29,8 @@ using sfmpnp::kPnPFields;
 using sfmpnp::pnp_score;
 using sfmpnp::PnPCamera;
 
-constexpr int kPnPSample = 6;
+constexpr int kPnPSample = 6;   // the DLT's sample
+constexpr int kP3PSample = 4;   // P3P: three items solved for, the fourth picks the solution
 // A sample is degenerate when sigma_11 / sigma_1 of its conditioned 12 x 12 DLT matrix is below this (or not a number).
 // Coplanar and collinear points give three or more null vectors: their ratio is at the rounding level (~1e-16).
 constexpr double kPnPDegenerateFloor = 1e-9;
@@ -198,11 +200,65 @@ __global__ __launch_bounds__(64) void pnp_sample_fit_philox_kernel(uint64_t seed
     flags[bh] = flag;
 }
 
+// P3P fit of one hypothesis (sfm_p3p.h) from sample indices idx[0..3]: SFM_FIT_DEGENERATE when items 0-2 are collinear or
+// coincide or an index is out of range; otherwise the chosen model, or 12 NaNs when the sample has no solution (flag 0).
+SFM_DEVICE int p3p_fit_indices(const double* __restrict__ pts, int64_t n, const int32_t idx[kP3PSample], const PnPCamera& k,
+                               double out[12]) {
+    bool bad = false;
+    const double* q0 = pts + checked_index(idx[0], n, bad) * kPnPFields;
+    const double* q1 = pts + checked_index(idx[1], n, bad) * kPnPFields;
+    const double* q2 = pts + checked_index(idx[2], n, bad) * kPnPFields;
+    const double* q3 = pts + checked_index(idx[3], n, bad) * kPnPFields;
+    const bool ok = sfmp3p::p3p_fit_one(q0, q1, q2, q3, k, out);
+    return (bad || !ok) ? SFM_FIT_DEGENERATE : 0;
+}
+
+// One hypothesis per lane, all in registers: the up-to-four candidates are scored as they are made (sfm_p3p.h).
+__global__ __launch_bounds__(64) void p3p_fit_kernel(const double* __restrict__ pts, int64_t n, const int32_t* __restrict__ S,
+                                                     int64_t h_count, PnPCamera cam, double* __restrict__ model,
+                                                     int32_t* __restrict__ flags) {
+    const int64_t h = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (h >= h_count) return;
+    const int64_t b = blockIdx.y;
+    const int64_t bh = b * h_count + h;
+    int32_t idx[kP3PSample];
+#pragma unroll
+    for (int i = 0; i < kP3PSample; ++i) idx[i] = S[bh * 8 + i];
+    double out[12];
+    const int flag = p3p_fit_indices(pts + b * n * kPnPFields, n, idx, cam, out);
+#pragma unroll
+    for (int i = 0; i < 12; ++i) model[bh * 12 + i] = out[i];
+    flags[bh] = flag;
+}
+
+// Philox sampling fused into the P3P fit, as pnp_sample_fit_philox_kernel: the first four of philox_sample8 are the sample;
+// S receives all eight (-1 at positions >= n, so n = 4 and 5 are valid).
+__global__ __launch_bounds__(64) void p3p_sample_fit_philox_kernel(uint64_t seed, uint64_t seed_stride, int64_t h_begin,
+                                                                   const double* __restrict__ pts, int64_t n, int64_t h_count,
+                                                                   PnPCamera cam, int32_t* __restrict__ S,
+                                                                   double* __restrict__ model, int32_t* __restrict__ flags) {
+    const int64_t h = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (h >= h_count) return;
+    const int64_t b = blockIdx.y;
+    const int64_t bh = b * h_count + h;
+    int32_t idx[8];
+    sfm::philox_sample8(seed + (uint64_t)b * seed_stride, (uint64_t)(h_begin + h), (uint32_t)n, idx);
+#pragma unroll
+    for (int i = kP3PSample; i < 8; ++i) idx[i] = i < n ? idx[i] : -1;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) S[bh * 8 + i] = idx[i];
+    double out[12];
+    const int flag = p3p_fit_indices(pts + b * n * kPnPFields, n, idx, cam, out);
+#pragma unroll
+    for (int i = 0; i < 12; ++i) model[bh * 12 + i] = out[i];
+    flags[bh] = flag;
+}
+
 // --------------------------------------------------------------------------------------------------
 // Scoring: one hypothesis per lane (its model in registers), the points staged through LDS in tiles that every lane of
 // the block reads at the same address (broadcast).  cnt = non-sample points with e <= thr; s1 / s2 = sums of e / e^2 over
 // the six sample points and those survivors (the layout sfm_select_best reads).  The tile loop counts every point; the
-// six sample points are then corrected: one that passed the gate is taken out of the count (its value is already in the
+// SAMPLE sample points are then corrected: one that passed the gate is taken out of the count (its value is already in the
 // sums), one that did not is added to the sums.  All fp64 with the divisions of pnp_score: no fast path, so every value is
 // the oracle's bit for bit and only the summation order differs.
 // --------------------------------------------------------------------------------------------------
@@ -213,6 +269,7 @@ struct alignas(16) TilePoint {
     double2 xy, zu, v_;
 };
 
+template <int SAMPLE>
 __global__ __launch_bounds__(kPnPScoreBlock) void pnp_score_kernel(const double* __restrict__ pts, int64_t n,
                                                                    const double* __restrict__ model,
                                                                    const int32_t* __restrict__ S, int64_t h_count, PnPCamera cam,
@@ -251,7 +308,7 @@ __global__ __launch_bounds__(kPnPScoreBlock) void pnp_score_kernel(const double*
     }
     bool bad = false;
 #pragma unroll
-    for (int k = 0; k < kPnPSample; ++k) {
+    for (int k = 0; k < SAMPLE; ++k) {
         const double* q = P + checked_index(S[bh * 8 + k], n, bad) * kPnPFields;
         const double e = pnp_score(m, cam, q[0], q[1], q[2], q[3], q[4]);
         if (e <= thr) {
@@ -269,11 +326,12 @@ __global__ __launch_bounds__(kPnPScoreBlock) void pnp_score_kernel(const double*
 }
 
 // --------------------------------------------------------------------------------------------------
-// Selection (ransac.py:75-86 with a six-point sample in the mean): one block per batch entry, the block_select of the
-// essential-matrix path with sample_size 6.
+// Selection (ransac.py:75-86 with a SAMPLE-point sample in the mean): one block per batch entry, the block_select of the
+// essential-matrix path with sample_size SAMPLE (6 for the DLT, 4 for P3P).
 // --------------------------------------------------------------------------------------------------
 constexpr int kPnPSelectBlock = 256;
 
+template <int SAMPLE>
 __global__ __launch_bounds__(kPnPSelectBlock) void pnp_select_kernel(const int32_t* __restrict__ cnt, const double* __restrict__ s1,
                                                                      const double* __restrict__ s2, const int32_t* __restrict__ flags,
                                                                      int64_t h_count, int64_t h_offset, double min_extra,
@@ -283,11 +341,12 @@ __global__ __launch_bounds__(kPnPSelectBlock) void pnp_select_kernel(const int32
     const int64_t b = blockIdx.x;
     sfmsel::block_select<kPnPSelectBlock>(cnt + b * h_count, s1 + b * h_count, s2 + b * h_count,
                                           flags != nullptr ? flags + b * h_count : nullptr, h_count, h_offset, min_extra,
-                                          aggregation, result + b, sh, &winner, kPnPSample);
+                                          aggregation, result + b, sh, &winner, SAMPLE);
 }
 
-// mask[b, i] = 2 for the six sample points of the winner, 1 for the other points with e <= thr, 0 otherwise (all 0 when
+// mask[b, i] = 2 for the SAMPLE sample points of the winner, 1 for the other points with e <= thr, 0 otherwise (all 0 when
 // the record holds no model).  Grid-stride over the points; every byte of the mask is written.
+template <int SAMPLE>
 __global__ void pnp_inlier_mask_kernel(const double* __restrict__ pts, int64_t n, const double* __restrict__ model,
                                        const int32_t* __restrict__ S, int64_t h_count, PnPCamera cam,
                                        const sfm_select_result* __restrict__ result, double thr, uint8_t* __restrict__ mask) {
@@ -303,31 +362,31 @@ __global__ void pnp_inlier_mask_kernel(const double* __restrict__ pts, int64_t n
         return;
     }
     double m[12];
-    int32_t smp[kPnPSample];
+    int32_t smp[SAMPLE];
 #pragma unroll
     for (int k = 0; k < 12; ++k) m[k] = model[bh * 12 + k];
 #pragma unroll
-    for (int k = 0; k < kPnPSample; ++k) smp[k] = S[bh * 8 + k];
+    for (int k = 0; k < SAMPLE; ++k) smp[k] = S[bh * 8 + k];
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         const double* q = P + i * kPnPFields;
         const double e = pnp_score(m, cam, q[0], q[1], q[2], q[3], q[4]);
         bool in_sample = false;
 #pragma unroll
-        for (int k = 0; k < kPnPSample; ++k) in_sample |= (smp[k] == (int32_t)i);
+        for (int k = 0; k < SAMPLE; ++k) in_sample |= (smp[k] == (int32_t)i);
         out[i] = in_sample ? 2 : ((e <= thr) ? 1 : 0);
     }
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
-// Every size check of a call, before anything is launched.
-int check_sizes(const char* fn, int64_t n, int64_t h_count, int64_t batch) {
+// Every size check of a call, before anything is launched.  `sample` is the sample size: n must be at least that.
+int check_sizes(const char* fn, int64_t n, int64_t h_count, int64_t batch, int sample = kPnPSample) {
     char msg[200];
     if (n < 0 || h_count < 0 || batch < 0) {
         snprintf(msg, sizeof msg, "%s: negative size", fn);
         return fail(SFM_EINVAL, msg);
     }
-    if (n < kPnPSample || n > 0x7FFFFFFF) {
-        snprintf(msg, sizeof msg, "%s: need 6 <= n < 2^31 2D-3D pairs", fn);
+    if (n < sample || n > 0x7FFFFFFF) {
+        snprintf(msg, sizeof msg, "%s: need %d <= n < 2^31 2D-3D pairs", fn, sample);
         return fail(SFM_EINVAL, msg);
     }
     if (batch > 65535 || !grid_fits(h_count, kPnPScoreBlock, kPnPScoreBlock, batch) || !grid_fits(h_count, 64, 64, batch)) {
@@ -337,106 +396,274 @@ int check_sizes(const char* fn, int64_t n, int64_t h_count, int64_t batch) {
     return SFM_OK;
 }
 
+int check_sample_size(const char* fn, int sample_size) {
+    if (sample_size == kPnPSample || sample_size == kP3PSample) return SFM_OK;
+    char msg[160];
+    snprintf(msg, sizeof msg, "%s: sample_size must be 4 or 6, got %d", fn, sample_size);
+    return fail(SFM_EINVAL, msg);
+}
+
+// The launches shared by the plain and the _ex entry points (SAMPLE 6: exactly the launches of the DLT path).
+template <int SAMPLE>
+int launch_score(const double* pts, int64_t n, const double* model, const int32_t* S, int64_t h_count, int64_t batch,
+                 const PnPCamera& cam, double thr, int32_t* cnt, double* s1, double* s2, hipStream_t st) {
+    hipLaunchKernelGGL(pnp_score_kernel<SAMPLE>, dim3(grid_for(h_count, kPnPScoreBlock), (unsigned)batch), dim3(kPnPScoreBlock), 0,
+                       st, pts, n, model, S, h_count, cam, thr, cnt, s1, s2);
+    return check_launch("pnp_score_kernel");
+}
+
+template <int SAMPLE>
+int launch_select(const int32_t* cnt, const double* s1, const double* s2, const int32_t* flags, int64_t h_count, int64_t batch,
+                  double min_extra, int aggregation, int64_t h_offset, sfm_select_result* result, hipStream_t st) {
+    hipLaunchKernelGGL(pnp_select_kernel<SAMPLE>, dim3((unsigned)batch), dim3(kPnPSelectBlock), 0, st, cnt, s1, s2, flags, h_count,
+                       h_offset, min_extra, aggregation, result);
+    return check_launch("pnp_select_kernel");
+}
+
+template <int SAMPLE>
+int launch_mask(const double* pts, int64_t n, const double* model, const int32_t* S, int64_t h_count, int64_t batch,
+                const PnPCamera& cam, const sfm_select_result* result, double thr, uint8_t* mask, hipStream_t st) {
+    hipLaunchKernelGGL(pnp_inlier_mask_kernel<SAMPLE>, dim3(grid_stride(n, 256, 1024), (unsigned)batch), dim3(256), 0, st, pts, n,
+                       model, S, h_count, cam, result, thr, mask);
+    return check_launch("pnp_inlier_mask_kernel");
+}
+
+int score_any(int sample, const double* pts, int64_t n, const double* model, const int32_t* S, int64_t h_count, int64_t batch,
+              const PnPCamera& cam, double thr, int32_t* cnt, double* s1, double* s2, hipStream_t st) {
+    return sample == kP3PSample ? launch_score<kP3PSample>(pts, n, model, S, h_count, batch, cam, thr, cnt, s1, s2, st)
+                                : launch_score<kPnPSample>(pts, n, model, S, h_count, batch, cam, thr, cnt, s1, s2, st);
+}
+
+int select_any(int sample, const int32_t* cnt, const double* s1, const double* s2, const int32_t* flags, int64_t h_count,
+               int64_t batch, double min_extra, int aggregation, int64_t h_offset, sfm_select_result* result, hipStream_t st) {
+    return sample == kP3PSample
+               ? launch_select<kP3PSample>(cnt, s1, s2, flags, h_count, batch, min_extra, aggregation, h_offset, result, st)
+               : launch_select<kPnPSample>(cnt, s1, s2, flags, h_count, batch, min_extra, aggregation, h_offset, result, st);
+}
+
+int mask_any(int sample, const double* pts, int64_t n, const double* model, const int32_t* S, int64_t h_count, int64_t batch,
+             const PnPCamera& cam, const sfm_select_result* result, double thr, uint8_t* mask, hipStream_t st) {
+    return sample == kP3PSample ? launch_mask<kP3PSample>(pts, n, model, S, h_count, batch, cam, result, thr, mask, st)
+                                : launch_mask<kPnPSample>(pts, n, model, S, h_count, batch, cam, result, thr, mask, st);
+}
+
+int fit_entry(const char* fn, bool p3p, const double* pts, int64_t n, const int32_t* S, int64_t h_count, int64_t batch,
+              const double* K, double* model, int32_t* flags, void* stream) {
+    int rc = check_sizes(fn, n, h_count, batch, p3p ? kP3PSample : kPnPSample);
+    if (rc != SFM_OK) return rc;
+    PnPCamera cam;
+    if ((rc = camera_from(K, cam, fn)) != SFM_OK) return rc;
+    if (h_count == 0 || batch == 0) return SFM_OK;
+    char msg[120];
+    snprintf(msg, sizeof msg, "%s: null pointer", fn);
+    if (!pts || !S || !model || !flags) return fail(SFM_EINVAL, msg);
+    const dim3 grid(grid_for(h_count, 64), (unsigned)batch);
+    if (p3p) {
+        hipLaunchKernelGGL(p3p_fit_kernel, grid, dim3(64), 0, (hipStream_t)stream, pts, n, S, h_count, cam, model, flags);
+        return check_launch("p3p_fit_kernel");
+    }
+    hipLaunchKernelGGL(pnp_fit_kernel, grid, dim3(64), 0, (hipStream_t)stream, pts, n, S, h_count, cam, model, flags);
+    return check_launch("pnp_fit_kernel");
+}
+
+int sample_fit_entry(const char* fn, bool p3p, uint64_t seed, uint64_t seed_stride, int64_t h_begin, const double* pts, int64_t n,
+                     int64_t h_count, int64_t batch, const double* K, int32_t* S, double* model, int32_t* flags, void* stream) {
+    int rc = check_sizes(fn, n, h_count, batch, p3p ? kP3PSample : kPnPSample);
+    if (rc != SFM_OK) return rc;
+    char msg[120];
+    if (h_begin < 0) {
+        snprintf(msg, sizeof msg, "%s: negative h_begin", fn);
+        return fail(SFM_EINVAL, msg);
+    }
+    PnPCamera cam;
+    if ((rc = camera_from(K, cam, fn)) != SFM_OK) return rc;
+    if (h_count == 0 || batch == 0) return SFM_OK;
+    snprintf(msg, sizeof msg, "%s: null pointer", fn);
+    if (!pts || !S || !model || !flags) return fail(SFM_EINVAL, msg);
+    const dim3 grid(grid_for(h_count, 64), (unsigned)batch);
+    if (p3p) {
+        hipLaunchKernelGGL(p3p_sample_fit_philox_kernel, grid, dim3(64), 0, (hipStream_t)stream, seed, seed_stride, h_begin, pts, n,
+                           h_count, cam, S, model, flags);
+        return check_launch("p3p_sample_fit_philox_kernel");
+    }
+    hipLaunchKernelGGL(pnp_sample_fit_philox_kernel, grid, dim3(64), 0, (hipStream_t)stream, seed, seed_stride, h_begin, pts, n,
+                       h_count, cam, S, model, flags);
+    return check_launch("pnp_sample_fit_philox_kernel");
+}
+
+int score_entry(const char* fn, int sample, const double* pts, int64_t n, const double* model, const int32_t* S, int64_t h_count,
+                int64_t batch, const double* K, double thr, int32_t* cnt, double* s1, double* s2, void* stream) {
+    int rc = check_sample_size(fn, sample);
+    if (rc != SFM_OK) return rc;
+    if ((rc = check_sizes(fn, n, h_count, batch, sample)) != SFM_OK) return rc;
+    PnPCamera cam;
+    if ((rc = camera_from(K, cam, fn)) != SFM_OK) return rc;
+    if (h_count == 0 || batch == 0) return SFM_OK;
+    char msg[120];
+    snprintf(msg, sizeof msg, "%s: null pointer", fn);
+    if (!pts || !model || !S || !cnt || !s1 || !s2) return fail(SFM_EINVAL, msg);
+    return score_any(sample, pts, n, model, S, h_count, batch, cam, thr, cnt, s1, s2, (hipStream_t)stream);
+}
+
+int select_entry(const char* fn, int sample, const int32_t* cnt, const double* s1, const double* s2, const int32_t* flags,
+                 int64_t h_count, int64_t batch, double min_extra, int aggregation, int64_t h_offset, sfm_select_result* result,
+                 void* stream) {
+    int rc = check_sample_size(fn, sample);
+    if (rc != SFM_OK) return rc;
+    char msg[160];
+    if (h_count < 0 || batch < 0) {
+        snprintf(msg, sizeof msg, "%s: negative size", fn);
+        return fail(SFM_EINVAL, msg);
+    }
+    if (aggregation < SFM_AGG_SUM || aggregation > SFM_AGG_RMS) {
+        snprintf(msg, sizeof msg, "%s: unknown aggregation", fn);
+        return fail(SFM_EINVAL, msg);
+    }
+    if (batch > 65535) {
+        snprintf(msg, sizeof msg, "%s: batch > 65535", fn);
+        return fail(SFM_EINVAL, msg);
+    }
+    if (batch == 0) return SFM_OK;
+    snprintf(msg, sizeof msg, "%s: null pointer", fn);
+    if (!result || (h_count > 0 && (!cnt || !s1 || !s2))) return fail(SFM_EINVAL, msg);
+    return select_any(sample, cnt, s1, s2, flags, h_count, batch, min_extra, aggregation, h_offset, result, (hipStream_t)stream);
+}
+
+int mask_entry(const char* fn, int sample, const double* pts, int64_t n, const double* model, const int32_t* S, int64_t h_count,
+               int64_t batch, const double* K, const sfm_select_result* result, double thr, uint8_t* mask, void* stream) {
+    int rc = check_sample_size(fn, sample);
+    if (rc != SFM_OK) return rc;
+    if ((rc = check_sizes(fn, n, h_count, batch, sample)) != SFM_OK) return rc;
+    PnPCamera cam;
+    if ((rc = camera_from(K, cam, fn)) != SFM_OK) return rc;
+    if (batch == 0) return SFM_OK;
+    char msg[120];
+    snprintf(msg, sizeof msg, "%s: null pointer", fn);
+    if (!pts || !model || !S || !result || !mask) return fail(SFM_EINVAL, msg);
+    return mask_any(sample, pts, n, model, S, h_count, batch, cam, result, thr, mask, (hipStream_t)stream);
+}
+
+int pass_entry(const char* fn, int solver, uint64_t seed, uint64_t seed_stride, int use_philox, int64_t h_begin, const double* pts,
+               int64_t n, int64_t h_count, int64_t batch, const double* K, double thr, double min_extra, int aggregation,
+               int32_t* S, double* model, int32_t* flags, int32_t* cnt, double* s1, double* s2, sfm_select_result* result,
+               uint8_t* mask, void* stream) {
+    // every argument and grid is checked before the first launch: a refused call has enqueued nothing
+    char msg[160];
+    if (solver != SFM_PNP_SOLVER_DLT && solver != SFM_PNP_SOLVER_P3P) {
+        snprintf(msg, sizeof msg, "%s: unknown solver %d", fn, solver);
+        return fail(SFM_EINVAL, msg);
+    }
+    const bool p3p = solver == SFM_PNP_SOLVER_P3P;
+    const int sample = p3p ? kP3PSample : kPnPSample;
+    int rc = check_sizes(fn, n, h_count, batch, sample);
+    if (rc != SFM_OK) return rc;
+    PnPCamera cam;
+    if ((rc = camera_from(K, cam, fn)) != SFM_OK) return rc;
+    if (aggregation < SFM_AGG_SUM || aggregation > SFM_AGG_RMS) {
+        snprintf(msg, sizeof msg, "%s: unknown aggregation", fn);
+        return fail(SFM_EINVAL, msg);
+    }
+    if (h_begin < 0) {
+        snprintf(msg, sizeof msg, "%s: negative h_begin", fn);
+        return fail(SFM_EINVAL, msg);
+    }
+    if (batch == 0) return SFM_OK;
+    snprintf(msg, sizeof msg, "%s: null pointer", fn);
+    if (!pts || !S || !model || !flags || !cnt || !s1 || !s2 || !result) return fail(SFM_EINVAL, msg);
+    hipStream_t st = (hipStream_t)stream;
+    if (h_count > 0) {
+        const dim3 fit_grid(grid_for(h_count, 64), (unsigned)batch);
+        if (p3p && use_philox)
+            hipLaunchKernelGGL(p3p_sample_fit_philox_kernel, fit_grid, dim3(64), 0, st, seed, seed_stride, h_begin, pts, n, h_count, cam,
+                               S, model, flags);
+        else if (p3p)
+            hipLaunchKernelGGL(p3p_fit_kernel, fit_grid, dim3(64), 0, st, pts, n, (const int32_t*)S, h_count, cam, model, flags);
+        else if (use_philox)
+            hipLaunchKernelGGL(pnp_sample_fit_philox_kernel, fit_grid, dim3(64), 0, st, seed, seed_stride, h_begin, pts, n, h_count, cam,
+                               S, model, flags);
+        else
+            hipLaunchKernelGGL(pnp_fit_kernel, fit_grid, dim3(64), 0, st, pts, n, (const int32_t*)S, h_count, cam, model, flags);
+        if ((rc = check_launch(p3p ? "p3p_fit_kernel" : "pnp_fit_kernel")) != SFM_OK) return rc;
+        if ((rc = score_any(sample, pts, n, model, S, h_count, batch, cam, thr, cnt, s1, s2, st)) != SFM_OK) return rc;
+    }
+    if ((rc = select_any(sample, cnt, s1, s2, flags, h_count, batch, min_extra, aggregation, 0, result, st)) != SFM_OK) return rc;
+    if (mask == nullptr) return SFM_OK;
+    return mask_any(sample, pts, n, model, S, h_count, batch, cam, result, thr, mask, st);
+}
+
 }  // namespace
 
 int sfm_pnp_fit(const double* pts, int64_t n, const int32_t* S, int64_t h_count, int64_t batch, const double* K, double* model,
                 int32_t* flags, void* stream) {
-    int rc = check_sizes("sfm_pnp_fit", n, h_count, batch);
-    if (rc != SFM_OK) return rc;
-    PnPCamera cam;
-    if ((rc = camera_from(K, cam, "sfm_pnp_fit")) != SFM_OK) return rc;
-    if (h_count == 0 || batch == 0) return SFM_OK;
-    if (!pts || !S || !model || !flags) return fail(SFM_EINVAL, "sfm_pnp_fit: null pointer");
-    hipLaunchKernelGGL(pnp_fit_kernel, dim3(grid_for(h_count, 64), (unsigned)batch), dim3(64), 0, (hipStream_t)stream, pts, n, S,
-                       h_count, cam, model, flags);
-    return check_launch("pnp_fit_kernel");
+    return fit_entry("sfm_pnp_fit", false, pts, n, S, h_count, batch, K, model, flags, stream);
 }
 
 int sfm_pnp_sample_fit_philox(uint64_t seed, uint64_t seed_stride, int64_t h_begin, const double* pts, int64_t n,
                               int64_t h_count, int64_t batch, const double* K, int32_t* S, double* model, int32_t* flags,
                               void* stream) {
-    int rc = check_sizes("sfm_pnp_sample_fit_philox", n, h_count, batch);
-    if (rc != SFM_OK) return rc;
-    if (h_begin < 0) return fail(SFM_EINVAL, "sfm_pnp_sample_fit_philox: negative h_begin");
-    PnPCamera cam;
-    if ((rc = camera_from(K, cam, "sfm_pnp_sample_fit_philox")) != SFM_OK) return rc;
-    if (h_count == 0 || batch == 0) return SFM_OK;
-    if (!pts || !S || !model || !flags) return fail(SFM_EINVAL, "sfm_pnp_sample_fit_philox: null pointer");
-    hipLaunchKernelGGL(pnp_sample_fit_philox_kernel, dim3(grid_for(h_count, 64), (unsigned)batch), dim3(64), 0,
-                       (hipStream_t)stream, seed, seed_stride, h_begin, pts, n, h_count, cam, S, model, flags);
-    return check_launch("pnp_sample_fit_philox_kernel");
+    return sample_fit_entry("sfm_pnp_sample_fit_philox", false, seed, seed_stride, h_begin, pts, n, h_count, batch, K, S, model,
+                            flags, stream);
+}
+
+int sfm_p3p_fit(const double* pts, int64_t n, const int32_t* S, int64_t h_count, int64_t batch, const double* K, double* model,
+                int32_t* flags, void* stream) {
+    return fit_entry("sfm_p3p_fit", true, pts, n, S, h_count, batch, K, model, flags, stream);
+}
+
+int sfm_p3p_sample_fit_philox(uint64_t seed, uint64_t seed_stride, int64_t h_begin, const double* pts, int64_t n,
+                              int64_t h_count, int64_t batch, const double* K, int32_t* S, double* model, int32_t* flags,
+                              void* stream) {
+    return sample_fit_entry("sfm_p3p_sample_fit_philox", true, seed, seed_stride, h_begin, pts, n, h_count, batch, K, S, model,
+                            flags, stream);
 }
 
 int sfm_pnp_score(const double* pts, int64_t n, const double* model, const int32_t* S, int64_t h_count, int64_t batch,
                   const double* K, double thr, int32_t* cnt, double* s1, double* s2, void* stream) {
-    int rc = check_sizes("sfm_pnp_score", n, h_count, batch);
-    if (rc != SFM_OK) return rc;
-    PnPCamera cam;
-    if ((rc = camera_from(K, cam, "sfm_pnp_score")) != SFM_OK) return rc;
-    if (h_count == 0 || batch == 0) return SFM_OK;
-    if (!pts || !model || !S || !cnt || !s1 || !s2) return fail(SFM_EINVAL, "sfm_pnp_score: null pointer");
-    hipLaunchKernelGGL(pnp_score_kernel, dim3(grid_for(h_count, kPnPScoreBlock), (unsigned)batch), dim3(kPnPScoreBlock), 0,
-                       (hipStream_t)stream, pts, n, model, S, h_count, cam, thr, cnt, s1, s2);
-    return check_launch("pnp_score_kernel");
+    return score_entry("sfm_pnp_score", kPnPSample, pts, n, model, S, h_count, batch, K, thr, cnt, s1, s2, stream);
+}
+
+int sfm_pnp_score_ex(const double* pts, int64_t n, const double* model, const int32_t* S, int64_t h_count, int64_t batch,
+                     const double* K, double thr, int sample_size, int32_t* cnt, double* s1, double* s2, void* stream) {
+    return score_entry("sfm_pnp_score_ex", sample_size, pts, n, model, S, h_count, batch, K, thr, cnt, s1, s2, stream);
 }
 
 int sfm_pnp_select_best(const int32_t* cnt, const double* s1, const double* s2, const int32_t* flags, int64_t h_count,
                         int64_t batch, double min_extra, int aggregation, int64_t h_offset, sfm_select_result* result,
                         void* stream) {
-    if (h_count < 0 || batch < 0) return fail(SFM_EINVAL, "sfm_pnp_select_best: negative size");
-    if (aggregation < SFM_AGG_SUM || aggregation > SFM_AGG_RMS) return fail(SFM_EINVAL, "sfm_pnp_select_best: unknown aggregation");
-    if (batch > 65535) return fail(SFM_EINVAL, "sfm_pnp_select_best: batch > 65535");
-    if (batch == 0) return SFM_OK;
-    if (!result || (h_count > 0 && (!cnt || !s1 || !s2))) return fail(SFM_EINVAL, "sfm_pnp_select_best: null pointer");
-    hipLaunchKernelGGL(pnp_select_kernel, dim3((unsigned)batch), dim3(kPnPSelectBlock), 0, (hipStream_t)stream, cnt, s1, s2, flags,
-                       h_count, h_offset, min_extra, aggregation, result);
-    return check_launch("pnp_select_kernel");
+    return select_entry("sfm_pnp_select_best", kPnPSample, cnt, s1, s2, flags, h_count, batch, min_extra, aggregation, h_offset,
+                        result, stream);
+}
+
+int sfm_pnp_select_best_ex(const int32_t* cnt, const double* s1, const double* s2, const int32_t* flags, int64_t h_count,
+                           int64_t batch, double min_extra, int aggregation, int64_t h_offset, int sample_size,
+                           sfm_select_result* result, void* stream) {
+    return select_entry("sfm_pnp_select_best_ex", sample_size, cnt, s1, s2, flags, h_count, batch, min_extra, aggregation, h_offset,
+                        result, stream);
 }
 
 int sfm_pnp_inlier_mask(const double* pts, int64_t n, const double* model, const int32_t* S, int64_t h_count, int64_t batch,
                         const double* K, const sfm_select_result* result, double thr, uint8_t* mask, void* stream) {
-    int rc = check_sizes("sfm_pnp_inlier_mask", n, h_count, batch);
-    if (rc != SFM_OK) return rc;
-    PnPCamera cam;
-    if ((rc = camera_from(K, cam, "sfm_pnp_inlier_mask")) != SFM_OK) return rc;
-    if (batch == 0) return SFM_OK;
-    if (!pts || !model || !S || !result || !mask) return fail(SFM_EINVAL, "sfm_pnp_inlier_mask: null pointer");
-    hipLaunchKernelGGL(pnp_inlier_mask_kernel, dim3(grid_stride(n, 256, 1024), (unsigned)batch), dim3(256), 0, (hipStream_t)stream,
-                       pts, n, model, S, h_count, cam, result, thr, mask);
-    return check_launch("pnp_inlier_mask_kernel");
+    return mask_entry("sfm_pnp_inlier_mask", kPnPSample, pts, n, model, S, h_count, batch, K, result, thr, mask, stream);
+}
+
+int sfm_pnp_inlier_mask_ex(const double* pts, int64_t n, const double* model, const int32_t* S, int64_t h_count, int64_t batch,
+                           const double* K, const sfm_select_result* result, double thr, int sample_size, uint8_t* mask,
+                           void* stream) {
+    return mask_entry("sfm_pnp_inlier_mask_ex", sample_size, pts, n, model, S, h_count, batch, K, result, thr, mask, stream);
 }
 
 int sfm_pnp_ransac_pass(uint64_t seed, uint64_t seed_stride, int use_philox, int64_t h_begin, const double* pts, int64_t n,
                         int64_t h_count, int64_t batch, const double* K, double thr, double min_extra, int aggregation, int32_t* S,
                         double* model, int32_t* flags, int32_t* cnt, double* s1, double* s2, sfm_select_result* result,
                         uint8_t* mask, void* stream) {
-    // every argument and grid is checked before the first launch: a refused call has enqueued nothing
-    int rc = check_sizes("sfm_pnp_ransac_pass", n, h_count, batch);
-    if (rc != SFM_OK) return rc;
-    PnPCamera cam;
-    if ((rc = camera_from(K, cam, "sfm_pnp_ransac_pass")) != SFM_OK) return rc;
-    if (aggregation < SFM_AGG_SUM || aggregation > SFM_AGG_RMS) return fail(SFM_EINVAL, "sfm_pnp_ransac_pass: unknown aggregation");
-    if (h_begin < 0) return fail(SFM_EINVAL, "sfm_pnp_ransac_pass: negative h_begin");
-    if (batch == 0) return SFM_OK;
-    if (!pts || !S || !model || !flags || !cnt || !s1 || !s2 || !result) return fail(SFM_EINVAL, "sfm_pnp_ransac_pass: null pointer");
-    hipStream_t st = (hipStream_t)stream;
-    if (h_count > 0) {
-        const dim3 fit_grid(grid_for(h_count, 64), (unsigned)batch);
-        if (use_philox)
-            hipLaunchKernelGGL(pnp_sample_fit_philox_kernel, fit_grid, dim3(64), 0, st, seed, seed_stride, h_begin, pts, n, h_count, cam,
-                               S, model, flags);
-        else
-            hipLaunchKernelGGL(pnp_fit_kernel, fit_grid, dim3(64), 0, st, pts, n, (const int32_t*)S, h_count, cam, model, flags);
-        if ((rc = check_launch("pnp_fit_kernel")) != SFM_OK) return rc;
-        hipLaunchKernelGGL(pnp_score_kernel, dim3(grid_for(h_count, kPnPScoreBlock), (unsigned)batch), dim3(kPnPScoreBlock), 0, st, pts,
-                           n, (const double*)model, (const int32_t*)S, h_count, cam, thr, cnt, s1, s2);
-        if ((rc = check_launch("pnp_score_kernel")) != SFM_OK) return rc;
-    }
-    hipLaunchKernelGGL(pnp_select_kernel, dim3((unsigned)batch), dim3(kPnPSelectBlock), 0, st, (const int32_t*)cnt, (const double*)s1,
-                       (const double*)s2, (const int32_t*)flags, h_count, (int64_t)0, min_extra, aggregation, result);
-    if ((rc = check_launch("pnp_select_kernel")) != SFM_OK) return rc;
-    if (mask == nullptr) return SFM_OK;
-    hipLaunchKernelGGL(pnp_inlier_mask_kernel, dim3(grid_stride(n, 256, 1024), (unsigned)batch), dim3(256), 0, st, pts, n,
-                       (const double*)model, (const int32_t*)S, h_count, cam, (const sfm_select_result*)result, thr, mask);
-    return check_launch("pnp_inlier_mask_kernel");
+    return pass_entry("sfm_pnp_ransac_pass", SFM_PNP_SOLVER_DLT, seed, seed_stride, use_philox, h_begin, pts, n, h_count, batch, K,
+                      thr, min_extra, aggregation, S, model, flags, cnt, s1, s2, result, mask, stream);
+}
+
+int sfm_pnp_ransac_pass_ex(int solver, uint64_t seed, uint64_t seed_stride, int use_philox, int64_t h_begin, const double* pts,
+                           int64_t n, int64_t h_count, int64_t batch, const double* K, double thr, double min_extra, int aggregation,
+                           int32_t* S, double* model, int32_t* flags, int32_t* cnt, double* s1, double* s2,
+                           sfm_select_result* result, uint8_t* mask, void* stream) {
+    return pass_entry("sfm_pnp_ransac_pass_ex", solver, seed, seed_stride, use_philox, h_begin, pts, n, h_count, batch, K, thr,
+                      min_extra, aggregation, S, model, flags, cnt, s1, s2, result, mask, stream);
 }

@@ -6,7 +6,8 @@
 // select_best, inlier_mask, cheirality, triangulate — each in a functional form (allocates its outputs; has a Meta
 // kernel, so fake-tensor tracing / torch.compile / opcheck work) and, where the engine pre-allocates its buffers
 // (device.RansacWorkspace), an in-place `_`-suffixed form with mutable arguments, plus the fused
-// sample_fit_philox_; and the PnP ops (sfm_pnp.hip) pnp_fit, pnp_score and the whole pass pnp_ransac_pass_, and the
+// sample_fit_philox_; and the PnP ops (sfm_pnp.hip) pnp_fit, pnp_score and the whole pass pnp_ransac_pass_, their P3P
+// forms p3p_fit and p3p_ransac_pass_ (sfm_p3p.h), and the
 // refinement of a winner pnp_refine (sfm_pnp_refine.hip), bundle_adjust (sfm_bundle.hip) and triangulate_tracks
 // (sfm_tracks.hip).  The reference call sites these serve: apps/sfm.py:110-119 (RANSAC-E), :133-138 (pose),
 // :181-186 (triangulation).
@@ -415,6 +416,37 @@ void check_model(const Tensor& model, const Dims& d) {
                 "sfm_hip: model must be [batch, h, 12]");
 }
 
+void fit_checks(const Tensor& pts, const Tensor& S, at::ArrayRef<double> K, Tensor& model, Tensor& flags);
+
+// P3P fit (four-item samples, sfm_p3p.h): the same tensors as pnp_fit
+void p3p_fit_out(const Tensor& pts, const Tensor& S, at::ArrayRef<double> K, Tensor& model, Tensor& flags) {
+    const OpDevice scope(pts);
+    fit_checks(pts, S, K, model, flags);
+    const Dims d = pnp_dims(pts, S);
+    ok(sfm_p3p_fit(ptr<double>(pts), d.n, ptr<int32_t>(S), d.h, d.batch, K.data(), ptr<double>(model), ptr<int32_t>(flags),
+                   current_stream()),
+       "sfm_p3p_fit");
+}
+
+std::tuple<Tensor, Tensor> p3p_fit(const Tensor& pts, const Tensor& S, at::ArrayRef<double> K) {
+    const Dims d = pnp_dims(pts, S);
+    Tensor model = at::empty({d.batch, d.h, 12}, like(pts, at::kDouble));
+    Tensor flags = at::empty({d.batch, d.h}, like(pts, at::kInt));
+    p3p_fit_out(pts, S, K, model, flags);
+    return {model, flags};
+}
+
+void fit_checks(const Tensor& pts, const Tensor& S, at::ArrayRef<double> K, Tensor& model, Tensor& flags) {
+    need(pts, "pts", at::kDouble);
+    need(S, "S", at::kInt);
+    need(model, "model", at::kDouble);
+    need(flags, "flags", at::kInt);
+    check_K(K);
+    const Dims d = pnp_dims(pts, S);
+    check_model(model, d);
+    TORCH_CHECK(flags.numel() == d.batch * d.h, "sfm_hip: flags must be [batch, h]");
+}
+
 void pnp_fit_out(const Tensor& pts, const Tensor& S, at::ArrayRef<double> K, Tensor& model, Tensor& flags) {
     const OpDevice scope(pts);
     need(pts, "pts", at::kDouble);
@@ -479,6 +511,44 @@ std::tuple<Tensor, Tensor, Tensor> pnp_score_meta(const Tensor& pts, const Tenso
     return {at::empty_symint({pts.sym_size(0), S.sym_size(1)}, like(pts, at::kInt)),
             at::empty_symint({pts.sym_size(0), S.sym_size(1)}, like(pts, at::kDouble)),
             at::empty_symint({pts.sym_size(0), S.sym_size(1)}, like(pts, at::kDouble))};
+}
+
+void pass_checks(const Tensor& pts, Tensor& S, Tensor& model, Tensor& flags, Tensor& cnt, Tensor& s1, Tensor& s2, Tensor& result,
+                 const std::optional<Tensor>& mask, at::ArrayRef<double> K);
+
+// the whole P3P pass (sfm_pnp_ransac_pass_ex with SFM_PNP_SOLVER_P3P): the arguments of pnp_ransac_pass_
+void p3p_ransac_pass_out(const Tensor& pts, int64_t seed, int64_t seed_stride, bool use_philox, int64_t h_begin,
+                         at::ArrayRef<double> K, double thr, double min_extra, int64_t aggregation, Tensor& S, Tensor& model,
+                         Tensor& flags, Tensor& cnt, Tensor& s1, Tensor& s2, Tensor& result, const std::optional<Tensor>& mask) {
+    const OpDevice scope(pts);
+    pass_checks(pts, S, model, flags, cnt, s1, s2, result, mask, K);
+    const Dims d = pnp_dims(pts, S);
+    ok(sfm_pnp_ransac_pass_ex(SFM_PNP_SOLVER_P3P, (uint64_t)seed, (uint64_t)seed_stride, use_philox ? 1 : 0, h_begin, ptr<double>(pts),
+                              d.n, d.h, d.batch, K.data(), thr, min_extra, (int)aggregation, ptr<int32_t>(S), ptr<double>(model),
+                              ptr<int32_t>(flags), ptr<int32_t>(cnt), ptr<double>(s1), ptr<double>(s2),
+                              reinterpret_cast<sfm_select_result*>(ptr<int64_t>(result)), ptr<uint8_t>(mask), current_stream()),
+       "sfm_pnp_ransac_pass_ex");
+}
+
+void pass_checks(const Tensor& pts, Tensor& S, Tensor& model, Tensor& flags, Tensor& cnt, Tensor& s1, Tensor& s2, Tensor& result,
+                 const std::optional<Tensor>& mask, at::ArrayRef<double> K) {
+    need(pts, "pts", at::kDouble);
+    need(S, "S", at::kInt);
+    need(model, "model", at::kDouble);
+    need(flags, "flags", at::kInt);
+    need(cnt, "cnt", at::kInt);
+    need(s1, "s1", at::kDouble);
+    need(s2, "s2", at::kDouble);
+    need(result, "result", at::kLong);
+    if (mask.has_value()) need(*mask, "mask", at::kByte);
+    check_K(K);
+    const Dims d = pnp_dims(pts, S);
+    check_model(model, d);
+    TORCH_CHECK(flags.numel() == d.batch * d.h && cnt.numel() == d.batch * d.h && s1.numel() == d.batch * d.h &&
+                    s2.numel() == d.batch * d.h,
+                "sfm_hip: flags, cnt, s1, s2 must be [batch, h]");
+    TORCH_CHECK(result.numel() == d.batch * kRecordWords, "sfm_hip: result must be int64 [batch, 5]");
+    TORCH_CHECK(!mask.has_value() || mask->numel() == d.batch * d.n, "sfm_hip: mask must be uint8 [batch, n]");
 }
 
 // the whole pass into the caller's buffers (device.PnPWorkspace); `mask` optional
@@ -803,10 +873,15 @@ TORCH_LIBRARY(sfm_hip, m) {
     m.def("triangulate(Tensor corr, Tensor P1, Tensor P2) -> Tensor");
     m.def("pnp_fit(Tensor pts, Tensor S, float[] K) -> (Tensor, Tensor)");
     m.def("pnp_fit_(Tensor pts, Tensor S, float[] K, Tensor(a!) model, Tensor(b!) flags) -> ()");
+    m.def("p3p_fit(Tensor pts, Tensor S, float[] K) -> (Tensor, Tensor)");
+    m.def("p3p_fit_(Tensor pts, Tensor S, float[] K, Tensor(a!) model, Tensor(b!) flags) -> ()");
     m.def("pnp_score(Tensor pts, Tensor model, Tensor S, float[] K, float thr) -> (Tensor, Tensor, Tensor)");
     m.def("pnp_score_(Tensor pts, Tensor model, Tensor S, float[] K, float thr, Tensor(a!) cnt, Tensor(b!) s1, "
           "Tensor(c!) s2) -> ()");
     m.def("pnp_ransac_pass_(Tensor pts, int seed, int seed_stride, bool use_philox, int h_begin, float[] K, float thr, "
+          "float min_extra, int aggregation, Tensor(a!) S, Tensor(b!) model, Tensor(c!) flags, Tensor(d!) cnt, Tensor(e!) s1, "
+          "Tensor(f!) s2, Tensor(g!) result, Tensor(h!)? mask) -> ()");
+    m.def("p3p_ransac_pass_(Tensor pts, int seed, int seed_stride, bool use_philox, int h_begin, float[] K, float thr, "
           "float min_extra, int aggregation, Tensor(a!) S, Tensor(b!) model, Tensor(c!) flags, Tensor(d!) cnt, Tensor(e!) s1, "
           "Tensor(f!) s2, Tensor(g!) result, Tensor(h!)? mask) -> ()");
     m.def("pnp_refine(Tensor pts, Tensor model, Tensor mask, Tensor err, float[] K, float thr, int aggregation, int rounds, "
@@ -851,6 +926,9 @@ TORCH_LIBRARY_IMPL(sfm_hip, CUDA, m) {
     m.impl("pnp_score", &pnp_score);
     m.impl("pnp_score_", &pnp_score_out);
     m.impl("pnp_ransac_pass_", &pnp_ransac_pass_out);
+    m.impl("p3p_fit", &p3p_fit);
+    m.impl("p3p_fit_", &p3p_fit_out);
+    m.impl("p3p_ransac_pass_", &p3p_ransac_pass_out);
     m.impl("pnp_refine", &pnp_refine);
     m.impl("pnp_refine_", &pnp_refine_out);
     m.impl("bundle_adjust", &bundle_adjust);
@@ -911,6 +989,9 @@ TORCH_LIBRARY_IMPL(sfm_hip, Meta, m) {
     m.impl("pnp_fit_", &pnp_fit_out_meta);
     m.impl("pnp_score_", &pnp_score_out_meta);
     m.impl("pnp_ransac_pass_", &pnp_ransac_pass_out_meta);
+    m.impl("p3p_fit", &pnp_fit_meta);
+    m.impl("p3p_fit_", &pnp_fit_out_meta);
+    m.impl("p3p_ransac_pass_", &pnp_ransac_pass_out_meta);
     m.impl("pnp_refine", &pnp_refine_meta);
     m.impl("pnp_refine_", &pnp_refine_out_meta);
     m.impl("bundle_adjust", &bundle_adjust_meta);

@@ -637,8 +637,41 @@ def pnp_fit(pts: torch.Tensor, S: torch.Tensor, K, model=None, flags=None):
     return model, flags
 
 
-def pnp_score(pts: torch.Tensor, model: torch.Tensor, S: torch.Tensor, K, thr: float, cnt=None, s1=None, s2=None):
-    """Per hypothesis (extra-inlier count, sum e, sum e^2) of the squared reprojection error e."""
+def p3p_fit(pts: torch.Tensor, S: torch.Tensor, K, model=None, flags=None):
+    """P3P fit of every hypothesis from the first four entries of each row of S -> model [B,H,12] (12 NaNs: no solution),
+    flags [B,H] (SFM_FIT_DEGENERATE: collinear solve points or an index out of range)."""
+    op = ops.load()
+    if model is None and flags is None:
+        return op.p3p_fit(pts, S, _camera_list(K))
+    B, H = S.shape[0], S.shape[1]
+    if model is None:
+        model = torch.empty((B, H, 12), dtype=F64, device=pts.device)
+    if flags is None:
+        flags = torch.empty((B, H), dtype=torch.int32, device=pts.device)
+    op.p3p_fit_(pts, S, _camera_list(K), model, flags)
+    return model, flags
+
+
+def _pnp_camera(K):
+    Kc = (C.c_double * 9)(*_camera_list(K))
+    return Kc, C.cast(Kc, C.c_void_p)
+
+
+def pnp_score(pts: torch.Tensor, model: torch.Tensor, S: torch.Tensor, K, thr: float, cnt=None, s1=None, s2=None,
+              sample_size: int = 6):
+    """Per hypothesis (extra-inlier count, sum e, sum e^2) of the squared reprojection error e; the first ``sample_size``
+    (6 or 4) entries of each row of S are the sample."""
+    if sample_size != 6:
+        B, N, _ = pts.shape
+        H = S.shape[1]
+        if cnt is None:
+            cnt = torch.empty((B, H), dtype=torch.int32, device=pts.device)
+            s1 = torch.empty((B, H), dtype=F64, device=pts.device)
+            s2 = torch.empty((B, H), dtype=F64, device=pts.device)
+        Kc, Kp = _pnp_camera(K)
+        check(_native.load().sfm_pnp_score_ex(_ptr(pts), N, _ptr(model), _ptr(S), H, B, Kp, float(thr), int(sample_size),
+                                              _ptr(cnt), _ptr(s1), _ptr(s2), _stream()), "sfm_pnp_score_ex")
+        return cnt, s1, s2
     op = ops.load()
     if cnt is None and s1 is None and s2 is None:
         return op.pnp_score(pts, model, S, _camera_list(K), float(thr))
@@ -646,23 +679,34 @@ def pnp_score(pts: torch.Tensor, model: torch.Tensor, S: torch.Tensor, K, thr: f
     return cnt, s1, s2
 
 
-def pnp_select_best(cnt, s1, s2, flags, min_extra: float, aggregation: int, h_offset: int = 0, out=None):
-    """sfm_pnp_select_best (six-item samples in the mean) -> int64 tensor [B,5] viewing sfm_select_result records."""
+def pnp_select_best(cnt, s1, s2, flags, min_extra: float, aggregation: int, h_offset: int = 0, out=None, sample_size: int = 6):
+    """sfm_pnp_select_best (``sample_size``-item samples in the mean, 6 or 4) -> int64 tensor [B,5] viewing sfm_select_result
+    records."""
     lib = _native.load()
     B, H = cnt.shape
     if out is None:
         out = torch.empty((B, SELECT_BYTES // 8), dtype=torch.int64, device=cnt.device)
+    if sample_size != 6:
+        check(lib.sfm_pnp_select_best_ex(_ptr(cnt), _ptr(s1), _ptr(s2), _ptr(flags), H, B, float(min_extra), int(aggregation),
+                                         h_offset, int(sample_size), _ptr(out), _stream()), "sfm_pnp_select_best_ex")
+        return out
     check(lib.sfm_pnp_select_best(_ptr(cnt), _ptr(s1), _ptr(s2), _ptr(flags), H, B, float(min_extra), int(aggregation),
                                   h_offset, _ptr(out), _stream()), "sfm_pnp_select_best")
     return out
 
 
-def pnp_inlier_mask(pts, model, S, K, result, thr: float, out=None):
-    """uint8 [B,N]: 2 sample point of the winner, 1 other inlier, 0 outlier."""
+def pnp_inlier_mask(pts, model, S, K, result, thr: float, out=None, sample_size: int = 6):
+    """uint8 [B,N]: 2 sample point of the winner (the first ``sample_size`` entries of its row of S), 1 other inlier,
+    0 outlier."""
     lib = _native.load()
     B, N, _ = pts.shape
     if out is None:
         out = torch.empty((B, N), dtype=torch.uint8, device=pts.device)
+    if sample_size != 6:
+        Kc, Kp = _pnp_camera(K)
+        check(lib.sfm_pnp_inlier_mask_ex(_ptr(pts), N, _ptr(model), _ptr(S), S.shape[1], B, Kp, _ptr(result), float(thr),
+                                         int(sample_size), _ptr(out), _stream()), "sfm_pnp_inlier_mask_ex")
+        return out
     Kc = (C.c_double * 9)(*_camera_list(K))
     check(lib.sfm_pnp_inlier_mask(_ptr(pts), N, _ptr(model), _ptr(S), S.shape[1], B, C.cast(Kc, C.c_void_p), _ptr(result),
                                   float(thr), _ptr(out), _stream()), "sfm_pnp_inlier_mask")
@@ -802,13 +846,16 @@ def read_tracks_info(info: torch.Tensor) -> TracksInfo:
     return TracksInfo(int(raw[0]), int(raw[1]), int(raw[2]))
 
 
+PNP_SAMPLE_SIZE = {"dlt": 6, "p3p": 4}   # sample size of each PnP solver (PnPWorkspace.run)
+
+
 @dataclass
 class PnPOutcome:
     best_h: int                # winning hypothesis, -1 if none
     error: float               # aggregated inlier error of the winner
     R: Optional[np.ndarray]    # (3,3) of the winner
     t: Optional[np.ndarray]    # (3,)
-    sample: Optional[np.ndarray]   # (6,) indices of the winner's sample, in sample order
+    sample: Optional[np.ndarray]   # (6,) indices of the winner's sample, in sample order ((4,) for P3P)
     mask: Optional[np.ndarray]     # (N,) uint8: 1 survivor, 2 sample point, 0 outlier
     n_flagged: int             # hypotheses whose sample was degenerate
     first_flagged: int         # lowest such hypothesis index, or -1
@@ -829,24 +876,41 @@ class PnPWorkspace:
         self.s2 = torch.empty((batch, h), dtype=F64, device=dev)
         self.result = torch.empty((batch, SELECT_BYTES // 8), dtype=torch.int64, device=dev)
         self.mask = torch.empty((batch, n), dtype=torch.uint8, device=dev)
+        self.sample_size = PNP_SAMPLE_SIZE["dlt"]
 
     def run(self, pts: torch.Tensor, K, thr: float, min_extra: float, aggregation: int, with_mask: bool = True,
-            philox=None) -> None:
+            philox=None, solver: str = "dlt") -> None:
         """fit + score + select (+ mask) in one call (``sfm_pnp_ransac_pass``) for the sample table in ``self.S`` — or, with
-        ``philox=(seed, h_begin, seed_stride)``, for Philox samples drawn inside the fit launch (which also fills ``self.S``)."""
+        ``philox=(seed, h_begin, seed_stride)``, for Philox samples drawn inside the fit launch (which also fills ``self.S``).
+        ``solver="p3p"``: the P3P fit on four-item samples (``sfm_pnp_ransac_pass_ex``); ``outcome`` and ``refine`` then
+        read this pass."""
+        if solver not in PNP_SAMPLE_SIZE:
+            raise ValueError(f"unknown PnP solver {solver!r}: expected one of {sorted(PNP_SAMPLE_SIZE)}")
+        self.sample_size = PNP_SAMPLE_SIZE[solver]
         seed, h_begin, stride = (0, 0, 1) if philox is None else philox
-        ops.load().pnp_ransac_pass_(pts, _as_int64(seed), _as_int64(stride), philox is not None, h_begin, _camera_list(K),
-                                    float(thr), float(min_extra), int(aggregation), self.S, self.model, self.flags, self.cnt,
-                                    self.s1, self.s2, self.result, self.mask if with_mask else None)
+        op = ops.load()
+        run_pass = op.p3p_ransac_pass_ if solver == "p3p" else op.pnp_ransac_pass_
+        run_pass(pts, _as_int64(seed), _as_int64(stride), philox is not None, h_begin, _camera_list(K), float(thr),
+                 float(min_extra), int(aggregation), self.S, self.model, self.flags, self.cnt, self.s1, self.s2, self.result,
+                 self.mask if with_mask else None)
 
     def refine(self, pts: torch.Tensor, K, thr: float, aggregation: int, rounds: int = 1, max_steps: int = 20):
         """``pnp_refine`` of every view's winner, chained on this pass's buffers: model[b, best_h] (row 0 when a view has no
         winner: its mask is all zero and it keeps that row), the pass's mask and the record's best_err.  Stream-ordered
-        after ``run``: no host round trip.  -> (model_out [B,12], mask_out [B,N], info [B,3])."""
+        after ``run``: no host round trip.  -> (model_out [B,12], mask_out [B,N], info [B,3]).
+
+        After a P3P pass the winner's sample item 3 does not seed the refinement: P3P reproduces items 0-2 exactly, while
+        item 3 only picked the solution and can be an outlier of a good pose, which would then dominate the least squares.
+        The re-score of every item counts it again if it fits."""
+        rows = torch.arange(self.batch, device=self.result.device)
         best_h = self.result[:, 1].clamp(min=0)
-        model = self.model[torch.arange(self.batch, device=best_h.device), best_h]
+        model = self.model[rows, best_h]
         err = self.result[:, 2].contiguous().view(F64)
-        return pnp_refine(pts, model, self.mask, err, K, thr, aggregation, rounds, max_steps)
+        mask = self.mask
+        if self.sample_size == PNP_SAMPLE_SIZE["p3p"]:
+            mask = mask.clone()
+            mask[rows, self.S[rows, best_h, 3].long().clamp(min=0)] = 0
+        return pnp_refine(pts, model, mask, err, K, thr, aggregation, rounds, max_steps)
 
     def outcome(self, b: int = 0) -> PnPOutcome:
         rec = read_select(self.result)[b]
@@ -855,7 +919,7 @@ class PnPWorkspace:
             return PnPOutcome(-1, float("inf"), None, None, None, None, int(rec.n_flagged), first, 0)
         h = int(rec.best_h)
         m = self.model[b, h].cpu().numpy()
-        sample = self.S[b, h, :6].cpu().numpy().astype(np.int64)
+        sample = self.S[b, h, :self.sample_size].cpu().numpy().astype(np.int64)
         mask = checked_mask(self.mask[b].cpu().numpy().copy())
         return PnPOutcome(h, float(rec.best_err), m[:9].reshape(3, 3).copy(), m[9:].copy(), sample, mask,
                           int(rec.n_flagged), first, int(rec.best_cnt))

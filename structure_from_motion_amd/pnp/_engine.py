@@ -25,7 +25,8 @@ def item_array(data) -> np.ndarray:
     return out
 
 
-def ransac_pnp_items(data, camera_matrix, threshold, min_extra, aggregation, iterations, refine_rounds=0, refine_steps=20):
+def ransac_pnp_items(data, camera_matrix, threshold, min_extra, aggregation, iterations, refine_rounds=0, refine_steps=20,
+                     solver="dlt"):
     """Returns ((R, t) or None, inlier items) with the semantics of ransac._host_loop: sample ``pyshuffle`` (default) replays
     the reference's cumulative ``random.shuffle`` and advances the global ``random`` state; ``philox`` draws on the device
     (seed ``SFM_SEED`` or 64 bits of ``random``).  Inliers come back as deep copies, the sample first, then the survivors
@@ -33,14 +34,20 @@ def ransac_pnp_items(data, camera_matrix, threshold, min_extra, aggregation, ite
 
     ``refine_rounds > 0`` refines the winner on its inliers right after the pass, on the pass's own buffers
     (``PnPWorkspace.refine``).  When a round is kept, the pose is the refined one and the inliers are the items with
-    e <= threshold under it, in index order; otherwise the return value is the unrefined one."""
-    from .pnp import SAMPLE_SIZE, PnPCalculationError, check_camera_matrix
+    e <= threshold under it, in index order; otherwise the return value is the unrefined one.
 
+    ``solver`` is ``"dlt"`` (six-item samples) or ``"p3p"`` (four-item samples: ``PyShuffleTable.S[:, :4]``, the first four
+    of ``philox_sample8``); the sample size sets the minimum n, the sample the inliers start with and the degenerate error."""
+    from .pnp import SOLVERS, PnPCalculationError, check_camera_matrix
+
+    if solver not in SOLVERS:
+        raise ValueError(f"unknown PnP solver {solver!r}: expected one of {sorted(SOLVERS)}")
+    sample_size = SOLVERS[solver]
     n = len(data)
     if iterations <= 0:
         return None, []
-    if n < SAMPLE_SIZE:
-        raise ValueError("Six 2D-3D pairs are expected.")
+    if n < sample_size:
+        raise ValueError(f"{'Six' if sample_size == 6 else 'Four'} 2D-3D pairs are expected.")
     K = check_camera_matrix(camera_matrix)
     dev = device.require_gpu()
     pts = device.to_device(item_array(data)).reshape(1, n, 5)
@@ -50,16 +57,17 @@ def ransac_pnp_items(data, camera_matrix, threshold, min_extra, aggregation, ite
     if sampler == "pyshuffle":
         table = device.PyShuffleTable(n, iterations, random, advance=True)
         ws.S.copy_(device.to_device(table.S, dtype=ws.S.dtype).reshape(1, iterations, 8))
-        ws.run(pts, K, threshold, min_extra, aggregation)
+        ws.run(pts, K, threshold, min_extra, aggregation, solver=solver)
     else:
         seed = int(os.environ["SFM_SEED"]) if "SFM_SEED" in os.environ else random.getrandbits(64)
-        ws.run(pts, K, threshold, min_extra, aggregation, philox=(seed, 0, 1))
+        ws.run(pts, K, threshold, min_extra, aggregation, philox=(seed, 0, 1), solver=solver)
     refined = ws.refine(pts, K, threshold, aggregation, refine_rounds, refine_steps) if refine_rounds > 0 else None
     outcome = ws.outcome(0)
     if outcome.n_flagged and degenerate_policy() == "raise":
+        what = ("The six 3-D points of a sample are coplanar or collinear" if solver == "dlt" else
+                "The three 3-D points a P3P sample solves for are collinear")
         raise PnPCalculationError(
-            "The six 3-D points of a sample are coplanar or collinear: cannot estimate the pose."
-            f" (hypothesis {outcome.first_flagged}, {outcome.n_flagged} in total)")
+            f"{what}: cannot estimate the pose. (hypothesis {outcome.first_flagged}, {outcome.n_flagged} in total)")
     if logger.isEnabledFor(logging.DEBUG):
         logger.debug("RANSAC-PnP: %d pairs x %d hypotheses (%s sampler): best hypothesis %d, %d extra inliers, "
                      "aggregated error %.6g, %d degenerate sample(s)", n, iterations, sampler, outcome.best_h,
@@ -75,8 +83,8 @@ def ransac_pnp_items(data, camera_matrix, threshold, min_extra, aggregation, ite
     survivors = outcome.mask == 1
     if sampler == "pyshuffle":
         perm = table.permutation_after(outcome.best_h)
-        rest = perm[SAMPLE_SIZE:]
-        order = np.concatenate([perm[:SAMPLE_SIZE], rest[survivors[rest]]])
+        rest = perm[sample_size:]
+        order = np.concatenate([perm[:sample_size], rest[survivors[rest]]])
     else:
         order = np.concatenate([outcome.sample, np.nonzero(survivors)[0]])
     return (outcome.R, outcome.t), [copy.deepcopy(data[i]) for i in order.tolist()]

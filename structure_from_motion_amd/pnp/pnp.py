@@ -3,9 +3,9 @@
 Data items are ``(X, f)`` pairs: ``X`` a 3-D point (length-3 float array) in the frame of camera 1, ``f`` the ``Feature`` of
 its match in the new image, in pixels.  The model is ``(R, t)`` with ``x_cam = R X + t`` — the convention of
 ``recover_r_t_from_e`` and ``Transform3D.from_rmat_t``.  The RANSAC contract is the reference's ``fit_with_ransac``
-(``lib/ransac/ransac.py``) with a six-item sample: ``estimate_pose_pnp_with_ransac`` passes the tagged fitter / scorer
-below, which ``fit_with_ransac`` routes to the HIP kernels of ``csrc/sfm_pnp.hip``; the same call with untagged callables
-runs on the host.
+(``lib/ransac/ransac.py``) with a six-item sample (the DLT) or a four-item one (P3P, ``solver="p3p"``):
+``estimate_pose_pnp_with_ransac`` passes the tagged fitter / scorer below, which ``fit_with_ransac`` routes to the HIP
+kernels of ``csrc/sfm_pnp.hip``; the same call with untagged callables runs on the host.
 """
 from __future__ import annotations
 
@@ -19,6 +19,7 @@ from ..common.feature import Feature
 from ..epipolar import _engine
 from ..feature_matching.matching import Match
 from ..ransac.ransac import DEFAULT_MAX_ITERATIONS, ErrorAggregationMethod, aggregation_code, fit_with_ransac
+from . import p3p
 
 PnPItem = Tuple[npt.NDArray, Feature]
 PnPModel = Tuple[npt.NDArray, npt.NDArray]
@@ -96,8 +97,45 @@ def calculate_reprojection_score(model: PnPModel, item: PnPItem, camera_matrix: 
     return du * du + dv * dv
 
 
-# fit_with_ransac recognises partials of these two (with model_fit_data_count == 6) and runs the whole loop on the GPU.
+P3P_SAMPLE_SIZE = 4
+SOLVERS = {"dlt": SAMPLE_SIZE, "p3p": P3P_SAMPLE_SIZE}
+
+
+def p3p_candidates(items: Sequence[PnPItem], camera_matrix: npt.NDArray) -> list:
+    """Every candidate (R, t) of the P3P solve on items 0-2, in the solver's fixed order (``pnp/p3p.py``); [] for a
+    collinear triple."""
+    K = np.asarray(camera_matrix, dtype=np.float64).tolist()
+    X = [[float(v) for v in np.asarray(item[0], dtype=np.float64).reshape(3)] for item in items[:3]]
+    if p3p.collinear(*X):
+        return []
+    f = [p3p.bearing(float(item[1].x), float(item[1].y), K) for item in items[:3]]
+    return [(np.array(R), np.array(t)) for R, t in p3p.p3p_solve(X, f)]
+
+
+def p3p_model_fitter(items: Sequence[PnPItem], camera_matrix: npt.NDArray) -> PnPModel:
+    """(R, t) from exactly four 2D-3D pairs by P3P (the RANSAC model fitter of ``solver="p3p"``; host form of
+    ``sfm_p3p_fit``).  Items 0-2 are solved for (up to four candidates, ``p3p_candidates``); item 3 picks the candidate with
+    the strictly lowest ``calculate_reprojection_score``, the earliest on ties.  When no candidate scores below +inf the
+    sample has no solution and the model is (R, t) of NaNs, which never becomes an inlier nor wins.  Raises
+    PnPCalculationError when the three solve points are collinear or coincide (coplanar samples are not degenerate)."""
+    if len(items) != P3P_SAMPLE_SIZE:
+        raise ValueError("Four 2D-3D pairs are expected.")
+    K = np.asarray(camera_matrix, dtype=np.float64)
+    X = [[float(v) for v in np.asarray(item[0], dtype=np.float64).reshape(3)] for item in items[:3]]
+    if p3p.collinear(*X):
+        raise PnPCalculationError("The three 3-D points of the sample are collinear: cannot estimate the pose.")
+    best, best_e = (np.full((3, 3), np.nan), np.full(3, np.nan)), float("inf")
+    for R, t in p3p_candidates(items, K):
+        e = calculate_reprojection_score((R, t), items[3], K)
+        if e < best_e:
+            best, best_e = (R, t), e
+    return best
+
+
+# fit_with_ransac recognises partials of these (with model_fit_data_count 6 for the DLT, 4 for P3P) and runs the whole loop
+# on the GPU.
 pnp_model_fitter._sfm_hip_role = "pnp_fitter"
+p3p_model_fitter._sfm_hip_role = "p3p_fitter"
 calculate_reprojection_score._sfm_hip_role = "reprojection_scorer"
 
 
@@ -111,8 +149,10 @@ def estimate_pose_pnp_with_ransac(
     error_aggregation_method: ErrorAggregationMethod | None = None,
     max_iterations: int | None = None,
     refine_rounds: int = 0,
+    solver: str = "dlt",
 ) -> Tuple[npt.NDArray, npt.NDArray, list]:
-    """Pose (R, t) of a further view from 2D-3D matches with RANSAC over six-point DLT hypotheses.
+    """Pose (R, t) of a further view from 2D-3D matches with RANSAC over six-point DLT hypotheses (``solver="dlt"``, the
+    default) or P3P hypotheses on four-item samples (``solver="p3p"``, ``p3p_model_fitter``).
 
     ``matches[i].a_index`` indexes ``points_3d`` and ``b_index`` indexes ``features`` (pixels of the new view).  A pair is an
     inlier when its squared reprojection error is at most ``reprojection_threshold`` (pixels squared).  Returns
@@ -123,20 +163,31 @@ def estimate_pose_pnp_with_ransac(
     ``refine_rounds > 0`` refines the RANSAC winner on its inliers on the device, right after the pass (see
     ``refine_pose_pnp``, at most 20 Levenberg-Marquardt steps per round).  If no round is kept the result is exactly the
     unrefined one; otherwise the inliers are the pairs with an error of at most the threshold under the refined pose, in
-    match order.  0 (the default) runs the unrefined path unchanged."""
+    match order.  0 (the default) runs the unrefined path unchanged.
+
+    P3P needs at least four matches and handles planar scenes, which the DLT flags as degenerate.  Its samples without a
+    real solution are not errors: they never win.  Only a sample whose three solve points are collinear is degenerate
+    (``PnPCalculationError`` under the default policy).  An unknown ``solver`` raises ``ValueError`` before any device
+    work."""
     K = check_camera_matrix(camera_matrix)
-    if len(matches) < SAMPLE_SIZE:
-        raise ValueError(f"At least six 2D-3D matches are expected, got {len(matches)}.")
+    if solver not in SOLVERS:
+        raise ValueError(f"unknown PnP solver {solver!r}: expected one of {sorted(SOLVERS)}")
+    sample_size = SOLVERS[solver]
+    if len(matches) < sample_size:
+        if solver == "dlt":
+            raise ValueError(f"At least six 2D-3D matches are expected, got {len(matches)}.")
+        raise ValueError(f"At least four 2D-3D matches are expected for solver 'p3p', got {len(matches)}.")
     refine_rounds = _non_negative(refine_rounds, "refine_rounds")
     if refine_rounds > 0:
         return _ransac_refined(K, points_3d, features, matches, reprojection_threshold, min_num_extra_inliers,
-                               error_aggregation_method, max_iterations, refine_rounds)
+                               error_aggregation_method, max_iterations, refine_rounds, solver)
+    fitter = pnp_model_fitter if solver == "dlt" else p3p_model_fitter
     with _engine.gc_paused():
         items = [(np.asarray(points_3d[m.a_index], dtype=np.float64).reshape(3), features[m.b_index]) for m in matches]
         model, inliers = fit_with_ransac(
             items,
-            model_fit_data_count=SAMPLE_SIZE,
-            model_fitter=partial(pnp_model_fitter, camera_matrix=K),
+            model_fit_data_count=sample_size,
+            model_fitter=partial(fitter, camera_matrix=K),
             inlier_scorer=partial(calculate_reprojection_score, camera_matrix=K),
             inlier_threshold=reprojection_threshold,
             min_num_extra_inliers=min_num_extra_inliers,
@@ -159,7 +210,7 @@ def _items(points_3d, features, matches):
     return [(np.asarray(points_3d[m.a_index], dtype=np.float64).reshape(3), features[m.b_index]) for m in matches]
 
 
-def _ransac_refined(K, points_3d, features, matches, threshold, min_extra, method, max_iterations, rounds):
+def _ransac_refined(K, points_3d, features, matches, threshold, min_extra, method, max_iterations, rounds, solver="dlt"):
     """The device route of fit_with_ransac (the one the tagged pair takes) with the refinement chained after the pass."""
     from . import _engine as pnp_engine
 
@@ -169,9 +220,9 @@ def _ransac_refined(K, points_3d, features, matches, threshold, min_extra, metho
     with _engine.gc_paused():
         items = _items(points_3d, features, matches)
         model, inliers = pnp_engine.ransac_pnp_items(items, K, threshold, min_extra, aggregation_code(method), iterations,
-                                                     refine_rounds=rounds)
+                                                     refine_rounds=rounds, solver=solver)
     if model is None:
-        raise ValueError(f"No model could be found with at least {min_extra + SAMPLE_SIZE} inliers.")
+        raise ValueError(f"No model could be found with at least {min_extra + SOLVERS[solver]} inliers.")
     R, t = model
     return R, t, inliers
 

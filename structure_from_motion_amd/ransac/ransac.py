@@ -6,7 +6,8 @@ Two execution routes behind one signature:
   ``epipolar_ransac`` (which is what ``estimate_essential_mat_with_ransac`` passes, exactly like the
   reference's ``epipolar_ransac.py:58-67``), the whole loop — fit, H x N scoring, gate, aggregation,
   selection — runs as HIP kernels on the MI355X (``device.RansacWorkspace``); likewise for the six-point PnP fitter
-  and reprojection scorer of ``pnp.pnp`` with ``model_fit_data_count == 6`` (``device.PnPWorkspace``);
+  and reprojection scorer of ``pnp.pnp`` with ``model_fit_data_count == 6``, and its P3P fitter with
+  ``model_fit_data_count == 4`` (``device.PnPWorkspace``);
 * for arbitrary Python callables (e.g. the 2-point line fitter of the reference's own
   ``test_ransac.py``) the loop is host logic: there is nothing to put on a GPU.
 
@@ -70,7 +71,7 @@ def fit_with_ransac(
         from ..pnp import _engine as pnp_engine
 
         model, inliers = pnp_engine.ransac_pnp_items(
-            data, spec.camera_matrix, inlier_threshold, min_extra, aggregation_code(method), iterations)
+            data, spec.camera_matrix, inlier_threshold, min_extra, aggregation_code(method), iterations, solver=spec.solver)
     elif spec is not None:
         from ..epipolar import _engine
 
@@ -87,26 +88,33 @@ def fit_with_ransac(
 
 
 class PnPDeviceSpec(NamedTuple):
-    """Device route of the six-point PnP fitter / reprojection scorer pair."""
+    """Device route of a PnP fitter (six-point DLT or P3P) / reprojection scorer pair."""
     camera_matrix: np.ndarray
+    solver: str = "dlt"
+
+
+# the tagged PnP fitters: role -> (solver, sample size)
+_PNP_FITTERS = {"pnp_fitter": ("dlt", 6), "p3p_fitter": ("p3p", 4)}
 
 
 def _device_spec(model_fitter, inlier_scorer, model_fit_data_count):
     """Camera matrix if (fitter, scorer) are partials of the eight-point / SED pair, a PnPDeviceSpec if they are partials
-    of the PnP fitter / reprojection scorer with a six-item sample (and one camera matrix), else None."""
+    of a PnP fitter / reprojection scorer with that fitter's sample size (six for the DLT, four for P3P) and one camera
+    matrix, else None."""
     fit_fn = getattr(model_fitter, "func", None)
     score_fn = getattr(inlier_scorer, "func", None)
     if fit_fn is None or score_fn is None:
         return None
-    if (getattr(fit_fn, "_sfm_hip_role", None) == "pnp_fitter"
+    if (getattr(fit_fn, "_sfm_hip_role", None) in _PNP_FITTERS
             and getattr(score_fn, "_sfm_hip_role", None) == "reprojection_scorer"):
-        if model_fit_data_count != 6:
+        solver, sample_size = _PNP_FITTERS[fit_fn._sfm_hip_role]
+        if model_fit_data_count != sample_size:
             return None
         k_fit = model_fitter.keywords.get("camera_matrix") if not model_fitter.args else None
         k_score = inlier_scorer.keywords.get("camera_matrix") if not inlier_scorer.args else None
         if k_fit is None or k_score is None or not np.array_equal(np.asarray(k_fit), np.asarray(k_score)):
             return None
-        return PnPDeviceSpec(np.asarray(k_fit, dtype=np.float64))
+        return PnPDeviceSpec(np.asarray(k_fit, dtype=np.float64), solver)
     if model_fit_data_count != 8:
         return None
     if not getattr(fit_fn, "_sfm_hip_role", None) == "eight_point_fitter":

@@ -169,3 +169,27 @@ def multi_view_scene(views: int = 8, points: int = 2000, seed: int = 21, noise_p
     pix = np.where(is_out[:, None], rand_px, pix)
     return dict(K=K, camera_indices=cam.astype(np.int32), point_indices=pt.astype(np.int32), pixels=pix, is_outlier=is_out,
                 poses_true=poses, points_true=X)
+
+
+def planar_pnp_scene(n: int, seed: int = 0, K: np.ndarray = BENCH_K, outlier_fraction: float = 0.3, noise_px: float = 0.5):
+    """A PnP input whose 3-D points all lie on one plane, z = 5 + 0.3 x (x, y uniform in [-1, 1]): a wall, a floor or a
+    calibration board, which the six-point DLT cannot register.  The view has a random pose (rotation of 0.05 to 0.4 rad
+    about a random axis, t uniform in [-0.5, 0.5]^3), Gaussian pixel noise, and a fraction of pixels replaced by uniform
+    random ones.  Returns (pts (n, 5) {X, Y, Z, u, v}, R, t, is_outlier)."""
+    rng = np.random.default_rng(seed)
+    a = rng.normal(size=3)
+    a *= rng.uniform(0.05, 0.4) / np.linalg.norm(a)
+    th = float(np.linalg.norm(a))
+    k = a / th
+    W = np.array([[0.0, -k[2], k[1]], [k[2], 0.0, -k[0]], [-k[1], k[0], 0.0]])
+    R = np.eye(3) + np.sin(th) * W + (1.0 - np.cos(th)) * (W @ W)
+    t = rng.uniform(-0.5, 0.5, 3)
+    x = rng.uniform(-1.0, 1.0, n)
+    y = rng.uniform(-1.0, 1.0, n)
+    X = np.column_stack([x, y, 5.0 + 0.3 * x])
+    uvw = (X @ R.T + t) @ K.T
+    uv = uvw[:, :2] / uvw[:, 2:3] + rng.normal(0.0, noise_px, (n, 2))
+    is_out = rng.random(n) < outlier_fraction
+    rand_px = np.column_stack([rng.uniform(0, 2 * K[0, 2], n), rng.uniform(0, 2 * K[1, 2], n)])
+    uv = np.where(is_out[:, None], rand_px, uv)
+    return np.column_stack([X, uv]), R, t, is_out
