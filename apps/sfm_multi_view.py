@@ -125,9 +125,11 @@ class Reconstruction:
 def run(views: int = 8, points: int = 2000, seed: int = 21, noise_px: float = 0.5, outlier_fraction: float = 0.2,
         sed_threshold: float = 6e-6, reprojection_threshold: float = 16.0, iterations: int = 2000, refine_steps: int = 10,
         ba_steps: int = 20, final_ba_steps: int = 50, step_deg: float = 5.0, bundle_solver: str = "dense",
-        details: bool = False, pnp_solver: str = "dlt") -> dict:
+        details: bool = False, pnp_solver: str = "dlt", e_solver: str = "eight_point") -> dict:
     if pnp_solver not in ("dlt", "p3p"):
         raise ValueError(f"pnp_solver must be 'dlt' or 'p3p', got {pnp_solver!r}")
+    if e_solver not in ("eight_point", "five_point"):
+        raise ValueError(f"e_solver must be 'eight_point' or 'five_point', got {e_solver!r}")
     if bundle_solver not in BUNDLE_SOLVERS:
         raise ValueError(f"bundle_solver must be one of {BUNDLE_SOLVERS}, got {bundle_solver!r}")
     limit = DENSE_MAX_VIEWS if bundle_solver == "dense" else MAX_VIEWS
@@ -151,12 +153,13 @@ def run(views: int = 8, points: int = 2000, seed: int = 21, noise_px: float = 0.
     # model fitted to a few outliers from winning (about 64 % of the pairs are clean at 20 % outliers per view)
     e, pairs = estimate_essential_mat_with_ransac(K, fa, fb, create_trivial_matches(len(both)),
                                                   sed_inlier_threshold=sed_threshold,
-                                                  min_num_extra_inliers=int(0.4 * len(both)), max_iterations=iterations)
+                                                  min_num_extra_inliers=int(0.4 * len(both)), max_iterations=iterations,
+                                                  solver=e_solver)
     R1, t1, _ = recover_r_t_from_e(e, K, [p[0] for p in pairs], [p[1] for p in pairs])
     rec.poses[0] = _pose(np.eye(3), np.zeros(3))
     rec.poses[1] = _pose(R1, t1)
     rec.registered = [0, 1]
-    # The RANSAC winner is an eight-point fit to one sample: with 5 degrees between the views its pose can be off by a few
+    # The RANSAC winner is a minimal fit to one sample: with 5 degrees between the views its pose can be off by a few
     # hundredths of a radian, enough to push most two-view points over the threshold.  So the pairs E keeps are triangulated
     # without the error check first and views 0-1 are adjusted on them; then every track is triangulated with the checks.
     index_of = {(f.x, f.y): k for k, f in enumerate(fa)}
@@ -244,13 +247,16 @@ def main():
                     help="dense: at most 64 views; auto: the iterative solver above 64 registered cameras")
     ap.add_argument("--pnp-solver", choices=("dlt", "p3p"), default="dlt",
                     help="minimal solver that registers each further view: six-point DLT or P3P on four-item samples")
+    ap.add_argument("--e-solver", choices=("eight_point", "five_point"), default="eight_point",
+                    help="minimal solver of the two-view seed: eight-point, or five-point on six-item samples")
     args = ap.parse_args()
     limit = DENSE_MAX_VIEWS if args.bundle_solver == "dense" else MAX_VIEWS
     if not 2 <= args.views <= limit:
         ap.error(f"--views must be between 2 and {limit} with --bundle-solver {args.bundle_solver}")
     print(json.dumps(run(args.views, args.points, args.seed, args.noise, args.outliers, sed_threshold=args.sed_threshold,
                          reprojection_threshold=args.reprojection_threshold, refine_steps=args.refine_steps,
-                         step_deg=args.step_deg, bundle_solver=args.bundle_solver, pnp_solver=args.pnp_solver)))
+                         step_deg=args.step_deg, bundle_solver=args.bundle_solver, pnp_solver=args.pnp_solver,
+                         e_solver=args.e_solver)))
 
 
 if __name__ == "__main__":

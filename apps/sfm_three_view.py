@@ -59,7 +59,7 @@ def rotation_angle(Ra: np.ndarray, Rb: np.ndarray) -> float:
 
 def run(n: int = 400, seed: int = 11, outlier_fraction: float = 0.3, noise_px: float = 0.0, sed_threshold: float = 1.5e-6,
         reprojection_threshold: float = 4.0, iterations: int = 2000, refine: int = 0, bundle_adjust: int = 0,
-        pnp_solver: str = "dlt") -> dict:
+        pnp_solver: str = "dlt", e_solver: str = "eight_point") -> dict:
     scene = three_view_scene(n, seed, outlier_fraction, noise_px)
     K = scene["K"]
     features_a = [Feature(float(x), float(y)) for x, y in scene["pa"]]
@@ -69,7 +69,7 @@ def run(n: int = 400, seed: int = 11, outlier_fraction: float = 0.3, noise_px: f
     # views 1-2: E, pose, triangulation of the cheirality survivors
     e, inlier_pairs = estimate_essential_mat_with_ransac(
         K, features_a, features_b, create_trivial_matches(n), sed_inlier_threshold=sed_threshold,
-        min_num_extra_inliers=10, max_iterations=iterations)
+        min_num_extra_inliers=10, max_iterations=iterations, solver=e_solver)
     R2, t2, mask = recover_r_t_from_e(e, K, [p[0] for p in inlier_pairs], [p[1] for p in inlier_pairs])
     kept = [inlier_pairs[i] for i in mask]
     points = triangulate_points([p[0] for p in kept], [p[1] for p in kept], K, Transform3D.from_rmat_t(R2, t2))
@@ -159,10 +159,13 @@ def main():
                          "errors before it")
     ap.add_argument("--pnp-solver", choices=("dlt", "p3p"), default="dlt",
                     help="minimal solver of the view-3 PnP: six-point DLT or P3P on four-item samples")
+    ap.add_argument("--e-solver", choices=("eight_point", "five_point"), default="eight_point",
+                    help="minimal solver of the views-1-2 essential matrix: eight-point, or five-point on six-item samples")
     args = ap.parse_args()
     print(json.dumps(run(args.points, args.seed, args.outliers, args.noise, sed_threshold=args.sed_threshold,
                          reprojection_threshold=args.reprojection_threshold, iterations=args.iterations,
-                         refine=args.refine, bundle_adjust=args.bundle_adjust, pnp_solver=args.pnp_solver)))
+                         refine=args.refine, bundle_adjust=args.bundle_adjust, pnp_solver=args.pnp_solver,
+                         e_solver=args.e_solver)))
 
 
 if __name__ == "__main__":

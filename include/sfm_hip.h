@@ -366,6 +366,40 @@ int sfm_pnp_ransac_pass_ex(int solver, uint64_t seed, uint64_t seed_stride, int 
                            int32_t* S, double* model, int32_t* flags, int32_t* cnt, double* s1, double* s2,
                            sfm_select_result* result, uint8_t* mask, void* stream);
 
+/* ---- five-point essential matrix (csrc/sfm_five_point.hip; an extension, off unless asked for) ----
+ * corr: dev [batch,n,4] K-normalised {xa, ya, xb, yb}; S: dev int32 [batch,h_count,8], the first 6 entries of a row are the
+ * sample: items 0-4 are solved for, item 5 picks the candidate with the smallest SED (strict <, the earlier root on ties).
+ * E: dev [batch,h_count,9], scaled to ||E||_F = sqrt(2) with its largest-magnitude entry positive (E[2,2] is not 1); 9 NaNs
+ * with flag 0 when the sample has no real solution.  flags: SFM_FIT_DEGENERATE when the 5 x 9 system of items 0-4 has
+ * numerical rank < 5 (collinear or repeated items), an input is not finite or an index is out of range.  n >= 6. */
+int sfm_five_point_fit(const double* corr, int64_t n, const int32_t* S, int64_t h_count, int64_t batch, double* E, int32_t* flags,
+                       void* stream);
+
+/* Philox sampling fused into the five-point fit (first 6 of philox_sample8, all 8 stored in S, -1 at positions >= n). */
+int sfm_five_point_sample_fit_philox(uint64_t seed, uint64_t seed_stride, int64_t h_begin, const double* corr, int64_t n,
+                                     int64_t h_count, int64_t batch, int32_t* S, double* E, int32_t* flags, void* stream);
+
+/* Every candidate of items 0-4 of each sample in ascending root order: out dev [batch,h_count,10,9] (NaN beyond the count),
+ * count dev int32 [batch,h_count] (-1 for a sample sfm_five_point_fit flags). */
+int sfm_five_point_candidates(const double* corr, int64_t n, const int32_t* S, int64_t h_count, int64_t batch, double* out,
+                              int32_t* count, void* stream);
+
+/* sfm_score_sed (all-fp64 kernel), sfm_select_best and sfm_inlier_mask for samples of sample_size items (6 or 8; SFM_EINVAL
+ * otherwise): the first sample_size entries of a row of S are the sample, the mean and RMS divide by count + sample_size. */
+int sfm_score_sed_sample_ex(const double* corr, int64_t n, const double* E, const int32_t* S, int64_t h_count, int64_t batch,
+                            double thr, int sample_size, int32_t* cnt, double* s1, double* s2, void* stream);
+int sfm_select_best_ex(const int32_t* cnt, const double* s1, const double* s2, const int32_t* flags, int64_t h_count, int64_t batch,
+                       double min_extra, int aggregation, int64_t h_offset, int sample_size, sfm_select_result* result, void* stream);
+int sfm_inlier_mask_ex(const double* corr, int64_t n, const double* E, const int32_t* S, int64_t h_count, int64_t batch,
+                       const sfm_select_result* result, double thr, int sample_size, uint8_t* mask, void* stream);
+
+/* One five-point pass: fit (from S, or Philox-sampled with use_philox), six-item scoring, selection and (mask != NULL) the
+ * winner's mask, as the separate calls above.  Every size is checked before the first launch. */
+int sfm_five_point_ransac_pass(uint64_t seed, uint64_t seed_stride, int use_philox, int64_t h_begin, const double* corr, int64_t n,
+                               int64_t h_count, int64_t batch, double thr, double min_extra, int aggregation, int32_t* S, double* E,
+                               int32_t* flags, int32_t* cnt, double* s1, double* s2, sfm_select_result* result, uint8_t* mask,
+                               void* stream);
+
 /* ---- refinement of a PnP winner on its inliers (csrc/sfm_pnp_refine.hip; an extension, off unless asked for) ---- */
 
 typedef struct sfm_pnp_refine_info {

@@ -167,6 +167,14 @@ SIGNATURES = {
     "sfm_pnp_score_ex": [_P, _I64, _P, _P, _I64, _I64, _P, _D, C.c_int, _P, _P, _P, _P],
     "sfm_pnp_select_best_ex": [_P, _P, _P, _P, _I64, _I64, _D, C.c_int, _I64, C.c_int, _P, _P],
     "sfm_pnp_inlier_mask_ex": [_P, _I64, _P, _P, _I64, _I64, _P, _P, _D, C.c_int, _P, _P],
+    "sfm_five_point_fit": [_P, _I64, _P, _I64, _I64, _P, _P, _P],
+    "sfm_five_point_sample_fit_philox": [_U64, _U64, _I64, _P, _I64, _I64, _I64, _P, _P, _P, _P],
+    "sfm_five_point_candidates": [_P, _I64, _P, _I64, _I64, _P, _P, _P],
+    "sfm_score_sed_sample_ex": [_P, _I64, _P, _P, _I64, _I64, _D, C.c_int, _P, _P, _P, _P],
+    "sfm_select_best_ex": [_P, _P, _P, _P, _I64, _I64, _D, C.c_int, _I64, C.c_int, _P, _P],
+    "sfm_inlier_mask_ex": [_P, _I64, _P, _P, _I64, _I64, _P, _D, C.c_int, _P, _P],
+    "sfm_five_point_ransac_pass": [_U64, _U64, C.c_int, _I64, _P, _I64, _I64, _I64, _D, _D, C.c_int, _P, _P, _P, _P, _P, _P,
+                                   _P, _P, _P],
     "sfm_pnp_ransac_pass_ex": [C.c_int, _U64, _U64, C.c_int, _I64, _P, _I64, _I64, _I64, _P, _D, _D, C.c_int, _P, _P, _P, _P, _P,
                                _P, _P, _P, _P],
     "sfm_pnp_refine": [_P, _I64, _I64, _P, _P, _P, _P, _D, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P],

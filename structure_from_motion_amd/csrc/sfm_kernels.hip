@@ -403,6 +403,7 @@ __global__ void select_init_kernel(sfm_select_result* __restrict__ result) {
     result[blockIdx.x] = r;
 }
 
+template <int SAMPLE = 8>
 __global__ __launch_bounds__(256) void select_pass1_kernel(
     const int32_t* __restrict__ cnt, const double* __restrict__ s1, const double* __restrict__ s2,
     const int32_t* __restrict__ flags, int64_t h_count, double min_extra, int aggregation,
@@ -416,7 +417,7 @@ __global__ __launch_bounds__(256) void select_pass1_kernel(
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t h = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; h < h_count; h += stride) {
         bool flagged;
-        const uint64_t k = hypothesis_key(cnt, s1, s2, flags, h, min_extra, aggregation, flagged);
+        const uint64_t k = hypothesis_key(cnt, s1, s2, flags, h, min_extra, aggregation, flagged, SAMPLE);
         key = k < key ? k : key;
         if (flagged) {
             first_flag = h < first_flag ? h : first_flag;
@@ -440,6 +441,7 @@ __global__ __launch_bounds__(256) void select_pass1_kernel(
     }
 }
 
+template <int SAMPLE = 8>
 __global__ __launch_bounds__(256) void select_pass2_kernel(
     const int32_t* __restrict__ cnt, const double* __restrict__ s1, const double* __restrict__ s2,
     const int32_t* __restrict__ flags, int64_t h_count, double min_extra, int aggregation,
@@ -453,7 +455,7 @@ __global__ __launch_bounds__(256) void select_pass2_kernel(
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t h = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; h < h_count; h += stride) {
         bool flagged;
-        const uint64_t k = hypothesis_key(cnt, s1, s2, flags, h, min_extra, aggregation, flagged);
+        const uint64_t k = hypothesis_key(cnt, s1, s2, flags, h, min_extra, aggregation, flagged, SAMPLE);
         if (k == target && h < best) best = h;
     }
 #pragma unroll
@@ -482,6 +484,7 @@ __global__ void select_final_kernel(const int32_t* __restrict__ cnt, int64_t h_c
 // lexicographic minimum of (error bits, index) directly — same keys, same winner as the three passes above, three
 // launches fewer (a small RANSAC pass is a chain of ~4 us kernels; profiles/r01/README.md).
 constexpr int kSelectBlock = 1024;
+template <int SAMPLE = 8>
 __global__ __launch_bounds__(kSelectBlock) void select_block_kernel(
     const int32_t* __restrict__ cnt, const double* __restrict__ s1, const double* __restrict__ s2,
     const int32_t* __restrict__ flags, int64_t h_count, int64_t h_offset, double min_extra, int aggregation,
@@ -491,7 +494,7 @@ __global__ __launch_bounds__(kSelectBlock) void select_block_kernel(
     const int64_t b = blockIdx.x;
     sfmsel::block_select<kSelectBlock>(cnt + b * h_count, s1 + b * h_count, s2 + b * h_count,
                                        flags != nullptr ? flags + b * h_count : nullptr, h_count, h_offset, min_extra,
-                                       aggregation, result + b, scratch, &winner);
+                                       aggregation, result + b, scratch, &winner, SAMPLE);
 }
 
 // Smallest passes (the reference's own workload: a few hundred matches, 2000 iterations): one 1024-thread block selects
@@ -845,14 +848,15 @@ __global__ __launch_bounds__(kSelectBlock) void select_fold_mask_batch_kernel(
 // ------------------------------------------------------------------------------------------------
 // Inlier mask of the winner (ransac.py:70-76): 1 = surviving non-sample point, 2 = sample point.
 // ------------------------------------------------------------------------------------------------
+template <int SAMPLE = 8>
 __global__ void inlier_mask_kernel(const Corr* __restrict__ corr, int64_t n,
                                    const double* __restrict__ E, const int32_t* __restrict__ S,
                                    int64_t h_count, const sfm_select_result* __restrict__ result,
                                    double thr, uint8_t* __restrict__ mask) {
     const int64_t b = blockIdx.y;
-    sfmsel::write_inlier_mask(corr + b * n, n, E + b * h_count * 9, S + b * h_count * 8, h_count, result[b].best_h, thr,
-                              mask + b * n, (int64_t)blockIdx.x * blockDim.x + threadIdx.x,
-                              (int64_t)gridDim.x * blockDim.x);
+    sfmsel::write_inlier_mask<1, SAMPLE>(corr + b * n, n, E + b * h_count * 9, S + b * h_count * 8, h_count, result[b].best_h, thr,
+                                         mask + b * n, (int64_t)blockIdx.x * blockDim.x + threadIdx.x,
+                                         (int64_t)gridDim.x * blockDim.x);
 }
 
 __global__ void sed_values_kernel(const Corr* __restrict__ corr, int64_t n, const double* __restrict__ E,
@@ -1032,6 +1036,48 @@ __global__ __launch_bounds__(kWave) void decompose_essential_kernel(const double
 MatrixPrep matrix_prep(const sfmhost::ScorePlan& plan, int step_blocks) {
     if (!plan.ws.matrix) return MatrixPrep{nullptr, 0, 0.0, 0.0, nullptr, nullptr, nullptr, 0};
     return MatrixPrep{plan.partial, (int)plan.matrix.setup_blocks, plan.a_scale, plan.thr, plan.hyp_table, plan.fix, plan.table, step_blocks};
+}
+
+// The launches of sfm_select_best / sfm_select_best_ex for SAMPLE-item samples (8: exactly the launches of the eight-point path).
+template <int SAMPLE>
+int select_best_launch(const int32_t* cnt, const double* s1, const double* s2, const int32_t* flags, int64_t h_count, int64_t batch,
+                       double min_extra, int aggregation, int64_t h_offset, sfm_select_result* result, void* stream) {
+    if (h_count < 0 || batch < 0) return fail(SFM_EINVAL, "sfm_select_best: negative size");
+    if (aggregation < SFM_AGG_SUM || aggregation > SFM_AGG_RMS)
+        return fail(SFM_EINVAL, "sfm_select_best: unknown aggregation");
+    if (batch == 0) return SFM_OK;
+    if (batch > 65535) return fail(SFM_EINVAL, "sfm_select_best: batch > 65535");
+    if (!result || (h_count > 0 && (!cnt || !s1 || !s2)))
+        return fail(SFM_EINVAL, "sfm_select_best: null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    if (h_count <= 32 * kSelectBlock) {  // <= 32 hypotheses per thread: one block per batch entry, one launch
+        hipLaunchKernelGGL(select_block_kernel<SAMPLE>, dim3((unsigned)batch), dim3(kSelectBlock), 0, st, cnt, s1, s2, flags,
+                           h_count, h_offset, min_extra, aggregation, result);
+        return check_launch("select_block_kernel");
+    }
+    hipLaunchKernelGGL(select_init_kernel, dim3((unsigned)batch), dim3(1), 0, st, result);
+    if (h_count > 0) {
+        const dim3 grid(grid_stride(h_count, 256, 64), (unsigned)batch);
+        hipLaunchKernelGGL(select_pass1_kernel<SAMPLE>, grid, dim3(256), 0, st, cnt, s1, s2, flags, h_count, min_extra,
+                           aggregation, result);
+        hipLaunchKernelGGL(select_pass2_kernel<SAMPLE>, grid, dim3(256), 0, st, cnt, s1, s2, flags, h_count, min_extra,
+                           aggregation, result);
+    }
+    hipLaunchKernelGGL(select_final_kernel, dim3((unsigned)batch), dim3(1), 0, st, cnt, h_count, h_offset, result);
+    return check_launch("select_best_kernel");
+}
+
+// The launch of sfm_inlier_mask / sfm_inlier_mask_ex for SAMPLE-item samples.
+template <int SAMPLE>
+int inlier_mask_launch(const double* corr, int64_t n, const double* E, const int32_t* S, int64_t h_count, int64_t batch,
+                       const sfm_select_result* result, double thr, uint8_t* mask, void* stream) {
+    if (h_count < 0 || batch < 0 || n < 0) return fail(SFM_EINVAL, "sfm_inlier_mask: negative size");
+    if (n == 0 || batch == 0) return SFM_OK;
+    if (!corr || !E || !S || !result || !mask) return fail(SFM_EINVAL, "sfm_inlier_mask: null pointer");
+    SFM_REQUIRE_GRID("sfm_inlier_mask", 1, 1, 256, batch);
+    hipLaunchKernelGGL(inlier_mask_kernel<SAMPLE>, dim3(grid_stride(n, 256, 1024), (unsigned)batch), dim3(256), 0,
+                       (hipStream_t)stream, (const Corr*)corr, n, E, S, h_count, result, thr, mask);
+    return check_launch("inlier_mask_kernel");
 }
 
 }  // namespace
@@ -1303,41 +1349,29 @@ int sfm_hartley_normalize(const double* coords, int64_t n, double* out, void* st
 int sfm_select_best(const int32_t* cnt, const double* s1, const double* s2, const int32_t* flags,
                     int64_t h_count, int64_t batch, double min_extra, int aggregation, int64_t h_offset,
                     sfm_select_result* result, void* stream) {
-    if (h_count < 0 || batch < 0) return fail(SFM_EINVAL, "sfm_select_best: negative size");
-    if (aggregation < SFM_AGG_SUM || aggregation > SFM_AGG_RMS)
-        return fail(SFM_EINVAL, "sfm_select_best: unknown aggregation");
-    if (batch == 0) return SFM_OK;
-    if (batch > 65535) return fail(SFM_EINVAL, "sfm_select_best: batch > 65535");
-    if (!result || (h_count > 0 && (!cnt || !s1 || !s2)))
-        return fail(SFM_EINVAL, "sfm_select_best: null pointer");
-    hipStream_t st = (hipStream_t)stream;
-    if (h_count <= 32 * kSelectBlock) {  // <= 32 hypotheses per thread: one block per batch entry, one launch
-        hipLaunchKernelGGL(select_block_kernel, dim3((unsigned)batch), dim3(kSelectBlock), 0, st, cnt, s1, s2, flags,
-                           h_count, h_offset, min_extra, aggregation, result);
-        return check_launch("select_block_kernel");
-    }
-    hipLaunchKernelGGL(select_init_kernel, dim3((unsigned)batch), dim3(1), 0, st, result);
-    if (h_count > 0) {
-        const dim3 grid(grid_stride(h_count, 256, 64), (unsigned)batch);
-        hipLaunchKernelGGL(select_pass1_kernel, grid, dim3(256), 0, st, cnt, s1, s2, flags, h_count, min_extra,
-                           aggregation, result);
-        hipLaunchKernelGGL(select_pass2_kernel, grid, dim3(256), 0, st, cnt, s1, s2, flags, h_count, min_extra,
-                           aggregation, result);
-    }
-    hipLaunchKernelGGL(select_final_kernel, dim3((unsigned)batch), dim3(1), 0, st, cnt, h_count, h_offset, result);
-    return check_launch("select_best_kernel");
+    return select_best_launch<8>(cnt, s1, s2, flags, h_count, batch, min_extra, aggregation, h_offset, result, stream);
+}
+
+int sfm_select_best_ex(const int32_t* cnt, const double* s1, const double* s2, const int32_t* flags, int64_t h_count, int64_t batch,
+                       double min_extra, int aggregation, int64_t h_offset, int sample_size, sfm_select_result* result, void* stream) {
+    if (sample_size == 6)
+        return select_best_launch<6>(cnt, s1, s2, flags, h_count, batch, min_extra, aggregation, h_offset, result, stream);
+    if (sample_size == 8)
+        return select_best_launch<8>(cnt, s1, s2, flags, h_count, batch, min_extra, aggregation, h_offset, result, stream);
+    return fail(SFM_EINVAL, "sfm_select_best_ex: sample_size must be 6 or 8");
 }
 
 int sfm_inlier_mask(const double* corr, int64_t n, const double* E, const int32_t* S, int64_t h_count,
                     int64_t batch, const sfm_select_result* result, double thr, uint8_t* mask,
                     void* stream) {
-    if (h_count < 0 || batch < 0 || n < 0) return fail(SFM_EINVAL, "sfm_inlier_mask: negative size");
-    if (n == 0 || batch == 0) return SFM_OK;
-    if (!corr || !E || !S || !result || !mask) return fail(SFM_EINVAL, "sfm_inlier_mask: null pointer");
-    SFM_REQUIRE_GRID("sfm_inlier_mask", 1, 1, 256, batch);
-    hipLaunchKernelGGL(inlier_mask_kernel, dim3(grid_stride(n, 256, 1024), (unsigned)batch), dim3(256), 0,
-                       (hipStream_t)stream, (const Corr*)corr, n, E, S, h_count, result, thr, mask);
-    return check_launch("inlier_mask_kernel");
+    return inlier_mask_launch<8>(corr, n, E, S, h_count, batch, result, thr, mask, stream);
+}
+
+int sfm_inlier_mask_ex(const double* corr, int64_t n, const double* E, const int32_t* S, int64_t h_count, int64_t batch,
+                       const sfm_select_result* result, double thr, int sample_size, uint8_t* mask, void* stream) {
+    if (sample_size == 6) return inlier_mask_launch<6>(corr, n, E, S, h_count, batch, result, thr, mask, stream);
+    if (sample_size == 8) return inlier_mask_launch<8>(corr, n, E, S, h_count, batch, result, thr, mask, stream);
+    return fail(SFM_EINVAL, "sfm_inlier_mask_ex: sample_size must be 6 or 8");
 }
 
 int sfm_sed_values(const double* corr, int64_t n, const double* E, double* out, void* stream) {

@@ -68,14 +68,16 @@ constexpr int kStack = 256;  // entries per (wave, hypothesis) survivor stack; <
 
 // ------------------------------------------------------------------------------------------------
 // Epilogue shared by both kernels: fixed-order wave reduction + sample fix-up + store.
-// The 8 sample points are never counted and always summed (ransac.py:70-79): the main loop treats them
-// like any other point, lanes 0..7 then re-score them exactly and patch the totals.
+// The SAMPLE sample points (8 for the eight-point fit, 6 for the five-point fit) are never counted and always summed
+// (ransac.py:70-79): the main loop treats them like any other point, lanes 0..SAMPLE-1 then re-score them exactly and patch
+// the totals.
 // ------------------------------------------------------------------------------------------------
+template <int SAMPLE = 8>
 SFM_DEVICE void finish_hypothesis(const Corr* __restrict__ pts, const int32_t* __restrict__ sample,
                                   const double (&e)[9], double thr, int lane, int c, double a1, double a2,
                                   int32_t* cnt_out, double* s1_out, double* s2_out) {
-    // the sample fix-up goes into the per-lane partials of lanes 0..7 first: one set of reductions, not two
-    if (lane < 8) {
+    // the sample fix-up goes into the per-lane partials of lanes 0..SAMPLE-1 first: one set of reductions, not two
+    if (lane < SAMPLE) {
         const Corr p = pts[sample[lane]];
         const double sed = sfm::sed_value(e, p.xa, p.ya, p.xb, p.yb);
         const bool counted = sed <= thr;  // already in (c, a1, a2)
@@ -97,7 +99,7 @@ SFM_DEVICE void finish_hypothesis(const Corr* __restrict__ pts, const int32_t* _
 // ------------------------------------------------------------------------------------------------
 // Exact kernel: one wave owns HPW hypotheses (E in scalar registers) and streams all n points.
 // ------------------------------------------------------------------------------------------------
-template <int HPW>
+template <int HPW, int SAMPLE = 8>
 __global__ __launch_bounds__(256) void score_sed_exact_kernel(
     const Corr* __restrict__ corr, int n, const double* __restrict__ E, const int32_t* __restrict__ S,
     int h_count, double thr, int32_t* __restrict__ cnt, double* __restrict__ s1,
@@ -144,8 +146,8 @@ __global__ __launch_bounds__(256) void score_sed_exact_kernel(
         const int h = h0 + k;
         if (h < h_count) {  // wave-uniform
             const int64_t o = b * (int64_t)h_count + h;
-            finish_hypothesis(pts, Sb + (int64_t)h * 8, e[k], thr, lane, c[k], a1[k], a2[k], cnt + o, s1 + o,
-                              s2 + o);
+            finish_hypothesis<SAMPLE>(pts, Sb + (int64_t)h * 8, e[k], thr, lane, c[k], a1[k], a2[k], cnt + o, s1 + o,
+                                      s2 + o);
         }
     }
 }
@@ -1234,7 +1236,7 @@ int plan_score(const char* fn, int64_t n, int64_t h_count, int64_t batch, double
     if (!load_options(options, &plan->opt)) return refuse(fn, "an option is out of range");
     if (workspace == nullptr) {   // the exact kernel: waves of kHypPerWave hypotheses
         plan->exact = true;
-        if (!grid_fits((h_count + kHypPerWave - 1) / kHypPerWave, 256 / kWave, 256, batch)) return refuse(fn, kBeyondOneLaunch);
+        if (!sfmhost::grid_fits((h_count + kHypPerWave - 1) / kHypPerWave, 256 / kWave, 256, batch)) return refuse(fn, kBeyondOneLaunch);
         return SFM_OK;
     }
     const int rc = plan_launches(fn, plan);
@@ -1429,6 +1431,27 @@ int sfm_score_sed_ex(const double* corr, int64_t n, const double* E, const int32
     const int rc = sfmhost::plan_score("sfm_score_sed", n, h_count, batch, thr, options, workspace, workspace_bytes, &plan);
     if (rc != SFM_OK) return rc;
     return sfmhost::launch_score(plan, sfmhost::ScoreArrays{corr, E, S, cnt, s1, s2, (hipStream_t)stream});
+}
+
+// Six-item samples (the five-point fit) or eight-item ones: the all-fp64 kernel with the sample fix-up of SAMPLE items.
+int sfm_score_sed_sample_ex(const double* corr, int64_t n, const double* E, const int32_t* S, int64_t h_count, int64_t batch,
+                            double thr, int sample_size, int32_t* cnt, double* s1, double* s2, void* stream) {
+    if (sample_size != 6 && sample_size != 8) return fail(SFM_EINVAL, "sfm_score_sed_sample_ex: sample_size must be 6 or 8");
+    if (h_count < 0 || batch < 0 || n < 0) return fail(SFM_EINVAL, "sfm_score_sed_sample_ex: negative size");
+    if (n > 0x7FFFFFFF || h_count > 0x3FFFFFFF) return fail(SFM_EINVAL, "sfm_score_sed_sample_ex: size too large");
+    if (h_count == 0 || batch == 0) return SFM_OK;
+    if (!corr || !E || !S || !cnt || !s1 || !s2) return fail(SFM_EINVAL, "sfm_score_sed_sample_ex: null pointer");
+    if (n < sample_size) return fail(SFM_EINVAL, "sfm_score_sed_sample_ex: need at least sample_size correspondences");
+    if (!sfmhost::grid_fits((h_count + kHypPerWave - 1) / kHypPerWave, 256 / kWave, 256, batch))
+        return fail(SFM_EINVAL, "sfm_score_sed_sample_ex: size exceeds what one launch covers");
+    const dim3 grid(grid_for((h_count + kHypPerWave - 1) / kHypPerWave, 256 / kWave), (unsigned)batch);
+    if (sample_size == 6)
+        hipLaunchKernelGGL((score_sed_exact_kernel<kHypPerWave, 6>), grid, dim3(256), 0, (hipStream_t)stream, (const Corr*)corr,
+                           (int)n, E, S, (int)h_count, thr, cnt, s1, s2);
+    else
+        hipLaunchKernelGGL(score_sed_exact_kernel<kHypPerWave>, grid, dim3(256), 0, (hipStream_t)stream, (const Corr*)corr, (int)n, E,
+                           S, (int)h_count, thr, cnt, s1, s2);
+    return check_launch("score_sed_exact_kernel");
 }
 
 }  // extern "C"

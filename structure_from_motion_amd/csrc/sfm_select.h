@@ -183,9 +183,10 @@ __device__ __forceinline__ int64_t block_select(const int32_t* __restrict__ cnt,
     return *sh_winner;
 }
 
-// mask[i] = 2 for the 8 sample points of hypothesis h, 1 for the other points with sed <= thr, 0 otherwise; all zero
-// for h outside [0, h_count).  Points i = first, first + stride, ... (a block- or grid-stride walk).
-template <int UNROLL = 1>
+// mask[i] = 2 for the SAMPLE sample points of hypothesis h (the first SAMPLE entries of its row of S: 8 for the eight-point
+// fit, 6 for the five-point fit), 1 for the other points with sed <= thr, 0 otherwise; all zero for h outside [0, h_count).
+// Points i = first, first + stride, ... (a block- or grid-stride walk).
+template <int UNROLL = 1, int SAMPLE = 8>
 __device__ __forceinline__ void write_inlier_mask(const Corr* __restrict__ pts, int64_t n, const double* __restrict__ E,
                                                   const int32_t* __restrict__ S, int64_t h_count, int64_t h, double thr,
                                                   uint8_t* __restrict__ out, int64_t first, int64_t stride) {
@@ -194,11 +195,11 @@ __device__ __forceinline__ void write_inlier_mask(const Corr* __restrict__ pts, 
         return;
     }
     double e[9];
-    int32_t smp[8];
+    int32_t smp[SAMPLE];
 #pragma unroll
     for (int k = 0; k < 9; ++k) e[k] = E[h * 9 + k];
 #pragma unroll
-    for (int k = 0; k < 8; ++k) smp[k] = S[h * 8 + k];
+    for (int k = 0; k < SAMPLE; ++k) smp[k] = S[h * 8 + k];
     // UNROLL points per trip with their loads issued together (a single block walking many points is load-latency bound)
     for (int64_t i0 = first; i0 < n; i0 += stride * UNROLL) {
         Corr p[UNROLL];
@@ -214,7 +215,7 @@ __device__ __forceinline__ void write_inlier_mask(const Corr* __restrict__ pts, 
                 const double sed = sfm::sed_value(e, p[u].xa, p[u].ya, p[u].xb, p[u].yb);
                 bool in_sample = false;
 #pragma unroll
-                for (int k = 0; k < 8; ++k) in_sample |= (smp[k] == (int32_t)i);
+                for (int k = 0; k < SAMPLE; ++k) in_sample |= (smp[k] == (int32_t)i);
                 out[i] = in_sample ? 2 : ((sed <= thr) ? 1 : 0);
             }
         }

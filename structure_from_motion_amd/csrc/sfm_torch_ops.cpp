@@ -7,7 +7,8 @@
 // kernel, so fake-tensor tracing / torch.compile / opcheck work) and, where the engine pre-allocates its buffers
 // (device.RansacWorkspace), an in-place `_`-suffixed form with mutable arguments, plus the fused
 // sample_fit_philox_; and the PnP ops (sfm_pnp.hip) pnp_fit, pnp_score and the whole pass pnp_ransac_pass_, their P3P
-// forms p3p_fit and p3p_ransac_pass_ (sfm_p3p.h), and the
+// forms p3p_fit and p3p_ransac_pass_ (sfm_p3p.h), the five-point fit five_point_fit and pass five_point_ransac_pass_
+// (sfm_five_point.hip), and the
 // refinement of a winner pnp_refine (sfm_pnp_refine.hip), bundle_adjust (sfm_bundle.hip) and triangulate_tracks
 // (sfm_tracks.hip).  The reference call sites these serve: apps/sfm.py:110-119 (RANSAC-E), :133-138 (pose),
 // :181-186 (triangulation).
@@ -184,6 +185,57 @@ std::tuple<Tensor, Tensor> fit_eight_point_meta(const Tensor& corr, const Tensor
     meta_dims(corr, S);
     return {at::empty_symint({corr.sym_size(0), S.sym_size(1), 9}, like(corr, at::kDouble)),
             at::empty_symint({corr.sym_size(0), S.sym_size(1)}, like(corr, at::kInt))};
+}
+
+// ---- five-point fit (six-item samples, sfm_five_point.hip): the tensors of fit_eight_point --------------------------
+void five_point_fit_out(const Tensor& corr, const Tensor& S, Tensor& E, Tensor& flags) {
+    const OpDevice scope(corr);
+    need(corr, "corr", at::kDouble);
+    need(S, "S", at::kInt);
+    need(E, "E", at::kDouble);
+    need(flags, "flags", at::kInt);
+    const Dims d = hypothesis_dims(corr, S);
+    check_E(E, d);
+    TORCH_CHECK(flags.numel() == d.batch * d.h, "sfm_hip: flags must be [batch, h]");
+    ok(sfm_five_point_fit(ptr<double>(corr), d.n, ptr<int32_t>(S), d.h, d.batch, ptr<double>(E), ptr<int32_t>(flags), current_stream()),
+       "sfm_five_point_fit");
+}
+
+std::tuple<Tensor, Tensor> five_point_fit(const Tensor& corr, const Tensor& S) {
+    const Dims d = hypothesis_dims(corr, S);
+    Tensor E = at::empty({d.batch, d.h, 9}, like(corr, at::kDouble));
+    Tensor flags = at::empty({d.batch, d.h}, like(corr, at::kInt));
+    five_point_fit_out(corr, S, E, flags);
+    return {E, flags};
+}
+
+// the whole five-point pass (sfm_five_point_ransac_pass): fit (from S, or Philox-sampled with use_philox), six-item scoring,
+// selection and the optional mask
+void five_point_ransac_pass_out(const Tensor& corr, int64_t seed, int64_t seed_stride, bool use_philox, int64_t h_begin, double thr,
+                                double min_extra, int64_t aggregation, Tensor& S, Tensor& E, Tensor& flags, Tensor& cnt, Tensor& s1,
+                                Tensor& s2, Tensor& result, const std::optional<Tensor>& mask) {
+    const OpDevice scope(corr);
+    need(corr, "corr", at::kDouble);
+    need(S, "S", at::kInt);
+    need(E, "E", at::kDouble);
+    need(flags, "flags", at::kInt);
+    need(cnt, "cnt", at::kInt);
+    need(s1, "s1", at::kDouble);
+    need(s2, "s2", at::kDouble);
+    need(result, "result", at::kLong);
+    if (mask.has_value()) need(*mask, "mask", at::kByte);
+    const Dims d = hypothesis_dims(corr, S);
+    check_E(E, d);
+    TORCH_CHECK(flags.numel() == d.batch * d.h && cnt.numel() == d.batch * d.h && s1.numel() == d.batch * d.h &&
+                    s2.numel() == d.batch * d.h,
+                "sfm_hip: flags, cnt, s1, s2 must be [batch, h]");
+    TORCH_CHECK(result.numel() == d.batch * 5, "sfm_hip: result must be [batch, 5] int64");
+    if (mask.has_value()) TORCH_CHECK(mask->numel() == d.batch * d.n, "sfm_hip: mask must be [batch, n]");
+    ok(sfm_five_point_ransac_pass((uint64_t)seed, (uint64_t)seed_stride, use_philox ? 1 : 0, h_begin, ptr<double>(corr), d.n, d.h,
+                                  d.batch, thr, min_extra, (int)aggregation, ptr<int32_t>(S), ptr<double>(E), ptr<int32_t>(flags),
+                                  ptr<int32_t>(cnt), ptr<double>(s1), ptr<double>(s2),
+                                  reinterpret_cast<sfm_select_result*>(ptr<int64_t>(result)), ptr<uint8_t>(mask), current_stream()),
+       "sfm_five_point_ransac_pass");
 }
 
 // Philox sampling fused into the fit launch; `seed_dev` (int64 [1] on the device) is read at kernel run time when given
@@ -871,6 +923,11 @@ TORCH_LIBRARY(sfm_hip, m) {
     m.def("inlier_mask_(Tensor corr, Tensor E, Tensor S, Tensor result, float thr, Tensor(a!) mask) -> ()");
     m.def("cheirality(Tensor corr, Tensor pose_rt, float distance_threshold) -> Tensor");
     m.def("triangulate(Tensor corr, Tensor P1, Tensor P2) -> Tensor");
+    m.def("five_point_fit(Tensor corr, Tensor S) -> (Tensor, Tensor)");
+    m.def("five_point_fit_(Tensor corr, Tensor S, Tensor(a!) E, Tensor(b!) flags) -> ()");
+    m.def("five_point_ransac_pass_(Tensor corr, int seed, int seed_stride, bool use_philox, int h_begin, float thr, float min_extra, "
+          "int aggregation, Tensor(a!) S, Tensor(b!) E, Tensor(c!) flags, Tensor(d!) cnt, Tensor(e!) s1, Tensor(f!) s2, "
+          "Tensor(g!) result, Tensor(h!)? mask) -> ()");
     m.def("pnp_fit(Tensor pts, Tensor S, float[] K) -> (Tensor, Tensor)");
     m.def("pnp_fit_(Tensor pts, Tensor S, float[] K, Tensor(a!) model, Tensor(b!) flags) -> ()");
     m.def("p3p_fit(Tensor pts, Tensor S, float[] K) -> (Tensor, Tensor)");
@@ -909,6 +966,9 @@ TORCH_LIBRARY_IMPL(sfm_hip, CUDA, m) {
     m.impl("normalize_coords", &normalize_coords);
     m.impl("normalize_coords_", &normalize_coords_out);
     m.impl("fit_eight_point", &fit_eight_point);
+    m.impl("five_point_fit", &five_point_fit);
+    m.impl("five_point_fit_", &five_point_fit_out);
+    m.impl("five_point_ransac_pass_", &five_point_ransac_pass_out);
     m.impl("fit_eight_point_", &fit_eight_point_out);
     m.impl("sample_fit_philox_", &sample_fit_philox_out);
     m.impl("score_sed", &score_sed);
@@ -945,6 +1005,8 @@ TORCH_LIBRARY_IMPL(sfm_hip, CompositeExplicitAutograd, m) { m.impl("sample_philo
 // in-place forms under fake tensors: shapes are fixed by the caller's buffers, nothing to compute
 void normalize_coords_out_meta(const Tensor&, const Tensor&, double, double, double, double, Tensor&) {}
 void fit_eight_point_out_meta(const Tensor&, const Tensor&, Tensor&, Tensor&) {}
+void five_point_ransac_pass_out_meta(const Tensor&, int64_t, int64_t, bool, int64_t, double, double, int64_t, Tensor&, Tensor&, Tensor&,
+                                     Tensor&, Tensor&, Tensor&, Tensor&, const std::optional<Tensor>&) {}
 void sample_fit_philox_out_meta(const Tensor&, int64_t, const std::optional<Tensor>&, int64_t, int64_t, Tensor&, Tensor&,
                                 Tensor&) {}
 void score_sed_out_meta(const Tensor&, const Tensor&, const Tensor&, double, Tensor&, Tensor&, Tensor&,
@@ -971,6 +1033,8 @@ void triangulate_tracks_out_meta(const Tensor&, const Tensor&, const Tensor&, co
 TORCH_LIBRARY_IMPL(sfm_hip, Meta, m) {
     m.impl("normalize_coords_", &normalize_coords_out_meta);
     m.impl("fit_eight_point_", &fit_eight_point_out_meta);
+    m.impl("five_point_fit_", &fit_eight_point_out_meta);
+    m.impl("five_point_ransac_pass_", &five_point_ransac_pass_out_meta);
     m.impl("sample_fit_philox_", &sample_fit_philox_out_meta);
     m.impl("score_sed_", &score_sed_out_meta);
     m.impl("ransac_pass_small_", &ransac_pass_small_out_meta);
@@ -979,6 +1043,7 @@ TORCH_LIBRARY_IMPL(sfm_hip, Meta, m) {
     m.impl("inlier_mask_", &inlier_mask_out_meta);
     m.impl("normalize_coords", &normalize_coords_meta);
     m.impl("fit_eight_point", &fit_eight_point_meta);
+    m.impl("five_point_fit", &fit_eight_point_meta);
     m.impl("score_sed", &score_sed_meta);
     m.impl("select_best", &select_best_meta);
     m.impl("inlier_mask", &inlier_mask_meta);

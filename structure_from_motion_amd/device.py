@@ -201,14 +201,29 @@ def score_workspace(n: int, h_count: int, batch: int, device, options: Optional[
 
 def score_sed(corr: torch.Tensor, E: torch.Tensor, S: torch.Tensor, thr: float, cnt=None, s1=None,
               s2=None, workspace: Optional[torch.Tensor] = None, exact_only: bool = False,
-              options: Optional[ScoreOptions] = None):
+              options: Optional[ScoreOptions] = None, sample_size: int = 8):
     """Per-hypothesis (extra-inlier count, sum sed, sum sed^2).  Uses the two-tier kernel (fp32 pre-filter
     + exact fp64) unless ``exact_only``; both give identical counts / decisions.  ``options`` (launch options of the
     two-tier kernels: which filter kernel, ranges, order ...; ``sfm_score_sed_ex``) default to the process-wide set, which
-    the SFM_SCORE_* variables initialised when the library was loaded."""
+    the SFM_SCORE_* variables initialised when the library was loaded.  ``sample_size=6``: the first six entries of a row of
+    S are the sample (the five-point fit), scored by the all-fp64 kernel (``sfm_score_sed_sample_ex``)."""
     op = ops.load()
     B, N, _ = corr.shape
     H = E.shape[1]
+    if sample_size != 8:
+        if workspace is not None or options is not None:
+            raise ValueError("score_sed(sample_size != 8) runs the all-fp64 kernel: it takes no workspace and no launch options")
+        if cnt is None:
+            cnt = torch.empty((B, H), dtype=torch.int32, device=corr.device)
+        if s1 is None:
+            s1 = torch.empty((B, H), dtype=F64, device=corr.device)
+        if s2 is None:
+            s2 = torch.empty((B, H), dtype=F64, device=corr.device)
+        assert S.dtype == torch.int32 and corr.dtype == F64 and E.dtype == F64
+        with torch.cuda.device(corr.device):
+            check(_native.load().sfm_score_sed_sample_ex(_ptr(corr), N, _ptr(E), _ptr(S), H, B, float(thr), int(sample_size),
+                                                         _ptr(cnt), _ptr(s1), _ptr(s2), _stream()), "sfm_score_sed_sample_ex")
+        return cnt, s1, s2
     exact = exact_only or os.environ.get("SFM_SCORE_KERNEL", "filtered") == "exact"
     if options is not None:   # per-call launch options (and timing events): straight through the C ABI
         if cnt is None:
@@ -356,8 +371,18 @@ def large_pass_eligible(batch: int, n: int, h: int) -> bool:
     return _native.load().sfm_score_kernel_choice(n, h, 1) == _native.SCORE_KERNEL_MATRIX
 
 
-def select_best(cnt, s1, s2, flags, min_extra: float, aggregation: int, h_offset: int = 0, out=None):
-    """-> int64 tensor [B,5] viewing the sfm_select_result records."""
+def select_best(cnt, s1, s2, flags, min_extra: float, aggregation: int, h_offset: int = 0, out=None, sample_size: int = 8):
+    """-> int64 tensor [B,5] viewing the sfm_select_result records.  ``sample_size``: items of a sample in the mean / RMS (8, or 6
+    for the five-point fit: ``sfm_select_best_ex``)."""
+    if sample_size != 8:
+        B, H = cnt.shape
+        if out is None:
+            out = torch.empty((B, SELECT_BYTES // 8), dtype=torch.int64, device=cnt.device)
+        with torch.cuda.device(cnt.device):
+            check(_native.load().sfm_select_best_ex(_ptr(cnt), _ptr(s1), _ptr(s2), _ptr(flags), H, B, float(min_extra),
+                                                    int(aggregation), h_offset, int(sample_size), _ptr(out), _stream()),
+                  "sfm_select_best_ex")
+        return out
     op = ops.load()
     if out is None:
         return op.select_best(cnt, s1, s2, flags, float(min_extra), int(aggregation), h_offset)
@@ -365,7 +390,16 @@ def select_best(cnt, s1, s2, flags, min_extra: float, aggregation: int, h_offset
     return out
 
 
-def inlier_mask(corr, E, S, result, thr: float, out=None):
+def inlier_mask(corr, E, S, result, thr: float, out=None, sample_size: int = 8):
+    """uint8 [B,N]: 2 on the winner's ``sample_size`` sample items (8, or 6 for the five-point fit), 1 other inlier, 0 outlier."""
+    if sample_size != 8:
+        B, N, _ = corr.shape
+        if out is None:
+            out = torch.empty((B, N), dtype=torch.uint8, device=corr.device)
+        with torch.cuda.device(corr.device):
+            check(_native.load().sfm_inlier_mask_ex(_ptr(corr), N, _ptr(E), _ptr(S), S.shape[1], B, _ptr(result), float(thr),
+                                                    int(sample_size), _ptr(out), _stream()), "sfm_inlier_mask_ex")
+        return out
     op = ops.load()
     if out is None:
         return op.inlier_mask(corr, E, S, result, float(thr))
@@ -393,6 +427,64 @@ def read_refine_info(info: torch.Tensor):
     raw = info.cpu().numpy()
     return [(float(raw[i, 0:1].view(np.float64)[0]), int(raw[i, 1] & 0xFFFFFFFF), int(raw[i, 1] >> 32))
             for i in range(raw.shape[0])]
+
+
+E_SOLVERS = {"eight_point": 8, "five_point": 6}   # sample size of each essential-matrix solver (RansacWorkspace.run)
+
+
+def check_e_solver(solver: str) -> int:
+    """Sample size of an essential-matrix solver; ``ValueError`` for an unknown one."""
+    if solver not in E_SOLVERS:
+        raise ValueError(f"unknown essential-matrix solver {solver!r}: expected one of {sorted(E_SOLVERS)}")
+    return E_SOLVERS[solver]
+
+
+def five_point_fit(corr: torch.Tensor, S: torch.Tensor, E=None, flags=None, philox=None):
+    """Five-point fit of every hypothesis from the first six entries of each row of S (``sfm_five_point_fit``): corr [B,N,4],
+    S [B,H,8] -> E [B,H,9] (9 NaNs: no real solution), flags [B,H] (SFM_FIT_DEGENERATE).  ``philox=(seed, h_begin,
+    seed_stride)``: the samples are drawn in the fit launch, which also fills S."""
+    B, N, _ = corr.shape
+    H = S.shape[1]
+    assert S.shape == (B, H, 8) and S.dtype == torch.int32 and corr.dtype == F64
+    op = ops.load()
+    if philox is None and E is None and flags is None:
+        return op.five_point_fit(corr, S)
+    if E is None:
+        E = torch.empty((B, H, 9), dtype=F64, device=corr.device)
+    if flags is None:
+        flags = torch.empty((B, H), dtype=torch.int32, device=corr.device)
+    if philox is None:
+        op.five_point_fit_(corr, S, E, flags)
+        return E, flags
+    seed, h_begin, stride = philox   # Philox fused into the fit: a diagnostic entry outside the op set, through the C ABI
+    with torch.cuda.device(corr.device):
+        check(_native.load().sfm_five_point_sample_fit_philox(seed & (2**64 - 1), stride & (2**64 - 1), h_begin, _ptr(corr), N, H, B,
+                                                              _ptr(S), _ptr(E), _ptr(flags), _stream()),
+              "sfm_five_point_sample_fit_philox")
+    return E, flags
+
+
+def five_point_candidates(corr: torch.Tensor, S: torch.Tensor):
+    """Every candidate of items 0-4 of each sample (``sfm_five_point_candidates``) -> (out [B,H,10,9] NaN beyond the count,
+    count int32 [B,H], -1 for a degenerate sample)."""
+    B, N, _ = corr.shape
+    H = S.shape[1]
+    assert S.shape == (B, H, 8) and S.dtype == torch.int32 and corr.dtype == F64
+    out = torch.empty((B, H, 10, 9), dtype=F64, device=corr.device)
+    count = torch.empty((B, H), dtype=torch.int32, device=corr.device)
+    with torch.cuda.device(corr.device):
+        check(_native.load().sfm_five_point_candidates(_ptr(corr), N, _ptr(S), H, B, _ptr(out), _ptr(count), _stream()),
+              "sfm_five_point_candidates")
+    return out, count
+
+
+def five_point_ransac_pass(corr, S, E, flags, cnt, s1, s2, result, mask, thr: float, min_extra: float, aggregation: int,
+                           philox=None) -> None:
+    """One five-point pass (the ``five_point_ransac_pass_`` op, ``sfm_five_point_ransac_pass``): fit, six-item scoring,
+    selection, mask (``mask=None``: none).  ``philox=(seed, h_begin, seed_stride)``: samples drawn in the fit launch."""
+    seed, h_begin, stride = (0, 0, 1) if philox is None else philox
+    ops.load().five_point_ransac_pass_(corr, _as_int64(seed), _as_int64(stride), philox is not None, h_begin, float(thr),
+                                       float(min_extra), int(aggregation), S, E, flags, cnt, s1, s2, result, mask)
 
 
 def read_select(result: torch.Tensor) -> List[SelectResult]:
@@ -507,7 +599,7 @@ class RansacOutcome:
     best_h: int                # winning hypothesis (global index), -1 if none
     error: float               # aggregated inlier error of the winner
     E: Optional[np.ndarray]    # (3,3) essential matrix of the winner
-    sample: Optional[np.ndarray]   # (8,) indices of the winner's sample, in sample order
+    sample: Optional[np.ndarray]   # (8,) indices of the winner's sample, in sample order ((6,) after a five-point pass)
     mask: Optional[np.ndarray]     # (N,) uint8: 1 survivor, 2 sample point, 0 outlier
     n_flagged: int             # hypotheses whose sample was degenerate (eight_point.py:415-421)
     first_flagged: int         # lowest such hypothesis index, or -1
@@ -539,6 +631,7 @@ class RansacWorkspace:
         self.mask = torch.empty((batch, n), dtype=torch.uint8, device=dev)
         self.score_ws = score_workspace(n, h, batch, dev)   # (for the process-wide options of this moment: see _fit_workspace)
         self.frozen = False   # set by ShardedRansac.capture: the buffers' addresses are baked into a graph
+        self.sample_size = E_SOLVERS["eight_point"]   # of the last pass (outcome reads it)
 
     def _fit_workspace(self, options: Optional[ScoreOptions]) -> None:
         """The scoring workspace is sized by what a call launches: other options (per call, or process-wide defaults changed
@@ -551,11 +644,20 @@ class RansacWorkspace:
             self.score_ws = torch.empty((need,), dtype=torch.uint8, device=self.score_ws.device)
 
     def run(self, corr: torch.Tensor, thr: float, min_extra: float, aggregation: int,
-            h_offset: int = 0, with_mask: bool = True, philox=None, options: Optional[ScoreOptions] = None) -> None:
+            h_offset: int = 0, with_mask: bool = True, philox=None, options: Optional[ScoreOptions] = None,
+            solver: str = "eight_point") -> None:
         """fit + score + select (+ mask) for the sample table currently in ``self.S`` — or, with
         ``philox=(seed, h_begin, seed_stride)``, for Philox samples drawn inside the fit kernel (which also fills
         ``self.S``); ``seed`` may be an int64 device tensor (read at kernel run time).  ``options``: launch options of the
-        scoring launch of THIS pass (timing events included); default: the process-wide set."""
+        scoring launch of THIS pass (timing events included); default: the process-wide set.  ``solver="five_point"``: the
+        five-point fit on six-item samples (``sfm_five_point_ransac_pass``; an int seed, h_offset 0, no launch options)."""
+        self.sample_size = check_e_solver(solver)
+        if solver == "five_point":
+            if h_offset != 0 or options is not None or isinstance(philox and philox[0], torch.Tensor):
+                raise ValueError("RansacWorkspace.run(solver='five_point'): h_offset, options and a device seed are not supported")
+            five_point_ransac_pass(corr, self.S, self.E, self.flags, self.cnt, self.s1, self.s2, self.result,
+                                   self.mask if with_mask else None, thr, min_extra, aggregation, philox)
+            return
         if not torch.cuda.is_current_stream_capturing():
             self._fit_workspace(options)
         if small_pass_eligible(self.batch, self.n, self.h):
@@ -595,7 +697,7 @@ class RansacWorkspace:
             return RansacOutcome(-1, float("inf"), None, None, None, int(rec.n_flagged), first, 0)
         local = int(rec.best_h) - h_offset
         E = self.E[b, local].cpu().numpy().reshape(3, 3).copy()
-        sample = self.S[b, local].cpu().numpy().astype(np.int64)
+        sample = self.S[b, local, :self.sample_size].cpu().numpy().astype(np.int64)
         mask = checked_mask(self.mask[b].cpu().numpy().copy())
         return RansacOutcome(int(rec.best_h), float(rec.best_err), E, sample, mask, int(rec.n_flagged),
                              first, int(rec.best_cnt))

@@ -158,20 +158,31 @@ def local_optimisation_rounds() -> int:
 logger = logging.getLogger(__name__)   # one line per call, never per hypothesis
 
 
-def ransac_feature_pairs(data, camera_matrix, threshold, min_extra, aggregation, iterations):
+def ransac_feature_pairs(data, camera_matrix, threshold, min_extra, aggregation, iterations, solver="eight_point"):
     """Device route of fit_with_ransac for (Feature, Feature) pairs.  Returns (E or None, inlier pairs).
 
     Sampler ``pyshuffle`` (default) draws the hypothesis samples from the global ``random`` state
     exactly like the reference's cumulative ``random.shuffle`` (ransac.py:59-64) and advances it;
     ``philox`` (``SFM_SAMPLER=philox``, seed ``SFM_SEED`` or 64 bits from ``random``) is the
     counter-based sampler for large H, generated on the device.
+
+    ``solver="five_point"``: six-item samples (the first six entries of the same tables) fitted by the five-point solver
+    (DESIGN.md §6l); a degenerate sample raises ``FivePointCalculationError`` under the default policy.
     """
     from .eight_point import EightPointCalculationError
+    from .five_point import FivePointCalculationError
 
+    sample_size = device.check_e_solver(solver)
     n = len(data)
+    if solver == "five_point":
+        if n < 6:
+            raise ValueError("Six feature pairs are expected.")
+        if local_optimisation_rounds():
+            # the refit would take item 5 (which only picked the solution, and may be an outlier) as a sample point
+            raise ValueError("SFM_LOCAL_OPTIMIZATION is not supported with solver='five_point'")
     if iterations <= 0:
         return None, []
-    if n < 8:
+    if n < 8 and solver == "eight_point":
         # reference: data[:8] is short, eight_point_model_fitter raises (epipolar_ransac.py:31-32)
         raise ValueError("Eight feature pairs are expected.")
     dev = device.require_gpu()
@@ -185,9 +196,19 @@ def ransac_feature_pairs(data, camera_matrix, threshold, min_extra, aggregation,
         ws.S.copy_(device.to_device(table.S, dtype=ws.S.dtype).reshape(1, iterations, 8))
     else:
         seed = int(os.environ["SFM_SEED"]) if "SFM_SEED" in os.environ else random.getrandbits(64)
-        device.sample_philox(seed, 0, iterations, n, out=ws.S)
-    ws.run(corr.reshape(1, n, 4), threshold, min_extra, aggregation)
+    if solver == "five_point":
+        # the Philox samples are drawn inside the fit launch (positions >= n are -1, so n = 6 and 7 are valid)
+        ws.run(corr.reshape(1, n, 4), threshold, min_extra, aggregation, philox=None if table is not None else (seed, 0, 1),
+               solver=solver)
+    else:
+        if table is None:
+            device.sample_philox(seed, 0, iterations, n, out=ws.S)
+        ws.run(corr.reshape(1, n, 4), threshold, min_extra, aggregation)
     outcome = ws.outcome(0)
+    if outcome.n_flagged and degenerate_policy() == "raise" and solver == "five_point":
+        raise FivePointCalculationError(
+            f"A sampled six-tuple is degenerate for the five-point solver (hypothesis {outcome.first_flagged},"
+            f" {outcome.n_flagged} in total)")
     if outcome.n_flagged and degenerate_policy() == "raise":
         raise EightPointCalculationError(
             "More than one eigenvalue of Y.T @ Y is small. Cannot confidently estimate"
@@ -212,8 +233,8 @@ def ransac_feature_pairs(data, camera_matrix, threshold, min_extra, aggregation,
     survivors = outcome.mask == 1
     if sampler == "pyshuffle":
         perm = table.permutation_after(outcome.best_h)
-        rest = perm[8:]
-        order = np.concatenate([perm[:8], rest[survivors[rest]]])
+        rest = perm[sample_size:]
+        order = np.concatenate([perm[:sample_size], rest[survivors[rest]]])
     else:
         order = np.concatenate([outcome.sample, np.nonzero(survivors)[0]])
     return outcome.E, copy_pairs(data, order)

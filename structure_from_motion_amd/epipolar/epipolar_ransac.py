@@ -7,11 +7,13 @@ from typing import Tuple
 
 import numpy.typing as npt
 
+from .. import device
 from ..common.feature import Feature
 from ..feature_matching.matching import Match
 from ..ransac.ransac import ErrorAggregationMethod, fit_with_ransac
 from . import _engine
 from .eight_point import estimate_essential_mat, to_normalized_image_coords
+from .five_point import FivePointCalculationError, five_point  # noqa: F401  (FivePointCalculationError: re-exported)
 from .sed import calculate_symmetric_epipolar_distance
 
 FeaturePair = Tuple[Feature, Feature]
@@ -40,8 +42,22 @@ def eight_point_model_fitter(
     )
 
 
-# fit_with_ransac recognises partials of these two and runs the whole loop on the GPU.
+def five_point_model_fitter(
+    matching_features: list[FeaturePair], camera_matrix: npt.NDArray
+) -> npt.NDArray:
+    """Essential matrix from exactly six pixel-coordinate pairs (the five-point RANSAC model fitter): pairs 0-4 are solved
+    for, pair 5 picks the solution with the smallest SED.  ||E||_F = sqrt(2), largest-magnitude entry positive; NaNs when
+    the sample has no real solution.  Raises ``FivePointCalculationError`` for a degenerate sample."""
+    if 6 != len(matching_features):
+        raise ValueError("Six feature pairs are expected.")
+    coords_a = [to_normalized_image_coords(pair[0], camera_matrix) for pair in matching_features]
+    coords_b = [to_normalized_image_coords(pair[1], camera_matrix) for pair in matching_features]
+    return five_point([(f.x, f.y) for f in coords_a], [(f.x, f.y) for f in coords_b])
+
+
+# fit_with_ransac recognises partials of these and runs the whole loop on the GPU.
 eight_point_model_fitter._sfm_hip_role = "eight_point_fitter"
+five_point_model_fitter._sfm_hip_role = "five_point_fitter"
 calculate_sed_inlier_score._sfm_hip_role = "sed_scorer"
 
 
@@ -54,19 +70,27 @@ def estimate_essential_mat_with_ransac(
     min_num_extra_inliers: int | None = None,
     error_aggregation_method: ErrorAggregationMethod | None = None,
     max_iterations: int | None = None,
+    solver: str = "eight_point",
 ) -> Tuple[npt.NDArray, list[FeaturePair]]:
     """Estimate E from matched pixel features with RANSAC over eight-point hypotheses scored by SED in
     K-normalised coordinates.  Returns ``(E with E[2,2] == 1, inlier (Feature, Feature) pairs)``.
 
-    Raises ``ValueError`` when no hypothesis has enough inliers and ``EightPointCalculationError`` when
-    a sampled eight-tuple is degenerate (reference behaviour; ``SFM_DEGENERATE=skip`` ignores such
+    ``solver="five_point"`` fits six-item samples with the five-point solver instead: items 0-4 are solved
+    for and item 5 picks the solution.  Its E does NOT have E[2,2] == 1: it is scaled to ||E||_F = sqrt(2) with its
+    largest-magnitude entry positive (E[2,2] is 0 for every pure translation).  A degenerate sample raises
+    ``FivePointCalculationError``, a subclass of ``EightPointCalculationError``.
+
+    Raises ``ValueError`` when no hypothesis has enough inliers or ``solver`` is unknown, and ``EightPointCalculationError``
+    when a sampled eight-tuple is degenerate (reference behaviour; ``SFM_DEGENERATE=skip`` ignores such
     hypotheses instead)."""
+    sample_size = device.check_e_solver(solver)   # ValueError for an unknown solver
+    fitter = five_point_model_fitter if solver == "five_point" else eight_point_model_fitter
     with _engine.gc_paused():  # bulk creation of pair tuples and inlier copies: see _engine.gc_paused
         feature_pairs = _engine.match_pairs(features_a, features_b, matches)
         e, inlier_feature_pairs = fit_with_ransac(
             feature_pairs,
-            model_fit_data_count=8,
-            model_fitter=partial(eight_point_model_fitter, camera_matrix=camera_matrix),
+            model_fit_data_count=sample_size,
+            model_fitter=partial(fitter, camera_matrix=camera_matrix),
             inlier_scorer=partial(calculate_sed_inlier_score, camera_matrix=camera_matrix),
             inlier_threshold=sed_inlier_threshold,
             min_num_extra_inliers=min_num_extra_inliers,

@@ -5,7 +5,8 @@ Two execution routes behind one signature:
 * when ``model_fitter`` / ``inlier_scorer`` are the eight-point fitter and SED scorer of
   ``epipolar_ransac`` (which is what ``estimate_essential_mat_with_ransac`` passes, exactly like the
   reference's ``epipolar_ransac.py:58-67``), the whole loop — fit, H x N scoring, gate, aggregation,
-  selection — runs as HIP kernels on the MI355X (``device.RansacWorkspace``); likewise for the six-point PnP fitter
+  selection — runs as HIP kernels on the MI355X (``device.RansacWorkspace``), and so does the five-point fitter of
+  ``epipolar_ransac`` with ``model_fit_data_count == 6``; likewise for the six-point PnP fitter
   and reprojection scorer of ``pnp.pnp`` with ``model_fit_data_count == 6``, and its P3P fitter with
   ``model_fit_data_count == 4`` (``device.PnPWorkspace``);
 * for arbitrary Python callables (e.g. the 2-point line fitter of the reference's own
@@ -72,6 +73,11 @@ def fit_with_ransac(
 
         model, inliers = pnp_engine.ransac_pnp_items(
             data, spec.camera_matrix, inlier_threshold, min_extra, aggregation_code(method), iterations, solver=spec.solver)
+    elif isinstance(spec, EssentialDeviceSpec):
+        from ..epipolar import _engine
+
+        model, inliers = _engine.ransac_feature_pairs(
+            data, spec.camera_matrix, inlier_threshold, min_extra, aggregation_code(method), iterations, solver=spec.solver)
     elif spec is not None:
         from ..epipolar import _engine
 
@@ -91,6 +97,12 @@ class PnPDeviceSpec(NamedTuple):
     """Device route of a PnP fitter (six-point DLT or P3P) / reprojection scorer pair."""
     camera_matrix: np.ndarray
     solver: str = "dlt"
+
+
+class EssentialDeviceSpec(NamedTuple):
+    """Device route of the five-point fitter / SED scorer pair (the eight-point pair routes as a bare camera matrix)."""
+    camera_matrix: np.ndarray
+    solver: str = "five_point"
 
 
 # the tagged PnP fitters: role -> (solver, sample size)
@@ -115,6 +127,13 @@ def _device_spec(model_fitter, inlier_scorer, model_fit_data_count):
         if k_fit is None or k_score is None or not np.array_equal(np.asarray(k_fit), np.asarray(k_score)):
             return None
         return PnPDeviceSpec(np.asarray(k_fit, dtype=np.float64), solver)
+    if (getattr(fit_fn, "_sfm_hip_role", None) == "five_point_fitter" and model_fit_data_count == 6
+            and getattr(score_fn, "_sfm_hip_role", None) == "sed_scorer"):
+        k_fit = model_fitter.keywords.get("camera_matrix") if not model_fitter.args else None
+        k_score = inlier_scorer.keywords.get("camera_matrix") if not inlier_scorer.args else None
+        if k_fit is None or k_score is None or not np.array_equal(np.asarray(k_fit), np.asarray(k_score)):
+            return None
+        return EssentialDeviceSpec(np.asarray(k_fit, dtype=np.float64))
     if model_fit_data_count != 8:
         return None
     if not getattr(fit_fn, "_sfm_hip_role", None) == "eight_point_fitter":

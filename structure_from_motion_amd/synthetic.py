@@ -193,3 +193,30 @@ def planar_pnp_scene(n: int, seed: int = 0, K: np.ndarray = BENCH_K, outlier_fra
     rand_px = np.column_stack([rng.uniform(0, 2 * K[0, 2], n), rng.uniform(0, 2 * K[1, 2], n)])
     uv = np.where(is_out[:, None], rand_px, uv)
     return np.column_stack([X, uv]), R, t, is_out
+
+
+def planar_two_view_scene(n: int, seed: int = 0, outlier_fraction: float = 0.3, noise_px: float = 0.5,
+                          K: np.ndarray = BENCH_K):
+    """Two views of points on one plane, z = 5 + 0.3 x - 0.2 y (x, y uniform in [-1, 1]), which the eight-point algorithm
+    cannot fit and the five-point solver can.  Camera 1 = [I|0]; camera 2 as in ``two_view_scene``; Gaussian pixel noise on
+    every projection and a fraction of image-2 points replaced by uniform random pixels.  Returns (pix_a (n,2),
+    pix_b (n,2), K, R, t, is_outlier, plane) with plane = (normal, d): normal . X = d for every point."""
+    rng = np.random.default_rng(seed)
+    x = rng.uniform(-1.0, 1.0, n)
+    y = rng.uniform(-1.0, 1.0, n)
+    X = np.column_stack([x, y, 5.0 + 0.3 * x - 0.2 * y])
+    R = rotation_xy(-5.0, -10.0)
+    t = np.array([0.5, 0.05, 0.1])
+
+    def project(Xc):
+        uvw = Xc @ K.T
+        return uvw[:, :2] / uvw[:, 2:3]
+
+    pa = project(X) + rng.normal(0.0, noise_px, (n, 2))
+    pb = project(X @ R.T + t) + rng.normal(0.0, noise_px, (n, 2))
+    is_out = rng.random(n) < outlier_fraction
+    width, height = 2.0 * K[0, 2], 2.0 * K[1, 2]
+    rand_px = np.column_stack([rng.uniform(0, width, n), rng.uniform(0, height, n)])
+    pb = np.where(is_out[:, None], rand_px, pb)
+    normal = np.array([-0.3, 0.2, 1.0])
+    return pa, pb, K, R, t, is_out, (normal, 5.0)
