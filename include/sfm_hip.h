@@ -56,7 +56,7 @@ typedef struct sfm_select_result {
 
 /* Version of this interface: libsfm_hip.so reports the one it was compiled from (sfm_abi_version), the Python binding
  * and the torch op library (sfm_torch_ops_abi_version) refuse a library of another version. */
-#define SFM_ABI_VERSION 14
+#define SFM_ABI_VERSION 15
 
 const char* sfm_last_error(void);
 int sfm_abi_version(void);
@@ -257,10 +257,11 @@ int sfm_ransac_pass_batch(uint64_t seed, const uint64_t* seed_dev, uint64_t seed
                           uint8_t* mask, void* workspace, int64_t workspace_bytes, void* stream, const sfm_score_options* options);
 
 /* Model selection (ransac.py:75-86): lowest aggregated error among hypotheses with
- * cnt >= min_extra, strict <, earliest index wins, NaN/inf never win.  result: dev [batch]. */
-int sfm_select_best(const int32_t* cnt, const double* s1, const double* s2, const int32_t* flags,
-                    int64_t h_count, int64_t batch, double min_extra, int aggregation, int64_t h_offset,
-                    sfm_select_result* result, void* stream);
+ * cnt >= min_extra, strict <, earliest index wins, NaN/inf never win.  sample_size: the items of a sample that enter
+ * the mean and RMS aggregates (count + sample_size): 8 (eight-point), 6 (five-point, PnP DLT) or 4 (P3P); SFM_EINVAL
+ * otherwise.  result: dev [batch]. */
+int sfm_select_best(const int32_t* cnt, const double* s1, const double* s2, const int32_t* flags, int64_t h_count, int64_t batch,
+                    double min_extra, int aggregation, int64_t h_offset, int sample_size, sfm_select_result* result, void* stream);
 
 /* Cross-shard selection for hypothesis-sharded RANSAC (one rank per GPU).  Each rank runs
  * sfm_select_best over its own block of hypotheses with h_offset = the block's first global index, the ranks
@@ -279,12 +280,11 @@ int sfm_fold_select_records_host(const sfm_select_result* gathered, int64_t worl
                                  sfm_select_result* global, int64_t* best_h, sfm_select_result* single);
 
 /* Inlier mask of the selected model: mask[b,i] = 1 if point i is a non-sample survivor, 2 if it is one of
- * the 8 sample points, 0 otherwise.  `result` as written by sfm_select_best with h_offset 0 (or with
- * best_h rewritten to a local index); entries with best_h < 0 leave their mask zeroed.
- * mask: dev uint8 [batch,n]. */
-int sfm_inlier_mask(const double* corr, int64_t n, const double* E, const int32_t* S, int64_t h_count,
-                    int64_t batch, const sfm_select_result* result, double thr, uint8_t* mask,
-                    void* stream);
+ * the sample_size sample points (the first sample_size entries of its row of S: 8 or 6; SFM_EINVAL otherwise), 0 otherwise.
+ * `result` as written by sfm_select_best with h_offset 0 (or with best_h rewritten to a local index); entries with
+ * best_h < 0 leave their mask zeroed.  mask: dev uint8 [batch,n]. */
+int sfm_inlier_mask(const double* corr, int64_t n, const double* E, const int32_t* S, int64_t h_count, int64_t batch,
+                    const sfm_select_result* result, double thr, int sample_size, uint8_t* mask, void* stream);
 
 /* ---- RANSAC absolute pose (PnP) of a further view against triangulated points (csrc/sfm_pnp.hip) ----
  * The reference's fit_with_ransac (ransac.py:55-86) with a six-item sample, a six-point DLT fitter and the squared
@@ -309,26 +309,27 @@ int sfm_pnp_sample_fit_philox(uint64_t seed, uint64_t seed_stride, int64_t h_beg
                               void* stream);
 
 /* Scoring of all n items under all hypotheses: e = (p0/c2 - u)^2 + (p1/c2 - v)^2 with c = R X + t, p = K c (operation order
- * fixed in sfm_pnp.hip), +inf when c2 <= 0.  cnt[b,h] = non-sample items with e <= thr; s1 / s2 = sums of e / e^2 over the
- * 6 sample items plus those survivors.  All fp64, exact divisions: the values are the host scorer's bit for bit. */
+ * fixed in sfm_pnp.hip), +inf when c2 <= 0.  The first sample_size entries of a row of S are the sample (6 for the DLT, 4 for
+ * P3P; SFM_EINVAL otherwise).  cnt[b,h] = non-sample items with e <= thr; s1 / s2 = sums of e / e^2 over the sample_size
+ * sample items plus those survivors.  All fp64, exact divisions: the values are the host scorer's bit for bit.  Selection:
+ * sfm_select_best with the same sample_size. */
 int sfm_pnp_score(const double* pts, int64_t n, const double* model, const int32_t* S, int64_t h_count, int64_t batch,
-                  const double* K, double thr, int32_t* cnt, double* s1, double* s2, void* stream);
+                  const double* K, double thr, int sample_size, int32_t* cnt, double* s1, double* s2, void* stream);
 
-/* sfm_select_best with a six-item sample in the mean and RMS aggregates (count + 6); same record, same rules. */
-int sfm_pnp_select_best(const int32_t* cnt, const double* s1, const double* s2, const int32_t* flags, int64_t h_count,
-                        int64_t batch, double min_extra, int aggregation, int64_t h_offset, sfm_select_result* result,
-                        void* stream);
-
-/* Inlier mask of the selected model: 2 for the 6 sample items, 1 for other items with e <= thr, 0 otherwise (all 0 when the
- * record holds no model).  `result` as written by sfm_pnp_select_best with h_offset 0.  mask: dev uint8 [batch,n]. */
+/* Inlier mask of the selected model: 2 for the sample_size (6 or 4) sample items, 1 for other items with e <= thr, 0 otherwise
+ * (all 0 when the record holds no model).  `result` as written by sfm_select_best with h_offset 0.  mask: dev uint8 [batch,n]. */
 int sfm_pnp_inlier_mask(const double* pts, int64_t n, const double* model, const int32_t* S, int64_t h_count, int64_t batch,
-                        const double* K, const sfm_select_result* result, double thr, uint8_t* mask, void* stream);
+                        const double* K, const sfm_select_result* result, double thr, int sample_size, uint8_t* mask, void* stream);
 
-/* One whole PnP pass: fit (use_philox: sampled in the fit launch as sfm_pnp_sample_fit_philox, else from S), scoring,
- * selection, and the mask when `mask` is not NULL — four launches, every size checked before the first. */
-int sfm_pnp_ransac_pass(uint64_t seed, uint64_t seed_stride, int use_philox, int64_t h_begin, const double* pts, int64_t n,
-                        int64_t h_count, int64_t batch, const double* K, double thr, double min_extra, int aggregation, int32_t* S,
-                        double* model, int32_t* flags, int32_t* cnt, double* s1, double* s2, sfm_select_result* result,
+#define SFM_PNP_SOLVER_DLT 0 /* six-point DLT, six-item samples */
+#define SFM_PNP_SOLVER_P3P 1 /* P3P, four-item samples; n >= 4 */
+
+/* One whole PnP pass with the fit of `solver` (use_philox: sampled in the fit launch as sfm_pnp_sample_fit_philox /
+ * sfm_p3p_sample_fit_philox, else from S), then the scoring, selection (sfm_select_best) and, when `mask` is not NULL, the
+ * mask of its sample size — every argument checked before the first launch. */
+int sfm_pnp_ransac_pass(int solver, uint64_t seed, uint64_t seed_stride, int use_philox, int64_t h_begin, const double* pts,
+                        int64_t n, int64_t h_count, int64_t batch, const double* K, double thr, double min_extra, int aggregation,
+                        int32_t* S, double* model, int32_t* flags, int32_t* cnt, double* s1, double* s2, sfm_select_result* result,
                         uint8_t* mask, void* stream);
 
 /* ---- P3P: the minimal solver of RANSAC PnP (csrc/sfm_p3p.h, csrc/sfm_pnp.hip; an extension, added under ABI 14) ----
@@ -346,25 +347,6 @@ int sfm_p3p_sample_fit_philox(uint64_t seed, uint64_t seed_stride, int64_t h_beg
                               int64_t h_count, int64_t batch, const double* K, int32_t* S, double* model, int32_t* flags,
                               void* stream);
 
-/* sfm_pnp_score, sfm_pnp_select_best and sfm_pnp_inlier_mask for a sample of sample_size items (4 or 6; SFM_EINVAL
- * otherwise): the first sample_size entries of S are the sample, the mean and RMS divide by count + sample_size. */
-int sfm_pnp_score_ex(const double* pts, int64_t n, const double* model, const int32_t* S, int64_t h_count, int64_t batch,
-                     const double* K, double thr, int sample_size, int32_t* cnt, double* s1, double* s2, void* stream);
-int sfm_pnp_select_best_ex(const int32_t* cnt, const double* s1, const double* s2, const int32_t* flags, int64_t h_count,
-                           int64_t batch, double min_extra, int aggregation, int64_t h_offset, int sample_size,
-                           sfm_select_result* result, void* stream);
-int sfm_pnp_inlier_mask_ex(const double* pts, int64_t n, const double* model, const int32_t* S, int64_t h_count, int64_t batch,
-                           const double* K, const sfm_select_result* result, double thr, int sample_size, uint8_t* mask,
-                           void* stream);
-
-#define SFM_PNP_SOLVER_DLT 0 /* six-point DLT, six-item samples (sfm_pnp_ransac_pass) */
-#define SFM_PNP_SOLVER_P3P 1 /* P3P, four-item samples; n >= 4 */
-
-/* sfm_pnp_ransac_pass with the fit of `solver` and the scoring, selection and mask of its sample size. */
-int sfm_pnp_ransac_pass_ex(int solver, uint64_t seed, uint64_t seed_stride, int use_philox, int64_t h_begin, const double* pts,
-                           int64_t n, int64_t h_count, int64_t batch, const double* K, double thr, double min_extra, int aggregation,
-                           int32_t* S, double* model, int32_t* flags, int32_t* cnt, double* s1, double* s2,
-                           sfm_select_result* result, uint8_t* mask, void* stream);
 
 /* ---- five-point essential matrix (csrc/sfm_five_point.hip; an extension, off unless asked for) ----
  * corr: dev [batch,n,4] K-normalised {xa, ya, xb, yb}; S: dev int32 [batch,h_count,8], the first 6 entries of a row are the
@@ -384,14 +366,10 @@ int sfm_five_point_sample_fit_philox(uint64_t seed, uint64_t seed_stride, int64_
 int sfm_five_point_candidates(const double* corr, int64_t n, const int32_t* S, int64_t h_count, int64_t batch, double* out,
                               int32_t* count, void* stream);
 
-/* sfm_score_sed (all-fp64 kernel), sfm_select_best and sfm_inlier_mask for samples of sample_size items (6 or 8; SFM_EINVAL
- * otherwise): the first sample_size entries of a row of S are the sample, the mean and RMS divide by count + sample_size. */
+/* sfm_score_sed (all-fp64 kernel) for samples of sample_size items (6 or 8; SFM_EINVAL otherwise): the first sample_size
+ * entries of a row of S are the sample (select and mask with the same sample_size). */
 int sfm_score_sed_sample_ex(const double* corr, int64_t n, const double* E, const int32_t* S, int64_t h_count, int64_t batch,
                             double thr, int sample_size, int32_t* cnt, double* s1, double* s2, void* stream);
-int sfm_select_best_ex(const int32_t* cnt, const double* s1, const double* s2, const int32_t* flags, int64_t h_count, int64_t batch,
-                       double min_extra, int aggregation, int64_t h_offset, int sample_size, sfm_select_result* result, void* stream);
-int sfm_inlier_mask_ex(const double* corr, int64_t n, const double* E, const int32_t* S, int64_t h_count, int64_t batch,
-                       const sfm_select_result* result, double thr, int sample_size, uint8_t* mask, void* stream);
 
 /* One five-point pass: fit (from S, or Philox-sampled with use_philox), six-item scoring, selection and (mask != NULL) the
  * winner's mask, as the separate calls above.  Every size is checked before the first launch. */

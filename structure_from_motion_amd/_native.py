@@ -12,12 +12,12 @@ LIB_PATH = os.path.join(HERE, "csrc", "libsfm_hip.so")
 
 SFM_OK = 0
 AGG_SUM, AGG_SQUARE, AGG_MEAN, AGG_RMS = 0, 1, 2, 3
-PNP_SOLVER_DLT, PNP_SOLVER_P3P = 0, 1   # SFM_PNP_SOLVER_* (sfm_pnp_ransac_pass_ex)
+PNP_SOLVER_DLT, PNP_SOLVER_P3P = 0, 1   # SFM_PNP_SOLVER_* (sfm_pnp_ransac_pass)
 FIT_DEGENERATE = 1
 MATCH_NCC, MATCH_SSD = 0, 1
 PATCH_PLAIN, PATCH_MEAN_REMOVED, PATCH_RAW64 = 0, 1, 2
 INT64_MAX = (1 << 63) - 1
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 
 def match_ssd_int(bits: int, signed: bool) -> int:
@@ -131,10 +131,10 @@ SIGNATURES = {
                               _P, _P, _P, _I64, _P, _P],
     "sfm_ransac_pass_batch": [_U64, _P, _U64, C.c_int, _I64, _P, _I64, _I64, _I64, _D, _D, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                               _I64, _P, _P],
-    "sfm_select_best": [_P, _P, _P, _P, _I64, _I64, _D, C.c_int, _I64, _P, _P],
+    "sfm_select_best": [_P, _P, _P, _P, _I64, _I64, _D, C.c_int, _I64, C.c_int, _P, _P],
     "sfm_fold_select_records": [_P, _I64, _I64, _P, _P, _P, _P],
     "sfm_fold_select_records_host": [_P, _I64, _I64, _P, _P, _P],
-    "sfm_inlier_mask": [_P, _I64, _P, _P, _I64, _I64, _P, _D, _P, _P],
+    "sfm_inlier_mask": [_P, _I64, _P, _P, _I64, _I64, _P, _D, C.c_int, _P, _P],
     "sfm_sed_values": [_P, _I64, _P, _P, _P],
     "sfm_cheirality": [_P, _I64, _P, _I64, _D, _P, _P],
     "sfm_triangulate": [_P, _I64, _P, _P, _P, _P],
@@ -157,26 +157,18 @@ SIGNATURES = {
     "sfm_score_kernel_choice": [_I64, _I64, _I64],
     "sfm_pnp_fit": [_P, _I64, _P, _I64, _I64, _P, _P, _P, _P],
     "sfm_pnp_sample_fit_philox": [_U64, _U64, _I64, _P, _I64, _I64, _I64, _P, _P, _P, _P, _P],
-    "sfm_pnp_score": [_P, _I64, _P, _P, _I64, _I64, _P, _D, _P, _P, _P, _P],
-    "sfm_pnp_select_best": [_P, _P, _P, _P, _I64, _I64, _D, C.c_int, _I64, _P, _P],
-    "sfm_pnp_inlier_mask": [_P, _I64, _P, _P, _I64, _I64, _P, _P, _D, _P, _P],
-    "sfm_pnp_ransac_pass": [_U64, _U64, C.c_int, _I64, _P, _I64, _I64, _I64, _P, _D, _D, C.c_int, _P, _P, _P, _P, _P, _P, _P,
-                            _P, _P],
+    "sfm_pnp_score": [_P, _I64, _P, _P, _I64, _I64, _P, _D, C.c_int, _P, _P, _P, _P],
+    "sfm_pnp_inlier_mask": [_P, _I64, _P, _P, _I64, _I64, _P, _P, _D, C.c_int, _P, _P],
+    "sfm_pnp_ransac_pass": [C.c_int, _U64, _U64, C.c_int, _I64, _P, _I64, _I64, _I64, _P, _D, _D, C.c_int, _P, _P, _P, _P, _P, _P,
+                            _P, _P, _P],
     "sfm_p3p_fit": [_P, _I64, _P, _I64, _I64, _P, _P, _P, _P],
     "sfm_p3p_sample_fit_philox": [_U64, _U64, _I64, _P, _I64, _I64, _I64, _P, _P, _P, _P, _P],
-    "sfm_pnp_score_ex": [_P, _I64, _P, _P, _I64, _I64, _P, _D, C.c_int, _P, _P, _P, _P],
-    "sfm_pnp_select_best_ex": [_P, _P, _P, _P, _I64, _I64, _D, C.c_int, _I64, C.c_int, _P, _P],
-    "sfm_pnp_inlier_mask_ex": [_P, _I64, _P, _P, _I64, _I64, _P, _P, _D, C.c_int, _P, _P],
     "sfm_five_point_fit": [_P, _I64, _P, _I64, _I64, _P, _P, _P],
     "sfm_five_point_sample_fit_philox": [_U64, _U64, _I64, _P, _I64, _I64, _I64, _P, _P, _P, _P],
     "sfm_five_point_candidates": [_P, _I64, _P, _I64, _I64, _P, _P, _P],
     "sfm_score_sed_sample_ex": [_P, _I64, _P, _P, _I64, _I64, _D, C.c_int, _P, _P, _P, _P],
-    "sfm_select_best_ex": [_P, _P, _P, _P, _I64, _I64, _D, C.c_int, _I64, C.c_int, _P, _P],
-    "sfm_inlier_mask_ex": [_P, _I64, _P, _P, _I64, _I64, _P, _D, C.c_int, _P, _P],
     "sfm_five_point_ransac_pass": [_U64, _U64, C.c_int, _I64, _P, _I64, _I64, _I64, _D, _D, C.c_int, _P, _P, _P, _P, _P, _P,
                                    _P, _P, _P],
-    "sfm_pnp_ransac_pass_ex": [C.c_int, _U64, _U64, C.c_int, _I64, _P, _I64, _I64, _I64, _P, _D, _D, C.c_int, _P, _P, _P, _P, _P,
-                               _P, _P, _P, _P],
     "sfm_pnp_refine": [_P, _I64, _I64, _P, _P, _P, _P, _D, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P],
     "sfm_bundle_adjust": [_P, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _I64, _P],
     "sfm_bundle_adjust_pcg": [_P, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, _D, _P, _P, _P, _P, _I64, _P],

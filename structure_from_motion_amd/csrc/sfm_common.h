@@ -62,6 +62,13 @@ inline unsigned grid_stride(int64_t work, int64_t block, int64_t cap) {
 
 constexpr int kWave = 64;
 
+// Sample index of a hypothesis, checked: an index outside [0, n) reads item 0 and flags the hypothesis.
+__device__ __forceinline__ int64_t checked_index(int32_t i, int64_t n, bool& bad) {
+    const bool out = i < 0 || (int64_t)i >= n;
+    bad = bad || out;
+    return out ? 0 : (int64_t)i;
+}
+
 // One correspondence in K-normalised coordinates: 32 bytes, read as two 16-byte loads.
 struct alignas(32) Corr {
     double xa, ya, xb, yb;

@@ -20,12 +20,6 @@ using sfmhost::grid_for;
 constexpr int kFiveSample = 6;   // five items solved for, the sixth picks the solution
 constexpr int kFitBlock = 64;
 
-SFM_DEVICE int64_t checked_index(int32_t i, int64_t n, bool& bad) {
-    const bool out = i < 0 || (int64_t)i >= n;
-    bad = bad || out;
-    return out ? 0 : (int64_t)i;
-}
-
 // The items of one sample; bad when an index is out of range.
 SFM_DEVICE void load_items(const Corr* __restrict__ pts, int64_t n, const int32_t (&idx)[8], double (&xa)[5], double (&ya)[5],
                            double (&xb)[5], double (&yb)[5], Corr& item5, bool& bad) {
@@ -209,9 +203,9 @@ int sfm_five_point_ransac_pass(uint64_t seed, uint64_t seed_stride, int use_phil
         rc = sfm_score_sed_sample_ex(corr, n, E, S, h_count, batch, thr, kFiveSample, cnt, s1, s2, stream);
         if (rc != SFM_OK) return rc;
     }
-    rc = sfm_select_best_ex(cnt, s1, s2, flags, h_count, batch, min_extra, aggregation, 0, kFiveSample, result, stream);
+    rc = sfm_select_best(cnt, s1, s2, flags, h_count, batch, min_extra, aggregation, 0, kFiveSample, result, stream);
     if (rc != SFM_OK || mask == nullptr) return rc;
-    return sfm_inlier_mask_ex(corr, n, E, S, h_count, batch, result, thr, kFiveSample, mask, stream);
+    return sfm_inlier_mask(corr, n, E, S, h_count, batch, result, thr, kFiveSample, mask, stream);
 }
 
 }  // extern "C"

@@ -1038,7 +1038,7 @@ MatrixPrep matrix_prep(const sfmhost::ScorePlan& plan, int step_blocks) {
     return MatrixPrep{plan.partial, (int)plan.matrix.setup_blocks, plan.a_scale, plan.thr, plan.hyp_table, plan.fix, plan.table, step_blocks};
 }
 
-// The launches of sfm_select_best / sfm_select_best_ex for SAMPLE-item samples (8: exactly the launches of the eight-point path).
+// The launches of sfm_select_best for SAMPLE-item samples (8: the eight-point fit, 6: five-point and DLT, 4: P3P).
 template <int SAMPLE>
 int select_best_launch(const int32_t* cnt, const double* s1, const double* s2, const int32_t* flags, int64_t h_count, int64_t batch,
                        double min_extra, int aggregation, int64_t h_offset, sfm_select_result* result, void* stream) {
@@ -1067,7 +1067,7 @@ int select_best_launch(const int32_t* cnt, const double* s1, const double* s2, c
     return check_launch("select_best_kernel");
 }
 
-// The launch of sfm_inlier_mask / sfm_inlier_mask_ex for SAMPLE-item samples.
+// The launch of sfm_inlier_mask for SAMPLE-item samples.
 template <int SAMPLE>
 int inlier_mask_launch(const double* corr, int64_t n, const double* E, const int32_t* S, int64_t h_count, int64_t batch,
                        const sfm_select_result* result, double thr, uint8_t* mask, void* stream) {
@@ -1260,9 +1260,9 @@ int sfm_ransac_pass_large(uint64_t seed, const uint64_t* seed_dev, int use_philo
     rc = sfmhost::launch_large_score(plan, io, select_state, /*fold_in_selection=*/state_fits);
     if (rc != SFM_OK) return rc;
     if (!state_fits) {   // a few hundred hypotheses: the separate selection and mask launches
-        rc = sfm_select_best(cnt, s1, s2, flags, h_count, 1, min_extra, aggregation, h_offset, result, stream);
+        rc = sfm_select_best(cnt, s1, s2, flags, h_count, 1, min_extra, aggregation, h_offset, 8, result, stream);
         if (rc != SFM_OK || mask == nullptr) return rc;
-        return sfm_inlier_mask(corr, n, E, S, h_count, 1, result, thr, mask, stream);
+        return sfm_inlier_mask(corr, n, E, S, h_count, 1, result, thr, 8, mask, stream);
     }
     // last launch: fold of the ranges + selection over up to 256 blocks + (behind them) the blocks that write the winner's mask
     const int select_blocks = (int)std::min<int64_t>(kLargeSelectBlocks, (h_count + 511) / 512);
@@ -1346,32 +1346,21 @@ int sfm_hartley_normalize(const double* coords, int64_t n, double* out, void* st
     return check_launch("hartley_normalize_kernel");
 }
 
-int sfm_select_best(const int32_t* cnt, const double* s1, const double* s2, const int32_t* flags,
-                    int64_t h_count, int64_t batch, double min_extra, int aggregation, int64_t h_offset,
-                    sfm_select_result* result, void* stream) {
-    return select_best_launch<8>(cnt, s1, s2, flags, h_count, batch, min_extra, aggregation, h_offset, result, stream);
+int sfm_select_best(const int32_t* cnt, const double* s1, const double* s2, const int32_t* flags, int64_t h_count, int64_t batch,
+                    double min_extra, int aggregation, int64_t h_offset, int sample_size, sfm_select_result* result, void* stream) {
+    switch (sample_size) {
+        case 4: return select_best_launch<4>(cnt, s1, s2, flags, h_count, batch, min_extra, aggregation, h_offset, result, stream);
+        case 6: return select_best_launch<6>(cnt, s1, s2, flags, h_count, batch, min_extra, aggregation, h_offset, result, stream);
+        case 8: return select_best_launch<8>(cnt, s1, s2, flags, h_count, batch, min_extra, aggregation, h_offset, result, stream);
+    }
+    return fail(SFM_EINVAL, "sfm_select_best: sample_size must be 4, 6 or 8");
 }
 
-int sfm_select_best_ex(const int32_t* cnt, const double* s1, const double* s2, const int32_t* flags, int64_t h_count, int64_t batch,
-                       double min_extra, int aggregation, int64_t h_offset, int sample_size, sfm_select_result* result, void* stream) {
-    if (sample_size == 6)
-        return select_best_launch<6>(cnt, s1, s2, flags, h_count, batch, min_extra, aggregation, h_offset, result, stream);
-    if (sample_size == 8)
-        return select_best_launch<8>(cnt, s1, s2, flags, h_count, batch, min_extra, aggregation, h_offset, result, stream);
-    return fail(SFM_EINVAL, "sfm_select_best_ex: sample_size must be 6 or 8");
-}
-
-int sfm_inlier_mask(const double* corr, int64_t n, const double* E, const int32_t* S, int64_t h_count,
-                    int64_t batch, const sfm_select_result* result, double thr, uint8_t* mask,
-                    void* stream) {
-    return inlier_mask_launch<8>(corr, n, E, S, h_count, batch, result, thr, mask, stream);
-}
-
-int sfm_inlier_mask_ex(const double* corr, int64_t n, const double* E, const int32_t* S, int64_t h_count, int64_t batch,
-                       const sfm_select_result* result, double thr, int sample_size, uint8_t* mask, void* stream) {
+int sfm_inlier_mask(const double* corr, int64_t n, const double* E, const int32_t* S, int64_t h_count, int64_t batch,
+                    const sfm_select_result* result, double thr, int sample_size, uint8_t* mask, void* stream) {
     if (sample_size == 6) return inlier_mask_launch<6>(corr, n, E, S, h_count, batch, result, thr, mask, stream);
     if (sample_size == 8) return inlier_mask_launch<8>(corr, n, E, S, h_count, batch, result, thr, mask, stream);
-    return fail(SFM_EINVAL, "sfm_inlier_mask_ex: sample_size must be 6 or 8");
+    return fail(SFM_EINVAL, "sfm_inlier_mask: sample_size must be 6 or 8");
 }
 
 int sfm_sed_values(const double* corr, int64_t n, const double* E, double* out, void* stream) {

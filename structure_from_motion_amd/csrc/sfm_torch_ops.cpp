@@ -353,7 +353,7 @@ void ransac_pass_large_out(const Tensor& corr, int64_t seed, const std::optional
 
 // ---- select_best -----------------------------------------------------------------------------------------------
 void select_best_out(const Tensor& cnt, const Tensor& s1, const Tensor& s2, const std::optional<Tensor>& flags,
-                     double min_extra, int64_t aggregation, int64_t h_offset, Tensor& result) {
+                     double min_extra, int64_t aggregation, int64_t h_offset, Tensor& result, int64_t sample_size) {
     const OpDevice scope(cnt);
     need(cnt, "cnt", at::kInt);
     need(s1, "s1", at::kDouble);
@@ -364,28 +364,28 @@ void select_best_out(const Tensor& cnt, const Tensor& s1, const Tensor& s2, cons
                 "sfm_hip: cnt, s1, s2 must be [batch, h]");
     TORCH_CHECK(result.numel() == cnt.size(0) * kRecordWords, "sfm_hip: result must be int64 [batch, 5]");
     ok(sfm_select_best(ptr<int32_t>(cnt), ptr<double>(s1), ptr<double>(s2), ptr<int32_t>(flags), cnt.size(1),
-                       cnt.size(0), min_extra, (int)aggregation, h_offset,
+                       cnt.size(0), min_extra, (int)aggregation, h_offset, (int)sample_size,
                        reinterpret_cast<sfm_select_result*>(ptr<int64_t>(result)), current_stream()),
        "sfm_select_best");
 }
 
 Tensor select_best(const Tensor& cnt, const Tensor& s1, const Tensor& s2, const std::optional<Tensor>& flags,
-                   double min_extra, int64_t aggregation, int64_t h_offset) {
+                   double min_extra, int64_t aggregation, int64_t h_offset, int64_t sample_size) {
     TORCH_CHECK(cnt.dim() == 2, "sfm_hip: cnt must be [batch, h]");
     Tensor result = at::empty({cnt.size(0), kRecordWords}, like(cnt, at::kLong));
-    select_best_out(cnt, s1, s2, flags, min_extra, aggregation, h_offset, result);
+    select_best_out(cnt, s1, s2, flags, min_extra, aggregation, h_offset, result, sample_size);
     return result;
 }
 
 Tensor select_best_meta(const Tensor& cnt, const Tensor&, const Tensor&, const std::optional<Tensor>&, double, int64_t,
-                        int64_t) {
+                        int64_t, int64_t) {
     TORCH_CHECK(cnt.dim() == 2, "sfm_hip: cnt must be [batch, h]");
     return at::empty_symint({cnt.sym_size(0), kRecordWords}, like(cnt, at::kLong));
 }
 
 // ---- inlier_mask -----------------------------------------------------------------------------------------------
 void inlier_mask_out(const Tensor& corr, const Tensor& E, const Tensor& S, const Tensor& result, double thr,
-                     Tensor& mask) {
+                     Tensor& mask, int64_t sample_size) {
     const OpDevice scope(corr);
     need(corr, "corr", at::kDouble);
     need(E, "E", at::kDouble);
@@ -397,19 +397,19 @@ void inlier_mask_out(const Tensor& corr, const Tensor& E, const Tensor& S, const
     TORCH_CHECK(result.numel() == d.batch * kRecordWords, "sfm_hip: result must be int64 [batch, 5]");
     TORCH_CHECK(mask.numel() == d.batch * d.n, "sfm_hip: mask must be uint8 [batch, n]");
     ok(sfm_inlier_mask(ptr<double>(corr), d.n, ptr<double>(E), ptr<int32_t>(S), d.h, d.batch,
-                       reinterpret_cast<const sfm_select_result*>(ptr<int64_t>(result)), thr, ptr<uint8_t>(mask),
-                       current_stream()),
+                       reinterpret_cast<const sfm_select_result*>(ptr<int64_t>(result)), thr, (int)sample_size,
+                       ptr<uint8_t>(mask), current_stream()),
        "sfm_inlier_mask");
 }
 
-Tensor inlier_mask(const Tensor& corr, const Tensor& E, const Tensor& S, const Tensor& result, double thr) {
+Tensor inlier_mask(const Tensor& corr, const Tensor& E, const Tensor& S, const Tensor& result, double thr, int64_t sample_size) {
     const Dims d = corr_dims(corr);
     Tensor mask = at::empty({d.batch, d.n}, like(corr, at::kByte));
-    inlier_mask_out(corr, E, S, result, thr, mask);
+    inlier_mask_out(corr, E, S, result, thr, mask, sample_size);
     return mask;
 }
 
-Tensor inlier_mask_meta(const Tensor& corr, const Tensor&, const Tensor&, const Tensor&, double) {
+Tensor inlier_mask_meta(const Tensor& corr, const Tensor&, const Tensor&, const Tensor&, double, int64_t) {
     TORCH_CHECK(corr.dim() == 3, "sfm_hip: corr must be [batch, n, 4]");
     return at::empty_symint({corr.sym_size(0), corr.sym_size(1)}, like(corr, at::kByte));
 }
@@ -529,7 +529,7 @@ std::tuple<Tensor, Tensor> pnp_fit_meta(const Tensor& pts, const Tensor& S, at::
 }
 
 void pnp_score_out(const Tensor& pts, const Tensor& model, const Tensor& S, at::ArrayRef<double> K, double thr, Tensor& cnt,
-                   Tensor& s1, Tensor& s2) {
+                   Tensor& s1, Tensor& s2, int64_t sample_size) {
     const OpDevice scope(pts);
     need(pts, "pts", at::kDouble);
     need(model, "model", at::kDouble);
@@ -542,48 +542,34 @@ void pnp_score_out(const Tensor& pts, const Tensor& model, const Tensor& S, at::
     check_model(model, d);
     TORCH_CHECK(cnt.numel() == d.batch * d.h && s1.numel() == d.batch * d.h && s2.numel() == d.batch * d.h,
                 "sfm_hip: cnt, s1, s2 must be [batch, h]");
-    ok(sfm_pnp_score(ptr<double>(pts), d.n, ptr<double>(model), ptr<int32_t>(S), d.h, d.batch, K.data(), thr, ptr<int32_t>(cnt),
-                     ptr<double>(s1), ptr<double>(s2), current_stream()),
+    ok(sfm_pnp_score(ptr<double>(pts), d.n, ptr<double>(model), ptr<int32_t>(S), d.h, d.batch, K.data(), thr, (int)sample_size,
+                     ptr<int32_t>(cnt), ptr<double>(s1), ptr<double>(s2), current_stream()),
        "sfm_pnp_score");
 }
 
 std::tuple<Tensor, Tensor, Tensor> pnp_score(const Tensor& pts, const Tensor& model, const Tensor& S, at::ArrayRef<double> K,
-                                             double thr) {
+                                             double thr, int64_t sample_size) {
     const Dims d = pnp_dims(pts, S);
     Tensor cnt = at::empty({d.batch, d.h}, like(pts, at::kInt));
     Tensor s1 = at::empty({d.batch, d.h}, like(pts, at::kDouble));
     Tensor s2 = at::empty({d.batch, d.h}, like(pts, at::kDouble));
-    pnp_score_out(pts, model, S, K, thr, cnt, s1, s2);
+    pnp_score_out(pts, model, S, K, thr, cnt, s1, s2, sample_size);
     return {cnt, s1, s2};
 }
 
 std::tuple<Tensor, Tensor, Tensor> pnp_score_meta(const Tensor& pts, const Tensor&, const Tensor& S, at::ArrayRef<double>,
-                                                  double) {
+                                                  double, int64_t) {
     TORCH_CHECK(pts.dim() == 3 && S.dim() == 3, "sfm_hip: pts [batch, n, 5], S [batch, h, 8]");
     return {at::empty_symint({pts.sym_size(0), S.sym_size(1)}, like(pts, at::kInt)),
             at::empty_symint({pts.sym_size(0), S.sym_size(1)}, like(pts, at::kDouble)),
             at::empty_symint({pts.sym_size(0), S.sym_size(1)}, like(pts, at::kDouble))};
 }
 
-void pass_checks(const Tensor& pts, Tensor& S, Tensor& model, Tensor& flags, Tensor& cnt, Tensor& s1, Tensor& s2, Tensor& result,
-                 const std::optional<Tensor>& mask, at::ArrayRef<double> K);
-
-// the whole P3P pass (sfm_pnp_ransac_pass_ex with SFM_PNP_SOLVER_P3P): the arguments of pnp_ransac_pass_
-void p3p_ransac_pass_out(const Tensor& pts, int64_t seed, int64_t seed_stride, bool use_philox, int64_t h_begin,
-                         at::ArrayRef<double> K, double thr, double min_extra, int64_t aggregation, Tensor& S, Tensor& model,
-                         Tensor& flags, Tensor& cnt, Tensor& s1, Tensor& s2, Tensor& result, const std::optional<Tensor>& mask) {
+// the whole pass of `solver` into the caller's buffers (device.PnPWorkspace); `mask` optional
+void pnp_pass(int solver, const Tensor& pts, int64_t seed, int64_t seed_stride, bool use_philox, int64_t h_begin,
+              at::ArrayRef<double> K, double thr, double min_extra, int64_t aggregation, Tensor& S, Tensor& model, Tensor& flags,
+              Tensor& cnt, Tensor& s1, Tensor& s2, Tensor& result, const std::optional<Tensor>& mask) {
     const OpDevice scope(pts);
-    pass_checks(pts, S, model, flags, cnt, s1, s2, result, mask, K);
-    const Dims d = pnp_dims(pts, S);
-    ok(sfm_pnp_ransac_pass_ex(SFM_PNP_SOLVER_P3P, (uint64_t)seed, (uint64_t)seed_stride, use_philox ? 1 : 0, h_begin, ptr<double>(pts),
-                              d.n, d.h, d.batch, K.data(), thr, min_extra, (int)aggregation, ptr<int32_t>(S), ptr<double>(model),
-                              ptr<int32_t>(flags), ptr<int32_t>(cnt), ptr<double>(s1), ptr<double>(s2),
-                              reinterpret_cast<sfm_select_result*>(ptr<int64_t>(result)), ptr<uint8_t>(mask), current_stream()),
-       "sfm_pnp_ransac_pass_ex");
-}
-
-void pass_checks(const Tensor& pts, Tensor& S, Tensor& model, Tensor& flags, Tensor& cnt, Tensor& s1, Tensor& s2, Tensor& result,
-                 const std::optional<Tensor>& mask, at::ArrayRef<double> K) {
     need(pts, "pts", at::kDouble);
     need(S, "S", at::kInt);
     need(model, "model", at::kDouble);
@@ -601,35 +587,26 @@ void pass_checks(const Tensor& pts, Tensor& S, Tensor& model, Tensor& flags, Ten
                 "sfm_hip: flags, cnt, s1, s2 must be [batch, h]");
     TORCH_CHECK(result.numel() == d.batch * kRecordWords, "sfm_hip: result must be int64 [batch, 5]");
     TORCH_CHECK(!mask.has_value() || mask->numel() == d.batch * d.n, "sfm_hip: mask must be uint8 [batch, n]");
+    ok(sfm_pnp_ransac_pass(solver, (uint64_t)seed, (uint64_t)seed_stride, use_philox ? 1 : 0, h_begin, ptr<double>(pts), d.n, d.h,
+                           d.batch, K.data(), thr, min_extra, (int)aggregation, ptr<int32_t>(S), ptr<double>(model),
+                           ptr<int32_t>(flags), ptr<int32_t>(cnt), ptr<double>(s1), ptr<double>(s2),
+                           reinterpret_cast<sfm_select_result*>(ptr<int64_t>(result)), ptr<uint8_t>(mask), current_stream()),
+       "sfm_pnp_ransac_pass");
 }
 
-// the whole pass into the caller's buffers (device.PnPWorkspace); `mask` optional
 void pnp_ransac_pass_out(const Tensor& pts, int64_t seed, int64_t seed_stride, bool use_philox, int64_t h_begin,
                          at::ArrayRef<double> K, double thr, double min_extra, int64_t aggregation, Tensor& S, Tensor& model,
                          Tensor& flags, Tensor& cnt, Tensor& s1, Tensor& s2, Tensor& result, const std::optional<Tensor>& mask) {
-    const OpDevice scope(pts);
-    need(pts, "pts", at::kDouble);
-    need(S, "S", at::kInt);
-    need(model, "model", at::kDouble);
-    need(flags, "flags", at::kInt);
-    need(cnt, "cnt", at::kInt);
-    need(s1, "s1", at::kDouble);
-    need(s2, "s2", at::kDouble);
-    need(result, "result", at::kLong);
-    if (mask.has_value()) need(*mask, "mask", at::kByte);
-    check_K(K);
-    const Dims d = pnp_dims(pts, S);
-    check_model(model, d);
-    TORCH_CHECK(flags.numel() == d.batch * d.h && cnt.numel() == d.batch * d.h && s1.numel() == d.batch * d.h &&
-                    s2.numel() == d.batch * d.h,
-                "sfm_hip: flags, cnt, s1, s2 must be [batch, h]");
-    TORCH_CHECK(result.numel() == d.batch * kRecordWords, "sfm_hip: result must be int64 [batch, 5]");
-    TORCH_CHECK(!mask.has_value() || mask->numel() == d.batch * d.n, "sfm_hip: mask must be uint8 [batch, n]");
-    ok(sfm_pnp_ransac_pass((uint64_t)seed, (uint64_t)seed_stride, use_philox ? 1 : 0, h_begin, ptr<double>(pts), d.n, d.h, d.batch,
-                           K.data(), thr, min_extra, (int)aggregation, ptr<int32_t>(S), ptr<double>(model), ptr<int32_t>(flags),
-                           ptr<int32_t>(cnt), ptr<double>(s1), ptr<double>(s2),
-                           reinterpret_cast<sfm_select_result*>(ptr<int64_t>(result)), ptr<uint8_t>(mask), current_stream()),
-       "sfm_pnp_ransac_pass");
+    pnp_pass(SFM_PNP_SOLVER_DLT, pts, seed, seed_stride, use_philox, h_begin, K, thr, min_extra, aggregation, S, model, flags, cnt, s1,
+             s2, result, mask);
+}
+
+// the P3P pass: the arguments of pnp_ransac_pass_
+void p3p_ransac_pass_out(const Tensor& pts, int64_t seed, int64_t seed_stride, bool use_philox, int64_t h_begin,
+                         at::ArrayRef<double> K, double thr, double min_extra, int64_t aggregation, Tensor& S, Tensor& model,
+                         Tensor& flags, Tensor& cnt, Tensor& s1, Tensor& s2, Tensor& result, const std::optional<Tensor>& mask) {
+    pnp_pass(SFM_PNP_SOLVER_P3P, pts, seed, seed_stride, use_philox, h_begin, K, thr, min_extra, aggregation, S, model, flags, cnt, s1,
+             s2, result, mask);
 }
 
 // refinement of a winner on its inliers (sfm_pnp_refine.hip): model [batch, 12], mask uint8 [batch, n], err [batch];
@@ -916,11 +893,11 @@ TORCH_LIBRARY(sfm_hip, m) {
           "float min_extra, int aggregation, int h_offset, Tensor(a!) S, Tensor(b!) E, Tensor(c!) flags, Tensor(d!) cnt, "
           "Tensor(e!) s1, Tensor(f!) s2, Tensor(g!) result, Tensor(h!)? mask, Tensor(i!) workspace) -> ()");
     m.def("select_best(Tensor cnt, Tensor s1, Tensor s2, Tensor? flags, float min_extra, int aggregation, "
-          "int h_offset=0) -> Tensor");
+          "int h_offset=0, int sample_size=8) -> Tensor");
     m.def("select_best_(Tensor cnt, Tensor s1, Tensor s2, Tensor? flags, float min_extra, int aggregation, "
-          "int h_offset, Tensor(a!) result) -> ()");
-    m.def("inlier_mask(Tensor corr, Tensor E, Tensor S, Tensor result, float thr) -> Tensor");
-    m.def("inlier_mask_(Tensor corr, Tensor E, Tensor S, Tensor result, float thr, Tensor(a!) mask) -> ()");
+          "int h_offset, Tensor(a!) result, int sample_size=8) -> ()");
+    m.def("inlier_mask(Tensor corr, Tensor E, Tensor S, Tensor result, float thr, int sample_size=8) -> Tensor");
+    m.def("inlier_mask_(Tensor corr, Tensor E, Tensor S, Tensor result, float thr, Tensor(a!) mask, int sample_size=8) -> ()");
     m.def("cheirality(Tensor corr, Tensor pose_rt, float distance_threshold) -> Tensor");
     m.def("triangulate(Tensor corr, Tensor P1, Tensor P2) -> Tensor");
     m.def("five_point_fit(Tensor corr, Tensor S) -> (Tensor, Tensor)");
@@ -932,9 +909,9 @@ TORCH_LIBRARY(sfm_hip, m) {
     m.def("pnp_fit_(Tensor pts, Tensor S, float[] K, Tensor(a!) model, Tensor(b!) flags) -> ()");
     m.def("p3p_fit(Tensor pts, Tensor S, float[] K) -> (Tensor, Tensor)");
     m.def("p3p_fit_(Tensor pts, Tensor S, float[] K, Tensor(a!) model, Tensor(b!) flags) -> ()");
-    m.def("pnp_score(Tensor pts, Tensor model, Tensor S, float[] K, float thr) -> (Tensor, Tensor, Tensor)");
+    m.def("pnp_score(Tensor pts, Tensor model, Tensor S, float[] K, float thr, int sample_size=6) -> (Tensor, Tensor, Tensor)");
     m.def("pnp_score_(Tensor pts, Tensor model, Tensor S, float[] K, float thr, Tensor(a!) cnt, Tensor(b!) s1, "
-          "Tensor(c!) s2) -> ()");
+          "Tensor(c!) s2, int sample_size=6) -> ()");
     m.def("pnp_ransac_pass_(Tensor pts, int seed, int seed_stride, bool use_philox, int h_begin, float[] K, float thr, "
           "float min_extra, int aggregation, Tensor(a!) S, Tensor(b!) model, Tensor(c!) flags, Tensor(d!) cnt, Tensor(e!) s1, "
           "Tensor(f!) s2, Tensor(g!) result, Tensor(h!)? mask) -> ()");
@@ -1015,10 +992,11 @@ void ransac_pass_small_out_meta(const Tensor&, int64_t, const std::optional<Tens
                                 int64_t, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&,
                                 const std::optional<Tensor>&, Tensor&) {}
 void select_best_out_meta(const Tensor&, const Tensor&, const Tensor&, const std::optional<Tensor>&, double, int64_t,
-                          int64_t, Tensor&) {}
-void inlier_mask_out_meta(const Tensor&, const Tensor&, const Tensor&, const Tensor&, double, Tensor&) {}
+                          int64_t, Tensor&, int64_t) {}
+void inlier_mask_out_meta(const Tensor&, const Tensor&, const Tensor&, const Tensor&, double, Tensor&, int64_t) {}
 void pnp_fit_out_meta(const Tensor&, const Tensor&, at::ArrayRef<double>, Tensor&, Tensor&) {}
-void pnp_score_out_meta(const Tensor&, const Tensor&, const Tensor&, at::ArrayRef<double>, double, Tensor&, Tensor&, Tensor&) {}
+void pnp_score_out_meta(const Tensor&, const Tensor&, const Tensor&, at::ArrayRef<double>, double, Tensor&, Tensor&, Tensor&,
+                        int64_t) {}
 void pnp_ransac_pass_out_meta(const Tensor&, int64_t, int64_t, bool, int64_t, at::ArrayRef<double>, double, double, int64_t, Tensor&,
                               Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, const std::optional<Tensor>&) {}
 void pnp_refine_out_meta(const Tensor&, const Tensor&, const Tensor&, const Tensor&, at::ArrayRef<double>, double, int64_t, int64_t,

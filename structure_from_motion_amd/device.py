@@ -18,6 +18,7 @@ import torch
 
 from . import _native, ops
 from ._native import ScoreOptions, SelectResult, check  # noqa: F401  (ScoreOptions: re-exported for callers and tests)
+from .ransac.ransac import solver_sample_size
 
 F64 = torch.float64
 SELECT_BYTES = C.sizeof(SelectResult)
@@ -372,38 +373,21 @@ def large_pass_eligible(batch: int, n: int, h: int) -> bool:
 
 
 def select_best(cnt, s1, s2, flags, min_extra: float, aggregation: int, h_offset: int = 0, out=None, sample_size: int = 8):
-    """-> int64 tensor [B,5] viewing the sfm_select_result records.  ``sample_size``: items of a sample in the mean / RMS (8, or 6
-    for the five-point fit: ``sfm_select_best_ex``)."""
-    if sample_size != 8:
-        B, H = cnt.shape
-        if out is None:
-            out = torch.empty((B, SELECT_BYTES // 8), dtype=torch.int64, device=cnt.device)
-        with torch.cuda.device(cnt.device):
-            check(_native.load().sfm_select_best_ex(_ptr(cnt), _ptr(s1), _ptr(s2), _ptr(flags), H, B, float(min_extra),
-                                                    int(aggregation), h_offset, int(sample_size), _ptr(out), _stream()),
-                  "sfm_select_best_ex")
-        return out
+    """-> int64 tensor [B,5] viewing the sfm_select_result records.  ``sample_size``: items of a sample in the mean / RMS (8 for
+    the eight-point fit, 6 for the five-point fit and the DLT, 4 for P3P)."""
     op = ops.load()
     if out is None:
-        return op.select_best(cnt, s1, s2, flags, float(min_extra), int(aggregation), h_offset)
-    op.select_best_(cnt, s1, s2, flags, float(min_extra), int(aggregation), h_offset, out)
+        return op.select_best(cnt, s1, s2, flags, float(min_extra), int(aggregation), h_offset, int(sample_size))
+    op.select_best_(cnt, s1, s2, flags, float(min_extra), int(aggregation), h_offset, out, int(sample_size))
     return out
 
 
 def inlier_mask(corr, E, S, result, thr: float, out=None, sample_size: int = 8):
     """uint8 [B,N]: 2 on the winner's ``sample_size`` sample items (8, or 6 for the five-point fit), 1 other inlier, 0 outlier."""
-    if sample_size != 8:
-        B, N, _ = corr.shape
-        if out is None:
-            out = torch.empty((B, N), dtype=torch.uint8, device=corr.device)
-        with torch.cuda.device(corr.device):
-            check(_native.load().sfm_inlier_mask_ex(_ptr(corr), N, _ptr(E), _ptr(S), S.shape[1], B, _ptr(result), float(thr),
-                                                    int(sample_size), _ptr(out), _stream()), "sfm_inlier_mask_ex")
-        return out
     op = ops.load()
     if out is None:
-        return op.inlier_mask(corr, E, S, result, float(thr))
-    op.inlier_mask_(corr, E, S, result, float(thr), out)
+        return op.inlier_mask(corr, E, S, result, float(thr), int(sample_size))
+    op.inlier_mask_(corr, E, S, result, float(thr), out, int(sample_size))
     return out
 
 
@@ -427,16 +411,6 @@ def read_refine_info(info: torch.Tensor):
     raw = info.cpu().numpy()
     return [(float(raw[i, 0:1].view(np.float64)[0]), int(raw[i, 1] & 0xFFFFFFFF), int(raw[i, 1] >> 32))
             for i in range(raw.shape[0])]
-
-
-E_SOLVERS = {"eight_point": 8, "five_point": 6}   # sample size of each essential-matrix solver (RansacWorkspace.run)
-
-
-def check_e_solver(solver: str) -> int:
-    """Sample size of an essential-matrix solver; ``ValueError`` for an unknown one."""
-    if solver not in E_SOLVERS:
-        raise ValueError(f"unknown essential-matrix solver {solver!r}: expected one of {sorted(E_SOLVERS)}")
-    return E_SOLVERS[solver]
 
 
 def five_point_fit(corr: torch.Tensor, S: torch.Tensor, E=None, flags=None, philox=None):
@@ -631,7 +605,7 @@ class RansacWorkspace:
         self.mask = torch.empty((batch, n), dtype=torch.uint8, device=dev)
         self.score_ws = score_workspace(n, h, batch, dev)   # (for the process-wide options of this moment: see _fit_workspace)
         self.frozen = False   # set by ShardedRansac.capture: the buffers' addresses are baked into a graph
-        self.sample_size = E_SOLVERS["eight_point"]   # of the last pass (outcome reads it)
+        self.sample_size = solver_sample_size("essential", "eight_point")   # of the last pass (outcome reads it)
 
     def _fit_workspace(self, options: Optional[ScoreOptions]) -> None:
         """The scoring workspace is sized by what a call launches: other options (per call, or process-wide defaults changed
@@ -651,7 +625,7 @@ class RansacWorkspace:
         ``self.S``); ``seed`` may be an int64 device tensor (read at kernel run time).  ``options``: launch options of the
         scoring launch of THIS pass (timing events included); default: the process-wide set.  ``solver="five_point"``: the
         five-point fit on six-item samples (``sfm_five_point_ransac_pass``; an int seed, h_offset 0, no launch options)."""
-        self.sample_size = check_e_solver(solver)
+        self.sample_size = solver_sample_size("essential", solver)
         if solver == "five_point":
             if h_offset != 0 or options is not None or isinstance(philox and philox[0], torch.Tensor):
                 raise ValueError("RansacWorkspace.run(solver='five_point'): h_offset, options and a device seed are not supported")
@@ -754,64 +728,27 @@ def p3p_fit(pts: torch.Tensor, S: torch.Tensor, K, model=None, flags=None):
     return model, flags
 
 
-def _pnp_camera(K):
-    Kc = (C.c_double * 9)(*_camera_list(K))
-    return Kc, C.cast(Kc, C.c_void_p)
-
-
 def pnp_score(pts: torch.Tensor, model: torch.Tensor, S: torch.Tensor, K, thr: float, cnt=None, s1=None, s2=None,
               sample_size: int = 6):
     """Per hypothesis (extra-inlier count, sum e, sum e^2) of the squared reprojection error e; the first ``sample_size``
-    (6 or 4) entries of each row of S are the sample."""
-    if sample_size != 6:
-        B, N, _ = pts.shape
-        H = S.shape[1]
-        if cnt is None:
-            cnt = torch.empty((B, H), dtype=torch.int32, device=pts.device)
-            s1 = torch.empty((B, H), dtype=F64, device=pts.device)
-            s2 = torch.empty((B, H), dtype=F64, device=pts.device)
-        Kc, Kp = _pnp_camera(K)
-        check(_native.load().sfm_pnp_score_ex(_ptr(pts), N, _ptr(model), _ptr(S), H, B, Kp, float(thr), int(sample_size),
-                                              _ptr(cnt), _ptr(s1), _ptr(s2), _stream()), "sfm_pnp_score_ex")
-        return cnt, s1, s2
+    (6 or 4) entries of each row of S are the sample.  Selection: ``select_best`` with the same ``sample_size``."""
     op = ops.load()
     if cnt is None and s1 is None and s2 is None:
-        return op.pnp_score(pts, model, S, _camera_list(K), float(thr))
-    op.pnp_score_(pts, model, S, _camera_list(K), float(thr), cnt, s1, s2)
+        return op.pnp_score(pts, model, S, _camera_list(K), float(thr), int(sample_size))
+    op.pnp_score_(pts, model, S, _camera_list(K), float(thr), cnt, s1, s2, int(sample_size))
     return cnt, s1, s2
-
-
-def pnp_select_best(cnt, s1, s2, flags, min_extra: float, aggregation: int, h_offset: int = 0, out=None, sample_size: int = 6):
-    """sfm_pnp_select_best (``sample_size``-item samples in the mean, 6 or 4) -> int64 tensor [B,5] viewing sfm_select_result
-    records."""
-    lib = _native.load()
-    B, H = cnt.shape
-    if out is None:
-        out = torch.empty((B, SELECT_BYTES // 8), dtype=torch.int64, device=cnt.device)
-    if sample_size != 6:
-        check(lib.sfm_pnp_select_best_ex(_ptr(cnt), _ptr(s1), _ptr(s2), _ptr(flags), H, B, float(min_extra), int(aggregation),
-                                         h_offset, int(sample_size), _ptr(out), _stream()), "sfm_pnp_select_best_ex")
-        return out
-    check(lib.sfm_pnp_select_best(_ptr(cnt), _ptr(s1), _ptr(s2), _ptr(flags), H, B, float(min_extra), int(aggregation),
-                                  h_offset, _ptr(out), _stream()), "sfm_pnp_select_best")
-    return out
 
 
 def pnp_inlier_mask(pts, model, S, K, result, thr: float, out=None, sample_size: int = 6):
     """uint8 [B,N]: 2 sample point of the winner (the first ``sample_size`` entries of its row of S), 1 other inlier,
     0 outlier."""
-    lib = _native.load()
     B, N, _ = pts.shape
     if out is None:
         out = torch.empty((B, N), dtype=torch.uint8, device=pts.device)
-    if sample_size != 6:
-        Kc, Kp = _pnp_camera(K)
-        check(lib.sfm_pnp_inlier_mask_ex(_ptr(pts), N, _ptr(model), _ptr(S), S.shape[1], B, Kp, _ptr(result), float(thr),
-                                         int(sample_size), _ptr(out), _stream()), "sfm_pnp_inlier_mask_ex")
-        return out
     Kc = (C.c_double * 9)(*_camera_list(K))
-    check(lib.sfm_pnp_inlier_mask(_ptr(pts), N, _ptr(model), _ptr(S), S.shape[1], B, C.cast(Kc, C.c_void_p), _ptr(result),
-                                  float(thr), _ptr(out), _stream()), "sfm_pnp_inlier_mask")
+    check(_native.load().sfm_pnp_inlier_mask(_ptr(pts), N, _ptr(model), _ptr(S), S.shape[1], B, C.cast(Kc, C.c_void_p),
+                                              _ptr(result), float(thr), int(sample_size), _ptr(out), _stream()),
+          "sfm_pnp_inlier_mask")
     return out
 
 
@@ -948,9 +885,6 @@ def read_tracks_info(info: torch.Tensor) -> TracksInfo:
     return TracksInfo(int(raw[0]), int(raw[1]), int(raw[2]))
 
 
-PNP_SAMPLE_SIZE = {"dlt": 6, "p3p": 4}   # sample size of each PnP solver (PnPWorkspace.run)
-
-
 @dataclass
 class PnPOutcome:
     best_h: int                # winning hypothesis, -1 if none
@@ -978,17 +912,14 @@ class PnPWorkspace:
         self.s2 = torch.empty((batch, h), dtype=F64, device=dev)
         self.result = torch.empty((batch, SELECT_BYTES // 8), dtype=torch.int64, device=dev)
         self.mask = torch.empty((batch, n), dtype=torch.uint8, device=dev)
-        self.sample_size = PNP_SAMPLE_SIZE["dlt"]
+        self.sample_size = solver_sample_size("pose", "dlt")   # of the last pass (outcome and refine read it)
 
     def run(self, pts: torch.Tensor, K, thr: float, min_extra: float, aggregation: int, with_mask: bool = True,
             philox=None, solver: str = "dlt") -> None:
         """fit + score + select (+ mask) in one call (``sfm_pnp_ransac_pass``) for the sample table in ``self.S`` — or, with
         ``philox=(seed, h_begin, seed_stride)``, for Philox samples drawn inside the fit launch (which also fills ``self.S``).
-        ``solver="p3p"``: the P3P fit on four-item samples (``sfm_pnp_ransac_pass_ex``); ``outcome`` and ``refine`` then
-        read this pass."""
-        if solver not in PNP_SAMPLE_SIZE:
-            raise ValueError(f"unknown PnP solver {solver!r}: expected one of {sorted(PNP_SAMPLE_SIZE)}")
-        self.sample_size = PNP_SAMPLE_SIZE[solver]
+        ``solver="p3p"``: the P3P fit on four-item samples; ``outcome`` and ``refine`` then read this pass."""
+        self.sample_size = solver_sample_size("pose", solver)
         seed, h_begin, stride = (0, 0, 1) if philox is None else philox
         op = ops.load()
         run_pass = op.p3p_ransac_pass_ if solver == "p3p" else op.pnp_ransac_pass_
@@ -1009,7 +940,7 @@ class PnPWorkspace:
         model = self.model[rows, best_h]
         err = self.result[:, 2].contiguous().view(F64)
         mask = self.mask
-        if self.sample_size == PNP_SAMPLE_SIZE["p3p"]:
+        if self.sample_size == solver_sample_size("pose", "p3p"):
             mask = mask.clone()
             mask[rows, self.S[rows, best_h, 3].long().clamp(min=0)] = 0
         return pnp_refine(pts, model, mask, err, K, thr, aggregation, rounds, max_steps)

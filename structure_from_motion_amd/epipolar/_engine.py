@@ -16,6 +16,7 @@ import torch
 
 from .. import _native, device
 from ..common.feature import Feature
+from ..ransac.ransac import solver_sample_size
 
 
 _GET_X, _GET_Y = attrgetter("x"), attrgetter("y")
@@ -155,6 +156,31 @@ def local_optimisation_rounds() -> int:
     return rounds
 
 
+def draw_samples(S: torch.Tensor, n: int, iterations: int):
+    """The samples of a one-pair pass over ``n`` items -> ``(sampler, table, philox)``.  ``pyshuffle``: the ``PyShuffleTable``
+    of the global ``random`` state (advanced as the reference's loop would), uploaded into ``S`` [1, iterations, 8], and
+    ``philox`` None.  ``philox``: no table, and ``philox = (seed, 0, 1)`` with seed ``SFM_SEED`` or 64 bits of ``random``,
+    for the caller to draw on the device."""
+    sampler = sampler_name(n, iterations)
+    if sampler == "pyshuffle":
+        table = device.PyShuffleTable(n, iterations, random, advance=True)
+        S.copy_(device.to_device(table.S, dtype=S.dtype).reshape(1, iterations, 8))
+        return sampler, table, None
+    seed = int(os.environ["SFM_SEED"]) if "SFM_SEED" in os.environ else random.getrandbits(64)
+    return sampler, None, (seed, 0, 1)
+
+
+def inlier_order(table, outcome, sample_size: int) -> np.ndarray:
+    """Indices of the winner's inliers in the reference's order: its sample first, then the survivors (mask 1) in the order
+    of the shuffled list (``table``), or in index order for Philox samples (``table`` None)."""
+    survivors = outcome.mask == 1
+    if table is None:
+        return np.concatenate([outcome.sample, np.nonzero(survivors)[0]])
+    perm = table.permutation_after(outcome.best_h)
+    rest = perm[sample_size:]
+    return np.concatenate([perm[:sample_size], rest[survivors[rest]]])
+
+
 logger = logging.getLogger(__name__)   # one line per call, never per hypothesis (SURVEY.md §5)
 
 
@@ -172,7 +198,7 @@ def ransac_feature_pairs(data, camera_matrix, threshold, min_extra, aggregation,
     from .eight_point import EightPointCalculationError
     from .five_point import FivePointCalculationError
 
-    sample_size = device.check_e_solver(solver)
+    sample_size = solver_sample_size("essential", solver)
     n = len(data)
     if solver == "five_point":
         if n < 6:
@@ -189,20 +215,13 @@ def ransac_feature_pairs(data, camera_matrix, threshold, min_extra, aggregation,
     pix = device.to_device(pair_arrays(data))   # one upload: [2, n, 2]
     corr = device.normalize_correspondences(pix[0], pix[1], camera_matrix)
     ws = device.RansacWorkspace(1, n, iterations, dev)
-    sampler = sampler_name(n, iterations)
-    table = None
-    if sampler == "pyshuffle":
-        table = device.PyShuffleTable(n, iterations, random, advance=True)
-        ws.S.copy_(device.to_device(table.S, dtype=ws.S.dtype).reshape(1, iterations, 8))
-    else:
-        seed = int(os.environ["SFM_SEED"]) if "SFM_SEED" in os.environ else random.getrandbits(64)
+    sampler, table, philox = draw_samples(ws.S, n, iterations)
     if solver == "five_point":
         # the Philox samples are drawn inside the fit launch (positions >= n are -1, so n = 6 and 7 are valid)
-        ws.run(corr.reshape(1, n, 4), threshold, min_extra, aggregation, philox=None if table is not None else (seed, 0, 1),
-               solver=solver)
+        ws.run(corr.reshape(1, n, 4), threshold, min_extra, aggregation, philox=philox, solver=solver)
     else:
-        if table is None:
-            device.sample_philox(seed, 0, iterations, n, out=ws.S)
+        if philox is not None:
+            device.sample_philox(philox[0], 0, iterations, n, out=ws.S)
         ws.run(corr.reshape(1, n, 4), threshold, min_extra, aggregation)
     outcome = ws.outcome(0)
     if outcome.n_flagged and degenerate_policy() == "raise" and solver == "five_point":
@@ -230,11 +249,4 @@ def ransac_feature_pairs(data, camera_matrix, threshold, min_extra, aggregation,
         if device.read_refine_info(info)[0][2] > 0:
             keep = np.nonzero(mask_ref.cpu().numpy()[0])[0]
             return E_ref.cpu().numpy().reshape(3, 3), copy_pairs(data, keep)
-    survivors = outcome.mask == 1
-    if sampler == "pyshuffle":
-        perm = table.permutation_after(outcome.best_h)
-        rest = perm[sample_size:]
-        order = np.concatenate([perm[:sample_size], rest[survivors[rest]]])
-    else:
-        order = np.concatenate([outcome.sample, np.nonzero(survivors)[0]])
-    return outcome.E, copy_pairs(data, order)
+    return outcome.E, copy_pairs(data, inlier_order(table, outcome, sample_size))

@@ -7,10 +7,9 @@ from typing import Tuple
 
 import numpy.typing as npt
 
-from .. import device
 from ..common.feature import Feature
 from ..feature_matching.matching import Match
-from ..ransac.ransac import ErrorAggregationMethod, fit_with_ransac
+from ..ransac.ransac import ErrorAggregationMethod, fit_with_ransac, solver_sample_size
 from . import _engine
 from .eight_point import estimate_essential_mat, to_normalized_image_coords
 from .five_point import FivePointCalculationError, five_point  # noqa: F401  (FivePointCalculationError: re-exported)
@@ -83,7 +82,7 @@ def estimate_essential_mat_with_ransac(
     Raises ``ValueError`` when no hypothesis has enough inliers or ``solver`` is unknown, and ``EightPointCalculationError``
     when a sampled eight-tuple is degenerate (reference behaviour; ``SFM_DEGENERATE=skip`` ignores such
     hypotheses instead)."""
-    sample_size = device.check_e_solver(solver)   # ValueError for an unknown solver
+    sample_size = solver_sample_size("essential", solver)   # ValueError for an unknown solver
     fitter = five_point_model_fitter if solver == "five_point" else eight_point_model_fitter
     with _engine.gc_paused():  # bulk creation of pair tuples and inlier copies: see _engine.gc_paused
         feature_pairs = _engine.match_pairs(features_a, features_b, matches)

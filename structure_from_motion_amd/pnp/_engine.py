@@ -3,13 +3,12 @@ from __future__ import annotations
 
 import copy
 import logging
-import os
-import random
 
 import numpy as np
 
 from .. import device
-from ..epipolar._engine import degenerate_policy, sampler_name
+from ..epipolar._engine import degenerate_policy, draw_samples, inlier_order
+from ..ransac.ransac import solver_sample_size
 
 logger = logging.getLogger(__name__)
 
@@ -38,11 +37,9 @@ def ransac_pnp_items(data, camera_matrix, threshold, min_extra, aggregation, ite
 
     ``solver`` is ``"dlt"`` (six-item samples) or ``"p3p"`` (four-item samples: ``PyShuffleTable.S[:, :4]``, the first four
     of ``philox_sample8``); the sample size sets the minimum n, the sample the inliers start with and the degenerate error."""
-    from .pnp import SOLVERS, PnPCalculationError, check_camera_matrix
+    from .pnp import PnPCalculationError, check_camera_matrix
 
-    if solver not in SOLVERS:
-        raise ValueError(f"unknown PnP solver {solver!r}: expected one of {sorted(SOLVERS)}")
-    sample_size = SOLVERS[solver]
+    sample_size = solver_sample_size("pose", solver)
     n = len(data)
     if iterations <= 0:
         return None, []
@@ -52,15 +49,8 @@ def ransac_pnp_items(data, camera_matrix, threshold, min_extra, aggregation, ite
     dev = device.require_gpu()
     pts = device.to_device(item_array(data)).reshape(1, n, 5)
     ws = device.PnPWorkspace(1, n, iterations, dev)
-    sampler = sampler_name(n, iterations)
-    table = None
-    if sampler == "pyshuffle":
-        table = device.PyShuffleTable(n, iterations, random, advance=True)
-        ws.S.copy_(device.to_device(table.S, dtype=ws.S.dtype).reshape(1, iterations, 8))
-        ws.run(pts, K, threshold, min_extra, aggregation, solver=solver)
-    else:
-        seed = int(os.environ["SFM_SEED"]) if "SFM_SEED" in os.environ else random.getrandbits(64)
-        ws.run(pts, K, threshold, min_extra, aggregation, philox=(seed, 0, 1), solver=solver)
+    sampler, table, philox = draw_samples(ws.S, n, iterations)
+    ws.run(pts, K, threshold, min_extra, aggregation, philox=philox, solver=solver)
     refined = ws.refine(pts, K, threshold, aggregation, refine_rounds, refine_steps) if refine_rounds > 0 else None
     outcome = ws.outcome(0)
     if outcome.n_flagged and degenerate_policy() == "raise":
@@ -80,11 +70,4 @@ def ransac_pnp_items(data, camera_matrix, threshold, min_extra, aggregation, ite
             m = model[0].cpu().numpy()
             keep = np.nonzero(mask[0].cpu().numpy())[0]
             return (m[:9].reshape(3, 3).copy(), m[9:].copy()), [copy.deepcopy(data[i]) for i in keep.tolist()]
-    survivors = outcome.mask == 1
-    if sampler == "pyshuffle":
-        perm = table.permutation_after(outcome.best_h)
-        rest = perm[sample_size:]
-        order = np.concatenate([perm[:sample_size], rest[survivors[rest]]])
-    else:
-        order = np.concatenate([outcome.sample, np.nonzero(survivors)[0]])
-    return (outcome.R, outcome.t), [copy.deepcopy(data[i]) for i in order.tolist()]
+    return (outcome.R, outcome.t), [copy.deepcopy(data[i]) for i in inlier_order(table, outcome, sample_size).tolist()]

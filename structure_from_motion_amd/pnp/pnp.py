@@ -18,7 +18,7 @@ import numpy.typing as npt
 from ..common.feature import Feature
 from ..epipolar import _engine
 from ..feature_matching.matching import Match
-from ..ransac.ransac import DEFAULT_MAX_ITERATIONS, ErrorAggregationMethod, aggregation_code, fit_with_ransac
+from ..ransac.ransac import DEFAULT_MAX_ITERATIONS, ErrorAggregationMethod, aggregation_code, fit_with_ransac, solver_sample_size
 from . import p3p
 
 PnPItem = Tuple[npt.NDArray, Feature]
@@ -98,7 +98,6 @@ def calculate_reprojection_score(model: PnPModel, item: PnPItem, camera_matrix: 
 
 
 P3P_SAMPLE_SIZE = 4
-SOLVERS = {"dlt": SAMPLE_SIZE, "p3p": P3P_SAMPLE_SIZE}
 
 
 def p3p_candidates(items: Sequence[PnPItem], camera_matrix: npt.NDArray) -> list:
@@ -170,9 +169,7 @@ def estimate_pose_pnp_with_ransac(
     (``PnPCalculationError`` under the default policy).  An unknown ``solver`` raises ``ValueError`` before any device
     work."""
     K = check_camera_matrix(camera_matrix)
-    if solver not in SOLVERS:
-        raise ValueError(f"unknown PnP solver {solver!r}: expected one of {sorted(SOLVERS)}")
-    sample_size = SOLVERS[solver]
+    sample_size = solver_sample_size("pose", solver)
     if len(matches) < sample_size:
         if solver == "dlt":
             raise ValueError(f"At least six 2D-3D matches are expected, got {len(matches)}.")
@@ -222,7 +219,7 @@ def _ransac_refined(K, points_3d, features, matches, threshold, min_extra, metho
         model, inliers = pnp_engine.ransac_pnp_items(items, K, threshold, min_extra, aggregation_code(method), iterations,
                                                      refine_rounds=rounds, solver=solver)
     if model is None:
-        raise ValueError(f"No model could be found with at least {min_extra + SOLVERS[solver]} inliers.")
+        raise ValueError(f"No model could be found with at least {min_extra + solver_sample_size('pose', solver)} inliers.")
     R, t = model
     return R, t, inliers
 

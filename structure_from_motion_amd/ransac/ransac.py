@@ -93,6 +93,31 @@ def fit_with_ransac(
     return model, inliers
 
 
+class Solver(NamedTuple):
+    """A minimal solver of the device route."""
+    model: str         # "essential" or "pose"
+    sample_size: int   # items of a sample: they enter the aggregate, and its mean / RMS divide by count + sample_size
+    role: str          # the _sfm_hip_role of the fitter whose partials route to it
+
+
+SOLVERS = {
+    "eight_point": Solver("essential", 8, "eight_point_fitter"),
+    "five_point": Solver("essential", 6, "five_point_fitter"),
+    "dlt": Solver("pose", 6, "pnp_fitter"),
+    "p3p": Solver("pose", 4, "p3p_fitter"),
+}
+_SCORER_ROLE = {"essential": "sed_scorer", "pose": "reprojection_scorer"}
+
+
+def solver_sample_size(model: str, solver: str) -> int:
+    """Sample size of ``solver`` for a ``model`` ("essential" or "pose"); ``ValueError`` for an unknown one."""
+    known = sorted(name for name, s in SOLVERS.items() if s.model == model)
+    if solver not in known:
+        what = "essential-matrix" if model == "essential" else "PnP"
+        raise ValueError(f"unknown {what} solver {solver!r}: expected one of {known}")
+    return SOLVERS[solver].sample_size
+
+
 class PnPDeviceSpec(NamedTuple):
     """Device route of a PnP fitter (six-point DLT or P3P) / reprojection scorer pair."""
     camera_matrix: np.ndarray
@@ -105,46 +130,29 @@ class EssentialDeviceSpec(NamedTuple):
     solver: str = "five_point"
 
 
-# the tagged PnP fitters: role -> (solver, sample size)
-_PNP_FITTERS = {"pnp_fitter": ("dlt", 6), "p3p_fitter": ("p3p", 4)}
-
-
 def _device_spec(model_fitter, inlier_scorer, model_fit_data_count):
-    """Camera matrix if (fitter, scorer) are partials of the eight-point / SED pair, a PnPDeviceSpec if they are partials
-    of a PnP fitter / reprojection scorer with that fitter's sample size (six for the DLT, four for P3P) and one camera
-    matrix, else None."""
+    """For partials of a tagged fitter (``SOLVERS``) and the scorer of its model, with that solver's sample size and one
+    camera matrix: the bare camera matrix for the eight-point fitter, an EssentialDeviceSpec for the five-point one, a
+    PnPDeviceSpec for the DLT and P3P; else None."""
     fit_fn = getattr(model_fitter, "func", None)
     score_fn = getattr(inlier_scorer, "func", None)
     if fit_fn is None or score_fn is None:
         return None
-    if (getattr(fit_fn, "_sfm_hip_role", None) in _PNP_FITTERS
-            and getattr(score_fn, "_sfm_hip_role", None) == "reprojection_scorer"):
-        solver, sample_size = _PNP_FITTERS[fit_fn._sfm_hip_role]
-        if model_fit_data_count != sample_size:
-            return None
-        k_fit = model_fitter.keywords.get("camera_matrix") if not model_fitter.args else None
-        k_score = inlier_scorer.keywords.get("camera_matrix") if not inlier_scorer.args else None
-        if k_fit is None or k_score is None or not np.array_equal(np.asarray(k_fit), np.asarray(k_score)):
-            return None
-        return PnPDeviceSpec(np.asarray(k_fit, dtype=np.float64), solver)
-    if (getattr(fit_fn, "_sfm_hip_role", None) == "five_point_fitter" and model_fit_data_count == 6
-            and getattr(score_fn, "_sfm_hip_role", None) == "sed_scorer"):
-        k_fit = model_fitter.keywords.get("camera_matrix") if not model_fitter.args else None
-        k_score = inlier_scorer.keywords.get("camera_matrix") if not inlier_scorer.args else None
-        if k_fit is None or k_score is None or not np.array_equal(np.asarray(k_fit), np.asarray(k_score)):
-            return None
-        return EssentialDeviceSpec(np.asarray(k_fit, dtype=np.float64))
-    if model_fit_data_count != 8:
+    role = getattr(fit_fn, "_sfm_hip_role", None)
+    solver = next((name for name, s in SOLVERS.items() if s.role == role), None)
+    if solver is None:
         return None
-    if not getattr(fit_fn, "_sfm_hip_role", None) == "eight_point_fitter":
-        return None
-    if not getattr(score_fn, "_sfm_hip_role", None) == "sed_scorer":
+    spec = SOLVERS[solver]
+    if model_fit_data_count != spec.sample_size or getattr(score_fn, "_sfm_hip_role", None) != _SCORER_ROLE[spec.model]:
         return None
     k_fit = model_fitter.keywords.get("camera_matrix") if not model_fitter.args else None
     k_score = inlier_scorer.keywords.get("camera_matrix") if not inlier_scorer.args else None
     if k_fit is None or k_score is None or not np.array_equal(np.asarray(k_fit), np.asarray(k_score)):
         return None
-    return np.asarray(k_fit, dtype=np.float64)
+    K = np.asarray(k_fit, dtype=np.float64)
+    if spec.model == "pose":
+        return PnPDeviceSpec(K, solver)
+    return K if solver == "eight_point" else EssentialDeviceSpec(K, solver)
 
 
 def _host_loop(data, k, model_fitter, inlier_scorer, threshold, min_extra, method, iterations):

@@ -150,7 +150,7 @@ def test_oracle_bad_start_and_bad_index():
 def test_bundle_symbols_exported_and_bound(native_lib):
     from structure_from_motion_amd import _native
 
-    assert _native.ABI_VERSION == 14 and native_lib.sfm_abi_version() == 14
+    assert _native.ABI_VERSION == 15 and native_lib.sfm_abi_version() == 15
     assert "sfm_bundle_adjust" in _native.SIGNATURES and "sfm_bundle_workspace_bytes" in _native.OTHER_SYMBOLS
     assert hasattr(native_lib, "sfm_bundle_adjust")
     assert native_lib.sfm_bundle_workspace_bytes(16, 20000, 80000) > 80000 * 18 * 8

@@ -86,7 +86,7 @@ def test_sequence_problem_shapes_and_banded_visibility():
 def test_bundle_pcg_symbols_exported_and_bound(native_lib):
     from structure_from_motion_amd import _native
 
-    assert _native.ABI_VERSION == 14 and native_lib.sfm_abi_version() == 14
+    assert _native.ABI_VERSION == 15 and native_lib.sfm_abi_version() == 15
     assert "sfm_bundle_adjust_pcg" in _native.SIGNATURES and "sfm_bundle_pcg_workspace_bytes" in _native.OTHER_SYMBOLS
     assert hasattr(native_lib, "sfm_bundle_adjust_pcg")
     ws = native_lib.sfm_bundle_pcg_workspace_bytes

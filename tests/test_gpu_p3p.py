@@ -129,7 +129,7 @@ def test_score_select_mask_match_the_host():
     s1_d, s2_d = (device.to_device(a).reshape(1, h) for a in (s1, s2))
     for method in ransac.ErrorAggregationMethod:
         agg = ransac.aggregation_code(method)
-        result = device.pnp_select_best(cnt_d, s1_d, s2_d, flags_d, 10, agg, sample_size=4)
+        result = device.select_best(cnt_d, s1_d, s2_d, flags_d, 10, agg, sample_size=4)
         rec = device.read_select(result)[0]
         # the host loop's rule on the same models: strict <, earliest first, NaN never
         best, best_err = -1, np.inf
@@ -224,33 +224,34 @@ def test_batch_equals_single_views():
             assert torch.equal(_bits(getattr(ws, name)[b]), _bits(getattr(one, name)[0])), (b, name)
 
 
-def _pass(fn_name, solver, pts, ws, K_arr):
-    lib = _native.load()
-    P = device._ptr
-    args = [0x1234, 1, 1, 0, P(pts), ws.n, ws.h, ws.batch, K_arr.ctypes.data_as(C.c_void_p), 4.0, 10.0, AGG_RMS, P(ws.S),
-            P(ws.model), P(ws.flags), P(ws.cnt), P(ws.s1), P(ws.s2), P(ws.result), P(ws.mask), device._stream()]
-    if solver is not None:
-        args = [solver] + args
-    _native.check(getattr(lib, fn_name)(*args), fn_name)
-    torch.cuda.synchronize()
-
-
-def test_dlt_pass_through_ex_is_bit_identical():
+def test_pass_equals_its_stages_bit_for_bit():
+    """One sfm_pnp_ransac_pass call leaves exactly what its stages leave when called one by one on the same sample table —
+    the fit, pnp_score, select_best and pnp_inlier_mask with the solver's sample size — for both solvers; an unknown solver
+    and a sample size of 5 are refused."""
     n, h = 1500, 500
     pts = device.to_device(orc.scene(n, 36, K, outlier_fraction=0.3, noise_px=0.5)[0]).reshape(1, n, 5)
     K_arr = np.ascontiguousarray(K, dtype=np.float64)
-    a, b = device.PnPWorkspace(1, n, h, pts.device), device.PnPWorkspace(1, n, h, pts.device)
-    _pass("sfm_pnp_ransac_pass", None, pts, a, K_arr)
-    _pass("sfm_pnp_ransac_pass_ex", _native.PNP_SOLVER_DLT, pts, b, K_arr)
-    for name in ("S", "model", "flags", "cnt", "s1", "s2", "result", "mask"):
-        assert torch.equal(_bits(getattr(a, name)), _bits(getattr(b, name))), name
     lib = _native.load()
-    buffers = [device._ptr(getattr(a, k)) for k in ("S", "model", "flags", "cnt", "s1", "s2", "result", "mask")]
-    assert lib.sfm_pnp_ransac_pass_ex(7, 0, 1, 1, 0, device._ptr(pts), n, h, 1, K_arr.ctypes.data_as(C.c_void_p), 4.0, 10.0,
-                                      AGG_RMS, *buffers, device._stream()) != _native.SFM_OK   # unknown solver
-    assert lib.sfm_pnp_score_ex(device._ptr(pts), n, device._ptr(a.model), device._ptr(a.S), h, 1,
-                                K_arr.ctypes.data_as(C.c_void_p), 4.0, 5, device._ptr(a.cnt), device._ptr(a.s1),
-                                device._ptr(a.s2), device._stream()) != 0
+    for solver, code, size in (("dlt", _native.PNP_SOLVER_DLT, 6), ("p3p", _native.PNP_SOLVER_P3P, 4)):
+        ws = device.PnPWorkspace(1, n, h, pts.device)
+        ws.S.copy_(device.sample_philox(36, 0, h, n))
+        buffers = [device._ptr(getattr(ws, k)) for k in ("S", "model", "flags", "cnt", "s1", "s2", "result", "mask")]
+        _native.check(lib.sfm_pnp_ransac_pass(code, 0, 1, 0, 0, device._ptr(pts), n, h, 1, K_arr.ctypes.data_as(C.c_void_p), 4.0,
+                                              10.0, AGG_RMS, *buffers, device._stream()), "sfm_pnp_ransac_pass")
+        model, flags = (device.p3p_fit if solver == "p3p" else device.pnp_fit)(pts, ws.S, K)
+        cnt, s1, s2 = device.pnp_score(pts, model, ws.S, K, 4.0, sample_size=size)
+        result = device.select_best(cnt, s1, s2, flags, 10.0, AGG_RMS, sample_size=size)
+        mask = device.pnp_inlier_mask(pts, model, ws.S, K, result, 4.0, sample_size=size)
+        torch.cuda.synchronize()
+        assert device.read_select(result)[0].best_h >= 0, solver
+        for name, staged in (("model", model), ("flags", flags), ("cnt", cnt), ("s1", s1), ("s2", s2), ("result", result),
+                             ("mask", mask)):
+            assert torch.equal(_bits(getattr(ws, name)), _bits(staged)), (solver, name)
+    assert lib.sfm_pnp_ransac_pass(7, 0, 1, 1, 0, device._ptr(pts), n, h, 1, K_arr.ctypes.data_as(C.c_void_p), 4.0, 10.0,
+                                   AGG_RMS, *buffers, device._stream()) != _native.SFM_OK   # unknown solver
+    assert lib.sfm_pnp_score(device._ptr(pts), n, device._ptr(ws.model), device._ptr(ws.S), h, 1,
+                             K_arr.ctypes.data_as(C.c_void_p), 4.0, 5, device._ptr(ws.cnt), device._ptr(ws.s1),
+                             device._ptr(ws.s2), device._stream()) != 0   # sample size 5
 
 
 def test_p3p_ops_opcheck():

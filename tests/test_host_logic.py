@@ -150,7 +150,7 @@ def test_argument_validation_without_gpu(native_lib):
     assert native_lib.sfm_score_workspace_bytes(1000, 50, 2) >= 2 * 16 + 2 * 1000 * 16 + 2 * 50 * 4
     assert native_lib.sfm_cheirality_batched(None, 0, 3, None, None, 50.0, None, None) == 0
     assert native_lib.sfm_pose_vote(None, 5, 2, None, None, None, None) == -1
-    assert native_lib.sfm_select_best(None, None, None, None, 4, 1, 0.0, 9, 0, None, None) == -1
+    assert native_lib.sfm_select_best(None, None, None, None, 4, 1, 0.0, 9, 0, 8, None, None) == -1
     # empty work is a successful no-op
     assert native_lib.sfm_triangulate(None, 0, None, None, None, None) == 0
     assert native_lib.sfm_cheirality(None, 0, None, 4, 50.0, None, None) == 0

@@ -68,8 +68,8 @@ def test_oracle_keeps_model_of_degenerate_inlier_set():
 def test_refine_symbol_exported_and_abi(native_lib):
     from structure_from_motion_amd import _native
 
-    assert _native.ABI_VERSION == 14
-    assert native_lib.sfm_abi_version() == 14
+    assert _native.ABI_VERSION == 15
+    assert native_lib.sfm_abi_version() == 15
     assert "sfm_pnp_refine" in _native.SIGNATURES
     assert hasattr(native_lib, "sfm_pnp_refine")
 

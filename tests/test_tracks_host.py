@@ -133,7 +133,7 @@ def test_oracle_produces_every_status():
 def test_tracks_symbols_exported_and_bound(native_lib):
     from structure_from_motion_amd import _native
 
-    assert _native.ABI_VERSION == 14 and native_lib.sfm_abi_version() == 14
+    assert _native.ABI_VERSION == 15 and native_lib.sfm_abi_version() == 15
     assert "sfm_triangulate_tracks" in _native.SIGNATURES and "sfm_tracks_workspace_bytes" in _native.OTHER_SYMBOLS
     assert hasattr(native_lib, "sfm_triangulate_tracks")
     assert native_lib.sfm_tracks_workspace_bytes(100000, 400000) >= 4 * (100000 * 2 + 400000)

@@ -141,7 +141,7 @@ def profile(out_dir: str, n: int, h: int, steps: int, warmup: int, limit: int, s
     if stats:
         with open(stats[0]) as f:
             for row in csv.DictReader(f):
-                if "pnp" in row["Name"] or "p3p" in row["Name"]:
+                if any(key in row["Name"] for key in ("pnp", "p3p", "select_")):   # the pass's kernels, selection included
                     name = row["Name"].replace("(anonymous namespace)::", "").split("(")[0]
                     split[name] = {
                         "calls": int(row["Calls"]), "avg_us": float(row["AverageNs"]) / 1e3, "percent": float(row["Percentage"])}
