@@ -9,6 +9,12 @@ iterative one above that, and takes up to 1 024 views.  Both give the same resul
 Gaussian pixel noise and a fraction of the observations replaced by random pixels.  Prints the views registered, each
 view's rotation error and translation error (in units of |t_1|, the scale of the seed), the RMS reprojection error of the
 final bundle adjustment and the points that end OK, as JSON.
+
+``tracks="given"`` (the default) takes the scene's tracks as they are.  ``tracks="matches"`` starts from pairwise matches
+instead (``synthetic.pairwise_matches``: views up to three apart, 10 % wrong matches): every pair is verified by the
+essential-matrix RANSAC and keeps its winner's inliers (a pair without a model is dropped), ``build_tracks`` turns them into
+tracks, and the same reconstruction runs on the built observations.  The output then also holds the build's info and the
+fraction of OK tracks whose features all belong to one true point.
 """
 from __future__ import annotations
 
@@ -27,13 +33,14 @@ from lib.common.feature import Feature
 from lib.epipolar.eight_point import create_trivial_matches, recover_r_t_from_e
 from lib.epipolar.epipolar_ransac import estimate_essential_mat_with_ransac
 from lib.feature_matching.matching import Match
-from lib.multiview.tracks import triangulate_tracks
+from lib.multiview.tracks import build_tracks, triangulate_tracks
 from lib.pnp.pnp import estimate_pose_pnp_with_ransac
 from structure_from_motion_amd import device, synthetic
 
 DENSE_MAX_VIEWS = 64   # the dense bundle adjuster's camera limit
 MAX_VIEWS = 1024       # with bundle_solver="auto": a bound of the app (host-side bookkeeping and run time)
 BUNDLE_SOLVERS = ("dense", "auto")
+TRACK_SOURCES = ("given", "matches")
 MIN_PNP_INLIERS = 30
 
 
@@ -122,20 +129,77 @@ class Reconstruction:
         return info, len(use)
 
 
+def _verified_matches(K, pix_a, pix_b, m, sed_threshold: float, iterations: int, e_solver: str):
+    """The matches m ((n, 2) local indices) that the essential-matrix RANSAC winner keeps (its sample and its survivors,
+    taken by index from the engine's inlier mask), or None when no model wins."""
+    from structure_from_motion_amd.epipolar import _engine
+    from structure_from_motion_amd.ransac.ransac import ErrorAggregationMethod, aggregation_code
+
+    n = len(m)
+    if n < 8:
+        return None
+    corr = device.normalize_correspondences(device.to_device(pix_a[m[:, 0]]), device.to_device(pix_b[m[:, 1]]), K)
+    ws = device.RansacWorkspace(1, n, iterations)
+    _, _, philox = _engine.draw_samples(ws.S, n, iterations)
+    agg = aggregation_code(ErrorAggregationMethod.RMS)
+    if e_solver == "five_point":
+        ws.run(corr.reshape(1, n, 4), sed_threshold, int(0.4 * n), agg, philox=philox, solver=e_solver)
+    else:
+        if philox is not None:
+            device.sample_philox(philox[0], 0, iterations, n, out=ws.S)
+        ws.run(corr.reshape(1, n, 4), sed_threshold, int(0.4 * n), agg)
+    outcome = ws.outcome(0)
+    if outcome.best_h < 0:
+        return None
+    return m[device.checked_mask(outcome.mask) > 0]
+
+
+def tracks_from_matches(scene, sed_threshold: float, iterations: int, e_solver: str, seed: int):
+    """The scene's tracks rebuilt from verified pairwise matches: (scene with the built camera_indices, point_indices and
+    pixels, the build's info, the fraction of OK tracks whose features all belong to one true point, pairs kept)."""
+    K = scene["K"]
+    random.seed(seed)   # the pairs' RANSAC samples
+    pm = synthetic.pairwise_matches(scene, seed=seed)
+    pairs, kept = [], []
+    for (i, j), m in zip(pm["pairs"], pm["matches"]):
+        inliers = _verified_matches(K, pm["features"][i], pm["features"][j], m, sed_threshold, iterations, e_solver)
+        if inliers is None:
+            continue   # a pair without a model is dropped
+        pairs.append((i, j))
+        kept.append(inliers)
+    r = build_tracks(pm["features"], np.array(pairs, dtype=np.int64).reshape(-1, 2), kept)
+    truth = np.concatenate(pm["feature_points"])[r.feature_indices]
+    lo = np.full(r.info.tracks, np.iinfo(np.int64).max)
+    hi = np.full(r.info.tracks, -1)
+    np.minimum.at(lo, r.point_indices, truth)
+    np.maximum.at(hi, r.point_indices, truth)
+    pure = float(np.mean(lo == hi)) if r.info.tracks else float("nan")
+    built = dict(scene, camera_indices=r.camera_indices, point_indices=r.point_indices, pixels=r.pixels)
+    return built, r.info, pure, len(pairs)
+
+
 def run(views: int = 8, points: int = 2000, seed: int = 21, noise_px: float = 0.5, outlier_fraction: float = 0.2,
         sed_threshold: float = 6e-6, reprojection_threshold: float = 16.0, iterations: int = 2000, refine_steps: int = 10,
         ba_steps: int = 20, final_ba_steps: int = 50, step_deg: float = 5.0, bundle_solver: str = "dense",
-        details: bool = False, pnp_solver: str = "dlt", e_solver: str = "eight_point") -> dict:
+        details: bool = False, pnp_solver: str = "dlt", e_solver: str = "eight_point", tracks: str = "given") -> dict:
     if pnp_solver not in ("dlt", "p3p"):
         raise ValueError(f"pnp_solver must be 'dlt' or 'p3p', got {pnp_solver!r}")
     if e_solver not in ("eight_point", "five_point"):
         raise ValueError(f"e_solver must be 'eight_point' or 'five_point', got {e_solver!r}")
+    if tracks not in TRACK_SOURCES:
+        raise ValueError(f"tracks must be one of {TRACK_SOURCES}, got {tracks!r}")
     if bundle_solver not in BUNDLE_SOLVERS:
         raise ValueError(f"bundle_solver must be one of {BUNDLE_SOLVERS}, got {bundle_solver!r}")
     limit = DENSE_MAX_VIEWS if bundle_solver == "dense" else MAX_VIEWS
     if not 2 <= views <= limit:
         raise ValueError(f"between 2 and {limit} views are supported with bundle_solver={bundle_solver!r}, got {views}")
     scene = synthetic.multi_view_scene(views, points, seed, noise_px, outlier_fraction, step_deg=step_deg)
+    build = None
+    if tracks == "matches":
+        scene, build_info, pure, kept_pairs = tracks_from_matches(scene, sed_threshold, iterations, e_solver, seed)
+        build = dict(pairs_kept=kept_pairs, components=build_info.components, tracks=build_info.tracks,
+                     observations=build_info.observations, conflicts=build_info.conflicts,
+                     unmatched=build_info.unmatched, pure_track_fraction=pure)
     K = scene["K"]
     rec = Reconstruction(scene, reprojection_threshold, refine_steps, min_angle_deg=1.0, bundle_solver=bundle_solver)
     cam, pt, uv = rec.cam, rec.pt, rec.uv
@@ -219,6 +283,8 @@ def run(views: int = 8, points: int = 2000, seed: int = 21, noise_px: float = 0.
         "points_ok": int(np.count_nonzero(rec.status == device.TRACKS_OK)),
         "steps": log,
     }
+    if build is not None:
+        out["track_build"] = build
     if details:
         out["_scene"], out["_status"] = scene, rec.status.copy()
     return out
@@ -247,6 +313,8 @@ def main():
                     help="dense: at most 64 views; auto: the iterative solver above 64 registered cameras")
     ap.add_argument("--pnp-solver", choices=("dlt", "p3p"), default="dlt",
                     help="minimal solver that registers each further view: six-point DLT or P3P on four-item samples")
+    ap.add_argument("--tracks", choices=TRACK_SOURCES, default="given",
+                    help="given: the scene's tracks; matches: tracks built from RANSAC-verified pairwise matches")
     ap.add_argument("--e-solver", choices=("eight_point", "five_point"), default="eight_point",
                     help="minimal solver of the two-view seed: eight-point, or five-point on six-item samples")
     args = ap.parse_args()
@@ -256,7 +324,7 @@ def main():
     print(json.dumps(run(args.views, args.points, args.seed, args.noise, args.outliers, sed_threshold=args.sed_threshold,
                          reprojection_threshold=args.reprojection_threshold, refine_steps=args.refine_steps,
                          step_deg=args.step_deg, bundle_solver=args.bundle_solver, pnp_solver=args.pnp_solver,
-                         e_solver=args.e_solver)))
+                         e_solver=args.e_solver, tracks=args.tracks)))
 
 
 if __name__ == "__main__":

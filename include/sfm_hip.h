@@ -511,6 +511,46 @@ int sfm_triangulate_tracks(const double* K, int64_t cameras, int64_t points, int
                            double* obs_error, double* angle, sfm_tracks_info* info, void* workspace,
                            int64_t workspace_bytes, void* stream);
 
+/* ---- multi-view tracks from pairwise matches (csrc/sfm_track_build.hip; an extension, off unless asked for) ----
+ * These symbols were added under ABI 15 without a version change: they are new, and nothing an ABI-15 caller uses changed. */
+
+#define SFM_BUILD_OK 0        /* the feature belongs to a track */
+#define SFM_BUILD_UNMATCHED 1 /* no match touches the feature */
+#define SFM_BUILD_CONFLICT 2  /* its component holds two features of one image: the whole component is dropped */
+#define SFM_BUILD_BAD_INDEX 3 /* some input of the call is out of range: every feature, no observations */
+
+typedef struct sfm_build_tracks_info {
+    int64_t status;       /* 0; 1 an input out of range (every feature SFM_BUILD_BAD_INDEX); 2 a bounded device loop gave up
+                             (every other output undefined) */
+    int64_t components;   /* components of two or more features */
+    int64_t tracks;       /* OK components */
+    int64_t observations; /* M: features of OK components */
+    int64_t conflicts;    /* conflict components */
+    int64_t unmatched;    /* features no match touches */
+} sfm_build_tracks_info;
+
+/* Bytes of workspace sfm_build_tracks needs; -1 for sizes it refuses. */
+int64_t sfm_build_tracks_workspace_bytes(int64_t images, int64_t features, int64_t matches);
+
+/* Tracks from the matches of image pairs.  Image i has features image_offset[i] .. image_offset[i + 1] (global ids,
+ * image-major; image_offset[0] = 0, image_offset[images] = features, non-decreasing).  Pair q joins images
+ * pair_images[2q] != pair_images[2q + 1]; its matches are match_offset[q] .. match_offset[q + 1] (match_offset[0] = 0,
+ * match_offset[pairs] = matches, non-decreasing), each the local indices (a, b) = match_index[2m], match_index[2m + 1] in the
+ * pair's two images.  Duplicate matches and duplicate or reversed pairs are allowed.  Outputs, every one a function of the
+ * multiset of matches alone: component[g] the smallest global id of g's connected component (may be NULL); status[g]
+ * (SFM_BUILD_*); the OK components are the tracks, numbered in increasing component id, track[g] = g's track or -1; the M
+ * observations of the tracks by track and, inside a track, by global id: camera_index (the image), point_index (the track),
+ * feature_index (the global id), each of capacity `features`, entries M .. features - 1 set to -1.  An input out of range
+ * gives info.status 1.  No host synchronisation; deterministic, bit for bit.
+ * image_offset: dev int32 [images + 1]; pair_images: dev int32 [pairs, 2]; match_offset: dev int32 [pairs + 1]; match_index:
+ * dev int32 [matches, 2]; component, track, camera_index, point_index, feature_index: dev int32 [features]; status: dev
+ * uint8 [features]; info: dev, one record; workspace: dev, 16-byte aligned, at least sfm_build_tracks_workspace_bytes.
+ * images, features, pairs < 2^31 - 1, matches < 2^31. */
+int sfm_build_tracks(int64_t images, int64_t features, int64_t pairs, int64_t matches, const int32_t* image_offset,
+                     const int32_t* pair_images, const int32_t* match_offset, const int32_t* match_index, int32_t* component,
+                     int32_t* track, uint8_t* status, int32_t* camera_index, int32_t* point_index, int32_t* feature_index,
+                     sfm_build_tracks_info* info, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* SED of n correspondences under one E (sed.py:7-30).  E: dev [9]; out: dev [n]. */
 int sfm_sed_values(const double* corr, int64_t n, const double* E, double* out, void* stream);
 

@@ -174,10 +174,11 @@ SIGNATURES = {
     "sfm_bundle_adjust_pcg": [_P, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, _D, _P, _P, _P, _P, _I64, _P],
     "sfm_triangulate_tracks": [_P, _I64, _I64, _I64, _P, _P, _P, _P, C.c_int, _D, _D, C.c_int, _P, _P, _P, _P, _P, _P, _I64,
                                _P],
+    "sfm_build_tracks": [_I64, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P],
 }
 OTHER_SYMBOLS = ["sfm_last_error", "sfm_abi_version", "sfm_score_workspace_bytes", "sfm_score_workspace_bytes_ex",
                  "sfm_fit_trace_doubles", "sfm_match_summary_workspace_bytes", "sfm_bundle_workspace_bytes",
-                 "sfm_tracks_workspace_bytes", "sfm_bundle_pcg_workspace_bytes"]
+                 "sfm_tracks_workspace_bytes", "sfm_bundle_pcg_workspace_bytes", "sfm_build_tracks_workspace_bytes"]
 
 _lib = None
 
@@ -219,6 +220,8 @@ def load() -> C.CDLL:
     lib.sfm_tracks_workspace_bytes.argtypes = [_I64, _I64]
     lib.sfm_bundle_pcg_workspace_bytes.restype = C.c_int64
     lib.sfm_bundle_pcg_workspace_bytes.argtypes = [_I64, _I64, _I64]
+    lib.sfm_build_tracks_workspace_bytes.restype = C.c_int64
+    lib.sfm_build_tracks_workspace_bytes.argtypes = [_I64, _I64, _I64]
     if lib.sfm_abi_version() != ABI_VERSION:
         raise NativeLibraryError(
             f"libsfm_hip.so ABI {lib.sfm_abi_version()} != expected {ABI_VERSION}; rebuild it")

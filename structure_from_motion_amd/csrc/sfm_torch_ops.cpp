@@ -9,8 +9,8 @@
 // sample_fit_philox_; and the PnP ops (sfm_pnp.hip) pnp_fit, pnp_score and the whole pass pnp_ransac_pass_, their P3P
 // forms p3p_fit and p3p_ransac_pass_ (sfm_p3p.h), the five-point fit five_point_fit and pass five_point_ransac_pass_
 // (sfm_five_point.hip), and the
-// refinement of a winner pnp_refine (sfm_pnp_refine.hip), bundle_adjust (sfm_bundle.hip) and triangulate_tracks
-// (sfm_tracks.hip).  The reference call sites these serve: apps/sfm.py:110-119 (RANSAC-E), :133-138 (pose),
+// refinement of a winner pnp_refine (sfm_pnp_refine.hip), bundle_adjust (sfm_bundle.hip), triangulate_tracks
+// (sfm_tracks.hip) and build_tracks (sfm_track_build.hip).  The reference call sites these serve: apps/sfm.py:110-119 (RANSAC-E), :133-138 (pose),
 // :181-186 (triangulation).
 //
 // Built by structure_from_motion_amd/build.py into csrc/libsfm_torch_ops.so (host code only: no kernels here).
@@ -869,6 +869,77 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> triangulate_tracks_meta(const
             at::empty_symint({cam.sym_size(0)}, like(poses, at::kDouble)), at::empty_symint({P}, like(poses, at::kDouble)),
             at::empty_symint({c10::SymInt(kTracksInfoWords)}, like(poses, at::kLong))};
 }
+
+// tracks from pairwise matches (sfm_track_build.hip): image_offset int32 [I + 1], pair_images int32 [Q, 2], match_offset
+// int32 [Q + 1], match_index int32 [E, 2] (local indices), `features` = F -> component, track int32 [F], status uint8 [F],
+// camera_index, point_index, feature_index int32 [F] (the first info.observations valid, the rest -1), info int64 [6]
+// viewing the sfm_build_tracks_info record.  The workspace comes from the caching allocator (stream-ordered, no host sync).
+constexpr int64_t kBuildInfoWords = sizeof(sfm_build_tracks_info) / 8;
+
+void build_check(const Tensor& image_offset, const Tensor& pair_images, const Tensor& match_offset, const Tensor& match_index,
+                 int64_t features) {
+    TORCH_CHECK(image_offset.dim() == 1 && image_offset.size(0) >= 1, "sfm_hip: image_offset must be [I + 1]");
+    TORCH_CHECK(pair_images.dim() == 2 && pair_images.size(1) == 2, "sfm_hip: pair_images must be [Q, 2]");
+    TORCH_CHECK(match_offset.dim() == 1 && match_offset.size(0) == pair_images.size(0) + 1, "sfm_hip: match_offset must be [Q + 1]");
+    TORCH_CHECK(match_index.dim() == 2 && match_index.size(1) == 2, "sfm_hip: match_index must be [E, 2]");
+    TORCH_CHECK(features >= 0 && features < 0x7FFFFFFF, "sfm_hip: features must be in [0, 2^31 - 1)");
+}
+
+void build_tracks_out(const Tensor& image_offset, const Tensor& pair_images, const Tensor& match_offset, const Tensor& match_index,
+                      int64_t features, Tensor& component, Tensor& track, Tensor& status, Tensor& camera_index,
+                      Tensor& point_index, Tensor& feature_index, Tensor& info) {
+    const OpDevice scope(image_offset);
+    need(image_offset, "image_offset", at::kInt);
+    need(pair_images, "pair_images", at::kInt);
+    need(match_offset, "match_offset", at::kInt);
+    need(match_index, "match_index", at::kInt);
+    need(component, "component", at::kInt);
+    need(track, "track", at::kInt);
+    need(status, "status", at::kByte);
+    need(camera_index, "camera_index", at::kInt);
+    need(point_index, "point_index", at::kInt);
+    need(feature_index, "feature_index", at::kInt);
+    need(info, "info", at::kLong);
+    build_check(image_offset, pair_images, match_offset, match_index, features);
+    const int64_t I = image_offset.size(0) - 1, F = features, Q = pair_images.size(0), E = match_index.size(0);
+    for (const Tensor* t : {&component, &track, &camera_index, &point_index, &feature_index, &status})
+        TORCH_CHECK(t->dim() == 1 && t->size(0) == F, "sfm_hip: build_tracks outputs must be [features]");
+    TORCH_CHECK(info.numel() == kBuildInfoWords, "sfm_hip: info must be int64 [6]");
+    const int64_t bytes = sfm_build_tracks_workspace_bytes(I, F, E);
+    TORCH_CHECK(bytes >= 0, "sfm_hip: build_tracks: ", I, " images, ", F, " features, ", E, " matches exceed the limits");
+    Tensor ws = at::empty({bytes}, like(image_offset, at::kByte));
+    ok(sfm_build_tracks(I, F, Q, E, ptr<int32_t>(image_offset), ptr<int32_t>(pair_images), ptr<int32_t>(match_offset),
+                        ptr<int32_t>(match_index), ptr<int32_t>(component), ptr<int32_t>(track), ptr<uint8_t>(status),
+                        ptr<int32_t>(camera_index), ptr<int32_t>(point_index), ptr<int32_t>(feature_index),
+                        reinterpret_cast<sfm_build_tracks_info*>(ptr<int64_t>(info)), ws.data_ptr(), bytes, current_stream()),
+       "sfm_build_tracks");
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> build_tracks(const Tensor& image_offset,
+                                                                                const Tensor& pair_images,
+                                                                                const Tensor& match_offset,
+                                                                                const Tensor& match_index, int64_t features) {
+    build_check(image_offset, pair_images, match_offset, match_index, features);
+    auto i32 = [&] { return at::empty({features}, like(image_offset, at::kInt)); };
+    Tensor component = i32(), track = i32(), camera_index = i32(), point_index = i32(), feature_index = i32();
+    Tensor status = at::empty({features}, like(image_offset, at::kByte));
+    Tensor info = at::empty({kBuildInfoWords}, like(image_offset, at::kLong));
+    build_tracks_out(image_offset, pair_images, match_offset, match_index, features, component, track, status, camera_index,
+                     point_index, feature_index, info);
+    return {component, track, status, camera_index, point_index, feature_index, info};
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> build_tracks_meta(const Tensor& image_offset,
+                                                                                     const Tensor& pair_images,
+                                                                                     const Tensor& match_offset,
+                                                                                     const Tensor& match_index,
+                                                                                     int64_t features) {
+    build_check(image_offset, pair_images, match_offset, match_index, features);
+    const c10::SymInt F(features);
+    auto i32 = [&] { return at::empty_symint({F}, like(image_offset, at::kInt)); };
+    return {i32(), i32(), at::empty_symint({F}, like(image_offset, at::kByte)), i32(), i32(), i32(),
+            at::empty_symint({c10::SymInt(kBuildInfoWords)}, like(image_offset, at::kLong))};
+}
 }  // namespace
 
 // the C-ABI version this op library was compiled against (include/sfm_hip.h); ops.load() compares it with the
@@ -936,6 +1007,11 @@ TORCH_LIBRARY(sfm_hip, m) {
     m.def("triangulate_tracks_(Tensor poses, Tensor camera_indices, Tensor point_indices, Tensor pixels, int points, "
           "float[] K, int min_views, float min_angle, float max_error, int refine_steps, Tensor(a!) points_out, "
           "Tensor(b!) status, Tensor(c!) obs_error, Tensor(d!) angle, Tensor(e!) info) -> ()");
+    m.def("build_tracks(Tensor image_offset, Tensor pair_images, Tensor match_offset, Tensor match_index, int features) -> "
+          "(Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
+    m.def("build_tracks_(Tensor image_offset, Tensor pair_images, Tensor match_offset, Tensor match_index, int features, "
+          "Tensor(a!) component, Tensor(b!) track, Tensor(c!) status, Tensor(d!) camera_index, Tensor(e!) point_index, "
+          "Tensor(f!) feature_index, Tensor(g!) info) -> ()");
 }
 
 // ROCm devices dispatch under torch's "CUDA" key (the name of the dispatch key, not a CUDA code path)
@@ -974,6 +1050,8 @@ TORCH_LIBRARY_IMPL(sfm_hip, CUDA, m) {
     m.impl("bundle_adjust_pcg_", &bundle_adjust_pcg_inplace);
     m.impl("triangulate_tracks", &triangulate_tracks);
     m.impl("triangulate_tracks_", &triangulate_tracks_out);
+    m.impl("build_tracks", &build_tracks);
+    m.impl("build_tracks_", &build_tracks_out);
 }
 
 // sample_philox has no tensor argument to dispatch on: registered for every backend, it checks its device itself
@@ -1007,6 +1085,8 @@ void bundle_adjust_pcg_out_meta(Tensor&, Tensor&, const Tensor&, const Tensor&, 
                                 at::ArrayRef<int64_t>, int64_t, int64_t, double, Tensor&) {}
 void triangulate_tracks_out_meta(const Tensor&, const Tensor&, const Tensor&, const Tensor&, int64_t, at::ArrayRef<double>, int64_t,
                                  double, double, int64_t, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&) {}
+void build_tracks_out_meta(const Tensor&, const Tensor&, const Tensor&, const Tensor&, int64_t, Tensor&, Tensor&, Tensor&, Tensor&,
+                           Tensor&, Tensor&, Tensor&) {}
 
 TORCH_LIBRARY_IMPL(sfm_hip, Meta, m) {
     m.impl("normalize_coords_", &normalize_coords_out_meta);
@@ -1043,4 +1123,6 @@ TORCH_LIBRARY_IMPL(sfm_hip, Meta, m) {
     m.impl("bundle_adjust_pcg_", &bundle_adjust_pcg_out_meta);
     m.impl("triangulate_tracks", &triangulate_tracks_meta);
     m.impl("triangulate_tracks_", &triangulate_tracks_out_meta);
+    m.impl("build_tracks", &build_tracks_meta);
+    m.impl("build_tracks_", &build_tracks_out_meta);
 }

@@ -885,6 +885,44 @@ def read_tracks_info(info: torch.Tensor) -> TracksInfo:
     return TracksInfo(int(raw[0]), int(raw[1]), int(raw[2]))
 
 
+# ------------------------------------------------------------------------------------------------------
+# multi-view tracks from pairwise matches (csrc/sfm_track_build.hip): image_offset int32 [I+1], pair_images int32 [Q,2],
+# match_offset int32 [Q+1], match_index int32 [E,2] (local indices in the pair's two images)
+# ------------------------------------------------------------------------------------------------------
+def build_tracks(image_offset, pair_images, match_offset, match_index, features: int, out=None):
+    """Connected components of the match graph, conflicts dropped, tracks numbered by smallest feature id
+    (``sfm_build_tracks``) -> (component, track, status uint8 (BUILD_*), camera_index, point_index, feature_index, info
+    int64 [6] viewing the sfm_build_tracks_info record; ``read_track_build_info``).  Every array but info has ``features``
+    entries; the observation arrays hold info.observations valid entries, then -1.  ``out`` = those seven tensors runs the
+    in-place op on them instead.  No host synchronisation."""
+    op = ops.load()
+    args = (image_offset.contiguous(), pair_images.contiguous(), match_offset.contiguous(), match_index.contiguous(),
+            int(features))
+    if out is None:
+        return op.build_tracks(*args)
+    op.build_tracks_(*args, *out)
+    return out
+
+
+BUILD_OK, BUILD_UNMATCHED, BUILD_CONFLICT, BUILD_BAD_INDEX = range(4)
+
+
+@dataclass
+class TrackBuildInfo:
+    status: int        # 0; 1 an input out of range (every feature BUILD_BAD_INDEX); 2 a bounded device loop gave up
+    components: int    # components of two or more features
+    tracks: int        # OK components
+    observations: int  # M, the features of OK components
+    conflicts: int     # components holding two features of one image (dropped)
+    unmatched: int     # features no match touches
+
+
+def read_track_build_info(info: torch.Tensor) -> TrackBuildInfo:
+    """Host copy of an sfm_build_tracks_info record (int64 [6]) (synchronises)."""
+    raw = info.cpu().numpy()
+    return TrackBuildInfo(*(int(v) for v in raw[:6]))
+
+
 @dataclass
 class PnPOutcome:
     best_h: int                # winning hypothesis, -1 if none

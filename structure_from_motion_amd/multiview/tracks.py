@@ -88,3 +88,105 @@ def triangulate_tracks(
         device.to_device(pixels), num_points, K, min_views, math.radians(min_angle), max_error, refine_steps)
     return TracksResult(X.cpu().numpy(), status.cpu().numpy(), err.cpu().numpy(), np.degrees(angle.cpu().numpy()),
                         device.read_tracks_info(info))
+
+
+@dataclass
+class TrackBuildResult:
+    camera_indices: npt.NDArray     # (M,) int32: the image of each observation
+    point_indices: npt.NDArray      # (M,) int32: the track of each observation (tracks 0 .. info.tracks - 1)
+    pixels: npt.NDArray             # (M, 2) the feature's pixel
+    feature_indices: npt.NDArray    # (M,) int32: the feature's global id, image_offsets[image] + its index in the image
+    image_offsets: npt.NDArray      # (I + 1,) int64: first global id of each image, then F
+    track_of_feature: npt.NDArray   # (F,) int32: the feature's track, -1 unless its status is BUILD_OK
+    feature_status: npt.NDArray     # (F,) uint8, device.BUILD_*
+    component: npt.NDArray          # (F,) int32: the smallest global id of the feature's connected component
+    info: object                    # device.TrackBuildInfo
+
+
+def _feature_pixels(value, i: int) -> npt.NDArray:
+    if isinstance(value, (list, tuple)) and value and not isinstance(value[0], (list, tuple, np.ndarray)):
+        value = [(f.x, f.y) for f in value]   # a list of Feature
+    a = np.asarray(value, dtype=np.float64)
+    if a.size == 0:
+        return np.zeros((0, 2))
+    if a.ndim != 2 or a.shape[1] != 2:
+        raise ValueError(f"features[{i}] must be an (n, 2) pixel array or a list of Feature, got shape {a.shape}")
+    return a
+
+
+def _pair_matches(value, q: int) -> npt.NDArray:
+    if isinstance(value, (list, tuple)) and value and not isinstance(value[0], (list, tuple, np.ndarray)):
+        value = [(m.a_index, m.b_index) for m in value]   # a list of Match
+    a = np.asarray(value)
+    if a.size == 0:
+        return np.zeros((0, 2), dtype=np.int64)
+    if a.ndim != 2 or a.shape[1] != 2:
+        raise ValueError(f"matches[{q}] must be an (n, 2) index array or a list of Match, got shape {a.shape}")
+    if not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"matches[{q}] must hold integers, got {a.dtype}")
+    return a.astype(np.int64)
+
+
+def build_tracks(features: Sequence, pairs, matches: Sequence) -> TrackBuildResult:
+    """Multi-view tracks from the matches of image pairs (``sfm_build_tracks``).
+
+    ``features[i]`` is image i's features: an ``(n_i, 2)`` pixel array or a list of ``Feature``; feature k of image i has
+    the global id ``image_offsets[i] + k``.  ``pairs`` is ``(Q, 2)`` image indices, two different images per pair;
+    ``matches[q]`` is pair q's matches: an ``(n, 2)`` array of ``(a_index, b_index)`` or the ``List[Match]`` of
+    ``match_brute_force``.  Duplicate matches and duplicate or reversed pairs are allowed.  The connected components of the
+    match graph are the candidate tracks; one holding two features of one image is dropped whole (``BUILD_CONFLICT``), a
+    feature no match touches is ``BUILD_UNMATCHED``.  Tracks are numbered by their smallest global id, and the observations
+    come by track, then by image: ready for ``triangulate_tracks`` and ``bundle_adjust``.  The result depends on the
+    multiset of matches alone.  Every argument is checked before any device work (``ValueError``)."""
+    feats = [_feature_pixels(f, i) for i, f in enumerate(features)]
+    n = np.array([len(f) for f in feats], dtype=np.int64)
+    I, F = len(feats), int(n.sum())
+    if I >= _INT32 - 1 or F >= _INT32 - 1:
+        raise ValueError("images and features must number fewer than 2^31 - 1")
+    pair_arr = np.asarray(pairs)
+    if pair_arr.size == 0:
+        pair_arr = np.zeros((0, 2), dtype=np.int64)
+    if pair_arr.ndim != 2 or pair_arr.shape[1] != 2:
+        raise ValueError(f"pairs must have shape (Q, 2), got {pair_arr.shape}")
+    if not np.issubdtype(pair_arr.dtype, np.integer):
+        raise ValueError(f"pairs must hold integers, got {pair_arr.dtype}")
+    Q = pair_arr.shape[0]
+    if Q >= _INT32 - 1:
+        raise ValueError("pairs must number fewer than 2^31 - 1")
+    if len(matches) != Q:
+        raise ValueError(f"matches must hold one entry per pair ({Q}), got {len(matches)}")
+    if Q and (pair_arr.min() < 0 or pair_arr.max() >= I):
+        raise ValueError(f"pairs must index images 0 .. {I - 1}")
+    if Q and np.any(pair_arr[:, 0] == pair_arr[:, 1]):
+        raise ValueError("a pair must join two different images")
+    per_pair = [_pair_matches(m, q) for q, m in enumerate(matches)]
+    counts = np.array([len(m) for m in per_pair], dtype=np.int64)
+    E = int(counts.sum())
+    if E >= _INT32:
+        raise ValueError("matches must number fewer than 2^31")
+    local = np.concatenate(per_pair) if Q else np.zeros((0, 2), dtype=np.int64)
+    if E:
+        owner = np.repeat(pair_arr.astype(np.int64), counts, axis=0)
+        if local.min() < 0 or np.any(local[:, 0] >= n[owner[:, 0]]) or np.any(local[:, 1] >= n[owner[:, 1]]):
+            raise ValueError("a match indexes a feature outside its image")
+    import torch
+
+    from .. import device
+
+    dev = device.require_gpu()
+    i32 = dict(dtype=torch.int32, device=dev)
+    image_offset = torch.zeros(I + 1, **i32)
+    image_offset[1:] = torch.cumsum(torch.as_tensor(n, device=dev), 0)
+    match_offset = torch.zeros(Q + 1, **i32)
+    match_offset[1:] = torch.cumsum(torch.as_tensor(counts, device=dev), 0)
+    comp, track, status, cam, pt, fid, info = device.build_tracks(
+        image_offset, torch.as_tensor(pair_arr, **i32), match_offset, torch.as_tensor(local, **i32), F)
+    info = device.read_track_build_info(info)
+    if info.status == 2:
+        raise RuntimeError("build_tracks: a bounded device loop gave up (sfm_build_tracks info.status 2)")
+    M = info.observations
+    pix = torch.as_tensor(np.concatenate(feats) if I else np.zeros((0, 2)), dtype=torch.float64, device=dev)
+    fid = fid[:M]
+    return TrackBuildResult(cam[:M].cpu().numpy(), pt[:M].cpu().numpy(), pix[fid.long()].cpu().numpy(), fid.cpu().numpy(),
+                            image_offset.cpu().numpy().astype(np.int64), track.cpu().numpy(), status.cpu().numpy(),
+                            comp.cpu().numpy(), info)

@@ -220,3 +220,74 @@ def planar_two_view_scene(n: int, seed: int = 0, outlier_fraction: float = 0.3, 
     pb = np.where(is_out[:, None], rand_px, pb)
     normal = np.array([-0.3, 0.2, 1.0])
     return pa, pb, K, R, t, is_out, (normal, 5.0)
+
+
+def pairwise_matches(scene, window: int = 3, wrong_fraction: float = 0.1, seed: int = 0):
+    """Pairwise feature matches of a ``multi_view_scene``, the input of ``build_tracks``.  View v's features are its
+    observations in a seeded random order (a local index says nothing about the point); the pairs are (i, j) with
+    1 <= j - i <= ``window``; a pair's matches are every point both views observe, in random order, with ``wrong_fraction``
+    of them re-paired to a random feature of view j.  The scene's random-pixel outliers stay: they are matched like any other
+    observation.  Returns dict(features: list of (n_v, 2) pixels, pairs (Q, 2) int64, matches: list of (n_q, 2) int64 local
+    indices, feature_points: list of (n_v,) int64 true point of each feature, wrong: list of (n_q,) bool)."""
+    rng = np.random.default_rng(seed)
+    cam, pt, uv = scene["camera_indices"], scene["point_indices"], scene["pixels"]
+    views = int(cam.max()) + 1 if len(cam) else 0
+    P = int(pt.max()) + 1 if len(pt) else 0
+    features, points, local = [], [], []
+    for v in range(views):
+        obs = np.nonzero(cam == v)[0]
+        obs = obs[rng.permutation(len(obs))]
+        features.append(uv[obs])
+        points.append(pt[obs].astype(np.int64))
+        where = np.full(P, -1, dtype=np.int64)
+        where[pt[obs]] = np.arange(len(obs))
+        local.append(where)
+    pairs, matches, wrong = [], [], []
+    for i in range(views):
+        for j in range(i + 1, min(views, i + window + 1)):
+            common = np.nonzero((local[i] >= 0) & (local[j] >= 0))[0]
+            common = common[rng.permutation(len(common))]
+            m = np.column_stack([local[i][common], local[j][common]]).astype(np.int64)
+            bad = rng.random(len(m)) < wrong_fraction
+            m[bad, 1] = rng.integers(0, len(features[j]), int(bad.sum()))
+            pairs.append((i, j))
+            matches.append(m.reshape(-1, 2))
+            wrong.append(bad & (m[:, 1] != local[j][common]))
+    return dict(features=features, pairs=np.array(pairs, dtype=np.int64).reshape(-1, 2), matches=matches,
+                feature_points=points, wrong=wrong)
+
+
+def match_graph(images: int, features: int, neighbours: int, matches_per_pair: int, wrong_fraction: float = 0.0,
+                seed: int = 0):
+    """A match graph for scale, with no geometry, built vectorised.  Image i sees the latent points i * s .. i * s +
+    ``features`` - 1 (mod images * s, s = features // (2 neighbours)), feature k of an image is a seeded permutation of them;
+    image i is paired with (i + d) mod images for d = 1 .. ``neighbours``, and each pair matches ``matches_per_pair`` points
+    of the two images' overlap (a contiguous run of them at a random start), ``wrong_fraction`` of them re-paired to a
+    random feature of the second image.  Returns dict(image_offset (I + 1,), pairs (Q, 2), match_offset (Q + 1,),
+    match_index (E, 2), all int32, feature_points (F,) int64 the latent point of each global id)."""
+    if not 1 <= neighbours < images:
+        raise ValueError("neighbours must be in [1, images)")
+    rng = np.random.default_rng(seed)
+    step = max(1, features // (2 * neighbours))
+    P = max(images * step, features)
+    if matches_per_pair > features - neighbours * step:
+        raise ValueError("matches_per_pair exceeds the overlap of the farthest neighbours")
+    perm = rng.permuted(np.tile(np.arange(features, dtype=np.int64), (images, 1)), axis=1)   # canonical k -> local index
+    canon = np.argsort(perm, axis=1)                                                          # local index -> canonical k
+    feature_points = ((np.arange(images, dtype=np.int64)[:, None] * step + canon) % P).reshape(-1)
+    a_img = np.repeat(np.arange(images, dtype=np.int64), neighbours)
+    d = np.tile(np.arange(1, neighbours + 1, dtype=np.int64), images)
+    b_img = (a_img + d) % images
+    Q = len(a_img)
+    overlap = features - d * step
+    start = (rng.random(Q) * (overlap - matches_per_pair + 1)).astype(np.int64)
+    t = start[:, None] + np.arange(matches_per_pair, dtype=np.int64)[None, :]   # canonical index in image b
+    ka, kb = t + d[:, None] * step, t
+    la = perm[a_img[:, None], ka]
+    lb = perm[b_img[:, None], kb]
+    wrong = rng.random(lb.shape) < wrong_fraction
+    lb = np.where(wrong, rng.integers(0, features, lb.shape), lb)
+    off = np.arange(images + 1, dtype=np.int64) * features
+    return dict(image_offset=off.astype(np.int32), pairs=np.column_stack([a_img, b_img]).astype(np.int32),
+                match_offset=(np.arange(Q + 1, dtype=np.int64) * matches_per_pair).astype(np.int32),
+                match_index=np.column_stack([la.reshape(-1), lb.reshape(-1)]).astype(np.int32), feature_points=feature_points)
