@@ -290,7 +290,8 @@ int sfm_inlier_mask(const double* corr, int64_t n, const double* E, const int32_
  * The reference's fit_with_ransac (ransac.py:55-86) with a six-item sample, a six-point DLT fitter and the squared
  * reprojection error in pixels as the scorer.  pts: dev [batch,n,5] = {X, Y, Z, u, v}: a 3-D point in the frame of camera 1
  * and the pixel of its match in the new view.  K: host [9], the camera matrix row-major; row 2 must be (0, 0, 1)
- * (SFM_EINVAL otherwise).  S: dev int32 [batch,h_count,8], the sample tables of sfm_sample_philox / sfm_pyshuffle_table:
+ * and K00 K11 - K01 K10 neither zero nor NaN (SFM_EINVAL otherwise, here and in every entry point below that takes K); all
+ * six entries of rows 0 and 1 count in every kernel, the DLT's normalisation included, so K may carry skew.  S: dev int32 [batch,h_count,8], the sample tables of sfm_sample_philox / sfm_pyshuffle_table:
  * the first 6 entries of each row are the sample (an entry outside [0, n) flags the hypothesis).  model: dev
  * [batch,h_count,12] = R row-major (9) | t (3), x_cam = R X + t.  flags: dev int32 [batch,h_count], SFM_FIT_DEGENERATE when
  * sigma_11 / sigma_1 of the conditioned 12 x 12 DLT matrix is below 1e-9 (coplanar or collinear points) or not a number.

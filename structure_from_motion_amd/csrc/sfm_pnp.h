@@ -15,7 +15,24 @@ constexpr int kPnPFields = 5;  // X, Y, Z, u, v
 
 struct PnPCamera {
     double k00, k01, k02, k10, k11, k12;  // rows 0 and 1 of K; row 2 is (0, 0, 1)
+    int general;                          // k01 or k10 is not exactly zero (decided on the host: uniform over a launch)
 };
+
+// Pixel -> normalised image coordinates, (x, y, 1) = K^-1 (u, v, 1): the 2 x 2 block of K inverted by Cramer's rule, in the
+// operation order of sfmp3p::bearing, pnp/pnp.py::normalized_coords and tests/pnp_oracle.py::normalized_coords.  A camera
+// with k01 = k10 = 0 keeps the two plain divisions (u - k02) / k00, (v - k12) / k11, so its results keep their bits.
+SFM_DEVICE void normalized_coords(const PnPCamera& k, double u, double v, double& x, double& y) {
+    const double du = u - k.k02;
+    const double dv = v - k.k12;
+    if (k.general) {
+        const double det = k.k00 * k.k11 - k.k01 * k.k10;
+        x = (du * k.k11 - k.k01 * dv) / det;
+        y = (k.k00 * dv - k.k10 * du) / det;
+    } else {
+        x = du / k.k00;
+        y = dv / k.k11;
+    }
+}
 
 // --------------------------------------------------------------------------------------------------
 // Squared reprojection error in pixels of one item under one model m = {R (9) | t (3)}.
@@ -109,15 +126,21 @@ SFM_DEVICE void centre(const double* pose, double (&c)[3]) {
     for (int k = 0; k < 3; ++k) c[k] = -((pose[k] * pose[9] + pose[3 + k] * pose[10]) + pose[6 + k] * pose[11]);
 }
 
-// Rows 0 and 1 of a host camera matrix K [9]; SFM_EINVAL unless row 2 is (0, 0, 1).
+// Rows 0 and 1 of a host camera matrix K [9]; SFM_EINVAL unless row 2 is (0, 0, 1) and the 2 x 2 block of rows 0 and 1
+// is invertible (K00 K11 - K01 K10 neither zero nor NaN).
 inline int camera_from(const double* K, PnPCamera& cam, const char* fn) {
     if (!K) return sfmhost::fail(SFM_EINVAL, "sfm_pnp: null camera matrix");
+    char msg[160];
     if (K[6] != 0.0 || K[7] != 0.0 || K[8] != 1.0) {
-        char msg[160];
         snprintf(msg, sizeof msg, "%s: row 2 of the camera matrix must be (0, 0, 1)", fn);
         return sfmhost::fail(SFM_EINVAL, msg);
     }
-    cam = PnPCamera{K[0], K[1], K[2], K[3], K[4], K[5]};
+    const double det = K[0] * K[4] - K[1] * K[3];
+    if (det == 0.0 || det != det) {   // zero or NaN
+        snprintf(msg, sizeof msg, "%s: the camera matrix is singular (K00 K11 - K01 K10 is zero or not a number)", fn);
+        return sfmhost::fail(SFM_EINVAL, msg);
+    }
+    cam = PnPCamera{K[0], K[1], K[2], K[3], K[4], K[5], (K[1] != 0.0 || K[3] != 0.0) ? 1 : 0};
     return SFM_OK;
 }
 

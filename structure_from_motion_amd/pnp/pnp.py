@@ -35,28 +35,42 @@ class PnPCalculationError(Exception):
 
 
 def check_camera_matrix(camera_matrix) -> npt.NDArray:
-    """K as a float64 (3, 3) array; row 2 must be (0, 0, 1) (the scorer's p_2 = c_2)."""
+    """K as a float64 (3, 3) array; row 2 must be (0, 0, 1) (the scorer's p_2 = c_2) and the 2 x 2 block of rows 0 and 1
+    invertible.  All six entries of rows 0 and 1 count everywhere in this module: K may carry skew and K[1, 0]."""
     K = np.asarray(camera_matrix, dtype=np.float64)
     if K.shape != (3, 3):
         raise ValueError(f"camera matrix must be 3x3, got shape {K.shape}")
     if not np.array_equal(K[2], [0.0, 0.0, 1.0]):
         raise ValueError("row 2 of the camera matrix must be (0, 0, 1)")
+    det = K[0, 0] * K[1, 1] - K[0, 1] * K[1, 0]
+    if det == 0.0 or np.isnan(det):
+        raise ValueError("the camera matrix is singular: K[0,0] K[1,1] - K[0,1] K[1,0] is zero or not a number")
     return K
+
+
+def normalized_coords(K, u, v):
+    """(x, y) with (x, y, 1) = K^-1 (u, v, 1), in the operation order of csrc/sfm_pnp.h (normalized_coords): the 2 x 2 block
+    of K by Cramer's rule; when K[0][1] and K[1][0] are both exactly zero, the two plain divisions (the same values, and the
+    bits of the results at such cameras).  u, v: floats or arrays."""
+    du = u - K[0][2]
+    dv = v - K[1][2]
+    if K[0][1] == 0.0 and K[1][0] == 0.0:
+        return du / K[0][0], dv / K[1][1]
+    det = K[0][0] * K[1][1] - K[0][1] * K[1][0]
+    return (du * K[1][1] - K[0][1] * dv) / det, (K[0][0] * dv - K[1][0] * du) / det
 
 
 def pnp_model_fitter(items: Sequence[PnPItem], camera_matrix: npt.NDArray) -> PnPModel:
     """(R, t) from exactly six 2D-3D pairs by the six-point DLT (the RANSAC model fitter; host form).
 
-    K-normalised 2-D side; the 3-D side conditioned (centroid subtracted, mean distance sqrt(3)); the null vector of the
-    12 x 12 system A p = 0 as P = [M | p4]; conditioning undone; P negated if det(M) < 0; R = U V^T of M = U S V^T;
-    t = p4 / mean(S).  Raises PnPCalculationError for a degenerate sample (see DEGENERATE_FLOOR)."""
+    K-normalised 2-D side (``normalized_coords``: the whole 2 x 2 block of K); the 3-D side conditioned (centroid
+    subtracted, mean distance sqrt(3)); the null vector of the 12 x 12 system A p = 0 as P = [M | p4]; conditioning
+    undone; P negated if det(M) < 0; R = U V^T of M = U S V^T; t = p4 / mean(S).  Raises PnPCalculationError for a degenerate sample (see DEGENERATE_FLOOR)."""
     if len(items) != SAMPLE_SIZE:
         raise ValueError("Six 2D-3D pairs are expected.")
     K = np.asarray(camera_matrix, dtype=np.float64)
-    fx, fy, cx, cy = K[0][0], K[1][1], K[0][2], K[1][2]
     X = np.array([np.asarray(item[0], dtype=np.float64).reshape(3) for item in items])
-    x = np.array([(item[1].x - cx) / fx for item in items])
-    y = np.array([(item[1].y - cy) / fy for item in items])
+    x, y = normalized_coords(K, np.array([float(item[1].x) for item in items]), np.array([float(item[1].y) for item in items]))
     centroid = X.mean(axis=0)
     scale = np.sqrt(3.0) / np.linalg.norm(X - centroid, axis=1).mean()
     Xh = np.hstack([(X - centroid) * scale, np.ones((SAMPLE_SIZE, 1))])

@@ -9,12 +9,22 @@ class Degenerate(Exception):
     pass
 
 
+def normalized_coords(K, u, v):
+    """(x, y) with (x, y, 1) = K^-1 (u, v, 1) in the operation order of csrc/sfm_pnp.h: Cramer's rule on the 2 x 2 block, or
+    the two plain divisions when K[0][1] and K[1][0] are both exactly zero."""
+    du = u - K[0][2]
+    dv = v - K[1][2]
+    if K[0][1] == 0.0 and K[1][0] == 0.0:
+        return du / K[0][0], dv / K[1][1]
+    det = K[0][0] * K[1][1] - K[0][1] * K[1][0]
+    return (du * K[1][1] - K[0][1] * dv) / det, (K[0][0] * dv - K[1][0] * du) / det
+
+
 def fit(X, uv, K):
     """(R, t, ratio) from six 3-D points X (6, 3) and their pixels uv (6, 2); ratio = sigma_11 / sigma_1 of the conditioned A."""
     X = np.asarray(X, dtype=np.float64)
     uv = np.asarray(uv, dtype=np.float64)
-    x = (uv[:, 0] - K[0][2]) / K[0][0]
-    y = (uv[:, 1] - K[1][2]) / K[1][1]
+    x, y = normalized_coords(K, uv[:, 0], uv[:, 1])
     c = X.mean(axis=0)
     s = np.sqrt(3.0) / np.linalg.norm(X - c, axis=1).mean()
     Xh = np.hstack([(X - c) * s, np.ones((6, 1))])

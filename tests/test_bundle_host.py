@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import bundle_oracle as bo
+import geometry_cases as gc
 import pnp_refine_oracle as ro
 from oracle import sfm_oracle
 from structure_from_motion_amd import synthetic
@@ -37,9 +38,13 @@ def test_dense_and_schur_solvers_agree(C, P, fixed):
     assert np.max(np.abs(dense["points"] - schur["points"])) <= 1e-9
 
 
-def test_gradient_matches_finite_differences():
-    """g = J^T r is half the gradient of F = sum e, along the LM parametrisation of a free camera and of a point."""
-    pr = synthetic.bundle_problem(4, 50, per_point=3, seed=3)
+@pytest.mark.parametrize("world", ["id", "turned"])
+@pytest.mark.parametrize("camera", ["bench", "skew", "affine"])
+def test_gradient_matches_finite_differences(camera, world):
+    """g = J^T r is half the gradient of F = sum e, along the LM parametrisation of a free camera and of a point; at cameras
+    with K01 and K10 and in a turned world too (tests/geometry_cases.py)."""
+    K = gc.CAMERAS[camera]
+    pr = gc.problem_to(world, synthetic.bundle_problem(4, 50, per_point=3, seed=3, K=K))
     prob = bo.Problem(K, pr["poses"], pr["points"], pr["camera_indices"], pr["point_indices"], pr["pixels"], (0,))
     s = prob.system(pr["poses"], pr["points"])
 

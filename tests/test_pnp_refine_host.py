@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+import geometry_cases as gc
 import pnp_oracle as po
 import pnp_refine_oracle as ro
 from structure_from_motion_amd import synthetic
@@ -32,8 +33,11 @@ def test_oracle_converges_to_ground_truth_without_noise():
     assert np.max(np.abs(out["t"] - t)) <= 1e-9
 
 
-def test_oracle_result_is_stationary_and_gradient_matches_finite_differences():
-    pts, R, t = po.scene(2000, seed=4, K=K, outlier_fraction=0.3, noise_px=0.5)
+@pytest.mark.parametrize("world", ["id", "turned"])
+@pytest.mark.parametrize("camera", ["bench", "skew", "affine"])
+def test_oracle_result_is_stationary_and_gradient_matches_finite_differences(camera, world):
+    K = gc.CAMERAS[camera]
+    pts, R, t = gc.pnp_to(world, *po.scene(2000, seed=4, K=K, outlier_fraction=0.3, noise_px=0.5))
     inliers = pts[po.score_values(R, t, K, pts) <= 4.0]
     R0, t0 = ro.apply_step(R, t, np.array([0.002, -0.001, 0.001, 0.01, 0.0, 0.01]))
     # g = J^T r is half the gradient of C = sum e: central differences along the LM parametrisation

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import geometry_cases as gc
 import tracks_oracle as to
 from oracle import sfm_oracle
 from structure_from_motion_amd import synthetic
@@ -59,9 +60,14 @@ def test_oracle_two_view_track_is_the_reference_dlt():
     assert np.max(np.abs(out["points"][both] - ref) / np.linalg.norm(ref, axis=1, keepdims=True)) <= 1e-9
 
 
-def test_oracle_gradient_matches_finite_differences():
-    """g = J^T r is half the gradient of F = sum e; H is J^T J."""
-    sc = _scene(noise_px=1.0)
+@pytest.mark.parametrize("world", ["id", "turned"])
+@pytest.mark.parametrize("camera", ["bench", "skew", "affine"])
+def test_oracle_gradient_matches_finite_differences(camera, world):
+    """g = J^T r is half the gradient of F = sum e; H is J^T J; at cameras with K01 and K10 and in a turned world too
+    (tests/geometry_cases.py)."""
+    K = gc.CAMERAS[camera]
+    sc = synthetic.multi_view_scene(6, 200, 3, 1.0, 0.0, K=K)
+    sc = dict(sc, poses_true=gc.poses_to(world, sc["poses_true"]), points_true=gc.points_to(world, sc["points_true"]))
     out = _tri(sc)
     order = np.lexsort((np.arange(len(sc["point_indices"])), sc["point_indices"]))
     for p in (0, 7, 31):
