@@ -473,6 +473,41 @@ int sfm_bundle_adjust_pcg(const double* K, int64_t cameras, int64_t points, int6
                           double cg_tolerance, double* poses_out, double* points_out, sfm_bundle_pcg_info* info,
                           void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- robust losses of both bundle adjusters (csrc/sfm_loss.h; an extension, off unless asked for) ----
+ * These symbols were added under ABI 15 without a version change: they are new, and nothing an ABI-15 caller uses changed. */
+
+#define SFM_BUNDLE_LOSS_SQUARED 0 /* rho(e) = e */
+#define SFM_BUNDLE_LOSS_HUBER 1   /* rho(e) = e for e <= a^2, else 2 a sqrt(e) - a^2 */
+#define SFM_BUNDLE_LOSS_CAUCHY 2  /* rho(e) = a^2 log1p(e / a^2) */
+
+typedef struct sfm_bundle_options {
+    int32_t loss;      /* SFM_BUNDLE_LOSS_* */
+    int32_t reserved;  /* 0 */
+    double loss_scale; /* a, in pixels: finite and positive (read for the squared loss too, where it has no effect) */
+} sfm_bundle_options;
+
+/* sfm_bundle_adjust and sfm_bundle_adjust_pcg on F = sum over the observations of rho(e), e the squared reprojection error
+ * in px^2: initial_cost, final_cost, the accept test, the relative-decrease stop and SFM_BUNDLE_BAD_START all use this F
+ * (rho(+inf) = +inf).  The linearisation is iteratively reweighted least squares in its first-order form: the residual and
+ * both Jacobians of an observation are multiplied by sqrt(w), w = rho'(e) at the linearisation point (1 | a / sqrt(e) above
+ * a^2 | 1 / (1 + e / a^2)); everything else is the squared adjuster's.  options == NULL is the squared loss, and a squared
+ * call computes the bits of the entry point without options.  SFM_EINVAL before the first launch for a loss outside 0..2,
+ * reserved != 0 or a loss_scale that is not finite and positive.  The dense adjuster's workspace is
+ * sfm_bundle_workspace_bytes for every loss; the iterative one keeps sqrt(w) per observation for a non-squared loss and
+ * needs sfm_bundle_pcg_workspace_bytes_ex (-1 also for options it refuses; the plain size for NULL or squared). */
+int sfm_bundle_adjust_ex(const double* K, int64_t cameras, int64_t points, int64_t observations, const uint8_t* fixed,
+                         const double* poses_in, const double* points_in, const int32_t* camera_index,
+                         const int32_t* point_index, const double* pixels, int max_steps, double* poses_out,
+                         double* points_out, sfm_bundle_info* info, void* workspace, int64_t workspace_bytes, void* stream,
+                         const sfm_bundle_options* options);
+int64_t sfm_bundle_pcg_workspace_bytes_ex(int64_t cameras, int64_t points, int64_t observations,
+                                          const sfm_bundle_options* options);
+int sfm_bundle_adjust_pcg_ex(const double* K, int64_t cameras, int64_t points, int64_t observations, const uint8_t* fixed,
+                             const double* poses_in, const double* points_in, const int32_t* camera_index,
+                             const int32_t* point_index, const double* pixels, int max_steps, int max_cg_iterations,
+                             double cg_tolerance, double* poses_out, double* points_out, sfm_bundle_pcg_info* info,
+                             void* workspace, int64_t workspace_bytes, void* stream, const sfm_bundle_options* options);
+
 /* ---- triangulation of multi-view tracks (csrc/sfm_tracks.hip; an extension, off unless asked for) ----
  * These symbols were added under ABI 14 without a version change: they are new, and nothing an ABI-14 caller uses changed. */
 

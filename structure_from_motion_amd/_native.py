@@ -172,13 +172,26 @@ SIGNATURES = {
     "sfm_pnp_refine": [_P, _I64, _I64, _P, _P, _P, _P, _D, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P],
     "sfm_bundle_adjust": [_P, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _I64, _P],
     "sfm_bundle_adjust_pcg": [_P, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, _D, _P, _P, _P, _P, _I64, _P],
+    "sfm_bundle_adjust_ex": [_P, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _I64, _P, _P],
+    "sfm_bundle_adjust_pcg_ex": [_P, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, _D, _P, _P, _P, _P, _I64, _P,
+                                 _P],
     "sfm_triangulate_tracks": [_P, _I64, _I64, _I64, _P, _P, _P, _P, C.c_int, _D, _D, C.c_int, _P, _P, _P, _P, _P, _P, _I64,
                                _P],
     "sfm_build_tracks": [_I64, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P],
 }
 OTHER_SYMBOLS = ["sfm_last_error", "sfm_abi_version", "sfm_score_workspace_bytes", "sfm_score_workspace_bytes_ex",
                  "sfm_fit_trace_doubles", "sfm_match_summary_workspace_bytes", "sfm_bundle_workspace_bytes",
-                 "sfm_tracks_workspace_bytes", "sfm_bundle_pcg_workspace_bytes", "sfm_build_tracks_workspace_bytes"]
+                 "sfm_tracks_workspace_bytes", "sfm_bundle_pcg_workspace_bytes", "sfm_build_tracks_workspace_bytes",
+                 "sfm_bundle_pcg_workspace_bytes_ex"]
+
+# the losses of both bundle adjusters, in the order of their SFM_BUNDLE_LOSS_* codes (include/sfm_hip.h)
+BUNDLE_LOSSES = ("squared", "huber", "cauchy")
+
+
+class BundleOptions(C.Structure):
+    """sfm_bundle_options"""
+    _fields_ = [("loss", C.c_int32), ("reserved", C.c_int32), ("loss_scale", C.c_double)]
+
 
 _lib = None
 
@@ -220,6 +233,8 @@ def load() -> C.CDLL:
     lib.sfm_tracks_workspace_bytes.argtypes = [_I64, _I64]
     lib.sfm_bundle_pcg_workspace_bytes.restype = C.c_int64
     lib.sfm_bundle_pcg_workspace_bytes.argtypes = [_I64, _I64, _I64]
+    lib.sfm_bundle_pcg_workspace_bytes_ex.restype = C.c_int64
+    lib.sfm_bundle_pcg_workspace_bytes_ex.argtypes = [_I64, _I64, _I64, _P]
     lib.sfm_build_tracks_workspace_bytes.restype = C.c_int64
     lib.sfm_build_tracks_workspace_bytes.argtypes = [_I64, _I64, _I64]
     if lib.sfm_abi_version() != ABI_VERSION:

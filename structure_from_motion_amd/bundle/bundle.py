@@ -1,8 +1,9 @@
 """Bundle adjustment of camera poses and 3-D points on the GPU (``sfm_bundle_adjust``).
 
 Poses are ``R (9) | t (3)`` rows with ``x_cam = R X + t`` — the PnP model layout.  All cameras share one camera matrix
-``K`` whose row 2 is (0, 0, 1); intrinsics are not optimised.  The cost is the sum over the observations of the squared
-reprojection error of the PnP scorer.  Fixed cameras and points with fewer than two observations are held; with exactly
+``K`` whose row 2 is (0, 0, 1); intrinsics are not optimised.  The cost is the sum over the observations of rho(e), e the
+squared reprojection error of the PnP scorer and rho the loss: ``"squared"`` (rho = e, the default), ``"huber"`` or
+``"cauchy"`` with a scale in pixels.  Fixed cameras and points with fewer than two observations are held; with exactly
 one fixed camera the scale is held by the distance from it to the lowest-index free camera.
 
 Two linear solvers sit behind the same LM loop: ``"dense"`` factors the reduced camera system (at most 64 cameras,
@@ -16,6 +17,7 @@ from typing import Sequence, Tuple
 import numpy as np
 import numpy.typing as npt
 
+from .._native import BUNDLE_LOSSES as LOSSES
 from ..pnp.pnp import check_camera_matrix
 
 MAX_CAMERAS = 64   # of the dense solver
@@ -53,6 +55,8 @@ def bundle_adjust(
     linear_solver: str = "dense",
     max_cg_iterations: int = 100,
     cg_tolerance: float = 0.1,
+    loss: str = "squared",
+    loss_scale: float = 1.0,
 ):
     """Minimise the summed squared reprojection error over the free cameras' poses and the points.
 
@@ -65,7 +69,13 @@ def bundle_adjust(
     ``linear_solver="iterative"`` takes any number of cameras (at least 1) and solves each LM step's reduced camera
     system by preconditioned conjugate gradients: at most ``max_cg_iterations`` (>= 1) iterations, stopping once the
     residual is below ``cg_tolerance`` (in (0, 1)) times the right-hand side.  ``info`` is then a
-    ``device.BundlePcgInfo`` (the ``BundleInfo`` fields plus ``cg_iterations`` and ``cg_max``)."""
+    ``device.BundlePcgInfo`` (the ``BundleInfo`` fields plus ``cg_iterations`` and ``cg_max``).
+
+    ``loss`` is one of ``LOSSES``.  With e an observation's squared reprojection error in px^2 and a = ``loss_scale`` in
+    pixels (finite, > 0; no effect on ``"squared"``): ``"huber"`` is e up to a^2 and 2 a sqrt(e) - a^2 above, ``"cauchy"``
+    is a^2 log1p(e / a^2).  ``info.initial_cost`` and ``info.final_cost`` are then the sums of rho(e), not of e, and the
+    accept test and the stops use them.  Huber keeps a constant pull of 2 a per pixel on an outlier and suits moderate
+    ones; Cauchy re-descends and suits gross ones."""
     K = check_camera_matrix(camera_matrix)
     poses = _array(poses, "poses", (-1, 12))
     points = _array(points_3d, "points_3d", (-1, 3))
@@ -97,18 +107,24 @@ def bundle_adjust(
         raise ValueError(f"fixed_cameras must be distinct camera indices in [0, {n_cams}), got {fixed}")
     if isinstance(max_steps, bool) or not isinstance(max_steps, (int, np.integer)) or max_steps < 0:
         raise ValueError(f"max_steps must be a non-negative integer, got {max_steps!r}")
+    if not isinstance(loss, str) or loss not in LOSSES:
+        raise ValueError(f"loss must be one of {LOSSES}, got {loss!r}")
+    if (isinstance(loss_scale, bool) or not isinstance(loss_scale, (int, float, np.integer, np.floating))
+            or not np.isfinite(float(loss_scale)) or not float(loss_scale) > 0.0):
+        raise ValueError(f"loss_scale must be a finite number > 0, got {loss_scale!r}")
     import torch
 
     from .. import device
 
     device.require_gpu()
+    robust = {} if loss == "squared" else dict(loss=loss, loss_scale=float(loss_scale))   # squared: today's call
     if iterative:
         poses_d, points_d, info = device.bundle_adjust_pcg(
             device.to_device(poses), device.to_device(points), device.to_device(cams, dtype=torch.int32),
             device.to_device(pts, dtype=torch.int32), device.to_device(pixels), K, fixed, int(max_steps),
-            int(max_cg_iterations), float(cg_tolerance))
+            int(max_cg_iterations), float(cg_tolerance), **robust)
         return poses_d.cpu().numpy(), points_d.cpu().numpy(), device.read_bundle_pcg_info(info)
     poses_d, points_d, info = device.bundle_adjust(
         device.to_device(poses), device.to_device(points), device.to_device(cams, dtype=torch.int32),
-        device.to_device(pts, dtype=torch.int32), device.to_device(pixels), K, fixed, int(max_steps))
+        device.to_device(pts, dtype=torch.int32), device.to_device(pixels), K, fixed, int(max_steps), **robust)
     return poses_d.cpu().numpy(), points_d.cpu().numpy(), device.read_bundle_info(info)

@@ -18,6 +18,10 @@
 //   decide_kernel<256>      one workgroup: the cost in a fixed order, accept / reject, lambda, the gauge scale, stops
 //   commit_kernel           an accepted trial becomes the current estimate (rescaled when one camera is fixed)
 // No floating-point atomics anywhere: every sum runs in an order fixed by the sizes alone, so a call is bit-reproducible.
+//
+// A robust loss (csrc/sfm_loss.h) runs the kRobust = true forms of linearize_kernel, camera_kernel and
+// bundle_trial_kernel: W, V, U and both gradients are stored weighted, so the Schur complement, the solve and the
+// back-substitution are the same launches, and the workspace is the same size.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -229,7 +233,8 @@ __global__ __launch_bounds__(kSolveThreads) void bundle_solve_kernel(int F, int 
 }
 
 // Thread per point: dX_p = V_p*^-1 (-g_p - sum over its free-camera observations of W^T dc), the trial point, the trial cost
-// of its observations and its share of |delta|^2 and |x|^2; partials per block.
+// of its observations (kRobust: the sum of rho) and its share of |delta|^2 and |x|^2; partials per block.
+template <bool kRobust>
 __global__ __launch_bounds__(kThreads) void bundle_trial_kernel(Obs obs, int P, PnPCamera cam, const double* __restrict__ points,
                                                                 int C, Ws w) {
     __shared__ double pose[kMaxCameras * 12];
@@ -274,7 +279,8 @@ __global__ __launch_bounds__(kThreads) void bundle_trial_kernel(Obs obs, int P, 
         for (int i = 0; i < 3; ++i) l.tpts[3 * (int64_t)p + i] = X[i];
         for (int q = q0; q < q1; ++q) {
             const int m = l.ord_p[q];
-            a[0] += pnp_score(pose + 12 * l.camp[q], cam, X[0], X[1], X[2], obs.uv[2 * (int64_t)m], obs.uv[2 * (int64_t)m + 1]);
+            const double e = pnp_score(pose + 12 * l.camp[q], cam, X[0], X[1], X[2], obs.uv[2 * (int64_t)m], obs.uv[2 * (int64_t)m + 1]);
+            a[0] += kRobust ? sfmloss::rho(l.loss, e) : e;
         }
     }
     sfm::block_sum<3, kThreads>(a, part, total);
@@ -282,6 +288,73 @@ __global__ __launch_bounds__(kThreads) void bundle_trial_kernel(Obs obs, int P, 
 }
 
 __global__ void bundle_finish_kernel(Lm w, sfm_bundle_info* __restrict__ info) { sfmlm::write_info(w.st, info); }
+
+// A checked call: everything enqueue needs.
+struct Job {
+    PnPCamera cam;
+    int64_t C, P, M;
+    uint64_t mask;
+    const double *poses_in, *points_in;
+    Obs obs;
+    int max_steps;
+    double *poses_out, *points_out;
+    sfm_bundle_info* info;
+    hipStream_t st;
+};
+
+// Enqueue the whole call; kRobust picks the kernels of a non-squared loss (w.lm.loss).
+template <bool kRobust>
+int enqueue(const Job& job, Ws& w, const sfmlm::Core& core) {
+    const PnPCamera& cam = job.cam;
+    const int64_t C = job.C, P = job.P, M = job.M;
+    const uint64_t mask = job.mask;
+    const double *poses_in = job.poses_in, *points_in = job.points_in;
+    double *poses_out = job.poses_out, *points_out = job.points_out;
+    const int max_steps = job.max_steps;
+    hipStream_t st = job.st;
+    const Obs& obs = job.obs;
+    const int F = (int)C - __builtin_popcountll(mask);
+    const int f = __builtin_ctzll(mask);                                        // the gauge's fixed camera
+    const int anchor = C - F == 1 && F > 0 ? __builtin_ctzll(~mask) : -1;       // one fixed camera: the lowest free one
+    const unsigned pgrid = sfmhost::grid_for(P, kThreads), icgrid = sfmhost::grid_for(P > C ? P : C, kThreads);
+    const int pblocks = (int)((P + kThreads - 1) / kThreads);
+    const unsigned pairs = (unsigned)(F * (F + 1) / 2);
+
+    // the output starts as the input; the state and the point counters start at zero
+    if (poses_out != poses_in && hipMemcpyAsync(poses_out, poses_in, 8 * 12 * C, hipMemcpyDeviceToDevice, st) != hipSuccess)
+        return check_launch("sfm_bundle_adjust: copy poses");
+    if (P > 0 && points_out != points_in &&
+        hipMemcpyAsync(points_out, points_in, 8 * 3 * P, hipMemcpyDeviceToDevice, st) != hipSuccess)
+        return check_launch("sfm_bundle_adjust: copy points");
+    if (hipMemsetAsync(w.lm.off_p, 0, 4 * (P + 1), st) != hipSuccess) return check_launch("sfm_bundle_adjust: clear the counters");
+    hipLaunchKernelGGL(bundle_init_kernel, dim3(1), dim3(kMaxCameras), 0, st, mask, (int)C, w.lm);
+    w.pos_c = sfmlm::launch_orders(obs, M, C, P, core, st);
+    auto linearize = [&]() {
+        hipLaunchKernelGGL((sfmlm::linearize_kernel<true, kRobust>), dim3(pgrid), dim3(kThreads), 0, st, obs, (int)P, cam, poses_out,
+                           points_out, (int)C, w.lm, w.W);
+        if (F > 0)
+            hipLaunchKernelGGL(sfmlm::camera_kernel<kRobust>, dim3((unsigned)F), dim3(kThreads), 0, st, obs, cam, poses_out, points_out,
+                               w.lm);
+    };
+    linearize();
+    hipLaunchKernelGGL(sfmlm::start_kernel<kThreads>, dim3(1), dim3(kThreads), 0, st, pblocks, f, anchor, max_steps, poses_out,
+                       w.lm);
+    for (int step = 0; step < max_steps; ++step) {
+        linearize();
+        hipLaunchKernelGGL(sfmlm::point_kernel, dim3(pgrid), dim3(kThreads), 0, st, (int)P, w.lm);
+        if (pairs > 0) hipLaunchKernelGGL(bundle_schur_kernel, dim3(pairs), dim3(kThreads), 0, st, F, w);
+        if (F <= kLdsFree)
+            hipLaunchKernelGGL(bundle_solve_kernel<true>, dim3(1), dim3(kSolveThreads), 0, st, F, (int)C, poses_out, w);
+        else
+            hipLaunchKernelGGL(bundle_solve_kernel<false>, dim3(1), dim3(kSolveThreads), 0, st, F, (int)C, poses_out, w);
+        hipLaunchKernelGGL(bundle_trial_kernel<kRobust>, dim3(pgrid), dim3(kThreads), 0, st, obs, (int)P, cam, points_out, (int)C, w);
+        hipLaunchKernelGGL(sfmlm::decide_kernel<kThreads>, dim3(1), dim3(kThreads), 0, st, pblocks, anchor, max_steps, w.lm);
+        hipLaunchKernelGGL(sfmlm::commit_kernel, dim3(icgrid), dim3(kThreads), 0, st, (int)P, (int)C, anchor, poses_out,
+                           points_out, w.lm);
+    }
+    hipLaunchKernelGGL(bundle_finish_kernel, dim3(1), dim3(1), 0, st, w.lm, job.info);
+    return check_launch("sfm_bundle_adjust");
+}
 
 }  // namespace
 
@@ -296,15 +369,19 @@ int64_t sfm_bundle_workspace_bytes(int64_t cameras, int64_t points, int64_t obse
     return carve(0, cameras, points, observations, &w, &core);
 }
 
-int sfm_bundle_adjust(const double* K, int64_t cameras, int64_t points, int64_t observations, const uint8_t* fixed,
-                      const double* poses_in, const double* points_in, const int32_t* camera_index,
-                      const int32_t* point_index, const double* pixels, int max_steps, double* poses_out,
-                      double* points_out, sfm_bundle_info* info, void* workspace, int64_t workspace_bytes, void* stream) {
+int sfm_bundle_adjust_ex(const double* K, int64_t cameras, int64_t points, int64_t observations, const uint8_t* fixed,
+                         const double* poses_in, const double* points_in, const int32_t* camera_index,
+                         const int32_t* point_index, const double* pixels, int max_steps, double* poses_out,
+                         double* points_out, sfm_bundle_info* info, void* workspace, int64_t workspace_bytes, void* stream,
+                         const sfm_bundle_options* options) {
     // every check before the first launch: a refused call has enqueued nothing
     if (cameras < 1 || points < 0 || observations < 0 || max_steps < 0) return fail(SFM_EINVAL, "sfm_bundle_adjust: bad size");
     if (cameras > kMaxCameras) return fail(SFM_EINVAL, "sfm_bundle_adjust: more than 64 cameras");
     if (points > 0x7FFFFFFF || observations > 0x7FFFFFFF)
         return fail(SFM_EINVAL, "sfm_bundle_adjust: points and observations must be below 2^31");
+    sfmloss::Loss loss;
+    if (!sfmloss::from_options(options, loss))
+        return fail(SFM_EINVAL, "sfm_bundle_adjust: options need a loss in 0..2, reserved = 0 and a finite loss_scale > 0");
     PnPCamera cam;
     const int rc = camera_from(K, cam, "sfm_bundle_adjust");
     if (rc != SFM_OK) return rc;
@@ -323,49 +400,18 @@ int sfm_bundle_adjust(const double* K, int64_t cameras, int64_t points, int64_t 
         return fail(SFM_EINVAL, "sfm_bundle_adjust: workspace too small");
     if (((uintptr_t)workspace & 15) != 0) return fail(SFM_EINVAL, "sfm_bundle_adjust: workspace must be 16-byte aligned");
 
-    hipStream_t st = (hipStream_t)stream;
-    const Obs obs{camera_index, point_index, pixels};
-    const int F = (int)C - __builtin_popcountll(mask);
-    const int f = __builtin_ctzll(mask);                                        // the gauge's fixed camera
-    const int anchor = C - F == 1 && F > 0 ? __builtin_ctzll(~mask) : -1;       // one fixed camera: the lowest free one
-    const unsigned pgrid = sfmhost::grid_for(P, kThreads), icgrid = sfmhost::grid_for(P > C ? P : C, kThreads);
-    const int pblocks = (int)((P + kThreads - 1) / kThreads);
-    const unsigned pairs = (unsigned)(F * (F + 1) / 2);
+    w.lm.loss = loss;
+    const Job job{cam, C, P, M, mask, poses_in, points_in, Obs{camera_index, point_index, pixels}, max_steps, poses_out, points_out,
+                  info, (hipStream_t)stream};
+    return loss.kind == SFM_BUNDLE_LOSS_SQUARED ? enqueue<false>(job, w, core) : enqueue<true>(job, w, core);
+}
 
-    // the output starts as the input; the state and the point counters start at zero
-    if (poses_out != poses_in && hipMemcpyAsync(poses_out, poses_in, 8 * 12 * C, hipMemcpyDeviceToDevice, st) != hipSuccess)
-        return check_launch("sfm_bundle_adjust: copy poses");
-    if (P > 0 && points_out != points_in &&
-        hipMemcpyAsync(points_out, points_in, 8 * 3 * P, hipMemcpyDeviceToDevice, st) != hipSuccess)
-        return check_launch("sfm_bundle_adjust: copy points");
-    if (hipMemsetAsync(w.lm.off_p, 0, 4 * (P + 1), st) != hipSuccess) return check_launch("sfm_bundle_adjust: clear the counters");
-    hipLaunchKernelGGL(bundle_init_kernel, dim3(1), dim3(kMaxCameras), 0, st, mask, (int)C, w.lm);
-    w.pos_c = sfmlm::launch_orders(obs, M, C, P, core, st);
-    auto linearize = [&]() {
-        hipLaunchKernelGGL(sfmlm::linearize_kernel<true>, dim3(pgrid), dim3(kThreads), 0, st, obs, (int)P, cam, poses_out,
-                           points_out, (int)C, w.lm, w.W);
-        if (F > 0)
-            hipLaunchKernelGGL(sfmlm::camera_kernel, dim3((unsigned)F), dim3(kThreads), 0, st, obs, cam, poses_out, points_out,
-                               w.lm);
-    };
-    linearize();
-    hipLaunchKernelGGL(sfmlm::start_kernel<kThreads>, dim3(1), dim3(kThreads), 0, st, pblocks, f, anchor, max_steps, poses_out,
-                       w.lm);
-    for (int step = 0; step < max_steps; ++step) {
-        linearize();
-        hipLaunchKernelGGL(sfmlm::point_kernel, dim3(pgrid), dim3(kThreads), 0, st, (int)P, w.lm);
-        if (pairs > 0) hipLaunchKernelGGL(bundle_schur_kernel, dim3(pairs), dim3(kThreads), 0, st, F, w);
-        if (F <= kLdsFree)
-            hipLaunchKernelGGL(bundle_solve_kernel<true>, dim3(1), dim3(kSolveThreads), 0, st, F, (int)C, poses_out, w);
-        else
-            hipLaunchKernelGGL(bundle_solve_kernel<false>, dim3(1), dim3(kSolveThreads), 0, st, F, (int)C, poses_out, w);
-        hipLaunchKernelGGL(bundle_trial_kernel, dim3(pgrid), dim3(kThreads), 0, st, obs, (int)P, cam, points_out, (int)C, w);
-        hipLaunchKernelGGL(sfmlm::decide_kernel<kThreads>, dim3(1), dim3(kThreads), 0, st, pblocks, anchor, max_steps, w.lm);
-        hipLaunchKernelGGL(sfmlm::commit_kernel, dim3(icgrid), dim3(kThreads), 0, st, (int)P, (int)C, anchor, poses_out,
-                           points_out, w.lm);
-    }
-    hipLaunchKernelGGL(bundle_finish_kernel, dim3(1), dim3(1), 0, st, w.lm, info);
-    return check_launch("sfm_bundle_adjust");
+int sfm_bundle_adjust(const double* K, int64_t cameras, int64_t points, int64_t observations, const uint8_t* fixed,
+                      const double* poses_in, const double* points_in, const int32_t* camera_index,
+                      const int32_t* point_index, const double* pixels, int max_steps, double* poses_out,
+                      double* points_out, sfm_bundle_info* info, void* workspace, int64_t workspace_bytes, void* stream) {
+    return sfm_bundle_adjust_ex(K, cameras, points, observations, fixed, poses_in, points_in, camera_index, point_index, pixels,
+                                max_steps, poses_out, points_out, info, workspace, workspace_bytes, stream, nullptr);
 }
 
 }  // extern "C"

@@ -7,6 +7,10 @@
 // slot[c] is camera c's index among the free cameras (-1 for a fixed one), freec[s] the camera of slot s.  The gauge's
 // fixed camera f and anchor a (the lowest free camera when exactly one camera is fixed, else a = -1) come from the host.
 // No floating-point atomics anywhere: every sum runs in an order fixed by the sizes alone.
+//
+// The kernels that see a residual or a Jacobian take the loss (csrc/sfm_loss.h) as a template parameter:
+// kRobust = false is the squared loss and compiles to the code it was before there was a choice; kRobust = true reads the
+// launch-uniform Lm::loss, sums rho instead of e and multiplies r, Jc and Jp by sqrt(w).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -14,6 +18,7 @@
 #include <stdint.h>
 
 #include "sfm_common.h"
+#include "sfm_loss.h"
 #include "sfm_math.h"
 #include "sfm_obs_order.h"
 #include "sfm_pnp.h"
@@ -62,6 +67,8 @@ struct Lm {
     double *U, *gc;                  // per camera: U_c (upper 21), g_c
     double *dc, *tpose, *tpts;       // the trial step: camera steps, poses and points
     double* part;                    // per point block: trial cost | |dX|^2 | |X|^2
+    sfmloss::Loss loss;              // read by the kRobust kernels only
+    double* sw;                      // sqrt(w) per point-major position, for kernels without a residual (else nullptr)
 };
 
 // Bump allocation of a workspace in 256-byte aligned pieces from `base` (0: sizes only).
@@ -111,6 +118,8 @@ inline Core carve_core(Carver& k, int64_t C, int64_t P, int64_t M, int64_t F, St
     w.tpose = k.take<double>(12 * C);
     w.tpts = k.take<double>(3 * P);
     w.part = k.take<double>(3 * ((P + kThreads - 1) / kThreads));
+    w.loss = sfmloss::Loss{SFM_BUNDLE_LOSS_SQUARED, 0, 1.0, 1.0};
+    w.sw = nullptr;
     return c;
 }
 
@@ -203,8 +212,9 @@ namespace {
 // ------------------------------------------------------------------------------------------------------------------------
 // Thread per point: the cost of its observations (partial per block; the start needs it), V_p and g_p.  kStoreW (the
 // dense path, C <= kLdsCameras): the poses staged in LDS, and W = Jc^T Jp to W[18 q] for every point-major position q of a
-// moving point seen by a free camera.
-template <bool kStoreW>
+// moving point seen by a free camera.  kRobust: the cost is the sum of rho, r, Jc and Jp carry sqrt(w), which also goes to
+// w.sw[q] when the adjuster keeps it (0 for an observation behind its camera).
+template <bool kStoreW, bool kRobust>
 __global__ __launch_bounds__(kThreads) void linearize_kernel(Obs obs, int P, PnPCamera cam, const double* __restrict__ poses,
                                                              const double* __restrict__ points, int C, Lm w,
                                                              double* __restrict__ W) {
@@ -230,9 +240,16 @@ __global__ __launch_bounds__(kThreads) void linearize_kernel(Obs obs, int P, PnP
             const int c = w.camp[q];
             const double* mp = pose + 12 * (int64_t)c;
             const double u = obs.uv[2 * (int64_t)m], v = obs.uv[2 * (int64_t)m + 1];
-            e[0] += sfmpnp::pnp_score(mp, cam, X, Y, Z, u, v);
+            const double eq = sfmpnp::pnp_score(mp, cam, X, Y, Z, u, v);
+            e[0] += kRobust ? sfmloss::rho(w.loss, eq) : eq;
             double r[2], Jc[2][6], Jp[2][3];
-            if (!sfmpnp::jacobians(mp, cam, X, Y, Z, Jc, Jp, r, u, v)) continue;
+            const bool front = sfmpnp::jacobians(mp, cam, X, Y, Z, Jc, Jp, r, u, v);
+            if (kRobust) {
+                const double s = front ? sfmloss::sqrt_weight(w.loss, r) : 0.0;
+                if (w.sw) w.sw[q] = s;
+                if (front) sfmloss::scale(s, r, Jc, Jp);
+            }
+            if (!front) continue;
 #pragma unroll
             for (int i = 0; i < 3; ++i) {
 #pragma unroll
@@ -256,7 +273,9 @@ __global__ __launch_bounds__(kThreads) void linearize_kernel(Obs obs, int P, PnP
     if (threadIdx.x == 0) w.part[3 * (int64_t)blockIdx.x] = total[0];
 }
 
-// Block per free camera: U_c (upper 21) and g_c over its observations in camera-major order.
+// Block per free camera: U_c (upper 21) and g_c over its observations in camera-major order.  kRobust: sqrt(w) again
+// from the residual, the bits linearize_kernel got.
+template <bool kRobust>
 __global__ __launch_bounds__(kThreads) void camera_kernel(Obs obs, PnPCamera cam, const double* __restrict__ poses,
                                                           const double* __restrict__ points, Lm w) {
     __shared__ double part[kThreads / kWave * 27];
@@ -275,6 +294,7 @@ __global__ __launch_bounds__(kThreads) void camera_kernel(Obs obs, PnPCamera cam
         if (!sfmpnp::jacobians(m, cam, points[3 * p], points[3 * p + 1], points[3 * p + 2], Jc, Jp, r, obs.uv[2 * mo],
                                obs.uv[2 * mo + 1]))
             continue;
+        if (kRobust) sfmloss::scale(sfmloss::sqrt_weight(w.loss, r), r, Jc, Jp);
 #pragma unroll
         for (int x = 0; x < 6; ++x) {
 #pragma unroll

@@ -25,6 +25,11 @@
 // iterations, and enqueues no more work after a stop.  The device state alone decides the result: every kernel also
 // returns at once after a stop, so the reads only save launches.  No floating-point atomics anywhere: every sum runs in
 // an order fixed by the sizes alone, so a call is bit-reproducible.
+//
+// A robust loss (csrc/sfm_loss.h) runs the kRobust = true forms of the kernels that see a residual or a
+// Jacobian.  The kernels that recompute Jc and Jp without a residual (the preconditioner, both CG passes, the trial's
+// back-substitution) read sqrt(w) from lm.sw, which the linearisation stored once per point-major position (8 B per
+// observation, in the workspace of a non-squared call only); the camera-major ones reach it through pos_c.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -71,11 +76,12 @@ static_assert(offsetof(State, cg_done) == offsetof(State, lm) + offsetof(sfmlm::
 struct Ws {
     Lm lm;
     State* st;
+    const int32_t* pos_c;   // camera-major position -> point-major position (set after the orders are enqueued)
     double *y, *Minv, *b, *x, *r, *z, *p, *q, *part;
 };
 
 // The workspace from `base` (0: sizes only); its size in bytes.
-int64_t carve(uintptr_t base, int64_t C, int64_t P, int64_t M, int64_t F, Ws* w, sfmlm::Core* core) {
+int64_t carve(uintptr_t base, int64_t C, int64_t P, int64_t M, int64_t F, bool robust, Ws* w, sfmlm::Core* core) {
     sfmlm::Carver k{base, 0};
     w->st = k.take<State>(1);
     *core = sfmlm::carve_core(k, C, P, M, F, &w->st->lm);
@@ -89,6 +95,8 @@ int64_t carve(uintptr_t base, int64_t C, int64_t P, int64_t M, int64_t F, Ws* w,
     w->p = k.take<double>(6 * F);
     w->q = k.take<double>(6 * F);
     w->part = k.take<double>(F);
+    w->pos_c = nullptr;
+    if (robust) w->lm.sw = k.take<double>(M);   // last: the squared layout and size stay as they are
     return k.at;
 }
 
@@ -135,6 +143,7 @@ SFM_DEVICE void damped_u(const double* u, double lambda, double (&A)[6][6]) {
 
 // Block per free camera (slot s): M_c = U*_c - sum over its observations of moving points of W V_p*^-1 W^T, b_c = -g_c +
 // sum W V_p*^-1 g_p, and M_c^-1 (full 36) from its Cholesky factor.  A pivot <= 0 or not finite marks the step as failed.
+template <bool kRobust>
 __global__ __launch_bounds__(kThreads) void pcg_precond_kernel(PnPCamera cam, const double* __restrict__ poses,
                                                                const double* __restrict__ points, Ws w) {
     __shared__ double part[kThreads / kWave * 27];
@@ -152,6 +161,7 @@ __global__ __launch_bounds__(kThreads) void pcg_precond_kernel(PnPCamera cam, co
         if (w.lm.off_p[p + 1] - w.lm.off_p[p] < 2) continue;
         double Jc[2][6], Jp[2][3];
         if (!jacobians(m, cam, points[3 * p], points[3 * p + 1], points[3 * p + 2], Jc, Jp)) continue;
+        if (kRobust) sfmloss::scale(w.lm.sw[w.pos_c[i]], Jc, Jp);
         double Wm[6][3], Vi[3][3], Y[6][3];
 #pragma unroll
         for (int x = 0; x < 6; ++x)
@@ -273,6 +283,7 @@ __global__ __launch_bounds__(kOneGroup) void pcg_cg_init_kernel(int F, double to
 }
 
 // Thread per point: y_p = V_p*^-1 sum over its observations by free cameras of W^T p_c (0 for a point that does not move)
+template <bool kRobust>
 __global__ __launch_bounds__(kThreads) void pcg_cg_point_kernel(int P, PnPCamera cam, const double* __restrict__ poses,
                                                                 const double* __restrict__ points, Ws w) {
     if (w.st->lm.stop || w.st->cg_done) return;
@@ -287,6 +298,7 @@ __global__ __launch_bounds__(kThreads) void pcg_cg_point_kernel(int P, PnPCamera
             if (s < 0) continue;
             double Jc[2][6], Jp[2][3], d[3];
             if (!jacobians(poses + 12 * (int64_t)c, cam, X, Y, Z, Jc, Jp)) continue;
+            if (kRobust) sfmloss::scale(w.lm.sw[q], Jc, Jp);
             wt_times(Jc, Jp, w.p + 6 * (int64_t)s, d);
 #pragma unroll
             for (int j = 0; j < 3; ++j) t[j] += d[j];
@@ -304,6 +316,7 @@ __global__ __launch_bounds__(kThreads) void pcg_cg_point_kernel(int P, PnPCamera
 }
 
 // Block per free camera (slot s): q_s = U*_c p_s - sum over its observations of W y_p, and part_s = p_s . q_s
+template <bool kRobust>
 __global__ __launch_bounds__(kThreads) void pcg_cg_camera_kernel(PnPCamera cam, const double* __restrict__ poses,
                                                                  const double* __restrict__ points, Ws w) {
     __shared__ double part[kThreads / kWave * 6];
@@ -318,6 +331,7 @@ __global__ __launch_bounds__(kThreads) void pcg_cg_camera_kernel(PnPCamera cam, 
         const int64_t p = w.lm.pt_c[i];
         double Jc[2][6], Jp[2][3], e[6];
         if (!jacobians(m, cam, points[3 * p], points[3 * p + 1], points[3 * p + 2], Jc, Jp)) continue;
+        if (kRobust) sfmloss::scale(w.lm.sw[w.pos_c[i]], Jc, Jp);
         w_times(Jc, Jp, w.y + 3 * p, e);
 #pragma unroll
         for (int k = 0; k < 6; ++k) a[k] += e[k];
@@ -424,7 +438,8 @@ __global__ __launch_bounds__(kOneGroup) void pcg_apply_kernel(int C, const doubl
 }
 
 // Thread per point: dX_p = V_p*^-1 (-g_p - sum over its free-camera observations of W^T dc), the trial point, the trial
-// cost of its observations and its share of |delta|^2 and |x|^2; partials per block.
+// cost of its observations (kRobust: the sum of rho) and its share of |delta|^2 and |x|^2; partials per block.
+template <bool kRobust>
 __global__ __launch_bounds__(kThreads) void pcg_trial_kernel(Obs obs, int P, PnPCamera cam, const double* __restrict__ poses,
                                                              const double* __restrict__ points, Ws w) {
     __shared__ double part[kThreads / kWave * 3];
@@ -442,6 +457,7 @@ __global__ __launch_bounds__(kThreads) void pcg_trial_kernel(Obs obs, int P, PnP
                 if (w.lm.slot[c] < 0) continue;
                 double Jc[2][6], Jp[2][3], d[3];
                 if (!jacobians(poses + 12 * (int64_t)c, cam, X[0], X[1], X[2], Jc, Jp)) continue;
+                if (kRobust) sfmloss::scale(w.lm.sw[q], Jc, Jp);
                 wt_times(Jc, Jp, w.lm.dc + 6 * (int64_t)c, d);
 #pragma unroll
                 for (int j = 0; j < 3; ++j) t[j] -= d[j];
@@ -462,7 +478,8 @@ __global__ __launch_bounds__(kThreads) void pcg_trial_kernel(Obs obs, int P, PnP
         for (int i = 0; i < 3; ++i) w.lm.tpts[3 * (int64_t)p + i] = X[i];
         for (int q = q0; q < q1; ++q) {
             const int64_t m = w.lm.ord_p[q];
-            a[0] += pnp_score(w.lm.tpose + 12 * (int64_t)w.lm.camp[q], cam, X[0], X[1], X[2], obs.uv[2 * m], obs.uv[2 * m + 1]);
+            const double e = pnp_score(w.lm.tpose + 12 * (int64_t)w.lm.camp[q], cam, X[0], X[1], X[2], obs.uv[2 * m], obs.uv[2 * m + 1]);
+            a[0] += kRobust ? sfmloss::rho(w.lm.loss, e) : e;
         }
     }
     block_sum<3, kThreads>(a, part, total);
@@ -483,24 +500,129 @@ int32_t* pinned_flags() {
     return flags;
 }
 
+// A checked call: everything enqueue needs.
+struct Job {
+    PnPCamera cam;
+    int64_t C, P, M, F;
+    const int32_t* slot;   // host
+    int first_fixed, anchor;
+    const double *poses_in, *points_in;
+    Obs obs;
+    int max_steps, max_cg_iterations;
+    double cg_tolerance;
+    double *poses_out, *points_out;
+    sfm_bundle_pcg_info* info;
+    int32_t* flags;
+    hipStream_t st;
+};
+
+// Enqueue the call step by step; kRobust picks the kernels of a non-squared loss (w.lm.loss, w.lm.sw).
+template <bool kRobust>
+int enqueue(const Job& job, Ws& w, const sfmlm::Core& core) {
+    const PnPCamera& cam = job.cam;
+    const int64_t C = job.C, P = job.P, M = job.M, F = job.F;
+    const double *poses_in = job.poses_in, *points_in = job.points_in;
+    double *poses_out = job.poses_out, *points_out = job.points_out;
+    const int max_steps = job.max_steps, max_cg_iterations = job.max_cg_iterations, anchor = job.anchor;
+    const double cg_tolerance = job.cg_tolerance;
+    int32_t* flags = job.flags;
+    hipStream_t st = job.st;
+    const Obs& obs = job.obs;
+    const unsigned pgrid = sfmhost::grid_for(P, kThreads), cgrid = sfmhost::grid_for(C, kThreads);
+    const unsigned icgrid = sfmhost::grid_for(P > C ? P : C, kThreads);
+    const int pblocks = (int)((P + kThreads - 1) / kThreads);
+    // reads {stop, cg_done} into the pinned flags (synchronises the stream)
+    auto read_flags = [&]() -> int {
+        if (hipMemcpyAsync(flags, &w.st->lm.stop, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
+            hipStreamSynchronize(st) != hipSuccess)
+            return check_launch("sfm_bundle_adjust_pcg: read the flags");
+        return SFM_OK;
+    };
+
+    // the output starts as the input; the slots come from the host; the point counters start at zero
+    if (poses_out != poses_in && hipMemcpyAsync(poses_out, poses_in, 8 * 12 * C, hipMemcpyDeviceToDevice, st) != hipSuccess)
+        return check_launch("sfm_bundle_adjust_pcg: copy poses");
+    if (P > 0 && points_out != points_in &&
+        hipMemcpyAsync(points_out, points_in, 8 * 3 * P, hipMemcpyDeviceToDevice, st) != hipSuccess)
+        return check_launch("sfm_bundle_adjust_pcg: copy points");
+    if (hipMemcpyAsync(w.lm.slot, job.slot, 4 * C, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemsetAsync(w.lm.off_p, 0, 4 * (P + 1), st) != hipSuccess)
+        return check_launch("sfm_bundle_adjust_pcg: set up the workspace");
+    hipLaunchKernelGGL(pcg_init_kernel, dim3(cgrid), dim3(kThreads), 0, st, (int)C, w);
+    w.pos_c = sfmlm::launch_orders(obs, M, C, P, core, st);
+    auto linearize = [&]() {
+        hipLaunchKernelGGL((sfmlm::linearize_kernel<false, kRobust>), dim3(pgrid), dim3(kThreads), 0, st, obs, (int)P, cam,
+                           poses_out, points_out, (int)C, w.lm, nullptr);
+        if (F > 0)
+            hipLaunchKernelGGL(sfmlm::camera_kernel<kRobust>, dim3((unsigned)F), dim3(kThreads), 0, st, obs, cam, poses_out,
+                               points_out, w.lm);
+    };
+    linearize();
+    hipLaunchKernelGGL(sfmlm::start_kernel<kOneGroup>, dim3(1), dim3(kOneGroup), 0, st, pblocks, job.first_fixed, anchor,
+                       max_steps, poses_out, w.lm);
+    for (int step = 0; step < max_steps; ++step) {
+        int rc2 = read_flags();   // also the point after which the host slots may go
+        if (rc2 != SFM_OK) return rc2;
+        if (flags[0]) break;
+        linearize();
+        hipLaunchKernelGGL(sfmlm::point_kernel, dim3(pgrid), dim3(kThreads), 0, st, (int)P, w.lm);
+        if (F > 0)
+            hipLaunchKernelGGL(pcg_precond_kernel<kRobust>, dim3((unsigned)F), dim3(kThreads), 0, st, cam, poses_out, points_out,
+                               w);
+        hipLaunchKernelGGL(pcg_cg_init_kernel, dim3(1), dim3(kOneGroup), 0, st, (int)F, cg_tolerance, w);
+        for (int k0 = 0; F > 0 && k0 < max_cg_iterations; k0 += kCgChunk) {
+            if (k0 > 0) {
+                rc2 = read_flags();
+                if (rc2 != SFM_OK) return rc2;
+                if (flags[0] || flags[1]) break;
+            }
+            for (int k = k0; k < max_cg_iterations && k < k0 + kCgChunk; ++k) {
+                hipLaunchKernelGGL(pcg_cg_point_kernel<kRobust>, dim3(pgrid), dim3(kThreads), 0, st, (int)P, cam, poses_out,
+                                   points_out, w);
+                hipLaunchKernelGGL(pcg_cg_camera_kernel<kRobust>, dim3((unsigned)F), dim3(kThreads), 0, st, cam, poses_out,
+                                   points_out, w);
+                hipLaunchKernelGGL(pcg_cg_update_kernel, dim3(1), dim3(kOneGroup), 0, st, (int)F, max_cg_iterations, w);
+            }
+        }
+        hipLaunchKernelGGL(pcg_apply_kernel, dim3(1), dim3(kOneGroup), 0, st, (int)C, poses_out, w);
+        hipLaunchKernelGGL(pcg_trial_kernel<kRobust>, dim3(pgrid), dim3(kThreads), 0, st, obs, (int)P, cam, poses_out, points_out,
+                           w);
+        hipLaunchKernelGGL(sfmlm::decide_kernel<kOneGroup>, dim3(1), dim3(kOneGroup), 0, st, pblocks, anchor, max_steps, w.lm);
+        hipLaunchKernelGGL(sfmlm::commit_kernel, dim3(icgrid), dim3(kThreads), 0, st, (int)P, (int)C, anchor, poses_out,
+                           points_out, w.lm);
+    }
+    hipLaunchKernelGGL(pcg_finish_kernel, dim3(1), dim3(1), 0, st, w, job.info);
+    if (max_steps == 0) {   // no read above: the host slots must reach the device before they go
+        const int rc2 = read_flags();
+        if (rc2 != SFM_OK) return rc2;
+    }
+    return check_launch("sfm_bundle_adjust_pcg");
+}
+
 }  // namespace
 
 extern "C" {
 
-int64_t sfm_bundle_pcg_workspace_bytes(int64_t cameras, int64_t points, int64_t observations) {
+int64_t sfm_bundle_pcg_workspace_bytes_ex(int64_t cameras, int64_t points, int64_t observations,
+                                          const sfm_bundle_options* options) {
+    sfmloss::Loss loss;
     if (cameras < 1 || points < 0 || observations < 0 || cameras > 0x7FFFFFFF || points > 0x7FFFFFFF ||
-        observations > 0x7FFFFFFF)
+        observations > 0x7FFFFFFF || !sfmloss::from_options(options, loss))
         return -1;
     Ws w;
     sfmlm::Core core;
-    return carve(0, cameras, points, observations, cameras - 1, &w, &core);
+    return carve(0, cameras, points, observations, cameras - 1, loss.kind != SFM_BUNDLE_LOSS_SQUARED, &w, &core);
 }
 
-int sfm_bundle_adjust_pcg(const double* K, int64_t cameras, int64_t points, int64_t observations, const uint8_t* fixed,
-                          const double* poses_in, const double* points_in, const int32_t* camera_index,
-                          const int32_t* point_index, const double* pixels, int max_steps, int max_cg_iterations,
-                          double cg_tolerance, double* poses_out, double* points_out, sfm_bundle_pcg_info* info,
-                          void* workspace, int64_t workspace_bytes, void* stream) {
+int64_t sfm_bundle_pcg_workspace_bytes(int64_t cameras, int64_t points, int64_t observations) {
+    return sfm_bundle_pcg_workspace_bytes_ex(cameras, points, observations, nullptr);
+}
+
+int sfm_bundle_adjust_pcg_ex(const double* K, int64_t cameras, int64_t points, int64_t observations, const uint8_t* fixed,
+                             const double* poses_in, const double* points_in, const int32_t* camera_index,
+                             const int32_t* point_index, const double* pixels, int max_steps, int max_cg_iterations,
+                             double cg_tolerance, double* poses_out, double* points_out, sfm_bundle_pcg_info* info,
+                             void* workspace, int64_t workspace_bytes, void* stream, const sfm_bundle_options* options) {
     // every check before the first launch: a refused call has enqueued nothing
     if (cameras < 1 || points < 0 || observations < 0 || max_steps < 0)
         return fail(SFM_EINVAL, "sfm_bundle_adjust_pcg: bad size");
@@ -509,6 +631,9 @@ int sfm_bundle_adjust_pcg(const double* K, int64_t cameras, int64_t points, int6
     if (max_cg_iterations < 1) return fail(SFM_EINVAL, "sfm_bundle_adjust_pcg: max_cg_iterations must be at least 1");
     if (!(cg_tolerance > 0.0 && cg_tolerance < 1.0))
         return fail(SFM_EINVAL, "sfm_bundle_adjust_pcg: cg_tolerance must be finite and in (0, 1)");
+    sfmloss::Loss loss;
+    if (!sfmloss::from_options(options, loss))
+        return fail(SFM_EINVAL, "sfm_bundle_adjust_pcg: options need a loss in 0..2, reserved = 0 and a finite loss_scale > 0");
     PnPCamera cam;
     const int rc = camera_from(K, cam, "sfm_bundle_adjust_pcg");
     if (rc != SFM_OK) return rc;
@@ -529,84 +654,30 @@ int sfm_bundle_adjust_pcg(const double* K, int64_t cameras, int64_t points, int6
     if (!poses_in || !poses_out || !info || !workspace || (points > 0 && (!points_in || !points_out)) ||
         (observations > 0 && (!camera_index || !point_index || !pixels)))
         return fail(SFM_EINVAL, "sfm_bundle_adjust_pcg: null pointer");
+    const bool robust = loss.kind != SFM_BUNDLE_LOSS_SQUARED;
     Ws w;
     sfmlm::Core core;
-    if (workspace_bytes < carve((uintptr_t)workspace, C, P, M, F, &w, &core))
+    if (workspace_bytes < carve((uintptr_t)workspace, C, P, M, F, robust, &w, &core))
         return fail(SFM_EINVAL, "sfm_bundle_adjust_pcg: workspace too small");
     if (((uintptr_t)workspace & 15) != 0) return fail(SFM_EINVAL, "sfm_bundle_adjust_pcg: workspace must be 16-byte aligned");
     int32_t* flags = pinned_flags();
     if (!flags) return fail(SFM_EHIP, "sfm_bundle_adjust_pcg: no pinned host memory for the flags");
-
-    hipStream_t st = (hipStream_t)stream;
-    const Obs obs{camera_index, point_index, pixels};
+    w.lm.loss = loss;
     const int anchor = C - F == 1 && F > 0 ? (int)first_free : -1;   // one fixed camera: the gauge anchor
-    const unsigned pgrid = sfmhost::grid_for(P, kThreads), cgrid = sfmhost::grid_for(C, kThreads);
-    const unsigned icgrid = sfmhost::grid_for(P > C ? P : C, kThreads);
-    const int pblocks = (int)((P + kThreads - 1) / kThreads);
-    // reads {stop, cg_done} into the pinned flags (synchronises the stream)
-    auto read_flags = [&]() -> int {
-        if (hipMemcpyAsync(flags, &w.st->lm.stop, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipStreamSynchronize(st) != hipSuccess)
-            return check_launch("sfm_bundle_adjust_pcg: read the flags");
-        return SFM_OK;
-    };
+    const Job job{cam, C, P, M, F, slot.data(), (int)first_fixed, anchor, poses_in, points_in,
+                  Obs{camera_index, point_index, pixels}, max_steps, max_cg_iterations, cg_tolerance, poses_out, points_out,
+                  info, flags, (hipStream_t)stream};
+    return robust ? enqueue<true>(job, w, core) : enqueue<false>(job, w, core);
+}
 
-    // the output starts as the input; the slots come from the host; the point counters start at zero
-    if (poses_out != poses_in && hipMemcpyAsync(poses_out, poses_in, 8 * 12 * C, hipMemcpyDeviceToDevice, st) != hipSuccess)
-        return check_launch("sfm_bundle_adjust_pcg: copy poses");
-    if (P > 0 && points_out != points_in &&
-        hipMemcpyAsync(points_out, points_in, 8 * 3 * P, hipMemcpyDeviceToDevice, st) != hipSuccess)
-        return check_launch("sfm_bundle_adjust_pcg: copy points");
-    if (hipMemcpyAsync(w.lm.slot, slot.data(), 4 * C, hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipMemsetAsync(w.lm.off_p, 0, 4 * (P + 1), st) != hipSuccess)
-        return check_launch("sfm_bundle_adjust_pcg: set up the workspace");
-    hipLaunchKernelGGL(pcg_init_kernel, dim3(cgrid), dim3(kThreads), 0, st, (int)C, w);
-    sfmlm::launch_orders(obs, M, C, P, core, st);
-    auto linearize = [&]() {
-        hipLaunchKernelGGL(sfmlm::linearize_kernel<false>, dim3(pgrid), dim3(kThreads), 0, st, obs, (int)P, cam, poses_out,
-                           points_out, (int)C, w.lm, nullptr);
-        if (F > 0)
-            hipLaunchKernelGGL(sfmlm::camera_kernel, dim3((unsigned)F), dim3(kThreads), 0, st, obs, cam, poses_out, points_out,
-                               w.lm);
-    };
-    linearize();
-    hipLaunchKernelGGL(sfmlm::start_kernel<kOneGroup>, dim3(1), dim3(kOneGroup), 0, st, pblocks, (int)first_fixed, anchor,
-                       max_steps, poses_out, w.lm);
-    for (int step = 0; step < max_steps; ++step) {
-        int rc2 = read_flags();   // also the point after which the host slots may go
-        if (rc2 != SFM_OK) return rc2;
-        if (flags[0]) break;
-        linearize();
-        hipLaunchKernelGGL(sfmlm::point_kernel, dim3(pgrid), dim3(kThreads), 0, st, (int)P, w.lm);
-        if (F > 0)
-            hipLaunchKernelGGL(pcg_precond_kernel, dim3((unsigned)F), dim3(kThreads), 0, st, cam, poses_out, points_out, w);
-        hipLaunchKernelGGL(pcg_cg_init_kernel, dim3(1), dim3(kOneGroup), 0, st, (int)F, cg_tolerance, w);
-        for (int k0 = 0; F > 0 && k0 < max_cg_iterations; k0 += kCgChunk) {
-            if (k0 > 0) {
-                rc2 = read_flags();
-                if (rc2 != SFM_OK) return rc2;
-                if (flags[0] || flags[1]) break;
-            }
-            for (int k = k0; k < max_cg_iterations && k < k0 + kCgChunk; ++k) {
-                hipLaunchKernelGGL(pcg_cg_point_kernel, dim3(pgrid), dim3(kThreads), 0, st, (int)P, cam, poses_out,
-                                   points_out, w);
-                hipLaunchKernelGGL(pcg_cg_camera_kernel, dim3((unsigned)F), dim3(kThreads), 0, st, cam, poses_out,
-                                   points_out, w);
-                hipLaunchKernelGGL(pcg_cg_update_kernel, dim3(1), dim3(kOneGroup), 0, st, (int)F, max_cg_iterations, w);
-            }
-        }
-        hipLaunchKernelGGL(pcg_apply_kernel, dim3(1), dim3(kOneGroup), 0, st, (int)C, poses_out, w);
-        hipLaunchKernelGGL(pcg_trial_kernel, dim3(pgrid), dim3(kThreads), 0, st, obs, (int)P, cam, poses_out, points_out, w);
-        hipLaunchKernelGGL(sfmlm::decide_kernel<kOneGroup>, dim3(1), dim3(kOneGroup), 0, st, pblocks, anchor, max_steps, w.lm);
-        hipLaunchKernelGGL(sfmlm::commit_kernel, dim3(icgrid), dim3(kThreads), 0, st, (int)P, (int)C, anchor, poses_out,
-                           points_out, w.lm);
-    }
-    hipLaunchKernelGGL(pcg_finish_kernel, dim3(1), dim3(1), 0, st, w, info);
-    if (max_steps == 0) {   // no read above: the host slots must reach the device before they go
-        const int rc2 = read_flags();
-        if (rc2 != SFM_OK) return rc2;
-    }
-    return check_launch("sfm_bundle_adjust_pcg");
+int sfm_bundle_adjust_pcg(const double* K, int64_t cameras, int64_t points, int64_t observations, const uint8_t* fixed,
+                          const double* poses_in, const double* points_in, const int32_t* camera_index,
+                          const int32_t* point_index, const double* pixels, int max_steps, int max_cg_iterations,
+                          double cg_tolerance, double* poses_out, double* points_out, sfm_bundle_pcg_info* info,
+                          void* workspace, int64_t workspace_bytes, void* stream) {
+    return sfm_bundle_adjust_pcg_ex(K, cameras, points, observations, fixed, poses_in, points_in, camera_index, point_index,
+                                    pixels, max_steps, max_cg_iterations, cg_tolerance, poses_out, points_out, info, workspace,
+                                    workspace_bytes, stream, nullptr);
 }
 
 }  // extern "C"

@@ -672,9 +672,10 @@ void bundle_check(const Tensor& poses, const Tensor& points, const Tensor& cam, 
     for (int64_t c : fixed) TORCH_CHECK(c >= 0 && c < poses.size(0), "sfm_hip: fixed camera ", c, " out of range");
 }
 
+// options: null for the ops without a loss (sfm_bundle_adjust), else sfm_bundle_adjust_ex
 void bundle_adjust_out(Tensor& poses, Tensor& points, const Tensor& cam, const Tensor& pt, const Tensor& pixels,
                        at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed, int64_t max_steps, Tensor& info,
-                       const Tensor& poses_in, const Tensor& points_in) {
+                       const Tensor& poses_in, const Tensor& points_in, const sfm_bundle_options* options = nullptr) {
     const OpDevice scope(poses);
     need(poses, "poses", at::kDouble);
     need(points, "points", at::kDouble);
@@ -694,10 +695,17 @@ void bundle_adjust_out(Tensor& poses, Tensor& points, const Tensor& cam, const T
     TORCH_CHECK(bytes >= 0, "sfm_hip: bundle_adjust: ", C, " cameras, ", P, " points, ", M,
                 " observations exceed the limits (C <= 64, P and M < 2^31)");
     Tensor ws = at::empty({bytes}, like(poses, at::kByte));
-    ok(sfm_bundle_adjust(K.data(), C, P, M, mask.data(), ptr<double>(poses_in), ptr<double>(points_in), ptr<int32_t>(cam),
-                         ptr<int32_t>(pt), ptr<double>(pixels), (int)max_steps, ptr<double>(poses), ptr<double>(points),
-                         reinterpret_cast<sfm_bundle_info*>(ptr<int64_t>(info)), ws.data_ptr(), bytes, current_stream()),
-       "sfm_bundle_adjust");
+    if (options)
+        ok(sfm_bundle_adjust_ex(K.data(), C, P, M, mask.data(), ptr<double>(poses_in), ptr<double>(points_in),
+                                ptr<int32_t>(cam), ptr<int32_t>(pt), ptr<double>(pixels), (int)max_steps, ptr<double>(poses),
+                                ptr<double>(points), reinterpret_cast<sfm_bundle_info*>(ptr<int64_t>(info)), ws.data_ptr(),
+                                bytes, current_stream(), options),
+           "sfm_bundle_adjust_ex");
+    else
+        ok(sfm_bundle_adjust(K.data(), C, P, M, mask.data(), ptr<double>(poses_in), ptr<double>(points_in), ptr<int32_t>(cam),
+                             ptr<int32_t>(pt), ptr<double>(pixels), (int)max_steps, ptr<double>(poses), ptr<double>(points),
+                             reinterpret_cast<sfm_bundle_info*>(ptr<int64_t>(info)), ws.data_ptr(), bytes, current_stream()),
+           "sfm_bundle_adjust");
 }
 
 void bundle_adjust_inplace(Tensor& poses, Tensor& points, const Tensor& cam, const Tensor& pt, const Tensor& pixels,
@@ -739,7 +747,8 @@ void bundle_pcg_check(const Tensor& poses, const Tensor& points, const Tensor& c
 
 void bundle_adjust_pcg_out(Tensor& poses, Tensor& points, const Tensor& cam, const Tensor& pt, const Tensor& pixels,
                            at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed, int64_t max_steps, int64_t max_cg_iterations,
-                           double cg_tolerance, Tensor& info, const Tensor& poses_in, const Tensor& points_in) {
+                           double cg_tolerance, Tensor& info, const Tensor& poses_in, const Tensor& points_in,
+                           const sfm_bundle_options* options = nullptr) {
     const OpDevice scope(poses);
     need(poses, "poses", at::kDouble);
     need(points, "points", at::kDouble);
@@ -755,15 +764,24 @@ void bundle_adjust_pcg_out(Tensor& poses, Tensor& points, const Tensor& cam, con
     const int64_t C = poses.size(0), P = points.size(0), M = cam.size(0);
     std::vector<uint8_t> mask((size_t)C, 0);
     for (int64_t c : fixed) mask[(size_t)c] = 1;
-    const int64_t bytes = sfm_bundle_pcg_workspace_bytes(C, P, M);
+    const int64_t bytes = sfm_bundle_pcg_workspace_bytes_ex(C, P, M, options);   // null options: the plain size
     TORCH_CHECK(bytes >= 0, "sfm_hip: bundle_adjust_pcg: ", C, " cameras, ", P, " points, ", M,
                 " observations exceed the limits (C >= 1; C, P and M < 2^31)");
     Tensor ws = at::empty({bytes}, like(poses, at::kByte));
-    ok(sfm_bundle_adjust_pcg(K.data(), C, P, M, mask.data(), ptr<double>(poses_in), ptr<double>(points_in), ptr<int32_t>(cam),
-                             ptr<int32_t>(pt), ptr<double>(pixels), (int)max_steps, (int)max_cg_iterations, cg_tolerance,
-                             ptr<double>(poses), ptr<double>(points), reinterpret_cast<sfm_bundle_pcg_info*>(ptr<int64_t>(info)),
-                             ws.data_ptr(), bytes, current_stream()),
-       "sfm_bundle_adjust_pcg");
+    if (options)
+        ok(sfm_bundle_adjust_pcg_ex(K.data(), C, P, M, mask.data(), ptr<double>(poses_in), ptr<double>(points_in),
+                                    ptr<int32_t>(cam), ptr<int32_t>(pt), ptr<double>(pixels), (int)max_steps,
+                                    (int)max_cg_iterations, cg_tolerance, ptr<double>(poses), ptr<double>(points),
+                                    reinterpret_cast<sfm_bundle_pcg_info*>(ptr<int64_t>(info)), ws.data_ptr(), bytes,
+                                    current_stream(), options),
+           "sfm_bundle_adjust_pcg_ex");
+    else
+        ok(sfm_bundle_adjust_pcg(K.data(), C, P, M, mask.data(), ptr<double>(poses_in), ptr<double>(points_in),
+                                 ptr<int32_t>(cam), ptr<int32_t>(pt), ptr<double>(pixels), (int)max_steps, (int)max_cg_iterations,
+                                 cg_tolerance, ptr<double>(poses), ptr<double>(points),
+                                 reinterpret_cast<sfm_bundle_pcg_info*>(ptr<int64_t>(info)), ws.data_ptr(), bytes,
+                                 current_stream()),
+           "sfm_bundle_adjust_pcg");
 }
 
 void bundle_adjust_pcg_inplace(Tensor& poses, Tensor& points, const Tensor& cam, const Tensor& pt, const Tensor& pixels,
@@ -793,6 +811,75 @@ std::tuple<Tensor, Tensor, Tensor> bundle_adjust_pcg_meta(const Tensor& poses, c
     bundle_pcg_check(poses, points, cam, pt, pixels, K, fixed, max_steps, max_cg_iterations, cg_tolerance);
     return {at::empty_like(poses), at::empty_like(points),
             at::empty_symint({c10::SymInt(kBundlePcgInfoWords)}, like(poses, at::kLong))};
+}
+
+// both adjusters with a robust loss (csrc/sfm_loss.h): the schemas above plus loss (SFM_BUNDLE_LOSS_*) and loss_scale in
+// pixels.  New ops, so that no existing schema changes.
+sfm_bundle_options bundle_options(int64_t loss, double loss_scale) {
+    TORCH_CHECK(loss >= SFM_BUNDLE_LOSS_SQUARED && loss <= SFM_BUNDLE_LOSS_CAUCHY, "sfm_hip: loss must be 0 (squared), 1 (huber) or 2 (cauchy)");
+    TORCH_CHECK(loss_scale > 0.0 && std::isfinite(loss_scale), "sfm_hip: loss_scale must be finite and positive");
+    return sfm_bundle_options{(int32_t)loss, 0, loss_scale};
+}
+
+void bundle_adjust_robust_inplace(Tensor& poses, Tensor& points, const Tensor& cam, const Tensor& pt, const Tensor& pixels,
+                                  at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed, int64_t max_steps, int64_t loss,
+                                  double loss_scale, Tensor& info) {
+    const sfm_bundle_options options = bundle_options(loss, loss_scale);
+    bundle_adjust_out(poses, points, cam, pt, pixels, K, fixed, max_steps, info, poses, points, &options);
+}
+
+std::tuple<Tensor, Tensor, Tensor> bundle_adjust_robust(const Tensor& poses, const Tensor& points, const Tensor& cam,
+                                                        const Tensor& pt, const Tensor& pixels, at::ArrayRef<double> K,
+                                                        at::ArrayRef<int64_t> fixed, int64_t max_steps, int64_t loss,
+                                                        double loss_scale) {
+    const sfm_bundle_options options = bundle_options(loss, loss_scale);
+    bundle_check(poses, points, cam, pt, pixels, K, fixed, max_steps);
+    Tensor poses_out = at::empty_like(poses);
+    Tensor points_out = at::empty_like(points);
+    Tensor info = at::empty({kBundleInfoWords}, like(poses, at::kLong));
+    bundle_adjust_out(poses_out, points_out, cam, pt, pixels, K, fixed, max_steps, info, poses, points, &options);
+    return {poses_out, points_out, info};
+}
+
+std::tuple<Tensor, Tensor, Tensor> bundle_adjust_robust_meta(const Tensor& poses, const Tensor& points, const Tensor& cam,
+                                                             const Tensor& pt, const Tensor& pixels, at::ArrayRef<double> K,
+                                                             at::ArrayRef<int64_t> fixed, int64_t max_steps, int64_t loss,
+                                                             double loss_scale) {
+    bundle_options(loss, loss_scale);
+    return bundle_adjust_meta(poses, points, cam, pt, pixels, K, fixed, max_steps);
+}
+
+void bundle_adjust_pcg_robust_inplace(Tensor& poses, Tensor& points, const Tensor& cam, const Tensor& pt, const Tensor& pixels,
+                                      at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed, int64_t max_steps,
+                                      int64_t max_cg_iterations, double cg_tolerance, int64_t loss, double loss_scale,
+                                      Tensor& info) {
+    const sfm_bundle_options options = bundle_options(loss, loss_scale);
+    bundle_adjust_pcg_out(poses, points, cam, pt, pixels, K, fixed, max_steps, max_cg_iterations, cg_tolerance, info, poses,
+                          points, &options);
+}
+
+std::tuple<Tensor, Tensor, Tensor> bundle_adjust_pcg_robust(const Tensor& poses, const Tensor& points, const Tensor& cam,
+                                                            const Tensor& pt, const Tensor& pixels, at::ArrayRef<double> K,
+                                                            at::ArrayRef<int64_t> fixed, int64_t max_steps,
+                                                            int64_t max_cg_iterations, double cg_tolerance, int64_t loss,
+                                                            double loss_scale) {
+    const sfm_bundle_options options = bundle_options(loss, loss_scale);
+    bundle_pcg_check(poses, points, cam, pt, pixels, K, fixed, max_steps, max_cg_iterations, cg_tolerance);
+    Tensor poses_out = at::empty_like(poses);
+    Tensor points_out = at::empty_like(points);
+    Tensor info = at::empty({kBundlePcgInfoWords}, like(poses, at::kLong));
+    bundle_adjust_pcg_out(poses_out, points_out, cam, pt, pixels, K, fixed, max_steps, max_cg_iterations, cg_tolerance, info,
+                          poses, points, &options);
+    return {poses_out, points_out, info};
+}
+
+std::tuple<Tensor, Tensor, Tensor> bundle_adjust_pcg_robust_meta(const Tensor& poses, const Tensor& points, const Tensor& cam,
+                                                                 const Tensor& pt, const Tensor& pixels, at::ArrayRef<double> K,
+                                                                 at::ArrayRef<int64_t> fixed, int64_t max_steps,
+                                                                 int64_t max_cg_iterations, double cg_tolerance, int64_t loss,
+                                                                 double loss_scale) {
+    bundle_options(loss, loss_scale);
+    return bundle_adjust_pcg_meta(poses, points, cam, pt, pixels, K, fixed, max_steps, max_cg_iterations, cg_tolerance);
 }
 
 // triangulation of multi-view tracks (sfm_tracks.hip): poses [C, 12], camera / point indices int32 [M], pixels [M, 2],
@@ -1002,6 +1089,16 @@ TORCH_LIBRARY(sfm_hip, m) {
     m.def("bundle_adjust_pcg_(Tensor(a!) poses, Tensor(b!) points, Tensor camera_indices, Tensor point_indices, "
           "Tensor pixels, float[] K, int[] fixed, int max_steps, int max_cg_iterations, float cg_tolerance, "
           "Tensor(c!) info) -> ()");
+    m.def("bundle_adjust_robust(Tensor poses, Tensor points, Tensor camera_indices, Tensor point_indices, Tensor pixels, "
+          "float[] K, int[] fixed, int max_steps, int loss, float loss_scale) -> (Tensor, Tensor, Tensor)");
+    m.def("bundle_adjust_robust_(Tensor(a!) poses, Tensor(b!) points, Tensor camera_indices, Tensor point_indices, "
+          "Tensor pixels, float[] K, int[] fixed, int max_steps, int loss, float loss_scale, Tensor(c!) info) -> ()");
+    m.def("bundle_adjust_pcg_robust(Tensor poses, Tensor points, Tensor camera_indices, Tensor point_indices, Tensor pixels, "
+          "float[] K, int[] fixed, int max_steps, int max_cg_iterations, float cg_tolerance, int loss, float loss_scale) -> "
+          "(Tensor, Tensor, Tensor)");
+    m.def("bundle_adjust_pcg_robust_(Tensor(a!) poses, Tensor(b!) points, Tensor camera_indices, Tensor point_indices, "
+          "Tensor pixels, float[] K, int[] fixed, int max_steps, int max_cg_iterations, float cg_tolerance, int loss, "
+          "float loss_scale, Tensor(c!) info) -> ()");
     m.def("triangulate_tracks(Tensor poses, Tensor camera_indices, Tensor point_indices, Tensor pixels, int points, float[] K, "
           "int min_views, float min_angle, float max_error, int refine_steps) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
     m.def("triangulate_tracks_(Tensor poses, Tensor camera_indices, Tensor point_indices, Tensor pixels, int points, "
@@ -1048,6 +1145,10 @@ TORCH_LIBRARY_IMPL(sfm_hip, CUDA, m) {
     m.impl("bundle_adjust_", &bundle_adjust_inplace);
     m.impl("bundle_adjust_pcg", &bundle_adjust_pcg);
     m.impl("bundle_adjust_pcg_", &bundle_adjust_pcg_inplace);
+    m.impl("bundle_adjust_robust", &bundle_adjust_robust);
+    m.impl("bundle_adjust_robust_", &bundle_adjust_robust_inplace);
+    m.impl("bundle_adjust_pcg_robust", &bundle_adjust_pcg_robust);
+    m.impl("bundle_adjust_pcg_robust_", &bundle_adjust_pcg_robust_inplace);
     m.impl("triangulate_tracks", &triangulate_tracks);
     m.impl("triangulate_tracks_", &triangulate_tracks_out);
     m.impl("build_tracks", &build_tracks);
@@ -1083,6 +1184,10 @@ void bundle_adjust_out_meta(Tensor&, Tensor&, const Tensor&, const Tensor&, cons
                             int64_t, Tensor&) {}
 void bundle_adjust_pcg_out_meta(Tensor&, Tensor&, const Tensor&, const Tensor&, const Tensor&, at::ArrayRef<double>,
                                 at::ArrayRef<int64_t>, int64_t, int64_t, double, Tensor&) {}
+void bundle_adjust_robust_out_meta(Tensor&, Tensor&, const Tensor&, const Tensor&, const Tensor&, at::ArrayRef<double>,
+                                   at::ArrayRef<int64_t>, int64_t, int64_t, double, Tensor&) {}
+void bundle_adjust_pcg_robust_out_meta(Tensor&, Tensor&, const Tensor&, const Tensor&, const Tensor&, at::ArrayRef<double>,
+                                       at::ArrayRef<int64_t>, int64_t, int64_t, double, int64_t, double, Tensor&) {}
 void triangulate_tracks_out_meta(const Tensor&, const Tensor&, const Tensor&, const Tensor&, int64_t, at::ArrayRef<double>, int64_t,
                                  double, double, int64_t, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&) {}
 void build_tracks_out_meta(const Tensor&, const Tensor&, const Tensor&, const Tensor&, int64_t, Tensor&, Tensor&, Tensor&, Tensor&,
@@ -1121,6 +1226,10 @@ TORCH_LIBRARY_IMPL(sfm_hip, Meta, m) {
     m.impl("bundle_adjust_", &bundle_adjust_out_meta);
     m.impl("bundle_adjust_pcg", &bundle_adjust_pcg_meta);
     m.impl("bundle_adjust_pcg_", &bundle_adjust_pcg_out_meta);
+    m.impl("bundle_adjust_robust", &bundle_adjust_robust_meta);
+    m.impl("bundle_adjust_robust_", &bundle_adjust_robust_out_meta);
+    m.impl("bundle_adjust_pcg_robust", &bundle_adjust_pcg_robust_meta);
+    m.impl("bundle_adjust_pcg_robust_", &bundle_adjust_pcg_robust_out_meta);
     m.impl("triangulate_tracks", &triangulate_tracks_meta);
     m.impl("triangulate_tracks_", &triangulate_tracks_out_meta);
     m.impl("build_tracks", &build_tracks_meta);

@@ -781,14 +781,36 @@ def read_pnp_refine_info(info: torch.Tensor) -> List[PnPRefineInfo]:
 # bundle adjustment (csrc/sfm_bundle.hip): poses [C,12] = R (9) | t (3) world -> camera, points [P,3], observations
 # (camera index, point index) int32 [M] each and pixels [M,2]
 # ------------------------------------------------------------------------------------------------------
-def bundle_adjust(poses, points, camera_indices, point_indices, pixels, K, fixed=(0,), max_steps: int = 50, out=None):
+BUNDLE_LOSSES = _native.BUNDLE_LOSSES   # "squared", "huber", "cauchy": the index is the SFM_BUNDLE_LOSS_* code
+
+
+def _bundle_loss(loss: str, loss_scale: float):
+    """(code, scale) of a loss name; ValueError for an unknown name or a scale that is not finite and positive."""
+    if loss not in BUNDLE_LOSSES:
+        raise ValueError(f"loss must be one of {BUNDLE_LOSSES}, got {loss!r}")
+    scale = float(loss_scale)
+    if not (np.isfinite(scale) and scale > 0.0):
+        raise ValueError(f"loss_scale must be finite and positive, got {loss_scale!r}")
+    return BUNDLE_LOSSES.index(loss), scale
+
+
+def bundle_adjust(poses, points, camera_indices, point_indices, pixels, K, fixed=(0,), max_steps: int = 50, out=None, *,
+                  loss: str = "squared", loss_scale: float = 1.0):
     """Levenberg-Marquardt over the free cameras and the points seen at least twice (``sfm_bundle_adjust``) ->
     (poses [C,12], points [P,3], info int64 [4] viewing the sfm_bundle_info record; ``read_bundle_info``).  ``out`` =
     (poses, points, info) runs the in-place op on those tensors instead (poses and points there are the input).  No host
-    synchronisation: the whole call is enqueued at once."""
+    synchronisation: the whole call is enqueued at once.  ``loss`` in ``BUNDLE_LOSSES`` with ``loss_scale`` in pixels
+    (DESIGN.md §6n): ``"squared"`` is the op without a loss, the others run ``bundle_adjust_robust`` and the costs in
+    ``info`` are sums of rho."""
+    code, scale = _bundle_loss(loss, loss_scale)
     op = ops.load()
     args = (camera_indices.contiguous(), point_indices.contiguous(), pixels.contiguous(), _camera_list(K),
             [int(c) for c in fixed], int(max_steps))
+    if code != 0:
+        if out is None:
+            return op.bundle_adjust_robust(poses.contiguous(), points.contiguous(), *args, code, scale)
+        op.bundle_adjust_robust_(out[0], out[1], *args, code, scale, out[2])
+        return out
     if out is None:
         return op.bundle_adjust(poses.contiguous(), points.contiguous(), *args)
     op.bundle_adjust_(out[0], out[1], *args, out[2])
@@ -816,14 +838,22 @@ def read_bundle_info(info: torch.Tensor) -> BundleInfo:
 
 
 def bundle_adjust_pcg(poses, points, camera_indices, point_indices, pixels, K, fixed=(0,), max_steps: int = 50,
-                      max_cg_iterations: int = 100, cg_tolerance: float = 0.1, out=None):
+                      max_cg_iterations: int = 100, cg_tolerance: float = 0.1, out=None, *, loss: str = "squared",
+                      loss_scale: float = 1.0):
     """``bundle_adjust`` over any number of cameras with the iterative Schur solver (``sfm_bundle_adjust_pcg``,
     DESIGN.md §6j) -> (poses [C,12], points [P,3], info int64 [5] viewing the sfm_bundle_pcg_info record;
     ``read_bundle_pcg_info``).  ``out`` = (poses, points, info) runs the in-place op on those tensors instead.  The call
-    synchronises the current stream: the host reads the stop flags between LM steps and CG chunks."""
+    synchronises the current stream: the host reads the stop flags between LM steps and CG chunks.  ``loss`` and
+    ``loss_scale`` as in ``bundle_adjust`` (``bundle_adjust_pcg_robust`` for a non-squared loss)."""
+    code, scale = _bundle_loss(loss, loss_scale)
     op = ops.load()
     args = (camera_indices.contiguous(), point_indices.contiguous(), pixels.contiguous(), _camera_list(K),
             [int(c) for c in fixed], int(max_steps), int(max_cg_iterations), float(cg_tolerance))
+    if code != 0:
+        if out is None:
+            return op.bundle_adjust_pcg_robust(poses.contiguous(), points.contiguous(), *args, code, scale)
+        op.bundle_adjust_pcg_robust_(out[0], out[1], *args, code, scale, out[2])
+        return out
     if out is None:
         return op.bundle_adjust_pcg(poses.contiguous(), points.contiguous(), *args)
     op.bundle_adjust_pcg_(out[0], out[1], *args, out[2])

@@ -124,6 +124,17 @@ def sequence_bundle_problem(cameras: int, points: int, track_length: int = 4, se
                 point_indices=pt.astype(np.int32), pixels=pixels, poses_true=poses, points_true=X)
 
 
+def corrupt_observations(problem, fraction: float, spread_px: float, seed: int):
+    """``problem`` (the dict of ``bundle_problem``) with wrong observations: every observation is picked with probability
+    ``fraction`` and its pixel shifted by uniform +-``spread_px`` in u and in v.  Returns (a new dict with its own
+    ``pixels``, the boolean mask (M,) of the shifted observations)."""
+    rng = np.random.default_rng(seed)
+    pixels = np.array(problem["pixels"], dtype=np.float64)
+    bad = rng.random(len(pixels)) < fraction
+    pixels[bad] += rng.uniform(-spread_px, spread_px, (int(bad.sum()), 2))
+    return dict(problem, pixels=pixels), bad
+
+
 def multi_view_scene(views: int = 8, points: int = 2000, seed: int = 21, noise_px: float = 0.5,
                      outlier_fraction: float = 0.2, step_deg: float = 5.0, K: np.ndarray = BENCH_K):
     """An N-view scene for incremental reconstruction: points uniform in x, y in [-1, 1], z in [4, 6]; camera 0 = [I | 0]
