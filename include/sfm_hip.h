@@ -695,6 +695,31 @@ int sfm_match_summary(int metric, const double* patches_a, int64_t stride_a, con
                       const uint8_t* ok_b, int64_t n_a, int64_t n_b, int window_elements, void* workspace,
                       int64_t workspace_bytes, double* best, int32_t* arg, double* second, void* stream);
 
+/* ---- oriented integer BRIEF descriptors and their Hamming matcher (definition: tests/brief_oracle.py) ---- */
+
+/* 256-bit descriptors of n features of a uint8 image, all in integer arithmetic (bit-exact against the NumPy definition).
+ * Centre pixel xi = floor(x + 0.5), yi = floor(y + 0.5); a feature is valid iff x, y are finite, 15 <= xi <= width - 16 and
+ * 15 <= yi <= height - 16.  Orientation: the intensity moments m10 = sum dx I, m01 = sum dy I over the disc
+ * dx^2 + dy^2 <= 225 fall into the angle bin b with cross(B[b-1], m) >= 0 and cross(B[b], m) < 0 (indices mod bins,
+ * cross(p, m) = p.x m01 - p.y m10 in int64; m = 0: bin 0).  Bit t = 1 iff the 5 x 5 box sum at centre + (ax, ay) is smaller
+ * than the one at centre + (bx, by) for test t of that bin; byte t / 8, bit t % 8.
+ * image: dev u8 [height,width]; feats: dev f64 [n,2] (x, y); offsets: dev int8 [bins,256,4] = (ax, ay, bx, by), every
+ * coordinate within +-13 (clamped); boundaries: dev int64 [bins,2] = B; 1 <= bins <= 64; desc: dev u8 [n,32], 8-byte aligned;
+ * ok, angle_bin: dev u8 [n].  An invalid feature gets an all-zero descriptor, ok = 0, angle_bin = 0. */
+int sfm_brief_describe(const uint8_t* image, int64_t height, int64_t width, const double* feats, int64_t n,
+                       const int8_t* offsets, const int64_t* boundaries, int bins, uint8_t* desc, uint8_t* ok,
+                       uint8_t* angle_bin, void* stream);
+
+/* sfm_match_summary for those descriptors: the score of (a, b) is the Hamming distance of the two 32-byte descriptors as a
+ * double, +inf if either is invalid (ok = 0); best / arg / second have exactly the meaning they have there (heap[0] = first
+ * minimum in b order, heap[1] of the reference's heapq, NaN if n_b == 1), and the |A| x |B| matrix is never written.
+ * desc_a, desc_b: dev u8 [n,32], 16-byte aligned; workspace: dev, 16-byte aligned,
+ * >= sfm_hamming_summary_workspace_bytes(n_a, n_b) bytes. */
+int64_t sfm_hamming_summary_workspace_bytes(int64_t n_a, int64_t n_b);
+int sfm_hamming_summary(const uint8_t* desc_a, const uint8_t* ok_a, int64_t n_a, const uint8_t* desc_b, const uint8_t* ok_b,
+                        int64_t n_b, void* workspace, int64_t workspace_bytes, double* best, int32_t* arg, double* second,
+                        void* stream);
+
 /* ---- Harris corner detector stencils (reference lib/harris/harris_detector.py, lib/common/correlate.py) ---- */
 
 /* Zero-'same' cross-correlation with an odd square kernel (correlate.py:4-39).  image, out: dev f64

@@ -146,6 +146,8 @@ SIGNATURES = {
     "sfm_pair_scores": [C.c_int, _P, _I64, _P, _I64, _P, _P, _P, _P, _I64, _I64, C.c_int, _P, _P],
     "sfm_match_row_summary": [_P, _I64, _I64, _P, _P, _P, _P],
     "sfm_match_summary": [C.c_int, _P, _I64, _P, _I64, _P, _P, _P, _P, _I64, _I64, C.c_int, _P, _I64, _P, _P, _P, _P],
+    "sfm_brief_describe": [_P, _I64, _I64, _P, _I64, _P, _P, C.c_int, _P, _P, _P, _P],
+    "sfm_hamming_summary": [_P, _P, _I64, _P, _P, _I64, _P, _I64, _P, _P, _P, _P],
     "sfm_cross_correlate": [_P, _I64, _I64, _P, C.c_int, _P, _P],
     "sfm_harris_cornerness": [_P, _P, _I64, _I64, C.c_int, _D, C.c_int, _I64, _I64, _P, _P],
     "sfm_nms_inplace": [_P, _I64, _I64, _P],
@@ -182,7 +184,7 @@ SIGNATURES = {
 OTHER_SYMBOLS = ["sfm_last_error", "sfm_abi_version", "sfm_score_workspace_bytes", "sfm_score_workspace_bytes_ex",
                  "sfm_fit_trace_doubles", "sfm_match_summary_workspace_bytes", "sfm_bundle_workspace_bytes",
                  "sfm_tracks_workspace_bytes", "sfm_bundle_pcg_workspace_bytes", "sfm_build_tracks_workspace_bytes",
-                 "sfm_bundle_pcg_workspace_bytes_ex"]
+                 "sfm_bundle_pcg_workspace_bytes_ex", "sfm_hamming_summary_workspace_bytes"]
 
 # the losses of both bundle adjusters, in the order of their SFM_BUNDLE_LOSS_* codes (include/sfm_hip.h)
 BUNDLE_LOSSES = ("squared", "huber", "cauchy")
@@ -227,6 +229,8 @@ def load() -> C.CDLL:
     lib.sfm_score_workspace_bytes_ex.argtypes = [_I64, _I64, _I64, _P]
     lib.sfm_match_summary_workspace_bytes.restype = C.c_int64
     lib.sfm_match_summary_workspace_bytes.argtypes = [_I64, _I64]
+    lib.sfm_hamming_summary_workspace_bytes.restype = C.c_int64
+    lib.sfm_hamming_summary_workspace_bytes.argtypes = [_I64, _I64]
     lib.sfm_bundle_workspace_bytes.restype = C.c_int64
     lib.sfm_bundle_workspace_bytes.argtypes = [_I64, _I64, _I64]
     lib.sfm_tracks_workspace_bytes.restype = C.c_int64

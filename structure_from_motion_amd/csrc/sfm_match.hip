@@ -22,6 +22,7 @@
 #include <stdint.h>
 
 #include "sfm_common.h"
+#include "sfm_match_summary.h"
 #include "sfm_math.h"
 
 namespace {
@@ -333,22 +334,6 @@ __global__ __launch_bounds__(256, 2) void pair_scores_kernel(
     }
 }
 
-SFM_DEVICE bool in_left_subtree(int64_t position_1based) {
-    if (position_1based < 2) return false;
-    const int k = 63 - __builtin_clzll((unsigned long long)position_1based);
-    return position_1based < ((int64_t)1 << k) + ((int64_t)1 << (k - 1));
-}
-
-// (value, index) lexicographic minimum == first occurrence of the smallest value
-struct MinAt {
-    double v;
-    int64_t i;
-};
-SFM_DEVICE MinAt min_at(MinAt a, MinAt b) {
-    const bool take_b = (b.v < a.v) || (b.v == a.v && b.i < a.i);
-    return take_b ? b : a;
-}
-
 __global__ __launch_bounds__(256) void row_summary_kernel(const double* __restrict__ scores, int64_t nA,
                                                           int64_t nB, double* __restrict__ best,
                                                           int32_t* __restrict__ arg,
@@ -396,13 +381,10 @@ __global__ __launch_bounds__(256) void row_summary_kernel(const double* __restri
 }
 
 // ---- fused path: scores never leave the chip ---------------------------------------------------------------
-// The heap summary of a row is a scan in B order, but it splits over column tiles: with c = minimum of everything
-// before the tile and p_i = minimum of the tile's own columns before i,
-//     max(v_i, min(c, p_i)) = min(max(v_i, p_i), max(v_i, c)),   and   min_i max(v_i, c) = max(c, min_i v_i),
-// so per (row, tile) four numbers suffice: M = tile minimum, its first column, A = min over left-subtree columns of
-// max(v_i, p_i), B = min over left-subtree columns of v_i.  All of it is selection (min / max / compare), no
-// arithmetic: the result is bit-identical to row_summary_kernel on the full matrix.  32 B per 128 scores leave
-// the kernel instead of 1 KiB, and the matrix is never re-read.
+// The heap summary of a row is a scan in B order, but it splits over column tiles into four numbers per (row, tile)
+// (TileSummary and its derivation: sfm_match_summary.h, shared with the Hamming matcher); the result is bit-identical to
+// row_summary_kernel on the full matrix.  32 B per 128 scores leave the kernel instead of 1 KiB, and the matrix is
+// never re-read.
 // 16-lane row rotations by DPP (a VALU move modifier: no LDS crossbar, unlike __shfl): lane l of a row reads lane
 // (l + N) mod 16 of the same row.
 template <int N>
@@ -442,12 +424,6 @@ SFM_DEVICE TopTwo top_two_ror(const TopTwo& t) {
     r.m2 = row_ror<N>(t.m2);
     return r;
 }
-
-struct TileSummary {
-    double tile_min, left_prefixed, left_min;
-    int64_t tile_arg;
-};
-static_assert(sizeof(TileSummary) == 32, "workspace sizing in sfm_match_summary_workspace_bytes");
 
 template <int MODE, bool DIRECT>
 __global__ __launch_bounds__(256, 2) void pair_summary_kernel(
@@ -589,26 +565,6 @@ __global__ __launch_bounds__(256, 2) void pair_summary_kernel(
             tiles[tile.b_tile * nA + ia] = r;
         }
     }
-}
-
-// one thread per A-feature walks its tile summaries in B order
-__global__ void summary_combine_kernel(const TileSummary* __restrict__ tiles, int64_t nA, int64_t nB,
-                                       int64_t n_tiles, double* __restrict__ best, int32_t* __restrict__ arg,
-                                       double* __restrict__ second) {
-    const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (row >= nA) return;
-    double before = INFINITY, sec = INFINITY;  // `before`: minimum of all columns ahead of the tile
-    MinAt top = {INFINITY, INT64_MAX};
-    for (int64_t t = 0; t < n_tiles; ++t) {
-        const TileSummary r = tiles[t * nA + row];
-        const double via_before = (r.left_min < before) ? before : r.left_min;
-        sec = fmin(sec, fmin(r.left_prefixed, via_before));
-        top = min_at(top, MinAt{r.tile_min, r.tile_arg});
-        before = fmin(before, r.tile_min);
-    }
-    best[row] = top.v;
-    arg[row] = (int32_t)top.i;
-    second[row] = nB > 1 ? sec : NAN;
 }
 
 // LDS-DMA staging reads whole 128-feature rows: every row must be 16-byte aligned and long enough that the last

@@ -137,3 +137,29 @@ def match_summary(metric: int, image_a, image_b, feats_a, feats_b, window_size: 
                                     best.data_ptr(), arg.data_ptr(), second.data_ptr(), device._stream()),
               "sfm_match_summary")
     return _summary_to_host(out, nA)
+
+
+def hamming_summary(bits_a, valid_a, bits_b, valid_b):
+    """heap[0] score / b index and heap[1] score per A-descriptor for Hamming distances of 32-byte binary descriptors
+    (``sfm_hamming_summary``): the distance as a float64, +inf where either descriptor is invalid; the same meaning as
+    ``match_summary``, and the score matrix is never materialised.  bits: (n, 32) uint8; valid: (n,) bool."""
+    bits_a, bits_b = (np.ascontiguousarray(b, dtype=np.uint8) for b in (bits_a, bits_b))
+    valid_a, valid_b = (np.ascontiguousarray(np.asarray(v, dtype=bool), dtype=np.uint8) for v in (valid_a, valid_b))
+    for bits, valid in ((bits_a, valid_a), (bits_b, valid_b)):
+        if bits.ndim != 2 or bits.shape[1] != 32 or valid.shape != (bits.shape[0],):
+            raise ValueError("hamming_summary: descriptors must be (n, 32) uint8 with (n,) validity flags")
+    nA, nB = bits_a.shape[0], bits_b.shape[0]
+    if nA and not nB:
+        raise ValueError("hamming_summary: no descriptors to match against")
+    lib = _native.load()
+    dev = device.require_gpu()
+    out, best, arg, second = _summary_buffers(nA, dev)
+    if nA:
+        da, db = torch.as_tensor(bits_a).to(dev), torch.as_tensor(bits_b).to(dev)
+        oka, okb = torch.as_tensor(valid_a).to(dev), torch.as_tensor(valid_b).to(dev)
+        ws_bytes = int(lib.sfm_hamming_summary_workspace_bytes(nA, nB))
+        ws = torch.empty((ws_bytes // 8,), dtype=F64, device=dev)
+        check(lib.sfm_hamming_summary(da.data_ptr(), oka.data_ptr(), nA, db.data_ptr(), okb.data_ptr(), nB, ws.data_ptr(),
+                                      ws_bytes, best.data_ptr(), arg.data_ptr(), second.data_ptr(), device._stream()),
+              "sfm_hamming_summary")
+    return _summary_to_host(out, nA)

@@ -7,6 +7,8 @@
   ``ImagePairScore`` object, a ``functools.partial`` of ``calculate_ncc`` / ``calculate_ssd`` with both images
   bound, or a closure shaped like ``apps/sfm.py:_create_score_function``), all ``|A| x |B|`` scores and the
   per-feature heap summaries are computed by HIP kernels;
+* when it is a ``BriefScore`` (``brief.py``: Hamming distance of oriented BRIEF descriptors), both feature lists are
+  described and summarised by HIP kernels as well;
 * for any other callable the loop is host logic, with a real ``heapq`` like the reference.
 
 Kept quirks: the ratio test divides ``heap[0]`` by ``heap[1]`` of the per-feature heap — the root's left
@@ -25,6 +27,7 @@ from typing import Callable, Dict, List, NewType, Optional, Set
 import numpy as np
 
 from ..common.feature import Feature
+from .brief import BriefScore
 
 # Interface of a score function: (feature_a, feature_b) -> float, lower is better.
 ScoreFunction = NewType("ScoreFunction", Callable[[Feature, Feature], float])
@@ -137,7 +140,10 @@ def match_brute_force(
         strategies = {validation_strategies}
 
     spec = _device_score_spec(score_function)
-    if spec is not None and len(features_a) > 0 and len(features_b) > 0:
+    if isinstance(score_function, BriefScore) and len(features_a) > 0 and len(features_b) > 0:
+        best, arg, second = _brief_rows(score_function, features_a, features_b)
+        has_second = len(features_b) > 1
+    elif spec is not None and len(features_a) > 0 and len(features_b) > 0:
         best, arg, second = _device_rows(spec, features_a, features_b)
         has_second = len(features_b) > 1
     else:
@@ -177,6 +183,13 @@ def _device_rows(spec, features_a, features_b):
 
     metric, image_a, image_b, window_size = spec
     return _device_match.match_summary(metric, image_a, image_b, features_a, features_b, window_size)
+
+
+def _brief_rows(score: BriefScore, features_a, features_b):
+    from . import _device_match
+
+    a, b = score.describe(0, features_a), score.describe(1, features_b)
+    return _device_match.hamming_summary(a.bits, a.valid, b.bits, b.valid)
 
 
 def _host_rows(features_a, features_b, score_function):

@@ -302,3 +302,56 @@ def match_graph(images: int, features: int, neighbours: int, matches_per_pair: i
     return dict(image_offset=off.astype(np.int32), pairs=np.column_stack([a_img, b_img]).astype(np.int32),
                 match_offset=(np.arange(Q + 1, dtype=np.int64) * matches_per_pair).astype(np.int32),
                 match_index=np.column_stack([la.reshape(-1), lb.reshape(-1)]).astype(np.int32), feature_points=feature_points)
+
+
+def rotated_texture_pair(height: int, width: int, degrees: float, n: int, seed: int, noise: float = 0.01):
+    """Two uint8 views of one band-limited random texture, the second rotated by ``degrees`` about the image centre, with
+    ``n`` ground-truth feature pairs: the scene the descriptor matchers are compared on.
+
+    The texture is white noise smoothed by a separable Gaussian (sigma 1.5 px) on a square canvas that covers the image at
+    every rotation, stretched to 0..255 and quantised.  The first image is the canvas's central ``height`` x ``width``
+    crop.  Pixel q of the second image samples the quantised canvas bilinearly at centre + R(degrees) (q - centre), plus
+    Gaussian noise of standard deviation ``noise`` * 255, rounded and clipped.  A feature at p in the first image is
+    therefore at centre + R(-degrees) (p - centre) in the second.  First-image features are integer pixels; a pair is kept
+    only if both ends are at least 20 px from every border.  Pure NumPy, elementwise operations only.
+
+    Returns (image_a, image_b, pairs): pairs float64 [n, 4] = (xa, ya, xb, yb)."""
+    if height < 48 or width < 48:
+        raise ValueError("rotated_texture_pair: the image must be at least 48 x 48")
+    rng = np.random.default_rng(seed)
+    side = int(np.ceil(np.hypot(height, width))) + 8
+    radius, sigma = 5, 1.5
+    taps = np.exp(-0.5 * (np.arange(-radius, radius + 1) / sigma) ** 2)
+    taps /= taps.sum()
+    white = rng.standard_normal((side + 2 * radius, side + 2 * radius))
+    rows = sum(taps[k] * white[:, k:k + side] for k in range(2 * radius + 1))
+    smooth = sum(taps[k] * rows[k:k + side, :] for k in range(2 * radius + 1))
+    lo, hi = smooth.min(), smooth.max()
+    canvas = np.floor((smooth - lo) / (hi - lo) * 255.0 + 0.5)
+    oy, ox = (side - height) // 2, (side - width) // 2
+    image_a = canvas[oy:oy + height, ox:ox + width].astype(np.uint8)
+
+    cx, cy = (width - 1) / 2.0, (height - 1) / 2.0
+    th = np.deg2rad(degrees)
+    c, s = np.cos(th), np.sin(th)
+    qx, qy = np.meshgrid(np.arange(width, dtype=np.float64), np.arange(height, dtype=np.float64))
+    sx = cx + c * (qx - cx) - s * (qy - cy) + ox
+    sy = cy + s * (qx - cx) + c * (qy - cy) + oy
+    x0 = np.clip(np.floor(sx).astype(np.int64), 0, side - 2)
+    y0 = np.clip(np.floor(sy).astype(np.int64), 0, side - 2)
+    fx, fy = sx - x0, sy - y0
+    value = ((1 - fy) * ((1 - fx) * canvas[y0, x0] + fx * canvas[y0, x0 + 1])
+             + fy * ((1 - fx) * canvas[y0 + 1, x0] + fx * canvas[y0 + 1, x0 + 1]))
+    value = value + rng.standard_normal(value.shape) * (noise * 255.0)
+    image_b = np.clip(np.floor(value + 0.5), 0, 255).astype(np.uint8)
+
+    border = 20
+    pairs = np.empty((0, 4))
+    while len(pairs) < n:
+        xa = rng.integers(border, width - border, 4 * n).astype(np.float64)
+        ya = rng.integers(border, height - border, 4 * n).astype(np.float64)
+        xb = cx + c * (xa - cx) + s * (ya - cy)
+        yb = cy - s * (xa - cx) + c * (ya - cy)
+        keep = (xb >= border) & (xb <= width - 1 - border) & (yb >= border) & (yb <= height - 1 - border)
+        pairs = np.concatenate([pairs, np.column_stack([xa, ya, xb, yb])[keep]])
+    return image_a, image_b, pairs[:n]
