@@ -14,6 +14,7 @@
 
 #include "sfm_common.h"
 #include "sfm_math.h"
+#include "sfm_minimal_fit.h"
 #include "sfm_p3p.h"
 #include "sfm_pnp.h"
 
@@ -21,7 +22,7 @@ namespace {
 
 using sfmhost::check_launch;
 using sfmhost::fail;
-using sfmhost::grid_fits;
+using sfmhost::fail_in;
 using sfmhost::grid_for;
 using sfmhost::grid_stride;
 using sfmpnp::camera_from;
@@ -35,6 +36,14 @@ constexpr int kP3PSample = 4;   // P3P: three items solved for, the fourth picks
 // Coplanar and collinear points give three or more null vectors: their ratio is at the rounding level (~1e-16).
 constexpr double kPnPDegenerateFloor = 1e-9;
 
+// What the pose fits read besides the sample: the items of every batch entry and the camera.  The solvers below are the
+// `Solver` of sfmmin::minimal_fit_kernel (sfm_minimal_fit.h), named like the kernels they parameterise so that a profile
+// filtered by "pnp" / "p3p" finds minimal_fit_kernel<pnp_dlt_solver, ...> and minimal_fit_kernel<p3p_solver, ...>.
+struct PoseData {
+    const double* pts;
+    PnPCamera cam;
+};
+
 // --------------------------------------------------------------------------------------------------
 // Six-point DLT fit of one hypothesis (the steps of the PnP fitter, structure_from_motion_amd/pnp/pnp.py):
 //   1. pixels -> normalised image coordinates (x, y, 1) = K^-1 (u, v, 1) by sfmpnp::normalized_coords: with du = u - K02,
@@ -46,9 +55,18 @@ constexpr double kPnPDegenerateFloor = 1e-9;
 //   5. sign of P flipped if det(M) < 0; M = U S V^T, R = U V^T;
 //   6. t = p4 / mean(S).
 // Returns the fit flag: SFM_FIT_DEGENERATE when sigma_11 / sigma_1 < kPnPDegenerateFloor or a sample index is out of range.
+// One hypothesis per lane: the 12 x 12 SVD keeps its two matrices (288 doubles) in registers as far as they go.
 // --------------------------------------------------------------------------------------------------
-SFM_DEVICE int pnp_fit_one(const double* __restrict__ pts, int64_t n, const int32_t idx[kPnPSample], const PnPCamera& k,
-                           double out[12]) {
+struct pnp_dlt_solver {
+    static constexpr int kSample = kPnPSample, kModel = 12;
+    static constexpr const char* kName = "minimal_fit_kernel<pnp_dlt_solver>";
+    using Data = PoseData;
+    SFM_DEVICE static int fit(const Data& data, int64_t b, int64_t n, const int32_t (&idx)[8], double (&out)[12]);
+};
+
+SFM_DEVICE int pnp_dlt_solver::fit(const Data& data, int64_t b, int64_t n, const int32_t (&idx)[8], double (&out)[12]) {
+    const double* __restrict__ pts = data.pts + b * n * kPnPFields;
+    const PnPCamera& k = data.cam;
     bool bad = false;
     double X[kPnPSample][3], x[kPnPSample], y[kPnPSample];
 #pragma unroll
@@ -153,100 +171,24 @@ SFM_DEVICE int pnp_fit_one(const double* __restrict__ pts, int64_t n, const int3
     return degenerate ? SFM_FIT_DEGENERATE : 0;
 }
 
-// One hypothesis per lane: the 12 x 12 SVD keeps its two matrices (288 doubles) in registers as far as they go.
-__global__ __launch_bounds__(64) void pnp_fit_kernel(const double* __restrict__ pts, int64_t n, const int32_t* __restrict__ S,
-                                                     int64_t h_count, PnPCamera cam, double* __restrict__ model,
-                                                     int32_t* __restrict__ flags) {
-    const int64_t h = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (h >= h_count) return;
-    const int64_t b = blockIdx.y;
-    const int64_t bh = b * h_count + h;
-    int32_t idx[kPnPSample];
-#pragma unroll
-    for (int i = 0; i < kPnPSample; ++i) idx[i] = S[bh * 8 + i];
-    double out[12];
-    const int flag = pnp_fit_one(pts + b * n * kPnPFields, n, idx, cam, out);
-#pragma unroll
-    for (int i = 0; i < 12; ++i) model[bh * 12 + i] = out[i];
-    flags[bh] = flag;
-}
-
-// Philox sampling fused into the fit: hypothesis h of batch entry b draws philox_sample8(seed + b * seed_stride, h_begin + h)
-// (the sampler of sfm_sample_philox) and uses its first six indices; S receives all eight (-1 at positions >= n).
-__global__ __launch_bounds__(64) void pnp_sample_fit_philox_kernel(uint64_t seed, uint64_t seed_stride, int64_t h_begin,
-                                                                   const double* __restrict__ pts, int64_t n, int64_t h_count,
-                                                                   PnPCamera cam, int32_t* __restrict__ S,
-                                                                   double* __restrict__ model, int32_t* __restrict__ flags) {
-    const int64_t h = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (h >= h_count) return;
-    const int64_t b = blockIdx.y;
-    const int64_t bh = b * h_count + h;
-    int32_t idx[8];
-    sfm::philox_sample8(seed + (uint64_t)b * seed_stride, (uint64_t)(h_begin + h), (uint32_t)n, idx);
-#pragma unroll
-    for (int i = kPnPSample; i < 8; ++i) idx[i] = i < n ? idx[i] : -1;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) S[bh * 8 + i] = idx[i];
-    double out[12];
-    const int flag = pnp_fit_one(pts + b * n * kPnPFields, n, idx, cam, out);
-#pragma unroll
-    for (int i = 0; i < 12; ++i) model[bh * 12 + i] = out[i];
-    flags[bh] = flag;
-}
-
 // P3P fit of one hypothesis (sfm_p3p.h) from sample indices idx[0..3]: SFM_FIT_DEGENERATE when items 0-2 are collinear or
 // coincide or an index is out of range; otherwise the chosen model, or 12 NaNs when the sample has no solution (flag 0).
-SFM_DEVICE int p3p_fit_indices(const double* __restrict__ pts, int64_t n, const int32_t idx[kP3PSample], const PnPCamera& k,
-                               double out[12]) {
-    bool bad = false;
-    const double* q0 = pts + checked_index(idx[0], n, bad) * kPnPFields;
-    const double* q1 = pts + checked_index(idx[1], n, bad) * kPnPFields;
-    const double* q2 = pts + checked_index(idx[2], n, bad) * kPnPFields;
-    const double* q3 = pts + checked_index(idx[3], n, bad) * kPnPFields;
-    const bool ok = sfmp3p::p3p_fit_one(q0, q1, q2, q3, k, out);
-    return (bad || !ok) ? SFM_FIT_DEGENERATE : 0;
-}
-
-// One hypothesis per lane, all in registers: the up-to-four candidates are scored as they are made (sfm_p3p.h).
-__global__ __launch_bounds__(64) void p3p_fit_kernel(const double* __restrict__ pts, int64_t n, const int32_t* __restrict__ S,
-                                                     int64_t h_count, PnPCamera cam, double* __restrict__ model,
-                                                     int32_t* __restrict__ flags) {
-    const int64_t h = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (h >= h_count) return;
-    const int64_t b = blockIdx.y;
-    const int64_t bh = b * h_count + h;
-    int32_t idx[kP3PSample];
-#pragma unroll
-    for (int i = 0; i < kP3PSample; ++i) idx[i] = S[bh * 8 + i];
-    double out[12];
-    const int flag = p3p_fit_indices(pts + b * n * kPnPFields, n, idx, cam, out);
-#pragma unroll
-    for (int i = 0; i < 12; ++i) model[bh * 12 + i] = out[i];
-    flags[bh] = flag;
-}
-
-// Philox sampling fused into the P3P fit, as pnp_sample_fit_philox_kernel: the first four of philox_sample8 are the sample;
-// S receives all eight (-1 at positions >= n, so n = 4 and 5 are valid).
-__global__ __launch_bounds__(64) void p3p_sample_fit_philox_kernel(uint64_t seed, uint64_t seed_stride, int64_t h_begin,
-                                                                   const double* __restrict__ pts, int64_t n, int64_t h_count,
-                                                                   PnPCamera cam, int32_t* __restrict__ S,
-                                                                   double* __restrict__ model, int32_t* __restrict__ flags) {
-    const int64_t h = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (h >= h_count) return;
-    const int64_t b = blockIdx.y;
-    const int64_t bh = b * h_count + h;
-    int32_t idx[8];
-    sfm::philox_sample8(seed + (uint64_t)b * seed_stride, (uint64_t)(h_begin + h), (uint32_t)n, idx);
-#pragma unroll
-    for (int i = kP3PSample; i < 8; ++i) idx[i] = i < n ? idx[i] : -1;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) S[bh * 8 + i] = idx[i];
-    double out[12];
-    const int flag = p3p_fit_indices(pts + b * n * kPnPFields, n, idx, cam, out);
-#pragma unroll
-    for (int i = 0; i < 12; ++i) model[bh * 12 + i] = out[i];
-    flags[bh] = flag;
-}
+// One hypothesis per lane, all in registers: the up-to-four candidates are scored as they are made.
+struct p3p_solver {
+    static constexpr int kSample = kP3PSample, kModel = 12;
+    static constexpr const char* kName = "minimal_fit_kernel<p3p_solver>";
+    using Data = PoseData;
+    SFM_DEVICE static int fit(const Data& data, int64_t b, int64_t n, const int32_t (&idx)[8], double (&out)[12]) {
+        const double* __restrict__ pts = data.pts + b * n * kPnPFields;
+        bool bad = false;
+        const double* q0 = pts + checked_index(idx[0], n, bad) * kPnPFields;
+        const double* q1 = pts + checked_index(idx[1], n, bad) * kPnPFields;
+        const double* q2 = pts + checked_index(idx[2], n, bad) * kPnPFields;
+        const double* q3 = pts + checked_index(idx[3], n, bad) * kPnPFields;
+        const bool ok = sfmp3p::p3p_fit_one(q0, q1, q2, q3, data.cam, out);
+        return (bad || !ok) ? SFM_FIT_DEGENERATE : 0;
+    }
+};
 
 // --------------------------------------------------------------------------------------------------
 // Scoring: one hypothesis per lane (its model in registers), the points staged through LDS in tiles that every lane of
@@ -356,47 +298,20 @@ __global__ void pnp_inlier_mask_kernel(const double* __restrict__ pts, int64_t n
 // Every check of a call that depends on its sizes, before anything is launched: `sample` (4 or 6) items per sample, n at
 // least that, the grids of the fit and scoring launches, and the camera matrix.
 int check_call(const char* fn, int sample, int64_t n, int64_t h_count, int64_t batch, const double* K, PnPCamera& cam) {
-    char msg[200];
     if (sample != kPnPSample && sample != kP3PSample) {
+        char msg[200];
         snprintf(msg, sizeof msg, "%s: sample_size must be 4 or 6, got %d", fn, sample);
         return fail(SFM_EINVAL, msg);
     }
-    if (n < 0 || h_count < 0 || batch < 0) {
-        snprintf(msg, sizeof msg, "%s: negative size", fn);
-        return fail(SFM_EINVAL, msg);
-    }
-    if (n < sample || n > 0x7FFFFFFF) {
-        snprintf(msg, sizeof msg, "%s: need %d <= n < 2^31 2D-3D pairs", fn, sample);
-        return fail(SFM_EINVAL, msg);
-    }
-    if (batch > 65535 || !grid_fits(h_count, kPnPScoreBlock, kPnPScoreBlock, batch) || !grid_fits(h_count, 64, 64, batch)) {
-        snprintf(msg, sizeof msg, "%s: size exceeds what one launch covers (2^31-1 blocks, 2^32-1 threads in x; 65535 in y)", fn);
-        return fail(SFM_EINVAL, msg);
-    }
-    return camera_from(K, cam, fn);
-}
-
-int fail_with(const char* fn, const char* what) {
-    char msg[160];
-    snprintf(msg, sizeof msg, "%s: %s", fn, what);
-    return fail(SFM_EINVAL, msg);
+    const int rc = sfmhost::check_sizes(fn, sample, n, h_count, batch, {kPnPScoreBlock, sfmmin::kMinimalFitBlock});
+    return rc != SFM_OK ? rc : camera_from(K, cam, fn);
 }
 
 // The fit of every hypothesis: DLT or P3P, from the sample table S, or (philox) with the samples drawn in the launch.
 int launch_fit(bool p3p, bool philox, uint64_t seed, uint64_t seed_stride, int64_t h_begin, const double* pts, int64_t n,
                int64_t h_count, int64_t batch, const PnPCamera& cam, int32_t* S, double* model, int32_t* flags, hipStream_t st) {
-    const dim3 grid(grid_for(h_count, 64), (unsigned)batch);
-    if (p3p && philox)
-        hipLaunchKernelGGL(p3p_sample_fit_philox_kernel, grid, dim3(64), 0, st, seed, seed_stride, h_begin, pts, n, h_count, cam, S,
-                           model, flags);
-    else if (p3p)
-        hipLaunchKernelGGL(p3p_fit_kernel, grid, dim3(64), 0, st, pts, n, (const int32_t*)S, h_count, cam, model, flags);
-    else if (philox)
-        hipLaunchKernelGGL(pnp_sample_fit_philox_kernel, grid, dim3(64), 0, st, seed, seed_stride, h_begin, pts, n, h_count, cam, S,
-                           model, flags);
-    else
-        hipLaunchKernelGGL(pnp_fit_kernel, grid, dim3(64), 0, st, pts, n, (const int32_t*)S, h_count, cam, model, flags);
-    return check_launch(p3p ? "p3p_fit_kernel" : "pnp_fit_kernel");
+    const auto launch = p3p ? sfmmin::launch_minimal_fit<p3p_solver> : sfmmin::launch_minimal_fit<pnp_dlt_solver>;
+    return launch(PoseData{pts, cam}, philox, seed, seed_stride, h_begin, n, h_count, batch, S, model, flags, st);
 }
 
 int launch_score(int sample, const double* pts, int64_t n, const double* model, const int32_t* S, int64_t h_count, int64_t batch,
@@ -426,9 +341,9 @@ int fit_entry(const char* fn, bool p3p, bool philox, uint64_t seed, uint64_t see
     PnPCamera cam;
     const int rc = check_call(fn, p3p ? kP3PSample : kPnPSample, n, h_count, batch, K, cam);
     if (rc != SFM_OK) return rc;
-    if (h_begin < 0) return fail_with(fn, "negative h_begin");
+    if (h_begin < 0) return fail_in(fn, "negative h_begin");
     if (h_count == 0 || batch == 0) return SFM_OK;
-    if (!pts || !S || !model || !flags) return fail_with(fn, "null pointer");
+    if (!pts || !S || !model || !flags) return fail_in(fn, "null pointer");
     return launch_fit(p3p, philox, seed, seed_stride, h_begin, pts, n, h_count, batch, cam, S, model, flags, (hipStream_t)stream);
 }
 
@@ -464,7 +379,7 @@ int sfm_pnp_score(const double* pts, int64_t n, const double* model, const int32
     const int rc = check_call("sfm_pnp_score", sample_size, n, h_count, batch, K, cam);
     if (rc != SFM_OK) return rc;
     if (h_count == 0 || batch == 0) return SFM_OK;
-    if (!pts || !model || !S || !cnt || !s1 || !s2) return fail_with("sfm_pnp_score", "null pointer");
+    if (!pts || !model || !S || !cnt || !s1 || !s2) return fail_in("sfm_pnp_score", "null pointer");
     return launch_score(sample_size, pts, n, model, S, h_count, batch, cam, thr, cnt, s1, s2, (hipStream_t)stream);
 }
 
@@ -474,7 +389,7 @@ int sfm_pnp_inlier_mask(const double* pts, int64_t n, const double* model, const
     const int rc = check_call("sfm_pnp_inlier_mask", sample_size, n, h_count, batch, K, cam);
     if (rc != SFM_OK) return rc;
     if (batch == 0) return SFM_OK;
-    if (!pts || !model || !S || !result || !mask) return fail_with("sfm_pnp_inlier_mask", "null pointer");
+    if (!pts || !model || !S || !result || !mask) return fail_in("sfm_pnp_inlier_mask", "null pointer");
     return launch_mask(sample_size, pts, n, model, S, h_count, batch, cam, result, thr, mask, (hipStream_t)stream);
 }
 
@@ -482,8 +397,6 @@ int sfm_pnp_ransac_pass(int solver, uint64_t seed, uint64_t seed_stride, int use
                         int64_t h_count, int64_t batch, const double* K, double thr, double min_extra, int aggregation, int32_t* S,
                         double* model, int32_t* flags, int32_t* cnt, double* s1, double* s2, sfm_select_result* result,
                         uint8_t* mask, void* stream) {
-    // every argument and grid is checked before the first launch, all that sfm_select_best checks included: a refused call
-    // has enqueued nothing
     const char* fn = "sfm_pnp_ransac_pass";
     if (solver != SFM_PNP_SOLVER_DLT && solver != SFM_PNP_SOLVER_P3P) {
         char msg[120];
@@ -493,19 +406,11 @@ int sfm_pnp_ransac_pass(int solver, uint64_t seed, uint64_t seed_stride, int use
     const bool p3p = solver == SFM_PNP_SOLVER_P3P;
     const int sample = p3p ? kP3PSample : kPnPSample;
     PnPCamera cam;
-    int rc = check_call(fn, sample, n, h_count, batch, K, cam);
-    if (rc != SFM_OK) return rc;
-    if (aggregation < SFM_AGG_SUM || aggregation > SFM_AGG_RMS) return fail_with(fn, "unknown aggregation");
-    if (h_begin < 0) return fail_with(fn, "negative h_begin");
-    if (batch == 0) return SFM_OK;
-    if (!pts || !S || !model || !flags || !cnt || !s1 || !s2 || !result) return fail_with(fn, "null pointer");
     hipStream_t st = (hipStream_t)stream;
-    if (h_count > 0) {
-        rc = launch_fit(p3p, use_philox != 0, seed, seed_stride, h_begin, pts, n, h_count, batch, cam, S, model, flags, st);
-        if (rc != SFM_OK) return rc;
-        if ((rc = launch_score(sample, pts, n, model, S, h_count, batch, cam, thr, cnt, s1, s2, st)) != SFM_OK) return rc;
-    }
-    rc = sfm_select_best(cnt, s1, s2, flags, h_count, batch, min_extra, aggregation, 0, sample, result, stream);
-    if (rc != SFM_OK || mask == nullptr) return rc;
-    return launch_mask(sample, pts, n, model, S, h_count, batch, cam, result, thr, mask, st);
+    return sfmmin::ransac_pass(
+        fn, check_call(fn, sample, n, h_count, batch, K, cam), sample, h_begin, h_count, batch, min_extra, aggregation, pts,
+        {S, model, flags, cnt, s1, s2, result, mask}, stream,
+        [&] { return launch_fit(p3p, use_philox != 0, seed, seed_stride, h_begin, pts, n, h_count, batch, cam, S, model, flags, st); },
+        [&] { return launch_score(sample, pts, n, model, S, h_count, batch, cam, thr, cnt, s1, s2, st); },
+        [&] { return launch_mask(sample, pts, n, model, S, h_count, batch, cam, result, thr, mask, st); });
 }

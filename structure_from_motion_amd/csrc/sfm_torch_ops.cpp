@@ -153,8 +153,15 @@ Tensor sample_philox(int64_t seed, int64_t seed_stride, int64_t h_begin, int64_t
     return S;
 }
 
-// ---- fit_eight_point -------------------------------------------------------------------------------------------
-void fit_eight_point_out(const Tensor& corr, const Tensor& S, Tensor& E, Tensor& flags) {
+// ---- fit_eight_point and five_point_fit (six-item samples, sfm_five_point.hip): one body, the entry point differs ----
+using EssentialFit = int (*)(const double*, int64_t, const int32_t*, int64_t, int64_t, double*, int32_t*, void*);
+
+int fit_eight_point_entry(const double* corr, int64_t n, const int32_t* S, int64_t h, int64_t batch, double* E, int32_t* flags,
+                          void* stream) {
+    return sfm_fit_eight_point(corr, n, S, h, batch, E, flags, nullptr, stream);
+}
+
+void essential_fit(EssentialFit entry, const char* name, const Tensor& corr, const Tensor& S, Tensor& E, Tensor& flags) {
     const OpDevice scope(corr);
     need(corr, "corr", at::kDouble);
     need(S, "S", at::kInt);
@@ -163,16 +170,24 @@ void fit_eight_point_out(const Tensor& corr, const Tensor& S, Tensor& E, Tensor&
     const Dims d = hypothesis_dims(corr, S);
     check_E(E, d);
     TORCH_CHECK(flags.numel() == d.batch * d.h, "sfm_hip: flags must be [batch, h]");
-    ok(sfm_fit_eight_point(ptr<double>(corr), d.n, ptr<int32_t>(S), d.h, d.batch, ptr<double>(E), ptr<int32_t>(flags),
-                           nullptr, current_stream()),
-       "sfm_fit_eight_point");
+    ok(entry(ptr<double>(corr), d.n, ptr<int32_t>(S), d.h, d.batch, ptr<double>(E), ptr<int32_t>(flags), current_stream()), name);
 }
 
-std::tuple<Tensor, Tensor> fit_eight_point(const Tensor& corr, const Tensor& S) {
+void fit_eight_point_out(const Tensor& corr, const Tensor& S, Tensor& E, Tensor& flags) {
+    essential_fit(fit_eight_point_entry, "sfm_fit_eight_point", corr, S, E, flags);
+}
+
+void five_point_fit_out(const Tensor& corr, const Tensor& S, Tensor& E, Tensor& flags) {
+    essential_fit(sfm_five_point_fit, "sfm_five_point_fit", corr, S, E, flags);
+}
+
+// the allocating form of an in-place fit
+template <void (*FitOut)(const Tensor&, const Tensor&, Tensor&, Tensor&)>
+std::tuple<Tensor, Tensor> essential_fit_new(const Tensor& corr, const Tensor& S) {
     const Dims d = hypothesis_dims(corr, S);
     Tensor E = at::empty({d.batch, d.h, 9}, like(corr, at::kDouble));
     Tensor flags = at::empty({d.batch, d.h}, like(corr, at::kInt));
-    fit_eight_point_out(corr, S, E, flags);
+    FitOut(corr, S, E, flags);
     return {E, flags};
 }
 
@@ -187,26 +202,27 @@ std::tuple<Tensor, Tensor> fit_eight_point_meta(const Tensor& corr, const Tensor
             at::empty_symint({corr.sym_size(0), S.sym_size(1)}, like(corr, at::kInt))};
 }
 
-// ---- five-point fit (six-item samples, sfm_five_point.hip): the tensors of fit_eight_point --------------------------
-void five_point_fit_out(const Tensor& corr, const Tensor& S, Tensor& E, Tensor& flags) {
-    const OpDevice scope(corr);
-    need(corr, "corr", at::kDouble);
+// The tensors every whole-pass op takes, checked: `items` ("corr" / "pts") and `model` ("E" / "model") by their names in the
+// op; the shape of `model` is left to the caller.
+Dims pass_checks(const Tensor& items, const char* items_name, Dims (*dims)(const Tensor&, const Tensor&), const Tensor& S,
+                 const Tensor& model, const char* model_name, const Tensor& flags, const Tensor& cnt, const Tensor& s1, const Tensor& s2,
+                 const Tensor& result, const std::optional<Tensor>& mask) {
+    need(items, items_name, at::kDouble);
     need(S, "S", at::kInt);
-    need(E, "E", at::kDouble);
+    need(model, model_name, at::kDouble);
     need(flags, "flags", at::kInt);
-    const Dims d = hypothesis_dims(corr, S);
-    check_E(E, d);
-    TORCH_CHECK(flags.numel() == d.batch * d.h, "sfm_hip: flags must be [batch, h]");
-    ok(sfm_five_point_fit(ptr<double>(corr), d.n, ptr<int32_t>(S), d.h, d.batch, ptr<double>(E), ptr<int32_t>(flags), current_stream()),
-       "sfm_five_point_fit");
-}
-
-std::tuple<Tensor, Tensor> five_point_fit(const Tensor& corr, const Tensor& S) {
-    const Dims d = hypothesis_dims(corr, S);
-    Tensor E = at::empty({d.batch, d.h, 9}, like(corr, at::kDouble));
-    Tensor flags = at::empty({d.batch, d.h}, like(corr, at::kInt));
-    five_point_fit_out(corr, S, E, flags);
-    return {E, flags};
+    need(cnt, "cnt", at::kInt);
+    need(s1, "s1", at::kDouble);
+    need(s2, "s2", at::kDouble);
+    need(result, "result", at::kLong);
+    if (mask.has_value()) need(*mask, "mask", at::kByte);
+    const Dims d = dims(items, S);
+    TORCH_CHECK(flags.numel() == d.batch * d.h && cnt.numel() == d.batch * d.h && s1.numel() == d.batch * d.h &&
+                    s2.numel() == d.batch * d.h,
+                "sfm_hip: flags, cnt, s1, s2 must be [batch, h]");
+    TORCH_CHECK(result.numel() == d.batch * kRecordWords, "sfm_hip: result must be int64 [batch, 5]");
+    TORCH_CHECK(!mask.has_value() || mask->numel() == d.batch * d.n, "sfm_hip: mask must be uint8 [batch, n]");
+    return d;
 }
 
 // the whole five-point pass (sfm_five_point_ransac_pass): fit (from S, or Philox-sampled with use_philox), six-item scoring,
@@ -215,22 +231,8 @@ void five_point_ransac_pass_out(const Tensor& corr, int64_t seed, int64_t seed_s
                                 double min_extra, int64_t aggregation, Tensor& S, Tensor& E, Tensor& flags, Tensor& cnt, Tensor& s1,
                                 Tensor& s2, Tensor& result, const std::optional<Tensor>& mask) {
     const OpDevice scope(corr);
-    need(corr, "corr", at::kDouble);
-    need(S, "S", at::kInt);
-    need(E, "E", at::kDouble);
-    need(flags, "flags", at::kInt);
-    need(cnt, "cnt", at::kInt);
-    need(s1, "s1", at::kDouble);
-    need(s2, "s2", at::kDouble);
-    need(result, "result", at::kLong);
-    if (mask.has_value()) need(*mask, "mask", at::kByte);
-    const Dims d = hypothesis_dims(corr, S);
+    const Dims d = pass_checks(corr, "corr", hypothesis_dims, S, E, "E", flags, cnt, s1, s2, result, mask);
     check_E(E, d);
-    TORCH_CHECK(flags.numel() == d.batch * d.h && cnt.numel() == d.batch * d.h && s1.numel() == d.batch * d.h &&
-                    s2.numel() == d.batch * d.h,
-                "sfm_hip: flags, cnt, s1, s2 must be [batch, h]");
-    TORCH_CHECK(result.numel() == d.batch * 5, "sfm_hip: result must be [batch, 5] int64");
-    if (mask.has_value()) TORCH_CHECK(mask->numel() == d.batch * d.n, "sfm_hip: mask must be [batch, n]");
     ok(sfm_five_point_ransac_pass((uint64_t)seed, (uint64_t)seed_stride, use_philox ? 1 : 0, h_begin, ptr<double>(corr), d.n, d.h,
                                   d.batch, thr, min_extra, (int)aggregation, ptr<int32_t>(S), ptr<double>(E), ptr<int32_t>(flags),
                                   ptr<int32_t>(cnt), ptr<double>(s1), ptr<double>(s2),
@@ -468,27 +470,12 @@ void check_model(const Tensor& model, const Dims& d) {
                 "sfm_hip: model must be [batch, h, 12]");
 }
 
-void fit_checks(const Tensor& pts, const Tensor& S, at::ArrayRef<double> K, Tensor& model, Tensor& flags);
+// pnp_fit (six-point DLT) and p3p_fit (four-item samples, sfm_p3p.h): one body, the entry point differs
+using PoseFit = int (*)(const double*, int64_t, const int32_t*, int64_t, int64_t, const double*, double*, int32_t*, void*);
 
-// P3P fit (four-item samples, sfm_p3p.h): the same tensors as pnp_fit
-void p3p_fit_out(const Tensor& pts, const Tensor& S, at::ArrayRef<double> K, Tensor& model, Tensor& flags) {
+void pose_fit(PoseFit entry, const char* name, const Tensor& pts, const Tensor& S, at::ArrayRef<double> K, Tensor& model,
+              Tensor& flags) {
     const OpDevice scope(pts);
-    fit_checks(pts, S, K, model, flags);
-    const Dims d = pnp_dims(pts, S);
-    ok(sfm_p3p_fit(ptr<double>(pts), d.n, ptr<int32_t>(S), d.h, d.batch, K.data(), ptr<double>(model), ptr<int32_t>(flags),
-                   current_stream()),
-       "sfm_p3p_fit");
-}
-
-std::tuple<Tensor, Tensor> p3p_fit(const Tensor& pts, const Tensor& S, at::ArrayRef<double> K) {
-    const Dims d = pnp_dims(pts, S);
-    Tensor model = at::empty({d.batch, d.h, 12}, like(pts, at::kDouble));
-    Tensor flags = at::empty({d.batch, d.h}, like(pts, at::kInt));
-    p3p_fit_out(pts, S, K, model, flags);
-    return {model, flags};
-}
-
-void fit_checks(const Tensor& pts, const Tensor& S, at::ArrayRef<double> K, Tensor& model, Tensor& flags) {
     need(pts, "pts", at::kDouble);
     need(S, "S", at::kInt);
     need(model, "model", at::kDouble);
@@ -497,28 +484,24 @@ void fit_checks(const Tensor& pts, const Tensor& S, at::ArrayRef<double> K, Tens
     const Dims d = pnp_dims(pts, S);
     check_model(model, d);
     TORCH_CHECK(flags.numel() == d.batch * d.h, "sfm_hip: flags must be [batch, h]");
+    ok(entry(ptr<double>(pts), d.n, ptr<int32_t>(S), d.h, d.batch, K.data(), ptr<double>(model), ptr<int32_t>(flags), current_stream()),
+       name);
 }
 
 void pnp_fit_out(const Tensor& pts, const Tensor& S, at::ArrayRef<double> K, Tensor& model, Tensor& flags) {
-    const OpDevice scope(pts);
-    need(pts, "pts", at::kDouble);
-    need(S, "S", at::kInt);
-    need(model, "model", at::kDouble);
-    need(flags, "flags", at::kInt);
-    check_K(K);
-    const Dims d = pnp_dims(pts, S);
-    check_model(model, d);
-    TORCH_CHECK(flags.numel() == d.batch * d.h, "sfm_hip: flags must be [batch, h]");
-    ok(sfm_pnp_fit(ptr<double>(pts), d.n, ptr<int32_t>(S), d.h, d.batch, K.data(), ptr<double>(model), ptr<int32_t>(flags),
-                   current_stream()),
-       "sfm_pnp_fit");
+    pose_fit(sfm_pnp_fit, "sfm_pnp_fit", pts, S, K, model, flags);
 }
 
-std::tuple<Tensor, Tensor> pnp_fit(const Tensor& pts, const Tensor& S, at::ArrayRef<double> K) {
+void p3p_fit_out(const Tensor& pts, const Tensor& S, at::ArrayRef<double> K, Tensor& model, Tensor& flags) {
+    pose_fit(sfm_p3p_fit, "sfm_p3p_fit", pts, S, K, model, flags);
+}
+
+template <void (*FitOut)(const Tensor&, const Tensor&, at::ArrayRef<double>, Tensor&, Tensor&)>
+std::tuple<Tensor, Tensor> pose_fit_new(const Tensor& pts, const Tensor& S, at::ArrayRef<double> K) {
     const Dims d = pnp_dims(pts, S);
     Tensor model = at::empty({d.batch, d.h, 12}, like(pts, at::kDouble));
     Tensor flags = at::empty({d.batch, d.h}, like(pts, at::kInt));
-    pnp_fit_out(pts, S, K, model, flags);
+    FitOut(pts, S, K, model, flags);
     return {model, flags};
 }
 
@@ -570,23 +553,9 @@ void pnp_pass(int solver, const Tensor& pts, int64_t seed, int64_t seed_stride, 
               at::ArrayRef<double> K, double thr, double min_extra, int64_t aggregation, Tensor& S, Tensor& model, Tensor& flags,
               Tensor& cnt, Tensor& s1, Tensor& s2, Tensor& result, const std::optional<Tensor>& mask) {
     const OpDevice scope(pts);
-    need(pts, "pts", at::kDouble);
-    need(S, "S", at::kInt);
-    need(model, "model", at::kDouble);
-    need(flags, "flags", at::kInt);
-    need(cnt, "cnt", at::kInt);
-    need(s1, "s1", at::kDouble);
-    need(s2, "s2", at::kDouble);
-    need(result, "result", at::kLong);
-    if (mask.has_value()) need(*mask, "mask", at::kByte);
     check_K(K);
-    const Dims d = pnp_dims(pts, S);
+    const Dims d = pass_checks(pts, "pts", pnp_dims, S, model, "model", flags, cnt, s1, s2, result, mask);
     check_model(model, d);
-    TORCH_CHECK(flags.numel() == d.batch * d.h && cnt.numel() == d.batch * d.h && s1.numel() == d.batch * d.h &&
-                    s2.numel() == d.batch * d.h,
-                "sfm_hip: flags, cnt, s1, s2 must be [batch, h]");
-    TORCH_CHECK(result.numel() == d.batch * kRecordWords, "sfm_hip: result must be int64 [batch, 5]");
-    TORCH_CHECK(!mask.has_value() || mask->numel() == d.batch * d.n, "sfm_hip: mask must be uint8 [batch, n]");
     ok(sfm_pnp_ransac_pass(solver, (uint64_t)seed, (uint64_t)seed_stride, use_philox ? 1 : 0, h_begin, ptr<double>(pts), d.n, d.h,
                            d.batch, K.data(), thr, min_extra, (int)aggregation, ptr<int32_t>(S), ptr<double>(model),
                            ptr<int32_t>(flags), ptr<int32_t>(cnt), ptr<double>(s1), ptr<double>(s2),
@@ -1115,8 +1084,8 @@ TORCH_LIBRARY(sfm_hip, m) {
 TORCH_LIBRARY_IMPL(sfm_hip, CUDA, m) {
     m.impl("normalize_coords", &normalize_coords);
     m.impl("normalize_coords_", &normalize_coords_out);
-    m.impl("fit_eight_point", &fit_eight_point);
-    m.impl("five_point_fit", &five_point_fit);
+    m.impl("fit_eight_point", &essential_fit_new<fit_eight_point_out>);
+    m.impl("five_point_fit", &essential_fit_new<five_point_fit_out>);
     m.impl("five_point_fit_", &five_point_fit_out);
     m.impl("five_point_ransac_pass_", &five_point_ransac_pass_out);
     m.impl("fit_eight_point_", &fit_eight_point_out);
@@ -1131,12 +1100,12 @@ TORCH_LIBRARY_IMPL(sfm_hip, CUDA, m) {
     m.impl("inlier_mask_", &inlier_mask_out);
     m.impl("cheirality", &cheirality);
     m.impl("triangulate", &triangulate);
-    m.impl("pnp_fit", &pnp_fit);
+    m.impl("pnp_fit", &pose_fit_new<pnp_fit_out>);
     m.impl("pnp_fit_", &pnp_fit_out);
     m.impl("pnp_score", &pnp_score);
     m.impl("pnp_score_", &pnp_score_out);
     m.impl("pnp_ransac_pass_", &pnp_ransac_pass_out);
-    m.impl("p3p_fit", &p3p_fit);
+    m.impl("p3p_fit", &pose_fit_new<p3p_fit_out>);
     m.impl("p3p_fit_", &p3p_fit_out);
     m.impl("p3p_ransac_pass_", &p3p_ransac_pass_out);
     m.impl("pnp_refine", &pnp_refine);

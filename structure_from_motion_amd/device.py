@@ -53,6 +53,26 @@ def _as_int64(seed: int) -> int:
     return seed - 2**64 if seed >= 2**63 else seed
 
 
+def _score_buffers(cnt, s1, s2, B: int, H: int, device):
+    """cnt, s1, s2 [B,H]: the caller's buffers, new ones where it gave none."""
+    if cnt is None:
+        cnt = torch.empty((B, H), dtype=torch.int32, device=device)
+    if s1 is None:
+        s1 = torch.empty((B, H), dtype=F64, device=device)
+    if s2 is None:
+        s2 = torch.empty((B, H), dtype=F64, device=device)
+    return cnt, s1, s2
+
+
+def _fit_buffers(model, flags, B: int, H: int, width: int, device):
+    """model [B,H,12] or E [B,H,9], and flags [B,H]: the caller's buffers, new ones where it gave none."""
+    if model is None:
+        model = torch.empty((B, H, width), dtype=F64, device=device)
+    if flags is None:
+        flags = torch.empty((B, H), dtype=torch.int32, device=device)
+    return model, flags
+
+
 def to_device(array, dtype=F64) -> torch.Tensor:
     dev = require_gpu()
     return torch.as_tensor(np.ascontiguousarray(array), dtype=dtype).to(dev)
@@ -109,21 +129,13 @@ def fit_eight_point(corr: torch.Tensor, S: torch.Tensor, E=None, flags=None, lam
     B, N, _ = corr.shape
     H = S.shape[1]
     assert S.shape == (B, H, 8) and S.dtype == torch.int32
+    if lambda2 is None and E is None and flags is None:
+        return ops.load().fit_eight_point(corr, S)
+    E, flags = _fit_buffers(E, flags, B, H, 9, corr.device)
     if lambda2 is None:
-        op = ops.load()
-        if E is None and flags is None:
-            return op.fit_eight_point(corr, S)
-        if E is None:
-            E = torch.empty((B, H, 9), dtype=F64, device=corr.device)
-        if flags is None:
-            flags = torch.empty((B, H), dtype=torch.int32, device=corr.device)
-        op.fit_eight_point_(corr, S, E, flags)
+        ops.load().fit_eight_point_(corr, S, E, flags)
         return E, flags
     lib = _native.load()  # with the second-smallest eigenvalue written out: a diagnostic outside the op set
-    if E is None:
-        E = torch.empty((B, H, 9), dtype=F64, device=corr.device)
-    if flags is None:
-        flags = torch.empty((B, H), dtype=torch.int32, device=corr.device)
     check(lib.sfm_fit_eight_point(_ptr(corr), N, _ptr(S), H, B, _ptr(E), _ptr(flags), _ptr(lambda2),
                                   _stream()), "sfm_fit_eight_point")
     return E, flags
@@ -214,12 +226,7 @@ def score_sed(corr: torch.Tensor, E: torch.Tensor, S: torch.Tensor, thr: float, 
     if sample_size != 8:
         if workspace is not None or options is not None:
             raise ValueError("score_sed(sample_size != 8) runs the all-fp64 kernel: it takes no workspace and no launch options")
-        if cnt is None:
-            cnt = torch.empty((B, H), dtype=torch.int32, device=corr.device)
-        if s1 is None:
-            s1 = torch.empty((B, H), dtype=F64, device=corr.device)
-        if s2 is None:
-            s2 = torch.empty((B, H), dtype=F64, device=corr.device)
+        cnt, s1, s2 = _score_buffers(cnt, s1, s2, B, H, corr.device)
         assert S.dtype == torch.int32 and corr.dtype == F64 and E.dtype == F64
         with torch.cuda.device(corr.device):
             check(_native.load().sfm_score_sed_sample_ex(_ptr(corr), N, _ptr(E), _ptr(S), H, B, float(thr), int(sample_size),
@@ -227,12 +234,7 @@ def score_sed(corr: torch.Tensor, E: torch.Tensor, S: torch.Tensor, thr: float, 
         return cnt, s1, s2
     exact = exact_only or os.environ.get("SFM_SCORE_KERNEL", "filtered") == "exact"
     if options is not None:   # per-call launch options (and timing events): straight through the C ABI
-        if cnt is None:
-            cnt = torch.empty((B, H), dtype=torch.int32, device=corr.device)
-        if s1 is None:
-            s1 = torch.empty((B, H), dtype=F64, device=corr.device)
-        if s2 is None:
-            s2 = torch.empty((B, H), dtype=F64, device=corr.device)
+        cnt, s1, s2 = _score_buffers(cnt, s1, s2, B, H, corr.device)
         if exact:
             workspace = None   # NULL selects the all-fp64 kernel
         elif workspace is None:
@@ -245,12 +247,7 @@ def score_sed(corr: torch.Tensor, E: torch.Tensor, S: torch.Tensor, thr: float, 
         return cnt, s1, s2
     if cnt is None and s1 is None and s2 is None and (exact or workspace is None):
         return op.score_sed(corr, E, S, float(thr), exact)
-    if cnt is None:
-        cnt = torch.empty((B, H), dtype=torch.int32, device=corr.device)
-    if s1 is None:
-        s1 = torch.empty((B, H), dtype=F64, device=corr.device)
-    if s2 is None:
-        s2 = torch.empty((B, H), dtype=F64, device=corr.device)
+    cnt, s1, s2 = _score_buffers(cnt, s1, s2, B, H, corr.device)
     if exact:
         workspace = None
     elif workspace is None:
@@ -298,23 +295,35 @@ def _pass_with_options(entry: str, corr, seed, seed_dev, use_philox, h_begin, th
                                              _ptr(workspace), workspace.numel(), _stream(), C.byref(options)), entry)
 
 
+def _philox_args(philox):
+    """``philox`` of a pass, decoded -> (seed as 64 unsigned bits, seed_dev, use_philox, h_begin, seed_stride).  ``None``: the table
+    already in S.  Else ``(seed, h_begin[, seed_stride])`` with ``seed`` an int or an int64 device tensor read at kernel run time."""
+    if philox is None:
+        return 0, None, False, 0, 0
+    seed, h_begin, *stride = philox
+    on_device = isinstance(seed, torch.Tensor)
+    return 0 if on_device else seed & (2**64 - 1), seed if on_device else None, True, h_begin, stride[0] if stride else 1
+
+
+def _single_pair_pass(op, entry: str, corr, S, E, flags, cnt, s1, s2, result, mask, workspace, thr, min_extra, aggregation,
+                      h_offset, philox, options) -> None:
+    """``sfm_ransac_pass_small`` / ``_large``: the torch op ``op``, or with per-call ``options`` the C-ABI ``entry``."""
+    seed, seed_dev, use_philox, h_begin, _ = _philox_args(philox)
+    if options is not None:
+        return _pass_with_options(entry, corr, seed, seed_dev, use_philox, h_begin, thr, min_extra, aggregation,
+                                  h_offset, S, E, flags, cnt, s1, s2, result, mask, workspace, options)
+    op(corr, _as_int64(seed), seed_dev, use_philox, h_begin, float(thr), float(min_extra), int(aggregation), h_offset, S, E, flags,
+       cnt, s1, s2, result, mask, workspace)
+
+
 def ransac_pass_small(corr, S, E, flags, cnt, s1, s2, result, mask, workspace, thr: float, min_extra: float,
                       aggregation: int, h_offset: int = 0, philox=None, options: Optional[ScoreOptions] = None) -> None:
     """One whole pass of a small problem with lean launches (fit + workspace preparation, scoring, sharded selection, mask).
     ``philox=(seed, h_begin)``: samples drawn in the kernel (``seed`` an int or an int64 device tensor), else the
     table already in ``S``.  Same outputs as the separate calls.  ``options``: launch options of this call (default: the
     process-wide set)."""
-    if philox is None:
-        seed, seed_dev, use_philox, h_begin = 0, None, False, 0
-    else:
-        seed, h_begin = philox
-        on_device = isinstance(seed, torch.Tensor)
-        seed, seed_dev, use_philox = (0, seed, True) if on_device else (_as_int64(seed), None, True)
-    if options is not None:
-        return _pass_with_options("sfm_ransac_pass_small", corr, seed, seed_dev, use_philox, h_begin, thr, min_extra, aggregation,
-                                  h_offset, S, E, flags, cnt, s1, s2, result, mask, workspace, options)
-    ops.load().ransac_pass_small_(corr, seed, seed_dev, use_philox, h_begin, float(thr), float(min_extra),
-                                  int(aggregation), h_offset, S, E, flags, cnt, s1, s2, result, mask, workspace)
+    _single_pair_pass(ops.load().ransac_pass_small_, "sfm_ransac_pass_small", corr, S, E, flags, cnt, s1, s2, result, mask, workspace,
+                      thr, min_extra, aggregation, h_offset, philox, options)
 
 
 def ransac_pass_large(corr, S, E, flags, cnt, s1, s2, result, mask, workspace, thr: float, min_extra: float,
@@ -324,17 +333,8 @@ def ransac_pass_large(corr, S, E, flags, cnt, s1, s2, result, mask, workspace, t
     whose extra blocks write the point operand table; cost pre-pass, class histogram, scan + scatter (these three only in cost
     order); the scoring kernel; fold of the point ranges + selection + mask.  With the VALU filter: the fit, ``score_sed``'s
     launches, the selection.  Arguments and outputs as ``ransac_pass_small``."""
-    if philox is None:
-        seed, seed_dev, use_philox, h_begin = 0, None, False, 0
-    else:
-        seed, h_begin = philox
-        on_device = isinstance(seed, torch.Tensor)
-        seed, seed_dev, use_philox = (0, seed, True) if on_device else (_as_int64(seed), None, True)
-    if options is not None:
-        return _pass_with_options("sfm_ransac_pass_large", corr, seed, seed_dev, use_philox, h_begin, thr, min_extra, aggregation,
-                                  h_offset, S, E, flags, cnt, s1, s2, result, mask, workspace, options)
-    ops.load().ransac_pass_large_(corr, seed, seed_dev, use_philox, h_begin, float(thr), float(min_extra),
-                                  int(aggregation), h_offset, S, E, flags, cnt, s1, s2, result, mask, workspace)
+    _single_pair_pass(ops.load().ransac_pass_large_, "sfm_ransac_pass_large", corr, S, E, flags, cnt, s1, s2, result, mask, workspace,
+                      thr, min_extra, aggregation, h_offset, philox, options)
 
 
 def ransac_pass_batch(corr, S, E, flags, cnt, s1, s2, result, mask, workspace, thr: float, min_extra: float, aggregation: int,
@@ -344,12 +344,7 @@ def ransac_pass_batch(corr, S, E, flags, cnt, s1, s2, result, mask, workspace, t
     kernel (``seed`` an int or an int64 device tensor), else the tables already in ``S``.  Same outputs as the separate calls."""
     B, N, _ = corr.shape
     H = S.shape[1]
-    if philox is None:
-        seed, seed_dev, use_philox, h_begin, seed_stride = 0, None, False, 0, 0
-    else:
-        seed, h_begin, seed_stride = philox
-        on_device = isinstance(seed, torch.Tensor)
-        seed, seed_dev, use_philox = (0, seed, True) if on_device else (seed & (2**64 - 1), None, True)
+    seed, seed_dev, use_philox, h_begin, seed_stride = _philox_args(philox)
     with torch.cuda.device(corr.device):
         check(_native.load().sfm_ransac_pass_batch(seed, _ptr(seed_dev), seed_stride, 1 if use_philox else 0, h_begin, _ptr(corr), N, H, B,
                                                    float(thr), float(min_extra), int(aggregation), _ptr(S), _ptr(E), _ptr(flags),
@@ -423,10 +418,7 @@ def five_point_fit(corr: torch.Tensor, S: torch.Tensor, E=None, flags=None, phil
     op = ops.load()
     if philox is None and E is None and flags is None:
         return op.five_point_fit(corr, S)
-    if E is None:
-        E = torch.empty((B, H, 9), dtype=F64, device=corr.device)
-    if flags is None:
-        flags = torch.empty((B, H), dtype=torch.int32, device=corr.device)
+    E, flags = _fit_buffers(E, flags, B, H, 9, corr.device)
     if philox is None:
         op.five_point_fit_(corr, S, E, flags)
         return E, flags
@@ -589,23 +581,45 @@ def checked_mask(mask: np.ndarray) -> np.ndarray:
     return mask
 
 
-class RansacWorkspace:
-    """Pre-allocated device buffers for B pairs x H hypotheses x N correspondences."""
+class _PassWorkspace:
+    """What the RANSAC workspaces share: the device buffers of a pass over B entries x H hypotheses x N items whose models are
+    ``width`` doubles, and the decoding of the select record it leaves."""
 
-    def __init__(self, batch: int, n: int, h: int, device=None):
+    def __init__(self, batch: int, n: int, h: int, width: int, sample_size: int, device=None):
         dev = device or require_gpu()
         self.batch, self.n, self.h = batch, n, h
         self.S = torch.empty((batch, h, 8), dtype=torch.int32, device=dev)
-        self.E = torch.empty((batch, h, 9), dtype=F64, device=dev)
+        self.model = torch.empty((batch, h, width), dtype=F64, device=dev)
         self.flags = torch.empty((batch, h), dtype=torch.int32, device=dev)
         self.cnt = torch.empty((batch, h), dtype=torch.int32, device=dev)
         self.s1 = torch.empty((batch, h), dtype=F64, device=dev)
         self.s2 = torch.empty((batch, h), dtype=F64, device=dev)
         self.result = torch.empty((batch, SELECT_BYTES // 8), dtype=torch.int64, device=dev)
         self.mask = torch.empty((batch, n), dtype=torch.uint8, device=dev)
-        self.score_ws = score_workspace(n, h, batch, dev)   # (for the process-wide options of this moment: see _fit_workspace)
+        self.sample_size = sample_size   # of the last pass (outcome reads it)
+
+    def _winner(self, b: int, h_offset: int = 0):
+        """Entry b's record and winner on the host -> (best_h, error, model row, sample, mask, n_flagged, first_flagged,
+        extra_inliers), the fields of both outcome classes in their order; model row, sample and mask None without a winner."""
+        rec = read_select(self.result)[b]
+        first = -1 if rec.first_flagged == _native.INT64_MAX else int(rec.first_flagged)
+        if rec.best_h < 0:
+            return -1, float("inf"), None, None, None, int(rec.n_flagged), first, 0
+        local = int(rec.best_h) - h_offset
+        model = self.model[b, local].cpu().numpy()
+        sample = self.S[b, local, :self.sample_size].cpu().numpy().astype(np.int64)
+        mask = checked_mask(self.mask[b].cpu().numpy().copy())
+        return int(rec.best_h), float(rec.best_err), model, sample, mask, int(rec.n_flagged), first, int(rec.best_cnt)
+
+
+class RansacWorkspace(_PassWorkspace):
+    """Pre-allocated device buffers for B pairs x H hypotheses x N correspondences."""
+
+    def __init__(self, batch: int, n: int, h: int, device=None):
+        super().__init__(batch, n, h, 9, solver_sample_size("essential", "eight_point"), device)
+        self.E = self.model
+        self.score_ws = score_workspace(n, h, batch, self.S.device)   # (for the process-wide options of this moment: see _fit_workspace)
         self.frozen = False   # set by ShardedRansac.capture: the buffers' addresses are baked into a graph
-        self.sample_size = solver_sample_size("essential", "eight_point")   # of the last pass (outcome reads it)
 
     def _fit_workspace(self, options: Optional[ScoreOptions]) -> None:
         """The scoring workspace is sized by what a call launches: other options (per call, or process-wide defaults changed
@@ -665,16 +679,8 @@ class RansacWorkspace:
             inlier_mask(corr, self.E, self.S, self.result, thr, self.mask)
 
     def outcome(self, b: int = 0, h_offset: int = 0) -> RansacOutcome:
-        rec = read_select(self.result)[b]
-        first = -1 if rec.first_flagged == _native.INT64_MAX else int(rec.first_flagged)
-        if rec.best_h < 0:
-            return RansacOutcome(-1, float("inf"), None, None, None, int(rec.n_flagged), first, 0)
-        local = int(rec.best_h) - h_offset
-        E = self.E[b, local].cpu().numpy().reshape(3, 3).copy()
-        sample = self.S[b, local, :self.sample_size].cpu().numpy().astype(np.int64)
-        mask = checked_mask(self.mask[b].cpu().numpy().copy())
-        return RansacOutcome(int(rec.best_h), float(rec.best_err), E, sample, mask, int(rec.n_flagged),
-                             first, int(rec.best_cnt))
+        best_h, error, E, *rest = self._winner(b, h_offset)
+        return RansacOutcome(best_h, error, None if E is None else E.reshape(3, 3).copy(), *rest)
 
 
 def ransac_essential(corr: torch.Tensor, S, thr: float, min_extra: float, aggregation: int) -> RansacOutcome:
@@ -699,33 +705,26 @@ def _camera_list(K) -> List[float]:
     return [float(v) for v in K.reshape(9)]
 
 
+def _pose_fit(fit, fit_, pts, S, K, model, flags):
+    """``fit`` / ``fit_``: the functional and the in-place op of one pose solver."""
+    if model is None and flags is None:
+        return fit(pts, S, _camera_list(K))
+    model, flags = _fit_buffers(model, flags, S.shape[0], S.shape[1], 12, pts.device)
+    fit_(pts, S, _camera_list(K), model, flags)
+    return model, flags
+
+
 def pnp_fit(pts: torch.Tensor, S: torch.Tensor, K, model=None, flags=None):
     """Six-point DLT fit of every hypothesis -> model [B,H,12], flags [B,H] (SFM_FIT_DEGENERATE)."""
     op = ops.load()
-    if model is None and flags is None:
-        return op.pnp_fit(pts, S, _camera_list(K))
-    B, H = S.shape[0], S.shape[1]
-    if model is None:
-        model = torch.empty((B, H, 12), dtype=F64, device=pts.device)
-    if flags is None:
-        flags = torch.empty((B, H), dtype=torch.int32, device=pts.device)
-    op.pnp_fit_(pts, S, _camera_list(K), model, flags)
-    return model, flags
+    return _pose_fit(op.pnp_fit, op.pnp_fit_, pts, S, K, model, flags)
 
 
 def p3p_fit(pts: torch.Tensor, S: torch.Tensor, K, model=None, flags=None):
     """P3P fit of every hypothesis from the first four entries of each row of S -> model [B,H,12] (12 NaNs: no solution),
     flags [B,H] (SFM_FIT_DEGENERATE: collinear solve points or an index out of range)."""
     op = ops.load()
-    if model is None and flags is None:
-        return op.p3p_fit(pts, S, _camera_list(K))
-    B, H = S.shape[0], S.shape[1]
-    if model is None:
-        model = torch.empty((B, H, 12), dtype=F64, device=pts.device)
-    if flags is None:
-        flags = torch.empty((B, H), dtype=torch.int32, device=pts.device)
-    op.p3p_fit_(pts, S, _camera_list(K), model, flags)
-    return model, flags
+    return _pose_fit(op.p3p_fit, op.p3p_fit_, pts, S, K, model, flags)
 
 
 def pnp_score(pts: torch.Tensor, model: torch.Tensor, S: torch.Tensor, K, thr: float, cnt=None, s1=None, s2=None,
@@ -966,21 +965,11 @@ class PnPOutcome:
     extra_inliers: int
 
 
-class PnPWorkspace:
+class PnPWorkspace(_PassWorkspace):
     """Pre-allocated device buffers of a PnP pass for B views x H hypotheses x N 2D-3D pairs (as RansacWorkspace)."""
 
     def __init__(self, batch: int, n: int, h: int, device=None):
-        dev = device or require_gpu()
-        self.batch, self.n, self.h = batch, n, h
-        self.S = torch.empty((batch, h, 8), dtype=torch.int32, device=dev)
-        self.model = torch.empty((batch, h, 12), dtype=F64, device=dev)
-        self.flags = torch.empty((batch, h), dtype=torch.int32, device=dev)
-        self.cnt = torch.empty((batch, h), dtype=torch.int32, device=dev)
-        self.s1 = torch.empty((batch, h), dtype=F64, device=dev)
-        self.s2 = torch.empty((batch, h), dtype=F64, device=dev)
-        self.result = torch.empty((batch, SELECT_BYTES // 8), dtype=torch.int64, device=dev)
-        self.mask = torch.empty((batch, n), dtype=torch.uint8, device=dev)
-        self.sample_size = solver_sample_size("pose", "dlt")   # of the last pass (outcome and refine read it)
+        super().__init__(batch, n, h, 12, solver_sample_size("pose", "dlt"), device)   # (refine reads sample_size too)
 
     def run(self, pts: torch.Tensor, K, thr: float, min_extra: float, aggregation: int, with_mask: bool = True,
             philox=None, solver: str = "dlt") -> None:
@@ -1014,13 +1003,7 @@ class PnPWorkspace:
         return pnp_refine(pts, model, mask, err, K, thr, aggregation, rounds, max_steps)
 
     def outcome(self, b: int = 0) -> PnPOutcome:
-        rec = read_select(self.result)[b]
-        first = -1 if rec.first_flagged == _native.INT64_MAX else int(rec.first_flagged)
-        if rec.best_h < 0:
-            return PnPOutcome(-1, float("inf"), None, None, None, None, int(rec.n_flagged), first, 0)
-        h = int(rec.best_h)
-        m = self.model[b, h].cpu().numpy()
-        sample = self.S[b, h, :self.sample_size].cpu().numpy().astype(np.int64)
-        mask = checked_mask(self.mask[b].cpu().numpy().copy())
-        return PnPOutcome(h, float(rec.best_err), m[:9].reshape(3, 3).copy(), m[9:].copy(), sample, mask,
-                          int(rec.n_flagged), first, int(rec.best_cnt))
+        best_h, error, m, *rest = self._winner(b)
+        if m is None:
+            return PnPOutcome(best_h, error, None, None, *rest)
+        return PnPOutcome(best_h, error, m[:9].reshape(3, 3).copy(), m[9:].copy(), *rest)
