@@ -275,10 +275,11 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(2, 2))) v
         }
     }
 
-    // E = T2^T F T1 (eight_point.py:163), then divide by E[2][2] (:166, unguarded)
+    // E = T2^T F T1 (eight_point.py:163), then divide by E[2][2] (:166, unguarded but for an E[2][2] of exactly 0: there the
+    // reference's division leaves inf and NaN, and E is left as it is, which scores and decomposes the same at any scale)
     double e[9];
     unnormalise(fr, t1, t2, e);
-    const double e22 = e[8];
+    const double e22 = e[8] == 0.0 ? 1.0 : e[8];
     double en[9];
 #pragma unroll
     for (int k = 0; k < 9; ++k) en[k] = e[k] / e22;
@@ -929,6 +930,8 @@ __global__ __launch_bounds__(kWave) void triangulate_kernel(const Corr* __restri
 // Essential-matrix decomposition (eight_point.py:245-280): E = U S V^T, t = vee(U Z U^T) = u3,
 // R1 = U W^T V^T, R2 = U W V^T with U, V made proper rotations.  One lane per matrix.
 // ------------------------------------------------------------------------------------------------
+constexpr double kSigma3Noise = 1e-12;   // sigma_3 <= kSigma3Noise sigma_1: a rank-2 matrix in double precision
+
 __global__ __launch_bounds__(kWave) void decompose_essential_kernel(const double* __restrict__ E,
                                                                     int64_t batch,
                                                                     double* __restrict__ pose_rt,
@@ -938,7 +941,7 @@ __global__ __launch_bounds__(kWave) void decompose_essential_kernel(const double
     const int64_t b = active ? b_raw : batch - 1;
     const double* e = E + b * 9;
     // E can have any magnitude (the reference's SVD does not care): scaled exactly into the unit range for the Jacobi
-    // sweeps, singular values scaled back for the sigma_3 ~ 0 test, which is absolute (pow2_unit_scale)
+    // sweeps, singular values scaled back for the absolute part of the sigma_3 ~ 0 test (pow2_unit_scale)
     const double scale = sfmfit::pow2_unit_scale(e);
     double g[3][3], v[3][3];
 #pragma unroll
@@ -1000,9 +1003,11 @@ __global__ __launch_bounds__(kWave) void decompose_essential_kernel(const double
         vt[2][1] = -vt[2][1];
         vt[2][2] = -vt[2][2];
     }
-    // np.isclose(0, s[-1]) with atol 1e-8 (eight_point.py:268)
+    // np.isclose(0, s[-1]) with atol 1e-8 (eight_point.py:268), or sigma_3 at the rounding level of sigma_1: the fit's
+    // E / E[2][2] of a motion with E[2][2] = 0 has a magnitude of 1e12 .. 1e19, and the absolute test alone refuses the
+    // rounding noise of such a matrix
     const double s2_true = s2v / scale;   // exact: scale is a power of two
-    const int st = (s2_true <= 1e-8 + 1e-5 * s2_true) ? 0 : 1;
+    const int st = (s2_true <= 1e-8 + 1e-5 * s2_true || s2v <= kSigma3Noise * s0) ? 0 : 1;
     // R1 = U W^T V^T, R2 = U W V^T with W = [[0,-1,0],[1,0,0],[0,0,1]]:
     //   U W^T = [-u2, u1, u3] columns -> R1 = -u2 v1^T + u1 v2^T + u3 v3^T
     //   U W   = [ u2,-u1, u3]         -> R2 =  u2 v1^T - u1 v2^T + u3 v3^T

@@ -140,7 +140,7 @@ __global__ __launch_bounds__(kThreads) void refine_kernel(
             double fr[3][3], e[9];
             sfmfit::enforce_rank2(f, fr);
             sfmfit::unnormalise(fr, t1, t2, e);
-            const double e22 = e[8];
+            const double e22 = e[8] == 0.0 ? 1.0 : e[8];   // an E[2][2] of exactly 0: E stays undivided, as in the fit kernel
             if (tid == 0) {
 #pragma unroll
                 for (int k = 0; k < 9; ++k) e_new[k] = e[k] / e22;

@@ -72,7 +72,9 @@ def estimate_essential_mat_with_ransac(
     solver: str = "eight_point",
 ) -> Tuple[npt.NDArray, list[FeaturePair]]:
     """Estimate E from matched pixel features with RANSAC over eight-point hypotheses scored by SED in
-    K-normalised coordinates.  Returns ``(E with E[2,2] == 1, inlier (Feature, Feature) pairs)``.
+    K-normalised coordinates.  Returns ``(E with E[2,2] == 1, inlier (Feature, Feature) pairs)``; a fit whose E[2,2] comes
+    out as exactly 0 (possible on exact data of a motion with t_x R_12 = t_y R_02, such as a pure translation) is left
+    undivided instead of becoming inf and NaN.
 
     ``solver="five_point"`` fits six-item samples with the five-point solver instead: items 0-4 are solved
     for and item 5 picks the solution.  Its E does NOT have E[2,2] == 1: it is scaled to ||E||_F = sqrt(2) with its

@@ -3,18 +3,27 @@ operation order, fp64), vectorised over a batch of samples.
 
 Five K-normalised correspondences (a_i, b_i), a = (xa, ya, 1), b = (xb, yb, 1); every E with b_i^T E a_i = 0 on the five,
 det E = 0 and 2 E E^T E - tr(E E^T) E = 0 (Nister, PAMI 2004):
-  1. null basis X, Y, Z, W of the 5 x 9 epipolar system by Householder QR of its 9 x 5 transpose (the last four columns of
-     Q); SFM_FIT_DEGENERATE when min |r_kk| <= 1e-9 max |r_kk| (numerical rank < 5) or an input is not finite;
+  1. null basis of the 5 x 9 epipolar system by Householder QR of its 9 x 5 transpose (the last four columns of Q);
+     SFM_FIT_DEGENERATE when min |r_kk| <= 1e-9 max |r_kk| (numerical rank < 5) or an input is not finite.  X, Y, Z, W are
+     the four columns mixed by the fixed orthogonal ``MIX``: the last column of Q alone is orthogonal to the true E of
+     every motion with E[2][2] = 0 (pure translations, forward motion, rolls about the optical axis), whose solution would
+     then lie at infinity in (x, y, z);
   2. E = x X + y Y + z Z + W turns the ten constraints into ten cubics in x, y, z: a 10 x 20 coefficient matrix in the
      monomial order of ``CUBIC``, whose left 10 x 10 block is Gauss-Jordan eliminated with partial pivoting;
   3. rows e - z f, g - z h, i - z j of the reduced system give a 3 x 3 matrix B(z) with B(z) (x, y, 1)^T = 0; its
-     determinant is a degree-10 polynomial n(z), and (x, y, 1) is proportional to the cross product (p1, p2, p3) of its
-     first two rows;
+     determinant is a degree-10 polynomial n(z);
   4. the real roots of n by a Sturm sequence: the k-th smallest is isolated by bisection on the sign-change count (at most
      ``ISOLATE_STEPS`` steps), then polished by Newton's method kept inside its bracket (at most ``POLISH_STEPS``);
-  5. each root z gives x = p1(z) / p3(z), y = p2(z) / p3(z) and E, scaled to ||E||_F = sqrt(2) with its largest-magnitude
-     entry (the first in row-major order on ties) positive.
-Candidates come in ascending root order.  The fit scores each one on item 5 with the SED as it is made and keeps the best
+  5. each root z: (x, y, 1) is proportional to the cross product of two rows of B(z), the pair (of (0, 1), (0, 2), (1, 2),
+     the first on ties) whose product has the largest third component; (x, y, z) is then polished by ``REFINE_STEPS``
+     Newton steps on the three equations B(z) (x, y, 1)^T = 0, whose coefficients come straight from the elimination: the
+     roots of n carry the cancellation of its expansion (1e-6 in E at small parallax, forward motion), the polished ones
+     the conditioning of the elimination alone.  ``CONSTRAINT_STEPS`` Gauss-Newton steps on the ten constraints themselves,
+     evaluated on E = x X + y Y + z Z + W (their 10 x 3 Jacobian by the normal equations), then take the elimination out of
+     the result as well.  E is scaled to ||E||_F = sqrt(2) with its largest-magnitude entry (the first in row-major order on
+     ties) positive.
+Candidates come in the ascending order of the roots of n; the polish of step 5 can move z past a neighbouring root, and two
+nearly double roots can be polished onto the same solution, which then comes twice.  The fit scores each one on item 5 with the SED as it is made and keeps the best
 (strict <, from +inf); a sample without a real solution gives 9 NaNs and flag 0.
 """
 from __future__ import annotations
@@ -27,7 +36,16 @@ from .eight_point import EightPointCalculationError
 RANK_FLOOR = 1e-9
 ISOLATE_STEPS = 80
 POLISH_STEPS = 100
+REFINE_STEPS = 2
+CONSTRAINT_STEPS = 2
 MAX_CANDIDATES = 10
+
+# X, Y, Z, W = MIX @ (the last four columns of Q): orthogonal (the rows of the left-multiplication matrix of the quaternion
+# (2, 4, 5, 6), of norm 9), no entry zero, so that W has a component along every column
+MIX = [[2.0 / 9.0, -4.0 / 9.0, -5.0 / 9.0, -6.0 / 9.0],
+       [4.0 / 9.0, 2.0 / 9.0, -6.0 / 9.0, 5.0 / 9.0],
+       [5.0 / 9.0, 6.0 / 9.0, 2.0 / 9.0, -4.0 / 9.0],
+       [6.0 / 9.0, -5.0 / 9.0, 4.0 / 9.0, 2.0 / 9.0]]
 
 # monomials as exponents of (x, y, z); LIN: the linear entries of E, QUAD: products of two, CUBIC: Nister's order, whose
 # first ten columns are eliminated and whose last ten are xz^2, xz, x, yz^2, yz, y, z^3, z^2, z, 1
@@ -103,7 +121,7 @@ def null_basis(a: np.ndarray, b: np.ndarray):
     rmin = np.minimum.reduce(r)
     finite = np.all(np.isfinite(a), axis=(1, 2)) & np.all(np.isfinite(b), axis=(1, 2))
     degenerate = ~(rmin > RANK_FLOOR * rmax) | ~finite
-    basis = np.zeros((xa.shape[0], 4, 9))
+    q = np.zeros((xa.shape[0], 4, 9))
     for m in range(4):
         y = [np.zeros_like(rmax) for _ in range(9)]
         y[5 + m] = np.ones_like(rmax)
@@ -114,7 +132,10 @@ def null_basis(a: np.ndarray, b: np.ndarray):
             s = s * betas[k]
             for t in range(9 - k):
                 y[k + t] = y[k + t] - s * vs[k][t]
-        basis[:, m] = np.stack(y, axis=1)
+        q[:, m] = np.stack(y, axis=1)
+    basis = np.zeros_like(q)
+    for m in range(4):
+        basis[:, m] = ((MIX[m][0] * q[:, 0] + MIX[m][1] * q[:, 1]) + MIX[m][2] * q[:, 2]) + MIX[m][3] * q[:, 3]
     return basis, degenerate
 
 
@@ -183,8 +204,23 @@ def _horner(c, x):
     return v
 
 
+def _horner_d(c, x):
+    """The derivative of the polynomial c at x."""
+    k = len(c) - 1
+    v = float(k) * c[k]
+    for i in range(k - 1, 0, -1):
+        v = v * x + float(i) * c[i]
+    return v
+
+
+def _det3(m):
+    return ((m[0][0] * (m[1][1] * m[2][2] - m[1][2] * m[2][1]) - m[0][1] * (m[1][0] * m[2][2] - m[1][2] * m[2][0]))
+            + m[0][2] * (m[1][0] * m[2][1] - m[1][1] * m[2][0]))
+
+
 def hidden_polynomials(B: np.ndarray):
-    """(M, 10, 10) right block -> (p1, p2, p3, n) as lists of ascending coefficients (arrays over M).  Step 3."""
+    """(M, 10, 10) right block -> (rows, n): the three rows of B(z) as (x, y, 1) coefficient polynomials and det B(z), all as
+    lists of ascending coefficients (arrays over M).  Step 3."""
     def rows(e, f):
         be, bf = B[:, e], B[:, f]
         px = [be[:, 2], be[:, 1] - bf[:, 2], be[:, 0] - bf[:, 1], -bf[:, 0]]
@@ -200,7 +236,7 @@ def hidden_polynomials(B: np.ndarray):
     p3 = [u - v for u, v in zip(_conv(kx, ly), _conv(ky, lx))]
     t1, t2, t3 = _conv(p1, mx), _conv(p2, my), _conv(p3, m1)
     n = [(t1[i] + t2[i]) + t3[i] for i in range(11)]
-    return p1, p2, p3, n
+    return ((kx, ky, k1), (lx, ly, l1), (mx, my, m1)), n
 
 
 def _max_abs(c):
@@ -273,10 +309,88 @@ def sed_value(e, xa, ya, xb, yb):
     return (1.0 / da + 1.0 / db) * (r * r)
 
 
-def _candidate(basis, p1, p2, p3, z):
-    P1, P2, P3 = _horner(p1, z), _horner(p2, z), _horner(p3, z)
-    x = P1 / P3
-    y = P2 / P3
+def _constraints(e):
+    """det E and 2 E E^T E - tr(E E^T) E (row-major) of e (9 arrays) -> (F (10), G = E E^T, tr G, the cofactors of E)."""
+    G = [[(e[3 * r] * e[3 * c] + e[3 * r + 1] * e[3 * c + 1]) + e[3 * r + 2] * e[3 * c + 2] for c in range(3)] for r in range(3)]
+    tr = (G[0][0] + G[1][1]) + G[2][2]
+    cof = [e[4] * e[8] - e[5] * e[7], e[5] * e[6] - e[3] * e[8], e[3] * e[7] - e[4] * e[6],
+           e[7] * e[2] - e[8] * e[1], e[8] * e[0] - e[6] * e[2], e[6] * e[1] - e[7] * e[0],
+           e[1] * e[5] - e[2] * e[4], e[2] * e[3] - e[0] * e[5], e[0] * e[4] - e[1] * e[3]]
+    F = [(e[0] * cof[0] + e[1] * cof[1]) + e[2] * cof[2]]
+    for r in range(3):
+        for c in range(3):
+            F.append(2.0 * ((G[r][0] * e[c] + G[r][1] * e[3 + c]) + G[r][2] * e[6 + c]) - tr * e[3 * r + c])
+    return F, G, tr, cof
+
+
+def _constraints_along(e, d, G, tr, cof):
+    """The derivative of ``_constraints`` at e in the direction d (9 arrays)."""
+    H = [[(d[3 * r] * e[3 * c] + d[3 * r + 1] * e[3 * c + 1]) + d[3 * r + 2] * e[3 * c + 2] for c in range(3)] for r in range(3)]
+    dtr = 2.0 * ((H[0][0] + H[1][1]) + H[2][2])
+    dF = cof[0] * d[0]
+    for i in range(1, 9):
+        dF = dF + cof[i] * d[i]
+    out = [dF]
+    for r in range(3):
+        for c in range(3):
+            a = ((H[r][0] + H[0][r]) * e[c] + (H[r][1] + H[1][r]) * e[3 + c]) + (H[r][2] + H[2][r]) * e[6 + c]
+            b = (G[r][0] * d[c] + G[r][1] * d[3 + c]) + G[r][2] * d[6 + c]
+            out.append((2.0 * (a + b) - dtr * e[3 * r + c]) - tr * d[3 * r + c])
+    return out
+
+
+def _candidate(basis, rows, z):
+    B = [[_horner(p, z) for p in row] for row in rows]
+    x = y = w = None
+    for r, q in ((0, 1), (0, 2), (1, 2)):
+        (a1, b1, c1), (a2, b2, c2) = B[r], B[q]
+        u0, u1, u2 = b1 * c2 - c1 * b2, c1 * a2 - a1 * c2, a1 * b2 - b1 * a2
+        if w is None:
+            x, y, w = u0, u1, u2
+        else:
+            take = np.abs(u2) > np.abs(w)
+            x, y, w = np.where(take, u0, x), np.where(take, u1, y), np.where(take, u2, w)
+    x = x / w
+    y = y / w
+    for _ in range(REFINE_STEPS):   # Newton on F_r = a_r(z) x + b_r(z) y + c_r(z), r = 0, 1, 2 (Cramer's rule)
+        F, J = [], []
+        for row in rows:
+            a, b, c = (_horner(p, z) for p in row)
+            da, db, dc = (_horner_d(p, z) for p in row)
+            F.append((a * x + b * y) + c)
+            J.append([a, b, (da * x + db * y) + dc])
+        D = _det3(J)
+        dx = _det3([[F[r], J[r][1], J[r][2]] for r in range(3)]) / D
+        dy = _det3([[J[r][0], F[r], J[r][2]] for r in range(3)]) / D
+        dz = _det3([[J[r][0], J[r][1], F[r]] for r in range(3)]) / D
+        ok = np.isfinite(dx) & np.isfinite(dy) & np.isfinite(dz)   # a singular Jacobian: keep the point
+        x = np.where(ok, x - dx, x)
+        y = np.where(ok, y - dy, y)
+        z = np.where(ok, z - dz, z)
+    for _ in range(CONSTRAINT_STEPS):   # Gauss-Newton on the constraints of E = x X + y Y + z Z + W
+        e = [((x * basis[:, 0, i] + y * basis[:, 1, i]) + z * basis[:, 2, i]) + basis[:, 3, i] for i in range(9)]
+        F, G, tr, cof = _constraints(e)
+        J = [_constraints_along(e, [basis[:, m, i] for i in range(9)], G, tr, cof) for m in range(3)]
+        A = [[None] * 3 for _ in range(3)]
+        g = [None] * 3
+        for a in range(3):
+            for b in range(a, 3):
+                acc = J[a][0] * J[b][0]
+                for k in range(1, 10):
+                    acc = acc + J[a][k] * J[b][k]
+                A[a][b] = A[b][a] = acc
+            acc = J[a][0] * F[0]
+            for k in range(1, 10):
+                acc = acc + J[a][k] * F[k]
+            g[a] = acc
+        D = _det3(A)
+        dx = _det3([[g[r], A[r][1], A[r][2]] for r in range(3)]) / D
+        dy = _det3([[A[r][0], g[r], A[r][2]] for r in range(3)]) / D
+        dz = _det3([[A[r][0], A[r][1], g[r]] for r in range(3)]) / D
+        ok = np.isfinite(dx) & np.isfinite(dy) & np.isfinite(dz)
+        x = np.where(ok, x - dx, x)
+        y = np.where(ok, y - dy, y)
+        z = np.where(ok, z - dz, z)
     e = [((x * basis[:, 0, i] + y * basis[:, 1, i]) + z * basis[:, 2, i]) + basis[:, 3, i] for i in range(9)]
     ss = np.zeros_like(z)
     for i in range(9):
@@ -294,7 +408,7 @@ def _candidate(basis, p1, p2, p3, z):
 
 def solve(a: np.ndarray, b: np.ndarray, item5=None):
     """a, b: (M, 5, 2) K-normalised coordinates of the solved items; item5: (M, 4) = (xa, ya, xb, yb) of the choosing item
-    or None.  Returns (candidates (M, 10, 9) NaN-padded in ascending root order, count (M,), degenerate (M,), E (M, 9):
+    or None.  Returns (candidates (M, 10, 9) NaN-padded in the order of the roots of n, count (M,), degenerate (M,), E (M, 9):
     the candidate with the strictly smallest SED on item 5 (NaN when none; only with item5))."""
     a = np.asarray(a, dtype=np.float64)
     b = np.asarray(b, dtype=np.float64)
@@ -302,7 +416,7 @@ def solve(a: np.ndarray, b: np.ndarray, item5=None):
     with np.errstate(all="ignore"):
         basis, degenerate = null_basis(a, b)
         B = gauss_jordan(coefficient_matrix(basis))
-        p1, p2, p3, n = hidden_polynomials(B)
+        rows, n = hidden_polynomials(B)
         n, dn, chain, ok = sturm_chain(n)
         ok &= ~degenerate
         bound = root_bound(n)
@@ -353,7 +467,7 @@ def solve(a: np.ndarray, b: np.ndarray, item5=None):
                 zn = np.where(((zn > ba) & (zn < bb)) | conv, zn, 0.5 * (ba + bb))
                 z = np.where(run & ~hit, zn, z)
                 run &= ~hit & ~conv
-            e = _candidate(basis, p1, p2, p3, z)
+            e = _candidate(basis, rows, z)
             ev = np.stack(e, axis=1)
             cands[active, slot] = ev[active]
             count += active

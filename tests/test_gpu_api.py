@@ -445,20 +445,30 @@ def test_enforce_rank2_on_hard_matrices():
 
 
 def test_decompose_essential_at_any_magnitude():
-    """_recover_all_r_t (eight_point.py:245-280) is scale-free below the absolute sigma_3 ~ 0 test (:268-271): an E
-    scaled down by 1e-60 ... 1e-140 gives the same rotations and translation direction; scaled up by 1e60 its third
-    singular value (1e-16 of the first) exceeds the reference's atol of 1e-8 and the reference raises — so do we."""
+    """_recover_all_r_t (eight_point.py:245-280) is scale-free: an E scaled down by 1e-60 ... 1e-250 or up by 1e16 ... 1e250
+    gives the same rotations and translation direction.  The reference's sigma_3 ~ 0 test (:268-271) is absolute (atol
+    1e-8) and raises on the rounding noise of a large E (1e-16 of sigma_1), which is the size of every fitted E / E[2][2]
+    of a motion with E[2][2] = 0; the device also accepts sigma_3 <= 1e-12 sigma_1.  A matrix of full
+    rank still raises at every magnitude, and one whose sigma_3 is 1e-10 of sigma_1 passes at unit size, as in the
+    reference, and raises once it is large."""
     R = orc.euler_xy(-5.0, -10.0)
     t = np.array([0.5, 0.05, 0.1])
     t /= np.linalg.norm(t)
     tx = np.array([[0, -t[2], t[1]], [t[2], 0, -t[0]], [-t[1], t[0], 0]])
     E = tx @ R
-    for scale in (1.0, 1e-60, 1e-100, 1e-140, 1e-250):
+    for scale in (1.0, 1e-60, 1e-100, 1e-140, 1e-250, 1e16, 1e60, 1e250):
         r1, r2, tt = eight_point._recover_all_r_t(E * scale)
         assert min(np.abs(r1 - R).max(), np.abs(r2 - R).max()) <= 1e-12, scale
         assert min(np.abs(tt - t).max(), np.abs(tt + t).max()) <= 1e-12, scale
-    with pytest.raises(eight_point.EightPointCalculationError):
-        eight_point._recover_all_r_t(E * 1e60)
+    u, s, vh = np.linalg.svd(E)
+    for sigma3, scale, raises in ((1e-6, 1.0, True), (1e-6, 1e60, True), (1.0, 1e16, True), (1e-10, 1.0, False),
+                                  (1e-10, 1e16, True), (1e-10, 1e60, True)):
+        M = (u * np.array([s[0], s[1], sigma3 * s[0]])) @ vh * scale
+        if raises:
+            with pytest.raises(eight_point.EightPointCalculationError):
+                eight_point._recover_all_r_t(M)
+        else:
+            eight_point._recover_all_r_t(M)
 
 
 def test_traced_fit_intermediates_bit_exact(golden):
