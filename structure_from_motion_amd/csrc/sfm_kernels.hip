@@ -471,14 +471,9 @@ __global__ __launch_bounds__(256) void select_pass2_kernel(
 __global__ void select_final_kernel(const int32_t* __restrict__ cnt, int64_t h_count, int64_t h_offset,
                                     sfm_select_result* __restrict__ result) {
     const int64_t b = blockIdx.x;
-    sfm_select_result r = result[b];
-    const bool found = r.key != kNoModelKey && r.best_h != INT64_MAX;
-    r.best_cnt = found ? cnt[b * h_count + r.best_h] : 0;
-    r.best_err = found ? __longlong_as_double((long long)r.key) : INFINITY;
-    r.best_h = found ? r.best_h + h_offset : -1;
-    if (!found) r.key = kNoModelKey;
-    if (r.first_flagged != INT64_MAX) r.first_flagged += h_offset;
-    result[b] = r;
+    const sfm_select_result r = result[b];
+    const sfmsel::Candidate c{r.key, r.best_h, r.first_flagged, r.n_flagged, 0};
+    result[b] = sfmsel::finish_record(c, h_offset, c.found() ? cnt[b * h_count + c.best] : 0);
 }
 
 // The whole selection in ONE launch for moderate hypothesis counts: a 1024-thread block per batch entry takes the
@@ -512,54 +507,41 @@ __global__ __launch_bounds__(kSelectBlock) void select_block_mask_kernel(
     if (mask != nullptr) sfmsel::write_inlier_mask<4>(corr, n, E, S, h_count, best, thr, mask, threadIdx.x, kSelectBlock);
 }
 
-// Selection of a small pass (h_count <= 32768) spread over up to 32 blocks of ONE launch: a single block walking
-// every hypothesis is latency-bound (14 us at 10 000, 35 us at 30 000 hypotheses).  Each block folds its slice and
-// publishes a partial record write-through (sc1); an agent-scope arrival counter (cdna_hip_programming.md Guideline 16,
-// counter form; 32 arrivals, so a single counter does not serialise anything) tells the block that finishes last to
-// take one acquire and fold the partial records into the result record.  Counter and records live in the kPointsPad
-// bytes behind the fp32 points of the scoring workspace (only ever READ by the scoring loop's over-prefetch); the fit
-// launch of the same pass zeroes the counter (sfm_score_ws.h).
-struct PartialSelect {
-    uint64_t key;
-    int64_t best, first_flagged;
-    int32_t n_flagged, pad;
-};
-static_assert(sfmws::kFusedPartialOffset + sfmws::kFusedShards * (int)sizeof(PartialSelect) <= sfmws::kPointsPad,
-              "selection state fits the pad");
+// Selection and mask of a fused single-pair pass in ONE launch.  A single block walking every hypothesis is latency-bound
+// (14 us at 10 000, 35 us at 30 000 hypotheses), so the hypotheses are spread over `select_blocks` blocks: block b takes
+// hypotheses 256 * (b + select_blocks * k) + t, folds them (block_combine) and hands its candidate over (sfmsel::Handoff); the
+// block that arrives last folds the blocks' candidates into the result record.  With a mask requested the same launch carries
+// ceil(n / 256) further blocks behind the selecting ones: each loads its 256 points, waits for the "record published" flag the
+// last selecting block raises, and writes its slice of the winner's inlier mask — the mask costs no launch of its own.
+//   FOLD = false, the small pass (h_count <= 32768): up to 32 blocks, all four hypotheses of a thread in flight together.  State
+//     in the kPointsPad bytes behind the fp32 points of the scoring workspace (only ever READ by the scoring loop's
+//     over-prefetch); the fit launch of the same pass zeroes the counter's line (sfm_score_ws.h).
+//   FOLD = true, the large pass (any number of hypotheses): up to 256 blocks walk them grid-stride, with the fold of a range-split
+//     scoring launch in front: a thread first adds the partials of its hypothesis' ranges in range order and the sample
+//     correction (what matrix_fold_kernel does as a launch of its own: sfmws::range_totals, eight ranges in flight), writes
+//     cnt / s1 / s2, and selects from those totals.  State in the unused head of the range-split region of the scoring
+//     workspace, zeroed by the pass's first scoring launch.
+// The two instantiations differ in the fold, in the hypotheses a thread has in flight and in the sleep interval of the waiting
+// blocks — nothing else.
+constexpr int kLargeSelectBlocks = 256;
+static_assert(sfmsel::Handoff::state_bytes(sfmws::kFusedShards) <= sfmws::kPointsPad, "selection state fits the pad");
 
-// With a mask requested the same launch carries ceil(n / 256) further blocks behind the selecting ones: each loads its
-// 256 points, waits (one lane, relaxed agent-scope polls with s_sleep, bounded) for the "record published" flag the last
-// selecting block raises, and writes its slice of the winner's inlier mask — the mask costs no launch of its own.  All
-// blocks of the launch (at most 64) are resident together on any MI355X, so the wait cannot deadlock; should the flag
-// not arrive within the bound the slice is filled with 0xFF, a value no mask holds, rather than hanging the GPU.
-constexpr unsigned kSelectDoneWord = 8;   // unsigned index into `state`: counter at [0], flag at [8] (same 64-byte line)
-constexpr int kMaxFlagPolls = 1 << 22;
-
-__global__ __launch_bounds__(256) void select_sharded_kernel(
-    const int32_t* __restrict__ cnt, const double* __restrict__ s1, const double* __restrict__ s2,
-    const int32_t* __restrict__ flags, int64_t h_count, int64_t h_offset, double min_extra, int aggregation,
-    unsigned char* __restrict__ state, sfm_select_result* __restrict__ result, int select_blocks,
-    const Corr* __restrict__ corr, int64_t n, const double* __restrict__ E, const int32_t* __restrict__ S, double thr,
-    uint8_t* __restrict__ mask) {
+template <bool FOLD>
+__global__ __launch_bounds__(256) void select_grid_kernel(
+    int32_t* __restrict__ cnt, double* __restrict__ s1, double* __restrict__ s2, const int32_t* __restrict__ flags,
+    int64_t h_count, int64_t h_offset, double min_extra, int aggregation, unsigned char* __restrict__ state,
+    sfm_select_result* __restrict__ result, int select_blocks, sfmws::RangePartials ranges, const Corr* __restrict__ corr,
+    int64_t n, const double* __restrict__ E, const int32_t* __restrict__ S, double thr, uint8_t* __restrict__ mask) {
     __shared__ sfmsel::SelectScratch<256> scratch;
     __shared__ int last_block;
-    unsigned* counter = reinterpret_cast<unsigned*>(state);
-    unsigned* done = counter + kSelectDoneWord;
-    PartialSelect* partial = reinterpret_cast<PartialSelect*>(state + sfmws::kFusedPartialOffset);
+    const sfmsel::Handoff handoff(state);
     if ((int)blockIdx.x >= select_blocks) {
         // ---- mask block: points [256 * m, 256 * m + 256) ----
         const int64_t i = (int64_t)(blockIdx.x - select_blocks) * 256 + threadIdx.x;
         const Corr p = corr[i < n ? i : n - 1];   // in flight while waiting
-        if (threadIdx.x == 0) {
-            int polls = 0;
-            // acquire loads at agent scope pair with the release store of the flag below: once the flag reads 1 the
-            // record written before it is visible to this block
-            while (__hip_atomic_load(done, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) == 0u && polls < kMaxFlagPolls) {
-                __builtin_amdgcn_s_sleep(8);
-                ++polls;
-            }
-            last_block = polls < kMaxFlagPolls ? 1 : 0;   // reused as "record is there"
-        }
+        // (sleep intervals as the two passes had them before they shared this kernel: a small pass's record is ~10 us away, a
+        // large pass's 20-30 us with ~200 blocks polling)
+        if (threadIdx.x == 0) last_block = handoff.template await<FOLD ? 16 : 8>() ? 1 : 0;   // reused as "record is there"
         __syncthreads();
         if (i >= n) return;
         if (!last_block) {
@@ -574,239 +556,49 @@ __global__ __launch_bounds__(256) void select_sharded_kernel(
             return;
         }
         double e[9];
-        bool in_sample = false;
 #pragma unroll
         for (int k = 0; k < 9; ++k) e[k] = E[h * 9 + k];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) in_sample |= (S[h * 8 + k] == (int32_t)i);
-        const double sed = sfm::sed_value(e, p.xa, p.ya, p.xb, p.yb);
-        mask[i] = in_sample ? 2 : ((sed <= thr) ? 1 : 0);
+        mask[i] = sfmsel::mask_value<8>(e, S + h * 8, p, i, thr);
         return;
     }
-    uint64_t key = kNoModelKey;
-    int64_t best = INT64_MAX, first_flag = INT64_MAX;
-    int n_flag = 0;
-    // this block's slice: hypotheses blockIdx.x * 256 + t, + select_blocks * 256, ... — all loads of a thread in flight together
-    const int64_t stride = (int64_t)select_blocks * 256;
-    uint64_t k[4];
-    bool flagged[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        const int64_t h = (int64_t)blockIdx.x * 256 + threadIdx.x + u * stride;
-        flagged[u] = false;
-        k[u] = h < h_count ? hypothesis_key(cnt, s1, s2, flags, h, min_extra, aggregation, flagged[u]) : kNoModelKey;
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        const int64_t h = (int64_t)blockIdx.x * 256 + threadIdx.x + u * stride;
-        if (k[u] < key) {  // increasing h: strict < keeps the earliest
-            key = k[u];
-            best = h;
-        }
-        if (flagged[u]) {
-            first_flag = h < first_flag ? h : first_flag;
-            ++n_flag;
-        }
-    }
-    sfmsel::block_combine<256>(key, best, first_flag, n_flag, scratch);
-    if (threadIdx.x == 0) {
-        PartialSelect* out = partial + blockIdx.x;
-        __hip_atomic_store(&out->key, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&out->best, best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&out->first_flagged, first_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&out->n_flagged, (int32_t)n_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        // arrival: release (this block's partial record is visible before the count) + acquire (the block that
-        // arrives last sees every other block's record)
-        const unsigned arrived = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        last_block = arrived == (unsigned)select_blocks - 1 ? 1 : 0;
-    }
-    __syncthreads();
-    if (!last_block) return;
-    key = kNoModelKey;
-    best = INT64_MAX;
-    first_flag = INT64_MAX;
-    n_flag = 0;
-    if ((int)threadIdx.x < select_blocks) {
-        const PartialSelect p = partial[threadIdx.x];
-        key = p.key;
-        best = p.best;
-        first_flag = p.first_flagged;
-        n_flag = p.n_flagged;
-    }
-    sfmsel::block_combine<256>(key, best, first_flag, n_flag, scratch);
-    if (threadIdx.x == 0) {
-        const bool found = key != kNoModelKey && best != INT64_MAX;
-        // the record is read by the waiting mask blocks of this launch: write-through stores, drained, then the flag
-        __hip_atomic_store(&result->key, found ? key : kNoModelKey, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&result->best_h, found ? best + h_offset : (int64_t)-1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&result->best_err, found ? __longlong_as_double((long long)key) : (double)INFINITY,
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&result->first_flagged, first_flag != INT64_MAX ? first_flag + h_offset : INT64_MAX,
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&result->n_flagged, (int32_t)n_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&result->best_cnt, found ? cnt[best] : 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(done, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);   // publishes the record above
-    }
-}
-
-// Selection launch of a fused LARGE pass (sfm_ransac_pass_large): select_sharded_kernel for any number of hypotheses — up to 256
-// selecting blocks walk them grid-stride — with the fold of a range-split scoring launch in front: a thread first adds the
-// partials of its hypotheses' ranges in range order and the sample correction (what matrix_fold_kernel does as a launch of its
-// own), writes cnt / s1 / s2, and selects from those totals.  State (arrival counter, flag, partial records) in the unused head of
-// the range-split region of the scoring workspace, zeroed by the pass's first scoring launch.
-constexpr int kLargeSelectBlocks = 256;
-__global__ __launch_bounds__(256) void select_large_kernel(
-    int32_t* __restrict__ cnt, double* __restrict__ s1, double* __restrict__ s2, const int32_t* __restrict__ flags,
-    int64_t h_count, int64_t h_offset, double min_extra, int aggregation, unsigned char* __restrict__ state,
-    sfm_select_result* __restrict__ result, int select_blocks, int units, const unsigned char* __restrict__ split,
-    const unsigned char* __restrict__ fix, const Corr* __restrict__ corr, int64_t n, const double* __restrict__ E,
-    const int32_t* __restrict__ S, double thr, uint8_t* __restrict__ mask) {
-    __shared__ sfmsel::SelectScratch<256> scratch;
-    __shared__ int last_block;
-    unsigned* counter = reinterpret_cast<unsigned*>(state);
-    unsigned* done = counter + kSelectDoneWord;
-    PartialSelect* partial = reinterpret_cast<PartialSelect*>(state + sfmws::kFusedPartialOffset);
-    if ((int)blockIdx.x >= select_blocks) {
-        // ---- mask block: points [256 * m, 256 * m + 256), as in select_sharded_kernel ----
-        const int64_t i = (int64_t)(blockIdx.x - select_blocks) * 256 + threadIdx.x;
-        const Corr p = corr[i < n ? i : n - 1];   // in flight while waiting
-        if (threadIdx.x == 0) {
-            // relaxed polls (each one a load that bypasses the caches, nothing else) and ONE acquire fence once the flag is up:
-            // with ~200 blocks polling, an acquire per poll invalidates the XCD's L2 under the selecting blocks' loads
-            int polls = 0;
-            while (__hip_atomic_load(done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u && polls < kMaxFlagPolls) {
-                __builtin_amdgcn_s_sleep(16);
-                ++polls;
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            last_block = polls < kMaxFlagPolls ? 1 : 0;   // reused as "record is there"
-        }
-        __syncthreads();
-        if (i >= n) return;
-        if (!last_block) {
-            mask[i] = 0xFF;
-            return;
-        }
-        const int64_t global_h = __hip_atomic_load(&result->best_h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int64_t h = global_h - h_offset;
-        if (global_h < 0 || h < 0 || h >= h_count) {
-            mask[i] = 0;
-            return;
-        }
-        double e[9];
-        bool in_sample = false;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) e[k] = E[h * 9 + k];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) in_sample |= (S[h * 8 + k] == (int32_t)i);
-        const double sed = sfm::sed_value(e, p.xa, p.ya, p.xb, p.yb);
-        mask[i] = in_sample ? 2 : ((sed <= thr) ? 1 : 0);
-        return;
-    }
-    uint64_t key = kNoModelKey;
-    int64_t best = INT64_MAX, first_flag = INT64_MAX;
-    int n_flag = 0;
-    const int64_t hp = sfmws::split_padded(h_count);
-    const int32_t* part_c = units > 1 ? reinterpret_cast<const int32_t*>(split) + hp : nullptr;
-    const double* part_a1 = units > 1 ? reinterpret_cast<const double*>(part_c + (int64_t)units * hp) : nullptr;
-    const double* part_a2 = units > 1 ? part_a1 + (int64_t)units * hp : nullptr;
-    const int32_t* fix_c = reinterpret_cast<const int32_t*>(fix);
-    const double* fix_a1 = units > 1 ? reinterpret_cast<const double*>(fix + 4 * hp) : nullptr;
-    for (int64_t h = (int64_t)blockIdx.x * 256 + threadIdx.x; h < h_count; h += (int64_t)select_blocks * 256) {
-        if (units > 1) {   // the ranges in range order, then the sample correction: matrix_fold_kernel's sums, bit for bit
-            // (eight ranges' partials in flight together, then added in range order: one memory latency per eight ranges, not
-            // one per range — the launch spent 16 of its 25 us in eight dependent round trips)
+    const int64_t first = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)select_blocks * 256;
+    sfmsel::Candidate c;
+    if (FOLD)
+        c = sfmsel::scan_candidates<1>(first, stride, h_count, [&](int64_t h, bool& flagged) {
+            if (ranges.units <= 1) return hypothesis_key(cnt, s1, s2, flags, h, min_extra, aggregation, flagged);
             int total = 0;
             double t1 = 0.0, t2 = 0.0;
-            for (int u0 = 0; u0 < units; u0 += 8) {
-                int c8[8];
-                double a8[8], b8[8];
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    const int64_t at = (int64_t)(u0 + k < units ? u0 + k : u0) * hp + h;
-                    c8[k] = part_c[at];
-                    a8[k] = part_a1[at];
-                    b8[k] = part_a2[at];
-                }
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    if (u0 + k == 0) {   // (starts FROM range 0's values, as matrix_fold_kernel does: 0.0 + x is x, but -0.0 would not survive)
-                        total = c8[k];
-                        t1 = a8[k];
-                        t2 = b8[k];
-                    } else if (u0 + k < units) {
-                        total += c8[k];
-                        t1 += a8[k];
-                        t2 += b8[k];
-                    }
-                }
-            }
-            cnt[h] = total + fix_c[h];
-            s1[h] = t1 + fix_a1[h];
-            s2[h] = t2 + fix_a1[hp + h];
-        }
-        bool flagged = false;
-        const uint64_t k = hypothesis_key(cnt, s1, s2, flags, h, min_extra, aggregation, flagged);
-        if (k < key) {  // increasing h: strict < keeps the earliest
-            key = k;
-            best = h;
-        }
-        if (flagged) {
-            first_flag = h < first_flag ? h : first_flag;
-            ++n_flag;
-        }
-    }
-    sfmsel::block_combine<256>(key, best, first_flag, n_flag, scratch);
-    if (threadIdx.x == 0) {
-        PartialSelect* out = partial + blockIdx.x;
-        __hip_atomic_store(&out->key, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&out->best, best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&out->first_flagged, first_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&out->n_flagged, (int32_t)n_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        // arrival: release (this block's totals and partial record are visible before the count); the block that arrives last
-        // takes the acquire — one fence, not one per arrival
-        const unsigned arrived = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-        last_block = arrived == (unsigned)select_blocks - 1 ? 1 : 0;
-        if (last_block) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    }
+            sfmws::range_totals<8>(ranges, h, total, t1, t2);
+            cnt[h] = total;
+            s1[h] = t1;
+            s2[h] = t2;
+            flagged = sfmsel::is_flagged(flags, h);
+            return sfmsel::key_of(total, t1, t2, flagged, min_extra, aggregation);
+        });
+    else
+        c = sfmsel::scan_candidates<4>(first, stride, h_count, [&](int64_t h, bool& flagged) {
+            return hypothesis_key(cnt, s1, s2, flags, h, min_extra, aggregation, flagged);
+        });
+    sfmsel::block_combine<256>(c, scratch);
+    if (threadIdx.x == 0) last_block = handoff.arrive(c, (int)blockIdx.x, select_blocks) ? 1 : 0;
     __syncthreads();
     if (!last_block) return;
-    key = kNoModelKey;
-    best = INT64_MAX;
-    first_flag = INT64_MAX;
-    n_flag = 0;
-    if ((int)threadIdx.x < select_blocks) {
-        const PartialSelect p = partial[threadIdx.x];
-        key = p.key;
-        best = p.best;
-        first_flag = p.first_flagged;
-        n_flag = p.n_flagged;
-    }
-    sfmsel::block_combine<256>(key, best, first_flag, n_flag, scratch);
+    c = handoff.gather(select_blocks);
+    sfmsel::block_combine<256>(c, scratch);
     if (threadIdx.x == 0) {
-        const bool found = key != kNoModelKey && best != INT64_MAX;
-        __hip_atomic_store(&result->key, found ? key : kNoModelKey, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&result->best_h, found ? best + h_offset : (int64_t)-1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&result->best_err, found ? __longlong_as_double((long long)key) : (double)INFINITY,
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&result->first_flagged, first_flag != INT64_MAX ? first_flag + h_offset : INT64_MAX,
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&result->n_flagged, (int32_t)n_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        // (the winner's count was written by another block of this launch: an agent-scope load, behind the acquire above)
-        __hip_atomic_store(&result->best_cnt,
-                           found ? __hip_atomic_load(cnt + best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0,
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(done, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);   // publishes the record above
+        // (the winner's count may have been written by another block of this launch: an agent-scope load, behind arrive's acquire)
+        const int32_t best_cnt = c.found() ? __hip_atomic_load(cnt + c.best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
+        handoff.publish(result, sfmsel::finish_record(c, h_offset, best_cnt));
     }
 }
 
 // Last launch of a fused BATCHED pass (sfm_ransac_pass_batch): one 1024-thread block per image pair folds the ranges of its
-// pair's scoring launch (matrix_fold_kernel's sums, bit for bit: range order, then the sample correction), selects
+// pair's scoring launch (sfmws::range_totals, as matrix_fold_kernel does), selects
 // (ransac.py:75-86) and writes the winner's inlier mask — three launches of the separate calls in one, and no cross-block
 // hand-off: a pair's hypotheses (a few thousand) and points (~10 000) are one block's work.
 __global__ __launch_bounds__(kSelectBlock) void select_fold_mask_batch_kernel(
     int32_t* __restrict__ cnt, double* __restrict__ s1, double* __restrict__ s2, const int32_t* __restrict__ flags, int64_t h_count,
-    double min_extra, int aggregation, sfm_select_result* __restrict__ result, int units, const unsigned char* __restrict__ split,
+    double min_extra, int aggregation, sfm_select_result* __restrict__ result, int units, unsigned char* __restrict__ split,
     const unsigned char* __restrict__ fix, const Corr* __restrict__ corr, int64_t n, const double* __restrict__ E,
     const int32_t* __restrict__ S, double thr, uint8_t* __restrict__ mask) {
     __shared__ sfmsel::SelectScratch<kSelectBlock> scratch;
@@ -816,26 +608,15 @@ __global__ __launch_bounds__(kSelectBlock) void select_fold_mask_batch_kernel(
     s1 += b * h_count;
     s2 += b * h_count;
     if (units > 1) {
-        const int64_t hp = sfmws::split_padded(h_count);
-        const unsigned char* sp = split + b * sfmws::split_bytes(h_count, units);
-        const unsigned char* fx = fix + b * sfmws::matrix_fix_bytes(h_count);
-        const int32_t* part_c = reinterpret_cast<const int32_t*>(sp) + hp;
-        const double* part_a1 = reinterpret_cast<const double*>(part_c + (int64_t)units * hp);
-        const double* part_a2 = part_a1 + (int64_t)units * hp;
-        const int32_t* fix_c = reinterpret_cast<const int32_t*>(fx);
-        const double* fix_a1 = reinterpret_cast<const double*>(fx + 4 * hp);
+        const sfmws::RangePartials ranges = sfmws::range_partials(split, fix, h_count, units, b);
         // (thread t folds hypotheses t, t + 1024, ... — the ones block_select has it read back below)
         for (int64_t h = threadIdx.x; h < h_count; h += kSelectBlock) {
-            int total = part_c[h];
-            double t1 = part_a1[h], t2 = part_a2[h];
-            for (int u = 1; u < units; ++u) {
-                total += part_c[u * hp + h];
-                t1 += part_a1[u * hp + h];
-                t2 += part_a2[u * hp + h];
-            }
-            cnt[h] = total + fix_c[h];
-            s1[h] = t1 + fix_a1[h];
-            s2[h] = t2 + fix_a1[hp + h];
+            int total = 0;
+            double t1 = 0.0, t2 = 0.0;
+            sfmws::range_totals<1>(ranges, h, total, t1, t2);
+            cnt[h] = total;
+            s1[h] = t1;
+            s2[h] = t2;
         }
         __syncthreads();
     }
@@ -1212,11 +993,11 @@ int sfm_ransac_pass_small(uint64_t seed, const uint64_t* seed_dev, int use_philo
     const int select_blocks = (int)((h_count + 1023) / 1024);
     const int mask_blocks = mask != nullptr ? (int)((n + 255) / 256) : 0;
     unsigned char* state = plan.workspace + sfmws::ws_points_offset(1) + 16 * n;
-    hipLaunchKernelGGL(select_sharded_kernel, dim3((unsigned)(select_blocks + mask_blocks)), dim3(256), 0, st,
-                       (const int32_t*)cnt, (const double*)s1, (const double*)s2, (const int32_t*)flags, h_count, h_offset,
-                       min_extra, aggregation, state, result, select_blocks, (const Corr*)corr, n, (const double*)E,
+    hipLaunchKernelGGL(select_grid_kernel<false>, dim3((unsigned)(select_blocks + mask_blocks)), dim3(256), 0, st, cnt, s1, s2,
+                       (const int32_t*)flags, h_count, h_offset, min_extra, aggregation, state, result, select_blocks,
+                       sfmws::range_partials(nullptr, nullptr, h_count, 1, 0), (const Corr*)corr, n, (const double*)E,
                        (const int32_t*)S, thr, mask);
-    return check_launch("select_sharded_kernel");
+    return check_launch("select_grid_kernel (small pass)");
 }
 
 int sfm_ransac_pass_large(uint64_t seed, const uint64_t* seed_dev, int use_philox, int64_t h_begin, const double* corr,
@@ -1239,7 +1020,7 @@ int sfm_ransac_pass_large(uint64_t seed, const uint64_t* seed_dev, int use_philo
     SFM_REQUIRE_GRID("sfm_ransac_pass_large", (int64_t)grid_for(h_count, kWave) + step_blocks, 1, kWave);
     SFM_REQUIRE_GRID("sfm_ransac_pass_large (mask)", n, 256, 256);
     unsigned char* state = plan.workspace + sfmws::ws_tail_offset(n, h_count, 1);   // the unused head of the range-split region
-    const bool state_fits = 4 * sfmws::split_padded(h_count) >= sfmws::kFusedPartialOffset + kLargeSelectBlocks * (int64_t)sizeof(PartialSelect);
+    const bool state_fits = 4 * sfmws::split_padded(h_count) >= sfmsel::Handoff::state_bytes(kLargeSelectBlocks);
     unsigned* select_state = state_fits ? reinterpret_cast<unsigned*>(state) : nullptr;
     hipStream_t st = (hipStream_t)stream;
     const sfmhost::ScoreArrays io{corr, E, S, cnt, s1, s2, st};
@@ -1272,11 +1053,11 @@ int sfm_ransac_pass_large(uint64_t seed, const uint64_t* seed_dev, int use_philo
     // last launch: fold of the ranges + selection over up to 256 blocks + (behind them) the blocks that write the winner's mask
     const int select_blocks = (int)std::min<int64_t>(kLargeSelectBlocks, (h_count + 511) / 512);
     const int mask_blocks = mask != nullptr ? (int)((n + 255) / 256) : 0;
-    hipLaunchKernelGGL(select_large_kernel, dim3((unsigned)(select_blocks + mask_blocks)), dim3(256), 0, st, cnt, s1, s2,
+    hipLaunchKernelGGL(select_grid_kernel<true>, dim3((unsigned)(select_blocks + mask_blocks)), dim3(256), 0, st, cnt, s1, s2,
                        (const int32_t*)flags, h_count, h_offset, min_extra, aggregation, state, result, select_blocks,
-                       plan.deferred_units(), (const unsigned char*)plan.split, (const unsigned char*)plan.fix, (const Corr*)corr, n,
+                       sfmws::range_partials(plan.split, plan.fix, h_count, plan.deferred_units(), 0), (const Corr*)corr, n,
                        (const double*)E, (const int32_t*)S, thr, mask);
-    return check_launch("select_large_kernel");
+    return check_launch("select_grid_kernel (large pass)");
 }
 
 int sfm_ransac_pass_batch(uint64_t seed, const uint64_t* seed_dev, uint64_t seed_stride, int use_philox, int64_t h_begin,
@@ -1317,7 +1098,7 @@ int sfm_ransac_pass_batch(uint64_t seed, const uint64_t* seed_dev, uint64_t seed
     if (rc != SFM_OK) return rc;
     // last launch: fold of the ranges + selection + mask, one block per pair
     hipLaunchKernelGGL(select_fold_mask_batch_kernel, dim3((unsigned)batch), dim3(kSelectBlock), 0, st, cnt, s1, s2, (const int32_t*)flags,
-                       h_count, min_extra, aggregation, result, plan.deferred_units(), (const unsigned char*)plan.split,
+                       h_count, min_extra, aggregation, result, plan.deferred_units(), plan.split,
                        (const unsigned char*)plan.fix, (const Corr*)corr, n, (const double*)E, (const int32_t*)S, thr, mask);
     return check_launch("select_fold_mask_batch_kernel");
 }

@@ -865,13 +865,7 @@ __global__ __launch_bounds__(256, 5) void score_sed_filtered_kernel(
             my_h = (lane == k) ? hyp[k] : my_h;
         }
         if (owner) {
-            const int64_t hp = split_padded(h_count);
-            int32_t* part_c = reinterpret_cast<int32_t*>(split) + hp;
-            double* part_a1 = reinterpret_cast<double*>(part_c + (int64_t)units * hp);
-            double* part_a2 = part_a1 + (int64_t)units * hp;
-            part_c[unit * hp + my_h] = mine_c;
-            part_a1[unit * hp + my_h] = mine_a1;
-            part_a2[unit * hp + my_h] = mine_a2;
+            store_range_partial(range_partials(split, nullptr, h_count, units, 0), unit, my_h, mine_c, mine_a1, mine_a2);
         }
     }
 #if SFM_WAVE_STAMPS

@@ -708,13 +708,11 @@ SFM_DEVICE void matrix_item(const MatrixPair& a, int n, int h_count, double thr,
     const double s1k = WIDE ? a1 : (half == 0 ? a1 + a1_other : a1_other + a1);
     const double s2k = WIDE ? a2 : (half == 0 ? a2 + a2_other : a2_other + a2);
     if ((WIDE || half == 0) && valid) {
-        const int64_t hp = sfmws::split_padded(h_count);
         if (units <= 1) {   // the totals, with the correction for the sample points behind them
-            const int32_t* fix_c = reinterpret_cast<const int32_t*>(a.fix);
-            const double* fix_a1 = reinterpret_cast<const double*>(a.fix + 4 * hp);
-            cnt[h] = ck + fix_c[h];
-            s1[h] = s1k + fix_a1[h];
-            s2[h] = s2k + fix_a1[hp + h];
+            const sfmws::RangePartials fix = sfmws::range_partials(nullptr, a.fix, h_count, 1, 0);
+            cnt[h] = ck + fix.fix_cnt[h];
+            s1[h] = s1k + fix.fix_a1[h];
+            s2[h] = s2k + fix.fix_a2[h];
         } else {
             // Range split: this range's partial goes to [range][hypothesis] with PLAIN stores; matrix_fold_kernel, launched
             // behind this kernel, adds the ranges in range order (a fixed order: identical sums from run to run).  Until round 4
@@ -723,12 +721,7 @@ SFM_DEVICE void matrix_item(const MatrixPair& a, int n, int h_count, double thr,
             // 2.4 M write-through stores per launch, which the memory side of eight non-coherent L2s serves at ~1.5 M / ms — with
             // the step loop stubbed out the launch still took 0.6 ms, two thirds of every wave's life spent in that hand-off
             // (profiles/r04/README.md); a kernel boundary orders the same data for nothing.
-            int32_t* part_c = reinterpret_cast<int32_t*>(a.split) + hp;
-            double* part_a1 = reinterpret_cast<double*>(part_c + (int64_t)units * hp);
-            double* part_a2 = part_a1 + (int64_t)units * hp;
-            part_c[unit * hp + h] = ck;
-            part_a1[unit * hp + h] = s1k;
-            part_a2[unit * hp + h] = s2k;
+            sfmws::store_range_partial(sfmws::range_partials(a.split, nullptr, h_count, units, 0), unit, h, ck, s1k, s2k);
         }
     }
 #if SFM_MATRIX_STAMPS
@@ -755,34 +748,19 @@ SFM_DEVICE void matrix_item(const MatrixPair& a, int n, int h_count, double thr,
 }
 
 // Totals of a range-split launch: partials [range][hypothesis] added in range order, then the sample correction.
-__global__ __launch_bounds__(256) void matrix_fold_kernel(const unsigned char* __restrict__ split, const unsigned char* __restrict__ fix,
+__global__ __launch_bounds__(256) void matrix_fold_kernel(unsigned char* __restrict__ split, const unsigned char* __restrict__ fix,
                                                           int units, int h_count, int32_t* __restrict__ cnt,
                                                           double* __restrict__ s1, double* __restrict__ s2) {
     const int64_t pair = blockIdx.y;
-    const int64_t hp = sfmws::split_padded(h_count);
-    split += pair * sfmws::split_bytes(h_count, units);
-    if (fix != nullptr) fix += pair * sfmws::matrix_fix_bytes(h_count);
+    // (fix == NULL: the VALU-filter kernel corrects for its sample points itself)
+    const sfmws::RangePartials ranges = sfmws::range_partials(split, fix, h_count, units, pair);
     cnt += pair * (int64_t)h_count;
     s1 += pair * (int64_t)h_count;
     s2 += pair * (int64_t)h_count;
-    const int32_t* part_c = reinterpret_cast<const int32_t*>(split) + hp;
-    const double* part_a1 = reinterpret_cast<const double*>(part_c + (int64_t)units * hp);
-    const double* part_a2 = part_a1 + (int64_t)units * hp;
-    const int32_t* fix_c = reinterpret_cast<const int32_t*>(fix);
-    const double* fix_a1 = reinterpret_cast<const double*>(fix + 4 * hp);
     for (int64_t h = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; h < h_count; h += (int64_t)gridDim.x * blockDim.x) {
-        int total = part_c[h];
-        double t1 = part_a1[h], t2 = part_a2[h];
-        for (int u = 1; u < units; ++u) {
-            total += part_c[u * hp + h];
-            t1 += part_a1[u * hp + h];
-            t2 += part_a2[u * hp + h];
-        }
-        if (fix != nullptr) {   // (the VALU-filter kernel corrects for its sample points itself)
-            total += fix_c[h];
-            t1 += fix_a1[h];
-            t2 += fix_a1[hp + h];
-        }
+        int total = 0;
+        double t1 = 0.0, t2 = 0.0;
+        sfmws::range_totals<1>(ranges, h, total, t1, t2);
         cnt[h] = total;
         s1[h] = t1;
         s2[h] = t2;

@@ -27,11 +27,10 @@ constexpr int kPrepPoints = 512;             // 64 lanes x 8 points, all loads o
 constexpr int kSmallMaxPoints = 8192;
 constexpr int kMaxPrepBlocks = kSmallMaxPoints / kPrepPoints;  // 16 partial maxima x 4 words = buckets[0, 64)
 static_assert(4 * kMaxPrepBlocks <= kBuckets, "the partial maxima live in the class-counter words");
-// state of a small pass's sharded selection (select_sharded_kernel, sfm_kernels.hip) in the kPointsPad bytes behind
-// the fp32 points: one 64-byte line with the arrival counter and the "record published" flag, then one 32-byte partial
-// record per selecting block
+// state of a small pass's selection launch (select_grid_kernel, sfm_kernels.hip; laid out by sfmsel::Handoff, sfm_select.h)
+// in the kPointsPad bytes behind the fp32 points: one 64-byte line with the arrival counter and the "record published"
+// flag, then one 32-byte partial record per selecting block
 constexpr int kFusedShards = 32;             // selecting blocks: 32 x 256 threads x 4 hypotheses = 32768
-constexpr int kFusedPartialOffset = 64;      // bytes: partial records behind the counter's line
 
 __host__ __device__ inline int64_t ws_points_offset(int64_t batch) { return 16 * batch; }
 __host__ __device__ inline int64_t ws_buckets_offset(int64_t n, int64_t batch) {
@@ -61,8 +60,79 @@ __host__ __device__ inline int64_t split_bytes(int64_t h_count, int units) {   /
 __host__ __device__ inline int64_t split_region_bytes(int64_t h_count, int64_t batch, int units) {
     return batch == 1 ? split_bytes(h_count, units) : (units > 1 ? batch * split_bytes(h_count, units) : 0);
 }
-// The partials are written with plain stores by the scoring kernels and added in range order by matrixscore::matrix_fold_kernel
-// (or the selection launch of a fused pass).
+// The partials are written with plain stores by the scoring kernels (store_range_partial) and added in range order
+// (range_totals) by matrixscore::matrix_fold_kernel or the selection launch of a fused pass.
+//
+// Where one pair's partials, and the sample corrections the matrix-pipe kernel's totals still need ([h_pad] int32 | [h_pad] f64 |
+// [h_pad] f64; null where the scoring kernel has corrected for its sample points itself), lie.
+__host__ __device__ inline int64_t matrix_fix_bytes(int64_t h_count) { return split_padded(h_count) * (4 + 8 + 8); }
+struct RangePartials {
+    int32_t* cnt;             // [units][h_pad]; null without ranges (units <= 1)
+    double *a1, *a2;
+    const int32_t* fix_cnt;   // [h_pad]; null: no correction
+    const double *fix_a1, *fix_a2;
+    int64_t h_pad;
+    int units;
+};
+__host__ __device__ inline RangePartials range_partials(unsigned char* split, const unsigned char* fix, int64_t h_count, int units,
+                                                        int64_t pair) {
+    RangePartials v{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, split_padded(h_count), units};
+    if (units > 1) {
+        v.cnt = reinterpret_cast<int32_t*>(split + pair * split_bytes(h_count, units)) + v.h_pad;
+        v.a1 = reinterpret_cast<double*>(v.cnt + (int64_t)units * v.h_pad);
+        v.a2 = v.a1 + (int64_t)units * v.h_pad;
+    }
+    if (fix != nullptr) {
+        fix += pair * matrix_fix_bytes(h_count);
+        v.fix_cnt = reinterpret_cast<const int32_t*>(fix);
+        v.fix_a1 = reinterpret_cast<const double*>(fix + 4 * v.h_pad);
+        v.fix_a2 = v.fix_a1 + v.h_pad;
+    }
+    return v;
+}
+// A scoring wave leaves the partial of range `unit` of hypothesis h.
+__device__ __forceinline__ void store_range_partial(const RangePartials& v, int unit, int64_t h, int c, double a1, double a2) {
+    const int64_t at = unit * v.h_pad + h;
+    v.cnt[at] = c;
+    v.a1[at] = a1;
+    v.a2[at] = a2;
+}
+// Totals of hypothesis h: the ranges' partials added in range order, then the sample correction where there is one.  The sums
+// start FROM range 0's values, not from zero: 0.0 + x is x, but -0.0 would not survive.  IN_FLIGHT ranges' loads are issued
+// together before they are added (8: one memory latency per eight ranges, not one per range — the selection launch of a large
+// pass spent 16 of its 25 us in eight dependent round trips; a `units` that is no multiple re-reads the group's first range and
+// drops it); the additions and their order are the same for every IN_FLIGHT.
+template <int IN_FLIGHT>
+__device__ __forceinline__ void range_totals(const RangePartials& v, int64_t h, int& cnt, double& s1, double& s2) {
+    for (int u0 = 0; u0 < v.units; u0 += IN_FLIGHT) {
+        int c[IN_FLIGHT];
+        double a[IN_FLIGHT], b[IN_FLIGHT];
+#pragma unroll
+        for (int k = 0; k < IN_FLIGHT; ++k) {
+            const int64_t at = (int64_t)(u0 + k < v.units ? u0 + k : u0) * v.h_pad + h;
+            c[k] = v.cnt[at];
+            a[k] = v.a1[at];
+            b[k] = v.a2[at];
+        }
+#pragma unroll
+        for (int k = 0; k < IN_FLIGHT; ++k) {
+            if (u0 + k == 0) {
+                cnt = c[k];
+                s1 = a[k];
+                s2 = b[k];
+            } else if (u0 + k < v.units) {
+                cnt += c[k];
+                s1 += a[k];
+                s2 += b[k];
+            }
+        }
+    }
+    if (v.fix_cnt != nullptr) {
+        cnt += v.fix_cnt[h];
+        s1 += v.fix_a1[h];
+        s2 += v.fix_a2[h];
+    }
+}
 // Operand tables of the matrix-pipe kernel (sfm_score_matrix.h; at most kMatrixMaxPoints points per pair), behind the split
 // region: per pair and step of 32 points three blocks of 64 lanes x 16 bytes (96 bytes per point), then per pair and hypothesis
 // 2 halves x 3 blocks x 16 bytes, then per pair the sample corrections of the hypotheses ([h_pad] int32 | [h_pad] f64 | [h_pad] f64).
@@ -70,7 +140,6 @@ constexpr int64_t kMatrixMaxPoints = 1 << 22;   // 4 M points per pair (a 400 MB
 __host__ __device__ inline int64_t matrix_table_steps(int64_t n) { return (((n + 31) / 32) + 3) & ~(int64_t)3; }   // (with pad steps: sfm_score_matrix.h)
 __host__ __device__ inline int64_t matrix_table_bytes(int64_t n) { return matrix_table_steps(n) * 3 * 64 * 16; }   // one pair
 __host__ __device__ inline int64_t matrix_hyp_table_bytes(int64_t h_count) { return h_count * 96; }                // one pair
-__host__ __device__ inline int64_t matrix_fix_bytes(int64_t h_count) { return split_padded(h_count) * (4 + 8 + 8); }
 __host__ __device__ inline int64_t ws_matrix_offset(int64_t n, int64_t h_count, int64_t batch, const WsPlan& plan) {
     return ((ws_tail_offset(n, h_count, batch) + split_region_bytes(h_count, batch, plan.units) + 255) / 256) * 256;
 }

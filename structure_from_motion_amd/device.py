@@ -575,7 +575,7 @@ class RansacOutcome:
 def checked_mask(mask: np.ndarray) -> np.ndarray:
     """Inlier mask as read back from the device (0 out, 1 inlier, 2 sample).  The mask blocks of a small pass's
     selection launch wait for the selecting blocks' record with a bounded number of polls and fill their slice with
-    0xFF if it never arrives (``select_sharded_kernel``): that must surface here, not as an empty inlier list."""
+    0xFF if it never arrives (``select_grid_kernel``): that must surface here, not as an empty inlier list."""
     if mask.size and int(mask.max()) > 2:
         raise RuntimeError("sfm_hip: the inlier mask was not written (the selection record of the pass never arrived)")
     return mask

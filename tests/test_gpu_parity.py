@@ -1143,6 +1143,74 @@ def test_small_pass_mask_with_hypothesis_offset(dev, n, h):
     np.testing.assert_array_equal(np.nonzero(m0)[0], np.sort(ref["inliers"]))
 
 
+@pytest.mark.parametrize("entry,n,h", [("small", 600, 4097), ("large", 2100, 2064)])
+def test_fused_pass_tie_between_selecting_blocks(dev, entry, n, h):
+    """A tie between hypotheses that DIFFERENT selecting blocks of a fused pass own: the winning sample is planted in rows
+    300 and 1500 (and taken out of its own row).  Both passes select with five blocks here — the small one beyond 4096
+    hypotheses, the large one at the smallest count whose selection state fits, with the matrix-pipe kernel forced so that
+    two ranges are folded in the selection launch — and block b owns hypotheses 256 * (b + 5 k) + t: row 300 is block 1's,
+    row 1500 block 0's.  The hand-off must prefer the lower INDEX, not the lower block: 300 wins.  Outputs equal to the
+    separate calls' as in the tests of the two passes above."""
+    from structure_from_motion_amd._native import AGG_RMS
+
+    _, _, _, corr = scene(n, seed=12)
+    corr_d = dev.to_device(corr).reshape(1, n, 4)
+    thr, min_extra = 1.5e-6, 10
+    table = orc.philox_sample_table(9, 100, h, n)
+    w = int(orc.ransac_essential(corr, table, thr, min_extra, orc.RMS)["best"])
+    assert w >= 0 and w not in (300, 1500) and (w + 1) % h not in (300, 1500)
+    planted = table[w].copy()
+    table[w] = table[(w + 1) % h]
+    table[300] = planted
+    table[1500] = planted
+    S = dev.to_device(table, torch.int32).reshape(1, h, 8)
+    saved = dev.default_score_options()
+    try:
+        if entry == "large":
+            dev.set_default_score_options(_options(kernel="matrix"))
+            # this size takes the path the case is about: the selection state fits the head of the range-split region (a counter
+            # line + 256 partial records of 32 bytes in 4 bytes per padded hypothesis), and the workspace carries the partials of
+            # exactly TWO ranges (20 bytes per range and padded hypothesis, regions 256-byte aligned) for the selection to fold
+            hp = (h + 3) // 4 * 4
+            assert 4 * hp >= 64 + 256 * 32
+            ranged = dev.score_workspace_bytes(n, h, 1) - dev.score_workspace_bytes(n, h, 1, _options(kernel="matrix", split=0))
+            assert abs(ranged - 2 * 20 * hp) < 256
+        a, b = dev.RansacWorkspace(1, n, h), dev.RansacWorkspace(1, n, h)   # (sized for the options in force)
+        a.S.copy_(S)
+        b.S.copy_(S)
+        a.mask.fill_(7)
+        fused_pass = dev.ransac_pass_small if entry == "small" else dev.ransac_pass_large
+        fused_pass(corr_d, a.S, a.E, a.flags, a.cnt, a.s1, a.s2, a.result, a.mask, a.score_ws, thr, min_extra, AGG_RMS)
+        dev.fit_eight_point(corr_d, b.S, b.E, b.flags)
+        dev.score_sed(corr_d, b.E, b.S, thr, b.cnt, b.s1, b.s2, workspace=b.score_ws)
+        dev.select_best(b.cnt, b.s1, b.s2, b.flags, min_extra, AGG_RMS, 0, b.result)
+        dev.inlier_mask(corr_d, b.E, b.S, b.result, thr, b.mask)
+        torch.cuda.synchronize()
+    finally:
+        dev.set_default_score_options(saved)
+    fused = {k: getattr(a, k).cpu().numpy() for k in ("S", "E", "flags", "cnt", "s1", "s2", "result", "mask")}
+    plain = {k: getattr(b, k).cpu().numpy() for k in ("S", "E", "flags", "cnt", "s1", "s2", "result", "mask")}
+    if entry == "small":   # as test_fused_small_pass_equals_separate_calls: the sums and the error to summation order
+        for key in ("S", "E", "flags", "cnt", "mask"):
+            np.testing.assert_array_equal(fused[key], plain[key], err_msg=key)
+        np.testing.assert_allclose(fused["s1"], plain["s1"], rtol=1e-13, atol=0, equal_nan=True)
+        np.testing.assert_allclose(fused["s2"], plain["s2"], rtol=1e-13, atol=0, equal_nan=True)
+        rec_f, rec_p = fused["result"][0], plain["result"][0]
+        assert rec_f[1] == rec_p[1] and rec_f[3] == rec_p[3] and rec_f[4] == rec_p[4]
+        assert abs(rec_f[2:3].view(np.float64)[0] / rec_p[2:3].view(np.float64)[0] - 1.0) <= 1e-13
+    else:                  # as the large-pass tests: bit for bit
+        for key in ("S", "E", "flags", "cnt", "result", "mask"):
+            np.testing.assert_array_equal(fused[key], plain[key], err_msg=key)
+        for key in ("s1", "s2"):
+            np.testing.assert_array_equal(fused[key].view(np.int64), plain[key].view(np.int64), err_msg=key)
+    assert fused["cnt"][0, 300] == fused["cnt"][0, 1500]
+    for key in ("s1", "s2"):
+        bits = fused[key].view(np.int64)[0]
+        assert bits[300] == bits[1500], key
+    assert a.outcome(0).best_h == 300
+    np.testing.assert_array_equal(np.nonzero(fused["mask"][0] == 2)[0], np.sort(planted))
+
+
 @pytest.mark.parametrize("n,h", [(300, 2000), (9000, 12000)])
 def test_graph_replay_equals_eager(dev, n, h):
     """A captured HIP graph of the whole pass, replayed with the seed rewritten in device memory, gives the

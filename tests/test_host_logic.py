@@ -469,7 +469,7 @@ def test_numeric_entry_points_fail_loudly_without_gpu(native_lib):
 
 
 def test_unwritten_mask_is_an_error():
-    """The 0xFF fill of a mask slice whose selection record never arrived (select_sharded_kernel's bounded wait)
+    """The 0xFF fill of a mask slice whose selection record never arrived (select_grid_kernel's bounded wait)
     surfaces as an error on the host, not as an empty inlier list."""
     from structure_from_motion_amd import device
 
