@@ -379,6 +379,38 @@ int sfm_five_point_ransac_pass(uint64_t seed, uint64_t seed_stride, int use_phil
                                int32_t* flags, int32_t* cnt, double* s1, double* s2, sfm_select_result* result, uint8_t* mask,
                                void* stream);
 
+/* ---- RANSAC homography (csrc/sfm_homography.hip; an extension, added under ABI 15) ----
+ * corr: dev [batch,n,4] = {xa, ya, xb, yb} in any one unit (the public route passes K-normalised coordinates); S: dev int32
+ * [batch,h_count,8], the first 4 entries of a row are the sample.  H: dev [batch,h_count,9] row-major with x_b ~ H x_a,
+ * ||H||_F = 1 and det H >= 0.  flags: SFM_FIT_DEGENERATE when sigma_8 / sigma_1 of the conditioned 8 x 9 DLT system is below
+ * 1e-9 or not a number (a repeated item, three points collinear in both images, four coincident points) or an index is out
+ * of range; det H is not tested (three points collinear in one image only give a singular H, which cannot win).  n >= 4. */
+
+/* Four-point DLT fit of every hypothesis: each side conditioned per sample (centroid, mean distance sqrt(2)), null vector of
+ * the 8 x 9 system by Householder QR, conditioning undone in closed form, scale and sign as above. */
+int sfm_homography_fit(const double* corr, int64_t n, const int32_t* S, int64_t h_count, int64_t batch, double* H, int32_t* flags,
+                       void* stream);
+
+/* Scoring of all n items under all hypotheses with the symmetric transfer error e = |H xa - xb|^2 + |adj(H) xb - xa|^2 in
+ * inhomogeneous coordinates (operation order fixed in sfm_homography.hip), +inf when either third coordinate is <= 0.
+ * cnt[b,h] = non-sample items with e <= thr; s1 / s2 = sums of e / e^2 over the 4 sample items plus those survivors.  All
+ * fp64, exact divisions: the values are the host scorer's bit for bit.  Selection: sfm_select_best with sample_size 4. */
+int sfm_homography_score(const double* corr, int64_t n, const double* H, const int32_t* S, int64_t h_count, int64_t batch,
+                         double thr, int32_t* cnt, double* s1, double* s2, void* stream);
+
+/* Inlier mask of the selected model: 2 for its 4 sample items, 1 for other items with e <= thr, 0 otherwise (all 0 when the
+ * record holds no model).  `result` as written by sfm_select_best with h_offset 0.  mask: dev uint8 [batch,n]. */
+int sfm_homography_inlier_mask(const double* corr, int64_t n, const double* H, const int32_t* S, int64_t h_count,
+                               int64_t batch, const sfm_select_result* result, double thr, uint8_t* mask, void* stream);
+
+/* One homography pass: fit (from S, or with use_philox from the first 4 of philox_sample8(seed + b * seed_stride, h_begin + h),
+ * all 8 stored in S, -1 at positions >= n), scoring, selection (sfm_select_best) and, when `mask` is not NULL, the winner's
+ * mask — every argument checked before the first launch. */
+int sfm_homography_ransac_pass(uint64_t seed, uint64_t seed_stride, int use_philox, int64_t h_begin, const double* corr,
+                               int64_t n, int64_t h_count, int64_t batch, double thr, double min_extra, int aggregation,
+                               int32_t* S, double* H, int32_t* flags, int32_t* cnt, double* s1, double* s2,
+                               sfm_select_result* result, uint8_t* mask, void* stream);
+
 /* ---- refinement of a PnP winner on its inliers (csrc/sfm_pnp_refine.hip; an extension, off unless asked for) ---- */
 
 typedef struct sfm_pnp_refine_info {

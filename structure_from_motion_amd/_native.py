@@ -171,6 +171,11 @@ SIGNATURES = {
     "sfm_score_sed_sample_ex": [_P, _I64, _P, _P, _I64, _I64, _D, C.c_int, _P, _P, _P, _P],
     "sfm_five_point_ransac_pass": [_U64, _U64, C.c_int, _I64, _P, _I64, _I64, _I64, _D, _D, C.c_int, _P, _P, _P, _P, _P, _P,
                                    _P, _P, _P],
+    "sfm_homography_fit": [_P, _I64, _P, _I64, _I64, _P, _P, _P],
+    "sfm_homography_score": [_P, _I64, _P, _P, _I64, _I64, _D, _P, _P, _P, _P],
+    "sfm_homography_inlier_mask": [_P, _I64, _P, _P, _I64, _I64, _P, _D, _P, _P],
+    "sfm_homography_ransac_pass": [_U64, _U64, C.c_int, _I64, _P, _I64, _I64, _I64, _D, _D, C.c_int, _P, _P, _P, _P, _P, _P,
+                                   _P, _P, _P],
     "sfm_pnp_refine": [_P, _I64, _I64, _P, _P, _P, _P, _D, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P],
     "sfm_bundle_adjust": [_P, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _I64, _P],
     "sfm_bundle_adjust_pcg": [_P, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, _D, _P, _P, _P, _P, _I64, _P],

@@ -8,7 +8,8 @@
 // (device.RansacWorkspace), an in-place `_`-suffixed form with mutable arguments, plus the fused
 // sample_fit_philox_; and the PnP ops (sfm_pnp.hip) pnp_fit, pnp_score and the whole pass pnp_ransac_pass_, their P3P
 // forms p3p_fit and p3p_ransac_pass_ (sfm_p3p.h), the five-point fit five_point_fit and pass five_point_ransac_pass_
-// (sfm_five_point.hip), and the
+// (sfm_five_point.hip), the homography ops homography_fit, homography_score, homography_inlier_mask and the pass
+// homography_ransac_pass_ (sfm_homography.hip), and the
 // refinement of a winner pnp_refine (sfm_pnp_refine.hip), bundle_adjust (sfm_bundle.hip), triangulate_tracks
 // (sfm_tracks.hip) and build_tracks (sfm_track_build.hip).  The reference call sites these serve: apps/sfm.py:110-119 (RANSAC-E), :133-138 (pose),
 // :181-186 (triangulation).
@@ -452,6 +453,76 @@ Tensor triangulate(const Tensor& corr, const Tensor& P1, const Tensor& P2) {
 Tensor triangulate_meta(const Tensor& corr, const Tensor&, const Tensor&) {
     TORCH_CHECK(corr.dim() == 2, "sfm_hip: corr must be [m, 4]");
     return at::empty_symint({corr.sym_size(0), 3}, corr.options());
+}
+
+
+// ---- homography (sfm_homography.hip): corr [batch, n, 4], S [batch, h, 8] (first 4 entries used), H [batch, h, 9] ----------
+void check_H(const Tensor& H, const Dims& d) {
+    TORCH_CHECK(H.dim() == 3 && H.size(0) == d.batch && H.size(1) == d.h && H.size(2) == 9, "sfm_hip: H must be [batch, h, 9]");
+}
+
+void homography_fit_out(const Tensor& corr, const Tensor& S, Tensor& H, Tensor& flags) {
+    essential_fit(sfm_homography_fit, "sfm_homography_fit", corr, S, H, flags);
+}
+
+std::tuple<Tensor, Tensor, Tensor> homography_score(const Tensor& corr, const Tensor& H, const Tensor& S, double thr) {
+    const OpDevice scope(corr);
+    need(corr, "corr", at::kDouble);
+    need(H, "H", at::kDouble);
+    need(S, "S", at::kInt);
+    const Dims d = hypothesis_dims(corr, S);
+    check_H(H, d);
+    Tensor cnt = at::empty({d.batch, d.h}, like(corr, at::kInt));
+    Tensor s1 = at::empty({d.batch, d.h}, like(corr, at::kDouble));
+    Tensor s2 = at::empty({d.batch, d.h}, like(corr, at::kDouble));
+    ok(sfm_homography_score(ptr<double>(corr), d.n, ptr<double>(H), ptr<int32_t>(S), d.h, d.batch, thr, ptr<int32_t>(cnt),
+                            ptr<double>(s1), ptr<double>(s2), current_stream()),
+       "sfm_homography_score");
+    return {cnt, s1, s2};
+}
+
+std::tuple<Tensor, Tensor, Tensor> homography_score_meta(const Tensor& corr, const Tensor& H, const Tensor& S, double) {
+    meta_dims(corr, S);
+    TORCH_CHECK(H.dim() == 3, "sfm_hip: H must be [batch, h, 9]");
+    const c10::SymInt b = corr.sym_size(0), h = S.sym_size(1);
+    return {at::empty_symint({b, h}, like(corr, at::kInt)), at::empty_symint({b, h}, like(corr, at::kDouble)),
+            at::empty_symint({b, h}, like(corr, at::kDouble))};
+}
+
+Tensor homography_inlier_mask(const Tensor& corr, const Tensor& H, const Tensor& S, const Tensor& result, double thr) {
+    const OpDevice scope(corr);
+    need(corr, "corr", at::kDouble);
+    need(H, "H", at::kDouble);
+    need(S, "S", at::kInt);
+    need(result, "result", at::kLong);
+    const Dims d = hypothesis_dims(corr, S);
+    check_H(H, d);
+    TORCH_CHECK(result.numel() == d.batch * kRecordWords, "sfm_hip: result must be int64 [batch, 5]");
+    Tensor mask = at::empty({d.batch, d.n}, like(corr, at::kByte));
+    ok(sfm_homography_inlier_mask(ptr<double>(corr), d.n, ptr<double>(H), ptr<int32_t>(S), d.h, d.batch,
+                                  reinterpret_cast<const sfm_select_result*>(ptr<int64_t>(result)), thr, ptr<uint8_t>(mask),
+                                  current_stream()),
+       "sfm_homography_inlier_mask");
+    return mask;
+}
+
+Tensor homography_inlier_mask_meta(const Tensor& corr, const Tensor&, const Tensor&, const Tensor&, double) {
+    TORCH_CHECK(corr.dim() == 3, "sfm_hip: corr must be [batch, n, 4]");
+    return at::empty_symint({corr.sym_size(0), corr.sym_size(1)}, like(corr, at::kByte));
+}
+
+// the whole homography pass (sfm_homography_ransac_pass): the arguments of five_point_ransac_pass_ with H for E
+void homography_ransac_pass_out(const Tensor& corr, int64_t seed, int64_t seed_stride, bool use_philox, int64_t h_begin, double thr,
+                                double min_extra, int64_t aggregation, Tensor& S, Tensor& H, Tensor& flags, Tensor& cnt, Tensor& s1,
+                                Tensor& s2, Tensor& result, const std::optional<Tensor>& mask) {
+    const OpDevice scope(corr);
+    const Dims d = pass_checks(corr, "corr", hypothesis_dims, S, H, "H", flags, cnt, s1, s2, result, mask);
+    check_H(H, d);
+    ok(sfm_homography_ransac_pass((uint64_t)seed, (uint64_t)seed_stride, use_philox ? 1 : 0, h_begin, ptr<double>(corr), d.n, d.h,
+                                  d.batch, thr, min_extra, (int)aggregation, ptr<int32_t>(S), ptr<double>(H), ptr<int32_t>(flags),
+                                  ptr<int32_t>(cnt), ptr<double>(s1), ptr<double>(s2),
+                                  reinterpret_cast<sfm_select_result*>(ptr<int64_t>(result)), ptr<uint8_t>(mask), current_stream()),
+       "sfm_homography_ransac_pass");
 }
 
 
@@ -1032,6 +1103,12 @@ TORCH_LIBRARY(sfm_hip, m) {
     m.def("five_point_ransac_pass_(Tensor corr, int seed, int seed_stride, bool use_philox, int h_begin, float thr, float min_extra, "
           "int aggregation, Tensor(a!) S, Tensor(b!) E, Tensor(c!) flags, Tensor(d!) cnt, Tensor(e!) s1, Tensor(f!) s2, "
           "Tensor(g!) result, Tensor(h!)? mask) -> ()");
+    m.def("homography_fit(Tensor corr, Tensor S) -> (Tensor, Tensor)");
+    m.def("homography_score(Tensor corr, Tensor H, Tensor S, float thr) -> (Tensor, Tensor, Tensor)");
+    m.def("homography_inlier_mask(Tensor corr, Tensor H, Tensor S, Tensor result, float thr) -> Tensor");
+    m.def("homography_ransac_pass_(Tensor corr, int seed, int seed_stride, bool use_philox, int h_begin, float thr, float min_extra, "
+          "int aggregation, Tensor(a!) S, Tensor(b!) H, Tensor(c!) flags, Tensor(d!) cnt, Tensor(e!) s1, Tensor(f!) s2, "
+          "Tensor(g!) result, Tensor(h!)? mask) -> ()");
     m.def("pnp_fit(Tensor pts, Tensor S, float[] K) -> (Tensor, Tensor)");
     m.def("pnp_fit_(Tensor pts, Tensor S, float[] K, Tensor(a!) model, Tensor(b!) flags) -> ()");
     m.def("p3p_fit(Tensor pts, Tensor S, float[] K) -> (Tensor, Tensor)");
@@ -1100,6 +1177,10 @@ TORCH_LIBRARY_IMPL(sfm_hip, CUDA, m) {
     m.impl("inlier_mask_", &inlier_mask_out);
     m.impl("cheirality", &cheirality);
     m.impl("triangulate", &triangulate);
+    m.impl("homography_fit", &essential_fit_new<homography_fit_out>);
+    m.impl("homography_score", &homography_score);
+    m.impl("homography_inlier_mask", &homography_inlier_mask);
+    m.impl("homography_ransac_pass_", &homography_ransac_pass_out);
     m.impl("pnp_fit", &pose_fit_new<pnp_fit_out>);
     m.impl("pnp_fit_", &pnp_fit_out);
     m.impl("pnp_score", &pnp_score);
@@ -1181,6 +1262,10 @@ TORCH_LIBRARY_IMPL(sfm_hip, Meta, m) {
     m.impl("inlier_mask", &inlier_mask_meta);
     m.impl("cheirality", &cheirality_meta);
     m.impl("triangulate", &triangulate_meta);
+    m.impl("homography_fit", &fit_eight_point_meta);
+    m.impl("homography_score", &homography_score_meta);
+    m.impl("homography_inlier_mask", &homography_inlier_mask_meta);
+    m.impl("homography_ransac_pass_", &five_point_ransac_pass_out_meta);
     m.impl("pnp_fit", &pnp_fit_meta);
     m.impl("pnp_score", &pnp_score_meta);
     m.impl("pnp_fit_", &pnp_fit_out_meta);

@@ -600,7 +600,7 @@ class _PassWorkspace:
 
     def _winner(self, b: int, h_offset: int = 0):
         """Entry b's record and winner on the host -> (best_h, error, model row, sample, mask, n_flagged, first_flagged,
-        extra_inliers), the fields of both outcome classes in their order; model row, sample and mask None without a winner."""
+        extra_inliers), the fields of every outcome class in their order; model row, sample and mask None without a winner."""
         rec = read_select(self.result)[b]
         first = -1 if rec.first_flagged == _native.INT64_MAX else int(rec.first_flagged)
         if rec.best_h < 0:
@@ -1007,3 +1007,55 @@ class PnPWorkspace(_PassWorkspace):
         if m is None:
             return PnPOutcome(best_h, error, None, None, *rest)
         return PnPOutcome(best_h, error, m[:9].reshape(3, 3).copy(), m[9:].copy(), *rest)
+
+
+# ------------------------------------------------------------------------------------------------------
+# RANSAC homography (csrc/sfm_homography.hip): corr [B,N,4] = {xa, ya, xb, yb}, S [B,H,8] (first 4 entries used),
+# H [B,H,9] row-major with x_b ~ H x_a, ||H||_F = 1, det H >= 0
+# ------------------------------------------------------------------------------------------------------
+def homography_fit(corr: torch.Tensor, S: torch.Tensor):
+    """Four-point DLT fit of every hypothesis -> H [B,H,9], flags [B,H] (SFM_FIT_DEGENERATE)."""
+    return ops.load().homography_fit(corr, S)
+
+
+def homography_score(corr: torch.Tensor, H: torch.Tensor, S: torch.Tensor, thr: float):
+    """Per hypothesis (extra-inlier count, sum e, sum e^2) of the symmetric transfer error e; the first four entries of each
+    row of S are the sample.  Selection: ``select_best`` with ``sample_size=4``."""
+    return ops.load().homography_score(corr, H, S, float(thr))
+
+
+def homography_inlier_mask(corr: torch.Tensor, H: torch.Tensor, S: torch.Tensor, result: torch.Tensor, thr: float):
+    """uint8 [B,N]: 2 sample item of the winner (the first four entries of its row of S), 1 other inlier, 0 outlier."""
+    return ops.load().homography_inlier_mask(corr, H, S, result, float(thr))
+
+
+@dataclass
+class HomographyOutcome:
+    best_h: int                # winning hypothesis, -1 if none
+    error: float               # aggregated inlier error of the winner
+    H: Optional[np.ndarray]    # (3,3) of the winner
+    sample: Optional[np.ndarray]   # (4,) indices of the winner's sample, in sample order
+    mask: Optional[np.ndarray]     # (N,) uint8: 1 survivor, 2 sample point, 0 outlier
+    n_flagged: int             # hypotheses whose sample was degenerate
+    first_flagged: int         # lowest such hypothesis index, or -1
+    extra_inliers: int
+
+
+class HomographyWorkspace(_PassWorkspace):
+    """Pre-allocated device buffers of a homography pass for B pairs x H hypotheses x N correspondences."""
+
+    def __init__(self, batch: int, n: int, h: int, device=None):
+        super().__init__(batch, n, h, 9, solver_sample_size("homography", "homography"), device)
+        self.H = self.model
+
+    def run(self, corr: torch.Tensor, thr: float, min_extra: float, aggregation: int, with_mask: bool = True, philox=None) -> None:
+        """fit + score + select (+ mask) in one call (``sfm_homography_ransac_pass``) for the sample table in ``self.S`` — or,
+        with ``philox=(seed, h_begin, seed_stride)``, for Philox samples drawn inside the fit launch (which also fills ``self.S``)."""
+        seed, h_begin, stride = (0, 0, 1) if philox is None else philox
+        ops.load().homography_ransac_pass_(corr, _as_int64(seed), _as_int64(stride), philox is not None, h_begin, float(thr),
+                                           float(min_extra), int(aggregation), self.S, self.H, self.flags, self.cnt, self.s1,
+                                           self.s2, self.result, self.mask if with_mask else None)
+
+    def outcome(self, b: int = 0) -> HomographyOutcome:
+        best_h, error, m, *rest = self._winner(b)
+        return HomographyOutcome(best_h, error, None if m is None else m.reshape(3, 3).copy(), *rest)

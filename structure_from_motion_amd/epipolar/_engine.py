@@ -250,3 +250,77 @@ def ransac_feature_pairs(data, camera_matrix, threshold, min_extra, aggregation,
             keep = np.nonzero(mask_ref.cpu().numpy()[0])[0]
             return E_ref.cpu().numpy().reshape(3, 3), copy_pairs(data, keep)
     return outcome.E, copy_pairs(data, inlier_order(table, outcome, sample_size))
+
+
+def ransac_homography_pairs(data, camera_matrix, threshold, min_extra, aggregation, iterations):
+    """Device route of fit_with_ransac for (Feature, Feature) pairs and the four-point homography solver.
+    Returns (H (3, 3) or None, inlier pairs), with the samplers, inlier order and copies of ``ransac_feature_pairs``; a
+    degenerate sample raises ``HomographyCalculationError`` under the default policy."""
+    from .homography import HomographyCalculationError
+
+    sample_size = solver_sample_size("homography", "homography")
+    n = len(data)
+    if n < sample_size:
+        raise ValueError("Four feature pairs are expected.")
+    if iterations <= 0:
+        return None, []
+    dev = device.require_gpu()
+    pix = device.to_device(pair_arrays(data))   # one upload: [2, n, 2]
+    corr = device.normalize_correspondences(pix[0], pix[1], camera_matrix)
+    ws = device.HomographyWorkspace(1, n, iterations, dev)
+    sampler, table, philox = draw_samples(ws.S, n, iterations)
+    ws.run(corr.reshape(1, n, 4), threshold, min_extra, aggregation, philox=philox)
+    outcome = ws.outcome(0)
+    if outcome.n_flagged and degenerate_policy() == "raise":
+        raise HomographyCalculationError(
+            "A sampled four-tuple does not determine a homography (a repeated pair or three collinear points)."
+            f" (hypothesis {outcome.first_flagged}, {outcome.n_flagged} in total)")
+    if logger.isEnabledFor(logging.DEBUG):
+        logger.debug("RANSAC-H: %d matches x %d hypotheses (%s sampler): best hypothesis %d, %d extra inliers, "
+                     "aggregated error %.6g, %d degenerate sample(s)", n, iterations, sampler, outcome.best_h,
+                     outcome.extra_inliers, outcome.error, outcome.n_flagged)
+    if outcome.best_h < 0:
+        return None, []
+    return outcome.H, copy_pairs(data, inlier_order(table, outcome, sample_size))
+
+
+def two_view_passes(data, camera_matrix, threshold, min_extra, aggregation, iterations, essential_solver):
+    """The homography pass and the essential pass of ``homography.select_two_view_model`` over one upload of the pairs and
+    one sample table: the homography pass reads the first four entries of each row, the essential pass the first six or
+    eight of the same rows.  Flagged hypotheses never compete and never raise.  Returns (H or None, its inlier pairs, its
+    count, E or None, its inlier pairs, its count), a count being the winner's sample size plus its extra inliers.  Fewer
+    pairs than the essential solver's sample leave E without a winner."""
+    h_size = solver_sample_size("homography", "homography")
+    e_size = solver_sample_size("essential", essential_solver)
+    n = len(data)
+    if n < h_size:
+        raise ValueError("Four feature pairs are expected.")
+    if iterations <= 0:
+        return None, [], 0, None, [], 0
+    dev = device.require_gpu()
+    pix = device.to_device(pair_arrays(data))   # one upload: [2, n, 2]
+    corr = device.normalize_correspondences(pix[0], pix[1], camera_matrix).reshape(1, n, 4)
+    hws = device.HomographyWorkspace(1, n, iterations, dev)
+    sampler, table, philox = draw_samples(hws.S, n, iterations)
+    hws.run(corr, threshold, min_extra, aggregation, philox=philox)   # Philox: drawn in the fit launch, which fills S
+    results = []
+    passes = [(hws, h_size, "H")]
+    if n >= e_size:
+        ews = device.RansacWorkspace(1, n, iterations, dev)
+        ews.S.copy_(hws.S)   # the same rows: a Philox row holds all eight entries of its sample
+        ews.run(corr, threshold, min_extra, aggregation, solver=essential_solver)
+        passes.append((ews, e_size, "E"))
+    for ws, size, name in passes:
+        outcome = ws.outcome(0)
+        if logger.isEnabledFor(logging.DEBUG):
+            logger.debug("RANSAC-%s: %d matches x %d hypotheses (%s sampler): best hypothesis %d, %d extra inliers, "
+                         "aggregated error %.6g, %d degenerate sample(s)", name, n, iterations, sampler, outcome.best_h,
+                         outcome.extra_inliers, outcome.error, outcome.n_flagged)
+        if outcome.best_h < 0:
+            results += [None, [], 0]
+        else:
+            model = outcome.H if name == "H" else outcome.E
+            results += [model, copy_pairs(data, inlier_order(table, outcome, size)), size + outcome.extra_inliers]
+    if len(passes) == 1:
+        results += [None, [], 0]
+    return tuple(results)

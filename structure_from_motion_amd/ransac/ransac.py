@@ -8,7 +8,8 @@ Two execution routes behind one signature:
   selection — runs as HIP kernels on the MI355X (``device.RansacWorkspace``), and so does the five-point fitter of
   ``epipolar_ransac`` with ``model_fit_data_count == 6``; likewise for the six-point PnP fitter
   and reprojection scorer of ``pnp.pnp`` with ``model_fit_data_count == 6``, and its P3P fitter with
-  ``model_fit_data_count == 4`` (``device.PnPWorkspace``);
+  ``model_fit_data_count == 4`` (``device.PnPWorkspace``), and the four-point homography fitter and transfer-error
+  scorer of ``epipolar.homography`` (``device.HomographyWorkspace``);
 * for arbitrary Python callables (e.g. the 2-point line fitter of the reference's own
   ``test_ransac.py``) the loop is host logic: there is nothing to put on a GPU.
 
@@ -78,6 +79,11 @@ def fit_with_ransac(
 
         model, inliers = _engine.ransac_feature_pairs(
             data, spec.camera_matrix, inlier_threshold, min_extra, aggregation_code(method), iterations, solver=spec.solver)
+    elif isinstance(spec, HomographyDeviceSpec):
+        from ..epipolar import _engine
+
+        model, inliers = _engine.ransac_homography_pairs(
+            data, spec.camera_matrix, inlier_threshold, min_extra, aggregation_code(method), iterations)
     elif spec is not None:
         from ..epipolar import _engine
 
@@ -95,7 +101,7 @@ def fit_with_ransac(
 
 class Solver(NamedTuple):
     """A minimal solver of the device route."""
-    model: str         # "essential" or "pose"
+    model: str         # "essential", "pose" or "homography"
     sample_size: int   # items of a sample: they enter the aggregate, and its mean / RMS divide by count + sample_size
     role: str          # the _sfm_hip_role of the fitter whose partials route to it
 
@@ -105,16 +111,17 @@ SOLVERS = {
     "five_point": Solver("essential", 6, "five_point_fitter"),
     "dlt": Solver("pose", 6, "pnp_fitter"),
     "p3p": Solver("pose", 4, "p3p_fitter"),
+    "homography": Solver("homography", 4, "homography_fitter"),
 }
-_SCORER_ROLE = {"essential": "sed_scorer", "pose": "reprojection_scorer"}
+_SCORER_ROLE = {"essential": "sed_scorer", "pose": "reprojection_scorer", "homography": "transfer_scorer"}
+_MODEL_NAME = {"essential": "essential-matrix", "pose": "PnP", "homography": "homography"}
 
 
 def solver_sample_size(model: str, solver: str) -> int:
-    """Sample size of ``solver`` for a ``model`` ("essential" or "pose"); ``ValueError`` for an unknown one."""
+    """Sample size of ``solver`` for a ``model`` ("essential", "pose" or "homography"); ``ValueError`` for an unknown one."""
     known = sorted(name for name, s in SOLVERS.items() if s.model == model)
     if solver not in known:
-        what = "essential-matrix" if model == "essential" else "PnP"
-        raise ValueError(f"unknown {what} solver {solver!r}: expected one of {known}")
+        raise ValueError(f"unknown {_MODEL_NAME.get(model, model)} solver {solver!r}: expected one of {known}")
     return SOLVERS[solver].sample_size
 
 
@@ -130,10 +137,15 @@ class EssentialDeviceSpec(NamedTuple):
     solver: str = "five_point"
 
 
+class HomographyDeviceSpec(NamedTuple):
+    """Device route of the four-point homography fitter / transfer-error scorer pair."""
+    camera_matrix: np.ndarray
+
+
 def _device_spec(model_fitter, inlier_scorer, model_fit_data_count):
     """For partials of a tagged fitter (``SOLVERS``) and the scorer of its model, with that solver's sample size and one
     camera matrix: the bare camera matrix for the eight-point fitter, an EssentialDeviceSpec for the five-point one, a
-    PnPDeviceSpec for the DLT and P3P; else None."""
+    PnPDeviceSpec for the DLT and P3P, a HomographyDeviceSpec for the homography fitter; else None."""
     fit_fn = getattr(model_fitter, "func", None)
     score_fn = getattr(inlier_scorer, "func", None)
     if fit_fn is None or score_fn is None:
@@ -152,6 +164,8 @@ def _device_spec(model_fitter, inlier_scorer, model_fit_data_count):
     K = np.asarray(k_fit, dtype=np.float64)
     if spec.model == "pose":
         return PnPDeviceSpec(K, solver)
+    if spec.model == "homography":
+        return HomographyDeviceSpec(K)
     return K if solver == "eight_point" else EssentialDeviceSpec(K, solver)
 
 

@@ -1,0 +1,283 @@
+"""The NumPy definition of the homography kernels (csrc/sfm_homography.hip): the four-point DLT fit with
+np.linalg.svd, the symmetric transfer error, the score table, the selection rule and the mask, a host RANSAC loop through
+ransac.fit_with_ransac with untagged callables, and the scenes.  Imported by tests/test_homography_host.py and
+tests/test_gpu_homography.py."""
+import random
+
+import numpy as np
+
+from geometry_cases import rotation
+from structure_from_motion_amd import synthetic
+
+DEGENERATE_FLOOR = 1e-9
+SAMPLE = 4
+
+MOTIONS = {
+    # name -> (R, t, planar)
+    "pan10": (rotation((0.0, 1.0, 0.0), 10.0), np.zeros(3), False),
+    "gen12": (rotation((1.0, 2.0, 3.0), 12.0), np.zeros(3), False),
+    "plane_bench": (synthetic.rotation_xy(-5.0, -10.0), np.array([0.5, 0.05, 0.1]), True),
+    "bench": (synthetic.rotation_xy(-5.0, -10.0), np.array([0.5, 0.05, 0.1]), False),
+}
+
+
+def scene(R, t, planar, n, seed, noise_px=0.0, outlier_fraction=0.0, K=synthetic.BENCH_K):
+    """Points uniform in x, y in [-1, 1] and z in [4, 6], or (planar) on the plane z = 5 + 0.2 x - 0.1 y, seen by [I | 0] and
+    [R | t]: dict(pix_a, pix_b (n, 2) pixels, corr (n, 4) K-normalised {xa, ya, xb, yb}, K, R, t, is_outlier (n,)).  Gaussian
+    noise of noise_px pixels on both views before normalising; an outlier is a uniform pixel in view 2."""
+    rng = np.random.default_rng(seed)
+    X = np.empty((n, 3))
+    X[:, 0] = rng.uniform(-1.0, 1.0, n)
+    X[:, 1] = rng.uniform(-1.0, 1.0, n)
+    z = rng.uniform(4.0, 6.0, n)
+    X[:, 2] = 5.0 + 0.2 * X[:, 0] - 0.1 * X[:, 1] if planar else z
+    X2 = X @ R.T + t
+    assert (X[:, 2] > 0.0).all() and (X2[:, 2] > 0.0).all()
+
+    def project(Xc):
+        uvw = Xc @ K.T
+        return uvw[:, :2] / uvw[:, 2:3]
+
+    pa = project(X) + rng.normal(0.0, 1.0, (n, 2)) * noise_px
+    pb = project(X2) + rng.normal(0.0, 1.0, (n, 2)) * noise_px
+    is_out = rng.random(n) < outlier_fraction
+    width, height = 2.0 * K[0, 2], 2.0 * K[1, 2]
+    rand_px = np.column_stack([rng.uniform(0, width, n), rng.uniform(0, height, n)])
+    pb = np.where(is_out[:, None], rand_px, pb)
+
+    def normalise(p):
+        return np.column_stack([(p[:, 0] - K[0, 2]) / K[0, 0], (p[:, 1] - K[1, 2]) / K[1, 1]])
+
+    corr = np.ascontiguousarray(np.hstack([normalise(pa), normalise(pb)]))
+    return dict(pix_a=pa, pix_b=pb, corr=corr, K=K, R=R.copy(), t=t.copy(), is_outlier=is_out)
+
+
+# Two hand-made samples of four items each: items 0-2 collinear in image a only (not flagged: the system keeps rank 8 and H is
+# singular), and item 3 a repeat of item 0 (flagged: two null vectors).
+COLLINEAR_A = np.array([[0.0, 0.0, 0.01, 0.02], [0.1, 0.1, 0.12, 0.09], [0.2, 0.2, 0.25, 0.18], [0.3, -0.1, 0.31, -0.12]])
+REPEATED = np.vstack([COLLINEAR_A[[0, 1, 3]], COLLINEAR_A[0]])
+
+
+def motion_scene(name, n, seed, noise_px=0.0, outlier_fraction=0.0):
+    R, t, planar = MOTIONS[name]
+    return scene(R, t, planar, n, seed, noise_px, outlier_fraction)
+
+
+def _condition(x, y):
+    """x, y (h, 4) -> centroid (h,), (h,) and scale sqrt(2) / mean distance (h,)."""
+    cx = (((x[:, 0] + x[:, 1]) + x[:, 2]) + x[:, 3]) / 4.0
+    cy = (((y[:, 0] + y[:, 1]) + y[:, 2]) + y[:, 3]) / 4.0
+    dist = np.zeros(x.shape[0])
+    for i in range(4):
+        dx, dy = x[:, i] - cx, y[:, i] - cy
+        dist = dist + np.sqrt(dx * dx + dy * dy)
+    return cx, cy, np.sqrt(2.0) / (dist / 4.0)
+
+
+def fit(corr, S):
+    """corr (n, 4), S (h, >= 4) -> H (h, 9) with ||H||_F = 1 and det H >= 0, flags (h,) int32 (1: sigma_8 / sigma_1 of the
+    conditioned 8 x 9 system is not >= 1e-9, or an index is out of range), ratio (h,) = sigma_8 / sigma_1 (NaN where the
+    system is not finite or an index is out of range: H is NaN there)."""
+    corr = np.asarray(corr, dtype=np.float64)
+    S = np.asarray(S)[:, :SAMPLE].astype(np.int64)
+    h, n = S.shape[0], corr.shape[0]
+    bad = np.any((S < 0) | (S >= n), axis=1)
+    P = corr[np.where(bad[:, None], 0, S)]   # (h, 4, 4)
+    xa, ya, xb, yb = P[..., 0], P[..., 1], P[..., 2], P[..., 3]
+    with np.errstate(all="ignore"):
+        cax, cay, sa = _condition(xa, ya)
+        cbx, cby, sb = _condition(xb, yb)
+        A = np.zeros((h, 8, 9))
+        for i in range(4):
+            x, y = (xa[:, i] - cax) * sa, (ya[:, i] - cay) * sa
+            u, v = (xb[:, i] - cbx) * sb, (yb[:, i] - cby) * sb
+            A[:, 2 * i, 0], A[:, 2 * i, 1], A[:, 2 * i, 2] = x, y, 1.0
+            A[:, 2 * i, 6], A[:, 2 * i, 7], A[:, 2 * i, 8] = -u * x, -u * y, -u
+            A[:, 2 * i + 1, 3], A[:, 2 * i + 1, 4], A[:, 2 * i + 1, 5] = x, y, 1.0
+            A[:, 2 * i + 1, 6], A[:, 2 * i + 1, 7], A[:, 2 * i + 1, 8] = -v * x, -v * y, -v
+        finite = np.all(np.isfinite(A.reshape(h, -1)), axis=1) & ~bad
+        H = np.full((h, 9), np.nan)
+        ratio = np.full(h, np.nan)
+        if finite.any():
+            _, sigma, vt = np.linalg.svd(A[finite])
+            ht = vt[:, -1, :]
+            ratio[finite] = sigma[:, 7] / sigma[:, 0]
+            a_x, a_y, s_a, b_x, b_y, s_b = (v[finite] for v in (cax, cay, sa, cbx, cby, sb))
+            m = np.empty_like(ht)
+            for r in range(3):
+                m[:, 3 * r] = s_a * ht[:, 3 * r]
+                m[:, 3 * r + 1] = s_a * ht[:, 3 * r + 1]
+                m[:, 3 * r + 2] = ht[:, 3 * r + 2] - s_a * (ht[:, 3 * r] * a_x + ht[:, 3 * r + 1] * a_y)
+            g = np.empty_like(ht)
+            for c in range(3):
+                g[:, c] = m[:, c] / s_b + b_x * m[:, 6 + c]
+                g[:, 3 + c] = m[:, 3 + c] / s_b + b_y * m[:, 6 + c]
+                g[:, 6 + c] = m[:, 6 + c]
+            norm2 = np.zeros(g.shape[0])
+            for k in range(9):
+                norm2 = norm2 + g[:, k] * g[:, k]
+            g = g / np.sqrt(norm2)[:, None]
+            d = det(g)
+            H[finite] = np.where((d < 0.0)[:, None], -g, g)
+        flags = (~(ratio >= DEGENERATE_FLOOR)).astype(np.int32)
+    return H, flags, ratio
+
+
+def det(H):
+    """det of H (..., 9), in the kernel's operation order."""
+    h = [H[..., k] for k in range(9)]
+    return (h[0] * (h[4] * h[8] - h[5] * h[7]) - h[1] * (h[3] * h[8] - h[5] * h[6])) + h[2] * (h[3] * h[7] - h[4] * h[6])
+
+
+def transfer_error(H, corr):
+    """Symmetric transfer error of every item of corr (n, 4) under one H (9,), fixed operation order; +inf where either
+    point maps through the line at infinity."""
+    h = [np.float64(v) for v in np.ravel(H)]
+    g = [h[4] * h[8] - h[5] * h[7], h[2] * h[7] - h[1] * h[8], h[1] * h[5] - h[2] * h[4],
+         h[5] * h[6] - h[3] * h[8], h[0] * h[8] - h[2] * h[6], h[2] * h[3] - h[0] * h[5],
+         h[3] * h[7] - h[4] * h[6], h[1] * h[6] - h[0] * h[7], h[0] * h[4] - h[1] * h[3]]
+    xa, ya, xb, yb = (corr[..., k] for k in range(4))
+    with np.errstate(all="ignore"):
+        p0 = (h[0] * xa + h[1] * ya) + h[2]
+        p1 = (h[3] * xa + h[4] * ya) + h[5]
+        p2 = (h[6] * xa + h[7] * ya) + h[8]
+        q0 = (g[0] * xb + g[1] * yb) + g[2]
+        q1 = (g[3] * xb + g[4] * yb) + g[5]
+        q2 = (g[6] * xb + g[7] * yb) + g[8]
+        du, dv = p0 / p2 - xb, p1 / p2 - yb
+        eu, ev = q0 / q2 - xa, q1 / q2 - ya
+        e = (du * du + dv * dv) + (eu * eu + ev * ev)
+        return np.where((p2 <= 0.0) | (q2 <= 0.0), np.inf, e)
+
+
+def score_table(corr, H, S, thr):
+    """(cnt, s1, s2) of every hypothesis: H (h, 9), S (h, >= 4) with distinct valid entries.  cnt = non-sample items with
+    e <= thr; s1 / s2 = sums of e / e^2 over the four sample items and those survivors."""
+    h, n = H.shape[0], corr.shape[0]
+    cnt = np.zeros(h, dtype=np.int32)
+    s1 = np.zeros(h)
+    s2 = np.zeros(h)
+    for k in range(h):
+        e = transfer_error(H[k], corr)
+        sample = np.zeros(n, dtype=bool)
+        sample[S[k, :SAMPLE]] = True
+        with np.errstate(invalid="ignore"):
+            surv = (~sample) & (e <= thr)
+        cnt[k] = np.count_nonzero(surv)
+        chosen = e[sample | surv]
+        with np.errstate(over="ignore", invalid="ignore"):
+            s1[k] = np.sum(chosen)
+            s2[k] = np.sum(chosen * chosen)
+    return cnt, s1, s2
+
+
+def aggregate(cnt, s1, s2, method):
+    """ransac.py's aggregation on (count, sum, sum of squares) with four sample items; method 0 sum, 1 square, 2 mean, 3 rms."""
+    nn = cnt.astype(np.float64) + float(SAMPLE)
+    with np.errstate(all="ignore"):
+        return [s1, s2, s1 / nn, np.sqrt(s2 / nn)][method]
+
+
+def select(cnt, s1, s2, flags, min_extra, method):
+    """The host rule: lowest aggregated error among hypotheses with cnt >= min_extra, a finite error and no flag; earliest
+    index on ties.  Returns (best index or -1, its error or inf)."""
+    err = aggregate(cnt, s1, s2, method)
+    with np.errstate(invalid="ignore"):
+        ok = (cnt >= min_extra) & (err < np.inf) & (flags == 0)
+    if not ok.any():
+        return -1, np.inf
+    best = int(np.argmin(np.where(ok, err, np.inf)))
+    return best, float(err[best])
+
+
+def mask(corr, H, S, best, thr):
+    """uint8 (n,): 2 for the four sample items of hypothesis ``best``, 1 other items with e <= thr, 0 otherwise; all zero
+    for best < 0."""
+    out = np.zeros(corr.shape[0], dtype=np.uint8)
+    if best < 0:
+        return out
+    with np.errstate(invalid="ignore"):
+        out[transfer_error(H[best], corr) <= thr] = 1
+    out[S[best, :SAMPLE]] = 2
+    return out
+
+
+def fitter(pairs, K, skip_flagged=False):
+    """Untagged host fitter for ransac.fit_with_ransac: (Feature, Feature) pixel pairs -> H (3, 3); for a flagged sample
+    ArithmeticError, or (skip_flagged) NaNs, which never gate."""
+    corr = np.array([[(a.x - K[0, 2]) / K[0, 0], (a.y - K[1, 2]) / K[1, 1], (b.x - K[0, 2]) / K[0, 0], (b.y - K[1, 2]) / K[1, 1]]
+                     for a, b in pairs])
+    H, flags, _ = fit(corr, np.arange(SAMPLE)[None])
+    if flags[0] and not skip_flagged:
+        raise ArithmeticError("degenerate sample")
+    return np.full((3, 3), np.nan) if flags[0] else H[0].reshape(3, 3)
+
+
+def scorer(H, pair, K):
+    a, b = pair
+    corr = np.array([(a.x - K[0, 2]) / K[0, 0], (a.y - K[1, 2]) / K[1, 1], (b.x - K[0, 2]) / K[0, 0], (b.y - K[1, 2]) / K[1, 1]])
+    return float(transfer_error(H, corr))
+
+
+def feature_pairs(sc):
+    from structure_from_motion_amd.common.feature import Feature
+
+    return [(Feature(float(a[0]), float(a[1])), Feature(float(b[0]), float(b[1]))) for a, b in zip(sc["pix_a"], sc["pix_b"])]
+
+
+def host_ransac(sc, threshold, min_extra, iterations, shuffle_seed, method=None, skip_flagged=False):
+    """fit_with_ransac on the host (untagged callables, so nothing routes to the device) -> (H (3, 3), inlier pairs)."""
+    from structure_from_motion_amd.ransac import ransac
+
+    K = sc["K"]
+    random.seed(shuffle_seed)
+    return ransac.fit_with_ransac(feature_pairs(sc), SAMPLE, lambda pairs: fitter(pairs, K, skip_flagged), lambda H, pair: scorer(H, pair, K),
+                                  threshold, min_extra, method, iterations)
+
+
+def host_essential_count(sc, threshold, min_extra, iterations, shuffle_seed):
+    """Inlier count (sample + survivors) of the five-point host loop on the same shuffles, 0 when it finds no model; flagged
+    samples are skipped, as select_two_view_model does."""
+    from functools import partial
+
+    from structure_from_motion_amd.epipolar import epipolar_ransac as er
+    from structure_from_motion_amd.epipolar import five_point
+    from structure_from_motion_amd.ransac import ransac
+
+    K = sc["K"]
+    fit6 = partial(er.five_point_model_fitter, camera_matrix=K)
+
+    def fit_or_nan(sample):
+        try:
+            return fit6(sample)
+        except ArithmeticError:
+            return np.full((3, 3), np.nan)
+
+    def sed(E, pair):
+        (xa, ya), (xb, yb) = (((f.x - K[0, 2]) / K[0, 0], (f.y - K[1, 2]) / K[1, 1]) for f in pair)
+        with np.errstate(all="ignore"):
+            return float(five_point.sed_value(list(np.ravel(E)), xa, ya, xb, yb))
+
+    random.seed(shuffle_seed)
+    E, inliers = ransac._host_loop(feature_pairs(sc), 6, fit_or_nan, sed, threshold, min_extra,
+                                   ransac.ErrorAggregationMethod.RMS, iterations)
+    return 0 if E is None else len(inliers)
+
+
+def host_model_choice(name, n, scene_seed, shuffle_seed, threshold=2e-5, min_extra=20, iterations=200, noise_px=0.5,
+                      outlier_fraction=0.3):
+    """(homography count, essential count, ratio) of the two host loops on one scene: what select_two_view_model computes."""
+    sc = motion_scene(name, n, scene_seed, noise_px, outlier_fraction)
+    try:
+        _, inliers = host_ransac(sc, threshold, min_extra, iterations, shuffle_seed, skip_flagged=True)
+        h_count = len(inliers)
+    except ValueError:
+        h_count = 0
+    e_count = host_essential_count(sc, threshold, min_extra, iterations, shuffle_seed)
+    return h_count, e_count, (h_count / e_count if e_count else float("inf"))
+
+
+if __name__ == "__main__":   # PYTHONPATH=. python tests/homography_oracle.py: the margins of the model-choice test
+    for motion in MOTIONS:
+        for seed in (7, 8, 9):
+            print(motion, seed, host_model_choice(motion, 300, seed, 5))
