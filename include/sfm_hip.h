@@ -545,7 +545,8 @@ int sfm_bundle_adjust_pcg_ex(const double* K, int64_t cameras, int64_t points, i
 
 #define SFM_TRACKS_OK 0
 #define SFM_TRACKS_FEW_VIEWS 1   /* fewer than min_views observations: point, angle and errors NaN */
-#define SFM_TRACKS_DEGENERATE 2  /* the unit null vector is not finite or |v3| <= 1e-12: point, angle and errors NaN */
+#define SFM_TRACKS_DEGENERATE 2  /* every observation names one camera, or the unit null vector is not finite or |v3| <= 1e-12:
+                                  * point, angle and errors NaN */
 #define SFM_TRACKS_BEHIND 3      /* behind a camera of one of its observations (the estimate is written) */
 #define SFM_TRACKS_SMALL_ANGLE 4 /* triangulation angle below min_angle (the estimate is written) */
 #define SFM_TRACKS_LARGE_ERROR 5 /* an observation's squared reprojection error above max_error (the estimate is written) */

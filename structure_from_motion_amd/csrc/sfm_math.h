@@ -443,7 +443,8 @@ SFM_DEVICE bool rotate_rows4(double (&g)[4][4]) {
 // stage works on; verified against LAPACK's SVD to 6e-14 on 2000 noisy inliers, pixel and normalised units).
 // Up to 16 steps (the loop ends as soon as every lane of the wave has converged; with a cap of 4 a third of the waves
 // of the C5 batch still fell through to Jacobi).  Returns false if they did not converge (rays nearly parallel, or
-// gross outliers): the caller then uses the Jacobi route for the whole wave.
+// gross outliers) or if R lost rank in one of its first three columns: the caller then uses the Jacobi route for the
+// whole wave.
 SFM_DEVICE bool null_vector4_qr(const double rows[4][4], double x[4]) {
 #pragma clang fp contract(fast)   // converged iterations / tolerance-checked: multiplies and adds may fuse
     double r[4][4];
@@ -477,9 +478,16 @@ SFM_DEVICE bool null_vector4_qr(const double rows[4][4], double x[4]) {
     const double scale = fmax(fmax(fabs(r[0][0]), fabs(r[1][1])), fmax(fabs(r[2][2]), fabs(r[3][3])));
     const double tiny = scale * 1e-16 + 1e-300;
     double inv[4];
+    // A vanished r11, r22 or r33 is another matter: when its column is zero above it as well (two parallel cameras seeing
+    // one direction leave R = [a 0 0 b; 0 c 0 0; 0 0 0 0; 0 0 0 d]), the null vector is that column's unit vector, R^-1 e4
+    // has an exact 0 there and the iteration never leaves the other three coordinates: it would converge to the wrong
+    // vector.  Such a lane reports no convergence and takes the Jacobi route.
+    bool rank_lost = false;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        const double d = (fabs(r[i][i]) < tiny) ? ((r[i][i] < 0.0) ? -tiny : tiny) : r[i][i];
+        const bool guarded = fabs(r[i][i]) < tiny;
+        rank_lost = rank_lost || (guarded && i < 3);
+        const double d = guarded ? ((r[i][i] < 0.0) ? -tiny : tiny) : r[i][i];
         inv[i] = rcp_newton(d);
     }
     x[3] = 1.0;
@@ -513,7 +521,7 @@ SFM_DEVICE bool null_vector4_qr(const double rows[4][4], double x[4]) {
             change = fmax(change, fabs(next - x[i]));
             x[i] = next;
         }
-        converged = change < 1e-15;  // NaN / inf anywhere: stays false
+        converged = !rank_lost && change < 1e-15;  // NaN / inf anywhere: stays false
         if (__all(converged)) break;  // wave-uniform
     }
     return converged;

@@ -10,6 +10,8 @@
 //      condition number not squared), then R's null vector by sfm::null_vector4 and X = v[0:3] / v[3];
 //   2. optionally LM on the point alone, on F(X) = sum of sfm_pnp_score's e over its observations;
 //   3. e per observation, cheirality, the triangulation angle and the status.
+// A track whose observations all name one camera is DEGENERATE whatever its pixels say: its rays meet at that camera's
+// centre, which the DLT would return with a depth of rounding size.
 // null_vector4 decides per wave, so a point's lane is fixed by its index.  No floating-point atomics: a call is
 // bit-identical from run to run, and to any call whose observations keep each point's own order.
 #include <hip/hip_runtime.h>
@@ -239,9 +241,12 @@ __global__ __launch_bounds__(kThreads) void tracks_point_kernel(int P, Obs obs, 
 
     // 1. linear estimate
     double R[4][4] = {};
+    bool several = false;   // some observation's camera differs from the first one's
     if (mine && !few) {
+        const int32_t first = obs.cam[run[0]];
         for (int q = 0; q < n; ++q) {
             const int m = run[q];
+            several = several || obs.cam[m] != first;
             const double* pose = poses + 12 * (int64_t)obs.cam[m];
             const double x = obs.uv[2 * (int64_t)m], y = obs.uv[2 * (int64_t)m + 1];
             double Pm[3][4];
@@ -275,7 +280,7 @@ __global__ __launch_bounds__(kThreads) void tracks_point_kernel(int P, Obs obs, 
         status = SFM_TRACKS_BAD_INDEX;
     else if (few)
         status = SFM_TRACKS_FEW_VIEWS;
-    else if (!(isfinite(v[0]) && isfinite(v[1]) && isfinite(v[2]) && isfinite(v[3])) || !(fabs(v[3]) > kMinW))
+    else if (!several || !(isfinite(v[0]) && isfinite(v[1]) && isfinite(v[2]) && isfinite(v[3])) || !(fabs(v[3]) > kMinW))
         status = SFM_TRACKS_DEGENERATE;
     double X[3] = {NAN, NAN, NAN};
     double angle = NAN;

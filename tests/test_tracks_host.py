@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import geometry_cases as gc
+import tracks_cases as tc
 import tracks_oracle as to
 from oracle import sfm_oracle
 from structure_from_motion_amd import synthetic
@@ -98,40 +99,17 @@ def test_oracle_refinement_lowers_the_cost():
 
 
 def test_oracle_produces_every_status():
-    """One constructed track per status, in one call."""
-    poses = np.array([np.concatenate([np.eye(3).reshape(9), np.zeros(3)]),
-                      np.concatenate([synthetic.rotation_xy(0.0, -5.0).reshape(9), [0.5, 0.0, 0.0]]),
-                      np.concatenate([synthetic.rotation_xy(0.0, 5.0).reshape(9), [-0.5, 0.0, 0.0]]),
-                      np.concatenate([np.eye(3).reshape(9), [0.5, 0.0, 0.0]])])
-
-    def project(c, X):
-        xc = poses[c, :9].reshape(3, 3) @ X + poses[c, 9:]
-        return (K @ xc)[:2] / xc[2]
-
-    X = np.array([0.2, -0.1, 5.0])
-    cam, pt, uv = [], [], []
-
-    def add(p, c, pix):
-        cam.append(c)
-        pt.append(p)
-        uv.append(pix)
-
-    add(0, 0, project(0, X)), add(0, 1, project(1, X)), add(0, 2, project(2, X))               # 0 OK
-    add(1, 0, project(0, X))                                                                       # 1 FEW_VIEWS
-    add(2, 0, K[:2, 2]), add(2, 3, K[:2, 2])                          # 2 DEGENERATE: parallel rays, the point at infinity
-    behind = np.array([0.2, -0.1, -5.0])
-    add(3, 0, project(0, behind)), add(3, 1, project(1, behind))                                 # 3 BEHIND
-    far = np.array([0.2, -0.1, 400.0])
-    add(4, 0, project(0, far)), add(4, 1, project(1, far))                                       # 4 SMALL_ANGLE
-    add(5, 0, project(0, X)), add(5, 1, project(1, X) + [15.0, 0.0]), add(5, 2, project(2, X))   # 5 LARGE_ERROR
-    out = to.triangulate(K, poses, np.array(cam), np.array(pt), np.array(uv), 7, min_angle=np.radians(1.0), max_error=4.0)
-    assert out["status"].tolist() == [to.OK, to.FEW_VIEWS, to.DEGENERATE, to.BEHIND, to.SMALL_ANGLE, to.LARGE_ERROR,
-                                      to.FEW_VIEWS]
+    """One constructed track per status, in one call (tests/tracks_cases.py::every_status, its points 0 .. 6)."""
+    case = tc.every_status()
+    poses, cam, pt, uv = case["poses"], case["cam"].tolist(), case["pt"], case["uv"]
+    out = to.triangulate(K, poses, np.array(cam), pt, uv, case["P"], min_angle=np.radians(1.0), max_error=4.0)
+    assert out["status"][:7].tolist() == [to.OK, to.FEW_VIEWS, to.DEGENERATE, to.BEHIND, to.SMALL_ANGLE, to.LARGE_ERROR,
+                                          to.FEW_VIEWS]
     assert np.all(np.isnan(out["points"][[1, 2, 6]])) and np.all(np.isnan(out["angle"][[1, 2, 6]]))
     assert np.all(np.isfinite(out["points"][[0, 3, 4, 5]]))
     assert np.isnan(out["obs_error"][3]) and np.all(np.isnan(out["obs_error"][4:6]))
     assert out["info"] == dict(status=0, points_ok=1, max_refine_steps_taken=0)
-    bad = to.triangulate(K, poses, np.array(cam[:-1] + [4]), np.array(pt), np.array(uv), 7)
+    bad = to.triangulate(K, poses, np.array(cam[:-1] + [4]), pt, uv, case["P"])
     assert np.all(bad["status"] == to.BAD_INDEX) and bad["info"]["status"] == 1
     assert np.all(np.isnan(bad["points"])) and np.all(np.isnan(bad["obs_error"])) and np.all(np.isnan(bad["angle"]))
 

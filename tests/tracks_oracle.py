@@ -158,7 +158,8 @@ def triangulate(K, poses, cam, pt, uv, num_points, min_views=2, min_angle=0.0, m
         A[~finite] = 0.0
         v = np.linalg.svd(A)[2][:, -1, :]
         v = v / np.linalg.norm(v, axis=1, keepdims=True)
-        degenerate = ~finite | ~np.all(np.isfinite(v), axis=1) | ~(np.abs(v[:, 3]) > MIN_W)
+        one_camera = np.all(c == c[:, :1], axis=1)   # the rays meet at that camera's centre: no point, whatever the pixels
+        degenerate = one_camera | ~finite | ~np.all(np.isfinite(v), axis=1) | ~(np.abs(v[:, 3]) > MIN_W)
         status[ps[degenerate]] = DEGENERATE
         good = ~degenerate
         ps, obs, c, q, v = ps[good], obs[good], c[good], q[good], v[good]
