@@ -14,7 +14,10 @@ final bundle adjustment and the points that end OK, as JSON.
 instead (``synthetic.pairwise_matches``: views up to three apart, 10 % wrong matches): every pair is verified by the
 essential-matrix RANSAC and keeps its winner's inliers (a pair without a model is dropped), ``build_tracks`` turns them into
 tracks, and the same reconstruction runs on the built observations.  The output then also holds the build's info and the
-fraction of OK tracks whose features all belong to one true point.
+fraction of OK tracks whose features all belong to one true point.  ``verify="batched"`` (``--verify batched``) verifies all
+pairs in one ``verify_pairs`` call instead of one essential-matrix RANSAC per pair: a homography and a five-point essential
+pass per pair, the pairs whose kind is not ``"none"`` kept with the inliers of the model their kind names, and the number of
+pairs of each kind added to the output.
 
 ``bundle_loss`` (``--bundle-loss``) gives every bundle adjustment a robust loss (``"huber"`` or ``"cauchy"`` with
 ``bundle_loss_scale`` pixels); the drop rules stay as they are, and ``rms_px`` is then computed from the
@@ -36,6 +39,7 @@ from lib.bundle.bundle import bundle_adjust
 from lib.common.feature import Feature
 from lib.epipolar.eight_point import create_trivial_matches, recover_r_t_from_e
 from lib.epipolar.epipolar_ransac import estimate_essential_mat_with_ransac
+from lib.epipolar.view_graph import verify_pairs
 from lib.feature_matching.matching import Match
 from lib.multiview.tracks import build_tracks, triangulate_tracks
 from lib.pnp.pnp import estimate_pose_pnp_with_ransac
@@ -46,6 +50,7 @@ MAX_VIEWS = 1024       # with bundle_solver="auto": a bound of the app (host-sid
 BUNDLE_SOLVERS = ("dense", "auto")
 BUNDLE_LOSSES = device.BUNDLE_LOSSES
 TRACK_SOURCES = ("given", "matches")
+VERIFY_ROUTES = ("loop", "batched")
 MIN_PNP_INLIERS = 30
 
 
@@ -164,19 +169,29 @@ def _verified_matches(K, pix_a, pix_b, m, sed_threshold: float, iterations: int,
     return m[device.checked_mask(outcome.mask) > 0]
 
 
-def tracks_from_matches(scene, sed_threshold: float, iterations: int, e_solver: str, seed: int):
+def tracks_from_matches(scene, sed_threshold: float, iterations: int, e_solver: str, seed: int, verify: str = "loop"):
     """The scene's tracks rebuilt from verified pairwise matches: (scene with the built camera_indices, point_indices and
-    pixels, the build's info, the fraction of OK tracks whose features all belong to one true point, pairs kept)."""
+    pixels, the build's info, the fraction of OK tracks whose features all belong to one true point, pairs kept, and with
+    ``verify="batched"`` the number of pairs of each kind, else None)."""
     K = scene["K"]
     random.seed(seed)   # the pairs' RANSAC samples
     pm = synthetic.pairwise_matches(scene, seed=seed)
-    pairs, kept = [], []
-    for (i, j), m in zip(pm["pairs"], pm["matches"]):
-        inliers = _verified_matches(K, pm["features"][i], pm["features"][j], m, sed_threshold, iterations, e_solver)
-        if inliers is None:
-            continue   # a pair without a model is dropped
-        pairs.append((i, j))
-        kept.append(inliers)
+    pairs, kept, kinds = [], [], None
+    if verify == "batched":
+        graph = verify_pairs(K, pm["features"], pm["pairs"], pm["matches"], sed_threshold, min_extra_fraction=0.4,
+                             max_iterations=iterations)
+        kinds = {kind: graph.kind.count(kind) for kind in ("essential", "homography", "none")}
+        for (i, j), kind, inliers in zip(pm["pairs"], graph.kind, graph.inlier_matches):
+            if kind != "none":   # a pair without a model is dropped
+                pairs.append((i, j))
+                kept.append(inliers)
+    else:
+        for (i, j), m in zip(pm["pairs"], pm["matches"]):
+            inliers = _verified_matches(K, pm["features"][i], pm["features"][j], m, sed_threshold, iterations, e_solver)
+            if inliers is None:
+                continue   # a pair without a model is dropped
+            pairs.append((i, j))
+            kept.append(inliers)
     r = build_tracks(pm["features"], np.array(pairs, dtype=np.int64).reshape(-1, 2), kept)
     truth = np.concatenate(pm["feature_points"])[r.feature_indices]
     lo = np.full(r.info.tracks, np.iinfo(np.int64).max)
@@ -185,20 +200,22 @@ def tracks_from_matches(scene, sed_threshold: float, iterations: int, e_solver: 
     np.maximum.at(hi, r.point_indices, truth)
     pure = float(np.mean(lo == hi)) if r.info.tracks else float("nan")
     built = dict(scene, camera_indices=r.camera_indices, point_indices=r.point_indices, pixels=r.pixels)
-    return built, r.info, pure, len(pairs)
+    return built, r.info, pure, len(pairs), kinds
 
 
 def run(views: int = 8, points: int = 2000, seed: int = 21, noise_px: float = 0.5, outlier_fraction: float = 0.2,
         sed_threshold: float = 6e-6, reprojection_threshold: float = 16.0, iterations: int = 2000, refine_steps: int = 10,
         ba_steps: int = 20, final_ba_steps: int = 50, step_deg: float = 5.0, bundle_solver: str = "dense",
         details: bool = False, pnp_solver: str = "dlt", e_solver: str = "eight_point", tracks: str = "given",
-        bundle_loss: str = "squared", bundle_loss_scale: float = 2.0) -> dict:
+        bundle_loss: str = "squared", bundle_loss_scale: float = 2.0, verify: str = "loop") -> dict:
     if pnp_solver not in ("dlt", "p3p"):
         raise ValueError(f"pnp_solver must be 'dlt' or 'p3p', got {pnp_solver!r}")
     if e_solver not in ("eight_point", "five_point"):
         raise ValueError(f"e_solver must be 'eight_point' or 'five_point', got {e_solver!r}")
     if tracks not in TRACK_SOURCES:
         raise ValueError(f"tracks must be one of {TRACK_SOURCES}, got {tracks!r}")
+    if verify not in VERIFY_ROUTES:
+        raise ValueError(f"verify must be one of {VERIFY_ROUTES}, got {verify!r}")
     if bundle_solver not in BUNDLE_SOLVERS:
         raise ValueError(f"bundle_solver must be one of {BUNDLE_SOLVERS}, got {bundle_solver!r}")
     if bundle_loss not in BUNDLE_LOSSES:
@@ -211,10 +228,12 @@ def run(views: int = 8, points: int = 2000, seed: int = 21, noise_px: float = 0.
     scene = synthetic.multi_view_scene(views, points, seed, noise_px, outlier_fraction, step_deg=step_deg)
     build = None
     if tracks == "matches":
-        scene, build_info, pure, kept_pairs = tracks_from_matches(scene, sed_threshold, iterations, e_solver, seed)
+        scene, build_info, pure, kept_pairs, kinds = tracks_from_matches(scene, sed_threshold, iterations, e_solver, seed, verify)
         build = dict(pairs_kept=kept_pairs, components=build_info.components, tracks=build_info.tracks,
                      observations=build_info.observations, conflicts=build_info.conflicts,
                      unmatched=build_info.unmatched, pure_track_fraction=pure)
+        if kinds is not None:
+            build.update(pairs_essential=kinds["essential"], pairs_homography=kinds["homography"], pairs_none=kinds["none"])
     K = scene["K"]
     rec = Reconstruction(scene, reprojection_threshold, refine_steps, min_angle_deg=1.0, bundle_solver=bundle_solver,
                          bundle_loss=bundle_loss, bundle_loss_scale=float(bundle_loss_scale))
@@ -336,6 +355,9 @@ def main():
                     help="minimal solver that registers each further view: six-point DLT or P3P on four-item samples")
     ap.add_argument("--tracks", choices=TRACK_SOURCES, default="given",
                     help="given: the scene's tracks; matches: tracks built from RANSAC-verified pairwise matches")
+    ap.add_argument("--verify", choices=VERIFY_ROUTES, default="loop",
+                    help="with --tracks matches: loop: one essential-matrix RANSAC per pair; batched: all pairs in one "
+                         "verify_pairs call (homography and five-point essential per pair)")
     ap.add_argument("--e-solver", choices=("eight_point", "five_point"), default="eight_point",
                     help="minimal solver of the two-view seed: eight-point, or five-point on six-item samples")
     ap.add_argument("--bundle-loss", choices=BUNDLE_LOSSES, default="squared",
@@ -349,7 +371,7 @@ def main():
                          reprojection_threshold=args.reprojection_threshold, refine_steps=args.refine_steps,
                          step_deg=args.step_deg, bundle_solver=args.bundle_solver, pnp_solver=args.pnp_solver,
                          e_solver=args.e_solver, tracks=args.tracks, bundle_loss=args.bundle_loss,
-                         bundle_loss_scale=args.bundle_loss_scale)))
+                         bundle_loss_scale=args.bundle_loss_scale, verify=args.verify)))
 
 
 if __name__ == "__main__":

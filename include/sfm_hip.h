@@ -392,7 +392,7 @@ int sfm_homography_fit(const double* corr, int64_t n, const int32_t* S, int64_t 
                        void* stream);
 
 /* Scoring of all n items under all hypotheses with the symmetric transfer error e = |H xa - xb|^2 + |adj(H) xb - xa|^2 in
- * inhomogeneous coordinates (operation order fixed in sfm_homography.hip), +inf when either third coordinate is <= 0.
+ * inhomogeneous coordinates (operation order fixed in sfm_homography.h), +inf when either third coordinate is <= 0.
  * cnt[b,h] = non-sample items with e <= thr; s1 / s2 = sums of e / e^2 over the 4 sample items plus those survivors.  All
  * fp64, exact divisions: the values are the host scorer's bit for bit.  Selection: sfm_select_best with sample_size 4. */
 int sfm_homography_score(const double* corr, int64_t n, const double* H, const int32_t* S, int64_t h_count, int64_t batch,
@@ -410,6 +410,46 @@ int sfm_homography_ransac_pass(uint64_t seed, uint64_t seed_stride, int use_phil
                                int64_t n, int64_t h_count, int64_t batch, double thr, double min_extra, int aggregation,
                                int32_t* S, double* H, int32_t* flags, int32_t* cnt, double* s1, double* s2,
                                sfm_select_result* result, uint8_t* mask, void* stream);
+
+/* ---- two-view verification of every pair of a match graph in one call (csrc/sfm_view_graph.hip; an
+ * extension, added under ABI 15) ----
+ * corr: dev [n_total,4], the K-normalised correspondences of all pairs, concatenated; offset: dev int64 [pairs+1], pair q owns
+ * items offset[q] .. offset[q+1]-1 (n_q of them, any count, 0 included); min_extra: dev double [pairs], the gate of pair q.
+ * Pair q's outputs are those of sfm_homography_ransac_pass(seed + q * seed_stride, seed_stride, use_philox = 1, h_begin,
+ * its items, n_q, h_count, 1, thr, min_extra[q], aggregation, ...) followed by sfm_five_point_ransac_pass(use_philox = 0) on
+ * the rows of S the first one filled:
+ *   S int32 [pairs,h_count,8]; H, E [pairs,h_count,9]; h_* / e_* flags, cnt int32 and s1, s2 double [pairs,h_count];
+ *   h_result, e_result [pairs] (best_h local to the pair); h_mask, e_mask uint8 [n_total] (0 for an item no pair owns);
+ *   verdict [pairs].
+ * Every element of every output is written.  A pair with n_q below a model's sample size (4 for H, 6 for E) gets that model's
+ * filler: 9 NaNs, flag SFM_FIT_DEGENERATE, cnt 0, s1 = s2 = NaN, hence a record without a winner (n_flagged = h_count); with
+ * n_q < 4 the rows of S are -1 throughout.
+ * The offset table is checked on the device by the first launch: unless 0 <= offset[0] <= ... <= offset[pairs] <= n_total,
+ * every pair is treated as empty (filler throughout, masks 0) and every verdict is SFM_PAIR_BAD_OFFSETS; that is a status,
+ * not an error return, and nothing is read through such a table.
+ * Seven launches whatever `pairs` is, nothing read back; every size is checked before the first launch (pairs <= 65535,
+ * n_total < 2^31); pairs == 0 is a no-op.  No atomics: a call is reproducible bit for bit. */
+#define SFM_PAIR_NONE 0        /* neither model has a winner */
+#define SFM_PAIR_ESSENTIAL 1   /* an essential matrix explains the pair */
+#define SFM_PAIR_HOMOGRAPHY 2  /* E has no winner, or homography_count / essential_count > max_ratio */
+#define SFM_PAIR_BAD_OFFSETS 3 /* the offset table of the call is not non-decreasing within [0, n_total]: every pair, no model */
+
+typedef struct sfm_pair_verdict {
+    int32_t kind;             /* SFM_PAIR_* */
+    int32_t homography_count; /* the H winner's sample size (4) plus its extra inliers, 0 without a winner */
+    int32_t essential_count;  /* the same for E (sample size 6) */
+    int32_t reserved;         /* 0 */
+    double ratio;             /* homography_count / essential_count, +inf when essential_count is 0 */
+} sfm_pair_verdict;
+#ifdef __cplusplus
+static_assert(sizeof(sfm_pair_verdict) == 24, "sfm_pair_verdict is 24 bytes");
+#endif
+
+int sfm_verify_pairs(uint64_t seed, uint64_t seed_stride, int64_t h_begin, const double* corr, int64_t n_total,
+                     const int64_t* offset, int64_t pairs, const double* min_extra, int64_t h_count, double thr, int aggregation,
+                     double max_ratio, int32_t* S, double* H, double* E, int32_t* h_flags, int32_t* h_cnt, double* h_s1,
+                     double* h_s2, int32_t* e_flags, int32_t* e_cnt, double* e_s1, double* e_s2, sfm_select_result* h_result,
+                     sfm_select_result* e_result, uint8_t* h_mask, uint8_t* e_mask, sfm_pair_verdict* verdict, void* stream);
 
 /* ---- refinement of a PnP winner on its inliers (csrc/sfm_pnp_refine.hip; an extension, off unless asked for) ---- */
 

@@ -176,6 +176,7 @@ SIGNATURES = {
     "sfm_homography_inlier_mask": [_P, _I64, _P, _P, _I64, _I64, _P, _D, _P, _P],
     "sfm_homography_ransac_pass": [_U64, _U64, C.c_int, _I64, _P, _I64, _I64, _I64, _D, _D, C.c_int, _P, _P, _P, _P, _P, _P,
                                    _P, _P, _P],
+    "sfm_verify_pairs": [_U64, _U64, _I64, _P, _I64, _P, _I64, _P, _I64, _D, C.c_int, _D] + [_P] * 17,
     "sfm_pnp_refine": [_P, _I64, _I64, _P, _P, _P, _P, _D, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P],
     "sfm_bundle_adjust": [_P, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _I64, _P],
     "sfm_bundle_adjust_pcg": [_P, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, _D, _P, _P, _P, _P, _I64, _P],
@@ -193,6 +194,16 @@ OTHER_SYMBOLS = ["sfm_last_error", "sfm_abi_version", "sfm_score_workspace_bytes
 
 # the losses of both bundle adjusters, in the order of their SFM_BUNDLE_LOSS_* codes (include/sfm_hip.h)
 BUNDLE_LOSSES = ("squared", "huber", "cauchy")
+
+
+# the kinds of sfm_pair_verdict, in the order of their SFM_PAIR_* codes (include/sfm_hip.h)
+PAIR_KINDS = ("none", "essential", "homography", "bad_offsets")
+
+
+class PairVerdict(C.Structure):
+    """sfm_pair_verdict"""
+    _fields_ = [("kind", C.c_int32), ("homography_count", C.c_int32), ("essential_count", C.c_int32), ("reserved", C.c_int32),
+                ("ratio", C.c_double)]
 
 
 class BundleOptions(C.Structure):

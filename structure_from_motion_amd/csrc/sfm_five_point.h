@@ -602,4 +602,52 @@ SFM_DEVICE bool solve(const double (&xa)[5], const double (&ya)[5], const double
     return false;
 }
 
+// ---- the solver of the shared fit kernel (sfm_minimal_fit.h); also what the ragged pass of sfm_view_graph.hip fits with ----
+constexpr int kFiveSample = 6;   // five items solved for, the sixth picks the solution
+
+// The items of one sample; bad when an index is out of range.
+SFM_DEVICE void load_items(const Corr* __restrict__ pts, int64_t n, const int32_t (&idx)[8], double (&xa)[5], double (&ya)[5],
+                           double (&xb)[5], double (&yb)[5], Corr& item5, bool& bad) {
+#pragma unroll
+    for (int i = 0; i < 5; ++i) {
+        const Corr p = pts[checked_index(idx[i], n, bad)];
+        xa[i] = p.xa;
+        ya[i] = p.ya;
+        xb[i] = p.xb;
+        yb[i] = p.yb;
+    }
+    item5 = pts[checked_index(idx[5], n, bad)];
+}
+
+// Five-point fit of one hypothesis: SFM_FIT_DEGENERATE for a degenerate sample or an index out of range (E = 9 NaNs then),
+// otherwise the candidate with the strictly smallest SED on item 5, or 9 NaNs when there is none (flag 0).
+struct five_point_solver {
+    static constexpr int kSample = kFiveSample, kModel = 9;
+    static constexpr const char* kName = "minimal_fit_kernel<five_point_solver>";
+    using Data = const Corr*;
+    SFM_DEVICE static int fit(Data corr, int64_t b, int64_t n, const int32_t (&idx)[8], double (&out)[9]);
+};
+
+SFM_DEVICE int five_point_solver::fit(Data corr, int64_t b, int64_t n, const int32_t (&idx)[8], double (&out)[9]) {
+    const Corr* __restrict__ pts = corr + b * n;
+    double xa[5], ya[5], xb[5], yb[5];
+    Corr q;
+    bool bad = false;
+    load_items(pts, n, idx, xa, ya, xb, yb, q, bad);
+    double best = INFINITY;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) out[i] = NAN;
+    bool degenerate = true;
+    if (!bad) {
+        degenerate = sfm5::solve(xa, ya, xb, yb, [&](const double (&E)[9]) {
+            const double sed = sfm::sed_value(E, q.xa, q.ya, q.xb, q.yb);
+            const bool take = sed < best;
+            best = take ? sed : best;
+#pragma unroll
+            for (int i = 0; i < 9; ++i) out[i] = take ? E[i] : out[i];
+        });
+    }
+    return (bad || degenerate) ? SFM_FIT_DEGENERATE : 0;
+}
+
 }  // namespace sfm5

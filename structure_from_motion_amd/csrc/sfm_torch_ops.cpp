@@ -9,7 +9,7 @@
 // sample_fit_philox_; and the PnP ops (sfm_pnp.hip) pnp_fit, pnp_score and the whole pass pnp_ransac_pass_, their P3P
 // forms p3p_fit and p3p_ransac_pass_ (sfm_p3p.h), the five-point fit five_point_fit and pass five_point_ransac_pass_
 // (sfm_five_point.hip), the homography ops homography_fit, homography_score, homography_inlier_mask and the pass
-// homography_ransac_pass_ (sfm_homography.hip), and the
+// homography_ransac_pass_ (sfm_homography.hip), the ragged two-view pass verify_pairs_ (sfm_view_graph.hip), and the
 // refinement of a winner pnp_refine (sfm_pnp_refine.hip), bundle_adjust (sfm_bundle.hip), triangulate_tracks
 // (sfm_tracks.hip) and build_tracks (sfm_track_build.hip).  The reference call sites these serve: apps/sfm.py:110-119 (RANSAC-E), :133-138 (pose),
 // :181-186 (triangulation).
@@ -525,6 +525,49 @@ void homography_ransac_pass_out(const Tensor& corr, int64_t seed, int64_t seed_s
        "sfm_homography_ransac_pass");
 }
 
+
+// ---- the ragged two-view pass over a match graph (sfm_view_graph.hip): corr [n_total, 4], offset int64 [pairs + 1], min_extra
+// double [pairs]; S [pairs, h, 8], H / E [pairs, h, 9], the score tables [pairs, h], the records int64 [pairs, 5], the masks
+// uint8 [n_total], verdict int64 [pairs, 3] (sfm_pair_verdict) ----------------------------------------------------------
+void verify_pairs_out(const Tensor& corr, const Tensor& offset, const Tensor& min_extra, int64_t seed, int64_t seed_stride,
+                      int64_t h_begin, double thr, int64_t aggregation, double max_ratio, Tensor& S, Tensor& H, Tensor& E,
+                      Tensor& h_flags, Tensor& h_cnt, Tensor& h_s1, Tensor& h_s2, Tensor& e_flags, Tensor& e_cnt, Tensor& e_s1,
+                      Tensor& e_s2, Tensor& h_result, Tensor& e_result, Tensor& h_mask, Tensor& e_mask, Tensor& verdict) {
+    const OpDevice scope(corr);
+    static_assert(sizeof(sfm_pair_verdict) == 24, "verdict rows are three int64");
+    need(corr, "corr", at::kDouble);
+    need(offset, "offset", at::kLong);
+    need(min_extra, "min_extra", at::kDouble);
+    need(S, "S", at::kInt);
+    need(H, "H", at::kDouble);
+    need(E, "E", at::kDouble);
+    for (const Tensor* t : {&h_flags, &h_cnt, &e_flags, &e_cnt}) need(*t, "flags / cnt", at::kInt);
+    for (const Tensor* t : {&h_s1, &h_s2, &e_s1, &e_s2}) need(*t, "s1 / s2", at::kDouble);
+    for (const Tensor* t : {&h_result, &e_result, &verdict}) need(*t, "result / verdict", at::kLong);
+    need(h_mask, "h_mask", at::kByte);
+    need(e_mask, "e_mask", at::kByte);
+    TORCH_CHECK(corr.dim() == 2 && corr.size(1) == 4, "sfm_hip: corr must be [n_total, 4]");
+    TORCH_CHECK(offset.dim() == 1 && offset.size(0) >= 1, "sfm_hip: offset must be int64 [pairs + 1]");
+    const int64_t n_total = corr.size(0), pairs = offset.size(0) - 1;
+    TORCH_CHECK(S.dim() == 3 && S.size(0) == pairs && S.size(2) == 8, "sfm_hip: S must be [pairs, h, 8]");
+    const int64_t h = S.size(1);
+    TORCH_CHECK(min_extra.numel() == pairs, "sfm_hip: min_extra must be [pairs]");
+    TORCH_CHECK(H.numel() == pairs * h * 9 && E.numel() == pairs * h * 9, "sfm_hip: H, E must be [pairs, h, 9]");
+    for (const Tensor* t : {&h_flags, &h_cnt, &h_s1, &h_s2, &e_flags, &e_cnt, &e_s1, &e_s2})
+        TORCH_CHECK(t->numel() == pairs * h, "sfm_hip: flags, cnt, s1, s2 must be [pairs, h]");
+    TORCH_CHECK(h_result.numel() == pairs * kRecordWords && e_result.numel() == pairs * kRecordWords,
+                "sfm_hip: h_result, e_result must be int64 [pairs, 5]");
+    TORCH_CHECK(h_mask.numel() == n_total && e_mask.numel() == n_total, "sfm_hip: h_mask, e_mask must be uint8 [n_total]");
+    TORCH_CHECK(verdict.numel() == pairs * 3, "sfm_hip: verdict must be int64 [pairs, 3]");
+    ok(sfm_verify_pairs((uint64_t)seed, (uint64_t)seed_stride, h_begin, ptr<double>(corr), n_total, ptr<int64_t>(offset), pairs,
+                        ptr<double>(min_extra), h, thr, (int)aggregation, max_ratio, ptr<int32_t>(S), ptr<double>(H), ptr<double>(E),
+                        ptr<int32_t>(h_flags), ptr<int32_t>(h_cnt), ptr<double>(h_s1), ptr<double>(h_s2), ptr<int32_t>(e_flags),
+                        ptr<int32_t>(e_cnt), ptr<double>(e_s1), ptr<double>(e_s2),
+                        reinterpret_cast<sfm_select_result*>(ptr<int64_t>(h_result)),
+                        reinterpret_cast<sfm_select_result*>(ptr<int64_t>(e_result)), ptr<uint8_t>(h_mask), ptr<uint8_t>(e_mask),
+                        reinterpret_cast<sfm_pair_verdict*>(ptr<int64_t>(verdict)), current_stream()),
+       "sfm_verify_pairs");
+}
 
 // ---- PnP (sfm_pnp.hip): pts [batch, n, 5] = {X, Y, Z, u, v}, K 9 doubles (row-major, row 2 = 0 0 1), S [batch, h, 8],
 // model [batch, h, 12] = R (9) | t (3) ----------------------------------------------------------------------------------
@@ -1109,6 +1152,10 @@ TORCH_LIBRARY(sfm_hip, m) {
     m.def("homography_ransac_pass_(Tensor corr, int seed, int seed_stride, bool use_philox, int h_begin, float thr, float min_extra, "
           "int aggregation, Tensor(a!) S, Tensor(b!) H, Tensor(c!) flags, Tensor(d!) cnt, Tensor(e!) s1, Tensor(f!) s2, "
           "Tensor(g!) result, Tensor(h!)? mask) -> ()");
+    m.def("verify_pairs_(Tensor corr, Tensor offset, Tensor min_extra, int seed, int seed_stride, int h_begin, float thr, int aggregation, "
+          "float max_ratio, Tensor(a!) S, Tensor(b!) H, Tensor(c!) E, Tensor(d!) h_flags, Tensor(e!) h_cnt, Tensor(f!) h_s1, "
+          "Tensor(g!) h_s2, Tensor(h!) e_flags, Tensor(i!) e_cnt, Tensor(j!) e_s1, Tensor(k!) e_s2, Tensor(l!) h_result, "
+          "Tensor(m!) e_result, Tensor(n!) h_mask, Tensor(o!) e_mask, Tensor(p!) verdict) -> ()");
     m.def("pnp_fit(Tensor pts, Tensor S, float[] K) -> (Tensor, Tensor)");
     m.def("pnp_fit_(Tensor pts, Tensor S, float[] K, Tensor(a!) model, Tensor(b!) flags) -> ()");
     m.def("p3p_fit(Tensor pts, Tensor S, float[] K) -> (Tensor, Tensor)");
@@ -1181,6 +1228,7 @@ TORCH_LIBRARY_IMPL(sfm_hip, CUDA, m) {
     m.impl("homography_score", &homography_score);
     m.impl("homography_inlier_mask", &homography_inlier_mask);
     m.impl("homography_ransac_pass_", &homography_ransac_pass_out);
+    m.impl("verify_pairs_", &verify_pairs_out);
     m.impl("pnp_fit", &pose_fit_new<pnp_fit_out>);
     m.impl("pnp_fit_", &pnp_fit_out);
     m.impl("pnp_score", &pnp_score);
@@ -1213,6 +1261,9 @@ void normalize_coords_out_meta(const Tensor&, const Tensor&, double, double, dou
 void fit_eight_point_out_meta(const Tensor&, const Tensor&, Tensor&, Tensor&) {}
 void five_point_ransac_pass_out_meta(const Tensor&, int64_t, int64_t, bool, int64_t, double, double, int64_t, Tensor&, Tensor&, Tensor&,
                                      Tensor&, Tensor&, Tensor&, Tensor&, const std::optional<Tensor>&) {}
+void verify_pairs_out_meta(const Tensor&, const Tensor&, const Tensor&, int64_t, int64_t, int64_t, double, int64_t, double, Tensor&,
+                           Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&,
+                           Tensor&, Tensor&, Tensor&) {}
 void sample_fit_philox_out_meta(const Tensor&, int64_t, const std::optional<Tensor>&, int64_t, int64_t, Tensor&, Tensor&,
                                 Tensor&) {}
 void score_sed_out_meta(const Tensor&, const Tensor&, const Tensor&, double, Tensor&, Tensor&, Tensor&,
@@ -1266,6 +1317,7 @@ TORCH_LIBRARY_IMPL(sfm_hip, Meta, m) {
     m.impl("homography_score", &homography_score_meta);
     m.impl("homography_inlier_mask", &homography_inlier_mask_meta);
     m.impl("homography_ransac_pass_", &five_point_ransac_pass_out_meta);
+    m.impl("verify_pairs_", &verify_pairs_out_meta);
     m.impl("pnp_fit", &pnp_fit_meta);
     m.impl("pnp_score", &pnp_score_meta);
     m.impl("pnp_fit_", &pnp_fit_out_meta);

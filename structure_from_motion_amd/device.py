@@ -1059,3 +1059,97 @@ class HomographyWorkspace(_PassWorkspace):
     def outcome(self, b: int = 0) -> HomographyOutcome:
         best_h, error, m, *rest = self._winner(b)
         return HomographyOutcome(best_h, error, None if m is None else m.reshape(3, 3).copy(), *rest)
+
+
+# ------------------------------------------------------------------------------------------------------
+# Two-view verification of every pair of a match graph in one call (csrc/sfm_view_graph.hip): corr [N,4], the
+# pairs' K-normalised correspondences concatenated; offset int64 [Q+1]; per pair the homography pass and the five-point pass
+# ------------------------------------------------------------------------------------------------------
+PAIR_NONE, PAIR_ESSENTIAL, PAIR_HOMOGRAPHY, PAIR_BAD_OFFSETS = range(4)
+PAIR_KINDS = _native.PAIR_KINDS
+VERDICT_BYTES = C.sizeof(_native.PairVerdict)
+
+
+@dataclass
+class ViewGraphOutcome:
+    """What a ``ViewGraphWorkspace`` holds after a call, on the host: one row per pair."""
+    kind: np.ndarray               # (Q,) int32, PAIR_*
+    homography_count: np.ndarray   # (Q,) int32: the winner's sample size plus its extra inliers, 0 without a winner
+    essential_count: np.ndarray    # (Q,) int32
+    ratio: np.ndarray              # (Q,) homography_count / essential_count, inf when the latter is 0
+    H: np.ndarray                  # (Q, 3, 3), NaN where there is no homography
+    E: np.ndarray                  # (Q, 3, 3), NaN where there is no essential matrix
+    homography_best: np.ndarray    # (Q,) int64 winning hypothesis of the pair, -1 if none
+    essential_best: np.ndarray     # (Q,) int64
+    homography_sample: np.ndarray  # (Q, 4) int64 items of the winner's sample (local to the pair), -1 without a winner
+    essential_sample: np.ndarray   # (Q, 6) int64
+    homography_mask: np.ndarray    # (N,) uint8: 2 sample item of its pair's winner, 1 other inlier, 0 otherwise
+    essential_mask: np.ndarray     # (N,) uint8
+
+
+class ViewGraphWorkspace:
+    """Pre-allocated device buffers of ``sfm_verify_pairs`` for Q pairs x H hypotheses over N items in all (about 224 bytes
+    per pair-hypothesis), and the decoding of what a call leaves in them."""
+
+    def __init__(self, pairs: int, n_total: int, h: int, device=None):
+        dev = device or require_gpu()
+        self.pairs, self.n_total, self.h = pairs, n_total, h
+        i32, f64 = dict(dtype=torch.int32, device=dev), dict(dtype=F64, device=dev)
+        self.S = torch.empty((pairs, h, 8), **i32)
+        self.H = torch.empty((pairs, h, 9), **f64)
+        self.E = torch.empty((pairs, h, 9), **f64)
+        self.h_flags, self.h_cnt = torch.empty((pairs, h), **i32), torch.empty((pairs, h), **i32)
+        self.h_s1, self.h_s2 = torch.empty((pairs, h), **f64), torch.empty((pairs, h), **f64)
+        self.e_flags, self.e_cnt = torch.empty((pairs, h), **i32), torch.empty((pairs, h), **i32)
+        self.e_s1, self.e_s2 = torch.empty((pairs, h), **f64), torch.empty((pairs, h), **f64)
+        self.h_result = torch.empty((pairs, SELECT_BYTES // 8), dtype=torch.int64, device=dev)
+        self.e_result = torch.empty((pairs, SELECT_BYTES // 8), dtype=torch.int64, device=dev)
+        self.h_mask = torch.empty((n_total,), dtype=torch.uint8, device=dev)
+        self.e_mask = torch.empty((n_total,), dtype=torch.uint8, device=dev)
+        self.verdict = torch.empty((pairs, VERDICT_BYTES // 8), dtype=torch.int64, device=dev)
+
+    def buffers(self):
+        """The output tensors in the order of the ``verify_pairs_`` op."""
+        return (self.S, self.H, self.E, self.h_flags, self.h_cnt, self.h_s1, self.h_s2, self.e_flags, self.e_cnt, self.e_s1,
+                self.e_s2, self.h_result, self.e_result, self.h_mask, self.e_mask, self.verdict)
+
+    def run(self, corr: torch.Tensor, offset: torch.Tensor, min_extra: torch.Tensor, thr: float, aggregation: int,
+            max_ratio: float, seed: int, seed_stride: int = 1, h_begin: int = 0) -> None:
+        """One ``sfm_verify_pairs`` call (the ``verify_pairs_`` op), enqueue-only: corr f64 [N,4], offset int64 [Q+1],
+        min_extra f64 [Q] on the device; pair q draws its Philox samples with ``seed + q * seed_stride``."""
+        ops.load().verify_pairs_(corr, offset, min_extra, _as_int64(seed), _as_int64(seed_stride), int(h_begin), float(thr),
+                                 int(aggregation), float(max_ratio), *self.buffers())
+
+    def read_verdicts(self) -> List["_native.PairVerdict"]:
+        """Copy the verdict records to the host (synchronises)."""
+        raw = self.verdict.cpu().numpy().tobytes()
+        return [_native.PairVerdict.from_buffer_copy(raw[i * VERDICT_BYTES:(i + 1) * VERDICT_BYTES]) for i in range(self.pairs)]
+
+    def outcome(self) -> ViewGraphOutcome:
+        """Verdicts, winners and masks on the host (synchronises); the winners' rows are gathered on the device first."""
+        Q = self.pairs
+        verdicts = self.read_verdicts()
+        rows = torch.arange(Q, device=self.S.device)
+        out = {}
+        for name, result, model, size in (("homography", self.h_result, self.H, 4), ("essential", self.e_result, self.E, 6)):
+            best = result[:, 1]
+            if self.h:
+                at = best.clamp(min=0)
+                m = model[rows, at].cpu().numpy().reshape(Q, 3, 3).copy()
+                smp = self.S[rows, at, :size].cpu().numpy().astype(np.int64)
+            else:
+                m, smp = np.empty((Q, 3, 3)), np.empty((Q, size), dtype=np.int64)
+            best = best.cpu().numpy()
+            m[best < 0] = np.nan
+            smp[best < 0] = -1
+            out[name] = (m, best, smp)
+        return ViewGraphOutcome(
+            kind=np.array([v.kind for v in verdicts], dtype=np.int32),
+            homography_count=np.array([v.homography_count for v in verdicts], dtype=np.int32),
+            essential_count=np.array([v.essential_count for v in verdicts], dtype=np.int32),
+            ratio=np.array([v.ratio for v in verdicts], dtype=np.float64),
+            H=out["homography"][0], E=out["essential"][0],
+            homography_best=out["homography"][1], essential_best=out["essential"][1],
+            homography_sample=out["homography"][2], essential_sample=out["essential"][2],
+            homography_mask=checked_mask(self.h_mask.cpu().numpy().copy()),
+            essential_mask=checked_mask(self.e_mask.cpu().numpy().copy()))

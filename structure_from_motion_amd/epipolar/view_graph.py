@@ -1,0 +1,170 @@
+"""Two-view verification of every image pair of a match graph in one device call: per pair the RANSAC
+homography, the RANSAC five-point essential matrix on the same samples, both inlier lists and which of the two explains the
+pair — what ``homography.select_two_view_model`` answers for one pair, for all pairs of ``build_tracks``'s input at once
+(csrc/sfm_view_graph.hip, ``device.ViewGraphWorkspace``).  ``choose_seed_pair`` then picks the pair a reconstruction should
+start from: a pure rotation or a plane fits an essential matrix to every match and would win on the essential count alone."""
+from __future__ import annotations
+
+import os
+import random
+from typing import List, NamedTuple, Sequence
+
+import numpy as np
+import numpy.typing as npt
+
+from ..multiview.tracks import _feature_pixels, _pair_matches
+from ..ransac.ransac import DEFAULT_MAX_ITERATIONS, ErrorAggregationMethod, aggregation_code
+from .homography import MAX_HOMOGRAPHY_RATIO, check_camera_matrix
+
+MAX_PAIRS_PER_CALL = 65535          # the grid's y extent: one sfm_verify_pairs call takes no more
+BYTES_PER_PAIR_HYPOTHESIS = 224     # S 32, H and E 72 each, two sets of flags / cnt / s1 / s2 at 24
+
+
+class ViewGraph(NamedTuple):
+    pairs: npt.NDArray                 # (Q, 2) image indices, as given
+    kind: List[str]                    # per pair "essential", "homography" or "none"
+    E: npt.NDArray                     # (Q, 3, 3), NaN where no essential matrix has enough inliers
+    H: npt.NDArray                     # (Q, 3, 3), NaN where no homography has enough inliers
+    essential_count: npt.NDArray       # (Q,) the winner's sample size plus its extra inliers, 0 without a winner
+    homography_count: npt.NDArray      # (Q,)
+    ratio: npt.NDArray                 # (Q,) homography_count / essential_count, inf when essential_count is 0
+    essential_inliers: List[npt.NDArray]    # per pair (k, 2) rows of matches[q]: the sample first, then the survivors by index
+    homography_inliers: List[npt.NDArray]
+    inlier_matches: List[npt.NDArray]  # per pair the inliers of the model its kind names ((0, 2) for "none"): build_tracks's input
+
+
+def pair_min_extra(counts, min_num_extra_inliers=None, min_extra_fraction: float = 0.0) -> npt.NDArray:
+    """The gate of each pair: ``max(min_num_extra_inliers (an int or one per pair), floor(min_extra_fraction * n_q))``."""
+    counts = np.asarray(counts, dtype=np.int64)
+    fraction = float(min_extra_fraction)
+    if not (np.isfinite(fraction) and fraction >= 0.0):
+        raise ValueError(f"min_extra_fraction must be finite and >= 0, got {min_extra_fraction!r}")
+    given = np.zeros(len(counts), dtype=np.int64) if min_num_extra_inliers is None else np.asarray(min_num_extra_inliers)
+    if given.ndim == 0:
+        given = np.full(len(counts), given)
+    if given.shape != counts.shape or not np.issubdtype(given.dtype, np.integer):
+        raise ValueError(f"min_num_extra_inliers must be an int or one int per pair ({len(counts)})")
+    return np.maximum(given.astype(np.int64), np.floor(fraction * counts).astype(np.int64))
+
+
+def chunk_bounds(pairs: int, iterations: int, max_hypotheses_per_call: int) -> List[tuple]:
+    """``[(q0, q1), ...]``: the pairs of each device call, at most ``max_hypotheses_per_call // iterations`` (at least one, at
+    most 65 535) pairs each — the buffers of a call take about 224 bytes per pair-hypothesis."""
+    if max_hypotheses_per_call < 1:
+        raise ValueError(f"max_hypotheses_per_call must be positive, got {max_hypotheses_per_call!r}")
+    per_call = MAX_PAIRS_PER_CALL if iterations <= 0 else min(MAX_PAIRS_PER_CALL, max(1, max_hypotheses_per_call // iterations))
+    return [(q0, min(q0 + per_call, pairs)) for q0 in range(0, pairs, per_call)]
+
+
+def _checked_graph(features: Sequence, pairs, matches: Sequence):
+    """The checks of ``build_tracks`` on the same three arguments -> (pixels per image, (Q, 2) pairs, (n_q, 2) matches per pair)."""
+    feats = [_feature_pixels(f, i) for i, f in enumerate(features)]
+    pair_arr = np.asarray(pairs)
+    if pair_arr.size == 0:
+        pair_arr = np.zeros((0, 2), dtype=np.int64)
+    if pair_arr.ndim != 2 or pair_arr.shape[1] != 2:
+        raise ValueError(f"pairs must have shape (Q, 2), got {pair_arr.shape}")
+    if not np.issubdtype(pair_arr.dtype, np.integer):
+        raise ValueError(f"pairs must hold integers, got {pair_arr.dtype}")
+    Q = pair_arr.shape[0]
+    if len(matches) != Q:
+        raise ValueError(f"matches must hold one entry per pair ({Q}), got {len(matches)}")
+    if Q and (pair_arr.min() < 0 or pair_arr.max() >= len(feats)):
+        raise ValueError(f"pairs must index images 0 .. {len(feats) - 1}")
+    if Q and np.any(pair_arr[:, 0] == pair_arr[:, 1]):
+        raise ValueError("a pair must join two different images")
+    per_pair = [_pair_matches(m, q) for q, m in enumerate(matches)]
+    if sum(len(m) for m in per_pair) >= 2**31:
+        raise ValueError("matches must number fewer than 2^31")
+    for (i, j), m in zip(pair_arr.tolist(), per_pair):
+        if len(m) and (m.min() < 0 or m[:, 0].max() >= len(feats[i]) or m[:, 1].max() >= len(feats[j])):
+            raise ValueError("a match indexes a feature outside its image")
+    return feats, pair_arr.astype(np.int64), per_pair
+
+
+def verify_pairs(camera_matrix, features: Sequence, pairs, matches: Sequence, inlier_threshold: float,
+                 min_num_extra_inliers=None, min_extra_fraction: float = 0.0, max_iterations: int | None = None,
+                 max_homography_ratio: float = MAX_HOMOGRAPHY_RATIO, seed: int | None = None,
+                 max_hypotheses_per_call: int = 2**21) -> ViewGraph:
+    """Verify all Q pairs of a match graph: ``features``, ``pairs`` and ``matches`` exactly as ``build_tracks`` takes them.
+
+    Per pair, ``max_iterations`` Philox samples serve a homography pass (their first four items) and a five-point essential
+    pass (their first six), both with ``inlier_threshold`` in K-normalised units, the RMS aggregation and the gate
+    ``max(min_num_extra_inliers, floor(min_extra_fraction * n_q))`` (``min_num_extra_inliers``: an int or one per pair);
+    degenerate samples never compete and never raise.  The kind of a pair is ``"none"`` when neither model has a winner,
+    ``"homography"`` when E has none or ``homography_count / essential_count > max_homography_ratio``, else
+    ``"essential"``.  A pair with fewer than four matches has no model, one with four or five a homography at most.
+
+    Pair q draws its samples with ``seed + q`` (``seed``, else ``SFM_SEED``, else 64 bits of ``random``), so the result
+    does not depend on how the pairs are split into device calls (``max_hypotheses_per_call`` pair-hypotheses each).  One
+    upload and one normalisation serve all pairs.  Every argument is checked before any device work (``ValueError``)."""
+    K = check_camera_matrix(camera_matrix)
+    feats, pair_arr, per_pair = _checked_graph(features, pairs, matches)
+    Q = len(per_pair)
+    counts = np.array([len(m) for m in per_pair], dtype=np.int64)
+    gate = pair_min_extra(counts, min_num_extra_inliers, min_extra_fraction)
+    iterations = DEFAULT_MAX_ITERATIONS if max_iterations is None else int(max_iterations)
+    chunks = chunk_bounds(Q, iterations, max_hypotheses_per_call)
+    if seed is None:
+        seed = int(os.environ["SFM_SEED"]) if "SFM_SEED" in os.environ else random.getrandbits(64)
+    empty = np.zeros((0, 2), dtype=np.int64)
+    if Q == 0:
+        none = np.zeros((0, 3, 3))
+        return ViewGraph(pair_arr, [], none, none.copy(), np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0), [], [], [])
+    import torch
+
+    from .. import device
+
+    dev = device.require_gpu()
+    offset = np.zeros(Q + 1, dtype=np.int64)
+    offset[1:] = np.cumsum(counts)
+    pix = np.empty((2, int(offset[-1]), 2))
+    for q, ((i, j), m) in enumerate(zip(pair_arr.tolist(), per_pair)):
+        pix[0, offset[q]:offset[q + 1]] = feats[i][m[:, 0]]
+        pix[1, offset[q]:offset[q + 1]] = feats[j][m[:, 1]]
+    pix = device.to_device(pix)   # one upload: [2, N, 2]
+    corr = device.normalize_correspondences(pix[0], pix[1], K)
+    offset_dev = device.to_device(offset, torch.int64)
+    gate_dev = device.to_device(gate.astype(np.float64))
+    aggregation = aggregation_code(ErrorAggregationMethod.RMS)
+    outcomes = []
+    for q0, q1 in chunks:
+        lo, hi = int(offset[q0]), int(offset[q1])
+        ws = device.ViewGraphWorkspace(q1 - q0, hi - lo, max(iterations, 0), dev)
+        ws.run(corr[lo:hi], offset_dev[q0:q1 + 1] - lo, gate_dev[q0:q1], inlier_threshold, aggregation, max_homography_ratio,
+               seed + q0, seed_stride=1)
+        outcomes.append(ws.outcome())
+    cat = lambda name: np.concatenate([getattr(o, name) for o in outcomes])   # noqa: E731
+    code, h_mask, e_mask = cat("kind"), cat("homography_mask"), cat("essential_mask")
+    if np.any(code == device.PAIR_BAD_OFFSETS):
+        raise RuntimeError("verify_pairs: the device refused the offset table (SFM_PAIR_BAD_OFFSETS)")
+    h_sample, e_sample = cat("homography_sample"), cat("essential_sample")
+
+    def inliers(q, sample, mask):
+        if sample[q, 0] < 0:
+            return empty
+        survivors = np.nonzero(mask[offset[q]:offset[q + 1]] == 1)[0]
+        return per_pair[q][np.concatenate([sample[q], survivors])]
+
+    h_in = [inliers(q, h_sample, h_mask) for q in range(Q)]
+    e_in = [inliers(q, e_sample, e_mask) for q in range(Q)]
+    kind = [device.PAIR_KINDS[c] for c in code]
+    chosen = [e_in[q] if kind[q] == "essential" else (h_in[q] if kind[q] == "homography" else empty) for q in range(Q)]
+    return ViewGraph(pair_arr, kind, cat("E"), cat("H"), cat("essential_count").astype(np.int64),
+                     cat("homography_count").astype(np.int64), cat("ratio"), e_in, h_in, chosen)
+
+
+def choose_seed_pair(graph: ViewGraph, min_count: int = 0) -> int:
+    """The pair a reconstruction should start from: among the pairs of kind ``"essential"`` with ``essential_count >=
+    min_count`` the one with the largest ``essential_count``; ties go to the lower ratio, then to the lower index.
+    ``ValueError`` when there is none."""
+    best = None
+    for q, kind in enumerate(graph.kind):
+        if kind != "essential" or graph.essential_count[q] < min_count:
+            continue
+        key = (-int(graph.essential_count[q]), float(graph.ratio[q]), q)
+        if best is None or key < best:
+            best = key
+    if best is None:
+        raise ValueError("no pair of kind 'essential' with enough inliers")
+    return best[2]
