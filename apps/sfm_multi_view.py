@@ -17,7 +17,12 @@ tracks, and the same reconstruction runs on the built observations.  The output 
 fraction of OK tracks whose features all belong to one true point.  ``verify="batched"`` (``--verify batched``) verifies all
 pairs in one ``verify_pairs`` call instead of one essential-matrix RANSAC per pair: a homography and a five-point essential
 pass per pair, the pairs whose kind is not ``"none"`` kept with the inliers of the model their kind names, and the number of
-pairs of each kind added to the output.
+pairs of each kind added to the output.  ``seed_pair="auto"`` (``--seed-pair auto``, with ``--tracks matches --verify batched``)
+starts from the pair ``choose_seed_pair`` picks among the verified pairs, gated on the median triangulation angle of its
+inliers (``--seed-min-angle`` degrees), instead of from views 0 and 1: the pair's pose comes from the same ``verify_pairs``
+call (``relative_pose=True``), its first view sits at the identity, and the errors are reported in that gauge (the true poses
+relative to that view, in units of the pair's true baseline).  The output then also holds ``seed_pair`` and the pair's
+``median_angle_deg``.
 
 ``bundle_loss`` (``--bundle-loss``) gives every bundle adjustment a robust loss (``"huber"`` or ``"cauchy"`` with
 ``bundle_loss_scale`` pixels); the drop rules stay as they are, and ``rms_px`` is then computed from the
@@ -39,7 +44,7 @@ from lib.bundle.bundle import bundle_adjust
 from lib.common.feature import Feature
 from lib.epipolar.eight_point import create_trivial_matches, recover_r_t_from_e
 from lib.epipolar.epipolar_ransac import estimate_essential_mat_with_ransac
-from lib.epipolar.view_graph import verify_pairs
+from lib.epipolar.view_graph import choose_seed_pair, verify_pairs
 from lib.feature_matching.matching import Match
 from lib.multiview.tracks import build_tracks, triangulate_tracks
 from lib.pnp.pnp import estimate_pose_pnp_with_ransac
@@ -51,6 +56,7 @@ BUNDLE_SOLVERS = ("dense", "auto")
 BUNDLE_LOSSES = device.BUNDLE_LOSSES
 TRACK_SOURCES = ("given", "matches")
 VERIFY_ROUTES = ("loop", "batched")
+SEED_PAIRS = ("first", "auto")
 MIN_PNP_INLIERS = 30
 
 
@@ -169,17 +175,20 @@ def _verified_matches(K, pix_a, pix_b, m, sed_threshold: float, iterations: int,
     return m[device.checked_mask(outcome.mask) > 0]
 
 
-def tracks_from_matches(scene, sed_threshold: float, iterations: int, e_solver: str, seed: int, verify: str = "loop"):
+def tracks_from_matches(scene, sed_threshold: float, iterations: int, e_solver: str, seed: int, verify: str = "loop",
+                        relative_pose: bool = False):
     """The scene's tracks rebuilt from verified pairwise matches: (scene with the built camera_indices, point_indices and
     pixels, the build's info, the fraction of OK tracks whose features all belong to one true point, pairs kept, and with
-    ``verify="batched"`` the number of pairs of each kind, else None)."""
+    ``verify="batched"`` the number of pairs of each kind and the ``ViewGraph`` (with poses if ``relative_pose``), else None
+    twice)."""
     K = scene["K"]
     random.seed(seed)   # the pairs' RANSAC samples
     pm = synthetic.pairwise_matches(scene, seed=seed)
-    pairs, kept, kinds = [], [], None
+    pairs, kept, kinds, graph = [], [], None, None
     if verify == "batched":
+        pose = dict(relative_pose=True) if relative_pose else {}
         graph = verify_pairs(K, pm["features"], pm["pairs"], pm["matches"], sed_threshold, min_extra_fraction=0.4,
-                             max_iterations=iterations)
+                             max_iterations=iterations, **pose)
         kinds = {kind: graph.kind.count(kind) for kind in ("essential", "homography", "none")}
         for (i, j), kind, inliers in zip(pm["pairs"], graph.kind, graph.inlier_matches):
             if kind != "none":   # a pair without a model is dropped
@@ -200,14 +209,15 @@ def tracks_from_matches(scene, sed_threshold: float, iterations: int, e_solver: 
     np.maximum.at(hi, r.point_indices, truth)
     pure = float(np.mean(lo == hi)) if r.info.tracks else float("nan")
     built = dict(scene, camera_indices=r.camera_indices, point_indices=r.point_indices, pixels=r.pixels)
-    return built, r.info, pure, len(pairs), kinds
+    return built, r.info, pure, len(pairs), kinds, graph
 
 
 def run(views: int = 8, points: int = 2000, seed: int = 21, noise_px: float = 0.5, outlier_fraction: float = 0.2,
         sed_threshold: float = 6e-6, reprojection_threshold: float = 16.0, iterations: int = 2000, refine_steps: int = 10,
         ba_steps: int = 20, final_ba_steps: int = 50, step_deg: float = 5.0, bundle_solver: str = "dense",
         details: bool = False, pnp_solver: str = "dlt", e_solver: str = "eight_point", tracks: str = "given",
-        bundle_loss: str = "squared", bundle_loss_scale: float = 2.0, verify: str = "loop") -> dict:
+        bundle_loss: str = "squared", bundle_loss_scale: float = 2.0, verify: str = "loop", seed_pair: str = "first",
+        seed_min_angle_deg: float = 2.0) -> dict:
     if pnp_solver not in ("dlt", "p3p"):
         raise ValueError(f"pnp_solver must be 'dlt' or 'p3p', got {pnp_solver!r}")
     if e_solver not in ("eight_point", "five_point"):
@@ -216,6 +226,11 @@ def run(views: int = 8, points: int = 2000, seed: int = 21, noise_px: float = 0.
         raise ValueError(f"tracks must be one of {TRACK_SOURCES}, got {tracks!r}")
     if verify not in VERIFY_ROUTES:
         raise ValueError(f"verify must be one of {VERIFY_ROUTES}, got {verify!r}")
+    if seed_pair not in SEED_PAIRS:
+        raise ValueError(f"seed_pair must be one of {SEED_PAIRS}, got {seed_pair!r}")
+    auto_seed = seed_pair == "auto"
+    if auto_seed and not (tracks == "matches" and verify == "batched"):
+        raise ValueError("seed_pair='auto' needs tracks='matches' and verify='batched'")
     if bundle_solver not in BUNDLE_SOLVERS:
         raise ValueError(f"bundle_solver must be one of {BUNDLE_SOLVERS}, got {bundle_solver!r}")
     if bundle_loss not in BUNDLE_LOSSES:
@@ -226,9 +241,10 @@ def run(views: int = 8, points: int = 2000, seed: int = 21, noise_px: float = 0.
     if not 2 <= views <= limit:
         raise ValueError(f"between 2 and {limit} views are supported with bundle_solver={bundle_solver!r}, got {views}")
     scene = synthetic.multi_view_scene(views, points, seed, noise_px, outlier_fraction, step_deg=step_deg)
-    build = None
+    build, graph = None, None
     if tracks == "matches":
-        scene, build_info, pure, kept_pairs, kinds = tracks_from_matches(scene, sed_threshold, iterations, e_solver, seed, verify)
+        scene, build_info, pure, kept_pairs, kinds, graph = tracks_from_matches(scene, sed_threshold, iterations, e_solver, seed,
+                                                                                verify, relative_pose=auto_seed)
         build = dict(pairs_kept=kept_pairs, components=build_info.components, tracks=build_info.tracks,
                      observations=build_info.observations, conflicts=build_info.conflicts,
                      unmatched=build_info.unmatched, pure_track_fraction=pure)
@@ -240,37 +256,46 @@ def run(views: int = 8, points: int = 2000, seed: int = 21, noise_px: float = 0.
     cam, pt, uv = rec.cam, rec.pt, rec.uv
     random.seed(seed)
 
-    # 1. seed on views 0 and 1
+    # 1. seed on views 0 and 1, or on the pair the view graph recommends
+    va, vb, seed_q = 0, 1, None
+    if auto_seed:
+        seed_q = choose_seed_pair(graph, min_count=MIN_PNP_INLIERS, min_angle_deg=seed_min_angle_deg)
+        va, vb = (int(v) for v in graph.pairs[seed_q])
     in0 = np.full(rec.P, -1)
     in1 = np.full(rec.P, -1)
-    in0[pt[cam == 0]] = np.nonzero(cam == 0)[0]
-    in1[pt[cam == 1]] = np.nonzero(cam == 1)[0]
+    in0[pt[cam == va]] = np.nonzero(cam == va)[0]
+    in1[pt[cam == vb]] = np.nonzero(cam == vb)[0]
     both = np.nonzero((in0 >= 0) & (in1 >= 0))[0]
-    fa = [Feature(float(x), float(y)) for x, y in uv[in0[both]]]
-    fb = [Feature(float(x), float(y)) for x, y in uv[in1[both]]]
-    # RANSAC keeps the lowest-error model among those with enough extra inliers: asking for 40 % of the pairs keeps a
-    # model fitted to a few outliers from winning (about 64 % of the pairs are clean at 20 % outliers per view)
-    e, pairs = estimate_essential_mat_with_ransac(K, fa, fb, create_trivial_matches(len(both)),
-                                                  sed_inlier_threshold=sed_threshold,
-                                                  min_num_extra_inliers=int(0.4 * len(both)), max_iterations=iterations,
-                                                  solver=e_solver)
-    R1, t1, _ = recover_r_t_from_e(e, K, [p[0] for p in pairs], [p[1] for p in pairs])
-    rec.poses[0] = _pose(np.eye(3), np.zeros(3))
-    rec.poses[1] = _pose(R1, t1)
-    rec.registered = [0, 1]
+    if auto_seed:
+        # the pair's pose is the one its inliers voted for in the verify_pairs call; the tracks through both views were built
+        # from verified matches, so all of them start the reconstruction
+        R1, t1, kept = graph.pose.R[seed_q], graph.pose.t[seed_q], both
+    else:
+        fa = [Feature(float(x), float(y)) for x, y in uv[in0[both]]]
+        fb = [Feature(float(x), float(y)) for x, y in uv[in1[both]]]
+        # RANSAC keeps the lowest-error model among those with enough extra inliers: asking for 40 % of the pairs keeps a
+        # model fitted to a few outliers from winning (about 64 % of the pairs are clean at 20 % outliers per view)
+        e, pairs = estimate_essential_mat_with_ransac(K, fa, fb, create_trivial_matches(len(both)),
+                                                      sed_inlier_threshold=sed_threshold,
+                                                      min_num_extra_inliers=int(0.4 * len(both)), max_iterations=iterations,
+                                                      solver=e_solver)
+        R1, t1, _ = recover_r_t_from_e(e, K, [p[0] for p in pairs], [p[1] for p in pairs])
+        index_of = {(f.x, f.y): k for k, f in enumerate(fa)}
+        kept = both[sorted(index_of[(p[0].x, p[0].y)] for p in pairs)]
+    rec.poses[va] = _pose(np.eye(3), np.zeros(3))
+    rec.poses[vb] = _pose(R1, t1)
+    rec.registered = [va, vb]
     # The RANSAC winner is a minimal fit to one sample: with 5 degrees between the views its pose can be off by a few
     # hundredths of a radian, enough to push most two-view points over the threshold.  So the pairs E keeps are triangulated
-    # without the error check first and views 0-1 are adjusted on them; then every track is triangulated with the checks.
-    index_of = {(f.x, f.y): k for k, f in enumerate(fa)}
-    kept = both[sorted(index_of[(p[0].x, p[0].y)] for p in pairs)]
-    seed = np.nonzero(np.isin(pt, kept) & (cam <= 1))[0]
+    # without the error check first and the two views are adjusted on them; then every track is triangulated with the checks.
+    seed = np.nonzero(np.isin(pt, kept) & ((cam == va) | (cam == vb)))[0]
     r = triangulate_tracks(K, rec.poses, cam[seed], pt[seed], uv[seed], num_points=rec.P, min_angle_deg=1.0,
                            refine_steps=refine_steps)
     rec.X, rec.status = r.points, np.where(r.status == device.TRACKS_LARGE_ERROR, device.TRACKS_OK, r.status)
     rec.adjust(final_ba_steps, drop=False)
     rec.status[:] = device.TRACKS_FEW_VIEWS
     rec.triangulate(rec.pending())
-    log = [dict(view=1, points_ok=int(np.count_nonzero(rec.status == device.TRACKS_OK)))]
+    log = [dict(view=vb, points_ok=int(np.count_nonzero(rec.status == device.TRACKS_OK)))]
 
     # 2.-4. register the view with the most observations of OK points, triangulate, adjust
     while len(rec.registered) < views:
@@ -307,7 +332,11 @@ def run(views: int = 8, points: int = 2000, seed: int = 21, noise_px: float = 0.
         a = rec.adjusted
         sum_sq = float(np.sum(_errors(K, rec.poses, rec.X, cam[a], pt[a], uv[a])))
     truth = scene["poses_true"]
-    scale = float(np.linalg.norm(truth[1, 9:]))
+    if auto_seed:   # the gauge of the seed: the true poses relative to view va, in units of the pair's true baseline
+        Ra, ta = truth[va, :9].reshape(3, 3), truth[va, 9:]
+        Rv = np.einsum("vij,kj->vik", truth[:, :9].reshape(-1, 3, 3), Ra)   # R_v Ra^T
+        truth = np.hstack([Rv.reshape(-1, 9), truth[:, 9:] - Rv @ ta])
+    scale = float(np.linalg.norm(truth[vb, 9:]))
     rot_err = {int(v): rotation_angle(rec.poses[v, :9].reshape(3, 3), truth[v, :9].reshape(3, 3)) for v in rec.registered}
     t_err = {int(v): float(np.linalg.norm(rec.poses[v, 9:] - truth[v, 9:] / scale)) for v in rec.registered}
     out = {
@@ -325,8 +354,13 @@ def run(views: int = 8, points: int = 2000, seed: int = 21, noise_px: float = 0.
     }
     if build is not None:
         out["track_build"] = build
+    if auto_seed:
+        out["seed_pair"] = [va, vb]
+        out["median_angle_deg"] = float(graph.pose.median_angle_deg[seed_q])
     if details:
         out["_scene"], out["_status"] = scene, rec.status.copy()
+        if graph is not None:
+            out["_graph"] = graph
     return out
 
 
@@ -358,6 +392,11 @@ def main():
     ap.add_argument("--verify", choices=VERIFY_ROUTES, default="loop",
                     help="with --tracks matches: loop: one essential-matrix RANSAC per pair; batched: all pairs in one "
                          "verify_pairs call (homography and five-point essential per pair)")
+    ap.add_argument("--seed-pair", choices=SEED_PAIRS, default="first",
+                    help="first: seed on views 0 and 1; auto (with --tracks matches --verify batched): on the pair the view "
+                         "graph recommends")
+    ap.add_argument("--seed-min-angle", type=float, default=2.0,
+                    help="with --seed-pair auto: least median triangulation angle of the seed pair's inliers, in degrees")
     ap.add_argument("--e-solver", choices=("eight_point", "five_point"), default="eight_point",
                     help="minimal solver of the two-view seed: eight-point, or five-point on six-item samples")
     ap.add_argument("--bundle-loss", choices=BUNDLE_LOSSES, default="squared",
@@ -367,11 +406,14 @@ def main():
     limit = DENSE_MAX_VIEWS if args.bundle_solver == "dense" else MAX_VIEWS
     if not 2 <= args.views <= limit:
         ap.error(f"--views must be between 2 and {limit} with --bundle-solver {args.bundle_solver}")
+    if args.seed_pair == "auto" and not (args.tracks == "matches" and args.verify == "batched"):
+        ap.error("--seed-pair auto needs --tracks matches --verify batched")
     print(json.dumps(run(args.views, args.points, args.seed, args.noise, args.outliers, sed_threshold=args.sed_threshold,
                          reprojection_threshold=args.reprojection_threshold, refine_steps=args.refine_steps,
                          step_deg=args.step_deg, bundle_solver=args.bundle_solver, pnp_solver=args.pnp_solver,
                          e_solver=args.e_solver, tracks=args.tracks, bundle_loss=args.bundle_loss,
-                         bundle_loss_scale=args.bundle_loss_scale, verify=args.verify)))
+                         bundle_loss_scale=args.bundle_loss_scale, verify=args.verify, seed_pair=args.seed_pair,
+                         seed_min_angle_deg=args.seed_min_angle)))
 
 
 if __name__ == "__main__":

@@ -451,6 +451,50 @@ int sfm_verify_pairs(uint64_t seed, uint64_t seed_stride, int64_t h_begin, const
                      double* h_s2, int32_t* e_flags, int32_t* e_cnt, double* e_s1, double* e_s2, sfm_select_result* h_result,
                      sfm_select_result* e_result, uint8_t* h_mask, uint8_t* e_mask, sfm_pair_verdict* verdict, void* stream);
 
+/* ---- relative pose and triangulation angle of every pair, behind sfm_verify_pairs on that call's buffers
+ * (csrc/sfm_view_graph_pose.hip; an extension, added under ABI 15) ----
+ * corr, offset, E, e_result, e_mask, verdict: as sfm_verify_pairs took and left them.  Per pair q with an essential winner
+ * (whatever its kind), E_q = E[q, e_result[q].best_h]:
+ *   candidates  the four poses of sfm_decompose_essential(E_q), bit for bit, order (R1,t), (R1,-t), (R2,t), (R2,-t);
+ *   items       those of pair q with e_mask != 0 (the sample and the survivors; none is skipped);
+ *   cheirality  sfm_cheirality_batched's rule: DLT with P1 = [I|0], P2 = [R|t]; an item passes iff X[2] >= -1e-8 and
+ *               z2 >= -1e-8 and |X| <= distance_threshold; NaN fails;
+ *   votes[p]    the passing items of candidate p; best = the first maximum, -1 when all are zero;
+ *   angle       of an item under the best R, each operation rounded on its own: a = (xa, ya, 1), c = R^T (xb, yb, 1) with
+ *               c_j = (R[0][j] xb + R[1][j] yb) + R[2][j], w = a x c, atan2(sqrt((w0^2 + w1^2) + w2^2), (a0 c0 + a1 c1) + a2 c2);
+ *   median      the lower median of the angles of the k = votes[best] items passing under the best pose: the element of
+ *               rank (k - 1) / 2 in ascending order, selected exactly (a bit pattern of one of the angles).
+ * Every byte of pose[q] is written for every q.  Unless status is SFM_POSE_OK, R, t and median_angle are NaN, best is -1 and
+ * votes are 0.  workspace: dev, sfm_pair_poses_workspace_bytes(n_total, pairs) bytes (-1 for sizes the call refuses); after
+ * the call its first n_total doubles hold each item's angle under its pair's best pose, NaN for an item that is not a passing
+ * inlier of a pair with status SFM_POSE_OK.
+ * Three launches whatever `pairs` is, nothing read back; every size and pointer is checked before the first launch
+ * (pairs <= 65535, n_total < 2^31, h_count >= 1, the workspace size); pairs == 0 is a no-op that writes nothing, the angles
+ * of the workspace included, whatever n_total is.  No global and no floating-point atomics: a call is reproducible bit for bit.
+ * Nothing is indexed through an offset table marked SFM_PAIR_BAD_OFFSETS. */
+#define SFM_POSE_OK 0
+#define SFM_POSE_NO_MODEL 1      /* the pair has no essential winner (e_result[q].best_h < 0) */
+#define SFM_POSE_NOT_ESSENTIAL 2 /* the decomposition's own status 1: sigma_3 not ~0 */
+#define SFM_POSE_NO_VOTE 3       /* all four votes are zero */
+#define SFM_POSE_BAD_OFFSETS 4   /* verdict[q].kind == SFM_PAIR_BAD_OFFSETS: every pair */
+
+typedef struct sfm_pair_pose {
+    double R[9];         /* row-major; x_b ~ R x_a + t */
+    double t[3];         /* |t| = 1 */
+    double median_angle; /* radians */
+    int32_t votes[4];    /* passing inliers per candidate */
+    int32_t best;        /* first maximum of votes, -1 if all are zero */
+    int32_t status;      /* SFM_POSE_* */
+} sfm_pair_pose;
+#ifdef __cplusplus
+static_assert(sizeof(sfm_pair_pose) == 128, "sfm_pair_pose is 128 bytes");
+#endif
+
+int64_t sfm_pair_poses_workspace_bytes(int64_t n_total, int64_t pairs);
+int sfm_pair_poses(const double* corr, int64_t n_total, const int64_t* offset, int64_t pairs, const double* E, int64_t h_count,
+                   const sfm_select_result* e_result, const uint8_t* e_mask, const sfm_pair_verdict* verdict,
+                   double distance_threshold, sfm_pair_pose* pose, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- refinement of a PnP winner on its inliers (csrc/sfm_pnp_refine.hip; an extension, off unless asked for) ---- */
 
 typedef struct sfm_pnp_refine_info {

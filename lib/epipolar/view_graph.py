@@ -1,5 +1,6 @@
 """``lib.epipolar.view_graph``: two-view verification of every pair of a match graph in one device call and the choice of the seed pair (structure_from_motion_amd/epipolar/view_graph.py)."""
 from structure_from_motion_amd.epipolar.view_graph import (  # noqa: F401
+    PairPoses,
     ViewGraph,
     choose_seed_pair,
     chunk_bounds,

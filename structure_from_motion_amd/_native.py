@@ -177,6 +177,7 @@ SIGNATURES = {
     "sfm_homography_ransac_pass": [_U64, _U64, C.c_int, _I64, _P, _I64, _I64, _I64, _D, _D, C.c_int, _P, _P, _P, _P, _P, _P,
                                    _P, _P, _P],
     "sfm_verify_pairs": [_U64, _U64, _I64, _P, _I64, _P, _I64, _P, _I64, _D, C.c_int, _D] + [_P] * 17,
+    "sfm_pair_poses": [_P, _I64, _P, _I64, _P, _I64, _P, _P, _P, _D, _P, _P, _I64, _P],
     "sfm_pnp_refine": [_P, _I64, _I64, _P, _P, _P, _P, _D, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P],
     "sfm_bundle_adjust": [_P, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _I64, _P],
     "sfm_bundle_adjust_pcg": [_P, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, _D, _P, _P, _P, _P, _I64, _P],
@@ -190,7 +191,7 @@ SIGNATURES = {
 OTHER_SYMBOLS = ["sfm_last_error", "sfm_abi_version", "sfm_score_workspace_bytes", "sfm_score_workspace_bytes_ex",
                  "sfm_fit_trace_doubles", "sfm_match_summary_workspace_bytes", "sfm_bundle_workspace_bytes",
                  "sfm_tracks_workspace_bytes", "sfm_bundle_pcg_workspace_bytes", "sfm_build_tracks_workspace_bytes",
-                 "sfm_bundle_pcg_workspace_bytes_ex", "sfm_hamming_summary_workspace_bytes"]
+                 "sfm_bundle_pcg_workspace_bytes_ex", "sfm_hamming_summary_workspace_bytes", "sfm_pair_poses_workspace_bytes"]
 
 # the losses of both bundle adjusters, in the order of their SFM_BUNDLE_LOSS_* codes (include/sfm_hip.h)
 BUNDLE_LOSSES = ("squared", "huber", "cauchy")
@@ -204,6 +205,16 @@ class PairVerdict(C.Structure):
     """sfm_pair_verdict"""
     _fields_ = [("kind", C.c_int32), ("homography_count", C.c_int32), ("essential_count", C.c_int32), ("reserved", C.c_int32),
                 ("ratio", C.c_double)]
+
+
+# the statuses of sfm_pair_pose, in the order of their SFM_POSE_* codes (include/sfm_hip.h)
+POSE_STATUS = ("ok", "no_model", "not_essential", "no_vote", "bad_offsets")
+
+
+class PairPose(C.Structure):
+    """sfm_pair_pose"""
+    _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("median_angle", C.c_double), ("votes", C.c_int32 * 4),
+                ("best", C.c_int32), ("status", C.c_int32)]
 
 
 class BundleOptions(C.Structure):
@@ -257,6 +268,8 @@ def load() -> C.CDLL:
     lib.sfm_bundle_pcg_workspace_bytes_ex.argtypes = [_I64, _I64, _I64, _P]
     lib.sfm_build_tracks_workspace_bytes.restype = C.c_int64
     lib.sfm_build_tracks_workspace_bytes.argtypes = [_I64, _I64, _I64]
+    lib.sfm_pair_poses_workspace_bytes.restype = C.c_int64
+    lib.sfm_pair_poses_workspace_bytes.argtypes = [_I64, _I64]
     if lib.sfm_abi_version() != ABI_VERSION:
         raise NativeLibraryError(
             f"libsfm_hip.so ABI {lib.sfm_abi_version()} != expected {ABI_VERSION}; rebuild it")

@@ -9,7 +9,8 @@
 // sample_fit_philox_; and the PnP ops (sfm_pnp.hip) pnp_fit, pnp_score and the whole pass pnp_ransac_pass_, their P3P
 // forms p3p_fit and p3p_ransac_pass_ (sfm_p3p.h), the five-point fit five_point_fit and pass five_point_ransac_pass_
 // (sfm_five_point.hip), the homography ops homography_fit, homography_score, homography_inlier_mask and the pass
-// homography_ransac_pass_ (sfm_homography.hip), the ragged two-view pass verify_pairs_ (sfm_view_graph.hip), and the
+// homography_ransac_pass_ (sfm_homography.hip), the ragged two-view pass verify_pairs_ (sfm_view_graph.hip) and the poses behind it
+// pair_poses (sfm_view_graph_pose.hip), and the
 // refinement of a winner pnp_refine (sfm_pnp_refine.hip), bundle_adjust (sfm_bundle.hip), triangulate_tracks
 // (sfm_tracks.hip) and build_tracks (sfm_track_build.hip).  The reference call sites these serve: apps/sfm.py:110-119 (RANSAC-E), :133-138 (pose),
 // :181-186 (triangulation).
@@ -567,6 +568,46 @@ void verify_pairs_out(const Tensor& corr, const Tensor& offset, const Tensor& mi
                         reinterpret_cast<sfm_select_result*>(ptr<int64_t>(e_result)), ptr<uint8_t>(h_mask), ptr<uint8_t>(e_mask),
                         reinterpret_cast<sfm_pair_verdict*>(ptr<int64_t>(verdict)), current_stream()),
        "sfm_verify_pairs");
+}
+
+// ---- relative pose and triangulation angle of every pair behind verify_pairs_ (sfm_view_graph_pose.hip), on that op's tensors:
+// -> (pose uint8 [pairs, 128], the sfm_pair_pose records; angle double [n_total], each item's angle under its pair's best pose,
+// NaN off the passing inliers: the head of the call's workspace) ------------------------------------------------------------
+std::tuple<Tensor, Tensor> pair_poses(const Tensor& corr, const Tensor& offset, const Tensor& E, const Tensor& e_result,
+                                      const Tensor& e_mask, const Tensor& verdict, double distance_threshold) {
+    const OpDevice scope(corr);
+    static_assert(sizeof(sfm_pair_pose) == 128, "pose rows are 128 bytes");
+    need(corr, "corr", at::kDouble);
+    need(offset, "offset", at::kLong);
+    need(E, "E", at::kDouble);
+    need(e_result, "e_result", at::kLong);
+    need(e_mask, "e_mask", at::kByte);
+    need(verdict, "verdict", at::kLong);
+    TORCH_CHECK(corr.dim() == 2 && corr.size(1) == 4, "sfm_hip: corr must be [n_total, 4]");
+    TORCH_CHECK(offset.dim() == 1 && offset.size(0) >= 1, "sfm_hip: offset must be int64 [pairs + 1]");
+    const int64_t n_total = corr.size(0), pairs = offset.size(0) - 1;
+    TORCH_CHECK(E.dim() == 3 && E.size(0) == pairs && E.size(1) >= 1 && E.size(2) == 9, "sfm_hip: E must be [pairs, h >= 1, 9]");
+    TORCH_CHECK(e_result.numel() == pairs * kRecordWords, "sfm_hip: e_result must be int64 [pairs, 5]");
+    TORCH_CHECK(e_mask.numel() == n_total, "sfm_hip: e_mask must be uint8 [n_total]");
+    TORCH_CHECK(verdict.numel() == pairs * 3, "sfm_hip: verdict must be int64 [pairs, 3]");
+    const int64_t bytes = sfm_pair_poses_workspace_bytes(n_total, pairs);
+    TORCH_CHECK(bytes >= 0, "sfm_hip: pair_poses takes at most 65535 pairs and fewer than 2^31 items");
+    Tensor pose = at::empty({pairs, 128}, like(corr, at::kByte));
+    Tensor workspace = at::empty({(bytes + 7) / 8}, like(corr, at::kDouble));
+    if (pairs == 0) workspace.fill_(NAN);   // the entry is a no-op then: no item has a pair
+    ok(sfm_pair_poses(ptr<double>(corr), n_total, ptr<int64_t>(offset), pairs, ptr<double>(E), E.size(1),
+                      reinterpret_cast<const sfm_select_result*>(ptr<int64_t>(e_result)), ptr<uint8_t>(e_mask),
+                      reinterpret_cast<const sfm_pair_verdict*>(ptr<int64_t>(verdict)), distance_threshold,
+                      reinterpret_cast<sfm_pair_pose*>(ptr<uint8_t>(pose)), workspace.data_ptr(), bytes, current_stream()),
+       "sfm_pair_poses");
+    return {pose, workspace.narrow(0, 0, n_total)};
+}
+
+std::tuple<Tensor, Tensor> pair_poses_meta(const Tensor& corr, const Tensor& offset, const Tensor&, const Tensor&, const Tensor&,
+                                           const Tensor&, double) {
+    TORCH_CHECK(corr.dim() == 2 && offset.dim() == 1, "sfm_hip: corr must be [n_total, 4], offset int64 [pairs + 1]");
+    return {at::empty_symint({offset.sym_size(0) - 1, 128}, like(corr, at::kByte)),
+            at::empty_symint({corr.sym_size(0)}, like(corr, at::kDouble))};
 }
 
 // ---- PnP (sfm_pnp.hip): pts [batch, n, 5] = {X, Y, Z, u, v}, K 9 doubles (row-major, row 2 = 0 0 1), S [batch, h, 8],
@@ -1156,6 +1197,8 @@ TORCH_LIBRARY(sfm_hip, m) {
           "float max_ratio, Tensor(a!) S, Tensor(b!) H, Tensor(c!) E, Tensor(d!) h_flags, Tensor(e!) h_cnt, Tensor(f!) h_s1, "
           "Tensor(g!) h_s2, Tensor(h!) e_flags, Tensor(i!) e_cnt, Tensor(j!) e_s1, Tensor(k!) e_s2, Tensor(l!) h_result, "
           "Tensor(m!) e_result, Tensor(n!) h_mask, Tensor(o!) e_mask, Tensor(p!) verdict) -> ()");
+    m.def("pair_poses(Tensor corr, Tensor offset, Tensor E, Tensor e_result, Tensor e_mask, Tensor verdict, "
+          "float distance_threshold) -> (Tensor, Tensor)");
     m.def("pnp_fit(Tensor pts, Tensor S, float[] K) -> (Tensor, Tensor)");
     m.def("pnp_fit_(Tensor pts, Tensor S, float[] K, Tensor(a!) model, Tensor(b!) flags) -> ()");
     m.def("p3p_fit(Tensor pts, Tensor S, float[] K) -> (Tensor, Tensor)");
@@ -1229,6 +1272,7 @@ TORCH_LIBRARY_IMPL(sfm_hip, CUDA, m) {
     m.impl("homography_inlier_mask", &homography_inlier_mask);
     m.impl("homography_ransac_pass_", &homography_ransac_pass_out);
     m.impl("verify_pairs_", &verify_pairs_out);
+    m.impl("pair_poses", &pair_poses);
     m.impl("pnp_fit", &pose_fit_new<pnp_fit_out>);
     m.impl("pnp_fit_", &pnp_fit_out);
     m.impl("pnp_score", &pnp_score);
@@ -1318,6 +1362,7 @@ TORCH_LIBRARY_IMPL(sfm_hip, Meta, m) {
     m.impl("homography_inlier_mask", &homography_inlier_mask_meta);
     m.impl("homography_ransac_pass_", &five_point_ransac_pass_out_meta);
     m.impl("verify_pairs_", &verify_pairs_out_meta);
+    m.impl("pair_poses", &pair_poses_meta);
     m.impl("pnp_fit", &pnp_fit_meta);
     m.impl("pnp_score", &pnp_score_meta);
     m.impl("pnp_fit_", &pnp_fit_out_meta);

@@ -1068,6 +1068,12 @@ class HomographyWorkspace(_PassWorkspace):
 PAIR_NONE, PAIR_ESSENTIAL, PAIR_HOMOGRAPHY, PAIR_BAD_OFFSETS = range(4)
 PAIR_KINDS = _native.PAIR_KINDS
 VERDICT_BYTES = C.sizeof(_native.PairVerdict)
+POSE_OK, POSE_NO_MODEL, POSE_NOT_ESSENTIAL, POSE_NO_VOTE, POSE_BAD_OFFSETS = range(5)
+POSE_STATUS = _native.POSE_STATUS
+POSE_BYTES = C.sizeof(_native.PairPose)
+# sfm_pair_pose as a NumPy record: one row of the pose table of ``ViewGraphWorkspace.poses``
+POSE_DTYPE = np.dtype([("R", "<f8", (3, 3)), ("t", "<f8", (3,)), ("median_angle", "<f8"), ("votes", "<i4", (4,)), ("best", "<i4"),
+                       ("status", "<i4")])
 
 
 @dataclass
@@ -1085,6 +1091,13 @@ class ViewGraphOutcome:
     essential_sample: np.ndarray   # (Q, 6) int64
     homography_mask: np.ndarray    # (N,) uint8: 2 sample item of its pair's winner, 1 other inlier, 0 otherwise
     essential_mask: np.ndarray     # (N,) uint8
+    # after ``poses``, else None
+    pose_R: Optional[np.ndarray] = None             # (Q, 3, 3) x_b ~ R x_a + t, NaN unless pose_status is POSE_OK
+    pose_t: Optional[np.ndarray] = None             # (Q, 3) unit length
+    pose_votes: Optional[np.ndarray] = None         # (Q, 4) int32 passing inliers per candidate
+    pose_best: Optional[np.ndarray] = None          # (Q,) int32 first maximum of the votes, -1 if all are zero
+    pose_median_angle: Optional[np.ndarray] = None  # (Q,) radians, NaN unless pose_status is POSE_OK
+    pose_status: Optional[np.ndarray] = None        # (Q,) int32, POSE_*
 
 
 class ViewGraphWorkspace:
@@ -1107,6 +1120,7 @@ class ViewGraphWorkspace:
         self.h_mask = torch.empty((n_total,), dtype=torch.uint8, device=dev)
         self.e_mask = torch.empty((n_total,), dtype=torch.uint8, device=dev)
         self.verdict = torch.empty((pairs, VERDICT_BYTES // 8), dtype=torch.int64, device=dev)
+        self.pose = self.angle = self._corr = self._offset = None   # set by run / poses
 
     def buffers(self):
         """The output tensors in the order of the ``verify_pairs_`` op."""
@@ -1119,6 +1133,22 @@ class ViewGraphWorkspace:
         min_extra f64 [Q] on the device; pair q draws its Philox samples with ``seed + q * seed_stride``."""
         ops.load().verify_pairs_(corr, offset, min_extra, _as_int64(seed), _as_int64(seed_stride), int(h_begin), float(thr),
                                  int(aggregation), float(max_ratio), *self.buffers())
+        self._corr, self._offset, self.pose, self.angle = corr, offset, None, None
+
+    def poses(self, distance_threshold: float = 50.0) -> None:
+        """One ``sfm_pair_poses`` call (the ``pair_poses`` op) on what ``run`` took and left, enqueue-only: ``pose`` uint8
+        [Q,128] (``sfm_pair_pose`` records) and ``angle`` f64 [N], each item's angle under its pair's best pose, NaN off the
+        passing inliers."""
+        if self._corr is None:
+            raise RuntimeError("ViewGraphWorkspace.poses: call run first")
+        if self.h < 1:
+            raise ValueError("ViewGraphWorkspace.poses needs at least one hypothesis per pair")
+        self.pose, self.angle = ops.load().pair_poses(self._corr, self._offset, self.E, self.e_result, self.e_mask, self.verdict,
+                                                       float(distance_threshold))
+
+    def read_poses(self) -> np.ndarray:
+        """The pose table on the host as a (Q,) array of ``POSE_DTYPE`` records (synchronises)."""
+        return self.pose.cpu().numpy().reshape(-1).view(POSE_DTYPE).copy()
 
     def read_verdicts(self) -> List["_native.PairVerdict"]:
         """Copy the verdict records to the host (synchronises)."""
@@ -1152,4 +1182,12 @@ class ViewGraphWorkspace:
             homography_best=out["homography"][1], essential_best=out["essential"][1],
             homography_sample=out["homography"][2], essential_sample=out["essential"][2],
             homography_mask=checked_mask(self.h_mask.cpu().numpy().copy()),
-            essential_mask=checked_mask(self.e_mask.cpu().numpy().copy()))
+            essential_mask=checked_mask(self.e_mask.cpu().numpy().copy()), **self._pose_fields())
+
+    def _pose_fields(self) -> dict:
+        if self.pose is None:
+            return {}
+        table = self.read_poses()
+        return dict(pose_R=table["R"].copy(), pose_t=table["t"].copy(), pose_votes=table["votes"].copy(),
+                    pose_best=table["best"].copy(), pose_median_angle=table["median_angle"].copy(),
+                    pose_status=table["status"].copy())

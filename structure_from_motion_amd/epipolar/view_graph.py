@@ -2,12 +2,15 @@
 homography, the RANSAC five-point essential matrix on the same samples, both inlier lists and which of the two explains the
 pair — what ``homography.select_two_view_model`` answers for one pair, for all pairs of ``build_tracks``'s input at once
 (csrc/sfm_view_graph.hip, ``device.ViewGraphWorkspace``).  ``choose_seed_pair`` then picks the pair a reconstruction should
-start from: a pure rotation or a plane fits an essential matrix to every match and would win on the essential count alone."""
+start from: a pure rotation or a plane fits an essential matrix to every match and would win on the essential count alone.
+With ``relative_pose=True`` the same device calls also give how the two cameras of each pair stand to each other and the
+median triangulation angle of its inliers (csrc/sfm_view_graph_pose.hip), which ``choose_seed_pair`` can gate
+on: a pair with many inliers and a fraction of a degree of parallax is a poor place to start."""
 from __future__ import annotations
 
 import os
 import random
-from typing import List, NamedTuple, Sequence
+from typing import List, NamedTuple, Optional, Sequence
 
 import numpy as np
 import numpy.typing as npt
@@ -18,6 +21,17 @@ from .homography import MAX_HOMOGRAPHY_RATIO, check_camera_matrix
 
 MAX_PAIRS_PER_CALL = 65535          # the grid's y extent: one sfm_verify_pairs call takes no more
 BYTES_PER_PAIR_HYPOTHESIS = 224     # S 32, H and E 72 each, two sets of flags / cnt / s1 / s2 at 24
+
+
+class PairPoses(NamedTuple):
+    """The relative pose of each pair from its winning essential matrix (whatever the pair's kind) and the cheirality vote of
+    that matrix's inliers: ``x_b ~ R x_a + t``."""
+    R: npt.NDArray                     # (Q, 3, 3), NaN unless status is "ok"
+    t: npt.NDArray                     # (Q, 3) unit length, NaN unless status is "ok"
+    votes: npt.NDArray                 # (Q, 4) inliers in front of both cameras per candidate (R1,t), (R1,-t), (R2,t), (R2,-t)
+    in_front: npt.NDArray              # (Q,) the votes of the chosen candidate, 0 when there is none
+    median_angle_deg: npt.NDArray      # (Q,) lower median of the angle between the two viewing rays of those inliers, NaN unless "ok"
+    status: List[str]                  # per pair "ok", "no_model", "not_essential" or "no_vote"
 
 
 class ViewGraph(NamedTuple):
@@ -31,6 +45,7 @@ class ViewGraph(NamedTuple):
     essential_inliers: List[npt.NDArray]    # per pair (k, 2) rows of matches[q]: the sample first, then the survivors by index
     homography_inliers: List[npt.NDArray]
     inlier_matches: List[npt.NDArray]  # per pair the inliers of the model its kind names ((0, 2) for "none"): build_tracks's input
+    pose: Optional[PairPoses] = None   # with relative_pose=True
 
 
 def pair_min_extra(counts, min_num_extra_inliers=None, min_extra_fraction: float = 0.0) -> npt.NDArray:
@@ -85,7 +100,8 @@ def _checked_graph(features: Sequence, pairs, matches: Sequence):
 def verify_pairs(camera_matrix, features: Sequence, pairs, matches: Sequence, inlier_threshold: float,
                  min_num_extra_inliers=None, min_extra_fraction: float = 0.0, max_iterations: int | None = None,
                  max_homography_ratio: float = MAX_HOMOGRAPHY_RATIO, seed: int | None = None,
-                 max_hypotheses_per_call: int = 2**21) -> ViewGraph:
+                 max_hypotheses_per_call: int = 2**21, relative_pose: bool = False,
+                 distance_threshold: float = 50.0) -> ViewGraph:
     """Verify all Q pairs of a match graph: ``features``, ``pairs`` and ``matches`` exactly as ``build_tracks`` takes them.
 
     Per pair, ``max_iterations`` Philox samples serve a homography pass (their first four items) and a five-point essential
@@ -97,20 +113,31 @@ def verify_pairs(camera_matrix, features: Sequence, pairs, matches: Sequence, in
 
     Pair q draws its samples with ``seed + q`` (``seed``, else ``SFM_SEED``, else 64 bits of ``random``), so the result
     does not depend on how the pairs are split into device calls (``max_hypotheses_per_call`` pair-hypotheses each).  One
-    upload and one normalisation serve all pairs.  Every argument is checked before any device work (``ValueError``)."""
+    upload and one normalisation serve all pairs.  Every argument is checked before any device work (``ValueError``).
+
+    ``relative_pose=True`` adds ``pose`` (``PairPoses``): per pair with an essential winner the pose its inliers vote for among
+    the four of that matrix (an inlier votes when it triangulates in front of both cameras within ``distance_threshold``), and
+    the median angle between the viewing rays of the voters.  It needs ``max_iterations >= 1`` and changes no other field."""
     K = check_camera_matrix(camera_matrix)
+    distance = float(distance_threshold)
+    if not (np.isfinite(distance) and distance > 0.0):
+        raise ValueError(f"distance_threshold must be finite and positive, got {distance_threshold!r}")
     feats, pair_arr, per_pair = _checked_graph(features, pairs, matches)
     Q = len(per_pair)
     counts = np.array([len(m) for m in per_pair], dtype=np.int64)
     gate = pair_min_extra(counts, min_num_extra_inliers, min_extra_fraction)
     iterations = DEFAULT_MAX_ITERATIONS if max_iterations is None else int(max_iterations)
+    if relative_pose and iterations < 1:
+        raise ValueError(f"relative_pose needs max_iterations >= 1, got {max_iterations!r}")
     chunks = chunk_bounds(Q, iterations, max_hypotheses_per_call)
     if seed is None:
         seed = int(os.environ["SFM_SEED"]) if "SFM_SEED" in os.environ else random.getrandbits(64)
     empty = np.zeros((0, 2), dtype=np.int64)
     if Q == 0:
         none = np.zeros((0, 3, 3))
-        return ViewGraph(pair_arr, [], none, none.copy(), np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0), [], [], [])
+        no_pose = PairPoses(none.copy(), np.zeros((0, 3)), np.zeros((0, 4), np.int64), np.zeros(0, np.int64), np.zeros(0), [])
+        return ViewGraph(pair_arr, [], none, none.copy(), np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0), [], [], [],
+                         no_pose if relative_pose else None)
     import torch
 
     from .. import device
@@ -133,6 +160,8 @@ def verify_pairs(camera_matrix, features: Sequence, pairs, matches: Sequence, in
         ws = device.ViewGraphWorkspace(q1 - q0, hi - lo, max(iterations, 0), dev)
         ws.run(corr[lo:hi], offset_dev[q0:q1 + 1] - lo, gate_dev[q0:q1], inlier_threshold, aggregation, max_homography_ratio,
                seed + q0, seed_stride=1)
+        if relative_pose:
+            ws.poses(distance)
         outcomes.append(ws.outcome())
     cat = lambda name: np.concatenate([getattr(o, name) for o in outcomes])   # noqa: E731
     code, h_mask, e_mask = cat("kind"), cat("homography_mask"), cat("essential_mask")
@@ -150,17 +179,29 @@ def verify_pairs(camera_matrix, features: Sequence, pairs, matches: Sequence, in
     e_in = [inliers(q, e_sample, e_mask) for q in range(Q)]
     kind = [device.PAIR_KINDS[c] for c in code]
     chosen = [e_in[q] if kind[q] == "essential" else (h_in[q] if kind[q] == "homography" else empty) for q in range(Q)]
+    pose = None
+    if relative_pose:
+        votes, best = cat("pose_votes").astype(np.int64), cat("pose_best")
+        in_front = np.where(best >= 0, votes[np.arange(Q), np.maximum(best, 0)], 0)
+        pose = PairPoses(cat("pose_R"), cat("pose_t"), votes, in_front, np.degrees(cat("pose_median_angle")),
+                         [device.POSE_STATUS[c] for c in cat("pose_status")])
     return ViewGraph(pair_arr, kind, cat("E"), cat("H"), cat("essential_count").astype(np.int64),
-                     cat("homography_count").astype(np.int64), cat("ratio"), e_in, h_in, chosen)
+                     cat("homography_count").astype(np.int64), cat("ratio"), e_in, h_in, chosen, pose)
 
 
-def choose_seed_pair(graph: ViewGraph, min_count: int = 0) -> int:
+def choose_seed_pair(graph: ViewGraph, min_count: int = 0, min_angle_deg: float = 0.0) -> int:
     """The pair a reconstruction should start from: among the pairs of kind ``"essential"`` with ``essential_count >=
     min_count`` the one with the largest ``essential_count``; ties go to the lower ratio, then to the lower index.
-    ``ValueError`` when there is none."""
+    With ``min_angle_deg > 0`` a candidate must also have pose status ``"ok"`` and ``median_angle_deg >= min_angle_deg``
+    (``graph.pose`` must be there: ``verify_pairs(..., relative_pose=True)``).  ``ValueError`` when there is none."""
+    gated = min_angle_deg > 0
+    if gated and graph.pose is None:
+        raise ValueError("min_angle_deg needs graph.pose: call verify_pairs with relative_pose=True")
     best = None
     for q, kind in enumerate(graph.kind):
         if kind != "essential" or graph.essential_count[q] < min_count:
+            continue
+        if gated and not (graph.pose.status[q] == "ok" and graph.pose.median_angle_deg[q] >= min_angle_deg):
             continue
         key = (-int(graph.essential_count[q]), float(graph.ratio[q]), q)
         if best is None or key < best:
