@@ -69,6 +69,19 @@ __device__ __forceinline__ int64_t checked_index(int32_t i, int64_t n, bool& bad
     return out ? 0 : (int64_t)i;
 }
 
+// The pair that owns item i of a ragged layout (pair q owns items offset[q] .. offset[q + 1] - 1; the table holds pairs + 1
+// non-decreasing entries), or -1 for an item no pair owns.
+__device__ __forceinline__ int64_t pair_of_item(const int64_t* __restrict__ offset, int64_t pairs, int64_t i) {
+    // the first k in [0, pairs] with offset[k] > i: item i belongs to pair k - 1 when 1 <= k <= pairs
+    int64_t lo = 0, hi = pairs + 1;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (offset[mid] > i) hi = mid;
+        else lo = mid + 1;
+    }
+    return (lo >= 1 && lo <= pairs) ? lo - 1 : -1;
+}
+
 // One correspondence in K-normalised coordinates: 32 bytes, read as two 16-byte loads.
 struct alignas(32) Corr {
     double xa, ya, xb, yb;

@@ -650,4 +650,18 @@ SFM_DEVICE int five_point_solver::fit(Data corr, int64_t b, int64_t n, const int
     return (bad || degenerate) ? SFM_FIT_DEGENERATE : 0;
 }
 
+// The `Model` of sfm_minimal_score.h: E in registers, the symmetric epipolar distance of a correspondence.
+struct essential_model {
+    using Stored = Corr;
+    using Item = Corr;
+    static constexpr int kStride = 1, kModel = 9;
+    double m[9];
+    SFM_DEVICE explicit essential_model(const double* model) {
+#pragma unroll
+        for (int i = 0; i < 9; ++i) m[i] = model[i];
+    }
+    SFM_DEVICE static void load(const Corr* items, int64_t i, Corr& slot) { slot = items[i]; }
+    SFM_DEVICE double error(const Corr& t) const { return sfm::sed_value(m, t.xa, t.ya, t.xb, t.yb); }
+};
+
 }  // namespace sfm5

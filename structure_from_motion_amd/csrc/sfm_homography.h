@@ -151,4 +151,19 @@ SFM_DEVICE double transfer_error(const double (&h)[9], const double (&g)[9], dou
     return (p2 <= 0.0 || q2 <= 0.0) ? INFINITY : e;
 }
 
+// The `Model` of sfm_minimal_score.h: H and adj(H) in registers, the symmetric transfer error of a correspondence.
+struct homography_model {
+    using Stored = Corr;
+    using Item = Corr;
+    static constexpr int kStride = 1, kModel = 9;
+    double m[9], g[9];
+    SFM_DEVICE explicit homography_model(const double* model) {
+#pragma unroll
+        for (int i = 0; i < 9; ++i) m[i] = model[i];
+        adjugate(m, g);
+    }
+    SFM_DEVICE static void load(const Corr* items, int64_t i, Corr& slot) { slot = items[i]; }
+    SFM_DEVICE double error(const Corr& t) const { return transfer_error(m, g, t.xa, t.ya, t.xb, t.yb); }
+};
+
 }  // namespace sfmhg

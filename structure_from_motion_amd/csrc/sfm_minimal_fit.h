@@ -39,6 +39,15 @@ inline int check_sizes(const char* fn, int sample, int64_t n, int64_t h_count, i
     return SFM_OK;
 }
 
+// The prologue of an entry point that makes one launch: the outcome of its size checks, nothing to do, a null pointer, the launch.
+template <class Launch>
+int checked_entry(const char* fn, int sizes, bool nothing, bool null, Launch launch) {
+    if (sizes != SFM_OK) return sizes;
+    if (nothing) return SFM_OK;
+    if (null) return fail_in(fn, "null pointer");
+    return launch();
+}
+
 }  // namespace sfmhost
 
 namespace sfmmin {

@@ -15,16 +15,15 @@
 #include "sfm_common.h"
 #include "sfm_math.h"
 #include "sfm_minimal_fit.h"
+#include "sfm_minimal_score.h"
 #include "sfm_p3p.h"
 #include "sfm_pnp.h"
 
 namespace {
 
-using sfmhost::check_launch;
+using sfmhost::checked_entry;
 using sfmhost::fail;
 using sfmhost::fail_in;
-using sfmhost::grid_for;
-using sfmhost::grid_stride;
 using sfmpnp::camera_from;
 using sfmpnp::kPnPFields;
 using sfmpnp::pnp_score;
@@ -191,29 +190,28 @@ struct p3p_solver {
 };
 
 // --------------------------------------------------------------------------------------------------
-// Scoring: one hypothesis per lane (its model in registers), the points staged through LDS in tiles that every lane of
-// the block reads at the same address (broadcast).  cnt = non-sample points with e <= thr; s1 / s2 = sums of e / e^2 over
-// the six sample points and those survivors (the layout sfm_select_best reads).  The tile loop counts every point; the
-// SAMPLE sample points are then corrected: one that passed the gate is taken out of the count (its value is already in the
-// sums), one that did not is added to the sums.  All fp64 with the divisions of pnp_score: no fast path, so every value is
-// the oracle's bit for bit and only the summation order differs.
+// Scoring: the loop of sfmmin::score_hypothesis (sfm_minimal_score.h) written out for the pose — one hypothesis per lane, the
+// points staged through LDS in tiles read by broadcast (a slot holds a point as three 16-byte words: 512 x 48 B = 24 KiB), every
+// point counted, the SAMPLE sample points then corrected.  All fp64 with the divisions of pnp_score: no fast path, so every
+// value is the oracle's bit for bit and only the summation order differs.  The kernel keeps its own copy of the loop because
+// score_kernel<SAMPLE, pnp_model> schedules the sample correction differently (108 and 110 VGPRs for the 106 and 112 here,
+// one s_waitcnt apart; the tile loop itself comes out the same).
 // --------------------------------------------------------------------------------------------------
-constexpr int kPnPScoreBlock = 256;
-constexpr int kPnPTile = 512;  // points per tile: 512 x 48 B = 24 KiB of LDS
+using sfmmin::kScoreBlock;
+using sfmmin::kScoreTile;
 
 struct alignas(16) TilePoint {
     double2 xy, zu, v_;
 };
 
 template <int SAMPLE>
-__global__ __launch_bounds__(kPnPScoreBlock) void pnp_score_kernel(const double* __restrict__ pts, int64_t n,
-                                                                   const double* __restrict__ model,
-                                                                   const int32_t* __restrict__ S, int64_t h_count, PnPCamera cam,
-                                                                   double thr, int32_t* __restrict__ cnt, double* __restrict__ s1,
-                                                                   double* __restrict__ s2) {
-    __shared__ TilePoint tile[kPnPTile];
+__global__ __launch_bounds__(kScoreBlock) void pnp_score_kernel(const double* __restrict__ pts, int64_t n,
+                                                                const double* __restrict__ model, const int32_t* __restrict__ S,
+                                                                int64_t h_count, PnPCamera cam, double thr, int32_t* __restrict__ cnt,
+                                                                double* __restrict__ s1, double* __restrict__ s2) {
+    __shared__ TilePoint tile[kScoreTile];
     const int64_t b = blockIdx.y;
-    const int64_t h = (int64_t)blockIdx.x * kPnPScoreBlock + threadIdx.x;
+    const int64_t h = (int64_t)blockIdx.x * kScoreBlock + threadIdx.x;
     const int64_t hc = h < h_count ? h : h_count - 1;  // lanes past the end score a valid hypothesis and store nothing
     const int64_t bh = b * h_count + hc;
     const double* P = pts + b * n * kPnPFields;
@@ -222,10 +220,10 @@ __global__ __launch_bounds__(kPnPScoreBlock) void pnp_score_kernel(const double*
     for (int i = 0; i < 12; ++i) m[i] = model[bh * 12 + i];
     int c = 0;
     double a1 = 0.0, a2 = 0.0;
-    for (int64_t base = 0; base < n; base += kPnPTile) {
-        const int count = (int)(n - base < kPnPTile ? n - base : kPnPTile);
+    for (int64_t base = 0; base < n; base += kScoreTile) {
+        const int count = (int)(n - base < kScoreTile ? n - base : kScoreTile);
         __syncthreads();  // the previous tile has been read by every lane
-        for (int i = threadIdx.x; i < count; i += kPnPScoreBlock) {
+        for (int i = threadIdx.x; i < count; i += kScoreBlock) {
             const double* q = P + (base + i) * kPnPFields;
             tile[i].xy = make_double2(q[0], q[1]);
             tile[i].zu = make_double2(q[2], q[3]);
@@ -261,38 +259,26 @@ __global__ __launch_bounds__(kPnPScoreBlock) void pnp_score_kernel(const double*
     }
 }
 
-// mask[b, i] = 2 for the SAMPLE sample points of the winner, 1 for the other points with e <= thr, 0 otherwise (all 0 when
-// the record holds no model).  Grid-stride over the points; every byte of the mask is written.
-template <int SAMPLE>
-__global__ void pnp_inlier_mask_kernel(const double* __restrict__ pts, int64_t n, const double* __restrict__ model,
-                                       const int32_t* __restrict__ S, int64_t h_count, PnPCamera cam,
-                                       const sfm_select_result* __restrict__ result, double thr, uint8_t* __restrict__ mask) {
-    const int64_t b = blockIdx.y;
-    const int64_t best = result[b].best_h;
-    const bool none = best < 0 || best >= h_count;
-    const int64_t bh = b * h_count + (none ? 0 : best);
-    const double* P = pts + b * n * kPnPFields;
-    uint8_t* out = mask + b * n;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    if (none) {
-        for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[i] = 0;
-        return;
-    }
+// The `Model` of sfm_minimal_score.h for the winner's mask (sfmmin::mask_kernel): the pose and the camera in registers, a
+// point as the five doubles the error reads.
+struct pnp_model {
+    using Stored = double;
+    struct Item {
+        double f[kPnPFields];
+    };
+    static constexpr int kStride = kPnPFields, kModel = 12;
     double m[12];
-    int32_t smp[SAMPLE];
+    PnPCamera cam;
+    SFM_DEVICE pnp_model(const double* model, const PnPCamera& camera) : cam(camera) {
 #pragma unroll
-    for (int k = 0; k < 12; ++k) m[k] = model[bh * 12 + k];
-#pragma unroll
-    for (int k = 0; k < SAMPLE; ++k) smp[k] = S[bh * 8 + k];
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const double* q = P + i * kPnPFields;
-        const double e = pnp_score(m, cam, q[0], q[1], q[2], q[3], q[4]);
-        bool in_sample = false;
-#pragma unroll
-        for (int k = 0; k < SAMPLE; ++k) in_sample |= (smp[k] == (int32_t)i);
-        out[i] = in_sample ? 2 : ((e <= thr) ? 1 : 0);
+        for (int i = 0; i < 12; ++i) m[i] = model[i];
     }
-}
+    SFM_DEVICE static void load(const double* items, int64_t i, Item& slot) {
+#pragma unroll
+        for (int k = 0; k < kPnPFields; ++k) slot.f[k] = items[i * kPnPFields + k];
+    }
+    SFM_DEVICE double error(const Item& t) const { return pnp_score(m, cam, t.f[0], t.f[1], t.f[2], t.f[3], t.f[4]); }
+};
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
 // Every check of a call that depends on its sizes, before anything is launched: `sample` (4 or 6) items per sample, n at
@@ -303,7 +289,7 @@ int check_call(const char* fn, int sample, int64_t n, int64_t h_count, int64_t b
         snprintf(msg, sizeof msg, "%s: sample_size must be 4 or 6, got %d", fn, sample);
         return fail(SFM_EINVAL, msg);
     }
-    const int rc = sfmhost::check_sizes(fn, sample, n, h_count, batch, {kPnPScoreBlock, sfmmin::kMinimalFitBlock});
+    const int rc = sfmhost::check_sizes(fn, sample, n, h_count, batch, {sfmmin::kScoreBlock, sfmmin::kMinimalFitBlock});
     return rc != SFM_OK ? rc : camera_from(K, cam, fn);
 }
 
@@ -316,24 +302,17 @@ int launch_fit(bool p3p, bool philox, uint64_t seed, uint64_t seed_stride, int64
 
 int launch_score(int sample, const double* pts, int64_t n, const double* model, const int32_t* S, int64_t h_count, int64_t batch,
                  const PnPCamera& cam, double thr, int32_t* cnt, double* s1, double* s2, hipStream_t st) {
-    const dim3 grid(grid_for(h_count, kPnPScoreBlock), (unsigned)batch);
-    if (sample == kP3PSample)
-        hipLaunchKernelGGL(pnp_score_kernel<kP3PSample>, grid, dim3(kPnPScoreBlock), 0, st, pts, n, model, S, h_count, cam, thr, cnt, s1,
-                           s2);
-    else
-        hipLaunchKernelGGL(pnp_score_kernel<kPnPSample>, grid, dim3(kPnPScoreBlock), 0, st, pts, n, model, S, h_count, cam, thr, cnt, s1,
-                           s2);
-    return check_launch("pnp_score_kernel");
+    const auto kernel = sample == kP3PSample ? pnp_score_kernel<kP3PSample> : pnp_score_kernel<kPnPSample>;
+    hipLaunchKernelGGL(kernel, dim3(sfmhost::grid_for(h_count, kScoreBlock), (unsigned)batch), dim3(kScoreBlock), 0, st, pts, n, model, S,
+                       h_count, cam, thr, cnt, s1, s2);
+    return sfmhost::check_launch("pnp_score_kernel");
 }
 
 int launch_mask(int sample, const double* pts, int64_t n, const double* model, const int32_t* S, int64_t h_count, int64_t batch,
                 const PnPCamera& cam, const sfm_select_result* result, double thr, uint8_t* mask, hipStream_t st) {
-    const dim3 grid(grid_stride(n, 256, 1024), (unsigned)batch);
-    if (sample == kP3PSample)
-        hipLaunchKernelGGL(pnp_inlier_mask_kernel<kP3PSample>, grid, dim3(256), 0, st, pts, n, model, S, h_count, cam, result, thr, mask);
-    else
-        hipLaunchKernelGGL(pnp_inlier_mask_kernel<kPnPSample>, grid, dim3(256), 0, st, pts, n, model, S, h_count, cam, result, thr, mask);
-    return check_launch("pnp_inlier_mask_kernel");
+    const auto launch = sample == kP3PSample ? sfmmin::launch_mask<kP3PSample, pnp_model, PnPCamera>
+                                             : sfmmin::launch_mask<kPnPSample, pnp_model, PnPCamera>;
+    return launch(pts, n, model, S, h_count, batch, result, thr, mask, st, cam);
 }
 
 int fit_entry(const char* fn, bool p3p, bool philox, uint64_t seed, uint64_t seed_stride, int64_t h_begin, const double* pts,
@@ -376,21 +355,20 @@ int sfm_p3p_sample_fit_philox(uint64_t seed, uint64_t seed_stride, int64_t h_beg
 int sfm_pnp_score(const double* pts, int64_t n, const double* model, const int32_t* S, int64_t h_count, int64_t batch,
                   const double* K, double thr, int sample_size, int32_t* cnt, double* s1, double* s2, void* stream) {
     PnPCamera cam;
-    const int rc = check_call("sfm_pnp_score", sample_size, n, h_count, batch, K, cam);
-    if (rc != SFM_OK) return rc;
-    if (h_count == 0 || batch == 0) return SFM_OK;
-    if (!pts || !model || !S || !cnt || !s1 || !s2) return fail_in("sfm_pnp_score", "null pointer");
-    return launch_score(sample_size, pts, n, model, S, h_count, batch, cam, thr, cnt, s1, s2, (hipStream_t)stream);
+    const char* fn = "sfm_pnp_score";
+    return checked_entry(fn, check_call(fn, sample_size, n, h_count, batch, K, cam), h_count == 0 || batch == 0,
+                         !pts || !model || !S || !cnt || !s1 || !s2, [&] {
+        return launch_score(sample_size, pts, n, model, S, h_count, batch, cam, thr, cnt, s1, s2, (hipStream_t)stream);
+    });
 }
 
 int sfm_pnp_inlier_mask(const double* pts, int64_t n, const double* model, const int32_t* S, int64_t h_count, int64_t batch,
                         const double* K, const sfm_select_result* result, double thr, int sample_size, uint8_t* mask, void* stream) {
     PnPCamera cam;
-    const int rc = check_call("sfm_pnp_inlier_mask", sample_size, n, h_count, batch, K, cam);
-    if (rc != SFM_OK) return rc;
-    if (batch == 0) return SFM_OK;
-    if (!pts || !model || !S || !result || !mask) return fail_in("sfm_pnp_inlier_mask", "null pointer");
-    return launch_mask(sample_size, pts, n, model, S, h_count, batch, cam, result, thr, mask, (hipStream_t)stream);
+    const char* fn = "sfm_pnp_inlier_mask";
+    return checked_entry(fn, check_call(fn, sample_size, n, h_count, batch, K, cam), batch == 0, !pts || !model || !S || !result || !mask, [&] {
+        return launch_mask(sample_size, pts, n, model, S, h_count, batch, cam, result, thr, mask, (hipStream_t)stream);
+    });
 }
 
 int sfm_pnp_ransac_pass(int solver, uint64_t seed, uint64_t seed_stride, int use_philox, int64_t h_begin, const double* pts, int64_t n,

@@ -27,6 +27,7 @@
 #include "sfm_homography.h"
 #include "sfm_math.h"
 #include "sfm_minimal_fit.h"
+#include "sfm_minimal_score.h"
 #include "sfm_select.h"
 
 static_assert(sizeof(sfm_pair_verdict) == 24, "sfm_pair_verdict is 24 bytes");
@@ -40,8 +41,7 @@ using sfmhost::grid_for;
 using sfmhost::grid_stride;
 
 constexpr int kFitBlock = sfmmin::kMinimalFitBlock;
-constexpr int kScoreBlock = 256;
-constexpr int kTile = 512;   // correspondences per tile: 512 x 32 B = 16 KiB of LDS
+using sfmmin::kScoreBlock;
 constexpr int kSelectBlock = 1024;
 constexpr int kCheckBlock = 1024;
 constexpr int kHSample = sfmhg::kHomographySample, kESample = sfm5::kFiveSample;
@@ -115,63 +115,19 @@ __global__ __launch_bounds__(kFitBlock) void ragged_fit_kernel(const Corr* __res
     *flag = fit_flag;
 }
 
-// Error of one item under one lane's model: the symmetric transfer error with H and adj(H), or the SED with E.
-template <bool ESSENTIAL>
-struct ItemError {
-    double m[9], g[9];
-    SFM_DEVICE explicit ItemError(const double* __restrict__ model) {
-#pragma unroll
-        for (int i = 0; i < 9; ++i) m[i] = model[i];
-        if constexpr (!ESSENTIAL) sfmhg::adjugate(m, g);
-    }
-    SFM_DEVICE double operator()(const Corr& t) const {
-        if constexpr (ESSENTIAL) return sfm::sed_value(m, t.xa, t.ya, t.xb, t.yb);
-        else return sfmhg::transfer_error(m, g, t.xa, t.ya, t.xb, t.yb);
-    }
-};
-
-// The loop of homography_score_kernel (sfm_homography.hip) over one pair's items: every item counted in the tile loop, the SAMPLE
-// sample items then corrected — one that passed the gate leaves the count (its value is in the sums), one that did not joins the sums.
-template <bool ESSENTIAL>
-SFM_DEVICE void score_rows(Corr* tile, const PairItems& p, const double* __restrict__ model, const int32_t* __restrict__ S,
-                           int64_t q, int64_t h_count, double thr, int32_t* __restrict__ cnt, double* __restrict__ s1,
-                           double* __restrict__ s2) {
-    constexpr int SAMPLE = ESSENTIAL ? kESample : kHSample;
+// One hypothesis per lane over its pair's items: sfmmin::score_hypothesis (sfm_minimal_score.h) with the pair's items, the
+// lane's row of S and the model that z selected.
+template <class Model, int SAMPLE>
+SFM_DEVICE void score_pair(Corr* tile, const PairItems& p, const double* __restrict__ model, const int32_t* __restrict__ S, int64_t q,
+                           int64_t h_count, double thr, int32_t* __restrict__ cnt, double* __restrict__ s1, double* __restrict__ s2) {
     const int64_t h = (int64_t)blockIdx.x * kScoreBlock + threadIdx.x;
     const int64_t hc = h < h_count ? h : h_count - 1;   // lanes past the end score a valid hypothesis and store nothing
     const int64_t qh = q * h_count + hc;
-    const ItemError<ESSENTIAL> error(model + qh * 9);
-    int c = 0;
-    double a1 = 0.0, a2 = 0.0;
-    for (int64_t base = 0; base < p.n; base += kTile) {
-        const int count = (int)(p.n - base < kTile ? p.n - base : kTile);
-        __syncthreads();   // the previous tile has been read by every lane
-        for (int i = threadIdx.x; i < count; i += kScoreBlock) tile[i] = p.pts[base + i];
-        __syncthreads();
-#pragma unroll 4
-        for (int j = 0; j < count; ++j) {
-            const double e = error(tile[j]);
-            const bool in = e <= thr;
-            c += in ? 1 : 0;
-            a1 += in ? e : 0.0;
-            a2 += in ? e * e : 0.0;
-        }
-    }
-    bool bad = false;
-#pragma unroll
-    for (int k = 0; k < SAMPLE; ++k) {
-        const double e = error(p.pts[checked_index(S[qh * 8 + k], p.n, bad)]);
-        if (e <= thr) {
-            --c;
-        } else {
-            a1 += e;
-            a2 += e * e;
-        }
-    }
+    const sfmmin::HypothesisScore r = sfmmin::score_hypothesis<SAMPLE>(tile, Model(model + qh * 9), p.pts, p.n, S + qh * 8, thr);
     if (h < h_count) {
-        cnt[q * h_count + h] = c;
-        s1[q * h_count + h] = a1;
-        s2[q * h_count + h] = a2;
+        cnt[q * h_count + h] = r.c;
+        s1[q * h_count + h] = r.a1;
+        s2[q * h_count + h] = r.a2;
     }
 }
 
@@ -182,7 +138,7 @@ __global__ __launch_bounds__(kScoreBlock) void ragged_score_kernel(const Corr* _
                                                                    int32_t* __restrict__ h_cnt, double* __restrict__ h_s1,
                                                                    double* __restrict__ h_s2, int32_t* __restrict__ e_cnt,
                                                                    double* __restrict__ e_s1, double* __restrict__ e_s2) {
-    __shared__ Corr tile[kTile];
+    __shared__ Corr tile[sfmmin::kScoreTile];
     const int64_t q = blockIdx.y;
     const bool essential = blockIdx.z != 0;   // uniform over the block, like everything tested before a barrier below
     const PairItems p = pair_items(corr, offset, verdict, q);
@@ -195,8 +151,8 @@ __global__ __launch_bounds__(kScoreBlock) void ragged_score_kernel(const Corr* _
         }
         return;
     }
-    if (essential) score_rows<true>(tile, p, E, S, q, h_count, thr, e_cnt, e_s1, e_s2);
-    else score_rows<false>(tile, p, H, S, q, h_count, thr, h_cnt, h_s1, h_s2);
+    if (essential) score_pair<sfm5::essential_model, kESample>(tile, p, E, S, q, h_count, thr, e_cnt, e_s1, e_s2);
+    else score_pair<sfmhg::homography_model, kHSample>(tile, p, H, S, q, h_count, thr, h_cnt, h_s1, h_s2);
 }
 
 // The per-pair form of the selection: block (q, model) runs the one definition of sfm_select.h over pair q's h_count rows
@@ -230,35 +186,19 @@ __global__ void ragged_mask_kernel(const Corr* __restrict__ corr, int64_t n_tota
     const bool bad = verdict[0].kind == SFM_PAIR_BAD_OFFSETS;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_total; i += stride) {
-        // the first k in [0, pairs] with offset[k] > i: item i belongs to pair k - 1 when 1 <= k <= pairs
-        int64_t lo = 0, hi = pairs + 1;
-        while (lo < hi) {
-            const int64_t mid = (lo + hi) >> 1;
-            if (offset[mid] > i) hi = mid;
-            else lo = mid + 1;
-        }
+        const int64_t q = bad ? -1 : pair_of_item(offset, pairs, i);
         uint8_t hm = 0, em = 0;
-        if (!bad && lo >= 1 && lo <= pairs) {
-            const int64_t q = lo - 1, local = i - offset[q];
+        if (q >= 0) {
+            const int64_t local = i - offset[q];
             const Corr t = corr[i];
             const int64_t hb = h_result[q].best_h, eb = e_result[q].best_h;
             if (hb >= 0 && hb < h_count) {
                 const int64_t qh = q * h_count + hb;
-                const ItemError<false> error(H + qh * 9);
-                bool in_sample = false;
-#pragma unroll
-                for (int k = 0; k < kHSample; ++k) in_sample |= (S[qh * 8 + k] == (int32_t)local);
-                hm = in_sample ? 2 : ((error(t) <= thr) ? 1 : 0);
+                hm = sfmmin::mask_value<kHSample>(sfmhg::homography_model(H + qh * 9), S + qh * 8, t, local, thr);
             }
             if (eb >= 0 && eb < h_count) {
                 const int64_t qh = q * h_count + eb;
-                double e[9];
-                int32_t smp[kESample];
-#pragma unroll
-                for (int k = 0; k < 9; ++k) e[k] = E[qh * 9 + k];
-#pragma unroll
-                for (int k = 0; k < kESample; ++k) smp[k] = S[qh * 8 + k];
-                em = sfmsel::mask_value<kESample>(e, smp, t, local, thr);
+                em = sfmmin::mask_value<kESample>(sfm5::essential_model(E + qh * 9), S + qh * 8, t, local, thr);
             }
         }
         h_mask[i] = hm;

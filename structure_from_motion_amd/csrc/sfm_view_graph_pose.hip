@@ -114,17 +114,7 @@ __global__ __launch_bounds__(kCheiralityBlock) void pose_cheirality_kernel(const
     for (int s = 0; s < kChunkItems; s += kWave) {
         const int64_t i = base + s + lane;
         const bool inside = i < n_total;
-        int64_t q = -1;
-        if (inside && !bad) {
-            // the first k in [0, pairs] with offset[k] > i: item i belongs to pair k - 1 when 1 <= k <= pairs
-            int64_t lo = 0, hi = pairs + 1;
-            while (lo < hi) {
-                const int64_t mid = (lo + hi) >> 1;
-                if (offset[mid] > i) hi = mid;
-                else lo = mid + 1;
-            }
-            q = (lo >= 1 && lo <= pairs) ? lo - 1 : -1;
-        }
+        const int64_t q = (inside && !bad) ? pair_of_item(offset, pairs, i) : -1;
         const bool act = q >= 0 && pose[q].status == SFM_POSE_OK && e_mask[i] != 0;
         if (inside) {
             angle[i] = NAN;

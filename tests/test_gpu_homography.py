@@ -14,7 +14,7 @@ pytestmark = pytest.mark.gpu
 
 K = synthetic.BENCH_K
 THR = 2e-5
-TILE = 512   # kHomographyTile of csrc/sfm_homography.hip
+TILE = 512   # kScoreTile of csrc/sfm_minimal_score.h
 
 
 @pytest.fixture(scope="module")

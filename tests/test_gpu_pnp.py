@@ -78,9 +78,9 @@ def test_fit_flags_coplanar(dev):
     assert flags.tolist() == [1, 0, 1, 1]
 
 
-def _oracle_sums(pts, model, S, thr):
+def _oracle_sums(pts, model, S, thr, sample=6):
     """(cnt, s1, s2) with the device's summation order: survivors and passing sample points in index order, then the sample
-    points that did not pass, in sample order."""
+    points (the first ``sample`` entries of a row of S) that did not pass, in sample order."""
     h = model.shape[0]
     cnt = np.zeros(h, dtype=np.int32)
     s1, s2 = np.zeros(h), np.zeros(h)
@@ -88,7 +88,7 @@ def _oracle_sums(pts, model, S, thr):
         e = orc.score_values(model[k, :9].reshape(3, 3), model[k, 9:], K, pts)
         with np.errstate(invalid="ignore"):
             passed = e <= thr
-        smp = S[k, :6]
+        smp = S[k, :sample]
         a1 = np.cumsum(e[passed])[-1] if passed.any() else 0.0
         a2 = np.cumsum(e[passed] * e[passed])[-1] if passed.any() else 0.0
         c = int(np.count_nonzero(passed))
@@ -129,6 +129,62 @@ def test_score_parity(dev, n):
         c_o, s1_o, s2_o = _oracle_sums(pts, model, S, thr)
         assert np.array_equal(cnt, c_o), (thr, np.nonzero(cnt != c_o)[0][:5])
         assert _close(s1, s1_o, 1e-13) and _close(s2, s2_o, 1e-13), thr
+
+
+TILE, BLOCK = 512, 256   # kScoreTile and kScoreBlock of csrc/sfm_minimal_score.h
+
+
+@pytest.mark.parametrize("sample", [4, 6])
+@pytest.mark.parametrize("h", [1, BLOCK - 1, BLOCK + 1])
+@pytest.mark.parametrize("n", ["sample", TILE - 1, TILE, TILE + 1, 2 * TILE + 1])
+def test_score_mask_at_tile_and_block_edges(dev, n, h, sample):
+    """The scorer and the mask at their own edges, with two different scenes in one call (so the b * n * 5 item stride and
+    b * h_count are exercised): one point set that is exactly the sample, one point short of a tile, a full tile, one point
+    into the second tile and into the third; one hypothesis, one lane short of a block and one lane into the second.  The
+    device's own models on both sides: cnt exact, s1 and s2 within 1e-13 relative (the values are the oracle's bit for bit,
+    only the summation order differs), the mask byte-equal to the host rule for the selected winner, all zero over a buffer
+    of 7s for a record without a winner, and count 0 everywhere under a NaN threshold."""
+    from structure_from_motion_amd import device
+
+    n = sample if n == "sample" else n
+    thr = 4.0
+    outliers = 0.0 if n == sample else 0.3
+    pts = np.stack([orc.scene(n, seed=80 + 2 * (n % 89) + b, K=K, outlier_fraction=outliers, noise_px=0.02)[0] for b in range(2)])
+    if n > sample:   # (where every sample is the whole point set, a point behind the camera would leave no winner)
+        pts = np.stack([_with_behind(pts[b], 0.05, n + b) for b in range(2)])
+    S = np.zeros((2, h, 8), dtype=np.int32)
+    for b in range(2):
+        rng = np.random.default_rng(1000 * n + 10 * h + b)
+        S[b, :, :sample] = np.array([rng.choice(n, sample, replace=False) for _ in range(h)])
+    pts_d, S_d = device.to_device(pts), device.to_device(S, torch.int32)
+    model_d, flags_d = (device.p3p_fit if sample == 4 else device.pnp_fit)(pts_d, S_d, K)
+    model = model_d.cpu().numpy()
+    cnt_d, s1_d, s2_d = device.pnp_score(pts_d, model_d, S_d, K, thr, sample_size=sample)
+    cnt, s1, s2 = cnt_d.cpu().numpy(), s1_d.cpu().numpy(), s2_d.cpu().numpy()
+    for b in range(2):
+        c_o, s1_o, s2_o = _oracle_sums(pts[b], model[b], S[b], thr, sample)
+        assert np.array_equal(cnt[b], c_o), (b, np.nonzero(cnt[b] != c_o)[0][:5])
+        assert _close(s1[b], s1_o, 1e-13) and _close(s2[b], s2_o, 1e-13), b
+    min_extra = 0 if n == sample else 10
+    result = device.select_best(cnt_d, s1_d, s2_d, flags_d, min_extra, AGG["rms"], sample_size=sample)
+    rec = device.read_select(result)
+    mask = device.pnp_inlier_mask(pts_d, model_d, S_d, K, result, thr, sample_size=sample).cpu().numpy()
+    for b in range(2):
+        best = rec[b].best_h
+        assert best >= 0 or h == 1, (b, h)
+        expected = np.zeros(n, dtype=np.uint8)
+        if best >= 0:
+            e = orc.score_values(model[b, best, :9].reshape(3, 3), model[b, best, 9:], K, pts[b])
+            with np.errstate(invalid="ignore"):
+                expected[e <= thr] = 1
+            expected[S[b, best, :sample]] = 2
+        assert np.array_equal(mask[b], expected), (b, np.nonzero(mask[b] != expected)[0][:5])
+    nothing = device.select_best(cnt_d, s1_d, s2_d, flags_d, n + 1, AGG["rms"], sample_size=sample)
+    assert all(r.best_h == -1 for r in device.read_select(nothing))
+    filled = torch.full((2, n), 7, dtype=torch.uint8, device=pts_d.device)
+    device.pnp_inlier_mask(pts_d, model_d, S_d, K, nothing, thr, out=filled, sample_size=sample)
+    assert not filled.any()
+    assert not device.pnp_score(pts_d, model_d, S_d, K, float("nan"), sample_size=sample)[0].any()
 
 
 def _pair_data(n, seed, outliers=0.3):
