@@ -19,6 +19,7 @@
 #include "sfm_math.h"
 #include "sfm_fit.h"
 #include "sfm_decompose.h"
+#include "sfm_cheirality.h"
 #include "sfm_score_ws.h"
 #include "sfm_matrix_tables.h"
 #include "sfm_select.h"
@@ -655,7 +656,7 @@ __global__ void sed_values_kernel(const Corr* __restrict__ corr, int64_t n, cons
 }
 
 // ------------------------------------------------------------------------------------------------
-// Cheirality (eight_point.py:449-488): one lane per (pose, pair).  P1 = I4, P2 = [R t; 0 0 0 1].
+// Cheirality (eight_point.py:449-488): one lane per (pose, pair), the test of sfm_cheirality.h.
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kWave) void cheirality_kernel(const Corr* __restrict__ corr, int64_t m,
                                                            const double* __restrict__ pose_rt,
@@ -665,23 +666,7 @@ __global__ __launch_bounds__(kWave) void cheirality_kernel(const Corr* __restric
     const bool active = i_raw < m;
     const int64_t i = active ? i_raw : m - 1;
     const int pose = blockIdx.y;
-    const double* rt = pose_rt + pose * 12;
-    double P1[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-    double P2[12];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        P2[r * 4 + 0] = rt[r * 3 + 0];
-        P2[r * 4 + 1] = rt[r * 3 + 1];
-        P2[r * 4 + 2] = rt[r * 3 + 2];
-        P2[r * 4 + 3] = rt[9 + r];
-    }
-    const Corr p = corr[i];
-    double X[3];
-    sfm::triangulate_dlt(P1, P2, p.xa, p.ya, p.xb, p.yb, X);
-    // depth in camera 2: third row of P2 @ [X, 1] (eight_point.py:476), left to right
-    const double z2 = ((P2[8] * X[0] + P2[9] * X[1]) + P2[10] * X[2]) + P2[11];
-    const double norm = sqrt((X[0] * X[0] + X[1] * X[1]) + X[2] * X[2]);
-    const bool ok = (X[2] >= -1e-8) && (z2 >= -1e-8) && (norm <= distance_threshold);
+    const bool ok = sfmchi::cheirality_test(pose_rt + pose * 12, corr[i], distance_threshold).ok;
     if (active) pass[(int64_t)pose * m + i] = ok ? 1 : 0;
 }
 

@@ -3,11 +3,13 @@
 // on GPU").  These entry points chain after sfm_select_best / sfm_inlier_mask without a host round
 // trip; together they are the device form of reference eight_point.py:181-242 (_recover_r_t) and
 // triangulation.py:42-62 (triangulate_points) applied to the RANSAC inliers, as apps/sfm.py:110-186 does.
+// The test, the chunk compaction and the vote are those of sfm_cheirality.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "sfm_common.h"
 #include "sfm_math.h"
+#include "sfm_cheirality.h"
 
 namespace {
 
@@ -15,73 +17,52 @@ using sfmhost::check_launch;
 using sfmhost::fail;
 using sfmhost::grid_for;
 
-// Cheirality test (eight_point.py:449-488) of every correspondence of every pair under its 4 candidate
-// poses.  Points whose inlier mask is 0 are reported as not passing — and cost nothing: each wave first compacts
-// the inliers of its 512-point chunk (ballot + prefix count into an LDS list), then runs the DLT solves only on
-// full 64-lane groups of inliers.  With the usual 30-40 % inliers that is ~3 passes per chunk instead of 8 per pose.
-constexpr int kChunkPoints = 512;
+// Cheirality test (sfm_cheirality.h) of every correspondence of every pair under its 4 candidate poses.  Points whose inlier
+// mask is 0 are reported as not passing — and cost nothing: each wave first compacts the inliers of its 512-point chunk, then
+// runs the DLT solves only on full 64-lane groups of inliers.  With the usual 30-40 % inliers that is ~3 passes per chunk
+// instead of 8 per pose.
+using sfmchi::kChunk;
 
 __global__ __launch_bounds__(256) void cheirality_batched_kernel(
     const Corr* __restrict__ corr, int64_t n, const double* __restrict__ pose_rt,
     const uint8_t* __restrict__ mask, double distance_threshold, uint8_t* __restrict__ pass) {
-    __shared__ int32_t list[256 / kWave][kChunkPoints];
+    __shared__ int32_t list[256 / kWave][kChunk];
     const int wave = threadIdx.x / kWave, lane = threadIdx.x & (kWave - 1);
     const int64_t b = blockIdx.y;
-    const int64_t base = ((int64_t)blockIdx.x * (256 / kWave) + wave) * kChunkPoints;
+    const int64_t base = ((int64_t)blockIdx.x * (256 / kWave) + wave) * kChunk;
     if (base >= n) return;  // whole wave; no block-level barrier below
     const uint8_t* m = mask != nullptr ? mask + b * n : nullptr;
-    uint8_t* out = pass + b * 4 * n;
     // The four candidates come in two antipodal pairs, (R, t) and (R, -t) (eight_point.py:210-212; sfm_decompose_essential writes
-    // them so): with P1 = [I | 0] the DLT null vector of (R, -t) is that of (R, t) with its last component negated — X' = -X —
-    // and R X' - t = -(R X + t), so both depths change sign and the norm stays: ONE solve decides both poses.  Taken only when
-    // the second pose of a pair IS the first with t negated, bit for bit (block-uniform); any other pose table is solved pose
-    // by pose.  One pair of poses per block in z (more waves in flight; the compaction is cheap enough to repeat).
+    // them so), and one solve decides both (sfm_cheirality.h).  Taken only when the second pose of a pair IS the first with t
+    // negated, bit for bit (block-uniform); any other pose table is solved pose by pose.  One pair of poses per block in z (more
+    // waves in flight; the compaction is cheap enough to repeat).
     const int pose_begin = 2 * (int)blockIdx.z;
     const double* rt0 = pose_rt + (b * 4 + pose_begin) * 12;
     const double* rt1 = rt0 + 12;
     bool antipodal = true;
 #pragma unroll
     for (int k = 0; k < 12; ++k) antipodal = antipodal && (k < 9 ? rt1[k] == rt0[k] : rt1[k] == -rt0[k]);
-    int total = 0;  // wave-uniform
-    for (int s = 0; s < kChunkPoints; s += kWave) {
-        const int64_t i = base + s + lane;
+    uint8_t* out0 = pass + (b * 4 + pose_begin) * n;   // the rows of this block's two poses
+    uint8_t* out1 = out0 + n;
+    const int total = sfmchi::compact_chunk<kChunk>(list[wave], lane, [&](int position, int32_t& entry) {
+        const int64_t i = base + position;
         const bool inside = i < n;
         const bool act = inside && (m == nullptr || m[i] != 0);
         if (inside && !act) {
-            out[pose_begin * n + i] = 0;
-            out[(pose_begin + 1) * n + i] = 0;
+            out0[i] = 0;
+            out1[i] = 0;
         }
-        const unsigned long long votes = __ballot(act);
-        const int before = __builtin_amdgcn_mbcnt_hi((unsigned)(votes >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)votes, 0));
-        if (act) list[wave][total + before] = s + lane;
-        total += (int)__popcll(votes);
-    }
-    const double P1[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+        entry = position;
+        return act;
+    });
     for (int j = 0; j < total; j += kWave) {
-        const bool active = j + lane < total;
-        // tail lanes redo the group's first point so the wave-uniform Jacobi loops see valid data
-        const int64_t i = base + list[wave][active ? j + lane : j];
+        bool active;
+        const int64_t i = base + sfmchi::group_entry(list[wave], j, lane, total, active);
         const Corr p = corr[b * n + i];
         for (int k = 0; k < (antipodal ? 1 : 2); ++k) {
-            const double* rt = k == 0 ? rt0 : rt1;
-            double P2[12];
-#pragma unroll
-            for (int r = 0; r < 3; ++r) {
-                P2[r * 4 + 0] = rt[r * 3 + 0];
-                P2[r * 4 + 1] = rt[r * 3 + 1];
-                P2[r * 4 + 2] = rt[r * 3 + 2];
-                P2[r * 4 + 3] = rt[9 + r];
-            }
-            double X[3];
-            sfm::triangulate_dlt(P1, P2, p.xa, p.ya, p.xb, p.yb, X);
-            const double z2 = ((P2[8] * X[0] + P2[9] * X[1]) + P2[10] * X[2]) + P2[11];
-            const double norm = sqrt((X[0] * X[0] + X[1] * X[1]) + X[2] * X[2]);
-            const bool ok = (X[2] >= -1e-8) && (z2 >= -1e-8) && (norm <= distance_threshold);
-            if (active) out[(pose_begin + k) * n + i] = ok ? 1 : 0;
-            if (antipodal) {   // the mirrored pose: -X, -z2, the same norm (NaN fails both, as it does when solved)
-                const bool mirrored = (-X[2] >= -1e-8) && (-z2 >= -1e-8) && (norm <= distance_threshold);
-                if (active) out[(pose_begin + 1) * n + i] = mirrored ? 1 : 0;
-            }
+            const sfmchi::Cheirality c = sfmchi::cheirality_test(k == 0 ? rt0 : rt1, p, distance_threshold);
+            if (active) (k == 0 ? out0 : out1)[i] = c.ok ? 1 : 0;
+            if (antipodal && active) out1[i] = c.mirrored ? 1 : 0;
         }
     }
 }
@@ -101,26 +82,14 @@ __global__ __launch_bounds__(256) void pose_vote_kernel(const uint8_t* __restric
 #pragma unroll
         for (int p = 0; p < 4; ++p) cnt[p] += use & (int)pass[(b * 4 + p) * n + i];
     }
-    __shared__ int partial[4][4];
-    const int wave = threadIdx.x / kWave, lane = threadIdx.x & (kWave - 1);
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        const int total = sfm::wave_sum(cnt[p]);
-        if (lane == 0) partial[wave][p] = total;
-    }
-    __syncthreads();
+    __shared__ int partial[256 / kWave][4];
+    int v[4];
+    sfmchi::block_votes(cnt, partial, v);
     if (threadIdx.x == 0) {
-        int v[4];
-        int arg = -1, top = 0;
+        int arg, top;
+        sfmchi::first_maximum(v, arg, top);
 #pragma unroll
-        for (int p = 0; p < 4; ++p) {
-            v[p] = partial[0][p] + partial[1][p] + partial[2][p] + partial[3][p];
-            votes[b * 4 + p] = v[p];
-            if (v[p] > top) {  // strict: the first maximum wins (np.argmax)
-                top = v[p];
-                arg = p;
-            }
-        }
+        for (int p = 0; p < 4; ++p) votes[b * 4 + p] = v[p];
         best[b] = arg;
     }
 }
@@ -135,18 +104,17 @@ __global__ __launch_bounds__(256) void triangulate_selected_kernel(
     const double2* __restrict__ pix_a, const double2* __restrict__ pix_b, int64_t n, Intrinsics K,
     const double* __restrict__ pose_rt, const int32_t* __restrict__ best, const uint8_t* __restrict__ pass,
     double* __restrict__ X, uint8_t* __restrict__ valid) {
-    // same wave-level compaction as cheirality_batched_kernel: DLT solves only for the points that passed
-    __shared__ int32_t list[256 / kWave][kChunkPoints];
+    // DLT solves only for the points that passed
+    __shared__ int32_t list[256 / kWave][kChunk];
     const int wave = threadIdx.x / kWave, lane = threadIdx.x & (kWave - 1);
     const int64_t b = blockIdx.y;
-    const int64_t base = ((int64_t)blockIdx.x * (256 / kWave) + wave) * kChunkPoints;
+    const int64_t base = ((int64_t)blockIdx.x * (256 / kWave) + wave) * kChunk;
     if (base >= n) return;
     const int pose = best[b];
     const bool have_pose = pose >= 0;
     const uint8_t* chosen = pass + (b * 4 + (have_pose ? pose : 0)) * n;
-    int total = 0;
-    for (int s = 0; s < kChunkPoints; s += kWave) {
-        const int64_t i = base + s + lane;
+    const int total = sfmchi::compact_chunk<kChunk>(list[wave], lane, [&](int position, int32_t& entry) {
+        const int64_t i = base + position;
         const bool inside = i < n;
         const bool keep = inside && have_pose && chosen[i] != 0;
         if (inside && !keep) {
@@ -156,11 +124,9 @@ __global__ __launch_bounds__(256) void triangulate_selected_kernel(
             out[2] = 0.0;
             valid[b * n + i] = 0;
         }
-        const unsigned long long votes = __ballot(keep);
-        const int before = __builtin_amdgcn_mbcnt_hi((unsigned)(votes >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)votes, 0));
-        if (keep) list[wave][total + before] = s + lane;
-        total += (int)__popcll(votes);
-    }
+        entry = position;
+        return keep;
+    });
     if (total == 0) return;
     const double* rt = pose_rt + (b * 4 + pose) * 12;
     double P1[12], P2[12];
@@ -175,8 +141,8 @@ __global__ __launch_bounds__(256) void triangulate_selected_kernel(
         P2[r * 4 + 3] = (K.k[r * 3 + 0] * rt[9 + 0] + K.k[r * 3 + 1] * rt[9 + 1]) + K.k[r * 3 + 2] * rt[9 + 2];
     }
     for (int j = 0; j < total; j += kWave) {
-        const bool active = j + lane < total;
-        const int64_t i = base + list[wave][active ? j + lane : j];
+        bool active;
+        const int64_t i = base + sfmchi::group_entry(list[wave], j, lane, total, active);
         const double2 a = pix_a[b * n + i];
         const double2 q = pix_b[b * n + i];
         double Xp[3];
@@ -203,8 +169,8 @@ int sfm_cheirality_batched(const double* corr, int64_t n, int64_t batch, const d
     if (!corr || !pose_rt || !pass) return fail(SFM_EINVAL, "sfm_cheirality_batched: null pointer");
     // one antipodal pair of poses per block in z (one pose per block until round 5: 5.08 ms per C5 batch vs 5.29 with all four
     // poses in one wave, profiles/r01/README.md; the pair shares its solve now)
-    SFM_REQUIRE_GRID("sfm_cheirality_batched", n, kChunkPoints * (256 / kWave), 256, batch);
-    hipLaunchKernelGGL(cheirality_batched_kernel, dim3(grid_for(n, kChunkPoints * (256 / kWave)), (unsigned)batch, 2),
+    SFM_REQUIRE_GRID("sfm_cheirality_batched", n, kChunk * (256 / kWave), 256, batch);
+    hipLaunchKernelGGL(cheirality_batched_kernel, dim3(grid_for(n, kChunk * (256 / kWave)), (unsigned)batch, 2),
                        dim3(256), 0, (hipStream_t)stream, (const Corr*)corr, n, pose_rt, mask, distance_threshold, pass);
     return check_launch("cheirality_batched_kernel");
 }
@@ -229,8 +195,8 @@ int sfm_triangulate_selected(const double* pix_a, const double* pix_b, int64_t n
         return fail(SFM_EINVAL, "sfm_triangulate_selected: null pointer");
     Intrinsics intr;
     for (int j = 0; j < 9; ++j) intr.k[j] = K[j];  // host pointer, passed by value
-    SFM_REQUIRE_GRID("sfm_triangulate_selected", n, kChunkPoints * (256 / kWave), 256, batch);
-    hipLaunchKernelGGL(triangulate_selected_kernel, dim3(grid_for(n, kChunkPoints * (256 / kWave)), (unsigned)batch),
+    SFM_REQUIRE_GRID("sfm_triangulate_selected", n, kChunk * (256 / kWave), 256, batch);
+    hipLaunchKernelGGL(triangulate_selected_kernel, dim3(grid_for(n, kChunk * (256 / kWave)), (unsigned)batch),
                        dim3(256), 0, (hipStream_t)stream, (const double2*)pix_a, (const double2*)pix_b, n, intr, pose_rt, best,
                        pass, X, valid);
     return check_launch("triangulate_selected_kernel");

@@ -2,7 +2,7 @@
 // (sfm_view_graph.hip) on that call's buffers: per pair the four poses of its winning essential matrix, the cheirality vote of
 // its inliers (the items with e_mask != 0, all of them), the winning pose and the lower median of the angle between the two
 // viewing rays of the items that pass under it.  The decomposition is sfmdec::decompose_essential (sfm_decompose.h, the body of
-// sfm_decompose_essential), the solve is sfm::triangulate_dlt and the test is that of cheirality_batched_kernel (sfm_pose.hip).
+// sfm_decompose_essential); the solve and test, the chunk compaction and the vote are those of sfm_cheirality.h.
 //
 // Three launches whatever the number of pairs, nothing read back:
 //   1. pose_decompose_kernel    one lane per pair: status, the four candidates (workspace), the filler of a pair without a pose
@@ -20,6 +20,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "sfm_cheirality.h"
 #include "sfm_common.h"
 #include "sfm_decompose.h"
 #include "sfm_math.h"
@@ -33,7 +34,7 @@ using sfmhost::check_launch;
 using sfmhost::fail_in;
 using sfmhost::grid_for;
 
-constexpr int kChunkItems = 512;      // items per wave in the cheirality walk
+using sfmchi::kChunk;                 // items per wave in the cheirality walk
 constexpr int kCheiralityBlock = 256;
 constexpr int kMedianBlock = 256;     // one thread per bin of the digit histogram
 constexpr int kCandidateDoubles = 48; // four poses of R (9) | t (3)
@@ -93,10 +94,8 @@ __global__ __launch_bounds__(kWave) void pose_decompose_kernel(const double* __r
     else pose[q].status = SFM_POSE_OK;
 }
 
-// The cheirality test of cheirality_batched_kernel over the concatenated items: an item is solved when its pair has candidates
-// and its e_mask is not 0.  With P1 = [I | 0] the null vector of (R, -t) is that of (R, t) with its last component negated, so
-// X' = -X, both depths change sign and the norm stays: one solve decides both poses of an antipodal pair (the candidates are
-// written so by the decomposition).  NaN fails every test.
+// The cheirality test (sfm_cheirality.h) over the concatenated items: an item is solved when its pair has candidates and its
+// e_mask is not 0.  The decomposition writes candidates 2k and 2k + 1 as an antipodal pair, so two solves decide all four.
 __global__ __launch_bounds__(kCheiralityBlock) void pose_cheirality_kernel(const Corr* __restrict__ corr, int64_t n_total,
                                                                            const int64_t* __restrict__ offset, int64_t pairs,
                                                                            const sfm_pair_verdict* __restrict__ verdict,
@@ -105,14 +104,13 @@ __global__ __launch_bounds__(kCheiralityBlock) void pose_cheirality_kernel(const
                                                                            const double* __restrict__ candidates,
                                                                            double distance_threshold, uint8_t* __restrict__ pass,
                                                                            double* __restrict__ angle) {
-    __shared__ int32_t list[kCheiralityBlock / kWave][kChunkItems];   // (pair << 9) | position in the chunk; pair <= 65534
+    __shared__ int32_t list[kCheiralityBlock / kWave][kChunk];   // (pair << 9) | position in the chunk; pair <= 65534
     const int wave = threadIdx.x / kWave, lane = threadIdx.x & (kWave - 1);
-    const int64_t base = ((int64_t)blockIdx.x * (kCheiralityBlock / kWave) + wave) * kChunkItems;
+    const int64_t base = ((int64_t)blockIdx.x * (kCheiralityBlock / kWave) + wave) * kChunk;
     if (base >= n_total) return;   // whole wave; no block-level barrier below
     const bool bad = verdict[0].kind == SFM_PAIR_BAD_OFFSETS;
-    int total = 0;   // wave-uniform
-    for (int s = 0; s < kChunkItems; s += kWave) {
-        const int64_t i = base + s + lane;
+    const int total = sfmchi::compact_chunk<kChunk>(list[wave], lane, [&](int position, int32_t& entry) {
+        const int64_t i = base + position;
         const bool inside = i < n_total;
         const int64_t q = (inside && !bad) ? pair_of_item(offset, pairs, i) : -1;
         const bool act = q >= 0 && pose[q].status == SFM_POSE_OK && e_mask[i] != 0;
@@ -120,38 +118,20 @@ __global__ __launch_bounds__(kCheiralityBlock) void pose_cheirality_kernel(const
             angle[i] = NAN;
             if (!act) pass[i] = 0;
         }
-        const unsigned long long votes = __ballot(act);
-        const int before = __builtin_amdgcn_mbcnt_hi((unsigned)(votes >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)votes, 0));
-        if (act) list[wave][total + before] = (int32_t)(q << 9) | (s + lane);
-        total += (int)__popcll(votes);
-    }
-    const double P1[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+        entry = (int32_t)(q << 9) | position;
+        return act;
+    });
     for (int j = 0; j < total; j += kWave) {
-        const bool active = j + lane < total;
-        // tail lanes redo the group's first item so the wave-uniform Jacobi loops see valid data
-        const int32_t entry = list[wave][active ? j + lane : j];
-        const int64_t i = base + (entry & (kChunkItems - 1));
+        bool active;
+        const int32_t entry = sfmchi::group_entry(list[wave], j, lane, total, active);
+        const int64_t i = base + (entry & (kChunk - 1));
         const double* __restrict__ cand = candidates + (int64_t)(entry >> 9) * kCandidateDoubles;
         const Corr p = corr[i];
         unsigned bits = 0;
 #pragma unroll 1
-        for (int k = 0; k < 2; ++k) {
-            const double* rt = cand + k * 24;   // candidates 0 and 2: (R1, t), (R2, t)
-            double P2[12];
-#pragma unroll
-            for (int r = 0; r < 3; ++r) {
-                P2[r * 4 + 0] = rt[r * 3 + 0];
-                P2[r * 4 + 1] = rt[r * 3 + 1];
-                P2[r * 4 + 2] = rt[r * 3 + 2];
-                P2[r * 4 + 3] = rt[9 + r];
-            }
-            double X[3];
-            sfm::triangulate_dlt(P1, P2, p.xa, p.ya, p.xb, p.yb, X);
-            const double z2 = ((P2[8] * X[0] + P2[9] * X[1]) + P2[10] * X[2]) + P2[11];
-            const double norm = sqrt((X[0] * X[0] + X[1] * X[1]) + X[2] * X[2]);
-            const bool ok = (X[2] >= -1e-8) && (z2 >= -1e-8) && (norm <= distance_threshold);
-            const bool mirrored = (-X[2] >= -1e-8) && (-z2 >= -1e-8) && (norm <= distance_threshold);
-            bits |= (ok ? 1u : 0u) << (2 * k) | (mirrored ? 1u : 0u) << (2 * k + 1);
+        for (int k = 0; k < 2; ++k) {   // candidates 0 and 2: (R1, t), (R2, t)
+            const sfmchi::Cheirality c = sfmchi::cheirality_test(cand + k * 24, p, distance_threshold);
+            bits |= (c.ok ? 1u : 0u) << (2 * k) | (c.mirrored ? 1u : 0u) << (2 * k + 1);
         }
         if (active) pass[i] = (uint8_t)bits;
     }
@@ -193,24 +173,9 @@ __global__ __launch_bounds__(kMedianBlock) void pose_vote_median_kernel(const Co
 #pragma unroll
         for (int p = 0; p < 4; ++p) cnt[p] += (b >> p) & 1;
     }
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        const int total = sfm::wave_sum(cnt[p]);
-        if (lane == 0) partial[wave][p] = total;
-    }
-    __syncthreads();
-    int votes[4];
-    int best = -1, top = 0;
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        votes[p] = 0;
-#pragma unroll
-        for (int w = 0; w < kMedianBlock / kWave; ++w) votes[p] += partial[w][p];
-        if (votes[p] > top) {   // strict: the first maximum wins
-            top = votes[p];
-            best = p;
-        }
-    }
+    int votes[4], best, top;
+    sfmchi::block_votes(cnt, partial, votes);
+    sfmchi::first_maximum(votes, best, top);
     if (best < 0) {   // block-uniform
         if (threadIdx.x == 0) write_filler(pose + q, SFM_POSE_NO_VOTE);
         return;
@@ -310,7 +275,7 @@ int sfm_pair_poses(const double* corr, int64_t n_total, const int64_t* offset, i
     hipLaunchKernelGGL(pose_decompose_kernel, dim3(grid_for(pairs, kWave)), dim3(kWave), 0, st, E, h_count, e_result, verdict, pairs,
                        ws.candidates, pose);
     if (n_total > 0)
-        hipLaunchKernelGGL(pose_cheirality_kernel, dim3(grid_for(n_total, kChunkItems * (kCheiralityBlock / kWave))),
+        hipLaunchKernelGGL(pose_cheirality_kernel, dim3(grid_for(n_total, kChunk * (kCheiralityBlock / kWave))),
                            dim3(kCheiralityBlock), 0, st, items, n_total, offset, pairs, verdict, e_mask, pose, ws.candidates,
                            distance_threshold, ws.pass, ws.angle);
     hipLaunchKernelGGL(pose_vote_median_kernel, dim3((unsigned)pairs), dim3(kMedianBlock), 0, st, items, n_total, offset, ws.candidates,
