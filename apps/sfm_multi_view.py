@@ -154,6 +154,7 @@ def _verified_matches(K, pix_a, pix_b, m, sed_threshold: float, iterations: int,
     """The matches m ((n, 2) local indices) that the essential-matrix RANSAC winner keeps (its sample and its survivors,
     taken by index from the engine's inlier mask), or None when no model wins."""
     from structure_from_motion_amd.epipolar import _engine
+    from structure_from_motion_amd.ransac._device_route import run_pass
     from structure_from_motion_amd.ransac.ransac import ErrorAggregationMethod, aggregation_code
 
     n = len(m)
@@ -162,13 +163,8 @@ def _verified_matches(K, pix_a, pix_b, m, sed_threshold: float, iterations: int,
     corr = device.normalize_correspondences(device.to_device(pix_a[m[:, 0]]), device.to_device(pix_b[m[:, 1]]), K)
     ws = device.RansacWorkspace(1, n, iterations)
     _, _, philox = _engine.draw_samples(ws.S, n, iterations)
-    agg = aggregation_code(ErrorAggregationMethod.RMS)
-    if e_solver == "five_point":
-        ws.run(corr.reshape(1, n, 4), sed_threshold, int(0.4 * n), agg, philox=philox, solver=e_solver)
-    else:
-        if philox is not None:
-            device.sample_philox(philox[0], 0, iterations, n, out=ws.S)
-        ws.run(corr.reshape(1, n, 4), sed_threshold, int(0.4 * n), agg)
+    run_pass(e_solver, ws, corr.reshape(1, n, 4), sed_threshold, int(0.4 * n), aggregation_code(ErrorAggregationMethod.RMS),
+             philox)
     outcome = ws.outcome(0)
     if outcome.best_h < 0:
         return None

@@ -560,16 +560,44 @@ class PyShuffleTable:
 # ------------------------------------------------------------------------------------------------------
 # the RANSAC engine: sample table -> fit -> score -> select -> mask, all enqueued on one stream
 # ------------------------------------------------------------------------------------------------------
+def model_matrix(row: np.ndarray) -> np.ndarray:
+    """A 9-entry model row (E or H, row-major) as a fresh (3,3) array."""
+    return row.reshape(3, 3).copy()
+
+
+def model_pose(row: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """A 12-entry model row R (9) | t (3) as fresh (3,3) and (3,) arrays."""
+    return row[:9].reshape(3, 3).copy(), row[9:].copy()
+
+
 @dataclass
-class RansacOutcome:
+class PassOutcome:
+    """What one entry of a RANSAC pass left, on the host (``_PassWorkspace.outcome``)."""
     best_h: int                # winning hypothesis (global index), -1 if none
     error: float               # aggregated inlier error of the winner
-    E: Optional[np.ndarray]    # (3,3) essential matrix of the winner
-    sample: Optional[np.ndarray]   # (8,) indices of the winner's sample, in sample order ((6,) after a five-point pass)
+    model: Optional[np.ndarray]    # the winner's row, a flat copy: 9 entries (E or H) or 12 (R | t); None without a winner
+    sample: Optional[np.ndarray]   # indices of the winner's sample, in sample order (as many as the pass's solver takes)
     mask: Optional[np.ndarray]     # (N,) uint8: 1 survivor, 2 sample point, 0 outlier
     n_flagged: int             # hypotheses whose sample was degenerate (eight_point.py:415-421)
     first_flagged: int         # lowest such hypothesis index, or -1
     extra_inliers: int
+
+    @property
+    def E(self) -> Optional[np.ndarray]:
+        """(3,3) of the winner of an essential or homography pass."""
+        return None if self.model is None else model_matrix(self.model)
+
+    H = E
+
+    @property
+    def R(self) -> Optional[np.ndarray]:
+        """(3,3) of the winner of a pose pass."""
+        return None if self.model is None else model_pose(self.model)[0]
+
+    @property
+    def t(self) -> Optional[np.ndarray]:
+        """(3,) of the winner of a pose pass."""
+        return None if self.model is None else model_pose(self.model)[1]
 
 
 def checked_mask(mask: np.ndarray) -> np.ndarray:
@@ -598,18 +626,18 @@ class _PassWorkspace:
         self.mask = torch.empty((batch, n), dtype=torch.uint8, device=dev)
         self.sample_size = sample_size   # of the last pass (outcome reads it)
 
-    def _winner(self, b: int, h_offset: int = 0):
-        """Entry b's record and winner on the host -> (best_h, error, model row, sample, mask, n_flagged, first_flagged,
-        extra_inliers), the fields of every outcome class in their order; model row, sample and mask None without a winner."""
+    def outcome(self, b: int = 0, h_offset: int = 0) -> PassOutcome:
+        """Entry b's record and winner on the host (synchronises); ``h_offset``: the global index of this pass's hypothesis 0."""
         rec = read_select(self.result)[b]
         first = -1 if rec.first_flagged == _native.INT64_MAX else int(rec.first_flagged)
         if rec.best_h < 0:
-            return -1, float("inf"), None, None, None, int(rec.n_flagged), first, 0
+            return PassOutcome(-1, float("inf"), None, None, None, int(rec.n_flagged), first, 0)
         local = int(rec.best_h) - h_offset
         model = self.model[b, local].cpu().numpy()
         sample = self.S[b, local, :self.sample_size].cpu().numpy().astype(np.int64)
         mask = checked_mask(self.mask[b].cpu().numpy().copy())
-        return int(rec.best_h), float(rec.best_err), model, sample, mask, int(rec.n_flagged), first, int(rec.best_cnt)
+        return PassOutcome(int(rec.best_h), float(rec.best_err), model, sample, mask, int(rec.n_flagged), first,
+                           int(rec.best_cnt))
 
 
 class RansacWorkspace(_PassWorkspace):
@@ -678,13 +706,9 @@ class RansacWorkspace(_PassWorkspace):
             assert h_offset == 0, "mask needs local hypothesis indices"
             inlier_mask(corr, self.E, self.S, self.result, thr, self.mask)
 
-    def outcome(self, b: int = 0, h_offset: int = 0) -> RansacOutcome:
-        best_h, error, E, *rest = self._winner(b, h_offset)
-        return RansacOutcome(best_h, error, None if E is None else E.reshape(3, 3).copy(), *rest)
 
-
-def ransac_essential(corr: torch.Tensor, S, thr: float, min_extra: float, aggregation: int) -> RansacOutcome:
-    """One image pair: corr [N,4] on device, S [H,8] (numpy or tensor) -> RansacOutcome."""
+def ransac_essential(corr: torch.Tensor, S, thr: float, min_extra: float, aggregation: int) -> PassOutcome:
+    """One image pair: corr [N,4] on device, S [H,8] (numpy or tensor) -> PassOutcome."""
     n = corr.shape[0]
     S_t = S if isinstance(S, torch.Tensor) else to_device(S, torch.int32)
     h = S_t.shape[0]
@@ -952,19 +976,6 @@ def read_track_build_info(info: torch.Tensor) -> TrackBuildInfo:
     return TrackBuildInfo(*(int(v) for v in raw[:6]))
 
 
-@dataclass
-class PnPOutcome:
-    best_h: int                # winning hypothesis, -1 if none
-    error: float               # aggregated inlier error of the winner
-    R: Optional[np.ndarray]    # (3,3) of the winner
-    t: Optional[np.ndarray]    # (3,)
-    sample: Optional[np.ndarray]   # (6,) indices of the winner's sample, in sample order ((4,) for P3P)
-    mask: Optional[np.ndarray]     # (N,) uint8: 1 survivor, 2 sample point, 0 outlier
-    n_flagged: int             # hypotheses whose sample was degenerate
-    first_flagged: int         # lowest such hypothesis index, or -1
-    extra_inliers: int
-
-
 class PnPWorkspace(_PassWorkspace):
     """Pre-allocated device buffers of a PnP pass for B views x H hypotheses x N 2D-3D pairs (as RansacWorkspace)."""
 
@@ -1002,12 +1013,6 @@ class PnPWorkspace(_PassWorkspace):
             mask[rows, self.S[rows, best_h, 3].long().clamp(min=0)] = 0
         return pnp_refine(pts, model, mask, err, K, thr, aggregation, rounds, max_steps)
 
-    def outcome(self, b: int = 0) -> PnPOutcome:
-        best_h, error, m, *rest = self._winner(b)
-        if m is None:
-            return PnPOutcome(best_h, error, None, None, *rest)
-        return PnPOutcome(best_h, error, m[:9].reshape(3, 3).copy(), m[9:].copy(), *rest)
-
 
 # ------------------------------------------------------------------------------------------------------
 # RANSAC homography (csrc/sfm_homography.hip): corr [B,N,4] = {xa, ya, xb, yb}, S [B,H,8] (first 4 entries used),
@@ -1029,18 +1034,6 @@ def homography_inlier_mask(corr: torch.Tensor, H: torch.Tensor, S: torch.Tensor,
     return ops.load().homography_inlier_mask(corr, H, S, result, float(thr))
 
 
-@dataclass
-class HomographyOutcome:
-    best_h: int                # winning hypothesis, -1 if none
-    error: float               # aggregated inlier error of the winner
-    H: Optional[np.ndarray]    # (3,3) of the winner
-    sample: Optional[np.ndarray]   # (4,) indices of the winner's sample, in sample order
-    mask: Optional[np.ndarray]     # (N,) uint8: 1 survivor, 2 sample point, 0 outlier
-    n_flagged: int             # hypotheses whose sample was degenerate
-    first_flagged: int         # lowest such hypothesis index, or -1
-    extra_inliers: int
-
-
 class HomographyWorkspace(_PassWorkspace):
     """Pre-allocated device buffers of a homography pass for B pairs x H hypotheses x N correspondences."""
 
@@ -1055,10 +1048,6 @@ class HomographyWorkspace(_PassWorkspace):
         ops.load().homography_ransac_pass_(corr, _as_int64(seed), _as_int64(stride), philox is not None, h_begin, float(thr),
                                            float(min_extra), int(aggregation), self.S, self.H, self.flags, self.cnt, self.s1,
                                            self.s2, self.result, self.mask if with_mask else None)
-
-    def outcome(self, b: int = 0) -> HomographyOutcome:
-        best_h, error, m, *rest = self._winner(b)
-        return HomographyOutcome(best_h, error, None if m is None else m.reshape(3, 3).copy(), *rest)
 
 
 # ------------------------------------------------------------------------------------------------------

@@ -16,7 +16,6 @@ import torch
 
 from .. import _native, device
 from ..common.feature import Feature
-from ..ransac.ransac import solver_sample_size
 
 
 _GET_X, _GET_Y = attrgetter("x"), attrgetter("y")
@@ -182,145 +181,3 @@ def inlier_order(table, outcome, sample_size: int) -> np.ndarray:
 
 
 logger = logging.getLogger(__name__)   # one line per call, never per hypothesis
-
-
-def ransac_feature_pairs(data, camera_matrix, threshold, min_extra, aggregation, iterations, solver="eight_point"):
-    """Device route of fit_with_ransac for (Feature, Feature) pairs.  Returns (E or None, inlier pairs).
-
-    Sampler ``pyshuffle`` (default) draws the hypothesis samples from the global ``random`` state
-    exactly like the reference's cumulative ``random.shuffle`` (ransac.py:59-64) and advances it;
-    ``philox`` (``SFM_SAMPLER=philox``, seed ``SFM_SEED`` or 64 bits from ``random``) is the
-    counter-based sampler for large H, generated on the device.
-
-    ``solver="five_point"``: six-item samples (the first six entries of the same tables) fitted by the five-point solver
-    (DESIGN.md §6l); a degenerate sample raises ``FivePointCalculationError`` under the default policy.
-    """
-    from .eight_point import EightPointCalculationError
-    from .five_point import FivePointCalculationError
-
-    sample_size = solver_sample_size("essential", solver)
-    n = len(data)
-    if solver == "five_point":
-        if n < 6:
-            raise ValueError("Six feature pairs are expected.")
-        if local_optimisation_rounds():
-            # the refit would take item 5 (which only picked the solution, and may be an outlier) as a sample point
-            raise ValueError("SFM_LOCAL_OPTIMIZATION is not supported with solver='five_point'")
-    if iterations <= 0:
-        return None, []
-    if n < 8 and solver == "eight_point":
-        # reference: data[:8] is short, eight_point_model_fitter raises (epipolar_ransac.py:31-32)
-        raise ValueError("Eight feature pairs are expected.")
-    dev = device.require_gpu()
-    pix = device.to_device(pair_arrays(data))   # one upload: [2, n, 2]
-    corr = device.normalize_correspondences(pix[0], pix[1], camera_matrix)
-    ws = device.RansacWorkspace(1, n, iterations, dev)
-    sampler, table, philox = draw_samples(ws.S, n, iterations)
-    if solver == "five_point":
-        # the Philox samples are drawn inside the fit launch (positions >= n are -1, so n = 6 and 7 are valid)
-        ws.run(corr.reshape(1, n, 4), threshold, min_extra, aggregation, philox=philox, solver=solver)
-    else:
-        if philox is not None:
-            device.sample_philox(philox[0], 0, iterations, n, out=ws.S)
-        ws.run(corr.reshape(1, n, 4), threshold, min_extra, aggregation)
-    outcome = ws.outcome(0)
-    if outcome.n_flagged and degenerate_policy() == "raise" and solver == "five_point":
-        raise FivePointCalculationError(
-            f"A sampled six-tuple is degenerate for the five-point solver (hypothesis {outcome.first_flagged},"
-            f" {outcome.n_flagged} in total)")
-    if outcome.n_flagged and degenerate_policy() == "raise":
-        raise EightPointCalculationError(
-            "More than one eigenvalue of Y.T @ Y is small. Cannot confidently estimate"
-            f" fundamental matrix. (hypothesis {outcome.first_flagged}, {outcome.n_flagged} in total)"
-        )
-    if logger.isEnabledFor(logging.DEBUG):
-        logger.debug("RANSAC-E: %d matches x %d hypotheses (%s sampler): best hypothesis %d, %d extra inliers, "
-                     "aggregated error %.6g, %d degenerate sample(s)", n, iterations, sampler, outcome.best_h,
-                     outcome.extra_inliers, outcome.error, outcome.n_flagged)
-    if outcome.best_h < 0:
-        return None, []
-    rounds = local_optimisation_rounds()
-    if rounds:
-        # extension (SURVEY.md §8f rank 4): the refined model has no "sample", so its inliers come back in
-        # index order; an unrefined winner (no refit accepted) falls through to the reference's ordering
-        err = ws.result.view(torch.float64)[:, 2]
-        E_ref, mask_ref, info = device.refine_inliers(corr.reshape(1, n, 4), ws.E[:, outcome.best_h], ws.mask, err,
-                                                      threshold, aggregation, rounds)
-        if device.read_refine_info(info)[0][2] > 0:
-            keep = np.nonzero(mask_ref.cpu().numpy()[0])[0]
-            return E_ref.cpu().numpy().reshape(3, 3), copy_pairs(data, keep)
-    return outcome.E, copy_pairs(data, inlier_order(table, outcome, sample_size))
-
-
-def ransac_homography_pairs(data, camera_matrix, threshold, min_extra, aggregation, iterations):
-    """Device route of fit_with_ransac for (Feature, Feature) pairs and the four-point homography solver.
-    Returns (H (3, 3) or None, inlier pairs), with the samplers, inlier order and copies of ``ransac_feature_pairs``; a
-    degenerate sample raises ``HomographyCalculationError`` under the default policy."""
-    from .homography import HomographyCalculationError
-
-    sample_size = solver_sample_size("homography", "homography")
-    n = len(data)
-    if n < sample_size:
-        raise ValueError("Four feature pairs are expected.")
-    if iterations <= 0:
-        return None, []
-    dev = device.require_gpu()
-    pix = device.to_device(pair_arrays(data))   # one upload: [2, n, 2]
-    corr = device.normalize_correspondences(pix[0], pix[1], camera_matrix)
-    ws = device.HomographyWorkspace(1, n, iterations, dev)
-    sampler, table, philox = draw_samples(ws.S, n, iterations)
-    ws.run(corr.reshape(1, n, 4), threshold, min_extra, aggregation, philox=philox)
-    outcome = ws.outcome(0)
-    if outcome.n_flagged and degenerate_policy() == "raise":
-        raise HomographyCalculationError(
-            "A sampled four-tuple does not determine a homography (a repeated pair or three collinear points)."
-            f" (hypothesis {outcome.first_flagged}, {outcome.n_flagged} in total)")
-    if logger.isEnabledFor(logging.DEBUG):
-        logger.debug("RANSAC-H: %d matches x %d hypotheses (%s sampler): best hypothesis %d, %d extra inliers, "
-                     "aggregated error %.6g, %d degenerate sample(s)", n, iterations, sampler, outcome.best_h,
-                     outcome.extra_inliers, outcome.error, outcome.n_flagged)
-    if outcome.best_h < 0:
-        return None, []
-    return outcome.H, copy_pairs(data, inlier_order(table, outcome, sample_size))
-
-
-def two_view_passes(data, camera_matrix, threshold, min_extra, aggregation, iterations, essential_solver):
-    """The homography pass and the essential pass of ``homography.select_two_view_model`` over one upload of the pairs and
-    one sample table: the homography pass reads the first four entries of each row, the essential pass the first six or
-    eight of the same rows.  Flagged hypotheses never compete and never raise.  Returns (H or None, its inlier pairs, its
-    count, E or None, its inlier pairs, its count), a count being the winner's sample size plus its extra inliers.  Fewer
-    pairs than the essential solver's sample leave E without a winner."""
-    h_size = solver_sample_size("homography", "homography")
-    e_size = solver_sample_size("essential", essential_solver)
-    n = len(data)
-    if n < h_size:
-        raise ValueError("Four feature pairs are expected.")
-    if iterations <= 0:
-        return None, [], 0, None, [], 0
-    dev = device.require_gpu()
-    pix = device.to_device(pair_arrays(data))   # one upload: [2, n, 2]
-    corr = device.normalize_correspondences(pix[0], pix[1], camera_matrix).reshape(1, n, 4)
-    hws = device.HomographyWorkspace(1, n, iterations, dev)
-    sampler, table, philox = draw_samples(hws.S, n, iterations)
-    hws.run(corr, threshold, min_extra, aggregation, philox=philox)   # Philox: drawn in the fit launch, which fills S
-    results = []
-    passes = [(hws, h_size, "H")]
-    if n >= e_size:
-        ews = device.RansacWorkspace(1, n, iterations, dev)
-        ews.S.copy_(hws.S)   # the same rows: a Philox row holds all eight entries of its sample
-        ews.run(corr, threshold, min_extra, aggregation, solver=essential_solver)
-        passes.append((ews, e_size, "E"))
-    for ws, size, name in passes:
-        outcome = ws.outcome(0)
-        if logger.isEnabledFor(logging.DEBUG):
-            logger.debug("RANSAC-%s: %d matches x %d hypotheses (%s sampler): best hypothesis %d, %d extra inliers, "
-                         "aggregated error %.6g, %d degenerate sample(s)", name, n, iterations, sampler, outcome.best_h,
-                         outcome.extra_inliers, outcome.error, outcome.n_flagged)
-        if outcome.best_h < 0:
-            results += [None, [], 0]
-        else:
-            model = outcome.H if name == "H" else outcome.E
-            results += [model, copy_pairs(data, inlier_order(table, outcome, size)), size + outcome.extra_inliers]
-    if len(passes) == 1:
-        results += [None, [], 0]
-    return tuple(results)

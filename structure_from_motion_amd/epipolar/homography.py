@@ -218,13 +218,15 @@ def select_two_view_model(
 
     Raises ``ValueError`` for fewer than four matches, an unknown ``essential_solver``, or when neither model has a
     winner.  Telling a plane from a pure rotation, decomposing H and refitting the winner are out of scope."""
+    from ..ransac._device_route import two_view_passes
+
     K = _check_call(camera_matrix, matches)
     solver_sample_size("essential", essential_solver)   # ValueError for an unknown solver
     iterations = DEFAULT_MAX_ITERATIONS if max_iterations is None else max_iterations
     min_extra = 0 if min_num_extra_inliers is None else min_num_extra_inliers
     with _engine.gc_paused():
         pairs = _engine.match_pairs(features_a, features_b, matches)
-        h, h_inliers, h_count, e, e_inliers, e_count = _engine.two_view_passes(
+        h, h_inliers, h_count, e, e_inliers, e_count = two_view_passes(
             pairs, K, inlier_threshold, min_extra, aggregation_code(ErrorAggregationMethod.RMS), iterations, essential_solver)
     if h is None and e is None:
         raise ValueError("Could not estimate an essential matrix or a homography with RANSAC.")

@@ -18,7 +18,8 @@ import numpy.typing as npt
 from ..common.feature import Feature
 from ..epipolar import _engine
 from ..feature_matching.matching import Match
-from ..ransac.ransac import DEFAULT_MAX_ITERATIONS, ErrorAggregationMethod, aggregation_code, fit_with_ransac, solver_sample_size
+from ..ransac.ransac import (DEFAULT_MAX_ITERATIONS, DeviceSpec, ErrorAggregationMethod, aggregation_code, fit_with_ransac,
+                             solver_sample_size)
 from . import p3p
 
 PnPItem = Tuple[npt.NDArray, Feature]
@@ -223,15 +224,15 @@ def _items(points_3d, features, matches):
 
 def _ransac_refined(K, points_3d, features, matches, threshold, min_extra, method, max_iterations, rounds, solver="dlt"):
     """The device route of fit_with_ransac (the one the tagged pair takes) with the refinement chained after the pass."""
-    from . import _engine as pnp_engine
+    from ..ransac._device_route import ransac_on_device
 
     iterations = DEFAULT_MAX_ITERATIONS if max_iterations is None else max_iterations
     method = ErrorAggregationMethod.RMS if method is None else method
     min_extra = 0 if min_extra is None else min_extra
     with _engine.gc_paused():
         items = _items(points_3d, features, matches)
-        model, inliers = pnp_engine.ransac_pnp_items(items, K, threshold, min_extra, aggregation_code(method), iterations,
-                                                     refine_rounds=rounds, solver=solver)
+        model, inliers = ransac_on_device(items, DeviceSpec(K, solver), threshold, min_extra, aggregation_code(method),
+                                          iterations, refine_rounds=rounds)
     if model is None:
         raise ValueError(f"No model could be found with at least {min_extra + solver_sample_size('pose', solver)} inliers.")
     R, t = model

@@ -2,14 +2,10 @@
 
 Two execution routes behind one signature:
 
-* when ``model_fitter`` / ``inlier_scorer`` are the eight-point fitter and SED scorer of
-  ``epipolar_ransac`` (which is what ``estimate_essential_mat_with_ransac`` passes, exactly like the
-  reference's ``epipolar_ransac.py:58-67``), the whole loop — fit, H x N scoring, gate, aggregation,
-  selection — runs as HIP kernels on the MI355X (``device.RansacWorkspace``), and so does the five-point fitter of
-  ``epipolar_ransac`` with ``model_fit_data_count == 6``; likewise for the six-point PnP fitter
-  and reprojection scorer of ``pnp.pnp`` with ``model_fit_data_count == 6``, and its P3P fitter with
-  ``model_fit_data_count == 4`` (``device.PnPWorkspace``), and the four-point homography fitter and transfer-error
-  scorer of ``epipolar.homography`` (``device.HomographyWorkspace``);
+* when ``model_fitter`` / ``inlier_scorer`` are partials of a tagged fitter and the scorer of its model with that
+  solver's sample size (the table ``SOLVERS`` below; it is what ``estimate_essential_mat_with_ransac`` passes, exactly
+  like the reference's ``epipolar_ransac.py:58-67``), the whole loop — fit, H x N scoring, gate, aggregation,
+  selection — runs as HIP kernels on the MI355X (``_device_route.ransac_on_device``);
 * for arbitrary Python callables (e.g. the 2-point line fitter of the reference's own
   ``test_ransac.py``) the loop is host logic: there is nothing to put on a GPU.
 
@@ -69,26 +65,11 @@ def fit_with_ransac(
     min_extra = 0 if min_num_extra_inliers is None else min_num_extra_inliers
 
     spec = _device_spec(model_fitter, inlier_scorer, model_fit_data_count)
-    if isinstance(spec, PnPDeviceSpec):
-        from ..pnp import _engine as pnp_engine
+    if spec is not None:
+        from . import _device_route
 
-        model, inliers = pnp_engine.ransac_pnp_items(
-            data, spec.camera_matrix, inlier_threshold, min_extra, aggregation_code(method), iterations, solver=spec.solver)
-    elif isinstance(spec, EssentialDeviceSpec):
-        from ..epipolar import _engine
-
-        model, inliers = _engine.ransac_feature_pairs(
-            data, spec.camera_matrix, inlier_threshold, min_extra, aggregation_code(method), iterations, solver=spec.solver)
-    elif isinstance(spec, HomographyDeviceSpec):
-        from ..epipolar import _engine
-
-        model, inliers = _engine.ransac_homography_pairs(
-            data, spec.camera_matrix, inlier_threshold, min_extra, aggregation_code(method), iterations)
-    elif spec is not None:
-        from ..epipolar import _engine
-
-        model, inliers = _engine.ransac_feature_pairs(
-            data, spec, inlier_threshold, min_extra, aggregation_code(method), iterations)
+        model, inliers = _device_route.ransac_on_device(data, spec, inlier_threshold, min_extra, aggregation_code(method),
+                                                        iterations)
     else:
         model, inliers = _host_loop(data, model_fit_data_count, model_fitter, inlier_scorer,
                                     inlier_threshold, min_extra, method, iterations)
@@ -125,27 +106,15 @@ def solver_sample_size(model: str, solver: str) -> int:
     return SOLVERS[solver].sample_size
 
 
-class PnPDeviceSpec(NamedTuple):
-    """Device route of a PnP fitter (six-point DLT or P3P) / reprojection scorer pair."""
+class DeviceSpec(NamedTuple):
+    """Device route of a tagged fitter / scorer pair: the camera matrix both were bound to and the key of ``SOLVERS``."""
     camera_matrix: np.ndarray
-    solver: str = "dlt"
-
-
-class EssentialDeviceSpec(NamedTuple):
-    """Device route of the five-point fitter / SED scorer pair (the eight-point pair routes as a bare camera matrix)."""
-    camera_matrix: np.ndarray
-    solver: str = "five_point"
-
-
-class HomographyDeviceSpec(NamedTuple):
-    """Device route of the four-point homography fitter / transfer-error scorer pair."""
-    camera_matrix: np.ndarray
+    solver: str
 
 
 def _device_spec(model_fitter, inlier_scorer, model_fit_data_count):
     """For partials of a tagged fitter (``SOLVERS``) and the scorer of its model, with that solver's sample size and one
-    camera matrix: the bare camera matrix for the eight-point fitter, an EssentialDeviceSpec for the five-point one, a
-    PnPDeviceSpec for the DLT and P3P, a HomographyDeviceSpec for the homography fitter; else None."""
+    camera matrix: the DeviceSpec of that matrix and solver; else None."""
     fit_fn = getattr(model_fitter, "func", None)
     score_fn = getattr(inlier_scorer, "func", None)
     if fit_fn is None or score_fn is None:
@@ -161,12 +130,7 @@ def _device_spec(model_fitter, inlier_scorer, model_fit_data_count):
     k_score = inlier_scorer.keywords.get("camera_matrix") if not inlier_scorer.args else None
     if k_fit is None or k_score is None or not np.array_equal(np.asarray(k_fit), np.asarray(k_score)):
         return None
-    K = np.asarray(k_fit, dtype=np.float64)
-    if spec.model == "pose":
-        return PnPDeviceSpec(K, solver)
-    if spec.model == "homography":
-        return HomographyDeviceSpec(K)
-    return K if solver == "eight_point" else EssentialDeviceSpec(K, solver)
+    return DeviceSpec(np.asarray(k_fit, dtype=np.float64), solver)
 
 
 def _host_loop(data, k, model_fitter, inlier_scorer, threshold, min_extra, method, iterations):

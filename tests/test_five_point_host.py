@@ -152,11 +152,11 @@ def test_routing_and_argument_errors():
     fit = partial(er.five_point_model_fitter, camera_matrix=K)
     score = partial(er.calculate_sed_inlier_score, camera_matrix=K)
     spec = ransac._device_spec(fit, score, 6)
-    assert isinstance(spec, ransac.EssentialDeviceSpec) and spec.solver == "five_point"
+    assert isinstance(spec, ransac.DeviceSpec) and spec.solver == "five_point" and np.array_equal(spec.camera_matrix, K)
     assert ransac._device_spec(fit, score, 8) is None
     assert ransac._device_spec(fit, partial(er.calculate_sed_inlier_score, camera_matrix=2 * K), 6) is None
     eight = ransac._device_spec(partial(er.eight_point_model_fitter, camera_matrix=K), score, 8)
-    assert isinstance(eight, np.ndarray)
+    assert isinstance(eight, ransac.DeviceSpec) and eight.solver == "eight_point" and np.array_equal(eight.camera_matrix, K)
     feats = [Feature(float(i), float(i * i % 7)) for i in range(5)]
     matches = [Match(a_index=i, b_index=i) for i in range(5)]
     with pytest.raises(ValueError, match="solver"):

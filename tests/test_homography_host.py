@@ -154,7 +154,7 @@ def test_solver_table_and_routing():
     K = np.array(ho.synthetic.BENCH_K)
     fit, score = partial(hg.homography_model_fitter, camera_matrix=K), partial(hg.calculate_transfer_error_score, camera_matrix=K)
     spec = ransac._device_spec(fit, score, 4)
-    assert isinstance(spec, ransac.HomographyDeviceSpec) and np.array_equal(spec.camera_matrix, K)
+    assert isinstance(spec, ransac.DeviceSpec) and spec.solver == "homography" and np.array_equal(spec.camera_matrix, K)
     assert ransac._device_spec(fit, score, 6) is None
     from structure_from_motion_amd.epipolar import epipolar_ransac as er
 

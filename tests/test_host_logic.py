@@ -432,7 +432,8 @@ def test_device_route_detection():
     K = np.eye(3)
     fit = partial(er.eight_point_model_fitter, camera_matrix=K)
     score = partial(er.calculate_sed_inlier_score, camera_matrix=K)
-    assert np.array_equal(ransac._device_spec(fit, score, 8), K)
+    spec = ransac._device_spec(fit, score, 8)
+    assert isinstance(spec, ransac.DeviceSpec) and spec.solver == "eight_point" and np.array_equal(spec.camera_matrix, K)
     assert ransac._device_spec(fit, score, 7) is None
     assert ransac._device_spec(line_fitter_2d, line_scorer_2d, 8) is None
     assert ransac._device_spec(fit, partial(er.calculate_sed_inlier_score, camera_matrix=2 * K), 8) is None

@@ -123,19 +123,19 @@ def test_routing():
     fit = partial(pnp.p3p_model_fitter, camera_matrix=K)
     score = partial(pnp.calculate_reprojection_score, camera_matrix=K)
     spec = ransac._device_spec(fit, score, 4)
-    assert isinstance(spec, ransac.PnPDeviceSpec) and spec.solver == "p3p" and np.array_equal(spec.camera_matrix, K)
+    assert isinstance(spec, ransac.DeviceSpec) and spec.solver == "p3p" and np.array_equal(spec.camera_matrix, K)
     assert ransac._device_spec(fit, score, 6) is None
     assert ransac._device_spec(lambda items: None, score, 4) is None
     assert ransac._device_spec(fit, partial(pnp.calculate_reprojection_score, camera_matrix=2 * K), 4) is None
     # the existing routes are unchanged
     dlt = ransac._device_spec(partial(pnp.pnp_model_fitter, camera_matrix=K), score, 6)
-    assert isinstance(dlt, ransac.PnPDeviceSpec) and dlt.solver == "dlt"
+    assert isinstance(dlt, ransac.DeviceSpec) and dlt.solver == "dlt" and np.array_equal(dlt.camera_matrix, K)
     assert ransac._device_spec(partial(pnp.pnp_model_fitter, camera_matrix=K), score, 4) is None
     from structure_from_motion_amd.epipolar import epipolar_ransac as er
 
     e_spec = ransac._device_spec(partial(er.eight_point_model_fitter, camera_matrix=K),
                                  partial(er.calculate_sed_inlier_score, camera_matrix=K), 8)
-    assert isinstance(e_spec, np.ndarray)
+    assert isinstance(e_spec, ransac.DeviceSpec) and e_spec.solver == "eight_point" and np.array_equal(e_spec.camera_matrix, K)
 
 
 def test_argument_errors_before_device_work(monkeypatch):

@@ -79,7 +79,7 @@ def test_routing():
     fit = partial(pnp.pnp_model_fitter, camera_matrix=K)
     score = partial(pnp.calculate_reprojection_score, camera_matrix=K)
     spec = ransac._device_spec(fit, score, 6)
-    assert isinstance(spec, ransac.PnPDeviceSpec) and np.array_equal(spec.camera_matrix, K)
+    assert isinstance(spec, ransac.DeviceSpec) and spec.solver == "dlt" and np.array_equal(spec.camera_matrix, K)
     assert ransac._device_spec(fit, score, 7) is None
     assert ransac._device_spec(fit, score, 8) is None
     assert ransac._device_spec(fit, partial(pnp.calculate_reprojection_score, camera_matrix=2 * K), 6) is None
@@ -89,12 +89,12 @@ def test_routing():
 
 def test_untagged_callables_take_host_loop(monkeypatch):
     """Untagged callables (and a tagged pair with another sample size) run _host_loop and never touch the device."""
-    from structure_from_motion_amd.pnp import _engine
+    from structure_from_motion_amd.ransac import _device_route
 
     def no_device(*args, **kwargs):
         raise AssertionError("device route taken")
 
-    monkeypatch.setattr(_engine, "ransac_pnp_items", no_device)
+    monkeypatch.setattr(_device_route, "ransac_on_device", no_device)
     pts, R, t = orc.scene(60, seed=6, K=K, outlier_fraction=0.2, noise_px=0.2)
     items = _items(pts)
     random.seed(3)
