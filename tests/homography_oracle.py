@@ -1,7 +1,7 @@
 """The NumPy definition of the homography kernels (csrc/sfm_homography.hip): the four-point DLT fit with
 np.linalg.svd, the symmetric transfer error, the score table, the selection rule and the mask, a host RANSAC loop through
-ransac.fit_with_ransac with untagged callables, and the scenes.  Imported by tests/test_homography_host.py and
-tests/test_gpu_homography.py."""
+ransac.fit_with_ransac with untagged callables, and the scenes.  Imported by tests/test_homography_host.py,
+tests/test_gpu_homography.py and, through tests/homography_cases.py, by the tests of the special motions, planes and samples."""
 import random
 
 import numpy as np
@@ -21,16 +21,24 @@ MOTIONS = {
 }
 
 
+PLANE = (5.0, 0.2, -0.1)   # z = z0 + a x + b y of the planar scenes
+
+
 def scene(R, t, planar, n, seed, noise_px=0.0, outlier_fraction=0.0, K=synthetic.BENCH_K):
-    """Points uniform in x, y in [-1, 1] and z in [4, 6], or (planar) on the plane z = 5 + 0.2 x - 0.1 y, seen by [I | 0] and
-    [R | t]: dict(pix_a, pix_b (n, 2) pixels, corr (n, 4) K-normalised {xa, ya, xb, yb}, K, R, t, is_outlier (n,)).  Gaussian
-    noise of noise_px pixels on both views before normalising; an outlier is a uniform pixel in view 2."""
+    """Points uniform in x, y in [-1, 1] and z in [4, 6], or (planar True) on the plane z = 5 + 0.2 x - 0.1 y, or (planar a
+    tuple (z0, a, b)) on the plane z = z0 + a x + b y, seen by [I | 0] and [R | t]: dict(pix_a, pix_b (n, 2) pixels, corr
+    (n, 4) K-normalised {xa, ya, xb, yb}, K, R, t, is_outlier (n,)).  Gaussian noise of noise_px pixels on both views before
+    normalising; an outlier is a uniform pixel in view 2."""
     rng = np.random.default_rng(seed)
     X = np.empty((n, 3))
     X[:, 0] = rng.uniform(-1.0, 1.0, n)
     X[:, 1] = rng.uniform(-1.0, 1.0, n)
     z = rng.uniform(4.0, 6.0, n)
-    X[:, 2] = 5.0 + 0.2 * X[:, 0] - 0.1 * X[:, 1] if planar else z
+    if planar is False:
+        X[:, 2] = z
+    else:
+        z0, a, b = PLANE if planar is True else planar
+        X[:, 2] = z0 + a * X[:, 0] + b * X[:, 1]
     X2 = X @ R.T + t
     assert (X[:, 2] > 0.0).all() and (X2[:, 2] > 0.0).all()
 
@@ -133,11 +141,11 @@ def transfer_error(H, corr):
     """Symmetric transfer error of every item of corr (n, 4) under one H (9,), fixed operation order; +inf where either
     point maps through the line at infinity."""
     h = [np.float64(v) for v in np.ravel(H)]
-    g = [h[4] * h[8] - h[5] * h[7], h[2] * h[7] - h[1] * h[8], h[1] * h[5] - h[2] * h[4],
-         h[5] * h[6] - h[3] * h[8], h[0] * h[8] - h[2] * h[6], h[2] * h[3] - h[0] * h[5],
-         h[3] * h[7] - h[4] * h[6], h[1] * h[6] - h[0] * h[7], h[0] * h[4] - h[1] * h[3]]
     xa, ya, xb, yb = (corr[..., k] for k in range(4))
     with np.errstate(all="ignore"):
+        g = [h[4] * h[8] - h[5] * h[7], h[2] * h[7] - h[1] * h[8], h[1] * h[5] - h[2] * h[4],
+             h[5] * h[6] - h[3] * h[8], h[0] * h[8] - h[2] * h[6], h[2] * h[3] - h[0] * h[5],
+             h[3] * h[7] - h[4] * h[6], h[1] * h[6] - h[0] * h[7], h[0] * h[4] - h[1] * h[3]]
         p0 = (h[0] * xa + h[1] * ya) + h[2]
         p1 = (h[3] * xa + h[4] * ya) + h[5]
         p2 = (h[6] * xa + h[7] * ya) + h[8]

@@ -25,15 +25,24 @@ def dev(native_lib):
     return device.require_gpu()
 
 
+def _ragged(scenes, sizes):
+    from structure_from_motion_amd import device
+
+    corr, offset, min_extra = vo.ragged_arrays(scenes)
+    return dict(scenes=scenes, sizes=sizes, corr=corr, offset=offset, min_extra=min_extra, corr_t=device.to_device(corr),
+                offset_t=device.to_device(offset, torch.int64), min_extra_t=device.to_device(min_extra))
+
+
 @pytest.fixture(scope="module")
 def ragged(dev):
     """The 12-pair fixture on the host and on the device (computed once, never written)."""
-    from structure_from_motion_amd import device
+    return _ragged(vo.ragged_scenes(), vo.SIZES)
 
-    scenes = vo.ragged_scenes()
-    corr, offset, min_extra = vo.ragged_arrays(scenes)
-    return dict(scenes=scenes, corr=corr, offset=offset, min_extra=min_extra, corr_t=device.to_device(corr),
-                offset_t=device.to_device(offset, torch.int64), min_extra_t=device.to_device(min_extra))
+
+@pytest.fixture(scope="module")
+def ragged_special(dev):
+    """12 pairs on the special motions and planes of tests/homography_cases.py."""
+    return _ragged(vo.ragged_scenes(vo.SPECIAL_SIZES, scenes=vo.SPECIAL_SCENES), vo.SPECIAL_SIZES)
 
 
 def _prefilled(pairs, n_total, h, dev):
@@ -61,18 +70,21 @@ def _assert_written(out):
         assert not np.any(a == sentinel), name
 
 
-@pytest.mark.parametrize("h", [1, 255, 257])   # both sides of the scoring kernel's 256-lane block
-def test_equals_the_single_pair_passes(dev, ragged, h):
+# h: both sides of the scoring kernel's 256-lane block
+@pytest.mark.parametrize("h, fixture", [pytest.param(h, f, id=f"{h}{tag}")
+                                        for f, tag in (("ragged", ""), ("ragged_special", "-special")) for h in (1, 255, 257)])
+def test_equals_the_single_pair_passes(dev, request, fixture, h):
     from structure_from_motion_amd import device
 
-    corr, offset, min_extra = ragged["corr"], ragged["offset"], ragged["min_extra"]
-    Q, N = len(vo.SIZES), len(corr)
+    ragged = request.getfixturevalue(fixture)
+    corr, offset, min_extra, sizes = ragged["corr"], ragged["offset"], ragged["min_extra"], ragged["sizes"]
+    Q, N = len(sizes), len(corr)
     ws = _prefilled(Q, N, h, dev)
     ws.run(ragged["corr_t"], ragged["offset_t"], ragged["min_extra_t"], THR, vo.RMS, MAX_RATIO, SEED, STRIDE, H_BEGIN)
     out = _host(ws)
     _assert_written(out)
     h_rec, e_rec, verdicts = device.read_select(ws.h_result), device.read_select(ws.e_result), ws.read_verdicts()
-    for q, n in enumerate(vo.SIZES):
+    for q, n in enumerate(sizes):
         lo, hi = offset[q], offset[q + 1]
         c = corr[lo:hi]
         S = out["S"][q]
@@ -124,7 +136,7 @@ def test_equals_the_single_pair_passes(dev, ragged, h):
         if n < 4:
             assert v.kind == vo.NONE and h_rec[q].best_h == -1 and e_rec[q].best_h == -1
     if h >= 255:   # the fixture is not vacuous: the large pairs have both models
-        assert all(h_rec[q].best_h >= 0 and e_rec[q].best_h >= 0 for q in range(7, Q))
+        assert all(h_rec[q].best_h >= 0 and e_rec[q].best_h >= 0 for q in range(Q) if sizes[q] >= 300)
 
 
 def test_model_kinds_and_seed_pair(dev):

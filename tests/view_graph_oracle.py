@@ -16,9 +16,22 @@ SIZES = (0, 3, 4, 5, 6, 7, 8, 300, 511, 512, 513, 1025)
 MOTION_CYCLE = ("bench", "pan10", "plane_bench", "gen12")
 
 
-def ragged_scenes(sizes=SIZES, seed=40):
-    """One scene per size, cycling the four motions, 30 % outliers and 0.5 px noise."""
-    return [ho.motion_scene(MOTION_CYCLE[k % 4], n, seed + k, 0.5, 0.3) for k, n in enumerate(sizes)]
+# a second fixture on the special motions and planes of tests/homography_cases.py: the sizes cycle both sample sizes and both
+# sides of the 64-lane block; the pairs of 300 and 513 items are scenes that one homography explains, so both models exist
+SPECIAL_SIZES = (6, 7, 64, 65, 300, 513) * 2
+SPECIAL_SCENES = (("roll180_tx", "general"), ("turn170", "plane"), ("tz", "general"), ("roll15_tz", "general"), ("tz", "fronto"),
+                  ("tx", "steep"), ("roll90_tgen", "steep"), ("ty", "fronto"), ("gen_tz", "plane"), ("roll180", "general"),
+                  ("still", "general"), ("roll90", "general"))
+
+
+def ragged_scenes(sizes=SIZES, seed=40, scenes=None):
+    """One scene per size, 30 % outliers and 0.5 px noise: cycling the four motions, or (``scenes``) the (motion, shape) pairs
+    of homography_cases in turn."""
+    if scenes is None:
+        return [ho.motion_scene(MOTION_CYCLE[k % 4], n, seed + k, 0.5, 0.3) for k, n in enumerate(sizes)]
+    import homography_cases as hc
+
+    return [hc.scene(*scenes[k % len(scenes)], n, seed + k, 0.5, 0.3) for k, n in enumerate(sizes)]
 
 
 def ragged_arrays(scenes):
