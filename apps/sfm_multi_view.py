@@ -24,6 +24,14 @@ call (``relative_pose=True``), its first view sits at the identity, and the erro
 relative to that view, in units of the pair's true baseline).  The output then also holds ``seed_pair`` and the pair's
 ``median_angle_deg``.
 
+``rotations="global"`` (``--rotations global``, with ``--tracks matches --verify batched``) also averages the relative rotations
+of the verified pairs into one global rotation per view before any point exists (``average_graph_rotations``: Huber at one
+degree from the spanning tree, then Cauchy from Huber's result), and adds ``global_rotations`` to the output: each view's
+rotation error against the truth in the gauge of the reconstruction's first view, the solver's status and step counts, and the
+pairs whose rotation disagrees with the result by more than ``--drop-inconsistent-pairs`` degrees (5 when it is not given).
+``--drop-inconsistent-pairs DEG`` also removes those pairs' matches before ``build_tracks``.  Without these flags the output is
+what it was.
+
 ``bundle_loss`` (``--bundle-loss``) gives every bundle adjustment a robust loss (``"huber"`` or ``"cauchy"`` with
 ``bundle_loss_scale`` pixels); the drop rules stay as they are, and ``rms_px`` is then computed from the
 squared errors of the adjusted observations, since the adjuster's cost is a sum of rho.
@@ -46,6 +54,7 @@ from lib.epipolar.eight_point import create_trivial_matches, recover_r_t_from_e
 from lib.epipolar.epipolar_ransac import estimate_essential_mat_with_ransac
 from lib.epipolar.view_graph import choose_seed_pair, verify_pairs
 from lib.feature_matching.matching import Match
+from lib.multiview.rotation_averaging import average_graph_rotations, inconsistent_pairs
 from lib.multiview.tracks import build_tracks, triangulate_tracks
 from lib.pnp.pnp import estimate_pose_pnp_with_ransac
 from structure_from_motion_amd import device, synthetic
@@ -57,6 +66,8 @@ BUNDLE_LOSSES = device.BUNDLE_LOSSES
 TRACK_SOURCES = ("given", "matches")
 VERIFY_ROUTES = ("loop", "batched")
 SEED_PAIRS = ("first", "auto")
+ROTATION_ROUTES = ("incremental", "global")
+INCONSISTENT_DEG = 5.0   # a pair is reported as inconsistent above this residual unless --drop-inconsistent-pairs says otherwise
 MIN_PNP_INLIERS = 30
 
 
@@ -171,23 +182,38 @@ def _verified_matches(K, pix_a, pix_b, m, sed_threshold: float, iterations: int,
     return m[device.checked_mask(outcome.mask) > 0]
 
 
+def global_rotations(graph, views: int, max_residual_deg: float):
+    """Huber from the spanning tree, then Cauchy from Huber's result (``average_graph_rotations``): (the Cauchy result, the
+    indices of the graph's pairs whose residual is above ``max_residual_deg``)."""
+    huber = average_graph_rotations(graph, views, loss="huber", loss_scale_deg=1.0, max_steps=100)
+    cauchy = average_graph_rotations(graph, views, loss="cauchy", loss_scale_deg=1.0, initial_rotations=huber.R, max_steps=100)
+    return cauchy, inconsistent_pairs(cauchy, max_residual_deg)
+
+
 def tracks_from_matches(scene, sed_threshold: float, iterations: int, e_solver: str, seed: int, verify: str = "loop",
-                        relative_pose: bool = False):
+                        relative_pose: bool = False, rotations: str = "incremental", drop_inconsistent_deg=None):
     """The scene's tracks rebuilt from verified pairwise matches: (scene with the built camera_indices, point_indices and
     pixels, the build's info, the fraction of OK tracks whose features all belong to one true point, pairs kept, and with
     ``verify="batched"`` the number of pairs of each kind and the ``ViewGraph`` (with poses if ``relative_pose``), else None
-    twice)."""
+    twice; with ``rotations="global"`` the result of ``global_rotations``, else None).  ``drop_inconsistent_deg`` drops the
+    inconsistent pairs before the build."""
     K = scene["K"]
     random.seed(seed)   # the pairs' RANSAC samples
     pm = synthetic.pairwise_matches(scene, seed=seed)
-    pairs, kept, kinds, graph = [], [], None, None
+    pairs, kept, kinds, graph, averaged = [], [], None, None, None
     if verify == "batched":
-        pose = dict(relative_pose=True) if relative_pose else {}
+        pose = dict(relative_pose=True) if relative_pose or rotations == "global" else {}
         graph = verify_pairs(K, pm["features"], pm["pairs"], pm["matches"], sed_threshold, min_extra_fraction=0.4,
                              max_iterations=iterations, **pose)
         kinds = {kind: graph.kind.count(kind) for kind in ("essential", "homography", "none")}
-        for (i, j), kind, inliers in zip(pm["pairs"], graph.kind, graph.inlier_matches):
-            if kind != "none":   # a pair without a model is dropped
+        dropped = set()
+        if rotations == "global":
+            limit = INCONSISTENT_DEG if drop_inconsistent_deg is None else drop_inconsistent_deg
+            averaged = global_rotations(graph, len(pm["features"]), limit)
+            if drop_inconsistent_deg is not None:
+                dropped = set(averaged[1].tolist())
+        for q, ((i, j), kind, inliers) in enumerate(zip(pm["pairs"], graph.kind, graph.inlier_matches)):
+            if kind != "none" and q not in dropped:   # a pair without a model is dropped
                 pairs.append((i, j))
                 kept.append(inliers)
     else:
@@ -205,7 +231,7 @@ def tracks_from_matches(scene, sed_threshold: float, iterations: int, e_solver: 
     np.maximum.at(hi, r.point_indices, truth)
     pure = float(np.mean(lo == hi)) if r.info.tracks else float("nan")
     built = dict(scene, camera_indices=r.camera_indices, point_indices=r.point_indices, pixels=r.pixels)
-    return built, r.info, pure, len(pairs), kinds, graph
+    return built, r.info, pure, len(pairs), kinds, graph, averaged
 
 
 def run(views: int = 8, points: int = 2000, seed: int = 21, noise_px: float = 0.5, outlier_fraction: float = 0.2,
@@ -213,7 +239,7 @@ def run(views: int = 8, points: int = 2000, seed: int = 21, noise_px: float = 0.
         ba_steps: int = 20, final_ba_steps: int = 50, step_deg: float = 5.0, bundle_solver: str = "dense",
         details: bool = False, pnp_solver: str = "dlt", e_solver: str = "eight_point", tracks: str = "given",
         bundle_loss: str = "squared", bundle_loss_scale: float = 2.0, verify: str = "loop", seed_pair: str = "first",
-        seed_min_angle_deg: float = 2.0) -> dict:
+        seed_min_angle_deg: float = 2.0, rotations: str = "incremental", drop_inconsistent_pairs_deg=None) -> dict:
     if pnp_solver not in ("dlt", "p3p"):
         raise ValueError(f"pnp_solver must be 'dlt' or 'p3p', got {pnp_solver!r}")
     if e_solver not in ("eight_point", "five_point"):
@@ -224,6 +250,15 @@ def run(views: int = 8, points: int = 2000, seed: int = 21, noise_px: float = 0.
         raise ValueError(f"verify must be one of {VERIFY_ROUTES}, got {verify!r}")
     if seed_pair not in SEED_PAIRS:
         raise ValueError(f"seed_pair must be one of {SEED_PAIRS}, got {seed_pair!r}")
+    if rotations not in ROTATION_ROUTES:
+        raise ValueError(f"rotations must be one of {ROTATION_ROUTES}, got {rotations!r}")
+    if rotations == "global" and not (tracks == "matches" and verify == "batched"):
+        raise ValueError("rotations='global' needs tracks='matches' and verify='batched'")
+    if drop_inconsistent_pairs_deg is not None:
+        if rotations != "global":
+            raise ValueError("drop_inconsistent_pairs_deg needs rotations='global'")
+        if not (np.isfinite(drop_inconsistent_pairs_deg) and drop_inconsistent_pairs_deg > 0.0):
+            raise ValueError(f"drop_inconsistent_pairs_deg must be finite and positive, got {drop_inconsistent_pairs_deg!r}")
     auto_seed = seed_pair == "auto"
     if auto_seed and not (tracks == "matches" and verify == "batched"):
         raise ValueError("seed_pair='auto' needs tracks='matches' and verify='batched'")
@@ -237,10 +272,11 @@ def run(views: int = 8, points: int = 2000, seed: int = 21, noise_px: float = 0.
     if not 2 <= views <= limit:
         raise ValueError(f"between 2 and {limit} views are supported with bundle_solver={bundle_solver!r}, got {views}")
     scene = synthetic.multi_view_scene(views, points, seed, noise_px, outlier_fraction, step_deg=step_deg)
-    build, graph = None, None
+    build, graph, averaged = None, None, None
     if tracks == "matches":
-        scene, build_info, pure, kept_pairs, kinds, graph = tracks_from_matches(scene, sed_threshold, iterations, e_solver, seed,
-                                                                                verify, relative_pose=auto_seed)
+        scene, build_info, pure, kept_pairs, kinds, graph, averaged = tracks_from_matches(
+            scene, sed_threshold, iterations, e_solver, seed, verify, relative_pose=auto_seed, rotations=rotations,
+            drop_inconsistent_deg=drop_inconsistent_pairs_deg)
         build = dict(pairs_kept=kept_pairs, components=build_info.components, tracks=build_info.tracks,
                      observations=build_info.observations, conflicts=build_info.conflicts,
                      unmatched=build_info.unmatched, pure_track_fraction=pure)
@@ -353,6 +389,21 @@ def run(views: int = 8, points: int = 2000, seed: int = 21, noise_px: float = 0.
     if auto_seed:
         out["seed_pair"] = [va, vb]
         out["median_angle_deg"] = float(graph.pose.median_angle_deg[seed_q])
+    if averaged is not None:
+        result, inconsistent = averaged
+        # the gauge of the reconstruction: the true rotations above are relative to view va (its own when va is view 0)
+        Rg = result.R @ result.R[va].T
+        Rt = truth[:, :9].reshape(-1, 3, 3)
+        Rt = Rt @ Rt[va].T
+        out["global_rotations"] = {
+            "rotation_error_rad": {int(v): rotation_angle(Rg[v], Rt[v]) for v in range(views) if result.registered[v]},
+            "views_registered": int(np.count_nonzero(result.registered)),
+            "status": result.status,
+            "steps": result.steps,
+            "cg_iterations": result.cg_iterations,
+            "inconsistent_pairs": [[int(v) for v in graph.pairs[q]] for q in inconsistent],
+            "pairs_dropped": len(inconsistent) if drop_inconsistent_pairs_deg is not None else 0,
+        }
     if details:
         out["_scene"], out["_status"] = scene, rec.status.copy()
         if graph is not None:
@@ -393,6 +444,11 @@ def main():
                          "graph recommends")
     ap.add_argument("--seed-min-angle", type=float, default=2.0,
                     help="with --seed-pair auto: least median triangulation angle of the seed pair's inliers, in degrees")
+    ap.add_argument("--rotations", choices=ROTATION_ROUTES, default="incremental",
+                    help="global (with --tracks matches --verify batched): also average the verified pairs' relative rotations "
+                         "into one rotation per view and report each view's error and the inconsistent pairs")
+    ap.add_argument("--drop-inconsistent-pairs", type=float, default=None, metavar="DEG",
+                    help="with --rotations global: drop the pairs whose rotation residual is above DEG degrees before build_tracks")
     ap.add_argument("--e-solver", choices=("eight_point", "five_point"), default="eight_point",
                     help="minimal solver of the two-view seed: eight-point, or five-point on six-item samples")
     ap.add_argument("--bundle-loss", choices=BUNDLE_LOSSES, default="squared",
@@ -404,12 +460,17 @@ def main():
         ap.error(f"--views must be between 2 and {limit} with --bundle-solver {args.bundle_solver}")
     if args.seed_pair == "auto" and not (args.tracks == "matches" and args.verify == "batched"):
         ap.error("--seed-pair auto needs --tracks matches --verify batched")
+    if args.rotations == "global" and not (args.tracks == "matches" and args.verify == "batched"):
+        ap.error("--rotations global needs --tracks matches --verify batched")
+    if args.drop_inconsistent_pairs is not None and not (args.rotations == "global" and args.drop_inconsistent_pairs > 0):
+        ap.error("--drop-inconsistent-pairs needs --rotations global and a positive angle")
     print(json.dumps(run(args.views, args.points, args.seed, args.noise, args.outliers, sed_threshold=args.sed_threshold,
                          reprojection_threshold=args.reprojection_threshold, refine_steps=args.refine_steps,
                          step_deg=args.step_deg, bundle_solver=args.bundle_solver, pnp_solver=args.pnp_solver,
                          e_solver=args.e_solver, tracks=args.tracks, bundle_loss=args.bundle_loss,
                          bundle_loss_scale=args.bundle_loss_scale, verify=args.verify, seed_pair=args.seed_pair,
-                         seed_min_angle_deg=args.seed_min_angle)))
+                         seed_min_angle_deg=args.seed_min_angle, rotations=args.rotations,
+                         drop_inconsistent_pairs_deg=args.drop_inconsistent_pairs)))
 
 
 if __name__ == "__main__":

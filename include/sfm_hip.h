@@ -704,6 +704,69 @@ int sfm_build_tracks(int64_t images, int64_t features, int64_t pairs, int64_t ma
                      int32_t* track, uint8_t* status, int32_t* camera_index, int32_t* point_index, int32_t* feature_index,
                      sfm_build_tracks_info* info, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- rotation averaging over a view graph (csrc/sfm_rotation_averaging.hip; an extension, off unless asked for) ----
+ * These symbols were added under ABI 15 without a version change: they are new, and nothing an ABI-15 caller uses changed. */
+
+#define SFM_ROTAVG_CONVERGED 0 /* the largest |x_c|_inf of a step was <= step_tolerance, or there is no free camera */
+#define SFM_ROTAVG_MAX_STEPS 1 /* max_steps steps were taken (max_steps = 0: the initialisation is the result) */
+#define SFM_ROTAVG_CG_FAILED 2 /* a step's CG broke down at k = 0 or met a non-finite scalar: the rotations of the last
+                                * completed step are the result */
+#define SFM_ROTAVG_BAD_INDEX 3 /* a camera index out of range or a self-pair: every rotation and residual NaN */
+
+#define SFM_ROTAVG_INIT_TREE 0  /* start from the maximum-weight breadth-first spanning tree of the root */
+#define SFM_ROTAVG_INIT_GIVEN 1 /* start from `initial` (the root keeps its given rotation and is held) */
+
+typedef struct sfm_rotavg_options {
+    int32_t loss;              /* SFM_BUNDLE_LOSS_*: rho of e = |log(R_j^T R_q R_i)|^2 in rad^2 */
+    int32_t init;              /* SFM_ROTAVG_INIT_* */
+    int32_t max_steps;         /* >= 0 */
+    int32_t max_cg_iterations; /* >= 1 */
+    double loss_scale;         /* a, in radians: finite and positive (read for the squared loss too, where it has no effect) */
+    double cg_tolerance;       /* finite, in (0, 1) */
+    double step_tolerance;     /* finite and positive, radians */
+} sfm_rotavg_options;
+
+typedef struct sfm_rotavg_info {
+    double initial_cost;   /* sum over the used edges of w rho(e) at the initialisation (NaN for SFM_ROTAVG_BAD_INDEX) */
+    double final_cost;     /* ... at the result */
+    int32_t steps;         /* completed steps */
+    int32_t status;        /* SFM_ROTAVG_* */
+    int32_t cg_iterations; /* conjugate-gradient iterations over all steps */
+    int32_t cg_max;        /* the most conjugate-gradient iterations of one step */
+    int32_t registered;    /* cameras with a level, the root included */
+    int32_t rounds;        /* the largest level */
+} sfm_rotavg_info;
+
+/* Bytes of workspace sfm_average_rotations needs; -1 for sizes it refuses (cameras < 1, cameras >= 2^31, edges < 0 or
+ * edges >= 2^30). */
+int64_t sfm_average_rotations_workspace_bytes(int64_t cameras, int64_t edges);
+
+/* One absolute rotation per camera (world -> camera) that agrees with the relative rotations of all edges at once:
+ * edge q joins cameras i = pairs[2q] != j = pairs[2q + 1] with R_q ~ R_j R_i^T (x_j ~ R_q x_i, the convention of
+ * sfm_pair_pose.R) and weight w_q.  An edge is active iff w_q is finite and > 0 and the nine entries of R_q are finite; an
+ * inactive edge is ignored and its residual is NaN.  Parallel edges and either orientation are allowed.
+ * Levels: level[root] = 0; in round k a camera without a level that has an active edge to a camera of level < k takes level
+ * k (with SFM_ROTAVG_INIT_TREE: and its rotation through the heaviest such edge, ties to the earliest half-edge 2q / 2q + 1 of
+ * the camera in increasing index, R_root = I).  A camera that never gets a level is unregistered: rotation NaN, registered 0.
+ * Then at most max_steps steps of iteratively reweighted Gauss-Newton: per used edge (active, both ends registered)
+ * D = R_j^T (R_q R_i), r = log D, e = |r|^2, omega = w rho'(e); the weighted graph Laplacian system
+ * sum_{q at c} omega (x_c - x_other) = sum_{q at c} s omega r (s = +1 at the j end, -1 at the i end; x_root = 0) is solved by
+ * conjugate gradients with the Jacobi preconditioner from x = 0, stopping as sfm_bundle_adjust_pcg's CG does, and
+ * R_c <- R_c exp([x_c]x).  The stop rules are the SFM_ROTAVG_* statuses.  residual[q] = |log D| in radians for a used edge.
+ * Every sum runs in an order fixed by the edge list alone and there are no floating-point atomics: a call is reproducible
+ * bit for bit.  The host reads three flags between batches of level rounds, steps and chunks of 10 CG iterations, so the
+ * call synchronises `stream`; the result does not depend on those reads.  Every byte of every output is written whatever
+ * the status.  The definition, operation by operation, is tests/rotation_averaging_oracle.py.
+ * pairs: dev int32 [edges,2]; relative: dev [edges,9]; weights: dev [edges]; 0 <= root < cameras; initial: dev [cameras,9],
+ * read with SFM_ROTAVG_INIT_GIVEN only (else may be NULL); rotations: dev [cameras,9]; registered: dev uint8 [cameras];
+ * level: dev int32 [cameras] or NULL, -1 for an unregistered camera (and for every camera after SFM_ROTAVG_BAD_INDEX);
+ * residual: dev [edges]; info: dev, one record; workspace: dev, 16-byte aligned, at least
+ * sfm_average_rotations_workspace_bytes.  SFM_EINVAL before the first launch for a refused size, pointer or option. */
+int sfm_average_rotations(int64_t cameras, int64_t edges, const int32_t* pairs, const double* relative,
+                          const double* weights, int64_t root, const double* initial, const sfm_rotavg_options* options,
+                          double* rotations, uint8_t* registered, int32_t* level, double* residual, sfm_rotavg_info* info,
+                          void* workspace, int64_t workspace_bytes, void* stream);
+
 /* SED of n correspondences under one E (sed.py:7-30).  E: dev [9]; out: dev [n]. */
 int sfm_sed_values(const double* corr, int64_t n, const double* E, double* out, void* stream);
 

@@ -71,17 +71,7 @@ struct Lm {
     double* sw;                      // sqrt(w) per point-major position, for kernels without a residual (else nullptr)
 };
 
-// Bump allocation of a workspace in 256-byte aligned pieces from `base` (0: sizes only).
-struct Carver {
-    uintptr_t base;
-    int64_t at;
-    template <class T>
-    T* take(int64_t count) {
-        const int64_t o = at, bytes = count * (int64_t)sizeof(T);
-        at = (o + (bytes > 0 ? bytes : 8) + 255) & ~(int64_t)255;
-        return reinterpret_cast<T*>(base + o);
-    }
-};
+using sfmhost::Carver;   // csrc/sfm_common.h
 
 // The core's arrays and both orders' buffers (csrc/sfm_obs_order.h), in one fixed sequence.
 struct Core {

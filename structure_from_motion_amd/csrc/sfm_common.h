@@ -51,6 +51,18 @@ inline unsigned grid_stride(int64_t work, int64_t block, int64_t cap) {
     return (unsigned)g;
 }
 
+// Bump allocation of a workspace in 256-byte aligned pieces from `base` (0: sizes only).
+struct Carver {
+    uintptr_t base;
+    int64_t at;
+    template <class T>
+    T* take(int64_t count) {
+        const int64_t o = at, bytes = count * (int64_t)sizeof(T);
+        at = (o + (bytes > 0 ? bytes : 8) + 255) & ~(int64_t)255;
+        return reinterpret_cast<T*>(base + o);
+    }
+};
+
 }  // namespace sfmhost
 
 #define SFM_REQUIRE_GRID(fn, work, per_block, ...)                                                     \

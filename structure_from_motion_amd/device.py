@@ -904,6 +904,49 @@ def read_bundle_pcg_info(info: torch.Tensor) -> BundlePcgInfo:
 
 
 # ------------------------------------------------------------------------------------------------------
+# rotation averaging over a view graph (csrc/sfm_rotation_averaging.hip): pairs int32 [Q,2], relative rotations [Q,3,3]
+# (R_q ~ R_j R_i^T), weights [Q]
+# ------------------------------------------------------------------------------------------------------
+ROTAVG_STATUS = _native.ROTAVG_STATUS   # "converged", "max_steps", "cg_failed", "bad_index": the index is the SFM_ROTAVG_* code
+ROTAVG_CONVERGED, ROTAVG_MAX_STEPS, ROTAVG_CG_FAILED, ROTAVG_BAD_INDEX = 0, 1, 2, 3
+
+
+def average_rotations(pairs, relative, weights, cameras: int, root: int = 0, initial=None, loss: str = "squared",
+                      loss_scale: float = 1.0, max_steps: int = 50, max_cg_iterations: int = 500, cg_tolerance: float = 1e-6,
+                      step_tolerance: float = 1e-8):
+    """One absolute rotation per camera from the relative rotations of a graph (``sfm_average_rotations``)
+    -> (rotations [C,3,3], registered uint8 [C], level int32 [C] (-1: unregistered), residual [Q] in radians, info int64 [5] viewing the sfm_rotavg_info record;
+    ``read_rotavg_info``).  ``initial`` [C,3,3] starts from those rotations instead of the spanning tree.  ``loss`` in
+    ``BUNDLE_LOSSES`` with ``loss_scale`` in radians.  The call synchronises the current stream: the host reads the stop
+    flags between level rounds, steps and CG chunks."""
+    code, scale = _bundle_loss(loss, loss_scale)
+    op = ops.load()
+    return op.average_rotations(pairs.contiguous(), relative.contiguous(), weights.contiguous(), int(cameras), int(root),
+                                None if initial is None else initial.contiguous(), code, scale, int(max_steps),
+                                int(max_cg_iterations), float(cg_tolerance), float(step_tolerance))
+
+
+@dataclass
+class RotavgInfo:
+    initial_cost: float   # sum of w rho(e) over the used edges at the initialisation (NaN for ROTAVG_BAD_INDEX)
+    final_cost: float     # ... at the result
+    steps: int            # completed steps
+    status: int           # ROTAVG_*
+    cg_iterations: int    # conjugate-gradient iterations over all steps
+    cg_max: int           # the most conjugate-gradient iterations of one step
+    registered: int       # cameras with a level, the root included
+    rounds: int           # the largest level
+
+
+def read_rotavg_info(info: torch.Tensor) -> RotavgInfo:
+    """Host copy of an sfm_rotavg_info record (int64 [5]) (synchronises)."""
+    raw = info.cpu().numpy()
+    costs = raw[0:2].view(np.float64)
+    ints = raw[2:5].view(np.int32)
+    return RotavgInfo(float(costs[0]), float(costs[1]), *(int(v) for v in ints))
+
+
+# ------------------------------------------------------------------------------------------------------
 # triangulation of multi-view tracks (csrc/sfm_tracks.hip): poses [C,12] = R (9) | t (3) world -> camera, observations
 # (camera index, point index) int32 [M] each and pixels [M,2]
 # ------------------------------------------------------------------------------------------------------
