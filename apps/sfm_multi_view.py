@@ -32,6 +32,16 @@ pairs whose rotation disagrees with the result by more than ``--drop-inconsisten
 ``--drop-inconsistent-pairs DEG`` also removes those pairs' matches before ``build_tracks``.  Without these flags the output is
 what it was.
 
+``positions="global"`` (``--positions global``, with ``--rotations global``) goes on to average the pairs' translation
+directions into one position per view (``average_graph_translations`` on the global rotations: Huber at the sine of two
+degrees from the spanning tree with the warm-up, then Cauchy from Huber's result), and adds ``global_positions`` to the output:
+each view's centre error against the truth after the scale-and-shift alignment in which the rotations are taken as given (in
+units of the first pair's true baseline), the solver's status and step counts, and the pairs whose direction disagrees with the
+result by more than the residual limit.  ``register="global"`` (``--register global``, with ``--positions global``) starts the
+reconstruction from those poses (``global_poses``) instead of from a seed pair and a PnP chain: every track is triangulated
+from all registered views at once and the bundle adjustment follows; the per-view errors are reported as for the incremental
+route, and ``bundle`` holds the cost of the first adjustment before and after.
+
 ``bundle_loss`` (``--bundle-loss``) gives every bundle adjustment a robust loss (``"huber"`` or ``"cauchy"`` with
 ``bundle_loss_scale`` pixels); the drop rules stay as they are, and ``rms_px`` is then computed from the
 squared errors of the adjusted observations, since the adjuster's cost is a sum of rho.
@@ -56,6 +66,7 @@ from lib.epipolar.view_graph import choose_seed_pair, verify_pairs
 from lib.feature_matching.matching import Match
 from lib.multiview.rotation_averaging import average_graph_rotations, inconsistent_pairs
 from lib.multiview.tracks import build_tracks, triangulate_tracks
+from lib.multiview.translation_averaging import average_graph_translations, global_poses
 from lib.pnp.pnp import estimate_pose_pnp_with_ransac
 from structure_from_motion_amd import device, synthetic
 
@@ -67,6 +78,12 @@ TRACK_SOURCES = ("given", "matches")
 VERIFY_ROUTES = ("loop", "batched")
 SEED_PAIRS = ("first", "auto")
 ROTATION_ROUTES = ("incremental", "global")
+POSITION_ROUTES = ("incremental", "global")
+REGISTER_ROUTES = ("incremental", "global")
+# The scene's cameras stand on an arc a few degrees apart, nearly on a line, where directions fix the positions along the line
+# only weakly and the alternation of translation averaging converges slowly: on the default 8 views the library's default of 500
+# steps leaves view 1 nearer to view 2's true centre than to its own, 3 000 steps per loss do not.
+POSITION_STEPS = 3000
 INCONSISTENT_DEG = 5.0   # a pair is reported as inconsistent above this residual unless --drop-inconsistent-pairs says otherwise
 MIN_PNP_INLIERS = 30
 
@@ -126,6 +143,18 @@ class Reconstruction:
                 return
             self.active[bad] = False
             points = np.unique(self.pt[bad])
+
+    def start(self, obs: np.ndarray, max_steps: int):
+        """The first points and the first adjustment: the tracks of the observations ``obs`` triangulated without the error
+        check, the registered views adjusted on them, then every track triangulated with the checks.  Returns the
+        adjustment's info."""
+        r = triangulate_tracks(self.K, self.poses, self.cam[obs], self.pt[obs], self.uv[obs], num_points=self.P,
+                               min_angle_deg=self.min_angle_deg, refine_steps=self.refine_steps)
+        self.X, self.status = r.points, np.where(r.status == device.TRACKS_LARGE_ERROR, device.TRACKS_OK, r.status)
+        info, _ = self.adjust(max_steps, drop=False)
+        self.status[:] = device.TRACKS_FEW_VIEWS
+        self.triangulate(self.pending())
+        return info
 
     def pending(self) -> np.ndarray:
         """Tracks that are not OK and have at least two active observations in registered views."""
@@ -190,17 +219,27 @@ def global_rotations(graph, views: int, max_residual_deg: float):
     return cauchy, inconsistent_pairs(cauchy, max_residual_deg)
 
 
+def global_positions(graph, rotations, views: int, max_residual_deg: float):
+    """Huber with the warm-up from the spanning tree, then Cauchy from Huber's result (``average_graph_translations``): (the
+    Cauchy result, the indices of the graph's pairs whose residual is above ``max_residual_deg``)."""
+    huber = average_graph_translations(graph, rotations, views, loss="huber", loss_scale_deg=2.0, max_steps=POSITION_STEPS)
+    cauchy = average_graph_translations(graph, rotations, views, loss="cauchy", loss_scale_deg=2.0, warmup_steps=0,
+                                        initial_positions=huber.c, max_steps=POSITION_STEPS)
+    return cauchy, inconsistent_pairs(cauchy, max_residual_deg)
+
+
 def tracks_from_matches(scene, sed_threshold: float, iterations: int, e_solver: str, seed: int, verify: str = "loop",
-                        relative_pose: bool = False, rotations: str = "incremental", drop_inconsistent_deg=None):
+                        relative_pose: bool = False, rotations: str = "incremental", drop_inconsistent_deg=None,
+                        positions: str = "incremental"):
     """The scene's tracks rebuilt from verified pairwise matches: (scene with the built camera_indices, point_indices and
     pixels, the build's info, the fraction of OK tracks whose features all belong to one true point, pairs kept, and with
     ``verify="batched"`` the number of pairs of each kind and the ``ViewGraph`` (with poses if ``relative_pose``), else None
-    twice; with ``rotations="global"`` the result of ``global_rotations``, else None).  ``drop_inconsistent_deg`` drops the
-    inconsistent pairs before the build."""
+    twice; with ``rotations="global"`` the result of ``global_rotations``, else None; with ``positions="global"`` the result
+    of ``global_positions``, else None).  ``drop_inconsistent_deg`` drops the inconsistent pairs before the build."""
     K = scene["K"]
     random.seed(seed)   # the pairs' RANSAC samples
     pm = synthetic.pairwise_matches(scene, seed=seed)
-    pairs, kept, kinds, graph, averaged = [], [], None, None, None
+    pairs, kept, kinds, graph, averaged, positioned = [], [], None, None, None, None
     if verify == "batched":
         pose = dict(relative_pose=True) if relative_pose or rotations == "global" else {}
         graph = verify_pairs(K, pm["features"], pm["pairs"], pm["matches"], sed_threshold, min_extra_fraction=0.4,
@@ -210,6 +249,8 @@ def tracks_from_matches(scene, sed_threshold: float, iterations: int, e_solver: 
         if rotations == "global":
             limit = INCONSISTENT_DEG if drop_inconsistent_deg is None else drop_inconsistent_deg
             averaged = global_rotations(graph, len(pm["features"]), limit)
+            if positions == "global":
+                positioned = global_positions(graph, averaged[0], len(pm["features"]), limit)
             if drop_inconsistent_deg is not None:
                 dropped = set(averaged[1].tolist())
         for q, ((i, j), kind, inliers) in enumerate(zip(pm["pairs"], graph.kind, graph.inlier_matches)):
@@ -231,7 +272,7 @@ def tracks_from_matches(scene, sed_threshold: float, iterations: int, e_solver: 
     np.maximum.at(hi, r.point_indices, truth)
     pure = float(np.mean(lo == hi)) if r.info.tracks else float("nan")
     built = dict(scene, camera_indices=r.camera_indices, point_indices=r.point_indices, pixels=r.pixels)
-    return built, r.info, pure, len(pairs), kinds, graph, averaged
+    return built, r.info, pure, len(pairs), kinds, graph, averaged, positioned
 
 
 def run(views: int = 8, points: int = 2000, seed: int = 21, noise_px: float = 0.5, outlier_fraction: float = 0.2,
@@ -239,7 +280,8 @@ def run(views: int = 8, points: int = 2000, seed: int = 21, noise_px: float = 0.
         ba_steps: int = 20, final_ba_steps: int = 50, step_deg: float = 5.0, bundle_solver: str = "dense",
         details: bool = False, pnp_solver: str = "dlt", e_solver: str = "eight_point", tracks: str = "given",
         bundle_loss: str = "squared", bundle_loss_scale: float = 2.0, verify: str = "loop", seed_pair: str = "first",
-        seed_min_angle_deg: float = 2.0, rotations: str = "incremental", drop_inconsistent_pairs_deg=None) -> dict:
+        seed_min_angle_deg: float = 2.0, rotations: str = "incremental", drop_inconsistent_pairs_deg=None,
+        positions: str = "incremental", register: str = "incremental") -> dict:
     if pnp_solver not in ("dlt", "p3p"):
         raise ValueError(f"pnp_solver must be 'dlt' or 'p3p', got {pnp_solver!r}")
     if e_solver not in ("eight_point", "five_point"):
@@ -254,6 +296,14 @@ def run(views: int = 8, points: int = 2000, seed: int = 21, noise_px: float = 0.
         raise ValueError(f"rotations must be one of {ROTATION_ROUTES}, got {rotations!r}")
     if rotations == "global" and not (tracks == "matches" and verify == "batched"):
         raise ValueError("rotations='global' needs tracks='matches' and verify='batched'")
+    if positions not in POSITION_ROUTES:
+        raise ValueError(f"positions must be one of {POSITION_ROUTES}, got {positions!r}")
+    if register not in REGISTER_ROUTES:
+        raise ValueError(f"register must be one of {REGISTER_ROUTES}, got {register!r}")
+    if positions == "global" and rotations != "global":
+        raise ValueError("positions='global' needs rotations='global'")
+    if register == "global" and positions != "global":
+        raise ValueError("register='global' needs positions='global'")
     if drop_inconsistent_pairs_deg is not None:
         if rotations != "global":
             raise ValueError("drop_inconsistent_pairs_deg needs rotations='global'")
@@ -272,11 +322,11 @@ def run(views: int = 8, points: int = 2000, seed: int = 21, noise_px: float = 0.
     if not 2 <= views <= limit:
         raise ValueError(f"between 2 and {limit} views are supported with bundle_solver={bundle_solver!r}, got {views}")
     scene = synthetic.multi_view_scene(views, points, seed, noise_px, outlier_fraction, step_deg=step_deg)
-    build, graph, averaged = None, None, None
+    build, graph, averaged, positioned = None, None, None, None
     if tracks == "matches":
-        scene, build_info, pure, kept_pairs, kinds, graph, averaged = tracks_from_matches(
+        scene, build_info, pure, kept_pairs, kinds, graph, averaged, positioned = tracks_from_matches(
             scene, sed_threshold, iterations, e_solver, seed, verify, relative_pose=auto_seed, rotations=rotations,
-            drop_inconsistent_deg=drop_inconsistent_pairs_deg)
+            drop_inconsistent_deg=drop_inconsistent_pairs_deg, positions=positions)
         build = dict(pairs_kept=kept_pairs, components=build_info.components, tracks=build_info.tracks,
                      observations=build_info.observations, conflicts=build_info.conflicts,
                      unmatched=build_info.unmatched, pure_track_fraction=pure)
@@ -293,44 +343,55 @@ def run(views: int = 8, points: int = 2000, seed: int = 21, noise_px: float = 0.
     if auto_seed:
         seed_q = choose_seed_pair(graph, min_count=MIN_PNP_INLIERS, min_angle_deg=seed_min_angle_deg)
         va, vb = (int(v) for v in graph.pairs[seed_q])
-    in0 = np.full(rec.P, -1)
-    in1 = np.full(rec.P, -1)
-    in0[pt[cam == va]] = np.nonzero(cam == va)[0]
-    in1[pt[cam == vb]] = np.nonzero(cam == vb)[0]
-    both = np.nonzero((in0 >= 0) & (in1 >= 0))[0]
-    if auto_seed:
-        # the pair's pose is the one its inliers voted for in the verify_pairs call; the tracks through both views were built
-        # from verified matches, so all of them start the reconstruction
-        R1, t1, kept = graph.pose.R[seed_q], graph.pose.t[seed_q], both
+    if register == "global":
+        # every registered view starts at its global pose, in the gauge of view va and in units of the baseline va - vb
+        P = global_poses(averaged[0], positioned[0])
+        ok = np.nonzero(~np.isnan(P).any(axis=(1, 2)))[0]
+        if not (np.isin([va, vb], ok).all()):
+            raise ValueError(f"register='global' needs views {va} and {vb} registered in the global poses")
+        Rg, cg = averaged[0].R, positioned[0].c
+        base = float(np.linalg.norm(cg[vb] - cg[va]))
+        for v in ok:
+            Rv = Rg[v] @ Rg[va].T
+            rec.poses[v] = _pose(Rv, -Rv @ (Rg[va] @ (cg[v] - cg[va]) / base))
+        rec.registered = [va] + [int(v) for v in ok if v != va]
+        first = rec.start(np.nonzero(rec.in_registered())[0], final_ba_steps)
+        log = [dict(view=rec.registered[-1], points_ok=int(np.count_nonzero(rec.status == device.TRACKS_OK)))]
     else:
-        fa = [Feature(float(x), float(y)) for x, y in uv[in0[both]]]
-        fb = [Feature(float(x), float(y)) for x, y in uv[in1[both]]]
-        # RANSAC keeps the lowest-error model among those with enough extra inliers: asking for 40 % of the pairs keeps a
-        # model fitted to a few outliers from winning (about 64 % of the pairs are clean at 20 % outliers per view)
-        e, pairs = estimate_essential_mat_with_ransac(K, fa, fb, create_trivial_matches(len(both)),
-                                                      sed_inlier_threshold=sed_threshold,
-                                                      min_num_extra_inliers=int(0.4 * len(both)), max_iterations=iterations,
-                                                      solver=e_solver)
-        R1, t1, _ = recover_r_t_from_e(e, K, [p[0] for p in pairs], [p[1] for p in pairs])
-        index_of = {(f.x, f.y): k for k, f in enumerate(fa)}
-        kept = both[sorted(index_of[(p[0].x, p[0].y)] for p in pairs)]
-    rec.poses[va] = _pose(np.eye(3), np.zeros(3))
-    rec.poses[vb] = _pose(R1, t1)
-    rec.registered = [va, vb]
-    # The RANSAC winner is a minimal fit to one sample: with 5 degrees between the views its pose can be off by a few
-    # hundredths of a radian, enough to push most two-view points over the threshold.  So the pairs E keeps are triangulated
-    # without the error check first and the two views are adjusted on them; then every track is triangulated with the checks.
-    seed = np.nonzero(np.isin(pt, kept) & ((cam == va) | (cam == vb)))[0]
-    r = triangulate_tracks(K, rec.poses, cam[seed], pt[seed], uv[seed], num_points=rec.P, min_angle_deg=1.0,
-                           refine_steps=refine_steps)
-    rec.X, rec.status = r.points, np.where(r.status == device.TRACKS_LARGE_ERROR, device.TRACKS_OK, r.status)
-    rec.adjust(final_ba_steps, drop=False)
-    rec.status[:] = device.TRACKS_FEW_VIEWS
-    rec.triangulate(rec.pending())
-    log = [dict(view=vb, points_ok=int(np.count_nonzero(rec.status == device.TRACKS_OK)))]
+        in0 = np.full(rec.P, -1)
+        in1 = np.full(rec.P, -1)
+        in0[pt[cam == va]] = np.nonzero(cam == va)[0]
+        in1[pt[cam == vb]] = np.nonzero(cam == vb)[0]
+        both = np.nonzero((in0 >= 0) & (in1 >= 0))[0]
+        if auto_seed:
+            # the pair's pose is the one its inliers voted for in the verify_pairs call; the tracks through both views were
+            # built from verified matches, so all of them start the reconstruction
+            R1, t1, kept = graph.pose.R[seed_q], graph.pose.t[seed_q], both
+        else:
+            fa = [Feature(float(x), float(y)) for x, y in uv[in0[both]]]
+            fb = [Feature(float(x), float(y)) for x, y in uv[in1[both]]]
+            # RANSAC keeps the lowest-error model among those with enough extra inliers: asking for 40 % of the pairs keeps a
+            # model fitted to a few outliers from winning (about 64 % of the pairs are clean at 20 % outliers per view)
+            e, pairs = estimate_essential_mat_with_ransac(K, fa, fb, create_trivial_matches(len(both)),
+                                                          sed_inlier_threshold=sed_threshold,
+                                                          min_num_extra_inliers=int(0.4 * len(both)), max_iterations=iterations,
+                                                          solver=e_solver)
+            R1, t1, _ = recover_r_t_from_e(e, K, [p[0] for p in pairs], [p[1] for p in pairs])
+            index_of = {(f.x, f.y): k for k, f in enumerate(fa)}
+            kept = both[sorted(index_of[(p[0].x, p[0].y)] for p in pairs)]
+        rec.poses[va] = _pose(np.eye(3), np.zeros(3))
+        rec.poses[vb] = _pose(R1, t1)
+        rec.registered = [va, vb]
+        # The RANSAC winner is a minimal fit to one sample: with 5 degrees between the views its pose can be off by a few
+        # hundredths of a radian, enough to push most two-view points over the threshold.  So the pairs E keeps are
+        # triangulated without the error check first and the two views are adjusted on them; then every track is
+        # triangulated with the checks.
+        rec.start(np.nonzero(np.isin(pt, kept) & ((cam == va) | (cam == vb)))[0], final_ba_steps)
+        log = [dict(view=vb, points_ok=int(np.count_nonzero(rec.status == device.TRACKS_OK)))]
 
-    # 2.-4. register the view with the most observations of OK points, triangulate, adjust
-    while len(rec.registered) < views:
+    # 2.-4. register the view with the most observations of OK points, triangulate, adjust (with register="global" every
+    # view is registered already)
+    while register != "global" and len(rec.registered) < views:
         use = rec.active & (rec.status[pt] == device.TRACKS_OK)
         counts = np.bincount(cam[use], minlength=views)
         counts[rec.registered] = -1
@@ -404,10 +465,32 @@ def run(views: int = 8, points: int = 2000, seed: int = 21, noise_px: float = 0.
             "inconsistent_pairs": [[int(v) for v in graph.pairs[q]] for q in inconsistent],
             "pairs_dropped": len(inconsistent) if drop_inconsistent_pairs_deg is not None else 0,
         }
+    if positioned is not None:
+        result, off = positioned
+        # the true centres in the gauge above, in units of the first pair's true baseline; the result turned into view va's
+        # frame by its own global rotation, then scaled and shifted onto the truth
+        Rt = truth[:, :9].reshape(-1, 3, 3)
+        centres = -np.einsum("vji,vj->vi", Rt, truth[:, 9:] / scale)
+        reg = np.nonzero(result.registered & averaged[0].registered)[0]
+        mine = (result.c[reg] - result.c[reg].mean(axis=0)) @ averaged[0].R[va].T
+        theirs = centres[reg] - centres[reg].mean(axis=0)
+        s = float(np.sum(mine * theirs) / np.sum(mine * mine)) if len(reg) > 1 else 1.0
+        out["global_positions"] = {
+            "centre_error": {int(v): float(np.linalg.norm(s * mine[k] - theirs[k])) for k, v in enumerate(reg)},
+            "views_registered": int(len(reg)),
+            "status": result.status,
+            "steps": result.steps,
+            "cg_iterations": result.cg_iterations,
+            "inconsistent_pairs": [[int(v) for v in graph.pairs[q]] for q in off],
+        }
+    if register == "global":
+        out["bundle"] = {"initial_cost": float(first.initial_cost), "final_cost": float(first.final_cost)}
     if details:
         out["_scene"], out["_status"] = scene, rec.status.copy()
         if graph is not None:
             out["_graph"] = graph
+        if positioned is not None:
+            out["_rotations"], out["_positions"] = averaged[0], positioned[0]
     return out
 
 
@@ -449,6 +532,12 @@ def main():
                          "into one rotation per view and report each view's error and the inconsistent pairs")
     ap.add_argument("--drop-inconsistent-pairs", type=float, default=None, metavar="DEG",
                     help="with --rotations global: drop the pairs whose rotation residual is above DEG degrees before build_tracks")
+    ap.add_argument("--positions", choices=POSITION_ROUTES, default="incremental",
+                    help="global (with --rotations global): also average the pairs' translation directions into one position "
+                         "per view and report each view's centre error and the inconsistent pairs")
+    ap.add_argument("--register", choices=REGISTER_ROUTES, default="incremental",
+                    help="global (with --positions global): start the reconstruction from the global poses instead of a seed "
+                         "pair and a PnP chain")
     ap.add_argument("--e-solver", choices=("eight_point", "five_point"), default="eight_point",
                     help="minimal solver of the two-view seed: eight-point, or five-point on six-item samples")
     ap.add_argument("--bundle-loss", choices=BUNDLE_LOSSES, default="squared",
@@ -462,6 +551,10 @@ def main():
         ap.error("--seed-pair auto needs --tracks matches --verify batched")
     if args.rotations == "global" and not (args.tracks == "matches" and args.verify == "batched"):
         ap.error("--rotations global needs --tracks matches --verify batched")
+    if args.positions == "global" and args.rotations != "global":
+        ap.error("--positions global needs --rotations global")
+    if args.register == "global" and args.positions != "global":
+        ap.error("--register global needs --positions global")
     if args.drop_inconsistent_pairs is not None and not (args.rotations == "global" and args.drop_inconsistent_pairs > 0):
         ap.error("--drop-inconsistent-pairs needs --rotations global and a positive angle")
     print(json.dumps(run(args.views, args.points, args.seed, args.noise, args.outliers, sed_threshold=args.sed_threshold,
@@ -470,7 +563,8 @@ def main():
                          e_solver=args.e_solver, tracks=args.tracks, bundle_loss=args.bundle_loss,
                          bundle_loss_scale=args.bundle_loss_scale, verify=args.verify, seed_pair=args.seed_pair,
                          seed_min_angle_deg=args.seed_min_angle, rotations=args.rotations,
-                         drop_inconsistent_pairs_deg=args.drop_inconsistent_pairs)))
+                         drop_inconsistent_pairs_deg=args.drop_inconsistent_pairs, positions=args.positions,
+                         register=args.register)))
 
 
 if __name__ == "__main__":

@@ -767,6 +767,73 @@ int sfm_average_rotations(int64_t cameras, int64_t edges, const int32_t* pairs, 
                           double* rotations, uint8_t* registered, int32_t* level, double* residual, sfm_rotavg_info* info,
                           void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- translation averaging over a view graph (csrc/sfm_translation_averaging.hip; an extension, off unless asked for) ----
+ * These symbols were added under ABI 15 without a version change: they are new, and nothing an ABI-15 caller uses changed. */
+
+#define SFM_TRANSAVG_CONVERGED 0 /* the largest |x_c|_inf of a step after the warm-up was <= step_tolerance, or no free camera */
+#define SFM_TRANSAVG_MAX_STEPS 1 /* max_steps steps were taken (max_steps = 0: the initialisation is the result) */
+#define SFM_TRANSAVG_CG_FAILED 2 /* a step's CG broke down at k = 0 or met a non-finite scalar: the positions of the last
+                                  * completed step are the result */
+#define SFM_TRANSAVG_BAD_INDEX 3 /* a camera index out of range or a self-pair: every position, residual and scale NaN */
+
+#define SFM_TRANSAVG_INIT_TREE 0  /* start from the maximum-weight breadth-first spanning tree of the root, c_root = 0 */
+#define SFM_TRANSAVG_INIT_GIVEN 1 /* start from `initial` (the root keeps its given position and is held) */
+
+typedef struct sfm_transavg_options {
+    int32_t loss;              /* SFM_BUNDLE_LOSS_*: rho of e = |d (c_j - c_i) - v|^2, at the best d the squared sine of the angle */
+    int32_t init;              /* SFM_TRANSAVG_INIT_* */
+    int32_t max_steps;         /* >= 0 */
+    int32_t max_cg_iterations; /* >= 1 */
+    int32_t warmup_steps;      /* >= 0: the first steps take every scale d = 1 and do not end the call as converged */
+    int32_t reserved;          /* 0 */
+    double loss_scale;         /* a, a sine: finite and positive (read for the squared loss too, where it has no effect) */
+    double cg_tolerance;       /* finite, in (0, 1) */
+    double step_tolerance;     /* finite and positive, in the unit of the positions */
+} sfm_transavg_options;
+
+typedef struct sfm_transavg_info {
+    double initial_cost;   /* sum over the used edges of w rho(e) at the first linearisation (NaN for SFM_TRANSAVG_BAD_INDEX) */
+    double final_cost;     /* ... at the result, with the best scales */
+    int32_t steps;         /* completed steps */
+    int32_t status;        /* SFM_TRANSAVG_* */
+    int32_t cg_iterations; /* conjugate-gradient iterations over all steps */
+    int32_t cg_max;        /* the most conjugate-gradient iterations of one step */
+    int32_t registered;    /* cameras with a level, the root included */
+    int32_t rounds;        /* the largest level */
+} sfm_transavg_info;
+
+/* Bytes of workspace sfm_average_translations needs; -1 for sizes it refuses (cameras < 1, cameras >= 2^31, edges < 0 or
+ * edges >= 2^30). */
+int64_t sfm_average_translations_workspace_bytes(int64_t cameras, int64_t edges);
+
+/* One position (camera centre) per camera from one world direction per edge: edge q joins cameras i = pairs[2q] !=
+ * j = pairs[2q + 1] with the unit vector v_q ~ c_j - c_i and the weight w_q.  rotations == NULL: directions holds v_q.
+ * Otherwise directions holds t_q of x_j ~ R_q x_i + t_q (sfm_pair_pose.t) and rotations the global world -> camera rotations
+ * (the result of sfm_average_rotations), and v_q = -(R_j^T t_q) / |t_q| is computed on the device.  An edge is active iff w_q
+ * is finite and > 0, v_q (or t_q and the nine entries of R_j) is finite and |t_q| > 0; an inactive edge is ignored, its
+ * residual and scale are NaN.  Parallel edges and either orientation are allowed.  Levels and registration as
+ * sfm_average_rotations; with SFM_TRANSAVG_INIT_TREE c_root = 0 and a camera's start is its tree parent's position + v_q at
+ * the j end, - v_q at the i end, so the unit of the result is one tree baseline.
+ * Then at most max_steps steps on sum w rho(|d_q Delta_q - v_q|^2), Delta_q = c_j - c_i, d_q >= 0 (Zhuang, Cheong and Lee,
+ * CVPR 2018): d_q = max(<Delta_q, v_q>, 0) / |Delta_q|^2 (0 for Delta_q = 0; 1 in the first warmup_steps steps),
+ * r_q = v_q - d_q Delta_q, omega_q = w_q rho'(|r_q|^2), and the weighted graph Laplacian system
+ * sum_{q at c} omega d^2 (x_c - x_other) = sum_{q at c} s omega d^2 (r / d) (s = +1 at the j end, -1 at the i end; x_root = 0; an
+ * edge with d = 0 adds nothing, a camera whose row is zero takes a zero step) is solved by conjugate gradients as in
+ * sfm_average_rotations; c <- c + x.  The stop rules are the SFM_TRANSAVG_* statuses.  residual[q] is the angle between
+ * Delta_q and v_q in radians (0..pi) and scale[q] = d_q for a used edge.  Reproducible bit for bit; the call synchronises
+ * `stream`; every byte of every output is written whatever the status.  The definition, operation by operation, is
+ * tests/translation_averaging_oracle.py.
+ * pairs: dev int32 [edges,2]; directions: dev [edges,3]; rotations: dev [cameras,9] or NULL; weights: dev [edges];
+ * 0 <= root < cameras; initial: dev [cameras,3], read with SFM_TRANSAVG_INIT_GIVEN only (else may be NULL); positions: dev
+ * [cameras,3]; registered: dev uint8 [cameras]; level: dev int32 [cameras] or NULL; residual, scale: dev [edges]; info: dev,
+ * one record; workspace: dev, 16-byte aligned, at least sfm_average_translations_workspace_bytes.  SFM_EINVAL before the
+ * first launch for a refused size, pointer or option. */
+int sfm_average_translations(int64_t cameras, int64_t edges, const int32_t* pairs, const double* directions,
+                             const double* rotations, const double* weights, int64_t root, const double* initial,
+                             const sfm_transavg_options* options, double* positions, uint8_t* registered, int32_t* level,
+                             double* residual, double* scale, sfm_transavg_info* info, void* workspace,
+                             int64_t workspace_bytes, void* stream);
+
 /* SED of n correspondences under one E (sed.py:7-30).  E: dev [9]; out: dev [n]. */
 int sfm_sed_values(const double* corr, int64_t n, const double* E, double* out, void* stream);
 

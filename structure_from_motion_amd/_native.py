@@ -188,12 +188,13 @@ SIGNATURES = {
                                _P],
     "sfm_build_tracks": [_I64, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P],
     "sfm_average_rotations": [_I64, _I64, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P],
+    "sfm_average_translations": [_I64, _I64, _P, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P],
 }
 OTHER_SYMBOLS = ["sfm_last_error", "sfm_abi_version", "sfm_score_workspace_bytes", "sfm_score_workspace_bytes_ex",
                  "sfm_fit_trace_doubles", "sfm_match_summary_workspace_bytes", "sfm_bundle_workspace_bytes",
                  "sfm_tracks_workspace_bytes", "sfm_bundle_pcg_workspace_bytes", "sfm_build_tracks_workspace_bytes",
                  "sfm_bundle_pcg_workspace_bytes_ex", "sfm_hamming_summary_workspace_bytes", "sfm_pair_poses_workspace_bytes",
-                 "sfm_average_rotations_workspace_bytes"]
+                 "sfm_average_rotations_workspace_bytes", "sfm_average_translations_workspace_bytes"]
 
 # the losses of both bundle adjusters, in the order of their SFM_BUNDLE_LOSS_* codes (include/sfm_hip.h)
 BUNDLE_LOSSES = ("squared", "huber", "cauchy")
@@ -237,6 +238,24 @@ class RotavgOptions(C.Structure):
 
 class RotavgInfo(C.Structure):
     """sfm_rotavg_info"""
+    _fields_ = [("initial_cost", C.c_double), ("final_cost", C.c_double), ("steps", C.c_int32), ("status", C.c_int32),
+                ("cg_iterations", C.c_int32), ("cg_max", C.c_int32), ("registered", C.c_int32), ("rounds", C.c_int32)]
+
+
+# the statuses of sfm_average_translations, in the order of their SFM_TRANSAVG_* codes (include/sfm_hip.h)
+TRANSAVG_STATUS = ("converged", "max_steps", "cg_failed", "bad_index")
+TRANSAVG_INIT_TREE, TRANSAVG_INIT_GIVEN = 0, 1
+
+
+class TransavgOptions(C.Structure):
+    """sfm_transavg_options"""
+    _fields_ = [("loss", C.c_int32), ("init", C.c_int32), ("max_steps", C.c_int32), ("max_cg_iterations", C.c_int32),
+                ("warmup_steps", C.c_int32), ("reserved", C.c_int32), ("loss_scale", C.c_double), ("cg_tolerance", C.c_double),
+                ("step_tolerance", C.c_double)]
+
+
+class TransavgInfo(C.Structure):
+    """sfm_transavg_info"""
     _fields_ = [("initial_cost", C.c_double), ("final_cost", C.c_double), ("steps", C.c_int32), ("status", C.c_int32),
                 ("cg_iterations", C.c_int32), ("cg_max", C.c_int32), ("registered", C.c_int32), ("rounds", C.c_int32)]
 
@@ -291,6 +310,8 @@ def load() -> C.CDLL:
     lib.sfm_pair_poses_workspace_bytes.argtypes = [_I64, _I64]
     lib.sfm_average_rotations_workspace_bytes.restype = C.c_int64
     lib.sfm_average_rotations_workspace_bytes.argtypes = [_I64, _I64]
+    lib.sfm_average_translations_workspace_bytes.restype = C.c_int64
+    lib.sfm_average_translations_workspace_bytes.argtypes = [_I64, _I64]
     if lib.sfm_abi_version() != ABI_VERSION:
         raise NativeLibraryError(
             f"libsfm_hip.so ABI {lib.sfm_abi_version()} != expected {ABI_VERSION}; rebuild it")

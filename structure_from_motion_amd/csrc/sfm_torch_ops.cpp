@@ -12,7 +12,7 @@
 // homography_ransac_pass_ (sfm_homography.hip), the ragged two-view pass verify_pairs_ (sfm_view_graph.hip) and the poses behind it
 // pair_poses (sfm_view_graph_pose.hip), and the
 // refinement of a winner pnp_refine (sfm_pnp_refine.hip), bundle_adjust (sfm_bundle.hip), triangulate_tracks
-// (sfm_tracks.hip), build_tracks (sfm_track_build.hip) and average_rotations (sfm_rotation_averaging.hip).  The reference call sites these serve: apps/sfm.py:110-119 (RANSAC-E), :133-138 (pose),
+// (sfm_tracks.hip), build_tracks (sfm_track_build.hip), average_rotations (sfm_rotation_averaging.hip) and average_translations (sfm_translation_averaging.hip).  The reference call sites these serve: apps/sfm.py:110-119 (RANSAC-E), :133-138 (pose),
 // :181-186 (triangulation).
 //
 // Built by structure_from_motion_amd/build.py into csrc/libsfm_torch_ops.so (host code only: no kernels here).
@@ -1228,6 +1228,91 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> average_rotations_meta(const 
             at::empty_symint({pairs.sym_size(0)}, like(pairs, at::kDouble)),
             at::empty_symint({c10::SymInt(kRotavgInfoWords)}, like(pairs, at::kLong))};
 }
+
+// translation averaging over a view graph (sfm_translation_averaging.hip): pairs int32 [Q, 2], directions f64 [Q, 3] (the
+// world directions v_q, or with `rotations` f64 [C, 9] or [C, 3, 3] the pairs' t_q), weights f64 [Q], `cameras` = C, the root,
+// initial f64 [C, 3] (given: the start; None: the spanning tree), the loss (SFM_BUNDLE_LOSS_*) with its scale (a sine) and the
+// limits -> positions f64 [C, 3], registered uint8 [C], level int32 [C] (-1: unregistered), residual f64 [Q] (radians),
+// scale f64 [Q], info int64 [5] viewing the sfm_transavg_info record.  The call synchronises the stream.
+constexpr int64_t kTransavgInfoWords = sizeof(sfm_transavg_info) / 8;
+
+void transavg_check(const Tensor& pairs, const Tensor& directions, const std::optional<Tensor>& rotations, const Tensor& weights,
+                    int64_t cameras, int64_t root, const std::optional<Tensor>& initial, int64_t loss, double loss_scale,
+                    int64_t warmup_steps, int64_t max_steps, int64_t max_cg_iterations, double cg_tolerance,
+                    double step_tolerance) {
+    TORCH_CHECK(pairs.dim() == 2 && pairs.size(1) == 2, "sfm_hip: pairs must be [Q, 2]");
+    const int64_t Q = pairs.size(0);
+    TORCH_CHECK(directions.dim() == 2 && directions.size(0) == Q && directions.size(1) == 3, "sfm_hip: directions must be [Q, 3]");
+    TORCH_CHECK(weights.dim() == 1 && weights.size(0) == Q, "sfm_hip: weights must be [Q]");
+    TORCH_CHECK(cameras >= 1 && cameras <= 0x7FFFFFFF && Q < ((int64_t)1 << 30),
+                "sfm_hip: average_translations: cameras must be in [1, 2^31) and edges below 2^30");
+    TORCH_CHECK(root >= 0 && root < cameras, "sfm_hip: root must be a camera index");
+    if (rotations.has_value() && rotations->defined())
+        TORCH_CHECK((rotations->dim() == 2 && rotations->size(0) == cameras && rotations->size(1) == 9) ||
+                        (rotations->dim() == 3 && rotations->size(0) == cameras && rotations->size(1) == 3 && rotations->size(2) == 3),
+                    "sfm_hip: rotations must be [cameras, 9] or [cameras, 3, 3]");
+    if (initial.has_value() && initial->defined())
+        TORCH_CHECK(initial->dim() == 2 && initial->size(0) == cameras && initial->size(1) == 3, "sfm_hip: initial must be [cameras, 3]");
+    TORCH_CHECK(loss >= SFM_BUNDLE_LOSS_SQUARED && loss <= SFM_BUNDLE_LOSS_CAUCHY, "sfm_hip: loss must be 0 (squared), 1 (huber) or 2 (cauchy)");
+    TORCH_CHECK(loss_scale > 0.0 && std::isfinite(loss_scale), "sfm_hip: loss_scale must be finite and positive");
+    TORCH_CHECK(warmup_steps >= 0 && warmup_steps <= 0x7FFFFFFF, "sfm_hip: warmup_steps must be in [0, 2^31)");
+    TORCH_CHECK(max_steps >= 0 && max_steps <= 0x7FFFFFFF, "sfm_hip: max_steps must be in [0, 2^31)");
+    TORCH_CHECK(max_cg_iterations >= 1 && max_cg_iterations <= 0x7FFFFFFF, "sfm_hip: max_cg_iterations must be in [1, 2^31)");
+    TORCH_CHECK(cg_tolerance > 0.0 && cg_tolerance < 1.0, "sfm_hip: cg_tolerance must be in (0, 1)");
+    TORCH_CHECK(step_tolerance > 0.0 && std::isfinite(step_tolerance), "sfm_hip: step_tolerance must be finite and positive");
+}
+
+using TransavgResult = std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor>;
+
+TransavgResult average_translations(const Tensor& pairs, const Tensor& directions, const std::optional<Tensor>& rotations,
+                                    const Tensor& weights, int64_t cameras, int64_t root, const std::optional<Tensor>& initial,
+                                    int64_t loss, double loss_scale, int64_t warmup_steps, int64_t max_steps,
+                                    int64_t max_cg_iterations, double cg_tolerance, double step_tolerance) {
+    const OpDevice scope(pairs);
+    need(pairs, "pairs", at::kInt);
+    need(directions, "directions", at::kDouble);
+    need(weights, "weights", at::kDouble);
+    const bool rotated = rotations.has_value() && rotations->defined();
+    if (rotated) need(*rotations, "rotations", at::kDouble);
+    const bool given = initial.has_value() && initial->defined();
+    if (given) need(*initial, "initial", at::kDouble);
+    transavg_check(pairs, directions, rotations, weights, cameras, root, initial, loss, loss_scale, warmup_steps, max_steps,
+                   max_cg_iterations, cg_tolerance, step_tolerance);
+    const int64_t Q = pairs.size(0);
+    Tensor positions = at::empty({cameras, 3}, like(pairs, at::kDouble));
+    Tensor registered = at::empty({cameras}, like(pairs, at::kByte));
+    Tensor level = at::empty({cameras}, like(pairs, at::kInt));
+    Tensor residual = at::empty({Q}, like(pairs, at::kDouble));
+    Tensor scale = at::empty({Q}, like(pairs, at::kDouble));
+    Tensor info = at::empty({kTransavgInfoWords}, like(pairs, at::kLong));
+    const int64_t bytes = sfm_average_translations_workspace_bytes(cameras, Q);
+    TORCH_CHECK(bytes >= 0, "sfm_hip: average_translations: ", cameras, " cameras, ", Q, " edges exceed the limits");
+    Tensor ws = at::empty({bytes}, like(pairs, at::kByte));
+    const sfm_transavg_options options{(int32_t)loss, given ? SFM_TRANSAVG_INIT_GIVEN : SFM_TRANSAVG_INIT_TREE, (int32_t)max_steps,
+                                       (int32_t)max_cg_iterations, (int32_t)warmup_steps, 0, loss_scale, cg_tolerance,
+                                       step_tolerance};
+    ok(sfm_average_translations(cameras, Q, ptr<int32_t>(pairs), ptr<double>(directions),
+                                rotated ? ptr<double>(*rotations) : nullptr, ptr<double>(weights), root,
+                                given ? ptr<double>(*initial) : nullptr, &options, ptr<double>(positions),
+                                ptr<uint8_t>(registered), ptr<int32_t>(level), ptr<double>(residual), ptr<double>(scale),
+                                reinterpret_cast<sfm_transavg_info*>(ptr<int64_t>(info)), ws.data_ptr(), bytes, current_stream()),
+       "sfm_average_translations");
+    return {positions, registered, level, residual, scale, info};
+}
+
+TransavgResult average_translations_meta(const Tensor& pairs, const Tensor& directions, const std::optional<Tensor>& rotations,
+                                         const Tensor& weights, int64_t cameras, int64_t root,
+                                         const std::optional<Tensor>& initial, int64_t loss, double loss_scale,
+                                         int64_t warmup_steps, int64_t max_steps, int64_t max_cg_iterations,
+                                         double cg_tolerance, double step_tolerance) {
+    transavg_check(pairs, directions, rotations, weights, cameras, root, initial, loss, loss_scale, warmup_steps, max_steps,
+                   max_cg_iterations, cg_tolerance, step_tolerance);
+    const c10::SymInt C(cameras);
+    return {at::empty_symint({C, c10::SymInt(3)}, like(pairs, at::kDouble)), at::empty_symint({C}, like(pairs, at::kByte)),
+            at::empty_symint({C}, like(pairs, at::kInt)), at::empty_symint({pairs.sym_size(0)}, like(pairs, at::kDouble)),
+            at::empty_symint({pairs.sym_size(0)}, like(pairs, at::kDouble)),
+            at::empty_symint({c10::SymInt(kTransavgInfoWords)}, like(pairs, at::kLong))};
+}
 }  // namespace
 
 // the C-ABI version this op library was compiled against (include/sfm_hip.h); ops.load() compares it with the
@@ -1325,6 +1410,9 @@ TORCH_LIBRARY(sfm_hip, m) {
     m.def("average_rotations(Tensor pairs, Tensor relative, Tensor weights, int cameras, int root, Tensor? initial, int loss, "
           "float loss_scale, int max_steps, int max_cg_iterations, float cg_tolerance, float step_tolerance) -> "
           "(Tensor, Tensor, Tensor, Tensor, Tensor)");
+    m.def("average_translations(Tensor pairs, Tensor directions, Tensor? rotations, Tensor weights, int cameras, int root, "
+          "Tensor? initial, int loss, float loss_scale, int warmup_steps, int max_steps, int max_cg_iterations, "
+          "float cg_tolerance, float step_tolerance) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
 }
 
 // ROCm devices dispatch under torch's "CUDA" key (the name of the dispatch key, not a CUDA code path)
@@ -1376,6 +1464,7 @@ TORCH_LIBRARY_IMPL(sfm_hip, CUDA, m) {
     m.impl("build_tracks", &build_tracks);
     m.impl("build_tracks_", &build_tracks_out);
     m.impl("average_rotations", &average_rotations);
+    m.impl("average_translations", &average_translations);
 }
 
 // sample_philox has no tensor argument to dispatch on: registered for every backend, it checks its device itself
@@ -1467,4 +1556,5 @@ TORCH_LIBRARY_IMPL(sfm_hip, Meta, m) {
     m.impl("build_tracks", &build_tracks_meta);
     m.impl("build_tracks_", &build_tracks_out_meta);
     m.impl("average_rotations", &average_rotations_meta);
+    m.impl("average_translations", &average_translations_meta);
 }

@@ -947,6 +947,52 @@ def read_rotavg_info(info: torch.Tensor) -> RotavgInfo:
 
 
 # ------------------------------------------------------------------------------------------------------
+# translation averaging over a view graph (csrc/sfm_translation_averaging.hip): pairs int32 [Q,2], directions [Q,3] (the world
+# directions v_q ~ c_j - c_i, or with ``rotations`` the pairs' t_q), weights [Q]
+# ------------------------------------------------------------------------------------------------------
+TRANSAVG_STATUS = _native.TRANSAVG_STATUS   # "converged", "max_steps", "cg_failed", "bad_index": the index is the SFM_TRANSAVG_* code
+TRANSAVG_CONVERGED, TRANSAVG_MAX_STEPS, TRANSAVG_CG_FAILED, TRANSAVG_BAD_INDEX = 0, 1, 2, 3
+
+
+def average_translations(pairs, directions, weights, cameras: int, root: int = 0, rotations=None, initial=None,
+                         loss: str = "squared", loss_scale: float = 1.0, warmup_steps: int = 10, max_steps: int = 500,
+                         max_cg_iterations: int = 500, cg_tolerance: float = 1e-6, step_tolerance: float = 1e-8):
+    """One position per camera from one direction per edge of a graph (``sfm_average_translations``)
+    -> (positions [C,3], registered uint8 [C], level int32 [C] (-1: unregistered), residual [Q] in radians, scale [Q], info
+    int64 [5] viewing the sfm_transavg_info record; ``read_transavg_info``).  ``rotations`` [C,3,3] (world -> camera): the
+    directions are the pairs' ``t_q`` and the world directions are computed on the device.  ``initial`` [C,3] starts from
+    those positions instead of the spanning tree.  ``loss`` in ``BUNDLE_LOSSES`` with ``loss_scale`` a sine.  The call
+    synchronises the current stream: the host reads the stop flags between level rounds, steps and CG chunks."""
+    code, scale = _bundle_loss(loss, loss_scale)
+    op = ops.load()
+    return op.average_translations(pairs.contiguous(), directions.contiguous(),
+                                   None if rotations is None else rotations.contiguous(), weights.contiguous(), int(cameras),
+                                   int(root), None if initial is None else initial.contiguous(), code, scale,
+                                   int(warmup_steps), int(max_steps), int(max_cg_iterations), float(cg_tolerance),
+                                   float(step_tolerance))
+
+
+@dataclass
+class TransavgInfo:
+    initial_cost: float   # sum of w rho(e) over the used edges at the first linearisation (NaN for TRANSAVG_BAD_INDEX)
+    final_cost: float     # ... at the result
+    steps: int            # completed steps
+    status: int           # TRANSAVG_*
+    cg_iterations: int    # conjugate-gradient iterations over all steps
+    cg_max: int           # the most conjugate-gradient iterations of one step
+    registered: int       # cameras with a level, the root included
+    rounds: int           # the largest level
+
+
+def read_transavg_info(info: torch.Tensor) -> TransavgInfo:
+    """Host copy of an sfm_transavg_info record (int64 [5]) (synchronises)."""
+    raw = info.cpu().numpy()
+    costs = raw[0:2].view(np.float64)
+    ints = raw[2:5].view(np.int32)
+    return TransavgInfo(float(costs[0]), float(costs[1]), *(int(v) for v in ints))
+
+
+# ------------------------------------------------------------------------------------------------------
 # triangulation of multi-view tracks (csrc/sfm_tracks.hip): poses [C,12] = R (9) | t (3) world -> camera, observations
 # (camera index, point index) int32 [M] each and pixels [M,2]
 # ------------------------------------------------------------------------------------------------------
