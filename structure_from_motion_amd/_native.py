@@ -225,9 +225,19 @@ class BundleOptions(C.Structure):
     _fields_ = [("loss", C.c_int32), ("reserved", C.c_int32), ("loss_scale", C.c_double)]
 
 
-# the statuses of sfm_average_rotations, in the order of their SFM_ROTAVG_* codes (include/sfm_hip.h)
-ROTAVG_STATUS = ("converged", "max_steps", "cg_failed", "bad_index")
-ROTAVG_INIT_TREE, ROTAVG_INIT_GIVEN = 0, 1
+# the statuses of sfm_average_rotations and sfm_average_translations, in the order of their SFM_ROTAVG_* / SFM_TRANSAVG_* codes
+# (include/sfm_hip.h), and their two starts: one set of values and one info record under the names of both solvers
+GRAPH_STATUS = ROTAVG_STATUS = TRANSAVG_STATUS = ("converged", "max_steps", "cg_failed", "bad_index")
+ROTAVG_INIT_TREE, ROTAVG_INIT_GIVEN = TRANSAVG_INIT_TREE, TRANSAVG_INIT_GIVEN = 0, 1
+
+
+class GraphInfo(C.Structure):
+    """sfm_rotavg_info and sfm_transavg_info"""
+    _fields_ = [("initial_cost", C.c_double), ("final_cost", C.c_double), ("steps", C.c_int32), ("status", C.c_int32),
+                ("cg_iterations", C.c_int32), ("cg_max", C.c_int32), ("registered", C.c_int32), ("rounds", C.c_int32)]
+
+
+RotavgInfo = TransavgInfo = GraphInfo
 
 
 class RotavgOptions(C.Structure):
@@ -236,28 +246,11 @@ class RotavgOptions(C.Structure):
                 ("loss_scale", C.c_double), ("cg_tolerance", C.c_double), ("step_tolerance", C.c_double)]
 
 
-class RotavgInfo(C.Structure):
-    """sfm_rotavg_info"""
-    _fields_ = [("initial_cost", C.c_double), ("final_cost", C.c_double), ("steps", C.c_int32), ("status", C.c_int32),
-                ("cg_iterations", C.c_int32), ("cg_max", C.c_int32), ("registered", C.c_int32), ("rounds", C.c_int32)]
-
-
-# the statuses of sfm_average_translations, in the order of their SFM_TRANSAVG_* codes (include/sfm_hip.h)
-TRANSAVG_STATUS = ("converged", "max_steps", "cg_failed", "bad_index")
-TRANSAVG_INIT_TREE, TRANSAVG_INIT_GIVEN = 0, 1
-
-
 class TransavgOptions(C.Structure):
     """sfm_transavg_options"""
     _fields_ = [("loss", C.c_int32), ("init", C.c_int32), ("max_steps", C.c_int32), ("max_cg_iterations", C.c_int32),
                 ("warmup_steps", C.c_int32), ("reserved", C.c_int32), ("loss_scale", C.c_double), ("cg_tolerance", C.c_double),
                 ("step_tolerance", C.c_double)]
-
-
-class TransavgInfo(C.Structure):
-    """sfm_transavg_info"""
-    _fields_ = [("initial_cost", C.c_double), ("final_cost", C.c_double), ("steps", C.c_int32), ("status", C.c_int32),
-                ("cg_iterations", C.c_int32), ("cg_max", C.c_int32), ("registered", C.c_int32), ("rounds", C.c_int32)]
 
 
 _lib = None

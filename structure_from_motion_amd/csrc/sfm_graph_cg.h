@@ -1,7 +1,8 @@
 // What the two averaging solvers over a camera graph share (rotation averaging, DESIGN.md §6t, and translation averaging,
 // §6u), defined once: the state and the workspace, the self-pair check, the level rounds with the tree start as a policy,
 // registration, adjacency, the weighted graph Laplacian system, the three-launch conjugate-gradient iteration with the
-// Jacobi preconditioner, the step maximum, the stop decision and the host loop that reads three flags from pinned memory.
+// Jacobi preconditioner, the step maximum, the stop decision, the host loop that reads three flags from pinned memory, the
+// checks of an entry point (check_entry) and the info record at the end of a finish kernel (finish_info).
 //
 // A solver brings an `Args` (a trivially copyable struct passed to every kernel by value) with
 //   int C, Q, root;  const int32_t* pairs;  const double* weights;  uint8_t* registered;  int32_t* level;
@@ -17,7 +18,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include <stddef.h>
 #include <stdint.h>
+#include <stdio.h>
 
 #include "sfm_common.h"
 #include "sfm_math.h"
@@ -35,6 +38,16 @@ constexpr int kRoundBatch = 32;    // level rounds enqueued between two reads of
 
 // the statuses of both solvers (SFM_ROTAVG_* and SFM_TRANSAVG_* carry these values)
 constexpr int kConverged = 0, kMaxSteps = 1, kCgFailed = 2, kBadIndex = 3;
+// the starts of both solvers (SFM_ROTAVG_INIT_* and SFM_TRANSAVG_INIT_*)
+constexpr int kInitTree = 0, kInitGiven = 1;
+
+// finish_info() writes either info record: one layout under two names
+#define SFM_SAME_FIELD(f) (offsetof(sfm_rotavg_info, f) == offsetof(sfm_transavg_info, f))
+static_assert(sizeof(sfm_rotavg_info) == sizeof(sfm_transavg_info) && SFM_SAME_FIELD(initial_cost) && SFM_SAME_FIELD(final_cost) &&
+                  SFM_SAME_FIELD(steps) && SFM_SAME_FIELD(status) && SFM_SAME_FIELD(cg_iterations) && SFM_SAME_FIELD(cg_max) &&
+                  SFM_SAME_FIELD(registered) && SFM_SAME_FIELD(rounds),
+              "sfm_rotavg_info and sfm_transavg_info have one layout");
+#undef SFM_SAME_FIELD
 
 // Written by one thread of a launch (last_round, registered, unknowns and xmax_bits: by integer atomics or by stores of one
 // value), read by every launch after it.
@@ -395,12 +408,69 @@ static __global__ void decide_kernel(int max_steps, int min_converged_steps, dou
     }
 }
 
+// The end of a solver's finish kernel (one workgroup of kOneGroup threads, after the final edge pass): after a bad index the
+// filler of `registered` and `level` (the solver's kernel fills its own arrays with NaN) and the BAD_INDEX record; otherwise
+// the final cost and the record from the state.
+template <class Info, class Args>
+SFM_DEVICE void finish_info(const Args& a, int blocks, const Ws& w, Info* __restrict__ info) {
+    __shared__ double part[kOneGroup / kWave];
+    __shared__ double total[1];
+    const State* st = w.st;
+    if (st->bad) {
+        for (int64_t i = threadIdx.x; i < a.C; i += kOneGroup) a.registered[i] = 0;
+        for (int64_t i = threadIdx.x; a.level && i < a.C; i += kOneGroup) a.level[i] = -1;
+        if (threadIdx.x == 0) *info = Info{(double)NAN, (double)NAN, 0, kBadIndex, 0, 0, 0, 0};
+        return;
+    }
+    const double cost = sum_cost<kOneGroup>(w, blocks, part, total);
+    if (threadIdx.x != 0) return;
+    *info = Info{st->have_initial ? st->initial_cost : cost, cost, st->steps, st->status, st->cg_total, st->cg_max,
+                 st->registered, st->last_round};
+}
+
 // The host's copy of the three flags {stop, cg_done, last_round}: pinned, one per host thread, allocated on its first call.
 inline int32_t* pinned_flags() {
     thread_local int32_t* flags = nullptr;
     if (!flags && hipHostMalloc(reinterpret_cast<void**>(&flags), 3 * sizeof(int32_t), hipHostMallocDefault) != hipSuccess)
         flags = nullptr;
     return flags;
+}
+
+// Every check of an entry point before its first launch (a refused call has enqueued nothing), in the order of the texts
+// below; the message is "<name>: <text>".  `o` is read only where `has_options`; `tag` names the solver's SFM_<tag>_INIT_*.
+// `own`: the refusal of the solver's own option checks, whose place is after max_cg_iterations, or nullptr.  `pointers`: every
+// pointer the call needs is there.  `needed`: the size of the workspace from the solver's carve (any value for refused
+// sizes).  On SFM_OK *flags is the host's copy of the three flags.
+template <class Options>
+int check_entry(const char* name, const char* tag, int64_t cameras, int64_t edges, int64_t root, bool has_options,
+                const Options& o, const char* own, bool pointers, const void* workspace, int64_t workspace_bytes,
+                int64_t needed, int32_t** flags) {
+    char init[80];
+    snprintf(init, sizeof(init), "init must be SFM_%s_INIT_TREE or SFM_%s_INIT_GIVEN", tag, tag);
+    const char* text =
+        !sizes_ok(cameras, edges)                                  ? "cameras must be in [1, 2^31) and edges in [0, 2^30)"
+        : root < 0 || root >= cameras                              ? "root must be a camera index"
+        : !has_options                                             ? "null pointer (options)"
+        : o.loss < SFM_BUNDLE_LOSS_SQUARED || o.loss > SFM_BUNDLE_LOSS_CAUCHY ? "loss must be in 0..2"
+        : o.init != kInitTree && o.init != kInitGiven              ? init
+        : o.max_steps < 0                                          ? "max_steps must be at least 0"
+        : o.max_cg_iterations < 1                                  ? "max_cg_iterations must be at least 1"
+        : own                                                      ? own
+        : !(o.loss_scale > 0.0) || !isfinite(o.loss_scale)         ? "loss_scale must be finite and positive"
+        : !(o.cg_tolerance > 0.0 && o.cg_tolerance < 1.0)          ? "cg_tolerance must be finite and in (0, 1)"
+        : !(o.step_tolerance > 0.0) || !isfinite(o.step_tolerance) ? "step_tolerance must be finite and positive"
+        : !pointers                                                ? "null pointer"
+        : workspace_bytes < needed                                 ? "workspace too small"
+        : ((uintptr_t)workspace & 15) != 0                         ? "workspace must be 16-byte aligned"
+                                                                   : nullptr;
+    int code = SFM_EINVAL;
+    if (!text && !(*flags = pinned_flags())) {
+        text = "no pinned host memory for the flags";
+        code = SFM_EHIP;
+    }
+    if (!text) return SFM_OK;
+    snprintf(sfmhost::error_buffer(), sfmhost::kErrorBytes, "%s: %s", name, text);
+    return code;
 }
 
 struct Limits {

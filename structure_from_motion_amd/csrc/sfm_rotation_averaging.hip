@@ -46,12 +46,9 @@ namespace {
 using graphcg::is_free;
 using graphcg::kOneGroup;
 using graphcg::kThreads;
-using graphcg::sizes_ok;
 using graphcg::State;
-using graphcg::sum_cost;
 using graphcg::Ws;
 using sfm::block_sum;
-using sfmhost::fail;
 
 static_assert(sizeof(sfm_rotavg_info) == 40, "sfm_rotavg_info layout is part of the ABI");
 static_assert(sizeof(sfm_rotavg_options) == 40, "sfm_rotavg_options layout is part of the ABI");
@@ -59,8 +56,12 @@ static_assert(sizeof(sfm_rotavg_options) == 40, "sfm_rotavg_options layout is pa
 static_assert(SFM_ROTAVG_CONVERGED == graphcg::kConverged && SFM_ROTAVG_MAX_STEPS == graphcg::kMaxSteps &&
                   SFM_ROTAVG_CG_FAILED == graphcg::kCgFailed && SFM_ROTAVG_BAD_INDEX == graphcg::kBadIndex,
               "the shared kernels write these statuses");
+static_assert(SFM_ROTAVG_INIT_TREE == graphcg::kInitTree && SFM_ROTAVG_INIT_GIVEN == graphcg::kInitGiven,
+              "graphcg::check_entry tests these");
 
+// The bytes of the workspace, carved from `base` (0: the size only); -1 for sizes the call refuses
 int64_t carve(uintptr_t base, int64_t C, int64_t Q, Ws* w) {
+    if (!graphcg::sizes_ok(C, Q)) return -1;
     sfmhost::Carver k{base, 0};
     graphcg::carve(k, C, Q, w);
     return k.at;
@@ -190,24 +191,14 @@ __global__ __launch_bounds__(kThreads) void rotavg_step_kernel(Args a, Ws w) {
     graphcg::record_step(w, x);
 }
 
-// One workgroup, after the final edge pass: info; after a bad index the filler of every output.
+// One workgroup, after the final edge pass: after a bad index the filler of the rotations and residuals; graphcg::finish_info
+// has the rest of the filler and info.
 __global__ __launch_bounds__(kOneGroup) void rotavg_finish_kernel(Args a, int blocks, Ws w, sfm_rotavg_info* __restrict__ info) {
-    __shared__ double part[kOneGroup / kWave];
-    __shared__ double total[1];
-    const State* st = w.st;
-    if (st->bad) {
+    if (w.st->bad) {
         for (int64_t i = threadIdx.x; i < 9 * (int64_t)a.C; i += kOneGroup) a.R[i] = (double)NAN;
-        for (int64_t i = threadIdx.x; i < a.C; i += kOneGroup) a.registered[i] = 0;
-        for (int64_t i = threadIdx.x; a.level && i < a.C; i += kOneGroup) a.level[i] = -1;
         for (int64_t i = threadIdx.x; i < a.Q; i += kOneGroup) a.residual[i] = (double)NAN;
-        if (threadIdx.x == 0)
-            *info = sfm_rotavg_info{(double)NAN, (double)NAN, 0, SFM_ROTAVG_BAD_INDEX, 0, 0, 0, 0};
-        return;
     }
-    const double cost = sum_cost<kOneGroup>(w, blocks, part, total);
-    if (threadIdx.x != 0) return;
-    *info = sfm_rotavg_info{st->have_initial ? st->initial_cost : cost, cost, st->steps, st->status, st->cg_total, st->cg_max,
-                            st->registered, st->last_round};
+    graphcg::finish_info(a, blocks, w, info);
 }
 
 // The launches that are rotation averaging's own (graphcg::run has the rest)
@@ -232,7 +223,6 @@ struct Driver {
 extern "C" {
 
 int64_t sfm_average_rotations_workspace_bytes(int64_t cameras, int64_t edges) {
-    if (!sizes_ok(cameras, edges)) return -1;
     Ws w;
     return carve(0, cameras, edges, &w);
 }
@@ -241,34 +231,16 @@ int sfm_average_rotations(int64_t cameras, int64_t edges, const int32_t* pairs, 
                           const double* weights, int64_t root, const double* initial, const sfm_rotavg_options* options,
                           double* rotations, uint8_t* registered, int32_t* level, double* residual, sfm_rotavg_info* info,
                           void* workspace, int64_t workspace_bytes, void* stream) {
-    // every check before the first launch: a refused call has enqueued nothing
-    if (!sizes_ok(cameras, edges))
-        return fail(SFM_EINVAL, "sfm_average_rotations: cameras must be in [1, 2^31) and edges in [0, 2^30)");
-    if (root < 0 || root >= cameras) return fail(SFM_EINVAL, "sfm_average_rotations: root must be a camera index");
-    if (!options) return fail(SFM_EINVAL, "sfm_average_rotations: null pointer (options)");
-    const sfm_rotavg_options o = *options;
-    if (o.loss < SFM_BUNDLE_LOSS_SQUARED || o.loss > SFM_BUNDLE_LOSS_CAUCHY)
-        return fail(SFM_EINVAL, "sfm_average_rotations: loss must be in 0..2");
-    if (o.init != SFM_ROTAVG_INIT_TREE && o.init != SFM_ROTAVG_INIT_GIVEN)
-        return fail(SFM_EINVAL, "sfm_average_rotations: init must be SFM_ROTAVG_INIT_TREE or SFM_ROTAVG_INIT_GIVEN");
-    if (o.max_steps < 0) return fail(SFM_EINVAL, "sfm_average_rotations: max_steps must be at least 0");
-    if (o.max_cg_iterations < 1) return fail(SFM_EINVAL, "sfm_average_rotations: max_cg_iterations must be at least 1");
-    if (!(o.loss_scale > 0.0) || !isfinite(o.loss_scale))
-        return fail(SFM_EINVAL, "sfm_average_rotations: loss_scale must be finite and positive");
-    if (!(o.cg_tolerance > 0.0 && o.cg_tolerance < 1.0))
-        return fail(SFM_EINVAL, "sfm_average_rotations: cg_tolerance must be finite and in (0, 1)");
-    if (!(o.step_tolerance > 0.0) || !isfinite(o.step_tolerance))
-        return fail(SFM_EINVAL, "sfm_average_rotations: step_tolerance must be finite and positive");
+    const sfm_rotavg_options o = options ? *options : sfm_rotavg_options{};
     const bool given = o.init == SFM_ROTAVG_INIT_GIVEN;
-    if (!rotations || !registered || !info || !workspace || (given && !initial) ||
-        (edges > 0 && (!pairs || !relative || !weights || !residual)))
-        return fail(SFM_EINVAL, "sfm_average_rotations: null pointer");
+    const bool pointers = rotations && registered && info && workspace && (!given || initial) &&
+                          (edges == 0 || (pairs && relative && weights && residual));
     Ws w;
-    if (workspace_bytes < carve((uintptr_t)workspace, cameras, edges, &w))
-        return fail(SFM_EINVAL, "sfm_average_rotations: workspace too small");
-    if (((uintptr_t)workspace & 15) != 0) return fail(SFM_EINVAL, "sfm_average_rotations: workspace must be 16-byte aligned");
-    int32_t* flags = graphcg::pinned_flags();
-    if (!flags) return fail(SFM_EHIP, "sfm_average_rotations: no pinned host memory for the flags");
+    int32_t* flags;
+    const int rc = graphcg::check_entry("sfm_average_rotations", "ROTAVG", cameras, edges, root, options != nullptr, o, nullptr,
+                                        pointers, workspace, workspace_bytes, carve((uintptr_t)workspace, cameras, edges, &w),
+                                        &flags);
+    if (rc != SFM_OK) return rc;
     const sfmloss::Loss loss{o.loss, 0, o.loss_scale, o.loss_scale * o.loss_scale};
     const Args a{(int)cameras, (int)edges, (int)root, given, pairs, relative, weights, initial, rotations, registered, level, residual};
     const graphcg::Limits limits{o.max_steps, o.max_cg_iterations, 0, o.cg_tolerance, o.step_tolerance};

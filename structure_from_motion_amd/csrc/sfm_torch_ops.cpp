@@ -9,10 +9,11 @@
 // sample_fit_philox_; and the PnP ops (sfm_pnp.hip) pnp_fit, pnp_score and the whole pass pnp_ransac_pass_, their P3P
 // forms p3p_fit and p3p_ransac_pass_ (sfm_p3p.h), the five-point fit five_point_fit and pass five_point_ransac_pass_
 // (sfm_five_point.hip), the homography ops homography_fit, homography_score, homography_inlier_mask and the pass
-// homography_ransac_pass_ (sfm_homography.hip), the ragged two-view pass verify_pairs_ (sfm_view_graph.hip) and the poses behind it
-// pair_poses (sfm_view_graph_pose.hip), and the
-// refinement of a winner pnp_refine (sfm_pnp_refine.hip), bundle_adjust (sfm_bundle.hip), triangulate_tracks
-// (sfm_tracks.hip), build_tracks (sfm_track_build.hip), average_rotations (sfm_rotation_averaging.hip) and average_translations (sfm_translation_averaging.hip).  The reference call sites these serve: apps/sfm.py:110-119 (RANSAC-E), :133-138 (pose),
+// homography_ransac_pass_ (sfm_homography.hip), the ragged two-view pass verify_pairs_ (sfm_view_graph.hip) and the poses
+// behind it pair_poses (sfm_view_graph_pose.hip), and the refinement of a winner pnp_refine (sfm_pnp_refine.hip),
+// bundle_adjust (sfm_bundle.hip, sfm_bundle_pcg.hip), triangulate_tracks (sfm_tracks.hip), build_tracks
+// (sfm_track_build.hip), average_rotations (sfm_rotation_averaging.hip) and average_translations
+// (sfm_translation_averaging.hip).  The reference call sites these serve: apps/sfm.py:110-119 (RANSAC-E), :133-138 (pose),
 // :181-186 (triangulation).
 //
 // Built by structure_from_motion_amd/build.py into csrc/libsfm_torch_ops.so (host code only: no kernels here).
@@ -780,13 +781,35 @@ std::tuple<Tensor, Tensor, Tensor> pnp_refine_meta(const Tensor& pts, const Tens
             at::empty_symint({pts.sym_size(0), c10::SymInt(kRefineInfoWords)}, like(pts, at::kLong))};
 }
 
-// bundle adjustment (sfm_bundle.hip): poses [C, 12], points [P, 3], camera / point indices int32 [M], pixels [M, 2];
-// fixed: the indices of the fixed cameras; info int64 [4] viewing the sfm_bundle_info record.  The workspace comes from
-// the caching allocator, stream-ordered like everything else (no host synchronisation).
-constexpr int64_t kBundleInfoWords = sizeof(sfm_bundle_info) / 8;
+// bundle adjustment, dense (sfm_bundle.hip) and with the iterative Schur solver (sfm_bundle_pcg.hip): poses [C, 12], points
+// [P, 3], camera / point indices int32 [M], pixels [M, 2]; fixed: the indices of the fixed cameras; the iterative solver takes
+// max_cg_iterations and cg_tolerance as well; info int64 [4] viewing the sfm_bundle_info record, int64 [5] viewing
+// sfm_bundle_pcg_info.  The workspace comes from the caching allocator, stream-ordered like everything else; the dense solver
+// does not synchronise the host, the iterative one synchronises the stream (the host reads the LM and CG stop flags).
+// The `_robust` ops add a loss (SFM_BUNDLE_LOSS_*, csrc/sfm_loss.h) and its scale in pixels: new ops, so that no existing
+// schema changes.  Four op families, each functional, in-place and Meta, over one body.
+void loss_check(int64_t loss, double loss_scale) {
+    TORCH_CHECK(loss >= SFM_BUNDLE_LOSS_SQUARED && loss <= SFM_BUNDLE_LOSS_CAUCHY, "sfm_hip: loss must be 0 (squared), 1 (huber) or 2 (cauchy)");
+    TORCH_CHECK(loss_scale > 0.0 && std::isfinite(loss_scale), "sfm_hip: loss_scale must be finite and positive");
+}
 
-void bundle_check(const Tensor& poses, const Tensor& points, const Tensor& cam, const Tensor& pt, const Tensor& pixels,
-                  at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed, int64_t max_steps) {
+sfm_bundle_options bundle_options(int64_t loss, double loss_scale) {
+    loss_check(loss, loss_scale);
+    return sfm_bundle_options{(int32_t)loss, 0, loss_scale};
+}
+
+// Which adjuster a call runs: the dense one (max_cg_iterations and cg_tolerance unread) or the iterative one; options: null
+// for the ops without a loss
+struct BundleSolver {
+    bool pcg;
+    int64_t max_cg_iterations;
+    double cg_tolerance;
+    const sfm_bundle_options* options;
+    int64_t info_words() const { return (pcg ? sizeof(sfm_bundle_pcg_info) : sizeof(sfm_bundle_info)) / 8; }
+};
+
+void bundle_check(const BundleSolver& s, const Tensor& poses, const Tensor& points, const Tensor& cam, const Tensor& pt,
+                  const Tensor& pixels, at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed, int64_t max_steps) {
     check_K(K);
     TORCH_CHECK(poses.dim() == 2 && poses.size(1) == 12, "sfm_hip: poses must be [C, 12]");
     TORCH_CHECK(points.dim() == 2 && points.size(1) == 3, "sfm_hip: points must be [P, 3]");
@@ -794,12 +817,16 @@ void bundle_check(const Tensor& poses, const Tensor& points, const Tensor& cam, 
     TORCH_CHECK(pixels.dim() == 2 && pixels.size(1) == 2 && pixels.size(0) == cam.size(0), "sfm_hip: pixels must be [M, 2]");
     TORCH_CHECK(max_steps >= 0 && max_steps <= 0x7FFFFFFF, "sfm_hip: max_steps must be in [0, 2^31)");
     for (int64_t c : fixed) TORCH_CHECK(c >= 0 && c < poses.size(0), "sfm_hip: fixed camera ", c, " out of range");
+    if (!s.pcg) return;
+    TORCH_CHECK(s.max_cg_iterations >= 1 && s.max_cg_iterations <= 0x7FFFFFFF, "sfm_hip: max_cg_iterations must be in [1, 2^31)");
+    TORCH_CHECK(s.cg_tolerance > 0.0 && s.cg_tolerance < 1.0, "sfm_hip: cg_tolerance must be in (0, 1)");
 }
 
-// options: null for the ops without a loss (sfm_bundle_adjust), else sfm_bundle_adjust_ex
-void bundle_adjust_out(Tensor& poses, Tensor& points, const Tensor& cam, const Tensor& pt, const Tensor& pixels,
-                       at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed, int64_t max_steps, Tensor& info,
-                       const Tensor& poses_in, const Tensor& points_in, const sfm_bundle_options* options = nullptr) {
+// The in-place form: poses_in / points_in are the start, poses / points the result (the same tensors for the `_` ops).  The
+// plain entry points forward to the _ex ones with null options, so the _ex ones serve every call.
+void bundle_run(const BundleSolver& s, Tensor& poses, Tensor& points, const Tensor& cam, const Tensor& pt, const Tensor& pixels,
+                at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed, int64_t max_steps, Tensor& info, const Tensor& poses_in,
+                const Tensor& points_in) {
     const OpDevice scope(poses);
     need(poses, "poses", at::kDouble);
     need(points, "points", at::kDouble);
@@ -809,168 +836,99 @@ void bundle_adjust_out(Tensor& poses, Tensor& points, const Tensor& cam, const T
     need(pt, "point_indices", at::kInt);
     need(pixels, "pixels", at::kDouble);
     need(info, "info", at::kLong);
-    bundle_check(poses_in, points_in, cam, pt, pixels, K, fixed, max_steps);
+    bundle_check(s, poses_in, points_in, cam, pt, pixels, K, fixed, max_steps);
     TORCH_CHECK(poses.sizes() == poses_in.sizes() && points.sizes() == points_in.sizes(), "sfm_hip: output shapes differ");
-    TORCH_CHECK(info.numel() == kBundleInfoWords, "sfm_hip: info must be int64 [4]");
+    TORCH_CHECK(info.numel() == s.info_words(), "sfm_hip: info must be int64 [", s.info_words(), "]");
     const int64_t C = poses.size(0), P = points.size(0), M = cam.size(0);
     std::vector<uint8_t> mask((size_t)C, 0);
     for (int64_t c : fixed) mask[(size_t)c] = 1;
-    const int64_t bytes = sfm_bundle_workspace_bytes(C, P, M);
-    TORCH_CHECK(bytes >= 0, "sfm_hip: bundle_adjust: ", C, " cameras, ", P, " points, ", M,
-                " observations exceed the limits (C <= 64, P and M < 2^31)");
+    const int64_t bytes = s.pcg ? sfm_bundle_pcg_workspace_bytes_ex(C, P, M, s.options) : sfm_bundle_workspace_bytes(C, P, M);
+    TORCH_CHECK(bytes >= 0, "sfm_hip: ", s.pcg ? "bundle_adjust_pcg: " : "bundle_adjust: ", C, " cameras, ", P, " points, ", M,
+                " observations exceed the limits ", s.pcg ? "(C >= 1; C, P and M < 2^31)" : "(C <= 64, P and M < 2^31)");
     Tensor ws = at::empty({bytes}, like(poses, at::kByte));
-    if (options)
+    void* const record = ptr<int64_t>(info);
+    if (s.pcg)
+        ok(sfm_bundle_adjust_pcg_ex(K.data(), C, P, M, mask.data(), ptr<double>(poses_in), ptr<double>(points_in),
+                                    ptr<int32_t>(cam), ptr<int32_t>(pt), ptr<double>(pixels), (int)max_steps,
+                                    (int)s.max_cg_iterations, s.cg_tolerance, ptr<double>(poses), ptr<double>(points),
+                                    static_cast<sfm_bundle_pcg_info*>(record), ws.data_ptr(), bytes, current_stream(), s.options),
+           s.options ? "sfm_bundle_adjust_pcg_ex" : "sfm_bundle_adjust_pcg");
+    else
         ok(sfm_bundle_adjust_ex(K.data(), C, P, M, mask.data(), ptr<double>(poses_in), ptr<double>(points_in),
                                 ptr<int32_t>(cam), ptr<int32_t>(pt), ptr<double>(pixels), (int)max_steps, ptr<double>(poses),
-                                ptr<double>(points), reinterpret_cast<sfm_bundle_info*>(ptr<int64_t>(info)), ws.data_ptr(),
-                                bytes, current_stream(), options),
-           "sfm_bundle_adjust_ex");
-    else
-        ok(sfm_bundle_adjust(K.data(), C, P, M, mask.data(), ptr<double>(poses_in), ptr<double>(points_in), ptr<int32_t>(cam),
-                             ptr<int32_t>(pt), ptr<double>(pixels), (int)max_steps, ptr<double>(poses), ptr<double>(points),
-                             reinterpret_cast<sfm_bundle_info*>(ptr<int64_t>(info)), ws.data_ptr(), bytes, current_stream()),
-           "sfm_bundle_adjust");
+                                ptr<double>(points), static_cast<sfm_bundle_info*>(record), ws.data_ptr(), bytes,
+                                current_stream(), s.options),
+           s.options ? "sfm_bundle_adjust_ex" : "sfm_bundle_adjust");
 }
 
-void bundle_adjust_inplace(Tensor& poses, Tensor& points, const Tensor& cam, const Tensor& pt, const Tensor& pixels,
-                           at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed, int64_t max_steps, Tensor& info) {
-    bundle_adjust_out(poses, points, cam, pt, pixels, K, fixed, max_steps, info, poses, points);
-}
+using BundleResult = std::tuple<Tensor, Tensor, Tensor>;
 
-std::tuple<Tensor, Tensor, Tensor> bundle_adjust(const Tensor& poses, const Tensor& points, const Tensor& cam, const Tensor& pt,
-                                                 const Tensor& pixels, at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed,
-                                                 int64_t max_steps) {
-    bundle_check(poses, points, cam, pt, pixels, K, fixed, max_steps);
+// The functional form; `meta`: the shapes of the results only
+BundleResult bundle_new(const BundleSolver& s, bool meta, const Tensor& poses, const Tensor& points, const Tensor& cam,
+                        const Tensor& pt, const Tensor& pixels, at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed,
+                        int64_t max_steps) {
+    bundle_check(s, poses, points, cam, pt, pixels, K, fixed, max_steps);
     Tensor poses_out = at::empty_like(poses);
     Tensor points_out = at::empty_like(points);
-    Tensor info = at::empty({kBundleInfoWords}, like(poses, at::kLong));
-    bundle_adjust_out(poses_out, points_out, cam, pt, pixels, K, fixed, max_steps, info, poses, points);
+    Tensor info = at::empty_symint({c10::SymInt(s.info_words())}, like(poses, at::kLong));
+    if (!meta) bundle_run(s, poses_out, points_out, cam, pt, pixels, K, fixed, max_steps, info, poses, points);
     return {poses_out, points_out, info};
 }
 
-std::tuple<Tensor, Tensor, Tensor> bundle_adjust_meta(const Tensor& poses, const Tensor& points, const Tensor& cam,
-                                                      const Tensor& pt, const Tensor& pixels, at::ArrayRef<double> K,
-                                                      at::ArrayRef<int64_t> fixed, int64_t max_steps) {
-    bundle_check(poses, points, cam, pt, pixels, K, fixed, max_steps);
-    return {at::empty_like(poses), at::empty_like(points),
-            at::empty_symint({c10::SymInt(kBundleInfoWords)}, like(poses, at::kLong))};
+// The twelve registered signatures
+void bundle_adjust_inplace(Tensor& poses, Tensor& points, const Tensor& cam, const Tensor& pt, const Tensor& pixels,
+                           at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed, int64_t max_steps, Tensor& info) {
+    bundle_run({false, 0, 0.0, nullptr}, poses, points, cam, pt, pixels, K, fixed, max_steps, info, poses, points);
 }
 
-// bundle adjustment with the iterative Schur solver (sfm_bundle_pcg.hip): the arguments of bundle_adjust plus
-// max_cg_iterations and cg_tolerance; info int64 [5] viewing the sfm_bundle_pcg_info record.  The call synchronises the
-// stream (the host reads the LM and CG stop flags).
-constexpr int64_t kBundlePcgInfoWords = sizeof(sfm_bundle_pcg_info) / 8;
-
-void bundle_pcg_check(const Tensor& poses, const Tensor& points, const Tensor& cam, const Tensor& pt, const Tensor& pixels,
-                      at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed, int64_t max_steps, int64_t max_cg_iterations,
-                      double cg_tolerance) {
-    bundle_check(poses, points, cam, pt, pixels, K, fixed, max_steps);
-    TORCH_CHECK(max_cg_iterations >= 1 && max_cg_iterations <= 0x7FFFFFFF, "sfm_hip: max_cg_iterations must be in [1, 2^31)");
-    TORCH_CHECK(cg_tolerance > 0.0 && cg_tolerance < 1.0, "sfm_hip: cg_tolerance must be in (0, 1)");
+BundleResult bundle_adjust(const Tensor& poses, const Tensor& points, const Tensor& cam, const Tensor& pt, const Tensor& pixels,
+                           at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed, int64_t max_steps) {
+    return bundle_new({false, 0, 0.0, nullptr}, false, poses, points, cam, pt, pixels, K, fixed, max_steps);
 }
 
-void bundle_adjust_pcg_out(Tensor& poses, Tensor& points, const Tensor& cam, const Tensor& pt, const Tensor& pixels,
-                           at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed, int64_t max_steps, int64_t max_cg_iterations,
-                           double cg_tolerance, Tensor& info, const Tensor& poses_in, const Tensor& points_in,
-                           const sfm_bundle_options* options = nullptr) {
-    const OpDevice scope(poses);
-    need(poses, "poses", at::kDouble);
-    need(points, "points", at::kDouble);
-    need(poses_in, "poses", at::kDouble);
-    need(points_in, "points", at::kDouble);
-    need(cam, "camera_indices", at::kInt);
-    need(pt, "point_indices", at::kInt);
-    need(pixels, "pixels", at::kDouble);
-    need(info, "info", at::kLong);
-    bundle_pcg_check(poses_in, points_in, cam, pt, pixels, K, fixed, max_steps, max_cg_iterations, cg_tolerance);
-    TORCH_CHECK(poses.sizes() == poses_in.sizes() && points.sizes() == points_in.sizes(), "sfm_hip: output shapes differ");
-    TORCH_CHECK(info.numel() == kBundlePcgInfoWords, "sfm_hip: info must be int64 [5]");
-    const int64_t C = poses.size(0), P = points.size(0), M = cam.size(0);
-    std::vector<uint8_t> mask((size_t)C, 0);
-    for (int64_t c : fixed) mask[(size_t)c] = 1;
-    const int64_t bytes = sfm_bundle_pcg_workspace_bytes_ex(C, P, M, options);   // null options: the plain size
-    TORCH_CHECK(bytes >= 0, "sfm_hip: bundle_adjust_pcg: ", C, " cameras, ", P, " points, ", M,
-                " observations exceed the limits (C >= 1; C, P and M < 2^31)");
-    Tensor ws = at::empty({bytes}, like(poses, at::kByte));
-    if (options)
-        ok(sfm_bundle_adjust_pcg_ex(K.data(), C, P, M, mask.data(), ptr<double>(poses_in), ptr<double>(points_in),
-                                    ptr<int32_t>(cam), ptr<int32_t>(pt), ptr<double>(pixels), (int)max_steps,
-                                    (int)max_cg_iterations, cg_tolerance, ptr<double>(poses), ptr<double>(points),
-                                    reinterpret_cast<sfm_bundle_pcg_info*>(ptr<int64_t>(info)), ws.data_ptr(), bytes,
-                                    current_stream(), options),
-           "sfm_bundle_adjust_pcg_ex");
-    else
-        ok(sfm_bundle_adjust_pcg(K.data(), C, P, M, mask.data(), ptr<double>(poses_in), ptr<double>(points_in),
-                                 ptr<int32_t>(cam), ptr<int32_t>(pt), ptr<double>(pixels), (int)max_steps, (int)max_cg_iterations,
-                                 cg_tolerance, ptr<double>(poses), ptr<double>(points),
-                                 reinterpret_cast<sfm_bundle_pcg_info*>(ptr<int64_t>(info)), ws.data_ptr(), bytes,
-                                 current_stream()),
-           "sfm_bundle_adjust_pcg");
+BundleResult bundle_adjust_meta(const Tensor& poses, const Tensor& points, const Tensor& cam, const Tensor& pt,
+                                const Tensor& pixels, at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed, int64_t max_steps) {
+    return bundle_new({false, 0, 0.0, nullptr}, true, poses, points, cam, pt, pixels, K, fixed, max_steps);
 }
 
 void bundle_adjust_pcg_inplace(Tensor& poses, Tensor& points, const Tensor& cam, const Tensor& pt, const Tensor& pixels,
                                at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed, int64_t max_steps,
                                int64_t max_cg_iterations, double cg_tolerance, Tensor& info) {
-    bundle_adjust_pcg_out(poses, points, cam, pt, pixels, K, fixed, max_steps, max_cg_iterations, cg_tolerance, info, poses,
-                          points);
+    bundle_run({true, max_cg_iterations, cg_tolerance, nullptr}, poses, points, cam, pt, pixels, K, fixed, max_steps, info, poses,
+               points);
 }
 
-std::tuple<Tensor, Tensor, Tensor> bundle_adjust_pcg(const Tensor& poses, const Tensor& points, const Tensor& cam,
-                                                     const Tensor& pt, const Tensor& pixels, at::ArrayRef<double> K,
-                                                     at::ArrayRef<int64_t> fixed, int64_t max_steps, int64_t max_cg_iterations,
-                                                     double cg_tolerance) {
-    bundle_pcg_check(poses, points, cam, pt, pixels, K, fixed, max_steps, max_cg_iterations, cg_tolerance);
-    Tensor poses_out = at::empty_like(poses);
-    Tensor points_out = at::empty_like(points);
-    Tensor info = at::empty({kBundlePcgInfoWords}, like(poses, at::kLong));
-    bundle_adjust_pcg_out(poses_out, points_out, cam, pt, pixels, K, fixed, max_steps, max_cg_iterations, cg_tolerance, info,
-                          poses, points);
-    return {poses_out, points_out, info};
+BundleResult bundle_adjust_pcg(const Tensor& poses, const Tensor& points, const Tensor& cam, const Tensor& pt,
+                               const Tensor& pixels, at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed, int64_t max_steps,
+                               int64_t max_cg_iterations, double cg_tolerance) {
+    return bundle_new({true, max_cg_iterations, cg_tolerance, nullptr}, false, poses, points, cam, pt, pixels, K, fixed, max_steps);
 }
 
-std::tuple<Tensor, Tensor, Tensor> bundle_adjust_pcg_meta(const Tensor& poses, const Tensor& points, const Tensor& cam,
-                                                          const Tensor& pt, const Tensor& pixels, at::ArrayRef<double> K,
-                                                          at::ArrayRef<int64_t> fixed, int64_t max_steps,
-                                                          int64_t max_cg_iterations, double cg_tolerance) {
-    bundle_pcg_check(poses, points, cam, pt, pixels, K, fixed, max_steps, max_cg_iterations, cg_tolerance);
-    return {at::empty_like(poses), at::empty_like(points),
-            at::empty_symint({c10::SymInt(kBundlePcgInfoWords)}, like(poses, at::kLong))};
-}
-
-// both adjusters with a robust loss (csrc/sfm_loss.h): the schemas above plus loss (SFM_BUNDLE_LOSS_*) and loss_scale in
-// pixels.  New ops, so that no existing schema changes.
-sfm_bundle_options bundle_options(int64_t loss, double loss_scale) {
-    TORCH_CHECK(loss >= SFM_BUNDLE_LOSS_SQUARED && loss <= SFM_BUNDLE_LOSS_CAUCHY, "sfm_hip: loss must be 0 (squared), 1 (huber) or 2 (cauchy)");
-    TORCH_CHECK(loss_scale > 0.0 && std::isfinite(loss_scale), "sfm_hip: loss_scale must be finite and positive");
-    return sfm_bundle_options{(int32_t)loss, 0, loss_scale};
+BundleResult bundle_adjust_pcg_meta(const Tensor& poses, const Tensor& points, const Tensor& cam, const Tensor& pt,
+                                    const Tensor& pixels, at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed, int64_t max_steps,
+                                    int64_t max_cg_iterations, double cg_tolerance) {
+    return bundle_new({true, max_cg_iterations, cg_tolerance, nullptr}, true, poses, points, cam, pt, pixels, K, fixed, max_steps);
 }
 
 void bundle_adjust_robust_inplace(Tensor& poses, Tensor& points, const Tensor& cam, const Tensor& pt, const Tensor& pixels,
                                   at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed, int64_t max_steps, int64_t loss,
                                   double loss_scale, Tensor& info) {
     const sfm_bundle_options options = bundle_options(loss, loss_scale);
-    bundle_adjust_out(poses, points, cam, pt, pixels, K, fixed, max_steps, info, poses, points, &options);
+    bundle_run({false, 0, 0.0, &options}, poses, points, cam, pt, pixels, K, fixed, max_steps, info, poses, points);
 }
 
-std::tuple<Tensor, Tensor, Tensor> bundle_adjust_robust(const Tensor& poses, const Tensor& points, const Tensor& cam,
-                                                        const Tensor& pt, const Tensor& pixels, at::ArrayRef<double> K,
-                                                        at::ArrayRef<int64_t> fixed, int64_t max_steps, int64_t loss,
-                                                        double loss_scale) {
+BundleResult bundle_adjust_robust(const Tensor& poses, const Tensor& points, const Tensor& cam, const Tensor& pt,
+                                  const Tensor& pixels, at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed, int64_t max_steps,
+                                  int64_t loss, double loss_scale) {
     const sfm_bundle_options options = bundle_options(loss, loss_scale);
-    bundle_check(poses, points, cam, pt, pixels, K, fixed, max_steps);
-    Tensor poses_out = at::empty_like(poses);
-    Tensor points_out = at::empty_like(points);
-    Tensor info = at::empty({kBundleInfoWords}, like(poses, at::kLong));
-    bundle_adjust_out(poses_out, points_out, cam, pt, pixels, K, fixed, max_steps, info, poses, points, &options);
-    return {poses_out, points_out, info};
+    return bundle_new({false, 0, 0.0, &options}, false, poses, points, cam, pt, pixels, K, fixed, max_steps);
 }
 
-std::tuple<Tensor, Tensor, Tensor> bundle_adjust_robust_meta(const Tensor& poses, const Tensor& points, const Tensor& cam,
-                                                             const Tensor& pt, const Tensor& pixels, at::ArrayRef<double> K,
-                                                             at::ArrayRef<int64_t> fixed, int64_t max_steps, int64_t loss,
-                                                             double loss_scale) {
-    bundle_options(loss, loss_scale);
-    return bundle_adjust_meta(poses, points, cam, pt, pixels, K, fixed, max_steps);
+BundleResult bundle_adjust_robust_meta(const Tensor& poses, const Tensor& points, const Tensor& cam, const Tensor& pt,
+                                       const Tensor& pixels, at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed,
+                                       int64_t max_steps, int64_t loss, double loss_scale) {
+    const sfm_bundle_options options = bundle_options(loss, loss_scale);
+    return bundle_new({false, 0, 0.0, &options}, true, poses, points, cam, pt, pixels, K, fixed, max_steps);
 }
 
 void bundle_adjust_pcg_robust_inplace(Tensor& poses, Tensor& points, const Tensor& cam, const Tensor& pt, const Tensor& pixels,
@@ -978,32 +936,24 @@ void bundle_adjust_pcg_robust_inplace(Tensor& poses, Tensor& points, const Tenso
                                       int64_t max_cg_iterations, double cg_tolerance, int64_t loss, double loss_scale,
                                       Tensor& info) {
     const sfm_bundle_options options = bundle_options(loss, loss_scale);
-    bundle_adjust_pcg_out(poses, points, cam, pt, pixels, K, fixed, max_steps, max_cg_iterations, cg_tolerance, info, poses,
-                          points, &options);
+    bundle_run({true, max_cg_iterations, cg_tolerance, &options}, poses, points, cam, pt, pixels, K, fixed, max_steps, info, poses,
+               points);
 }
 
-std::tuple<Tensor, Tensor, Tensor> bundle_adjust_pcg_robust(const Tensor& poses, const Tensor& points, const Tensor& cam,
-                                                            const Tensor& pt, const Tensor& pixels, at::ArrayRef<double> K,
-                                                            at::ArrayRef<int64_t> fixed, int64_t max_steps,
-                                                            int64_t max_cg_iterations, double cg_tolerance, int64_t loss,
-                                                            double loss_scale) {
+BundleResult bundle_adjust_pcg_robust(const Tensor& poses, const Tensor& points, const Tensor& cam, const Tensor& pt,
+                                      const Tensor& pixels, at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed,
+                                      int64_t max_steps, int64_t max_cg_iterations, double cg_tolerance, int64_t loss,
+                                      double loss_scale) {
     const sfm_bundle_options options = bundle_options(loss, loss_scale);
-    bundle_pcg_check(poses, points, cam, pt, pixels, K, fixed, max_steps, max_cg_iterations, cg_tolerance);
-    Tensor poses_out = at::empty_like(poses);
-    Tensor points_out = at::empty_like(points);
-    Tensor info = at::empty({kBundlePcgInfoWords}, like(poses, at::kLong));
-    bundle_adjust_pcg_out(poses_out, points_out, cam, pt, pixels, K, fixed, max_steps, max_cg_iterations, cg_tolerance, info,
-                          poses, points, &options);
-    return {poses_out, points_out, info};
+    return bundle_new({true, max_cg_iterations, cg_tolerance, &options}, false, poses, points, cam, pt, pixels, K, fixed, max_steps);
 }
 
-std::tuple<Tensor, Tensor, Tensor> bundle_adjust_pcg_robust_meta(const Tensor& poses, const Tensor& points, const Tensor& cam,
-                                                                 const Tensor& pt, const Tensor& pixels, at::ArrayRef<double> K,
-                                                                 at::ArrayRef<int64_t> fixed, int64_t max_steps,
-                                                                 int64_t max_cg_iterations, double cg_tolerance, int64_t loss,
-                                                                 double loss_scale) {
-    bundle_options(loss, loss_scale);
-    return bundle_adjust_pcg_meta(poses, points, cam, pt, pixels, K, fixed, max_steps, max_cg_iterations, cg_tolerance);
+BundleResult bundle_adjust_pcg_robust_meta(const Tensor& poses, const Tensor& points, const Tensor& cam, const Tensor& pt,
+                                           const Tensor& pixels, at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed,
+                                           int64_t max_steps, int64_t max_cg_iterations, double cg_tolerance, int64_t loss,
+                                           double loss_scale) {
+    const sfm_bundle_options options = bundle_options(loss, loss_scale);
+    return bundle_new({true, max_cg_iterations, cg_tolerance, &options}, true, poses, points, cam, pt, pixels, K, fixed, max_steps);
 }
 
 // triangulation of multi-view tracks (sfm_tracks.hip): poses [C, 12], camera / point indices int32 [M], pixels [M, 2],
@@ -1152,35 +1102,43 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> build_tracks_
             at::empty_symint({c10::SymInt(kBuildInfoWords)}, like(image_offset, at::kLong))};
 }
 
+// What the solvers over a view graph check alike; `op` names the solver in the refusal of the sizes
+void graph_solver_check(const char* op, const Tensor& pairs, const Tensor& weights, int64_t cameras, int64_t root, int64_t loss,
+                        double loss_scale, int64_t max_steps, int64_t max_cg_iterations, double cg_tolerance,
+                        double step_tolerance) {
+    TORCH_CHECK(pairs.dim() == 2 && pairs.size(1) == 2, "sfm_hip: pairs must be [Q, 2]");
+    TORCH_CHECK(weights.dim() == 1 && weights.size(0) == pairs.size(0), "sfm_hip: weights must be [Q]");
+    TORCH_CHECK(cameras >= 1 && cameras <= 0x7FFFFFFF && pairs.size(0) < ((int64_t)1 << 30), "sfm_hip: ", op,
+                ": cameras must be in [1, 2^31) and edges below 2^30");
+    TORCH_CHECK(root >= 0 && root < cameras, "sfm_hip: root must be a camera index");
+    loss_check(loss, loss_scale);
+    TORCH_CHECK(max_steps >= 0 && max_steps <= 0x7FFFFFFF, "sfm_hip: max_steps must be in [0, 2^31)");
+    TORCH_CHECK(max_cg_iterations >= 1 && max_cg_iterations <= 0x7FFFFFFF, "sfm_hip: max_cg_iterations must be in [1, 2^31)");
+    TORCH_CHECK(cg_tolerance > 0.0 && cg_tolerance < 1.0, "sfm_hip: cg_tolerance must be in (0, 1)");
+    TORCH_CHECK(step_tolerance > 0.0 && std::isfinite(step_tolerance), "sfm_hip: step_tolerance must be finite and positive");
+}
+
+// A table of rotations: [rows, 9] or [rows, 3, 3]; `rows_text` is how the message writes the row count
+void rotation_table_check(const Tensor& t, int64_t rows, const char* name, const char* rows_text) {
+    TORCH_CHECK((t.dim() == 2 && t.size(0) == rows && t.size(1) == 9) ||
+                    (t.dim() == 3 && t.size(0) == rows && t.size(1) == 3 && t.size(2) == 3),
+                "sfm_hip: ", name, " must be [", rows_text, ", 9] or [", rows_text, ", 3, 3]");
+}
+
 // rotation averaging over a view graph (sfm_rotation_averaging.hip): pairs int32 [Q, 2], relative f64 [Q, 9] or [Q, 3, 3],
 // weights f64 [Q], `cameras` = C, the root, initial f64 [C, 9] or [C, 3, 3] (given: the start; None: the spanning tree), the
 // loss (SFM_BUNDLE_LOSS_*) with its scale in radians and the limits -> rotations f64 [C, 3, 3], registered uint8 [C],
-// level int32 [C] (-1: unregistered), residual f64 [Q] (radians), info int64 [5] viewing the sfm_rotavg_info record.  The call synchronises the stream (the host
-// reads the stop flags).
+// level int32 [C] (-1: unregistered), residual f64 [Q] (radians), info int64 [5] viewing the sfm_rotavg_info record.  The call
+// synchronises the stream (the host reads the stop flags).
 constexpr int64_t kRotavgInfoWords = sizeof(sfm_rotavg_info) / 8;
 
 void rotavg_check(const Tensor& pairs, const Tensor& relative, const Tensor& weights, int64_t cameras, int64_t root,
                   const std::optional<Tensor>& initial, int64_t loss, double loss_scale, int64_t max_steps,
                   int64_t max_cg_iterations, double cg_tolerance, double step_tolerance) {
-    TORCH_CHECK(pairs.dim() == 2 && pairs.size(1) == 2, "sfm_hip: pairs must be [Q, 2]");
-    const int64_t Q = pairs.size(0);
-    TORCH_CHECK((relative.dim() == 2 && relative.size(0) == Q && relative.size(1) == 9) ||
-                    (relative.dim() == 3 && relative.size(0) == Q && relative.size(1) == 3 && relative.size(2) == 3),
-                "sfm_hip: relative must be [Q, 9] or [Q, 3, 3]");
-    TORCH_CHECK(weights.dim() == 1 && weights.size(0) == Q, "sfm_hip: weights must be [Q]");
-    TORCH_CHECK(cameras >= 1 && cameras <= 0x7FFFFFFF && Q < ((int64_t)1 << 30),
-                "sfm_hip: average_rotations: cameras must be in [1, 2^31) and edges below 2^30");
-    TORCH_CHECK(root >= 0 && root < cameras, "sfm_hip: root must be a camera index");
-    if (initial.has_value() && initial->defined())
-        TORCH_CHECK((initial->dim() == 2 && initial->size(0) == cameras && initial->size(1) == 9) ||
-                        (initial->dim() == 3 && initial->size(0) == cameras && initial->size(1) == 3 && initial->size(2) == 3),
-                    "sfm_hip: initial must be [cameras, 9] or [cameras, 3, 3]");
-    TORCH_CHECK(loss >= SFM_BUNDLE_LOSS_SQUARED && loss <= SFM_BUNDLE_LOSS_CAUCHY, "sfm_hip: loss must be 0 (squared), 1 (huber) or 2 (cauchy)");
-    TORCH_CHECK(loss_scale > 0.0 && std::isfinite(loss_scale), "sfm_hip: loss_scale must be finite and positive");
-    TORCH_CHECK(max_steps >= 0 && max_steps <= 0x7FFFFFFF, "sfm_hip: max_steps must be in [0, 2^31)");
-    TORCH_CHECK(max_cg_iterations >= 1 && max_cg_iterations <= 0x7FFFFFFF, "sfm_hip: max_cg_iterations must be in [1, 2^31)");
-    TORCH_CHECK(cg_tolerance > 0.0 && cg_tolerance < 1.0, "sfm_hip: cg_tolerance must be in (0, 1)");
-    TORCH_CHECK(step_tolerance > 0.0 && std::isfinite(step_tolerance), "sfm_hip: step_tolerance must be finite and positive");
+    graph_solver_check("average_rotations", pairs, weights, cameras, root, loss, loss_scale, max_steps, max_cg_iterations,
+                       cg_tolerance, step_tolerance);
+    rotation_table_check(relative, pairs.size(0), "relative", "Q");
+    if (initial.has_value() && initial->defined()) rotation_table_check(*initial, cameras, "initial", "cameras");
 }
 
 std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> average_rotations(const Tensor& pairs, const Tensor& relative, const Tensor& weights,
@@ -1240,26 +1198,14 @@ void transavg_check(const Tensor& pairs, const Tensor& directions, const std::op
                     int64_t cameras, int64_t root, const std::optional<Tensor>& initial, int64_t loss, double loss_scale,
                     int64_t warmup_steps, int64_t max_steps, int64_t max_cg_iterations, double cg_tolerance,
                     double step_tolerance) {
-    TORCH_CHECK(pairs.dim() == 2 && pairs.size(1) == 2, "sfm_hip: pairs must be [Q, 2]");
-    const int64_t Q = pairs.size(0);
-    TORCH_CHECK(directions.dim() == 2 && directions.size(0) == Q && directions.size(1) == 3, "sfm_hip: directions must be [Q, 3]");
-    TORCH_CHECK(weights.dim() == 1 && weights.size(0) == Q, "sfm_hip: weights must be [Q]");
-    TORCH_CHECK(cameras >= 1 && cameras <= 0x7FFFFFFF && Q < ((int64_t)1 << 30),
-                "sfm_hip: average_translations: cameras must be in [1, 2^31) and edges below 2^30");
-    TORCH_CHECK(root >= 0 && root < cameras, "sfm_hip: root must be a camera index");
-    if (rotations.has_value() && rotations->defined())
-        TORCH_CHECK((rotations->dim() == 2 && rotations->size(0) == cameras && rotations->size(1) == 9) ||
-                        (rotations->dim() == 3 && rotations->size(0) == cameras && rotations->size(1) == 3 && rotations->size(2) == 3),
-                    "sfm_hip: rotations must be [cameras, 9] or [cameras, 3, 3]");
+    graph_solver_check("average_translations", pairs, weights, cameras, root, loss, loss_scale, max_steps, max_cg_iterations,
+                       cg_tolerance, step_tolerance);
+    TORCH_CHECK(directions.dim() == 2 && directions.size(0) == pairs.size(0) && directions.size(1) == 3,
+                "sfm_hip: directions must be [Q, 3]");
+    if (rotations.has_value() && rotations->defined()) rotation_table_check(*rotations, cameras, "rotations", "cameras");
     if (initial.has_value() && initial->defined())
         TORCH_CHECK(initial->dim() == 2 && initial->size(0) == cameras && initial->size(1) == 3, "sfm_hip: initial must be [cameras, 3]");
-    TORCH_CHECK(loss >= SFM_BUNDLE_LOSS_SQUARED && loss <= SFM_BUNDLE_LOSS_CAUCHY, "sfm_hip: loss must be 0 (squared), 1 (huber) or 2 (cauchy)");
-    TORCH_CHECK(loss_scale > 0.0 && std::isfinite(loss_scale), "sfm_hip: loss_scale must be finite and positive");
     TORCH_CHECK(warmup_steps >= 0 && warmup_steps <= 0x7FFFFFFF, "sfm_hip: warmup_steps must be in [0, 2^31)");
-    TORCH_CHECK(max_steps >= 0 && max_steps <= 0x7FFFFFFF, "sfm_hip: max_steps must be in [0, 2^31)");
-    TORCH_CHECK(max_cg_iterations >= 1 && max_cg_iterations <= 0x7FFFFFFF, "sfm_hip: max_cg_iterations must be in [1, 2^31)");
-    TORCH_CHECK(cg_tolerance > 0.0 && cg_tolerance < 1.0, "sfm_hip: cg_tolerance must be in (0, 1)");
-    TORCH_CHECK(step_tolerance > 0.0 && std::isfinite(step_tolerance), "sfm_hip: step_tolerance must be finite and positive");
 }
 
 using TransavgResult = std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor>;

@@ -29,18 +29,17 @@ namespace {
 using graphcg::is_free;
 using graphcg::kOneGroup;
 using graphcg::kThreads;
-using graphcg::sizes_ok;
 using graphcg::State;
-using graphcg::sum_cost;
 using graphcg::Ws;
 using sfm::block_sum;
-using sfmhost::fail;
 
 static_assert(sizeof(sfm_transavg_info) == 40, "sfm_transavg_info layout is part of the ABI");
 static_assert(sizeof(sfm_transavg_options) == 48, "sfm_transavg_options layout is part of the ABI");
 static_assert(SFM_TRANSAVG_CONVERGED == graphcg::kConverged && SFM_TRANSAVG_MAX_STEPS == graphcg::kMaxSteps &&
                   SFM_TRANSAVG_CG_FAILED == graphcg::kCgFailed && SFM_TRANSAVG_BAD_INDEX == graphcg::kBadIndex,
               "the shared kernels write these statuses");
+static_assert(SFM_TRANSAVG_INIT_TREE == graphcg::kInitTree && SFM_TRANSAVG_INIT_GIVEN == graphcg::kInitGiven,
+              "graphcg::check_entry tests these");
 
 struct Args {
     int C, Q, root;
@@ -59,7 +58,9 @@ struct Args {
     }
 };
 
+// The bytes of the workspace, carved from `base` (0: the size only); -1 for sizes the call refuses
 int64_t carve(uintptr_t base, int64_t C, int64_t Q, Ws* w, double** v) {
+    if (!graphcg::sizes_ok(C, Q)) return -1;
     sfmhost::Carver k{base, 0};
     graphcg::carve(k, C, Q, w);
     *v = k.take<double>(3 * Q);
@@ -170,27 +171,17 @@ __global__ __launch_bounds__(kThreads) void transavg_step_kernel(Args a, Ws w) {
     graphcg::record_step(w, x);
 }
 
-// One workgroup, after the final edge pass: info; after a bad index the filler of every output.
+// One workgroup, after the final edge pass: after a bad index the filler of the positions, residuals and scales;
+// graphcg::finish_info has the rest of the filler and info.
 __global__ __launch_bounds__(kOneGroup) void transavg_finish_kernel(Args a, int blocks, Ws w, sfm_transavg_info* __restrict__ info) {
-    __shared__ double part[kOneGroup / kWave];
-    __shared__ double total[1];
-    const State* st = w.st;
-    if (st->bad) {
+    if (w.st->bad) {
         for (int64_t i = threadIdx.x; i < 3 * (int64_t)a.C; i += kOneGroup) a.c[i] = (double)NAN;
-        for (int64_t i = threadIdx.x; i < a.C; i += kOneGroup) a.registered[i] = 0;
-        for (int64_t i = threadIdx.x; a.level && i < a.C; i += kOneGroup) a.level[i] = -1;
         for (int64_t i = threadIdx.x; i < a.Q; i += kOneGroup) {
             a.residual[i] = (double)NAN;
             a.scale[i] = (double)NAN;
         }
-        if (threadIdx.x == 0)
-            *info = sfm_transavg_info{(double)NAN, (double)NAN, 0, SFM_TRANSAVG_BAD_INDEX, 0, 0, 0, 0};
-        return;
     }
-    const double cost = sum_cost<kOneGroup>(w, blocks, part, total);
-    if (threadIdx.x != 0) return;
-    *info = sfm_transavg_info{st->have_initial ? st->initial_cost : cost, cost, st->steps, st->status, st->cg_total, st->cg_max,
-                              st->registered, st->last_round};
+    graphcg::finish_info(a, blocks, w, info);
 }
 
 // The launches that are translation averaging's own (graphcg::run has the rest)
@@ -221,7 +212,6 @@ struct Driver {
 extern "C" {
 
 int64_t sfm_average_translations_workspace_bytes(int64_t cameras, int64_t edges) {
-    if (!sizes_ok(cameras, edges)) return -1;
     Ws w;
     double* v;
     return carve(0, cameras, edges, &w, &v);
@@ -232,37 +222,18 @@ int sfm_average_translations(int64_t cameras, int64_t edges, const int32_t* pair
                              const sfm_transavg_options* options, double* positions, uint8_t* registered, int32_t* level,
                              double* residual, double* scale, sfm_transavg_info* info, void* workspace,
                              int64_t workspace_bytes, void* stream) {
-    // every check before the first launch: a refused call has enqueued nothing
-    if (!sizes_ok(cameras, edges))
-        return fail(SFM_EINVAL, "sfm_average_translations: cameras must be in [1, 2^31) and edges in [0, 2^30)");
-    if (root < 0 || root >= cameras) return fail(SFM_EINVAL, "sfm_average_translations: root must be a camera index");
-    if (!options) return fail(SFM_EINVAL, "sfm_average_translations: null pointer (options)");
-    const sfm_transavg_options o = *options;
-    if (o.loss < SFM_BUNDLE_LOSS_SQUARED || o.loss > SFM_BUNDLE_LOSS_CAUCHY)
-        return fail(SFM_EINVAL, "sfm_average_translations: loss must be in 0..2");
-    if (o.init != SFM_TRANSAVG_INIT_TREE && o.init != SFM_TRANSAVG_INIT_GIVEN)
-        return fail(SFM_EINVAL, "sfm_average_translations: init must be SFM_TRANSAVG_INIT_TREE or SFM_TRANSAVG_INIT_GIVEN");
-    if (o.max_steps < 0) return fail(SFM_EINVAL, "sfm_average_translations: max_steps must be at least 0");
-    if (o.max_cg_iterations < 1) return fail(SFM_EINVAL, "sfm_average_translations: max_cg_iterations must be at least 1");
-    if (o.warmup_steps < 0) return fail(SFM_EINVAL, "sfm_average_translations: warmup_steps must be at least 0");
-    if (o.reserved != 0) return fail(SFM_EINVAL, "sfm_average_translations: reserved must be 0");
-    if (!(o.loss_scale > 0.0) || !isfinite(o.loss_scale))
-        return fail(SFM_EINVAL, "sfm_average_translations: loss_scale must be finite and positive");
-    if (!(o.cg_tolerance > 0.0 && o.cg_tolerance < 1.0))
-        return fail(SFM_EINVAL, "sfm_average_translations: cg_tolerance must be finite and in (0, 1)");
-    if (!(o.step_tolerance > 0.0) || !isfinite(o.step_tolerance))
-        return fail(SFM_EINVAL, "sfm_average_translations: step_tolerance must be finite and positive");
+    const sfm_transavg_options o = options ? *options : sfm_transavg_options{};
+    const char* own = o.warmup_steps < 0 ? "warmup_steps must be at least 0" : o.reserved != 0 ? "reserved must be 0" : nullptr;
     const bool given = o.init == SFM_TRANSAVG_INIT_GIVEN;
-    if (!positions || !registered || !info || !workspace || (given && !initial) ||
-        (edges > 0 && (!pairs || !directions || !weights || !residual || !scale)))
-        return fail(SFM_EINVAL, "sfm_average_translations: null pointer");
+    const bool pointers = positions && registered && info && workspace && (!given || initial) &&
+                          (edges == 0 || (pairs && directions && weights && residual && scale));
     Ws w;
     double* v;
-    if (workspace_bytes < carve((uintptr_t)workspace, cameras, edges, &w, &v))
-        return fail(SFM_EINVAL, "sfm_average_translations: workspace too small");
-    if (((uintptr_t)workspace & 15) != 0) return fail(SFM_EINVAL, "sfm_average_translations: workspace must be 16-byte aligned");
-    int32_t* flags = graphcg::pinned_flags();
-    if (!flags) return fail(SFM_EHIP, "sfm_average_translations: no pinned host memory for the flags");
+    int32_t* flags;
+    const int rc = graphcg::check_entry("sfm_average_translations", "TRANSAVG", cameras, edges, root, options != nullptr, o, own,
+                                        pointers, workspace, workspace_bytes,
+                                        carve((uintptr_t)workspace, cameras, edges, &w, &v), &flags);
+    if (rc != SFM_OK) return rc;
     const sfmloss::Loss loss{o.loss, 0, o.loss_scale, o.loss_scale * o.loss_scale};
     const Args a{(int)cameras, (int)edges, (int)root, given, pairs, directions, rotations, weights, initial, positions, registered,
                  level, residual, scale, v};

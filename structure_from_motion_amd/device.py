@@ -401,11 +401,17 @@ def refine_inliers(corr, E, mask, err, thr: float, aggregation: int, iterations:
     return E_out, mask_out, info
 
 
+def _read_records(info: torch.Tensor, doubles: int, ints: int) -> List[tuple]:
+    """Host copy of info records held as int64 words (one record, or [B, words]): ``doubles`` leading float64 fields, then
+    ``ints`` int32 fields -> one tuple of Python numbers per record (synchronises)."""
+    raw = np.ascontiguousarray(info.cpu().numpy()).reshape(-1, info.shape[-1])
+    return [tuple(float(v) for v in row[:doubles].view(np.float64)) + tuple(int(v) for v in row[doubles:].view(np.int32)[:ints])
+            for row in raw]
+
+
 def read_refine_info(info: torch.Tensor):
     """Host copy of sfm_refine_info records -> list of (error, count, accepted) (synchronises)."""
-    raw = info.cpu().numpy()
-    return [(float(raw[i, 0:1].view(np.float64)[0]), int(raw[i, 1] & 0xFFFFFFFF), int(raw[i, 1] >> 32))
-            for i in range(raw.shape[0])]
+    return _read_records(info, 1, 2)
 
 
 def five_point_fit(corr: torch.Tensor, S: torch.Tensor, E=None, flags=None, philox=None):
@@ -794,10 +800,7 @@ class PnPRefineInfo:
 
 def read_pnp_refine_info(info: torch.Tensor) -> List[PnPRefineInfo]:
     """Host copy of sfm_pnp_refine_info records (int64 [B,3]) (synchronises)."""
-    raw = info.cpu().numpy()
-    return [PnPRefineInfo(float(raw[i, 0:1].view(np.float64)[0]), int(raw[i, 1:2].view(np.int32)[0]),
-                          int(raw[i, 1:2].view(np.int32)[1]), int(raw[i, 2:3].view(np.int32)[0]))
-            for i in range(raw.shape[0])]
+    return [PnPRefineInfo(*fields) for fields in _read_records(info, 1, 3)]
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -817,6 +820,21 @@ def _bundle_loss(loss: str, loss_scale: float):
     return BUNDLE_LOSSES.index(loss), scale
 
 
+def _bundle(name: str, poses, points, camera_indices, point_indices, pixels, K, fixed, max_steps, cg, out, loss, loss_scale):
+    """The op ``name`` (its ``_robust`` form for a loss other than "squared", its ``_`` form with ``out``); ``cg`` is () or
+    (max_cg_iterations, cg_tolerance)."""
+    code, scale = _bundle_loss(loss, loss_scale)
+    op = ops.load()
+    args = (camera_indices.contiguous(), point_indices.contiguous(), pixels.contiguous(), _camera_list(K),
+            [int(c) for c in fixed], int(max_steps), *((int(cg[0]), float(cg[1])) if cg else ()))
+    if code != 0:
+        name, args = name + "_robust", args + (code, scale)
+    if out is None:
+        return getattr(op, name)(poses.contiguous(), points.contiguous(), *args)
+    getattr(op, name + "_")(out[0], out[1], *args, out[2])
+    return out
+
+
 def bundle_adjust(poses, points, camera_indices, point_indices, pixels, K, fixed=(0,), max_steps: int = 50, out=None, *,
                   loss: str = "squared", loss_scale: float = 1.0):
     """Levenberg-Marquardt over the free cameras and the points seen at least twice (``sfm_bundle_adjust``) ->
@@ -825,19 +843,8 @@ def bundle_adjust(poses, points, camera_indices, point_indices, pixels, K, fixed
     synchronisation: the whole call is enqueued at once.  ``loss`` in ``BUNDLE_LOSSES`` with ``loss_scale`` in pixels
     (DESIGN.md §6n): ``"squared"`` is the op without a loss, the others run ``bundle_adjust_robust`` and the costs in
     ``info`` are sums of rho."""
-    code, scale = _bundle_loss(loss, loss_scale)
-    op = ops.load()
-    args = (camera_indices.contiguous(), point_indices.contiguous(), pixels.contiguous(), _camera_list(K),
-            [int(c) for c in fixed], int(max_steps))
-    if code != 0:
-        if out is None:
-            return op.bundle_adjust_robust(poses.contiguous(), points.contiguous(), *args, code, scale)
-        op.bundle_adjust_robust_(out[0], out[1], *args, code, scale, out[2])
-        return out
-    if out is None:
-        return op.bundle_adjust(poses.contiguous(), points.contiguous(), *args)
-    op.bundle_adjust_(out[0], out[1], *args, out[2])
-    return out
+    return _bundle("bundle_adjust", poses, points, camera_indices, point_indices, pixels, K, fixed, max_steps, (), out, loss,
+                   loss_scale)
 
 
 @dataclass
@@ -854,10 +861,7 @@ BUNDLE_OK, BUNDLE_BAD_START, BUNDLE_BAD_INDEX = 0, 1, 2
 
 def read_bundle_info(info: torch.Tensor) -> BundleInfo:
     """Host copy of an sfm_bundle_info record (int64 [4]) (synchronises)."""
-    raw = info.cpu().numpy()
-    costs = raw[0:2].view(np.float64)
-    ints = raw[2:4].view(np.int32)
-    return BundleInfo(float(costs[0]), float(costs[1]), int(ints[0]), int(ints[1]), int(ints[2]))
+    return BundleInfo(*_read_records(info, 2, 3)[0])
 
 
 def bundle_adjust_pcg(poses, points, camera_indices, point_indices, pixels, K, fixed=(0,), max_steps: int = 50,
@@ -868,49 +872,55 @@ def bundle_adjust_pcg(poses, points, camera_indices, point_indices, pixels, K, f
     ``read_bundle_pcg_info``).  ``out`` = (poses, points, info) runs the in-place op on those tensors instead.  The call
     synchronises the current stream: the host reads the stop flags between LM steps and CG chunks.  ``loss`` and
     ``loss_scale`` as in ``bundle_adjust`` (``bundle_adjust_pcg_robust`` for a non-squared loss)."""
-    code, scale = _bundle_loss(loss, loss_scale)
-    op = ops.load()
-    args = (camera_indices.contiguous(), point_indices.contiguous(), pixels.contiguous(), _camera_list(K),
-            [int(c) for c in fixed], int(max_steps), int(max_cg_iterations), float(cg_tolerance))
-    if code != 0:
-        if out is None:
-            return op.bundle_adjust_pcg_robust(poses.contiguous(), points.contiguous(), *args, code, scale)
-        op.bundle_adjust_pcg_robust_(out[0], out[1], *args, code, scale, out[2])
-        return out
-    if out is None:
-        return op.bundle_adjust_pcg(poses.contiguous(), points.contiguous(), *args)
-    op.bundle_adjust_pcg_(out[0], out[1], *args, out[2])
-    return out
+    return _bundle("bundle_adjust_pcg", poses, points, camera_indices, point_indices, pixels, K, fixed, max_steps,
+                   (max_cg_iterations, cg_tolerance), out, loss, loss_scale)
 
 
 @dataclass
-class BundlePcgInfo:
-    initial_cost: float   # cost of the input (NaN when an index is out of range)
-    final_cost: float     # cost of the last accepted trial (initial_cost when none was accepted)
-    steps: int            # Levenberg-Marquardt trial steps
-    accepted: int         # accepted steps
-    status: int           # BUNDLE_OK, BUNDLE_BAD_START or BUNDLE_BAD_INDEX
+class BundlePcgInfo(BundleInfo):   # sfm_bundle_pcg_info: the fields of sfm_bundle_info, then
     cg_iterations: int    # conjugate-gradient iterations over all trial steps
     cg_max: int           # the most conjugate-gradient iterations of one trial step
 
 
 def read_bundle_pcg_info(info: torch.Tensor) -> BundlePcgInfo:
     """Host copy of an sfm_bundle_pcg_info record (int64 [5]) (synchronises)."""
-    raw = info.cpu().numpy()
-    costs = raw[0:2].view(np.float64)
-    ints = raw[2:5].view(np.int32)
-    return BundlePcgInfo(float(costs[0]), float(costs[1]), int(ints[0]), int(ints[1]), int(ints[2]), int(ints[3]),
-                         int(ints[4]))
+    return BundlePcgInfo(*_read_records(info, 2, 5)[0])
+
+
+# ------------------------------------------------------------------------------------------------------
+# the solvers over a view graph: one set of statuses and one info record (sfm_rotavg_info and sfm_transavg_info have one
+# layout) under the names of both
+# ------------------------------------------------------------------------------------------------------
+GRAPH_STATUS = ROTAVG_STATUS = TRANSAVG_STATUS = _native.GRAPH_STATUS   # the index is the SFM_ROTAVG_* / SFM_TRANSAVG_* code
+ROTAVG_CONVERGED, ROTAVG_MAX_STEPS, ROTAVG_CG_FAILED, ROTAVG_BAD_INDEX = 0, 1, 2, 3
+TRANSAVG_CONVERGED, TRANSAVG_MAX_STEPS, TRANSAVG_CG_FAILED, TRANSAVG_BAD_INDEX = 0, 1, 2, 3
+
+
+@dataclass
+class GraphInfo:
+    initial_cost: float   # sum of w rho(e) over the used edges at the first linearisation (NaN for *_BAD_INDEX)
+    final_cost: float     # ... at the result
+    steps: int            # completed steps
+    status: int           # ROTAVG_* / TRANSAVG_*
+    cg_iterations: int    # conjugate-gradient iterations over all steps
+    cg_max: int           # the most conjugate-gradient iterations of one step
+    registered: int       # cameras with a level, the root included
+    rounds: int           # the largest level
+
+
+def read_graph_info(info: torch.Tensor) -> GraphInfo:
+    """Host copy of an sfm_rotavg_info or sfm_transavg_info record (int64 [5]) (synchronises)."""
+    return GraphInfo(*_read_records(info, 2, 6)[0])
+
+
+RotavgInfo = TransavgInfo = GraphInfo
+read_rotavg_info = read_transavg_info = read_graph_info
 
 
 # ------------------------------------------------------------------------------------------------------
 # rotation averaging over a view graph (csrc/sfm_rotation_averaging.hip): pairs int32 [Q,2], relative rotations [Q,3,3]
 # (R_q ~ R_j R_i^T), weights [Q]
 # ------------------------------------------------------------------------------------------------------
-ROTAVG_STATUS = _native.ROTAVG_STATUS   # "converged", "max_steps", "cg_failed", "bad_index": the index is the SFM_ROTAVG_* code
-ROTAVG_CONVERGED, ROTAVG_MAX_STEPS, ROTAVG_CG_FAILED, ROTAVG_BAD_INDEX = 0, 1, 2, 3
-
-
 def average_rotations(pairs, relative, weights, cameras: int, root: int = 0, initial=None, loss: str = "squared",
                       loss_scale: float = 1.0, max_steps: int = 50, max_cg_iterations: int = 500, cg_tolerance: float = 1e-6,
                       step_tolerance: float = 1e-8):
@@ -926,34 +936,10 @@ def average_rotations(pairs, relative, weights, cameras: int, root: int = 0, ini
                                 int(max_cg_iterations), float(cg_tolerance), float(step_tolerance))
 
 
-@dataclass
-class RotavgInfo:
-    initial_cost: float   # sum of w rho(e) over the used edges at the initialisation (NaN for ROTAVG_BAD_INDEX)
-    final_cost: float     # ... at the result
-    steps: int            # completed steps
-    status: int           # ROTAVG_*
-    cg_iterations: int    # conjugate-gradient iterations over all steps
-    cg_max: int           # the most conjugate-gradient iterations of one step
-    registered: int       # cameras with a level, the root included
-    rounds: int           # the largest level
-
-
-def read_rotavg_info(info: torch.Tensor) -> RotavgInfo:
-    """Host copy of an sfm_rotavg_info record (int64 [5]) (synchronises)."""
-    raw = info.cpu().numpy()
-    costs = raw[0:2].view(np.float64)
-    ints = raw[2:5].view(np.int32)
-    return RotavgInfo(float(costs[0]), float(costs[1]), *(int(v) for v in ints))
-
-
 # ------------------------------------------------------------------------------------------------------
 # translation averaging over a view graph (csrc/sfm_translation_averaging.hip): pairs int32 [Q,2], directions [Q,3] (the world
 # directions v_q ~ c_j - c_i, or with ``rotations`` the pairs' t_q), weights [Q]
 # ------------------------------------------------------------------------------------------------------
-TRANSAVG_STATUS = _native.TRANSAVG_STATUS   # "converged", "max_steps", "cg_failed", "bad_index": the index is the SFM_TRANSAVG_* code
-TRANSAVG_CONVERGED, TRANSAVG_MAX_STEPS, TRANSAVG_CG_FAILED, TRANSAVG_BAD_INDEX = 0, 1, 2, 3
-
-
 def average_translations(pairs, directions, weights, cameras: int, root: int = 0, rotations=None, initial=None,
                          loss: str = "squared", loss_scale: float = 1.0, warmup_steps: int = 10, max_steps: int = 500,
                          max_cg_iterations: int = 500, cg_tolerance: float = 1e-6, step_tolerance: float = 1e-8):
@@ -970,26 +956,6 @@ def average_translations(pairs, directions, weights, cameras: int, root: int = 0
                                    int(root), None if initial is None else initial.contiguous(), code, scale,
                                    int(warmup_steps), int(max_steps), int(max_cg_iterations), float(cg_tolerance),
                                    float(step_tolerance))
-
-
-@dataclass
-class TransavgInfo:
-    initial_cost: float   # sum of w rho(e) over the used edges at the first linearisation (NaN for TRANSAVG_BAD_INDEX)
-    final_cost: float     # ... at the result
-    steps: int            # completed steps
-    status: int           # TRANSAVG_*
-    cg_iterations: int    # conjugate-gradient iterations over all steps
-    cg_max: int           # the most conjugate-gradient iterations of one step
-    registered: int       # cameras with a level, the root included
-    rounds: int           # the largest level
-
-
-def read_transavg_info(info: torch.Tensor) -> TransavgInfo:
-    """Host copy of an sfm_transavg_info record (int64 [5]) (synchronises)."""
-    raw = info.cpu().numpy()
-    costs = raw[0:2].view(np.float64)
-    ints = raw[2:5].view(np.int32)
-    return TransavgInfo(float(costs[0]), float(costs[1]), *(int(v) for v in ints))
 
 
 # ------------------------------------------------------------------------------------------------------

@@ -19,9 +19,8 @@ from typing import Optional, Sequence
 import numpy as np
 import numpy.typing as npt
 
-LOSSES = ("squared", "huber", "cauchy")
-_INT32 = 2**31
-MAX_EDGES = 2**30
+from ._graph_args import LOSSES, MAX_EDGES, _checked, _positive, _root_alone, _scatter  # noqa: F401
+
 ROTATION_TOLERANCE = 1e-6   # an active edge's R_q: max |R^T R - I| and det > 0
 
 
@@ -36,22 +35,6 @@ class GlobalRotations:
     initial_cost: float        # sum of w rho(angle^2) in rad^2 at the start (NaN for "bad_index")
     final_cost: float          # ... at the result
     status: str                # "converged", "max_steps", "cg_failed" or "bad_index"
-
-
-def _integer(value, name: str, low: int, high: int = _INT32) -> int:
-    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or value < low or value >= high:
-        raise ValueError(f"{name} must be an integer in [{low}, {high}), got {value!r}")
-    return int(value)
-
-
-def _positive(value, name: str, below: float = math.inf) -> float:
-    try:
-        v = float(value)
-    except (TypeError, ValueError):
-        raise ValueError(f"{name} must be a number, got {value!r}") from None
-    if not (math.isfinite(v) and 0.0 < v < below):
-        raise ValueError(f"{name} must be finite and in (0, {below}), got {value!r}")
-    return v
 
 
 def active_edges(relative_rotations: npt.NDArray, weights: npt.NDArray) -> npt.NDArray:
@@ -78,55 +61,10 @@ def average_rotations(num_cameras: int, pairs, relative_rotations, weights=None,
     conjugate gradients (at most ``max_cg_iterations`` per step, to ``cg_tolerance`` relative residual) break down
     (``"cg_failed"``).  A call is reproducible bit for bit.  Every argument is checked before any device work
     (``ValueError``); ``Q = 0`` needs no GPU."""
-    C = _integer(num_cameras, "num_cameras", 1)
-    try:
-        pair_arr = np.asarray(pairs)
-    except (TypeError, ValueError):
-        raise ValueError("pairs must be an integer array of shape (Q, 2)") from None
-    if pair_arr.size == 0:
-        pair_arr = np.zeros((0, 2), dtype=np.int64)
-    if pair_arr.ndim != 2 or pair_arr.shape[1] != 2 or not np.issubdtype(pair_arr.dtype, np.integer):
-        raise ValueError(f"pairs must be an integer array of shape (Q, 2), got {pair_arr.dtype} {pair_arr.shape}")
-    Q = pair_arr.shape[0]
-    if Q >= MAX_EDGES:
-        raise ValueError("pairs must number fewer than 2^30")
-    if Q and (pair_arr.min() < 0 or pair_arr.max() >= C):
-        raise ValueError(f"pairs must hold camera indices in [0, {C})")
-    if np.any(pair_arr[:, 0] == pair_arr[:, 1]):
-        raise ValueError("pairs must not join a camera with itself")
-    try:
-        rel = np.asarray(relative_rotations, dtype=np.float64)
-    except (TypeError, ValueError):
-        raise ValueError("relative_rotations must be a float array of shape (Q, 3, 3)") from None
-    if rel.size == 0 and Q == 0:
-        rel = np.zeros((0, 3, 3))
-    if rel.shape != (Q, 3, 3):
-        raise ValueError(f"relative_rotations must have shape ({Q}, 3, 3), got {rel.shape}")
-    if weights is None:
-        w = np.ones(Q)
-    else:
-        try:
-            w = np.asarray(weights, dtype=np.float64)
-        except (TypeError, ValueError):
-            raise ValueError("weights must be a float array of shape (Q,)") from None
-        if w.shape != (Q,):
-            raise ValueError(f"weights must have shape ({Q},), got {w.shape}")
-    root = _integer(root, "root", 0, C)
-    if loss not in LOSSES:
-        raise ValueError(f"loss must be one of {LOSSES}, got {loss!r}")
-    scale = math.radians(_positive(loss_scale_deg, "loss_scale_deg"))
-    init = None
-    if initial_rotations is not None:
-        try:
-            init = np.asarray(initial_rotations, dtype=np.float64)
-        except (TypeError, ValueError):
-            raise ValueError("initial_rotations must be a float array of shape (C, 3, 3)") from None
-        if init.shape != (C, 3, 3):
-            raise ValueError(f"initial_rotations must have shape ({C}, 3, 3), got {init.shape}")
-    max_steps = _integer(max_steps, "max_steps", 0)
-    max_cg_iterations = _integer(max_cg_iterations, "max_cg_iterations", 1)
-    cg_tolerance = _positive(cg_tolerance, "cg_tolerance", below=1.0)
-    step_tolerance = _positive(step_tolerance, "step_tolerance")
+    C, pair_arr, rel, w, root, angle, init, limits = _checked(
+        num_cameras, pairs, (relative_rotations, "relative_rotations", (3, 3)), weights, root, loss, loss_scale_deg, math.inf,
+        (initial_rotations, "initial_rotations", (3, 3)),
+        dict(max_steps=max_steps, max_cg_iterations=max_cg_iterations, cg_tolerance=cg_tolerance, step_tolerance=step_tolerance))
     act = active_edges(rel, w)
     if act.any():
         Ra = rel[act]
@@ -135,12 +73,10 @@ def average_rotations(num_cameras: int, pairs, relative_rotations, weights=None,
             bad = np.nonzero(act)[0][int(np.argmax((np.max(np.abs(gram), axis=(1, 2)) > ROTATION_TOLERANCE) |
                                                    (np.linalg.det(Ra) <= 0)))]
             raise ValueError(f"relative_rotations[{bad}] is not a rotation (|R^T R - I| <= {ROTATION_TOLERANCE}, det > 0)")
-    if Q == 0:   # nothing to average: the root alone is registered
+    if len(pair_arr) == 0:   # nothing to average: the root alone is registered
         R = np.full((C, 3, 3), np.nan)
         R[root] = np.eye(3) if init is None else init[root]
-        registered = np.zeros(C, dtype=bool)
-        registered[root] = True
-        return GlobalRotations(R, registered, np.where(registered, 0, -1), np.zeros(0), 0, 0, 0.0, 0.0, "converged")
+        return GlobalRotations(R, *_root_alone(C, root), np.zeros(0), 0, 0, 0.0, 0.0, "converged")
     import torch
 
     from .. import device
@@ -148,8 +84,7 @@ def average_rotations(num_cameras: int, pairs, relative_rotations, weights=None,
     device.require_gpu()
     R, registered, level, residual, info = device.average_rotations(
         device.to_device(pair_arr.astype(np.int32), torch.int32), device.to_device(rel), device.to_device(w), C, root,
-        None if init is None else device.to_device(init), loss, scale, max_steps, max_cg_iterations, cg_tolerance,
-        step_tolerance)
+        None if init is None else device.to_device(init), loss, math.radians(angle), **limits)
     rec = device.read_rotavg_info(info)
     return GlobalRotations(R.cpu().numpy(), registered.cpu().numpy().astype(bool), level.cpu().numpy().astype(np.int64),
                            np.degrees(residual.cpu().numpy()),
@@ -178,9 +113,7 @@ def average_graph_rotations(graph, num_images: int, root: Optional[int] = None, 
     if root is None:
         root = int(pairs[int(np.argmax(w))].min()) if len(idx) else 0
     r = average_rotations(num_images, pairs, R, w, root=root, **options)
-    residual = np.full(len(graph.kind), np.nan)
-    residual[idx] = r.residual_deg
-    r.residual_deg = residual
+    r.residual_deg = _scatter(r.residual_deg, idx, len(graph.kind))
     return r
 
 

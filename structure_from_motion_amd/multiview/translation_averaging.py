@@ -21,8 +21,9 @@ from typing import Optional, Sequence
 import numpy as np
 import numpy.typing as npt
 
-from .rotation_averaging import (LOSSES, MAX_EDGES, GlobalRotations, _integer, _positive, graph_edges,  # noqa: F401
-                                 inconsistent_pairs)
+from . import _graph_args
+from ._graph_args import _array, _integer, _root_alone, _scatter
+from .rotation_averaging import LOSSES, MAX_EDGES, GlobalRotations, graph_edges, inconsistent_pairs  # noqa: F401
 
 UNIT_TOLERANCE = 1e-6   # an active edge's direction: | |v| - 1 |
 
@@ -41,47 +42,13 @@ class GlobalPositions:
     status: str                # "converged", "max_steps", "cg_failed" or "bad_index"
 
 
-def _array(value, name: str, shape, what: str):
-    try:
-        arr = np.asarray(value, dtype=np.float64)
-    except (TypeError, ValueError):
-        raise ValueError(f"{name} must be a float array of shape {what}") from None
-    if arr.size == 0 and 0 in shape:
-        arr = np.zeros(shape)
-    if arr.shape != shape:
-        raise ValueError(f"{name} must have shape {shape}, got {arr.shape}")
-    return arr
-
-
 def _checked(num_cameras, pairs, directions, weights, root, loss, loss_scale_deg, initial_positions, warmup_steps, max_steps,
              max_cg_iterations, cg_tolerance, step_tolerance):
-    C = _integer(num_cameras, "num_cameras", 1)
-    try:
-        pair_arr = np.asarray(pairs)
-    except (TypeError, ValueError):
-        raise ValueError("pairs must be an integer array of shape (Q, 2)") from None
-    if pair_arr.size == 0:
-        pair_arr = np.zeros((0, 2), dtype=np.int64)
-    if pair_arr.ndim != 2 or pair_arr.shape[1] != 2 or not np.issubdtype(pair_arr.dtype, np.integer):
-        raise ValueError(f"pairs must be an integer array of shape (Q, 2), got {pair_arr.dtype} {pair_arr.shape}")
-    Q = pair_arr.shape[0]
-    if Q >= MAX_EDGES:
-        raise ValueError("pairs must number fewer than 2^30")
-    if Q and (pair_arr.min() < 0 or pair_arr.max() >= C):
-        raise ValueError(f"pairs must hold camera indices in [0, {C})")
-    if np.any(pair_arr[:, 0] == pair_arr[:, 1]):
-        raise ValueError("pairs must not join a camera with itself")
-    v = _array(directions, "directions", (Q, 3), "(Q, 3)")
-    w = np.ones(Q) if weights is None else _array(weights, "weights", (Q,), "(Q,)")
-    root = _integer(root, "root", 0, C)
-    if loss not in LOSSES:
-        raise ValueError(f"loss must be one of {LOSSES}, got {loss!r}")
-    angle = _positive(loss_scale_deg, "loss_scale_deg", below=90.0)
-    init = None if initial_positions is None else _array(initial_positions, "initial_positions", (C, 3), "(C, 3)")
-    options = dict(warmup_steps=_integer(warmup_steps, "warmup_steps", 0), max_steps=_integer(max_steps, "max_steps", 0),
-                   max_cg_iterations=_integer(max_cg_iterations, "max_cg_iterations", 1),
-                   cg_tolerance=_positive(cg_tolerance, "cg_tolerance", below=1.0),
-                   step_tolerance=_positive(step_tolerance, "step_tolerance"))
+    C, pair_arr, v, w, root, angle, init, options = _graph_args._checked(
+        num_cameras, pairs, (directions, "directions", (3,)), weights, root, loss, loss_scale_deg, 90.0,
+        (initial_positions, "initial_positions", (3,)),
+        dict(warmup_steps=warmup_steps, max_steps=max_steps, max_cg_iterations=max_cg_iterations, cg_tolerance=cg_tolerance,
+             step_tolerance=step_tolerance))
     return C, pair_arr, v, w, root, math.sin(math.radians(angle)), init, options
 
 
@@ -94,9 +61,7 @@ def active_edges(directions: npt.NDArray, weights: npt.NDArray) -> npt.NDArray:
 def _empty(C: int, root: int, init) -> GlobalPositions:
     c = np.full((C, 3), np.nan)
     c[root] = 0.0 if init is None else init[root]
-    registered = np.zeros(C, dtype=bool)
-    registered[root] = True
-    return GlobalPositions(c, registered, np.where(registered, 0, -1), np.zeros(0), np.zeros(0), 0, 0, 0.0, 0.0, "converged")
+    return GlobalPositions(c, *_root_alone(C, root), np.zeros(0), np.zeros(0), 0, 0, 0.0, 0.0, "converged")
 
 
 def _run(C, pair_arr, v, w, root, loss, scale, init, options, rotations=None) -> GlobalPositions:
@@ -188,9 +153,7 @@ def average_graph_translations(graph, rotations: GlobalRotations, num_images: in
         r = _empty(C, root, init)
     else:
         r = _run(C, pair_arr, t, w, root, loss, scale, init, opts, rotations=np.where(reg[:, None, None], R, np.nan))
-    residual, d = np.full(len(graph.kind), np.nan), np.full(len(graph.kind), np.nan)
-    residual[idx], d[idx] = r.residual_deg, r.scale
-    r.residual_deg, r.scale = residual, d
+    r.residual_deg, r.scale = _scatter(r.residual_deg, idx, len(graph.kind)), _scatter(r.scale, idx, len(graph.kind))
     return r
 
 

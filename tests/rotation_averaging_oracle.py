@@ -6,38 +6,29 @@ of ``PairPoses.R``); weights w_q; a root; a loss with its scale a in radians; op
 An edge is *active* iff w_q is finite and > 0 and all nine entries of R_q are finite.  An inactive edge is ignored
 everywhere and its residual is NaN.  Parallel edges and either orientation are allowed.
 
-1. Adjacency: half-edge 2q belongs to i_q and 2q + 1 to j_q; a camera's half-edges are taken in increasing index.  An index
-   outside 0..C-1 or i_q == j_q gives status BAD_INDEX (every rotation and residual NaN, nothing registered).
-2. Levels: level[root] = 0; in round k = 1, 2, ... a camera without a level looks at its active half-edges whose other end
-   has a level < k; if there are any it takes level k and, in tree mode, its rotation through the heaviest of them (the first
-   of equals): R_c = R_q R_i at the j end, R_q^T R_j at the i end, every entry (a0 b0 + a1 b1) + a2 b2.  R_root = I.  The rounds
-   end when one sets nothing.  A camera without a level is unregistered (R = NaN).  With initial rotations the levels are
-   the same and the given rotations of registered cameras are kept; the root is held.
-3. Steps (at most max_steps): per used edge (active, both ends registered) D = R_j^T (R_q R_i) in this order of products,
-   r = log D, e = (r0 r0 + r1 r1) + r2 r2, omega = w rho'(e).  Solve sum_{q at c} omega (x_c - x_other) = sum_{q at c} s (omega r)
-   (s = +1 at the j end, -1 at the i end; x_root = 0; the sums in half-edge order) for the free cameras by conjugate
-   gradients with the Jacobi preconditioner d_c = sum omega from x = 0, stopping at |r_k| <= cg_tolerance |b|, at
-   max_cg_iterations or at a breakdown (p.Ap <= 0: the iterate so far is the step; at k = 0, or any non-finite scalar: status
-   CG_FAILED with the rotations of the last completed step).  Then R_c <- exp([R_c x_c]x) R_c (= R_c exp([x_c]x)) by
-   Rodrigues, and the step counts.  CONVERGED when max_c |x_c|_inf <= step_tolerance, else MAX_STEPS after max_steps steps.
-   No free camera is CONVERGED with 0 steps; max_steps = 0 with a free camera is MAX_STEPS.
+The adjacency, the level rounds, the system of a step, its solve by conjugate gradients (or ``solver="dense"``), the loop over
+the steps with its statuses, the costs and ``reverse_adjacency`` are tests/graph_cg_oracle.py, shared with translation
+averaging; its numbering is used here.  What is rotation averaging's own:
+
+1. A bad index gives status BAD_INDEX (every rotation and residual NaN, nothing registered).
+2. Levels: in tree mode a camera takes its rotation through its tree edge: R_c = R_q R_i at the j end, R_q^T R_j at the i end,
+   every entry (a0 b0 + a1 b1) + a2 b2.  R_root = I.  An unregistered camera has R = NaN.  With initial rotations the levels
+   are the same and the given rotations of registered cameras are kept; the root is held.
+3. Steps: per used edge D = R_j^T (R_q R_i) in this order of products, r = log D, e = (r0 r0 + r1 r1) + r2 r2,
+   omega = w rho'(e), rvec = r and the cost w rho(e).  The update is R_c <- exp([R_c x_c]x) R_c (= R_c exp([x_c]x)) by
+   Rodrigues.  min_converged_steps = 0.
 4. log D: v = ((D21 - D12) / 2, (D02 - D20) / 2, (D10 - D01) / 2), s = sqrt((v0 v0 + v1 v1) + v2 v2), c = (((D00 + D11) + D22) - 1) / 2
    clamped to [-1, 1], theta = atan2(s, c).  s >= TINY_SINE = 1e-10: r = v (theta / s).  Below it: r = v when c > 0, else
    r = theta (col / |col|) with col the column of (D + I) / 2 whose diagonal entry is largest (the first of equals).
-5. Final pass: residual[q] = sqrt(e) in radians for a used edge, NaN otherwise; cost = sum over the used edges of w rho(e)
-   (initial_cost at the first linearisation, final_cost at the result; equal without a step).
-
-``solver="pcg"`` is the solve above; ``solver="dense"`` replaces the CG by ``numpy.linalg.solve`` on the assembled
-Laplacian (no CG counters, never CG_FAILED).  ``reverse_adjacency=True`` walks every camera's half-edges backwards in the
-sums of step 3 (not in the levels): the spread between the two is what the summation order is worth.
+5. Final pass: residual[q] = sqrt(e) in radians for a used edge, NaN otherwise.
 """
 from __future__ import annotations
 
 import numpy as np
 
-CONVERGED, MAX_STEPS, CG_FAILED, BAD_INDEX = 0, 1, 2, 3
-STATUS = ("converged", "max_steps", "cg_failed", "bad_index")
-LOSSES = ("squared", "huber", "cauchy")
+from graph_cg_oracle import (BAD_INDEX, CG_FAILED, CONVERGED, LOSSES, MAX_STEPS, STATUS, adjacency, bad_index,  # noqa: F401
+                             iterate, levels, rho, weight)
+
 TINY_SINE = 1e-10
 
 
@@ -79,24 +70,6 @@ def exp_map(w):
     return (np.eye(3) + A * W) + B * mul(W, W)
 
 
-def rho(loss, a, e):
-    a2 = a * a
-    if loss == "huber":
-        return e if e <= a2 else (2.0 * a) * np.sqrt(e) - a2
-    if loss == "cauchy":
-        return a2 * np.log1p(e / a2)
-    return e
-
-
-def weight(loss, a, e):
-    a2 = a * a
-    if loss == "huber":
-        return 1.0 if e <= a2 else a / np.sqrt(e)
-    if loss == "cauchy":
-        return 1.0 / (1.0 + e / a2)
-    return 1.0
-
-
 def active_edges(relative, weights):
     w = np.asarray(weights, dtype=np.float64)
     R = np.asarray(relative, dtype=np.float64).reshape(-1, 9)
@@ -104,49 +77,16 @@ def active_edges(relative, weights):
         return np.isfinite(w) & (w > 0) & np.all(np.isfinite(R), axis=1)
 
 
-def adjacency(C, pairs):
-    """Per camera the half-edges 2q (i end) and 2q + 1 (j end) in increasing index."""
-    adj = [[] for _ in range(C)]
-    for h, c in enumerate(np.asarray(pairs).reshape(-1)):
-        adj[int(c)].append(h)
-    return adj
-
-
 def levels_and_tree(C, pairs, relative, weights, root, tree=True):
     """(level [C] (-1: unregistered), R [C,3,3] of the tree initialisation (NaN where unregistered; only with ``tree``))."""
-    pairs = np.asarray(pairs).reshape(-1, 2)
-    flat = pairs.reshape(-1)
-    act = active_edges(relative, weights)
-    adj = adjacency(C, pairs)
-    level = np.full(C, -1, dtype=np.int64)
-    level[root] = 0
     R = np.full((C, 3, 3), np.nan)
     R[root] = np.eye(3)
-    for k in range(1, C):
-        new = []
-        for c in range(C):
-            if level[c] >= 0:
-                continue
-            best, best_w = -1, 0.0
-            for h in adj[c]:
-                q = h >> 1
-                if not act[q]:
-                    continue
-                lv = level[flat[h ^ 1]]
-                if lv < 0 or lv >= k:
-                    continue
-                if best < 0 or weights[q] > best_w:
-                    best, best_w = h, weights[q]
-            if best >= 0:
-                new.append((c, best))
-        if not new:
-            break
-        for c, h in new:   # after the scan: no camera of this round sees another of this round
-            level[c] = k
-            if tree:
-                Rq, Ro = np.asarray(relative[h >> 1], dtype=np.float64).reshape(3, 3), R[flat[h ^ 1]]
-                R[c] = mul(Rq, Ro) if h & 1 else mul(Rq.T, Ro)
-    return level, R
+
+    def place(c, h, other):
+        Rq = np.asarray(relative[h >> 1], dtype=np.float64).reshape(3, 3)
+        R[c] = mul(Rq, R[other]) if h & 1 else mul(Rq.T, R[other])
+
+    return levels(C, pairs, weights, active_edges(relative, weights), root, place if tree else None), R
 
 
 def edge_residuals(pairs, relative, R, used):
@@ -170,7 +110,7 @@ def average_rotations(num_cameras, pairs, relative_rotations, weights=None, root
     w = np.ones(Q) if weights is None else np.asarray(weights, dtype=np.float64)
     out = dict(R=np.full((C, 3, 3), np.nan), registered=np.zeros(C, dtype=bool), level=np.full(C, -1), residual=np.full(Q, np.nan),
                steps=0, cg_iterations=0, cg_max=0, initial_cost=np.nan, final_cost=np.nan, status=BAD_INDEX)
-    if Q and (pairs.min() < 0 or pairs.max() >= C or np.any(pairs[:, 0] == pairs[:, 1])):
+    if bad_index(C, pairs):
         return out
     level, R = levels_and_tree(C, pairs, rel, w, root, tree=initial_rotations is None)
     reg = level >= 0
@@ -178,108 +118,29 @@ def average_rotations(num_cameras, pairs, relative_rotations, weights=None, root
         R = np.array(initial_rotations, dtype=np.float64).reshape(C, 3, 3)
         R[~reg] = np.nan
     used = active_edges(rel, w) & reg[pairs[:, 0]] & reg[pairs[:, 1]] if Q else np.zeros(0, dtype=bool)
-    free = reg.copy()
-    free[root] = False
-    adj = adjacency(C, pairs)
-    if reverse_adjacency:
-        adj = [a[::-1] for a in adj]
-    flat = pairs.reshape(-1)
     a = float(loss_scale)
 
-    def cost_of(r):
-        return float(sum(w[q] * rho(loss, a, (r[q, 0] * r[q, 0] + r[q, 1] * r[q, 1]) + r[q, 2] * r[q, 2])
-                         for q in np.nonzero(used)[0]))
-
-    def apply(om, p):
-        y = np.zeros((C, 3))
-        for c in np.nonzero(free)[0]:
-            acc = np.zeros(3)
-            for h in adj[c]:
-                q = h >> 1
-                if used[q]:
-                    acc += om[q] * (p[c] - p[flat[h ^ 1]])
-            y[c] = acc
-        return y
-
-    status, steps, cg_total, cg_max, initial_cost = MAX_STEPS, 0, 0, 0, None
-    if not free.any():
-        status = CONVERGED
-    while status == MAX_STEPS and steps < max_steps:
+    def edge_terms(step):
         r = edge_residuals(pairs, rel, R, used)
-        if initial_cost is None:
-            initial_cost = cost_of(r)
-        om = np.zeros(Q)
+        om, cost = np.zeros(Q), np.zeros(Q)
         for q in np.nonzero(used)[0]:
-            om[q] = w[q] * weight(loss, a, (r[q, 0] * r[q, 0] + r[q, 1] * r[q, 1]) + r[q, 2] * r[q, 2])
-        d, b = np.zeros(C), np.zeros((C, 3))
-        for c in np.nonzero(free)[0]:
-            for h in adj[c]:
-                q = h >> 1
-                if used[q]:
-                    d[c] += om[q]
-                    b[c] += (1.0 if h & 1 else -1.0) * (om[q] * r[q])
-        if solver == "dense":
-            idx = np.nonzero(free)[0]
-            slot = np.full(C, -1)
-            slot[idx] = np.arange(len(idx))
-            L = np.zeros((len(idx), len(idx)))
-            for q in np.nonzero(used)[0]:
-                si, sj = slot[pairs[q, 0]], slot[pairs[q, 1]]
-                for s in (si, sj):
-                    if s >= 0:
-                        L[s, s] += om[q]
-                if si >= 0 and sj >= 0:
-                    L[si, sj] -= om[q]
-                    L[sj, si] -= om[q]
-            x = np.zeros((C, 3))
-            x[idx] = np.linalg.solve(L, b[idx])
-        else:
-            inv_d = np.where(free, 1.0, 0.0) / np.where(free, d, 1.0)
-            x = np.zeros((C, 3))
-            res = b.copy()
-            z = res * inv_d[:, None]
-            p = z.copy()
-            rz, bb = float(np.sum(res * z)), float(np.sum(b * b))
-            tol2 = cg_tolerance * cg_tolerance * bb
-            failed = not (np.isfinite(rz) and np.isfinite(bb))
-            k = 0
-            done = failed or bb <= tol2
-            while not done:
-                Ap = apply(om, p)
-                pq = float(np.sum(p * Ap))
-                with np.errstate(divide="ignore", invalid="ignore"):
-                    alpha = np.float64(rz) / np.float64(pq)
-                if not (pq > 0.0) or not np.isfinite(pq) or not np.isfinite(alpha):
-                    failed = k == 0 or not np.isfinite(pq) or not np.isfinite(alpha)
-                    break
-                x = x + alpha * p
-                res = res - alpha * Ap
-                z = res * inv_d[:, None]
-                rz_new, rr = float(np.sum(res * z)), float(np.sum(res * res))
-                k += 1
-                if not (np.isfinite(rz_new) and np.isfinite(rr)):
-                    failed = True
-                    break
-                done = rr <= tol2 or k == max_cg_iterations
-                if not done:
-                    p = z + (rz_new / rz) * p
-                rz = rz_new
-            if failed:
-                status = CG_FAILED
-                break
-            cg_total += k
-            cg_max = max(cg_max, k)
+            e = (r[q, 0] * r[q, 0] + r[q, 1] * r[q, 1]) + r[q, 2] * r[q, 2]
+            om[q] = w[q] * weight(loss, a, e)
+            cost[q] = w[q] * rho(loss, a, e)
+        return om, r, cost
+
+    def update(x, free):
         for c in np.nonzero(free)[0]:
             y = np.array([(R[c][k, 0] * x[c][0] + R[c][k, 1] * x[c][1]) + R[c][k, 2] * x[c][2] for k in range(3)])
             R[c] = mul(exp_map(y), R[c])
-        steps += 1
-        if np.max(np.abs(x[free])) <= step_tolerance:
-            status = CONVERGED
-    r = edge_residuals(pairs, rel, R, used)
-    final_cost = cost_of(r)
-    residual = np.where(used, np.sqrt((r[:, 0] * r[:, 0] + r[:, 1] * r[:, 1]) + r[:, 2] * r[:, 2]), np.nan) if Q else np.zeros(0)
-    out.update(R=R, registered=reg, level=level, residual=residual, steps=steps, cg_iterations=cg_total, cg_max=cg_max,
-               initial_cost=final_cost if initial_cost is None else initial_cost, final_cost=final_cost, status=status)
+
+    def final():
+        _, r, cost = edge_terms(None)
+        e = (r[:, 0] * r[:, 0] + r[:, 1] * r[:, 1]) + r[:, 2] * r[:, 2]
+        return cost, dict(R=R, residual=np.where(used, np.sqrt(e), np.nan) if Q else np.zeros(0))
+
+    out.update(iterate(C, pairs, root, level, used, edge_terms, update, final, max_steps, max_cg_iterations, cg_tolerance,
+                       step_tolerance, solver=solver, reverse_adjacency=reverse_adjacency))
     return out
 
 

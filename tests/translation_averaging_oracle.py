@@ -7,35 +7,29 @@ weights w_q; a root; a loss of csrc/sfm_loss.h whose scale a is a sine; optional
 0. World directions from (R, t): u_k = (R_j[0,k] t0 + R_j[1,k] t1) + R_j[2,k] t2, n = sqrt((t0 t0 + t1 t1) + t2 t2), v = -(u / n).
    An edge is *active* iff w_q is finite and > 0 and v_q is finite (with rotations: t_q and the nine entries of R_j are finite
    and n > 0).  An inactive edge is ignored everywhere; its residual and scale are NaN.
-1. Adjacency, the levels and the heaviest breadth-first spanning tree are those of tests/rotation_averaging_oracle.py.  An index
-   outside 0..C-1 or i_q == j_q gives status BAD_INDEX (every position, residual and scale NaN, nothing registered).  In tree
-   mode c_root = 0 and a camera takes c_other + v_q through its tree edge at the j end, c_other - v_q at the i end: the unit
-   of the result is one tree baseline.  With initial positions the registered cameras keep theirs and the root is held.
-2. Steps (at most max_steps), per used edge (active, both ends registered): D = c_j - c_i, n2 = (D0 D0 + D1 D1) + D2 D2,
-   dv = (D0 v0 + D1 v1) + D2 v2, the scale d = max(dv, 0) / n2 (0 when n2 = 0; 1 in the first warmup_steps steps),
-   r = v - d D, e = (r0 r0 + r1 r1) + r2 r2, omega = w rho'(e); stored are omega2 = omega (d d) and rd = r / d (0 when d = 0).
-   Solve sum_{q at c} omega2 (x_c - x_other) = sum_{q at c} s (omega2 rd) (s = +1 at the j end, -1 at the i end; x_root = 0; the
-   sums in half-edge order) for the free cameras by the conjugate gradients of the rotation oracle with the Jacobi
-   preconditioner d_c = sum omega2; a free camera with d_c = 0 (every used edge at it has d = 0) gets d_c = 1, and with its
-   zero right-hand side a zero step.  Then c <- c + x and the step counts.  CONVERGED when max_c |x_c|_inf <= step_tolerance
-   after a step that was not a warm-up step, else MAX_STEPS after max_steps steps; CG_FAILED as in the rotation oracle.
+1. Adjacency, the levels, the system of a step and its solve, the loop over the steps with its statuses and the costs are
+   tests/graph_cg_oracle.py, shared with rotation averaging.  A bad index gives status BAD_INDEX (every position, residual and
+   scale NaN, nothing registered).  In tree mode c_root = 0 and a camera takes c_other + v_q through its tree edge at the j
+   end, c_other - v_q at the i end: the unit of the result is one tree baseline.  With initial positions the registered
+   cameras keep theirs and the root is held.
+2. Steps, per used edge: D = c_j - c_i, n2 = (D0 D0 + D1 D1) + D2 D2, dv = (D0 v0 + D1 v1) + D2 v2, the scale
+   d = max(dv, 0) / n2 (0 when n2 = 0; 1 in the first warmup_steps steps), r = v - d D, e = (r0 r0 + r1 r1) + r2 r2; the edge
+   terms are omega = (w rho'(e)) (d d), rvec = r / d (0 when d = 0) and the cost w rho(e).  A free camera whose every used edge
+   has d = 0 has a zero row and takes a zero step.  The update is c <- c + x.  min_converged_steps = warmup_steps: a warm-up
+   step does not end the call as CONVERGED.
 3. Final pass, with the scale of step 2 (never the warm-up's): residual[q] = atan2(|D x v|, dv) in radians (0..pi; the cross
-   product as (D1 v2 - D2 v1, D2 v0 - D0 v2, D0 v1 - D1 v0), its norm sqrt((x0 x0 + x1 x1) + x2 x2)), scale[q] = d; cost = sum over
-   the used edges of w rho(e) (initial_cost at the first linearisation, with d = 1 when that is a warm-up step; final_cost at
-   the result; equal without a step).
+   product as (D1 v2 - D2 v1, D2 v0 - D0 v2, D0 v1 - D1 v0), its norm sqrt((x0 x0 + x1 x1) + x2 x2)), scale[q] = d.  The
+   initial cost is taken with d = 1 when the first step is a warm-up step.
 
-A graph of one edge from the tree start has D = v bit for bit, so n2 = dv, d = 1, r = 0 and the step is exactly zero.
-
-``solver="pcg"`` is the solve above; ``solver="dense"`` replaces the CG by ``numpy.linalg.solve`` on the assembled Laplacian
-(a zero diagonal set to 1; least squares when an interior part of the graph is cut off by zero scales).
-``reverse_adjacency=True`` walks every camera's half-edges backwards in the sums of step 2.
+A graph of one edge from the tree start has D = v bit for bit, so n2 = dv, d = 1, r = 0 and the step is exactly zero.  The
+dense solve meets a singular matrix when an interior part of the graph is cut off by zero scales.
 """
 from __future__ import annotations
 
 import numpy as np
 
-from rotation_averaging_oracle import (BAD_INDEX, CG_FAILED, CONVERGED, LOSSES, MAX_STEPS, STATUS, adjacency, rho,  # noqa: F401
-                                       weight)
+from graph_cg_oracle import (BAD_INDEX, CG_FAILED, CONVERGED, LOSSES, MAX_STEPS, STATUS, adjacency, bad_index,  # noqa: F401
+                             iterate, levels, rho, weight)
 
 
 def world_directions(pairs, t, R):
@@ -67,38 +61,13 @@ def active_edges(pairs, directions, weights, rotations=None):
 
 def levels_and_tree(C, pairs, v, weights, act, root, tree=True):
     """(level [C] (-1: unregistered), c [C,3] of the tree start (NaN where unregistered; only with ``tree``))."""
-    pairs = np.asarray(pairs).reshape(-1, 2)
-    flat = pairs.reshape(-1)
-    adj = adjacency(C, pairs)
-    level = np.full(C, -1, dtype=np.int64)
-    level[root] = 0
     c = np.full((C, 3), np.nan)
     c[root] = 0.0
-    for k in range(1, C):
-        new = []
-        for cam in range(C):
-            if level[cam] >= 0:
-                continue
-            best, best_w = -1, 0.0
-            for h in adj[cam]:
-                q = h >> 1
-                if not act[q]:
-                    continue
-                lv = level[flat[h ^ 1]]
-                if lv < 0 or lv >= k:
-                    continue
-                if best < 0 or weights[q] > best_w:
-                    best, best_w = h, weights[q]
-            if best >= 0:
-                new.append((cam, best))
-        if not new:
-            break
-        for cam, h in new:   # after the scan: no camera of this round sees another of this round
-            level[cam] = k
-            if tree:
-                co = c[flat[h ^ 1]]
-                c[cam] = co + v[h >> 1] if h & 1 else co - v[h >> 1]
-    return level, c
+
+    def place(cam, h, other):
+        c[cam] = c[other] + v[h >> 1] if h & 1 else c[other] - v[h >> 1]
+
+    return levels(C, pairs, weights, act, root, place if tree else None), c
 
 
 def dot3(a, b):
@@ -134,7 +103,7 @@ def average_translations(num_cameras, pairs, directions, weights=None, root=0, l
     out = dict(c=np.full((C, 3), np.nan), registered=np.zeros(C, dtype=bool), level=np.full(C, -1), residual=np.full(Q, np.nan),
                scale=np.full(Q, np.nan), steps=0, cg_iterations=0, cg_max=0, initial_cost=np.nan, final_cost=np.nan,
                status=BAD_INDEX, v=np.full((Q, 3), np.nan))
-    if Q and (pairs.min() < 0 or pairs.max() >= C or np.any(pairs[:, 0] == pairs[:, 1])):
+    if bad_index(C, pairs):
         return out
     act = active_edges(pairs, dirs, w, rotations) if Q else np.zeros(0, dtype=bool)
     v = dirs if rotations is None else world_directions(pairs, dirs, rotations)
@@ -147,122 +116,37 @@ def average_translations(num_cameras, pairs, directions, weights=None, root=0, l
         c = np.array(initial_positions, dtype=np.float64).reshape(C, 3)
         c[~reg] = np.nan
     used = act & reg[pairs[:, 0]] & reg[pairs[:, 1]] if Q else np.zeros(0, dtype=bool)
-    free = reg.copy()
-    free[root] = False
-    adj = adjacency(C, pairs)
-    if reverse_adjacency:
-        adj = [a[::-1] for a in adj]
-    flat = pairs.reshape(-1)
     a = float(loss_scale)
 
     def cost_of(e):
-        return float(sum(w[q] * rho(loss, a, e[q]) for q in np.nonzero(used)[0]))
+        cost = np.zeros(Q)
+        for q in np.nonzero(used)[0]:
+            cost[q] = w[q] * rho(loss, a, e[q])
+        return cost
 
-    def apply(om, p):
-        y = np.zeros((C, 3))
-        for cam in np.nonzero(free)[0]:
-            acc = np.zeros(3)
-            for h in adj[cam]:
-                q = h >> 1
-                if used[q]:
-                    acc += om[q] * (p[cam] - p[flat[h ^ 1]])
-            y[cam] = acc
-        return y
-
-    status, steps, cg_total, cg_max, initial_cost = MAX_STEPS, 0, 0, 0, None
-    if not free.any():
-        status = CONVERGED
-    while status == MAX_STEPS and steps < max_steps:
-        d, r, e, _, _ = edge_terms(pairs, v, c, used, steps < warmup_steps)
-        if initial_cost is None:
-            initial_cost = cost_of(e)
+    def terms(step):
+        d, r, e, _, _ = edge_terms(pairs, v, c, used, step < warmup_steps)
         om, rd = np.zeros(Q), np.zeros((Q, 3))
         for q in np.nonzero(used)[0]:
             om[q] = (w[q] * weight(loss, a, e[q])) * (d[q] * d[q])
             if d[q] != 0.0:
                 rd[q] = r[q] / d[q]
-        dd, b = np.zeros(C), np.zeros((C, 3))
-        for cam in np.nonzero(free)[0]:
-            for h in adj[cam]:
-                q = h >> 1
-                if used[q]:
-                    dd[cam] += om[q]
-                    b[cam] += (1.0 if h & 1 else -1.0) * (om[q] * rd[q])
-            if dd[cam] == 0.0:
-                dd[cam] = 1.0
-        if solver == "dense":
-            idx = np.nonzero(free)[0]
-            slot = np.full(C, -1)
-            slot[idx] = np.arange(len(idx))
-            L = np.zeros((len(idx), len(idx)))
-            for q in np.nonzero(used)[0]:
-                si, sj = slot[pairs[q, 0]], slot[pairs[q, 1]]
-                for s in (si, sj):
-                    if s >= 0:
-                        L[s, s] += om[q]
-                if si >= 0 and sj >= 0:
-                    L[si, sj] -= om[q]
-                    L[sj, si] -= om[q]
-            for s in range(len(idx)):
-                if L[s, s] == 0.0:
-                    L[s, s] = 1.0
-            x = np.zeros((C, 3))
-            try:
-                x[idx] = np.linalg.solve(L, b[idx])
-            except np.linalg.LinAlgError:
-                x[idx] = np.linalg.lstsq(L, b[idx], rcond=None)[0]
-        else:
-            inv_d = np.where(free, 1.0, 0.0) / np.where(free, dd, 1.0)
-            x = np.zeros((C, 3))
-            res = b.copy()
-            z = res * inv_d[:, None]
-            p = z.copy()
-            rz, bb = float(np.sum(res * z)), float(np.sum(b * b))
-            tol2 = cg_tolerance * cg_tolerance * bb
-            failed = not (np.isfinite(rz) and np.isfinite(bb))
-            k = 0
-            done = failed or bb <= tol2
-            while not done:
-                Ap = apply(om, p)
-                pq = float(np.sum(p * Ap))
-                with np.errstate(divide="ignore", invalid="ignore"):
-                    alpha = np.float64(rz) / np.float64(pq)
-                if not (pq > 0.0) or not np.isfinite(pq) or not np.isfinite(alpha):
-                    failed = k == 0 or not np.isfinite(pq) or not np.isfinite(alpha)
-                    break
-                x = x + alpha * p
-                res = res - alpha * Ap
-                z = res * inv_d[:, None]
-                rz_new, rr = float(np.sum(res * z)), float(np.sum(res * res))
-                k += 1
-                if not (np.isfinite(rz_new) and np.isfinite(rr)):
-                    failed = True
-                    break
-                done = rr <= tol2 or k == max_cg_iterations
-                if not done:
-                    p = z + (rz_new / rz) * p
-                rz = rz_new
-            if failed:
-                status = CG_FAILED
-                break
-            cg_total += k
-            cg_max = max(cg_max, k)
+        return om, rd, cost_of(e)
+
+    def update(x, free):
         c[free] = c[free] + x[free]
-        steps += 1
-        if np.max(np.abs(x[free])) <= step_tolerance and steps > warmup_steps:
-            status = CONVERGED
-    d, r, e, dv, D = edge_terms(pairs, v, c, used, False)
-    final_cost = cost_of(e)
-    if Q:
+
+    def final():
+        d, r, e, dv, D = edge_terms(pairs, v, c, used, False)
+        if not Q:
+            return cost_of(e), dict(c=c, v=v, residual=np.zeros(0), scale=np.zeros(0))
         x = np.stack([D[:, 1] * v[:, 2] - D[:, 2] * v[:, 1], D[:, 2] * v[:, 0] - D[:, 0] * v[:, 2],
                       D[:, 0] * v[:, 1] - D[:, 1] * v[:, 0]], axis=1)
-        residual = np.where(used, np.arctan2(np.sqrt(dot3(x, x)), dv), np.nan)
-        scale = np.where(used, d, np.nan)
-    else:
-        residual, scale = np.zeros(0), np.zeros(0)
-    out.update(c=c, registered=reg, level=level, residual=residual, scale=scale, steps=steps, cg_iterations=cg_total,
-               cg_max=cg_max, initial_cost=final_cost if initial_cost is None else initial_cost, final_cost=final_cost,
-               status=status, v=v)
+        return cost_of(e), dict(c=c, v=v, residual=np.where(used, np.arctan2(np.sqrt(dot3(x, x)), dv), np.nan),
+                                scale=np.where(used, d, np.nan))
+
+    out.update(iterate(C, pairs, root, level, used, terms, update, final, max_steps, max_cg_iterations, cg_tolerance,
+                       step_tolerance, min_converged_steps=warmup_steps, solver=solver, reverse_adjacency=reverse_adjacency))
     return out
 
 
