@@ -160,7 +160,8 @@ def iterate(C, pairs, root, level, used, edge_terms, update, final, max_steps, m
     """The steps of a solver.  ``edge_terms(step)`` -> (omega [Q], rvec [Q,3], cost [Q]) of the linearisation of step ``step``
     (zeros where an edge is not used); ``update(x, free)`` moves the solver's state by the step x [C,3]; ``final()`` -> (cost
     [Q] at the result, a dict of the solver's own per-edge results).  Returns that dict with registered, level, steps,
-    cg_iterations, cg_max, initial_cost, final_cost and status (an index of ``STATUS``)."""
+    cg_iterations, cg_max, cg_at_limit (``solver="pcg"`` and every solve of at least one step ended at ``max_cg_iterations``),
+    initial_cost, final_cost and status (an index of ``STATUS``)."""
     reg = level >= 0
     free = reg.copy()
     free[root] = False
@@ -173,6 +174,7 @@ def iterate(C, pairs, root, level, used, edge_terms, update, final, max_steps, m
         return float(sum(cost[q] for q in np.nonzero(used)[0]))
 
     status, steps, cg_total, cg_max, initial_cost = MAX_STEPS, 0, 0, 0, None
+    at_limit = solver == "pcg"   # every solve ended at max_cg_iterations: the counters do not depend on rounding
     if not free.any():
         status = CONVERGED
     while status == MAX_STEPS and steps < max_steps:
@@ -208,6 +210,7 @@ def iterate(C, pairs, root, level, used, edge_terms, update, final, max_steps, m
                 break
             cg_total += k
             cg_max = max(cg_max, k)
+            at_limit = at_limit and k == max_cg_iterations
         update(x, free)
         steps += 1
         if np.max(np.abs(x[free])) <= step_tolerance and steps > min_converged_steps:
@@ -215,5 +218,6 @@ def iterate(C, pairs, root, level, used, edge_terms, update, final, max_steps, m
     cost, result = final()
     final_cost = total(cost)
     result.update(registered=reg, level=level, steps=steps, cg_iterations=cg_total, cg_max=cg_max,
+                  cg_at_limit=at_limit and steps > 0 and status != CG_FAILED,
                   initial_cost=final_cost if initial_cost is None else initial_cost, final_cost=final_cost, status=status)
     return result

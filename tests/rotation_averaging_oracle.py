@@ -18,8 +18,12 @@ averaging; its numbering is used here.  What is rotation averaging's own:
    omega = w rho'(e), rvec = r and the cost w rho(e).  The update is R_c <- exp([R_c x_c]x) R_c (= R_c exp([x_c]x)) by
    Rodrigues.  min_converged_steps = 0.
 4. log D: v = ((D21 - D12) / 2, (D02 - D20) / 2, (D10 - D01) / 2), s = sqrt((v0 v0 + v1 v1) + v2 v2), c = (((D00 + D11) + D22) - 1) / 2
-   clamped to [-1, 1], theta = atan2(s, c).  s >= TINY_SINE = 1e-10: r = v (theta / s).  Below it: r = v when c > 0, else
-   r = theta (col / |col|) with col the column of (D + I) / 2 whose diagonal entry is largest (the first of equals).
+   clamped to [-1, 1], theta = atan2(s, c).  c > HALF_TURN_COSINE = -0.5 (below 120 degrees): r = v (theta / s) for
+   s >= TINY_SINE = 1e-10 and r = v below it.  c <= -0.5: the axis from the symmetric part (D + D^T) / 2 = c I + (1 - c) a a^T,
+   which stays well conditioned up to the half turn where v vanishes: b_m = D_mm - c, k the largest of them (the first of
+   equals), col_k = b_k and col_m = (D_mk + D_km) / 2 otherwise, n = sqrt((col0 col0 + col1 col1) + col2 col2), the sign
+   g = -1 when (col0 v0 + col1 v1) + col2 v2 < 0 and +1 otherwise (v = s a; at the half turn itself both signs are logarithms),
+   r = (g theta) (col / n).
 5. Final pass: residual[q] = sqrt(e) in radians for a used edge, NaN otherwise.
 """
 from __future__ import annotations
@@ -30,6 +34,7 @@ from graph_cg_oracle import (BAD_INDEX, CG_FAILED, CONVERGED, LOSSES, MAX_STEPS,
                              iterate, levels, rho, weight)
 
 TINY_SINE = 1e-10
+HALF_TURN_COSINE = -0.5
 
 
 def mul(A, B):
@@ -42,19 +47,18 @@ def log_map(D):
     s = np.sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2])
     c = min(1.0, max(-1.0, 0.5 * (((D[0, 0] + D[1, 1]) + D[2, 2]) - 1.0)))
     theta = np.arctan2(s, c)
-    if s >= TINY_SINE:
-        return v * (theta / s)
-    if c > 0.0:
-        return v
-    b = [0.5 * (D[0, 0] + 1.0), 0.5 * (D[1, 1] + 1.0), 0.5 * (D[2, 2] + 1.0)]
+    if c > HALF_TURN_COSINE:
+        return v * (theta / s) if s >= TINY_SINE else v
+    b = [D[0, 0] - c, D[1, 1] - c, D[2, 2] - c]
     k = 0
     if b[1] > b[k]:
         k = 1
     if b[2] > b[k]:
         k = 2
-    col = np.array([b[k] if m == k else 0.5 * D[m, k] for m in range(3)])
+    col = np.array([b[k] if m == k else 0.5 * (D[m, k] + D[k, m]) for m in range(3)])
     n = np.sqrt((col[0] * col[0] + col[1] * col[1]) + col[2] * col[2])
-    return theta * (col / n)
+    g = -1.0 if (col[0] * v[0] + col[1] * v[1]) + col[2] * v[2] < 0.0 else 1.0
+    return (g * theta) * (col / n)
 
 
 def exp_map(w):

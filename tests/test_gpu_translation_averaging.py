@@ -54,7 +54,10 @@ def _device(case, loss_scale=None, **kw):
 
 
 def _assert_matches(got, want, where):
-    """Registration, levels, step count and status equal; positions, residuals, scales and costs within the tolerance."""
+    """Registration, levels, step count and status equal; positions, residuals, scales and costs within the tolerance.  Where
+    the oracle ran ``solver="pcg"`` and every one of its solves ended at ``max_cg_iterations`` (``cg_at_limit``), ``cg_iterations``
+    equals too; a solve that stops at its tolerance may stop an iteration apart.  The public record carries no ``cg_max``:
+    tests/test_gpu_averaging_edges.py compares it on the device's info record."""
     assert np.array_equal(got.registered, want["registered"]) and np.array_equal(got.level, want["level"]), where
     assert got.status == to.STATUS[want["status"]] and got.steps == want["steps"], (where, got.status, got.steps, want["steps"])
     reg, used = want["registered"], ~np.isnan(want["residual"])
@@ -68,6 +71,8 @@ def _assert_matches(got, want, where):
     assert pos <= TOL and res <= TOL and scale <= TOL, (where, pos, res, scale)
     for a, b in ((got.initial_cost, want["initial_cost"]), (got.final_cost, want["final_cost"])):
         assert abs(a - b) <= 1e-9 * max(abs(b), 1e-12), (where, a, b)   # a sum of Q terms, each good to TOL
+    if want.get("cg_at_limit"):
+        assert got.cg_iterations == want["cg_iterations"], (where, got.cg_iterations, want["cg_iterations"])
 
 
 @pytest.fixture(scope="module")
