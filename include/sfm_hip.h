@@ -967,6 +967,47 @@ int sfm_hamming_summary(const uint8_t* desc_a, const uint8_t* ok_a, int64_t n_a,
                         int64_t n_b, void* workspace, int64_t workspace_bytes, double* best, int32_t* arg, double* second,
                         void* stream);
 
+/* ---- descriptor matching of every image pair of a collection (definition: tests/graph_matching_oracle.py) ---- */
+
+/* (added within ABI 15) How sfm_match_pairs validates a row's nearest column. */
+typedef struct sfm_match_pairs_options {
+    int32_t max_distance; /* 0..256: a kept match has a Hamming distance of at most this */
+    int32_t cross_check;  /* 0 or 1: the row must also be its column's nearest row, and distinctive on that side too */
+    int32_t use_ratio;    /* 0 or 1: 0 skips the ratio test */
+    int32_t reserved;     /* must be 0 */
+    double ratio;         /* finite, > 0 (read only with use_ratio): distance d is distinctive against the runner-up s iff
+                             (double)d <= ratio * (double)s */
+} sfm_match_pairs_options;
+
+/* Bytes of workspace sfm_match_pairs needs; -1 for sizes it refuses (negative, pairs > 65535, rows or max_image_features
+ * >= 2^31). */
+int64_t sfm_match_pairs_workspace_bytes(int64_t pairs, int64_t rows, int64_t max_image_features);
+
+/* Matches the 32-byte binary descriptors (sfm_brief_describe's) of every image pair of a collection in one call.  The
+ * descriptors of all images lie image-major in desc / ok: image i owns entries image_offset[i] .. image_offset[i + 1] - 1
+ * (sfm_build_tracks's image_offset and pair_images).  Pair q = (i, j) has one output row per feature of image i, rows
+ * row_offset[q] .. row_offset[q + 1] - 1; its columns are the features of image j.  d(a, b), the Hamming distance, is defined
+ * when both descriptors are valid (ok != 0).  For a valid row a: best = the smallest d(a, .), arg = the smallest column that
+ * attains it, second = the smallest d(a, b) over valid b != arg (none when there is no such b; a tie for the best gives
+ * second == best); the same per column with the roles swapped.  Row a keeps partner[r] = arg, distance[r] = best iff best <=
+ * max_distance, best is distinctive against the row's second (always, when there is none or use_ratio is 0) and, with
+ * cross_check, a is the arg of column arg and best is distinctive against that column's second.  Every other row gets -1 in
+ * both; an invalid descriptor never matches and is nobody's best or second.  All integer but the ratio test: bit-identical
+ * to the NumPy definition.
+ * pair_status[q] is 1, every row of the pair's span that lies inside [0, rows) is -1 and nothing is read through the pair's
+ * indices, when the pair names an image outside [0, images) or twice the same image, an image's offsets leave
+ * [0, features] or its size exceeds max_image_features, or the pair's row_offset span is not its first image's size or leaves
+ * [0, rows]; otherwise 0.  A row no pair's span holds gets -1.  Every entry of partner, distance and pair_status is written.
+ * image_offset: dev int32 [images + 1]; desc: dev u8 [features,32], 16-byte aligned; ok: dev u8 [features]; pair_images: dev
+ * int32 [pairs,2]; row_offset: dev int64 [pairs + 1], non-decreasing; partner, distance: dev int32 [rows]; pair_status: dev
+ * int32 [pairs]; workspace: dev, 16-byte aligned, at least sfm_match_pairs_workspace_bytes(pairs, rows, max_image_features).
+ * SFM_EINVAL before the first launch for a negative size, pairs > 65535, a size >= 2^31, rows without pairs, a null or
+ * misaligned pointer, an option out of range, reserved != 0 or a workspace too small. */
+int sfm_match_pairs(int64_t images, int64_t features, int64_t pairs, int64_t rows, int64_t max_image_features,
+                    const int32_t* image_offset, const uint8_t* desc, const uint8_t* ok, const int32_t* pair_images,
+                    const int64_t* row_offset, const sfm_match_pairs_options* options, int32_t* partner, int32_t* distance,
+                    int32_t* pair_status, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- Harris corner detector stencils (reference lib/harris/harris_detector.py, lib/common/correlate.py) ---- */
 
 /* Zero-'same' cross-correlation with an odd square kernel (correlate.py:4-39).  image, out: dev f64

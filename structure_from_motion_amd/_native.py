@@ -148,6 +148,7 @@ SIGNATURES = {
     "sfm_match_summary": [C.c_int, _P, _I64, _P, _I64, _P, _P, _P, _P, _I64, _I64, C.c_int, _P, _I64, _P, _P, _P, _P],
     "sfm_brief_describe": [_P, _I64, _I64, _P, _I64, _P, _P, C.c_int, _P, _P, _P, _P],
     "sfm_hamming_summary": [_P, _P, _I64, _P, _P, _I64, _P, _I64, _P, _P, _P, _P],
+    "sfm_match_pairs": [_I64, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P],
     "sfm_cross_correlate": [_P, _I64, _I64, _P, C.c_int, _P, _P],
     "sfm_harris_cornerness": [_P, _P, _I64, _I64, C.c_int, _D, C.c_int, _I64, _I64, _P, _P],
     "sfm_nms_inplace": [_P, _I64, _I64, _P],
@@ -194,7 +195,8 @@ OTHER_SYMBOLS = ["sfm_last_error", "sfm_abi_version", "sfm_score_workspace_bytes
                  "sfm_fit_trace_doubles", "sfm_match_summary_workspace_bytes", "sfm_bundle_workspace_bytes",
                  "sfm_tracks_workspace_bytes", "sfm_bundle_pcg_workspace_bytes", "sfm_build_tracks_workspace_bytes",
                  "sfm_bundle_pcg_workspace_bytes_ex", "sfm_hamming_summary_workspace_bytes", "sfm_pair_poses_workspace_bytes",
-                 "sfm_average_rotations_workspace_bytes", "sfm_average_translations_workspace_bytes"]
+                 "sfm_average_rotations_workspace_bytes", "sfm_average_translations_workspace_bytes",
+                 "sfm_match_pairs_workspace_bytes"]
 
 # the losses of both bundle adjusters, in the order of their SFM_BUNDLE_LOSS_* codes (include/sfm_hip.h)
 BUNDLE_LOSSES = ("squared", "huber", "cauchy")
@@ -253,6 +255,12 @@ class TransavgOptions(C.Structure):
                 ("step_tolerance", C.c_double)]
 
 
+class MatchPairsOptions(C.Structure):
+    """sfm_match_pairs_options"""
+    _fields_ = [("max_distance", C.c_int32), ("cross_check", C.c_int32), ("use_ratio", C.c_int32), ("reserved", C.c_int32),
+                ("ratio", C.c_double)]
+
+
 _lib = None
 
 
@@ -305,6 +313,8 @@ def load() -> C.CDLL:
     lib.sfm_average_rotations_workspace_bytes.argtypes = [_I64, _I64]
     lib.sfm_average_translations_workspace_bytes.restype = C.c_int64
     lib.sfm_average_translations_workspace_bytes.argtypes = [_I64, _I64]
+    lib.sfm_match_pairs_workspace_bytes.restype = C.c_int64
+    lib.sfm_match_pairs_workspace_bytes.argtypes = [_I64, _I64, _I64]
     if lib.sfm_abi_version() != ABI_VERSION:
         raise NativeLibraryError(
             f"libsfm_hip.so ABI {lib.sfm_abi_version()} != expected {ABI_VERSION}; rebuild it")

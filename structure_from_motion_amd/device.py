@@ -1031,6 +1031,36 @@ def read_track_build_info(info: torch.Tensor) -> TrackBuildInfo:
     return TrackBuildInfo(*(int(v) for v in raw[:6]))
 
 
+# ------------------------------------------------------------------------------------------------------
+# descriptor matching of every image pair of a collection (csrc/sfm_match_pairs.hip): image_offset int32 [I+1] and pair_images
+# int32 [Q,2] as above, row_offset int64 [Q+1] = running sum of the first images' sizes
+# ------------------------------------------------------------------------------------------------------
+def match_pairs_options(max_distance: int = 64, ratio: Optional[float] = 0.8, cross_check: bool = True):
+    """The sfm_match_pairs_options record of these choices (``ratio=None``: no ratio test)."""
+    return _native.MatchPairsOptions(int(max_distance), int(bool(cross_check)), int(ratio is not None), 0,
+                                     0.0 if ratio is None else float(ratio))
+
+
+def match_pairs(images: int, features: int, image_offset, desc, ok, pair_images, row_offset, rows: int, max_image_features: int,
+                max_distance: int, ratio: Optional[float], cross_check: bool, partner, distance, pair_status, workspace=None):
+    """Nearest, ratio-tested and cross-checked partner of every row of every pair (``sfm_match_pairs``; ctypes: there is no
+    torch op, like the other matchers) into ``partner`` / ``distance`` int32 [rows] and ``pair_status`` int32 [Q].  Returns the
+    workspace it used: ``workspace`` when that is large enough, else a new one.  No host synchronisation."""
+    lib = _native.load()
+    Q = int(pair_images.shape[0])
+    need = int(lib.sfm_match_pairs_workspace_bytes(Q, int(rows), int(max_image_features)))
+    if need < 0:
+        raise ValueError("match_pairs: sizes out of range (at most 65535 pairs per call, rows and image sizes below 2^31)")
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty((max(need, 1),), dtype=torch.uint8, device=desc.device)
+    options = match_pairs_options(max_distance, ratio, cross_check)
+    check(lib.sfm_match_pairs(int(images), int(features), Q, int(rows), int(max_image_features), _ptr(image_offset), _ptr(desc),
+                              _ptr(ok), _ptr(pair_images), _ptr(row_offset), C.byref(options), _ptr(partner),
+                              _ptr(distance), _ptr(pair_status), _ptr(workspace), workspace.numel(), _stream()),
+          "sfm_match_pairs")
+    return workspace
+
+
 class PnPWorkspace(_PassWorkspace):
     """Pre-allocated device buffers of a PnP pass for B views x H hypotheses x N 2D-3D pairs (as RansacWorkspace)."""
 

@@ -355,3 +355,67 @@ def rotated_texture_pair(height: int, width: int, degrees: float, n: int, seed: 
         keep = (xb >= border) & (xb <= width - 1 - border) & (yb >= border) & (yb <= height - 1 - border)
         pairs = np.concatenate([pairs, np.column_stack([xa, ya, xb, yb])[keep]])
     return image_a, image_b, pairs[:n]
+
+
+def rotated_texture_views(height: int, width: int, degrees, n: int, extra: int, seed: int, noise: float = 0.01):
+    """``rotated_texture_pair``'s scene as a collection: one uint8 view of the same kind of canvas per entry of ``degrees``,
+    with ``n`` ground-truth features that every view sees and ``extra`` partnerless ones per view — what a graph matcher is
+    measured on.
+
+    The canvas and the sampling are ``rotated_texture_pair``'s: pixel q of view v samples the quantised canvas bilinearly
+    at centre + R(degrees[v]) (q - centre), plus Gaussian noise of standard deviation ``noise`` * 255, rounded and clipped
+    (every view, a view at 0 degrees included, is sampled and noisy).  The latent points are integer pixels of the
+    unrotated frame inside the disc about the image centre that stays 20 px from the borders of every view; latent point p
+    is at centre + R(-degrees[v]) (p - centre) in view v.  The partnerless features of a view are integer pixels at least
+    20 px from its borders.  Each view's features are shuffled, so an index says nothing.
+
+    Returns (images, features, ids): per view a uint8 [height, width] image, a float64 [n + extra, 2] array of (x, y) and an
+    int64 [n + extra] array with the latent point of each feature, -1 for a partnerless one."""
+    if height < 48 or width < 48:
+        raise ValueError("rotated_texture_views: the image must be at least 48 x 48")
+    if n < 0 or extra < 0:
+        raise ValueError("rotated_texture_views: n and extra must not be negative")
+    rng = np.random.default_rng(seed)
+    side = int(np.ceil(np.hypot(height, width))) + 8
+    radius, sigma = 5, 1.5
+    taps = np.exp(-0.5 * (np.arange(-radius, radius + 1) / sigma) ** 2)
+    taps /= taps.sum()
+    white = rng.standard_normal((side + 2 * radius, side + 2 * radius))
+    rows = sum(taps[k] * white[:, k:k + side] for k in range(2 * radius + 1))
+    smooth = sum(taps[k] * rows[k:k + side, :] for k in range(2 * radius + 1))
+    lo, hi = smooth.min(), smooth.max()
+    canvas = np.floor((smooth - lo) / (hi - lo) * 255.0 + 0.5)
+    oy, ox = (side - height) // 2, (side - width) // 2
+    cx, cy = (width - 1) / 2.0, (height - 1) / 2.0
+    qx, qy = np.meshgrid(np.arange(width, dtype=np.float64), np.arange(height, dtype=np.float64))
+    turns = [(np.cos(np.deg2rad(d)), np.sin(np.deg2rad(d))) for d in degrees]
+    images = []
+    for c, s in turns:
+        sx = cx + c * (qx - cx) - s * (qy - cy) + ox
+        sy = cy + s * (qx - cx) + c * (qy - cy) + oy
+        x0 = np.clip(np.floor(sx).astype(np.int64), 0, side - 2)
+        y0 = np.clip(np.floor(sy).astype(np.int64), 0, side - 2)
+        fx, fy = sx - x0, sy - y0
+        value = ((1 - fy) * ((1 - fx) * canvas[y0, x0] + fx * canvas[y0, x0 + 1])
+                 + fy * ((1 - fx) * canvas[y0 + 1, x0] + fx * canvas[y0 + 1, x0 + 1]))
+        value = value + rng.standard_normal(value.shape) * (noise * 255.0)
+        images.append(np.clip(np.floor(value + 0.5), 0, 255).astype(np.uint8))
+
+    border = 20
+    reach = min(cx, cy) - border                       # the disc every rotation keeps inside every view's margin
+    latent = np.empty((0, 2))
+    while len(latent) < n:
+        x = rng.integers(border, width - border, 4 * n).astype(np.float64)
+        y = rng.integers(border, height - border, 4 * n).astype(np.float64)
+        keep = (x - cx) ** 2 + (y - cy) ** 2 <= reach * reach
+        latent = np.concatenate([latent, np.column_stack([x, y])[keep]])
+    latent = latent[:n]
+    features, ids = [], []
+    for c, s in turns:
+        seen = np.column_stack([cx + c * (latent[:, 0] - cx) + s * (latent[:, 1] - cy),
+                                cy - s * (latent[:, 0] - cx) + c * (latent[:, 1] - cy)])
+        alone = np.column_stack([rng.integers(border, width - border, extra), rng.integers(border, height - border, extra)])
+        order = rng.permutation(n + extra)
+        features.append(np.concatenate([seen, alone.astype(np.float64)])[order])
+        ids.append(np.concatenate([np.arange(n, dtype=np.int64), np.full(extra, -1, dtype=np.int64)])[order])
+    return images, features, ids

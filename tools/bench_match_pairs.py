@@ -1,0 +1,144 @@
+"""Timing of the graph matcher beside the per-pair code it replaces, in one session.
+
+Two shapes: 32 images x 2 000 descriptors with all 496 pairs, and 64 images x 8 000 descriptors with the 8 next images of
+each (512 pairs).  Per shape, one JSON line each for
+
+  kernel        ``sfm_match_pairs`` on resident inputs, device events around the C call;
+  api           ``match_image_pairs`` from host arrays, wall clock (the upload, the read-back and the compaction included);
+  summary_loop  Q bare ``sfm_hamming_summary`` calls on resident inputs, device events around the loop (one direction per
+                pair; the ragged call scores both);
+  brute_loop    Q ``match_brute_force(features_a, features_b, BriefScore(image_a, image_b))`` calls with the ratio test and
+                the cross-check, wall clock.  ``--loop-pairs`` caps the pairs this loop and the summary loop run (0: all);
+                their totals are then scaled to Q and marked ``extrapolated``.
+
+    python tools/bench_match_pairs.py [--reps 10] [--loop-pairs 64] [--shapes small large]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from structure_from_motion_amd import _native, device  # noqa: E402
+from structure_from_motion_amd.feature_matching import brief, matching  # noqa: E402
+from structure_from_motion_amd.feature_matching.graph_matching import all_pairs, match_image_pairs  # noqa: E402
+
+SHAPES = {"small": (32, 2000, None), "large": (64, 8000, 8)}   # images, descriptors per image, neighbours (None: all pairs)
+HEIGHT, WIDTH = 1080, 1920
+
+
+def event_ms(fn, reps):
+    fn()
+    torch.cuda.synchronize()
+    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    start.record()
+    for _ in range(reps):
+        fn()
+    stop.record()
+    torch.cuda.synchronize()
+    return start.elapsed_time(stop) / reps
+
+
+def wall_ms(fn, reps):
+    fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / reps * 1e3
+
+
+def shape_pairs(images, neighbours):
+    if neighbours is None:
+        return all_pairs(images)
+    return np.array([(i, (i + k) % images) for i in range(images) for k in range(1, neighbours + 1)], dtype=np.int64)
+
+
+def run_shape(name, reps, loop_pairs):
+    I, n, neighbours = SHAPES[name]
+    rng = np.random.default_rng(0)
+    pairs = shape_pairs(I, neighbours)
+    Q = len(pairs)
+    # one textured frame and shifted crops of it, so that descriptors of different images really match
+    canvas = rng.integers(0, 256, (HEIGHT + 2 * I, WIDTH + 2 * I), dtype=np.uint8)
+    views = [np.ascontiguousarray(canvas[2 * v:2 * v + HEIGHT, 2 * v:2 * v + WIDTH]) for v in range(I)]
+    points = np.column_stack([rng.integers(80, WIDTH - 80, n), rng.integers(80, HEIGHT - 80, n)]).astype(np.float64)
+    feats = [points - 2.0 * v for v in range(I)]
+    dev = device.require_gpu()
+    lib = _native.load()
+    st = device._stream()
+    descriptors = [brief.compute_brief(image, f) for image, f in zip(views, feats)]
+    base = dict(shape=name, images=I, descriptors_per_image=n, pairs=Q)
+
+    # --- the ragged call on resident inputs
+    sizes = np.full(I, n, dtype=np.int64)
+    image_offset = device.to_device(np.arange(I + 1, dtype=np.int32) * n, torch.int32)
+    desc = device.to_device(np.concatenate([d.bits for d in descriptors]), torch.uint8)
+    ok = device.to_device(np.concatenate([d.valid for d in descriptors]).astype(np.uint8), torch.uint8)
+    pair_images = device.to_device(pairs.astype(np.int32), torch.int32)
+    row_offset = device.to_device(np.arange(Q + 1, dtype=np.int64) * n, torch.int64)
+    rows = Q * n
+    out = torch.empty((2 * rows + Q,), dtype=torch.int32, device=dev)
+    state = dict(ws=None)
+
+    def ragged():
+        state["ws"] = device.match_pairs(I, I * n, image_offset, desc, ok, pair_images, row_offset, rows, int(sizes.max()), 64,
+                                         0.8, True, out[:rows], out[rows:2 * rows], out[2 * rows:], state["ws"])
+
+    kernel_ms = event_ms(ragged, reps)
+    kept = int((out[:rows] >= 0).sum().item())
+    print(json.dumps(dict(base, what="kernel", ms=kernel_ms, ms_per_pair=kernel_ms / Q, kept=kept,
+                          workspace_mb=state["ws"].numel() / 1e6,
+                          descriptor_pairs_per_s=2.0 * Q * n * n / (kernel_ms * 1e-3))), flush=True)
+    api_ms = wall_ms(lambda: match_image_pairs(descriptors, pairs), max(reps // 3, 1))
+    print(json.dumps(dict(base, what="api", ms=api_ms, ms_per_pair=api_ms / Q)), flush=True)
+
+    # --- the per-pair code: bare summaries on resident inputs, then the public per-pair matcher from host arrays
+    sample = pairs if loop_pairs <= 0 or loop_pairs >= Q else pairs[np.linspace(0, Q - 1, loop_pairs).astype(np.int64)]
+    scale = Q / len(sample)
+    ws_bytes = int(lib.sfm_hamming_summary_workspace_bytes(n, n))
+    ws = torch.empty((max(ws_bytes // 8, 1),), dtype=torch.float64, device=dev)
+    best = torch.empty((n,), dtype=torch.float64, device=dev)
+    second = torch.empty((n,), dtype=torch.float64, device=dev)
+    arg = torch.empty((n,), dtype=torch.int32, device=dev)
+    dptr, okptr = desc.data_ptr(), ok.data_ptr()
+
+    def summaries():
+        for i, j in sample.tolist():
+            _native.check(lib.sfm_hamming_summary(dptr + 32 * n * i, okptr + n * i, n, dptr + 32 * n * j, okptr + n * j, n,
+                                                  ws.data_ptr(), ws_bytes, best.data_ptr(), arg.data_ptr(), second.data_ptr(), st),
+                          "sfm_hamming_summary")
+
+    summary_ms = event_ms(summaries, max(reps // 3, 1)) * scale
+    print(json.dumps(dict(base, what="summary_loop", ms=summary_ms, ms_per_pair=summary_ms / Q, pairs_run=len(sample),
+                          extrapolated=len(sample) != Q)), flush=True)
+
+    strategies = {matching.ValidationStrategy.RATIO_TEST, matching.ValidationStrategy.CROSSCHECK}
+
+    def brute():
+        for i, j in sample.tolist():
+            matching.match_brute_force(feats[i], feats[j], brief.BriefScore(views[i], views[j]), validation_strategies=strategies,
+                                       ratio_test_threshold=0.8)
+
+    brute_ms = wall_ms(brute, 1) * scale
+    print(json.dumps(dict(base, what="brute_loop", ms=brute_ms, ms_per_pair=brute_ms / Q, pairs_run=len(sample),
+                          extrapolated=len(sample) != Q)), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--loop-pairs", type=int, default=64)
+    ap.add_argument("--shapes", nargs="+", default=list(SHAPES), choices=list(SHAPES))
+    args = ap.parse_args()
+    for name in args.shapes:
+        run_shape(name, args.reps, args.loop_pairs)
+
+
+if __name__ == "__main__":
+    main()
