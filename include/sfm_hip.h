@@ -1008,6 +1008,55 @@ int sfm_match_pairs(int64_t images, int64_t features, int64_t pairs, int64_t row
                     const int64_t* row_offset, const sfm_match_pairs_options* options, int32_t* partner, int32_t* distance,
                     int32_t* pair_status, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- multi-scale FAST keypoints with BRIEF per pyramid level (definition: tests/keypoint_oracle.py) ---- */
+
+/* (added within ABI 15) One plane of the pixel pool of sfm_detect_keypoints: level `level` of image `image`. */
+typedef struct sfm_keypoint_plane {
+    int32_t image;    /* 0 .. images - 1 */
+    int32_t level;    /* 0 .. 11 */
+    int32_t height;   /* level 0: the image's; level l + 1: 4 * height_l / 5, at least 48 */
+    int32_t width;    /* likewise */
+    int64_t offset;   /* of the plane's first pixel in the pool, and of its first entry in both score maps */
+    int32_t quota;    /* >= 0: how many of its strongest keypoints the plane is to keep */
+    int32_t reserved; /* must be 0 */
+} sfm_keypoint_plane;
+
+/* (added within ABI 15) One keypoint candidate: plane = index into the plane table, (x, y) in that plane's pixels. */
+typedef struct sfm_keypoint_candidate {
+    int32_t plane, x, y, score;
+} sfm_keypoint_candidate;
+
+/* Bytes of workspace sfm_detect_keypoints needs for a table of `planes` planes; -1 for a negative count or more than 65535. */
+int64_t sfm_detect_keypoints_workspace_bytes(int64_t planes);
+
+/* Pyramid, FAST-9 score, non-maximum suppression, per-plane cutoff, candidate list and BRIEF descriptors of a whole image
+ * collection in one submission; all integer, byte-identical to the NumPy definition.
+ * The caller has put every image into its level-0 plane of `pool`; the call fills the planes of the levels above: pixel
+ * (x, y) of level l + 1 is ((8-fy)((8-fx) I[y0,x0] + fx I[y0,x0+1]) + fy((8-fx) I[y0+1,x0] + fx I[y0+1,x0+1]) + 32) >> 6 of level
+ * l with ux = 10 x + 1, x0 = ux >> 3, fx = ux & 7 and the same in y.  score[offset + y * width + x] is the FAST-9 score of the
+ * pixel: with centre value p, circle pixel k (radius 3, 16 pixels from (0,-3) clockwise) is brighter iff I_k > p + threshold,
+ * darker iff I_k < p - threshold; 9 cyclically contiguous brighter or darker pixels make a corner of score
+ * max(sum over the brighter of I_k - p - threshold, sum over the darker of p - I_k - threshold), every other pixel, and every
+ * pixel outside 15 <= x <= width - 16, 15 <= y <= height - 16, scores 0.  kept holds the score of every pixel that is positive,
+ * larger than its 3 x 3 neighbours before it in raster order and at least as large as those after it (outside the plane: 0), 0
+ * elsewhere.  A plane's cutoff is the largest T >= 1 with at least `quota` kept scores >= T, 1 if there are fewer, nothing
+ * for quota 0; every kept pixel at or above it becomes a candidate, in no particular slot order.  *counter receives their
+ * number; only the first `capacity` slots of candidates, desc, ok and angle_bin are written, and a caller that finds
+ * *counter > capacity calls again with that capacity.  Slot i < min(*counter, capacity) holds sfm_brief_describe's descriptor
+ * of candidate i on its plane.  The caller sorts by (score descending, y, x) and trims each plane to its quota: ties at the
+ * cutoff are the only surplus.
+ * plane_table: HOST [planes], in ascending levels, a plane above level 0 after the plane of its image one level down, planes
+ * apart in the pool in table order; pool: dev u8 [pool_bytes], pool_bytes < 2^31; offsets, boundaries, bins: as
+ * sfm_brief_describe; score, kept: dev u16 [pool_bytes]; counter: dev int32; candidates: dev [capacity], 16-byte aligned;
+ * desc: dev u8 [capacity,32], 8-byte aligned; ok, angle_bin: dev u8 [capacity]; workspace: dev, 16-byte aligned, at least
+ * sfm_detect_keypoints_workspace_bytes(planes).  planes == 0 only zeroes *counter.
+ * SFM_EINVAL before the first launch for a negative or too large size, a threshold outside 1..254, bins outside 1..64,
+ * capacity < 1, a null or misaligned pointer, a workspace too small or a table that breaks one of the rules above. */
+int sfm_detect_keypoints(const sfm_keypoint_plane* plane_table, int64_t planes, int64_t images, uint8_t* pool, int64_t pool_bytes,
+                         int threshold, const int8_t* offsets, const int64_t* boundaries, int bins, uint16_t* score,
+                         uint16_t* kept, int64_t capacity, int32_t* counter, sfm_keypoint_candidate* candidates, uint8_t* desc,
+                         uint8_t* ok, uint8_t* angle_bin, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- Harris corner detector stencils (reference lib/harris/harris_detector.py, lib/common/correlate.py) ---- */
 
 /* Zero-'same' cross-correlation with an odd square kernel (correlate.py:4-39).  image, out: dev f64

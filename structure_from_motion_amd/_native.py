@@ -189,6 +189,7 @@ SIGNATURES = {
                                _P],
     "sfm_build_tracks": [_I64, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P],
     "sfm_average_rotations": [_I64, _I64, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P],
+    "sfm_detect_keypoints": [_P, _I64, _I64, _P, _I64, C.c_int, _P, _P, C.c_int, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _I64, _P],
     "sfm_average_translations": [_I64, _I64, _P, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P],
 }
 OTHER_SYMBOLS = ["sfm_last_error", "sfm_abi_version", "sfm_score_workspace_bytes", "sfm_score_workspace_bytes_ex",
@@ -196,7 +197,7 @@ OTHER_SYMBOLS = ["sfm_last_error", "sfm_abi_version", "sfm_score_workspace_bytes
                  "sfm_tracks_workspace_bytes", "sfm_bundle_pcg_workspace_bytes", "sfm_build_tracks_workspace_bytes",
                  "sfm_bundle_pcg_workspace_bytes_ex", "sfm_hamming_summary_workspace_bytes", "sfm_pair_poses_workspace_bytes",
                  "sfm_average_rotations_workspace_bytes", "sfm_average_translations_workspace_bytes",
-                 "sfm_match_pairs_workspace_bytes"]
+                 "sfm_match_pairs_workspace_bytes", "sfm_detect_keypoints_workspace_bytes"]
 
 # the losses of both bundle adjusters, in the order of their SFM_BUNDLE_LOSS_* codes (include/sfm_hip.h)
 BUNDLE_LOSSES = ("squared", "huber", "cauchy")
@@ -261,6 +262,17 @@ class MatchPairsOptions(C.Structure):
                 ("ratio", C.c_double)]
 
 
+class KeypointPlane(C.Structure):
+    """sfm_keypoint_plane"""
+    _fields_ = [("image", C.c_int32), ("level", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("offset", C.c_int64),
+                ("quota", C.c_int32), ("reserved", C.c_int32)]
+
+
+class KeypointCandidate(C.Structure):
+    """sfm_keypoint_candidate"""
+    _fields_ = [("plane", C.c_int32), ("x", C.c_int32), ("y", C.c_int32), ("score", C.c_int32)]
+
+
 _lib = None
 
 
@@ -315,6 +327,8 @@ def load() -> C.CDLL:
     lib.sfm_average_translations_workspace_bytes.argtypes = [_I64, _I64]
     lib.sfm_match_pairs_workspace_bytes.restype = C.c_int64
     lib.sfm_match_pairs_workspace_bytes.argtypes = [_I64, _I64, _I64]
+    lib.sfm_detect_keypoints_workspace_bytes.restype = C.c_int64
+    lib.sfm_detect_keypoints_workspace_bytes.argtypes = [_I64]
     if lib.sfm_abi_version() != ABI_VERSION:
         raise NativeLibraryError(
             f"libsfm_hip.so ABI {lib.sfm_abi_version()} != expected {ABI_VERSION}; rebuild it")

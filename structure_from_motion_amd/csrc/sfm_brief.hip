@@ -2,8 +2,9 @@
 // tests/brief_oracle.py).  Everything is integer arithmetic on a uint8 image — no libm, no floating-point rounding —, so
 // both kernels are bit-identical to the NumPy definition.
 //
-//   brief_describe_kernel    one wave per feature: the 31 x 31 patch goes to LDS while the lanes accumulate the intensity
-//                            moments m10 / m01 over the radius-15 disc (integer sums: any order); lanes 0..bins-1 each test
+//   brief_describe_kernel    (its body is sfmbrief::describe_feature of sfm_brief_device.h, which the keypoint detector of
+//                            sfm_keypoints.hip calls too) one wave per feature: the 31 x 31 patch goes to LDS while the
+//                            lanes accumulate the intensity moments m10 / m01 over the radius-15 disc (integer sums: any order); lanes 0..bins-1 each test
 //                            one angle bin with two int64 cross products against the table's boundary vectors and a ballot
 //                            picks the bin; the 27 x 27 sums of 5 x 5 boxes are built separably in LDS (at most 25 * 255 =
 //                            6375: 16 bits); lane l evaluates tests l, l + 64, l + 128, l + 192 of the bin's pattern and four
@@ -18,6 +19,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "sfm_brief_device.h"
 #include "sfm_common.h"
 #include "sfm_match_summary.h"
 
@@ -27,96 +29,15 @@ using sfmhost::check_launch;
 using sfmhost::fail;
 using sfmhost::grid_for;
 
-constexpr int kPatchRadius = 15;                    // orientation disc and patch half-width
-constexpr int kPatch = 2 * kPatchRadius + 1;        // 31
-constexpr int kBoxSide = 5;                         // a sample is the sum of a 5 x 5 box
-constexpr int kBox = kPatch - kBoxSide + 1;         // 27 box centres per axis: offsets -13 .. 13
-constexpr int kReach = kBox / 2;                    // 13
-constexpr int kTests = 256;
-constexpr int kWords = kTests / 64;                 // descriptor: 4 x 64 bits = 32 bytes
-static_assert(kTests == kWords * kWave, "one ballot per descriptor word");
+using sfmbrief::kWords;
 
 __global__ __launch_bounds__(kWave) void brief_describe_kernel(
     const uint8_t* __restrict__ image, int64_t height, int64_t width, const double* __restrict__ feats,
     const int32_t* __restrict__ offsets, const long long* __restrict__ boundaries, int bins,
     unsigned long long* __restrict__ desc, uint8_t* __restrict__ ok, uint8_t* __restrict__ angle_bin) {
-    __shared__ uint8_t s_patch[kPatch * kPatch];
-    __shared__ uint16_t s_rows[kPatch * kBox];      // horizontal 5-sums
-    __shared__ uint16_t s_box[kBox * kBox];
-    const int lane = threadIdx.x;
     const int64_t f = blockIdx.x;
-    const double x = feats[2 * f], y = feats[2 * f + 1];
-    const double xc = floor(x + 0.5), yc = floor(y + 0.5);
-    // block-uniform.  NaN fails every comparison; the range test also bounds the int conversion below
-    const bool valid = xc >= (double)kPatchRadius && xc <= (double)(width - kPatchRadius - 1) &&
-                       yc >= (double)kPatchRadius && yc <= (double)(height - kPatchRadius - 1);
-    if (!valid) {
-        if (lane < kWords) desc[f * kWords + lane] = 0ull;
-        if (lane == 0) {
-            ok[f] = 0;
-            angle_bin[f] = 0;
-        }
-        return;
-    }
-    const int64_t x0 = (int64_t)xc - kPatchRadius, y0 = (int64_t)yc - kPatchRadius;
-    int m10 = 0, m01 = 0;                           // |m| <= 709 pixels * 15 * 255
-    for (int idx = lane; idx < kPatch * kPatch; idx += kWave) {
-        const int r = idx / kPatch, c = idx - r * kPatch;
-        const int p = image[(y0 + r) * width + (x0 + c)];
-        s_patch[idx] = (uint8_t)p;
-        const int dx = c - kPatchRadius, dy = r - kPatchRadius;
-        if (dx * dx + dy * dy <= kPatchRadius * kPatchRadius) {
-            m10 += dx * p;
-            m01 += dy * p;
-        }
-    }
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) {
-        m10 += __shfl_xor(m10, off, kWave);
-        m01 += __shfl_xor(m01, off, kWave);
-    }
-    // bin b: cross(B[b-1], m) >= 0 and cross(B[b], m) < 0 — a 12 degree wedge, exactly one for m != 0, none for m = 0
-    bool hit = false;
-    if (lane < bins) {
-        const int prev = lane == 0 ? bins - 1 : lane - 1;
-        const long long px = boundaries[2 * prev], py = boundaries[2 * prev + 1];
-        const long long qx = boundaries[2 * lane], qy = boundaries[2 * lane + 1];
-        hit = (px * m01 - py * m10 >= 0) && (qx * m01 - qy * m10 < 0);
-    }
-    const unsigned long long hits = __ballot(hit);
-    const int bin = hits ? __ffsll((long long)hits) - 1 : 0;
-    __syncthreads();
-    for (int idx = lane; idx < kPatch * kBox; idx += kWave) {
-        const int r = idx / kBox, c = idx - r * kBox;
-        int s = 0;
-#pragma unroll
-        for (int k = 0; k < kBoxSide; ++k) s += s_patch[r * kPatch + c + k];
-        s_rows[idx] = (uint16_t)s;
-    }
-    __syncthreads();
-    for (int idx = lane; idx < kBox * kBox; idx += kWave) {
-        int s = 0;
-#pragma unroll
-        for (int k = 0; k < kBoxSide; ++k) s += s_rows[idx + k * kBox];
-        s_box[idx] = (uint16_t)s;
-    }
-    __syncthreads();
-    auto coordinate = [](int32_t packed, int byte) {   // int8 of the packed (ax, ay, bx, by), held inside the box array
-        const int v = (int)(int8_t)(packed >> (8 * byte));
-        return min(max(v, -kReach), kReach) + kReach;
-    };
-#pragma unroll
-    for (int k = 0; k < kWords; ++k) {
-        const int32_t o = offsets[(int64_t)bin * kTests + k * kWave + lane];
-        const int a = s_box[coordinate(o, 1) * kBox + coordinate(o, 0)];
-        const int b = s_box[coordinate(o, 3) * kBox + coordinate(o, 2)];
-        const unsigned long long word = __ballot(a < b);
-        if (lane == 0) desc[f * kWords + k] = word;
-    }
-    if (lane == 0) {
-        ok[f] = 1;
-        angle_bin[f] = (uint8_t)bin;
-    }
+    sfmbrief::describe_feature(image, height, width, feats[2 * f], feats[2 * f + 1], offsets, boundaries, bins,
+                               desc + f * kWords, ok + f, angle_bin + f);
 }
 
 constexpr int kHamRows = 256;                       // A rows per block, one per lane

@@ -1061,6 +1061,39 @@ def match_pairs(images: int, features: int, image_offset, desc, ok, pair_images,
     return workspace
 
 
+# ------------------------------------------------------------------------------------------------------
+# multi-scale FAST keypoints with BRIEF per pyramid level (csrc/sfm_keypoints.hip)
+# ------------------------------------------------------------------------------------------------------
+def keypoint_plane_table(rows):
+    """The sfm_keypoint_plane array (HOST memory) of ``rows`` = (image, level, height, width, offset, quota) per plane."""
+    table = (_native.KeypointPlane * max(len(rows), 1))()
+    for entry, (image, level, height, width, offset, quota) in zip(table, rows):
+        entry.image, entry.level, entry.height, entry.width = int(image), int(level), int(height), int(width)
+        entry.offset, entry.quota, entry.reserved = int(offset), int(quota), 0
+    return table
+
+
+def detect_keypoints(table, planes: int, images: int, pool, threshold: int, offsets, boundaries, bins: int, score, kept,
+                     capacity: int, counter, candidates, desc, ok, angle_bin, workspace=None):
+    """Pyramid, FAST score, suppression, cutoff, candidates and descriptors of every plane of ``table`` in one submission
+    (``sfm_detect_keypoints``; ctypes: there is no torch op, like the matchers).  ``pool`` uint8 holds the level-0 planes and
+    receives the others, ``score`` / ``kept`` uint16 of the pool's length receive both maps, ``counter`` int32 [1] the number of
+    candidates (it may exceed ``capacity``), ``candidates`` int32 [capacity, 4] = (plane, x, y, score), ``desc`` uint8
+    [capacity, 32], ``ok`` / ``angle_bin`` uint8 [capacity].  Returns the workspace it used: ``workspace`` when that is large
+    enough, else a new one.  No host synchronisation beyond the upload of the table."""
+    lib = _native.load()
+    need = int(lib.sfm_detect_keypoints_workspace_bytes(int(planes)))
+    if need < 0:
+        raise ValueError("detect_keypoints: at most 65535 planes per call")
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty((max(need, 1),), dtype=torch.uint8, device=pool.device)
+    check(lib.sfm_detect_keypoints(table, int(planes), int(images), _ptr(pool), pool.numel(), int(threshold), _ptr(offsets),
+                                   _ptr(boundaries), int(bins), _ptr(score), _ptr(kept), int(capacity), _ptr(counter),
+                                   _ptr(candidates), _ptr(desc), _ptr(ok), _ptr(angle_bin), _ptr(workspace), workspace.numel(),
+                                   _stream()), "sfm_detect_keypoints")
+    return workspace
+
+
 class PnPWorkspace(_PassWorkspace):
     """Pre-allocated device buffers of a PnP pass for B views x H hypotheses x N 2D-3D pairs (as RansacWorkspace)."""
 

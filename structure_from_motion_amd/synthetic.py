@@ -419,3 +419,58 @@ def rotated_texture_views(height: int, width: int, degrees, n: int, extra: int, 
         features.append(np.concatenate([seen, alone.astype(np.float64)])[order])
         ids.append(np.concatenate([np.arange(n, dtype=np.int64), np.full(extra, -1, dtype=np.int64)])[order])
     return images, features, ids
+
+
+def similarity_texture_views(height: int, width: int, degrees, scales, seed: int, noise: float = 0.01):
+    """Views of one multi-scale random texture that differ by a rotation AND a scale about the image centre — two photographs
+    of one object taken from different distances — what a multi-scale detector is measured on.
+
+    The canvas is the sum of four unit-variance Gaussian-smoothed white noises (sigma = 1.5, 3, 6 and 12 px: structure at every
+    scale a pyramid looks at), stretched to 0 .. 255 and quantised, and large enough for the largest scale at every rotation.
+    Pixel q of view v looks at canvas point C + scales[v] R(degrees[v]) (q - c), c the image centre and C the canvas centre: it
+    is the mean of k x k bilinear samples spread evenly over the pixel's footprint, k = ceil(scales[v]), plus Gaussian noise of
+    standard deviation ``noise`` * 255, rounded and clipped as in ``rotated_texture_views``.
+
+    Returns (images, to_canvas): per view a uint8 [height, width] image and a float64 [2, 3] matrix A with
+    canvas (x, y) = A @ (x, y, 1) for a pixel (x, y) of that view."""
+    degrees, scales = [float(d) for d in degrees], [float(s) for s in scales]
+    if height < 48 or width < 48:
+        raise ValueError("similarity_texture_views: the image must be at least 48 x 48")
+    if len(degrees) != len(scales) or not all(np.isfinite(s) and s > 0 for s in scales):
+        raise ValueError("similarity_texture_views: one positive scale per rotation")
+    rng = np.random.default_rng(seed)
+    side = int(np.ceil(max(scales, default=1.0) * np.hypot(height, width))) + 8
+    smooth = np.zeros((side, side))
+    for sigma in (1.5, 3.0, 6.0, 12.0):
+        radius = int(np.ceil(3 * sigma))
+        taps = np.exp(-0.5 * (np.arange(-radius, radius + 1) / sigma) ** 2)
+        taps /= taps.sum()
+        white = rng.standard_normal((side + 2 * radius, side + 2 * radius))
+        rows = sum(taps[k] * white[:, k:k + side] for k in range(2 * radius + 1))
+        band = sum(taps[k] * rows[k:k + side, :] for k in range(2 * radius + 1))
+        smooth += band / np.sum(taps * taps)            # the standard deviation of the separable filter's output
+    lo, hi = smooth.min(), smooth.max()
+    canvas = np.floor((smooth - lo) / (hi - lo) * 255.0 + 0.5)
+    C = (side - 1) / 2.0
+    cx, cy = (width - 1) / 2.0, (height - 1) / 2.0
+    qx, qy = np.meshgrid(np.arange(width, dtype=np.float64), np.arange(height, dtype=np.float64))
+    images, to_canvas = [], []
+    for d, scale in zip(degrees, scales):
+        c, s = scale * np.cos(np.deg2rad(d)), scale * np.sin(np.deg2rad(d))
+        A = np.array([[c, -s, C - c * cx + s * cy], [s, c, C - s * cx - c * cy]])
+        k = int(np.ceil(scale))
+        value = np.zeros((height, width))
+        for iy in range(k):
+            for ix in range(k):
+                px, py = qx + ((ix + 0.5) / k - 0.5), qy + ((iy + 0.5) / k - 0.5)
+                sx = A[0, 0] * px + A[0, 1] * py + A[0, 2]
+                sy = A[1, 0] * px + A[1, 1] * py + A[1, 2]
+                x0 = np.clip(np.floor(sx).astype(np.int64), 0, side - 2)
+                y0 = np.clip(np.floor(sy).astype(np.int64), 0, side - 2)
+                fx, fy = sx - x0, sy - y0
+                value += ((1 - fy) * ((1 - fx) * canvas[y0, x0] + fx * canvas[y0, x0 + 1])
+                          + fy * ((1 - fx) * canvas[y0 + 1, x0] + fx * canvas[y0 + 1, x0 + 1]))
+        value = value / (k * k) + rng.standard_normal(value.shape) * (noise * 255.0)
+        images.append(np.clip(np.floor(value + 0.5), 0, 255).astype(np.uint8))
+        to_canvas.append(A)
+    return images, to_canvas
