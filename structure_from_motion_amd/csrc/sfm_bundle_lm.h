@@ -2,6 +2,7 @@
 // 64 cameras) and sfm_bundle_pcg.hip (conjugate gradients, any camera count).  Here: the LM state and the workspace
 // arrays both use, the linearisation, the damped point blocks, the start, the accept / reject decision, the commit and
 // the info record.  Each adjuster adds only the solve of its damped reduced camera system, which ends in finish_step.
+// The LM constants, the step rules and the small SPD solves are those of every LM loop of the library: csrc/sfm_lm.h.
 //
 // Every launch reads the LM state in the workspace first and returns at once after a stop.  Cameras are named by slots:
 // slot[c] is camera c's index among the free cameras (-1 for a fixed one), freec[s] the camera of slot s.  The gauge's
@@ -18,6 +19,7 @@
 #include <stdint.h>
 
 #include "sfm_common.h"
+#include "sfm_lm.h"
 #include "sfm_loss.h"
 #include "sfm_math.h"
 #include "sfm_obs_order.h"
@@ -29,10 +31,6 @@ using sfmpnp::PnPCamera;
 
 constexpr int kThreads = 256;      // point-parallel and per-camera kernels
 constexpr int kLdsCameras = 64;    // linearize_kernel<true> stages this many poses in LDS (the dense path's limit)
-constexpr double kLambda0 = 1e-3;
-constexpr double kLambdaMax = 1e16;
-constexpr double kMinDecrease = 1e-12;
-constexpr double kMinStep = 1e-12;
 
 // The LM state: written by one thread of the one-workgroup kernels, read by every launch after it.
 struct State {
@@ -300,8 +298,8 @@ __global__ __launch_bounds__(kThreads) void camera_kernel(Obs obs, PnPCamera cam
 // ------------------------------------------------------------------------------------------------------------------------
 // One LM trial step: the damped point blocks before the solve; the decision and the commit after the trial.
 // ------------------------------------------------------------------------------------------------------------------------
-// Thread per moving point: V_p* = V_p + lambda diag V_p, its 3 x 3 Cholesky, and V_p*^-1 (upper 6).  A pivot <= 0 or not
-// finite marks the step as failed.
+// Thread per moving point: V_p* = V_p + lambda diag V_p, its 3 x 3 Cholesky (sfm_lm.h), and V_p*^-1 (upper 6).  A pivot
+// <= 0 or not finite marks the step as failed.
 __global__ __launch_bounds__(kThreads) void point_kernel(int P, Lm w) {
     if (w.st->stop) return;
     const int p = blockIdx.x * kThreads + threadIdx.x;
@@ -311,44 +309,17 @@ __global__ __launch_bounds__(kThreads) void point_kernel(int P, Lm w) {
     sym3(w.V + 6 * (int64_t)p, A);
 #pragma unroll
     for (int i = 0; i < 3; ++i) A[i][i] = A[i][i] + lambda * A[i][i];
-    // L L^T = A
-    double L[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
-    bool ok = true;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        double s = A[j][j];
-#pragma unroll
-        for (int k = 0; k < j; ++k) s -= L[j][k] * L[j][k];
-        ok = ok && s > 0.0 && isfinite(s);
-        L[j][j] = sqrt(fmax(s, 0.0));
-#pragma unroll
-        for (int i = j + 1; i < 3; ++i) {
-            double x = A[i][j];
-#pragma unroll
-            for (int k = 0; k < j; ++k) x -= L[i][k] * L[j][k];
-            L[i][j] = x / L[j][j];
-        }
-    }
-    if (!ok) {
+    double L[3][3], inv[3][3];
+    if (!factor<3>(A, 0.0, L)) {
         w.st->fail = 1;
         return;
     }
-    // A^-1 = L^-T L^-1: columns of L^-1 by forward substitution, then the products
-    double Li[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-#pragma unroll
-        for (int i = c; i < 3; ++i) {
-            double x = i == c ? 1.0 : 0.0;
-#pragma unroll
-            for (int k = c; k < i; ++k) x -= L[i][k] * Li[k][c];
-            Li[i][c] = x / L[i][i];
-        }
+    inverse<3>(L, inv);
     double* out = w.Vi + 6 * (int64_t)p;
 #pragma unroll
     for (int i = 0; i < 3; ++i)
 #pragma unroll
-        for (int j = i; j < 3; ++j) out[upper3(i, j)] = (Li[0][i] * Li[0][j] + Li[1][i] * Li[1][j]) + Li[2][i] * Li[2][j];
+        for (int j = i; j < 3; ++j) out[upper3(i, j)] = inv[i][j];
 }
 
 // After the first linearisation: an index out of range stops the call; else the starting cost, the bad-start status and
@@ -404,19 +375,19 @@ __global__ __launch_bounds__(kBlock) void decide_kernel(int blocks, int a, int m
     double lambda = st->lambda;
     bool done = false;
     if (!step_ok) {
-        lambda *= 10.0;
+        lambda = more_damping(lambda);
     } else {
         const double dn = total[1] + st->dn_c, xn = total[2] + st->xn_c;
         const double c_new = total[0], c_old = st->cost;
-        if (sqrt(dn) <= kMinStep * (1.0 + sqrt(xn))) {
+        if (small_step(sqrt(dn), sqrt(xn))) {   // here and not before the trial: the points' share is known only now
             done = true;
-        } else if (isfinite(c_new) && c_new < c_old) {
-            done = c_old - c_new < kMinDecrease * c_old;
+        } else if (improved(c_new, c_old)) {
+            done = converged(c_old, c_new);
             st->cost = c_new;
             st->accepted += 1;
             st->commit = 1;
             st->need_lin = 1;
-            lambda /= 10.0;
+            lambda = less_damping(lambda);
             if (a >= 0) {
                 double ca[3];
                 sfmpnp::centre(w.tpose + 12 * (int64_t)a, ca);
@@ -424,11 +395,11 @@ __global__ __launch_bounds__(kBlock) void decide_kernel(int blocks, int a, int m
                 st->scale = st->dist / sqrt((d0 * d0 + d1 * d1) + d2 * d2);
             }
         } else {
-            lambda *= 10.0;
+            lambda = more_damping(lambda);
         }
     }
     st->lambda = lambda;
-    st->stop = done || st->steps >= max_steps || lambda > kLambdaMax;
+    st->stop = done || exhausted(st->steps, max_steps, lambda);
 }
 
 // An accepted trial becomes the current estimate; with one fixed camera (a >= 0), scaled about its centre by st->scale.

@@ -142,7 +142,8 @@ SFM_DEVICE void damped_u(const double* u, double lambda, double (&A)[6][6]) {
 }
 
 // Block per free camera (slot s): M_c = U*_c - sum over its observations of moving points of W V_p*^-1 W^T, b_c = -g_c +
-// sum W V_p*^-1 g_p, and M_c^-1 (full 36) from its Cholesky factor.  A pivot <= 0 or not finite marks the step as failed.
+// sum W V_p*^-1 g_p, and M_c^-1 (full 36) from its Cholesky factor (sfm_lm.h).  A pivot <= 0 or not finite marks the step
+// as failed.
 template <bool kRobust>
 __global__ __launch_bounds__(kThreads) void pcg_precond_kernel(PnPCamera cam, const double* __restrict__ poses,
                                                                const double* __restrict__ points, Ws w) {
@@ -191,37 +192,17 @@ __global__ __launch_bounds__(kThreads) void pcg_precond_kernel(PnPCamera cam, co
         for (int j = i; j < 6; ++j) A[i][j] = A[j][i] = A[i][j] - total[upper6(i, j)];
 #pragma unroll
     for (int i = 0; i < 6; ++i) w.b[6 * (int64_t)s + i] = -w.lm.gc[6 * (int64_t)ch.c + i] + total[21 + i];
-    double L[6][6] = {};
-    bool ok = true;
-    for (int j = 0; j < 6; ++j) {
-        double d = A[j][j];
-        for (int k = 0; k < j; ++k) d -= L[j][k] * L[j][k];
-        ok = ok && d > 0.0 && isfinite(d);
-        L[j][j] = sqrt(fmax(d, 0.0));
-        for (int i = j + 1; i < 6; ++i) {
-            double x = A[i][j];
-            for (int k = 0; k < j; ++k) x -= L[i][k] * L[j][k];
-            L[i][j] = x / L[j][j];
-        }
-    }
-    if (!ok) {
+    double L[6][6], inv[6][6];
+    if (!sfmlm::factor<6>(A, 0.0, L)) {
         w.st->lm.fail = 1;
         return;
     }
-    double Li[6][6] = {};
-    for (int c = 0; c < 6; ++c)
-        for (int i = c; i < 6; ++i) {
-            double x = i == c ? 1.0 : 0.0;
-            for (int k = c; k < i; ++k) x -= L[i][k] * Li[k][c];
-            Li[i][c] = x / L[i][i];
-        }
+    sfmlm::inverse<6>(L, inv);
     double* out = w.Minv + 36 * (int64_t)s;
+#pragma unroll
     for (int i = 0; i < 6; ++i)
-        for (int j = 0; j < 6; ++j) {
-            double v = 0.0;
-            for (int k = max(i, j); k < 6; ++k) v += Li[k][i] * Li[k][j];
-            out[6 * i + j] = v;
-        }
+#pragma unroll
+        for (int j = 0; j < 6; ++j) out[6 * i + j] = inv[i][j];
 }
 
 // z_s = M_s^-1 r_s

@@ -352,4 +352,10 @@ SFM_DEVICE double aggregate_error(int aggregation, int count, double sum1, doubl
     }
 }
 
+// The accept rule of the two winner refinements (sfm_refine.hip, sfm_pnp_refine.hip), whose errors are aggregate_error
+// with sample_size = 0: more inliers, or as many and a lower aggregated error.  A NaN error never wins.
+SFM_DEVICE bool refit_wins(double count, double error, double best_count, double best_error) {
+    return count > best_count || (count == best_count && error < best_error);
+}
+
 }  // namespace sfmfit

@@ -1,6 +1,7 @@
 // The PnP camera and squared reprojection error shared by the PnP kernels (sfm_pnp.hip) and the refinement of the
 // winner (sfm_pnp_refine.hip): both must compute the same e for the same item bit for bit.  Also the pose model's
-// Jacobian rows, update and camera centre, shared by the refinement and the bundle adjusters (sfm_bundle_lm.h).
+// Jacobian rows, update and camera centre, shared by the refinement, the bundle adjusters (sfm_bundle_lm.h) and the
+// per-point refinement of sfm_tracks.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>

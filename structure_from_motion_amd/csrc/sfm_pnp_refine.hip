@@ -1,6 +1,7 @@
 // Nonlinear refinement of a PnP winner on its inliers: Levenberg-Marquardt on the sum of the PnP scorer's squared
 // reprojection errors, then a re-score of every item and the accept rule of sfm_refine_inliers (more inliers, or as
-// many and a lower aggregated error).  The PnP counterpart of sfm_refine.hip; off unless asked for.
+// many and a lower aggregated error: sfmfit::refit_wins).  The PnP counterpart of sfm_refine.hip; off unless asked for.
+// The LM constants, the step rules and the 6 x 6 Cholesky solve are those of sfm_lm.h.
 //
 // One 512-thread block per view runs the whole loop.  The pass over the inliers is latency-bound at one block per view
 // (50 000 items x 40 B are L2-resident), so eight waves keep twice the loads of four in flight; the 28-value reduction
@@ -13,6 +14,8 @@
 #include <stdint.h>
 
 #include "sfm_common.h"
+#include "sfm_fit.h"
+#include "sfm_lm.h"
 #include "sfm_math.h"
 #include "sfm_pnp.h"
 
@@ -32,25 +35,9 @@ constexpr int kThreads = 512;
 constexpr int kWaves = kThreads / kWave;
 constexpr int kSums = 28;  // H upper triangle (21, row-major) | g (6) | C
 constexpr int kMinItems = 6;
-constexpr double kLambda0 = 1e-3;
-constexpr double kLambdaMax = 1e16;
-constexpr double kMinDecrease = 1e-12;  // stop when an accepted step lowers C by less than this fraction of C
-constexpr double kMinStep = 1e-12;      // stop when |delta| <= kMinStep * (1 + |t|)
-// The undamped H of a round's start point must have full rank: every Cholesky pivot above this fraction of its diagonal
-// entry.  Inliers that pin fewer than six degrees of freedom (all at one 3-D point, say) stop the round.
-constexpr double kRankFloor = 1e-10;
 constexpr int kStop = 0, kEvaluate = 1;
 
 static_assert(sizeof(sfm_pnp_refine_info) == 24, "sfm_pnp_refine_info layout is part of the ABI");
-
-SFM_DEVICE double aggregate_total(int aggregation, double count, double sum1, double sum2) {
-    switch (aggregation) {
-        case SFM_AGG_SUM: return sum1;
-        case SFM_AGG_SQUARE: return sum2;
-        case SFM_AGG_MEAN: return sum1 / count;
-        default: return sqrt(sum2 / count);
-    }
-}
 
 // This thread's share of C, H and g over the items with a non-zero mask, at model m.  e is pnp_score's value; an item
 // behind the camera (c2 <= 0) makes C infinite and adds nothing to H or g.  J: the pose rows of sfmpnp::jacobians.
@@ -75,55 +62,26 @@ SFM_DEVICE void accumulate(const double* __restrict__ P, int n, const uint8_t* _
     }
 }
 
-SFM_DEVICE int upper(int r, int c) { return r * 6 - r * (r - 1) / 2 + (c - r); }  // r <= c
-
-// Cholesky factor L of H + lambda diag(H), H the upper triangle sys[0..21).  False when a pivot is not above rel times
-// its diagonal entry (rel = 0: not positive), or not a number.
-SFM_DEVICE bool cholesky6(const double* sys, double lambda, double rel, double (&L)[6][6]) {
-    bool ok = true;
+// Cholesky factor L of H + lambda diag(H), H the upper triangle sys[0..21) in row-major order.  False when a pivot is
+// not above rel times its diagonal entry (rel = 0: not positive), or not a number.
+SFM_DEVICE bool damped_factor(const double* sys, double lambda, double rel, double (&L)[6][6]) {
+    double A[6][6];
+    int idx = 0;
 #pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        const double hjj = sys[upper(j, j)];
-        const double mjj = hjj + lambda * hjj;
-        double s = mjj;
+    for (int r = 0; r < 6; ++r)
 #pragma unroll
-        for (int c = 0; c < j; ++c) s -= L[j][c] * L[j][c];
-        ok = ok && (s > rel * mjj);
-        const double d = sqrt(fmax(s, 0.0));
-        L[j][j] = d;
+        for (int c = r; c < 6; ++c) A[r][c] = A[c][r] = sys[idx++];
 #pragma unroll
-        for (int i = j + 1; i < 6; ++i) {
-            double x = sys[upper(j, i)];
-#pragma unroll
-            for (int c = 0; c < j; ++c) x -= L[i][c] * L[j][c];
-            L[i][j] = x / d;
-        }
-    }
-    return ok;
+    for (int i = 0; i < 6; ++i) A[i][i] = A[i][i] + lambda * A[i][i];
+    return sfmlm::factor<6>(A, rel, L);
 }
 
 // Solves (H + lambda diag H) delta = -g.  False when the factorisation fails or delta is not finite.
-SFM_DEVICE bool solve6(const double* sys, double lambda, double (&delta)[6]) {
+SFM_DEVICE bool damped_solve(const double* sys, double lambda, double (&delta)[6]) {
     double L[6][6];
-    if (!cholesky6(sys, lambda, 0.0, L)) return false;
-    double y[6];
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        double x = -sys[21 + j];
-#pragma unroll
-        for (int c = 0; c < j; ++c) x -= L[j][c] * y[c];
-        y[j] = x / L[j][j];
-    }
-    bool finite = true;
-#pragma unroll
-    for (int j = 5; j >= 0; --j) {
-        double x = y[j];
-#pragma unroll
-        for (int r = j + 1; r < 6; ++r) x -= L[r][j] * delta[r];
-        delta[j] = x / L[j][j];
-        finite = finite && isfinite(delta[j]);
-    }
-    return finite;
+    if (!damped_factor(sys, lambda, 0.0, L)) return false;
+    const double b[6] = {-sys[21], -sys[22], -sys[23], -sys[24], -sys[25], -sys[26]};
+    return sfmlm::solve<6>(L, b, delta);
 }
 
 __global__ __launch_bounds__(kThreads) void pnp_refine_kernel(
@@ -172,30 +130,30 @@ __global__ __launch_bounds__(kThreads) void pnp_refine_kernel(
         for (int k = 0; k < 12; ++k) m[k] = trial[k];
         accumulate(P, n, mout, m, cam, a);
         block_sum<kSums, kThreads>(a, part, total);
-        double lambda = kLambda0;
+        double lambda = sfmlm::kLambda0;
         bool stop = false;
         int round_steps = 0;
         if (tid == 0) {
 #pragma unroll
             for (int k = 0; k < kSums; ++k) sys[k] = total[k];
             double L[6][6];
-            stop = !cholesky6(sys, 0.0, kRankFloor, L);
+            stop = !damped_factor(sys, 0.0, sfmlm::kRankFloor, L);
         }
         // LM: thread 0 plans the next trial (or stops), everybody evaluates it, thread 0 accepts or rejects it
         for (;;) {
             if (tid == 0) {
                 int next = kStop;
-                while (!stop && round_steps < max_steps && !(lambda > kLambdaMax)) {
+                while (!stop && !sfmlm::exhausted(round_steps, max_steps, lambda)) {
                     ++round_steps;
                     double delta[6];
-                    if (!solve6(sys, lambda, delta)) {
-                        lambda *= 10.0;
+                    if (!damped_solve(sys, lambda, delta)) {
+                        lambda = sfmlm::more_damping(lambda);
                         continue;
                     }
                     const double dn = sqrt(((delta[0] * delta[0] + delta[1] * delta[1]) + (delta[2] * delta[2] + delta[3] * delta[3])) +
                                            (delta[4] * delta[4] + delta[5] * delta[5]));
                     const double tn = sqrt((pose[9] * pose[9] + pose[10] * pose[10]) + pose[11] * pose[11]);
-                    if (dn <= kMinStep * (1.0 + tn)) break;
+                    if (sfmlm::small_step(dn, tn)) break;
                     apply_step(pose, delta, trial);
                     next = kEvaluate;
                     break;
@@ -210,15 +168,15 @@ __global__ __launch_bounds__(kThreads) void pnp_refine_kernel(
             block_sum<kSums, kThreads>(a, part, total);
             if (tid == 0) {
                 const double c_new = total[kSums - 1], c_old = sys[kSums - 1];
-                if (isfinite(c_new) && c_new < c_old) {
+                if (sfmlm::improved(c_new, c_old)) {
 #pragma unroll
                     for (int k = 0; k < kSums; ++k) sys[k] = total[k];
 #pragma unroll
                     for (int k = 0; k < 12; ++k) pose[k] = trial[k];
-                    lambda /= 10.0;
-                    stop = c_old - c_new < kMinDecrease * c_old;
+                    lambda = sfmlm::less_damping(lambda);
+                    stop = sfmlm::converged(c_old, c_new);
                 } else {
-                    lambda *= 10.0;
+                    lambda = sfmlm::more_damping(lambda);
                 }
             }
         }
@@ -238,9 +196,8 @@ __global__ __launch_bounds__(kThreads) void pnp_refine_kernel(
         }
         block_sum<3, kThreads>(c, part, total);
         const double cnt = total[0];
-        const double err = aggregate_total(aggregation, cnt, total[1], total[2]);
-        const bool better = cnt > best_cnt || (cnt == best_cnt && err < best_err);  // NaN error never wins
-        if (!better) break;
+        const double err = sfmfit::aggregate_error(aggregation, (int)cnt, total[1], total[2], 0);
+        if (!sfmfit::refit_wins(cnt, err, best_cnt, best_err)) break;
         for (int i = tid; i < n; i += kThreads) {
             const double* q = P + (int64_t)i * kPnPFields;
             mout[i] = pnp_score(m, cam, q[0], q[1], q[2], q[3], q[4]) <= thr ? 1 : 0;

@@ -19,6 +19,7 @@
 
 namespace {
 
+using sfm::block_sum;
 using sfmhost::check_launch;
 using sfmhost::fail;
 
@@ -27,40 +28,12 @@ constexpr int kWaves = kThreads / kWave;
 
 static_assert(sizeof(sfm_refine_info) == 16, "sfm_refine_info layout is part of the ABI");
 
-// Block-wide sums of K doubles per thread in a fixed order: butterfly inside each wave, then the wave
-// partials added in wave order by one thread per value.  Result broadcast through `total`.
-template <int K>
-SFM_DEVICE void block_sum(double (&v)[K], double (*part)[48], double* total) {
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const double s = sfm::wave_sum(v[k]);
-        if (lane == 0) part[wave][k] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < K) {
-        double acc = part[0][threadIdx.x];
-        for (int w = 1; w < kWaves; ++w) acc += part[w][threadIdx.x];
-        total[threadIdx.x] = acc;
-    }
-    __syncthreads();
-}
-
-SFM_DEVICE double aggregate_total(int aggregation, double count, double sum1, double sum2) {
-    switch (aggregation) {
-        case SFM_AGG_SUM: return sum1;
-        case SFM_AGG_SQUARE: return sum2;
-        case SFM_AGG_MEAN: return sum1 / count;
-        default: return sqrt(sum2 / count);
-    }
-}
-
 __global__ __launch_bounds__(kThreads) void refine_kernel(
     const Corr* __restrict__ corr, int n, const double* __restrict__ E_in, const uint8_t* __restrict__ mask_in,
     const double* __restrict__ err_in, double thr, int aggregation, int iterations, double* __restrict__ E_out,
     uint8_t* __restrict__ mask_out, sfm_refine_info* __restrict__ info) {
-    __shared__ double part[kWaves][48];
-    __shared__ double total[48];
+    __shared__ double part[kWaves * 45];
+    __shared__ double total[45];
     __shared__ double e_new[9];
     __shared__ int flag_new;
 
@@ -77,7 +50,7 @@ __global__ __launch_bounds__(kThreads) void refine_kernel(
         mout[i] = m;
         v1[0] += (double)m;
     }
-    block_sum<1>(v1, part, total);
+    block_sum<1, kThreads>(v1, part, total);
     double best_cnt = total[0];
     double best_err = err_in[b];
     if (tid < 9) E_out[b * 9 + tid] = E_in[b * 9 + tid];
@@ -93,7 +66,7 @@ __global__ __launch_bounds__(kThreads) void refine_kernel(
                 s[0] += p.xa; s[1] += p.ya; s[2] += p.xb; s[3] += p.yb;
             }
         }
-        block_sum<4>(s, part, total);
+        block_sum<4, kThreads>(s, part, total);
         sfmfit::Hartley t1, t2;
         t1.cx = total[0] / best_cnt; t1.cy = total[1] / best_cnt;
         t2.cx = total[2] / best_cnt; t2.cy = total[3] / best_cnt;
@@ -108,7 +81,7 @@ __global__ __launch_bounds__(kThreads) void refine_kernel(
                 d[1] += sqrt(bx * bx + by * by);
             }
         }
-        block_sum<2>(d, part, total);
+        block_sum<2, kThreads>(d, part, total);
         t1.scale = sqrt(2.0) / (total[0] / best_cnt);
         t2.scale = sqrt(2.0) / (total[1] / best_cnt);
         // pass C: upper triangle of Y^T Y over the normalised inliers (eight_point.py:363-393)
@@ -128,7 +101,7 @@ __global__ __launch_bounds__(kThreads) void refine_kernel(
                     for (int q = r; q < 9; ++q) a[idx++] += col[r] * col[q];
             }
         }
-        block_sum<45>(a, part, total);
+        block_sum<45, kThreads>(a, part, total);
         // eigen-solve + rank 2 + un-normalise: every lane of wave 0 runs the same problem (the Jacobi sweeps are
         // wave-uniform loops); lane 0 publishes
         if (tid < kWave) {
@@ -153,7 +126,9 @@ __global__ __launch_bounds__(kThreads) void refine_kernel(
 #pragma unroll
         for (int k = 0; k < 9; ++k) e[k] = e_new[k];
         // pass D: score every correspondence under the refit model (sed.py:7-30; `<=` as ransac.py:74)
-        double c[3] = {0.0, 0.0, 0.0};
+        // count | sum e | sum e^2 | unused: four values as in pass A, so that the two passes share one LDS row offset.  The
+        // kernel sits at its 256-register cap, and a fifth offset kept across the round is reloaded from scratch here.
+        double c[4] = {0.0, 0.0, 0.0, 0.0};
         for (int i = tid; i < n; i += kThreads) {
             const Corr p = pts[i];
             const double sed = sfm::sed_value(e, p.xa, p.ya, p.xb, p.yb);
@@ -163,11 +138,10 @@ __global__ __launch_bounds__(kThreads) void refine_kernel(
                 c[2] += sed * sed;
             }
         }
-        block_sum<3>(c, part, total);
+        block_sum<4, kThreads>(c, part, total);
         const double cnt = total[0];
-        const double err = aggregate_total(aggregation, cnt, total[1], total[2]);
-        const bool better = cnt > best_cnt || (cnt == best_cnt && err < best_err);  // NaN error never wins
-        if (!better) break;
+        const double err = sfmfit::aggregate_error(aggregation, (int)cnt, total[1], total[2], 0);
+        if (!sfmfit::refit_wins(cnt, err, best_cnt, best_err)) break;
         for (int i = tid; i < n; i += kThreads) {
             const Corr p = pts[i];
             mout[i] = sfm::sed_value(e, p.xa, p.ya, p.xb, p.yb) <= thr ? 1 : 0;

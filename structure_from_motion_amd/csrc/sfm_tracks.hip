@@ -8,7 +8,8 @@
 //   1. the DLT rows of the reference's triangulate_dlt (y P3 - P2, P1 - x P3 with P = K [R | t]) of each observation,
 //      streamed by Givens rotations into a 4 x 4 upper-triangular R (same right singular vectors as the stacked A, the
 //      condition number not squared), then R's null vector by sfm::null_vector4 and X = v[0:3] / v[3];
-//   2. optionally LM on the point alone, on F(X) = sum of sfm_pnp_score's e over its observations;
+//   2. optionally LM on the point alone (the rules of sfm_lm.h, the Jacobian of sfm_pnp.h), on F(X) = sum of
+//      sfm_pnp_score's e over its observations;
 //   3. e per observation, cheirality, the triangulation angle and the status.
 // A track whose observations all name one camera is DEGENERATE whatever its pixels say: its rays meet at that camera's
 // centre, which the DLT would return with a depth of rounding size.
@@ -19,6 +20,7 @@
 #include <stdint.h>
 
 #include "sfm_common.h"
+#include "sfm_lm.h"
 #include "sfm_math.h"
 #include "sfm_obs_order.h"
 #include "sfm_pnp.h"
@@ -32,11 +34,6 @@ using sfmpnp::pnp_score;
 using sfmpnp::PnPCamera;
 
 constexpr int kThreads = 256;
-constexpr double kLambda0 = 1e-3;
-constexpr double kLambdaMax = 1e16;
-constexpr double kMinDecrease = 1e-12;
-constexpr double kMinStep = 1e-12;
-constexpr double kRankFloor = 1e-10;
 constexpr double kMinW = 1e-12;   // |v3| of the unit null vector at or below this: the point is at infinity
 
 static_assert(sizeof(sfm_tracks_info) == 32, "sfm_tracks_info layout is part of the ABI");
@@ -121,7 +118,7 @@ SFM_DEVICE void givens_add(double (&R)[4][4], double (&a)[4]) {
 }
 
 // F, H (packed upper 3 x 3) and g = J^T r of the point X over its run.  An observation behind the camera makes F infinite
-// and adds nothing to H or g.  Jp = A R, with A = dr/dc as in sfm_bundle.hip's linearize.
+// and adds nothing to H or g.  J: the point rows of sfmpnp::jacobians, one add per row.
 SFM_DEVICE double point_system(const double (&X)[3], const int32_t* run, int n, const Obs& obs,
                                const double* __restrict__ poses, const PnPCamera& k, double (&H)[6], double (&g)[3]) {
     double F = 0.0;
@@ -133,20 +130,11 @@ SFM_DEVICE double point_system(const double (&X)[3], const int32_t* run, int n, 
         const double* pose = poses + 12 * (int64_t)obs.cam[m];
         const double u = obs.uv[2 * (int64_t)m], v = obs.uv[2 * (int64_t)m + 1];
         F += pnp_score(pose, k, X[0], X[1], X[2], u, v);
-        const double c0 = ((pose[0] * X[0] + pose[1] * X[1]) + pose[2] * X[2]) + pose[9];
-        const double c1 = ((pose[3] * X[0] + pose[4] * X[1]) + pose[5] * X[2]) + pose[10];
-        const double c2 = ((pose[6] * X[0] + pose[7] * X[1]) + pose[8] * X[2]) + pose[11];
-        if (!(c2 > 0.0)) continue;
-        const double w0 = ((k.k00 * c0 + k.k01 * c1) + k.k02 * c2) / c2;
-        const double w1 = ((k.k10 * c0 + k.k11 * c1) + k.k12 * c2) / c2;
-        const double r[2] = {w0 - u, w1 - v};
-        const double ic = 1.0 / c2;
-        const double A[2][3] = {{k.k00 * ic, k.k01 * ic, (k.k02 - w0) * ic}, {k.k10 * ic, k.k11 * ic, (k.k12 - w1) * ic}};
+        double r[2], Jc[2][6], Jp[2][3];
+        if (!sfmpnp::jacobians(pose, k, X[0], X[1], X[2], Jc, Jp, r, u, v)) continue;
 #pragma unroll
         for (int row = 0; row < 2; ++row) {
-            double J[3];
-#pragma unroll
-            for (int j = 0; j < 3; ++j) J[j] = (A[row][0] * pose[j] + A[row][1] * pose[3 + j]) + A[row][2] * pose[6 + j];
+            const double(&J)[3] = Jp[row];
             H[0] += J[0] * J[0];
             H[1] += J[0] * J[1];
             H[2] += J[0] * J[2];
@@ -160,7 +148,10 @@ SFM_DEVICE double point_system(const double (&X)[3], const int32_t* run, int n, 
     return F;
 }
 
-// Cholesky of the packed symmetric 3 x 3 M: false when a pivot is not above rel times its diagonal entry
+// Cholesky of the packed symmetric 3 x 3 M: false when a pivot is not above rel times its diagonal entry.
+// Not sfmlm::factor<3>, and to stay so: the last pivot here, and the triangular solves of refine_point, subtract the
+// accumulated sum, M - (a + b), where the shared factor subtracts term by term, (M - a) - b.  This is the order
+// tests/tracks_oracle.py defines, and test_parity_with_oracle pins the step counts that follow from it.
 SFM_DEVICE bool cholesky3(const double (&M)[6], double rel, double (&L)[6]) {
     // L packed lower: L00, L10, L11, L20, L21, L22
     const double s0 = M[0];
@@ -178,19 +169,19 @@ SFM_DEVICE bool cholesky3(const double (&M)[6], double rel, double (&L)[6]) {
     return true;
 }
 
-// LM on the point alone (the rules of sfm_pnp_refine.hip): returns the trial steps taken
+// LM on the point alone (the constants and rules of sfm_lm.h): returns the trial steps taken
 SFM_DEVICE int refine_point(double (&X)[3], const int32_t* run, int n, const Obs& obs, const double* __restrict__ poses,
                             const PnPCamera& k, int max_steps) {
     double H[6], g[3], L[6];
     double F = point_system(X, run, n, obs, poses, k, H, g);
-    if (!isfinite(F) || !cholesky3(H, kRankFloor, L)) return 0;
-    double lambda = kLambda0;
+    if (!isfinite(F) || !cholesky3(H, sfmlm::kRankFloor, L)) return 0;
+    double lambda = sfmlm::kLambda0;
     int steps = 0;
-    while (steps < max_steps && !(lambda > kLambdaMax)) {
+    while (!sfmlm::exhausted(steps, max_steps, lambda)) {
         ++steps;
         const double D[6] = {H[0] + lambda * H[0], H[1], H[2], H[3] + lambda * H[3], H[4], H[5] + lambda * H[5]};
         if (!cholesky3(D, 0.0, L)) {
-            lambda *= 10.0;
+            lambda = sfmlm::more_damping(lambda);
             continue;
         }
         const double y0 = -g[0] / L[0];
@@ -200,17 +191,17 @@ SFM_DEVICE int refine_point(double (&X)[3], const int32_t* run, int n, const Obs
         const double d1 = (y1 - L[4] * d2) / L[2];
         const double d0 = (y0 - (L[1] * d1 + L[3] * d2)) / L[0];
         if (!(isfinite(d0) && isfinite(d1) && isfinite(d2))) {
-            lambda *= 10.0;
+            lambda = sfmlm::more_damping(lambda);
             continue;
         }
         const double dn = sqrt((d0 * d0 + d1 * d1) + d2 * d2);
         const double xn = sqrt((X[0] * X[0] + X[1] * X[1]) + X[2] * X[2]);
-        if (dn <= kMinStep * (1.0 + xn)) break;
+        if (sfmlm::small_step(dn, xn)) break;
         const double Xt[3] = {X[0] + d0, X[1] + d1, X[2] + d2};
         double Ht[6], gt[3];
         const double Ft = point_system(Xt, run, n, obs, poses, k, Ht, gt);
-        if (isfinite(Ft) && Ft < F) {
-            const double decrease = F - Ft, F_old = F;
+        if (sfmlm::improved(Ft, F)) {
+            const bool last = sfmlm::converged(F, Ft);
 #pragma unroll
             for (int i = 0; i < 3; ++i) {
                 X[i] = Xt[i];
@@ -219,10 +210,10 @@ SFM_DEVICE int refine_point(double (&X)[3], const int32_t* run, int n, const Obs
 #pragma unroll
             for (int i = 0; i < 6; ++i) H[i] = Ht[i];
             F = Ft;
-            lambda /= 10.0;
-            if (decrease < kMinDecrease * F_old) break;
+            lambda = sfmlm::less_damping(lambda);
+            if (last) break;
         } else {
-            lambda *= 10.0;
+            lambda = sfmlm::more_damping(lambda);
         }
     }
     return steps;

@@ -168,6 +168,59 @@ def test_non_finite_start_and_bad_index_leave_input(dev):
         assert np.array_equal(poses, pr["poses"]) and np.array_equal(points, pr["points"])
 
 
+def _three_cameras(seed):
+    """3 cameras x 8 points, every camera sees every point, 0.5 px noise; the start is off by 0.01."""
+    rng = np.random.default_rng(seed)
+    K = synthetic.BENCH_K
+    eye = np.eye(3).reshape(9)
+    poses = np.array([np.concatenate([eye, t]) for t in ([0.0, 0.0, 0.0], [0.3, 0.0, 1.0], [-0.3, 0.1, 1.0])])
+    X = np.column_stack([rng.uniform(-1.0, 1.0, 8), rng.uniform(-1.0, 1.0, 8), rng.uniform(4.0, 6.0, 8)])
+    cam, pt = np.repeat(np.arange(3), 8).astype(np.int32), np.tile(np.arange(8), 3).astype(np.int32)
+    uvw = (X[pt] + poses[cam, 9:]) @ K.T
+    pixels = uvw[:, :2] / uvw[:, 2:3] + rng.normal(0.0, 0.5, (24, 2))
+    start = poses.copy()
+    start[1:, 9:] += rng.normal(0.0, 0.01, (2, 3))
+    return dict(K=K, poses=start, points=X + rng.normal(0.0, 0.01, X.shape), camera_indices=cam, point_indices=pt,
+                pixels=pixels)
+
+
+def _every_step_rejected(pr, got, ref):
+    """lambda goes from 1e-3 past 1e16 in 20 rejected steps and the input comes back bit-unchanged."""
+    poses, points, info = got
+    assert (info.status, info.steps, info.accepted) == (ref["status"], ref["steps"], ref["accepted"]) == (0, 20, 0), (info, ref)
+    assert abs(info.initial_cost - ref["initial_cost"]) <= 1e-12 * ref["initial_cost"]
+    assert info.final_cost == info.initial_cost
+    assert np.array_equal(poses, pr["poses"]) and np.array_equal(points, pr["points"])
+
+
+def test_free_camera_without_observations_rejects_every_step(dev):
+    """The preconditioner block of a free camera that sees nothing is 0 and does not factor (sfmlm::factor<6> at rel = 0):
+    every step is rejected until lambda passes 1e16, as in the oracle."""
+    pr = _three_cameras(51)
+    keep = pr["camera_indices"] != 2
+    sub = dict(pr, camera_indices=pr["camera_indices"][keep], point_indices=pr["point_indices"][keep],
+               pixels=pr["pixels"][keep])
+    got = _pcg(sub)
+    _every_step_rejected(sub, got, _oracle(sub))
+    assert got[2].cg_iterations == 0
+
+
+def test_point_block_with_an_infinite_pivot_rejects_every_step(dev):
+    """A moving point 1e-160 in front of the fixed camera has a finite cost and an infinite V_p: its damped block has the
+    pivot +inf, which sfmlm::factor<3> refuses at rel = 0 like a pivot <= 0.  Both adjusters reject every step, as their
+    oracles do."""
+    pr = _three_cameras(52)
+    pr["points"][3] = [0.0, 0.0, 1e-160]
+    at = (pr["point_indices"] == 3) & (pr["camera_indices"] == 0)
+    pr["pixels"][at] = [pr["K"][0, 2], pr["K"][1, 2]]
+    with np.errstate(all="ignore"):
+        ref_dense = bo.adjust(pr["K"], pr["poses"], pr["points"], pr["camera_indices"], pr["point_indices"], pr["pixels"])
+        ref_pcg = _oracle(pr)
+    assert np.isfinite(ref_dense["initial_cost"])
+    _every_step_rejected(pr, _dense(pr), ref_dense)
+    _every_step_rejected(pr, _pcg(pr), ref_pcg)
+
+
 def test_inplace_op_matches_functional_and_opcheck(dev):
     from structure_from_motion_amd import device, ops
 

@@ -146,6 +146,27 @@ def test_six_items(dev):
     assert np.array_equal(mask[0].cpu().numpy(), ref["mask"])
 
 
+def test_six_items_stop_where_the_oracle_stops(dev):
+    """With a budget of 50 trial steps, LM on six noisy items ends on its own rules (a small decrease or a small step) long
+    before the budget, on the device as in the oracle.  Once the pose has converged, the last bits of the two costs decide
+    the relative-decrease test (the device and the oracle differ in summation order), so the two may stop one trial step
+    apart in a round, as in test_gpu_tracks.py: the step counts agree to one per round, the poses to the file's 1e-9."""
+    from structure_from_motion_amd import device
+
+    view, _, _ = po.scene(6, seed=500, K=K, outlier_fraction=0.0, noise_px=0.5)
+    ws, pts = _pass([view], 4, AGG["rms"], 1, dev, min_extra=0)
+    R0, t0, mask_in, err = _inputs(ws, 0)
+    for rounds in (1, 2):
+        model, mask, info = ws.refine(pts, K, THR, AGG["rms"], rounds=rounds, max_steps=50)
+        ref = ro.refine(view, R0, t0, K, mask_in, err, THR, AGG["rms"], rounds=rounds, max_steps=50)
+        rec = device.read_pnp_refine_info(info)[0]
+        print(f"six items, {rounds} round(s): device {rec.lm_steps} trial steps, oracle {ref['lm_steps']}")
+        assert 1 <= rec.lm_steps < 50 and 1 <= ref["lm_steps"] < 50, (rec, ref["lm_steps"])
+        assert abs(rec.lm_steps - ref["lm_steps"]) <= rounds, (rec, ref["lm_steps"])
+        assert rec.accepted == ref["accepted"] and rec.count == ref["count"]
+        assert np.max(np.abs(model[0].cpu().numpy()[:9] - ref["R"].reshape(9))) <= 1e-9
+
+
 def test_view_without_model_is_unchanged(dev):
     from structure_from_motion_amd import device
 
