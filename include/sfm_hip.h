@@ -618,6 +618,7 @@ int sfm_bundle_adjust_ex(const double* K, int64_t cameras, int64_t points, int64
                          const sfm_bundle_options* options);
 int64_t sfm_bundle_pcg_workspace_bytes_ex(int64_t cameras, int64_t points, int64_t observations,
                                           const sfm_bundle_options* options);
+/* As sfm_bundle_adjust_pcg, the host reads the two stop flags between LM steps and CG chunks: the call synchronises `stream`. */
 int sfm_bundle_adjust_pcg_ex(const double* K, int64_t cameras, int64_t points, int64_t observations, const uint8_t* fixed,
                              const double* poses_in, const double* points_in, const int32_t* camera_index,
                              const int32_t* point_index, const double* pixels, int max_steps, int max_cg_iterations,
