@@ -68,7 +68,7 @@ from lib.multiview.rotation_averaging import average_graph_rotations, inconsiste
 from lib.multiview.tracks import build_tracks, triangulate_tracks
 from lib.multiview.translation_averaging import average_graph_translations, global_poses
 from lib.pnp.pnp import estimate_pose_pnp_with_ransac
-from structure_from_motion_amd import device, synthetic
+from structure_from_motion_amd import _native, device, synthetic
 
 DENSE_MAX_VIEWS = 64   # the dense bundle adjuster's camera limit
 MAX_VIEWS = 1024       # with bundle_solver="auto": a bound of the app (host-side bookkeeping and run time)
@@ -316,8 +316,8 @@ def run(views: int = 8, points: int = 2000, seed: int = 21, noise_px: float = 0.
         raise ValueError(f"bundle_solver must be one of {BUNDLE_SOLVERS}, got {bundle_solver!r}")
     if bundle_loss not in BUNDLE_LOSSES:
         raise ValueError(f"bundle_loss must be one of {BUNDLE_LOSSES}, got {bundle_loss!r}")
-    if not (np.isfinite(bundle_loss_scale) and bundle_loss_scale > 0.0):
-        raise ValueError(f"bundle_loss_scale must be finite and positive, got {bundle_loss_scale!r}")
+    if not (np.isfinite(bundle_loss_scale) and _native.loss_scale_ok(bundle_loss_scale)):
+        raise ValueError(f"bundle_loss_scale must be positive with a normal finite square, got {bundle_loss_scale!r}")
     limit = DENSE_MAX_VIEWS if bundle_solver == "dense" else MAX_VIEWS
     if not 2 <= views <= limit:
         raise ValueError(f"between 2 and {limit} views are supported with bundle_solver={bundle_solver!r}, got {views}")

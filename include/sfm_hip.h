@@ -599,7 +599,8 @@ int sfm_bundle_adjust_pcg(const double* K, int64_t cameras, int64_t points, int6
 typedef struct sfm_bundle_options {
     int32_t loss;      /* SFM_BUNDLE_LOSS_* */
     int32_t reserved;  /* 0 */
-    double loss_scale; /* a, in pixels: finite and positive (read for the squared loss too, where it has no effect) */
+    double loss_scale; /* a, in pixels: positive, a * a a normal finite double, about 1.5e-154 .. 1.3e154 (read and checked
+                          for the squared loss too, where it has no effect) */
 } sfm_bundle_options;
 
 /* sfm_bundle_adjust and sfm_bundle_adjust_pcg on F = sum over the observations of rho(e), e the squared reprojection error
@@ -608,7 +609,9 @@ typedef struct sfm_bundle_options {
  * both Jacobians of an observation are multiplied by sqrt(w), w = rho'(e) at the linearisation point (1 | a / sqrt(e) above
  * a^2 | 1 / (1 + e / a^2)); everything else is the squared adjuster's.  options == NULL is the squared loss, and a squared
  * call computes the bits of the entry point without options.  SFM_EINVAL before the first launch for a loss outside 0..2,
- * reserved != 0 or a loss_scale that is not finite and positive.  The dense adjuster's workspace is
+ * reserved != 0 or a loss_scale that is not positive with a normal finite square (a^2 is computed in double: at 0 or inf
+ * Cauchy's rho would be NaN for every e).  Within that range rho is +inf where e / a^2 overflows, and the start is then
+ * SFM_BUNDLE_BAD_START, as for a point behind a camera.  The dense adjuster's workspace is
  * sfm_bundle_workspace_bytes for every loss; the iterative one keeps sqrt(w) per observation for a non-squared loss and
  * needs sfm_bundle_pcg_workspace_bytes_ex (-1 also for options it refuses; the plain size for NULL or squared). */
 int sfm_bundle_adjust_ex(const double* K, int64_t cameras, int64_t points, int64_t observations, const uint8_t* fixed,
@@ -722,7 +725,7 @@ typedef struct sfm_rotavg_options {
     int32_t init;              /* SFM_ROTAVG_INIT_* */
     int32_t max_steps;         /* >= 0 */
     int32_t max_cg_iterations; /* >= 1 */
-    double loss_scale;         /* a, in radians: finite and positive (read for the squared loss too, where it has no effect) */
+    double loss_scale;         /* a, in radians: positive with a normal finite square, as sfm_bundle_options.loss_scale */
     double cg_tolerance;       /* finite, in (0, 1) */
     double step_tolerance;     /* finite and positive, radians */
 } sfm_rotavg_options;
@@ -787,7 +790,7 @@ typedef struct sfm_transavg_options {
     int32_t max_cg_iterations; /* >= 1 */
     int32_t warmup_steps;      /* >= 0: the first steps take every scale d = 1 and do not end the call as converged */
     int32_t reserved;          /* 0 */
-    double loss_scale;         /* a, a sine: finite and positive (read for the squared loss too, where it has no effect) */
+    double loss_scale;         /* a, a sine: positive with a normal finite square, as sfm_bundle_options.loss_scale */
     double cg_tolerance;       /* finite, in (0, 1) */
     double step_tolerance;     /* finite and positive, in the unit of the positions */
 } sfm_transavg_options;

@@ -203,6 +203,13 @@ OTHER_SYMBOLS = ["sfm_last_error", "sfm_abi_version", "sfm_score_workspace_bytes
 BUNDLE_LOSSES = ("squared", "huber", "cauchy")
 
 
+def loss_scale_ok(a: float) -> bool:
+    """sfmloss::scale_ok (csrc/sfm_loss.h): positive, with a square that is a normal finite double.  The value the device
+    receives is the one to check; False for NaN."""
+    a = float(a)
+    return a > 0.0 and 2.2250738585072014e-308 <= a * a <= 1.7976931348623157e308
+
+
 # the kinds of sfm_pair_verdict, in the order of their SFM_PAIR_* codes (include/sfm_hip.h)
 PAIR_KINDS = ("none", "essential", "homography", "bad_offsets")
 

@@ -109,7 +109,8 @@ def _compile(cmd, target: str, verbose: bool) -> None:
 def build_ops(force: bool = False, verbose: bool = False) -> str:
     """Compile csrc/sfm_torch_ops.cpp — TORCH_LIBRARY(sfm_hip): the PyTorch-ROCm custom-op registration above the
     C ABI — into csrc/libsfm_torch_ops.so.  Host code only (g++), linked against libsfm_hip.so and torch's libraries."""
-    deps = [OPS_SOURCE, os.path.join(CSRC, "..", "..", "include", "sfm_hip.h"), os.path.abspath(__file__)]
+    deps = [OPS_SOURCE, os.path.join(CSRC, "sfm_loss.h"), os.path.join(CSRC, "..", "..", "include", "sfm_hip.h"),
+            os.path.abspath(__file__)]
 
     def fresh() -> bool:
         return os.path.exists(OPS_LIB_PATH) and all(os.path.getmtime(d) <= os.path.getmtime(OPS_LIB_PATH) for d in deps)

@@ -18,6 +18,7 @@ import numpy as np
 import numpy.typing as npt
 
 from .._native import BUNDLE_LOSSES as LOSSES
+from .._native import loss_scale_ok
 from ..pnp.pnp import check_camera_matrix
 
 MAX_CAMERAS = 64   # of the dense solver
@@ -72,7 +73,7 @@ def bundle_adjust(
     ``device.BundlePcgInfo`` (the ``BundleInfo`` fields plus ``cg_iterations`` and ``cg_max``).
 
     ``loss`` is one of ``LOSSES``.  With e an observation's squared reprojection error in px^2 and a = ``loss_scale`` in
-    pixels (finite, > 0; no effect on ``"squared"``): ``"huber"`` is e up to a^2 and 2 a sqrt(e) - a^2 above, ``"cauchy"``
+    pixels (> 0 with a normal finite square, about 1.5e-154 to 1.3e154; no effect on ``"squared"``): ``"huber"`` is e up to a^2 and 2 a sqrt(e) - a^2 above, ``"cauchy"``
     is a^2 log1p(e / a^2).  ``info.initial_cost`` and ``info.final_cost`` are then the sums of rho(e), not of e, and the
     accept test and the stops use them.  Huber keeps a constant pull of 2 a per pixel on an outlier and suits moderate
     ones; Cauchy re-descends and suits gross ones."""
@@ -110,8 +111,8 @@ def bundle_adjust(
     if not isinstance(loss, str) or loss not in LOSSES:
         raise ValueError(f"loss must be one of {LOSSES}, got {loss!r}")
     if (isinstance(loss_scale, bool) or not isinstance(loss_scale, (int, float, np.integer, np.floating))
-            or not np.isfinite(float(loss_scale)) or not float(loss_scale) > 0.0):
-        raise ValueError(f"loss_scale must be a finite number > 0, got {loss_scale!r}")
+            or not loss_scale_ok(float(loss_scale))):
+        raise ValueError(f"loss_scale must be a number > 0 with a normal finite square, got {loss_scale!r}")
     import torch
 
     from .. import device

@@ -381,7 +381,7 @@ int sfm_bundle_adjust_ex(const double* K, int64_t cameras, int64_t points, int64
         return fail(SFM_EINVAL, "sfm_bundle_adjust: points and observations must be below 2^31");
     sfmloss::Loss loss;
     if (!sfmloss::from_options(options, loss))
-        return fail(SFM_EINVAL, "sfm_bundle_adjust: options need a loss in 0..2, reserved = 0 and a finite loss_scale > 0");
+        return fail(SFM_EINVAL, "sfm_bundle_adjust: options need a loss in 0..2, reserved = 0 and a loss_scale > 0 with a normal finite square");
     PnPCamera cam;
     const int rc = camera_from(K, cam, "sfm_bundle_adjust");
     if (rc != SFM_OK) return rc;

@@ -614,7 +614,7 @@ int sfm_bundle_adjust_pcg_ex(const double* K, int64_t cameras, int64_t points, i
         return fail(SFM_EINVAL, "sfm_bundle_adjust_pcg: cg_tolerance must be finite and in (0, 1)");
     sfmloss::Loss loss;
     if (!sfmloss::from_options(options, loss))
-        return fail(SFM_EINVAL, "sfm_bundle_adjust_pcg: options need a loss in 0..2, reserved = 0 and a finite loss_scale > 0");
+        return fail(SFM_EINVAL, "sfm_bundle_adjust_pcg: options need a loss in 0..2, reserved = 0 and a loss_scale > 0 with a normal finite square");
     PnPCamera cam;
     const int rc = camera_from(K, cam, "sfm_bundle_adjust_pcg");
     if (rc != SFM_OK) return rc;

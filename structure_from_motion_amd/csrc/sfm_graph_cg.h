@@ -23,6 +23,7 @@
 #include <stdio.h>
 
 #include "sfm_common.h"
+#include "sfm_loss.h"
 #include "sfm_math.h"
 #include "sfm_obs_order.h"
 
@@ -456,7 +457,7 @@ int check_entry(const char* name, const char* tag, int64_t cameras, int64_t edge
         : o.max_steps < 0                                          ? "max_steps must be at least 0"
         : o.max_cg_iterations < 1                                  ? "max_cg_iterations must be at least 1"
         : own                                                      ? own
-        : !(o.loss_scale > 0.0) || !isfinite(o.loss_scale)         ? "loss_scale must be finite and positive"
+        : !sfmloss::scale_ok(o.loss_scale)                         ? "loss_scale must be positive with a normal finite square"
         : !(o.cg_tolerance > 0.0 && o.cg_tolerance < 1.0)          ? "cg_tolerance must be finite and in (0, 1)"
         : !(o.step_tolerance > 0.0) || !isfinite(o.step_tolerance) ? "step_tolerance must be finite and positive"
         : !pointers                                                ? "null pointer"

@@ -8,10 +8,24 @@
 // Jp of every observation are multiplied by sqrt(w) at the linearisation point, everything after sees w J^T J and w J^T r.
 // Both rho are concave in e, so rho(e) <= rho(e0) + w(e0) (e - e0): the weighted squared cost majorises the robust one and
 // touches it at the linearisation point.  rho(+inf) = +inf and w(+inf) = 0 for both.
+//
+// The scale contract: a2 is computed in double, so a scale whose square is zero, subnormal or infinite is refused like a
+// non-positive one (scale_ok; about 1.5e-154 <= a <= 1.3e154).  With a2 = 0 or inf Cauchy's rho is 0 * log1p(e / 0) or
+// inf * log1p(0), NaN for every e, and every start would be BAD_START.  Within the contract rho is still +inf where e / a2
+// overflows: a bad start, like a point behind a camera.
 #pragma once
+#include <float.h>
 #include <math.h>
 #include <stdint.h>
 
+namespace sfmloss {
+
+// A loss scale every door accepts: positive, with a normal finite square (false for NaN: the first comparison fails).
+inline bool scale_ok(double a) { return a > 0.0 && a * a >= DBL_MIN && a * a <= DBL_MAX; }
+
+}  // namespace sfmloss
+
+#ifdef __HIPCC__   // the rest is for the library's translation units; the host-only torch ops take scale_ok alone
 #include "sfm_common.h"
 #include "sfm_math.h"
 
@@ -23,12 +37,12 @@ struct Loss {
     double a, a2;   // the scale in pixels and its square
 };
 
-// NULL options: the squared loss.  False for a loss code outside 0..2, reserved != 0, or a scale not finite and positive.
+// NULL options: the squared loss.  False for a loss code outside 0..2, reserved != 0, or a scale that is not scale_ok.
 inline bool from_options(const sfm_bundle_options* o, Loss& l) {
     l = Loss{SFM_BUNDLE_LOSS_SQUARED, 0, 1.0, 1.0};
     if (!o) return true;
     if (o->loss < SFM_BUNDLE_LOSS_SQUARED || o->loss > SFM_BUNDLE_LOSS_CAUCHY || o->reserved != 0) return false;
-    if (!(o->loss_scale > 0.0) || !isfinite(o->loss_scale)) return false;
+    if (!scale_ok(o->loss_scale)) return false;
     l = Loss{o->loss, 0, o->loss_scale, o->loss_scale * o->loss_scale};
     return true;
 }
@@ -66,3 +80,4 @@ SFM_DEVICE void scale(double s, double (&r)[2], double (&Jc)[2][6], double (&Jp)
 }
 
 }  // namespace sfmloss
+#endif  // __HIPCC__

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "../../include/sfm_hip.h"
+#include "sfm_loss.h"   // sfmloss::scale_ok alone: the rest of it is for the HIP compiler
 
 namespace {
 
@@ -790,7 +791,7 @@ std::tuple<Tensor, Tensor, Tensor> pnp_refine_meta(const Tensor& pts, const Tens
 // schema changes.  Four op families, each functional, in-place and Meta, over one body.
 void loss_check(int64_t loss, double loss_scale) {
     TORCH_CHECK(loss >= SFM_BUNDLE_LOSS_SQUARED && loss <= SFM_BUNDLE_LOSS_CAUCHY, "sfm_hip: loss must be 0 (squared), 1 (huber) or 2 (cauchy)");
-    TORCH_CHECK(loss_scale > 0.0 && std::isfinite(loss_scale), "sfm_hip: loss_scale must be finite and positive");
+    TORCH_CHECK(sfmloss::scale_ok(loss_scale), "sfm_hip: loss_scale must be positive with a normal finite square");
 }
 
 sfm_bundle_options bundle_options(int64_t loss, double loss_scale) {

@@ -811,12 +811,13 @@ BUNDLE_LOSSES = _native.BUNDLE_LOSSES   # "squared", "huber", "cauchy": the inde
 
 
 def _bundle_loss(loss: str, loss_scale: float):
-    """(code, scale) of a loss name; ValueError for an unknown name or a scale that is not finite and positive."""
+    """(code, scale) of a loss name; ValueError for an unknown name or a scale that is not positive with a normal finite
+    square (``_native.loss_scale_ok``)."""
     if loss not in BUNDLE_LOSSES:
         raise ValueError(f"loss must be one of {BUNDLE_LOSSES}, got {loss!r}")
     scale = float(loss_scale)
-    if not (np.isfinite(scale) and scale > 0.0):
-        raise ValueError(f"loss_scale must be finite and positive, got {loss_scale!r}")
+    if not _native.loss_scale_ok(scale):
+        raise ValueError(f"loss_scale must be positive with a normal finite square, got {loss_scale!r}")
     return BUNDLE_LOSSES.index(loss), scale
 
 

@@ -6,6 +6,8 @@ import math
 
 import numpy as np
 
+from .._native import loss_scale_ok
+
 LOSSES = ("squared", "huber", "cauchy")
 _INT32 = 2**31
 MAX_EDGES = 2**30
@@ -17,13 +19,17 @@ def _integer(value, name: str, low: int, high: int = _INT32) -> int:
     return int(value)
 
 
-def _positive(value, name: str, below: float = math.inf) -> float:
+def _positive(value, name: str, below: float = math.inf, loss_scale=None) -> float:
+    """``value`` as a float, finite and in (0, ``below``).  ``loss_scale``: the map from ``value`` to the loss scale the device
+    receives (degrees to radians, or to a sine), which must pass ``loss_scale_ok``."""
     try:
         v = float(value)
     except (TypeError, ValueError):
         raise ValueError(f"{name} must be a number, got {value!r}") from None
     if not (math.isfinite(v) and 0.0 < v < below):
         raise ValueError(f"{name} must be finite and in (0, {below}), got {value!r}")
+    if loss_scale is not None and not loss_scale_ok(loss_scale(v)):
+        raise ValueError(f"{name} must give a loss scale with a normal finite square, got {value!r}")
     return v
 
 
@@ -43,9 +49,10 @@ def _named(rows: str, per_row) -> str:
     return "(" + ", ".join([rows, *map(str, per_row)]) + ")"
 
 
-def _checked(num_cameras, pairs, measured, weights, root, loss, loss_scale_deg, scale_below, initial, limits):
+def _checked(num_cameras, pairs, measured, weights, root, loss, loss_scale_deg, scale_below, device_scale, initial, limits):
     """Every argument both solvers take, checked in the order of their signatures -> (C, pairs (Q, 2), the measurements, weights
-    (Q,), root, loss_scale_deg as a float below ``scale_below``, the start or None, the limits as Python numbers).  ``measured``
+    (Q,), root, loss_scale_deg as a float below ``scale_below`` whose ``device_scale`` (the scale the device receives) passes
+    ``loss_scale_ok``, the start or None, the limits as Python numbers).  ``measured``
     and ``initial`` are (value, name, shape of one row): one row per edge and one per camera (value None: no start).
     ``limits`` maps ``max_steps``, ``max_cg_iterations``, ``cg_tolerance``, ``step_tolerance`` and any further step count to
     its value; they are checked in its order."""
@@ -71,7 +78,7 @@ def _checked(num_cameras, pairs, measured, weights, root, loss, loss_scale_deg, 
     root = _integer(root, "root", 0, C)
     if loss not in LOSSES:
         raise ValueError(f"loss must be one of {LOSSES}, got {loss!r}")
-    scale = _positive(loss_scale_deg, "loss_scale_deg", below=scale_below)
+    scale = _positive(loss_scale_deg, "loss_scale_deg", below=scale_below, loss_scale=device_scale)
     value, name, row = initial
     init = None if value is None else _array(value, name, (C, *row), _named("C", row))
     options = {}

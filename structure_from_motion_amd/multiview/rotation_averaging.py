@@ -63,7 +63,7 @@ def average_rotations(num_cameras: int, pairs, relative_rotations, weights=None,
     (``ValueError``); ``Q = 0`` needs no GPU."""
     C, pair_arr, rel, w, root, angle, init, limits = _checked(
         num_cameras, pairs, (relative_rotations, "relative_rotations", (3, 3)), weights, root, loss, loss_scale_deg, math.inf,
-        (initial_rotations, "initial_rotations", (3, 3)),
+        math.radians, (initial_rotations, "initial_rotations", (3, 3)),
         dict(max_steps=max_steps, max_cg_iterations=max_cg_iterations, cg_tolerance=cg_tolerance, step_tolerance=step_tolerance))
     act = active_edges(rel, w)
     if act.any():

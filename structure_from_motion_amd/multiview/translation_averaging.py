@@ -42,14 +42,19 @@ class GlobalPositions:
     status: str                # "converged", "max_steps", "cg_failed" or "bad_index"
 
 
+def _device_scale(angle_deg: float) -> float:
+    """The loss scale the device receives: the sine of the angle."""
+    return math.sin(math.radians(angle_deg))
+
+
 def _checked(num_cameras, pairs, directions, weights, root, loss, loss_scale_deg, initial_positions, warmup_steps, max_steps,
              max_cg_iterations, cg_tolerance, step_tolerance):
     C, pair_arr, v, w, root, angle, init, options = _graph_args._checked(
-        num_cameras, pairs, (directions, "directions", (3,)), weights, root, loss, loss_scale_deg, 90.0,
+        num_cameras, pairs, (directions, "directions", (3,)), weights, root, loss, loss_scale_deg, 90.0, _device_scale,
         (initial_positions, "initial_positions", (3,)),
         dict(warmup_steps=warmup_steps, max_steps=max_steps, max_cg_iterations=max_cg_iterations, cg_tolerance=cg_tolerance,
              step_tolerance=step_tolerance))
-    return C, pair_arr, v, w, root, math.sin(math.radians(angle)), init, options
+    return C, pair_arr, v, w, root, _device_scale(angle), init, options
 
 
 def active_edges(directions: npt.NDArray, weights: npt.NDArray) -> npt.NDArray:

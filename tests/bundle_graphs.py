@@ -132,3 +132,34 @@ def mixed(cameras, points, seed, order="random", full=True, sparse_camera=None, 
         args["duplicates"] = len(pr["camera_indices"]) // 50
         pr = irregular_problem(cameras, points, seed, order=order, **args)
     return pr
+
+
+def corrupt_long_tracks(problem, fraction, spread_px, seed, min_cameras=3):
+    """The problem with ``int(fraction * M)`` gross errors placed where a parity input can bear them -> (new dict, (M,) bool
+    mask).  That many distinct points are picked among those seen by at least ``min_cameras`` distinct cameras, and one
+    observation of each is shifted by uniform +-``spread_px`` in u and in v.  A point that owns a corrupted observation and
+    has only one other view is barely held, and the reference's own result then depends on the summation order (DESIGN.md
+    §6n): ``synthetic.corrupt_observations`` draws per observation and cannot avoid that on an irregular graph.
+
+    The choice is made on the observations sorted by (point, camera, u, v), so it does not depend on the order of the
+    observation arrays: the four ``order``s of one seed carry the same multiset of (camera, point, pixel)."""
+    cam = np.asarray(problem["camera_indices"], dtype=np.int64)
+    pt = np.asarray(problem["point_indices"], dtype=np.int64)
+    uv = np.asarray(problem["pixels"], dtype=np.float64)
+    M, P = len(cam), len(problem["points"])
+    canon = np.lexsort((uv[:, 1], uv[:, 0], cam, pt))   # position in the canonical order -> observation
+    first = np.searchsorted(pt[canon], np.arange(P + 1))   # canonical range of every point
+    pairs = np.unique(np.column_stack([pt, cam]), axis=0)
+    distinct = np.bincount(pairs[:, 0], minlength=P)
+    eligible = np.nonzero(distinct >= min_cameras)[0]
+    n = int(fraction * M)
+    assert n <= len(eligible), f"{n} points wanted, {len(eligible)} seen by at least {min_cameras} cameras"
+    rng = np.random.default_rng(seed)
+    picked = np.sort(rng.choice(eligible, n, replace=False))
+    which = first[picked] + rng.integers(0, first[picked + 1] - first[picked])   # one observation of each, canonical
+    shift = rng.uniform(-spread_px, spread_px, (n, 2))
+    pixels = uv.copy()
+    pixels[canon[which]] += shift
+    mask = np.zeros(M, dtype=bool)
+    mask[canon[which]] = True
+    return dict(problem, pixels=pixels), mask

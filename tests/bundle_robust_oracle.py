@@ -21,7 +21,10 @@ LOSSES = ("squared", "huber", "cauchy")
 
 
 def rho_and_weight(e, loss, scale):
-    """(rho(e), w(e) = rho'(e)) elementwise; rho(inf) = inf and w(inf) = 0 for huber and cauchy."""
+    """(rho(e), w(e) = rho'(e)) elementwise; rho(inf) = inf and w(inf) = 0 for huber and cauchy.  Defined for the scales
+    of the contract of csrc/sfm_loss.h (``sfmloss::scale_ok``): a > 0 whose square is a normal finite double, about 1.5e-154
+    to 1.3e154.  Outside it a2 is 0 or inf and cauchy's rho is NaN for every e, as the device's would be; every entry point
+    refuses such a scale.  Within it rho is +inf where e / a2 overflows."""
     e = np.asarray(e, dtype=np.float64)
     a = float(scale)
     a2 = a * a
