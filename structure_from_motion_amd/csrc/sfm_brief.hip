@@ -9,10 +9,9 @@
 //                            picks the bin; the 27 x 27 sums of 5 x 5 boxes are built separably in LDS (at most 25 * 255 =
 //                            6375: 16 bits); lane l evaluates tests l, l + 64, l + 128, l + 192 of the bin's pattern and four
 //                            64-bit ballots ARE the four little-endian descriptor words.
-//   hamming_summary_kernel   a 256-thread block owns 256 A rows x 512 B columns: every lane keeps the descriptor of one A row
-//                            in eight registers, the B tile sits in LDS and is read as a broadcast; the lane scans its 512
-//                            columns in B order and leaves the four numbers of sfm_match_summary.h.  The shared
-//                            summary_combine_kernel then walks the tiles: same best / arg / second as sfm_match_summary,
+//   hamming_summary_kernel   a 256-thread block owns 256 A rows x 512 B columns (the tile of sfm_hamming_tile.h): the
+//                            lane scans its 512 columns in B order and leaves the four numbers of sfm_match_summary.h.  The
+//                            shared summary_combine_kernel then walks the tiles: same best / arg / second as sfm_match_summary,
 //                            and the |A| x |B| matrix is never written.  Splitting the columns over blocks gives
 //                            20 000 x 20 000 descriptors 79 x 40 blocks instead of 313 waves.
 #include <hip/hip_runtime.h>
@@ -21,6 +20,7 @@
 
 #include "sfm_brief_device.h"
 #include "sfm_common.h"
+#include "sfm_hamming_tile.h"
 #include "sfm_match_summary.h"
 
 namespace {
@@ -40,41 +40,31 @@ __global__ __launch_bounds__(kWave) void brief_describe_kernel(
                                desc + f * kWords, ok + f, angle_bin + f);
 }
 
-constexpr int kHamRows = 256;                       // A rows per block, one per lane
-constexpr int kHamCols = 512;                       // B columns per block: 16 KiB of LDS
+using sfmham::kCols;
+using sfmham::kRows;
 // distances are at most 256; an invalid pair scores +inf.  "Nothing yet" ranks above it so that the first column of a tile
 // of invalid pairs still becomes the tile's first minimum, as +inf does in the heap.
 constexpr int kHamInvalid = 0x7FFFFFFE, kHamNothing = 0x7FFFFFFF;
 
 SFM_DEVICE double hamming_score(int v) { return v >= kHamInvalid ? INFINITY : (double)v; }
 
-__global__ __launch_bounds__(kHamRows) void hamming_summary_kernel(
+__global__ __launch_bounds__(kRows) void hamming_summary_kernel(
     const uint4* __restrict__ desc_a, const uint8_t* __restrict__ ok_a, int64_t nA, const uint4* __restrict__ desc_b,
     const uint8_t* __restrict__ ok_b, int64_t nB, int64_t row_blocks, TileSummary* __restrict__ tiles) {
-    __shared__ uint4 s_b[kHamCols][2];
-    __shared__ int s_ok[kHamCols];
-    const int tid = threadIdx.x;
+    __shared__ sfmham::Tile s_b;
     // consecutive blocks share a B tile
     const int64_t row_block = blockIdx.x % row_blocks, tile = blockIdx.x / row_blocks;
-    const int64_t c0 = tile * kHamCols;
-    const int cols = (int)min((int64_t)kHamCols, nB - c0);   // >= 1
-    for (int j = tid; j < cols; j += kHamRows) {
-        s_b[j][0] = desc_b[2 * (c0 + j)];
-        s_b[j][1] = desc_b[2 * (c0 + j) + 1];
-        s_ok[j] = ok_b[c0 + j] != 0;
-    }
-    const int64_t row = row_block * kHamRows + tid;
-    const int64_t src = min(row, nA - 1);
-    const uint4 a0 = desc_a[2 * src], a1 = desc_a[2 * src + 1];
-    const bool a_valid = ok_a[src] != 0;
+    const int64_t c0 = tile * kCols;
+    const int cols = (int)min((int64_t)kCols, nB - c0);   // >= 1
+    sfmham::stage(s_b, desc_b, ok_b, c0, cols);
+    const int64_t row = row_block * kRows + threadIdx.x;
+    const sfmham::Row a = sfmham::load_row(desc_a, ok_a, min(row, nA - 1));
     __syncthreads();
     int tile_min = kHamNothing, tile_arg = 0, left_prefixed = kHamNothing, left_min = kHamNothing;
 #pragma unroll 4
     for (int j = 0; j < cols; ++j) {
-        const uint4 b0 = s_b[j][0], b1 = s_b[j][1];
-        const int d = __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
-                      __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
-        const int v = (a_valid && s_ok[j]) ? d : kHamInvalid;
+        const int d = SFM_HAMMING_DISTANCE(a, s_b, j);
+        const int v = (a.valid && s_b.ok[j]) ? d : kHamInvalid;
         if (in_left_subtree(c0 + j + 1)) {           // wave-uniform; tile_min is still the minimum BEFORE column j
             left_prefixed = min(left_prefixed, max(v, tile_min));
             left_min = min(left_min, v);
@@ -118,7 +108,7 @@ int sfm_brief_describe(const uint8_t* image, int64_t height, int64_t width, cons
 
 int64_t sfm_hamming_summary_workspace_bytes(int64_t n_a, int64_t n_b) {
     if (n_a < 0 || n_b < 0) return -1;
-    return (int64_t)sizeof(TileSummary) * n_a * ((n_b + kHamCols - 1) / kHamCols);
+    return (int64_t)sizeof(TileSummary) * n_a * ((n_b + kCols - 1) / kCols);
 }
 
 int sfm_hamming_summary(const uint8_t* desc_a, const uint8_t* ok_a, int64_t n_a, const uint8_t* desc_b, const uint8_t* ok_b,
@@ -134,12 +124,12 @@ int sfm_hamming_summary(const uint8_t* desc_a, const uint8_t* ok_a, int64_t n_a,
         return fail(SFM_EINVAL, "sfm_hamming_summary: workspace smaller than sfm_hamming_summary_workspace_bytes(n_a, n_b)");
     if (((reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(desc_a) | reinterpret_cast<uintptr_t>(desc_b)) & 15u) != 0)
         return fail(SFM_EINVAL, "sfm_hamming_summary: workspace and descriptors must be 16-byte aligned");
-    const int64_t row_blocks = (n_a + kHamRows - 1) / kHamRows, n_tiles = (n_b + kHamCols - 1) / kHamCols;
+    const int64_t row_blocks = (n_a + kRows - 1) / kRows, n_tiles = (n_b + kCols - 1) / kCols;
     if (row_blocks * n_tiles > 0x7FFFFFFF) return fail(SFM_EINVAL, "sfm_hamming_summary: too many tiles");
     SFM_REQUIRE_GRID("sfm_hamming_summary", n_a, 256, 256);
     TileSummary* tiles = static_cast<TileSummary*>(workspace);
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(hamming_summary_kernel, dim3((unsigned)(row_blocks * n_tiles)), dim3(kHamRows), 0, st,
+    hipLaunchKernelGGL(hamming_summary_kernel, dim3((unsigned)(row_blocks * n_tiles)), dim3(kRows), 0, st,
                        reinterpret_cast<const uint4*>(desc_a), ok_a, n_a, reinterpret_cast<const uint4*>(desc_b), ok_b, n_b,
                        row_blocks, tiles);
     hipLaunchKernelGGL(summary_combine_kernel, dim3(grid_for(n_a, 256)), dim3(256), 0, st, tiles, n_a, n_b, n_tiles, best,

@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "sfm_common.h"
 #include "sfm_match_summary.h"
@@ -107,7 +108,6 @@ SFM_DEVICE TileCoord decode_tile(int64_t tiles_a, int64_t tiles_b) {
     t.valid = t.a_tile < tiles_a && t.b_tile < tiles_b;
     return t;
 }
-inline unsigned tile_grid(int64_t tiles_a, int64_t tiles_b) { return (unsigned)(8 * ((tiles_a + 7) / 8) * tiles_b); }
 
 // Tile core shared by the score-matrix kernel and the fused summary kernel.  A 256-thread block owns a
 // kTileA x kTileB tile; lane (ty, tx) accumulates rows a0 + ty*8 + i (i < 8) against columns
@@ -115,7 +115,6 @@ inline unsigned tile_grid(int64_t tiles_a, int64_t tiles_b) { return (unsigned)(
 // (conflict-free), its A operands two 32-byte broadcasts.  16 LDS doubles feed 64 multiply + 64 add per window
 // element (the 4x4 tile this replaces needed 8 for 16 + 16).  The window sum runs over k = 0..K-1 in order with
 // separate multiply / add roundings, so the result does not depend on the tiling.
-// MODE 0: NCC numerator sum a*b (patches mean-removed); MODE 1: SSD sum (a-b)^2.
 static_assert(kTileA == 2 * kWave && kTileB == 2 * kWave, "one LDS-DMA instruction (64 x 16 B) = one tile row");
 // 64 lanes x 16 bytes from per-lane global addresses to 1 KiB of LDS starting at `row` (wave-uniform)
 SFM_DEVICE void direct_row(const double* src, double* row) {
@@ -123,14 +122,11 @@ SFM_DEVICE void direct_row(const double* src, double* row) {
                                      (__attribute__((address_space(3))) void*)row, 16, 0, 0);
 }
 
-// MODEs of the tile core.  0: NCC numerator sum a*b (patches mean-removed); 1: SSD sum (a-b)^2 in float64;
-// 2 / 3 / 4: SSD of INTEGER images in the image dtype's modular arithmetic (ssd.py:31-35: `diff` and `np.square(diff)`
-// wrap modulo 2^bits — into the signed range for signed types —, np.sum accumulates in int64 / uint64) on patches that
-// hold the pixels as int64 bit patterns (SFM_PATCH_RAW64):
-//   2  signed 8 / 16-bit types, 3  unsigned 8 / 16-bit types: 32-bit arithmetic (subtract, bit-field extract, 24-bit
-//      multiply, bit-field extract, add — five full-rate integer instructions per pair and window element), int32
-//      accumulators: windows of at most kNarrowMaxWindow elements
-//   4  any width (32- and 64-bit types; narrow types with huge windows): 64-bit arithmetic, int64 accumulators
+// MODEs of the tile core (the arithmetic of each: its policy below).  0: NCC numerator sum a*b (patches mean-removed);
+// 1: SSD sum (a-b)^2 in float64; 2 / 3 / 4: SSD of INTEGER images in the image dtype's modular arithmetic (ssd.py:31-35:
+// `diff` and `np.square(diff)` wrap modulo 2^bits — into the signed range for signed types —, np.sum accumulates in int64 /
+// uint64) on patches that hold the pixels as int64 bit patterns (SFM_PATCH_RAW64): 2 signed, 3 unsigned 8 / 16-bit types with
+// windows of at most kNarrowMaxWindow elements; 4 any width (32- and 64-bit types; narrow types with huge windows).
 constexpr int kModeNcc = 0, kModeSsd = 1, kModeSsdNarrowSigned = 2, kModeSsdNarrowUnsigned = 3, kModeSsdWide = 4;
 constexpr int kNarrowMaxWindow = 32768;   // 32768 terms of magnitude < 2^16 fit an int32 / uint32 accumulator
 struct IntKind {
@@ -154,144 +150,108 @@ SFM_DEVICE void stage_chunk(const double* __restrict__ Pa, int64_t stride_a, con
             direct_row(Pb + (int64_t)(k0 + kk) * stride_b + b0 + 2 * lane, &sB[kk][0]);
         }
     } else {
-        for (int idx = tid; idx < kc * kTileA; idx += 256) {
-            const int kk = idx / kTileA, f = idx % kTileA;
-            const int64_t ia = a0 + f;
-            sA[kk][f] = ia < nA ? Pa[(int64_t)(k0 + kk) * stride_a + ia] : 0.0;   // (0.0 is also the integer 0)
-        }
-        for (int idx = tid; idx < kc * kTileB; idx += 256) {
-            const int kk = idx / kTileB, f = idx % kTileB;
-            const int64_t ib = b0 + f;
-            sB[kk][f] = ib < nB ? Pb[(int64_t)(k0 + kk) * stride_b + ib] : 0.0;
-        }
+        auto fill = [&](double (*s)[kTileA], const double* __restrict__ P, int64_t stride, int64_t n, int64_t f0) {
+            for (int idx = tid; idx < kc * kTileA; idx += 256) {
+                const int kk = idx / kTileA, f = idx % kTileA;
+                s[kk][f] = f0 + f < n ? P[(int64_t)(k0 + kk) * stride + f0 + f] : 0.0;   // (0.0 is also the integer 0)
+            }
+        };
+        fill(sA, Pa, stride_a, nA, a0);
+        fill(sB, Pb, stride_b, nB, b0);
     }
 }
 
+// What a MODE does with one pair of staged operands: what a staged double is read as (`operand`, whose result type is
+// the operand type), the accumulator, one term of the window sum and the conversion of the finished sum.
+template <bool kSquaredDifference>   // false: NCC numerator a * b; true: float64 SSD (a - b)^2
+struct FloatPolicy {
+    using Acc = double;
+    SFM_DEVICE explicit FloatPolicy(IntKind) {}
+    SFM_DEVICE static double operand(double staged) { return staged; }
+    SFM_DEVICE void add(double& acc, double a, double b) const {   // separate multiply / add roundings
+        const double d = a - b;
+        acc += kSquaredDifference ? d * d : a * b;
+    }
+    SFM_DEVICE double finish(double acc) const { return acc; }
+};
+// 8 / 16-bit pixels: everything fits 32-bit registers — the low dword of the staged int64 IS the pixel (two's
+// complement), the difference is reduced to `bits` by one bit-field extract (sign- or zero-extending: the wrap of the
+// image dtype), its square (|d| < 2^16: a 24-bit multiply, exact in 32 bits) is reduced the same way, and the sum of at
+// most kNarrowMaxWindow such terms cannot leave 32 bits.  Five full-rate integer instructions per pair and window element.
+template <bool kSigned>
+struct NarrowSsdPolicy {
+    using Acc = int;
+    unsigned bits;
+    SFM_DEVICE explicit NarrowSsdPolicy(IntKind kind) : bits((unsigned)kind.bits) {}
+    SFM_DEVICE static int operand(double staged) { return __double2loint(staged); }
+    SFM_DEVICE int narrow(int x) const {
+        return kSigned ? __builtin_amdgcn_sbfe(x, 0u, bits) : (int)__builtin_amdgcn_ubfe((unsigned)x, 0u, bits);
+    }
+    SFM_DEVICE void add(int& acc, int a, int b) const {
+        const int d = narrow(a - b);
+        const int sq = kSigned ? __mul24(d, d) : (int)__umul24((unsigned)d, (unsigned)d);
+        acc += narrow(sq);
+    }
+    SFM_DEVICE double finish(int acc) const { return kSigned ? (double)acc : (double)(unsigned)acc; }
+};
+// any width: 64-bit two's-complement arithmetic wraps modulo 2^64 by itself; a reduction to `bits` is a shift up and an
+// arithmetic (signed) or logical (unsigned) shift back down.  The int64 / uint64 accumulator of np.sum wraps the same way.
+struct WideSsdPolicy {
+    using Acc = unsigned long long;
+    unsigned sh;
+    bool is_signed;
+    SFM_DEVICE explicit WideSsdPolicy(IntKind kind) : sh(64u - (unsigned)kind.bits), is_signed(kind.is_signed != 0) {}
+    SFM_DEVICE static Acc operand(double staged) { return (Acc)__double_as_longlong(staged); }
+    SFM_DEVICE Acc narrow(Acc x) const {
+        const Acc up = x << sh;
+        return is_signed ? (Acc)((long long)up >> sh) : up >> sh;
+    }
+    SFM_DEVICE void add(Acc& acc, Acc a, Acc b) const {
+        const Acc d = narrow(a - b);
+        acc += narrow(d * d);
+    }
+    SFM_DEVICE double finish(Acc acc) const { return is_signed ? (double)(long long)acc : (double)acc; }
+};
+template <int MODE>
+using ModePolicy = std::conditional_t<MODE == kModeNcc || MODE == kModeSsd, FloatPolicy<MODE == kModeSsd>,
+                   std::conditional_t<MODE == kModeSsdWide, WideSsdPolicy, NarrowSsdPolicy<MODE == kModeSsdNarrowSigned>>>;
+
 template <int MODE, bool DIRECT>
 SFM_DEVICE void tile_accumulate(const double* __restrict__ Pa, int64_t stride_a, const double* __restrict__ Pb,
-                                int64_t stride_b, int64_t nA, int64_t nB, int K, int64_t a0, int64_t b0,
-                                double (*sA)[kTileA], double (*sB)[kTileB],
-                                double (&acc)[kRowsPerLane][kColsPerLane], IntKind kind) {
-    const int tid = threadIdx.x;
-    const int ty = tid / 16, tx = tid % 16;
-    if constexpr (MODE == kModeNcc || MODE == kModeSsd) {
+                                int64_t stride_b, int64_t nA, int64_t nB, int K, int64_t a0, int64_t b0, double (*sA)[kTileA],
+                                double (*sB)[kTileB], double (&acc)[kRowsPerLane][kColsPerLane], IntKind kind) {
+    using Policy = ModePolicy<MODE>;
+    const Policy policy(kind);
+    const int ty = threadIdx.x / 16, tx = threadIdx.x % 16;
+    typename Policy::Acc total[kRowsPerLane][kColsPerLane];
 #pragma unroll
-        for (int i = 0; i < kRowsPerLane; ++i)
+    for (int i = 0; i < kRowsPerLane; ++i)   // (a loop, not `= {}`: the narrow modes then need two VGPRs fewer)
 #pragma unroll
-            for (int j = 0; j < kColsPerLane; ++j) acc[i][j] = 0.0;
-        for (int k0 = 0; k0 < K; k0 += kChunk) {
-            const int kc = min(kChunk, K - k0);
-            __syncthreads();
-            stage_chunk<DIRECT>(Pa, stride_a, Pb, stride_b, nA, nB, k0, kc, a0, b0, sA, sB);
-            __syncthreads();
-            for (int kk = 0; kk < kc; ++kk) {
-                double av[kRowsPerLane], bv[kColsPerLane];
+        for (int j = 0; j < kColsPerLane; ++j) total[i][j] = 0;
+    for (int k0 = 0; k0 < K; k0 += kChunk) {
+        const int kc = min(kChunk, K - k0);
+        __syncthreads();
+        stage_chunk<DIRECT>(Pa, stride_a, Pb, stride_b, nA, nB, k0, kc, a0, b0, sA, sB);
+        __syncthreads();
+        for (int kk = 0; kk < kc; ++kk) {
+            decltype(Policy::operand(0.0)) av[kRowsPerLane], bv[kColsPerLane];
 #pragma unroll
-                for (int i = 0; i < kRowsPerLane; ++i) av[i] = sA[kk][ty * kRowsPerLane + i];
+            for (int i = 0; i < kRowsPerLane; ++i) av[i] = Policy::operand(sA[kk][ty * kRowsPerLane + i]);
 #pragma unroll
-                for (int g = 0; g < kColGroups; ++g) {
-                    bv[2 * g] = sB[kk][g * 32 + tx * 2];
-                    bv[2 * g + 1] = sB[kk][g * 32 + tx * 2 + 1];
-                }
-#pragma unroll
-                for (int i = 0; i < kRowsPerLane; ++i)
-#pragma unroll
-                    for (int j = 0; j < kColsPerLane; ++j) {
-                        if (MODE == kModeNcc) {
-                            acc[i][j] += av[i] * bv[j];
-                        } else {
-                            const double d = av[i] - bv[j];
-                            acc[i][j] += d * d;
-                        }
-                    }
+            for (int g = 0; g < kColGroups; ++g) {
+                bv[2 * g] = Policy::operand(sB[kk][g * 32 + tx * 2]);
+                bv[2 * g + 1] = Policy::operand(sB[kk][g * 32 + tx * 2 + 1]);
             }
+#pragma unroll
+            for (int i = 0; i < kRowsPerLane; ++i)
+#pragma unroll
+                for (int j = 0; j < kColsPerLane; ++j) policy.add(total[i][j], av[i], bv[j]);
         }
-    } else if constexpr (MODE == kModeSsdNarrowSigned || MODE == kModeSsdNarrowUnsigned) {
-        // 8 / 16-bit pixels: everything fits 32-bit registers — the low dword of the staged int64 IS the pixel (two's
-        // complement), the difference is reduced to `bits` by one bit-field extract (sign- or zero-extending: the wrap of the
-        // image dtype), its square (|d| < 2^16: a 24-bit multiply, exact in 32 bits) is reduced the same way, and the sum of at
-        // most kNarrowMaxWindow such terms cannot leave 32 bits.
-        constexpr bool kSigned = MODE == kModeSsdNarrowSigned;
-        const unsigned bits = (unsigned)kind.bits;
-        int total[kRowsPerLane][kColsPerLane];
-#pragma unroll
-        for (int i = 0; i < kRowsPerLane; ++i)
-#pragma unroll
-            for (int j = 0; j < kColsPerLane; ++j) total[i][j] = 0;
-        auto narrow = [&](int x) __attribute__((always_inline)) {
-            return kSigned ? __builtin_amdgcn_sbfe(x, 0u, bits) : (int)__builtin_amdgcn_ubfe((unsigned)x, 0u, bits);
-        };
-        for (int k0 = 0; k0 < K; k0 += kChunk) {
-            const int kc = min(kChunk, K - k0);
-            __syncthreads();
-            stage_chunk<DIRECT>(Pa, stride_a, Pb, stride_b, nA, nB, k0, kc, a0, b0, sA, sB);
-            __syncthreads();
-            for (int kk = 0; kk < kc; ++kk) {
-                int av[kRowsPerLane], bv[kColsPerLane];
-#pragma unroll
-                for (int i = 0; i < kRowsPerLane; ++i) av[i] = __double2loint(sA[kk][ty * kRowsPerLane + i]);
-#pragma unroll
-                for (int g = 0; g < kColGroups; ++g) {
-                    bv[2 * g] = __double2loint(sB[kk][g * 32 + tx * 2]);
-                    bv[2 * g + 1] = __double2loint(sB[kk][g * 32 + tx * 2 + 1]);
-                }
-#pragma unroll
-                for (int i = 0; i < kRowsPerLane; ++i)
-#pragma unroll
-                    for (int j = 0; j < kColsPerLane; ++j) {
-                        const int d = narrow(av[i] - bv[j]);
-                        const int sq = kSigned ? __mul24(d, d) : (int)__umul24((unsigned)d, (unsigned)d);
-                        total[i][j] += narrow(sq);
-                    }
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < kRowsPerLane; ++i)
-#pragma unroll
-            for (int j = 0; j < kColsPerLane; ++j) acc[i][j] = kSigned ? (double)total[i][j] : (double)(unsigned)total[i][j];
-    } else {
-        // any width: 64-bit two's-complement arithmetic wraps modulo 2^64 by itself; a reduction to `bits` is a shift up and an
-        // arithmetic (signed) or logical (unsigned) shift back down.  The int64 / uint64 accumulator of np.sum wraps the same way.
-        const unsigned sh = 64u - (unsigned)kind.bits;
-        const bool is_signed = kind.is_signed != 0;
-        unsigned long long total[kRowsPerLane][kColsPerLane];
-#pragma unroll
-        for (int i = 0; i < kRowsPerLane; ++i)
-#pragma unroll
-            for (int j = 0; j < kColsPerLane; ++j) total[i][j] = 0ull;
-        auto narrow = [&](unsigned long long x) __attribute__((always_inline)) {
-            const unsigned long long up = x << sh;
-            return is_signed ? (unsigned long long)((long long)up >> sh) : up >> sh;
-        };
-        for (int k0 = 0; k0 < K; k0 += kChunk) {
-            const int kc = min(kChunk, K - k0);
-            __syncthreads();
-            stage_chunk<DIRECT>(Pa, stride_a, Pb, stride_b, nA, nB, k0, kc, a0, b0, sA, sB);
-            __syncthreads();
-            for (int kk = 0; kk < kc; ++kk) {
-                unsigned long long av[kRowsPerLane], bv[kColsPerLane];
-#pragma unroll
-                for (int i = 0; i < kRowsPerLane; ++i) av[i] = (unsigned long long)__double_as_longlong(sA[kk][ty * kRowsPerLane + i]);
-#pragma unroll
-                for (int g = 0; g < kColGroups; ++g) {
-                    bv[2 * g] = (unsigned long long)__double_as_longlong(sB[kk][g * 32 + tx * 2]);
-                    bv[2 * g + 1] = (unsigned long long)__double_as_longlong(sB[kk][g * 32 + tx * 2 + 1]);
-                }
-#pragma unroll
-                for (int i = 0; i < kRowsPerLane; ++i)
-#pragma unroll
-                    for (int j = 0; j < kColsPerLane; ++j) {
-                        const unsigned long long d = narrow(av[i] - bv[j]);
-                        total[i][j] += narrow(d * d);
-                    }
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < kRowsPerLane; ++i)
-#pragma unroll
-            for (int j = 0; j < kColsPerLane; ++j)
-                acc[i][j] = is_signed ? (double)(long long)total[i][j] : (double)total[i][j];
     }
+#pragma unroll
+    for (int i = 0; i < kRowsPerLane; ++i)
+#pragma unroll
+        for (int j = 0; j < kColsPerLane; ++j) acc[i][j] = policy.finish(total[i][j]);
 }
 
 // Window sum -> score.  NCC: (num / sqrt(qa qb)) * -1 + 1, 2.0 if a window is out of the image or the denominator is zero
@@ -306,6 +266,18 @@ SFM_DEVICE double finish_score(double acc, bool inside, double qa, double qb, in
     return inside ? acc / (double)K : INFINITY;
 }
 
+// Head of both tile kernels: the block's tile, its first row a0 and column b0, this lane's 8 x 8 window sums; false: no tile
+template <int MODE, bool DIRECT>
+SFM_DEVICE bool tile_sums(const double* __restrict__ Pa, int64_t stride_a, const double* __restrict__ Pb, int64_t stride_b,
+                          int64_t nA, int64_t nB, int K, double (*sA)[kTileA], double (*sB)[kTileB], IntKind kind,
+                          TileCoord& tile, int64_t& a0, int64_t& b0, double (&acc)[kRowsPerLane][kColsPerLane]) {
+    tile = decode_tile((nA + kTileA - 1) / kTileA, (nB + kTileB - 1) / kTileB);
+    a0 = tile.a_tile * kTileA;
+    b0 = tile.b_tile * kTileB;
+    if (tile.valid) tile_accumulate<MODE, DIRECT>(Pa, stride_a, Pb, stride_b, nA, nB, K, a0, b0, sA, sB, acc, kind);
+    return tile.valid;
+}
+
 template <int MODE, bool DIRECT>
 __global__ __launch_bounds__(256, 2) void pair_scores_kernel(
     const double* __restrict__ Pa, int64_t stride_a, const double* __restrict__ Pb, int64_t stride_b,
@@ -314,11 +286,10 @@ __global__ __launch_bounds__(256, 2) void pair_scores_kernel(
     __shared__ double sA[kChunk][kTileA];
     __shared__ double sB[kChunk][kTileB];
     const int ty = threadIdx.x / 16, tx = threadIdx.x % 16;
-    const TileCoord tile = decode_tile((nA + kTileA - 1) / kTileA, (nB + kTileB - 1) / kTileB);
-    if (!tile.valid) return;  // whole block
-    const int64_t a0 = tile.a_tile * kTileA, b0 = tile.b_tile * kTileB;
+    TileCoord tile;
+    int64_t a0, b0;
     double acc[kRowsPerLane][kColsPerLane];
-    tile_accumulate<MODE, DIRECT>(Pa, stride_a, Pb, stride_b, nA, nB, K, a0, b0, sA, sB, acc, kind);
+    if (!tile_sums<MODE, DIRECT>(Pa, stride_a, Pb, stride_b, nA, nB, K, sA, sB, kind, tile, a0, b0, acc)) return;
 #pragma unroll
     for (int i = 0; i < kRowsPerLane; ++i) {
         const int64_t ia = a0 + ty * kRowsPerLane + i;
@@ -433,11 +404,10 @@ __global__ __launch_bounds__(256, 2) void pair_summary_kernel(
     __shared__ double sA[kChunk][kTileA];
     __shared__ double sB[kChunk][kTileB];
     const int ty = threadIdx.x / 16, tx = threadIdx.x % 16;
-    const TileCoord tile = decode_tile((nA + kTileA - 1) / kTileA, (nB + kTileB - 1) / kTileB);
-    if (!tile.valid) return;  // whole block
-    const int64_t a0 = tile.a_tile * kTileA, b0 = tile.b_tile * kTileB;
+    TileCoord tile;
+    int64_t a0, b0;
     double acc[kRowsPerLane][kColsPerLane];
-    tile_accumulate<MODE, DIRECT>(Pa, stride_a, Pb, stride_b, nA, nB, K, a0, b0, sA, sB, acc, kind);
+    if (!tile_sums<MODE, DIRECT>(Pa, stride_a, Pb, stride_b, nA, nB, K, sA, sB, kind, tile, a0, b0, acc)) return;
     // Per-column and per-row operands of this lane's 8 x 8 block, fetched in one batch: unconditional loads at
     // clamped indices (a predicated load per element compiles to load -> wait -> next load, 32 memory latencies in a
     // row at two waves per SIMD — it was most of the kernel's fixed 1.5 ms).
@@ -587,6 +557,41 @@ int decode_metric(int metric, int window_elements, IntKind* kind) {
     return kModeSsdWide;
 }
 
+// What both entry points work out before launching.  Refuses nothing: each tests `mode` and `blocks` in its own order.
+struct TilePlan {
+    int mode;                  // -1: unknown metric
+    IntKind kind;
+    int64_t tiles_b, blocks;   // blocks: the 1-D grid (decode_tile); beyond 2^31 - 1: too many tiles
+    bool direct;
+};
+TilePlan plan_tiles(int metric, int window_elements, const double* patches_a, int64_t stride_a, int64_t n_a,
+                    const double* patches_b, int64_t stride_b, int64_t n_b) {
+    TilePlan p;
+    p.mode = decode_metric(metric, window_elements, &p.kind);
+    const int64_t tiles_a = (n_a + kTileA - 1) / kTileA;
+    p.tiles_b = (n_b + kTileB - 1) / kTileB;
+    p.blocks = 8 * ((tiles_a + 7) / 8) * p.tiles_b;
+    p.direct = direct_staging_ok(patches_a, stride_a, n_a) && direct_staging_ok(patches_b, stride_b, n_b);
+    return p;
+}
+
+// (plan.mode, plan.direct) -> the instantiation, launched.  `kernel_of(mode, direct)` names the kernel family: it returns the
+// kernel for a std::integral_constant mode and a std::bool_constant staging.  `args`: the kernel's arguments up to `kind`.
+template <class KernelOf, class... Args>
+void launch_tile_kernel(KernelOf kernel_of, const TilePlan& plan, hipStream_t stream, Args... args) {
+    auto launch = [&](auto mode, auto direct) {
+        hipLaunchKernelGGL(kernel_of(mode, direct), dim3((unsigned)plan.blocks), dim3(256), 0, stream, args..., plan.kind);
+    };
+    auto staged = [&](auto mode) { plan.direct ? launch(mode, std::true_type{}) : launch(mode, std::false_type{}); };
+    switch (plan.mode) {
+        case kModeNcc: staged(std::integral_constant<int, kModeNcc>{}); break;
+        case kModeSsd: staged(std::integral_constant<int, kModeSsd>{}); break;
+        case kModeSsdNarrowSigned: staged(std::integral_constant<int, kModeSsdNarrowSigned>{}); break;
+        case kModeSsdNarrowUnsigned: staged(std::integral_constant<int, kModeSsdNarrowUnsigned>{}); break;
+        default: staged(std::integral_constant<int, kModeSsdWide>{}); break;
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -612,29 +617,14 @@ int sfm_pair_scores(int metric, const double* patches_a, int64_t stride_a, const
                     const uint8_t* ok_b, int64_t n_a, int64_t n_b, int window_elements, double* scores,
                     void* stream) {
     if (n_a < 0 || n_b < 0 || window_elements < 1) return fail(SFM_EINVAL, "sfm_pair_scores: bad size");
-    IntKind kind;
-    const int mode = decode_metric(metric, window_elements, &kind);
-    if (mode < 0) return fail(SFM_EINVAL, "sfm_pair_scores: unknown metric");
+    const TilePlan plan = plan_tiles(metric, window_elements, patches_a, stride_a, n_a, patches_b, stride_b, n_b);
+    if (plan.mode < 0) return fail(SFM_EINVAL, "sfm_pair_scores: unknown metric");
     if (n_a == 0 || n_b == 0) return SFM_OK;
     if (!patches_a || !patches_b || !ssq_a || !ssq_b || !ok_a || !ok_b || !scores)
         return fail(SFM_EINVAL, "sfm_pair_scores: null pointer");
-    const int64_t tiles_a = (n_a + kTileA - 1) / kTileA, tiles_b = (n_b + kTileB - 1) / kTileB;
-    if (8 * ((tiles_a + 7) / 8) * tiles_b > 0x7FFFFFFF) return fail(SFM_EINVAL, "sfm_pair_scores: too many tiles");
-    const dim3 grid(tile_grid(tiles_a, tiles_b));
-    const bool direct = direct_staging_ok(patches_a, stride_a, n_a) && direct_staging_ok(patches_b, stride_b, n_b);
-    auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, (hipStream_t)stream, patches_a, stride_a, patches_b, stride_b,
-                           ssq_a, ssq_b, ok_a, ok_b, n_a, n_b, window_elements, scores, kind);
-    };
-#define SFM_LAUNCH_MODE(M) do { if (direct) launch(pair_scores_kernel<M, true>); else launch(pair_scores_kernel<M, false>); } while (0)
-    switch (mode) {
-        case kModeNcc: SFM_LAUNCH_MODE(kModeNcc); break;
-        case kModeSsd: SFM_LAUNCH_MODE(kModeSsd); break;
-        case kModeSsdNarrowSigned: SFM_LAUNCH_MODE(kModeSsdNarrowSigned); break;
-        case kModeSsdNarrowUnsigned: SFM_LAUNCH_MODE(kModeSsdNarrowUnsigned); break;
-        default: SFM_LAUNCH_MODE(kModeSsdWide); break;
-    }
-#undef SFM_LAUNCH_MODE
+    if (plan.blocks > 0x7FFFFFFF) return fail(SFM_EINVAL, "sfm_pair_scores: too many tiles");
+    launch_tile_kernel([](auto mode, auto direct) { return pair_scores_kernel<mode(), direct()>; }, plan, (hipStream_t)stream,
+                       patches_a, stride_a, patches_b, stride_b, ssq_a, ssq_b, ok_a, ok_b, n_a, n_b, window_elements, scores);
     return check_launch("pair_scores_kernel");
 }
 
@@ -648,9 +638,8 @@ int sfm_match_summary(int metric, const double* patches_a, int64_t stride_a, con
                       const uint8_t* ok_b, int64_t n_a, int64_t n_b, int window_elements, void* workspace,
                       int64_t workspace_bytes, double* best, int32_t* arg, double* second, void* stream) {
     if (n_a < 0 || n_b < 0 || window_elements < 1) return fail(SFM_EINVAL, "sfm_match_summary: bad size");
-    IntKind kind;
-    const int mode = decode_metric(metric, window_elements, &kind);
-    if (mode < 0) return fail(SFM_EINVAL, "sfm_match_summary: unknown metric");
+    const TilePlan plan = plan_tiles(metric, window_elements, patches_a, stride_a, n_a, patches_b, stride_b, n_b);
+    if (plan.mode < 0) return fail(SFM_EINVAL, "sfm_match_summary: unknown metric");
     if (n_a == 0) return SFM_OK;
     if (n_b == 0) return fail(SFM_EINVAL, "sfm_match_summary: empty rows");
     if (n_b > 0x7FFFFFFF) return fail(SFM_EINVAL, "sfm_match_summary: rows too long");
@@ -660,28 +649,13 @@ int sfm_match_summary(int metric, const double* patches_a, int64_t stride_a, con
         return fail(SFM_EINVAL, "sfm_match_summary: workspace smaller than sfm_match_summary_workspace_bytes(n_a, n_b)");
     if ((reinterpret_cast<uintptr_t>(workspace) & 15u) != 0)
         return fail(SFM_EINVAL, "sfm_match_summary: workspace must be 16-byte aligned");
-    const int64_t n_tiles = (n_b + kTileB - 1) / kTileB;
-    const int64_t tiles_a = (n_a + kTileA - 1) / kTileA;
-    if (8 * ((tiles_a + 7) / 8) * n_tiles > 0x7FFFFFFF) return fail(SFM_EINVAL, "sfm_match_summary: too many tiles");
+    if (plan.blocks > 0x7FFFFFFF) return fail(SFM_EINVAL, "sfm_match_summary: too many tiles");
     SFM_REQUIRE_GRID("sfm_match_summary", n_a, 256, 256);
-    const dim3 grid(tile_grid(tiles_a, n_tiles));
     TileSummary* tiles = static_cast<TileSummary*>(workspace);
     hipStream_t st = (hipStream_t)stream;
-    const bool direct = direct_staging_ok(patches_a, stride_a, n_a) && direct_staging_ok(patches_b, stride_b, n_b);
-    auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, patches_a, stride_a, patches_b, stride_b, ssq_a, ssq_b,
-                           ok_a, ok_b, n_a, n_b, window_elements, tiles, kind);
-    };
-#define SFM_LAUNCH_MODE(M) do { if (direct) launch(pair_summary_kernel<M, true>); else launch(pair_summary_kernel<M, false>); } while (0)
-    switch (mode) {
-        case kModeNcc: SFM_LAUNCH_MODE(kModeNcc); break;
-        case kModeSsd: SFM_LAUNCH_MODE(kModeSsd); break;
-        case kModeSsdNarrowSigned: SFM_LAUNCH_MODE(kModeSsdNarrowSigned); break;
-        case kModeSsdNarrowUnsigned: SFM_LAUNCH_MODE(kModeSsdNarrowUnsigned); break;
-        default: SFM_LAUNCH_MODE(kModeSsdWide); break;
-    }
-#undef SFM_LAUNCH_MODE
-    hipLaunchKernelGGL(summary_combine_kernel, dim3(grid_for(n_a, 256)), dim3(256), 0, st, tiles, n_a, n_b, n_tiles,
+    launch_tile_kernel([](auto mode, auto direct) { return pair_summary_kernel<mode(), direct()>; }, plan, st, patches_a,
+                       stride_a, patches_b, stride_b, ssq_a, ssq_b, ok_a, ok_b, n_a, n_b, window_elements, tiles);
+    hipLaunchKernelGGL(summary_combine_kernel, dim3(grid_for(n_a, 256)), dim3(256), 0, st, tiles, n_a, n_b, plan.tiles_b,
                        best, arg, second);
     return check_launch("pair_summary_kernel");
 }

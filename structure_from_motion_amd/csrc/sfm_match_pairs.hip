@@ -7,8 +7,8 @@
 // (its columns) and owns the output rows row_offset[q] .. row_offset[q + 1] - 1, one per feature of image i.
 //
 //   match_pairs_nearest_kernel   grid (row blocks of the largest image, pairs, 2 directions), 256 lanes, one row per lane;
-//                                direction 1 swaps the two images.  The lane keeps its descriptor in eight registers, the other
-//                                image passes through LDS in tiles of 512 descriptors read as broadcasts, and the lane carries
+//                                direction 1 swaps the two images.  The other image passes through the tile of
+//                                sfm_hamming_tile.h 512 descriptors at a time, and the lane carries
 //                                (best, arg, second) over ALL tiles itself: v < best moves best to second and takes the column,
 //                                else v < second takes second.  Scanning in column order with strict comparisons leaves the
 //                                smallest column of the smallest distance and the smallest distance among the other columns.
@@ -24,6 +24,7 @@
 #include <stdint.h>
 
 #include "sfm_common.h"
+#include "sfm_hamming_tile.h"
 #include "sfm_math.h"
 
 namespace {
@@ -32,8 +33,8 @@ using sfmhost::check_launch;
 using sfmhost::fail;
 using sfmhost::grid_for;
 
-constexpr int kRows = 256;                          // rows per block, one per lane
-constexpr int kCols = 512;                          // descriptors of the other image per LDS tile: 16 KiB plus the flags
+using sfmham::kCols;                                // descriptors of the other image per LDS tile
+using sfmham::kRows;                                // rows per block, one per lane
 constexpr int kNone = 0x7FFFFFFF;                   // no distance: above every Hamming distance (<= 256)
 constexpr int64_t kMaxPairs = 65535;                // the grid's y extent
 
@@ -72,36 +73,26 @@ SFM_DEVICE PairView pair_view(const In& in, int q) {
 
 __global__ __launch_bounds__(kRows) void match_pairs_nearest_kernel(In in, const uint4* __restrict__ desc,
                                                                     const uint8_t* __restrict__ ok, Ws ws) {
-    __shared__ uint4 s_b[kCols][2];
-    __shared__ int s_ok[kCols];
-    const int tid = threadIdx.x, q = blockIdx.y, dir = blockIdx.z;
+    __shared__ sfmham::Tile s_b;
+    const int q = blockIdx.y, dir = blockIdx.z;
     const PairView p = pair_view(in, q);   // block-uniform
     if (!p.ok) return;
     const int self0 = dir ? p.oj : p.oi, n_self = dir ? p.nj : p.ni;
     const int other0 = dir ? p.oi : p.oj, n_other = dir ? p.ni : p.nj;
     const int row0 = blockIdx.x * kRows;
     if (row0 >= n_self) return;            // block-uniform and before the first barrier
-    const int row = row0 + tid;
-    const int64_t src = self0 + min(row, n_self - 1);
-    const uint4 a0 = desc[2 * src], a1 = desc[2 * src + 1];
-    const bool a_valid = ok[src] != 0;
+    const int row = row0 + threadIdx.x;
+    const sfmham::Row a = sfmham::load_row(desc, ok, self0 + min(row, n_self - 1));
     int best = kNone, arg = -1, second = kNone;
     for (int c0 = 0; c0 < n_other; c0 += kCols) {
         const int cols = min(kCols, n_other - c0);
         __syncthreads();                   // the previous tile has been scanned by every lane
-        for (int k = tid; k < cols; k += kRows) {
-            const int64_t b = (int64_t)other0 + c0 + k;
-            s_b[k][0] = desc[2 * b];
-            s_b[k][1] = desc[2 * b + 1];
-            s_ok[k] = ok[b] != 0;
-        }
+        sfmham::stage(s_b, desc, ok, (int64_t)other0 + c0, cols);
         __syncthreads();
 #pragma unroll 4
         for (int k = 0; k < cols; ++k) {
-            const uint4 b0 = s_b[k][0], b1 = s_b[k][1];
-            const int d = __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
-                          __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
-            const int v = s_ok[k] ? d : kNone;       // an invalid column is below nothing
+            const int d = SFM_HAMMING_DISTANCE(a, s_b, k);
+            const int v = s_b.ok[k] ? d : kNone;       // an invalid column is below nothing
             if (v < best) {                          // strict: the first minimum keeps its column
                 second = best;
                 best = v;
@@ -112,7 +103,7 @@ __global__ __launch_bounds__(kRows) void match_pairs_nearest_kernel(In in, const
         }
     }
     if (row >= n_self) return;
-    if (!a_valid) {
+    if (!a.valid) {
         best = second = kNone;
         arg = -1;
     }

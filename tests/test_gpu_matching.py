@@ -211,8 +211,79 @@ def test_unpadded_patch_layout_takes_the_fallback_staging():
         np.testing.assert_array_equal(second.cpu().numpy(), want_sum[2])
 
 
+# ---- every mode of the tile core x both stagings x both entry points -----------------------------------------------------
+# mode -> (metric of the public API, image dtype, oracle): NCC and float SSD on a float64 image, the narrow signed, the narrow
+# unsigned and the wide integer SSD
+TILE_CORE_MODES = {"ncc": (0, "float64", mo.ncc_scores), "ssd": (1, "float64", mo.ssd_scores),
+                   "int8": (1, "int8", mo.ssd_scores_in_dtype), "uint8": (1, "uint8", mo.ssd_scores_in_dtype),
+                   "int32": (1, "int32", mo.ssd_scores_in_dtype)}
+
+
+@functools.lru_cache(maxsize=None)
+def _tile_core_case(mode):
+    """Patches of 131 x 203 features (two tiles per side with a ragged edge) with window 7 (49 elements: one full chunk of 32 and
+    a partial one) in the padded layout of _extract_patches, and the oracle's scores and summaries: once per mode."""
+    metric, dtype, oracle = TILE_CORE_MODES[mode]
+    rng = np.random.default_rng(17)
+    H, W, ws, nA, nB = 80, 100, 7, 131, 203
+    if dtype == "float64":
+        ia = rng.integers(0, 256, (H, W)).astype(np.float64)
+        ib = np.roll(ia, (1, 1), axis=(0, 1))
+    else:
+        info = np.iinfo(np.dtype(dtype))   # the full range: differences and squares wrap all the time
+        ia = rng.integers(info.min, info.max, (H, W), dtype=np.dtype(dtype), endpoint=True)
+        ib = rng.integers(info.min, info.max, (H, W), dtype=np.dtype(dtype), endpoint=True)
+    fa = np.column_stack([rng.integers(0, W, nA), rng.integers(0, H, nA)]).astype(np.float64)   # some windows leave the image
+    fb = np.column_stack([rng.integers(0, W, nB), rng.integers(0, H, nB)]).astype(np.float64)
+    a, b, K, device_metric = _device_match._extract_patches(metric, ia, ib, feats(fa), feats(fb), ws)
+    assert K == 49 and a[3] == nA and b[3] == nB
+    want = oracle(ia, ib, fa, fb, ws)
+    outside = want == 2.0 if mode == "ncc" else np.isinf(want)
+    assert outside.any() and not outside.all()
+    return a, b, K, device_metric, want, mo.row_summary(want)
+
+
+@pytest.mark.parametrize("entry", ["scores", "summary"])
+@pytest.mark.parametrize("staging", ["padded", "tight"])
+@pytest.mark.parametrize("mode", list(TILE_CORE_MODES))
+def test_every_tile_core_mode_through_both_stagings_and_entry_points(mode, staging, entry):
+    """Bit-equal to the NumPy oracle whichever way the patches reach LDS: rows padded to whole tiles and 16-byte aligned (LDS-DMA
+    staging), or the same patches in a tight odd-stride layout at an 8-byte offset (the fallback staging)."""
+    from structure_from_motion_amd import _native, device
+
+    lib = _native.load()
+    (pa, qa, oka, nA), (pb, qb, okb, nB), K, metric, want, want_summary = _tile_core_case(mode)
+    if staging == "tight":
+        ta = torch.empty(K * nA + 1, dtype=torch.float64, device="cuda")[1:].view(K, nA)
+        tb = torch.empty(K * nB + 1, dtype=torch.float64, device="cuda")[1:].view(K, nB)
+        ta.view(torch.int64).copy_(pa[:, :nA].view(torch.int64))    # (bit patterns: copied as integers, whatever they hold)
+        tb.view(torch.int64).copy_(pb[:, :nB].view(torch.int64))
+        assert ta.data_ptr() % 16 == 8 and tb.data_ptr() % 16 == 8 and nA % 2 == 1 and nB % 2 == 1
+    else:
+        ta, tb = pa, pb
+        assert ta.data_ptr() % 16 == 0 and tb.data_ptr() % 16 == 0 and ta.shape[1] == 256 and tb.shape[1] == 256
+    st = device._stream()
+    if entry == "scores":
+        scores = torch.empty((nA, nB), dtype=torch.float64, device="cuda")
+        _native.check(lib.sfm_pair_scores(metric, ta.data_ptr(), ta.shape[1], tb.data_ptr(), tb.shape[1], qa.data_ptr(),
+                                          qb.data_ptr(), oka.data_ptr(), okb.data_ptr(), nA, nB, K, scores.data_ptr(), st), "scores")
+        np.testing.assert_array_equal(scores.cpu().numpy(), want)
+        return
+    nbytes = int(lib.sfm_match_summary_workspace_bytes(nA, nB))
+    wsp = torch.empty(nbytes // 8, dtype=torch.float64, device="cuda")
+    best = torch.empty(nA, dtype=torch.float64, device="cuda")
+    arg = torch.empty(nA, dtype=torch.int32, device="cuda")
+    second = torch.empty(nA, dtype=torch.float64, device="cuda")
+    _native.check(lib.sfm_match_summary(metric, ta.data_ptr(), ta.shape[1], tb.data_ptr(), tb.shape[1], qa.data_ptr(),
+                                        qb.data_ptr(), oka.data_ptr(), okb.data_ptr(), nA, nB, K, wsp.data_ptr(), nbytes,
+                                        best.data_ptr(), arg.data_ptr(), second.data_ptr(), st), "summary")
+    np.testing.assert_array_equal(best.cpu().numpy(), want_summary[0])
+    np.testing.assert_array_equal(arg.cpu().numpy(), want_summary[1])
+    np.testing.assert_array_equal(second.cpu().numpy(), want_summary[2])
+
+
 # ---- SSD on integer images: the reference computes in the image dtype (ssd.py:31-36), golden G14 ------------------------------
-INT_DTYPES = ("uint8", "int8", "uint16", "int16", "uint32", "int32", "uint64", "int64")
+INT_DTYPES =("uint8", "int8", "uint16", "int16", "uint32", "int32", "uint64", "int64")
 
 
 @pytest.mark.parametrize("name", INT_DTYPES)
