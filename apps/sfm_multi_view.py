@@ -45,6 +45,11 @@ route, and ``bundle`` holds the cost of the first adjustment before and after.
 ``bundle_loss`` (``--bundle-loss``) gives every bundle adjustment a robust loss (``"huber"`` or ``"cauchy"`` with
 ``bundle_loss_scale`` pixels); the drop rules stay as they are, and ``rms_px`` is then computed from the
 squared errors of the adjusted observations, since the adjuster's cost is a sum of rho.
+
+``focal_error`` (``--focal-error 0.05``) runs the whole pipeline with a camera matrix whose focal lengths are that fraction
+off, as a guess from image metadata would be.  ``bundle_refine`` (``--bundle-refine focal[,principal_point]``) frees those
+intrinsics in the final bundle adjustment (the dense solver, so at most 64 views).  With either, the output
+holds ``focal``: the relative focal error before and after, and the camera matrix the run ends with.
 """
 from __future__ import annotations
 
@@ -168,9 +173,10 @@ class Reconstruction:
         e = _errors(self.K, self.poses, self.X, self.cam[use], self.pt[use], self.uv[use])
         self.active[use[~(e <= self.threshold)]] = False
 
-    def adjust(self, max_steps: int, drop: bool = True):
+    def adjust(self, max_steps: int, drop: bool = True, refine=()):
         """Bundle adjustment of the registered cameras (camera 0 fixed) and the OK points on their active observations
-        (first, with ``drop``, without the observations above the threshold)."""
+        (first, with ``drop``, without the observations above the threshold).  ``refine``: the intrinsics to free; the
+        refined camera matrix then replaces ``self.K``."""
         if drop:
             self.drop_outliers()
         ok = np.nonzero(self.status == device.TRACKS_OK)[0]
@@ -183,7 +189,9 @@ class Reconstruction:
         solver = "iterative" if auto else "dense"
         poses, X, info = bundle_adjust(self.K, self.poses[self.registered], self.X[ok], cam_slot[self.cam[use]],
                                        pt_slot[self.pt[use]], self.uv[use], fixed_cameras=(0,), max_steps=max_steps,
-                                       linear_solver=solver, **self.loss)
+                                       linear_solver=solver, refine_intrinsics=refine, **self.loss)
+        if refine and info.status == device.BUNDLE_OK:
+            self.K = info.camera_matrix
         self.poses[self.registered] = poses
         self.X[ok] = X
         self.adjusted = use
@@ -281,7 +289,8 @@ def run(views: int = 8, points: int = 2000, seed: int = 21, noise_px: float = 0.
         details: bool = False, pnp_solver: str = "dlt", e_solver: str = "eight_point", tracks: str = "given",
         bundle_loss: str = "squared", bundle_loss_scale: float = 2.0, verify: str = "loop", seed_pair: str = "first",
         seed_min_angle_deg: float = 2.0, rotations: str = "incremental", drop_inconsistent_pairs_deg=None,
-        positions: str = "incremental", register: str = "incremental") -> dict:
+        positions: str = "incremental", register: str = "incremental", focal_error: float = 0.0,
+        bundle_refine=()) -> dict:
     if pnp_solver not in ("dlt", "p3p"):
         raise ValueError(f"pnp_solver must be 'dlt' or 'p3p', got {pnp_solver!r}")
     if e_solver not in ("eight_point", "five_point"):
@@ -321,7 +330,17 @@ def run(views: int = 8, points: int = 2000, seed: int = 21, noise_px: float = 0.
     limit = DENSE_MAX_VIEWS if bundle_solver == "dense" else MAX_VIEWS
     if not 2 <= views <= limit:
         raise ValueError(f"between 2 and {limit} views are supported with bundle_solver={bundle_solver!r}, got {views}")
+    bundle_refine = tuple(bundle_refine) if not isinstance(bundle_refine, str) else bundle_refine
+    if _native.bundle_refine_mask(bundle_refine) and views > DENSE_MAX_VIEWS:
+        raise ValueError(f"bundle_refine needs the dense solver: at most {DENSE_MAX_VIEWS} views, got {views}")
+    if not (np.isfinite(focal_error) and focal_error > -1.0):
+        raise ValueError(f"focal_error must be a finite fraction above -1, got {focal_error!r}")
     scene = synthetic.multi_view_scene(views, points, seed, noise_px, outlier_fraction, step_deg=step_deg)
+    K_true = scene["K"]
+    if focal_error != 0.0:   # every stage sees the wrong camera matrix
+        K_wrong = np.array(K_true, dtype=np.float64)
+        K_wrong[:2, :2] *= 1.0 + focal_error
+        scene = dict(scene, K=K_wrong)
     build, graph, averaged, positioned = None, None, None, None
     if tracks == "matches":
         scene, build_info, pure, kept_pairs, kinds, graph, averaged, positioned = tracks_from_matches(
@@ -418,12 +437,12 @@ def run(views: int = 8, points: int = 2000, seed: int = 21, noise_px: float = 0.
                         ba_status=info.status))
 
     # 5. final bundle adjustment
-    info, m = rec.adjust(final_ba_steps)
+    info, m = rec.adjust(final_ba_steps, refine=bundle_refine)
     if bundle_loss == "squared":
         sum_sq = info.final_cost
     else:   # final_cost is a sum of rho there: the squared errors of the adjusted observations
         a = rec.adjusted
-        sum_sq = float(np.sum(_errors(K, rec.poses, rec.X, cam[a], pt[a], uv[a])))
+        sum_sq = float(np.sum(_errors(rec.K, rec.poses, rec.X, cam[a], pt[a], uv[a])))
     truth = scene["poses_true"]
     if auto_seed:   # the gauge of the seed: the true poses relative to view va, in units of the pair's true baseline
         Ra, ta = truth[va, :9].reshape(3, 3), truth[va, 9:]
@@ -445,6 +464,10 @@ def run(views: int = 8, points: int = 2000, seed: int = 21, noise_px: float = 0.
         "points_ok": int(np.count_nonzero(rec.status == device.TRACKS_OK)),
         "steps": log,
     }
+    if focal_error != 0.0 or bundle_refine:
+        out["focal"] = {"true": float(K_true[0, 0]), "error_before": float(abs(K[0, 0] / K_true[0, 0] - 1.0)),
+                        "error_after": float(abs(rec.K[0, 0] / K_true[0, 0] - 1.0)),
+                        "camera_matrix": [float(v) for v in np.asarray(rec.K).reshape(9)]}
     if build is not None:
         out["track_build"] = build
     if auto_seed:
@@ -543,7 +566,20 @@ def main():
     ap.add_argument("--bundle-loss", choices=BUNDLE_LOSSES, default="squared",
                     help="loss of every bundle adjustment: squared, huber or cauchy")
     ap.add_argument("--bundle-loss-scale", type=float, default=2.0, help="scale of a huber or cauchy loss in pixels")
+    ap.add_argument("--focal-error", type=float, default=0.0,
+                    help="run the pipeline with a camera matrix whose focal lengths are this fraction off (0.05: 5 %% too long)")
+    ap.add_argument("--bundle-refine", default="", metavar="focal[,principal_point]",
+                    help="intrinsics the final bundle adjustment refines (at most 64 views)")
     args = ap.parse_args()
+    refine = tuple(name for name in args.bundle_refine.split(",") if name)
+    try:
+        _native.bundle_refine_mask(refine)
+    except ValueError as e:
+        ap.error(f"--bundle-refine: {e}")
+    if refine and args.views > DENSE_MAX_VIEWS:
+        ap.error(f"--bundle-refine needs at most {DENSE_MAX_VIEWS} views")
+    if not (np.isfinite(args.focal_error) and args.focal_error > -1.0):
+        ap.error("--focal-error must be a finite fraction above -1")
     limit = DENSE_MAX_VIEWS if args.bundle_solver == "dense" else MAX_VIEWS
     if not 2 <= args.views <= limit:
         ap.error(f"--views must be between 2 and {limit} with --bundle-solver {args.bundle_solver}")
@@ -564,7 +600,7 @@ def main():
                          bundle_loss_scale=args.bundle_loss_scale, verify=args.verify, seed_pair=args.seed_pair,
                          seed_min_angle_deg=args.seed_min_angle, rotations=args.rotations,
                          drop_inconsistent_pairs_deg=args.drop_inconsistent_pairs, positions=args.positions,
-                         register=args.register)))
+                         register=args.register, focal_error=args.focal_error, bundle_refine=refine)))
 
 
 if __name__ == "__main__":

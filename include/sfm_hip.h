@@ -628,6 +628,42 @@ int sfm_bundle_adjust_pcg_ex(const double* K, int64_t cameras, int64_t points, i
                              double cg_tolerance, double* poses_out, double* points_out, sfm_bundle_pcg_info* info,
                              void* workspace, int64_t workspace_bytes, void* stream, const sfm_bundle_options* options);
 
+/* ---- shared intrinsics refined by the dense bundle adjuster (csrc/sfm_bundle.hip; an extension, off unless asked for) ----
+ * These symbols were added under ABI 15 without a version change: they are new, and nothing an ABI-15 caller uses changed. */
+
+#define SFM_BUNDLE_REFINE_FOCAL 1           /* f = K[0,0] */
+#define SFM_BUNDLE_REFINE_PRINCIPAL_POINT 2 /* cx = K[0,2] and cy = K[1,2], free or held together */
+
+typedef struct sfm_bundle_calibration_options {
+    sfm_bundle_options loss; /* as for sfm_bundle_adjust_ex */
+    int32_t refine;          /* SFM_BUNDLE_REFINE_* bits, at least one */
+    int32_t reserved;        /* 0 */
+} sfm_bundle_calibration_options;
+
+/* Bytes of workspace sfm_bundle_adjust_calibrated needs (at least sfm_bundle_workspace_bytes); -1 for sizes it refuses. */
+int64_t sfm_bundle_calibrated_workspace_bytes(int64_t cameras, int64_t points, int64_t observations);
+
+/* sfm_bundle_adjust_ex with up to three more unknowns theta = (f, cx, cy), shared by all cameras.  A step (df, dcx, dcy)
+ * gives K[0,0] <- f + df, multiplies K[0,1], K[1,0] and K[1,1] by (f + df) / f (the 2 x 2 block keeps its shape and a zero
+ * entry stays exactly zero) and adds (dcx, dcy) to (K[0,2], K[1,2]); an intrinsic whose bit is not set in options->refine is
+ * held.  F is the cost of sfm_bundle_adjust_ex under the current K.  With w the projection, the rows of the new Jacobian
+ * block are dw/df = ((w_0 - K[0,2]) / K[0,0], (w_1 - K[1,2]) / K[0,0]), dw/dcx = (1, 0), dw/dcy = (0, 1), multiplied by
+ * sqrt(w) under a robust loss as the others are.  Its normal-equation blocks are summed over every observation in front of
+ * its camera, those of fixed cameras and of held points included, and after the Schur complement on the points they border
+ * the reduced camera system with 1 to 3 rows, damped by lambda diag as every other block.  A trial K[0,0] that is not finite,
+ * is zero or differs in sign from the input's is a rejected step.  The intrinsics' step counts into |delta| and the free
+ * intrinsics into |x| of the small-step stop; the gauge similarity does not touch them.  The whole call is enqueued at once,
+ * the refined camera matrix is written by its last launch, and a call is bit-reproducible.
+ * K_out: dev [9], row 2 (0, 0, 1); for SFM_BUNDLE_BAD_START and SFM_BUNDLE_BAD_INDEX the input K.  options: not NULL.
+ * SFM_EINVAL before the first launch for a refine outside 1..3, reserved != 0, loss options sfm_bundle_adjust_ex refuses,
+ * K[0,0] == 0 with SFM_BUNDLE_REFINE_FOCAL, and everything else sfm_bundle_adjust_ex refuses.  The workspace is at least
+ * sfm_bundle_calibrated_workspace_bytes.  The other arguments as sfm_bundle_adjust_ex. */
+int sfm_bundle_adjust_calibrated(const double* K, int64_t cameras, int64_t points, int64_t observations, const uint8_t* fixed,
+                                 const double* poses_in, const double* points_in, const int32_t* camera_index,
+                                 const int32_t* point_index, const double* pixels, int max_steps, double* poses_out,
+                                 double* points_out, sfm_bundle_info* info, double* K_out, void* workspace,
+                                 int64_t workspace_bytes, void* stream, const sfm_bundle_calibration_options* options);
+
 /* ---- triangulation of multi-view tracks (csrc/sfm_tracks.hip; an extension, off unless asked for) ----
  * These symbols were added under ABI 14 without a version change: they are new, and nothing an ABI-14 caller uses changed. */
 

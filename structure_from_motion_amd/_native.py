@@ -185,6 +185,7 @@ SIGNATURES = {
     "sfm_bundle_adjust_ex": [_P, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _I64, _P, _P],
     "sfm_bundle_adjust_pcg_ex": [_P, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, _D, _P, _P, _P, _P, _I64, _P,
                                  _P],
+    "sfm_bundle_adjust_calibrated": [_P, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _I64, _P, _P],
     "sfm_triangulate_tracks": [_P, _I64, _I64, _I64, _P, _P, _P, _P, C.c_int, _D, _D, C.c_int, _P, _P, _P, _P, _P, _P, _I64,
                                _P],
     "sfm_build_tracks": [_I64, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P],
@@ -197,7 +198,8 @@ OTHER_SYMBOLS = ["sfm_last_error", "sfm_abi_version", "sfm_score_workspace_bytes
                  "sfm_tracks_workspace_bytes", "sfm_bundle_pcg_workspace_bytes", "sfm_build_tracks_workspace_bytes",
                  "sfm_bundle_pcg_workspace_bytes_ex", "sfm_hamming_summary_workspace_bytes", "sfm_pair_poses_workspace_bytes",
                  "sfm_average_rotations_workspace_bytes", "sfm_average_translations_workspace_bytes",
-                 "sfm_match_pairs_workspace_bytes", "sfm_detect_keypoints_workspace_bytes"]
+                 "sfm_match_pairs_workspace_bytes", "sfm_detect_keypoints_workspace_bytes",
+                 "sfm_bundle_calibrated_workspace_bytes"]
 
 # the losses of both bundle adjusters, in the order of their SFM_BUNDLE_LOSS_* codes (include/sfm_hip.h)
 BUNDLE_LOSSES = ("squared", "huber", "cauchy")
@@ -208,6 +210,27 @@ def loss_scale_ok(a: float) -> bool:
     receives is the one to check; False for NaN."""
     a = float(a)
     return a > 0.0 and 2.2250738585072014e-308 <= a * a <= 1.7976931348623157e308
+
+
+# the intrinsics a calibrating bundle adjustment can free, with their SFM_BUNDLE_REFINE_* bits (include/sfm_hip.h)
+BUNDLE_REFINE = {"focal": 1, "principal_point": 2}
+
+
+def bundle_refine_mask(refine) -> int:
+    """The SFM_BUNDLE_REFINE_* bits of a collection of ``BUNDLE_REFINE`` names (0 for an empty one); ValueError for a
+    string (a name is not a collection of names), something that is no collection, an unknown name or a repeated one."""
+    if isinstance(refine, (str, bytes)):
+        raise ValueError(f"refine_intrinsics must be a collection of {tuple(BUNDLE_REFINE)}, got the string {refine!r}")
+    try:
+        names = list(refine)
+    except TypeError:
+        raise ValueError(f"refine_intrinsics must be a collection of {tuple(BUNDLE_REFINE)}, got {refine!r}") from None
+    for name in names:
+        if not isinstance(name, str) or name not in BUNDLE_REFINE:
+            raise ValueError(f"refine_intrinsics: {name!r} is not one of {tuple(BUNDLE_REFINE)}")
+    if len(set(names)) != len(names):
+        raise ValueError(f"refine_intrinsics: a name is repeated in {names!r}")
+    return sum(BUNDLE_REFINE[name] for name in names)
 
 
 # the kinds of sfm_pair_verdict, in the order of their SFM_PAIR_* codes (include/sfm_hip.h)
@@ -233,6 +256,11 @@ class PairPose(C.Structure):
 class BundleOptions(C.Structure):
     """sfm_bundle_options"""
     _fields_ = [("loss", C.c_int32), ("reserved", C.c_int32), ("loss_scale", C.c_double)]
+
+
+class BundleCalibrationOptions(C.Structure):
+    """sfm_bundle_calibration_options"""
+    _fields_ = [("loss", BundleOptions), ("refine", C.c_int32), ("reserved", C.c_int32)]
 
 
 # the statuses of sfm_average_rotations and sfm_average_translations, in the order of their SFM_ROTAVG_* / SFM_TRANSAVG_* codes
@@ -318,6 +346,8 @@ def load() -> C.CDLL:
     lib.sfm_hamming_summary_workspace_bytes.argtypes = [_I64, _I64]
     lib.sfm_bundle_workspace_bytes.restype = C.c_int64
     lib.sfm_bundle_workspace_bytes.argtypes = [_I64, _I64, _I64]
+    lib.sfm_bundle_calibrated_workspace_bytes.restype = C.c_int64
+    lib.sfm_bundle_calibrated_workspace_bytes.argtypes = [_I64, _I64, _I64]
     lib.sfm_tracks_workspace_bytes.restype = C.c_int64
     lib.sfm_tracks_workspace_bytes.argtypes = [_I64, _I64]
     lib.sfm_bundle_pcg_workspace_bytes.restype = C.c_int64

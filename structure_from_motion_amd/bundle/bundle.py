@@ -1,7 +1,8 @@
 """Bundle adjustment of camera poses and 3-D points on the GPU (``sfm_bundle_adjust``).
 
 Poses are ``R (9) | t (3)`` rows with ``x_cam = R X + t`` — the PnP model layout.  All cameras share one camera matrix
-``K`` whose row 2 is (0, 0, 1); intrinsics are not optimised.  The cost is the sum over the observations of rho(e), e the
+``K`` whose row 2 is (0, 0, 1); its focal length and principal point are refined on request (``refine_intrinsics``, the
+dense solver only) and held otherwise.  The cost is the sum over the observations of rho(e), e the
 squared reprojection error of the PnP scorer and rho the loss: ``"squared"`` (rho = e, the default), ``"huber"`` or
 ``"cauchy"`` with a scale in pixels.  Fixed cameras and points with fewer than two observations are held; with exactly
 one fixed camera the scale is held by the distance from it to the lowest-index free camera.
@@ -18,7 +19,7 @@ import numpy as np
 import numpy.typing as npt
 
 from .._native import BUNDLE_LOSSES as LOSSES
-from .._native import loss_scale_ok
+from .._native import bundle_refine_mask, loss_scale_ok
 from ..pnp.pnp import check_camera_matrix
 
 MAX_CAMERAS = 64   # of the dense solver
@@ -58,6 +59,7 @@ def bundle_adjust(
     cg_tolerance: float = 0.1,
     loss: str = "squared",
     loss_scale: float = 1.0,
+    refine_intrinsics: Sequence[str] = (),
 ):
     """Minimise the summed squared reprojection error over the free cameras' poses and the points.
 
@@ -76,7 +78,15 @@ def bundle_adjust(
     pixels (> 0 with a normal finite square, about 1.5e-154 to 1.3e154; no effect on ``"squared"``): ``"huber"`` is e up to a^2 and 2 a sqrt(e) - a^2 above, ``"cauchy"``
     is a^2 log1p(e / a^2).  ``info.initial_cost`` and ``info.final_cost`` are then the sums of rho(e), not of e, and the
     accept test and the stops use them.  Huber keeps a constant pull of 2 a per pixel on an outlier and suits moderate
-    ones; Cauchy re-descends and suits gross ones."""
+    ones; Cauchy re-descends and suits gross ones.
+
+    ``refine_intrinsics`` is a subset of ``("focal", "principal_point")``; empty (the default) holds ``camera_matrix`` and
+    is the call described above.  ``"focal"`` frees f = K[0,0] (the 2 x 2 block of K is scaled as a whole, so the aspect
+    ratio and the skew keep their proportions), ``"principal_point"`` frees K[0,2] and K[1,2] together; all cameras share
+    them and ``camera_matrix`` is the start.  ``info`` is then a ``device.BundleCalibrationInfo``: the ``BundleInfo`` fields
+    plus ``camera_matrix``, the refined K (the input K when ``info.status`` is not ``BUNDLE_OK``).  A scene must constrain
+    what it frees: cameras that converge on the points do, nearly parallel ones leave the focal length loose (DESIGN.md
+    §6ab).  Only the dense solver refines intrinsics: with ``linear_solver="iterative"`` a non-empty value is a ValueError."""
     K = check_camera_matrix(camera_matrix)
     poses = _array(poses, "poses", (-1, 12))
     points = _array(points_3d, "points_3d", (-1, 3))
@@ -113,11 +123,22 @@ def bundle_adjust(
     if (isinstance(loss_scale, bool) or not isinstance(loss_scale, (int, float, np.integer, np.floating))
             or not loss_scale_ok(float(loss_scale))):
         raise ValueError(f"loss_scale must be a number > 0 with a normal finite square, got {loss_scale!r}")
+    refine = bundle_refine_mask(refine_intrinsics)
+    if refine and iterative:
+        raise ValueError("refine_intrinsics needs linear_solver=\"dense\": the iterative solver holds the camera matrix")
+    if refine & 1 and K[0, 0] == 0.0:
+        raise ValueError("camera_matrix[0, 0] is zero: the focal length cannot be refined")
     import torch
 
     from .. import device
 
     device.require_gpu()
+    if refine:
+        poses_d, points_d, info, K_d = device.bundle_adjust_calibrated(
+            device.to_device(poses), device.to_device(points), device.to_device(cams, dtype=torch.int32),
+            device.to_device(pts, dtype=torch.int32), device.to_device(pixels), K, fixed, int(max_steps),
+            refine=list(refine_intrinsics), loss=loss, loss_scale=float(loss_scale))
+        return poses_d.cpu().numpy(), points_d.cpu().numpy(), device.read_bundle_calibration_info(info, K_d)
     robust = {} if loss == "squared" else dict(loss=loss, loss_scale=float(loss_scale))   # squared: today's call
     if iterative:
         poses_d, points_d, info = device.bundle_adjust_pcg(

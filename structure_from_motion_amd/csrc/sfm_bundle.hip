@@ -22,6 +22,16 @@
 // A robust loss (csrc/sfm_loss.h) runs the kRobust = true forms of linearize_kernel, camera_kernel and
 // bundle_trial_kernel: W, V, U and both gradients are stored weighted, so the Schur complement, the solve and the
 // back-substitution are the same launches, and the workspace is the same size.
+//
+// sfm_bundle_adjust_calibrated runs the kCal = true forms: up to three intrinsics theta = (f, cx, cy) shared by
+// all cameras border the reduced system with q = 1..3 rows.  The camera lives in the workspace (sfmlm::Calib: the current one
+// and the trial one).  linearize_kernel adds W_qp per point and U_qq, g_q per block, camera_kernel U_cq, the diagonal blocks
+// of bundle_schur_kernel sum_i W_i V_p*^-1 W_qp^T, and one more launch per trial step,
+//   bundle_border_kernel    thread per point: sum_p W_qp V_p*^-1 W_qp^T and sum_p W_qp V_p*^-1 g_p, partials per block
+// before bundle_solve_kernel, which factors the order 6F + q system and sets the trial camera; bundle_trial_kernel
+// back-substitutes with -W_qp^T dtheta, commit_kernel keeps the trial camera.  Every intrinsics array is 3 wide, a held
+// intrinsic's entries are zero and the solve skips its row.  A call without a free intrinsic is kCal = false: the
+// instantiations and the bits of before.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -45,8 +55,10 @@ using sfmpnp::PnPCamera;
 
 constexpr int kMaxCameras = sfmlm::kLdsCameras;
 constexpr int kLdsFree = 30;                 // S (packed lower triangle) in LDS up to this many free cameras: 127 KiB
+                                             // (132 KiB with the border of a calibrating call)
 constexpr int kSolveThreads = 1024;          // the one-workgroup solve
 constexpr int kMaxSolve = 6 * (kMaxCameras - 1);
+constexpr int kBorder = 3;                   // the intrinsics a calibrating call can free
 
 static_assert(sizeof(sfm_bundle_info) == 32, "sfm_bundle_info layout is part of the ABI");
 
@@ -54,10 +66,11 @@ struct Ws {
     Lm lm;
     const int32_t* pos_c;   // camera-major position -> point-major position (set after the orders are enqueued)
     double *W, *blk, *rhs, *S;
+    double* Sq;             // kCal: sum_i W_i V_p*^-1 W_qp^T (6 x 3) per free camera's slot
 };
 
 // The workspace from `base` (0: sizes only); its size in bytes.
-int64_t carve(uintptr_t base, int64_t C, int64_t P, int64_t M, Ws* w, sfmlm::Core* core) {
+int64_t carve(uintptr_t base, int64_t C, int64_t P, int64_t M, Ws* w, sfmlm::Core* core, bool cal = false) {
     const int64_t F = C > 0 ? C - 1 : 0;   // at most: at least one camera is fixed
     sfmlm::Carver k{base, 0};
     State* st = k.take<State>(1);
@@ -67,7 +80,17 @@ int64_t carve(uintptr_t base, int64_t C, int64_t P, int64_t M, Ws* w, sfmlm::Cor
     w->W = k.take<double>(18 * M);
     w->blk = k.take<double>(36 * (F * (F + 1) / 2));
     w->rhs = k.take<double>(6 * C);
-    w->S = k.take<double>(F > kLdsFree ? (6 * F) * (6 * F + 1) / 2 : 0);
+    const int64_t n = 6 * F + (cal ? kBorder : 0);
+    w->S = k.take<double>(F > kLdsFree ? n * (n + 1) / 2 : 0);
+    w->Sq = nullptr;
+    if (cal) {   // after everything a plain call has
+        const int64_t blocks = (P + kThreads - 1) / kThreads;
+        w->lm.cal = k.take<sfmlm::Calib>(1);
+        w->lm.Wq = k.take<double>(9 * P);
+        w->lm.Ucq = k.take<double>(18 * C);
+        w->lm.qpart = k.take<double>(18 * (blocks > 0 ? blocks : 1));
+        w->Sq = k.take<double>(18 * F);
+    }
     return k.at;
 }
 
@@ -90,12 +113,27 @@ __global__ __launch_bounds__(kMaxCameras) void bundle_init_kernel(uint64_t fixed
 // ------------------------------------------------------------------------------------------------------------------------
 // The dense solve of the damped reduced camera system.
 // ------------------------------------------------------------------------------------------------------------------------
+// The free intrinsics of a refine mask: their number, and the index in (f, cx, cy) of the s-th
+SFM_DEVICE int border_order(int refine) { return (refine & 1) + (refine & 2); }
+SFM_DEVICE int border_index(int refine, int s) { return (refine & 1) ? s : s + 1; }
+
+__global__ void bundle_calib_init_kernel(sfmlm::Calib* cal, PnPCamera cam, int refine) {
+    cal->cam = cam;
+    cal->trial = cam;
+    cal->dq[0] = cal->dq[1] = cal->dq[2] = 0.0;
+    cal->refine = refine;
+    cal->pad = 0;
+}
+
 // Block per upper block (a, b), a <= b, of the free cameras' slots: blk = sum over pairs (i in a, j in b) of observations
 // of the same moving point p of W_i V_p*^-1 W_j^T.  Thread t takes a contiguous chunk of a's list and walks b's list
-// beside it from a binary search.  On the diagonal blocks also rhs_a = sum_i W_i V_p*^-1 g_p.
+// beside it from a binary search.  On the diagonal blocks also rhs_a = sum_i W_i V_p*^-1 g_p, and (kCal) Sq_a =
+// sum_i W_i V_p*^-1 W_qp^T.
+template <bool kCal>
 __global__ __launch_bounds__(kThreads) void bundle_schur_kernel(int F, Ws w) {
-    __shared__ double part[kThreads / kWave * 42];
-    __shared__ double total[42];
+    constexpr int kSums = kCal ? 60 : 42;
+    __shared__ double part[kThreads / kWave * kSums];
+    __shared__ double total[kSums];
     const Lm& l = w.lm;
     if (l.st->stop || l.st->fail) return;
     // block -> (a, b) in row-major order of the upper triangle
@@ -106,9 +144,9 @@ __global__ __launch_bounds__(kThreads) void bundle_schur_kernel(int F, Ws w) {
     }
     const int b = a + idx;
     const int ca = l.freec[a], cb = l.freec[b];
-    double acc[42];
+    double acc[kSums];
 #pragma unroll
-    for (int k = 0; k < 42; ++k) acc[k] = 0.0;
+    for (int k = 0; k < kSums; ++k) acc[k] = 0.0;
     const int alo = l.off_c[ca], na = l.off_c[ca + 1] - alo;
     const int blo = l.off_c[cb], bhi = l.off_c[cb + 1];
     const int chunk = (na + kThreads - 1) / kThreads;
@@ -146,31 +184,82 @@ __global__ __launch_bounds__(kThreads) void bundle_schur_kernel(int F, Ws w) {
                 const double* g = l.gp + 3 * (int64_t)p;
 #pragma unroll
                 for (int x = 0; x < 6; ++x) acc[36 + x] += (Y[x][0] * g[0] + Y[x][1] * g[1]) + Y[x][2] * g[2];
+                if (kCal) {
+                    const double* Wq = l.Wq + 9 * (int64_t)p;
+#pragma unroll
+                    for (int x = 0; x < 6; ++x)
+#pragma unroll
+                        for (int y = 0; y < 3; ++y)
+                            acc[42 + 3 * x + y] += (Y[x][0] * Wq[3 * y] + Y[x][1] * Wq[3 * y + 1]) + Y[x][2] * Wq[3 * y + 2];
+                }
             }
         }
     }
-    sfm::block_sum<42, kThreads>(acc, part, total);
+    sfm::block_sum<kSums, kThreads>(acc, part, total);
     if (threadIdx.x < 36) w.blk[36 * (int64_t)blockIdx.x + threadIdx.x] = total[threadIdx.x];
     else if (a == b && threadIdx.x < 42) w.rhs[6 * a + threadIdx.x - 36] = total[threadIdx.x];
+    else if (kCal && a == b && threadIdx.x < 60) w.Sq[18 * a + threadIdx.x - 42] = total[threadIdx.x];
+}
+
+// Thread per point: a moving point's share of sum_p W_qp V_p*^-1 W_qp^T (upper 6) and of sum_p W_qp V_p*^-1 g_p; partials
+// per block, behind the block's U_qq and g_q.
+__global__ __launch_bounds__(kThreads) void bundle_border_kernel(int P, Lm l) {
+    __shared__ double part[kThreads / kWave * 9];
+    __shared__ double total[9];
+    if (l.st->stop || l.st->fail) return;
+    const int p = blockIdx.x * kThreads + threadIdx.x;
+    double a[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (p < P && l.off_p[p + 1] - l.off_p[p] >= 2) {
+        double Vi[3][3];
+        sfmlm::sym3(l.Vi + 6 * (int64_t)p, Vi);
+        const double* Wq = l.Wq + 9 * (int64_t)p;
+        const double* g = l.gp + 3 * (int64_t)p;
+        double Y[3][3];
+#pragma unroll
+        for (int x = 0; x < 3; ++x)
+#pragma unroll
+            for (int y = 0; y < 3; ++y) Y[x][y] = (Wq[3 * x] * Vi[0][y] + Wq[3 * x + 1] * Vi[1][y]) + Wq[3 * x + 2] * Vi[2][y];
+#pragma unroll
+        for (int x = 0; x < 3; ++x) {
+#pragma unroll
+            for (int y = x; y < 3; ++y)
+                a[sfmlm::upper3(x, y)] = (Y[x][0] * Wq[3 * y] + Y[x][1] * Wq[3 * y + 1]) + Y[x][2] * Wq[3 * y + 2];
+            a[6 + x] = (Y[x][0] * g[0] + Y[x][1] * g[1]) + Y[x][2] * g[2];
+        }
+    }
+    sfm::block_sum<9, kThreads>(a, part, total);
+    if (threadIdx.x < 9) l.qpart[18 * (int64_t)blockIdx.x + 9 + threadIdx.x] = total[threadIdx.x];
 }
 
 // One workgroup: S = U* - blk (lower triangle, packed), right-hand side -g_c + rhs, Cholesky, both triangular solves;
-// then the camera steps and the trial poses (finish_step).  S lives in LDS (kLds) or in the workspace.
-template <bool kLds>
-__global__ __launch_bounds__(kSolveThreads) void bundle_solve_kernel(int F, int C, const double* __restrict__ poses, Ws w) {
-    constexpr int kLdsN = 6 * kLdsFree;
+// then the camera steps and the trial poses (finish_step).  S lives in LDS (kLds) or in the workspace.  kCal: the system
+// has the q free intrinsics behind the cameras (S_aq = U_aq - Sq_a, S_qq = U_qq* - sum W_qp V_p*^-1 W_qp^T, right-hand side
+// -g_q + sum W_qp V_p*^-1 g_p, the sums over the `blocks` point blocks in their order), and the step sets the trial camera:
+// a trial k00 that is not finite, is zero or changes sign rejects the step.
+template <bool kLds, bool kCal>
+__global__ __launch_bounds__(kSolveThreads) void bundle_solve_kernel(int F, int C, const double* __restrict__ poses, Ws w,
+                                                                     int blocks) {
+    constexpr int kLdsN = 6 * kLdsFree + (kCal ? kBorder : 0);
     __shared__ double lds[kLds ? kLdsN * (kLdsN + 1) / 2 : 1];
-    __shared__ double y[kMaxSolve];
+    __shared__ double y[kMaxSolve + (kCal ? kBorder : 0)];
+    __shared__ double qsum[kCal ? 18 : 1];   // U_qq (upper 6) | g_q | sum W_qp V_p*^-1 W_qp^T (upper 6) | sum W_qp V_p*^-1 g_p
+    __shared__ double dq[kCal ? kBorder : 1];   // the trial step of (f, cx, cy), by thread 0
     __shared__ int ok;
     State* st = w.lm.st;
     if (st->stop) return;
     const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
     constexpr int kWaves = kSolveThreads / kWave;
     if (tid == 0) st->need_lin = 0;   // the linearisation kernels of this step have run
-    const int n = 6 * F;
+    const int refine = kCal ? w.lm.cal->refine : 0;
+    const int n = 6 * F + (kCal ? border_order(refine) : 0);
     double* A = kLds ? lds : w.S;
     if (tid == 0) ok = !st->fail;
     const double lambda = st->lambda;
+    if (kCal && tid < 18) {
+        double s = 0.0;
+        for (int b = 0; b < blocks; ++b) s += w.lm.qpart[18 * (int64_t)b + tid];
+        qsum[tid] = s;
+    }
     __syncthreads();
     if (ok) {
         for (int64_t e = tid; e < (int64_t)n * (n + 1) / 2; e += kSolveThreads) {
@@ -179,6 +268,18 @@ __global__ __launch_bounds__(kSolveThreads) void bundle_solve_kernel(int F, int 
             while ((int64_t)i * (i + 1) / 2 > e) --i;
             while ((int64_t)(i + 1) * (i + 2) / 2 <= e) ++i;
             const int j = (int)(e - (int64_t)i * (i + 1) / 2);
+            if (kCal && i >= 6 * F) {   // a row of the border
+                const int qi = border_index(refine, i - 6 * F);
+                if (j < 6 * F) {
+                    const int a = j / 6, r = j % 6;
+                    A[e] = w.lm.Ucq[18 * w.lm.freec[a] + 3 * r + qi] - w.Sq[18 * a + 3 * r + qi];
+                } else {
+                    const int k = sfmlm::upper3(border_index(refine, j - 6 * F), qi);
+                    const double u = qsum[k];
+                    A[e] = -qsum[9 + k] + (i == j ? u + lambda * u : u);
+                }
+                continue;
+            }
             const int a = j / 6, b = i / 6, r = j % 6, s = i % 6;   // a <= b: element (6a + r, 6b + s) of the upper blocks
             const int64_t pair = (int64_t)a * F - (int64_t)a * (a - 1) / 2 + (b - a);
             double v = -w.blk[36 * pair + 6 * r + s];
@@ -188,7 +289,8 @@ __global__ __launch_bounds__(kSolveThreads) void bundle_solve_kernel(int F, int 
             }
             A[e] = v;
         }
-        for (int i = tid; i < n; i += kSolveThreads) y[i] = -w.lm.gc[6 * w.lm.freec[i / 6] + i % 6] + w.rhs[i];
+        for (int i = tid; i < 6 * F; i += kSolveThreads) y[i] = -w.lm.gc[6 * w.lm.freec[i / 6] + i % 6] + w.rhs[i];
+        if (kCal && tid < n - 6 * F) y[6 * F + tid] = -qsum[6 + border_index(refine, tid)] + qsum[15 + border_index(refine, tid)];
     }
     __syncthreads();
     // right-looking Cholesky, column by column
@@ -229,12 +331,50 @@ __global__ __launch_bounds__(kSolveThreads) void bundle_solve_kernel(int F, int 
             __syncthreads();
         }
     }
+    if (kCal) {
+        if (tid == 0) {
+            sfmlm::Calib* cal = w.lm.cal;
+            PnPCamera t = cal->cam;
+            dq[0] = dq[1] = dq[2] = 0.0;
+            if (ok) {
+                for (int s = 0; s < n - 6 * F; ++s) dq[border_index(refine, s)] = y[6 * F + s];
+                if (refine & SFM_BUNDLE_REFINE_FOCAL) {
+                    const double f = t.k00 + dq[0];
+                    if (!isfinite(f) || f == 0.0 || (f < 0.0) != (t.k00 < 0.0)) {
+                        ok = 0;
+                    } else {
+                        const double ratio = f / t.k00;
+                        t.k00 = f;
+                        t.k01 *= ratio;
+                        t.k10 *= ratio;
+                        t.k11 *= ratio;
+                    }
+                }
+                t.k02 += dq[1];
+                t.k12 += dq[2];
+            }
+            if (!ok) {
+                t = cal->cam;
+                dq[0] = dq[1] = dq[2] = 0.0;
+            }
+            cal->trial = t;
+            for (int k = 0; k < 3; ++k) cal->dq[k] = dq[k];
+        }
+        __syncthreads();
+    }
     sfmlm::finish_step<kSolveThreads>(ok, y, C, poses, w.lm);
+    if (kCal && tid == 0 && ok) {   // the intrinsics' share of |delta|^2 and |x|^2, behind the cameras'
+        const PnPCamera& k = w.lm.cal->cam;
+        st->dn_c += (dq[0] * dq[0] + dq[1] * dq[1]) + dq[2] * dq[2];
+        if (refine & SFM_BUNDLE_REFINE_FOCAL) st->xn_c += k.k00 * k.k00;
+        if (refine & SFM_BUNDLE_REFINE_PRINCIPAL_POINT) st->xn_c += k.k02 * k.k02 + k.k12 * k.k12;
+    }
 }
 
 // Thread per point: dX_p = V_p*^-1 (-g_p - sum over its free-camera observations of W^T dc), the trial point, the trial cost
-// of its observations (kRobust: the sum of rho) and its share of |delta|^2 and |x|^2; partials per block.
-template <bool kRobust>
+// of its observations (kRobust: the sum of rho) and its share of |delta|^2 and |x|^2; partials per block.  kCal: under the
+// trial camera, with -W_qp^T dtheta in the back-substitution.
+template <bool kRobust, bool kCal>
 __global__ __launch_bounds__(kThreads) void bundle_trial_kernel(Obs obs, int P, PnPCamera cam, const double* __restrict__ points,
                                                                 int C, Ws w) {
     __shared__ double pose[kMaxCameras * 12];
@@ -243,6 +383,7 @@ __global__ __launch_bounds__(kThreads) void bundle_trial_kernel(Obs obs, int P, 
     __shared__ double total[3];
     const Lm& l = w.lm;
     if (l.st->stop || !l.st->step_ok) return;
+    if (kCal) cam = l.cal->trial;
     for (int k = threadIdx.x; k < 12 * C; k += kThreads) pose[k] = l.tpose[k];
     for (int k = threadIdx.x; k < 6 * C; k += kThreads) dc[k] = l.dc[k];
     __syncthreads();
@@ -264,6 +405,12 @@ __global__ __launch_bounds__(kThreads) void bundle_trial_kernel(Obs obs, int P, 
                     for (int i = 0; i < 6; ++i) s += Wq[3 * i + j] * dc[6 * c + i];
                     t[j] -= s;
                 }
+            }
+            if (kCal) {
+                const double* Wq = l.Wq + 9 * (int64_t)p;
+                const double* dq = l.cal->dq;
+#pragma unroll
+                for (int j = 0; j < 3; ++j) t[j] -= (Wq[j] * dq[0] + Wq[3 + j] * dq[1]) + Wq[6 + j] * dq[2];
             }
             double Vi[3][3];
             sfmlm::sym3(l.Vi + 6 * (int64_t)p, Vi);
@@ -289,6 +436,14 @@ __global__ __launch_bounds__(kThreads) void bundle_trial_kernel(Obs obs, int P, 
 
 __global__ void bundle_finish_kernel(Lm w, sfm_bundle_info* __restrict__ info) { sfmlm::write_info(w.st, info); }
 
+// The calibrating call's: also the current camera as K_out (the input K after a bad start or a bad index)
+__global__ void bundle_finish_calibrated_kernel(Lm w, sfm_bundle_info* __restrict__ info, double* __restrict__ K_out) {
+    sfmlm::write_info(w.st, info);
+    const PnPCamera& k = w.cal->cam;
+    const double K[9] = {k.k00, k.k01, k.k02, k.k10, k.k11, k.k12, 0.0, 0.0, 1.0};
+    for (int i = 0; i < 9; ++i) K_out[i] = K[i];
+}
+
 // A checked call: everything enqueue needs.
 struct Job {
     PnPCamera cam;
@@ -300,10 +455,12 @@ struct Job {
     double *poses_out, *points_out;
     sfm_bundle_info* info;
     hipStream_t st;
+    int refine;      // kCal: SFM_BUNDLE_REFINE_* bits and where the refined camera matrix goes
+    double* K_out;
 };
 
-// Enqueue the whole call; kRobust picks the kernels of a non-squared loss (w.lm.loss).
-template <bool kRobust>
+// Enqueue the whole call; kRobust picks the kernels of a non-squared loss (w.lm.loss), kCal those that refine intrinsics.
+template <bool kRobust, bool kCal = false>
 int enqueue(const Job& job, Ws& w, const sfmlm::Core& core) {
     const PnPCamera& cam = job.cam;
     const int64_t C = job.C, P = job.P, M = job.M;
@@ -328,13 +485,14 @@ int enqueue(const Job& job, Ws& w, const sfmlm::Core& core) {
         return check_launch("sfm_bundle_adjust: copy points");
     if (hipMemsetAsync(w.lm.off_p, 0, 4 * (P + 1), st) != hipSuccess) return check_launch("sfm_bundle_adjust: clear the counters");
     hipLaunchKernelGGL(bundle_init_kernel, dim3(1), dim3(kMaxCameras), 0, st, mask, (int)C, w.lm);
+    if (kCal) hipLaunchKernelGGL(bundle_calib_init_kernel, dim3(1), dim3(1), 0, st, w.lm.cal, cam, job.refine);
     w.pos_c = sfmlm::launch_orders(obs, M, C, P, core, st);
     auto linearize = [&]() {
-        hipLaunchKernelGGL((sfmlm::linearize_kernel<true, kRobust>), dim3(pgrid), dim3(kThreads), 0, st, obs, (int)P, cam, poses_out,
-                           points_out, (int)C, w.lm, w.W);
+        hipLaunchKernelGGL((sfmlm::linearize_kernel<true, kRobust, kCal>), dim3(pgrid), dim3(kThreads), 0, st, obs, (int)P, cam,
+                           poses_out, points_out, (int)C, w.lm, w.W);
         if (F > 0)
-            hipLaunchKernelGGL(sfmlm::camera_kernel<kRobust>, dim3((unsigned)F), dim3(kThreads), 0, st, obs, cam, poses_out, points_out,
-                               w.lm);
+            hipLaunchKernelGGL((sfmlm::camera_kernel<kRobust, kCal>), dim3((unsigned)F), dim3(kThreads), 0, st, obs, cam, poses_out,
+                               points_out, w.lm);
     };
     linearize();
     hipLaunchKernelGGL(sfmlm::start_kernel<kThreads>, dim3(1), dim3(kThreads), 0, st, pblocks, f, anchor, max_steps, poses_out,
@@ -342,18 +500,64 @@ int enqueue(const Job& job, Ws& w, const sfmlm::Core& core) {
     for (int step = 0; step < max_steps; ++step) {
         linearize();
         hipLaunchKernelGGL(sfmlm::point_kernel, dim3(pgrid), dim3(kThreads), 0, st, (int)P, w.lm);
-        if (pairs > 0) hipLaunchKernelGGL(bundle_schur_kernel, dim3(pairs), dim3(kThreads), 0, st, F, w);
+        if (pairs > 0) hipLaunchKernelGGL(bundle_schur_kernel<kCal>, dim3(pairs), dim3(kThreads), 0, st, F, w);
+        if (kCal) hipLaunchKernelGGL(bundle_border_kernel, dim3(pgrid), dim3(kThreads), 0, st, (int)P, w.lm);
         if (F <= kLdsFree)
-            hipLaunchKernelGGL(bundle_solve_kernel<true>, dim3(1), dim3(kSolveThreads), 0, st, F, (int)C, poses_out, w);
+            hipLaunchKernelGGL((bundle_solve_kernel<true, kCal>), dim3(1), dim3(kSolveThreads), 0, st, F, (int)C, poses_out, w,
+                               pblocks);
         else
-            hipLaunchKernelGGL(bundle_solve_kernel<false>, dim3(1), dim3(kSolveThreads), 0, st, F, (int)C, poses_out, w);
-        hipLaunchKernelGGL(bundle_trial_kernel<kRobust>, dim3(pgrid), dim3(kThreads), 0, st, obs, (int)P, cam, points_out, (int)C, w);
+            hipLaunchKernelGGL((bundle_solve_kernel<false, kCal>), dim3(1), dim3(kSolveThreads), 0, st, F, (int)C, poses_out, w,
+                               pblocks);
+        hipLaunchKernelGGL((bundle_trial_kernel<kRobust, kCal>), dim3(pgrid), dim3(kThreads), 0, st, obs, (int)P, cam, points_out,
+                           (int)C, w);
         hipLaunchKernelGGL(sfmlm::decide_kernel<kThreads>, dim3(1), dim3(kThreads), 0, st, pblocks, anchor, max_steps, w.lm);
-        hipLaunchKernelGGL(sfmlm::commit_kernel, dim3(icgrid), dim3(kThreads), 0, st, (int)P, (int)C, anchor, poses_out,
+        hipLaunchKernelGGL(sfmlm::commit_kernel<kCal>, dim3(icgrid), dim3(kThreads), 0, st, (int)P, (int)C, anchor, poses_out,
                            points_out, w.lm);
     }
-    hipLaunchKernelGGL(bundle_finish_kernel, dim3(1), dim3(1), 0, st, w.lm, job.info);
+    if (kCal) hipLaunchKernelGGL(bundle_finish_calibrated_kernel, dim3(1), dim3(1), 0, st, w.lm, job.info, job.K_out);
+    else hipLaunchKernelGGL(bundle_finish_kernel, dim3(1), dim3(1), 0, st, w.lm, job.info);
     return check_launch("sfm_bundle_adjust");
+}
+
+// Both doors of the adjuster: refine = 0 is sfm_bundle_adjust_ex; else the SFM_BUNDLE_REFINE_* bits of a calibrating call
+// (checked by the caller) and K_out.  Every check before the first launch: a refused call has enqueued nothing.
+int adjust(const double* K, int64_t cameras, int64_t points, int64_t observations, const uint8_t* fixed, const double* poses_in,
+           const double* points_in, const int32_t* camera_index, const int32_t* point_index, const double* pixels,
+           int max_steps, double* poses_out, double* points_out, sfm_bundle_info* info, void* workspace,
+           int64_t workspace_bytes, void* stream, const sfm_bundle_options* options, int refine, double* K_out) {
+    if (cameras < 1 || points < 0 || observations < 0 || max_steps < 0) return fail(SFM_EINVAL, "sfm_bundle_adjust: bad size");
+    if (cameras > kMaxCameras) return fail(SFM_EINVAL, "sfm_bundle_adjust: more than 64 cameras");
+    if (points > 0x7FFFFFFF || observations > 0x7FFFFFFF)
+        return fail(SFM_EINVAL, "sfm_bundle_adjust: points and observations must be below 2^31");
+    sfmloss::Loss loss;
+    if (!sfmloss::from_options(options, loss))
+        return fail(SFM_EINVAL, "sfm_bundle_adjust: options need a loss in 0..2, reserved = 0 and a loss_scale > 0 with a normal finite square");
+    PnPCamera cam;
+    const int rc = camera_from(K, cam, "sfm_bundle_adjust");
+    if (rc != SFM_OK) return rc;
+    if ((refine & SFM_BUNDLE_REFINE_FOCAL) && cam.k00 == 0.0)
+        return fail(SFM_EINVAL, "sfm_bundle_adjust_calibrated: K[0,0] is zero: the focal length cannot be refined");
+    if (!fixed) return fail(SFM_EINVAL, "sfm_bundle_adjust: null pointer (fixed)");
+    uint64_t mask = 0;
+    for (int64_t c = 0; c < cameras; ++c)
+        if (fixed[c]) mask |= 1ull << c;
+    if (mask == 0) return fail(SFM_EINVAL, "sfm_bundle_adjust: at least one camera must be fixed");
+    if (!poses_in || !poses_out || !info || !workspace || (points > 0 && (!points_in || !points_out)) ||
+        (observations > 0 && (!camera_index || !point_index || !pixels)) || (refine && !K_out))
+        return fail(SFM_EINVAL, "sfm_bundle_adjust: null pointer");
+    const int64_t C = cameras, P = points, M = observations;
+    Ws w;
+    sfmlm::Core core;
+    if (workspace_bytes < carve((uintptr_t)workspace, C, P, M, &w, &core, refine != 0))
+        return fail(SFM_EINVAL, "sfm_bundle_adjust: workspace too small");
+    if (((uintptr_t)workspace & 15) != 0) return fail(SFM_EINVAL, "sfm_bundle_adjust: workspace must be 16-byte aligned");
+
+    w.lm.loss = loss;
+    const Job job{cam, C, P, M, mask, poses_in, points_in, Obs{camera_index, point_index, pixels}, max_steps, poses_out, points_out,
+                  info, (hipStream_t)stream, refine, K_out};
+    const bool robust = loss.kind != SFM_BUNDLE_LOSS_SQUARED;
+    if (refine) return robust ? enqueue<true, true>(job, w, core) : enqueue<false, true>(job, w, core);
+    return robust ? enqueue<true>(job, w, core) : enqueue<false>(job, w, core);
 }
 
 }  // namespace
@@ -369,41 +573,33 @@ int64_t sfm_bundle_workspace_bytes(int64_t cameras, int64_t points, int64_t obse
     return carve(0, cameras, points, observations, &w, &core);
 }
 
+int64_t sfm_bundle_calibrated_workspace_bytes(int64_t cameras, int64_t points, int64_t observations) {
+    if (sfm_bundle_workspace_bytes(cameras, points, observations) < 0) return -1;
+    Ws w;
+    sfmlm::Core core;
+    return carve(0, cameras, points, observations, &w, &core, true);
+}
+
 int sfm_bundle_adjust_ex(const double* K, int64_t cameras, int64_t points, int64_t observations, const uint8_t* fixed,
                          const double* poses_in, const double* points_in, const int32_t* camera_index,
                          const int32_t* point_index, const double* pixels, int max_steps, double* poses_out,
                          double* points_out, sfm_bundle_info* info, void* workspace, int64_t workspace_bytes, void* stream,
                          const sfm_bundle_options* options) {
-    // every check before the first launch: a refused call has enqueued nothing
-    if (cameras < 1 || points < 0 || observations < 0 || max_steps < 0) return fail(SFM_EINVAL, "sfm_bundle_adjust: bad size");
-    if (cameras > kMaxCameras) return fail(SFM_EINVAL, "sfm_bundle_adjust: more than 64 cameras");
-    if (points > 0x7FFFFFFF || observations > 0x7FFFFFFF)
-        return fail(SFM_EINVAL, "sfm_bundle_adjust: points and observations must be below 2^31");
-    sfmloss::Loss loss;
-    if (!sfmloss::from_options(options, loss))
-        return fail(SFM_EINVAL, "sfm_bundle_adjust: options need a loss in 0..2, reserved = 0 and a loss_scale > 0 with a normal finite square");
-    PnPCamera cam;
-    const int rc = camera_from(K, cam, "sfm_bundle_adjust");
-    if (rc != SFM_OK) return rc;
-    if (!fixed) return fail(SFM_EINVAL, "sfm_bundle_adjust: null pointer (fixed)");
-    uint64_t mask = 0;
-    for (int64_t c = 0; c < cameras; ++c)
-        if (fixed[c]) mask |= 1ull << c;
-    if (mask == 0) return fail(SFM_EINVAL, "sfm_bundle_adjust: at least one camera must be fixed");
-    if (!poses_in || !poses_out || !info || !workspace || (points > 0 && (!points_in || !points_out)) ||
-        (observations > 0 && (!camera_index || !point_index || !pixels)))
-        return fail(SFM_EINVAL, "sfm_bundle_adjust: null pointer");
-    const int64_t C = cameras, P = points, M = observations;
-    Ws w;
-    sfmlm::Core core;
-    if (workspace_bytes < carve((uintptr_t)workspace, C, P, M, &w, &core))
-        return fail(SFM_EINVAL, "sfm_bundle_adjust: workspace too small");
-    if (((uintptr_t)workspace & 15) != 0) return fail(SFM_EINVAL, "sfm_bundle_adjust: workspace must be 16-byte aligned");
+    return adjust(K, cameras, points, observations, fixed, poses_in, points_in, camera_index, point_index, pixels, max_steps,
+                  poses_out, points_out, info, workspace, workspace_bytes, stream, options, 0, nullptr);
+}
 
-    w.lm.loss = loss;
-    const Job job{cam, C, P, M, mask, poses_in, points_in, Obs{camera_index, point_index, pixels}, max_steps, poses_out, points_out,
-                  info, (hipStream_t)stream};
-    return loss.kind == SFM_BUNDLE_LOSS_SQUARED ? enqueue<false>(job, w, core) : enqueue<true>(job, w, core);
+int sfm_bundle_adjust_calibrated(const double* K, int64_t cameras, int64_t points, int64_t observations, const uint8_t* fixed,
+                                 const double* poses_in, const double* points_in, const int32_t* camera_index,
+                                 const int32_t* point_index, const double* pixels, int max_steps, double* poses_out,
+                                 double* points_out, sfm_bundle_info* info, double* K_out, void* workspace,
+                                 int64_t workspace_bytes, void* stream, const sfm_bundle_calibration_options* options) {
+    if (!options) return fail(SFM_EINVAL, "sfm_bundle_adjust_calibrated: null pointer (options)");
+    if (options->refine < 1 || options->refine > (SFM_BUNDLE_REFINE_FOCAL | SFM_BUNDLE_REFINE_PRINCIPAL_POINT) ||
+        options->reserved != 0)
+        return fail(SFM_EINVAL, "sfm_bundle_adjust_calibrated: options need refine in 1..3 and reserved = 0");
+    return adjust(K, cameras, points, observations, fixed, poses_in, points_in, camera_index, point_index, pixels, max_steps,
+                  poses_out, points_out, info, workspace, workspace_bytes, stream, &options->loss, options->refine, K_out);
 }
 
 int sfm_bundle_adjust(const double* K, int64_t cameras, int64_t points, int64_t observations, const uint8_t* fixed,

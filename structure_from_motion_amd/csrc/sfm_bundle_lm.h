@@ -12,6 +12,10 @@
 // The kernels that see a residual or a Jacobian take the loss (csrc/sfm_loss.h) as a template parameter:
 // kRobust = false is the squared loss and compiles to the code it was before there was a choice; kRobust = true reads the
 // launch-uniform Lm::loss, sums rho instead of e and multiplies r, Jc and Jp by sqrt(w).
+//
+// kCal (the dense adjuster's calibrating call; false everywhere else and then the code it was before) refines
+// up to three intrinsics shared by all cameras: the camera is Lm::cal's, not the launch argument, and the kernels add the
+// blocks of Jq = dw / d(f, cx, cy): U_qq and g_q, U_cq per camera, W_qp per point.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -48,6 +52,14 @@ struct State {
 };
 static_assert(offsetof(State, stop) + sizeof(int32_t) == sizeof(State), "stop is the last word of State");
 
+// The calibrating call's cameras and intrinsics step.  A trial step scales the 2 x 2 block of K by (f + df) / f, f = k00
+// (a zero entry stays zero), and moves (k02, k12) by (dcx, dcy).
+struct Calib {
+    PnPCamera cam, trial;   // of the current estimate, of the trial step
+    double dq[3];           // the trial step of (f, cx, cy); 0 for a held intrinsic
+    int32_t refine, pad;    // SFM_BUNDLE_REFINE_* bits
+};
+
 // The observations: camera and point index, pixel.
 struct Obs {
     const int32_t* cam;
@@ -67,6 +79,9 @@ struct Lm {
     double* part;                    // per point block: trial cost | |dX|^2 | |X|^2
     sfmloss::Loss loss;              // read by the kRobust kernels only
     double* sw;                      // sqrt(w) per point-major position, for kernels without a residual (else nullptr)
+    Calib* cal;                      // the kCal kernels only (else nullptr), with
+    double *Wq, *Ucq;                //   W_qp (3 x 3) per point, U_cq (6 x 3) per camera, and per point block
+    double* qpart;                   //   U_qq (upper 6) | g_q | sum W_qp V_p*^-1 W_qp^T (upper 6) | sum W_qp V_p*^-1 g_p
 };
 
 using sfmhost::Carver;   // csrc/sfm_common.h
@@ -108,6 +123,8 @@ inline Core carve_core(Carver& k, int64_t C, int64_t P, int64_t M, int64_t F, St
     w.part = k.take<double>(3 * ((P + kThreads - 1) / kThreads));
     w.loss = sfmloss::Loss{SFM_BUNDLE_LOSS_SQUARED, 0, 1.0, 1.0};
     w.sw = nullptr;
+    w.cal = nullptr;
+    w.Wq = w.Ucq = w.qpart = nullptr;
     return c;
 }
 
@@ -193,6 +210,17 @@ SFM_DEVICE Chunk camera_chunk(const Lm& w) {
     return Chunk{c, lo + min(n, (int)threadIdx.x * chunk), lo + min(n, ((int)threadIdx.x + 1) * chunk)};
 }
 
+// Jq = dw / d(f, cx, cy) of an observation in front of its camera, times s, from its unweighted residual r = w - (u, v):
+// rows ((w_0 - k02) / k00, 1, 0) and ((w_1 - k12) / k00, 0, 1); the column of a held intrinsic is zero.
+SFM_DEVICE void intrinsic_rows(const PnPCamera& k, int refine, const double (&r)[2], double u, double v, double s,
+                               double (&Jq)[2][3]) {
+    const bool focal = refine & SFM_BUNDLE_REFINE_FOCAL, centre = refine & SFM_BUNDLE_REFINE_PRINCIPAL_POINT;
+    Jq[0][0] = focal ? s * (((r[0] + u) - k.k02) / k.k00) : 0.0;
+    Jq[1][0] = focal ? s * (((r[1] + v) - k.k12) / k.k00) : 0.0;
+    Jq[0][1] = Jq[1][2] = centre ? s : 0.0;
+    Jq[0][2] = Jq[1][1] = 0.0;
+}
+
 namespace {
 
 // ------------------------------------------------------------------------------------------------------------------------
@@ -201,15 +229,19 @@ namespace {
 // Thread per point: the cost of its observations (partial per block; the start needs it), V_p and g_p.  kStoreW (the
 // dense path, C <= kLdsCameras): the poses staged in LDS, and W = Jc^T Jp to W[18 q] for every point-major position q of a
 // moving point seen by a free camera.  kRobust: the cost is the sum of rho, r, Jc and Jp carry sqrt(w), which also goes to
-// w.sw[q] when the adjuster keeps it (0 for an observation behind its camera).
-template <bool kStoreW, bool kRobust>
+// w.sw[q] when the adjuster keeps it (0 for an observation behind its camera).  kCal: W_qp of a moving point over all its
+// observations, and the block's U_qq and g_q over every observation in front of its camera (held points included).
+template <bool kStoreW, bool kRobust, bool kCal = false>
 __global__ __launch_bounds__(kThreads) void linearize_kernel(Obs obs, int P, PnPCamera cam, const double* __restrict__ poses,
                                                              const double* __restrict__ points, int C, Lm w,
                                                              double* __restrict__ W) {
     __shared__ double lds_pose[kStoreW ? kLdsCameras * 12 : 1];
     __shared__ double part[kThreads / kWave];
     __shared__ double total[1];
+    __shared__ double qpart[kCal ? kThreads / kWave * 9 : 1];
+    __shared__ double qtotal[kCal ? 9 : 1];
     if (w.st->stop || w.st->bad || !w.st->need_lin) return;
+    if (kCal) cam = w.cal->cam;
     const double* pose = poses;
     if (kStoreW) {
         for (int k = threadIdx.x; k < 12 * C; k += kThreads) lds_pose[k] = poses[k];
@@ -218,11 +250,13 @@ __global__ __launch_bounds__(kThreads) void linearize_kernel(Obs obs, int P, PnP
     }
     const int p = blockIdx.x * kThreads + threadIdx.x;
     double e[1] = {0.0};
+    double qs[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // kCal: U_qq (upper 6) | g_q
     if (p < P) {
         const double X = points[3 * (int64_t)p], Y = points[3 * (int64_t)p + 1], Z = points[3 * (int64_t)p + 2];
         const int q0 = w.off_p[p], q1 = w.off_p[p + 1];
         const bool moving = q1 - q0 >= 2;
         double V[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, g[3] = {0.0, 0.0, 0.0};
+        double Wq[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
         for (int q = q0; q < q1; ++q) {
             const int m = w.ord_p[q];
             const int c = w.camp[q];
@@ -232,12 +266,27 @@ __global__ __launch_bounds__(kThreads) void linearize_kernel(Obs obs, int P, PnP
             e[0] += kRobust ? sfmloss::rho(w.loss, eq) : eq;
             double r[2], Jc[2][6], Jp[2][3];
             const bool front = sfmpnp::jacobians(mp, cam, X, Y, Z, Jc, Jp, r, u, v);
+            double s = 1.0;
             if (kRobust) {
-                const double s = front ? sfmloss::sqrt_weight(w.loss, r) : 0.0;
+                s = front ? sfmloss::sqrt_weight(w.loss, r) : 0.0;
                 if (w.sw) w.sw[q] = s;
-                if (front) sfmloss::scale(s, r, Jc, Jp);
             }
             if (!front) continue;
+            double Jq[2][3];
+            if (kCal) intrinsic_rows(cam, w.cal->refine, r, u, v, s, Jq);
+            if (kRobust) sfmloss::scale(s, r, Jc, Jp);
+            if (kCal) {
+#pragma unroll
+                for (int i = 0; i < 3; ++i) {
+#pragma unroll
+                    for (int j = i; j < 3; ++j) qs[upper3(i, j)] += Jq[0][i] * Jq[0][j] + Jq[1][i] * Jq[1][j];
+                    qs[6 + i] += Jq[0][i] * r[0] + Jq[1][i] * r[1];
+                    if (moving) {
+#pragma unroll
+                        for (int j = 0; j < 3; ++j) Wq[3 * i + j] += Jq[0][i] * Jp[0][j] + Jq[1][i] * Jp[1][j];
+                    }
+                }
+            }
 #pragma unroll
             for (int i = 0; i < 3; ++i) {
 #pragma unroll
@@ -256,43 +305,61 @@ __global__ __launch_bounds__(kThreads) void linearize_kernel(Obs obs, int P, PnP
         for (int k = 0; k < 6; ++k) w.V[6 * (int64_t)p + k] = V[k];
 #pragma unroll
         for (int k = 0; k < 3; ++k) w.gp[3 * (int64_t)p + k] = g[k];
+        if (kCal) {
+#pragma unroll
+            for (int k = 0; k < 9; ++k) w.Wq[9 * (int64_t)p + k] = Wq[k];
+        }
     }
     sfm::block_sum<1, kThreads>(e, part, total);
     if (threadIdx.x == 0) w.part[3 * (int64_t)blockIdx.x] = total[0];
+    if (kCal) {
+        sfm::block_sum<9, kThreads>(qs, qpart, qtotal);
+        if (threadIdx.x < 9) w.qpart[18 * (int64_t)blockIdx.x + threadIdx.x] = qtotal[threadIdx.x];
+    }
 }
 
 // Block per free camera: U_c (upper 21) and g_c over its observations in camera-major order.  kRobust: sqrt(w) again
-// from the residual, the bits linearize_kernel got.
-template <bool kRobust>
+// from the residual, the bits linearize_kernel got.  kCal: U_cq (6 x 3) as well.
+template <bool kRobust, bool kCal = false>
 __global__ __launch_bounds__(kThreads) void camera_kernel(Obs obs, PnPCamera cam, const double* __restrict__ poses,
                                                           const double* __restrict__ points, Lm w) {
-    __shared__ double part[kThreads / kWave * 27];
-    __shared__ double total[27];
+    constexpr int kSums = kCal ? 45 : 27;
+    __shared__ double part[kThreads / kWave * kSums];
+    __shared__ double total[kSums];
     if (w.st->stop || w.st->bad || !w.st->need_lin) return;
+    if (kCal) cam = w.cal->cam;
     const Chunk ch = camera_chunk(w);
     double m[12];
 #pragma unroll
     for (int k = 0; k < 12; ++k) m[k] = poses[12 * (int64_t)ch.c + k];
-    double a[27];
+    double a[kSums];
 #pragma unroll
-    for (int k = 0; k < 27; ++k) a[k] = 0.0;
+    for (int k = 0; k < kSums; ++k) a[k] = 0.0;
     for (int i = ch.i0; i < ch.i1; ++i) {
         const int64_t mo = w.obs_c[i], p = w.pt_c[i];
         double r[2], Jc[2][6], Jp[2][3];
         if (!sfmpnp::jacobians(m, cam, points[3 * p], points[3 * p + 1], points[3 * p + 2], Jc, Jp, r, obs.uv[2 * mo],
                                obs.uv[2 * mo + 1]))
             continue;
-        if (kRobust) sfmloss::scale(sfmloss::sqrt_weight(w.loss, r), r, Jc, Jp);
+        const double s = kRobust ? sfmloss::sqrt_weight(w.loss, r) : 1.0;
+        double Jq[2][3];
+        if (kCal) intrinsic_rows(cam, w.cal->refine, r, obs.uv[2 * mo], obs.uv[2 * mo + 1], s, Jq);
+        if (kRobust) sfmloss::scale(s, r, Jc, Jp);
 #pragma unroll
         for (int x = 0; x < 6; ++x) {
 #pragma unroll
             for (int y = x; y < 6; ++y) a[upper6(x, y)] += Jc[0][x] * Jc[0][y] + Jc[1][x] * Jc[1][y];
             a[21 + x] += Jc[0][x] * r[0] + Jc[1][x] * r[1];
+            if (kCal) {
+#pragma unroll
+                for (int y = 0; y < 3; ++y) a[27 + 3 * x + y] += Jc[0][x] * Jq[0][y] + Jc[1][x] * Jq[1][y];
+            }
         }
     }
-    sfm::block_sum<27, kThreads>(a, part, total);
+    sfm::block_sum<kSums, kThreads>(a, part, total);
     if (threadIdx.x < 21) w.U[21 * (int64_t)ch.c + threadIdx.x] = total[threadIdx.x];
     else if (threadIdx.x < 27) w.gc[6 * (int64_t)ch.c + threadIdx.x - 21] = total[threadIdx.x];
+    else if (kCal && threadIdx.x < 45) w.Ucq[18 * (int64_t)ch.c + threadIdx.x - 27] = total[threadIdx.x];
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
@@ -403,11 +470,13 @@ __global__ __launch_bounds__(kBlock) void decide_kernel(int blocks, int a, int m
 }
 
 // An accepted trial becomes the current estimate; with one fixed camera (a >= 0), scaled about its centre by st->scale.
-// Thread i takes point i and camera i.
+// Thread i takes point i and camera i.  kCal: the trial camera becomes the current one, untouched by the rescale.
+template <bool kCal = false>
 __global__ __launch_bounds__(kThreads) void commit_kernel(int P, int C, int a, double* __restrict__ poses,
                                                           double* __restrict__ points, Lm w) {
     const State* st = w.st;
     if (!st->commit) return;
+    if (kCal && blockIdx.x == 0 && threadIdx.x == 0) w.cal->cam = w.cal->trial;
     const bool rescale = a >= 0;
     const double s = st->scale, c0[3] = {st->c0[0], st->c0[1], st->c0[2]};
     const int i = blockIdx.x * kThreads + threadIdx.x;

@@ -569,7 +569,7 @@ int enqueue(const Job& job, Ws& w, const sfmlm::Core& core) {
         hipLaunchKernelGGL(pcg_trial_kernel<kRobust>, dim3(pgrid), dim3(kThreads), 0, st, obs, (int)P, cam, poses_out, points_out,
                            w);
         hipLaunchKernelGGL(sfmlm::decide_kernel<kOneGroup>, dim3(1), dim3(kOneGroup), 0, st, pblocks, anchor, max_steps, w.lm);
-        hipLaunchKernelGGL(sfmlm::commit_kernel, dim3(icgrid), dim3(kThreads), 0, st, (int)P, (int)C, anchor, poses_out,
+        hipLaunchKernelGGL(sfmlm::commit_kernel<>, dim3(icgrid), dim3(kThreads), 0, st, (int)P, (int)C, anchor, poses_out,
                            points_out, w.lm);
     }
     hipLaunchKernelGGL(pcg_finish_kernel, dim3(1), dim3(1), 0, st, w, job.info);

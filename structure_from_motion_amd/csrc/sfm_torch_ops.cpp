@@ -957,6 +957,85 @@ BundleResult bundle_adjust_pcg_robust_meta(const Tensor& poses, const Tensor& po
     return bundle_new({true, max_cg_iterations, cg_tolerance, &options}, true, poses, points, cam, pt, pixels, K, fixed, max_steps);
 }
 
+// The calibrating dense adjuster (sfm_bundle_adjust_calibrated): the arguments of bundle_adjust_robust plus the
+// SFM_BUNDLE_REFINE_* bits; a fourth result, the refined camera matrix [3, 3].  Enqueue-only like bundle_adjust.
+using BundleCalibratedResult = std::tuple<Tensor, Tensor, Tensor, Tensor>;
+
+sfm_bundle_calibration_options calibration_options(int64_t loss, double loss_scale, int64_t refine) {
+    TORCH_CHECK(refine >= 1 && refine <= (SFM_BUNDLE_REFINE_FOCAL | SFM_BUNDLE_REFINE_PRINCIPAL_POINT),
+                "sfm_hip: refine must be 1 (focal), 2 (principal point) or 3 (both)");
+    return sfm_bundle_calibration_options{bundle_options(loss, loss_scale), (int32_t)refine, 0};
+}
+
+void bundle_calibrated_run(Tensor& poses, Tensor& points, const Tensor& cam, const Tensor& pt, const Tensor& pixels,
+                           at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed, int64_t max_steps, int64_t loss, double loss_scale,
+                           int64_t refine, Tensor& info, Tensor& K_out, const Tensor& poses_in, const Tensor& points_in) {
+    const sfm_bundle_calibration_options options = calibration_options(loss, loss_scale, refine);
+    const BundleSolver s{false, 0, 0.0, &options.loss};
+    const OpDevice scope(poses);
+    need(poses, "poses", at::kDouble);
+    need(points, "points", at::kDouble);
+    need(poses_in, "poses", at::kDouble);
+    need(points_in, "points", at::kDouble);
+    need(cam, "camera_indices", at::kInt);
+    need(pt, "point_indices", at::kInt);
+    need(pixels, "pixels", at::kDouble);
+    need(info, "info", at::kLong);
+    need(K_out, "K_out", at::kDouble);
+    bundle_check(s, poses_in, points_in, cam, pt, pixels, K, fixed, max_steps);
+    TORCH_CHECK(poses.sizes() == poses_in.sizes() && points.sizes() == points_in.sizes(), "sfm_hip: output shapes differ");
+    TORCH_CHECK(info.numel() == s.info_words(), "sfm_hip: info must be int64 [", s.info_words(), "]");
+    TORCH_CHECK(K_out.numel() == 9, "sfm_hip: K_out must be [3, 3]");
+    const int64_t C = poses.size(0), P = points.size(0), M = cam.size(0);
+    std::vector<uint8_t> mask((size_t)C, 0);
+    for (int64_t c : fixed) mask[(size_t)c] = 1;
+    const int64_t bytes = sfm_bundle_calibrated_workspace_bytes(C, P, M);
+    TORCH_CHECK(bytes >= 0, "sfm_hip: bundle_adjust_calibrated: ", C, " cameras, ", P, " points, ", M,
+                " observations exceed the limits (C <= 64, P and M < 2^31)");
+    Tensor ws = at::empty({bytes}, like(poses, at::kByte));
+    ok(sfm_bundle_adjust_calibrated(K.data(), C, P, M, mask.data(), ptr<double>(poses_in), ptr<double>(points_in),
+                                    ptr<int32_t>(cam), ptr<int32_t>(pt), ptr<double>(pixels), (int)max_steps, ptr<double>(poses),
+                                    ptr<double>(points), static_cast<sfm_bundle_info*>(static_cast<void*>(ptr<int64_t>(info))),
+                                    ptr<double>(K_out), ws.data_ptr(), bytes, current_stream(), &options),
+       "sfm_bundle_adjust_calibrated");
+}
+
+BundleCalibratedResult bundle_calibrated_new(bool meta, const Tensor& poses, const Tensor& points, const Tensor& cam,
+                                             const Tensor& pt, const Tensor& pixels, at::ArrayRef<double> K,
+                                             at::ArrayRef<int64_t> fixed, int64_t max_steps, int64_t loss, double loss_scale,
+                                             int64_t refine) {
+    const sfm_bundle_calibration_options options = calibration_options(loss, loss_scale, refine);
+    const BundleSolver s{false, 0, 0.0, &options.loss};
+    bundle_check(s, poses, points, cam, pt, pixels, K, fixed, max_steps);
+    Tensor poses_out = at::empty_like(poses);
+    Tensor points_out = at::empty_like(points);
+    Tensor info = at::empty_symint({c10::SymInt(s.info_words())}, like(poses, at::kLong));
+    Tensor K_out = at::empty_symint({c10::SymInt(3), c10::SymInt(3)}, like(poses, at::kDouble));
+    if (!meta)
+        bundle_calibrated_run(poses_out, points_out, cam, pt, pixels, K, fixed, max_steps, loss, loss_scale, refine, info, K_out,
+                              poses, points);
+    return {poses_out, points_out, info, K_out};
+}
+
+void bundle_adjust_calibrated_inplace(Tensor& poses, Tensor& points, const Tensor& cam, const Tensor& pt, const Tensor& pixels,
+                                      at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed, int64_t max_steps, int64_t loss,
+                                      double loss_scale, int64_t refine, Tensor& info, Tensor& K_out) {
+    bundle_calibrated_run(poses, points, cam, pt, pixels, K, fixed, max_steps, loss, loss_scale, refine, info, K_out, poses,
+                          points);
+}
+
+BundleCalibratedResult bundle_adjust_calibrated(const Tensor& poses, const Tensor& points, const Tensor& cam, const Tensor& pt,
+                                                const Tensor& pixels, at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed,
+                                                int64_t max_steps, int64_t loss, double loss_scale, int64_t refine) {
+    return bundle_calibrated_new(false, poses, points, cam, pt, pixels, K, fixed, max_steps, loss, loss_scale, refine);
+}
+
+BundleCalibratedResult bundle_adjust_calibrated_meta(const Tensor& poses, const Tensor& points, const Tensor& cam, const Tensor& pt,
+                                                     const Tensor& pixels, at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed,
+                                                     int64_t max_steps, int64_t loss, double loss_scale, int64_t refine) {
+    return bundle_calibrated_new(true, poses, points, cam, pt, pixels, K, fixed, max_steps, loss, loss_scale, refine);
+}
+
 // triangulation of multi-view tracks (sfm_tracks.hip): poses [C, 12], camera / point indices int32 [M], pixels [M, 2],
 // `points` the number of points P -> points [P, 3], status uint8 [P], obs_error [M], angle [P] (radians), info int64 [4]
 // viewing the sfm_tracks_info record.  The workspace comes from the caching allocator (stream-ordered, no host sync).
@@ -1344,6 +1423,11 @@ TORCH_LIBRARY(sfm_hip, m) {
     m.def("bundle_adjust_pcg_robust_(Tensor(a!) poses, Tensor(b!) points, Tensor camera_indices, Tensor point_indices, "
           "Tensor pixels, float[] K, int[] fixed, int max_steps, int max_cg_iterations, float cg_tolerance, int loss, "
           "float loss_scale, Tensor(c!) info) -> ()");
+    m.def("bundle_adjust_calibrated(Tensor poses, Tensor points, Tensor camera_indices, Tensor point_indices, Tensor pixels, "
+          "float[] K, int[] fixed, int max_steps, int loss, float loss_scale, int refine) -> (Tensor, Tensor, Tensor, Tensor)");
+    m.def("bundle_adjust_calibrated_(Tensor(a!) poses, Tensor(b!) points, Tensor camera_indices, Tensor point_indices, "
+          "Tensor pixels, float[] K, int[] fixed, int max_steps, int loss, float loss_scale, int refine, Tensor(c!) info, "
+          "Tensor(d!) K_out) -> ()");
     m.def("triangulate_tracks(Tensor poses, Tensor camera_indices, Tensor point_indices, Tensor pixels, int points, float[] K, "
           "int min_views, float min_angle, float max_error, int refine_steps) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
     m.def("triangulate_tracks_(Tensor poses, Tensor camera_indices, Tensor point_indices, Tensor pixels, int points, "
@@ -1406,6 +1490,8 @@ TORCH_LIBRARY_IMPL(sfm_hip, CUDA, m) {
     m.impl("bundle_adjust_robust_", &bundle_adjust_robust_inplace);
     m.impl("bundle_adjust_pcg_robust", &bundle_adjust_pcg_robust);
     m.impl("bundle_adjust_pcg_robust_", &bundle_adjust_pcg_robust_inplace);
+    m.impl("bundle_adjust_calibrated", &bundle_adjust_calibrated);
+    m.impl("bundle_adjust_calibrated_", &bundle_adjust_calibrated_inplace);
     m.impl("triangulate_tracks", &triangulate_tracks);
     m.impl("triangulate_tracks_", &triangulate_tracks_out);
     m.impl("build_tracks", &build_tracks);
@@ -1450,6 +1536,8 @@ void bundle_adjust_robust_out_meta(Tensor&, Tensor&, const Tensor&, const Tensor
                                    at::ArrayRef<int64_t>, int64_t, int64_t, double, Tensor&) {}
 void bundle_adjust_pcg_robust_out_meta(Tensor&, Tensor&, const Tensor&, const Tensor&, const Tensor&, at::ArrayRef<double>,
                                        at::ArrayRef<int64_t>, int64_t, int64_t, double, int64_t, double, Tensor&) {}
+void bundle_adjust_calibrated_out_meta(Tensor&, Tensor&, const Tensor&, const Tensor&, const Tensor&, at::ArrayRef<double>,
+                                       at::ArrayRef<int64_t>, int64_t, int64_t, double, int64_t, Tensor&, Tensor&) {}
 void triangulate_tracks_out_meta(const Tensor&, const Tensor&, const Tensor&, const Tensor&, int64_t, at::ArrayRef<double>, int64_t,
                                  double, double, int64_t, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&) {}
 void build_tracks_out_meta(const Tensor&, const Tensor&, const Tensor&, const Tensor&, int64_t, Tensor&, Tensor&, Tensor&, Tensor&,
@@ -1498,6 +1586,8 @@ TORCH_LIBRARY_IMPL(sfm_hip, Meta, m) {
     m.impl("bundle_adjust_robust_", &bundle_adjust_robust_out_meta);
     m.impl("bundle_adjust_pcg_robust", &bundle_adjust_pcg_robust_meta);
     m.impl("bundle_adjust_pcg_robust_", &bundle_adjust_pcg_robust_out_meta);
+    m.impl("bundle_adjust_calibrated", &bundle_adjust_calibrated_meta);
+    m.impl("bundle_adjust_calibrated_", &bundle_adjust_calibrated_out_meta);
     m.impl("triangulate_tracks", &triangulate_tracks_meta);
     m.impl("triangulate_tracks_", &triangulate_tracks_out_meta);
     m.impl("build_tracks", &build_tracks_meta);

@@ -865,6 +865,37 @@ def read_bundle_info(info: torch.Tensor) -> BundleInfo:
     return BundleInfo(*_read_records(info, 2, 3)[0])
 
 
+BUNDLE_REFINE = _native.BUNDLE_REFINE   # "focal", "principal_point": the SFM_BUNDLE_REFINE_* bit of each name
+
+
+def bundle_adjust_calibrated(poses, points, camera_indices, point_indices, pixels, K, fixed=(0,), max_steps: int = 50,
+                             out=None, *, refine=("focal",), loss: str = "squared", loss_scale: float = 1.0):
+    """``bundle_adjust`` that also refines intrinsics shared by all cameras (``sfm_bundle_adjust_calibrated``, DESIGN.md
+    §6ab) -> (poses [C,12], points [P,3], info int64 [4], K_out [3,3]; ``read_bundle_calibration_info``).  ``refine``: a
+    non-empty collection of ``BUNDLE_REFINE`` names; ``K`` is the start.  ``out`` = (poses, points, info, K_out) runs the
+    in-place op on those tensors instead.  No host synchronisation: ``K_out`` is written on the device."""
+    mask = _native.bundle_refine_mask(refine)
+    if mask == 0:
+        raise ValueError("bundle_adjust_calibrated needs at least one intrinsic to refine; bundle_adjust refines none")
+    code, scale = _bundle_loss(loss, loss_scale)
+    args = (camera_indices.contiguous(), point_indices.contiguous(), pixels.contiguous(), _camera_list(K),
+            [int(c) for c in fixed], int(max_steps), code, scale, mask)
+    if out is None:
+        return ops.load().bundle_adjust_calibrated(poses.contiguous(), points.contiguous(), *args)
+    ops.load().bundle_adjust_calibrated_(out[0], out[1], *args, out[2], out[3])
+    return out
+
+
+@dataclass
+class BundleCalibrationInfo(BundleInfo):   # sfm_bundle_info, then
+    camera_matrix: np.ndarray   # the refined K (3, 3); the input K for BUNDLE_BAD_START and BUNDLE_BAD_INDEX
+
+
+def read_bundle_calibration_info(info: torch.Tensor, K_out: torch.Tensor) -> BundleCalibrationInfo:
+    """Host copy of the sfm_bundle_info record and the camera matrix of a calibrating call (synchronises)."""
+    return BundleCalibrationInfo(*_read_records(info, 2, 3)[0], K_out.cpu().numpy().reshape(3, 3).copy())
+
+
 def bundle_adjust_pcg(poses, points, camera_indices, point_indices, pixels, K, fixed=(0,), max_steps: int = 50,
                       max_cg_iterations: int = 100, cg_tolerance: float = 0.1, out=None, *, loss: str = "squared",
                       loss_scale: float = 1.0):

@@ -28,6 +28,7 @@ import sys
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 THR = None
+OUTCOME = ("best_h", "inliers", "pairs_ok", "final_cost", "lm_steps", "accepted")   # what two trees must agree on
 TREES = os.path.join(REPO, "tools", "tmp", "trees")
 KEEP = ("structure_from_motion_amd", "include", "lib", "oracle", "apps")   # what a tree needs to be imported and built
 
@@ -93,14 +94,14 @@ def run(args):
             for t in trees:
                 r = measure(t, config, args.steps, args.options)
                 results[t].append(r)
-                print(f"  {config} {t} rep {rep}: {r['ms_per_pass']:.4f} ms  {({k: v for k, v in r.items() if k in ('best_h', 'inliers', 'pairs_ok')})}",
+                print(f"  {config} {t} rep {rep}: {r['ms_per_pass']:.4f} ms  {({k: v for k, v in r.items() if k in OUTCOME})}",
                       flush=True)
         base = statistics.median(r["ms_per_pass"] for r in results[trees[0]])
         for t in trees:
             ms = [r["ms_per_pass"] for r in results[t]]
             med = statistics.median(ms)
             lines.append(f"{config:5s} {t:24s} median {med:8.4f} ms  min {min(ms):8.4f}  ({(med / base - 1) * 100:+5.1f} % vs {trees[0]})  "
-                         f"outcome {({k: v for k, v in results[t][-1].items() if k in ('best_h', 'inliers', 'pairs_ok')})}")
+                         f"outcome {({k: v for k, v in results[t][-1].items() if k in OUTCOME})}")
     text = "\n".join(lines)
     print(text)
     if args.out:

@@ -7,6 +7,8 @@ and the program rocprofv3 wraps for the per-kernel tables under profiles/.
 Configs (bench.py's scenes and seeds): c3 = 50 000 x 100 000 (the bench workload), c4 = 50 000 x 125 000 (one of eight ranks'
 share of C4), c4x4 / c4x2 = x 250 000 / x 500 000 (the share at 4 / 2 ranks), c2 = 5 000 x 10 000 (lean small pass),
 c5 = 256 pairs x 10 000 x 2 000 (batched pipeline), mid = 20 000 x 40 000, wide = 50 000 x 20 000.
+ba3 / ba64 = one dense bundle adjustment of 3 cameras x 5 000 points / 64 x 500 000 (``synthetic.bundle_problem``, ten LM
+steps per pass); ba3cal / ba64cal = the same call refining the focal length (``device.bundle_adjust_calibrated``).
 Prints one JSON line: ms per pass (wall clock over the timed passes, one synchronisation at each end) and, for c3-like
 configs, the winner (so that two trees can be seen to agree)."""
 import argparse
@@ -65,6 +67,22 @@ elif args.config == "c5":
     finish = lambda: {"pairs_ok": sum(r.status == batched.OK for r in pipe.results()),  # noqa: E731
                       "inliers": int(sum(len(r.inlier_order) for r in pipe.results() if r.inlier_order is not None))}
     evals = float(B) * n * h
+elif args.config in ("ba3", "ba64", "ba3cal", "ba64cal"):
+    cameras, points = (3, 5_000) if args.config.startswith("ba3") else (64, 500_000)
+    pr = synthetic.bundle_problem(cameras, points, seed=0)
+    data = (device.to_device(pr["poses"]), device.to_device(pr["points"]),
+            device.to_device(pr["camera_indices"], dtype=torch.int32), device.to_device(pr["point_indices"], dtype=torch.int32),
+            device.to_device(pr["pixels"]))
+    last = {}
+    if args.config.endswith("cal"):
+        run = lambda r: last.update(out=device.bundle_adjust_calibrated(*data, pr["K"], (0,), 10, refine=("focal",)))  # noqa: E731
+    else:
+        run = lambda r: last.update(out=device.bundle_adjust(*data, pr["K"], (0,), 10))  # noqa: E731
+
+    def finish():
+        info = device.read_bundle_info(last["out"][2])
+        return {"final_cost": info.final_cost, "lm_steps": info.steps, "accepted": info.accepted}
+    evals = float(len(pr["pixels"])) * 10
 else:
     raise SystemExit(f"unknown config {args.config}")
 
