@@ -50,6 +50,12 @@ squared errors of the adjusted observations, since the adjuster's cost is a sum 
 off, as a guess from image metadata would be.  ``bundle_refine`` (``--bundle-refine focal[,principal_point]``) frees those
 intrinsics in the final bundle adjustment (the dense solver, so at most 64 views).  With either, the output
 holds ``focal``: the relative focal error before and after, and the camera matrix the run ends with.
+
+``refine_pairs`` (``--refine-pairs K``, with ``--tracks matches --verify batched``) refines every verified pair's relative pose
+on its inliers with up to K rounds (``refine_relative_poses``) before the seed pair is chosen and before the
+averaging solvers run, so ``global_rotations`` and ``global_positions`` follow from the refined poses.  The output then holds
+``pair_refinement``: the median and the largest pairwise rotation and translation-direction error against the scene's truth,
+before and after.  0, the default, is the path without it.
 """
 from __future__ import annotations
 
@@ -67,7 +73,7 @@ from lib.bundle.bundle import bundle_adjust
 from lib.common.feature import Feature
 from lib.epipolar.eight_point import create_trivial_matches, recover_r_t_from_e
 from lib.epipolar.epipolar_ransac import estimate_essential_mat_with_ransac
-from lib.epipolar.view_graph import choose_seed_pair, verify_pairs
+from lib.epipolar.view_graph import choose_seed_pair, refine_relative_poses, verify_pairs
 from lib.feature_matching.matching import Match
 from lib.multiview.rotation_averaging import average_graph_rotations, inconsistent_pairs
 from lib.multiview.tracks import build_tracks, triangulate_tracks
@@ -236,22 +242,49 @@ def global_positions(graph, rotations, views: int, max_residual_deg: float):
     return cauchy, inconsistent_pairs(cauchy, max_residual_deg)
 
 
+def pair_pose_errors(pose, pairs, poses_true) -> dict:
+    """Median and largest rotation and translation-direction error in degrees of the pairwise poses with status "ok" against
+    the scene's true poses (R | t rows): the true relative pose of pair (i, j) is R_j R_i^T, t_j - R_j R_i^T t_i."""
+    rot, direction = [], []
+    for q, (i, j) in enumerate(np.asarray(pairs).tolist()):
+        if pose.status[q] != "ok":
+            continue
+        Ri, Rj = poses_true[i, :9].reshape(3, 3), poses_true[j, :9].reshape(3, 3)
+        R = Rj @ Ri.T
+        t = poses_true[j, 9:] - R @ poses_true[i, 9:]
+        rot.append(np.degrees(rotation_angle(pose.R[q], R)))
+        c = float(pose.t[q] @ t / np.linalg.norm(t))
+        direction.append(np.degrees(np.arccos(np.clip(c, -1.0, 1.0))))
+    if not rot:
+        return dict(pairs=0)
+    return dict(pairs=len(rot), rotation_median_deg=float(np.median(rot)), rotation_max_deg=float(np.max(rot)),
+                direction_median_deg=float(np.median(direction)), direction_max_deg=float(np.max(direction)))
+
+
 def tracks_from_matches(scene, sed_threshold: float, iterations: int, e_solver: str, seed: int, verify: str = "loop",
                         relative_pose: bool = False, rotations: str = "incremental", drop_inconsistent_deg=None,
-                        positions: str = "incremental"):
+                        positions: str = "incremental", refine_pairs: int = 0):
     """The scene's tracks rebuilt from verified pairwise matches: (scene with the built camera_indices, point_indices and
     pixels, the build's info, the fraction of OK tracks whose features all belong to one true point, pairs kept, and with
     ``verify="batched"`` the number of pairs of each kind and the ``ViewGraph`` (with poses if ``relative_pose``), else None
     twice; with ``rotations="global"`` the result of ``global_rotations``, else None; with ``positions="global"`` the result
-    of ``global_positions``, else None).  ``drop_inconsistent_deg`` drops the inconsistent pairs before the build."""
+    of ``global_positions``, else None; with ``refine_pairs`` rounds of ``refine_relative_poses`` on the graph's poses, which
+    every later stage then sees refined, ``pair_pose_errors`` before and after them, else None).  ``drop_inconsistent_deg``
+    drops the inconsistent pairs before the build."""
     K = scene["K"]
     random.seed(seed)   # the pairs' RANSAC samples
     pm = synthetic.pairwise_matches(scene, seed=seed)
-    pairs, kept, kinds, graph, averaged, positioned = [], [], None, None, None, None
+    pairs, kept, kinds, graph, averaged, positioned, pair_errors = [], [], None, None, None, None, None
     if verify == "batched":
-        pose = dict(relative_pose=True) if relative_pose or rotations == "global" else {}
+        pose = dict(relative_pose=True) if relative_pose or rotations == "global" or refine_pairs > 0 else {}
         graph = verify_pairs(K, pm["features"], pm["pairs"], pm["matches"], sed_threshold, min_extra_fraction=0.4,
                              max_iterations=iterations, **pose)
+        if refine_pairs > 0:
+            refined = refine_relative_poses(K, pm["features"], graph, pm["matches"], sed_threshold, rounds=refine_pairs)
+            pair_errors = dict(before=pair_pose_errors(graph.pose, graph.pairs, scene["poses_true"]),
+                               after=pair_pose_errors(refined.graph.pose, graph.pairs, scene["poses_true"]),
+                               rounds_kept=int(refined.accepted.sum()), lm_steps=int(refined.lm_steps.sum()))
+            graph = refined.graph
         kinds = {kind: graph.kind.count(kind) for kind in ("essential", "homography", "none")}
         dropped = set()
         if rotations == "global":
@@ -280,7 +313,7 @@ def tracks_from_matches(scene, sed_threshold: float, iterations: int, e_solver: 
     np.maximum.at(hi, r.point_indices, truth)
     pure = float(np.mean(lo == hi)) if r.info.tracks else float("nan")
     built = dict(scene, camera_indices=r.camera_indices, point_indices=r.point_indices, pixels=r.pixels)
-    return built, r.info, pure, len(pairs), kinds, graph, averaged, positioned
+    return built, r.info, pure, len(pairs), kinds, graph, averaged, positioned, pair_errors
 
 
 def run(views: int = 8, points: int = 2000, seed: int = 21, noise_px: float = 0.5, outlier_fraction: float = 0.2,
@@ -290,7 +323,7 @@ def run(views: int = 8, points: int = 2000, seed: int = 21, noise_px: float = 0.
         bundle_loss: str = "squared", bundle_loss_scale: float = 2.0, verify: str = "loop", seed_pair: str = "first",
         seed_min_angle_deg: float = 2.0, rotations: str = "incremental", drop_inconsistent_pairs_deg=None,
         positions: str = "incremental", register: str = "incremental", focal_error: float = 0.0,
-        bundle_refine=()) -> dict:
+        bundle_refine=(), refine_pairs: int = 0) -> dict:
     if pnp_solver not in ("dlt", "p3p"):
         raise ValueError(f"pnp_solver must be 'dlt' or 'p3p', got {pnp_solver!r}")
     if e_solver not in ("eight_point", "five_point"):
@@ -318,6 +351,10 @@ def run(views: int = 8, points: int = 2000, seed: int = 21, noise_px: float = 0.
             raise ValueError("drop_inconsistent_pairs_deg needs rotations='global'")
         if not (np.isfinite(drop_inconsistent_pairs_deg) and drop_inconsistent_pairs_deg > 0.0):
             raise ValueError(f"drop_inconsistent_pairs_deg must be finite and positive, got {drop_inconsistent_pairs_deg!r}")
+    if isinstance(refine_pairs, bool) or not isinstance(refine_pairs, int) or refine_pairs < 0:
+        raise ValueError(f"refine_pairs must be a non-negative int, got {refine_pairs!r}")
+    if refine_pairs > 0 and not (tracks == "matches" and verify == "batched"):
+        raise ValueError("refine_pairs needs tracks='matches' and verify='batched'")
     auto_seed = seed_pair == "auto"
     if auto_seed and not (tracks == "matches" and verify == "batched"):
         raise ValueError("seed_pair='auto' needs tracks='matches' and verify='batched'")
@@ -341,11 +378,11 @@ def run(views: int = 8, points: int = 2000, seed: int = 21, noise_px: float = 0.
         K_wrong = np.array(K_true, dtype=np.float64)
         K_wrong[:2, :2] *= 1.0 + focal_error
         scene = dict(scene, K=K_wrong)
-    build, graph, averaged, positioned = None, None, None, None
+    build, graph, averaged, positioned, pair_errors = None, None, None, None, None
     if tracks == "matches":
-        scene, build_info, pure, kept_pairs, kinds, graph, averaged, positioned = tracks_from_matches(
+        scene, build_info, pure, kept_pairs, kinds, graph, averaged, positioned, pair_errors = tracks_from_matches(
             scene, sed_threshold, iterations, e_solver, seed, verify, relative_pose=auto_seed, rotations=rotations,
-            drop_inconsistent_deg=drop_inconsistent_pairs_deg, positions=positions)
+            drop_inconsistent_deg=drop_inconsistent_pairs_deg, positions=positions, refine_pairs=refine_pairs)
         build = dict(pairs_kept=kept_pairs, components=build_info.components, tracks=build_info.tracks,
                      observations=build_info.observations, conflicts=build_info.conflicts,
                      unmatched=build_info.unmatched, pure_track_fraction=pure)
@@ -473,6 +510,8 @@ def run(views: int = 8, points: int = 2000, seed: int = 21, noise_px: float = 0.
     if auto_seed:
         out["seed_pair"] = [va, vb]
         out["median_angle_deg"] = float(graph.pose.median_angle_deg[seed_q])
+    if pair_errors is not None:
+        out["pair_refinement"] = pair_errors
     if averaged is not None:
         result, inconsistent = averaged
         # the gauge of the reconstruction: the true rotations above are relative to view va (its own when va is view 0)
@@ -570,7 +609,12 @@ def main():
                     help="run the pipeline with a camera matrix whose focal lengths are this fraction off (0.05: 5 %% too long)")
     ap.add_argument("--bundle-refine", default="", metavar="focal[,principal_point]",
                     help="intrinsics the final bundle adjustment refines (at most 64 views)")
+    ap.add_argument("--refine-pairs", type=int, default=0, metavar="K",
+                    help="refine every pair's relative pose on its inliers with up to K rounds (0: off; needs --tracks matches "
+                         "--verify batched); reports the pairwise pose errors against the truth before and after")
     args = ap.parse_args()
+    if args.refine_pairs < 0 or (args.refine_pairs > 0 and not (args.tracks == "matches" and args.verify == "batched")):
+        ap.error("--refine-pairs needs a non-negative K and, above 0, --tracks matches --verify batched")
     refine = tuple(name for name in args.bundle_refine.split(",") if name)
     try:
         _native.bundle_refine_mask(refine)
@@ -600,7 +644,8 @@ def main():
                          bundle_loss_scale=args.bundle_loss_scale, verify=args.verify, seed_pair=args.seed_pair,
                          seed_min_angle_deg=args.seed_min_angle, rotations=args.rotations,
                          drop_inconsistent_pairs_deg=args.drop_inconsistent_pairs, positions=args.positions,
-                         register=args.register, focal_error=args.focal_error, bundle_refine=refine)))
+                         register=args.register, focal_error=args.focal_error, bundle_refine=refine,
+                         refine_pairs=args.refine_pairs)))
 
 
 if __name__ == "__main__":

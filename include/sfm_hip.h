@@ -495,6 +495,52 @@ int sfm_pair_poses(const double* corr, int64_t n_total, const int64_t* offset, i
                    const sfm_select_result* e_result, const uint8_t* e_mask, const sfm_pair_verdict* verdict,
                    double distance_threshold, sfm_pair_pose* pose, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- refinement of every pair's relative pose on its inliers, behind sfm_pair_poses on that call's buffers
+ * (csrc/sfm_view_graph_refine.hip; an extension, off unless asked for, added under ABI 15) ----
+ * corr, offset: as sfm_verify_pairs took them; pose_in: dev [pairs], as sfm_pair_poses left it.  Per pair q with
+ * pose_in[q].status == SFM_POSE_OK, with E = [t]x R (each entry two products and one subtraction) and e the value of
+ * sfm_sed_values under E:
+ *   start set   the items of the pair with e <= thr under the start pose, scored here (e_mask is not read: a sample item
+ *               that is an outlier stays out; a NaN item never enters);
+ *   a round     Levenberg-Marquardt on the current set I (at most `max_steps` trial steps) minimising C = sum over I of e,
+ *               written as the two residuals r / sqrt(da), r / sqrt(db) per item, over five unknowns: R <- exp([w]x) R and
+ *               t <- (t + a b1 + b b2) / |t + a b1 + b b2| with b1 = (t x e_i) / |t x e_i|, b2 = t x b1, e_i the axis of the
+ *               smallest |t_i| (the first on ties); damping lambda diag(H) from 1e-3 (/10 on an accepted step, *10
+ *               otherwise).  Then every item of the pair is re-scored and the result kept iff it has more items within thr,
+ *               or as many and a lower aggregated error (`aggregation` over those items, no sample term); a kept result's
+ *               inliers are the next round's set, a result that is not kept ends the rounds.  A round stops at once when the
+ *               Gauss-Newton matrix of its start point is rank-deficient (a Cholesky pivot <= 1e-10 of its diagonal entry);
+ *               fewer than 6 items in the set end the rounds.
+ * pose_out: dev [pairs], pose_in byte for byte with R and t replaced when at least one round was kept; votes, best,
+ * median_angle and status are carried over, not recomputed under the refined pose.  pose_out must not alias pose_in.
+ * mask_out: dev uint8 [n_total], 1 for an item within thr under its pair's kept pose, 0 elsewhere (pairs without a pose,
+ * items no pair owns).  info: dev [pairs].  Every byte of every output is written.
+ * Segment bounds are clamped to [0, n_total]; a pose table marked SFM_POSE_BAD_OFFSETS has no pair with a pose, so nothing
+ * is read through its offset table.  Two launches whatever `pairs` is, nothing read back; every size and pointer is checked
+ * before the first launch (pairs <= 65535, n_total < 2^31, rounds >= 0, max_steps >= 0, the aggregation); pairs == 0 is a
+ * no-op that writes nothing.  No atomics: a call is reproducible bit for bit. */
+#define SFM_PAIR_REFINE_OK 0      /* the pair had a pose and at least 6 items within thr under it */
+#define SFM_PAIR_REFINE_NO_POSE 1 /* pose_in[q].status != SFM_POSE_OK: pose_out[q] = pose_in[q], errors NaN, counts 0 */
+#define SFM_PAIR_REFINE_TOO_FEW 2 /* fewer than 6 items within thr under the start pose: the pose is unchanged */
+
+typedef struct sfm_pair_refine_info {
+    double start_error;  /* aggregated error of pose_in over its start set */
+    double error;        /* aggregated error of the pose left in pose_out over its `count` inliers */
+    int32_t start_count; /* items within thr under pose_in */
+    int32_t count;       /* items within thr under pose_out: the ones of mask_out */
+    int32_t accepted;    /* rounds whose result was kept (0 = pose_out is pose_in) */
+    int32_t lm_steps;    /* Levenberg-Marquardt trial steps over all rounds */
+    int32_t status;      /* SFM_PAIR_REFINE_* */
+    int32_t reserved;    /* 0 */
+} sfm_pair_refine_info;
+#ifdef __cplusplus
+static_assert(sizeof(sfm_pair_refine_info) == 40, "sfm_pair_refine_info is 40 bytes");
+#endif
+
+int sfm_refine_pair_poses(const double* corr, int64_t n_total, const int64_t* offset, int64_t pairs, const sfm_pair_pose* pose_in,
+                          double thr, int aggregation, int rounds, int max_steps, sfm_pair_pose* pose_out, uint8_t* mask_out,
+                          sfm_pair_refine_info* info, void* stream);
+
 /* ---- refinement of a PnP winner on its inliers (csrc/sfm_pnp_refine.hip; an extension, off unless asked for) ---- */
 
 typedef struct sfm_pnp_refine_info {

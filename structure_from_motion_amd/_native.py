@@ -179,6 +179,7 @@ SIGNATURES = {
                                    _P, _P, _P],
     "sfm_verify_pairs": [_U64, _U64, _I64, _P, _I64, _P, _I64, _P, _I64, _D, C.c_int, _D] + [_P] * 17,
     "sfm_pair_poses": [_P, _I64, _P, _I64, _P, _I64, _P, _P, _P, _D, _P, _P, _I64, _P],
+    "sfm_refine_pair_poses": [_P, _I64, _P, _I64, _P, _D, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P],
     "sfm_pnp_refine": [_P, _I64, _I64, _P, _P, _P, _P, _D, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P],
     "sfm_bundle_adjust": [_P, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _I64, _P],
     "sfm_bundle_adjust_pcg": [_P, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, _D, _P, _P, _P, _P, _I64, _P],
@@ -251,6 +252,16 @@ class PairPose(C.Structure):
     """sfm_pair_pose"""
     _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("median_angle", C.c_double), ("votes", C.c_int32 * 4),
                 ("best", C.c_int32), ("status", C.c_int32)]
+
+
+# the statuses of sfm_pair_refine_info, in the order of their SFM_PAIR_REFINE_* codes (include/sfm_hip.h)
+PAIR_REFINE_STATUS = ("ok", "no_pose", "too_few")
+
+
+class PairRefineInfo(C.Structure):
+    """sfm_pair_refine_info"""
+    _fields_ = [("start_error", C.c_double), ("error", C.c_double), ("start_count", C.c_int32), ("count", C.c_int32),
+                ("accepted", C.c_int32), ("lm_steps", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32)]
 
 
 class BundleOptions(C.Structure):

@@ -1,9 +1,9 @@
 // What every Levenberg-Marquardt loop of the library shares: the constants, the step rules and the
 // Cholesky factor, solve and inverse of a small dense SPD matrix.  The sites are the two bundle adjusters
-// (sfm_bundle_lm.h, sfm_bundle_pcg.hip), the refinement of the PnP winner (sfm_pnp_refine.hip) and the per-point
-// refinement of sfm_tracks.hip.  Each site keeps its own loop and the order in which it asks the rules: the bundle
-// adjusters know the points' share of |delta| only after the trial and test the small step there, the other two test it
-// before the trial.  The NumPy oracles under tests/ keep constants and loops of their own: the independent definition.
+// (sfm_bundle_lm.h, sfm_bundle_pcg.hip), the refinement of the PnP winner (sfm_pnp_refine.hip), that of every pair's
+// relative pose (sfm_view_graph_refine.hip) and the per-point refinement of sfm_tracks.hip.  Each site keeps its own loop
+// and the order in which it asks the rules: the bundle adjusters know the points' share of |delta| only after the trial
+// and test the small step there, the other three test it before the trial.  The NumPy oracles under tests/ keep constants and loops of their own: the independent definition.
 // Not here, on purpose: cholesky3 of sfm_tracks.hip (another subtraction order, pinned by its oracle) and the
 // conjugate-gradient loops of sfm_bundle_pcg.hip and sfm_graph_cg.h.
 #pragma once

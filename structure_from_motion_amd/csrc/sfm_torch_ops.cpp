@@ -10,7 +10,8 @@
 // forms p3p_fit and p3p_ransac_pass_ (sfm_p3p.h), the five-point fit five_point_fit and pass five_point_ransac_pass_
 // (sfm_five_point.hip), the homography ops homography_fit, homography_score, homography_inlier_mask and the pass
 // homography_ransac_pass_ (sfm_homography.hip), the ragged two-view pass verify_pairs_ (sfm_view_graph.hip) and the poses
-// behind it pair_poses (sfm_view_graph_pose.hip), and the refinement of a winner pnp_refine (sfm_pnp_refine.hip),
+// behind it pair_poses (sfm_view_graph_pose.hip) with their refinement refine_pair_poses (sfm_view_graph_refine.hip), and
+// the refinement of a winner pnp_refine (sfm_pnp_refine.hip),
 // bundle_adjust (sfm_bundle.hip, sfm_bundle_pcg.hip), triangulate_tracks (sfm_tracks.hip), build_tracks
 // (sfm_track_build.hip), average_rotations (sfm_rotation_averaging.hip) and average_translations
 // (sfm_translation_averaging.hip).  The reference call sites these serve: apps/sfm.py:110-119 (RANSAC-E), :133-138 (pose),
@@ -610,6 +611,44 @@ std::tuple<Tensor, Tensor> pair_poses_meta(const Tensor& corr, const Tensor& off
     TORCH_CHECK(corr.dim() == 2 && offset.dim() == 1, "sfm_hip: corr must be [n_total, 4], offset int64 [pairs + 1]");
     return {at::empty_symint({offset.sym_size(0) - 1, 128}, like(corr, at::kByte)),
             at::empty_symint({corr.sym_size(0)}, like(corr, at::kDouble))};
+}
+
+// ---- refinement of every pair's pose on its inliers behind pair_poses (sfm_view_graph_refine.hip): pose uint8 [pairs, 128] as
+// pair_poses returned it -> (pose_out uint8 [pairs, 128]; mask uint8 [n_total], 1 = within thr under the kept pose; info int64
+// [pairs, 5] viewing the sfm_pair_refine_info records) ------------------------------------------------------------------------
+constexpr int64_t kPairRefineInfoWords = sizeof(sfm_pair_refine_info) / 8;
+
+std::tuple<Tensor, Tensor, Tensor> refine_pair_poses(const Tensor& corr, const Tensor& offset, const Tensor& pose, double thr,
+                                                     int64_t aggregation, int64_t rounds, int64_t max_steps) {
+    const OpDevice scope(corr);
+    static_assert(sizeof(sfm_pair_pose) == 128 && sizeof(sfm_pair_refine_info) == 40, "pose rows are 128 bytes, info rows 40");
+    need(corr, "corr", at::kDouble);
+    need(offset, "offset", at::kLong);
+    need(pose, "pose", at::kByte);
+    TORCH_CHECK(corr.dim() == 2 && corr.size(1) == 4, "sfm_hip: corr must be [n_total, 4]");
+    TORCH_CHECK(offset.dim() == 1 && offset.size(0) >= 1, "sfm_hip: offset must be int64 [pairs + 1]");
+    const int64_t n_total = corr.size(0), pairs = offset.size(0) - 1;
+    TORCH_CHECK(pose.numel() == pairs * 128, "sfm_hip: pose must be uint8 [pairs, 128]");
+    TORCH_CHECK(rounds >= 0 && rounds <= 0x7FFFFFFF && max_steps >= 0 && max_steps <= 0x7FFFFFFF,
+                "sfm_hip: rounds and max_steps must be in [0, 2^31)");
+    Tensor pose_out = at::empty({pairs, 128}, like(corr, at::kByte));
+    Tensor mask = at::empty({n_total}, like(corr, at::kByte));
+    Tensor info = at::empty({pairs, kPairRefineInfoWords}, like(corr, at::kLong));
+    if (pairs == 0) mask.zero_();   // the entry is a no-op then: no item has a pair
+    ok(sfm_refine_pair_poses(ptr<double>(corr), n_total, ptr<int64_t>(offset), pairs,
+                             reinterpret_cast<const sfm_pair_pose*>(ptr<uint8_t>(pose)), thr, (int)aggregation, (int)rounds,
+                             (int)max_steps, reinterpret_cast<sfm_pair_pose*>(ptr<uint8_t>(pose_out)), ptr<uint8_t>(mask),
+                             reinterpret_cast<sfm_pair_refine_info*>(ptr<int64_t>(info)), current_stream()),
+       "sfm_refine_pair_poses");
+    return {pose_out, mask, info};
+}
+
+std::tuple<Tensor, Tensor, Tensor> refine_pair_poses_meta(const Tensor& corr, const Tensor& offset, const Tensor&, double, int64_t,
+                                                          int64_t, int64_t) {
+    TORCH_CHECK(corr.dim() == 2 && offset.dim() == 1, "sfm_hip: corr must be [n_total, 4], offset int64 [pairs + 1]");
+    return {at::empty_symint({offset.sym_size(0) - 1, 128}, like(corr, at::kByte)),
+            at::empty_symint({corr.sym_size(0)}, like(corr, at::kByte)),
+            at::empty_symint({offset.sym_size(0) - 1, c10::SymInt(kPairRefineInfoWords)}, like(corr, at::kLong))};
 }
 
 // ---- PnP (sfm_pnp.hip): pts [batch, n, 5] = {X, Y, Z, u, v}, K 9 doubles (row-major, row 2 = 0 0 1), S [batch, h, 8],
@@ -1387,6 +1426,8 @@ TORCH_LIBRARY(sfm_hip, m) {
           "Tensor(m!) e_result, Tensor(n!) h_mask, Tensor(o!) e_mask, Tensor(p!) verdict) -> ()");
     m.def("pair_poses(Tensor corr, Tensor offset, Tensor E, Tensor e_result, Tensor e_mask, Tensor verdict, "
           "float distance_threshold) -> (Tensor, Tensor)");
+    m.def("refine_pair_poses(Tensor corr, Tensor offset, Tensor pose, float thr, int aggregation, int rounds, int max_steps) -> "
+          "(Tensor, Tensor, Tensor)");
     m.def("pnp_fit(Tensor pts, Tensor S, float[] K) -> (Tensor, Tensor)");
     m.def("pnp_fit_(Tensor pts, Tensor S, float[] K, Tensor(a!) model, Tensor(b!) flags) -> ()");
     m.def("p3p_fit(Tensor pts, Tensor S, float[] K) -> (Tensor, Tensor)");
@@ -1472,6 +1513,7 @@ TORCH_LIBRARY_IMPL(sfm_hip, CUDA, m) {
     m.impl("homography_ransac_pass_", &homography_ransac_pass_out);
     m.impl("verify_pairs_", &verify_pairs_out);
     m.impl("pair_poses", &pair_poses);
+    m.impl("refine_pair_poses", &refine_pair_poses);
     m.impl("pnp_fit", &pose_fit_new<pnp_fit_out>);
     m.impl("pnp_fit_", &pnp_fit_out);
     m.impl("pnp_score", &pnp_score);
@@ -1568,6 +1610,7 @@ TORCH_LIBRARY_IMPL(sfm_hip, Meta, m) {
     m.impl("homography_ransac_pass_", &five_point_ransac_pass_out_meta);
     m.impl("verify_pairs_", &verify_pairs_out_meta);
     m.impl("pair_poses", &pair_poses_meta);
+    m.impl("refine_pair_poses", &refine_pair_poses_meta);
     m.impl("pnp_fit", &pnp_fit_meta);
     m.impl("pnp_score", &pnp_score_meta);
     m.impl("pnp_fit_", &pnp_fit_out_meta);

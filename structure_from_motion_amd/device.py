@@ -1214,6 +1214,28 @@ POSE_BYTES = C.sizeof(_native.PairPose)
 POSE_DTYPE = np.dtype([("R", "<f8", (3, 3)), ("t", "<f8", (3,)), ("median_angle", "<f8"), ("votes", "<i4", (4,)), ("best", "<i4"),
                        ("status", "<i4")])
 
+PAIR_REFINE_OK, PAIR_REFINE_NO_POSE, PAIR_REFINE_TOO_FEW = range(3)
+PAIR_REFINE_STATUS = _native.PAIR_REFINE_STATUS
+PAIR_REFINE_INFO_BYTES = C.sizeof(_native.PairRefineInfo)
+# sfm_pair_refine_info as a NumPy record: one row of the info table of ``refine_pair_poses``
+PAIR_REFINE_INFO_DTYPE = np.dtype([("start_error", "<f8"), ("error", "<f8"), ("start_count", "<i4"), ("count", "<i4"),
+                                   ("accepted", "<i4"), ("lm_steps", "<i4"), ("status", "<i4"), ("reserved", "<i4")])
+
+
+def refine_pair_poses(corr: torch.Tensor, offset: torch.Tensor, pose: torch.Tensor, thr: float, aggregation: int,
+                      rounds: int = 2, max_steps: int = 20):
+    """Refine every pair's relative pose on its inliers (``sfm_refine_pair_poses``): corr f64 [N,4], offset
+    int64 [Q+1], pose uint8 [Q,128] as ``pair_poses`` left it.  Returns (pose_out uint8 [Q,128], mask uint8 [N]: 1 = within
+    ``thr`` under the kept pose, info int64 [Q,5] viewing the sfm_pair_refine_info records; ``read_pair_refine_info``).  No
+    host synchronisation."""
+    return ops.load().refine_pair_poses(corr, offset, pose, float(thr), int(aggregation), int(rounds), int(max_steps))
+
+
+def read_pair_refine_info(info: torch.Tensor) -> np.ndarray:
+    """Host copy of sfm_pair_refine_info records (int64 [Q,5]) as a (Q,) array of ``PAIR_REFINE_INFO_DTYPE`` (synchronises)."""
+    return info.cpu().numpy().reshape(-1).view(PAIR_REFINE_INFO_DTYPE).copy()
+
+
 
 @dataclass
 class ViewGraphOutcome:
@@ -1237,6 +1259,15 @@ class ViewGraphOutcome:
     pose_best: Optional[np.ndarray] = None          # (Q,) int32 first maximum of the votes, -1 if all are zero
     pose_median_angle: Optional[np.ndarray] = None  # (Q,) radians, NaN unless pose_status is POSE_OK
     pose_status: Optional[np.ndarray] = None        # (Q,) int32, POSE_*
+    # after ``refine_poses``, else None; pose_R and pose_t are then the refined ones
+    refine_start_error: Optional[np.ndarray] = None  # (Q,) aggregated error of the start pose over its start set, NaN without a pose
+    refine_error: Optional[np.ndarray] = None        # (Q,) the same of the kept pose over its inliers
+    refine_start_count: Optional[np.ndarray] = None  # (Q,) int32 items within the threshold under the start pose
+    refine_count: Optional[np.ndarray] = None        # (Q,) int32 the same under the kept pose
+    refine_accepted: Optional[np.ndarray] = None     # (Q,) int32 rounds whose result was kept
+    refine_lm_steps: Optional[np.ndarray] = None     # (Q,) int32 LM trial steps over all rounds
+    refine_status: Optional[np.ndarray] = None       # (Q,) int32, PAIR_REFINE_*
+    refine_mask: Optional[np.ndarray] = None         # (N,) uint8: 1 = within the threshold under its pair's kept pose
 
 
 class ViewGraphWorkspace:
@@ -1260,6 +1291,7 @@ class ViewGraphWorkspace:
         self.e_mask = torch.empty((n_total,), dtype=torch.uint8, device=dev)
         self.verdict = torch.empty((pairs, VERDICT_BYTES // 8), dtype=torch.int64, device=dev)
         self.pose = self.angle = self._corr = self._offset = None   # set by run / poses
+        self.refine_mask = self.refine_info = None                  # set by refine_poses
 
     def buffers(self):
         """The output tensors in the order of the ``verify_pairs_`` op."""
@@ -1273,6 +1305,7 @@ class ViewGraphWorkspace:
         ops.load().verify_pairs_(corr, offset, min_extra, _as_int64(seed), _as_int64(seed_stride), int(h_begin), float(thr),
                                  int(aggregation), float(max_ratio), *self.buffers())
         self._corr, self._offset, self.pose, self.angle = corr, offset, None, None
+        self.refine_mask = self.refine_info = None
 
     def poses(self, distance_threshold: float = 50.0) -> None:
         """One ``sfm_pair_poses`` call (the ``pair_poses`` op) on what ``run`` took and left, enqueue-only: ``pose`` uint8
@@ -1284,6 +1317,16 @@ class ViewGraphWorkspace:
             raise ValueError("ViewGraphWorkspace.poses needs at least one hypothesis per pair")
         self.pose, self.angle = ops.load().pair_poses(self._corr, self._offset, self.E, self.e_result, self.e_mask, self.verdict,
                                                        float(distance_threshold))
+        self.refine_mask = self.refine_info = None
+
+    def refine_poses(self, thr: float, aggregation: int, rounds: int = 2, max_steps: int = 20) -> None:
+        """One ``sfm_refine_pair_poses`` call (the ``refine_pair_poses`` op) on what ``run`` took and ``poses`` left,
+        enqueue-only: ``pose`` becomes the refined table (R and t replaced where a round was kept, the rest carried over),
+        ``refine_mask`` uint8 [N] and ``refine_info`` int64 [Q,5] (``sfm_pair_refine_info`` records)."""
+        if self.pose is None:
+            raise RuntimeError("ViewGraphWorkspace.refine_poses: call run and poses first")
+        self.pose, self.refine_mask, self.refine_info = refine_pair_poses(self._corr, self._offset, self.pose, thr, aggregation,
+                                                                          rounds, max_steps)
 
     def read_poses(self) -> np.ndarray:
         """The pose table on the host as a (Q,) array of ``POSE_DTYPE`` records (synchronises)."""
@@ -1327,6 +1370,12 @@ class ViewGraphWorkspace:
         if self.pose is None:
             return {}
         table = self.read_poses()
-        return dict(pose_R=table["R"].copy(), pose_t=table["t"].copy(), pose_votes=table["votes"].copy(),
-                    pose_best=table["best"].copy(), pose_median_angle=table["median_angle"].copy(),
-                    pose_status=table["status"].copy())
+        fields = dict(pose_R=table["R"].copy(), pose_t=table["t"].copy(), pose_votes=table["votes"].copy(),
+                      pose_best=table["best"].copy(), pose_median_angle=table["median_angle"].copy(),
+                      pose_status=table["status"].copy())
+        if self.refine_info is not None:
+            info = read_pair_refine_info(self.refine_info)
+            fields.update({"refine_" + k: info[k].copy() for k in ("start_error", "error", "start_count", "count", "accepted",
+                                                                   "lm_steps", "status")})
+            fields["refine_mask"] = self.refine_mask.cpu().numpy().copy()
+        return fields

@@ -5,7 +5,9 @@ pair — what ``homography.select_two_view_model`` answers for one pair, for all
 start from: a pure rotation or a plane fits an essential matrix to every match and would win on the essential count alone.
 With ``relative_pose=True`` the same device calls also give how the two cameras of each pair stand to each other and the
 median triangulation angle of its inliers (csrc/sfm_view_graph_pose.hip), which ``choose_seed_pair`` can gate
-on: a pair with many inliers and a fraction of a degree of parallax is a poor place to start."""
+on: a pair with many inliers and a fraction of a degree of parallax is a poor place to start.  That pose is fitted to the five
+items of a sample; ``refine_pose_rounds`` / ``refine_relative_poses`` refine it on the pair's inliers (DESIGN.md §6ac,
+csrc/sfm_view_graph_refine.hip) before the averaging solvers and the seed pair see it."""
 from __future__ import annotations
 
 import os
@@ -15,6 +17,7 @@ from typing import List, NamedTuple, Optional, Sequence
 import numpy as np
 import numpy.typing as npt
 
+from .._native import POSE_STATUS as _POSE_STATUS   # PairPoses.status names by SFM_POSE_* code
 from ..multiview.tracks import _feature_pixels, _pair_matches
 from ..ransac.ransac import DEFAULT_MAX_ITERATIONS, ErrorAggregationMethod, aggregation_code
 from .homography import MAX_HOMOGRAPHY_RATIO, check_camera_matrix
@@ -46,6 +49,20 @@ class ViewGraph(NamedTuple):
     homography_inliers: List[npt.NDArray]
     inlier_matches: List[npt.NDArray]  # per pair the inliers of the model its kind names ((0, 2) for "none"): build_tracks's input
     pose: Optional[PairPoses] = None   # with relative_pose=True
+
+
+class PairRefinement(NamedTuple):
+    """What ``refine_relative_poses`` returns: the graph with the refined poses and the record of each pair."""
+    graph: ViewGraph                   # ``graph.pose.R`` / ``.t`` refined where a round was kept; every other field as given
+    start_error: npt.NDArray           # (Q,) RMS symmetric epipolar distance of the start pose over its start set, NaN without a pose
+    error: npt.NDArray                 # (Q,) the same of the kept pose over its inliers
+    start_count: npt.NDArray           # (Q,) matches within the threshold under the start pose
+    count: npt.NDArray                 # (Q,) matches within the threshold under the kept pose
+    accepted: npt.NDArray              # (Q,) rounds whose result was kept (0: the pose is the start pose)
+    lm_steps: npt.NDArray              # (Q,) Levenberg-Marquardt trial steps over all rounds
+    status: List[str]                  # per pair "ok", "no_pose" or "too_few"
+    inlier_matches: List[npt.NDArray]  # per pair (k, 2) rows of matches[q] within the threshold under the kept pose, by index
+
 
 
 def pair_min_extra(counts, min_num_extra_inliers=None, min_extra_fraction: float = 0.0) -> npt.NDArray:
@@ -97,11 +114,38 @@ def _checked_graph(features: Sequence, pairs, matches: Sequence):
     return feats, pair_arr.astype(np.int64), per_pair
 
 
+def _refine_arguments(rounds, max_steps):
+    """(rounds, max_steps) as ints, both >= 0 (``ValueError``)."""
+    for name, value in (("rounds", rounds), ("max_steps", max_steps)):
+        if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or value < 0 or value > 2**31 - 1:
+            raise ValueError(f"pose refinement: {name} must be an int in [0, 2^31), got {value!r}")
+    return int(rounds), int(max_steps)
+
+
+def _upload_graph(K, feats, pair_arr, per_pair):
+    """One upload and one normalisation for all pairs -> (device, corr f64 [N,4] on it, offset (Q + 1,) on the host and on
+    the device): the pairs' K-normalised correspondences concatenated in pair order."""
+    import torch
+
+    from .. import device
+
+    dev = device.require_gpu()
+    offset = np.zeros(len(per_pair) + 1, dtype=np.int64)
+    offset[1:] = np.cumsum([len(m) for m in per_pair])
+    pix = np.empty((2, int(offset[-1]), 2))
+    for q, ((i, j), m) in enumerate(zip(pair_arr.tolist(), per_pair)):
+        pix[0, offset[q]:offset[q + 1]] = feats[i][m[:, 0]]
+        pix[1, offset[q]:offset[q + 1]] = feats[j][m[:, 1]]
+    pix = device.to_device(pix)   # one upload: [2, N, 2]
+    corr = device.normalize_correspondences(pix[0], pix[1], K)
+    return dev, corr, offset, device.to_device(offset, torch.int64)
+
+
 def verify_pairs(camera_matrix, features: Sequence, pairs, matches: Sequence, inlier_threshold: float,
                  min_num_extra_inliers=None, min_extra_fraction: float = 0.0, max_iterations: int | None = None,
                  max_homography_ratio: float = MAX_HOMOGRAPHY_RATIO, seed: int | None = None,
                  max_hypotheses_per_call: int = 2**21, relative_pose: bool = False,
-                 distance_threshold: float = 50.0) -> ViewGraph:
+                 distance_threshold: float = 50.0, refine_pose_rounds: int = 0, refine_pose_max_steps: int = 20) -> ViewGraph:
     """Verify all Q pairs of a match graph: ``features``, ``pairs`` and ``matches`` exactly as ``build_tracks`` takes them.
 
     Per pair, ``max_iterations`` Philox samples serve a homography pass (their first four items) and a five-point essential
@@ -117,8 +161,17 @@ def verify_pairs(camera_matrix, features: Sequence, pairs, matches: Sequence, in
 
     ``relative_pose=True`` adds ``pose`` (``PairPoses``): per pair with an essential winner the pose its inliers vote for among
     the four of that matrix (an inlier votes when it triangulates in front of both cameras within ``distance_threshold``), and
-    the median angle between the viewing rays of the voters.  It needs ``max_iterations >= 1`` and changes no other field."""
+    the median angle between the viewing rays of the voters.  It needs ``max_iterations >= 1`` and changes no other field.
+
+    ``refine_pose_rounds > 0`` (it needs ``relative_pose=True``) refines each of those poses on the pair's matches within
+    ``inlier_threshold`` under it: up to that many rounds of at most ``refine_pose_max_steps`` Levenberg-Marquardt steps on the
+    summed symmetric epipolar distance, a round kept when it has more inliers, or as many and a lower RMS error
+    (``sfm_refine_pair_poses``).  ``pose.R`` and ``pose.t`` are then the refined ones; the votes, ``in_front`` and the median
+    angle stay those of the start pose, and no other field changes.  ``refine_relative_poses`` also returns each pair's record."""
     K = check_camera_matrix(camera_matrix)
+    refine_rounds, refine_steps = _refine_arguments(refine_pose_rounds, refine_pose_max_steps)
+    if refine_rounds > 0 and not relative_pose:
+        raise ValueError("refine_pose_rounds needs relative_pose=True")
     distance = float(distance_threshold)
     if not (np.isfinite(distance) and distance > 0.0):
         raise ValueError(f"distance_threshold must be finite and positive, got {distance_threshold!r}")
@@ -138,20 +191,9 @@ def verify_pairs(camera_matrix, features: Sequence, pairs, matches: Sequence, in
         no_pose = PairPoses(none.copy(), np.zeros((0, 3)), np.zeros((0, 4), np.int64), np.zeros(0, np.int64), np.zeros(0), [])
         return ViewGraph(pair_arr, [], none, none.copy(), np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0), [], [], [],
                          no_pose if relative_pose else None)
-    import torch
-
     from .. import device
 
-    dev = device.require_gpu()
-    offset = np.zeros(Q + 1, dtype=np.int64)
-    offset[1:] = np.cumsum(counts)
-    pix = np.empty((2, int(offset[-1]), 2))
-    for q, ((i, j), m) in enumerate(zip(pair_arr.tolist(), per_pair)):
-        pix[0, offset[q]:offset[q + 1]] = feats[i][m[:, 0]]
-        pix[1, offset[q]:offset[q + 1]] = feats[j][m[:, 1]]
-    pix = device.to_device(pix)   # one upload: [2, N, 2]
-    corr = device.normalize_correspondences(pix[0], pix[1], K)
-    offset_dev = device.to_device(offset, torch.int64)
+    dev, corr, offset, offset_dev = _upload_graph(K, feats, pair_arr, per_pair)
     gate_dev = device.to_device(gate.astype(np.float64))
     aggregation = aggregation_code(ErrorAggregationMethod.RMS)
     outcomes = []
@@ -162,6 +204,8 @@ def verify_pairs(camera_matrix, features: Sequence, pairs, matches: Sequence, in
                seed + q0, seed_stride=1)
         if relative_pose:
             ws.poses(distance)
+        if refine_rounds > 0:
+            ws.refine_poses(inlier_threshold, aggregation, refine_rounds, refine_steps)
         outcomes.append(ws.outcome())
     cat = lambda name: np.concatenate([getattr(o, name) for o in outcomes])   # noqa: E731
     code, h_mask, e_mask = cat("kind"), cat("homography_mask"), cat("essential_mask")
@@ -187,6 +231,59 @@ def verify_pairs(camera_matrix, features: Sequence, pairs, matches: Sequence, in
                          [device.POSE_STATUS[c] for c in cat("pose_status")])
     return ViewGraph(pair_arr, kind, cat("E"), cat("H"), cat("essential_count").astype(np.int64),
                      cat("homography_count").astype(np.int64), cat("ratio"), e_in, h_in, chosen, pose)
+
+
+def refine_relative_poses(camera_matrix, features: Sequence, graph: ViewGraph, matches: Sequence, inlier_threshold: float,
+                          rounds: int = 2, max_steps: int = 20) -> PairRefinement:
+    """Refine the relative poses of ``graph`` (``verify_pairs(..., relative_pose=True)``) on the matches they were verified
+    on: what ``refine_pose_rounds`` does inside ``verify_pairs``, on a graph that is already there, with each pair's record
+    (``PairRefinement``).  ``features`` and ``matches`` as ``verify_pairs`` took them; the pairs are ``graph.pairs``.  Every
+    argument is checked before any device work (``ValueError``)."""
+    K = check_camera_matrix(camera_matrix)
+    rounds, max_steps = _refine_arguments(rounds, max_steps)
+    thr = float(inlier_threshold)
+    if np.isnan(thr):
+        raise ValueError("inlier_threshold must be a number")
+    if graph.pose is None:
+        raise ValueError("refine_relative_poses needs graph.pose: call verify_pairs with relative_pose=True")
+    feats, pair_arr, per_pair = _checked_graph(features, graph.pairs, matches)
+    Q = len(per_pair)
+    pose = graph.pose
+    if not (len(pose.status) == Q and np.shape(pose.R) == (Q, 3, 3) and np.shape(pose.t) == (Q, 3)):
+        raise ValueError(f"graph.pose must hold one pose per pair ({Q})")
+    unknown = sorted(set(pose.status) - set(_POSE_STATUS))
+    if unknown:
+        raise ValueError(f"graph.pose.status holds unknown names {unknown}")
+    if Q == 0:
+        none = np.zeros(0, np.int64)
+        return PairRefinement(graph, np.zeros(0), np.zeros(0), none, none.copy(), none.copy(), none.copy(), [], [])
+    import torch
+
+    from .. import device
+
+    table = np.zeros(Q, dtype=device.POSE_DTYPE)
+    table["R"], table["t"], table["votes"] = pose.R, pose.t, pose.votes
+    table["median_angle"] = np.radians(pose.median_angle_deg)
+    table["status"] = [_POSE_STATUS.index(name) for name in pose.status]
+    table["best"] = np.where(table["status"] == device.POSE_OK, np.argmax(table["votes"], axis=1), -1)
+    dev, corr, offset, offset_dev = _upload_graph(K, feats, pair_arr, per_pair)
+    aggregation = aggregation_code(ErrorAggregationMethod.RMS)
+    tables, masks, infos = [], [], []
+    for q0 in range(0, Q, MAX_PAIRS_PER_CALL):
+        q1 = min(q0 + MAX_PAIRS_PER_CALL, Q)
+        lo, hi = int(offset[q0]), int(offset[q1])
+        pose_in = torch.from_numpy(table[q0:q1].view(np.uint8).reshape(q1 - q0, device.POSE_BYTES).copy()).to(dev)
+        out, mask, info = device.refine_pair_poses(corr[lo:hi], offset_dev[q0:q1 + 1] - lo, pose_in, thr, aggregation, rounds,
+                                                   max_steps)
+        tables.append(out.cpu().numpy().reshape(-1).view(device.POSE_DTYPE))
+        masks.append(mask.cpu().numpy())
+        infos.append(device.read_pair_refine_info(info))
+    refined, mask, info = np.concatenate(tables), np.concatenate(masks), np.concatenate(infos)
+    inliers = [per_pair[q][np.nonzero(mask[offset[q]:offset[q + 1]])[0]] for q in range(Q)]
+    new_pose = pose._replace(R=refined["R"].copy(), t=refined["t"].copy())
+    return PairRefinement(graph._replace(pose=new_pose), info["start_error"].copy(), info["error"].copy(),
+                          info["start_count"].astype(np.int64), info["count"].astype(np.int64), info["accepted"].astype(np.int64),
+                          info["lm_steps"].astype(np.int64), [device.PAIR_REFINE_STATUS[c] for c in info["status"]], inliers)
 
 
 def choose_seed_pair(graph: ViewGraph, min_count: int = 0, min_angle_deg: float = 0.0) -> int:
