@@ -1094,6 +1094,29 @@ int sfm_match_pairs(int64_t images, int64_t features, int64_t pairs, int64_t row
                     const int64_t* row_offset, const sfm_match_pairs_options* options, int32_t* partner, int32_t* distance,
                     int32_t* pair_status, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* (added within ABI 15) Guided matching: sfm_match_pairs restricted to the partners that each pair's verified two-view model
+ * admits (definition: tests/guided_matching_oracle.py).  Every argument of sfm_match_pairs keeps its meaning; in addition
+ * xy: dev f64 [features,2], the K-normalised coordinates of every feature, image-major like desc; model: dev f64 [pairs,9],
+ * row-major; model_kind: dev int32 [pairs], sfm_pair_verdict's codes 0 none, 1 essential, 2 homography; threshold: dev f64
+ * [pairs].  For pair q = (i, j), feature a of image i and feature b of image j are admissible iff both are valid and
+ * err(a, b) <= threshold[q] (one IEEE compare: false for a NaN error, so a NaN model, coordinate or threshold admits
+ * nothing), where err is the symmetric epipolar distance of sfm_sed_values under model q for kind 1 and the symmetric
+ * transfer error of sfm_homography_score under model q and its adjugate for kind 2, always with image i's feature first.
+ * Kind 0 admits nothing: the pair's rows are -1 and its status 0.  The row summary (best, arg, second) is taken over the
+ * admissible columns only and the column summary over the admissible rows only; the keep rule and the outputs are
+ * sfm_match_pairs's on those summaries.  With kind 2, the identity matrix, finite coordinates and threshold +inf everything
+ * valid is admissible and the outputs are sfm_match_pairs's byte for byte.  Bit-identical to the NumPy definition.
+ * pair_status[q] is 1 and the pair's rows are -1, as for a pair sfm_match_pairs refuses, also when model_kind[q] is not 0, 1
+ * or 2.  Every entry of partner, distance and pair_status is written.  The workspace is sfm_match_pairs's:
+ * sfm_match_pairs_workspace_bytes(pairs, rows, max_image_features).
+ * SFM_EINVAL before the first launch for everything sfm_match_pairs refuses, a null xy (with features > 0), model, model_kind
+ * or threshold, an xy, model or threshold that is not 8-byte aligned or a model_kind that is not 4-byte aligned. */
+int sfm_match_pairs_guided(int64_t images, int64_t features, int64_t pairs, int64_t rows, int64_t max_image_features,
+                           const int32_t* image_offset, const uint8_t* desc, const uint8_t* ok, const double* xy,
+                           const int32_t* pair_images, const int64_t* row_offset, const double* model, const int32_t* model_kind,
+                           const double* threshold, const sfm_match_pairs_options* options, int32_t* partner, int32_t* distance,
+                           int32_t* pair_status, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- multi-scale FAST keypoints with BRIEF per pyramid level (definition: tests/keypoint_oracle.py) ---- */
 
 /* (added within ABI 15) One plane of the pixel pool of sfm_detect_keypoints: level `level` of image `image`. */

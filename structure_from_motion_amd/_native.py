@@ -149,6 +149,7 @@ SIGNATURES = {
     "sfm_brief_describe": [_P, _I64, _I64, _P, _I64, _P, _P, C.c_int, _P, _P, _P, _P],
     "sfm_hamming_summary": [_P, _P, _I64, _P, _P, _I64, _P, _I64, _P, _P, _P, _P],
     "sfm_match_pairs": [_I64, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P],
+    "sfm_match_pairs_guided": [_I64, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P],
     "sfm_cross_correlate": [_P, _I64, _I64, _P, C.c_int, _P, _P],
     "sfm_harris_cornerness": [_P, _P, _I64, _I64, C.c_int, _D, C.c_int, _I64, _I64, _P, _P],
     "sfm_nms_inplace": [_P, _I64, _I64, _P],

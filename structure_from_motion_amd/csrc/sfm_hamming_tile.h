@@ -1,7 +1,7 @@
 // The tile of the brute-force Hamming matchers of 32-byte descriptors (hamming_summary_kernel of sfm_brief.hip,
-// match_pairs_nearest_kernel of sfm_match_pairs.hip).  A 256-thread block owns 256 rows, one per lane: the lane keeps its
-// descriptor in eight registers and walks 512 descriptors of the other side, which sit in LDS with their validity flags
-// and are read as broadcasts.  The walk stays in the kernels and the distance is a macro: a callback per column, or a
+// match_pairs_nearest_kernel and, with coordinates, match_pairs_guided_kernel of sfm_match_pairs.hip).  A 256-thread
+// block owns 256 rows, one per lane: the lane keeps its descriptor in eight registers and walks 512 descriptors of the
+// other side, which sit in LDS with their validity flags and are read as broadcasts.  The walk stays in the kernels and the distance is a macro: a callback per column, or a
 // distance function, changed the order of selects, sums and LDS reads: 2 to 8 % slower on small calls.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -34,9 +34,26 @@ SFM_DEVICE void stage(Tile& tile, const uint4* __restrict__ desc, const uint8_t*
     }
 }
 
+// The same tile with the columns' K-normalised coordinates beside them (match_pairs_guided_kernel: 8 KiB more), staged in
+// the same pass by the same lanes.  xy is only 8-byte aligned in global memory: two loads, one 16-byte LDS store.
+struct TileXY {
+    uint4 desc[kCols][2];
+    int ok[kCols];
+    double2 xy[kCols];
+};
+SFM_DEVICE void stage(TileXY& tile, const uint4* __restrict__ desc, const uint8_t* __restrict__ ok, const double* __restrict__ xy,
+                      int64_t first, int cols) {
+    for (int j = threadIdx.x; j < cols; j += kRows) {
+        tile.desc[j][0] = desc[2 * (first + j)];
+        tile.desc[j][1] = desc[2 * (first + j) + 1];
+        tile.ok[j] = ok[first + j] != 0;
+        tile.xy[j] = make_double2(xy[2 * (first + j)], xy[2 * (first + j) + 1]);
+    }
+}
+
 }  // namespace sfmham
 
-// Hamming distance of a Row to column j of a Tile
+// Hamming distance of a Row to column j of a Tile or a TileXY
 #define SFM_HAMMING_DISTANCE(row, tile, j)                                                     \
     (__popc((row).lo.x ^ (tile).desc[j][0].x) + __popc((row).lo.y ^ (tile).desc[j][0].y) +     \
      __popc((row).lo.z ^ (tile).desc[j][0].z) + __popc((row).lo.w ^ (tile).desc[j][0].w) +     \

@@ -1093,6 +1093,29 @@ def match_pairs(images: int, features: int, image_offset, desc, ok, pair_images,
     return workspace
 
 
+def match_pairs_guided(images: int, features: int, image_offset, desc, ok, xy, pair_images, row_offset, model, model_kind,
+                       threshold, rows: int, max_image_features: int, max_distance: int, ratio: Optional[float],
+                       cross_check: bool, partner, distance, pair_status, workspace=None):
+    """``match_pairs`` restricted to the partners each pair's two-view model admits (``sfm_match_pairs_guided``, DESIGN.md
+    section 6ad; ctypes like ``match_pairs``): ``xy`` float64 [F, 2] K-normalised, ``model`` float64 [Q, 9], ``model_kind`` int32
+    [Q] (0 none, 1 essential, 2 homography) and ``threshold`` float64 [Q].  Returns the workspace it used, which is
+    ``match_pairs``'s.  No host synchronisation."""
+    lib = _native.load()
+    Q = int(pair_images.shape[0])
+    need = int(lib.sfm_match_pairs_workspace_bytes(Q, int(rows), int(max_image_features)))
+    if need < 0:
+        raise ValueError("match_pairs_guided: sizes out of range (at most 65535 pairs per call, rows and image sizes below 2^31)")
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty((max(need, 1),), dtype=torch.uint8, device=desc.device)
+    options = match_pairs_options(max_distance, ratio, cross_check)
+    check(lib.sfm_match_pairs_guided(int(images), int(features), Q, int(rows), int(max_image_features), _ptr(image_offset),
+                                     _ptr(desc), _ptr(ok), _ptr(xy), _ptr(pair_images), _ptr(row_offset), _ptr(model),
+                                     _ptr(model_kind), _ptr(threshold), C.byref(options), _ptr(partner), _ptr(distance),
+                                     _ptr(pair_status), _ptr(workspace), workspace.numel(), _stream()),
+          "sfm_match_pairs_guided")
+    return workspace
+
+
 # ------------------------------------------------------------------------------------------------------
 # multi-scale FAST keypoints with BRIEF per pyramid level (csrc/sfm_keypoints.hip, DESIGN.md section 6x)
 # ------------------------------------------------------------------------------------------------------

@@ -474,3 +474,43 @@ def similarity_texture_views(height: int, width: int, degrees, scales, seed: int
         images.append(np.clip(np.floor(value + 0.5), 0, 255).astype(np.uint8))
         to_canvas.append(A)
     return images, to_canvas
+
+
+def repeated_structure_views(views: int, points: int, unique: int, groups: int, extra: int, seed: int, flips: int = 20,
+                             noise_px: float = 0.5, step_deg: float = 5.0):
+    """Views of a scene with repeated structure, for guided matching: the geometry of
+    ``multi_view_scene(views, points, seed, noise_px, 0.0, step_deg)`` with a 32-byte binary descriptor per observation.
+
+    Latent points 0 .. ``unique`` - 1 have a random prototype descriptor of their own; the other ``points - unique`` share
+    ``groups`` prototypes (point ``unique + k`` has prototype ``k % groups``): look-alikes at different places, which a
+    descriptor-space ratio test cannot tell apart.  Every observation is its point's prototype with 0 .. ``flips`` random bits
+    flipped.  Each view also gets ``extra`` partnerless features: uniform random pixels with random descriptors.  The features
+    of a view are shuffled.
+
+    Returns dict(pixels: per view float64 (n_v, 2); descriptors: per view (bits uint8 (n_v, 32), valid bool (n_v,), all true);
+    ids: per view int64 (n_v,), the latent point or -1 for a partnerless feature; K; poses_true (views, 12))."""
+    if not 0 <= unique <= points or groups < 0 or (points > unique and groups < 1) or extra < 0 or not 0 <= flips <= 256:
+        raise ValueError("repeated_structure_views: need 0 <= unique <= points, groups >= 1 when points > unique, extra >= 0 "
+                         "and 0 <= flips <= 256")
+    scene = multi_view_scene(views, points, seed, noise_px, 0.0, step_deg)
+    rng = np.random.default_rng([seed, 0x6ad])
+    K = scene["K"]
+    width, height = 2.0 * K[0, 2], 2.0 * K[1, 2]
+    prototypes = rng.integers(0, 256, (unique + groups, 32), dtype=np.uint8)
+    prototype_of = np.concatenate([np.arange(unique), unique + np.arange(points - unique) % max(groups, 1)]).astype(np.int64)
+    pixels, descriptors, ids = [], [], []
+    for v in range(views):
+        seen = scene["camera_indices"] == v
+        latent = scene["point_indices"][seen].astype(np.int64)
+        n = len(latent)
+        flip = np.zeros((n, 256), dtype=np.uint8)
+        for row, count in zip(flip, rng.integers(0, flips + 1, n)):
+            row[rng.choice(256, count, replace=False)] = 1
+        bits = prototypes[prototype_of[latent]] ^ np.packbits(flip, axis=1, bitorder="little")
+        alone_px = np.column_stack([rng.uniform(0, width, extra), rng.uniform(0, height, extra)])
+        alone_bits = rng.integers(0, 256, (extra, 32), dtype=np.uint8)
+        order = rng.permutation(n + extra)
+        pixels.append(np.ascontiguousarray(np.vstack([scene["pixels"][seen], alone_px])[order]))
+        descriptors.append((np.ascontiguousarray(np.vstack([bits, alone_bits])[order]), np.ones(n + extra, dtype=bool)))
+        ids.append(np.concatenate([latent, np.full(extra, -1, dtype=np.int64)])[order])
+    return dict(pixels=pixels, descriptors=descriptors, ids=ids, K=K, poses_true=scene["poses_true"])

@@ -11,7 +11,12 @@ each (512 pairs).  Per shape, one JSON line each for
                 the cross-check, wall clock.  ``--loop-pairs`` caps the pairs this loop and the summary loop run (0: all);
                 their totals are then scaled to Q and marked ``extrapolated``.
 
-    python tools/bench_match_pairs.py [--reps 10] [--loop-pairs 64] [--shapes small large]
+``--guided`` prints, after ``kernel`` and in place of the other three, ``sfm_match_pairs_guided`` on the
+same resident inputs (``what`` = ``guided``): the features' pixels K-normalised, every pair with the model of one synthetic
+motion — its essential matrix, then the homography of a plane under it — and a threshold that admits about 5 % of the
+feature pairs (the quantile of a sample of them), then +inf, which admits everything.  ``--kernel-only`` prints ``kernel`` alone.
+
+    python tools/bench_match_pairs.py [--reps 10] [--loop-pairs 64] [--shapes small large] [--guided | --kernel-only]
 """
 import argparse
 import json
@@ -23,7 +28,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from structure_from_motion_amd import _native, device  # noqa: E402
+from structure_from_motion_amd import _native, device, synthetic  # noqa: E402
 from structure_from_motion_amd.feature_matching import brief, matching  # noqa: E402
 from structure_from_motion_amd.feature_matching.graph_matching import all_pairs, match_image_pairs  # noqa: E402
 
@@ -59,7 +64,64 @@ def shape_pairs(images, neighbours):
     return np.array([(i, (i + k) % images) for i in range(images) for k in range(1, neighbours + 1)], dtype=np.int64)
 
 
-def run_shape(name, reps, loop_pairs):
+MOTION = (synthetic.rotation_xy(-5.0, -10.0), np.array([0.5, 0.05, 0.1]))   # the bench motion of the two-view generators
+PLANE = (5.0, 0.2, -0.1)                                                     # z = z0 + a x + b y, for the homography
+BENCH_K = np.array([[1500.0, 0.0, WIDTH / 2.0], [0.0, 1500.0, HEIGHT / 2.0], [0.0, 0.0, 1.0]])
+
+
+def guided_models():
+    """{kind name: (code, model (3, 3), the error of (n, 4) coordinate pairs in NumPy: it only picks the band's threshold)}."""
+    R, t = MOTION
+    E = np.array([[0.0, -t[2], t[1]], [t[2], 0.0, -t[0]], [-t[1], t[0], 0.0]]) @ R
+    H = R + np.outer(t, np.array([-PLANE[1], -PLANE[2], 1.0])) / PLANE[0]
+
+    def homogeneous(xy):
+        return np.column_stack([xy, np.ones(len(xy))])
+
+    def sed(corr):
+        a, b = homogeneous(corr[:, :2]), homogeneous(corr[:, 2:])
+        la, lb = a @ E.T, b @ E
+        r = np.sum(lb * a, axis=1)
+        return (1.0 / (la[:, 0] ** 2 + la[:, 1] ** 2) + 1.0 / (lb[:, 0] ** 2 + lb[:, 1] ** 2)) * r * r
+
+    def transfer(corr):
+        a, b = homogeneous(corr[:, :2]), homogeneous(corr[:, 2:])
+        p, q = a @ H.T, b @ np.linalg.inv(H).T
+        e = np.sum((p[:, :2] / p[:, 2:] - b[:, :2]) ** 2, axis=1) + np.sum((q[:, :2] / q[:, 2:] - a[:, :2]) ** 2, axis=1)
+        return np.where((p[:, 2] <= 0.0) | (q[:, 2] <= 0.0), np.inf, e)
+
+    return {"essential": (1, E, sed), "homography": (2, H, transfer)}
+
+
+def run_guided(base, reps, I, n, Q, feats, image_offset, desc, ok, pair_images, row_offset, out, workspace):
+    rows = Q * n
+    xy_host = np.concatenate([np.column_stack([(f[:, 0] - BENCH_K[0, 2]) / BENCH_K[0, 0], (f[:, 1] - BENCH_K[1, 2]) / BENCH_K[1, 1]])
+                              for f in feats])
+    xy = device.to_device(xy_host, torch.float64)
+    rng = np.random.default_rng(1)
+    sample = np.hstack([xy_host[rng.integers(0, n, 200000)], xy_host[n + rng.integers(0, n, 200000)]])   # images 0 and 1
+    state = dict(ws=workspace)
+    for name, (code, model, error) in guided_models().items():
+        with np.errstate(all="ignore"):
+            e = error(sample)
+        for band, thr in (("5%", float(np.quantile(e[np.isfinite(e)], 0.05))), ("all", float("inf"))):
+            model_dev = device.to_device(np.tile(model.reshape(1, 9), (Q, 1)), torch.float64)
+            kind_dev = device.to_device(np.full(Q, code, dtype=np.int32), torch.int32)
+            thr_dev = device.to_device(np.full(Q, thr), torch.float64)
+
+            def guided():
+                state["ws"] = device.match_pairs_guided(I, I * n, image_offset, desc, ok, xy, pair_images, row_offset, model_dev,
+                                                        kind_dev, thr_dev, rows, n, 64, 0.8, True, out[:rows], out[rows:2 * rows],
+                                                        out[2 * rows:], state["ws"])
+
+            ms = event_ms(guided, reps)
+            with np.errstate(invalid="ignore"):
+                share = float(np.mean(e <= thr))
+            print(json.dumps(dict(base, what="guided", kind=name, band=band, threshold=thr, admitted_share_of_sample=share, ms=ms,
+                                  ms_per_pair=ms / Q, kept=int((out[:rows] >= 0).sum().item()))), flush=True)
+
+
+def run_shape(name, reps, loop_pairs, guided=False, kernel_only=False):
     I, n, neighbours = SHAPES[name]
     rng = np.random.default_rng(0)
     pairs = shape_pairs(I, neighbours)
@@ -95,6 +157,10 @@ def run_shape(name, reps, loop_pairs):
     print(json.dumps(dict(base, what="kernel", ms=kernel_ms, ms_per_pair=kernel_ms / Q, kept=kept,
                           workspace_mb=state["ws"].numel() / 1e6,
                           descriptor_pairs_per_s=2.0 * Q * n * n / (kernel_ms * 1e-3))), flush=True)
+    if guided:
+        run_guided(base, reps, I, n, Q, feats, image_offset, desc, ok, pair_images, row_offset, out, state["ws"])
+    if guided or kernel_only:
+        return
     api_ms = wall_ms(lambda: match_image_pairs(descriptors, pairs), max(reps // 3, 1))
     print(json.dumps(dict(base, what="api", ms=api_ms, ms_per_pair=api_ms / Q)), flush=True)
 
@@ -135,9 +201,11 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--loop-pairs", type=int, default=64)
     ap.add_argument("--shapes", nargs="+", default=list(SHAPES), choices=list(SHAPES))
+    ap.add_argument("--guided", action="store_true", help="time sfm_match_pairs_guided after the kernel, skip the rest")
+    ap.add_argument("--kernel-only", action="store_true", help="time the kernel alone")
     args = ap.parse_args()
     for name in args.shapes:
-        run_shape(name, args.reps, args.loop_pairs)
+        run_shape(name, args.reps, args.loop_pairs, args.guided, args.kernel_only)
 
 
 if __name__ == "__main__":
