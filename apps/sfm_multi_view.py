@@ -56,6 +56,11 @@ on its inliers with up to K rounds (``refine_relative_poses``) 
 averaging solvers run, so ``global_rotations`` and ``global_positions`` follow from the refined poses.  The output then holds
 ``pair_refinement``: the median and the largest pairwise rotation and translation-direction error against the scene's truth,
 before and after.  0, the default, is the path without it.
+
+``triangulation="robust"`` (``--triangulation robust``) triangulates with ``triangulate_tracks_robust`` (per-track RANSAC,
+DESIGN.md §6ae): one call instead of triangulating, dropping the observations above the threshold and triangulating once
+more; the observations it flags out on points that got an estimate become inactive.  The output then holds
+``triangulation``.  ``plain``, the default, is the path without it.
 """
 from __future__ import annotations
 
@@ -76,7 +81,7 @@ from lib.epipolar.epipolar_ransac import estimate_essential_mat_with_ransac
 from lib.epipolar.view_graph import choose_seed_pair, refine_relative_poses, verify_pairs
 from lib.feature_matching.matching import Match
 from lib.multiview.rotation_averaging import average_graph_rotations, inconsistent_pairs
-from lib.multiview.tracks import build_tracks, triangulate_tracks
+from lib.multiview.tracks import build_tracks, triangulate_tracks, triangulate_tracks_robust
 from lib.multiview.translation_averaging import average_graph_translations, global_poses
 from lib.pnp.pnp import estimate_pose_pnp_with_ransac
 from structure_from_motion_amd import _native, device, synthetic
@@ -86,6 +91,7 @@ MAX_VIEWS = 1024       # with bundle_solver="auto": a bound of the app (host-sid
 BUNDLE_SOLVERS = ("dense", "auto")
 BUNDLE_LOSSES = device.BUNDLE_LOSSES
 TRACK_SOURCES = ("given", "matches")
+TRIANGULATIONS = ("plain", "robust")
 VERIFY_ROUTES = ("loop", "batched")
 SEED_PAIRS = ("first", "auto")
 ROTATION_ROUTES = ("incremental", "global")
@@ -118,8 +124,9 @@ class Reconstruction:
     still in use (an observation dropped as an outlier stays dropped)."""
 
     def __init__(self, scene, threshold: float, refine_steps: int, min_angle_deg: float, bundle_solver: str = "dense",
-                 bundle_loss: str = "squared", bundle_loss_scale: float = 2.0):
+                 bundle_loss: str = "squared", bundle_loss_scale: float = 2.0, triangulation: str = "plain"):
         self.bundle_solver = bundle_solver
+        self.triangulation = triangulation
         # a squared loss is the call without a loss: the scale has no effect on it
         self.loss = {} if bundle_loss == "squared" else dict(loss=bundle_loss, loss_scale=bundle_loss_scale)
         self.adjusted = np.zeros(0, dtype=np.int64)   # the observations of the last adjustment
@@ -139,7 +146,18 @@ class Reconstruction:
 
     def triangulate(self, points: np.ndarray):
         """(Re-)triangulate `points` from their active observations in registered views; observations above the threshold
-        are dropped and the points they belonged to re-triangulated once."""
+        are dropped and the points they belonged to re-triangulated once.  With ``triangulation="robust"``: one robust call
+        instead, and the observations it flags 0 on points that got an estimate become inactive."""
+        if self.triangulation == "robust":
+            use = self.in_registered() & np.isin(self.pt, points)
+            if not use.any():
+                return
+            idx = np.nonzero(use)[0]
+            r = triangulate_tracks_robust(self.K, self.poses, self.cam[idx], self.pt[idx], self.uv[idx], self.threshold,
+                                          num_points=self.P, min_angle_deg=self.min_angle_deg, refine_steps=self.refine_steps)
+            self.X[points], self.status[points] = r.points[points], r.status[points]
+            self.active[idx[~np.isnan(r.observation_error) & ~r.inlier]] = False
+            return
         for attempt in range(2):
             use = self.in_registered() & np.isin(self.pt, points)
             if not use.any():
@@ -323,7 +341,9 @@ def run(views: int = 8, points: int = 2000, seed: int = 21, noise_px: float = 0.
         bundle_loss: str = "squared", bundle_loss_scale: float = 2.0, verify: str = "loop", seed_pair: str = "first",
         seed_min_angle_deg: float = 2.0, rotations: str = "incremental", drop_inconsistent_pairs_deg=None,
         positions: str = "incremental", register: str = "incremental", focal_error: float = 0.0,
-        bundle_refine=(), refine_pairs: int = 0) -> dict:
+        bundle_refine=(), refine_pairs: int = 0, triangulation: str = "plain") -> dict:
+    if triangulation not in TRIANGULATIONS:
+        raise ValueError(f"triangulation must be one of {TRIANGULATIONS}, got {triangulation!r}")
     if pnp_solver not in ("dlt", "p3p"):
         raise ValueError(f"pnp_solver must be 'dlt' or 'p3p', got {pnp_solver!r}")
     if e_solver not in ("eight_point", "five_point"):
@@ -390,7 +410,7 @@ def run(views: int = 8, points: int = 2000, seed: int = 21, noise_px: float = 0.
             build.update(pairs_essential=kinds["essential"], pairs_homography=kinds["homography"], pairs_none=kinds["none"])
     K = scene["K"]
     rec = Reconstruction(scene, reprojection_threshold, refine_steps, min_angle_deg=1.0, bundle_solver=bundle_solver,
-                         bundle_loss=bundle_loss, bundle_loss_scale=float(bundle_loss_scale))
+                         bundle_loss=bundle_loss, bundle_loss_scale=float(bundle_loss_scale), triangulation=triangulation)
     cam, pt, uv = rec.cam, rec.pt, rec.uv
     random.seed(seed)
 
@@ -505,6 +525,8 @@ def run(views: int = 8, points: int = 2000, seed: int = 21, noise_px: float = 0.
         out["focal"] = {"true": float(K_true[0, 0]), "error_before": float(abs(K[0, 0] / K_true[0, 0] - 1.0)),
                         "error_after": float(abs(rec.K[0, 0] / K_true[0, 0] - 1.0)),
                         "camera_matrix": [float(v) for v in np.asarray(rec.K).reshape(9)]}
+    if triangulation != "plain":
+        out["triangulation"] = triangulation
     if build is not None:
         out["track_build"] = build
     if auto_seed:
@@ -581,6 +603,9 @@ def main():
                     help="minimal solver that registers each further view: six-point DLT or P3P on four-item samples")
     ap.add_argument("--tracks", choices=TRACK_SOURCES, default="given",
                     help="given: the scene's tracks; matches: tracks built from RANSAC-verified pairwise matches")
+    ap.add_argument("--triangulation", choices=TRIANGULATIONS, default="plain",
+                    help="plain: the N-view DLT of all observations, those above the threshold dropped and the point triangulated "
+                         "once more; robust: per-track RANSAC in one call (triangulate_tracks_robust)")
     ap.add_argument("--verify", choices=VERIFY_ROUTES, default="loop",
                     help="with --tracks matches: loop: one essential-matrix RANSAC per pair; batched: all pairs in one "
                          "verify_pairs call (homography and five-point essential per pair)")
@@ -645,7 +670,7 @@ def main():
                          seed_min_angle_deg=args.seed_min_angle, rotations=args.rotations,
                          drop_inconsistent_pairs_deg=args.drop_inconsistent_pairs, positions=args.positions,
                          register=args.register, focal_error=args.focal_error, bundle_refine=refine,
-                         refine_pairs=args.refine_pairs)))
+                         refine_pairs=args.refine_pairs, triangulation=args.triangulation)))
 
 
 if __name__ == "__main__":

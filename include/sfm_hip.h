@@ -750,6 +750,49 @@ int sfm_triangulate_tracks(const double* K, int64_t cameras, int64_t points, int
                            double* obs_error, double* angle, sfm_tracks_info* info, void* workspace,
                            int64_t workspace_bytes, void* stream);
 
+/* ---- outlier-robust triangulation of multi-view tracks (csrc/sfm_tracks_robust.hip; an extension, off unless asked for) ----
+ * These symbols were added under ABI 15 without a version change: they are new, and nothing an ABI-15 caller uses changed. */
+
+#define SFM_TRACKS_NO_CONSENSUS 7 /* sfm_triangulate_tracks_robust only: no valid hypothesis, or fewer than min_views inliers,
+                                   * or inliers of one camera only: point, angle and errors NaN, no flags */
+
+typedef struct sfm_tracks_robust_info {
+    int64_t status;                 /* 0, or 1 when an index is out of range (every point SFM_TRACKS_BAD_INDEX) */
+    int64_t points_ok;              /* points with SFM_TRACKS_OK */
+    int64_t max_refine_steps_taken; /* the most Levenberg-Marquardt trial steps of any point */
+    int64_t inlier_observations;    /* the inlier flags set on points with SFM_TRACKS_OK */
+    int64_t hypotheses;             /* valid hypotheses scored, summed over the points */
+    int64_t reserved;               /* 0 */
+} sfm_tracks_robust_info;
+
+/* Bytes of workspace sfm_triangulate_tracks_robust needs; -1 for sizes it refuses. */
+int64_t sfm_tracks_robust_workspace_bytes(int64_t points, int64_t observations);
+
+/* sfm_triangulate_tracks for tracks that hold wrong observations: per-track RANSAC (the definition is
+ * tests/robust_tracks_oracle.py).  Point p has the observations o_0 .. o_{k-1} in increasing observation index.  An index out of
+ * range, fewer than min_views observations and a track of one camera give SFM_TRACKS_BAD_INDEX, _FEW_VIEWS and _DEGENERATE as
+ * there.  Otherwise, with T = k (k - 1) / 2 and H = min(T, max_hypotheses), hypothesis h is the pair i < j of rank r_h in
+ * lexicographic order, r_h = h when T <= max_hypotheses and h (T div max_hypotheses) + min(h, T mod max_hypotheses) otherwise
+ * (no random numbers).  It is valid when its two cameras differ, its two-view DLT (the four rows above, i then j) gives a
+ * finite unit null vector with |v3| > 1e-12, the point lies in front of both cameras and their two rays open at least
+ * min_angle.  A valid hypothesis scores n = the observations of the track with e <= max_error (sfm_pnp_score's e) and c = the
+ * sum of min(e, max_error) in run order; the winner has the largest n, then the smallest c, then the smallest h.  No valid
+ * hypothesis, or n < min_views, gives SFM_TRACKS_NO_CONSENSUS, and so does a winner whose inliers name one camera.  The point
+ * is then sfm_triangulate_tracks's N-view DLT and optional Levenberg-Marquardt over the winner's inliers only (a bad null
+ * vector: SFM_TRACKS_DEGENERATE).  At the final X: obs_error[m] = e_m for every observation of the track, inlier[m] =
+ * e_m <= max_error; fewer than min_views inliers, or inliers of one camera, give SFM_TRACKS_NO_CONSENSUS; the angle is taken
+ * over the pairs of final inliers, below min_angle gives SFM_TRACKS_SMALL_ANGLE, else SFM_TRACKS_OK.  SFM_TRACKS_BEHIND and
+ * _LARGE_ERROR do not occur.  OK and SMALL_ANGLE write the estimate, the angle, the errors and the flags; every other status
+ * writes NaN and no flags.  Deterministic, bit for bit, from run to run and under any permutation of the observations that
+ * keeps each point's own order.
+ * Arguments as sfm_triangulate_tracks, except: max_error (px^2) finite and >= 0; max_hypotheses in 1 .. 1024; inlier: dev
+ * uint8 [observations]; workspace at least sfm_tracks_robust_workspace_bytes. */
+int sfm_triangulate_tracks_robust(const double* K, int64_t cameras, int64_t points, int64_t observations, const double* poses,
+                                  const int32_t* camera_index, const int32_t* point_index, const double* pixels,
+                                  int min_views, double min_angle, double max_error, int refine_steps, int max_hypotheses,
+                                  double* points_out, uint8_t* status, double* obs_error, uint8_t* inlier, double* angle,
+                                  sfm_tracks_robust_info* info, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- multi-view tracks from pairwise matches (csrc/sfm_track_build.hip; an extension, off unless asked for) ----
  * These symbols were added under ABI 15 without a version change: they are new, and nothing an ABI-15 caller uses changed. */
 

@@ -190,6 +190,8 @@ SIGNATURES = {
     "sfm_bundle_adjust_calibrated": [_P, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _I64, _P, _P],
     "sfm_triangulate_tracks": [_P, _I64, _I64, _I64, _P, _P, _P, _P, C.c_int, _D, _D, C.c_int, _P, _P, _P, _P, _P, _P, _I64,
                                _P],
+    "sfm_triangulate_tracks_robust": [_P, _I64, _I64, _I64, _P, _P, _P, _P, C.c_int, _D, _D, C.c_int, C.c_int, _P, _P, _P, _P, _P,
+                                      _P, _P, _I64, _P],
     "sfm_build_tracks": [_I64, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P],
     "sfm_average_rotations": [_I64, _I64, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P],
     "sfm_detect_keypoints": [_P, _I64, _I64, _P, _I64, C.c_int, _P, _P, C.c_int, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _I64, _P],
@@ -201,7 +203,7 @@ OTHER_SYMBOLS = ["sfm_last_error", "sfm_abi_version", "sfm_score_workspace_bytes
                  "sfm_bundle_pcg_workspace_bytes_ex", "sfm_hamming_summary_workspace_bytes", "sfm_pair_poses_workspace_bytes",
                  "sfm_average_rotations_workspace_bytes", "sfm_average_translations_workspace_bytes",
                  "sfm_match_pairs_workspace_bytes", "sfm_detect_keypoints_workspace_bytes",
-                 "sfm_bundle_calibrated_workspace_bytes"]
+                 "sfm_bundle_calibrated_workspace_bytes", "sfm_tracks_robust_workspace_bytes"]
 
 # the losses of both bundle adjusters, in the order of their SFM_BUNDLE_LOSS_* codes (include/sfm_hip.h)
 BUNDLE_LOSSES = ("squared", "huber", "cauchy")
@@ -263,6 +265,12 @@ class PairRefineInfo(C.Structure):
     """sfm_pair_refine_info"""
     _fields_ = [("start_error", C.c_double), ("error", C.c_double), ("start_count", C.c_int32), ("count", C.c_int32),
                 ("accepted", C.c_int32), ("lm_steps", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
+class TracksRobustInfo(C.Structure):
+    """sfm_tracks_robust_info"""
+    _fields_ = [("status", C.c_int64), ("points_ok", C.c_int64), ("max_refine_steps_taken", C.c_int64),
+                ("inlier_observations", C.c_int64), ("hypotheses", C.c_int64), ("reserved", C.c_int64)]
 
 
 class BundleOptions(C.Structure):
@@ -362,6 +370,8 @@ def load() -> C.CDLL:
     lib.sfm_bundle_calibrated_workspace_bytes.argtypes = [_I64, _I64, _I64]
     lib.sfm_tracks_workspace_bytes.restype = C.c_int64
     lib.sfm_tracks_workspace_bytes.argtypes = [_I64, _I64]
+    lib.sfm_tracks_robust_workspace_bytes.restype = C.c_int64
+    lib.sfm_tracks_robust_workspace_bytes.argtypes = [_I64, _I64]
     lib.sfm_bundle_pcg_workspace_bytes.restype = C.c_int64
     lib.sfm_bundle_pcg_workspace_bytes.argtypes = [_I64, _I64, _I64]
     lib.sfm_bundle_pcg_workspace_bytes_ex.restype = C.c_int64

@@ -3,8 +3,8 @@
 // Point-major: a counting sort by point (integer atomics), a multi-workgroup exclusive scan of the counts, a scatter, then
 // each point's run sorted by observation index.  The result does not depend on the order the atomics ran in:
 // ord[off[p] .. off[p+1]) lists point p's observations in increasing observation index.  An index out of range sets *flag
-// and every later step returns at once (the order is then undefined).  Used by sfm_tracks.hip and both
-// bundle adjusters.
+// and every later step returns at once (the order is then undefined).  Used by sfm_tracks.hip,
+// sfm_tracks_robust.hip (§6ae) and both bundle adjusters.
 //
 // Camera-major, after the point-major order: a stable LSD radix sort of the point-major positions on the camera index,
 // 8 bits per pass (per-tile digit counts: 256 words per 1 024 observations, whatever the camera count), so that inside a

@@ -1026,6 +1026,57 @@ def read_tracks_info(info: torch.Tensor) -> TracksInfo:
 
 
 # ------------------------------------------------------------------------------------------------------
+# outlier-robust triangulation of multi-view tracks (csrc/sfm_tracks_robust.hip): the inputs of triangulate_tracks
+# ------------------------------------------------------------------------------------------------------
+TRACKS_NO_CONSENSUS = 7
+
+
+def triangulate_tracks_robust(poses, camera_indices, point_indices, pixels, points: int, K, max_error: float, min_views: int = 2,
+                              min_angle: float = 0.0, refine_steps: int = 0, max_hypotheses: int = 64, out=None, workspace=None):
+    """Per-track RANSAC over two-view hypotheses, MSAC scoring, refit on the winner's inliers (``sfm_triangulate_tracks_robust``,
+    DESIGN.md section 6ae; ctypes: there is no torch op) -> ((points [P,3], status uint8 [P] (TRACKS_*), obs_error [M] (px^2),
+    inlier uint8 [M], angle [P] (radians), info int64 [6] viewing the sfm_tracks_robust_info record; ``read_robust_tracks_info``),
+    the workspace it used: ``workspace`` when that is large enough, else a new one).  ``out`` = those six tensors are written
+    instead of new ones.  No host synchronisation."""
+    lib = _native.load()
+    P, M, Cn = int(points), int(pixels.shape[0]), int(poses.shape[0])
+    need = int(lib.sfm_tracks_robust_workspace_bytes(P, M))
+    if need < 0:
+        raise ValueError("triangulate_tracks_robust: sizes out of range (observations below 2^31, points below 2^31 - 1)")
+    dev = pixels.device
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty((max(need, 16),), dtype=torch.uint8, device=dev)
+    if out is None:
+        out = (torch.empty((P, 3), dtype=F64, device=dev), torch.empty((P,), dtype=torch.uint8, device=dev),
+               torch.empty((M,), dtype=F64, device=dev), torch.empty((M,), dtype=torch.uint8, device=dev),
+               torch.empty((P,), dtype=F64, device=dev), torch.empty((6,), dtype=torch.int64, device=dev))
+    X, status, err, inlier, angle, info = out
+    poses, camera_indices, point_indices, pixels = (t.contiguous() for t in (poses, camera_indices, point_indices, pixels))
+    Kc = (C.c_double * 9)(*_camera_list(K))
+    check(lib.sfm_triangulate_tracks_robust(Kc, Cn, P, M, _ptr(poses), _ptr(camera_indices), _ptr(point_indices), _ptr(pixels),
+                                            int(min_views), float(min_angle), float(max_error), int(refine_steps),
+                                            int(max_hypotheses), _ptr(X), _ptr(status), _ptr(err), _ptr(inlier), _ptr(angle),
+                                            _ptr(info), _ptr(workspace), workspace.numel(), _stream()),
+          "sfm_triangulate_tracks_robust")
+    return out, workspace
+
+
+@dataclass
+class RobustTracksInfo:
+    status: int                  # 0, or 1 when a camera or point index is out of range (every point TRACKS_BAD_INDEX)
+    points_ok: int               # points with TRACKS_OK
+    max_refine_steps_taken: int  # the most LM trial steps of any point
+    inlier_observations: int     # the inlier flags set on points with TRACKS_OK
+    hypotheses: int              # valid hypotheses scored, summed over the points
+
+
+def read_robust_tracks_info(info: torch.Tensor) -> RobustTracksInfo:
+    """Host copy of an sfm_tracks_robust_info record (int64 [6]) (synchronises)."""
+    raw = info.cpu().numpy()
+    return RobustTracksInfo(*(int(v) for v in raw[:5]))
+
+
+# ------------------------------------------------------------------------------------------------------
 # multi-view tracks from pairwise matches (csrc/sfm_track_build.hip): image_offset int32 [I+1], pair_images int32 [Q,2],
 # match_offset int32 [Q+1], match_index int32 [E,2] (local indices in the pair's two images)
 # ------------------------------------------------------------------------------------------------------

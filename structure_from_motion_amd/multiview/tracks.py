@@ -91,6 +91,78 @@ def triangulate_tracks(
 
 
 @dataclass
+class RobustTracksResult:
+    points: npt.NDArray             # (P, 3); NaN unless the status is TRACKS_OK or TRACKS_SMALL_ANGLE
+    status: npt.NDArray             # (P,) uint8, device.TRACKS_* (never BEHIND or LARGE_ERROR; TRACKS_NO_CONSENSUS is new)
+    observation_error: npt.NDArray  # (M,) squared reprojection error in px^2 at the point's final estimate, NaN without one
+    inlier: npt.NDArray             # (M,) bool: the observation's error is within the limit at the final estimate
+    angle_deg: npt.NDArray          # (P,) triangulation angle in degrees over the pairs of inlier observations
+    info: object                    # device.RobustTracksInfo
+
+
+def triangulate_tracks_robust(
+    camera_matrix: npt.NDArray,
+    poses: npt.NDArray,
+    camera_indices: Sequence[int],
+    point_indices: Sequence[int],
+    pixels: npt.NDArray,
+    max_reprojection_error: float,
+    num_points: Optional[int] = None,
+    min_views: int = 2,
+    min_angle_deg: float = 0.0,
+    refine_steps: int = 0,
+    max_hypotheses: int = 64,
+) -> RobustTracksResult:
+    """``triangulate_tracks`` for tracks that hold wrong observations (``sfm_triangulate_tracks_robust``).
+
+    Per track: two-view hypotheses from pairs of its observations (all of them, or ``max_hypotheses`` evenly spaced ones; no
+    random numbers), each scored over the whole track by its inlier count at ``max_reprojection_error`` (px^2, finite) and
+    its truncated error sum; the N-view DLT and the optional Levenberg-Marquardt then run over the winner's inliers only.
+    ``inlier`` flags the observations within the limit at the final estimate.  A point is OK when it has at least
+    ``min_views`` inliers from more than one camera and their triangulation angle is at least ``min_angle_deg``; a track
+    without such a consensus is ``device.TRACKS_NO_CONSENSUS``.  An index out of range is not an exception: every point
+    then has status ``device.TRACKS_BAD_INDEX`` and ``info.status`` is 1.  Every argument is checked before any device
+    work."""
+    K = check_camera_matrix(camera_matrix)
+    poses = _array(poses, "poses", (-1, 12))
+    pixels = _array(pixels, "pixels", (-1, 2))
+    m = pixels.shape[0]
+    cams = _indices(camera_indices, "camera_indices", m)
+    pts = _indices(point_indices, "point_indices", m)
+    if poses.shape[0] >= _INT32 or m >= _INT32:
+        raise ValueError("cameras and observations must number fewer than 2^31")
+    if num_points is None:
+        num_points = int(pts.max()) + 1 if m else 0
+    num_points = _non_negative_int(num_points, "num_points")
+    if num_points >= _INT32 - 1:
+        raise ValueError("num_points must be below 2^31 - 1")
+    min_views = _non_negative_int(min_views, "min_views", low=2)
+    refine_steps = _non_negative_int(refine_steps, "refine_steps")
+    max_hypotheses = _non_negative_int(max_hypotheses, "max_hypotheses", low=1)
+    if max_hypotheses > 1024:
+        raise ValueError(f"max_hypotheses must be in 1 .. 1024, got {max_hypotheses}")
+    try:
+        min_angle = float(min_angle_deg)
+        max_error = float(max_reprojection_error)
+    except (TypeError, ValueError):
+        raise ValueError("min_angle_deg and max_reprojection_error must be numbers") from None
+    if not (math.isfinite(min_angle) and min_angle >= 0.0):
+        raise ValueError(f"min_angle_deg must be finite and >= 0, got {min_angle_deg!r}")
+    if not (math.isfinite(max_error) and max_error >= 0.0):
+        raise ValueError(f"max_reprojection_error must be finite and >= 0, got {max_reprojection_error!r}")
+    import torch
+
+    from .. import device
+
+    device.require_gpu()
+    (X, status, err, inlier, angle, info), _ = device.triangulate_tracks_robust(
+        device.to_device(poses), device.to_device(cams, dtype=torch.int32), device.to_device(pts, dtype=torch.int32),
+        device.to_device(pixels), num_points, K, max_error, min_views, math.radians(min_angle), refine_steps, max_hypotheses)
+    return RobustTracksResult(X.cpu().numpy(), status.cpu().numpy(), err.cpu().numpy(), inlier.cpu().numpy().astype(bool),
+                              np.degrees(angle.cpu().numpy()), device.read_robust_tracks_info(info))
+
+
+@dataclass
 class TrackBuildResult:
     camera_indices: npt.NDArray     # (M,) int32: the image of each observation
     point_indices: npt.NDArray      # (M,) int32: the track of each observation (tracks 0 .. info.tracks - 1)
