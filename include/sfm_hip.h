@@ -565,6 +565,41 @@ int sfm_pnp_refine(const double* pts, int64_t n, int64_t batch, const double* K,
                    const double* err_in, double thr, int aggregation, int rounds, int max_steps, double* model_out,
                    uint8_t* mask_out, sfm_pnp_refine_info* info, void* stream);
 
+/* ---- absolute pose of every candidate view against the model in one call (csrc/sfm_register_views.hip; an
+ * extension, added under ABI 15) ----
+ * pts: dev [n_total,5] = {X, Y, Z, u, v} as sfm_pnp_score takes them, the 2D-3D items of all views, concatenated; offset: dev
+ * int64 [views+1], view v owns items offset[v] .. offset[v+1]-1 (n_v of them, any count, 0 included); min_extra: dev double
+ * [views], the gate of view v; K: host [9], row 2 (0, 0, 1).  View v's outputs are those of
+ * sfm_pnp_ransac_pass(SFM_PNP_SOLVER_P3P, seed + v * seed_stride, seed_stride, use_philox = 1, h_begin, its items, n_v, h_count,
+ * 1, K, thr, min_extra[v], aggregation, ...) with a mask, followed by sfm_pnp_refine(its items, n_v, 1, K, model[v, best_h],
+ * that mask with the winner's sample item 3 cleared, the record's best_err, thr, aggregation, refine_rounds, refine_max_steps,
+ * ...), bit for bit:
+ *   S int32 [views,h_count,8]; model [views,h_count,12]; flags, cnt int32 and s1, s2 double [views,h_count]; result [views]
+ *   (best_h local to the view); mask uint8 [n_total] (2 sample item of the winner, 1 other inlier, 0 otherwise);
+ *   pose_out [views,12]; mask_out uint8 [n_total] (1 = inlier of pose_out), must not alias mask; info [views]; status int32
+ *   [views].
+ * refine_rounds = 0 means what it means for sfm_pnp_refine: pose_out is the winner, mask_out is mask != 0 with item 3 cleared,
+ * accepted = lm_steps = 0.  Only the P3P solver is supported.  Every element of every output is written; a mask byte that no
+ * view owns is 0.  A view without a winner has pose_out = 12 NaNs, its mask and mask_out bytes 0 and info {+inf, 0, 0, 0}; a
+ * view with n_v < 4 also gets the pass's filler: rows of S all -1, models of 12 NaNs, flags SFM_FIT_DEGENERATE, cnt 0,
+ * s1 = s2 = NaN, hence a record without a winner (n_flagged = h_count).
+ * The offset table is checked on the device by the first launch: unless 0 <= offset[0] <= ... <= offset[views] <= n_total,
+ * every view is treated as empty (filler throughout, masks 0) and every status is SFM_REGISTER_BAD_OFFSETS; that is a status,
+ * not an error return, and nothing is read through such a table.
+ * Six launches whatever `views` is, nothing read back; every size and pointer is checked before the first launch
+ * (views <= 65535, n_total < 2^31, h_count >= 1, h_begin >= 0, refine_rounds >= 0, refine_max_steps >= 0, the aggregation,
+ * K); views == 0 is a no-op that writes nothing.  No atomics: a call is reproducible bit for bit. */
+#define SFM_REGISTER_OK 0          /* the view has a winner: pose_out is that winner, refined where a round was kept */
+#define SFM_REGISTER_NO_MODEL 1    /* n_v >= 4, but no hypothesis passed the gate */
+#define SFM_REGISTER_TOO_FEW 2     /* n_v < 4 */
+#define SFM_REGISTER_BAD_OFFSETS 3 /* the offset table of the call is not non-decreasing within [0, n_total]: every view */
+
+int sfm_register_views(uint64_t seed, uint64_t seed_stride, int64_t h_begin, const double* pts, int64_t n_total,
+                       const int64_t* offset, int64_t views, const double* min_extra, const double* K, int64_t h_count,
+                       double thr, int aggregation, int refine_rounds, int refine_max_steps, int32_t* S, double* model,
+                       int32_t* flags, int32_t* cnt, double* s1, double* s2, sfm_select_result* result, uint8_t* mask,
+                       double* pose_out, uint8_t* mask_out, sfm_pnp_refine_info* info, int32_t* status, void* stream);
+
 /* ---- bundle adjustment of cameras and points (csrc/sfm_bundle.hip; an extension, off unless asked for) ----
  * These symbols were added under ABI 14 without a version change: they are new, and nothing an ABI-14 caller uses changed. */
 

@@ -182,6 +182,7 @@ SIGNATURES = {
     "sfm_pair_poses": [_P, _I64, _P, _I64, _P, _I64, _P, _P, _P, _D, _P, _P, _I64, _P],
     "sfm_refine_pair_poses": [_P, _I64, _P, _I64, _P, _D, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P],
     "sfm_pnp_refine": [_P, _I64, _I64, _P, _P, _P, _P, _D, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P],
+    "sfm_register_views": [_U64, _U64, _I64, _P, _I64, _P, _I64, _P, _P, _I64, _D, C.c_int, C.c_int, C.c_int] + [_P] * 13,
     "sfm_bundle_adjust": [_P, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _I64, _P],
     "sfm_bundle_adjust_pcg": [_P, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, _D, _P, _P, _P, _P, _I64, _P],
     "sfm_bundle_adjust_ex": [_P, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _I64, _P, _P],
@@ -245,6 +246,10 @@ class PairVerdict(C.Structure):
     """sfm_pair_verdict"""
     _fields_ = [("kind", C.c_int32), ("homography_count", C.c_int32), ("essential_count", C.c_int32), ("reserved", C.c_int32),
                 ("ratio", C.c_double)]
+
+
+# the statuses of sfm_register_views, in the order of their SFM_REGISTER_* codes (include/sfm_hip.h)
+REGISTER_STATUS = ("ok", "no_model", "too_few", "bad_offsets")
 
 
 # the statuses of sfm_pair_pose, in the order of their SFM_POSE_* codes (include/sfm_hip.h)

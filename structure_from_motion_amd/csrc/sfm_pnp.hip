@@ -18,6 +18,7 @@
 #include "sfm_minimal_score.h"
 #include "sfm_p3p.h"
 #include "sfm_pnp.h"
+#include "sfm_pnp_pass.h"
 
 namespace {
 
@@ -25,23 +26,21 @@ using sfmhost::checked_entry;
 using sfmhost::fail;
 using sfmhost::fail_in;
 using sfmpnp::camera_from;
+using sfmpnp::kP3PSample;
 using sfmpnp::kPnPFields;
+using sfmpnp::p3p_solver;
+using sfmpnp::pnp_model;
 using sfmpnp::pnp_score;
 using sfmpnp::PnPCamera;
+using sfmpnp::PoseData;
+using sfmpnp::TilePoint;
 
 constexpr int kPnPSample = 6;   // the DLT's sample
-constexpr int kP3PSample = 4;   // P3P: three items solved for, the fourth picks the solution
 // A sample is degenerate when sigma_11 / sigma_1 of its conditioned 12 x 12 DLT matrix is below this (or not a number).
 // Coplanar and collinear points give three or more null vectors: their ratio is at the rounding level (~1e-16).
 constexpr double kPnPDegenerateFloor = 1e-9;
 
-// What the pose fits read besides the sample: the items of every batch entry and the camera.  The solvers below are the
-// `Solver` of sfmmin::minimal_fit_kernel (sfm_minimal_fit.h), named like the kernels they parameterise so that a profile
-// filtered by "pnp" / "p3p" finds minimal_fit_kernel<pnp_dlt_solver, ...> and minimal_fit_kernel<p3p_solver, ...>.
-struct PoseData {
-    const double* pts;
-    PnPCamera cam;
-};
+// PoseData, what the pose fits read besides the sample, and the P3P solver: sfm_pnp_pass.h.
 
 // --------------------------------------------------------------------------------------------------
 // Six-point DLT fit of one hypothesis (the steps of the PnP fitter, structure_from_motion_amd/pnp/pnp.py):
@@ -170,39 +169,14 @@ SFM_DEVICE int pnp_dlt_solver::fit(const Data& data, int64_t b, int64_t n, const
     return degenerate ? SFM_FIT_DEGENERATE : 0;
 }
 
-// P3P fit of one hypothesis (sfm_p3p.h) from sample indices idx[0..3]: SFM_FIT_DEGENERATE when items 0-2 are collinear or
-// coincide or an index is out of range; otherwise the chosen model, or 12 NaNs when the sample has no solution (flag 0).
-// One hypothesis per lane, all in registers: the up-to-four candidates are scored as they are made.
-struct p3p_solver {
-    static constexpr int kSample = kP3PSample, kModel = 12;
-    static constexpr const char* kName = "minimal_fit_kernel<p3p_solver>";
-    using Data = PoseData;
-    SFM_DEVICE static int fit(const Data& data, int64_t b, int64_t n, const int32_t (&idx)[8], double (&out)[12]) {
-        const double* __restrict__ pts = data.pts + b * n * kPnPFields;
-        bool bad = false;
-        const double* q0 = pts + checked_index(idx[0], n, bad) * kPnPFields;
-        const double* q1 = pts + checked_index(idx[1], n, bad) * kPnPFields;
-        const double* q2 = pts + checked_index(idx[2], n, bad) * kPnPFields;
-        const double* q3 = pts + checked_index(idx[3], n, bad) * kPnPFields;
-        const bool ok = sfmp3p::p3p_fit_one(q0, q1, q2, q3, data.cam, out);
-        return (bad || !ok) ? SFM_FIT_DEGENERATE : 0;
-    }
-};
-
 // --------------------------------------------------------------------------------------------------
-// Scoring: the loop of sfmmin::score_hypothesis (sfm_minimal_score.h) written out for the pose — one hypothesis per lane, the
-// points staged through LDS in tiles read by broadcast (a slot holds a point as three 16-byte words: 512 x 48 B = 24 KiB), every
-// point counted, the SAMPLE sample points then corrected.  All fp64 with the divisions of pnp_score: no fast path, so every
-// value is the oracle's bit for bit and only the summation order differs.  The kernel keeps its own copy of the loop because
-// score_kernel<SAMPLE, pnp_model> schedules the sample correction differently (108 and 110 VGPRs for the 106 and 112 here,
-// one s_waitcnt apart; the tile loop itself comes out the same).
+// Scoring: sfmpnp::score_pose_hypothesis (sfm_pnp_pass.h), the loop of sfmmin::score_hypothesis written out for the pose — one
+// hypothesis per lane, the points staged through LDS in tiles read by broadcast (a slot holds a point as three 16-byte words:
+// 512 x 48 B = 24 KiB), every point counted, the SAMPLE sample points then corrected.  The ragged call of
+// sfm_register_views.hip runs the same function over each view's own items.
 // --------------------------------------------------------------------------------------------------
 using sfmmin::kScoreBlock;
 using sfmmin::kScoreTile;
-
-struct alignas(16) TilePoint {
-    double2 xy, zu, v_;
-};
 
 template <int SAMPLE>
 __global__ __launch_bounds__(kScoreBlock) void pnp_score_kernel(const double* __restrict__ pts, int64_t n,
@@ -214,71 +188,16 @@ __global__ __launch_bounds__(kScoreBlock) void pnp_score_kernel(const double* __
     const int64_t h = (int64_t)blockIdx.x * kScoreBlock + threadIdx.x;
     const int64_t hc = h < h_count ? h : h_count - 1;  // lanes past the end score a valid hypothesis and store nothing
     const int64_t bh = b * h_count + hc;
-    const double* P = pts + b * n * kPnPFields;
-    double m[12];
-#pragma unroll
-    for (int i = 0; i < 12; ++i) m[i] = model[bh * 12 + i];
-    int c = 0;
-    double a1 = 0.0, a2 = 0.0;
-    for (int64_t base = 0; base < n; base += kScoreTile) {
-        const int count = (int)(n - base < kScoreTile ? n - base : kScoreTile);
-        __syncthreads();  // the previous tile has been read by every lane
-        for (int i = threadIdx.x; i < count; i += kScoreBlock) {
-            const double* q = P + (base + i) * kPnPFields;
-            tile[i].xy = make_double2(q[0], q[1]);
-            tile[i].zu = make_double2(q[2], q[3]);
-            tile[i].v_ = make_double2(q[4], 0.0);
-        }
-        __syncthreads();
-#pragma unroll 4
-        for (int j = 0; j < count; ++j) {
-            const TilePoint t = tile[j];
-            const double e = pnp_score(m, cam, t.xy.x, t.xy.y, t.zu.x, t.zu.y, t.v_.x);
-            const bool in = e <= thr;
-            c += in ? 1 : 0;
-            a1 += in ? e : 0.0;
-            a2 += in ? e * e : 0.0;
-        }
-    }
-    bool bad = false;
-#pragma unroll
-    for (int k = 0; k < SAMPLE; ++k) {
-        const double* q = P + checked_index(S[bh * 8 + k], n, bad) * kPnPFields;
-        const double e = pnp_score(m, cam, q[0], q[1], q[2], q[3], q[4]);
-        if (e <= thr) {
-            --c;
-        } else {
-            a1 += e;
-            a2 += e * e;
-        }
-    }
+    const sfmmin::HypothesisScore r =
+        sfmpnp::score_pose_hypothesis<SAMPLE>(tile, pts + b * n * kPnPFields, n, model + bh * 12, S + bh * 8, cam, thr);
     if (h < h_count) {
-        cnt[b * h_count + h] = c;
-        s1[b * h_count + h] = a1;
-        s2[b * h_count + h] = a2;
+        cnt[b * h_count + h] = r.c;
+        s1[b * h_count + h] = r.a1;
+        s2[b * h_count + h] = r.a2;
     }
 }
 
-// The `Model` of sfm_minimal_score.h for the winner's mask (sfmmin::mask_kernel): the pose and the camera in registers, a
-// point as the five doubles the error reads.
-struct pnp_model {
-    using Stored = double;
-    struct Item {
-        double f[kPnPFields];
-    };
-    static constexpr int kStride = kPnPFields, kModel = 12;
-    double m[12];
-    PnPCamera cam;
-    SFM_DEVICE pnp_model(const double* model, const PnPCamera& camera) : cam(camera) {
-#pragma unroll
-        for (int i = 0; i < 12; ++i) m[i] = model[i];
-    }
-    SFM_DEVICE static void load(const double* items, int64_t i, Item& slot) {
-#pragma unroll
-        for (int k = 0; k < kPnPFields; ++k) slot.f[k] = items[i * kPnPFields + k];
-    }
-    SFM_DEVICE double error(const Item& t) const { return pnp_score(m, cam, t.f[0], t.f[1], t.f[2], t.f[3], t.f[4]); }
-};
+// pnp_model, the `Model` of sfm_minimal_score.h for the winner's mask (sfmmin::mask_kernel): sfm_pnp_pass.h.
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
 // Every check of a call that depends on its sizes, before anything is launched: `sample` (4 or 6) items per sample, n at

@@ -11,7 +11,7 @@
 // (sfm_five_point.hip), the homography ops homography_fit, homography_score, homography_inlier_mask and the pass
 // homography_ransac_pass_ (sfm_homography.hip), the ragged two-view pass verify_pairs_ (sfm_view_graph.hip) and the poses
 // behind it pair_poses (sfm_view_graph_pose.hip) with their refinement refine_pair_poses (sfm_view_graph_refine.hip), and
-// the refinement of a winner pnp_refine (sfm_pnp_refine.hip),
+// the refinement of a winner pnp_refine (sfm_pnp_refine.hip), the ragged absolute-pose call register_views (sfm_register_views.hip),
 // bundle_adjust (sfm_bundle.hip, sfm_bundle_pcg.hip), triangulate_tracks (sfm_tracks.hip), build_tracks
 // (sfm_track_build.hip), average_rotations (sfm_rotation_averaging.hip) and average_translations
 // (sfm_translation_averaging.hip).  The reference call sites these serve: apps/sfm.py:110-119 (RANSAC-E), :133-138 (pose),
@@ -821,6 +821,88 @@ std::tuple<Tensor, Tensor, Tensor> pnp_refine_meta(const Tensor& pts, const Tens
             at::empty_symint({pts.sym_size(0), c10::SymInt(kRefineInfoWords)}, like(pts, at::kLong))};
 }
 
+// ---- absolute pose of every candidate view in one call (sfm_register_views.hip): pts [n_total, 5], offset int64 [views + 1],
+// min_extra double [views]; S [views, h, 8], model [views, h, 12], the score tables [views, h], result int64 [views, 5], mask
+// uint8 [n_total]; pose_out [views, 12], mask_out uint8 [n_total], info int64 [views, 3] (sfm_pnp_refine_info), status int32
+// [views] ------------------------------------------------------------------------------------------------------------------
+void register_views_out(const Tensor& pts, const Tensor& offset, const Tensor& min_extra, at::ArrayRef<double> K, int64_t seed,
+                        int64_t seed_stride, int64_t h_begin, double thr, int64_t aggregation, int64_t refine_rounds,
+                        int64_t refine_max_steps, Tensor& S, Tensor& model, Tensor& flags, Tensor& cnt, Tensor& s1, Tensor& s2,
+                        Tensor& result, Tensor& mask, Tensor& pose_out, Tensor& mask_out, Tensor& info, Tensor& status) {
+    const OpDevice scope(pts);
+    need(pts, "pts", at::kDouble);
+    need(offset, "offset", at::kLong);
+    need(min_extra, "min_extra", at::kDouble);
+    need(S, "S", at::kInt);
+    need(model, "model", at::kDouble);
+    for (const Tensor* t : {&flags, &cnt, &status}) need(*t, "flags / cnt / status", at::kInt);
+    for (const Tensor* t : {&s1, &s2, &pose_out}) need(*t, "s1 / s2 / pose_out", at::kDouble);
+    for (const Tensor* t : {&result, &info}) need(*t, "result / info", at::kLong);
+    need(mask, "mask", at::kByte);
+    need(mask_out, "mask_out", at::kByte);
+    check_K(K);
+    TORCH_CHECK(pts.dim() == 2 && pts.size(1) == 5, "sfm_hip: pts must be [n_total, 5]");
+    TORCH_CHECK(offset.dim() == 1 && offset.size(0) >= 1, "sfm_hip: offset must be int64 [views + 1]");
+    const int64_t n_total = pts.size(0), views = offset.size(0) - 1;
+    TORCH_CHECK(S.dim() == 3 && S.size(0) == views && S.size(2) == 8, "sfm_hip: S must be [views, h, 8]");
+    const int64_t h = S.size(1);
+    TORCH_CHECK(min_extra.numel() == views, "sfm_hip: min_extra must be [views]");
+    TORCH_CHECK(model.numel() == views * h * 12, "sfm_hip: model must be [views, h, 12]");
+    for (const Tensor* t : {&flags, &cnt, &s1, &s2}) TORCH_CHECK(t->numel() == views * h, "sfm_hip: flags, cnt, s1, s2 must be [views, h]");
+    TORCH_CHECK(result.numel() == views * kRecordWords, "sfm_hip: result must be int64 [views, 5]");
+    TORCH_CHECK(mask.numel() == n_total && mask_out.numel() == n_total, "sfm_hip: mask, mask_out must be uint8 [n_total]");
+    TORCH_CHECK(pose_out.numel() == views * 12, "sfm_hip: pose_out must be [views, 12]");
+    TORCH_CHECK(info.numel() == views * kRefineInfoWords, "sfm_hip: info must be int64 [views, 3]");
+    TORCH_CHECK(status.numel() == views, "sfm_hip: status must be int32 [views]");
+    TORCH_CHECK(refine_rounds >= 0 && refine_rounds <= 0x7FFFFFFF && refine_max_steps >= 0 && refine_max_steps <= 0x7FFFFFFF,
+                "sfm_hip: refine_rounds and refine_max_steps must be in [0, 2^31)");
+    ok(sfm_register_views((uint64_t)seed, (uint64_t)seed_stride, h_begin, ptr<double>(pts), n_total, ptr<int64_t>(offset), views,
+                          ptr<double>(min_extra), K.data(), h, thr, (int)aggregation, (int)refine_rounds, (int)refine_max_steps,
+                          ptr<int32_t>(S), ptr<double>(model), ptr<int32_t>(flags), ptr<int32_t>(cnt), ptr<double>(s1), ptr<double>(s2),
+                          reinterpret_cast<sfm_select_result*>(ptr<int64_t>(result)), ptr<uint8_t>(mask), ptr<double>(pose_out),
+                          ptr<uint8_t>(mask_out), reinterpret_cast<sfm_pnp_refine_info*>(ptr<int64_t>(info)), ptr<int32_t>(status),
+                          current_stream()),
+       "sfm_register_views");
+}
+
+// the functional form: h hypotheses per view -> (pose_out, mask_out, info, status, mask, result); the tables of the pass are
+// temporaries of the call
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> register_views(const Tensor& pts, const Tensor& offset,
+                                                                          const Tensor& min_extra, at::ArrayRef<double> K, int64_t seed,
+                                                                          int64_t seed_stride, int64_t h_begin, int64_t h, double thr,
+                                                                          int64_t aggregation, int64_t refine_rounds,
+                                                                          int64_t refine_max_steps) {
+    TORCH_CHECK(pts.dim() == 2 && offset.dim() == 1 && offset.size(0) >= 1, "sfm_hip: pts must be [n_total, 5], offset int64 [views + 1]");
+    TORCH_CHECK(h >= 1, "sfm_hip: register_views needs at least one hypothesis per view");
+    const int64_t n_total = pts.size(0), views = offset.size(0) - 1;
+    Tensor S = at::empty({views, h, 8}, like(pts, at::kInt)), model = at::empty({views, h, 12}, like(pts, at::kDouble));
+    Tensor flags = at::empty({views, h}, like(pts, at::kInt)), cnt = at::empty({views, h}, like(pts, at::kInt));
+    Tensor s1 = at::empty({views, h}, like(pts, at::kDouble)), s2 = at::empty({views, h}, like(pts, at::kDouble));
+    Tensor result = at::empty({views, kRecordWords}, like(pts, at::kLong));
+    Tensor mask = at::empty({n_total}, like(pts, at::kByte)), mask_out = at::empty({n_total}, like(pts, at::kByte));
+    Tensor pose_out = at::empty({views, 12}, like(pts, at::kDouble));
+    Tensor info = at::empty({views, kRefineInfoWords}, like(pts, at::kLong));
+    Tensor status = at::empty({views}, like(pts, at::kInt));
+    if (views == 0) {   // the entry is a no-op then: no item has a view
+        mask.zero_();
+        mask_out.zero_();
+    }
+    register_views_out(pts, offset, min_extra, K, seed, seed_stride, h_begin, thr, aggregation, refine_rounds, refine_max_steps, S, model,
+                       flags, cnt, s1, s2, result, mask, pose_out, mask_out, info, status);
+    return {pose_out, mask_out, info, status, mask, result};
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> register_views_meta(const Tensor& pts, const Tensor& offset, const Tensor&,
+                                                                               at::ArrayRef<double>, int64_t, int64_t, int64_t, int64_t,
+                                                                               double, int64_t, int64_t, int64_t) {
+    TORCH_CHECK(pts.dim() == 2 && offset.dim() == 1, "sfm_hip: pts must be [n_total, 5], offset int64 [views + 1]");
+    const c10::SymInt views = offset.sym_size(0) - 1;
+    return {at::empty_symint({views, c10::SymInt(12)}, like(pts, at::kDouble)), at::empty_symint({pts.sym_size(0)}, like(pts, at::kByte)),
+            at::empty_symint({views, c10::SymInt(kRefineInfoWords)}, like(pts, at::kLong)), at::empty_symint({views}, like(pts, at::kInt)),
+            at::empty_symint({pts.sym_size(0)}, like(pts, at::kByte)),
+            at::empty_symint({views, c10::SymInt(kRecordWords)}, like(pts, at::kLong))};
+}
+
 // bundle adjustment, dense (sfm_bundle.hip) and with the iterative Schur solver (sfm_bundle_pcg.hip): poses [C, 12], points
 // [P, 3], camera / point indices int32 [M], pixels [M, 2]; fixed: the indices of the fixed cameras; the iterative solver takes
 // max_cg_iterations and cg_tolerance as well; info int64 [4] viewing the sfm_bundle_info record, int64 [5] viewing
@@ -1445,6 +1527,12 @@ TORCH_LIBRARY(sfm_hip, m) {
           "int max_steps) -> (Tensor, Tensor, Tensor)");
     m.def("pnp_refine_(Tensor pts, Tensor model, Tensor mask, Tensor err, float[] K, float thr, int aggregation, int rounds, "
           "int max_steps, Tensor(a!) model_out, Tensor(b!) mask_out, Tensor(c!) info) -> ()");
+    m.def("register_views(Tensor pts, Tensor offset, Tensor min_extra, float[] K, int seed, int seed_stride, int h_begin, int h, "
+          "float thr, int aggregation, int refine_rounds, int refine_max_steps) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
+    m.def("register_views_(Tensor pts, Tensor offset, Tensor min_extra, float[] K, int seed, int seed_stride, int h_begin, float thr, "
+          "int aggregation, int refine_rounds, int refine_max_steps, Tensor(a!) S, Tensor(b!) model, Tensor(c!) flags, Tensor(d!) cnt, "
+          "Tensor(e!) s1, Tensor(f!) s2, Tensor(g!) result, Tensor(h!) mask, Tensor(i!) pose_out, Tensor(j!) mask_out, "
+          "Tensor(k!) info, Tensor(l!) status) -> ()");
     m.def("bundle_adjust(Tensor poses, Tensor points, Tensor camera_indices, Tensor point_indices, Tensor pixels, float[] K, "
           "int[] fixed, int max_steps) -> (Tensor, Tensor, Tensor)");
     m.def("bundle_adjust_(Tensor(a!) poses, Tensor(b!) points, Tensor camera_indices, Tensor point_indices, Tensor pixels, "
@@ -1524,6 +1612,8 @@ TORCH_LIBRARY_IMPL(sfm_hip, CUDA, m) {
     m.impl("p3p_ransac_pass_", &p3p_ransac_pass_out);
     m.impl("pnp_refine", &pnp_refine);
     m.impl("pnp_refine_", &pnp_refine_out);
+    m.impl("register_views", &register_views);
+    m.impl("register_views_", &register_views_out);
     m.impl("bundle_adjust", &bundle_adjust);
     m.impl("bundle_adjust_", &bundle_adjust_inplace);
     m.impl("bundle_adjust_pcg", &bundle_adjust_pcg);
@@ -1570,6 +1660,9 @@ void pnp_ransac_pass_out_meta(const Tensor&, int64_t, int64_t, bool, int64_t, at
                               Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, const std::optional<Tensor>&) {}
 void pnp_refine_out_meta(const Tensor&, const Tensor&, const Tensor&, const Tensor&, at::ArrayRef<double>, double, int64_t, int64_t,
                          int64_t, Tensor&, Tensor&, Tensor&) {}
+void register_views_out_meta(const Tensor&, const Tensor&, const Tensor&, at::ArrayRef<double>, int64_t, int64_t, int64_t, double, int64_t,
+                             int64_t, int64_t, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&,
+                             Tensor&, Tensor&) {}
 void bundle_adjust_out_meta(Tensor&, Tensor&, const Tensor&, const Tensor&, const Tensor&, at::ArrayRef<double>, at::ArrayRef<int64_t>,
                             int64_t, Tensor&) {}
 void bundle_adjust_pcg_out_meta(Tensor&, Tensor&, const Tensor&, const Tensor&, const Tensor&, at::ArrayRef<double>,
@@ -1621,6 +1714,8 @@ TORCH_LIBRARY_IMPL(sfm_hip, Meta, m) {
     m.impl("p3p_ransac_pass_", &pnp_ransac_pass_out_meta);
     m.impl("pnp_refine", &pnp_refine_meta);
     m.impl("pnp_refine_", &pnp_refine_out_meta);
+    m.impl("register_views", &register_views_meta);
+    m.impl("register_views_", &register_views_out_meta);
     m.impl("bundle_adjust", &bundle_adjust_meta);
     m.impl("bundle_adjust_", &bundle_adjust_out_meta);
     m.impl("bundle_adjust_pcg", &bundle_adjust_pcg_meta);

@@ -1453,3 +1453,48 @@ class ViewGraphWorkspace:
                                                                    "lm_steps", "status")})
             fields["refine_mask"] = self.refine_mask.cpu().numpy().copy()
         return fields
+
+
+# ------------------------------------------------------------------------------------------------------
+# Absolute pose of every candidate view in one call (csrc/sfm_register_views.hip): pts [N,5], the views'
+# 2D-3D items concatenated; offset int64 [V+1]; per view the P3P pass and the refinement of its winner
+# ------------------------------------------------------------------------------------------------------
+REGISTER_OK, REGISTER_NO_MODEL, REGISTER_TOO_FEW, REGISTER_BAD_OFFSETS = range(4)
+REGISTER_STATUS = _native.REGISTER_STATUS
+
+
+def read_register_status(status: torch.Tensor) -> np.ndarray:
+    """Host copy of the statuses of a ``sfm_register_views`` call (int32 [V], REGISTER_*) (synchronises)."""
+    return status.cpu().numpy().astype(np.int32)
+
+
+class RegisterViewsWorkspace:
+    """Pre-allocated device buffers of ``sfm_register_views`` for V views x H hypotheses over N items in all (about 152 bytes
+    per view-hypothesis).  ``run`` fills them; nothing is read back until the caller asks."""
+
+    def __init__(self, views: int, n_total: int, h: int, device=None):
+        dev = device or require_gpu()
+        self.views, self.n_total, self.h = views, n_total, h
+        i32, f64 = dict(dtype=torch.int32, device=dev), dict(dtype=F64, device=dev)
+        self.S = torch.empty((views, h, 8), **i32)
+        self.model = torch.empty((views, h, 12), **f64)
+        self.flags, self.cnt = torch.empty((views, h), **i32), torch.empty((views, h), **i32)
+        self.s1, self.s2 = torch.empty((views, h), **f64), torch.empty((views, h), **f64)
+        self.result = torch.empty((views, SELECT_BYTES // 8), dtype=torch.int64, device=dev)
+        self.mask = torch.empty((n_total,), dtype=torch.uint8, device=dev)
+        self.pose_out = torch.empty((views, 12), **f64)
+        self.mask_out = torch.empty((n_total,), dtype=torch.uint8, device=dev)
+        self.info = torch.empty((views, 3), dtype=torch.int64, device=dev)
+        self.status = torch.empty((views,), **i32)
+
+    def buffers(self):
+        """The output tensors in the order of the ``register_views_`` op."""
+        return (self.S, self.model, self.flags, self.cnt, self.s1, self.s2, self.result, self.mask, self.pose_out, self.mask_out,
+                self.info, self.status)
+
+    def run(self, pts: torch.Tensor, offset: torch.Tensor, min_extra: torch.Tensor, K, thr: float, aggregation: int, seed: int,
+            seed_stride: int = 1, h_begin: int = 0, refine_rounds: int = 2, refine_max_steps: int = 20) -> None:
+        """One ``sfm_register_views`` call (the ``register_views_`` op), enqueue-only: pts f64 [N,5], offset int64 [V+1],
+        min_extra f64 [V] on the device; view v draws its Philox samples with ``seed + v * seed_stride``."""
+        ops.load().register_views_(pts, offset, min_extra, _camera_list(K), _as_int64(seed), _as_int64(seed_stride), int(h_begin),
+                                   float(thr), int(aggregation), int(refine_rounds), int(refine_max_steps), *self.buffers())
