@@ -258,7 +258,8 @@ int sfm_ransac_pass_batch(uint64_t seed, const uint64_t* seed_dev, uint64_t seed
 
 /* Model selection (ransac.py:75-86): lowest aggregated error among hypotheses with
  * cnt >= min_extra, strict <, earliest index wins, NaN/inf never win.  sample_size: the items of a sample that enter
- * the mean and RMS aggregates (count + sample_size): 8 (eight-point), 6 (five-point, PnP DLT) or 4 (P3P); SFM_EINVAL
+ * the mean and RMS aggregates (count + sample_size): 8 (eight-point), 6 (five-point, PnP DLT), 4 (P3P, homography) or 3
+ * (similarity); SFM_EINVAL
  * otherwise.  result: dev [batch]. */
 int sfm_select_best(const int32_t* cnt, const double* s1, const double* s2, const int32_t* flags, int64_t h_count, int64_t batch,
                     double min_extra, int aggregation, int64_t h_offset, int sample_size, sfm_select_result* result, void* stream);
@@ -599,6 +600,64 @@ int sfm_register_views(uint64_t seed, uint64_t seed_stride, int64_t h_begin, con
                        double thr, int aggregation, int refine_rounds, int refine_max_steps, int32_t* S, double* model,
                        int32_t* flags, int32_t* cnt, double* s1, double* s2, sfm_select_result* result, uint8_t* mask,
                        double* pose_out, uint8_t* mask_out, sfm_pnp_refine_info* info, int32_t* status, void* stream);
+
+/* ---- RANSAC similarity alignment of two reconstructions (csrc/sfm_similarity.hip; an extension, added under
+ * ABI 15) ----
+ * pairs: dev [batch,n,6] = {ax, ay, az, bx, by, bz}, 16-byte aligned; a model is 13 doubles R (row-major) | t | s with
+ * b ~ s R a + t.  The error of a pair is e = |s R a + t - b|^2, squared and in the units of side B (operation order fixed in
+ * csrc/sfm_similarity.h).  The least-squares model of an index set I (Umeyama 1991; Horn 1987): mu_a, mu_b the means over I,
+ * a' = a - mu_a, b' = b - mu_b, M = sum b' a'^T, sa2 = sum |a'|^2, sb2 = sum |b'|^2; R = argmax over SO(3) of tr(R^T M), always
+ * a proper rotation; s = tr(R^T M) / sa2; t = mu_b - s R mu_a.  With sigma_1 >= sigma_2 >= sigma_3 the singular values of M and
+ * d = sigma_2 + sign(det M) sigma_3 (d = sigma_2 when det M = 0), the flag is SFM_FIT_DEGENERATE when d <= 1e-9 sqrt(sa2 sb2),
+ * sa2 = 0, s is not finite or <= 0, anything is not a number or, for a minimal fit, a sample index lies outside [0, n).
+ * n >= 3. */
+
+/* One similarity pass: three-item fit (from S, or with use_philox from the first 3 of philox_sample8(seed + b * seed_stride,
+ * h_begin + h), all 8 stored in S, -1 at positions >= n), scoring (cnt[b,h] = non-sample items with e <= thr; s1 / s2 = sums of
+ * e / e^2 over the 3 sample items plus those survivors), selection (sfm_select_best with sample_size 3) and, when `mask` is not
+ * NULL, the winner's mask (2 sample item, 1 other inlier, 0 otherwise; all 0 without a winner) — every argument checked before
+ * the first launch.  S: dev int32 [batch,h_count,8]; model: dev [batch,h_count,13]; flags, cnt: dev int32 and s1, s2: dev double
+ * [batch,h_count]; result: dev [batch]; mask: dev uint8 [batch,n] or NULL. */
+int sfm_similarity_ransac_pass(uint64_t seed, uint64_t seed_stride, int use_philox, int64_t h_begin, const double* pairs, int64_t n,
+                               int64_t h_count, int64_t batch, double thr, double min_extra, int aggregation, int32_t* S,
+                               double* model, int32_t* flags, int32_t* cnt, double* s1, double* s2, sfm_select_result* result,
+                               uint8_t* mask, void* stream);
+
+/* Bytes of workspace sfm_similarity_fit_masked needs; -1 for sizes it refuses (n < 3, n >= 2^31, batch < 0 or > 65535). */
+int64_t sfm_similarity_fit_workspace_bytes(int64_t n, int64_t batch);
+
+/* The least-squares model of the set {i : mask[b,i] != 0} of every entry, or of all n items when mask is NULL: one model and
+ * one flag per entry.  Two reduction passes (centroid, then centred moments) over up to 128 blocks per entry whose partial sums
+ * are added in block order, then the solve: three launches, no atomics, bit-reproducible.  mask: dev uint8 [batch,n] or NULL;
+ * model_out: dev [batch,13]; flags_out: dev int32 [batch]; workspace: dev, 16-byte aligned, at least
+ * sfm_similarity_fit_workspace_bytes(n, batch).  SFM_EINVAL before the first launch for a refused size, a null or misaligned
+ * pointer or a workspace too small; batch == 0 is a no-op. */
+int sfm_similarity_fit_masked(const double* pairs, int64_t n, int64_t batch, const uint8_t* mask, double* model_out, int32_t* flags_out,
+                              void* workspace, int64_t workspace_bytes, void* stream);
+
+typedef struct sfm_similarity_refine_info {
+    double error;       /* aggregated error of the model left in model_out (over its `count` inliers) */
+    int32_t count;      /* inliers of that model (for an unrefined model: non-zero entries of mask_in) */
+    int32_t accepted;   /* rounds whose result was kept (0 = model_out is model_in) */
+    int32_t rounds_run; /* rounds that fitted a model: entered with at least 3 inliers (a degenerate or rejected one included) */
+    int32_t reserved;   /* 0 */
+} sfm_similarity_refine_info;
+
+/* Bytes of workspace sfm_similarity_refine needs; -1 for sizes it refuses (as sfm_similarity_fit_workspace_bytes). */
+int64_t sfm_similarity_refine_workspace_bytes(int64_t n, int64_t batch);
+
+/* Per entry, up to `rounds` times: the least-squares model of the current inliers (the reductions and the solve of
+ * sfm_similarity_fit_masked), every item re-scored (e <= thr), and the result kept iff it has more inliers, or as many and a
+ * lower aggregated error (the rule of sfm_pnp_refine).  A round stops early with fewer than 3 inliers or a degenerate set, and
+ * nothing follows a rejected round.  model_in: dev [batch,13] (e.g. model[b, best_h] of a pass); mask_in: dev uint8 [batch,n],
+ * non-zero = inlier; err_in: dev [batch], the aggregated error of model_in (sfm_select_result.best_err); model_out: dev
+ * [batch,13]; mask_out: dev uint8 [batch,n], 1 = inlier, must not alias mask_in; info: dev [batch]; workspace: dev, 16-byte
+ * aligned, at least sfm_similarity_refine_workspace_bytes(n, batch).  An entry whose mask is all zero keeps its model and reports
+ * count 0; rounds = 0 copies.  2 + 4 rounds launches, nothing read back; SFM_EINVAL before the first launch for a refused size,
+ * rounds < 0, an unknown aggregation, a null or misaligned pointer or a workspace too small. */
+int sfm_similarity_refine(const double* pairs, int64_t n, int64_t batch, const double* model_in, const uint8_t* mask_in,
+                          const double* err_in, double thr, int aggregation, int rounds, double* model_out, uint8_t* mask_out,
+                          sfm_similarity_refine_info* info, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---- bundle adjustment of cameras and points (csrc/sfm_bundle.hip; an extension, off unless asked for) ----
  * These symbols were added under ABI 14 without a version change: they are new, and nothing an ABI-14 caller uses changed. */

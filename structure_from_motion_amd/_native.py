@@ -178,6 +178,10 @@ SIGNATURES = {
     "sfm_homography_inlier_mask": [_P, _I64, _P, _P, _I64, _I64, _P, _D, _P, _P],
     "sfm_homography_ransac_pass": [_U64, _U64, C.c_int, _I64, _P, _I64, _I64, _I64, _D, _D, C.c_int, _P, _P, _P, _P, _P, _P,
                                    _P, _P, _P],
+    "sfm_similarity_ransac_pass": [_U64, _U64, C.c_int, _I64, _P, _I64, _I64, _I64, _D, _D, C.c_int, _P, _P, _P, _P, _P, _P,
+                                   _P, _P, _P],
+    "sfm_similarity_fit_masked": [_P, _I64, _I64, _P, _P, _P, _P, _I64, _P],
+    "sfm_similarity_refine": [_P, _I64, _I64, _P, _P, _P, _D, C.c_int, C.c_int, _P, _P, _P, _P, _I64, _P],
     "sfm_verify_pairs": [_U64, _U64, _I64, _P, _I64, _P, _I64, _P, _I64, _D, C.c_int, _D] + [_P] * 17,
     "sfm_pair_poses": [_P, _I64, _P, _I64, _P, _I64, _P, _P, _P, _D, _P, _P, _I64, _P],
     "sfm_refine_pair_poses": [_P, _I64, _P, _I64, _P, _D, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P],
@@ -204,7 +208,8 @@ OTHER_SYMBOLS = ["sfm_last_error", "sfm_abi_version", "sfm_score_workspace_bytes
                  "sfm_bundle_pcg_workspace_bytes_ex", "sfm_hamming_summary_workspace_bytes", "sfm_pair_poses_workspace_bytes",
                  "sfm_average_rotations_workspace_bytes", "sfm_average_translations_workspace_bytes",
                  "sfm_match_pairs_workspace_bytes", "sfm_detect_keypoints_workspace_bytes",
-                 "sfm_bundle_calibrated_workspace_bytes", "sfm_tracks_robust_workspace_bytes"]
+                 "sfm_bundle_calibrated_workspace_bytes", "sfm_tracks_robust_workspace_bytes",
+                 "sfm_similarity_fit_workspace_bytes", "sfm_similarity_refine_workspace_bytes"]
 
 # the losses of both bundle adjusters, in the order of their SFM_BUNDLE_LOSS_* codes (include/sfm_hip.h)
 BUNDLE_LOSSES = ("squared", "huber", "cauchy")
@@ -246,6 +251,12 @@ class PairVerdict(C.Structure):
     """sfm_pair_verdict"""
     _fields_ = [("kind", C.c_int32), ("homography_count", C.c_int32), ("essential_count", C.c_int32), ("reserved", C.c_int32),
                 ("ratio", C.c_double)]
+
+
+class SimilarityRefineInfo(C.Structure):
+    """sfm_similarity_refine_info"""
+    _fields_ = [("error", C.c_double), ("count", C.c_int32), ("accepted", C.c_int32), ("rounds_run", C.c_int32),
+                ("reserved", C.c_int32)]
 
 
 # the statuses of sfm_register_views, in the order of their SFM_REGISTER_* codes (include/sfm_hip.h)
@@ -391,6 +402,10 @@ def load() -> C.CDLL:
     lib.sfm_average_translations_workspace_bytes.argtypes = [_I64, _I64]
     lib.sfm_match_pairs_workspace_bytes.restype = C.c_int64
     lib.sfm_match_pairs_workspace_bytes.argtypes = [_I64, _I64, _I64]
+    lib.sfm_similarity_fit_workspace_bytes.restype = C.c_int64
+    lib.sfm_similarity_fit_workspace_bytes.argtypes = [_I64, _I64]
+    lib.sfm_similarity_refine_workspace_bytes.restype = C.c_int64
+    lib.sfm_similarity_refine_workspace_bytes.argtypes = [_I64, _I64]
     lib.sfm_detect_keypoints_workspace_bytes.restype = C.c_int64
     lib.sfm_detect_keypoints_workspace_bytes.argtypes = [_I64]
     if lib.sfm_abi_version() != ABI_VERSION:

@@ -1026,11 +1026,12 @@ int sfm_hartley_normalize(const double* coords, int64_t n, double* out, void* st
 int sfm_select_best(const int32_t* cnt, const double* s1, const double* s2, const int32_t* flags, int64_t h_count, int64_t batch,
                     double min_extra, int aggregation, int64_t h_offset, int sample_size, sfm_select_result* result, void* stream) {
     switch (sample_size) {
+        case 3: return select_best_launch<3>(cnt, s1, s2, flags, h_count, batch, min_extra, aggregation, h_offset, result, stream);
         case 4: return select_best_launch<4>(cnt, s1, s2, flags, h_count, batch, min_extra, aggregation, h_offset, result, stream);
         case 6: return select_best_launch<6>(cnt, s1, s2, flags, h_count, batch, min_extra, aggregation, h_offset, result, stream);
         case 8: return select_best_launch<8>(cnt, s1, s2, flags, h_count, batch, min_extra, aggregation, h_offset, result, stream);
     }
-    return fail(SFM_EINVAL, "sfm_select_best: sample_size must be 4, 6 or 8");
+    return fail(SFM_EINVAL, "sfm_select_best: sample_size must be 3, 4, 6 or 8");
 }
 
 int sfm_inlier_mask(const double* corr, int64_t n, const double* E, const int32_t* S, int64_t h_count, int64_t batch,

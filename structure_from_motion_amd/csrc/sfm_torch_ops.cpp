@@ -12,6 +12,7 @@
 // homography_ransac_pass_ (sfm_homography.hip), the ragged two-view pass verify_pairs_ (sfm_view_graph.hip) and the poses
 // behind it pair_poses (sfm_view_graph_pose.hip) with their refinement refine_pair_poses (sfm_view_graph_refine.hip), and
 // the refinement of a winner pnp_refine (sfm_pnp_refine.hip), the ragged absolute-pose call register_views (sfm_register_views.hip),
+// the similarity alignment similarity_ransac_pass, similarity_fit and similarity_refine (sfm_similarity.hip),
 // bundle_adjust (sfm_bundle.hip, sfm_bundle_pcg.hip), triangulate_tracks (sfm_tracks.hip), build_tracks
 // (sfm_track_build.hip), average_rotations (sfm_rotation_averaging.hip) and average_translations
 // (sfm_translation_averaging.hip).  The reference call sites these serve: apps/sfm.py:110-119 (RANSAC-E), :133-138 (pose),
@@ -903,6 +904,145 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> register_views_meta(c
             at::empty_symint({views, c10::SymInt(kRecordWords)}, like(pts, at::kLong))};
 }
 
+// ---- similarity alignment of two reconstructions (sfm_similarity.hip): pairs [batch, n, 6], S [batch, h, 8] (first 3 entries
+// used), model [batch, h, 13] = R | t | s; the masked fit and the refinement take model [batch, 13], mask uint8 [batch, n], err
+// [batch] and leave info int64 [batch, 3] viewing the sfm_similarity_refine_info records.  Their workspaces come from the
+// caching allocator, stream-ordered like everything else ----------------------------------------------------------------
+constexpr int64_t kSimilarityModelWidth = 13;
+constexpr int64_t kSimilarityInfoWords = sizeof(sfm_similarity_refine_info) / 8;
+
+Dims similarity_dims(const Tensor& pairs, const Tensor& S) {
+    TORCH_CHECK(pairs.dim() == 3 && pairs.size(2) == 6, "sfm_hip: pairs must be [batch, n, 6]");
+    TORCH_CHECK(S.dim() == 3 && S.size(0) == pairs.size(0) && S.size(2) == 8, "sfm_hip: S must be [batch, h, 8]");
+    return {pairs.size(0), pairs.size(1), S.size(1)};
+}
+
+void similarity_ransac_pass_out(const Tensor& pairs, int64_t seed, int64_t seed_stride, bool use_philox, int64_t h_begin, double thr,
+                                double min_extra, int64_t aggregation, Tensor& S, Tensor& model, Tensor& flags, Tensor& cnt, Tensor& s1,
+                                Tensor& s2, Tensor& result, const std::optional<Tensor>& mask) {
+    const OpDevice scope(pairs);
+    const Dims d = pass_checks(pairs, "pairs", similarity_dims, S, model, "model", flags, cnt, s1, s2, result, mask);
+    TORCH_CHECK(model.dim() == 3 && model.size(0) == d.batch && model.size(1) == d.h && model.size(2) == kSimilarityModelWidth,
+                "sfm_hip: model must be [batch, h, 13]");
+    ok(sfm_similarity_ransac_pass((uint64_t)seed, (uint64_t)seed_stride, use_philox ? 1 : 0, h_begin, ptr<double>(pairs), d.n, d.h,
+                                  d.batch, thr, min_extra, (int)aggregation, ptr<int32_t>(S), ptr<double>(model), ptr<int32_t>(flags),
+                                  ptr<int32_t>(cnt), ptr<double>(s1), ptr<double>(s2),
+                                  reinterpret_cast<sfm_select_result*>(ptr<int64_t>(result)), ptr<uint8_t>(mask), current_stream()),
+       "sfm_similarity_ransac_pass");
+}
+
+// the functional form: h Philox-sampled hypotheses per entry -> (model, flags, cnt, s1, s2, S, result, mask)
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> similarity_ransac_pass(const Tensor& pairs, int64_t seed,
+                                                                                                  int64_t seed_stride, int64_t h_begin,
+                                                                                                  int64_t h, double thr, double min_extra,
+                                                                                                  int64_t aggregation) {
+    TORCH_CHECK(pairs.dim() == 3, "sfm_hip: pairs must be [batch, n, 6]");
+    TORCH_CHECK(h >= 0, "sfm_hip: similarity_ransac_pass needs h >= 0");
+    const int64_t batch = pairs.size(0), n = pairs.size(1);
+    Tensor S = at::empty({batch, h, 8}, like(pairs, at::kInt)), model = at::empty({batch, h, kSimilarityModelWidth}, like(pairs, at::kDouble));
+    Tensor flags = at::empty({batch, h}, like(pairs, at::kInt)), cnt = at::empty({batch, h}, like(pairs, at::kInt));
+    Tensor s1 = at::empty({batch, h}, like(pairs, at::kDouble)), s2 = at::empty({batch, h}, like(pairs, at::kDouble));
+    Tensor result = at::empty({batch, kRecordWords}, like(pairs, at::kLong));
+    Tensor mask = at::empty({batch, n}, like(pairs, at::kByte));
+    similarity_ransac_pass_out(pairs, seed, seed_stride, true, h_begin, thr, min_extra, aggregation, S, model, flags, cnt, s1, s2, result,
+                               mask);
+    return {model, flags, cnt, s1, s2, S, result, mask};
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> similarity_ransac_pass_meta(const Tensor& pairs, int64_t, int64_t,
+                                                                                                       int64_t, int64_t h_count, double,
+                                                                                                       double, int64_t) {
+    TORCH_CHECK(pairs.dim() == 3, "sfm_hip: pairs must be [batch, n, 6]");
+    const c10::SymInt b = pairs.sym_size(0), n = pairs.sym_size(1), h(h_count);
+    return {at::empty_symint({b, h, c10::SymInt(kSimilarityModelWidth)}, like(pairs, at::kDouble)),
+            at::empty_symint({b, h}, like(pairs, at::kInt)),
+            at::empty_symint({b, h}, like(pairs, at::kInt)),
+            at::empty_symint({b, h}, like(pairs, at::kDouble)),
+            at::empty_symint({b, h}, like(pairs, at::kDouble)),
+            at::empty_symint({b, h, c10::SymInt(8)}, like(pairs, at::kInt)),
+            at::empty_symint({b, c10::SymInt(kRecordWords)}, like(pairs, at::kLong)),
+            at::empty_symint({b, n}, like(pairs, at::kByte))};
+}
+
+Tensor similarity_workspace(const Tensor& pairs, int64_t bytes, const char* what) {
+    TORCH_CHECK(bytes >= 0, "sfm_hip: ", what, " refuses these sizes (need 3 <= n < 2^31 and batch <= 65535)");
+    return at::empty({bytes > 16 ? bytes : 16}, like(pairs, at::kByte));
+}
+
+void similarity_fit_out(const Tensor& pairs, const std::optional<Tensor>& mask, Tensor& model_out, Tensor& flags_out) {
+    const OpDevice scope(pairs);
+    need(pairs, "pairs", at::kDouble);
+    if (mask.has_value()) need(*mask, "mask", at::kByte);
+    need(model_out, "model_out", at::kDouble);
+    need(flags_out, "flags_out", at::kInt);
+    TORCH_CHECK(pairs.dim() == 3 && pairs.size(2) == 6, "sfm_hip: pairs must be [batch, n, 6]");
+    const int64_t batch = pairs.size(0), n = pairs.size(1);
+    TORCH_CHECK(!mask.has_value() || mask->numel() == batch * n, "sfm_hip: mask must be uint8 [batch, n]");
+    TORCH_CHECK(model_out.numel() == batch * kSimilarityModelWidth, "sfm_hip: model_out must be [batch, 13]");
+    TORCH_CHECK(flags_out.numel() == batch, "sfm_hip: flags_out must be int32 [batch]");
+    Tensor ws = similarity_workspace(pairs, sfm_similarity_fit_workspace_bytes(n, batch), "sfm_similarity_fit_masked");
+    ok(sfm_similarity_fit_masked(ptr<double>(pairs), n, batch, ptr<uint8_t>(mask), ptr<double>(model_out), ptr<int32_t>(flags_out),
+                                 ws.data_ptr(), ws.numel(), current_stream()),
+       "sfm_similarity_fit_masked");
+}
+
+std::tuple<Tensor, Tensor> similarity_fit(const Tensor& pairs, const std::optional<Tensor>& mask) {
+    TORCH_CHECK(pairs.dim() == 3, "sfm_hip: pairs must be [batch, n, 6]");
+    Tensor model_out = at::empty({pairs.size(0), kSimilarityModelWidth}, like(pairs, at::kDouble));
+    Tensor flags_out = at::empty({pairs.size(0)}, like(pairs, at::kInt));
+    similarity_fit_out(pairs, mask, model_out, flags_out);
+    return {model_out, flags_out};
+}
+
+std::tuple<Tensor, Tensor> similarity_fit_meta(const Tensor& pairs, const std::optional<Tensor>&) {
+    TORCH_CHECK(pairs.dim() == 3, "sfm_hip: pairs must be [batch, n, 6]");
+    return {at::empty_symint({pairs.sym_size(0), c10::SymInt(kSimilarityModelWidth)}, like(pairs, at::kDouble)),
+            at::empty_symint({pairs.sym_size(0)}, like(pairs, at::kInt))};
+}
+
+void similarity_refine_out(const Tensor& pairs, const Tensor& model, const Tensor& mask, const Tensor& err, double thr,
+                           int64_t aggregation, int64_t rounds, Tensor& model_out, Tensor& mask_out, Tensor& info) {
+    const OpDevice scope(pairs);
+    need(pairs, "pairs", at::kDouble);
+    need(model, "model", at::kDouble);
+    need(mask, "mask", at::kByte);
+    need(err, "err", at::kDouble);
+    need(model_out, "model_out", at::kDouble);
+    need(mask_out, "mask_out", at::kByte);
+    need(info, "info", at::kLong);
+    TORCH_CHECK(pairs.dim() == 3 && pairs.size(2) == 6, "sfm_hip: pairs must be [batch, n, 6]");
+    const int64_t batch = pairs.size(0), n = pairs.size(1);
+    TORCH_CHECK(model.numel() == batch * kSimilarityModelWidth && model_out.numel() == batch * kSimilarityModelWidth,
+                "sfm_hip: model, model_out must be [batch, 13]");
+    TORCH_CHECK(mask.numel() == batch * n && mask_out.numel() == batch * n, "sfm_hip: mask, mask_out must be uint8 [batch, n]");
+    TORCH_CHECK(err.numel() == batch, "sfm_hip: err must be [batch]");
+    TORCH_CHECK(info.numel() == batch * kSimilarityInfoWords, "sfm_hip: info must be int64 [batch, 3]");
+    Tensor ws = similarity_workspace(pairs, sfm_similarity_refine_workspace_bytes(n, batch), "sfm_similarity_refine");
+    ok(sfm_similarity_refine(ptr<double>(pairs), n, batch, ptr<double>(model), ptr<uint8_t>(mask), ptr<double>(err), thr,
+                             (int)aggregation, (int)rounds, ptr<double>(model_out), ptr<uint8_t>(mask_out),
+                             reinterpret_cast<sfm_similarity_refine_info*>(ptr<int64_t>(info)), ws.data_ptr(), ws.numel(),
+                             current_stream()),
+       "sfm_similarity_refine");
+}
+
+std::tuple<Tensor, Tensor, Tensor> similarity_refine(const Tensor& pairs, const Tensor& model, const Tensor& mask, const Tensor& err,
+                                                     double thr, int64_t aggregation, int64_t rounds) {
+    TORCH_CHECK(pairs.dim() == 3, "sfm_hip: pairs must be [batch, n, 6]");
+    Tensor model_out = at::empty({pairs.size(0), kSimilarityModelWidth}, like(pairs, at::kDouble));
+    Tensor mask_out = at::empty({pairs.size(0), pairs.size(1)}, like(pairs, at::kByte));
+    Tensor info = at::empty({pairs.size(0), kSimilarityInfoWords}, like(pairs, at::kLong));
+    similarity_refine_out(pairs, model, mask, err, thr, aggregation, rounds, model_out, mask_out, info);
+    return {model_out, mask_out, info};
+}
+
+std::tuple<Tensor, Tensor, Tensor> similarity_refine_meta(const Tensor& pairs, const Tensor&, const Tensor&, const Tensor&, double, int64_t,
+                                                          int64_t) {
+    TORCH_CHECK(pairs.dim() == 3, "sfm_hip: pairs must be [batch, n, 6]");
+    return {at::empty_symint({pairs.sym_size(0), c10::SymInt(kSimilarityModelWidth)}, like(pairs, at::kDouble)),
+            at::empty_symint({pairs.sym_size(0), pairs.sym_size(1)}, like(pairs, at::kByte)),
+            at::empty_symint({pairs.sym_size(0), c10::SymInt(kSimilarityInfoWords)}, like(pairs, at::kLong))};
+}
+
 // bundle adjustment, dense (sfm_bundle.hip) and with the iterative Schur solver (sfm_bundle_pcg.hip): poses [C, 12], points
 // [P, 3], camera / point indices int32 [M], pixels [M, 2]; fixed: the indices of the fixed cameras; the iterative solver takes
 // max_cg_iterations and cg_tolerance as well; info int64 [4] viewing the sfm_bundle_info record, int64 [5] viewing
@@ -1533,6 +1673,17 @@ TORCH_LIBRARY(sfm_hip, m) {
           "int aggregation, int refine_rounds, int refine_max_steps, Tensor(a!) S, Tensor(b!) model, Tensor(c!) flags, Tensor(d!) cnt, "
           "Tensor(e!) s1, Tensor(f!) s2, Tensor(g!) result, Tensor(h!) mask, Tensor(i!) pose_out, Tensor(j!) mask_out, "
           "Tensor(k!) info, Tensor(l!) status) -> ()");
+    m.def("similarity_ransac_pass(Tensor pairs, int seed, int seed_stride, int h_begin, int h, float thr, float min_extra, "
+          "int aggregation) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
+    m.def("similarity_ransac_pass_(Tensor pairs, int seed, int seed_stride, bool use_philox, int h_begin, float thr, float min_extra, "
+          "int aggregation, Tensor(a!) S, Tensor(b!) model, Tensor(c!) flags, Tensor(d!) cnt, Tensor(e!) s1, Tensor(f!) s2, "
+          "Tensor(g!) result, Tensor(h!)? mask) -> ()");
+    m.def("similarity_fit(Tensor pairs, Tensor? mask) -> (Tensor, Tensor)");
+    m.def("similarity_fit_(Tensor pairs, Tensor? mask, Tensor(a!) model_out, Tensor(b!) flags_out) -> ()");
+    m.def("similarity_refine(Tensor pairs, Tensor model, Tensor mask, Tensor err, float thr, int aggregation, int rounds) -> "
+          "(Tensor, Tensor, Tensor)");
+    m.def("similarity_refine_(Tensor pairs, Tensor model, Tensor mask, Tensor err, float thr, int aggregation, int rounds, "
+          "Tensor(a!) model_out, Tensor(b!) mask_out, Tensor(c!) info) -> ()");
     m.def("bundle_adjust(Tensor poses, Tensor points, Tensor camera_indices, Tensor point_indices, Tensor pixels, float[] K, "
           "int[] fixed, int max_steps) -> (Tensor, Tensor, Tensor)");
     m.def("bundle_adjust_(Tensor(a!) poses, Tensor(b!) points, Tensor camera_indices, Tensor point_indices, Tensor pixels, "
@@ -1614,6 +1765,12 @@ TORCH_LIBRARY_IMPL(sfm_hip, CUDA, m) {
     m.impl("pnp_refine_", &pnp_refine_out);
     m.impl("register_views", &register_views);
     m.impl("register_views_", &register_views_out);
+    m.impl("similarity_ransac_pass", &similarity_ransac_pass);
+    m.impl("similarity_ransac_pass_", &similarity_ransac_pass_out);
+    m.impl("similarity_fit", &similarity_fit);
+    m.impl("similarity_fit_", &similarity_fit_out);
+    m.impl("similarity_refine", &similarity_refine);
+    m.impl("similarity_refine_", &similarity_refine_out);
     m.impl("bundle_adjust", &bundle_adjust);
     m.impl("bundle_adjust_", &bundle_adjust_inplace);
     m.impl("bundle_adjust_pcg", &bundle_adjust_pcg);
@@ -1663,6 +1820,9 @@ void pnp_refine_out_meta(const Tensor&, const Tensor&, const Tensor&, const Tens
 void register_views_out_meta(const Tensor&, const Tensor&, const Tensor&, at::ArrayRef<double>, int64_t, int64_t, int64_t, double, int64_t,
                              int64_t, int64_t, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&,
                              Tensor&, Tensor&) {}
+void similarity_fit_out_meta(const Tensor&, const std::optional<Tensor>&, Tensor&, Tensor&) {}
+void similarity_refine_out_meta(const Tensor&, const Tensor&, const Tensor&, const Tensor&, double, int64_t, int64_t, Tensor&, Tensor&,
+                                Tensor&) {}
 void bundle_adjust_out_meta(Tensor&, Tensor&, const Tensor&, const Tensor&, const Tensor&, at::ArrayRef<double>, at::ArrayRef<int64_t>,
                             int64_t, Tensor&) {}
 void bundle_adjust_pcg_out_meta(Tensor&, Tensor&, const Tensor&, const Tensor&, const Tensor&, at::ArrayRef<double>,
@@ -1716,6 +1876,12 @@ TORCH_LIBRARY_IMPL(sfm_hip, Meta, m) {
     m.impl("pnp_refine_", &pnp_refine_out_meta);
     m.impl("register_views", &register_views_meta);
     m.impl("register_views_", &register_views_out_meta);
+    m.impl("similarity_ransac_pass", &similarity_ransac_pass_meta);
+    m.impl("similarity_ransac_pass_", &five_point_ransac_pass_out_meta);
+    m.impl("similarity_fit", &similarity_fit_meta);
+    m.impl("similarity_fit_", &similarity_fit_out_meta);
+    m.impl("similarity_refine", &similarity_refine_meta);
+    m.impl("similarity_refine_", &similarity_refine_out_meta);
     m.impl("bundle_adjust", &bundle_adjust_meta);
     m.impl("bundle_adjust_", &bundle_adjust_out_meta);
     m.impl("bundle_adjust_pcg", &bundle_adjust_pcg_meta);

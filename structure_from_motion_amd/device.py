@@ -1275,6 +1275,88 @@ class HomographyWorkspace(_PassWorkspace):
 
 
 # ------------------------------------------------------------------------------------------------------
+# RANSAC similarity alignment of two reconstructions (csrc/sfm_similarity.hip): pairs [B,N,6] =
+# {ax, ay, az, bx, by, bz}, S [B,H,8] (first 3 entries used), model [B,H,13] = R (row-major) | t | s with b ~ s R a + t
+# ------------------------------------------------------------------------------------------------------
+SIMILARITY_SAMPLE, SIMILARITY_MODEL = 3, 13
+
+
+def model_similarity(row: np.ndarray) -> Tuple[float, np.ndarray, np.ndarray]:
+    """A 13-entry model row R (9) | t (3) | s as (s, fresh (3,3), fresh (3,))."""
+    return float(row[12]), row[:9].reshape(3, 3).copy(), row[9:12].copy()
+
+
+def fit_similarity(pairs: torch.Tensor, mask: Optional[torch.Tensor] = None, out=None):
+    """The least-squares model of the items with a non-zero mask (``mask=None``: of all items), one per entry
+    (``sfm_similarity_fit_masked``).  pairs [B,N,6], mask uint8 [B,N] -> (model [B,13], flags int32 [B], SFM_FIT_DEGENERATE
+    where the set does not determine a model).  ``out=(model, flags)``: the caller's buffers.  No host synchronisation."""
+    if out is None:
+        return ops.load().similarity_fit(pairs, mask)
+    ops.load().similarity_fit_(pairs, mask, out[0], out[1])
+    return out
+
+
+def similarity_refine(pairs, model, mask, err, thr: float, aggregation: int, rounds: int = 2, out=None):
+    """Closed-form refit of one model per entry on its inliers, re-scored and kept only if better (``sfm_similarity_refine``).
+    pairs [B,N,6], model f64 [B,13], mask uint8 [B,N] (non-zero = inlier), err f64 [B] (the aggregated error of ``model``) ->
+    (model_out [B,13], mask_out uint8 [B,N] (1 = inlier), info int64 [B,3] viewing sfm_similarity_refine_info records;
+    ``read_similarity_refine_info``).  ``out``: the caller's three buffers.  No host synchronisation."""
+    if out is None:
+        return ops.load().similarity_refine(pairs, model.contiguous(), mask.contiguous(), err.contiguous(), float(thr),
+                                            int(aggregation), int(rounds))
+    ops.load().similarity_refine_(pairs, model.contiguous(), mask.contiguous(), err.contiguous(), float(thr), int(aggregation),
+                                  int(rounds), out[0], out[1], out[2])
+    return out
+
+
+@dataclass
+class SimilarityRefineInfo:
+    error: float      # aggregated error of the model left in model_out, over its `count` inliers
+    count: int        # inliers of that model
+    accepted: int     # rounds whose result was kept (0: model_out is the input model)
+    rounds_run: int   # rounds that fitted a model (entered with at least three inliers)
+
+
+def read_similarity_refine_info(info: torch.Tensor) -> List[SimilarityRefineInfo]:
+    """Host copy of sfm_similarity_refine_info records (int64 [B,3]) (synchronises)."""
+    return [SimilarityRefineInfo(*fields) for fields in _read_records(info, 1, 3)]
+
+
+class SimilarityWorkspace(_PassWorkspace):
+    """Pre-allocated device buffers of a similarity pass for B entries x H hypotheses x N 3-D / 3-D pairs (as RansacWorkspace),
+    and those of the refinement behind it."""
+
+    def __init__(self, batch: int, n: int, h: int, device=None):
+        super().__init__(batch, n, h, SIMILARITY_MODEL, SIMILARITY_SAMPLE, device)
+        dev = self.S.device
+        self.model_out = torch.empty((batch, SIMILARITY_MODEL), dtype=F64, device=dev)
+        self.mask_out = torch.empty((batch, n), dtype=torch.uint8, device=dev)
+        self.info = torch.empty((batch, 3), dtype=torch.int64, device=dev)
+
+    def buffers(self):
+        """Every output buffer, in the order a test names them."""
+        return (self.S, self.model, self.flags, self.cnt, self.s1, self.s2, self.result, self.mask, self.model_out, self.mask_out,
+                self.info)
+
+    def run(self, pairs: torch.Tensor, thr: float, min_extra: float, aggregation: int, with_mask: bool = True, philox=None) -> None:
+        """fit + score + select (+ mask) in one call (``sfm_similarity_ransac_pass``) for the sample table in ``self.S`` — or,
+        with ``philox=(seed, h_begin, seed_stride)``, for Philox samples drawn inside the fit launch (which also fills ``self.S``)."""
+        seed, h_begin, stride = (0, 0, 1) if philox is None else philox
+        ops.load().similarity_ransac_pass_(pairs, _as_int64(seed), _as_int64(stride), philox is not None, h_begin, float(thr),
+                                           float(min_extra), int(aggregation), self.S, self.model, self.flags, self.cnt, self.s1,
+                                           self.s2, self.result, self.mask if with_mask else None)
+
+    def refine(self, pairs: torch.Tensor, thr: float, aggregation: int, rounds: int = 2):
+        """``similarity_refine`` of every entry's winner, chained on this pass's buffers: model[b, best_h] (row 0 when an entry
+        has no winner: its mask is all zero and it keeps that row), the pass's mask and the record's best_err.  Stream-ordered
+        after ``run``: no host round trip.  -> (model_out [B,13], mask_out [B,N], info [B,3]), this workspace's buffers."""
+        rows = torch.arange(self.batch, device=self.result.device)
+        model = self.model[rows, self.result[:, 1].clamp(min=0)]
+        err = self.result[:, 2].contiguous().view(F64)
+        return similarity_refine(pairs, model, self.mask, err, thr, aggregation, rounds, out=(self.model_out, self.mask_out, self.info))
+
+
+# ------------------------------------------------------------------------------------------------------
 # Two-view verification of every pair of a match graph in one call (csrc/sfm_view_graph.hip, DESIGN.md §6q): corr [N,4], the
 # pairs' K-normalised correspondences concatenated; offset int64 [Q+1]; per pair the homography pass and the five-point pass
 # ------------------------------------------------------------------------------------------------------
