@@ -11,6 +11,15 @@ baselines, the alignment RMS, and the per-view pose errors of the merged model a
 first view, in units of A's true seed baseline) before and after the final adjustment, next to those of the two halves on their
 own.  ``--corrupt FRACTION`` displaces that share of B's common points before the alignment and prints the plain least-squares
 ``fit_similarity`` over all pairs next to the RANSAC result: what the robust estimate buys.
+
+``--parts K`` with K > 2 reconstructs K overlapping view ranges along the arc instead, aligns every pair of parts that share at
+least 30 standing tracks in ONE ``align_models`` call, puts the parts into the frame of the first with
+``merge_frames`` and runs one final adjustment over the union (the iterative solver above 64 cameras, as
+``apps/sfm_multi_view.py`` chooses it).  Each pair's threshold is ``--align-threshold`` in the unit of its side B, that part's own
+seed baseline, and ``--corrupt`` displaces that share of every pair's side-A points.  Printed then: per pair the common tracks,
+the inliers, the displaced points among them and the scale error against the ratio of the two true seed baselines; the
+disagreement of every pair with the frames (the loops); the worst pose error of the merged model before and after the
+adjustment, next to each part's own.
 """
 from __future__ import annotations
 
@@ -30,10 +39,13 @@ from lib.common.feature import Feature   # noqa: E402
 from lib.epipolar.eight_point import create_trivial_matches, recover_r_t_from_e   # noqa: E402
 from lib.epipolar.epipolar_ransac import estimate_essential_mat_with_ransac   # noqa: E402
 from lib.feature_matching.matching import Match   # noqa: E402
-from lib.multiview.alignment import (apply_similarity, estimate_similarity_with_ransac, fit_similarity,   # noqa: E402
-                                     transform_poses)
+from lib.multiview.alignment import (align_models, apply_similarity, estimate_similarity_with_ransac,   # noqa: E402
+                                     fit_similarity, inconsistent_alignments, merge_frames, transform_poses)
 from lib.pnp.pnp import estimate_pose_pnp_with_ransac   # noqa: E402
 from structure_from_motion_amd import device, synthetic   # noqa: E402
+
+MIN_COMMON_TRACKS = 30   # a pair of parts is aligned when it shares at least this many standing tracks
+DENSE_MAX_VIEWS = 64     # the dense bundle adjuster's camera limit (apps/sfm_multi_view.py)
 
 
 def sub_scene(scene, first: int, last: int) -> dict:
@@ -115,9 +127,14 @@ def summary(errors: dict) -> dict:
 def run(views: int = 12, overlap: int = 4, points: int = 2000, seed: int = 21, noise_px: float = 0.5, outlier_fraction: float = 0.2,
         corrupt: float = 0.0, align_threshold: float = 0.05, align_iterations: int = 1000, sed_threshold: float = 6e-6,
         reprojection_threshold: float = 16.0, iterations: int = 2000, refine_steps: int = 10, ba_steps: int = 20,
-        final_ba_steps: int = 50, step_deg: float = 5.0) -> dict:
+        final_ba_steps: int = 50, step_deg: float = 5.0, parts: int = 2) -> dict:
     if not 0.0 <= corrupt < 1.0:
         raise ValueError(f"corrupt must be a fraction in [0, 1), got {corrupt!r}")
+    if isinstance(parts, bool) or not isinstance(parts, (int, np.integer)) or parts < 2:
+        raise ValueError(f"parts must be an integer >= 2, got {parts!r}")
+    if parts > 2:
+        return run_parts(parts, views, overlap, points, seed, noise_px, outlier_fraction, corrupt, align_threshold, align_iterations,
+                         (sed_threshold, reprojection_threshold, iterations, refine_steps, ba_steps, final_ba_steps), step_deg)
     if not (4 <= views <= 64 and 2 <= overlap <= views - 2 and (views + overlap) // 2 >= 3):
         raise ValueError(f"need 4 <= views <= 64 and 2 <= overlap <= views - 2, got views={views}, overlap={overlap}")
     if not (np.isfinite(align_threshold) and align_threshold > 0.0):
@@ -207,6 +224,109 @@ def run(views: int = 12, overlap: int = 4, points: int = 2000, seed: int = 21, n
     }
 
 
+def part_ranges(views: int, overlap: int, parts: int):
+    """K view ranges [first, last) of equal length along the arc, consecutive ones sharing `overlap` views, the last ending at
+    the last view."""
+    length = -(-(views + (parts - 1) * overlap) // parts)
+    firsts = [min(k * (length - overlap), views - length) for k in range(parts)]
+    return [(first, first + length) for first in firsts]
+
+
+def run_parts(parts: int, views: int, overlap: int, points: int, seed: int, noise_px: float, outlier_fraction: float, corrupt: float,
+              align_threshold: float, align_iterations: int, options, step_deg: float) -> dict:
+    if not (np.isfinite(align_threshold) and align_threshold > 0.0):
+        raise ValueError(f"align_threshold must be a positive length in a part's units, got {align_threshold!r}")
+    if overlap < 2 or views < parts * 3:
+        raise ValueError(f"need overlap >= 2 and at least {parts * 3} views for {parts} parts, got views={views}, overlap={overlap}")
+    ranges = part_ranges(views, overlap, parts)
+    length = ranges[0][1] - ranges[0][0]
+    if not (overlap + 1 <= length <= DENSE_MAX_VIEWS) or any(a[0] >= b[0] for a, b in zip(ranges, ranges[1:])):
+        raise ValueError(f"{parts} parts of {views} views with {overlap} in common are ranges of {length} views: need "
+                         f"{overlap + 1} to {DENSE_MAX_VIEWS}, each starting behind the one before")
+    scene = synthetic.multi_view_scene(views, points, seed, noise_px, outlier_fraction, step_deg=step_deg)
+    random.seed(seed)
+    recs = [reconstruct(sub_scene(scene, first, last), *options) for first, last in ranges]
+    truth = scene["poses_true"]
+    units = [baseline(truth, first, first + 1) for first, _ in ranges]
+    total = int(scene["point_indices"].max()) + 1
+    standing = [np.nonzero(rec.status == device.TRACKS_OK)[0] for rec in recs]
+
+    # every pair of parts that shares enough standing tracks; side A of pair q is a copy of part i's common points, so that
+    # --corrupt can displace a share of them pair by pair: model parts + q of the call
+    clouds, ids = [rec.X[ok] for rec, ok in zip(recs, standing)], list(standing)
+    pairs, displaced = [], []
+    rng = np.random.default_rng(seed + 1)
+    for i in range(parts):
+        for j in range(i + 1, parts):
+            common = np.intersect1d(standing[i], standing[j])
+            if len(common) < MIN_COMMON_TRACKS:
+                continue
+            side_a = recs[i].X[common].copy()
+            moved = np.sort(rng.permutation(len(common))[:int(round(corrupt * len(common)))])
+            extent = float(np.max(np.abs(side_a - np.median(side_a, axis=0))))
+            side_a[moved] += rng.uniform(-1.0, 1.0, size=(len(moved), 3)) * extent
+            clouds.append(side_a), ids.append(common), displaced.append(common[moved])
+            pairs.append((i, j))
+    if not pairs:
+        raise ValueError(f"no two parts share {MIN_COMMON_TRACKS} standing tracks")
+    call_pairs = np.array([[parts + q, j] for q, (_, j) in enumerate(pairs)])
+    found = align_models(clouds, ids, call_pairs, align_threshold ** 2, iterations=align_iterations, min_num_extra_inliers=3,
+                         min_extra_fraction=0.25, seed=seed)
+    pair_arr = np.array(pairs)
+    frames = merge_frames(parts, pair_arr, found, root=0, min_inliers=MIN_COMMON_TRACKS // 2)
+    per_pair = []
+    for q, (i, j) in enumerate(pairs):
+        ratio = units[i] / units[j]   # part i's unit in part j's
+        per_pair.append({
+            "parts": [i, j], "status": found.status[q], "common_tracks": int(found.common_count[q]),
+            "inliers": int(found.inlier_count[q]), "corrupted": int(len(displaced[q])),
+            "corrupted_among_inliers": int(np.count_nonzero(np.isin(found.inliers[q], displaced[q]))),
+            "scale": float(found.scale[q]), "true_baseline_ratio": ratio, "scale_error": abs(float(found.scale[q]) / ratio - 1.0),
+            "in_tree": bool(q in frames.tree_pairs.tolist()),
+            "disagreement": {"rotation_deg": float(frames.rotation_deg[q]), "log_scale": float(frames.log_scale[q]),
+                             "distance": float(frames.distance[q])}})
+
+    # the union in the frame of part 0: a view or a track that stands in several parts keeps the earliest part's
+    poses, X = np.full((views, 12), np.nan), np.full((total, 3), np.nan)
+    for k in reversed(range(parts)):
+        if not frames.reached[k]:
+            continue
+        G = frames.frame(k)
+        moved = transform_poses(G, recs[k].poses)
+        poses[ranges[k][0] + np.array(recs[k].registered)] = moved[recs[k].registered]
+        X[standing[k]] = apply_similarity(G, recs[k].X[standing[k]])
+    registered = np.nonzero(~np.isnan(poses).any(axis=1))[0]
+    truth_0 = true_poses_in_gauge(truth, 0, units[0])
+    before = pose_errors(poses, truth_0, registered)
+    cam, pt, uv = scene["camera_indices"], scene["point_indices"], scene["pixels"]
+    kept = np.nonzero(~np.isnan(X).any(axis=1))[0]
+    cam_slot, pt_slot = np.full(views, -1), np.full(total, -1)
+    cam_slot[registered] = np.arange(len(registered))
+    pt_slot[kept] = np.arange(len(kept))
+    use = np.nonzero((cam_slot[cam] >= 0) & (pt_slot[pt] >= 0))[0]
+    use = use[_errors(scene["K"], poses, X, cam[use], pt[use], uv[use]) <= options[1]]
+    solver = "iterative" if len(registered) > DENSE_MAX_VIEWS else "dense"
+    adjusted, _, info = bundle_adjust(scene["K"], poses[registered], X[kept], cam_slot[cam[use]], pt_slot[pt[use]], uv[use],
+                                      fixed_cameras=(0,), max_steps=options[5], linear_solver=solver)
+    after_poses = poses.copy()
+    after_poses[registered] = adjusted
+    after = pose_errors(after_poses, truth_0, registered)
+    own = [summary(pose_errors(rec.poses, true_poses_in_gauge(truth, first, unit)[first:], rec.registered))
+           for rec, (first, _), unit in zip(recs, ranges, units)]
+    return {
+        "views": views, "parts": parts, "ranges": [list(r) for r in ranges],
+        "views_registered": {"parts": [len(rec.registered) for rec in recs], "merged": int(len(registered))},
+        "parts_merged": int(np.count_nonzero(frames.reached)), "pairs": per_pair,
+        "tree_pairs": [int(q) for q in frames.tree_pairs], "corrupt": corrupt,
+        "inconsistent_pairs": [int(q) for q in inconsistent_alignments(frames, 1.0, 0.02)],
+        "parts_own": own,
+        "merged_before_adjustment": {"worst": summary(before)},
+        "merged_after_adjustment": {"worst": summary(after), "ba_status": info.status, "ba_solver": solver,
+                                    "ba_observations": int(len(use)),
+                                    "rms_px": float(np.sqrt(info.final_cost / len(use))) if len(use) else float("nan")},
+    }
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--views", type=int, default=12, help="views of the scene (4 to 64)")
@@ -220,10 +340,12 @@ def main():
     ap.add_argument("--align-threshold", type=float, default=0.05,
                     help="inlier distance of the alignment, in units of A's seed baseline")
     ap.add_argument("--align-iterations", type=int, default=1000, help="RANSAC hypotheses of the alignment")
+    ap.add_argument("--parts", type=int, default=2, metavar="K",
+                    help="reconstruct K overlapping view ranges and align every pair of them in one call (default 2: two halves)")
     args = ap.parse_args()
     try:
         out = run(args.views, args.overlap, args.points, args.seed, args.noise, args.outliers, corrupt=args.corrupt,
-                  align_threshold=args.align_threshold, align_iterations=args.align_iterations)
+                  align_threshold=args.align_threshold, align_iterations=args.align_iterations, parts=args.parts)
     except ValueError as e:
         ap.error(str(e))
     print(json.dumps(out))

@@ -659,6 +659,48 @@ int sfm_similarity_refine(const double* pairs, int64_t n, int64_t batch, const d
                           const double* err_in, double thr, int aggregation, int rounds, double* model_out, uint8_t* mask_out,
                           sfm_similarity_refine_info* info, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- similarity alignment of every overlapping pair of sub-models in one call (csrc/sfm_align_models.hip; an
+ * extension, added under ABI 15) ----
+ * pairs: dev [n_total,6] = {ax, ay, az, bx, by, bz} as sfm_similarity_ransac_pass takes them, the items of all sub-model pairs,
+ * concatenated, 16-byte aligned; offset: dev int64 [pair_count+1], pair q owns items offset[q] .. offset[q+1]-1 (n_q of them, any
+ * count, 0 included); max_items: host, an upper bound on every n_q (it sizes the grid of the reduction passes: the host never
+ * reads the table); thr: dev double [pair_count], squared distance in the units of side B of pair q; min_extra: dev double
+ * [pair_count], the gate of pair q.  Pair q's outputs are those of sfm_similarity_ransac_pass(seed + q * seed_stride, seed_stride,
+ * use_philox = 1, h_begin, its items, n_q, h_count, 1, thr[q], min_extra[q], aggregation, ...) with a mask, followed by
+ * sfm_similarity_refine(its items, n_q, 1, model[q, best_h], that mask, the record's best_err, thr[q], aggregation, refine_rounds,
+ * ...), bit for bit:
+ *   S int32 [pair_count,h_count,8]; model [pair_count,h_count,13]; flags, cnt int32 and s1, s2 double [pair_count,h_count]; result
+ *   [pair_count] (best_h local to the pair); mask uint8 [n_total] (2 sample item of the winner, 1 other inlier, 0 otherwise);
+ *   model_out [pair_count,13]; mask_out uint8 [n_total] (1 = inlier of model_out), must not alias mask; info [pair_count]; status
+ *   int32 [pair_count].
+ * refine_rounds = 0 means what it means for sfm_similarity_refine: model_out is the winner, mask_out is mask != 0.  Every element
+ * of every output is written; a mask byte that no pair owns is 0.  A pair without a winner has model_out = 13 NaNs, its mask and
+ * mask_out bytes 0 and info {+inf, 0, 0, 0, 0} (not the single call's "row 0 with an empty mask"); a pair with n_q < 3 also gets
+ * the pass's filler: rows of S all -1, models of 13 NaNs, flags SFM_FIT_DEGENERATE, cnt 0, s1 = s2 = NaN, hence a record without a
+ * winner (n_flagged = h_count).
+ * The offset table is checked on the device by the first launch: unless 0 <= offset[0] <= ... <= offset[pair_count] <= n_total
+ * and every n_q <= max_items, every pair is treated as empty (filler throughout, masks 0) and every status is
+ * SFM_ALIGN_BAD_OFFSETS; that is a status, not an error return, and nothing is read through such a table.
+ * workspace: dev, 16-byte aligned, at least sfm_align_models_workspace_bytes(n_total, pair_count, max_items).
+ * 7 + 4 refine_rounds launches whatever pair_count is, nothing read back; every size and pointer is checked before the first
+ * launch (pair_count <= 65535, n_total < 2^31, 0 <= max_items <= n_total, h_count >= 1, h_begin >= 0, refine_rounds >= 0, the
+ * aggregation, alignment, the workspace); pair_count == 0 is a no-op that writes nothing.  No atomics: a call is reproducible bit
+ * for bit. */
+#define SFM_ALIGN_OK 0          /* the pair has a winner: model_out is that winner, refitted where a round was kept */
+#define SFM_ALIGN_NO_MODEL 1    /* n_q >= 3, but no hypothesis passed the gate */
+#define SFM_ALIGN_TOO_FEW 2     /* n_q < 3 */
+#define SFM_ALIGN_BAD_OFFSETS 3 /* the offset table of the call was refused: every pair */
+
+/* Bytes of workspace sfm_align_models needs; -1 for sizes it refuses (n_total < 0 or >= 2^31, pair_count < 0 or > 65535,
+ * max_items < 0 or > n_total). */
+int64_t sfm_align_models_workspace_bytes(int64_t n_total, int64_t pair_count, int64_t max_items);
+
+int sfm_align_models(uint64_t seed, uint64_t seed_stride, int64_t h_begin, const double* pairs, int64_t n_total,
+                     const int64_t* offset, int64_t pair_count, int64_t max_items, const double* thr, const double* min_extra,
+                     int64_t h_count, int aggregation, int refine_rounds, int32_t* S, double* model, int32_t* flags, int32_t* cnt,
+                     double* s1, double* s2, sfm_select_result* result, uint8_t* mask, double* model_out, uint8_t* mask_out,
+                     sfm_similarity_refine_info* info, int32_t* status, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- bundle adjustment of cameras and points (csrc/sfm_bundle.hip; an extension, off unless asked for) ----
  * These symbols were added under ABI 14 without a version change: they are new, and nothing an ABI-14 caller uses changed. */
 

@@ -12,7 +12,8 @@
 // homography_ransac_pass_ (sfm_homography.hip), the ragged two-view pass verify_pairs_ (sfm_view_graph.hip) and the poses
 // behind it pair_poses (sfm_view_graph_pose.hip) with their refinement refine_pair_poses (sfm_view_graph_refine.hip), and
 // the refinement of a winner pnp_refine (sfm_pnp_refine.hip), the ragged absolute-pose call register_views (sfm_register_views.hip),
-// the similarity alignment similarity_ransac_pass, similarity_fit and similarity_refine (sfm_similarity.hip),
+// the similarity alignment similarity_ransac_pass, similarity_fit and similarity_refine (sfm_similarity.hip), the ragged
+// alignment of every pair of sub-models align_models (sfm_align_models.hip),
 // bundle_adjust (sfm_bundle.hip, sfm_bundle_pcg.hip), triangulate_tracks (sfm_tracks.hip), build_tracks
 // (sfm_track_build.hip), average_rotations (sfm_rotation_averaging.hip) and average_translations
 // (sfm_translation_averaging.hip).  The reference call sites these serve: apps/sfm.py:110-119 (RANSAC-E), :133-138 (pose),
@@ -1043,6 +1044,91 @@ std::tuple<Tensor, Tensor, Tensor> similarity_refine_meta(const Tensor& pairs, c
             at::empty_symint({pairs.sym_size(0), c10::SymInt(kSimilarityInfoWords)}, like(pairs, at::kLong))};
 }
 
+// ---- similarity alignment of every pair of sub-models in one call (sfm_align_models.hip): pairs [n_total, 6], offset int64
+// [Q + 1], thr and min_extra double [Q]; S [Q, h, 8], model [Q, h, 13], the score tables [Q, h], result int64 [Q, 5], mask uint8
+// [n_total]; model_out [Q, 13], mask_out uint8 [n_total], info int64 [Q, 3] (sfm_similarity_refine_info), status int32 [Q].
+// max_items: an upper bound on every pair's item count.  The workspace comes from the caching allocator -------------------------
+void align_models_out(const Tensor& pairs, const Tensor& offset, const Tensor& thr, const Tensor& min_extra, int64_t max_items,
+                      int64_t seed, int64_t seed_stride, int64_t h_begin, int64_t aggregation, int64_t refine_rounds, Tensor& S,
+                      Tensor& model, Tensor& flags, Tensor& cnt, Tensor& s1, Tensor& s2, Tensor& result, Tensor& mask, Tensor& model_out,
+                      Tensor& mask_out, Tensor& info, Tensor& status) {
+    const OpDevice scope(pairs);
+    need(pairs, "pairs", at::kDouble);
+    need(offset, "offset", at::kLong);
+    need(thr, "thr", at::kDouble);
+    need(min_extra, "min_extra", at::kDouble);
+    need(S, "S", at::kInt);
+    need(model, "model", at::kDouble);
+    for (const Tensor* t : {&flags, &cnt, &status}) need(*t, "flags / cnt / status", at::kInt);
+    for (const Tensor* t : {&s1, &s2, &model_out}) need(*t, "s1 / s2 / model_out", at::kDouble);
+    for (const Tensor* t : {&result, &info}) need(*t, "result / info", at::kLong);
+    need(mask, "mask", at::kByte);
+    need(mask_out, "mask_out", at::kByte);
+    TORCH_CHECK(pairs.dim() == 2 && pairs.size(1) == 6, "sfm_hip: pairs must be [n_total, 6]");
+    TORCH_CHECK(offset.dim() == 1 && offset.size(0) >= 1, "sfm_hip: offset must be int64 [pairs + 1]");
+    const int64_t n_total = pairs.size(0), Q = offset.size(0) - 1;
+    TORCH_CHECK(S.dim() == 3 && S.size(0) == Q && S.size(2) == 8, "sfm_hip: S must be [pairs, h, 8]");
+    const int64_t h = S.size(1);
+    TORCH_CHECK(thr.numel() == Q && min_extra.numel() == Q, "sfm_hip: thr, min_extra must be [pairs]");
+    TORCH_CHECK(model.numel() == Q * h * kSimilarityModelWidth, "sfm_hip: model must be [pairs, h, 13]");
+    for (const Tensor* t : {&flags, &cnt, &s1, &s2}) TORCH_CHECK(t->numel() == Q * h, "sfm_hip: flags, cnt, s1, s2 must be [pairs, h]");
+    TORCH_CHECK(result.numel() == Q * kRecordWords, "sfm_hip: result must be int64 [pairs, 5]");
+    TORCH_CHECK(mask.numel() == n_total && mask_out.numel() == n_total, "sfm_hip: mask, mask_out must be uint8 [n_total]");
+    TORCH_CHECK(model_out.numel() == Q * kSimilarityModelWidth, "sfm_hip: model_out must be [pairs, 13]");
+    TORCH_CHECK(info.numel() == Q * kSimilarityInfoWords, "sfm_hip: info must be int64 [pairs, 3]");
+    TORCH_CHECK(status.numel() == Q, "sfm_hip: status must be int32 [pairs]");
+    TORCH_CHECK(refine_rounds >= 0 && refine_rounds <= 0x7FFFFFFF, "sfm_hip: refine_rounds must be in [0, 2^31)");
+    const int64_t bytes = sfm_align_models_workspace_bytes(n_total, Q, max_items);
+    TORCH_CHECK(bytes >= 0, "sfm_hip: sfm_align_models refuses these sizes (need n_total < 2^31, pairs <= 65535 and 0 <= max_items <= "
+                            "n_total)");
+    Tensor ws = at::empty({bytes > 16 ? bytes : 16}, like(pairs, at::kByte));
+    ok(sfm_align_models((uint64_t)seed, (uint64_t)seed_stride, h_begin, ptr<double>(pairs), n_total, ptr<int64_t>(offset), Q, max_items,
+                        ptr<double>(thr), ptr<double>(min_extra), h, (int)aggregation, (int)refine_rounds, ptr<int32_t>(S),
+                        ptr<double>(model), ptr<int32_t>(flags), ptr<int32_t>(cnt), ptr<double>(s1), ptr<double>(s2),
+                        reinterpret_cast<sfm_select_result*>(ptr<int64_t>(result)), ptr<uint8_t>(mask), ptr<double>(model_out),
+                        ptr<uint8_t>(mask_out), reinterpret_cast<sfm_similarity_refine_info*>(ptr<int64_t>(info)), ptr<int32_t>(status),
+                        ws.data_ptr(), ws.numel(), current_stream()),
+       "sfm_align_models");
+}
+
+// the functional form: h hypotheses per pair -> (model_out, mask_out, info, status, mask, result); the tables of the pass are
+// temporaries of the call
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> align_models(const Tensor& pairs, const Tensor& offset, const Tensor& thr,
+                                                                        const Tensor& min_extra, int64_t max_items, int64_t seed,
+                                                                        int64_t seed_stride, int64_t h_begin, int64_t h,
+                                                                        int64_t aggregation, int64_t refine_rounds) {
+    TORCH_CHECK(pairs.dim() == 2 && offset.dim() == 1 && offset.size(0) >= 1, "sfm_hip: pairs must be [n_total, 6], offset int64 [pairs + 1]");
+    TORCH_CHECK(h >= 1, "sfm_hip: align_models needs at least one hypothesis per pair");
+    const int64_t n_total = pairs.size(0), Q = offset.size(0) - 1;
+    Tensor S = at::empty({Q, h, 8}, like(pairs, at::kInt)), model = at::empty({Q, h, kSimilarityModelWidth}, like(pairs, at::kDouble));
+    Tensor flags = at::empty({Q, h}, like(pairs, at::kInt)), cnt = at::empty({Q, h}, like(pairs, at::kInt));
+    Tensor s1 = at::empty({Q, h}, like(pairs, at::kDouble)), s2 = at::empty({Q, h}, like(pairs, at::kDouble));
+    Tensor result = at::empty({Q, kRecordWords}, like(pairs, at::kLong));
+    Tensor mask = at::empty({n_total}, like(pairs, at::kByte)), mask_out = at::empty({n_total}, like(pairs, at::kByte));
+    Tensor model_out = at::empty({Q, kSimilarityModelWidth}, like(pairs, at::kDouble));
+    Tensor info = at::empty({Q, kSimilarityInfoWords}, like(pairs, at::kLong));
+    Tensor status = at::empty({Q}, like(pairs, at::kInt));
+    if (Q == 0) {   // the entry is a no-op then: no item has a pair
+        mask.zero_();
+        mask_out.zero_();
+    }
+    align_models_out(pairs, offset, thr, min_extra, max_items, seed, seed_stride, h_begin, aggregation, refine_rounds, S, model, flags, cnt,
+                     s1, s2, result, mask, model_out, mask_out, info, status);
+    return {model_out, mask_out, info, status, mask, result};
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> align_models_meta(const Tensor& pairs, const Tensor& offset, const Tensor&,
+                                                                             const Tensor&, int64_t, int64_t, int64_t, int64_t, int64_t,
+                                                                             int64_t, int64_t) {
+    TORCH_CHECK(pairs.dim() == 2 && offset.dim() == 1, "sfm_hip: pairs must be [n_total, 6], offset int64 [pairs + 1]");
+    const c10::SymInt Q = offset.sym_size(0) - 1;
+    return {at::empty_symint({Q, c10::SymInt(kSimilarityModelWidth)}, like(pairs, at::kDouble)),
+            at::empty_symint({pairs.sym_size(0)}, like(pairs, at::kByte)),
+            at::empty_symint({Q, c10::SymInt(kSimilarityInfoWords)}, like(pairs, at::kLong)), at::empty_symint({Q}, like(pairs, at::kInt)),
+            at::empty_symint({pairs.sym_size(0)}, like(pairs, at::kByte)),
+            at::empty_symint({Q, c10::SymInt(kRecordWords)}, like(pairs, at::kLong))};
+}
+
 // bundle adjustment, dense (sfm_bundle.hip) and with the iterative Schur solver (sfm_bundle_pcg.hip): poses [C, 12], points
 // [P, 3], camera / point indices int32 [M], pixels [M, 2]; fixed: the indices of the fixed cameras; the iterative solver takes
 // max_cg_iterations and cg_tolerance as well; info int64 [4] viewing the sfm_bundle_info record, int64 [5] viewing
@@ -1684,6 +1770,12 @@ TORCH_LIBRARY(sfm_hip, m) {
           "(Tensor, Tensor, Tensor)");
     m.def("similarity_refine_(Tensor pairs, Tensor model, Tensor mask, Tensor err, float thr, int aggregation, int rounds, "
           "Tensor(a!) model_out, Tensor(b!) mask_out, Tensor(c!) info) -> ()");
+    m.def("align_models(Tensor pairs, Tensor offset, Tensor thr, Tensor min_extra, int max_items, int seed, int seed_stride, "
+          "int h_begin, int h, int aggregation, int refine_rounds) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
+    m.def("align_models_(Tensor pairs, Tensor offset, Tensor thr, Tensor min_extra, int max_items, int seed, int seed_stride, "
+          "int h_begin, int aggregation, int refine_rounds, Tensor(a!) S, Tensor(b!) model, Tensor(c!) flags, Tensor(d!) cnt, "
+          "Tensor(e!) s1, Tensor(f!) s2, Tensor(g!) result, Tensor(h!) mask, Tensor(i!) model_out, Tensor(j!) mask_out, "
+          "Tensor(k!) info, Tensor(l!) status) -> ()");
     m.def("bundle_adjust(Tensor poses, Tensor points, Tensor camera_indices, Tensor point_indices, Tensor pixels, float[] K, "
           "int[] fixed, int max_steps) -> (Tensor, Tensor, Tensor)");
     m.def("bundle_adjust_(Tensor(a!) poses, Tensor(b!) points, Tensor camera_indices, Tensor point_indices, Tensor pixels, "
@@ -1771,6 +1863,8 @@ TORCH_LIBRARY_IMPL(sfm_hip, CUDA, m) {
     m.impl("similarity_fit_", &similarity_fit_out);
     m.impl("similarity_refine", &similarity_refine);
     m.impl("similarity_refine_", &similarity_refine_out);
+    m.impl("align_models", &align_models);
+    m.impl("align_models_", &align_models_out);
     m.impl("bundle_adjust", &bundle_adjust);
     m.impl("bundle_adjust_", &bundle_adjust_inplace);
     m.impl("bundle_adjust_pcg", &bundle_adjust_pcg);
@@ -1820,6 +1914,9 @@ void pnp_refine_out_meta(const Tensor&, const Tensor&, const Tensor&, const Tens
 void register_views_out_meta(const Tensor&, const Tensor&, const Tensor&, at::ArrayRef<double>, int64_t, int64_t, int64_t, double, int64_t,
                              int64_t, int64_t, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&,
                              Tensor&, Tensor&) {}
+void align_models_out_meta(const Tensor&, const Tensor&, const Tensor&, const Tensor&, int64_t, int64_t, int64_t, int64_t, int64_t,
+                           int64_t, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&,
+                           Tensor&) {}
 void similarity_fit_out_meta(const Tensor&, const std::optional<Tensor>&, Tensor&, Tensor&) {}
 void similarity_refine_out_meta(const Tensor&, const Tensor&, const Tensor&, const Tensor&, double, int64_t, int64_t, Tensor&, Tensor&,
                                 Tensor&) {}
@@ -1882,6 +1979,8 @@ TORCH_LIBRARY_IMPL(sfm_hip, Meta, m) {
     m.impl("similarity_fit_", &similarity_fit_out_meta);
     m.impl("similarity_refine", &similarity_refine_meta);
     m.impl("similarity_refine_", &similarity_refine_out_meta);
+    m.impl("align_models", &align_models_meta);
+    m.impl("align_models_", &align_models_out_meta);
     m.impl("bundle_adjust", &bundle_adjust_meta);
     m.impl("bundle_adjust_", &bundle_adjust_out_meta);
     m.impl("bundle_adjust_pcg", &bundle_adjust_pcg_meta);

@@ -1580,3 +1580,49 @@ class RegisterViewsWorkspace:
         min_extra f64 [V] on the device; view v draws its Philox samples with ``seed + v * seed_stride``."""
         ops.load().register_views_(pts, offset, min_extra, _camera_list(K), _as_int64(seed), _as_int64(seed_stride), int(h_begin),
                                    float(thr), int(aggregation), int(refine_rounds), int(refine_max_steps), *self.buffers())
+
+
+# ------------------------------------------------------------------------------------------------------
+# Similarity alignment of every pair of sub-models in one call (csrc/sfm_align_models.hip, DESIGN.md §6ah): pairs [N,6], the
+# sub-model pairs' 3-D / 3-D items concatenated; offset int64 [Q+1]; per pair the similarity pass and the refinement of its winner
+# ------------------------------------------------------------------------------------------------------
+ALIGN_OK, ALIGN_NO_MODEL, ALIGN_TOO_FEW, ALIGN_BAD_OFFSETS = range(4)
+ALIGN_STATUS = _native.ALIGN_STATUS
+
+
+def read_align_status(status: torch.Tensor) -> np.ndarray:
+    """Host copy of the statuses of a ``sfm_align_models`` call (int32 [Q], ALIGN_*) (synchronises)."""
+    return status.cpu().numpy().astype(np.int32)
+
+
+class AlignModelsWorkspace:
+    """Pre-allocated device buffers of ``sfm_align_models`` for Q pairs x H hypotheses over N items in all, none of the pairs
+    with more than ``max_items`` (about 160 bytes per pair-hypothesis).  ``run`` fills them; nothing is read back until the
+    caller asks."""
+
+    def __init__(self, pairs: int, n_total: int, h: int, max_items: int, device=None):
+        dev = device or require_gpu()
+        self.pairs, self.n_total, self.h, self.max_items = pairs, n_total, h, max_items
+        i32, f64 = dict(dtype=torch.int32, device=dev), dict(dtype=F64, device=dev)
+        self.S = torch.empty((pairs, h, 8), **i32)
+        self.model = torch.empty((pairs, h, SIMILARITY_MODEL), **f64)
+        self.flags, self.cnt = torch.empty((pairs, h), **i32), torch.empty((pairs, h), **i32)
+        self.s1, self.s2 = torch.empty((pairs, h), **f64), torch.empty((pairs, h), **f64)
+        self.result = torch.empty((pairs, SELECT_BYTES // 8), dtype=torch.int64, device=dev)
+        self.mask = torch.empty((n_total,), dtype=torch.uint8, device=dev)
+        self.model_out = torch.empty((pairs, SIMILARITY_MODEL), **f64)
+        self.mask_out = torch.empty((n_total,), dtype=torch.uint8, device=dev)
+        self.info = torch.empty((pairs, 3), dtype=torch.int64, device=dev)
+        self.status = torch.empty((pairs,), **i32)
+
+    def buffers(self):
+        """The output tensors in the order of the ``align_models_`` op."""
+        return (self.S, self.model, self.flags, self.cnt, self.s1, self.s2, self.result, self.mask, self.model_out, self.mask_out,
+                self.info, self.status)
+
+    def run(self, pairs: torch.Tensor, offset: torch.Tensor, thr: torch.Tensor, min_extra: torch.Tensor, aggregation: int,
+            seed: int, seed_stride: int = 1, h_begin: int = 0, refine_rounds: int = 2) -> None:
+        """One ``sfm_align_models`` call (the ``align_models_`` op), enqueue-only: pairs f64 [N,6], offset int64 [Q+1], thr and
+        min_extra f64 [Q] on the device; pair q draws its Philox samples with ``seed + q * seed_stride``."""
+        ops.load().align_models_(pairs, offset, thr, min_extra, int(self.max_items), _as_int64(seed), _as_int64(seed_stride),
+                                 int(h_begin), int(aggregation), int(refine_rounds), *self.buffers())
