@@ -701,6 +701,54 @@ int sfm_align_models(uint64_t seed, uint64_t seed_stride, int64_t h_begin, const
                      double* s1, double* s2, sfm_select_result* result, uint8_t* mask, double* model_out, uint8_t* mask_out,
                      sfm_similarity_refine_info* info, int32_t* status, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- plane-sweep depth maps and their consistency filter (csrc/sfm_plane_sweep.hip; an extension, added under
+ * ABI 15) ----
+ * Both calls are defined as a fixed sequence of fp64 + - * / sqrt (DESIGN.md §6ai states it; tests/plane_sweep_oracle.py is the
+ * same sequence in NumPy), so their outputs are reproducible bit for bit. */
+#define SFM_SWEEP_OK 0            /* the reference index is a view: its maps are computed */
+#define SFM_SWEEP_BAD_REFERENCE 1 /* refs[r] is outside [0, views): the maps of r hold the filler */
+
+/* Bytes of workspace sfm_plane_sweep needs (the homographies, [refs, sources, depths, 9] doubles); -1 for sizes it refuses
+ * whatever the radius: views < 1, height or width < 4, height * width >= 2^31, refs < 0 or > 65535, sources outside [1, 8],
+ * depths outside [1, 4096]. */
+int64_t sfm_plane_sweep_workspace_bytes(int64_t views, int64_t height, int64_t width, int64_t refs, int64_t sources, int64_t depths);
+
+/* One depth map per reference view by plane-sweep stereo.
+ * images: dev uint8 [views,height,width], grey, all of one size; K: dev [9], upper triangular (the entries 0, 1, 2, 4, 5 are read);
+ * poses: dev [views,12], world to camera, R row-major (9) then t (3); refs: dev int32 [ref_count]; sources: dev int32 [ref_count,source_count],
+ * a slot that is -1, outside [0, views) or the reference itself is absent; depths: dev [ref_count,depth_count], the hypotheses of
+ * each reference, a non-finite or non-positive one is invalid.  Host scalars: the window is (2 radius + 1)^2 pixels, 1 <= radius
+ * <= 5; the cost of a hypothesis is the mean of its top_k lowest source scores (0: all); it is valid with at least min_sources >= 1
+ * valid scores; a score is valid with both window variances (times n^2) at least min_variance n^2, min_variance >= 0.
+ * Outputs, every element written: depth [ref_count,height,width] (the winner's depth after a parabola step in inverse depth, NaN
+ * without a winner), index int32 (the winner, -1 without), cost (the winner's, NaN without), status int32 [ref_count] (SFM_SWEEP_*),
+ * and, unless NULL, volume [ref_count,depth_count,height,width] (the cost of each hypothesis, NaN where invalid).  A reference with
+ * status SFM_SWEEP_BAD_REFERENCE has depth = cost = NaN, index = -1 and a volume of NaNs; that is a status, never an error return,
+ * and no table is read by the host.
+ * workspace: dev, 16-byte aligned, at least sfm_plane_sweep_workspace_bytes(...).  Two launches, no atomics, no memset, the same
+ * bits on every call.  SFM_EINVAL before the first launch for a refused size (as above; height and width at least 2 radius + 2), a
+ * scalar out of range, a null or misaligned pointer or a workspace too small; ref_count == 0 is a no-op. */
+int sfm_plane_sweep(const uint8_t* images, int64_t views, int64_t height, int64_t width, const double* K, const double* poses,
+                    const int32_t* refs, int64_t ref_count, const int32_t* sources, int64_t source_count, const double* depths,
+                    int64_t depth_count, int radius, int top_k, int min_sources, double min_variance, double* depth, int32_t* index,
+                    double* cost, int32_t* status, double* volume, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* Forward-backward consistency of depth maps across views.
+ * depth: dev [views,height,width], NaN = none; K, poses, refs, sources as for sfm_plane_sweep.  A pixel of view refs[r] with a finite
+ * depth d is taken to the world, into each source, to the nearest pixel there (which must lie in the image and hold a finite depth),
+ * back to the world with that depth and into the reference again as (x', y', z'); the source agrees iff
+ * (x' - x)^2 + (y' - y)^2 <= max_pixel_error^2 and |z' - d| <= max_relative_depth_error d.
+ * Outputs, every element written: count int32 [ref_count,height,width], the agreeing sources; filtered [ref_count,height,width], d
+ * iff count >= min_consistent, else NaN; points [ref_count,height,width,3], the world point of a kept pixel, else NaN; status int32
+ * [ref_count] (SFM_SWEEP_*; a bad reference has count 0 and NaNs).
+ * One launch, no workspace, no atomics.  SFM_EINVAL before the launch for views < 1, height * width outside [1, 2^31), ref_count
+ * outside [0, 65535], source_count outside [1, 8], a bound that is negative or not finite, min_consistent < 0 or a null or
+ * misaligned pointer; ref_count == 0 is a no-op. */
+int sfm_filter_depth_maps(const double* depth, int64_t views, int64_t height, int64_t width, const double* K, const double* poses,
+                          const int32_t* refs, int64_t ref_count, const int32_t* sources, int64_t source_count, double max_pixel_error,
+                          double max_relative_depth_error, int min_consistent, int32_t* count, double* filtered, double* points,
+                          int32_t* status, void* stream);
+
 /* ---- bundle adjustment of cameras and points (csrc/sfm_bundle.hip; an extension, off unless asked for) ----
  * These symbols were added under ABI 14 without a version change: they are new, and nothing an ABI-14 caller uses changed. */
 

@@ -13,7 +13,8 @@
 // behind it pair_poses (sfm_view_graph_pose.hip) with their refinement refine_pair_poses (sfm_view_graph_refine.hip), and
 // the refinement of a winner pnp_refine (sfm_pnp_refine.hip), the ragged absolute-pose call register_views (sfm_register_views.hip),
 // the similarity alignment similarity_ransac_pass, similarity_fit and similarity_refine (sfm_similarity.hip), the ragged
-// alignment of every pair of sub-models align_models (sfm_align_models.hip),
+// alignment of every pair of sub-models align_models (sfm_align_models.hip), the dense stage plane_sweep and filter_depth_maps
+// (sfm_plane_sweep.hip),
 // bundle_adjust (sfm_bundle.hip, sfm_bundle_pcg.hip), triangulate_tracks (sfm_tracks.hip), build_tracks
 // (sfm_track_build.hip), average_rotations (sfm_rotation_averaging.hip) and average_translations
 // (sfm_translation_averaging.hip).  The reference call sites these serve: apps/sfm.py:110-119 (RANSAC-E), :133-138 (pose),
@@ -1129,6 +1130,124 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> align_models_meta(con
             at::empty_symint({Q, c10::SymInt(kRecordWords)}, like(pairs, at::kLong))};
 }
 
+// ---- plane-sweep depth maps and their consistency filter (sfm_plane_sweep.hip): images uint8 [V, H, W], K [9] and poses [V, 12]
+// on the device, refs int32 [R], sources int32 [R, S], depths [R, D]; depth, cost [R, H, W], index int32 [R, H, W], status int32 [R],
+// volume [R, D, H, W] or none.  The workspace comes from the caching allocator ------------------------------------------------------
+struct SweepDims {
+    int64_t V, H, W, R, S, D;
+};
+
+SweepDims sweep_dims(const Tensor& maps, const Tensor& K, const Tensor& poses, const Tensor& refs, const Tensor& sources) {
+    TORCH_CHECK(maps.dim() == 3, "sfm_hip: images / depth must be [views, height, width]");
+    TORCH_CHECK(K.numel() == 9, "sfm_hip: K must hold 9 doubles");
+    TORCH_CHECK(poses.dim() == 2 && poses.size(0) == maps.size(0) && poses.size(1) == 12, "sfm_hip: poses must be [views, 12]");
+    TORCH_CHECK(refs.dim() == 1, "sfm_hip: refs must be int32 [refs]");
+    TORCH_CHECK(sources.dim() == 2 && sources.size(0) == refs.size(0), "sfm_hip: sources must be int32 [refs, sources]");
+    return {maps.size(0), maps.size(1), maps.size(2), refs.size(0), sources.size(1), 0};
+}
+
+void plane_sweep_out(const Tensor& images, const Tensor& K, const Tensor& poses, const Tensor& refs, const Tensor& sources,
+                     const Tensor& depths, int64_t radius, int64_t top_k, int64_t min_sources, double min_variance, Tensor& depth,
+                     Tensor& index, Tensor& cost, Tensor& status, const std::optional<Tensor>& volume) {
+    const OpDevice scope(images);
+    need(images, "images", at::kByte);
+    for (const Tensor* t : {&K, &poses, &depths}) need(*t, "K / poses / depths", at::kDouble);
+    for (const Tensor* t : {&depth, &cost}) need(*t, "depth / cost", at::kDouble);
+    for (const Tensor* t : {&refs, &sources}) need(*t, "refs / sources", at::kInt);
+    for (const Tensor* t : {&index, &status}) need(*t, "index / status", at::kInt);
+    SweepDims d = sweep_dims(images, K, poses, refs, sources);
+    TORCH_CHECK(depths.dim() == 2 && depths.size(0) == d.R, "sfm_hip: depths must be [refs, depths]");
+    d.D = depths.size(1);
+    const int64_t pixels = d.R * d.H * d.W;
+    TORCH_CHECK(depth.numel() == pixels && cost.numel() == pixels && index.numel() == pixels,
+                "sfm_hip: depth, index, cost must be [refs, height, width]");
+    TORCH_CHECK(status.numel() == d.R, "sfm_hip: status must be int32 [refs]");
+    const bool with_volume = volume.has_value() && volume->defined();
+    if (with_volume) {
+        need(*volume, "volume", at::kDouble);
+        TORCH_CHECK(volume->numel() == pixels * d.D, "sfm_hip: volume must be [refs, depths, height, width]");
+    }
+    for (int64_t v : {radius, top_k, min_sources}) TORCH_CHECK(v >= 0 && v <= 0x7FFFFFFF, "sfm_hip: radius, top_k, min_sources must be in [0, 2^31)");
+    const int64_t bytes = sfm_plane_sweep_workspace_bytes(d.V, d.H, d.W, d.R, d.S, d.D);
+    TORCH_CHECK(bytes >= 0, "sfm_hip: sfm_plane_sweep refuses these sizes (need views >= 1, height and width >= 4, height * width < "
+                            "2^31, refs <= 65535, 1 <= sources <= 8, 1 <= depths <= 4096)");
+    Tensor ws = at::empty({bytes > 16 ? bytes : 16}, like(images, at::kByte));
+    ok(sfm_plane_sweep(ptr<uint8_t>(images), d.V, d.H, d.W, ptr<double>(K), ptr<double>(poses), ptr<int32_t>(refs), d.R,
+                       ptr<int32_t>(sources), d.S, ptr<double>(depths), d.D, (int)radius, (int)top_k, (int)min_sources, min_variance,
+                       ptr<double>(depth), ptr<int32_t>(index), ptr<double>(cost), ptr<int32_t>(status),
+                       with_volume ? ptr<double>(*volume) : nullptr, ws.data_ptr(), ws.numel(), current_stream()),
+       "sfm_plane_sweep");
+}
+
+// the functional form -> (depth, index, cost, status, volume); volume is [refs, depths, height, width], or [0] when not asked for
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> plane_sweep(const Tensor& images, const Tensor& K, const Tensor& poses,
+                                                               const Tensor& refs, const Tensor& sources, const Tensor& depths,
+                                                               int64_t radius, int64_t top_k, int64_t min_sources, double min_variance,
+                                                               bool return_volume) {
+    TORCH_CHECK(images.dim() == 3 && refs.dim() == 1 && depths.dim() == 2, "sfm_hip: images must be [views, height, width], refs [refs], "
+                                                                           "depths [refs, depths]");
+    const int64_t R = refs.size(0), H = images.size(1), W = images.size(2);
+    Tensor depth = at::empty({R, H, W}, like(images, at::kDouble)), cost = at::empty({R, H, W}, like(images, at::kDouble));
+    Tensor index = at::empty({R, H, W}, like(images, at::kInt)), status = at::empty({R}, like(images, at::kInt));
+    Tensor volume = return_volume ? at::empty({R, depths.size(1), H, W}, like(images, at::kDouble)) : at::empty({0}, like(images, at::kDouble));
+    plane_sweep_out(images, K, poses, refs, sources, depths, radius, top_k, min_sources, min_variance, depth, index, cost, status,
+                    return_volume ? std::optional<Tensor>(volume) : std::nullopt);
+    return {depth, index, cost, status, volume};
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> plane_sweep_meta(const Tensor& images, const Tensor&, const Tensor&, const Tensor& refs,
+                                                                    const Tensor&, const Tensor& depths, int64_t, int64_t, int64_t, double,
+                                                                    bool return_volume) {
+    TORCH_CHECK(images.dim() == 3 && refs.dim() == 1 && depths.dim() == 2, "sfm_hip: images must be [views, height, width], refs [refs], "
+                                                                           "depths [refs, depths]");
+    const c10::SymInt R = refs.sym_size(0), H = images.sym_size(1), W = images.sym_size(2);
+    Tensor volume = return_volume ? at::empty_symint({R, depths.sym_size(1), H, W}, like(images, at::kDouble))
+                                  : at::empty_symint({c10::SymInt(0)}, like(images, at::kDouble));
+    return {at::empty_symint({R, H, W}, like(images, at::kDouble)), at::empty_symint({R, H, W}, like(images, at::kInt)),
+            at::empty_symint({R, H, W}, like(images, at::kDouble)), at::empty_symint({R}, like(images, at::kInt)), volume};
+}
+
+void filter_depth_maps_out(const Tensor& depth, const Tensor& K, const Tensor& poses, const Tensor& refs, const Tensor& sources,
+                           double max_pixel_error, double max_relative_depth_error, int64_t min_consistent, Tensor& count,
+                           Tensor& filtered, Tensor& points, Tensor& status) {
+    const OpDevice scope(depth);
+    for (const Tensor* t : {&depth, &K, &poses}) need(*t, "depth / K / poses", at::kDouble);
+    for (const Tensor* t : {&filtered, &points}) need(*t, "filtered / points", at::kDouble);
+    for (const Tensor* t : {&refs, &sources}) need(*t, "refs / sources", at::kInt);
+    for (const Tensor* t : {&count, &status}) need(*t, "count / status", at::kInt);
+    const SweepDims d = sweep_dims(depth, K, poses, refs, sources);
+    const int64_t pixels = d.R * d.H * d.W;
+    TORCH_CHECK(count.numel() == pixels && filtered.numel() == pixels, "sfm_hip: count, filtered must be [refs, height, width]");
+    TORCH_CHECK(points.numel() == 3 * pixels, "sfm_hip: points must be [refs, height, width, 3]");
+    TORCH_CHECK(status.numel() == d.R, "sfm_hip: status must be int32 [refs]");
+    TORCH_CHECK(min_consistent >= 0 && min_consistent <= 0x7FFFFFFF, "sfm_hip: min_consistent must be in [0, 2^31)");
+    ok(sfm_filter_depth_maps(ptr<double>(depth), d.V, d.H, d.W, ptr<double>(K), ptr<double>(poses), ptr<int32_t>(refs), d.R,
+                             ptr<int32_t>(sources), d.S, max_pixel_error, max_relative_depth_error, (int)min_consistent,
+                             ptr<int32_t>(count), ptr<double>(filtered), ptr<double>(points), ptr<int32_t>(status), current_stream()),
+       "sfm_filter_depth_maps");
+}
+
+// the functional form -> (count, filtered, points, status)
+std::tuple<Tensor, Tensor, Tensor, Tensor> filter_depth_maps(const Tensor& depth, const Tensor& K, const Tensor& poses, const Tensor& refs,
+                                                             const Tensor& sources, double max_pixel_error,
+                                                             double max_relative_depth_error, int64_t min_consistent) {
+    TORCH_CHECK(depth.dim() == 3 && refs.dim() == 1, "sfm_hip: depth must be [views, height, width], refs [refs]");
+    const int64_t R = refs.size(0), H = depth.size(1), W = depth.size(2);
+    Tensor count = at::empty({R, H, W}, like(depth, at::kInt)), filtered = at::empty({R, H, W}, like(depth, at::kDouble));
+    Tensor points = at::empty({R, H, W, 3}, like(depth, at::kDouble)), status = at::empty({R}, like(depth, at::kInt));
+    filter_depth_maps_out(depth, K, poses, refs, sources, max_pixel_error, max_relative_depth_error, min_consistent, count, filtered, points,
+                          status);
+    return {count, filtered, points, status};
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor> filter_depth_maps_meta(const Tensor& depth, const Tensor&, const Tensor&, const Tensor& refs,
+                                                                  const Tensor&, double, double, int64_t) {
+    TORCH_CHECK(depth.dim() == 3 && refs.dim() == 1, "sfm_hip: depth must be [views, height, width], refs [refs]");
+    const c10::SymInt R = refs.sym_size(0), H = depth.sym_size(1), W = depth.sym_size(2);
+    return {at::empty_symint({R, H, W}, like(depth, at::kInt)), at::empty_symint({R, H, W}, like(depth, at::kDouble)),
+            at::empty_symint({R, H, W, c10::SymInt(3)}, like(depth, at::kDouble)), at::empty_symint({R}, like(depth, at::kInt))};
+}
+
 // bundle adjustment, dense (sfm_bundle.hip) and with the iterative Schur solver (sfm_bundle_pcg.hip): poses [C, 12], points
 // [P, 3], camera / point indices int32 [M], pixels [M, 2]; fixed: the indices of the fixed cameras; the iterative solver takes
 // max_cg_iterations and cg_tolerance as well; info int64 [4] viewing the sfm_bundle_info record, int64 [5] viewing
@@ -1776,6 +1895,16 @@ TORCH_LIBRARY(sfm_hip, m) {
           "int h_begin, int aggregation, int refine_rounds, Tensor(a!) S, Tensor(b!) model, Tensor(c!) flags, Tensor(d!) cnt, "
           "Tensor(e!) s1, Tensor(f!) s2, Tensor(g!) result, Tensor(h!) mask, Tensor(i!) model_out, Tensor(j!) mask_out, "
           "Tensor(k!) info, Tensor(l!) status) -> ()");
+    m.def("plane_sweep(Tensor images, Tensor K, Tensor poses, Tensor refs, Tensor sources, Tensor depths, int radius, int top_k, "
+          "int min_sources, float min_variance, bool return_volume) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
+    m.def("plane_sweep_(Tensor images, Tensor K, Tensor poses, Tensor refs, Tensor sources, Tensor depths, int radius, int top_k, "
+          "int min_sources, float min_variance, Tensor(a!) depth, Tensor(b!) index, Tensor(c!) cost, Tensor(d!) status, "
+          "Tensor(e!)? volume) -> ()");
+    m.def("filter_depth_maps(Tensor depth, Tensor K, Tensor poses, Tensor refs, Tensor sources, float max_pixel_error, "
+          "float max_relative_depth_error, int min_consistent) -> (Tensor, Tensor, Tensor, Tensor)");
+    m.def("filter_depth_maps_(Tensor depth, Tensor K, Tensor poses, Tensor refs, Tensor sources, float max_pixel_error, "
+          "float max_relative_depth_error, int min_consistent, Tensor(a!) count, Tensor(b!) filtered, Tensor(c!) points, "
+          "Tensor(d!) status) -> ()");
     m.def("bundle_adjust(Tensor poses, Tensor points, Tensor camera_indices, Tensor point_indices, Tensor pixels, float[] K, "
           "int[] fixed, int max_steps) -> (Tensor, Tensor, Tensor)");
     m.def("bundle_adjust_(Tensor(a!) poses, Tensor(b!) points, Tensor camera_indices, Tensor point_indices, Tensor pixels, "
@@ -1865,6 +1994,10 @@ TORCH_LIBRARY_IMPL(sfm_hip, CUDA, m) {
     m.impl("similarity_refine_", &similarity_refine_out);
     m.impl("align_models", &align_models);
     m.impl("align_models_", &align_models_out);
+    m.impl("plane_sweep", &plane_sweep);
+    m.impl("plane_sweep_", &plane_sweep_out);
+    m.impl("filter_depth_maps", &filter_depth_maps);
+    m.impl("filter_depth_maps_", &filter_depth_maps_out);
     m.impl("bundle_adjust", &bundle_adjust);
     m.impl("bundle_adjust_", &bundle_adjust_inplace);
     m.impl("bundle_adjust_pcg", &bundle_adjust_pcg);
@@ -1917,6 +2050,10 @@ void register_views_out_meta(const Tensor&, const Tensor&, const Tensor&, at::Ar
 void align_models_out_meta(const Tensor&, const Tensor&, const Tensor&, const Tensor&, int64_t, int64_t, int64_t, int64_t, int64_t,
                            int64_t, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&,
                            Tensor&) {}
+void plane_sweep_out_meta(const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, int64_t, int64_t, int64_t,
+                          double, Tensor&, Tensor&, Tensor&, Tensor&, const std::optional<Tensor>&) {}
+void filter_depth_maps_out_meta(const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, double, double, int64_t, Tensor&,
+                                Tensor&, Tensor&, Tensor&) {}
 void similarity_fit_out_meta(const Tensor&, const std::optional<Tensor>&, Tensor&, Tensor&) {}
 void similarity_refine_out_meta(const Tensor&, const Tensor&, const Tensor&, const Tensor&, double, int64_t, int64_t, Tensor&, Tensor&,
                                 Tensor&) {}
@@ -1981,6 +2118,10 @@ TORCH_LIBRARY_IMPL(sfm_hip, Meta, m) {
     m.impl("similarity_refine_", &similarity_refine_out_meta);
     m.impl("align_models", &align_models_meta);
     m.impl("align_models_", &align_models_out_meta);
+    m.impl("plane_sweep", &plane_sweep_meta);
+    m.impl("plane_sweep_", &plane_sweep_out_meta);
+    m.impl("filter_depth_maps", &filter_depth_maps_meta);
+    m.impl("filter_depth_maps_", &filter_depth_maps_out_meta);
     m.impl("bundle_adjust", &bundle_adjust_meta);
     m.impl("bundle_adjust_", &bundle_adjust_out_meta);
     m.impl("bundle_adjust_pcg", &bundle_adjust_pcg_meta);

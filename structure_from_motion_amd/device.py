@@ -1626,3 +1626,54 @@ class AlignModelsWorkspace:
         min_extra f64 [Q] on the device; pair q draws its Philox samples with ``seed + q * seed_stride``."""
         ops.load().align_models_(pairs, offset, thr, min_extra, int(self.max_items), _as_int64(seed), _as_int64(seed_stride),
                                  int(h_begin), int(aggregation), int(refine_rounds), *self.buffers())
+
+
+# ------------------------------------------------------------------------------------------------------
+# Plane-sweep depth maps and their consistency filter (csrc/sfm_plane_sweep.hip, DESIGN.md §6ai): images uint8 [V,H,W], K [9] and
+# poses [V,12] on the device; per reference view a source list int32 [S] and a depth list [D]
+# ------------------------------------------------------------------------------------------------------
+SWEEP_OK, SWEEP_BAD_REFERENCE = range(2)
+SWEEP_STATUS = _native.SWEEP_STATUS
+
+
+def read_sweep_status(status: torch.Tensor) -> np.ndarray:
+    """Host copy of the statuses of a ``sfm_plane_sweep`` or ``sfm_filter_depth_maps`` call (int32 [R], SWEEP_*) (synchronises)."""
+    return status.cpu().numpy().astype(np.int32)
+
+
+class PlaneSweepWorkspace:
+    """Pre-allocated device buffers of ``sfm_plane_sweep`` for R reference views of H x W pixels and D depth hypotheses each
+    (20 bytes per pixel, and 8 D more with the cost volume).  ``run`` fills them; nothing is read back until the caller asks."""
+
+    def __init__(self, refs: int, height: int, width: int, depths: int, device=None, volume: bool = False):
+        dev = device or require_gpu()
+        self.refs, self.height, self.width, self.depths = refs, height, width, depths
+        self.depth = torch.empty((refs, height, width), dtype=F64, device=dev)
+        self.index = torch.empty((refs, height, width), dtype=torch.int32, device=dev)
+        self.cost = torch.empty((refs, height, width), dtype=F64, device=dev)
+        self.status = torch.empty((refs,), dtype=torch.int32, device=dev)
+        self.volume = torch.empty((refs, depths, height, width), dtype=F64, device=dev) if volume else None
+
+    def buffers(self):
+        """The output tensors in the order of the ``plane_sweep_`` op (``volume`` may be None)."""
+        return (self.depth, self.index, self.cost, self.status, self.volume)
+
+    def run(self, images: torch.Tensor, K: torch.Tensor, poses: torch.Tensor, refs: torch.Tensor, sources: torch.Tensor,
+            depths: torch.Tensor, radius: int = 3, top_k: int = 0, min_sources: int = 1, min_variance: float = 1.0) -> None:
+        """One ``sfm_plane_sweep`` call (the ``plane_sweep_`` op), enqueue-only: images uint8 [V,H,W], K f64 [9], poses f64
+        [V,12], refs int32 [R], sources int32 [R,S], depths f64 [R,D] on the device."""
+        ops.load().plane_sweep_(images, K, poses, refs, sources, depths, int(radius), int(top_k), int(min_sources), float(min_variance),
+                                *self.buffers())
+
+
+def filter_depth_maps(depth: torch.Tensor, K: torch.Tensor, poses: torch.Tensor, refs: torch.Tensor, sources: torch.Tensor,
+                      max_pixel_error: float = 1.0, max_relative_depth_error: float = 0.01, min_consistent: int = 2, out=None):
+    """One ``sfm_filter_depth_maps`` call, enqueue-only: depth f64 [V,H,W] (NaN = none) -> (count int32 [R,H,W], filtered f64
+    [R,H,W], points f64 [R,H,W,3], status int32 [R]); ``out``: the caller's four buffers."""
+    op = ops.load()
+    if out is None:
+        return op.filter_depth_maps(depth, K, poses, refs, sources, float(max_pixel_error), float(max_relative_depth_error),
+                                    int(min_consistent))
+    op.filter_depth_maps_(depth, K, poses, refs, sources, float(max_pixel_error), float(max_relative_depth_error), int(min_consistent),
+                          *out)
+    return out

@@ -514,3 +514,69 @@ def repeated_structure_views(views: int, points: int, unique: int, groups: int, 
         descriptors.append((np.ascontiguousarray(np.vstack([bits, alone_bits])[order]), np.ones(n + extra, dtype=bool)))
         ids.append(np.concatenate([latent, np.full(extra, -1, dtype=np.int64)])[order])
     return dict(pixels=pixels, descriptors=descriptors, ids=ids, K=K, poses_true=scene["poses_true"])
+
+
+def arc_poses(views: int, step_deg: float = 4.0, distance: float = 5.0) -> np.ndarray:
+    """(views, 12) poses, R row-major then t: cameras on an arc about the point (0, 0, distance), ``step_deg`` degrees apart about
+    the Y axis and centred on the Z axis, all looking at that point (the arc of ``multi_view_scene``, centred)."""
+    poses = np.zeros((views, 12))
+    for i in range(views):
+        a = np.radians((i - (views - 1) / 2.0) * step_deg)
+        R = np.array([[np.cos(a), 0.0, -np.sin(a)], [0.0, 1.0, 0.0], [np.sin(a), 0.0, np.cos(a)]])
+        centre = np.array([-distance * np.sin(a), 0.0, distance - distance * np.cos(a)])
+        poses[i, :9] = R.reshape(9)
+        poses[i, 9:] = -R @ centre
+    return poses
+
+
+def plane_views(height: int, width: int, poses, planes, seed: int, K=None, texels_per_unit: float = 24.0, texture_size: int = 128):
+    """Grey views of one or more textured planes, with the exact depth of every pixel.
+
+    ``poses``: (V, 12) world to camera, R row-major then t.  ``planes``: a list of ``(origin, u, v, extent)``: the plane through
+    ``origin`` spanned by the orthonormal directions ``u`` and ``v``, cut to ``|s| <= extent[0]``, ``|t| <= extent[1]`` in those
+    coordinates, or unbounded with ``extent=None``.  ``K``: the camera matrix (default: focal length 1.2 ``width``, principal
+    point at the image centre).  Per pixel the ray is intersected with every plane and the nearest hit in front of the camera
+    is taken; its grey value is the bilinear lookup of the plane's own random texture (``texture_size`` squared texels, repeated,
+    ``texels_per_unit`` texels per world unit), rounded to uint8.  A slanted plane gives a depth ramp; a second, bounded plane in
+    front gives occlusions.  Returns dict(images (V, H, W) uint8, depth (V, H, W) camera depth of the hit (NaN: no plane hit, grey
+    0), plane (V, H, W) int32 index of the plane hit or -1, K)."""
+    poses = np.asarray(poses, dtype=np.float64).reshape(-1, 12)
+    if K is None:
+        K = np.array([[1.2 * width, 0.0, (width - 1) / 2.0], [0.0, 1.2 * width, (height - 1) / 2.0], [0.0, 0.0, 1.0]])
+    K = np.asarray(K, dtype=np.float64)
+    rng = np.random.default_rng(seed)
+    textures = [rng.integers(0, 256, size=(texture_size, texture_size)).astype(np.float64) for _ in planes]
+    V = len(poses)
+    images = np.zeros((V, height, width), dtype=np.uint8)
+    depth = np.full((V, height, width), np.nan)
+    hit = np.full((V, height, width), -1, dtype=np.int32)
+    x, y = np.meshgrid(np.arange(width, dtype=np.float64), np.arange(height, dtype=np.float64))
+    rays_cam = np.stack([x, y, np.ones_like(x)], axis=-1) @ np.linalg.inv(K).T   # camera depth 1 along every ray
+    for i in range(V):
+        R, t = poses[i, :9].reshape(3, 3), poses[i, 9:]
+        centre = -R.T @ t
+        rays = rays_cam @ R   # world directions: R^T applied to every row
+        nearest = np.full((height, width), np.inf)
+        grey = np.zeros((height, width))
+        for k, ((origin, u, v, extent), texture) in enumerate(zip(planes, textures)):
+            origin, u, v = (np.asarray(a, dtype=np.float64) for a in (origin, u, v))
+            normal = np.cross(u, v)
+            with np.errstate(all="ignore"):
+                lam = float(normal @ (origin - centre)) / (rays @ normal)   # the camera depth of the hit, as rays have depth 1
+            P = centre + lam[..., None] * rays - origin
+            s, tt = P @ u, P @ v
+            ok = np.isfinite(lam) & (lam > 0.0) & (lam < nearest)
+            if extent is not None:
+                ok &= (np.abs(s) <= extent[0]) & (np.abs(tt) <= extent[1])
+            a, b = np.where(ok, s, 0.0) * texels_per_unit, np.where(ok, tt, 0.0) * texels_per_unit
+            a0, b0 = np.floor(a), np.floor(b)
+            fa, fb = a - a0, b - b0
+            ia, ib = a0.astype(np.int64) % texture_size, b0.astype(np.int64) % texture_size
+            ja, jb = (ia + 1) % texture_size, (ib + 1) % texture_size
+            value = (texture[ib, ia] * (1 - fa) + texture[ib, ja] * fa) * (1 - fb) + (texture[jb, ia] * (1 - fa) + texture[jb, ja] * fa) * fb
+            grey = np.where(ok, value, grey)
+            nearest = np.where(ok, lam, nearest)
+            hit[i][ok] = k
+        images[i] = np.clip(np.rint(grey), 0, 255).astype(np.uint8)
+        depth[i] = np.where(np.isfinite(nearest), nearest, np.nan)
+    return dict(images=images, depth=depth, plane=hit, K=K)
