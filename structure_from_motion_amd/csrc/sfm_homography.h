@@ -31,6 +31,7 @@ struct homography_solver {
     static constexpr int kSample = kHomographySample, kModel = 9;
     static constexpr const char* kName = "minimal_fit_kernel<homography_solver>";
     using Data = const Corr*;
+    SFM_DEVICE static Data from(Data corr, int64_t first) { return corr + first; }
     SFM_DEVICE static int fit(Data corr, int64_t b, int64_t n, const int32_t (&idx)[8], double (&out)[9]);
 };
 

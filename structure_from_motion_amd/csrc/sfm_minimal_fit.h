@@ -5,7 +5,9 @@
 //   kSample, kModel   items per sample (the leading entries of a row of S) and doubles per model;
 //   kName             what a failed launch is reported as;
 //   Data              what its fit reads besides the sample, passed to the kernel by value;
-//   fit(data, b, n, idx, out)   device function: the model of batch entry b from sample idx into out, returns the fit flag.
+//   fit(data, b, n, idx, out)   device function: the model of batch entry b from sample idx into out, returns the fit flag;
+//   from(data, first)  device function, needed by the ragged fit (sfm_ragged_pass.h) only: the Data whose entry 0 begins at item
+//                      `first` of data's, whatever else data holds kept.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

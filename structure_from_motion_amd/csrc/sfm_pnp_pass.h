@@ -33,6 +33,7 @@ struct p3p_solver {
     static constexpr int kSample = kP3PSample, kModel = 12;
     static constexpr const char* kName = "minimal_fit_kernel<p3p_solver>";
     using Data = PoseData;
+    SFM_DEVICE static Data from(const Data& data, int64_t first) { return Data{data.pts + first * kPnPFields, data.cam}; }
     SFM_DEVICE static int fit(const Data& data, int64_t b, int64_t n, const int32_t (&idx)[8], double (&out)[12]) {
         const double* __restrict__ pts = data.pts + b * n * kPnPFields;
         bool bad = false;

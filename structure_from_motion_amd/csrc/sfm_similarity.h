@@ -133,6 +133,7 @@ struct similarity_solver {
     static constexpr int kSample = kSimilaritySample, kModel = kSimilarityModel;
     static constexpr const char* kName = "minimal_fit_kernel<similarity_solver>";
     using Data = const SimPair*;
+    SFM_DEVICE static Data from(Data pairs, int64_t first) { return pairs + first; }
     SFM_DEVICE static int fit(Data pairs, int64_t b, int64_t n, const int32_t (&idx)[8], double (&out)[kSimilarityModel]) {
         const SimPair* __restrict__ items = pairs + b * n;
         bool bad = false;

@@ -184,7 +184,7 @@ def test_filler_and_every_element_written(dev, ragged):
     assert set(np.unique(out["mask"])) <= {0, 1, 2} and set(np.unique(out["mask_out"])) <= {0, 1}
 
 
-@pytest.mark.parametrize("table", ["decreasing", "past_the_end", "above_max_items"])
+@pytest.mark.parametrize("table", ["decreasing", "past_the_end", "negative", "above_max_items"])
 def test_bad_offset_tables(dev, ragged, table):
     """Ordinary inputs with a defined result: a status on every pair, the filler throughout, no error return, and nothing is
     read through the table."""
@@ -196,6 +196,8 @@ def test_bad_offset_tables(dev, ragged, table):
         offset[6], offset[7] = offset[7], offset[6]
     elif table == "past_the_end":
         offset[-1] = N + 1
+    elif table == "negative":
+        offset[0] = -1
     else:
         most = max(cases.SIZES) - 1
     ws = _prefilled(Q, N, h, most, dev)

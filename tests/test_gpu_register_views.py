@@ -262,6 +262,34 @@ def test_bad_offset_tables(dev, ragged, table):
         _assert_no_model(out, info, v, 0, N)
 
 
+def test_items_no_view_owns(dev):
+    """5 items in front of offset[0] and 7 behind offset[views], around views of 4, 0, 7 and 513 items (one item past a 512-item
+    score tile) with 70 hypotheses (one fit block of 64 and a partial one): both mask bytes of an item no view owns are 0, and
+    every other byte of every buffer is that of the call on the same views without those items."""
+    from structure_from_motion_amd import device
+
+    sizes, h, front, back = (4, 0, 7, 513), 70, 5, 7
+    pts, offset, min_extra = rv.ragged_arrays(rv.fixture(3, sizes))
+
+    def call(p, o):
+        ws = _prefilled(len(sizes), len(p), h, dev)
+        ws.run(device.to_device(p), device.to_device(o, torch.int64), device.to_device(min_extra), K, THR, RMS, SEED, STRIDE, H_BEGIN,
+               ROUNDS, MAX_STEPS)
+        out = _host(ws)
+        _assert_written(out)
+        return out
+    plain = call(pts, offset)
+    # the unowned items are copies of the large view's: owned by mistake, they would be marked like them
+    padded = call(np.concatenate([pts[-front:], pts, pts[-back:]]), offset + front)
+    assert plain["status"].tolist()[1::2] == [rv.TOO_FEW, rv.OK] and plain["mask_out"][-513:].any()   # not vacuous
+    for name in plain:
+        if name in ("mask", "mask_out"):
+            assert not padded[name][:front].any() and not padded[name][-back:].any(), name
+            assert np.array_equal(padded[name][front:-back], plain[name]), name
+        else:
+            assert padded[name].tobytes() == plain[name].tobytes(), name
+
+
 def test_other_passes_are_untouched_and_the_op(dev, ragged):
     """The single-view P3P pass and pnp_refine give their earlier bytes after a ragged call on the same stream; the functional op
     passes opcheck and agrees with the in-place one."""

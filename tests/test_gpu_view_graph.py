@@ -209,6 +209,34 @@ def test_bad_offsets_are_a_status(dev, ragged, table):
     assert np.all(outcome.kind == device.PAIR_BAD_OFFSETS) and np.isnan(outcome.H).all() and np.isnan(outcome.E).all()
 
 
+def test_items_no_pair_owns(dev):
+    """5 items in front of offset[0] and 7 behind offset[pairs], around pairs of 4, 0, 7 and 513 items (one item past a 512-item
+    score tile) with 70 hypotheses (one fit block of 64 and a partial one): both mask bytes of an item no pair owns are 0, and
+    every other byte of every buffer is that of the call on the same pairs without those items."""
+    from structure_from_motion_amd import device
+
+    sizes, h, front, back = (4, 0, 7, 513), 70, 5, 7
+    corr, offset, min_extra = vo.ragged_arrays(vo.ragged_scenes(sizes))
+
+    def call(c, o):
+        ws = _prefilled(len(sizes), len(c), h, dev)
+        ws.run(device.to_device(c), device.to_device(o, torch.int64), device.to_device(min_extra), THR, vo.RMS, MAX_RATIO, SEED, STRIDE,
+               H_BEGIN)
+        out = _host(ws)
+        _assert_written(out)
+        return out
+    plain = call(corr, offset)
+    # the unowned items are copies of the large pair's: owned by mistake, they would be marked like them
+    padded = call(np.concatenate([corr[-front:], corr, corr[-back:]]), offset + front)
+    assert plain["h_mask"][-513:].any() or plain["e_mask"][-513:].any()   # not vacuous: the large pair has a winner
+    for name in plain:
+        if name in ("h_mask", "e_mask"):
+            assert not padded[name][:front].any() and not padded[name][-back:].any(), name
+            assert np.array_equal(padded[name][front:-back], plain[name]), name
+        else:
+            assert padded[name].tobytes() == plain[name].tobytes(), name
+
+
 def test_other_passes_are_untouched_and_opcheck(dev, ragged):
     """One essential, one five-point and one homography single-pair pass before and after a ragged call on the same stream leave
     bit-equal records; the op passes opcheck."""

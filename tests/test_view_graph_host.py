@@ -53,6 +53,23 @@ def test_entry_refuses_bad_arguments_before_any_launch(native_lib):
     assert _call(lib, pairs=0) == 0   # no pairs: a no-op
 
 
+def test_zero_hypotheses_per_entry_point(native_lib):
+    """The one parameter of the size checks that the three ragged calls share (csrc/sfm_ragged_pass.h): ``sfm_verify_pairs`` takes
+    h_count = 0 (its selection then runs over zero rows) and is refused only for what comes behind the size checks;
+    ``sfm_register_views`` and ``sfm_align_models`` refuse it."""
+    lib = native_lib
+    assert _call(lib, h=0) == EINVAL and b"null pointer" in lib.sfm_last_error()
+    assert _call(lib, h=0, pairs=0) == 0
+    assert _call(lib, h=-1) == EINVAL and b"negative size" in lib.sfm_last_error()
+    p, q = C.c_void_p(0x1000), C.c_void_p(0x2000)   # never dereferenced: the calls are refused first
+    Kc = (C.c_double * 9)(*[float(v) for v in K.reshape(9)])
+    for h in (0, -1):
+        assert lib.sfm_register_views(1, 1, 0, p, 10, p, 2, p, Kc, h, 4.0, 3, 2, 20, p, p, p, p, p, p, p, p, p, q, p, p, None) == EINVAL
+        assert b"at least one hypothesis" in lib.sfm_last_error()
+        assert lib.sfm_align_models(1, 1, 0, p, 10, p, 2, 10, p, p, h, 3, 2, p, p, p, p, p, p, p, p, p, q, p, p, p, 1 << 30, None) == EINVAL
+        assert b"at least one hypothesis" in lib.sfm_last_error()
+
+
 def _graph(sizes=(10, 12)):
     rng = np.random.default_rng(3)
     features, pairs, matches = [], [], []

@@ -170,7 +170,7 @@ def profile(out_dir: str, args) -> dict:
         with open(stats[0]) as f:
             for row in csv.DictReader(f):
                 name = row["Name"].replace("(anonymous namespace)::", "").split("(")[0]
-                if any(key in name for key in ("register_", "pnp", "p3p", "select", "mask_kernel")):
+                if any(key in name for key in ("register_", "ragged_", "pnp", "p3p", "select", "mask_kernel")):
                     split[name] = {"calls": int(row["Calls"]), "avg_us": float(row["AverageNs"]) / 1e3,
                                    "total_ms": float(row["TotalDurationNs"]) / 1e6, "percent": float(row["Percentage"])}
     return {"kernels": split, "timing": proc.stdout.strip().splitlines()[-1:]}
