@@ -749,6 +749,56 @@ int sfm_filter_depth_maps(const double* depth, int64_t views, int64_t height, in
                           double max_relative_depth_error, int min_consistent, int32_t* count, double* filtered, double* points,
                           int32_t* status, void* stream);
 
+/* ---- fusion of depth maps into a TSDF volume and the triangles of its zero level set (csrc/sfm_tsdf.hip; an
+ * extension, added under ABI 15) ----
+ * Both calls are defined as a fixed sequence of fp64 + - * / (DESIGN.md §6aj states it; tests/tsdf_oracle.py is the same sequence
+ * in NumPy), so their outputs are reproducible bit for bit.  A volume has nx x ny x nz voxels, voxel (i, j, k) at the linear index
+ * (k ny + j) nx + i with its centre at (ox + (i + 0.5) s, oy + (j + 0.5) s, oz + (k + 0.5) s), s = voxel_size. */
+#define SFM_TSDF_OK 0       /* the view index is a view: its depth map was added */
+#define SFM_TSDF_BAD_VIEW 1 /* view_list[n] is outside [0, views): the entry was skipped */
+
+/* Average depth maps into a volume.
+ * State, in-out, dev, so that views can be added in several calls (the caller zeroes a fresh volume): sum [nz,ny,nx] doubles, count
+ * int32 [nz,ny,nx], grey_sum int32 [nz,ny,nx] or NULL.  Inputs, dev: depth [views,height,width], z-depths, a non-finite or
+ * non-positive one is no depth; images uint8 [views,height,width] or NULL, NULL exactly when grey_sum is; K [9] and poses [views,12]
+ * as for sfm_plane_sweep; view_list int32 [view_count], the views to add, in this order.  Host scalars: the origin, finite;
+ * voxel_size and truncation, finite and > 0.
+ * Per voxel and listed view: the centre is projected as sfm_filter_depth_maps projects a point; with a camera depth z > 0 and
+ * the nearest pixel (floor(u + 0.5), floor(v + 0.5)) in the image holding a depth d, sdf = d - z; the view is skipped for
+ * sdf < -truncation, else sum += sdf < truncation ? sdf / truncation : 1, count += 1 and grey_sum += the pixel's grey value.
+ * A voxel depends on no other and adds its views in the order of the list: splitting the list over calls gives the same bytes.
+ * Output: status int32 [view_count] (SFM_TSDF_*); a bad view index is a status, never an error return, and no table is read by
+ * the host.  One launch, no workspace, no atomics, no memset.  SFM_EINVAL before the launch for nx, ny or nz < 1,
+ * nx ny nz >= 2^31, views < 1, height * width outside [1, 2^31), view_count < 0, a scalar out of range, images and grey_sum not
+ * both or neither NULL, or a null or misaligned pointer; view_count == 0 is a no-op. */
+int sfm_tsdf_integrate(double* sum, int32_t* count, int32_t* grey_sum, int64_t nx, int64_t ny, int64_t nz, double ox, double oy, double oz,
+                       double voxel_size, double truncation, const double* depth, const uint8_t* images, int64_t views, int64_t height,
+                       int64_t width, const double* K, const double* poses, const int32_t* view_list, int64_t view_count, int32_t* status,
+                       void* stream);
+
+/* Bytes of workspace sfm_tsdf_extract_mesh needs (an int32 per cell and the tiles of the scan); -1 for sizes it refuses: nx, ny or
+ * nz < 2, nx ny nz >= 2^31, or 12 (nx-1)(ny-1)(nz-1) >= 2^31 (twelve triangles a cell at most, counted in int32). */
+int64_t sfm_tsdf_mesh_workspace_bytes(int64_t nx, int64_t ny, int64_t nz);
+
+/* The zero level set of a volume as triangles, by marching tetrahedra.
+ * sum, count, grey_sum (or NULL): the state of sfm_tsdf_integrate, read only.  Cell (i, j, k), i < nx-1, j < ny-1, k < nz-1, has the
+ * voxels (i + (q&1), j + ((q>>1)&1), k + ((q>>2)&1)) as corners q = 0..7; it is valid iff every corner has count >= min_count
+ * (>= 1); a corner's value is sum / count, its grey grey_sum / count, and it is negative iff the value is < 0.  A valid cell is
+ * split into the six tetrahedra (0,1,3,7) (0,3,2,7) (0,2,6,7) (0,6,4,7) (0,4,5,7) (0,5,1,7); each gives no, one or two triangles
+ * with their vertices where the value interpolated along an edge is zero, oriented so that the normal (B - A) x (C - A) points to
+ * the non-negative side (DESIGN.md §6aj has the table).
+ * Outputs, dev, every element written: vertices [max_triangles,3,3]; grey [max_triangles,3], or NULL when grey_sum is NULL; total
+ * int64 [1], the true number of triangles, also when it exceeds max_triangles.  The rows below min(total, max_triangles) hold
+ * the first triangles in the order cells (x fastest), tetrahedra, triangles; every later row is NaN.  max_triangles == 0 asks
+ * for the total alone (vertices and grey may then be NULL).
+ * workspace: dev, 16-byte aligned, at least sfm_tsdf_mesh_workspace_bytes(...), taken as it comes.  Six launches, no atomics,
+ * no memset, nothing read by the host, the same bits on every call.  SFM_EINVAL before the first launch for a refused size, a
+ * scalar out of range, min_count < 1, max_triangles < 0, grey and grey_sum not both or neither NULL, a null or misaligned pointer
+ * or a workspace too small. */
+int sfm_tsdf_extract_mesh(const double* sum, const int32_t* count, const int32_t* grey_sum, int64_t nx, int64_t ny, int64_t nz, double ox,
+                          double oy, double oz, double voxel_size, int min_count, int64_t max_triangles, double* vertices, double* grey,
+                          int64_t* total, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- bundle adjustment of cameras and points (csrc/sfm_bundle.hip; an extension, off unless asked for) ----
  * These symbols were added under ABI 14 without a version change: they are new, and nothing an ABI-14 caller uses changed. */
 

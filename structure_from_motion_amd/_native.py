@@ -190,6 +190,8 @@ SIGNATURES = {
     "sfm_align_models": [_U64, _U64, _I64, _P, _I64, _P, _I64, _I64, _P, _P, _I64, C.c_int, C.c_int] + [_P] * 13 + [_I64, _P],
     "sfm_plane_sweep": [_P, _I64, _I64, _I64, _P, _P, _P, _I64, _P, _I64, _P, _I64, C.c_int, C.c_int, C.c_int, _D] + [_P] * 6 + [_I64, _P],
     "sfm_filter_depth_maps": [_P, _I64, _I64, _I64, _P, _P, _P, _I64, _P, _I64, _D, _D, C.c_int, _P, _P, _P, _P, _P],
+    "sfm_tsdf_integrate": [_P, _P, _P, _I64, _I64, _I64, _D, _D, _D, _D, _D, _P, _P, _I64, _I64, _I64, _P, _P, _P, _I64, _P, _P],
+    "sfm_tsdf_extract_mesh": [_P, _P, _P, _I64, _I64, _I64, _D, _D, _D, _D, C.c_int, _I64, _P, _P, _P, _P, _I64, _P],
     "sfm_bundle_adjust": [_P, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _I64, _P],
     "sfm_bundle_adjust_pcg": [_P, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, _D, _P, _P, _P, _P, _I64, _P],
     "sfm_bundle_adjust_ex": [_P, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _I64, _P, _P],
@@ -213,7 +215,7 @@ OTHER_SYMBOLS = ["sfm_last_error", "sfm_abi_version", "sfm_score_workspace_bytes
                  "sfm_match_pairs_workspace_bytes", "sfm_detect_keypoints_workspace_bytes",
                  "sfm_bundle_calibrated_workspace_bytes", "sfm_tracks_robust_workspace_bytes",
                  "sfm_similarity_fit_workspace_bytes", "sfm_similarity_refine_workspace_bytes",
-                 "sfm_align_models_workspace_bytes", "sfm_plane_sweep_workspace_bytes"]
+                 "sfm_align_models_workspace_bytes", "sfm_plane_sweep_workspace_bytes", "sfm_tsdf_mesh_workspace_bytes"]
 
 # the losses of both bundle adjusters, in the order of their SFM_BUNDLE_LOSS_* codes (include/sfm_hip.h)
 BUNDLE_LOSSES = ("squared", "huber", "cauchy")
@@ -271,6 +273,9 @@ ALIGN_STATUS = ("ok", "no_model", "too_few", "bad_offsets")
 
 # the statuses of sfm_plane_sweep and sfm_filter_depth_maps, in the order of their SFM_SWEEP_* codes (include/sfm_hip.h)
 SWEEP_STATUS = ("ok", "bad_reference")
+
+# the statuses of sfm_tsdf_integrate, in the order of their SFM_TSDF_* codes (include/sfm_hip.h)
+TSDF_STATUS = ("ok", "bad_view")
 
 
 # the statuses of sfm_pair_pose, in the order of their SFM_POSE_* codes (include/sfm_hip.h)
@@ -420,6 +425,8 @@ def load() -> C.CDLL:
     lib.sfm_align_models_workspace_bytes.argtypes = [_I64, _I64, _I64]
     lib.sfm_plane_sweep_workspace_bytes.restype = C.c_int64
     lib.sfm_plane_sweep_workspace_bytes.argtypes = [_I64] * 6
+    lib.sfm_tsdf_mesh_workspace_bytes.restype = C.c_int64
+    lib.sfm_tsdf_mesh_workspace_bytes.argtypes = [_I64] * 3
     lib.sfm_detect_keypoints_workspace_bytes.restype = C.c_int64
     lib.sfm_detect_keypoints_workspace_bytes.argtypes = [_I64]
     if lib.sfm_abi_version() != ABI_VERSION:

@@ -14,7 +14,7 @@
 // the refinement of a winner pnp_refine (sfm_pnp_refine.hip), the ragged absolute-pose call register_views (sfm_register_views.hip),
 // the similarity alignment similarity_ransac_pass, similarity_fit and similarity_refine (sfm_similarity.hip), the ragged
 // alignment of every pair of sub-models align_models (sfm_align_models.hip), the dense stage plane_sweep and filter_depth_maps
-// (sfm_plane_sweep.hip),
+// (sfm_plane_sweep.hip), the fusion tsdf_integrate and tsdf_extract_mesh (sfm_tsdf.hip),
 // bundle_adjust (sfm_bundle.hip, sfm_bundle_pcg.hip), triangulate_tracks (sfm_tracks.hip), build_tracks
 // (sfm_track_build.hip), average_rotations (sfm_rotation_averaging.hip) and average_translations
 // (sfm_translation_averaging.hip).  The reference call sites these serve: apps/sfm.py:110-119 (RANSAC-E), :133-138 (pose),
@@ -1248,6 +1248,114 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> filter_depth_maps_meta(const Tensor& 
             at::empty_symint({R, H, W, c10::SymInt(3)}, like(depth, at::kDouble)), at::empty_symint({R}, like(depth, at::kInt))};
 }
 
+// ---- fusion of depth maps into a TSDF volume and its mesh (sfm_tsdf.hip): the state sum [nz, ny, nx], count int32, grey_sum int32 or
+// none; depth [V, H, W], images uint8 [V, H, W] or none, K [9], poses [V, 12], views int32 [N]; vertices [T, 3, 3], grey [T, 3] or
+// none, total int64 [1].  The mesh's workspace comes from the caching allocator --------------------------------------------------------
+bool given(const std::optional<Tensor>& t) { return t.has_value() && t->defined(); }
+
+void tsdf_state_check(const Tensor& sum, const Tensor& count, const std::optional<Tensor>& grey_sum) {
+    need(sum, "sum", at::kDouble);
+    need(count, "count", at::kInt);
+    TORCH_CHECK(sum.dim() == 3 && count.sizes() == sum.sizes(), "sfm_hip: sum and count must be [nz, ny, nx]");
+    if (given(grey_sum)) {
+        need(*grey_sum, "grey_sum", at::kInt);
+        TORCH_CHECK(grey_sum->sizes() == sum.sizes(), "sfm_hip: grey_sum must be [nz, ny, nx]");
+    }
+}
+
+void tsdf_integrate_out(Tensor& sum, Tensor& count, const std::optional<Tensor>& grey_sum, const Tensor& depth,
+                        const std::optional<Tensor>& images, const Tensor& K, const Tensor& poses, const Tensor& views, double ox, double oy,
+                        double oz, double voxel_size, double truncation, Tensor& status) {
+    const OpDevice scope(sum);
+    tsdf_state_check(sum, count, grey_sum);
+    for (const Tensor* t : {&depth, &K, &poses}) need(*t, "depth / K / poses", at::kDouble);
+    need(views, "views", at::kInt);
+    need(status, "status", at::kInt);
+    TORCH_CHECK(depth.dim() == 3, "sfm_hip: depth must be [views, height, width]");
+    TORCH_CHECK(K.numel() == 9, "sfm_hip: K must hold 9 doubles");
+    TORCH_CHECK(poses.dim() == 2 && poses.size(0) == depth.size(0) && poses.size(1) == 12, "sfm_hip: poses must be [views, 12]");
+    TORCH_CHECK(views.dim() == 1 && status.numel() == views.numel(), "sfm_hip: views and status must be int32 [n]");
+    TORCH_CHECK(given(images) == given(grey_sum), "sfm_hip: images must be given exactly when grey_sum is");
+    if (given(images)) {
+        need(*images, "images", at::kByte);
+        TORCH_CHECK(images->sizes() == depth.sizes(), "sfm_hip: images must be [views, height, width] like depth");
+    }
+    TORCH_CHECK(sum.numel() > 0 && depth.numel() > 0, "sfm_hip: the volume and the depth maps must not be empty");
+    ok(sfm_tsdf_integrate(ptr<double>(sum), ptr<int32_t>(count), ptr<int32_t>(grey_sum), sum.size(2), sum.size(1), sum.size(0), ox, oy, oz,
+                          voxel_size, truncation, ptr<double>(depth), ptr<uint8_t>(images), depth.size(0), depth.size(1), depth.size(2),
+                          ptr<double>(K), ptr<double>(poses), ptr<int32_t>(views), views.numel(), ptr<int32_t>(status), current_stream()),
+       "sfm_tsdf_integrate");
+}
+
+// the functional form -> (sum, count, grey_sum, status): new tensors; grey_sum is [0] without one
+std::tuple<Tensor, Tensor, Tensor, Tensor> tsdf_integrate(const Tensor& sum, const Tensor& count, const std::optional<Tensor>& grey_sum,
+                                                          const Tensor& depth, const std::optional<Tensor>& images, const Tensor& K,
+                                                          const Tensor& poses, const Tensor& views, double ox, double oy, double oz,
+                                                          double voxel_size, double truncation) {
+    TORCH_CHECK(views.dim() == 1, "sfm_hip: views must be int32 [n]");
+    Tensor new_sum = sum.clone(), new_count = count.clone();
+    Tensor new_grey = given(grey_sum) ? grey_sum->clone() : at::empty({0}, like(sum, at::kInt));
+    Tensor status = at::empty({views.size(0)}, like(sum, at::kInt));
+    tsdf_integrate_out(new_sum, new_count, given(grey_sum) ? std::optional<Tensor>(new_grey) : std::nullopt, depth, images, K, poses, views,
+                       ox, oy, oz, voxel_size, truncation, status);
+    return {new_sum, new_count, new_grey, status};
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor> tsdf_integrate_meta(const Tensor& sum, const Tensor& count, const std::optional<Tensor>& grey_sum,
+                                                               const Tensor&, const std::optional<Tensor>&, const Tensor&, const Tensor&,
+                                                               const Tensor& views, double, double, double, double, double) {
+    TORCH_CHECK(views.dim() == 1, "sfm_hip: views must be int32 [n]");
+    return {at::empty_like(sum), at::empty_like(count),
+            given(grey_sum) ? at::empty_like(*grey_sum) : at::empty_symint({c10::SymInt(0)}, like(sum, at::kInt)),
+            at::empty_symint({views.sym_size(0)}, like(sum, at::kInt))};
+}
+
+void tsdf_extract_mesh_out(const Tensor& sum, const Tensor& count, const std::optional<Tensor>& grey_sum, double ox, double oy, double oz,
+                           double voxel_size, int64_t min_count, Tensor& vertices, const std::optional<Tensor>& grey, Tensor& total) {
+    const OpDevice scope(sum);
+    tsdf_state_check(sum, count, grey_sum);
+    need(vertices, "vertices", at::kDouble);
+    need(total, "total", at::kLong);
+    TORCH_CHECK(vertices.dim() == 3 && vertices.size(1) == 3 && vertices.size(2) == 3, "sfm_hip: vertices must be [max_triangles, 3, 3]");
+    TORCH_CHECK(total.numel() == 1, "sfm_hip: total must be int64 [1]");
+    TORCH_CHECK(given(grey) == given(grey_sum), "sfm_hip: grey must be given exactly when grey_sum is");
+    const int64_t T = vertices.size(0);
+    if (given(grey)) {
+        need(*grey, "grey", at::kDouble);
+        TORCH_CHECK(grey->dim() == 2 && grey->size(0) == T && grey->size(1) == 3, "sfm_hip: grey must be [max_triangles, 3]");
+    }
+    TORCH_CHECK(min_count >= 1 && min_count <= 0x7FFFFFFF, "sfm_hip: min_count must be in [1, 2^31)");
+    const int64_t bytes = sfm_tsdf_mesh_workspace_bytes(sum.size(2), sum.size(1), sum.size(0));
+    TORCH_CHECK(bytes >= 0, "sfm_hip: sfm_tsdf_extract_mesh refuses these sizes (need nx, ny, nz >= 2, nx ny nz < 2^31 and "
+                            "12 (nx-1)(ny-1)(nz-1) < 2^31)");
+    Tensor ws = at::empty({bytes > 16 ? bytes : 16}, like(sum, at::kByte));
+    // with no row to write the entry point takes no grey either: a [0, 3] tensor has no address
+    ok(sfm_tsdf_extract_mesh(ptr<double>(sum), ptr<int32_t>(count), ptr<int32_t>(grey_sum), sum.size(2), sum.size(1), sum.size(0), ox, oy,
+                             oz, voxel_size, (int)min_count, T, ptr<double>(vertices), ptr<double>(grey), ptr<int64_t>(total),
+                             ws.data_ptr(), ws.numel(), current_stream()),
+       "sfm_tsdf_extract_mesh");
+}
+
+// the functional form -> (vertices, grey, total); grey is [0] without a grey_sum
+std::tuple<Tensor, Tensor, Tensor> tsdf_extract_mesh(const Tensor& sum, const Tensor& count, const std::optional<Tensor>& grey_sum, double ox,
+                                                     double oy, double oz, double voxel_size, int64_t min_count, int64_t max_triangles) {
+    TORCH_CHECK(max_triangles >= 0, "sfm_hip: max_triangles must be >= 0");
+    Tensor vertices = at::empty({max_triangles, 3, 3}, like(sum, at::kDouble)), total = at::empty({1}, like(sum, at::kLong));
+    Tensor grey = given(grey_sum) ? at::empty({max_triangles, 3}, like(sum, at::kDouble)) : at::empty({0}, like(sum, at::kDouble));
+    tsdf_extract_mesh_out(sum, count, grey_sum, ox, oy, oz, voxel_size, min_count, vertices,
+                          given(grey_sum) ? std::optional<Tensor>(grey) : std::nullopt, total);
+    return {vertices, grey, total};
+}
+
+std::tuple<Tensor, Tensor, Tensor> tsdf_extract_mesh_meta(const Tensor& sum, const Tensor&, const std::optional<Tensor>& grey_sum, double,
+                                                          double, double, double, int64_t, int64_t max_triangles) {
+    const c10::SymInt T(max_triangles);
+    Tensor grey = given(grey_sum) ? at::empty_symint({T, c10::SymInt(3)}, like(sum, at::kDouble))
+                                  : at::empty_symint({c10::SymInt(0)}, like(sum, at::kDouble));
+    return {at::empty_symint({T, c10::SymInt(3), c10::SymInt(3)}, like(sum, at::kDouble)), grey,
+            at::empty_symint({c10::SymInt(1)}, like(sum, at::kLong))};
+}
+
 // bundle adjustment, dense (sfm_bundle.hip) and with the iterative Schur solver (sfm_bundle_pcg.hip): poses [C, 12], points
 // [P, 3], camera / point indices int32 [M], pixels [M, 2]; fixed: the indices of the fixed cameras; the iterative solver takes
 // max_cg_iterations and cg_tolerance as well; info int64 [4] viewing the sfm_bundle_info record, int64 [5] viewing
@@ -1905,6 +2013,14 @@ TORCH_LIBRARY(sfm_hip, m) {
     m.def("filter_depth_maps_(Tensor depth, Tensor K, Tensor poses, Tensor refs, Tensor sources, float max_pixel_error, "
           "float max_relative_depth_error, int min_consistent, Tensor(a!) count, Tensor(b!) filtered, Tensor(c!) points, "
           "Tensor(d!) status) -> ()");
+    m.def("tsdf_integrate(Tensor sum, Tensor count, Tensor? grey_sum, Tensor depth, Tensor? images, Tensor K, Tensor poses, Tensor views, "
+          "float ox, float oy, float oz, float voxel_size, float truncation) -> (Tensor, Tensor, Tensor, Tensor)");
+    m.def("tsdf_integrate_(Tensor(a!) sum, Tensor(b!) count, Tensor(c!)? grey_sum, Tensor depth, Tensor? images, Tensor K, Tensor poses, "
+          "Tensor views, float ox, float oy, float oz, float voxel_size, float truncation, Tensor(d!) status) -> ()");
+    m.def("tsdf_extract_mesh(Tensor sum, Tensor count, Tensor? grey_sum, float ox, float oy, float oz, float voxel_size, int min_count, "
+          "int max_triangles) -> (Tensor, Tensor, Tensor)");
+    m.def("tsdf_extract_mesh_(Tensor sum, Tensor count, Tensor? grey_sum, float ox, float oy, float oz, float voxel_size, int min_count, "
+          "Tensor(a!) vertices, Tensor(b!)? grey, Tensor(c!) total) -> ()");
     m.def("bundle_adjust(Tensor poses, Tensor points, Tensor camera_indices, Tensor point_indices, Tensor pixels, float[] K, "
           "int[] fixed, int max_steps) -> (Tensor, Tensor, Tensor)");
     m.def("bundle_adjust_(Tensor(a!) poses, Tensor(b!) points, Tensor camera_indices, Tensor point_indices, Tensor pixels, "
@@ -1998,6 +2114,10 @@ TORCH_LIBRARY_IMPL(sfm_hip, CUDA, m) {
     m.impl("plane_sweep_", &plane_sweep_out);
     m.impl("filter_depth_maps", &filter_depth_maps);
     m.impl("filter_depth_maps_", &filter_depth_maps_out);
+    m.impl("tsdf_integrate", &tsdf_integrate);
+    m.impl("tsdf_integrate_", &tsdf_integrate_out);
+    m.impl("tsdf_extract_mesh", &tsdf_extract_mesh);
+    m.impl("tsdf_extract_mesh_", &tsdf_extract_mesh_out);
     m.impl("bundle_adjust", &bundle_adjust);
     m.impl("bundle_adjust_", &bundle_adjust_inplace);
     m.impl("bundle_adjust_pcg", &bundle_adjust_pcg);
@@ -2054,6 +2174,10 @@ void plane_sweep_out_meta(const Tensor&, const Tensor&, const Tensor&, const Ten
                           double, Tensor&, Tensor&, Tensor&, Tensor&, const std::optional<Tensor>&) {}
 void filter_depth_maps_out_meta(const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, double, double, int64_t, Tensor&,
                                 Tensor&, Tensor&, Tensor&) {}
+void tsdf_integrate_out_meta(Tensor&, Tensor&, const std::optional<Tensor>&, const Tensor&, const std::optional<Tensor>&, const Tensor&,
+                             const Tensor&, const Tensor&, double, double, double, double, double, Tensor&) {}
+void tsdf_extract_mesh_out_meta(const Tensor&, const Tensor&, const std::optional<Tensor>&, double, double, double, double, int64_t, Tensor&,
+                                const std::optional<Tensor>&, Tensor&) {}
 void similarity_fit_out_meta(const Tensor&, const std::optional<Tensor>&, Tensor&, Tensor&) {}
 void similarity_refine_out_meta(const Tensor&, const Tensor&, const Tensor&, const Tensor&, double, int64_t, int64_t, Tensor&, Tensor&,
                                 Tensor&) {}
@@ -2122,6 +2246,10 @@ TORCH_LIBRARY_IMPL(sfm_hip, Meta, m) {
     m.impl("plane_sweep_", &plane_sweep_out_meta);
     m.impl("filter_depth_maps", &filter_depth_maps_meta);
     m.impl("filter_depth_maps_", &filter_depth_maps_out_meta);
+    m.impl("tsdf_integrate", &tsdf_integrate_meta);
+    m.impl("tsdf_integrate_", &tsdf_integrate_out_meta);
+    m.impl("tsdf_extract_mesh", &tsdf_extract_mesh_meta);
+    m.impl("tsdf_extract_mesh_", &tsdf_extract_mesh_out_meta);
     m.impl("bundle_adjust", &bundle_adjust_meta);
     m.impl("bundle_adjust_", &bundle_adjust_out_meta);
     m.impl("bundle_adjust_pcg", &bundle_adjust_pcg_meta);

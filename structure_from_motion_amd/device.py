@@ -1677,3 +1677,45 @@ def filter_depth_maps(depth: torch.Tensor, K: torch.Tensor, poses: torch.Tensor,
     op.filter_depth_maps_(depth, K, poses, refs, sources, float(max_pixel_error), float(max_relative_depth_error), int(min_consistent),
                           *out)
     return out
+
+
+# ------------------------------------------------------------------------------------------------------
+# Fusion of depth maps into a TSDF volume and its mesh (csrc/sfm_tsdf.hip): the state sum f64 [nz,ny,nx], count
+# int32 [nz,ny,nx] and grey_sum int32 [nz,ny,nx] or None on the device; origin a triple of floats
+# ------------------------------------------------------------------------------------------------------
+TSDF_OK, TSDF_BAD_VIEW = range(2)
+TSDF_STATUS = _native.TSDF_STATUS
+
+
+def read_tsdf_status(status: torch.Tensor) -> np.ndarray:
+    """Host copy of the statuses of a ``sfm_tsdf_integrate`` call (int32 [N], TSDF_*) (synchronises)."""
+    return status.cpu().numpy().astype(np.int32)
+
+
+def tsdf_integrate(state, depth: torch.Tensor, images, K: torch.Tensor, poses: torch.Tensor, views: torch.Tensor, origin,
+                   voxel_size: float, truncation: float, status=None):
+    """One ``sfm_tsdf_integrate`` call, enqueue-only.  ``state``: (sum, count, grey_sum or None); depth f64 [V,H,W], images uint8
+    [V,H,W] or None (None exactly when grey_sum is), K f64 [9], poses f64 [V,12], views int32 [N].  Without ``status`` the state
+    is left as it is and -> (sum, count, grey_sum or None, status), new tensors; with ``status`` (int32 [N]) the state is
+    updated in place and ``status`` filled."""
+    op = ops.load()
+    total, count, grey_sum = state
+    scalars = (float(origin[0]), float(origin[1]), float(origin[2]), float(voxel_size), float(truncation))
+    if status is None:
+        total, count, grey, status = op.tsdf_integrate(total, count, grey_sum, depth, images, K, poses, views, *scalars)
+        return total, count, (None if grey_sum is None else grey), status
+    op.tsdf_integrate_(total, count, grey_sum, depth, images, K, poses, views, *scalars, status)
+    return total, count, grey_sum, status
+
+
+def tsdf_extract_mesh(state, origin, voxel_size: float, min_count: int = 1, max_triangles: int = 0, out=None):
+    """One ``sfm_tsdf_extract_mesh`` call, enqueue-only: -> (vertices f64 [max_triangles,3,3], grey f64 [max_triangles,3] or None,
+    total int64 [1]); ``out``: the caller's three buffers (grey None without a grey_sum), whose row count is max_triangles."""
+    op = ops.load()
+    total, count, grey_sum = state
+    scalars = (float(origin[0]), float(origin[1]), float(origin[2]), float(voxel_size), int(min_count))
+    if out is None:
+        vertices, grey, found = op.tsdf_extract_mesh(total, count, grey_sum, *scalars, int(max_triangles))
+        return vertices, (None if grey_sum is None else grey), found
+    op.tsdf_extract_mesh_(total, count, grey_sum, *scalars, *out)
+    return out
