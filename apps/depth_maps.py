@@ -10,6 +10,9 @@ hypothesis lies within one hypothesis step of the truth, before the filter (of a
 it kept), the share it kept, the median relative depth error of the sub-sample depths before and after, and the number of
 points of the view in the cloud.
 
+``--smooth P1 P2`` adds the same figures under ``"smoothed"`` for the maps whose cost volume was smoothed along 8 scanline paths
+with these penalties before the winners were taken (``compute_depth_maps(..., smoothness=(P1, P2))``).
+
 ``--from-model`` takes nothing from the truth but the images and the camera matrix: sparse points of the same scene are observed
 with pixel noise, reconstructed by the incremental route of ``apps/merge_reconstructions.py`` (in the gauge of its first view and
 seed baseline), and the poses, each view's depth range (``depth_ranges``) and its sources (``select_source_views``) come from
@@ -101,7 +104,7 @@ def _median(values) -> float | None:
 
 def run(views: int = 5, height: int = 120, width: int = 160, depths: int = 64, radius: int = 3, top_k: int = 2, seed: int = 2,
         step_deg: float = 4.0, max_pixel_error: float = 1.0, max_relative_depth_error: float = 0.02, min_consistent: int = 2,
-        from_model: bool = False, sparse_points: int = 3000, noise_px: float = 0.1) -> dict:
+        from_model: bool = False, sparse_points: int = 3000, noise_px: float = 0.1, smooth=None) -> dict:
     if views < 3:
         raise ValueError(f"need at least 3 views, got {views!r}")
     scene = two_plane_scene(views, height, width, seed, step_deg)
@@ -120,12 +123,23 @@ def run(views: int = 5, height: int = 120, width: int = 160, depths: int = 64, r
         sources = np.array([sorted((u for u in range(views) if u != v), key=lambda u, v=v: (abs(u - v), u))[:4] for v in range(views)],
                            dtype=np.int32)
     z = np.stack([depth_hypotheses(near[v], far[v], depths) for v in range(views)])
-    maps = compute_depth_maps(scene["images"], scene["K"], poses, z, sources=sources, radius=radius, top_k=top_k)
-    kept = filter_depth_maps(maps, scene["K"], poses, sources, max_pixel_error, max_relative_depth_error, min_consistent)
-    points, grey, view = point_cloud(kept)
     inner = np.zeros((height, width), dtype=bool)
     inner[radius:height - radius, radius:width - radius] = True
-    report["per_view"] = []
+    filter_args = (max_pixel_error, max_relative_depth_error, min_consistent)
+    report.update(_figures(scene, poses, z, sources, radius, top_k, None, filter_args, truth, inner))
+    if smooth is not None:
+        report["smoothed"] = {"p1": float(smooth[0]), "p2": float(smooth[1]),
+                              **_figures(scene, poses, z, sources, radius, top_k, tuple(smooth), filter_args, truth, inner)}
+    return report
+
+
+def _figures(scene, poses, z, sources, radius, top_k, smoothness, filter_args, truth, inner) -> dict:
+    """The depth maps with or without smoothing, the filter and the cloud: the figures of the module docstring."""
+    views = len(z)
+    maps = compute_depth_maps(scene["images"], scene["K"], poses, z, sources=sources, radius=radius, top_k=top_k, smoothness=smoothness)
+    kept = filter_depth_maps(maps, scene["K"], poses, sources, *filter_args)
+    points, grey, view = point_cloud(kept)
+    report = {"per_view": []}
     for v in range(views):
         with np.errstate(all="ignore"):
             want = np.abs(1.0 / truth[v][..., None] - 1.0 / z[v]).argmin(axis=-1)
@@ -163,9 +177,11 @@ def main():
     ap.add_argument("--from-model", action="store_true", help="poses, depth ranges and sources from a sparse reconstruction")
     ap.add_argument("--sparse-points", type=int, default=3000)
     ap.add_argument("--noise-px", type=float, default=0.1, help="pixel noise of the sparse observations")
+    ap.add_argument("--smooth", type=float, nargs=2, metavar=("P1", "P2"), default=None,
+                    help="also report the maps of the cost volume smoothed with these penalties")
     a = ap.parse_args()
     print(json.dumps(run(a.views, a.height, a.width, a.depths, a.radius, a.top_k, a.seed, a.step_deg, a.max_pixel_error,
-                         a.max_relative_depth_error, a.min_consistent, a.from_model, a.sparse_points, a.noise_px)))
+                         a.max_relative_depth_error, a.min_consistent, a.from_model, a.sparse_points, a.noise_px, a.smooth)))
 
 
 if __name__ == "__main__":

@@ -11,6 +11,9 @@ Printed as JSON: the number of triangles and of welded points, the share of the 
 largest distance of the mesh's points to the nearest of the two true planes, in voxels, and the share of the triangles whose
 normal faces the middle camera.  ``--ply PATH`` writes the welded mesh with its grey values.
 
+``--smooth P1 P2`` adds the same figures under ``"smoothed"`` for the surface fused from the depth maps whose cost volume was
+smoothed with these penalties (``compute_depth_maps(..., smoothness=(P1, P2))``).
+
 ``--from-model`` takes the poses, depth ranges and sources from a sparse reconstruction, as in ``apps/depth_maps.py``; the mesh
 is brought back from the model's gauge into the scene's for the comparison only."""
 from __future__ import annotations
@@ -43,7 +46,7 @@ def distance_to_planes(points: np.ndarray) -> np.ndarray:
 def run(views: int = 5, height: int = 120, width: int = 160, depths: int = 64, radius: int = 3, top_k: int = 2, seed: int = 2,
         step_deg: float = 4.0, max_pixel_error: float = 1.0, max_relative_depth_error: float = 0.02, min_consistent: int = 2,
         pixels: float = 2.0, truncation_voxels: float = 4.0, min_count: int = 2, from_model: bool = False, sparse_points: int = 3000,
-        noise_px: float = 0.1, ply: str | None = None) -> dict:
+        noise_px: float = 0.1, ply: str | None = None, smooth=None) -> dict:
     if views < 3:
         raise ValueError(f"need at least 3 views, got {views!r}")
     scene = two_plane_scene(views, height, width, seed, step_deg)
@@ -61,8 +64,21 @@ def run(views: int = 5, height: int = 120, width: int = 160, depths: int = 64, r
         sources = np.array([sorted((u for u in range(views) if u != v), key=lambda u, v=v: (abs(u - v), u))[:4] for v in range(views)],
                            dtype=np.int32)
     z = np.stack([depth_hypotheses(near[v], far[v], depths) for v in range(views)])
-    maps = compute_depth_maps(scene["images"], scene["K"], poses, z, sources=sources, radius=radius, top_k=top_k)
-    kept = filter_depth_maps(maps, scene["K"], poses, sources, max_pixel_error, max_relative_depth_error, min_consistent)
+    filter_args = (max_pixel_error, max_relative_depth_error, min_consistent)
+    fusion_args = (pixels, truncation_voxels, min_count)
+    report.update(_surface(scene, poses, z, sources, radius, top_k, None, filter_args, fusion_args, scale, ply))
+    if smooth is not None:
+        report["smoothed"] = {"p1": float(smooth[0]), "p2": float(smooth[1]),
+                              **_surface(scene, poses, z, sources, radius, top_k, tuple(smooth), filter_args, fusion_args, scale, None)}
+    return report
+
+
+def _surface(scene, poses, z, sources, radius, top_k, smoothness, filter_args, fusion_args, scale, ply) -> dict:
+    """The depth maps with or without smoothing, the filter, the fusion and the mesh: the figures of the module docstring."""
+    views = len(z)
+    pixels, truncation_voxels, min_count = fusion_args
+    maps = compute_depth_maps(scene["images"], scene["K"], poses, z, sources=sources, radius=radius, top_k=top_k, smoothness=smoothness)
+    kept = filter_depth_maps(maps, scene["K"], poses, sources, *filter_args)
     voxel = suggest_voxel_size(kept, scene["K"], pixels)
     truncation = truncation_voxels * voxel
     low, high = volume_bounds(kept, truncation)
@@ -90,12 +106,11 @@ def run(views: int = 5, height: int = 120, width: int = 160, depths: int = 64, r
     corners = to_scene(mesh.vertices.reshape(-1, 3)).reshape(-1, 3, 3)
     normal = np.cross(corners[:, 1] - corners[:, 0], corners[:, 2] - corners[:, 0])
     facing = np.einsum("ij,ij->i", normal, centre - corners.mean(axis=1)) > 0
-    report.update({"voxel_size": voxel, "dims": [int(d) for d in dims], "triangles": int(len(faces)), "points": int(len(points)),
-                   "valid_cells": float(cells.mean()),
-                   "mean_distance_voxels": float(distance.mean()) if len(distance) else None,
-                   "max_distance_voxels": float(distance.max()) if len(distance) else None,
-                   "normals_facing_cameras": float(facing.mean()) if len(facing) else None})
-    return report
+    return {"voxel_size": voxel, "dims": [int(d) for d in dims], "triangles": int(len(faces)), "points": int(len(points)),
+            "valid_cells": float(cells.mean()),
+            "mean_distance_voxels": float(distance.mean()) if len(distance) else None,
+            "max_distance_voxels": float(distance.max()) if len(distance) else None,
+            "normals_facing_cameras": float(facing.mean()) if len(facing) else None}
 
 
 def main():
@@ -118,10 +133,12 @@ def main():
     ap.add_argument("--sparse-points", type=int, default=3000)
     ap.add_argument("--noise-px", type=float, default=0.1, help="pixel noise of the sparse observations")
     ap.add_argument("--ply", default=None, help="write the welded mesh to this PLY file")
+    ap.add_argument("--smooth", type=float, nargs=2, metavar=("P1", "P2"), default=None,
+                    help="also report the surface of the depth maps smoothed with these penalties")
     a = ap.parse_args()
     print(json.dumps(run(a.views, a.height, a.width, a.depths, a.radius, a.top_k, a.seed, a.step_deg, a.max_pixel_error,
                          a.max_relative_depth_error, a.min_consistent, a.pixels, a.truncation_voxels, a.min_count, a.from_model,
-                         a.sparse_points, a.noise_px, a.ply)))
+                         a.sparse_points, a.noise_px, a.ply, a.smooth)))
 
 
 if __name__ == "__main__":

@@ -749,6 +749,34 @@ int sfm_filter_depth_maps(const double* depth, int64_t views, int64_t height, in
                           double max_relative_depth_error, int min_consistent, int32_t* count, double* filtered, double* points,
                           int32_t* status, void* stream);
 
+/* ---- semi-global smoothing of the plane-sweep cost volume (csrc/sfm_sgm.hip; an extension, added under ABI 15) ----
+ * The call is defined as a fixed sequence of fp64 + - * / min (DESIGN.md §6ak states it; tests/sgm_oracle.py is the same sequence in
+ * NumPy), so its outputs are reproducible bit for bit. */
+
+/* Bytes of workspace sfm_sgm_aggregate needs: the running sum, [refs, depths, height, width] doubles, when the call is not given an
+ * `aggregated` to keep it in (keep_aggregated == 0), else 0; -1 for sizes it refuses: refs < 0 or > 65535, depths outside [1, 256],
+ * height or width < 1, height * width >= 2^31. */
+int64_t sfm_sgm_workspace_bytes(int64_t refs, int64_t depths, int64_t height, int64_t width, int keep_aggregated);
+
+/* Semi-global aggregation of a cost volume along 4 or 8 scanline directions, and the winner of every pixel.
+ * volume: dev [ref_count,depth_count,height,width] and depths: dev [ref_count,depth_count], what sfm_plane_sweep writes and reads.
+ * C'(p, d) is volume[r,d,y,x] if finite, else invalid_cost; d is eligible at p iff volume[r,d,y,x] is finite and depths[r,d] is
+ * finite and > 0.  Directions (dx, dy), in this order: (0,1) (1,1) (-1,1) (0,-1) (-1,-1) (1,-1) (1,0) (-1,0) for paths == 8,
+ * (0,1) (0,-1) (1,0) (-1,0) for paths == 4.  Along direction k, with q = (x - dx, y - dy): L_k(p, d) = C'(p, d) if q is outside the
+ * image, else (C'(p, d) + min(L_k(q, d), L_k(q, d-1) + p1 [d > 0], L_k(q, d+1) + p1 [d < depth_count-1], m + p2)) - m with
+ * m = min_j L_k(q, j).  S = ((L_0 + L_1) + L_2) + ..., in the order of the list.
+ * Outputs, every element written: aggregated [ref_count,depth_count,height,width], S at every hypothesis, eligible or not, or NULL
+ * (the workspace then holds it); index int32 [ref_count,height,width], the eligible d of lowest S, ties to the lower index, -1
+ * without one; cost, S at the winner, NaN without; depth, the winner's depth after the parabola step of sfm_plane_sweep on S in
+ * inverse depth (both neighbours eligible), NaN without.  A volume of NaNs gives maps of NaN and -1.
+ * workspace: dev, 16-byte aligned, at least sfm_sgm_workspace_bytes(..., aggregated != NULL).  paths + 1 launches whatever the
+ * sizes, no atomics, no memset, nothing read by the host, the same bits on every call.  SFM_EINVAL before the first launch for a
+ * refused size (as above), paths other than 4 or 8, p1, p2 or invalid_cost not finite or not 0 <= p1 <= p2, a null or misaligned
+ * pointer, aggregated == volume or a workspace too small; ref_count == 0 is a no-op. */
+int sfm_sgm_aggregate(const double* volume, int64_t ref_count, int64_t depth_count, int64_t height, int64_t width, const double* depths,
+                      double p1, double p2, double invalid_cost, int paths, double* depth, int32_t* index, double* cost,
+                      double* aggregated, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- fusion of depth maps into a TSDF volume and the triangles of its zero level set (csrc/sfm_tsdf.hip; an
  * extension, added under ABI 15) ----
  * Both calls are defined as a fixed sequence of fp64 + - * / (DESIGN.md §6aj states it; tests/tsdf_oracle.py is the same sequence

@@ -192,6 +192,7 @@ SIGNATURES = {
     "sfm_filter_depth_maps": [_P, _I64, _I64, _I64, _P, _P, _P, _I64, _P, _I64, _D, _D, C.c_int, _P, _P, _P, _P, _P],
     "sfm_tsdf_integrate": [_P, _P, _P, _I64, _I64, _I64, _D, _D, _D, _D, _D, _P, _P, _I64, _I64, _I64, _P, _P, _P, _I64, _P, _P],
     "sfm_tsdf_extract_mesh": [_P, _P, _P, _I64, _I64, _I64, _D, _D, _D, _D, C.c_int, _I64, _P, _P, _P, _P, _I64, _P],
+    "sfm_sgm_aggregate": [_P, _I64, _I64, _I64, _I64, _P, _D, _D, _D, C.c_int, _P, _P, _P, _P, _P, _I64, _P],
     "sfm_bundle_adjust": [_P, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _I64, _P],
     "sfm_bundle_adjust_pcg": [_P, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, _D, _P, _P, _P, _P, _I64, _P],
     "sfm_bundle_adjust_ex": [_P, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _I64, _P, _P],
@@ -215,7 +216,8 @@ OTHER_SYMBOLS = ["sfm_last_error", "sfm_abi_version", "sfm_score_workspace_bytes
                  "sfm_match_pairs_workspace_bytes", "sfm_detect_keypoints_workspace_bytes",
                  "sfm_bundle_calibrated_workspace_bytes", "sfm_tracks_robust_workspace_bytes",
                  "sfm_similarity_fit_workspace_bytes", "sfm_similarity_refine_workspace_bytes",
-                 "sfm_align_models_workspace_bytes", "sfm_plane_sweep_workspace_bytes", "sfm_tsdf_mesh_workspace_bytes"]
+                 "sfm_align_models_workspace_bytes", "sfm_plane_sweep_workspace_bytes", "sfm_tsdf_mesh_workspace_bytes",
+                 "sfm_sgm_workspace_bytes"]
 
 # the losses of both bundle adjusters, in the order of their SFM_BUNDLE_LOSS_* codes (include/sfm_hip.h)
 BUNDLE_LOSSES = ("squared", "huber", "cauchy")
@@ -427,6 +429,8 @@ def load() -> C.CDLL:
     lib.sfm_plane_sweep_workspace_bytes.argtypes = [_I64] * 6
     lib.sfm_tsdf_mesh_workspace_bytes.restype = C.c_int64
     lib.sfm_tsdf_mesh_workspace_bytes.argtypes = [_I64] * 3
+    lib.sfm_sgm_workspace_bytes.restype = C.c_int64
+    lib.sfm_sgm_workspace_bytes.argtypes = [_I64] * 4 + [C.c_int]
     lib.sfm_detect_keypoints_workspace_bytes.restype = C.c_int64
     lib.sfm_detect_keypoints_workspace_bytes.argtypes = [_I64]
     if lib.sfm_abi_version() != ABI_VERSION:

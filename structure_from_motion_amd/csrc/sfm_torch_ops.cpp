@@ -14,7 +14,8 @@
 // the refinement of a winner pnp_refine (sfm_pnp_refine.hip), the ragged absolute-pose call register_views (sfm_register_views.hip),
 // the similarity alignment similarity_ransac_pass, similarity_fit and similarity_refine (sfm_similarity.hip), the ragged
 // alignment of every pair of sub-models align_models (sfm_align_models.hip), the dense stage plane_sweep and filter_depth_maps
-// (sfm_plane_sweep.hip), the fusion tsdf_integrate and tsdf_extract_mesh (sfm_tsdf.hip),
+// (sfm_plane_sweep.hip), the smoothing of its cost volume sgm_aggregate (sfm_sgm.hip), the fusion tsdf_integrate and
+// tsdf_extract_mesh (sfm_tsdf.hip),
 // bundle_adjust (sfm_bundle.hip, sfm_bundle_pcg.hip), triangulate_tracks (sfm_tracks.hip), build_tracks
 // (sfm_track_build.hip), average_rotations (sfm_rotation_averaging.hip) and average_translations
 // (sfm_translation_averaging.hip).  The reference call sites these serve: apps/sfm.py:110-119 (RANSAC-E), :133-138 (pose),
@@ -1248,6 +1249,59 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> filter_depth_maps_meta(const Tensor& 
             at::empty_symint({R, H, W, c10::SymInt(3)}, like(depth, at::kDouble)), at::empty_symint({R}, like(depth, at::kInt))};
 }
 
+// ---- semi-global smoothing of the plane-sweep cost volume (sfm_sgm.hip): volume [R, D, H, W] and depths [R, D] on the device; depth,
+// cost [R, H, W], index int32 [R, H, W], aggregated [R, D, H, W] or none.  The workspace comes from the caching allocator ------------
+void sgm_aggregate_out(const Tensor& volume, const Tensor& depths, double p1, double p2, double invalid_cost, int64_t paths, Tensor& depth,
+                       Tensor& index, Tensor& cost, const std::optional<Tensor>& aggregated) {
+    const OpDevice scope(volume);
+    for (const Tensor* t : {&volume, &depths}) need(*t, "volume / depths", at::kDouble);
+    for (const Tensor* t : {&depth, &cost}) need(*t, "depth / cost", at::kDouble);
+    need(index, "index", at::kInt);
+    TORCH_CHECK(volume.dim() == 4, "sfm_hip: volume must be [refs, depths, height, width]");
+    const int64_t R = volume.size(0), D = volume.size(1), H = volume.size(2), W = volume.size(3);
+    TORCH_CHECK(depths.dim() == 2 && depths.size(0) == R && depths.size(1) == D, "sfm_hip: depths must be [refs, depths]");
+    const int64_t pixels = R * H * W;
+    TORCH_CHECK(depth.numel() == pixels && cost.numel() == pixels && index.numel() == pixels,
+                "sfm_hip: depth, index, cost must be [refs, height, width]");
+    const bool keep = aggregated.has_value() && aggregated->defined();
+    if (keep) {
+        need(*aggregated, "aggregated", at::kDouble);
+        TORCH_CHECK(aggregated->numel() == pixels * D, "sfm_hip: aggregated must be [refs, depths, height, width]");
+    }
+    TORCH_CHECK(paths >= 0 && paths <= 0x7FFFFFFF, "sfm_hip: paths must be 4 or 8");
+    const int64_t bytes = sfm_sgm_workspace_bytes(R, D, H, W, keep ? 1 : 0);
+    TORCH_CHECK(bytes >= 0, "sfm_hip: sfm_sgm_aggregate refuses these sizes (need refs <= 65535, 1 <= depths <= 256, height and width >= 1, "
+                            "height * width < 2^31)");
+    Tensor ws = at::empty({bytes > 16 ? bytes : 16}, like(volume, at::kByte));
+    ok(sfm_sgm_aggregate(ptr<double>(volume), R, D, H, W, ptr<double>(depths), p1, p2, invalid_cost, (int)paths, ptr<double>(depth),
+                         ptr<int32_t>(index), ptr<double>(cost), keep ? ptr<double>(*aggregated) : nullptr, ws.data_ptr(), ws.numel(),
+                         current_stream()),
+       "sfm_sgm_aggregate");
+}
+
+// the functional form -> (depth, index, cost, aggregated); aggregated is [refs, depths, height, width], or [0] when not asked for
+std::tuple<Tensor, Tensor, Tensor, Tensor> sgm_aggregate(const Tensor& volume, const Tensor& depths, double p1, double p2, double invalid_cost,
+                                                         int64_t paths, bool return_aggregated) {
+    TORCH_CHECK(volume.dim() == 4, "sfm_hip: volume must be [refs, depths, height, width]");
+    const int64_t R = volume.size(0), H = volume.size(2), W = volume.size(3);
+    Tensor depth = at::empty({R, H, W}, like(volume, at::kDouble)), cost = at::empty({R, H, W}, like(volume, at::kDouble));
+    Tensor index = at::empty({R, H, W}, like(volume, at::kInt));
+    Tensor aggregated = return_aggregated ? at::empty({R, volume.size(1), H, W}, like(volume, at::kDouble)) : at::empty({0}, like(volume, at::kDouble));
+    sgm_aggregate_out(volume, depths, p1, p2, invalid_cost, paths, depth, index, cost,
+                      return_aggregated ? std::optional<Tensor>(aggregated) : std::nullopt);
+    return {depth, index, cost, aggregated};
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor> sgm_aggregate_meta(const Tensor& volume, const Tensor&, double, double, double, int64_t,
+                                                              bool return_aggregated) {
+    TORCH_CHECK(volume.dim() == 4, "sfm_hip: volume must be [refs, depths, height, width]");
+    const c10::SymInt R = volume.sym_size(0), H = volume.sym_size(2), W = volume.sym_size(3);
+    Tensor aggregated = return_aggregated ? at::empty_symint({R, volume.sym_size(1), H, W}, like(volume, at::kDouble))
+                                          : at::empty_symint({c10::SymInt(0)}, like(volume, at::kDouble));
+    return {at::empty_symint({R, H, W}, like(volume, at::kDouble)), at::empty_symint({R, H, W}, like(volume, at::kInt)),
+            at::empty_symint({R, H, W}, like(volume, at::kDouble)), aggregated};
+}
+
 // ---- fusion of depth maps into a TSDF volume and its mesh (sfm_tsdf.hip): the state sum [nz, ny, nx], count int32, grey_sum int32 or
 // none; depth [V, H, W], images uint8 [V, H, W] or none, K [9], poses [V, 12], views int32 [N]; vertices [T, 3, 3], grey [T, 3] or
 // none, total int64 [1].  The mesh's workspace comes from the caching allocator --------------------------------------------------------
@@ -2013,7 +2067,11 @@ TORCH_LIBRARY(sfm_hip, m) {
     m.def("filter_depth_maps_(Tensor depth, Tensor K, Tensor poses, Tensor refs, Tensor sources, float max_pixel_error, "
           "float max_relative_depth_error, int min_consistent, Tensor(a!) count, Tensor(b!) filtered, Tensor(c!) points, "
           "Tensor(d!) status) -> ()");
-    m.def("tsdf_integrate(Tensor sum, Tensor count, Tensor? grey_sum, Tensor depth, Tensor? images, Tensor K, Tensor poses, Tensor views, "
+    m.def("sgm_aggregate(Tensor volume, Tensor depths, float p1, float p2, float invalid_cost, int paths, bool return_aggregated) -> "
+          "(Tensor, Tensor, Tensor, Tensor)");
+    m.def("sgm_aggregate_(Tensor volume, Tensor depths, float p1, float p2, float invalid_cost, int paths, Tensor(a!) depth, "
+          "Tensor(b!) index, Tensor(c!) cost, Tensor(d!)? aggregated) -> ()");
+    m.def("tsdf_integrate(Tensor sum,Tensor count, Tensor? grey_sum, Tensor depth, Tensor? images, Tensor K, Tensor poses, Tensor views, "
           "float ox, float oy, float oz, float voxel_size, float truncation) -> (Tensor, Tensor, Tensor, Tensor)");
     m.def("tsdf_integrate_(Tensor(a!) sum, Tensor(b!) count, Tensor(c!)? grey_sum, Tensor depth, Tensor? images, Tensor K, Tensor poses, "
           "Tensor views, float ox, float oy, float oz, float voxel_size, float truncation, Tensor(d!) status) -> ()");
@@ -2114,6 +2172,8 @@ TORCH_LIBRARY_IMPL(sfm_hip, CUDA, m) {
     m.impl("plane_sweep_", &plane_sweep_out);
     m.impl("filter_depth_maps", &filter_depth_maps);
     m.impl("filter_depth_maps_", &filter_depth_maps_out);
+    m.impl("sgm_aggregate", &sgm_aggregate);
+    m.impl("sgm_aggregate_", &sgm_aggregate_out);
     m.impl("tsdf_integrate", &tsdf_integrate);
     m.impl("tsdf_integrate_", &tsdf_integrate_out);
     m.impl("tsdf_extract_mesh", &tsdf_extract_mesh);
@@ -2174,6 +2234,8 @@ void plane_sweep_out_meta(const Tensor&, const Tensor&, const Tensor&, const Ten
                           double, Tensor&, Tensor&, Tensor&, Tensor&, const std::optional<Tensor>&) {}
 void filter_depth_maps_out_meta(const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, double, double, int64_t, Tensor&,
                                 Tensor&, Tensor&, Tensor&) {}
+void sgm_aggregate_out_meta(const Tensor&, const Tensor&, double, double, double, int64_t, Tensor&, Tensor&, Tensor&,
+                            const std::optional<Tensor>&) {}
 void tsdf_integrate_out_meta(Tensor&, Tensor&, const std::optional<Tensor>&, const Tensor&, const std::optional<Tensor>&, const Tensor&,
                              const Tensor&, const Tensor&, double, double, double, double, double, Tensor&) {}
 void tsdf_extract_mesh_out_meta(const Tensor&, const Tensor&, const std::optional<Tensor>&, double, double, double, double, int64_t, Tensor&,
@@ -2246,6 +2308,8 @@ TORCH_LIBRARY_IMPL(sfm_hip, Meta, m) {
     m.impl("plane_sweep_", &plane_sweep_out_meta);
     m.impl("filter_depth_maps", &filter_depth_maps_meta);
     m.impl("filter_depth_maps_", &filter_depth_maps_out_meta);
+    m.impl("sgm_aggregate", &sgm_aggregate_meta);
+    m.impl("sgm_aggregate_", &sgm_aggregate_out_meta);
     m.impl("tsdf_integrate", &tsdf_integrate_meta);
     m.impl("tsdf_integrate_", &tsdf_integrate_out_meta);
     m.impl("tsdf_extract_mesh", &tsdf_extract_mesh_meta);

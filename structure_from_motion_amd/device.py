@@ -1680,6 +1680,43 @@ def filter_depth_maps(depth: torch.Tensor, K: torch.Tensor, poses: torch.Tensor,
 
 
 # ------------------------------------------------------------------------------------------------------
+# Semi-global smoothing of the plane-sweep cost volume (csrc/sfm_sgm.hip): volume f64 [R,D,H,W] and depths f64 [R,D]
+# on the device, as ``sfm_plane_sweep`` writes and reads them
+# ------------------------------------------------------------------------------------------------------
+class SgmWorkspace:
+    """Pre-allocated device buffers of ``sfm_sgm_aggregate`` for R reference views of H x W pixels and D depth hypotheses each
+    (20 bytes per pixel, and 8 D more with the aggregated volume; without it the call takes as much from the caching allocator
+    for the time it runs).  ``run`` fills them; nothing is read back until the caller asks."""
+
+    def __init__(self, refs: int, height: int, width: int, depths: int, device=None, aggregated: bool = False):
+        dev = device or require_gpu()
+        self.refs, self.height, self.width, self.depths = refs, height, width, depths
+        self.depth = torch.empty((refs, height, width), dtype=F64, device=dev)
+        self.index = torch.empty((refs, height, width), dtype=torch.int32, device=dev)
+        self.cost = torch.empty((refs, height, width), dtype=F64, device=dev)
+        self.aggregated = torch.empty((refs, depths, height, width), dtype=F64, device=dev) if aggregated else None
+
+    def buffers(self):
+        """The output tensors in the order of the ``sgm_aggregate_`` op (``aggregated`` may be None)."""
+        return (self.depth, self.index, self.cost, self.aggregated)
+
+    def run(self, volume: torch.Tensor, depths: torch.Tensor, p1: float = 0.1, p2: float = 0.8, invalid_cost: float = 1.0,
+            paths: int = 8) -> None:
+        """One ``sfm_sgm_aggregate`` call (the ``sgm_aggregate_`` op), enqueue-only: volume f64 [R,D,H,W], depths f64 [R,D]."""
+        ops.load().sgm_aggregate_(volume, depths, float(p1), float(p2), float(invalid_cost), int(paths), *self.buffers())
+
+
+def sgm_aggregate(volume: torch.Tensor, depths: torch.Tensor, p1: float = 0.1, p2: float = 0.8, invalid_cost: float = 1.0,
+                  paths: int = 8, aggregated: bool = False, workspace: Optional[SgmWorkspace] = None) -> SgmWorkspace:
+    """One ``sfm_sgm_aggregate`` call, enqueue-only -> the ``SgmWorkspace`` that holds its results (``workspace``, or a new one of
+    the volume's shape)."""
+    R, D, H, W = volume.shape
+    ws = workspace or SgmWorkspace(R, H, W, D, volume.device, aggregated=aggregated)
+    ws.run(volume, depths, p1, p2, invalid_cost, paths)
+    return ws
+
+
+# ------------------------------------------------------------------------------------------------------
 # Fusion of depth maps into a TSDF volume and its mesh (csrc/sfm_tsdf.hip, DESIGN.md §6aj): the state sum f64 [nz,ny,nx], count
 # int32 [nz,ny,nx] and grey_sum int32 [nz,ny,nx] or None on the device; origin a triple of floats
 # ------------------------------------------------------------------------------------------------------

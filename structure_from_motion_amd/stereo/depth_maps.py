@@ -1,5 +1,6 @@
 """Dense depth maps from posed images: plane-sweep stereo for every reference view in one device call per chunk, the
-forward-backward consistency filter across the maps, and the fused point cloud (csrc/sfm_plane_sweep.hip).
+forward-backward consistency filter across the maps, and the fused point cloud (csrc/sfm_plane_sweep.hip); the
+semi-global smoothing of the sweep's cost volume (csrc/sfm_sgm.hip; tests/sgm_oracle.py is its definition).
 
 The device results are defined as a fixed sequence of float64 operations (tests/plane_sweep_oracle.py is the same sequence in
 NumPy): a call is reproducible bit for bit, and how the references are split into device calls never changes a result.  The
@@ -14,6 +15,7 @@ import numpy as np
 from ..epipolar.view_graph import chunk_bounds
 
 MAX_SOURCES, MAX_DEPTHS, MAX_RADIUS = 8, 4096, 5
+MAX_SGM_DEPTHS, SGM_PATHS = 256, (4, 8)   # what sfm_sgm_aggregate accepts
 
 
 @dataclass
@@ -102,8 +104,73 @@ def _refs_and_sources(refs, sources, views: int):
     return np.ascontiguousarray(refs, dtype=np.int32), np.ascontiguousarray(sources, dtype=np.int32)
 
 
+def _penalties(p1, p2, invalid_cost=1.0, paths=8):
+    """The scalars of ``sfm_sgm_aggregate`` as it accepts them: finite, 0 <= p1 <= p2, paths 4 or 8."""
+    try:
+        p1, p2, invalid_cost = float(p1), float(p2), float(invalid_cost)
+    except (TypeError, ValueError):
+        raise ValueError(f"p1, p2 and invalid_cost must be numbers, got {p1!r}, {p2!r} and {invalid_cost!r}") from None
+    if not (np.isfinite(p1) and np.isfinite(p2) and np.isfinite(invalid_cost) and 0.0 <= p1 <= p2):
+        raise ValueError(f"need finite p1, p2 and invalid_cost with 0 <= p1 <= p2, got {p1!r}, {p2!r} and {invalid_cost!r}")
+    if isinstance(paths, bool) or not isinstance(paths, (int, np.integer)) or int(paths) not in SGM_PATHS:
+        raise ValueError(f"paths must be 4 or 8, got {paths!r}")
+    return p1, p2, invalid_cost, int(paths)
+
+
+def regularize_depth_maps(depth_maps_or_volume, depths, p1: float = 0.1, p2: float = 0.8, invalid_cost: float = 1.0, paths: int = 8,
+                          return_aggregated: bool = False, max_refs_per_call: int = 16) -> DepthMaps:
+    """Depth maps from a cost volume smoothed by semi-global aggregation, all references of a chunk in one device call.
+
+    ``depth_maps_or_volume``: a ``DepthMaps`` computed with ``return_volume=True``, or a (R, D, H, W) array, NaN where a
+    hypothesis has no cost; ``depths``: the (R, D) or (D,) hypotheses the volume was swept with, D <= 256.  Along each of ``paths``
+    (4 or 8) scanline directions a hypothesis pays its own cost (``invalid_cost`` where it has none) and the cheapest way to
+    reach it from the pixel before: for nothing from the same hypothesis, for ``p1`` from a neighbouring one, for ``p2`` from any.
+    The sums over the directions replace the costs: ``index`` is the hypothesis of lowest sum among those that have a cost and
+    a valid depth, ``cost`` that sum, ``depth`` its depth after the sweep's parabola step on the sums, and ``volume`` the sums
+    with ``return_aggregated`` (else None).  Every argument is checked before any device work (``ValueError``); how the
+    references are split into calls of at most ``max_refs_per_call`` never changes a result."""
+    refs = images = None
+    if isinstance(depth_maps_or_volume, DepthMaps):
+        if depth_maps_or_volume.volume is None:
+            raise ValueError("regularize_depth_maps needs the cost volume: compute_depth_maps(..., return_volume=True)")
+        volume, refs, images = depth_maps_or_volume.volume, depth_maps_or_volume.refs, depth_maps_or_volume.images
+    else:
+        volume = depth_maps_or_volume
+    volume = np.asarray(volume, dtype=np.float64)
+    if volume.ndim != 4 or not 1 <= volume.shape[1] <= MAX_SGM_DEPTHS or volume.shape[2] < 1 or volume.shape[3] < 1 or \
+            volume.shape[2] * volume.shape[3] >= 2**31:
+        raise ValueError(f"the volume must be (R, D, H, W) with 1 <= D <= {MAX_SGM_DEPTHS} and 1 <= H W < 2^31, got shape {volume.shape}")
+    R, D, H, W = volume.shape
+    depths = np.asarray(depths, dtype=np.float64)
+    if depths.ndim == 1:
+        depths = np.broadcast_to(depths, (R, len(depths)))
+    if depths.shape != (R, D):
+        raise ValueError(f"depths must have shape ({R}, {D}) or ({D},), got {depths.shape}")
+    p1, p2, invalid_cost, paths = _penalties(p1, p2, invalid_cost, paths)
+    chunks = chunk_bounds(R, 1, _integer(max_refs_per_call, "max_refs_per_call", 1))
+    if refs is None:
+        refs, images = np.arange(R, dtype=np.int32), np.zeros((R, H, W), dtype=np.uint8)
+    if R == 0:
+        return DepthMaps(np.zeros((0, H, W)), np.zeros((0, H, W), np.int32), np.zeros((0, H, W)), refs,
+                         np.zeros((0, D, H, W)) if return_aggregated else None, images)
+    from .. import device
+
+    dev = device.require_gpu()
+    depths_dev = device.to_device(np.ascontiguousarray(depths))
+    parts = []
+    for r0, r1 in chunks:
+        ws = device.SgmWorkspace(r1 - r0, H, W, D, dev, aggregated=bool(return_aggregated))
+        ws.run(device.to_device(np.ascontiguousarray(volume[r0:r1])), depths_dev[r0:r1], p1, p2, invalid_cost, paths)
+        parts.append(ws)
+    return DepthMaps(depth=np.concatenate([ws.depth.cpu().numpy() for ws in parts]),
+                     index=np.concatenate([ws.index.cpu().numpy() for ws in parts]),
+                     cost=np.concatenate([ws.cost.cpu().numpy() for ws in parts]), refs=refs,
+                     volume=np.concatenate([ws.aggregated.cpu().numpy() for ws in parts]) if return_aggregated else None, images=images)
+
+
 def compute_depth_maps(images, K, poses, depths, sources=None, refs=None, radius: int = 3, top_k: int = 0, min_sources: int = 1,
-                       min_variance: float = 1.0, return_volume: bool = False, max_refs_per_call: int = 64) -> DepthMaps:
+                       min_variance: float = 1.0, return_volume: bool = False, max_refs_per_call: int = 64,
+                       smoothness=None) -> DepthMaps:
     """One depth map per reference view by plane-sweep stereo, all references of a chunk in one device call.
 
     ``images``: (V, H, W) uint8 grey, all of one size; ``K``: the shared upper-triangular camera matrix; ``poses``: (V, 12) world
@@ -113,6 +180,10 @@ def compute_depth_maps(images, K, poses, depths, sources=None, refs=None, radius
     source warped through the plane's homography; a score is valid when both windows have a variance of at least
     ``min_variance`` grey levels squared; the cost of a hypothesis is the mean of its ``top_k`` lowest valid scores (0: all) and
     needs ``min_sources`` of them.  The winner of a pixel is refined by a parabola through its neighbours, in inverse depth.
+
+    ``smoothness``: None, or the penalties ``(p1, p2)`` of ``regularize_depth_maps``: each chunk's cost volume is then smoothed
+    on the device (8 paths, invalid cost 1) before the winners are taken, D <= 256; ``depth``, ``index`` and ``cost`` are those
+    of ``regularize_depth_maps`` and ``volume`` stays the sweep's.
 
     Every argument is checked before any device work (``ValueError``).  Images go up in one upload; the references are split
     into calls of at most ``max_refs_per_call``, which never changes a result."""
@@ -138,6 +209,14 @@ def compute_depth_maps(images, K, poses, depths, sources=None, refs=None, radius
     min_sources = _integer(min_sources, "min_sources", 1)
     min_variance = _bound(min_variance, "min_variance")
     chunks = chunk_bounds(R, 1, _integer(max_refs_per_call, "max_refs_per_call", 1))
+    if smoothness is not None:
+        try:
+            p1, p2 = smoothness
+        except (TypeError, ValueError):
+            raise ValueError(f"smoothness must be None or the two penalties (p1, p2), got {smoothness!r}") from None
+        p1, p2, invalid_cost, paths = _penalties(p1, p2)
+        if D > MAX_SGM_DEPTHS:
+            raise ValueError(f"smoothness needs at most {MAX_SGM_DEPTHS} depth hypotheses, got {D}")
     if R == 0:
         return DepthMaps(np.zeros((0, H, W)), np.zeros((0, H, W), np.int32), np.zeros((0, H, W)), refs,
                          np.zeros((0, D, H, W)) if return_volume else None, images)
@@ -150,18 +229,22 @@ def compute_depth_maps(images, K, poses, depths, sources=None, refs=None, radius
     K_dev, poses_dev = device.to_device(K.reshape(9)), device.to_device(poses)
     refs_dev, sources_dev = device.to_device(refs, torch.int32), device.to_device(sources, torch.int32)
     depths_dev = device.to_device(depths)
-    parts = []
+    parts, maps = [], []
     for r0, r1 in chunks:
-        ws = device.PlaneSweepWorkspace(r1 - r0, H, W, D, dev, volume=bool(return_volume))
+        ws = device.PlaneSweepWorkspace(r1 - r0, H, W, D, dev, volume=bool(return_volume) or smoothness is not None)
         ws.run(images_dev, K_dev, poses_dev, refs_dev[r0:r1], sources_dev[r0:r1], depths_dev[r0:r1], radius, top_k, min_sources,
                min_variance)
         parts.append(ws)
+        # the smoothed maps of a chunk, from its volume where it lies; without smoothness the sweep's own
+        maps.append(ws if smoothness is None else device.sgm_aggregate(ws.volume, depths_dev[r0:r1], p1, p2, invalid_cost, paths))
+        if smoothness is not None and not return_volume:
+            ws.volume = None
     code = np.concatenate([device.read_sweep_status(ws.status) for ws in parts])
     if np.any(code != device.SWEEP_OK):
         raise RuntimeError("compute_depth_maps: the device refused a reference index (SFM_SWEEP_BAD_REFERENCE)")
-    return DepthMaps(depth=np.concatenate([ws.depth.cpu().numpy() for ws in parts]),
-                     index=np.concatenate([ws.index.cpu().numpy() for ws in parts]),
-                     cost=np.concatenate([ws.cost.cpu().numpy() for ws in parts]), refs=refs,
+    return DepthMaps(depth=np.concatenate([ws.depth.cpu().numpy() for ws in maps]),
+                     index=np.concatenate([ws.index.cpu().numpy() for ws in maps]),
+                     cost=np.concatenate([ws.cost.cpu().numpy() for ws in maps]), refs=refs,
                      volume=np.concatenate([ws.volume.cpu().numpy() for ws in parts]) if return_volume else None, images=images)
 
 
