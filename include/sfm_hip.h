@@ -1471,6 +1471,58 @@ int sfm_detect_keypoints(const sfm_keypoint_plane* plane_table, int64_t planes, 
                          uint16_t* kept, int64_t capacity, int32_t* counter, sfm_keypoint_candidate* candidates, uint8_t* desc,
                          uint8_t* ok, uint8_t* angle_bin, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Bytes of workspace sfm_build_pyramid needs for a table of `planes` planes; -1 for a negative count or more than 65535. */
+int64_t sfm_build_pyramid_workspace_bytes(int64_t planes);
+
+/* (added within ABI 15) The pyramid of sfm_detect_keypoints alone: the same table checks, the table's upload and the same
+ * launches, so the pool holds the bytes sfm_detect_keypoints leaves there.  The caller has put every image into its level-0
+ * plane; the call fills the planes above.  plane_table, planes, images, pool, pool_bytes: as sfm_detect_keypoints (the quotas
+ * are checked and not used); workspace: dev, 16-byte aligned, at least sfm_build_pyramid_workspace_bytes(planes).
+ * planes == 0 is a no-op.  SFM_EINVAL before the first launch for a negative or too large size, a null or misaligned pointer,
+ * a workspace too small or a table that breaks one of the rules of sfm_detect_keypoints. */
+int sfm_build_pyramid(const sfm_keypoint_plane* plane_table, int64_t planes, int64_t images, uint8_t* pool, int64_t pool_bytes,
+                      void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---- sub-pixel refinement of track observations (definition: tests/track_refine_oracle.py) ---- */
+
+/* (added within ABI 15) The statuses of sfm_refine_observations.  Every status but OK returns the integer input position and warp0. */
+#define SFM_REFINE_OK 0              /* refined: xy and warp are the final state */
+#define SFM_REFINE_REFERENCE 1       /* reference == own index or -1: nothing to align with */
+#define SFM_REFINE_BAD_INDEX 2       /* a reference outside [0, M), a plane outside the table or a pixel outside its plane */
+#define SFM_REFINE_OUTSIDE 3         /* the template window or a warped sample leaves its plane */
+#define SFM_REFINE_FLAT 4            /* a window of constant grey value */
+#define SFM_REFINE_SINGULAR 5        /* a pivot of the 6 x 6 system is not positive, or its solution is not finite */
+#define SFM_REFINE_DIVERGED 6        /* the position moved further than max_shift from the input */
+#define SFM_REFINE_LOW_CORRELATION 7 /* the final correlation is below min_correlation */
+
+/* Bytes of workspace sfm_refine_observations needs for a table of `planes` planes; -1 for a negative count or more than 65535. */
+int64_t sfm_refine_observations_workspace_bytes(int64_t planes);
+
+/* (added within ABI 15) Aligns every observation o < observations with its reference observation q = reference[o] by
+ * Gauss-Newton on six affine parameters, maximising the normalised correlation between the (2 radius + 1)^2 window around the
+ * integer pixel (x[q], y[q]) on plane[q] and the window warped to plane[o]: sample (dx, dy) lies at u = t0 + (A00 dx + A01 dy),
+ * v = t1 + (A10 dx + A11 dy), starting from t = (x[o], y[o]), A = warp0[o] = (A00, A01, A10, A11).  Every sample of every
+ * iteration needs 1 <= u < W - 2 and 1 <= v < H - 2.  With I the bilinear samples, gx = 0.5 (I(u+1, v) - I(u-1, v)), gy likewise,
+ * I0 = I - mean(I), s = sqrt(sum I0^2) and T the template normalised the same way: res = T - I0 / s, the Jacobian rows
+ * (gx, gy, gx dx, gx dy, gy dx, gy dy) / s less their column means, H = sum J J^T + 1e-9 trace(H) on the diagonal, H delta =
+ * sum J res by Cholesky, t += delta[0..1], A += delta[2..5]; the loop ends after max_iterations solves or when
+ * delta0^2 + delta1^2 < min_step^2.  correlation = sum T (I0 / s) at the final state; at or above min_correlation the status is
+ * SFM_REFINE_OK and xy, warp are the final t, A.  All arithmetic is fp64 in the order of the definition, which the device
+ * equals byte for byte; the order of every window sum is stated there.  Every element of the five outputs is written;
+ * correlation is NaN unless the final state was sampled; iterations counts the solves done.
+ * plane_table, planes, images, pool, pool_bytes: as sfm_detect_keypoints after it (or sfm_build_pyramid) filled the pool;
+ * plane, x, y, reference: dev int32 [observations]; warp0: dev f64 [observations,4]; radius 2..7; max_iterations 1..50;
+ * min_step, max_shift > 0 and finite; xy: dev f64 [observations,2], level pixels; warp: dev f64 [observations,4]; correlation:
+ * dev f64 [observations]; iterations, status: dev int32 [observations]; workspace: dev, 16-byte aligned, at least
+ * sfm_refine_observations_workspace_bytes(planes).  observations == 0 is a no-op.  A wrong index is a status, never a fault.
+ * SFM_EINVAL before the first launch for a negative or too large size, a scalar out of range, a null or misaligned pointer, a
+ * workspace too small or a table that breaks one of the rules of sfm_detect_keypoints. */
+int sfm_refine_observations(const sfm_keypoint_plane* plane_table, int64_t planes, int64_t images, const uint8_t* pool,
+                            int64_t pool_bytes, int64_t observations, const int32_t* plane, const int32_t* x, const int32_t* y,
+                            const int32_t* reference, const double* warp0, int radius, int max_iterations, double min_step,
+                            double max_shift, double min_correlation, double* xy, double* warp, double* correlation,
+                            int32_t* iterations, int32_t* status, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- Harris corner detector stencils (reference lib/harris/harris_detector.py, lib/common/correlate.py) ---- */
 
 /* Zero-'same' cross-correlation with an odd square kernel (correlate.py:4-39).  image, out: dev f64

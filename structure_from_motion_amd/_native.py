@@ -206,6 +206,9 @@ SIGNATURES = {
     "sfm_build_tracks": [_I64, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P],
     "sfm_average_rotations": [_I64, _I64, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P],
     "sfm_detect_keypoints": [_P, _I64, _I64, _P, _I64, C.c_int, _P, _P, C.c_int, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _I64, _P],
+    "sfm_build_pyramid": [_P, _I64, _I64, _P, _I64, _P, _I64, _P],
+    "sfm_refine_observations": [_P, _I64, _I64, _P, _I64, _I64, _P, _P, _P, _P, _P, C.c_int, C.c_int, _D, _D, _D, _P, _P, _P, _P, _P,
+                                _P, _I64, _P],
     "sfm_average_translations": [_I64, _I64, _P, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P],
 }
 OTHER_SYMBOLS = ["sfm_last_error", "sfm_abi_version", "sfm_score_workspace_bytes", "sfm_score_workspace_bytes_ex",
@@ -217,7 +220,7 @@ OTHER_SYMBOLS = ["sfm_last_error", "sfm_abi_version", "sfm_score_workspace_bytes
                  "sfm_bundle_calibrated_workspace_bytes", "sfm_tracks_robust_workspace_bytes",
                  "sfm_similarity_fit_workspace_bytes", "sfm_similarity_refine_workspace_bytes",
                  "sfm_align_models_workspace_bytes", "sfm_plane_sweep_workspace_bytes", "sfm_tsdf_mesh_workspace_bytes",
-                 "sfm_sgm_workspace_bytes"]
+                 "sfm_sgm_workspace_bytes", "sfm_build_pyramid_workspace_bytes", "sfm_refine_observations_workspace_bytes"]
 
 # the losses of both bundle adjusters, in the order of their SFM_BUNDLE_LOSS_* codes (include/sfm_hip.h)
 BUNDLE_LOSSES = ("squared", "huber", "cauchy")
@@ -350,6 +353,10 @@ class MatchPairsOptions(C.Structure):
                 ("ratio", C.c_double)]
 
 
+# the statuses of sfm_refine_observations, in the order of their SFM_REFINE_* codes (include/sfm_hip.h)
+REFINE_STATUS = ("ok", "reference", "bad_index", "outside", "flat", "singular", "diverged", "low_correlation")
+
+
 class KeypointPlane(C.Structure):
     """sfm_keypoint_plane"""
     _fields_ = [("image", C.c_int32), ("level", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("offset", C.c_int64),
@@ -433,6 +440,10 @@ def load() -> C.CDLL:
     lib.sfm_sgm_workspace_bytes.argtypes = [_I64] * 4 + [C.c_int]
     lib.sfm_detect_keypoints_workspace_bytes.restype = C.c_int64
     lib.sfm_detect_keypoints_workspace_bytes.argtypes = [_I64]
+    lib.sfm_build_pyramid_workspace_bytes.restype = C.c_int64
+    lib.sfm_build_pyramid_workspace_bytes.argtypes = [_I64]
+    lib.sfm_refine_observations_workspace_bytes.restype = C.c_int64
+    lib.sfm_refine_observations_workspace_bytes.argtypes = [_I64]
     if lib.sfm_abi_version() != ABI_VERSION:
         raise NativeLibraryError(
             f"libsfm_hip.so ABI {lib.sfm_abi_version()} != expected {ABI_VERSION}; rebuild it")

@@ -8,7 +8,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libsfm_hip.so")
-SOURCES = ["sfm_kernels.hip", "sfm_score.hip", "sfm_refine.hip", "sfm_pose.hip", "sfm_shard.hip", "sfm_match.hip", "sfm_brief.hip", "sfm_match_pairs.hip", "sfm_harris.hip", "sfm_pnp.hip", "sfm_five_point.hip", "sfm_homography.hip", "sfm_similarity.hip", "sfm_align_models.hip", "sfm_plane_sweep.hip", "sfm_tsdf.hip", "sfm_sgm.hip", "sfm_view_graph.hip", "sfm_view_graph_pose.hip", "sfm_view_graph_refine.hip", "sfm_pnp_refine.hip", "sfm_register_views.hip", "sfm_bundle.hip", "sfm_bundle_pcg.hip", "sfm_tracks.hip", "sfm_tracks_robust.hip", "sfm_track_build.hip", "sfm_rotation_averaging.hip", "sfm_translation_averaging.hip", "sfm_keypoints.hip",
+SOURCES = ["sfm_kernels.hip", "sfm_score.hip", "sfm_refine.hip", "sfm_pose.hip", "sfm_shard.hip", "sfm_match.hip", "sfm_brief.hip", "sfm_match_pairs.hip", "sfm_harris.hip", "sfm_pnp.hip", "sfm_five_point.hip", "sfm_homography.hip", "sfm_similarity.hip", "sfm_align_models.hip", "sfm_plane_sweep.hip", "sfm_tsdf.hip", "sfm_sgm.hip", "sfm_view_graph.hip", "sfm_view_graph_pose.hip", "sfm_view_graph_refine.hip", "sfm_pnp_refine.hip", "sfm_register_views.hip", "sfm_bundle.hip", "sfm_bundle_pcg.hip", "sfm_tracks.hip", "sfm_tracks_robust.hip", "sfm_track_build.hip", "sfm_rotation_averaging.hip", "sfm_translation_averaging.hip", "sfm_keypoints.hip", "sfm_track_refine.hip",
            "pyshuffle.cpp"]
 # every header a translation unit can include: all of csrc/*.h plus the public C ABI header
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", "sfm_hip.h")]

@@ -24,31 +24,26 @@
 
 #include "sfm_brief_device.h"
 #include "sfm_common.h"
+#include "sfm_keypoint_planes.h"
 
 namespace {
 
 using sfmhost::check_launch;
 using sfmhost::fail;
 
-constexpr int kTileW = 64, kTileH = 16;             // pixels of a plane one block owns
+using sfmplanes::CheckedTable;
+using sfmplanes::DevPlane;                          // the plane table as the kernels read it (sfm_keypoint_planes.h)
+using sfmplanes::kMaxPlanes;
+using sfmplanes::kTileH;
+using sfmplanes::kTileW;
+
 constexpr int kThreads = 256;                       // lane x of the tile, rows y, y + 4, y + 8, y + 12
 constexpr int kRowsPerThread = kTileW * kTileH / kThreads;
 constexpr int kRowStep = kThreads / kTileW;
 constexpr int kRing = 3;                            // radius of the FAST circle
 constexpr int kBorder = 15;                         // a tested centre keeps a whole 31 x 31 BRIEF patch
 constexpr int kBins = 4096;                         // scores are at most 16 * 254 = 4064
-constexpr int kMaxLevel = 11, kMinSide = 48, kMaxPlanes = 65535;
 static_assert(kTileW == kWave && kThreads % kTileW == 0, "a wave owns one row of the tile");
-
-// the plane table as the kernels read it (built by the host from sfm_keypoint_plane)
-struct DevPlane {
-    int64_t offset;                                 // first pixel in the pool, and first entry in both score maps
-    int32_t height, width;
-    int32_t source;                                 // the plane of the same image one level down, -1 for level 0
-    int32_t tiles_x;
-    int32_t tile_start;                             // tiles of the planes before this one
-    int32_t quota;
-};
 
 // The plane whose tiles hold global tile `tile`: planes[n].tile_start is the total.
 __device__ __forceinline__ int plane_of_tile(const DevPlane* __restrict__ planes, int n, int tile) {
@@ -285,9 +280,52 @@ Layout carve(void* workspace, int64_t planes) {
     return l;
 }
 
+// What sfm_detect_keypoints and sfm_build_pyramid share behind their own size and pointer checks: the caller's table against
+// the rules of the header (sfmplanes::check_table, SFM_EINVAL under the caller's name `fn` before anything is enqueued), the
+// table's upload (it is pageable host memory: the copy has left it when the call returns) and one pyramid_level_kernel launch
+// per level above 0, over the images that have it.
+int build_pyramid(const char* fn, const sfm_keypoint_plane* plane_table, int64_t planes, int64_t images, uint8_t* pool,
+                  int64_t pool_bytes, DevPlane* planes_dev, hipStream_t st, CheckedTable& checked) {
+    if (sfmplanes::check_table(fn, plane_table, planes, images, pool_bytes, checked) != SFM_OK) return SFM_EINVAL;
+    const std::vector<DevPlane>& table = checked.table;
+    if (hipMemcpyAsync(planes_dev, table.data(), sizeof(DevPlane) * table.size(), hipMemcpyHostToDevice, st) != hipSuccess)
+        return check_launch(fn);
+    const int n = (int)planes;
+    for (size_t l = 1; l + 1 < checked.level_first.size(); ++l) {
+        const int first = table[(size_t)checked.level_first[l]].tile_start, last = table[(size_t)checked.level_first[l + 1]].tile_start;
+        hipLaunchKernelGGL(pyramid_level_kernel, dim3((unsigned)(last - first)), dim3(kThreads), 0, st, planes_dev, n, first, pool);
+    }
+    return SFM_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int64_t sfm_build_pyramid_workspace_bytes(int64_t planes) {
+    if (planes < 0 || planes > kMaxPlanes) return -1;
+    sfmhost::Carver c{0, 0};
+    c.take<DevPlane>(planes + 1);
+    return c.at;
+}
+
+int sfm_build_pyramid(const sfm_keypoint_plane* plane_table, int64_t planes, int64_t images, uint8_t* pool, int64_t pool_bytes,
+                      void* workspace, int64_t workspace_bytes, void* stream) {
+    if (planes < 0 || images < 0 || pool_bytes < 0 || workspace_bytes < 0) return fail(SFM_EINVAL, "sfm_build_pyramid: negative size");
+    if (planes > kMaxPlanes) return fail(SFM_EINVAL, "sfm_build_pyramid: more than 65535 planes");
+    if (pool_bytes > 0x7FFFFFFFLL || images > 0x7FFFFFFFLL)
+        return fail(SFM_EINVAL, "sfm_build_pyramid: the pool and the images must stay below 2^31");
+    if (planes == 0) return SFM_OK;
+    if (!plane_table || !pool || !workspace) return fail(SFM_EINVAL, "sfm_build_pyramid: null pointer");
+    if ((reinterpret_cast<uintptr_t>(workspace) & 15u) != 0) return fail(SFM_EINVAL, "sfm_build_pyramid: workspace must be 16-byte aligned");
+    if (workspace_bytes < sfm_build_pyramid_workspace_bytes(planes))
+        return fail(SFM_EINVAL, "sfm_build_pyramid: workspace smaller than sfm_build_pyramid_workspace_bytes(planes)");
+    CheckedTable checked;
+    const int rc = build_pyramid("sfm_build_pyramid", plane_table, planes, images, pool, pool_bytes, reinterpret_cast<DevPlane*>(workspace),
+                                 (hipStream_t)stream, checked);
+    if (rc != SFM_OK) return rc;
+    return check_launch("sfm_build_pyramid");
+}
 
 int64_t sfm_detect_keypoints_workspace_bytes(int64_t planes) {
     if (planes < 0 || planes > kMaxPlanes) return -1;
@@ -325,69 +363,15 @@ int sfm_detect_keypoints(const sfm_keypoint_plane* plane_table, int64_t planes, 
     const Layout layout = carve(workspace, planes);
     if (workspace_bytes < layout.bytes)
         return fail(SFM_EINVAL, "sfm_detect_keypoints: workspace smaller than sfm_detect_keypoints_workspace_bytes(planes)");
-    // the table: levels ascending, every plane above level 0 four fifths of its image's plane below, planes apart in the pool
-    std::vector<DevPlane> table((size_t)planes + 1);
-    std::vector<int32_t> below((size_t)images, -1), here((size_t)images, -1);   // per image: its plane one level down / at this level
-    int64_t end = 0, tiles = 0;
-    int level = 0;
-    std::vector<int64_t> level_first;               // first plane of every level, and the end
-    level_first.push_back(0);
-    for (int64_t p = 0; p < planes; ++p) {
-        const sfm_keypoint_plane& in = plane_table[p];
-        if (in.image < 0 || in.image >= images) return fail(SFM_EINVAL, "sfm_detect_keypoints: a plane names no image");
-        if (in.level < level || in.level > level + 1 || in.level > kMaxLevel)
-            return fail(SFM_EINVAL, "sfm_detect_keypoints: planes must come in ascending levels 0..11 without a gap");
-        if (in.level > level) {
-            level = in.level;
-            below.swap(here);
-            std::fill(here.begin(), here.end(), -1);
-            level_first.push_back(p);
-        }
-        if (here[in.image] >= 0) return fail(SFM_EINVAL, "sfm_detect_keypoints: an image has two planes of one level");
-        if (in.height < 1 || in.width < 1) return fail(SFM_EINVAL, "sfm_detect_keypoints: an empty plane");
-        if (in.quota < 0 || in.reserved != 0) return fail(SFM_EINVAL, "sfm_detect_keypoints: a negative quota or reserved != 0");
-        int32_t source = -1;
-        if (in.level > 0) {
-            source = below[in.image];
-            if (source < 0) return fail(SFM_EINVAL, "sfm_detect_keypoints: a plane without the plane one level down");
-            const DevPlane& s = table[(size_t)source];
-            if (in.height != 4 * s.height / 5 || in.width != 4 * s.width / 5 || in.height < kMinSide || in.width < kMinSide)
-                return fail(SFM_EINVAL, "sfm_detect_keypoints: a level must be 4/5 of the one below and at least 48 x 48");
-        }
-        const int64_t size = (int64_t)in.height * in.width;
-        if (in.offset < end || in.offset > pool_bytes || size > pool_bytes - in.offset)
-            return fail(SFM_EINVAL, "sfm_detect_keypoints: planes must lie in the pool in table order without overlap");
-        end = in.offset + size;
-        here[in.image] = (int32_t)p;
-        DevPlane& out = table[(size_t)p];
-        out.offset = in.offset;
-        out.height = in.height;
-        out.width = in.width;
-        out.source = source;
-        out.tiles_x = (in.width + kTileW - 1) / kTileW;
-        out.tile_start = (int32_t)tiles;
-        out.quota = in.quota;
-        tiles += (int64_t)out.tiles_x * ((in.height + kTileH - 1) / kTileH);
-        if (tiles > 0x7FFFFFFFLL) return fail(SFM_EINVAL, "sfm_detect_keypoints: too many tiles for one launch");
-    }
-    level_first.push_back(planes);
-    DevPlane& total = table[(size_t)planes];
-    total = DevPlane{};
-    total.tile_start = (int32_t)tiles;
-    total.source = -1;
     SFM_REQUIRE_GRID("sfm_detect_keypoints", capacity, 1, kWave);
-
-    // the table is pageable host memory: the copy has left it when the call returns
-    if (hipMemcpyAsync(layout.planes, table.data(), sizeof(DevPlane) * table.size(), hipMemcpyHostToDevice, st) != hipSuccess)
-        return check_launch("sfm_detect_keypoints: table upload");
+    CheckedTable checked;
+    const int rc = build_pyramid("sfm_detect_keypoints", plane_table, planes, images, pool, pool_bytes, layout.planes, st, checked);
+    if (rc != SFM_OK) return rc;
+    const int64_t tiles = checked.tiles;
     if (hipMemsetAsync(layout.histogram, 0, sizeof(int32_t) * (size_t)planes * kBins, st) != hipSuccess ||
         hipMemsetAsync(counter, 0, sizeof(int32_t), st) != hipSuccess)
         return check_launch("sfm_detect_keypoints: memset");
     const int n = (int)planes;
-    for (size_t l = 1; l + 1 < level_first.size(); ++l) {
-        const int first = table[(size_t)level_first[l]].tile_start, last = table[(size_t)level_first[l + 1]].tile_start;
-        hipLaunchKernelGGL(pyramid_level_kernel, dim3((unsigned)(last - first)), dim3(kThreads), 0, st, layout.planes, n, first, pool);
-    }
     hipLaunchKernelGGL(fast_score_kernel, dim3((unsigned)tiles), dim3(kThreads), 0, st, layout.planes, n, pool, threshold, score);
     hipLaunchKernelGGL(suppress_kernel, dim3((unsigned)tiles), dim3(kThreads), 0, st, layout.planes, n, score, kept, layout.histogram);
     hipLaunchKernelGGL(cutoff_kernel, dim3((unsigned)planes), dim3(kThreads), 0, st, layout.planes, layout.histogram, layout.cutoff);

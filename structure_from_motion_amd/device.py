@@ -1200,6 +1200,48 @@ def detect_keypoints(table, planes: int, images: int, pool, threshold: int, offs
     return workspace
 
 
+def build_pyramid(table, planes: int, images: int, pool, workspace=None):
+    """The planes above level 0 of every image of ``table`` into ``pool`` (``sfm_build_pyramid``; ctypes like
+    ``detect_keypoints``, whose pyramid it is): the caller has put every image into its level-0 plane.  Returns the workspace it
+    used: ``workspace`` when that is large enough, else a new one.  No host synchronisation beyond the upload of the table."""
+    lib = _native.load()
+    need = int(lib.sfm_build_pyramid_workspace_bytes(int(planes)))
+    if need < 0:
+        raise ValueError("build_pyramid: at most 65535 planes per call")
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty((max(need, 1),), dtype=torch.uint8, device=pool.device)
+    check(lib.sfm_build_pyramid(table, int(planes), int(images), _ptr(pool), pool.numel(), _ptr(workspace), workspace.numel(),
+                                _stream()), "sfm_build_pyramid")
+    return workspace
+
+
+# the statuses of refine_observations (SFM_REFINE_* of include/sfm_hip.h)
+(REFINE_OK, REFINE_REFERENCE, REFINE_BAD_INDEX, REFINE_OUTSIDE, REFINE_FLAT, REFINE_SINGULAR, REFINE_DIVERGED,
+ REFINE_LOW_CORRELATION) = range(8)
+
+
+def refine_observations(table, planes: int, images: int, pool, plane, x, y, reference, warp0, radius: int, max_iterations: int,
+                        min_step: float, max_shift: float, min_correlation: float, xy, warp, correlation, iterations, status,
+                        workspace=None):
+    """Sub-pixel alignment of every observation with its reference observation (``sfm_refine_observations``, DESIGN.md section
+    6al; ctypes like ``detect_keypoints``).  ``table`` / ``pool``: the plane table and the filled pixel pool; ``plane``, ``x``,
+    ``y``, ``reference`` int32 [M]; ``warp0`` float64 [M, 4]; outputs ``xy`` float64 [M, 2] (level pixels), ``warp`` float64
+    [M, 4], ``correlation`` float64 [M], ``iterations`` / ``status`` int32 [M].  Returns the workspace it used.  No host
+    synchronisation beyond the upload of the table."""
+    lib = _native.load()
+    need = int(lib.sfm_refine_observations_workspace_bytes(int(planes)))
+    if need < 0:
+        raise ValueError("refine_observations: at most 65535 planes per call")
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty((max(need, 1),), dtype=torch.uint8, device=pool.device)
+    check(lib.sfm_refine_observations(table, int(planes), int(images), _ptr(pool), pool.numel(), int(plane.numel()), _ptr(plane),
+                                      _ptr(x), _ptr(y), _ptr(reference), _ptr(warp0), int(radius), int(max_iterations),
+                                      float(min_step), float(max_shift), float(min_correlation), _ptr(xy), _ptr(warp),
+                                      _ptr(correlation), _ptr(iterations), _ptr(status), _ptr(workspace), workspace.numel(),
+                                      _stream()), "sfm_refine_observations")
+    return workspace
+
+
 class PnPWorkspace(_PassWorkspace):
     """Pre-allocated device buffers of a PnP pass for B views x H hypotheses x N 2D-3D pairs (as RansacWorkspace)."""
 
