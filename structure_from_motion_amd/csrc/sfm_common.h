@@ -51,6 +51,15 @@ inline unsigned grid_stride(int64_t work, int64_t block, int64_t cap) {
     return (unsigned)g;
 }
 
+// `bytes` a power of two; a null pointer is aligned
+inline bool aligned_to(const void* p, uintptr_t bytes) { return ((uintptr_t)p & (bytes - 1)) == 0; }
+
+// A stack of `views` image planes of height x width that kernels index with int32 coordinates and an int32 pixel within a plane.
+inline bool image_stack_ok(int64_t views, int64_t height, int64_t width) {
+    return views >= 1 && views <= 0x7FFFFFFF && height >= 1 && width >= 1 && height <= 0x7FFFFFFF && width <= 0x7FFFFFFF &&
+           height * width < ((int64_t)1 << 31);
+}
+
 // Bump allocation of a workspace in 256-byte aligned pieces from `base` (0: sizes only).
 struct Carver {
     uintptr_t base;

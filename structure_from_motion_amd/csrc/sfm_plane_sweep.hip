@@ -1,7 +1,8 @@
 // Plane-sweep depth maps of posed grey images and the forward-backward consistency filter across them.
 //
 // Every step of both is fp64 + - * / sqrt in a written order (the build has -ffp-contract=off), so a result is a matter of bytes:
-// tests/plane_sweep_oracle.py states the same sequence in NumPy.  Every 3-term product sum is (a0*b0 + a1*b1) + a2*b2.
+// tests/plane_sweep_oracle.py states the same sequence in NumPy.  The camera, the bilinear cell formula and the winner over the
+// depth hypotheses are those of sfm_dense.h, which the other dense translation units share.
 //
 // sfm_plane_sweep, 2 launches whatever the sizes, nothing read back:
 //   1. sweep_homography_kernel   one thread per (reference r, source slot s, depth d): G = K (Rrel + trel e3^T / z) K^-1 into the
@@ -13,7 +14,7 @@
 //                                256 (2 radius + 1)^2, and each thread forms the sums of b, b^2 and ab of its window from LDS: rows
 //                                left to right, then the row sums top to bottom.  The valid scores of a depth are kept sorted in
 //                                eight registers by insertion (equal scores add to the same bits in either order), the running
-//                                winner, the cost before it and the cost after it in registers as well.
+//                                winner, the cost before it and the cost after it (sfmdense::DepthWinner) in registers as well.
 // The LDS rows are 48 doubles apart: two rows of 16 threads then fall into disjoint halves of the 64 banks of an 8-byte read.
 // An invalid sample, sum, score or cost is a NaN on the way and in `volume`; nothing is indexed by a run-time value but LDS and
 // global memory, so no kernel uses scratch.
@@ -24,9 +25,12 @@
 #include <stdint.h>
 
 #include "sfm_common.h"
+#include "sfm_dense.h"
 
 namespace {
 
+using namespace sfmdense;   // dot3, Mat3, mul3, the camera, bilinear_cell, DepthWinner
+using sfmhost::aligned_to;
 using sfmhost::check_launch;
 using sfmhost::fail;
 using sfmhost::grid_fits;
@@ -40,32 +44,7 @@ constexpr int kMaxDepths = 4096;
 constexpr int kSetupBlock = 256;
 constexpr int kFilterBlock = 256;
 
-#define SFM_SWEEP_DEVICE __device__ __forceinline__
-
-SFM_SWEEP_DEVICE double dot3(double a0, double b0, double a1, double b1, double a2, double b2) { return (a0 * b0 + a1 * b1) + a2 * b2; }
-
-struct Mat3 {
-    double m[3][3];
-};
-
-SFM_SWEEP_DEVICE Mat3 mul3(const Mat3& A, const Mat3& B) {
-    Mat3 C;
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) C.m[i][j] = dot3(A.m[i][0], B.m[0][j], A.m[i][1], B.m[1][j], A.m[i][2], B.m[2][j]);
-    return C;
-}
-
-// K from its five entries, and its inverse in closed form
-SFM_SWEEP_DEVICE void camera_matrices(const double* __restrict__ K, Mat3& Km, Mat3& Ki) {
-    const double fx = K[0], sk = K[1], cx = K[2], fy = K[4], cy = K[5];
-    Km = Mat3{{{fx, sk, cx}, {0.0, fy, cy}, {0.0, 0.0, 1.0}}};
-    const double ff = fx * fy;
-    Ki = Mat3{{{1.0 / fx, -sk / ff, (sk * cy - cx * fy) / ff}, {0.0, 1.0 / fy, -cy / fy}, {0.0, 0.0, 1.0}}};
-}
-
-SFM_SWEEP_DEVICE bool slot_present(int32_t src, int32_t ref, int64_t views) { return src >= 0 && (int64_t)src < views && src != ref; }
+SFM_DEVICE bool slot_present(int32_t src, int32_t ref, int64_t views) { return src >= 0 && (int64_t)src < views && src != ref; }
 
 __global__ __launch_bounds__(kSetupBlock) void sweep_homography_kernel(const double* __restrict__ K, const double* __restrict__ poses,
                                                                        int64_t views, const int32_t* __restrict__ refs,
@@ -168,8 +147,7 @@ __global__ __launch_bounds__(kSweepBlock) void plane_sweep_kernel(const SweepArg
     const double va = n * saa - sa * sa;
     const bool va_ok = isfinite(va) && va >= a.gate;
 
-    int best = -1;
-    double best_cost = NAN, cost_before = NAN, cost_after = NAN, previous = NAN;
+    DepthWinner winner;
     for (int d = 0; d < D; ++d) {
         const double z = a.depths[r * D + d];
         double cost = NAN;
@@ -194,11 +172,7 @@ __global__ __launch_bounds__(kSweepBlock) void plane_sweep_kernel(const SweepArg
                             const double u = X * inv, v = Y * inv;
                             if (u >= 0.0 && u < (double)(W - 1) && v >= 0.0 && v < (double)(H - 1)) {
                                 const double xf = floor(u), yf = floor(v);
-                                const double fx = u - xf, fy = v - yf;
-                                const uint8_t* p = image + (int64_t)(int)yf * W + (int)xf;
-                                const double p00 = (double)p[0], p10 = (double)p[1], p01 = (double)p[W], p11 = (double)p[W + 1];
-                                const double top = p00 + fx * (p10 - p00), bot = p01 + fx * (p11 - p01);
-                                b = top + fy * (bot - top);
+                                b = bilinear_cell(image + (int64_t)(int)yf * W + (int)xf, W, u - xf, v - yf);
                             }
                         }
                     }
@@ -254,56 +228,12 @@ __global__ __launch_bounds__(kSweepBlock) void plane_sweep_kernel(const SweepArg
             }
         }
         if (a.volume && inside) a.volume[(r * D + d) * plane + (int64_t)py * W + px] = cost;
-        if (cost == cost && (best < 0 || cost < best_cost)) {
-            best = d;
-            best_cost = cost;
-            cost_before = previous;
-            cost_after = NAN;
-        } else if (d == best + 1 && best >= 0) {
-            cost_after = cost;
-        }
-        previous = cost;
+        winner.offer(d, cost);
     }
     if (!inside) return;
-    double depth = NAN;
-    if (best >= 0) {
-        const double zi = a.depths[r * D + best];
-        depth = zi;
-        if (best > 0 && best < D - 1 && cost_before == cost_before && cost_after == cost_after) {
-            const double den = (cost_before - best_cost) + (cost_after - best_cost);
-            if (den > 0.0) {
-                const double o = 0.5 * (cost_before - cost_after) / den;
-                const double zj = a.depths[r * D + (o > 0.0 ? best + 1 : best - 1)];
-                const double q = 1.0 / zi + fabs(o) * (1.0 / zj - 1.0 / zi);
-                depth = 1.0 / q;
-            }
-        }
-    }
-    a.depth[pixel] = depth;
-    a.cost[pixel] = best_cost;
-    a.index[pixel] = best;
-}
-
-// A pixel (x, y) of a view (pose P = R row-major, then t) at depth d in the world: R^T (d K^-1 (x, y, 1) - t).
-SFM_SWEEP_DEVICE void back_project(const Mat3& Ki, const double* __restrict__ P, double x, double y, double d, double* Xw) {
-    double e[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) e[i] = ((Ki.m[i][0] * x + Ki.m[i][1] * y) + Ki.m[i][2]) * d - P[9 + i];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) Xw[i] = dot3(P[i], e[0], P[3 + i], e[1], P[6 + i], e[2]);
-}
-
-// A world point in a view: its camera depth z and, for z whatever, the pixel (u, v) = K Y / (K Y)_2 with Y = R X + t.
-SFM_SWEEP_DEVICE void project(const Mat3& Km, const double* __restrict__ P, const double* Xw, double& u, double& v, double& z) {
-    double Y[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) Y[i] = dot3(P[3 * i], Xw[0], P[3 * i + 1], Xw[1], P[3 * i + 2], Xw[2]) + P[9 + i];
-    double p[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) p[i] = dot3(Km.m[i][0], Y[0], Km.m[i][1], Y[1], Km.m[i][2], Y[2]);
-    u = p[0] / p[2];
-    v = p[1] / p[2];
-    z = Y[2];
+    a.depth[pixel] = winner.depth(a.depths + r * D, D);
+    a.cost[pixel] = winner.best_cost;
+    a.index[pixel] = winner.best;
 }
 
 __global__ __launch_bounds__(kFilterBlock) void filter_depth_maps_kernel(const double* __restrict__ depth, int64_t views, int H, int W,
@@ -358,11 +288,8 @@ __global__ __launch_bounds__(kFilterBlock) void filter_depth_maps_kernel(const d
     points[at * 3 + 2] = keep ? Xw[2] : NAN;
 }
 
-bool aligned_to(const void* p, uintptr_t bytes) { return ((uintptr_t)p & (bytes - 1)) == 0; }
-
 bool image_sizes_ok(int64_t views, int64_t height, int64_t width, int64_t refs, int64_t sources) {
-    return views >= 1 && views <= 0x7FFFFFFF && height >= 1 && width >= 1 && height <= 0x7FFFFFFF && width <= 0x7FFFFFFF &&
-           height * width < ((int64_t)1 << 31) && refs >= 0 && refs <= 65535 && sources >= 1 && sources <= kMaxSources;
+    return sfmhost::image_stack_ok(views, height, width) && refs >= 0 && refs <= 65535 && sources >= 1 && sources <= kMaxSources;
 }
 
 // the sizes of a sweep whatever its radius: the smallest window (radius 1) must fit

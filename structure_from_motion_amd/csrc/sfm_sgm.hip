@@ -16,7 +16,8 @@
 //                              rows x 16 depth groups.  A tile of 4 rows x XT columns x D is read with x fastest across the lanes,
 //                              transposed through LDS, walked column by column with the same step as above, the L values put back
 //                              into LDS and added to the running sum with x fastest again.
-//   sgm_winner_kernel          one thread per pixel: the eligible hypothesis of lowest sum and the parabola step of the sweep.
+//   sgm_winner_kernel          one thread per pixel: the eligible hypothesis of lowest sum and the parabola step of the sweep
+//                              (sfmdense::DepthWinner, sfm_dense.h).
 // The first direction writes the running sum, the later ones add to it in launch order: the left fold of the definition.
 // G is 1, 2, 4, 8 or 16 (D up to 16, 32, 64, 128, 256); a value beyond D is +inf in the registers and never stored.  Nothing is
 // indexed by a run-time value but LDS and global memory, so no kernel uses scratch.
@@ -25,9 +26,11 @@
 #include <stdint.h>
 
 #include "sfm_common.h"
+#include "sfm_dense.h"
 
 namespace {
 
+using sfmhost::aligned_to;
 using sfmhost::check_launch;
 using sfmhost::fail;
 using sfmhost::grid_for;
@@ -40,8 +43,6 @@ constexpr int kHorizontalRows = 4;     // image rows of a block of the horizonta
 constexpr int kHorizontalBlock = kHorizontalRows * kGroups;
 constexpr int kWinnerBlock = 256;
 
-#define SFM_SGM_DEVICE __device__ __forceinline__
-
 struct SgmArgs {
     const double *volume, *depths;
     double* sum;   // [R, D, H, W]: `aggregated`, or the workspace
@@ -51,7 +52,7 @@ struct SgmArgs {
 
 // lane i of a DPP row of 16 reads the lane that CTRL names; a lane without a source gets `fill`
 template <int CTRL>
-SFM_SGM_DEVICE double row_move(double v, double fill) {
+SFM_DEVICE double row_move(double v, double fill) {
     const int lo = __builtin_amdgcn_update_dpp(__double2loint(fill), __double2loint(v), CTRL, 0xF, 0xF, false);
     const int hi = __builtin_amdgcn_update_dpp(__double2hiint(fill), __double2hiint(v), CTRL, 0xF, 0xF, false);
     return __hiloint2double(hi, lo);
@@ -62,7 +63,7 @@ constexpr int kDppHalfMirror = 0x141, kDppMirror = 0x140;   // row_half_mirror, 
 constexpr int kDppShl1 = 0x101, kDppShr1 = 0x111;           // row_shl:1 (lane i reads i + 1), row_shr:1 (lane i reads i - 1)
 
 // the minimum over the 16 lanes of a DPP row, in every lane
-SFM_SGM_DEVICE double row_min(double v) {
+SFM_DEVICE double row_min(double v) {
     v = fmin(v, row_move<kDppXor1>(v, v));
     v = fmin(v, row_move<kDppXor2>(v, v));
     v = fmin(v, row_move<kDppHalfMirror>(v, v));
@@ -71,7 +72,7 @@ SFM_SGM_DEVICE double row_min(double v) {
 
 // One pixel of a path.  L: the values of the previous pixel (in: +inf beyond D), replaced by those of this pixel; c: C' here.
 template <int G>
-SFM_SGM_DEVICE void sgm_step(double (&L)[G], const double (&c)[G], bool restart, int g, int D, double p1, double p2) {
+SFM_DEVICE void sgm_step(double (&L)[G], const double (&c)[G], bool restart, int g, int D, double p1, double p2) {
     double m = L[0];
 #pragma unroll
     for (int j = 1; j < G; ++j) m = fmin(m, L[j]);
@@ -90,7 +91,7 @@ SFM_SGM_DEVICE void sgm_step(double (&L)[G], const double (&c)[G], bool restart,
     for (int j = 0; j < G; ++j) L[j] = g * G + j < D ? out[j] : INFINITY;
 }
 
-SFM_SGM_DEVICE double unary(double v, double invalid_cost) { return isfinite(v) ? v : invalid_cost; }
+SFM_DEVICE double unary(double v, double invalid_cost) { return isfinite(v) ? v : invalid_cost; }
 
 template <int G>
 __global__ __launch_bounds__(kVerticalBlock) void sgm_vertical_kernel(const SgmArgs a, int dx, int dy, int first) {
@@ -208,7 +209,7 @@ __global__ __launch_bounds__(kHorizontalBlock) void sgm_horizontal_kernel(const 
     }
 }
 
-// The winner of a pixel: the sweep's rule (sfm_plane_sweep.hip) on the sums, a hypothesis that is not eligible counting as NaN.
+// The winner of a pixel: the sweep's rule (sfmdense::DepthWinner) on the sums, a hypothesis that is not eligible counting as NaN.
 __global__ __launch_bounds__(kWinnerBlock) void sgm_winner_kernel(const SgmArgs a, double* __restrict__ depth, int32_t* __restrict__ index,
                                                                   double* __restrict__ cost) {
     const int64_t plane = (int64_t)a.H * a.W, i = (int64_t)blockIdx.x * kWinnerBlock + threadIdx.x;
@@ -218,45 +219,19 @@ __global__ __launch_bounds__(kWinnerBlock) void sgm_winner_kernel(const SgmArgs 
     const double* vol = a.volume + r * D * plane + i;
     const double* sum = a.sum + r * D * plane + i;
     const double* z = a.depths + r * D;
-    int best = -1;
-    double best_cost = NAN, cost_before = NAN, cost_after = NAN, previous = NAN;
+    sfmdense::DepthWinner winner;
     for (int d = 0; d < D; ++d) {
         const double zd = z[d];
-        const double value = isfinite(vol[d * plane]) && isfinite(zd) && zd > 0.0 ? sum[d * plane] : NAN;
-        if (value == value && (best < 0 || value < best_cost)) {
-            best = d;
-            best_cost = value;
-            cost_before = previous;
-            cost_after = NAN;
-        } else if (d == best + 1 && best >= 0) {
-            cost_after = value;
-        }
-        previous = value;
+        winner.offer(d, isfinite(vol[d * plane]) && isfinite(zd) && zd > 0.0 ? sum[d * plane] : NAN);
     }
-    double out = NAN;
-    if (best >= 0) {
-        const double zi = z[best];
-        out = zi;
-        if (best > 0 && best < D - 1 && cost_before == cost_before && cost_after == cost_after) {
-            const double den = (cost_before - best_cost) + (cost_after - best_cost);
-            if (den > 0.0) {
-                const double o = 0.5 * (cost_before - cost_after) / den;
-                const double zj = z[o > 0.0 ? best + 1 : best - 1];
-                const double q = 1.0 / zi + fabs(o) * (1.0 / zj - 1.0 / zi);
-                out = 1.0 / q;
-            }
-        }
-    }
-    depth[r * plane + i] = out;
-    cost[r * plane + i] = best_cost;
-    index[r * plane + i] = best;
+    depth[r * plane + i] = winner.depth(z, D);
+    cost[r * plane + i] = winner.best_cost;
+    index[r * plane + i] = winner.best;
 }
 
-bool aligned_to(const void* p, uintptr_t bytes) { return ((uintptr_t)p & (bytes - 1)) == 0; }
-
 bool sgm_sizes_ok(int64_t refs, int64_t depths, int64_t height, int64_t width) {
-    return refs >= 0 && refs <= 65535 && depths >= 1 && depths <= kMaxDepths && height >= 1 && width >= 1 && height <= 0x7FFFFFFF &&
-           width <= 0x7FFFFFFF && height * width < ((int64_t)1 << 31);
+    // the volume of a reference is a stack of `depths` planes
+    return refs >= 0 && refs <= 65535 && depths <= kMaxDepths && sfmhost::image_stack_ok(depths, height, width);
 }
 
 int64_t sgm_bytes(int64_t refs, int64_t depths, int64_t height, int64_t width, bool keep_aggregated) {

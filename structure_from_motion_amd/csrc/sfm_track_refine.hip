@@ -1,7 +1,7 @@
 // Sub-pixel refinement of track observations by affine least-squares patch matching (definition:
 // tests/track_refine_oracle.py).  Every observation of a track but the reference is aligned with the reference's window by
 // Gauss-Newton on six affine parameters, maximising the normalised correlation.  All arithmetic is fp64 with + - * / and sqrt in
-// the definition's order, so the device equals the NumPy definition byte for byte.
+// the definition's order, so the device equals the NumPy definition byte for byte.  The bilinear cell formula is sfm_dense.h's.
 //
 //   refine_kernel<SPL>   one wave per observation, four observations per block.  Window sample k = lane + 64 j (j < SPL, SPL =
 //                        ceil((2r+1)^2 / 64)) belongs to lane k mod 64; template, state and every running sum stay in registers.
@@ -14,6 +14,7 @@
 #include <stdint.h>
 
 #include "sfm_common.h"
+#include "sfm_dense.h"
 #include "sfm_keypoint_planes.h"
 #include "sfm_lm.h"
 
@@ -40,37 +41,31 @@ struct RefineArgs {
     double min_step2, max_shift2, min_correlation;
 };
 
-#define SFM_REFINE_DEVICE __device__ __forceinline__
-
-// the sum of one value per lane, in every lane
-SFM_REFINE_DEVICE double wave_sum(double v) {
+// The sum of one value per lane, in every lane.  Not sfm::wave_sum: the order of this xor butterfly is section 6al's definition.
+SFM_DEVICE double butterfly_sum(double v) {
 #pragma unroll
     for (int m = kWave / 2; m >= 1; m >>= 1) v = v + __shfl_xor(v, m, kWave);
     return v;
 }
 
 template <int SPL>
-SFM_REFINE_DEVICE double window_sum(const double (&p)[SPL]) {
+SFM_DEVICE double window_sum(const double (&p)[SPL]) {
     double acc = p[0];
 #pragma unroll
     for (int j = 1; j < SPL; ++j) acc = acc + p[j];
-    return wave_sum(acc);
+    return butterfly_sum(acc);
 }
 
-// section 6ai's bilinear formula at (u, v), 0 <= u <= W - 1 and 0 <= v <= H - 1; the cell is the last one of its row or column
-// when u + 1 or v + 1 rounded up to the plane's edge
-SFM_REFINE_DEVICE double bilinear(const uint8_t* __restrict__ image, int W, int H, double u, double v) {
+// section 6ai's bilinear formula (sfm_dense.h) at (u, v), 0 <= u <= W - 1 and 0 <= v <= H - 1; the cell is the last one of its
+// row or column when u + 1 or v + 1 rounded up to the plane's edge
+SFM_DEVICE double bilinear(const uint8_t* __restrict__ image, int W, int H, double u, double v) {
     const int x0 = min((int)u, W - 2), y0 = min((int)v, H - 2);
-    const double fx = u - (double)x0, fy = v - (double)y0;
-    const uint8_t* p = image + (int64_t)y0 * W + x0;
-    const double p00 = (double)p[0], p10 = (double)p[1], p01 = (double)p[W], p11 = (double)p[W + 1];
-    const double top = p00 + fx * (p10 - p00), bot = p01 + fx * (p11 - p01);
-    return top + fy * (bot - top);
+    return sfmdense::bilinear_cell(image + (int64_t)y0 * W + x0, W, u - (double)x0, v - (double)y0);
 }
 
 // The window's positions under (t, A); false when a sample leaves 1 <= u < W - 2, 1 <= v < H - 2 (wave-uniform).
 template <int SPL>
-SFM_REFINE_DEVICE bool window_positions(const double (&dx)[SPL], const double (&dy)[SPL], const bool (&active)[SPL], double t0, double t1,
+SFM_DEVICE bool window_positions(const double (&dx)[SPL], const double (&dy)[SPL], const bool (&active)[SPL], double t0, double t1,
                                         const double (&A)[4], int W, int H, double (&u)[SPL], double (&v)[SPL]) {
     bool bad = false;
     const double ulim = (double)(W - 2), vlim = (double)(H - 2);
@@ -86,7 +81,7 @@ SFM_REFINE_DEVICE bool window_positions(const double (&dx)[SPL], const double (&
 
 // I0 = I - mean(I) in place (0 in a lane without the sample); returns the sum of I0^2
 template <int SPL>
-SFM_REFINE_DEVICE double centre(double (&I)[SPL], const bool (&active)[SPL], double n) {
+SFM_DEVICE double centre(double (&I)[SPL], const bool (&active)[SPL], double n) {
     const double mean = window_sum<SPL>(I) / n;
     double sq[SPL];
 #pragma unroll
@@ -97,7 +92,7 @@ SFM_REFINE_DEVICE double centre(double (&I)[SPL], const bool (&active)[SPL], dou
     return window_sum<SPL>(sq);
 }
 
-SFM_REFINE_DEVICE void write_result(const RefineArgs& a, int64_t o, int lane, int status, double x, double y, const double (&A)[4],
+SFM_DEVICE void write_result(const RefineArgs& a, int64_t o, int lane, int status, double x, double y, const double (&A)[4],
                                     double correlation, int iterations) {
     if (lane != 0) return;
     a.xy[2 * o] = x;

@@ -1,7 +1,8 @@
 // Fusion of depth maps into a truncated-signed-distance volume and the triangles of its zero level set.
 //
 // Every step of both is fp64 + - * / in a written order (the build has -ffp-contract=off), so a result is a matter of bytes:
-// tests/tsdf_oracle.py states the same sequence in NumPy.  Every 3-term product sum is (a0*b0 + a1*b1) + a2*b2.
+// tests/tsdf_oracle.py states the same sequence in NumPy.  Every 3-term product sum is sfm_dense.h's dot3, and a voxel is projected
+// into a view by that header's camera_matrices and project, as the depth filter projects a point.
 //
 // sfm_tsdf_integrate, 1 launch: one thread per voxel, x fastest, the loop over the views inside the thread.  The state (sum,
 //   count, grey_sum) is read once and written once per call whatever the number of views; the view list, K and the poses are read
@@ -20,11 +21,13 @@
 #include <stdint.h>
 
 #include "sfm_common.h"
-#include "sfm_math.h"   // SFM_DEVICE, which sfm_obs_order.h uses
+#include "sfm_dense.h"
 #include "sfm_obs_order.h"
 
 namespace {
 
+using sfmdense::dot3;
+using sfmhost::aligned_to;
 using sfmhost::check_launch;
 using sfmhost::fail;
 using sfmhost::grid_fits;
@@ -33,16 +36,12 @@ using sfmhost::grid_for;
 constexpr int kBlock = 256;
 constexpr int64_t kMaxTrianglesPerCell = 12;
 
-#define SFM_TSDF_DEVICE __device__ __forceinline__
-
-SFM_TSDF_DEVICE double dot3(double a0, double b0, double a1, double b1, double a2, double b2) { return (a0 * b0 + a1 * b1) + a2 * b2; }
-
 struct Volume {
     int nx, ny, nz;
     double ox, oy, oz, s;
 };
 
-SFM_TSDF_DEVICE double centre(double o, int i, double s) { return o + ((double)i + 0.5) * s; }
+SFM_DEVICE double centre(double o, int i, double s) { return o + ((double)i + 0.5) * s; }
 
 __global__ __launch_bounds__(kBlock) void tsdf_integrate_kernel(const Volume vol, double trunc, const double* __restrict__ depth,
                                                                 const uint8_t* __restrict__ images, int64_t views, int H, int W,
@@ -59,8 +58,9 @@ __global__ __launch_bounds__(kBlock) void tsdf_integrate_kernel(const Volume vol
     const int64_t l = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (l >= voxels) return;
     const int i = (int)(l % vol.nx), j = (int)((l / vol.nx) % vol.ny), k = (int)(l / ((int64_t)vol.nx * vol.ny));
-    const double c0 = centre(vol.ox, i, vol.s), c1 = centre(vol.oy, j, vol.s), c2 = centre(vol.oz, k, vol.s);
-    const double fx = K[0], sk = K[1], cx = K[2], fy = K[4], cy = K[5];   // K rebuilt from its five entries, as the filter does
+    const double c[3] = {centre(vol.ox, i, vol.s), centre(vol.oy, j, vol.s), centre(vol.oz, k, vol.s)};
+    sfmdense::Mat3 Km, Ki;   // only Km is used: the inverse folds away
+    sfmdense::camera_matrices(K, Km, Ki);
     const int64_t plane = (int64_t)H * W;
     double acc = sum[l];
     int32_t seen = count[l];
@@ -68,12 +68,8 @@ __global__ __launch_bounds__(kBlock) void tsdf_integrate_kernel(const Volume vol
     for (int n = 0; n < N; ++n) {
         const int32_t v = list[n];
         if (v < 0 || (int64_t)v >= views) continue;   // wave-uniform
-        const double* P = poses + (int64_t)v * 12;
-        const double Y0 = dot3(P[0], c0, P[1], c1, P[2], c2) + P[9];
-        const double Y1 = dot3(P[3], c0, P[4], c1, P[5], c2) + P[10];
-        const double Y2 = dot3(P[6], c0, P[7], c1, P[8], c2) + P[11];
-        const double p0 = dot3(fx, Y0, sk, Y1, cx, Y2), p1 = dot3(0.0, Y0, fy, Y1, cy, Y2), p2 = dot3(0.0, Y0, 0.0, Y1, 1.0, Y2);
-        const double u = p0 / p2, w = p1 / p2, z = Y2;
+        double u, w, z;
+        sfmdense::project(Km, poses + (int64_t)v * 12, c, u, w, z);
         if (!(z > 0.0)) continue;
         const double x = floor(u + 0.5), y = floor(w + 0.5);
         if (!(x >= 0.0 && x < (double)W && y >= 0.0 && y < (double)H)) continue;
@@ -106,18 +102,18 @@ struct Cell {
     int64_t base;   // the linear voxel index of corner 0
 };
 
-SFM_TSDF_DEVICE int64_t corner_voxel(const Cell& c, int q) {
+SFM_DEVICE int64_t corner_voxel(const Cell& c, int q) {
     return c.base + (q & 1) + (int64_t)((q >> 1) & 1) * c.nx + (int64_t)((q >> 2) & 1) * c.nx * c.ny;
 }
 
-SFM_TSDF_DEVICE bool cell_valid(const Cell& c, int min_count) {
+SFM_DEVICE bool cell_valid(const Cell& c, int min_count) {
     bool valid = true;
 #pragma unroll
     for (int q = 0; q < 8; ++q) valid = valid && c.count[corner_voxel(c, q)] >= min_count;
     return valid;
 }
 
-SFM_TSDF_DEVICE Corner load_corner(const Cell& c, int q) {
+SFM_DEVICE Corner load_corner(const Cell& c, int q) {
     const int64_t l = corner_voxel(c, q);
     const double n = (double)c.count[l];
     Corner r;
@@ -128,7 +124,7 @@ SFM_TSDF_DEVICE Corner load_corner(const Cell& c, int q) {
 }
 
 // negative corners in front of the others, both groups in the order they came in; -> the number of negative corners
-SFM_TSDF_DEVICE int negatives_first(Corner& e0, Corner& e1, Corner& e2, Corner& e3) {
+SFM_DEVICE int negatives_first(Corner& e0, Corner& e1, Corner& e2, Corner& e3) {
 #define SFM_TSDF_SWAP(a, b)                      \
     if (!(a.f < 0.0) && b.f < 0.0) {             \
         const Corner t = a;                      \
@@ -142,13 +138,13 @@ SFM_TSDF_DEVICE int negatives_first(Corner& e0, Corner& e1, Corner& e2, Corner& 
     return (e0.f < 0.0) + (e1.f < 0.0) + (e2.f < 0.0) + (e3.f < 0.0);
 }
 
-SFM_TSDF_DEVICE int triangles_of(int negatives) { return negatives == 2 ? 2 : (negatives == 1 || negatives == 3 ? 1 : 0); }
+SFM_DEVICE int triangles_of(int negatives) { return negatives == 2 ? 2 : (negatives == 1 || negatives == 3 ? 1 : 0); }
 
 struct Vertex {
     double x, y, z, g;
 };
 
-SFM_TSDF_DEVICE Vertex edge_vertex(const Volume& vol, const Cell& c, const Corner& p, const Corner& q) {
+SFM_DEVICE Vertex edge_vertex(const Volume& vol, const Cell& c, const Corner& p, const Corner& q) {
     const bool p_low = p.q < q.q;
     const double lf = p_low ? p.f : q.f, hf = p_low ? q.f : p.f, lg = p_low ? p.g : q.g, hg = p_low ? q.g : p.g;
     const int lq = p_low ? p.q : q.q, hq = p_low ? q.q : p.q;
@@ -169,7 +165,7 @@ struct MeshOut {
     int64_t max_triangles;
 };
 
-SFM_TSDF_DEVICE void store_triangle(const MeshOut& out, int64_t row, const Vertex& A, Vertex B, Vertex C, double D0, double D1, double D2) {
+SFM_DEVICE void store_triangle(const MeshOut& out, int64_t row, const Vertex& A, Vertex B, Vertex C, double D0, double D1, double D2) {
     if (row >= out.max_triangles) return;
     const double a0 = B.x - A.x, a1 = B.y - A.y, a2 = B.z - A.z;
     const double b0 = C.x - A.x, b1 = C.y - A.y, b2 = C.z - A.z;
@@ -190,12 +186,12 @@ SFM_TSDF_DEVICE void store_triangle(const MeshOut& out, int64_t row, const Verte
 }
 
 // the sum of one coordinate bit over the corners of a group
-SFM_TSDF_DEVICE int bit_sum(int shift, int qa, int qb, int qc) { return ((qa >> shift) & 1) + ((qb >> shift) & 1) + ((qc >> shift) & 1); }
+SFM_DEVICE int bit_sum(int shift, int qa, int qb, int qc) { return ((qa >> shift) & 1) + ((qb >> shift) & 1) + ((qc >> shift) & 1); }
 
 // The triangles of one tetrahedron (its corners in the tetrahedron's order) to the rows from `row` on; -> their number.
 // kEmit = false only counts.
 template <bool kEmit>
-SFM_TSDF_DEVICE int tetrahedron(const Volume& vol, const Cell& c, Corner e0, Corner e1, Corner e2, Corner e3, const MeshOut& out, int64_t row) {
+SFM_DEVICE int tetrahedron(const Volume& vol, const Cell& c, Corner e0, Corner e1, Corner e2, Corner e3, const MeshOut& out, int64_t row) {
     const int negatives = negatives_first(e0, e1, e2, e3);
     const int triangles = triangles_of(negatives);
     if (!kEmit || triangles == 0) return triangles;
@@ -222,7 +218,7 @@ SFM_TSDF_DEVICE int tetrahedron(const Volume& vol, const Cell& c, Corner e0, Cor
 
 // the six tetrahedra of the Kuhn split about the diagonal 0-7, in the order of the definition; -> the triangles of the cell
 template <bool kEmit>
-SFM_TSDF_DEVICE int march_cell(const Volume& vol, const Cell& c, const MeshOut& out, int64_t row) {
+SFM_DEVICE int march_cell(const Volume& vol, const Cell& c, const MeshOut& out, int64_t row) {
     const Corner c0 = load_corner(c, 0), c1 = load_corner(c, 1), c2 = load_corner(c, 2), c3 = load_corner(c, 3);
     const Corner c4 = load_corner(c, 4), c5 = load_corner(c, 5), c6 = load_corner(c, 6), c7 = load_corner(c, 7);
     int n = 0;
@@ -235,7 +231,7 @@ SFM_TSDF_DEVICE int march_cell(const Volume& vol, const Cell& c, const MeshOut& 
     return n;
 }
 
-SFM_TSDF_DEVICE Cell cell_of(const Volume& vol, int64_t cell, const double* sum, const int32_t* count, const int32_t* grey_sum) {
+SFM_DEVICE Cell cell_of(const Volume& vol, int64_t cell, const double* sum, const int32_t* count, const int32_t* grey_sum) {
     const int cxn = vol.nx - 1, cyn = vol.ny - 1;
     Cell c;
     c.sum = sum, c.count = count, c.grey_sum = grey_sum, c.nx = vol.nx, c.ny = vol.ny;
@@ -279,8 +275,6 @@ __global__ __launch_bounds__(kBlock) void tsdf_tail_kernel(const int32_t* __rest
         for (int a = 0; a < 3; ++a) out.grey[row * 3 + a] = NAN;
 }
 
-bool aligned_to(const void* p, uintptr_t bytes) { return ((uintptr_t)p & (bytes - 1)) == 0; }
-
 bool volume_sizes_ok(int64_t nx, int64_t ny, int64_t nz, int64_t least) {
     const int64_t limit = (int64_t)1 << 31;
     return nx >= least && ny >= least && nz >= least && nx < limit && ny < limit && nz < limit && nx * ny < limit && nx * ny * nz < limit;
@@ -320,8 +314,7 @@ int sfm_tsdf_integrate(double* sum, int32_t* count, int32_t* grey_sum, int64_t n
     if (!volume_sizes_ok(nx, ny, nz, 1)) return fail(SFM_EINVAL, "sfm_tsdf_integrate: need nx, ny, nz >= 1 and nx * ny * nz < 2^31");
     if (!volume_scalars_ok(ox, oy, oz, voxel_size) || !isfinite(truncation) || !(truncation > 0.0))
         return fail(SFM_EINVAL, "sfm_tsdf_integrate: the origin must be finite, voxel_size and truncation finite and > 0");
-    if (views < 1 || views > 0x7FFFFFFF || height < 1 || width < 1 || height > 0x7FFFFFFF || width > 0x7FFFFFFF ||
-        height * width >= ((int64_t)1 << 31))
+    if (!sfmhost::image_stack_ok(views, height, width))
         return fail(SFM_EINVAL, "sfm_tsdf_integrate: need 1 <= views < 2^31 and 1 <= height * width < 2^31");
     if (view_count < 0 || view_count > 0x7FFFFFFF) return fail(SFM_EINVAL, "sfm_tsdf_integrate: need 0 <= view_count < 2^31");
     if (!grid_fits(nx * ny * nz, kBlock, kBlock))

@@ -120,6 +120,37 @@ def aggregate(costs, top_k, min_sources):
     return np.where((count >= min_sources) & (count >= 1), cost, np.nan)
 
 
+def winners(values, eligible, z):
+    """-> (depth, index int32, cost) [H, W] of one reference from ``values`` [D, H, W] of the hypotheses at the depths ``z`` [D]:
+    the eligible hypothesis of lowest value, ties to the lower index (index -1, depth and cost NaN without one), and the parabola
+    step in inverse depth: for a winner 0 < i < D - 1 whose neighbours are both eligible and whose
+    den = (before - cost) + (after - cost) > 0, with o = 0.5 (before - after) / den and j = i + 1 for o > 0, else i - 1, the depth
+    1 / (1 / z_i + |o| (1 / z_j - 1 / z_i)) in place of z_i."""
+    D, H, W = values.shape
+    value = np.where(eligible, values, np.nan)
+    best, best_cost = np.full((H, W), -1, dtype=np.int32), np.full((H, W), np.nan)
+    for d in range(D):
+        with np.errstate(all="ignore"):
+            better = eligible[d] & ((best < 0) | (value[d] < best_cost))
+        best[better] = d
+        best_cost[better] = value[d][better]
+    has = best >= 0
+    at = np.where(has, best, 0)
+    with np.errstate(all="ignore"):
+        zi = z[at]
+        depth = np.where(has, zi, np.nan)
+        inner = has & (best > 0) & (best < D - 1)
+        before = np.take_along_axis(value, np.clip(at - 1, 0, D - 1)[None], axis=0)[0]
+        after = np.take_along_axis(value, np.clip(at + 1, 0, D - 1)[None], axis=0)[0]
+        den = (before - best_cost) + (after - best_cost)
+        take = inner & np.isfinite(before) & np.isfinite(after) & (den > 0.0)
+        o = 0.5 * (before - after) / den
+        zj = z[np.clip(np.where(o > 0.0, at + 1, at - 1), 0, D - 1)]
+        q = 1.0 / zi + np.abs(o) * (1.0 / zj - 1.0 / zi)
+        refined = 1.0 / q
+    return np.where(take, refined, depth), best, best_cost
+
+
 def plane_sweep(images, K, poses, refs, sources, depths, radius, top_k=0, min_sources=1, min_variance=1.0):
     """-> dict(depth [R, H, W], index int32, cost, status int32 [R], volume [R, D, H, W])."""
     images = np.asarray(images)
@@ -149,27 +180,7 @@ def plane_sweep(images, K, poses, refs, sources, depths, radius, top_k=0, min_so
                           for src in sources[r] if present(int(src), ref, V)]
             if per_source:
                 volume[d] = aggregate(np.stack(per_source), top_k, min_sources)
-        best, best_cost = out["index"][r], out["cost"][r]
-        for d in range(D):
-            with np.errstate(all="ignore"):
-                better = np.isfinite(volume[d]) & ((best < 0) | (volume[d] < best_cost))
-            best[better] = d
-            best_cost[better] = volume[d][better]
-        has = best >= 0
-        at = np.where(has, best, 0)
-        zi = depths[r][at]
-        depth = np.where(has, zi, np.nan)
-        inner = has & (best > 0) & (best < D - 1)
-        before = np.take_along_axis(volume, np.clip(at - 1, 0, D - 1)[None], axis=0)[0]
-        after = np.take_along_axis(volume, np.clip(at + 1, 0, D - 1)[None], axis=0)[0]
-        with np.errstate(all="ignore"):
-            den = (before - best_cost) + (after - best_cost)
-            step = inner & np.isfinite(before) & np.isfinite(after) & (den > 0.0)
-            o = 0.5 * (before - after) / den
-            zj = depths[r][np.clip(np.where(o > 0.0, at + 1, at - 1), 0, D - 1)]
-            q = 1.0 / zi + np.abs(o) * (1.0 / zj - 1.0 / zi)
-            refined = 1.0 / q
-        out["depth"][r] = np.where(step, refined, depth)
+        out["depth"][r], out["index"][r], out["cost"][r] = winners(volume, np.isfinite(volume), depths[r])
     return out
 
 

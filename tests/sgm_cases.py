@@ -82,6 +82,42 @@ def dyadic_volume(shape, seed):
     return np.random.default_rng(seed).integers(0, 32, size=shape).astype(np.float64) / 8.0
 
 
+# Hand-made cost columns of D = 5 hypotheses for the winner rule (plane_sweep_oracle.winners; sfmdense::DepthWinner on the device):
+# (what, costs, depths, index, depth, cost), a NaN cost being a hypothesis without one.  The costs are small integers, so the
+# smoothing of a 1 x 1 image, where every path restarts, turns a column c into exactly paths * c: the step is the same, since
+# o = 0.5 (before - after) / den does not change when all three costs are scaled by a power of two.
+# den = (before - cost) + (after - cost) == 0 cannot be reached: a hypothesis before the winner costs strictly more than the
+# winner, or it would have won; the flat columns below are what comes closest.
+_N = np.nan
+_Z = (1.0, 2.0, 4.0, 8.0, 16.0)
+WINNER_COLUMNS = (
+    ("no cost at all", (_N, _N, _N, _N, _N), _Z, -1, _N, _N),
+    ("winner at index 0: no step", (1, 2, 3, 4, 5), _Z, 0, 1.0, 1.0),
+    ("winner at index D - 1: no step", (5, 4, 3, 2, 1), _Z, 4, 16.0, 1.0),
+    ("no cost before the winner: no step", (3, _N, 1, 2, 3), _Z, 2, 4.0, 1.0),
+    ("no cost after the winner: no step", (3, 2, 1, _N, 3), _Z, 2, 4.0, 1.0),
+    ("a flat column: the lowest index, no step", (1, 1, 1, 1, 1), _Z, 0, 1.0, 1.0),
+    ("a flat triple: its lowest index, o = 0.5 (2 - 1) / 1", (2, 1, 1, 1, 2), _Z, 1, 1.0 / (1.0 / 2.0 + 0.5 * (1.0 / 4.0 - 1.0 / 2.0)), 1.0),
+    ("a step towards d + 1: o = 0.5 (4 - 2) / 4", (5, 4, 1, 2, 5), _Z, 2, 1.0 / (1.0 / 4.0 + 0.25 * (1.0 / 8.0 - 1.0 / 4.0)), 1.0),
+    ("a step towards d - 1: o = 0.5 (2 - 4) / 4", (5, 2, 1, 4, 5), _Z, 2, 1.0 / (1.0 / 4.0 + 0.25 * (1.0 / 2.0 - 1.0 / 4.0)), 1.0),
+    ("a symmetric triple: o = 0, the depth through 1 / (1 / z)", (5, 3, 1, 3, 5), _Z, 2, 4.0, 1.0),
+    ("two equal minima: the lower index, o = 0.5 (4 - 2) / 4", (4, 1, 2, 1, 4), _Z, 1, 1.0 / (1.0 / 2.0 + 0.25 * (1.0 / 4.0 - 1.0 / 2.0)), 1.0),
+    ("duplicated depths: z_j == z_i", (5, 4, 1, 2, 5), (1.0, 2.0, 4.0, 4.0, 16.0), 2, 4.0, 1.0),
+    ("a negative depth at the lowest cost", (5, 4, 1, 2, 5), (1.0, 2.0, -4.0, 8.0, 16.0), 3, 8.0, 2.0),
+    ("a depth of zero at the lowest cost", (5, 2, 1, 4, 5), (1.0, 2.0, 0.0, 8.0, 16.0), 1, 2.0, 2.0),
+    ("a NaN depth beside the winner: no step", (5, 4, 1, 2, 5), (1.0, 2.0, 4.0, _N, 16.0), 2, 4.0, 1.0),
+    ("an infinite depth at the lowest cost", (1, 4, 5, 2, 3), (np.inf, 2.0, 4.0, 8.0, 16.0), 3, 1.0 / (1.0 / 8.0 + 0.25 * (1.0 / 16.0 - 1.0 / 8.0)), 2.0),
+)
+
+
+def winner_columns():
+    """WINNER_COLUMNS as a volume [R, 5, 1, 1] with one case per reference, depths [R, 5] and the expected (index, depth, cost) [R]."""
+    costs = np.array([c[1] for c in WINNER_COLUMNS], dtype=np.float64)
+    depths = np.array([c[2] for c in WINNER_COLUMNS], dtype=np.float64)
+    want = tuple(np.array([c[k] for c in WINNER_COLUMNS], dtype=t) for k, t in ((3, np.int32), (4, np.float64), (5, np.float64)))
+    return costs[:, :, None, None], depths, want
+
+
 @functools.lru_cache(maxsize=None)
 def sweep_volume(seed=21):
     """The real cost volume of four views of 37 x 45 with D = 9 (the sweep's oracle, radius 2): -> (volume, depths [4, 9])."""

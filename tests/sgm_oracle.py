@@ -4,6 +4,8 @@ the device result is compared with it as bytes (``plane_sweep_oracle.same_bytes`
 pixels across a direction; an explicit loop along it.  Every term of a ``min`` is finite, so its order does not matter."""
 import numpy as np
 
+from plane_sweep_oracle import winners
+
 DIRECTIONS = {8: ((0, 1), (1, 1), (-1, 1), (0, -1), (-1, -1), (1, -1), (1, 0), (-1, 0)), 4: ((0, 1), (0, -1), (1, 0), (-1, 0))}
 
 
@@ -52,34 +54,6 @@ def aggregate(volume, p1, p2, invalid_cost, paths):
         L = path_costs(C, dx, dy, p1, p2)
         S = L if S is None else S + L
     return S
-
-
-def winners(S, eligible, z):
-    """-> (depth, index int32, cost) [H, W] of one reference: the eligible hypothesis of lowest S, ties to the lower index, and the
-    parabola step of the plane sweep in inverse depth, with S in place of the cost; both neighbours must be eligible."""
-    D, H, W = S.shape
-    value = np.where(eligible, S, np.nan)
-    best, best_cost = np.full((H, W), -1, dtype=np.int32), np.full((H, W), np.nan)
-    for d in range(D):
-        with np.errstate(all="ignore"):
-            better = eligible[d] & ((best < 0) | (value[d] < best_cost))
-        best[better] = d
-        best_cost[better] = value[d][better]
-    has = best >= 0
-    at = np.where(has, best, 0)
-    with np.errstate(all="ignore"):
-        zi = z[at]
-        depth = np.where(has, zi, np.nan)
-        inner = has & (best > 0) & (best < D - 1)
-        before = np.take_along_axis(value, np.clip(at - 1, 0, D - 1)[None], axis=0)[0]
-        after = np.take_along_axis(value, np.clip(at + 1, 0, D - 1)[None], axis=0)[0]
-        den = (before - best_cost) + (after - best_cost)
-        take = inner & np.isfinite(before) & np.isfinite(after) & (den > 0.0)
-        o = 0.5 * (before - after) / den
-        zj = z[np.clip(np.where(o > 0.0, at + 1, at - 1), 0, D - 1)]
-        q = 1.0 / zi + np.abs(o) * (1.0 / zj - 1.0 / zi)
-        refined = 1.0 / q
-    return np.where(take, refined, depth), best, best_cost
 
 
 def sgm_aggregate(volume, depths, p1=0.1, p2=0.8, invalid_cost=1.0, paths=8):

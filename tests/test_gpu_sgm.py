@@ -78,6 +78,16 @@ def test_first_and_last_depth_count_of_every_kernel(count):
     check(volume, depths, paths=8)
 
 
+@pytest.mark.parametrize("paths", [4, 8])
+def test_the_winner_rule_on_hand_made_columns(paths):
+    """One crafted column of 5 hypotheses per reference on a 1 x 1 image, where every path restarts and the winner kernel sees
+    paths times the column (tests/sgm_cases.py): every branch of the rule, against the definition and against the table."""
+    volume, depths, (index, depth, cost) = cases.winner_columns()
+    got, want = check(volume, depths, paths=paths)
+    assert po.same_bytes(got["index"][:, 0, 0], index) and po.same_bytes(got["depth"][:, 0, 0], depth)
+    assert po.same_bytes(got["cost"][:, 0, 0], paths * cost)
+
+
 # ---- settings ------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("p1,p2,invalid_cost", [(0.0, 0.8, 1.0), (0.5, 0.5, 1.0), (0.0, 0.0, 1.0), (0.1, 0.8, 0.0), (0.1, 0.8, 2.0)])
 def test_penalties_and_invalid_cost(p1, p2, invalid_cost):

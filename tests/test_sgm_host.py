@@ -50,6 +50,23 @@ def test_the_stream_case_runs_the_entry_point():
     assert va.shape == vb.shape and not np.array_equal(va, vb, equal_nan=True)
 
 
+# ---- the winner rule on hand-made columns ---------------------------------------------------------------------------------------------
+def test_the_winner_rule_on_hand_made_columns():
+    volume, depths, (index, depth, cost) = cases.winner_columns()
+    assert volume.shape[1:] == (5, 1, 1) and len(index) >= 12
+    for r, column in enumerate(cases.WINNER_COLUMNS):
+        with np.errstate(all="ignore"):
+            eligible = np.isfinite(volume[r]) & (np.isfinite(depths[r]) & (depths[r] > 0.0))[:, None, None]
+        got = po.winners(volume[r], eligible, depths[r])
+        for name, g, w in zip(("depth", "index", "cost"), got, (depth[r], index[r], cost[r])):
+            assert g.shape == (1, 1) and po.same_bytes(g[0, 0], w), f"{column[0]}: {name} {g[0, 0]} for {w}"
+    for paths in (4, 8):   # through the smoothing: every path of a 1 x 1 image restarts, so S = paths * C' exactly
+        smooth = so.sgm_aggregate(volume, depths, paths=paths, invalid_cost=1.0)
+        assert po.same_bytes(smooth["index"][:, 0, 0], index) and po.same_bytes(smooth["depth"][:, 0, 0], depth)
+        assert po.same_bytes(smooth["cost"][:, 0, 0], paths * cost)
+        assert po.same_bytes(smooth["aggregated"], paths * so.unary(volume, 1.0))
+
+
 # ---- the workspace ------------------------------------------------------------------------------------------------------------------
 def test_workspace_bytes_are_monotone_and_refused_sizes_give_minus_one():
     size = _native.load().sfm_sgm_workspace_bytes
