@@ -211,16 +211,35 @@ SIGNATURES = {
                                 _P, _I64, _P],
     "sfm_average_translations": [_I64, _I64, _P, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P],
 }
-OTHER_SYMBOLS = ["sfm_last_error", "sfm_abi_version", "sfm_score_workspace_bytes", "sfm_score_workspace_bytes_ex",
-                 "sfm_fit_trace_doubles", "sfm_match_summary_workspace_bytes", "sfm_bundle_workspace_bytes",
-                 "sfm_tracks_workspace_bytes", "sfm_bundle_pcg_workspace_bytes", "sfm_build_tracks_workspace_bytes",
-                 "sfm_bundle_pcg_workspace_bytes_ex", "sfm_hamming_summary_workspace_bytes", "sfm_pair_poses_workspace_bytes",
-                 "sfm_average_rotations_workspace_bytes", "sfm_average_translations_workspace_bytes",
-                 "sfm_match_pairs_workspace_bytes", "sfm_detect_keypoints_workspace_bytes",
-                 "sfm_bundle_calibrated_workspace_bytes", "sfm_tracks_robust_workspace_bytes",
-                 "sfm_similarity_fit_workspace_bytes", "sfm_similarity_refine_workspace_bytes",
-                 "sfm_align_models_workspace_bytes", "sfm_plane_sweep_workspace_bytes", "sfm_tsdf_mesh_workspace_bytes",
-                 "sfm_sgm_workspace_bytes", "sfm_build_pyramid_workspace_bytes", "sfm_refine_observations_workspace_bytes"]
+# name -> argtypes of the size functions; every one returns int64_t (negative: the sizes are refused)
+WORKSPACE_SIGNATURES = {
+    "sfm_score_workspace_bytes": [_I64] * 3,
+    "sfm_score_workspace_bytes_ex": [_I64] * 3 + [_P],
+    "sfm_match_summary_workspace_bytes": [_I64] * 2,
+    "sfm_hamming_summary_workspace_bytes": [_I64] * 2,
+    "sfm_bundle_workspace_bytes": [_I64] * 3,
+    "sfm_bundle_calibrated_workspace_bytes": [_I64] * 3,
+    "sfm_tracks_workspace_bytes": [_I64] * 2,
+    "sfm_tracks_robust_workspace_bytes": [_I64] * 2,
+    "sfm_bundle_pcg_workspace_bytes": [_I64] * 3,
+    "sfm_bundle_pcg_workspace_bytes_ex": [_I64] * 3 + [_P],
+    "sfm_build_tracks_workspace_bytes": [_I64] * 3,
+    "sfm_pair_poses_workspace_bytes": [_I64] * 2,
+    "sfm_average_rotations_workspace_bytes": [_I64] * 2,
+    "sfm_average_translations_workspace_bytes": [_I64] * 2,
+    "sfm_match_pairs_workspace_bytes": [_I64] * 3,
+    "sfm_similarity_fit_workspace_bytes": [_I64] * 2,
+    "sfm_similarity_refine_workspace_bytes": [_I64] * 2,
+    "sfm_align_models_workspace_bytes": [_I64] * 3,
+    "sfm_plane_sweep_workspace_bytes": [_I64] * 6,
+    "sfm_tsdf_mesh_workspace_bytes": [_I64] * 3,
+    "sfm_sgm_workspace_bytes": [_I64] * 4 + [C.c_int],
+    "sfm_detect_keypoints_workspace_bytes": [_I64],
+    "sfm_build_pyramid_workspace_bytes": [_I64],
+    "sfm_refine_observations_workspace_bytes": [_I64],
+}
+# every symbol of include/sfm_hip.h that SIGNATURES does not list: three that take nothing, and the size functions
+OTHER_SYMBOLS = ["sfm_last_error", "sfm_abi_version", "sfm_fit_trace_doubles"] + list(WORKSPACE_SIGNATURES)
 
 # the losses of both bundle adjusters, in the order of their SFM_BUNDLE_LOSS_* codes (include/sfm_hip.h)
 BUNDLE_LOSSES = ("squared", "huber", "cauchy")
@@ -396,54 +415,10 @@ def load() -> C.CDLL:
     lib.sfm_abi_version.argtypes = []
     lib.sfm_fit_trace_doubles.restype = C.c_int
     lib.sfm_fit_trace_doubles.argtypes = []
-    lib.sfm_score_workspace_bytes.restype = C.c_int64
-    lib.sfm_score_workspace_bytes.argtypes = [_I64, _I64, _I64]
-    lib.sfm_score_workspace_bytes_ex.restype = C.c_int64
-    lib.sfm_score_workspace_bytes_ex.argtypes = [_I64, _I64, _I64, _P]
-    lib.sfm_match_summary_workspace_bytes.restype = C.c_int64
-    lib.sfm_match_summary_workspace_bytes.argtypes = [_I64, _I64]
-    lib.sfm_hamming_summary_workspace_bytes.restype = C.c_int64
-    lib.sfm_hamming_summary_workspace_bytes.argtypes = [_I64, _I64]
-    lib.sfm_bundle_workspace_bytes.restype = C.c_int64
-    lib.sfm_bundle_workspace_bytes.argtypes = [_I64, _I64, _I64]
-    lib.sfm_bundle_calibrated_workspace_bytes.restype = C.c_int64
-    lib.sfm_bundle_calibrated_workspace_bytes.argtypes = [_I64, _I64, _I64]
-    lib.sfm_tracks_workspace_bytes.restype = C.c_int64
-    lib.sfm_tracks_workspace_bytes.argtypes = [_I64, _I64]
-    lib.sfm_tracks_robust_workspace_bytes.restype = C.c_int64
-    lib.sfm_tracks_robust_workspace_bytes.argtypes = [_I64, _I64]
-    lib.sfm_bundle_pcg_workspace_bytes.restype = C.c_int64
-    lib.sfm_bundle_pcg_workspace_bytes.argtypes = [_I64, _I64, _I64]
-    lib.sfm_bundle_pcg_workspace_bytes_ex.restype = C.c_int64
-    lib.sfm_bundle_pcg_workspace_bytes_ex.argtypes = [_I64, _I64, _I64, _P]
-    lib.sfm_build_tracks_workspace_bytes.restype = C.c_int64
-    lib.sfm_build_tracks_workspace_bytes.argtypes = [_I64, _I64, _I64]
-    lib.sfm_pair_poses_workspace_bytes.restype = C.c_int64
-    lib.sfm_pair_poses_workspace_bytes.argtypes = [_I64, _I64]
-    lib.sfm_average_rotations_workspace_bytes.restype = C.c_int64
-    lib.sfm_average_rotations_workspace_bytes.argtypes = [_I64, _I64]
-    lib.sfm_average_translations_workspace_bytes.restype = C.c_int64
-    lib.sfm_average_translations_workspace_bytes.argtypes = [_I64, _I64]
-    lib.sfm_match_pairs_workspace_bytes.restype = C.c_int64
-    lib.sfm_match_pairs_workspace_bytes.argtypes = [_I64, _I64, _I64]
-    lib.sfm_similarity_fit_workspace_bytes.restype = C.c_int64
-    lib.sfm_similarity_fit_workspace_bytes.argtypes = [_I64, _I64]
-    lib.sfm_similarity_refine_workspace_bytes.restype = C.c_int64
-    lib.sfm_similarity_refine_workspace_bytes.argtypes = [_I64, _I64]
-    lib.sfm_align_models_workspace_bytes.restype = C.c_int64
-    lib.sfm_align_models_workspace_bytes.argtypes = [_I64, _I64, _I64]
-    lib.sfm_plane_sweep_workspace_bytes.restype = C.c_int64
-    lib.sfm_plane_sweep_workspace_bytes.argtypes = [_I64] * 6
-    lib.sfm_tsdf_mesh_workspace_bytes.restype = C.c_int64
-    lib.sfm_tsdf_mesh_workspace_bytes.argtypes = [_I64] * 3
-    lib.sfm_sgm_workspace_bytes.restype = C.c_int64
-    lib.sfm_sgm_workspace_bytes.argtypes = [_I64] * 4 + [C.c_int]
-    lib.sfm_detect_keypoints_workspace_bytes.restype = C.c_int64
-    lib.sfm_detect_keypoints_workspace_bytes.argtypes = [_I64]
-    lib.sfm_build_pyramid_workspace_bytes.restype = C.c_int64
-    lib.sfm_build_pyramid_workspace_bytes.argtypes = [_I64]
-    lib.sfm_refine_observations_workspace_bytes.restype = C.c_int64
-    lib.sfm_refine_observations_workspace_bytes.argtypes = [_I64]
+    for name, argtypes in WORKSPACE_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.argtypes = argtypes
+        fn.restype = C.c_int64
     if lib.sfm_abi_version() != ABI_VERSION:
         raise NativeLibraryError(
             f"libsfm_hip.so ABI {lib.sfm_abi_version()} != expected {ABI_VERSION}; rebuild it")

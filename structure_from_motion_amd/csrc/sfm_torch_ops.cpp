@@ -2,24 +2,10 @@
 //
 // This is the thin torch-facing layer ABOVE the C ABI of include/sfm_hip.h (which stays free of torch types):
 // every op checks its tensors, takes the current HIP stream from torch and calls the matching sfm_* entry point
-// of libsfm_hip.so.  Op set = SURVEY.md §8b: normalize_coords, sample_philox, fit_eight_point, score_sed,
-// select_best, inlier_mask, cheirality, triangulate — each in a functional form (allocates its outputs; has a Meta
-// kernel, so fake-tensor tracing / torch.compile / opcheck work) and, where the engine pre-allocates its buffers
-// (device.RansacWorkspace), an in-place `_`-suffixed form with mutable arguments, plus the fused
-// sample_fit_philox_; and the PnP ops (sfm_pnp.hip) pnp_fit, pnp_score and the whole pass pnp_ransac_pass_, their P3P
-// forms p3p_fit and p3p_ransac_pass_ (sfm_p3p.h), the five-point fit five_point_fit and pass five_point_ransac_pass_
-// (sfm_five_point.hip), the homography ops homography_fit, homography_score, homography_inlier_mask and the pass
-// homography_ransac_pass_ (sfm_homography.hip), the ragged two-view pass verify_pairs_ (sfm_view_graph.hip) and the poses
-// behind it pair_poses (sfm_view_graph_pose.hip) with their refinement refine_pair_poses (sfm_view_graph_refine.hip), and
-// the refinement of a winner pnp_refine (sfm_pnp_refine.hip), the ragged absolute-pose call register_views (sfm_register_views.hip),
-// the similarity alignment similarity_ransac_pass, similarity_fit and similarity_refine (sfm_similarity.hip), the ragged
-// alignment of every pair of sub-models align_models (sfm_align_models.hip), the dense stage plane_sweep and filter_depth_maps
-// (sfm_plane_sweep.hip), the smoothing of its cost volume sgm_aggregate (sfm_sgm.hip), the fusion tsdf_integrate and
-// tsdf_extract_mesh (sfm_tsdf.hip),
-// bundle_adjust (sfm_bundle.hip, sfm_bundle_pcg.hip), triangulate_tracks (sfm_tracks.hip), build_tracks
-// (sfm_track_build.hip), average_rotations (sfm_rotation_averaging.hip) and average_translations
-// (sfm_translation_averaging.hip).  The reference call sites these serve: apps/sfm.py:110-119 (RANSAC-E), :133-138 (pose),
-// :181-186 (triangulation).
+// of libsfm_hip.so.  The TORCH_LIBRARY(sfm_hip, m) block below is the list of ops.  An op is an in-place form `x_out`
+// over the caller's buffers (`x_` in the schema; what the pre-allocating engine calls), a functional form
+// `x_new(bool meta, ...)` that allocates the outputs and, unless `meta`, fills them, or both; the device and the Meta
+// registration of each come from that one function (Forms, Noop).
 //
 // Built by structure_from_motion_amd/build.py into csrc/libsfm_torch_ops.so (host code only: no kernels here).
 #include <ATen/ATen.h>
@@ -41,19 +27,20 @@ using at::Tensor;
 // Every op runs on the device of its first tensor argument (sample_philox: of its `device` argument), not on whatever
 // device happens to be current: OpDevice makes that device current for the op's duration (the C ABI launches on the
 // current device), current_stream() is that device's current torch stream, and need() refuses a tensor that lives
-// elsewhere — a kernel handed pointers of two GPUs would fault or race.
+// elsewhere — a kernel handed pointers of two GPUs would fault or race.  A Meta form (`meta`) runs nothing and has no device.
 thread_local const c10::Device* g_op_device = nullptr;
 
 struct OpDevice {
     c10::Device device;
     c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard;
     const c10::Device* outer;
-    explicit OpDevice(const c10::Device& d) : device(d), outer(g_op_device) {
+    explicit OpDevice(const c10::Device& d, bool meta = false) : device(d), outer(g_op_device) {
+        if (meta) return;
         TORCH_CHECK(d.is_cuda(), "sfm_hip: expected a ROCm device, got ", d);
         guard.set_device(d);
         g_op_device = &device;
     }
-    explicit OpDevice(const Tensor& first) : OpDevice(first.device()) {}
+    explicit OpDevice(const Tensor& first, bool meta = false) : OpDevice(first.device(), meta) {}
     ~OpDevice() { g_op_device = outer; }
     OpDevice(const OpDevice&) = delete;
     OpDevice& operator=(const OpDevice&) = delete;
@@ -87,9 +74,38 @@ T* ptr(const std::optional<Tensor>& t) {
 
 at::TensorOptions like(const Tensor& t, at::ScalarType dtype) { return t.options().dtype(dtype); }
 
+// A new tensor beside `t`.  Its sizes are SymInt, taken with sym_size(): a functional form states each output's shape once,
+// for real tensors and for fake ones (under dynamic-shape tracing sizes are symbolic, and size() / sizes() / numel() are
+// not available: value checks stay with the in-place forms).
+using c10::SymInt;
+
+Tensor alloc(const Tensor& t, at::ScalarType dtype, std::initializer_list<SymInt> shape) {
+    return at::empty_symint(c10::SymIntArrayRef(shape.begin(), shape.size()), like(t, dtype));
+}
+
+// The two registrations of a functional form x_new(bool meta, ...): Forms<&x_new>::call<false> under the device key,
+// call<true> under Meta
+template <auto Fn>
+struct Forms;
+template <typename R, typename... A, R (*Fn)(bool, A...)>
+struct Forms<Fn> {
+    template <bool META>
+    static R call(A... a) {
+        return Fn(META, std::forward<A>(a)...);
+    }
+};
+
+// The Meta registration of an in-place form x_out: its parameter list and nothing to do, the caller's buffers fix every shape
+template <auto Fn>
+struct Noop;
+template <typename... A, void (*Fn)(A...)>
+struct Noop<Fn> {
+    static void call(A...) {}
+};
+
 constexpr int64_t kRecordWords = sizeof(sfm_select_result) / 8;
 
-// ---- shape helpers shared by the device and Meta kernels -------------------------------------------------------
+// ---- shape helpers --------------------------------------------------------------------------------------------
 struct Dims {
     int64_t batch, n, h;
 };
@@ -127,26 +143,14 @@ void normalize_coords_out(const Tensor& pix_a, const Tensor& pix_b, double fx, d
        "sfm_normalize_correspondences");
 }
 
-std::vector<int64_t> normalized_shape(const Tensor& pix_a) {
-    TORCH_CHECK(pix_a.dim() >= 1 && pix_a.size(-1) == 2, "sfm_hip: pix_a must be [..., 2]");
-    std::vector<int64_t> shape(pix_a.sizes().begin(), pix_a.sizes().end());
+Tensor normalize_coords_new(bool meta, const Tensor& pix_a, const Tensor& pix_b, double fx, double fy, double cx, double cy) {
+    TORCH_CHECK(pix_a.dim() >= 1 && (meta ? pix_a.dim() == pix_b.dim() : pix_a.size(-1) == 2),
+                meta ? "sfm_hip: pix_a, pix_b must be [..., 2] of equal shape" : "sfm_hip: pix_a must be [..., 2]");
+    std::vector<SymInt> shape(pix_a.sym_sizes().begin(), pix_a.sym_sizes().end());
     shape.back() = 4;
-    return shape;
-}
-
-Tensor normalize_coords(const Tensor& pix_a, const Tensor& pix_b, double fx, double fy, double cx, double cy) {
-    Tensor out = at::empty(normalized_shape(pix_a), pix_a.options());
-    normalize_coords_out(pix_a, pix_b, fx, fy, cx, cy, out);
+    Tensor out = at::empty_symint(shape, pix_a.options());
+    if (!meta) normalize_coords_out(pix_a, pix_b, fx, fy, cx, cy, out);
     return out;
-}
-
-// Meta kernels: shapes only, through the SymInt accessors (they also run under dynamic-shape tracing, where sizes
-// are symbolic and numel() / sizes() are not available); value checks stay with the device kernels.
-Tensor normalize_coords_meta(const Tensor& pix_a, const Tensor& pix_b, double, double, double, double) {
-    TORCH_CHECK(pix_a.dim() >= 1 && pix_a.dim() == pix_b.dim(), "sfm_hip: pix_a, pix_b must be [..., 2] of equal shape");
-    std::vector<c10::SymInt> shape(pix_a.sym_sizes().begin(), pix_a.sym_sizes().end());
-    shape.back() = 4;
-    return at::empty_symint(shape, pix_a.options());
 }
 
 // ---- sample_philox ---------------------------------------------------------------------------------------------
@@ -190,25 +194,21 @@ void five_point_fit_out(const Tensor& corr, const Tensor& S, Tensor& E, Tensor& 
     essential_fit(sfm_five_point_fit, "sfm_five_point_fit", corr, S, E, flags);
 }
 
-// the allocating form of an in-place fit
-template <void (*FitOut)(const Tensor&, const Tensor&, Tensor&, Tensor&)>
-std::tuple<Tensor, Tensor> essential_fit_new(const Tensor& corr, const Tensor& S) {
-    const Dims d = hypothesis_dims(corr, S);
-    Tensor E = at::empty({d.batch, d.h, 9}, like(corr, at::kDouble));
-    Tensor flags = at::empty({d.batch, d.h}, like(corr, at::kInt));
-    FitOut(corr, S, E, flags);
-    return {E, flags};
-}
-
-void meta_dims(const Tensor& corr, const Tensor& S) {
+// what a functional form over corr and S checks before it allocates: the ranks, and on the device the other sizes
+void fit_dims(bool meta, const Tensor& corr, const Tensor& S) {
     TORCH_CHECK(corr.dim() == 3, "sfm_hip: corr must be [batch, n, 4]");
     TORCH_CHECK(S.dim() == 3, "sfm_hip: S must be [batch, h, 8]");
+    if (!meta) hypothesis_dims(corr, S);
 }
 
-std::tuple<Tensor, Tensor> fit_eight_point_meta(const Tensor& corr, const Tensor& S) {
-    meta_dims(corr, S);
-    return {at::empty_symint({corr.sym_size(0), S.sym_size(1), 9}, like(corr, at::kDouble)),
-            at::empty_symint({corr.sym_size(0), S.sym_size(1)}, like(corr, at::kInt))};
+// the allocating form of an in-place fit
+template <void (*FitOut)(const Tensor&, const Tensor&, Tensor&, Tensor&)>
+std::tuple<Tensor, Tensor> essential_fit_new(bool meta, const Tensor& corr, const Tensor& S) {
+    fit_dims(meta, corr, S);
+    Tensor E = alloc(corr, at::kDouble, {corr.sym_size(0), S.sym_size(1), 9});
+    Tensor flags = alloc(corr, at::kInt, {corr.sym_size(0), S.sym_size(1)});
+    if (!meta) FitOut(corr, S, E, flags);
+    return {E, flags};
 }
 
 // The tensors every whole-pass op takes, checked: `items` ("corr" / "pts") and `model` ("E" / "model") by their names in the
@@ -291,24 +291,17 @@ void score_sed_out(const Tensor& corr, const Tensor& E, const Tensor& S, double 
 }
 
 // exact = the all-fp64 kernel; otherwise the two-tier kernel (needs a scratch buffer, allocated here)
-std::tuple<Tensor, Tensor, Tensor> score_sed(const Tensor& corr, const Tensor& E, const Tensor& S, double thr,
-                                             bool exact) {
-    const Dims d = hypothesis_dims(corr, S);
-    Tensor cnt = at::empty({d.batch, d.h}, like(corr, at::kInt));
-    Tensor s1 = at::empty({d.batch, d.h}, like(corr, at::kDouble));
-    Tensor s2 = at::empty({d.batch, d.h}, like(corr, at::kDouble));
+std::tuple<Tensor, Tensor, Tensor> score_sed_new(bool meta, const Tensor& corr, const Tensor& E, const Tensor& S, double thr,
+                                                 bool exact) {
+    fit_dims(meta, corr, S);
+    TORCH_CHECK(E.dim() == 3, "sfm_hip: E must be [batch, h, 9]");
+    const SymInt b = corr.sym_size(0), h = S.sym_size(1);
+    Tensor cnt = alloc(corr, at::kInt, {b, h}), s1 = alloc(corr, at::kDouble, {b, h}), s2 = alloc(corr, at::kDouble, {b, h});
+    if (meta) return {cnt, s1, s2};
     std::optional<Tensor> workspace;
-    if (!exact) workspace = at::empty({sfm_score_workspace_bytes(d.n, d.h, d.batch)}, like(corr, at::kByte));
+    if (!exact) workspace = at::empty({sfm_score_workspace_bytes(corr.size(1), S.size(1), corr.size(0))}, like(corr, at::kByte));
     score_sed_out(corr, E, S, thr, cnt, s1, s2, workspace);
     return {cnt, s1, s2};
-}
-
-std::tuple<Tensor, Tensor, Tensor> score_sed_meta(const Tensor& corr, const Tensor& E, const Tensor& S, double, bool) {
-    meta_dims(corr, S);
-    TORCH_CHECK(E.dim() == 3, "sfm_hip: E must be [batch, h, 9]");
-    const c10::SymInt b = corr.sym_size(0), h = S.sym_size(1);
-    return {at::empty_symint({b, h}, like(corr, at::kInt)), at::empty_symint({b, h}, like(corr, at::kDouble)),
-            at::empty_symint({b, h}, like(corr, at::kDouble))};
 }
 
 // ---- fused small pass (two launches: fit + workspace preparation, scoring + selection + mask) -------------------
@@ -380,18 +373,12 @@ void select_best_out(const Tensor& cnt, const Tensor& s1, const Tensor& s2, cons
        "sfm_select_best");
 }
 
-Tensor select_best(const Tensor& cnt, const Tensor& s1, const Tensor& s2, const std::optional<Tensor>& flags,
-                   double min_extra, int64_t aggregation, int64_t h_offset, int64_t sample_size) {
+Tensor select_best_new(bool meta, const Tensor& cnt, const Tensor& s1, const Tensor& s2, const std::optional<Tensor>& flags,
+                       double min_extra, int64_t aggregation, int64_t h_offset, int64_t sample_size) {
     TORCH_CHECK(cnt.dim() == 2, "sfm_hip: cnt must be [batch, h]");
-    Tensor result = at::empty({cnt.size(0), kRecordWords}, like(cnt, at::kLong));
-    select_best_out(cnt, s1, s2, flags, min_extra, aggregation, h_offset, result, sample_size);
+    Tensor result = alloc(cnt, at::kLong, {cnt.sym_size(0), kRecordWords});
+    if (!meta) select_best_out(cnt, s1, s2, flags, min_extra, aggregation, h_offset, result, sample_size);
     return result;
-}
-
-Tensor select_best_meta(const Tensor& cnt, const Tensor&, const Tensor&, const std::optional<Tensor>&, double, int64_t,
-                        int64_t, int64_t) {
-    TORCH_CHECK(cnt.dim() == 2, "sfm_hip: cnt must be [batch, h]");
-    return at::empty_symint({cnt.sym_size(0), kRecordWords}, like(cnt, at::kLong));
 }
 
 // ---- inlier_mask -----------------------------------------------------------------------------------------------
@@ -413,54 +400,49 @@ void inlier_mask_out(const Tensor& corr, const Tensor& E, const Tensor& S, const
        "sfm_inlier_mask");
 }
 
-Tensor inlier_mask(const Tensor& corr, const Tensor& E, const Tensor& S, const Tensor& result, double thr, int64_t sample_size) {
-    const Dims d = corr_dims(corr);
-    Tensor mask = at::empty({d.batch, d.n}, like(corr, at::kByte));
-    inlier_mask_out(corr, E, S, result, thr, mask, sample_size);
+Tensor inlier_mask_new(bool meta, const Tensor& corr, const Tensor& E, const Tensor& S, const Tensor& result, double thr,
+                       int64_t sample_size) {
+    TORCH_CHECK(corr.dim() == 3, "sfm_hip: corr must be [batch, n, 4]");
+    if (!meta) corr_dims(corr);
+    Tensor mask = alloc(corr, at::kByte, {corr.sym_size(0), corr.sym_size(1)});
+    if (!meta) inlier_mask_out(corr, E, S, result, thr, mask, sample_size);
     return mask;
 }
 
-Tensor inlier_mask_meta(const Tensor& corr, const Tensor&, const Tensor&, const Tensor&, double, int64_t) {
-    TORCH_CHECK(corr.dim() == 3, "sfm_hip: corr must be [batch, n, 4]");
-    return at::empty_symint({corr.sym_size(0), corr.sym_size(1)}, like(corr, at::kByte));
-}
-
-// ---- cheirality / triangulate ------------------------------------------------------------------------------------
-Tensor cheirality(const Tensor& corr, const Tensor& pose_rt, double distance_threshold) {
-    const OpDevice scope(corr);
-    need(corr, "corr", at::kDouble);
-    need(pose_rt, "pose_rt", at::kDouble);
-    TORCH_CHECK(corr.dim() == 2 && corr.size(1) == 4, "sfm_hip: corr must be [m, 4]");
-    TORCH_CHECK(pose_rt.dim() == 2 && pose_rt.size(1) == 12, "sfm_hip: pose_rt must be [poses, 12]");
-    Tensor pass = at::empty({pose_rt.size(0), corr.size(0)}, like(corr, at::kByte));
-    ok(sfm_cheirality(ptr<double>(corr), corr.size(0), ptr<double>(pose_rt), pose_rt.size(0), distance_threshold,
-                      ptr<uint8_t>(pass), current_stream()),
-       "sfm_cheirality");
+// ---- cheirality / triangulate: no in-place form, the device's checks and the launch are in the functional one ---------
+Tensor cheirality_new(bool meta, const Tensor& corr, const Tensor& pose_rt, double distance_threshold) {
+    const OpDevice scope(corr, meta);
+    if (meta) {
+        TORCH_CHECK(corr.dim() == 2 && pose_rt.dim() == 2, "sfm_hip: corr [m, 4], pose_rt [poses, 12]");
+    } else {
+        need(corr, "corr", at::kDouble);
+        need(pose_rt, "pose_rt", at::kDouble);
+        TORCH_CHECK(corr.dim() == 2 && corr.size(1) == 4, "sfm_hip: corr must be [m, 4]");
+        TORCH_CHECK(pose_rt.dim() == 2 && pose_rt.size(1) == 12, "sfm_hip: pose_rt must be [poses, 12]");
+    }
+    Tensor pass = alloc(corr, at::kByte, {pose_rt.sym_size(0), corr.sym_size(0)});
+    if (!meta)
+        ok(sfm_cheirality(ptr<double>(corr), corr.size(0), ptr<double>(pose_rt), pose_rt.size(0), distance_threshold,
+                          ptr<uint8_t>(pass), current_stream()),
+           "sfm_cheirality");
     return pass;
 }
 
-Tensor cheirality_meta(const Tensor& corr, const Tensor& pose_rt, double) {
-    TORCH_CHECK(corr.dim() == 2 && pose_rt.dim() == 2, "sfm_hip: corr [m, 4], pose_rt [poses, 12]");
-    return at::empty_symint({pose_rt.sym_size(0), corr.sym_size(0)}, like(corr, at::kByte));
-}
-
-Tensor triangulate(const Tensor& corr, const Tensor& P1, const Tensor& P2) {
-    const OpDevice scope(corr);
-    need(corr, "corr", at::kDouble);
-    need(P1, "P1", at::kDouble);
-    need(P2, "P2", at::kDouble);
-    TORCH_CHECK(corr.dim() == 2 && corr.size(1) == 4, "sfm_hip: corr must be [m, 4]");
-    TORCH_CHECK(P1.numel() == 12 && P2.numel() == 12, "sfm_hip: P1, P2 must hold 12 doubles (rows 0..2, 4 columns)");
-    Tensor X = at::empty({corr.size(0), 3}, corr.options());
-    ok(sfm_triangulate(ptr<double>(corr), corr.size(0), ptr<double>(P1), ptr<double>(P2), ptr<double>(X),
-                       current_stream()),
-       "sfm_triangulate");
+Tensor triangulate_new(bool meta, const Tensor& corr, const Tensor& P1, const Tensor& P2) {
+    const OpDevice scope(corr, meta);
+    if (!meta) {
+        need(corr, "corr", at::kDouble);
+        need(P1, "P1", at::kDouble);
+        need(P2, "P2", at::kDouble);
+    }
+    TORCH_CHECK(corr.dim() == 2 && (meta || corr.size(1) == 4), "sfm_hip: corr must be [m, 4]");
+    if (!meta) TORCH_CHECK(P1.numel() == 12 && P2.numel() == 12, "sfm_hip: P1, P2 must hold 12 doubles (rows 0..2, 4 columns)");
+    Tensor X = at::empty_symint({corr.sym_size(0), 3}, corr.options());
+    if (!meta)
+        ok(sfm_triangulate(ptr<double>(corr), corr.size(0), ptr<double>(P1), ptr<double>(P2), ptr<double>(X),
+                           current_stream()),
+           "sfm_triangulate");
     return X;
-}
-
-Tensor triangulate_meta(const Tensor& corr, const Tensor&, const Tensor&) {
-    TORCH_CHECK(corr.dim() == 2, "sfm_hip: corr must be [m, 4]");
-    return at::empty_symint({corr.sym_size(0), 3}, corr.options());
 }
 
 
@@ -473,50 +455,47 @@ void homography_fit_out(const Tensor& corr, const Tensor& S, Tensor& H, Tensor& 
     essential_fit(sfm_homography_fit, "sfm_homography_fit", corr, S, H, flags);
 }
 
-std::tuple<Tensor, Tensor, Tensor> homography_score(const Tensor& corr, const Tensor& H, const Tensor& S, double thr) {
-    const OpDevice scope(corr);
-    need(corr, "corr", at::kDouble);
-    need(H, "H", at::kDouble);
-    need(S, "S", at::kInt);
+// no in-place form of these two: the device's checks and the launch are in the functional one
+std::tuple<Tensor, Tensor, Tensor> homography_score_new(bool meta, const Tensor& corr, const Tensor& H, const Tensor& S, double thr) {
+    const OpDevice scope(corr, meta);
+    if (!meta) {
+        need(corr, "corr", at::kDouble);
+        need(H, "H", at::kDouble);
+        need(S, "S", at::kInt);
+    }
+    fit_dims(meta, corr, S);
+    TORCH_CHECK(H.dim() == 3, "sfm_hip: H must be [batch, h, 9]");
+    const SymInt b = corr.sym_size(0), h = S.sym_size(1);
+    Tensor cnt = alloc(corr, at::kInt, {b, h}), s1 = alloc(corr, at::kDouble, {b, h}), s2 = alloc(corr, at::kDouble, {b, h});
+    if (meta) return {cnt, s1, s2};
     const Dims d = hypothesis_dims(corr, S);
     check_H(H, d);
-    Tensor cnt = at::empty({d.batch, d.h}, like(corr, at::kInt));
-    Tensor s1 = at::empty({d.batch, d.h}, like(corr, at::kDouble));
-    Tensor s2 = at::empty({d.batch, d.h}, like(corr, at::kDouble));
     ok(sfm_homography_score(ptr<double>(corr), d.n, ptr<double>(H), ptr<int32_t>(S), d.h, d.batch, thr, ptr<int32_t>(cnt),
                             ptr<double>(s1), ptr<double>(s2), current_stream()),
        "sfm_homography_score");
     return {cnt, s1, s2};
 }
 
-std::tuple<Tensor, Tensor, Tensor> homography_score_meta(const Tensor& corr, const Tensor& H, const Tensor& S, double) {
-    meta_dims(corr, S);
-    TORCH_CHECK(H.dim() == 3, "sfm_hip: H must be [batch, h, 9]");
-    const c10::SymInt b = corr.sym_size(0), h = S.sym_size(1);
-    return {at::empty_symint({b, h}, like(corr, at::kInt)), at::empty_symint({b, h}, like(corr, at::kDouble)),
-            at::empty_symint({b, h}, like(corr, at::kDouble))};
-}
-
-Tensor homography_inlier_mask(const Tensor& corr, const Tensor& H, const Tensor& S, const Tensor& result, double thr) {
-    const OpDevice scope(corr);
-    need(corr, "corr", at::kDouble);
-    need(H, "H", at::kDouble);
-    need(S, "S", at::kInt);
-    need(result, "result", at::kLong);
-    const Dims d = hypothesis_dims(corr, S);
-    check_H(H, d);
-    TORCH_CHECK(result.numel() == d.batch * kRecordWords, "sfm_hip: result must be int64 [batch, 5]");
-    Tensor mask = at::empty({d.batch, d.n}, like(corr, at::kByte));
-    ok(sfm_homography_inlier_mask(ptr<double>(corr), d.n, ptr<double>(H), ptr<int32_t>(S), d.h, d.batch,
-                                  reinterpret_cast<const sfm_select_result*>(ptr<int64_t>(result)), thr, ptr<uint8_t>(mask),
-                                  current_stream()),
-       "sfm_homography_inlier_mask");
-    return mask;
-}
-
-Tensor homography_inlier_mask_meta(const Tensor& corr, const Tensor&, const Tensor&, const Tensor&, double) {
+Tensor homography_inlier_mask_new(bool meta, const Tensor& corr, const Tensor& H, const Tensor& S, const Tensor& result, double thr) {
+    const OpDevice scope(corr, meta);
     TORCH_CHECK(corr.dim() == 3, "sfm_hip: corr must be [batch, n, 4]");
-    return at::empty_symint({corr.sym_size(0), corr.sym_size(1)}, like(corr, at::kByte));
+    Dims d{};
+    if (!meta) {
+        need(corr, "corr", at::kDouble);
+        need(H, "H", at::kDouble);
+        need(S, "S", at::kInt);
+        need(result, "result", at::kLong);
+        d = hypothesis_dims(corr, S);
+        check_H(H, d);
+        TORCH_CHECK(result.numel() == d.batch * kRecordWords, "sfm_hip: result must be int64 [batch, 5]");
+    }
+    Tensor mask = alloc(corr, at::kByte, {corr.sym_size(0), corr.sym_size(1)});
+    if (!meta)
+        ok(sfm_homography_inlier_mask(ptr<double>(corr), d.n, ptr<double>(H), ptr<int32_t>(S), d.h, d.batch,
+                                      reinterpret_cast<const sfm_select_result*>(ptr<int64_t>(result)), thr, ptr<uint8_t>(mask),
+                                      current_stream()),
+           "sfm_homography_inlier_mask");
+    return mask;
 }
 
 // the whole homography pass (sfm_homography_ransac_pass): the arguments of five_point_ransac_pass_ with H for E
@@ -580,26 +559,41 @@ void verify_pairs_out(const Tensor& corr, const Tensor& offset, const Tensor& mi
 // ---- relative pose and triangulation angle of every pair behind verify_pairs_ (sfm_view_graph_pose.hip), on that op's tensors:
 // -> (pose uint8 [pairs, 128], the sfm_pair_pose records; angle double [n_total], each item's angle under its pair's best pose,
 // NaN off the passing inliers: the head of the call's workspace) ------------------------------------------------------------
-std::tuple<Tensor, Tensor> pair_poses(const Tensor& corr, const Tensor& offset, const Tensor& E, const Tensor& e_result,
-                                      const Tensor& e_mask, const Tensor& verdict, double distance_threshold) {
-    const OpDevice scope(corr);
-    static_assert(sizeof(sfm_pair_pose) == 128, "pose rows are 128 bytes");
-    need(corr, "corr", at::kDouble);
-    need(offset, "offset", at::kLong);
-    need(E, "E", at::kDouble);
-    need(e_result, "e_result", at::kLong);
-    need(e_mask, "e_mask", at::kByte);
-    need(verdict, "verdict", at::kLong);
+// what the two ops behind verify_pairs_ check of corr and offset before they allocate -> n_total, pairs (0, 0 under Meta)
+std::pair<int64_t, int64_t> ragged_pair_dims(bool meta, const Tensor& corr, const Tensor& offset) {
+    if (meta) {
+        TORCH_CHECK(corr.dim() == 2 && offset.dim() == 1, "sfm_hip: corr must be [n_total, 4], offset int64 [pairs + 1]");
+        return {0, 0};
+    }
     TORCH_CHECK(corr.dim() == 2 && corr.size(1) == 4, "sfm_hip: corr must be [n_total, 4]");
     TORCH_CHECK(offset.dim() == 1 && offset.size(0) >= 1, "sfm_hip: offset must be int64 [pairs + 1]");
-    const int64_t n_total = corr.size(0), pairs = offset.size(0) - 1;
-    TORCH_CHECK(E.dim() == 3 && E.size(0) == pairs && E.size(1) >= 1 && E.size(2) == 9, "sfm_hip: E must be [pairs, h >= 1, 9]");
-    TORCH_CHECK(e_result.numel() == pairs * kRecordWords, "sfm_hip: e_result must be int64 [pairs, 5]");
-    TORCH_CHECK(e_mask.numel() == n_total, "sfm_hip: e_mask must be uint8 [n_total]");
-    TORCH_CHECK(verdict.numel() == pairs * 3, "sfm_hip: verdict must be int64 [pairs, 3]");
-    const int64_t bytes = sfm_pair_poses_workspace_bytes(n_total, pairs);
-    TORCH_CHECK(bytes >= 0, "sfm_hip: pair_poses takes at most 65535 pairs and fewer than 2^31 items");
-    Tensor pose = at::empty({pairs, 128}, like(corr, at::kByte));
+    return {corr.size(0), offset.size(0) - 1};
+}
+
+std::tuple<Tensor, Tensor> pair_poses_new(bool meta, const Tensor& corr, const Tensor& offset, const Tensor& E, const Tensor& e_result,
+                                          const Tensor& e_mask, const Tensor& verdict, double distance_threshold) {
+    const OpDevice scope(corr, meta);
+    static_assert(sizeof(sfm_pair_pose) == 128, "pose rows are 128 bytes");
+    if (!meta) {
+        need(corr, "corr", at::kDouble);
+        need(offset, "offset", at::kLong);
+        need(E, "E", at::kDouble);
+        need(e_result, "e_result", at::kLong);
+        need(e_mask, "e_mask", at::kByte);
+        need(verdict, "verdict", at::kLong);
+    }
+    const auto [n_total, pairs] = ragged_pair_dims(meta, corr, offset);
+    int64_t bytes = 0;
+    if (!meta) {
+        TORCH_CHECK(E.dim() == 3 && E.size(0) == pairs && E.size(1) >= 1 && E.size(2) == 9, "sfm_hip: E must be [pairs, h >= 1, 9]");
+        TORCH_CHECK(e_result.numel() == pairs * kRecordWords, "sfm_hip: e_result must be int64 [pairs, 5]");
+        TORCH_CHECK(e_mask.numel() == n_total, "sfm_hip: e_mask must be uint8 [n_total]");
+        TORCH_CHECK(verdict.numel() == pairs * 3, "sfm_hip: verdict must be int64 [pairs, 3]");
+        bytes = sfm_pair_poses_workspace_bytes(n_total, pairs);
+        TORCH_CHECK(bytes >= 0, "sfm_hip: pair_poses takes at most 65535 pairs and fewer than 2^31 items");
+    }
+    Tensor pose = alloc(corr, at::kByte, {offset.sym_size(0) - 1, 128});
+    if (meta) return {pose, alloc(corr, at::kDouble, {corr.sym_size(0)})};   // angle: on the device the head of the workspace
     Tensor workspace = at::empty({(bytes + 7) / 8}, like(corr, at::kDouble));
     if (pairs == 0) workspace.fill_(NAN);   // the entry is a no-op then: no item has a pair
     ok(sfm_pair_poses(ptr<double>(corr), n_total, ptr<int64_t>(offset), pairs, ptr<double>(E), E.size(1),
@@ -610,34 +604,30 @@ std::tuple<Tensor, Tensor> pair_poses(const Tensor& corr, const Tensor& offset, 
     return {pose, workspace.narrow(0, 0, n_total)};
 }
 
-std::tuple<Tensor, Tensor> pair_poses_meta(const Tensor& corr, const Tensor& offset, const Tensor&, const Tensor&, const Tensor&,
-                                           const Tensor&, double) {
-    TORCH_CHECK(corr.dim() == 2 && offset.dim() == 1, "sfm_hip: corr must be [n_total, 4], offset int64 [pairs + 1]");
-    return {at::empty_symint({offset.sym_size(0) - 1, 128}, like(corr, at::kByte)),
-            at::empty_symint({corr.sym_size(0)}, like(corr, at::kDouble))};
-}
-
 // ---- refinement of every pair's pose on its inliers behind pair_poses (sfm_view_graph_refine.hip): pose uint8 [pairs, 128] as
 // pair_poses returned it -> (pose_out uint8 [pairs, 128]; mask uint8 [n_total], 1 = within thr under the kept pose; info int64
 // [pairs, 5] viewing the sfm_pair_refine_info records) ------------------------------------------------------------------------
 constexpr int64_t kPairRefineInfoWords = sizeof(sfm_pair_refine_info) / 8;
 
-std::tuple<Tensor, Tensor, Tensor> refine_pair_poses(const Tensor& corr, const Tensor& offset, const Tensor& pose, double thr,
-                                                     int64_t aggregation, int64_t rounds, int64_t max_steps) {
-    const OpDevice scope(corr);
+std::tuple<Tensor, Tensor, Tensor> refine_pair_poses_new(bool meta, const Tensor& corr, const Tensor& offset, const Tensor& pose,
+                                                         double thr, int64_t aggregation, int64_t rounds, int64_t max_steps) {
+    const OpDevice scope(corr, meta);
     static_assert(sizeof(sfm_pair_pose) == 128 && sizeof(sfm_pair_refine_info) == 40, "pose rows are 128 bytes, info rows 40");
-    need(corr, "corr", at::kDouble);
-    need(offset, "offset", at::kLong);
-    need(pose, "pose", at::kByte);
-    TORCH_CHECK(corr.dim() == 2 && corr.size(1) == 4, "sfm_hip: corr must be [n_total, 4]");
-    TORCH_CHECK(offset.dim() == 1 && offset.size(0) >= 1, "sfm_hip: offset must be int64 [pairs + 1]");
-    const int64_t n_total = corr.size(0), pairs = offset.size(0) - 1;
-    TORCH_CHECK(pose.numel() == pairs * 128, "sfm_hip: pose must be uint8 [pairs, 128]");
-    TORCH_CHECK(rounds >= 0 && rounds <= 0x7FFFFFFF && max_steps >= 0 && max_steps <= 0x7FFFFFFF,
-                "sfm_hip: rounds and max_steps must be in [0, 2^31)");
-    Tensor pose_out = at::empty({pairs, 128}, like(corr, at::kByte));
-    Tensor mask = at::empty({n_total}, like(corr, at::kByte));
-    Tensor info = at::empty({pairs, kPairRefineInfoWords}, like(corr, at::kLong));
+    if (!meta) {
+        need(corr, "corr", at::kDouble);
+        need(offset, "offset", at::kLong);
+        need(pose, "pose", at::kByte);
+    }
+    const auto [n_total, pairs] = ragged_pair_dims(meta, corr, offset);
+    if (!meta) {
+        TORCH_CHECK(pose.numel() == pairs * 128, "sfm_hip: pose must be uint8 [pairs, 128]");
+        TORCH_CHECK(rounds >= 0 && rounds <= 0x7FFFFFFF && max_steps >= 0 && max_steps <= 0x7FFFFFFF,
+                    "sfm_hip: rounds and max_steps must be in [0, 2^31)");
+    }
+    Tensor pose_out = alloc(corr, at::kByte, {offset.sym_size(0) - 1, 128});
+    Tensor mask = alloc(corr, at::kByte, {corr.sym_size(0)});
+    Tensor info = alloc(corr, at::kLong, {offset.sym_size(0) - 1, kPairRefineInfoWords});
+    if (meta) return {pose_out, mask, info};
     if (pairs == 0) mask.zero_();   // the entry is a no-op then: no item has a pair
     ok(sfm_refine_pair_poses(ptr<double>(corr), n_total, ptr<int64_t>(offset), pairs,
                              reinterpret_cast<const sfm_pair_pose*>(ptr<uint8_t>(pose)), thr, (int)aggregation, (int)rounds,
@@ -647,20 +637,21 @@ std::tuple<Tensor, Tensor, Tensor> refine_pair_poses(const Tensor& corr, const T
     return {pose_out, mask, info};
 }
 
-std::tuple<Tensor, Tensor, Tensor> refine_pair_poses_meta(const Tensor& corr, const Tensor& offset, const Tensor&, double, int64_t,
-                                                          int64_t, int64_t) {
-    TORCH_CHECK(corr.dim() == 2 && offset.dim() == 1, "sfm_hip: corr must be [n_total, 4], offset int64 [pairs + 1]");
-    return {at::empty_symint({offset.sym_size(0) - 1, 128}, like(corr, at::kByte)),
-            at::empty_symint({corr.sym_size(0)}, like(corr, at::kByte)),
-            at::empty_symint({offset.sym_size(0) - 1, c10::SymInt(kPairRefineInfoWords)}, like(corr, at::kLong))};
-}
-
 // ---- PnP (sfm_pnp.hip): pts [batch, n, 5] = {X, Y, Z, u, v}, K 9 doubles (row-major, row 2 = 0 0 1), S [batch, h, 8],
 // model [batch, h, 12] = R (9) | t (3) ----------------------------------------------------------------------------------
 Dims pnp_dims(const Tensor& pts, const Tensor& S) {
     TORCH_CHECK(pts.dim() == 3 && pts.size(2) == 5, "sfm_hip: pts must be [batch, n, 5]");
     TORCH_CHECK(S.dim() == 3 && S.size(0) == pts.size(0) && S.size(2) == 8, "sfm_hip: S must be [batch, h, 8]");
     return {pts.size(0), pts.size(1), S.size(1)};
+}
+
+// what a functional form over pts and S checks before it allocates: under Meta the ranks alone, in words of its own
+void pose_dims(bool meta, const Tensor& pts, const Tensor& S) {
+    if (meta) {
+        TORCH_CHECK(pts.dim() == 3 && S.dim() == 3, "sfm_hip: pts [batch, n, 5], S [batch, h, 8]");
+    } else {
+        pnp_dims(pts, S);
+    }
 }
 
 void check_K(at::ArrayRef<double> K) { TORCH_CHECK(K.size() == 9, "sfm_hip: K must hold 9 doubles (3 x 3, row-major)"); }
@@ -697,18 +688,12 @@ void p3p_fit_out(const Tensor& pts, const Tensor& S, at::ArrayRef<double> K, Ten
 }
 
 template <void (*FitOut)(const Tensor&, const Tensor&, at::ArrayRef<double>, Tensor&, Tensor&)>
-std::tuple<Tensor, Tensor> pose_fit_new(const Tensor& pts, const Tensor& S, at::ArrayRef<double> K) {
-    const Dims d = pnp_dims(pts, S);
-    Tensor model = at::empty({d.batch, d.h, 12}, like(pts, at::kDouble));
-    Tensor flags = at::empty({d.batch, d.h}, like(pts, at::kInt));
-    FitOut(pts, S, K, model, flags);
+std::tuple<Tensor, Tensor> pose_fit_new(bool meta, const Tensor& pts, const Tensor& S, at::ArrayRef<double> K) {
+    pose_dims(meta, pts, S);
+    Tensor model = alloc(pts, at::kDouble, {pts.sym_size(0), S.sym_size(1), 12});
+    Tensor flags = alloc(pts, at::kInt, {pts.sym_size(0), S.sym_size(1)});
+    if (!meta) FitOut(pts, S, K, model, flags);
     return {model, flags};
-}
-
-std::tuple<Tensor, Tensor> pnp_fit_meta(const Tensor& pts, const Tensor& S, at::ArrayRef<double>) {
-    TORCH_CHECK(pts.dim() == 3 && S.dim() == 3, "sfm_hip: pts [batch, n, 5], S [batch, h, 8]");
-    return {at::empty_symint({pts.sym_size(0), S.sym_size(1), 12}, like(pts, at::kDouble)),
-            at::empty_symint({pts.sym_size(0), S.sym_size(1)}, like(pts, at::kInt))};
 }
 
 void pnp_score_out(const Tensor& pts, const Tensor& model, const Tensor& S, at::ArrayRef<double> K, double thr, Tensor& cnt,
@@ -730,22 +715,13 @@ void pnp_score_out(const Tensor& pts, const Tensor& model, const Tensor& S, at::
        "sfm_pnp_score");
 }
 
-std::tuple<Tensor, Tensor, Tensor> pnp_score(const Tensor& pts, const Tensor& model, const Tensor& S, at::ArrayRef<double> K,
-                                             double thr, int64_t sample_size) {
-    const Dims d = pnp_dims(pts, S);
-    Tensor cnt = at::empty({d.batch, d.h}, like(pts, at::kInt));
-    Tensor s1 = at::empty({d.batch, d.h}, like(pts, at::kDouble));
-    Tensor s2 = at::empty({d.batch, d.h}, like(pts, at::kDouble));
-    pnp_score_out(pts, model, S, K, thr, cnt, s1, s2, sample_size);
+std::tuple<Tensor, Tensor, Tensor> pnp_score_new(bool meta, const Tensor& pts, const Tensor& model, const Tensor& S,
+                                                 at::ArrayRef<double> K, double thr, int64_t sample_size) {
+    pose_dims(meta, pts, S);
+    const SymInt b = pts.sym_size(0), h = S.sym_size(1);
+    Tensor cnt = alloc(pts, at::kInt, {b, h}), s1 = alloc(pts, at::kDouble, {b, h}), s2 = alloc(pts, at::kDouble, {b, h});
+    if (!meta) pnp_score_out(pts, model, S, K, thr, cnt, s1, s2, sample_size);
     return {cnt, s1, s2};
-}
-
-std::tuple<Tensor, Tensor, Tensor> pnp_score_meta(const Tensor& pts, const Tensor&, const Tensor& S, at::ArrayRef<double>,
-                                                  double, int64_t) {
-    TORCH_CHECK(pts.dim() == 3 && S.dim() == 3, "sfm_hip: pts [batch, n, 5], S [batch, h, 8]");
-    return {at::empty_symint({pts.sym_size(0), S.sym_size(1)}, like(pts, at::kInt)),
-            at::empty_symint({pts.sym_size(0), S.sym_size(1)}, like(pts, at::kDouble)),
-            at::empty_symint({pts.sym_size(0), S.sym_size(1)}, like(pts, at::kDouble))};
 }
 
 // the whole pass of `solver` into the caller's buffers (device.PnPWorkspace); `mask` optional
@@ -806,23 +782,15 @@ void pnp_refine_out(const Tensor& pts, const Tensor& model, const Tensor& mask, 
        "sfm_pnp_refine");
 }
 
-std::tuple<Tensor, Tensor, Tensor> pnp_refine(const Tensor& pts, const Tensor& model, const Tensor& mask, const Tensor& err,
-                                              at::ArrayRef<double> K, double thr, int64_t aggregation, int64_t rounds,
-                                              int64_t max_steps) {
+std::tuple<Tensor, Tensor, Tensor> pnp_refine_new(bool meta, const Tensor& pts, const Tensor& model, const Tensor& mask,
+                                                  const Tensor& err, at::ArrayRef<double> K, double thr, int64_t aggregation,
+                                                  int64_t rounds, int64_t max_steps) {
     TORCH_CHECK(pts.dim() == 3, "sfm_hip: pts must be [batch, n, 5]");
-    Tensor model_out = at::empty({pts.size(0), 12}, like(pts, at::kDouble));
-    Tensor mask_out = at::empty({pts.size(0), pts.size(1)}, like(pts, at::kByte));
-    Tensor info = at::empty({pts.size(0), kRefineInfoWords}, like(pts, at::kLong));
-    pnp_refine_out(pts, model, mask, err, K, thr, aggregation, rounds, max_steps, model_out, mask_out, info);
+    Tensor model_out = alloc(pts, at::kDouble, {pts.sym_size(0), 12});
+    Tensor mask_out = alloc(pts, at::kByte, {pts.sym_size(0), pts.sym_size(1)});
+    Tensor info = alloc(pts, at::kLong, {pts.sym_size(0), kRefineInfoWords});
+    if (!meta) pnp_refine_out(pts, model, mask, err, K, thr, aggregation, rounds, max_steps, model_out, mask_out, info);
     return {model_out, mask_out, info};
-}
-
-std::tuple<Tensor, Tensor, Tensor> pnp_refine_meta(const Tensor& pts, const Tensor&, const Tensor&, const Tensor&,
-                                                   at::ArrayRef<double>, double, int64_t, int64_t, int64_t) {
-    TORCH_CHECK(pts.dim() == 3, "sfm_hip: pts must be [batch, n, 5]");
-    return {at::empty_symint({pts.sym_size(0), 12}, like(pts, at::kDouble)),
-            at::empty_symint({pts.sym_size(0), pts.sym_size(1)}, like(pts, at::kByte)),
-            at::empty_symint({pts.sym_size(0), c10::SymInt(kRefineInfoWords)}, like(pts, at::kLong))};
 }
 
 // ---- absolute pose of every candidate view in one call (sfm_register_views.hip): pts [n_total, 5], offset int64 [views + 1],
@@ -871,40 +839,40 @@ void register_views_out(const Tensor& pts, const Tensor& offset, const Tensor& m
 
 // the functional form: h hypotheses per view -> (pose_out, mask_out, info, status, mask, result); the tables of the pass are
 // temporaries of the call
-std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> register_views(const Tensor& pts, const Tensor& offset,
-                                                                          const Tensor& min_extra, at::ArrayRef<double> K, int64_t seed,
-                                                                          int64_t seed_stride, int64_t h_begin, int64_t h, double thr,
-                                                                          int64_t aggregation, int64_t refine_rounds,
-                                                                          int64_t refine_max_steps) {
-    TORCH_CHECK(pts.dim() == 2 && offset.dim() == 1 && offset.size(0) >= 1, "sfm_hip: pts must be [n_total, 5], offset int64 [views + 1]");
-    TORCH_CHECK(h >= 1, "sfm_hip: register_views needs at least one hypothesis per view");
-    const int64_t n_total = pts.size(0), views = offset.size(0) - 1;
-    Tensor S = at::empty({views, h, 8}, like(pts, at::kInt)), model = at::empty({views, h, 12}, like(pts, at::kDouble));
-    Tensor flags = at::empty({views, h}, like(pts, at::kInt)), cnt = at::empty({views, h}, like(pts, at::kInt));
-    Tensor s1 = at::empty({views, h}, like(pts, at::kDouble)), s2 = at::empty({views, h}, like(pts, at::kDouble));
-    Tensor result = at::empty({views, kRecordWords}, like(pts, at::kLong));
-    Tensor mask = at::empty({n_total}, like(pts, at::kByte)), mask_out = at::empty({n_total}, like(pts, at::kByte));
-    Tensor pose_out = at::empty({views, 12}, like(pts, at::kDouble));
-    Tensor info = at::empty({views, kRefineInfoWords}, like(pts, at::kLong));
-    Tensor status = at::empty({views}, like(pts, at::kInt));
-    if (views == 0) {   // the entry is a no-op then: no item has a view
-        mask.zero_();
-        mask_out.zero_();
-    }
-    register_views_out(pts, offset, min_extra, K, seed, seed_stride, h_begin, thr, aggregation, refine_rounds, refine_max_steps, S, model,
-                       flags, cnt, s1, s2, result, mask, pose_out, mask_out, info, status);
-    return {pose_out, mask_out, info, status, mask, result};
-}
+// The tables of a ragged pass over `rows` groups with h hypotheses each, temporaries of a functional call: S, model [rows, h,
+// width], flags, cnt, s1, s2
+struct PassTables {
+    Tensor S, model, flags, cnt, s1, s2;
+    PassTables(const Tensor& t, const SymInt& rows, int64_t h, int64_t width)
+        : S(alloc(t, at::kInt, {rows, h, 8})), model(alloc(t, at::kDouble, {rows, h, width})), flags(alloc(t, at::kInt, {rows, h})),
+          cnt(alloc(t, at::kInt, {rows, h})), s1(alloc(t, at::kDouble, {rows, h})), s2(alloc(t, at::kDouble, {rows, h})) {}
+};
 
-std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> register_views_meta(const Tensor& pts, const Tensor& offset, const Tensor&,
-                                                                               at::ArrayRef<double>, int64_t, int64_t, int64_t, int64_t,
-                                                                               double, int64_t, int64_t, int64_t) {
-    TORCH_CHECK(pts.dim() == 2 && offset.dim() == 1, "sfm_hip: pts must be [n_total, 5], offset int64 [views + 1]");
-    const c10::SymInt views = offset.sym_size(0) - 1;
-    return {at::empty_symint({views, c10::SymInt(12)}, like(pts, at::kDouble)), at::empty_symint({pts.sym_size(0)}, like(pts, at::kByte)),
-            at::empty_symint({views, c10::SymInt(kRefineInfoWords)}, like(pts, at::kLong)), at::empty_symint({views}, like(pts, at::kInt)),
-            at::empty_symint({pts.sym_size(0)}, like(pts, at::kByte)),
-            at::empty_symint({views, c10::SymInt(kRecordWords)}, like(pts, at::kLong))};
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> register_views_new(bool meta, const Tensor& pts, const Tensor& offset,
+                                                                              const Tensor& min_extra, at::ArrayRef<double> K,
+                                                                              int64_t seed, int64_t seed_stride, int64_t h_begin,
+                                                                              int64_t h, double thr, int64_t aggregation,
+                                                                              int64_t refine_rounds, int64_t refine_max_steps) {
+    TORCH_CHECK(pts.dim() == 2 && offset.dim() == 1 && (meta || offset.size(0) >= 1),
+                "sfm_hip: pts must be [n_total, 5], offset int64 [views + 1]");
+    if (!meta) TORCH_CHECK(h >= 1, "sfm_hip: register_views needs at least one hypothesis per view");
+    const SymInt n_total = pts.sym_size(0), views = offset.sym_size(0) - 1;
+    std::optional<PassTables> pass;
+    if (!meta) pass.emplace(pts, views, h, 12);
+    Tensor result = alloc(pts, at::kLong, {views, kRecordWords});
+    Tensor mask = alloc(pts, at::kByte, {n_total}), mask_out = alloc(pts, at::kByte, {n_total});
+    Tensor pose_out = alloc(pts, at::kDouble, {views, 12});
+    Tensor info = alloc(pts, at::kLong, {views, kRefineInfoWords});
+    Tensor status = alloc(pts, at::kInt, {views});
+    if (!meta) {
+        if (offset.size(0) == 1) {   // the entry is a no-op then: no item has a view
+            mask.zero_();
+            mask_out.zero_();
+        }
+        register_views_out(pts, offset, min_extra, K, seed, seed_stride, h_begin, thr, aggregation, refine_rounds, refine_max_steps, pass->S,
+                           pass->model, pass->flags, pass->cnt, pass->s1, pass->s2, result, mask, pose_out, mask_out, info, status);
+    }
+    return {pose_out, mask_out, info, status, mask, result};
 }
 
 // ---- similarity alignment of two reconstructions (sfm_similarity.hip): pairs [batch, n, 6], S [batch, h, 8] (first 3 entries
@@ -935,36 +903,20 @@ void similarity_ransac_pass_out(const Tensor& pairs, int64_t seed, int64_t seed_
 }
 
 // the functional form: h Philox-sampled hypotheses per entry -> (model, flags, cnt, s1, s2, S, result, mask)
-std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> similarity_ransac_pass(const Tensor& pairs, int64_t seed,
-                                                                                                  int64_t seed_stride, int64_t h_begin,
-                                                                                                  int64_t h, double thr, double min_extra,
-                                                                                                  int64_t aggregation) {
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> similarity_ransac_pass_new(bool meta, const Tensor& pairs,
+                                                                                                      int64_t seed, int64_t seed_stride,
+                                                                                                      int64_t h_begin, int64_t h, double thr,
+                                                                                                      double min_extra,
+                                                                                                      int64_t aggregation) {
     TORCH_CHECK(pairs.dim() == 3, "sfm_hip: pairs must be [batch, n, 6]");
-    TORCH_CHECK(h >= 0, "sfm_hip: similarity_ransac_pass needs h >= 0");
-    const int64_t batch = pairs.size(0), n = pairs.size(1);
-    Tensor S = at::empty({batch, h, 8}, like(pairs, at::kInt)), model = at::empty({batch, h, kSimilarityModelWidth}, like(pairs, at::kDouble));
-    Tensor flags = at::empty({batch, h}, like(pairs, at::kInt)), cnt = at::empty({batch, h}, like(pairs, at::kInt));
-    Tensor s1 = at::empty({batch, h}, like(pairs, at::kDouble)), s2 = at::empty({batch, h}, like(pairs, at::kDouble));
-    Tensor result = at::empty({batch, kRecordWords}, like(pairs, at::kLong));
-    Tensor mask = at::empty({batch, n}, like(pairs, at::kByte));
-    similarity_ransac_pass_out(pairs, seed, seed_stride, true, h_begin, thr, min_extra, aggregation, S, model, flags, cnt, s1, s2, result,
-                               mask);
-    return {model, flags, cnt, s1, s2, S, result, mask};
-}
-
-std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> similarity_ransac_pass_meta(const Tensor& pairs, int64_t, int64_t,
-                                                                                                       int64_t, int64_t h_count, double,
-                                                                                                       double, int64_t) {
-    TORCH_CHECK(pairs.dim() == 3, "sfm_hip: pairs must be [batch, n, 6]");
-    const c10::SymInt b = pairs.sym_size(0), n = pairs.sym_size(1), h(h_count);
-    return {at::empty_symint({b, h, c10::SymInt(kSimilarityModelWidth)}, like(pairs, at::kDouble)),
-            at::empty_symint({b, h}, like(pairs, at::kInt)),
-            at::empty_symint({b, h}, like(pairs, at::kInt)),
-            at::empty_symint({b, h}, like(pairs, at::kDouble)),
-            at::empty_symint({b, h}, like(pairs, at::kDouble)),
-            at::empty_symint({b, h, c10::SymInt(8)}, like(pairs, at::kInt)),
-            at::empty_symint({b, c10::SymInt(kRecordWords)}, like(pairs, at::kLong)),
-            at::empty_symint({b, n}, like(pairs, at::kByte))};
+    if (!meta) TORCH_CHECK(h >= 0, "sfm_hip: similarity_ransac_pass needs h >= 0");
+    PassTables t(pairs, pairs.sym_size(0), h, kSimilarityModelWidth);
+    Tensor result = alloc(pairs, at::kLong, {pairs.sym_size(0), kRecordWords});
+    Tensor mask = alloc(pairs, at::kByte, {pairs.sym_size(0), pairs.sym_size(1)});
+    if (!meta)
+        similarity_ransac_pass_out(pairs, seed, seed_stride, true, h_begin, thr, min_extra, aggregation, t.S, t.model, t.flags, t.cnt, t.s1,
+                                   t.s2, result, mask);
+    return {t.model, t.flags, t.cnt, t.s1, t.s2, t.S, result, mask};
 }
 
 Tensor similarity_workspace(const Tensor& pairs, int64_t bytes, const char* what) {
@@ -989,18 +941,12 @@ void similarity_fit_out(const Tensor& pairs, const std::optional<Tensor>& mask, 
        "sfm_similarity_fit_masked");
 }
 
-std::tuple<Tensor, Tensor> similarity_fit(const Tensor& pairs, const std::optional<Tensor>& mask) {
+std::tuple<Tensor, Tensor> similarity_fit_new(bool meta, const Tensor& pairs, const std::optional<Tensor>& mask) {
     TORCH_CHECK(pairs.dim() == 3, "sfm_hip: pairs must be [batch, n, 6]");
-    Tensor model_out = at::empty({pairs.size(0), kSimilarityModelWidth}, like(pairs, at::kDouble));
-    Tensor flags_out = at::empty({pairs.size(0)}, like(pairs, at::kInt));
-    similarity_fit_out(pairs, mask, model_out, flags_out);
+    Tensor model_out = alloc(pairs, at::kDouble, {pairs.sym_size(0), kSimilarityModelWidth});
+    Tensor flags_out = alloc(pairs, at::kInt, {pairs.sym_size(0)});
+    if (!meta) similarity_fit_out(pairs, mask, model_out, flags_out);
     return {model_out, flags_out};
-}
-
-std::tuple<Tensor, Tensor> similarity_fit_meta(const Tensor& pairs, const std::optional<Tensor>&) {
-    TORCH_CHECK(pairs.dim() == 3, "sfm_hip: pairs must be [batch, n, 6]");
-    return {at::empty_symint({pairs.sym_size(0), c10::SymInt(kSimilarityModelWidth)}, like(pairs, at::kDouble)),
-            at::empty_symint({pairs.sym_size(0)}, like(pairs, at::kInt))};
 }
 
 void similarity_refine_out(const Tensor& pairs, const Tensor& model, const Tensor& mask, const Tensor& err, double thr,
@@ -1028,22 +974,14 @@ void similarity_refine_out(const Tensor& pairs, const Tensor& model, const Tenso
        "sfm_similarity_refine");
 }
 
-std::tuple<Tensor, Tensor, Tensor> similarity_refine(const Tensor& pairs, const Tensor& model, const Tensor& mask, const Tensor& err,
-                                                     double thr, int64_t aggregation, int64_t rounds) {
+std::tuple<Tensor, Tensor, Tensor> similarity_refine_new(bool meta, const Tensor& pairs, const Tensor& model, const Tensor& mask,
+                                                         const Tensor& err, double thr, int64_t aggregation, int64_t rounds) {
     TORCH_CHECK(pairs.dim() == 3, "sfm_hip: pairs must be [batch, n, 6]");
-    Tensor model_out = at::empty({pairs.size(0), kSimilarityModelWidth}, like(pairs, at::kDouble));
-    Tensor mask_out = at::empty({pairs.size(0), pairs.size(1)}, like(pairs, at::kByte));
-    Tensor info = at::empty({pairs.size(0), kSimilarityInfoWords}, like(pairs, at::kLong));
-    similarity_refine_out(pairs, model, mask, err, thr, aggregation, rounds, model_out, mask_out, info);
+    Tensor model_out = alloc(pairs, at::kDouble, {pairs.sym_size(0), kSimilarityModelWidth});
+    Tensor mask_out = alloc(pairs, at::kByte, {pairs.sym_size(0), pairs.sym_size(1)});
+    Tensor info = alloc(pairs, at::kLong, {pairs.sym_size(0), kSimilarityInfoWords});
+    if (!meta) similarity_refine_out(pairs, model, mask, err, thr, aggregation, rounds, model_out, mask_out, info);
     return {model_out, mask_out, info};
-}
-
-std::tuple<Tensor, Tensor, Tensor> similarity_refine_meta(const Tensor& pairs, const Tensor&, const Tensor&, const Tensor&, double, int64_t,
-                                                          int64_t) {
-    TORCH_CHECK(pairs.dim() == 3, "sfm_hip: pairs must be [batch, n, 6]");
-    return {at::empty_symint({pairs.sym_size(0), c10::SymInt(kSimilarityModelWidth)}, like(pairs, at::kDouble)),
-            at::empty_symint({pairs.sym_size(0), pairs.sym_size(1)}, like(pairs, at::kByte)),
-            at::empty_symint({pairs.sym_size(0), c10::SymInt(kSimilarityInfoWords)}, like(pairs, at::kLong))};
 }
 
 // ---- similarity alignment of every pair of sub-models in one call (sfm_align_models.hip): pairs [n_total, 6], offset int64
@@ -1095,40 +1033,30 @@ void align_models_out(const Tensor& pairs, const Tensor& offset, const Tensor& t
 
 // the functional form: h hypotheses per pair -> (model_out, mask_out, info, status, mask, result); the tables of the pass are
 // temporaries of the call
-std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> align_models(const Tensor& pairs, const Tensor& offset, const Tensor& thr,
-                                                                        const Tensor& min_extra, int64_t max_items, int64_t seed,
-                                                                        int64_t seed_stride, int64_t h_begin, int64_t h,
-                                                                        int64_t aggregation, int64_t refine_rounds) {
-    TORCH_CHECK(pairs.dim() == 2 && offset.dim() == 1 && offset.size(0) >= 1, "sfm_hip: pairs must be [n_total, 6], offset int64 [pairs + 1]");
-    TORCH_CHECK(h >= 1, "sfm_hip: align_models needs at least one hypothesis per pair");
-    const int64_t n_total = pairs.size(0), Q = offset.size(0) - 1;
-    Tensor S = at::empty({Q, h, 8}, like(pairs, at::kInt)), model = at::empty({Q, h, kSimilarityModelWidth}, like(pairs, at::kDouble));
-    Tensor flags = at::empty({Q, h}, like(pairs, at::kInt)), cnt = at::empty({Q, h}, like(pairs, at::kInt));
-    Tensor s1 = at::empty({Q, h}, like(pairs, at::kDouble)), s2 = at::empty({Q, h}, like(pairs, at::kDouble));
-    Tensor result = at::empty({Q, kRecordWords}, like(pairs, at::kLong));
-    Tensor mask = at::empty({n_total}, like(pairs, at::kByte)), mask_out = at::empty({n_total}, like(pairs, at::kByte));
-    Tensor model_out = at::empty({Q, kSimilarityModelWidth}, like(pairs, at::kDouble));
-    Tensor info = at::empty({Q, kSimilarityInfoWords}, like(pairs, at::kLong));
-    Tensor status = at::empty({Q}, like(pairs, at::kInt));
-    if (Q == 0) {   // the entry is a no-op then: no item has a pair
-        mask.zero_();
-        mask_out.zero_();
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> align_models_new(bool meta, const Tensor& pairs, const Tensor& offset,
+                                                                            const Tensor& thr, const Tensor& min_extra, int64_t max_items,
+                                                                            int64_t seed, int64_t seed_stride, int64_t h_begin, int64_t h,
+                                                                            int64_t aggregation, int64_t refine_rounds) {
+    TORCH_CHECK(pairs.dim() == 2 && offset.dim() == 1 && (meta || offset.size(0) >= 1),
+                "sfm_hip: pairs must be [n_total, 6], offset int64 [pairs + 1]");
+    if (!meta) TORCH_CHECK(h >= 1, "sfm_hip: align_models needs at least one hypothesis per pair");
+    const SymInt n_total = pairs.sym_size(0), Q = offset.sym_size(0) - 1;
+    std::optional<PassTables> pass;
+    if (!meta) pass.emplace(pairs, Q, h, kSimilarityModelWidth);
+    Tensor result = alloc(pairs, at::kLong, {Q, kRecordWords});
+    Tensor mask = alloc(pairs, at::kByte, {n_total}), mask_out = alloc(pairs, at::kByte, {n_total});
+    Tensor model_out = alloc(pairs, at::kDouble, {Q, kSimilarityModelWidth});
+    Tensor info = alloc(pairs, at::kLong, {Q, kSimilarityInfoWords});
+    Tensor status = alloc(pairs, at::kInt, {Q});
+    if (!meta) {
+        if (offset.size(0) == 1) {   // the entry is a no-op then: no item has a pair
+            mask.zero_();
+            mask_out.zero_();
+        }
+        align_models_out(pairs, offset, thr, min_extra, max_items, seed, seed_stride, h_begin, aggregation, refine_rounds, pass->S,
+                         pass->model, pass->flags, pass->cnt, pass->s1, pass->s2, result, mask, model_out, mask_out, info, status);
     }
-    align_models_out(pairs, offset, thr, min_extra, max_items, seed, seed_stride, h_begin, aggregation, refine_rounds, S, model, flags, cnt,
-                     s1, s2, result, mask, model_out, mask_out, info, status);
     return {model_out, mask_out, info, status, mask, result};
-}
-
-std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> align_models_meta(const Tensor& pairs, const Tensor& offset, const Tensor&,
-                                                                             const Tensor&, int64_t, int64_t, int64_t, int64_t, int64_t,
-                                                                             int64_t, int64_t) {
-    TORCH_CHECK(pairs.dim() == 2 && offset.dim() == 1, "sfm_hip: pairs must be [n_total, 6], offset int64 [pairs + 1]");
-    const c10::SymInt Q = offset.sym_size(0) - 1;
-    return {at::empty_symint({Q, c10::SymInt(kSimilarityModelWidth)}, like(pairs, at::kDouble)),
-            at::empty_symint({pairs.sym_size(0)}, like(pairs, at::kByte)),
-            at::empty_symint({Q, c10::SymInt(kSimilarityInfoWords)}, like(pairs, at::kLong)), at::empty_symint({Q}, like(pairs, at::kInt)),
-            at::empty_symint({pairs.sym_size(0)}, like(pairs, at::kByte)),
-            at::empty_symint({Q, c10::SymInt(kRecordWords)}, like(pairs, at::kLong))};
 }
 
 // ---- plane-sweep depth maps and their consistency filter (sfm_plane_sweep.hip): images uint8 [V, H, W], K [9] and poses [V, 12]
@@ -1181,31 +1109,20 @@ void plane_sweep_out(const Tensor& images, const Tensor& K, const Tensor& poses,
 }
 
 // the functional form -> (depth, index, cost, status, volume); volume is [refs, depths, height, width], or [0] when not asked for
-std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> plane_sweep(const Tensor& images, const Tensor& K, const Tensor& poses,
-                                                               const Tensor& refs, const Tensor& sources, const Tensor& depths,
-                                                               int64_t radius, int64_t top_k, int64_t min_sources, double min_variance,
-                                                               bool return_volume) {
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> plane_sweep_new(bool meta, const Tensor& images, const Tensor& K, const Tensor& poses,
+                                                                   const Tensor& refs, const Tensor& sources, const Tensor& depths,
+                                                                   int64_t radius, int64_t top_k, int64_t min_sources,
+                                                                   double min_variance, bool return_volume) {
     TORCH_CHECK(images.dim() == 3 && refs.dim() == 1 && depths.dim() == 2, "sfm_hip: images must be [views, height, width], refs [refs], "
                                                                            "depths [refs, depths]");
-    const int64_t R = refs.size(0), H = images.size(1), W = images.size(2);
-    Tensor depth = at::empty({R, H, W}, like(images, at::kDouble)), cost = at::empty({R, H, W}, like(images, at::kDouble));
-    Tensor index = at::empty({R, H, W}, like(images, at::kInt)), status = at::empty({R}, like(images, at::kInt));
-    Tensor volume = return_volume ? at::empty({R, depths.size(1), H, W}, like(images, at::kDouble)) : at::empty({0}, like(images, at::kDouble));
-    plane_sweep_out(images, K, poses, refs, sources, depths, radius, top_k, min_sources, min_variance, depth, index, cost, status,
-                    return_volume ? std::optional<Tensor>(volume) : std::nullopt);
+    const SymInt R = refs.sym_size(0), H = images.sym_size(1), W = images.sym_size(2);
+    Tensor depth = alloc(images, at::kDouble, {R, H, W}), cost = alloc(images, at::kDouble, {R, H, W});
+    Tensor index = alloc(images, at::kInt, {R, H, W}), status = alloc(images, at::kInt, {R});
+    Tensor volume = return_volume ? alloc(images, at::kDouble, {R, depths.sym_size(1), H, W}) : alloc(images, at::kDouble, {0});
+    if (!meta)
+        plane_sweep_out(images, K, poses, refs, sources, depths, radius, top_k, min_sources, min_variance, depth, index, cost, status,
+                        return_volume ? std::optional<Tensor>(volume) : std::nullopt);
     return {depth, index, cost, status, volume};
-}
-
-std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> plane_sweep_meta(const Tensor& images, const Tensor&, const Tensor&, const Tensor& refs,
-                                                                    const Tensor&, const Tensor& depths, int64_t, int64_t, int64_t, double,
-                                                                    bool return_volume) {
-    TORCH_CHECK(images.dim() == 3 && refs.dim() == 1 && depths.dim() == 2, "sfm_hip: images must be [views, height, width], refs [refs], "
-                                                                           "depths [refs, depths]");
-    const c10::SymInt R = refs.sym_size(0), H = images.sym_size(1), W = images.sym_size(2);
-    Tensor volume = return_volume ? at::empty_symint({R, depths.sym_size(1), H, W}, like(images, at::kDouble))
-                                  : at::empty_symint({c10::SymInt(0)}, like(images, at::kDouble));
-    return {at::empty_symint({R, H, W}, like(images, at::kDouble)), at::empty_symint({R, H, W}, like(images, at::kInt)),
-            at::empty_symint({R, H, W}, like(images, at::kDouble)), at::empty_symint({R}, like(images, at::kInt)), volume};
 }
 
 void filter_depth_maps_out(const Tensor& depth, const Tensor& K, const Tensor& poses, const Tensor& refs, const Tensor& sources,
@@ -1229,24 +1146,17 @@ void filter_depth_maps_out(const Tensor& depth, const Tensor& K, const Tensor& p
 }
 
 // the functional form -> (count, filtered, points, status)
-std::tuple<Tensor, Tensor, Tensor, Tensor> filter_depth_maps(const Tensor& depth, const Tensor& K, const Tensor& poses, const Tensor& refs,
-                                                             const Tensor& sources, double max_pixel_error,
-                                                             double max_relative_depth_error, int64_t min_consistent) {
+std::tuple<Tensor, Tensor, Tensor, Tensor> filter_depth_maps_new(bool meta, const Tensor& depth, const Tensor& K, const Tensor& poses,
+                                                                 const Tensor& refs, const Tensor& sources, double max_pixel_error,
+                                                                 double max_relative_depth_error, int64_t min_consistent) {
     TORCH_CHECK(depth.dim() == 3 && refs.dim() == 1, "sfm_hip: depth must be [views, height, width], refs [refs]");
-    const int64_t R = refs.size(0), H = depth.size(1), W = depth.size(2);
-    Tensor count = at::empty({R, H, W}, like(depth, at::kInt)), filtered = at::empty({R, H, W}, like(depth, at::kDouble));
-    Tensor points = at::empty({R, H, W, 3}, like(depth, at::kDouble)), status = at::empty({R}, like(depth, at::kInt));
-    filter_depth_maps_out(depth, K, poses, refs, sources, max_pixel_error, max_relative_depth_error, min_consistent, count, filtered, points,
-                          status);
+    const SymInt R = refs.sym_size(0), H = depth.sym_size(1), W = depth.sym_size(2);
+    Tensor count = alloc(depth, at::kInt, {R, H, W}), filtered = alloc(depth, at::kDouble, {R, H, W});
+    Tensor points = alloc(depth, at::kDouble, {R, H, W, 3}), status = alloc(depth, at::kInt, {R});
+    if (!meta)
+        filter_depth_maps_out(depth, K, poses, refs, sources, max_pixel_error, max_relative_depth_error, min_consistent, count, filtered,
+                              points, status);
     return {count, filtered, points, status};
-}
-
-std::tuple<Tensor, Tensor, Tensor, Tensor> filter_depth_maps_meta(const Tensor& depth, const Tensor&, const Tensor&, const Tensor& refs,
-                                                                  const Tensor&, double, double, int64_t) {
-    TORCH_CHECK(depth.dim() == 3 && refs.dim() == 1, "sfm_hip: depth must be [views, height, width], refs [refs]");
-    const c10::SymInt R = refs.sym_size(0), H = depth.sym_size(1), W = depth.sym_size(2);
-    return {at::empty_symint({R, H, W}, like(depth, at::kInt)), at::empty_symint({R, H, W}, like(depth, at::kDouble)),
-            at::empty_symint({R, H, W, c10::SymInt(3)}, like(depth, at::kDouble)), at::empty_symint({R}, like(depth, at::kInt))};
 }
 
 // ---- semi-global smoothing of the plane-sweep cost volume (sfm_sgm.hip): volume [R, D, H, W] and depths [R, D] on the device; depth,
@@ -1280,26 +1190,17 @@ void sgm_aggregate_out(const Tensor& volume, const Tensor& depths, double p1, do
 }
 
 // the functional form -> (depth, index, cost, aggregated); aggregated is [refs, depths, height, width], or [0] when not asked for
-std::tuple<Tensor, Tensor, Tensor, Tensor> sgm_aggregate(const Tensor& volume, const Tensor& depths, double p1, double p2, double invalid_cost,
-                                                         int64_t paths, bool return_aggregated) {
+std::tuple<Tensor, Tensor, Tensor, Tensor> sgm_aggregate_new(bool meta, const Tensor& volume, const Tensor& depths, double p1, double p2,
+                                                             double invalid_cost, int64_t paths, bool return_aggregated) {
     TORCH_CHECK(volume.dim() == 4, "sfm_hip: volume must be [refs, depths, height, width]");
-    const int64_t R = volume.size(0), H = volume.size(2), W = volume.size(3);
-    Tensor depth = at::empty({R, H, W}, like(volume, at::kDouble)), cost = at::empty({R, H, W}, like(volume, at::kDouble));
-    Tensor index = at::empty({R, H, W}, like(volume, at::kInt));
-    Tensor aggregated = return_aggregated ? at::empty({R, volume.size(1), H, W}, like(volume, at::kDouble)) : at::empty({0}, like(volume, at::kDouble));
-    sgm_aggregate_out(volume, depths, p1, p2, invalid_cost, paths, depth, index, cost,
-                      return_aggregated ? std::optional<Tensor>(aggregated) : std::nullopt);
+    const SymInt R = volume.sym_size(0), H = volume.sym_size(2), W = volume.sym_size(3);
+    Tensor depth = alloc(volume, at::kDouble, {R, H, W}), cost = alloc(volume, at::kDouble, {R, H, W});
+    Tensor index = alloc(volume, at::kInt, {R, H, W});
+    Tensor aggregated = return_aggregated ? alloc(volume, at::kDouble, {R, volume.sym_size(1), H, W}) : alloc(volume, at::kDouble, {0});
+    if (!meta)
+        sgm_aggregate_out(volume, depths, p1, p2, invalid_cost, paths, depth, index, cost,
+                          return_aggregated ? std::optional<Tensor>(aggregated) : std::nullopt);
     return {depth, index, cost, aggregated};
-}
-
-std::tuple<Tensor, Tensor, Tensor, Tensor> sgm_aggregate_meta(const Tensor& volume, const Tensor&, double, double, double, int64_t,
-                                                              bool return_aggregated) {
-    TORCH_CHECK(volume.dim() == 4, "sfm_hip: volume must be [refs, depths, height, width]");
-    const c10::SymInt R = volume.sym_size(0), H = volume.sym_size(2), W = volume.sym_size(3);
-    Tensor aggregated = return_aggregated ? at::empty_symint({R, volume.sym_size(1), H, W}, like(volume, at::kDouble))
-                                          : at::empty_symint({c10::SymInt(0)}, like(volume, at::kDouble));
-    return {at::empty_symint({R, H, W}, like(volume, at::kDouble)), at::empty_symint({R, H, W}, like(volume, at::kInt)),
-            at::empty_symint({R, H, W}, like(volume, at::kDouble)), aggregated};
 }
 
 // ---- fusion of depth maps into a TSDF volume and its mesh (sfm_tsdf.hip): the state sum [nz, ny, nx], count int32, grey_sum int32 or
@@ -1342,26 +1243,20 @@ void tsdf_integrate_out(Tensor& sum, Tensor& count, const std::optional<Tensor>&
 }
 
 // the functional form -> (sum, count, grey_sum, status): new tensors; grey_sum is [0] without one
-std::tuple<Tensor, Tensor, Tensor, Tensor> tsdf_integrate(const Tensor& sum, const Tensor& count, const std::optional<Tensor>& grey_sum,
-                                                          const Tensor& depth, const std::optional<Tensor>& images, const Tensor& K,
-                                                          const Tensor& poses, const Tensor& views, double ox, double oy, double oz,
-                                                          double voxel_size, double truncation) {
+std::tuple<Tensor, Tensor, Tensor, Tensor> tsdf_integrate_new(bool meta, const Tensor& sum, const Tensor& count,
+                                                              const std::optional<Tensor>& grey_sum, const Tensor& depth,
+                                                              const std::optional<Tensor>& images, const Tensor& K, const Tensor& poses,
+                                                              const Tensor& views, double ox, double oy, double oz, double voxel_size,
+                                                              double truncation) {
     TORCH_CHECK(views.dim() == 1, "sfm_hip: views must be int32 [n]");
-    Tensor new_sum = sum.clone(), new_count = count.clone();
-    Tensor new_grey = given(grey_sum) ? grey_sum->clone() : at::empty({0}, like(sum, at::kInt));
-    Tensor status = at::empty({views.size(0)}, like(sum, at::kInt));
-    tsdf_integrate_out(new_sum, new_count, given(grey_sum) ? std::optional<Tensor>(new_grey) : std::nullopt, depth, images, K, poses, views,
-                       ox, oy, oz, voxel_size, truncation, status);
+    auto copy = [meta](const Tensor& t) { return meta ? at::empty_like(t) : t.clone(); };   // the state the call goes on from
+    Tensor new_sum = copy(sum), new_count = copy(count);
+    Tensor new_grey = given(grey_sum) ? copy(*grey_sum) : alloc(sum, at::kInt, {0});
+    Tensor status = alloc(sum, at::kInt, {views.sym_size(0)});
+    if (!meta)
+        tsdf_integrate_out(new_sum, new_count, given(grey_sum) ? std::optional<Tensor>(new_grey) : std::nullopt, depth, images, K, poses,
+                           views, ox, oy, oz, voxel_size, truncation, status);
     return {new_sum, new_count, new_grey, status};
-}
-
-std::tuple<Tensor, Tensor, Tensor, Tensor> tsdf_integrate_meta(const Tensor& sum, const Tensor& count, const std::optional<Tensor>& grey_sum,
-                                                               const Tensor&, const std::optional<Tensor>&, const Tensor&, const Tensor&,
-                                                               const Tensor& views, double, double, double, double, double) {
-    TORCH_CHECK(views.dim() == 1, "sfm_hip: views must be int32 [n]");
-    return {at::empty_like(sum), at::empty_like(count),
-            given(grey_sum) ? at::empty_like(*grey_sum) : at::empty_symint({c10::SymInt(0)}, like(sum, at::kInt)),
-            at::empty_symint({views.sym_size(0)}, like(sum, at::kInt))};
 }
 
 void tsdf_extract_mesh_out(const Tensor& sum, const Tensor& count, const std::optional<Tensor>& grey_sum, double ox, double oy, double oz,
@@ -1391,23 +1286,16 @@ void tsdf_extract_mesh_out(const Tensor& sum, const Tensor& count, const std::op
 }
 
 // the functional form -> (vertices, grey, total); grey is [0] without a grey_sum
-std::tuple<Tensor, Tensor, Tensor> tsdf_extract_mesh(const Tensor& sum, const Tensor& count, const std::optional<Tensor>& grey_sum, double ox,
-                                                     double oy, double oz, double voxel_size, int64_t min_count, int64_t max_triangles) {
-    TORCH_CHECK(max_triangles >= 0, "sfm_hip: max_triangles must be >= 0");
-    Tensor vertices = at::empty({max_triangles, 3, 3}, like(sum, at::kDouble)), total = at::empty({1}, like(sum, at::kLong));
-    Tensor grey = given(grey_sum) ? at::empty({max_triangles, 3}, like(sum, at::kDouble)) : at::empty({0}, like(sum, at::kDouble));
-    tsdf_extract_mesh_out(sum, count, grey_sum, ox, oy, oz, voxel_size, min_count, vertices,
-                          given(grey_sum) ? std::optional<Tensor>(grey) : std::nullopt, total);
+std::tuple<Tensor, Tensor, Tensor> tsdf_extract_mesh_new(bool meta, const Tensor& sum, const Tensor& count,
+                                                         const std::optional<Tensor>& grey_sum, double ox, double oy, double oz,
+                                                         double voxel_size, int64_t min_count, int64_t max_triangles) {
+    if (!meta) TORCH_CHECK(max_triangles >= 0, "sfm_hip: max_triangles must be >= 0");
+    Tensor vertices = alloc(sum, at::kDouble, {max_triangles, 3, 3}), total = alloc(sum, at::kLong, {1});
+    Tensor grey = given(grey_sum) ? alloc(sum, at::kDouble, {max_triangles, 3}) : alloc(sum, at::kDouble, {0});
+    if (!meta)
+        tsdf_extract_mesh_out(sum, count, grey_sum, ox, oy, oz, voxel_size, min_count, vertices,
+                              given(grey_sum) ? std::optional<Tensor>(grey) : std::nullopt, total);
     return {vertices, grey, total};
-}
-
-std::tuple<Tensor, Tensor, Tensor> tsdf_extract_mesh_meta(const Tensor& sum, const Tensor&, const std::optional<Tensor>& grey_sum, double,
-                                                          double, double, double, int64_t, int64_t max_triangles) {
-    const c10::SymInt T(max_triangles);
-    Tensor grey = given(grey_sum) ? at::empty_symint({T, c10::SymInt(3)}, like(sum, at::kDouble))
-                                  : at::empty_symint({c10::SymInt(0)}, like(sum, at::kDouble));
-    return {at::empty_symint({T, c10::SymInt(3), c10::SymInt(3)}, like(sum, at::kDouble)), grey,
-            at::empty_symint({c10::SymInt(1)}, like(sum, at::kLong))};
 }
 
 // bundle adjustment, dense (sfm_bundle.hip) and with the iterative Schur solver (sfm_bundle_pcg.hip): poses [C, 12], points
@@ -1504,85 +1392,58 @@ BundleResult bundle_new(const BundleSolver& s, bool meta, const Tensor& poses, c
     return {poses_out, points_out, info};
 }
 
-// The twelve registered signatures
-void bundle_adjust_inplace(Tensor& poses, Tensor& points, const Tensor& cam, const Tensor& pt, const Tensor& pixels,
-                           at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed, int64_t max_steps, Tensor& info) {
+// The four families: each names its solver and forwards, in place and functional
+void bundle_adjust_out(Tensor& poses, Tensor& points, const Tensor& cam, const Tensor& pt, const Tensor& pixels,
+                       at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed, int64_t max_steps, Tensor& info) {
     bundle_run({false, 0, 0.0, nullptr}, poses, points, cam, pt, pixels, K, fixed, max_steps, info, poses, points);
 }
 
-BundleResult bundle_adjust(const Tensor& poses, const Tensor& points, const Tensor& cam, const Tensor& pt, const Tensor& pixels,
-                           at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed, int64_t max_steps) {
-    return bundle_new({false, 0, 0.0, nullptr}, false, poses, points, cam, pt, pixels, K, fixed, max_steps);
+BundleResult bundle_adjust_new(bool meta, const Tensor& poses, const Tensor& points, const Tensor& cam, const Tensor& pt,
+                               const Tensor& pixels, at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed, int64_t max_steps) {
+    return bundle_new({false, 0, 0.0, nullptr}, meta, poses, points, cam, pt, pixels, K, fixed, max_steps);
 }
 
-BundleResult bundle_adjust_meta(const Tensor& poses, const Tensor& points, const Tensor& cam, const Tensor& pt,
-                                const Tensor& pixels, at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed, int64_t max_steps) {
-    return bundle_new({false, 0, 0.0, nullptr}, true, poses, points, cam, pt, pixels, K, fixed, max_steps);
-}
-
-void bundle_adjust_pcg_inplace(Tensor& poses, Tensor& points, const Tensor& cam, const Tensor& pt, const Tensor& pixels,
-                               at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed, int64_t max_steps,
-                               int64_t max_cg_iterations, double cg_tolerance, Tensor& info) {
+void bundle_adjust_pcg_out(Tensor& poses, Tensor& points, const Tensor& cam, const Tensor& pt, const Tensor& pixels,
+                           at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed, int64_t max_steps, int64_t max_cg_iterations,
+                           double cg_tolerance, Tensor& info) {
     bundle_run({true, max_cg_iterations, cg_tolerance, nullptr}, poses, points, cam, pt, pixels, K, fixed, max_steps, info, poses,
                points);
 }
 
-BundleResult bundle_adjust_pcg(const Tensor& poses, const Tensor& points, const Tensor& cam, const Tensor& pt,
-                               const Tensor& pixels, at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed, int64_t max_steps,
-                               int64_t max_cg_iterations, double cg_tolerance) {
-    return bundle_new({true, max_cg_iterations, cg_tolerance, nullptr}, false, poses, points, cam, pt, pixels, K, fixed, max_steps);
+BundleResult bundle_adjust_pcg_new(bool meta, const Tensor& poses, const Tensor& points, const Tensor& cam, const Tensor& pt,
+                                   const Tensor& pixels, at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed, int64_t max_steps,
+                                   int64_t max_cg_iterations, double cg_tolerance) {
+    return bundle_new({true, max_cg_iterations, cg_tolerance, nullptr}, meta, poses, points, cam, pt, pixels, K, fixed, max_steps);
 }
 
-BundleResult bundle_adjust_pcg_meta(const Tensor& poses, const Tensor& points, const Tensor& cam, const Tensor& pt,
-                                    const Tensor& pixels, at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed, int64_t max_steps,
-                                    int64_t max_cg_iterations, double cg_tolerance) {
-    return bundle_new({true, max_cg_iterations, cg_tolerance, nullptr}, true, poses, points, cam, pt, pixels, K, fixed, max_steps);
-}
-
-void bundle_adjust_robust_inplace(Tensor& poses, Tensor& points, const Tensor& cam, const Tensor& pt, const Tensor& pixels,
-                                  at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed, int64_t max_steps, int64_t loss,
-                                  double loss_scale, Tensor& info) {
+void bundle_adjust_robust_out(Tensor& poses, Tensor& points, const Tensor& cam, const Tensor& pt, const Tensor& pixels,
+                              at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed, int64_t max_steps, int64_t loss,
+                              double loss_scale, Tensor& info) {
     const sfm_bundle_options options = bundle_options(loss, loss_scale);
     bundle_run({false, 0, 0.0, &options}, poses, points, cam, pt, pixels, K, fixed, max_steps, info, poses, points);
 }
 
-BundleResult bundle_adjust_robust(const Tensor& poses, const Tensor& points, const Tensor& cam, const Tensor& pt,
-                                  const Tensor& pixels, at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed, int64_t max_steps,
-                                  int64_t loss, double loss_scale) {
+BundleResult bundle_adjust_robust_new(bool meta, const Tensor& poses, const Tensor& points, const Tensor& cam, const Tensor& pt,
+                                      const Tensor& pixels, at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed, int64_t max_steps,
+                                      int64_t loss, double loss_scale) {
     const sfm_bundle_options options = bundle_options(loss, loss_scale);
-    return bundle_new({false, 0, 0.0, &options}, false, poses, points, cam, pt, pixels, K, fixed, max_steps);
+    return bundle_new({false, 0, 0.0, &options}, meta, poses, points, cam, pt, pixels, K, fixed, max_steps);
 }
 
-BundleResult bundle_adjust_robust_meta(const Tensor& poses, const Tensor& points, const Tensor& cam, const Tensor& pt,
-                                       const Tensor& pixels, at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed,
-                                       int64_t max_steps, int64_t loss, double loss_scale) {
-    const sfm_bundle_options options = bundle_options(loss, loss_scale);
-    return bundle_new({false, 0, 0.0, &options}, true, poses, points, cam, pt, pixels, K, fixed, max_steps);
-}
-
-void bundle_adjust_pcg_robust_inplace(Tensor& poses, Tensor& points, const Tensor& cam, const Tensor& pt, const Tensor& pixels,
-                                      at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed, int64_t max_steps,
-                                      int64_t max_cg_iterations, double cg_tolerance, int64_t loss, double loss_scale,
-                                      Tensor& info) {
+void bundle_adjust_pcg_robust_out(Tensor& poses, Tensor& points, const Tensor& cam, const Tensor& pt, const Tensor& pixels,
+                                  at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed, int64_t max_steps, int64_t max_cg_iterations,
+                                  double cg_tolerance, int64_t loss, double loss_scale, Tensor& info) {
     const sfm_bundle_options options = bundle_options(loss, loss_scale);
     bundle_run({true, max_cg_iterations, cg_tolerance, &options}, poses, points, cam, pt, pixels, K, fixed, max_steps, info, poses,
                points);
 }
 
-BundleResult bundle_adjust_pcg_robust(const Tensor& poses, const Tensor& points, const Tensor& cam, const Tensor& pt,
-                                      const Tensor& pixels, at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed,
-                                      int64_t max_steps, int64_t max_cg_iterations, double cg_tolerance, int64_t loss,
-                                      double loss_scale) {
+BundleResult bundle_adjust_pcg_robust_new(bool meta, const Tensor& poses, const Tensor& points, const Tensor& cam, const Tensor& pt,
+                                          const Tensor& pixels, at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed,
+                                          int64_t max_steps, int64_t max_cg_iterations, double cg_tolerance, int64_t loss,
+                                          double loss_scale) {
     const sfm_bundle_options options = bundle_options(loss, loss_scale);
-    return bundle_new({true, max_cg_iterations, cg_tolerance, &options}, false, poses, points, cam, pt, pixels, K, fixed, max_steps);
-}
-
-BundleResult bundle_adjust_pcg_robust_meta(const Tensor& poses, const Tensor& points, const Tensor& cam, const Tensor& pt,
-                                           const Tensor& pixels, at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed,
-                                           int64_t max_steps, int64_t max_cg_iterations, double cg_tolerance, int64_t loss,
-                                           double loss_scale) {
-    const sfm_bundle_options options = bundle_options(loss, loss_scale);
-    return bundle_new({true, max_cg_iterations, cg_tolerance, &options}, true, poses, points, cam, pt, pixels, K, fixed, max_steps);
+    return bundle_new({true, max_cg_iterations, cg_tolerance, &options}, meta, poses, points, cam, pt, pixels, K, fixed, max_steps);
 }
 
 // The calibrating dense adjuster (sfm_bundle_adjust_calibrated): the arguments of bundle_adjust_robust plus the
@@ -1645,23 +1506,11 @@ BundleCalibratedResult bundle_calibrated_new(bool meta, const Tensor& poses, con
     return {poses_out, points_out, info, K_out};
 }
 
-void bundle_adjust_calibrated_inplace(Tensor& poses, Tensor& points, const Tensor& cam, const Tensor& pt, const Tensor& pixels,
-                                      at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed, int64_t max_steps, int64_t loss,
-                                      double loss_scale, int64_t refine, Tensor& info, Tensor& K_out) {
+void bundle_adjust_calibrated_out(Tensor& poses, Tensor& points, const Tensor& cam, const Tensor& pt, const Tensor& pixels,
+                                  at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed, int64_t max_steps, int64_t loss,
+                                  double loss_scale, int64_t refine, Tensor& info, Tensor& K_out) {
     bundle_calibrated_run(poses, points, cam, pt, pixels, K, fixed, max_steps, loss, loss_scale, refine, info, K_out, poses,
                           points);
-}
-
-BundleCalibratedResult bundle_adjust_calibrated(const Tensor& poses, const Tensor& points, const Tensor& cam, const Tensor& pt,
-                                                const Tensor& pixels, at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed,
-                                                int64_t max_steps, int64_t loss, double loss_scale, int64_t refine) {
-    return bundle_calibrated_new(false, poses, points, cam, pt, pixels, K, fixed, max_steps, loss, loss_scale, refine);
-}
-
-BundleCalibratedResult bundle_adjust_calibrated_meta(const Tensor& poses, const Tensor& points, const Tensor& cam, const Tensor& pt,
-                                                     const Tensor& pixels, at::ArrayRef<double> K, at::ArrayRef<int64_t> fixed,
-                                                     int64_t max_steps, int64_t loss, double loss_scale, int64_t refine) {
-    return bundle_calibrated_new(true, poses, points, cam, pt, pixels, K, fixed, max_steps, loss, loss_scale, refine);
 }
 
 // triangulation of multi-view tracks (sfm_tracks.hip): poses [C, 12], camera / point indices int32 [M], pixels [M, 2],
@@ -1712,31 +1561,20 @@ void triangulate_tracks_out(const Tensor& poses, const Tensor& cam, const Tensor
        "sfm_triangulate_tracks");
 }
 
-std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> triangulate_tracks(const Tensor& poses, const Tensor& cam, const Tensor& pt,
-                                                                      const Tensor& pixels, int64_t points, at::ArrayRef<double> K,
-                                                                      int64_t min_views, double min_angle, double max_error,
-                                                                      int64_t refine_steps) {
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> triangulate_tracks_new(bool meta, const Tensor& poses, const Tensor& cam,
+                                                                          const Tensor& pt, const Tensor& pixels, int64_t points,
+                                                                          at::ArrayRef<double> K, int64_t min_views, double min_angle,
+                                                                          double max_error, int64_t refine_steps) {
     tracks_check(poses, cam, pt, pixels, points, K, min_views, min_angle, max_error, refine_steps);
-    Tensor points_out = at::empty({points, 3}, like(poses, at::kDouble));
-    Tensor status = at::empty({points}, like(poses, at::kByte));
-    Tensor obs_error = at::empty({cam.size(0)}, like(poses, at::kDouble));
-    Tensor angle = at::empty({points}, like(poses, at::kDouble));
-    Tensor info = at::empty({kTracksInfoWords}, like(poses, at::kLong));
-    triangulate_tracks_out(poses, cam, pt, pixels, points, K, min_views, min_angle, max_error, refine_steps, points_out, status,
-                           obs_error, angle, info);
+    Tensor points_out = alloc(poses, at::kDouble, {points, 3});
+    Tensor status = alloc(poses, at::kByte, {points});
+    Tensor obs_error = alloc(poses, at::kDouble, {cam.sym_size(0)});
+    Tensor angle = alloc(poses, at::kDouble, {points});
+    Tensor info = alloc(poses, at::kLong, {kTracksInfoWords});
+    if (!meta)
+        triangulate_tracks_out(poses, cam, pt, pixels, points, K, min_views, min_angle, max_error, refine_steps, points_out, status,
+                               obs_error, angle, info);
     return {points_out, status, obs_error, angle, info};
-}
-
-std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> triangulate_tracks_meta(const Tensor& poses, const Tensor& cam,
-                                                                           const Tensor& pt, const Tensor& pixels,
-                                                                           int64_t points, at::ArrayRef<double> K,
-                                                                           int64_t min_views, double min_angle,
-                                                                           double max_error, int64_t refine_steps) {
-    tracks_check(poses, cam, pt, pixels, points, K, min_views, min_angle, max_error, refine_steps);
-    const c10::SymInt P(points);
-    return {at::empty_symint({P, c10::SymInt(3)}, like(poses, at::kDouble)), at::empty_symint({P}, like(poses, at::kByte)),
-            at::empty_symint({cam.sym_size(0)}, like(poses, at::kDouble)), at::empty_symint({P}, like(poses, at::kDouble)),
-            at::empty_symint({c10::SymInt(kTracksInfoWords)}, like(poses, at::kLong))};
 }
 
 // tracks from pairwise matches (sfm_track_build.hip): image_offset int32 [I + 1], pair_images int32 [Q, 2], match_offset
@@ -1784,30 +1622,19 @@ void build_tracks_out(const Tensor& image_offset, const Tensor& pair_images, con
        "sfm_build_tracks");
 }
 
-std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> build_tracks(const Tensor& image_offset,
-                                                                                const Tensor& pair_images,
-                                                                                const Tensor& match_offset,
-                                                                                const Tensor& match_index, int64_t features) {
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> build_tracks_new(bool meta, const Tensor& image_offset,
+                                                                                    const Tensor& pair_images,
+                                                                                    const Tensor& match_offset,
+                                                                                    const Tensor& match_index, int64_t features) {
     build_check(image_offset, pair_images, match_offset, match_index, features);
-    auto i32 = [&] { return at::empty({features}, like(image_offset, at::kInt)); };
+    auto i32 = [&] { return alloc(image_offset, at::kInt, {features}); };
     Tensor component = i32(), track = i32(), camera_index = i32(), point_index = i32(), feature_index = i32();
-    Tensor status = at::empty({features}, like(image_offset, at::kByte));
-    Tensor info = at::empty({kBuildInfoWords}, like(image_offset, at::kLong));
-    build_tracks_out(image_offset, pair_images, match_offset, match_index, features, component, track, status, camera_index,
-                     point_index, feature_index, info);
+    Tensor status = alloc(image_offset, at::kByte, {features});
+    Tensor info = alloc(image_offset, at::kLong, {kBuildInfoWords});
+    if (!meta)
+        build_tracks_out(image_offset, pair_images, match_offset, match_index, features, component, track, status, camera_index,
+                         point_index, feature_index, info);
     return {component, track, status, camera_index, point_index, feature_index, info};
-}
-
-std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> build_tracks_meta(const Tensor& image_offset,
-                                                                                     const Tensor& pair_images,
-                                                                                     const Tensor& match_offset,
-                                                                                     const Tensor& match_index,
-                                                                                     int64_t features) {
-    build_check(image_offset, pair_images, match_offset, match_index, features);
-    const c10::SymInt F(features);
-    auto i32 = [&] { return at::empty_symint({F}, like(image_offset, at::kInt)); };
-    return {i32(), i32(), at::empty_symint({F}, like(image_offset, at::kByte)), i32(), i32(), i32(),
-            at::empty_symint({c10::SymInt(kBuildInfoWords)}, like(image_offset, at::kLong))};
 }
 
 // What the solvers over a view graph check alike; `op` names the solver in the refusal of the sizes
@@ -1849,25 +1676,28 @@ void rotavg_check(const Tensor& pairs, const Tensor& relative, const Tensor& wei
     if (initial.has_value() && initial->defined()) rotation_table_check(*initial, cameras, "initial", "cameras");
 }
 
-std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> average_rotations(const Tensor& pairs, const Tensor& relative, const Tensor& weights,
-                                                             int64_t cameras, int64_t root, const std::optional<Tensor>& initial,
-                                                             int64_t loss, double loss_scale, int64_t max_steps,
-                                                             int64_t max_cg_iterations, double cg_tolerance,
-                                                             double step_tolerance) {
-    const OpDevice scope(pairs);
-    need(pairs, "pairs", at::kInt);
-    need(relative, "relative", at::kDouble);
-    need(weights, "weights", at::kDouble);
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> average_rotations_new(bool meta, const Tensor& pairs, const Tensor& relative,
+                                                                         const Tensor& weights, int64_t cameras, int64_t root,
+                                                                         const std::optional<Tensor>& initial, int64_t loss,
+                                                                         double loss_scale, int64_t max_steps, int64_t max_cg_iterations,
+                                                                         double cg_tolerance, double step_tolerance) {
+    const OpDevice scope(pairs, meta);
     const bool given = initial.has_value() && initial->defined();
-    if (given) need(*initial, "initial", at::kDouble);
+    if (!meta) {
+        need(pairs, "pairs", at::kInt);
+        need(relative, "relative", at::kDouble);
+        need(weights, "weights", at::kDouble);
+        if (given) need(*initial, "initial", at::kDouble);
+    }
     rotavg_check(pairs, relative, weights, cameras, root, initial, loss, loss_scale, max_steps, max_cg_iterations, cg_tolerance,
                  step_tolerance);
+    Tensor rotations = alloc(pairs, at::kDouble, {cameras, 3, 3});
+    Tensor registered = alloc(pairs, at::kByte, {cameras});
+    Tensor level = alloc(pairs, at::kInt, {cameras});
+    Tensor residual = alloc(pairs, at::kDouble, {pairs.sym_size(0)});
+    Tensor info = alloc(pairs, at::kLong, {kRotavgInfoWords});
+    if (meta) return {rotations, registered, level, residual, info};
     const int64_t Q = pairs.size(0);
-    Tensor rotations = at::empty({cameras, 3, 3}, like(pairs, at::kDouble));
-    Tensor registered = at::empty({cameras}, like(pairs, at::kByte));
-    Tensor level = at::empty({cameras}, like(pairs, at::kInt));
-    Tensor residual = at::empty({Q}, like(pairs, at::kDouble));
-    Tensor info = at::empty({kRotavgInfoWords}, like(pairs, at::kLong));
     const int64_t bytes = sfm_average_rotations_workspace_bytes(cameras, Q);
     TORCH_CHECK(bytes >= 0, "sfm_hip: average_rotations: ", cameras, " cameras, ", Q, " edges exceed the limits");
     Tensor ws = at::empty({bytes}, like(pairs, at::kByte));
@@ -1879,20 +1709,6 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> average_rotations(const Tenso
                              current_stream()),
        "sfm_average_rotations");
     return {rotations, registered, level, residual, info};
-}
-
-std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> average_rotations_meta(const Tensor& pairs, const Tensor& relative,
-                                                                  const Tensor& weights, int64_t cameras, int64_t root,
-                                                                  const std::optional<Tensor>& initial, int64_t loss,
-                                                                  double loss_scale, int64_t max_steps, int64_t max_cg_iterations,
-                                                                  double cg_tolerance, double step_tolerance) {
-    rotavg_check(pairs, relative, weights, cameras, root, initial, loss, loss_scale, max_steps, max_cg_iterations, cg_tolerance,
-                 step_tolerance);
-    const c10::SymInt C(cameras);
-    return {at::empty_symint({C, c10::SymInt(3), c10::SymInt(3)}, like(pairs, at::kDouble)),
-            at::empty_symint({C}, like(pairs, at::kByte)), at::empty_symint({C}, like(pairs, at::kInt)),
-            at::empty_symint({pairs.sym_size(0)}, like(pairs, at::kDouble)),
-            at::empty_symint({c10::SymInt(kRotavgInfoWords)}, like(pairs, at::kLong))};
 }
 
 // translation averaging over a view graph (sfm_translation_averaging.hip): pairs int32 [Q, 2], directions f64 [Q, 3] (the
@@ -1918,27 +1734,30 @@ void transavg_check(const Tensor& pairs, const Tensor& directions, const std::op
 
 using TransavgResult = std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor>;
 
-TransavgResult average_translations(const Tensor& pairs, const Tensor& directions, const std::optional<Tensor>& rotations,
-                                    const Tensor& weights, int64_t cameras, int64_t root, const std::optional<Tensor>& initial,
-                                    int64_t loss, double loss_scale, int64_t warmup_steps, int64_t max_steps,
-                                    int64_t max_cg_iterations, double cg_tolerance, double step_tolerance) {
-    const OpDevice scope(pairs);
-    need(pairs, "pairs", at::kInt);
-    need(directions, "directions", at::kDouble);
-    need(weights, "weights", at::kDouble);
+TransavgResult average_translations_new(bool meta, const Tensor& pairs, const Tensor& directions, const std::optional<Tensor>& rotations,
+                                        const Tensor& weights, int64_t cameras, int64_t root, const std::optional<Tensor>& initial,
+                                        int64_t loss, double loss_scale, int64_t warmup_steps, int64_t max_steps,
+                                        int64_t max_cg_iterations, double cg_tolerance, double step_tolerance) {
+    const OpDevice scope(pairs, meta);
     const bool rotated = rotations.has_value() && rotations->defined();
-    if (rotated) need(*rotations, "rotations", at::kDouble);
     const bool given = initial.has_value() && initial->defined();
-    if (given) need(*initial, "initial", at::kDouble);
+    if (!meta) {
+        need(pairs, "pairs", at::kInt);
+        need(directions, "directions", at::kDouble);
+        need(weights, "weights", at::kDouble);
+        if (rotated) need(*rotations, "rotations", at::kDouble);
+        if (given) need(*initial, "initial", at::kDouble);
+    }
     transavg_check(pairs, directions, rotations, weights, cameras, root, initial, loss, loss_scale, warmup_steps, max_steps,
                    max_cg_iterations, cg_tolerance, step_tolerance);
+    Tensor positions = alloc(pairs, at::kDouble, {cameras, 3});
+    Tensor registered = alloc(pairs, at::kByte, {cameras});
+    Tensor level = alloc(pairs, at::kInt, {cameras});
+    Tensor residual = alloc(pairs, at::kDouble, {pairs.sym_size(0)});
+    Tensor scale = alloc(pairs, at::kDouble, {pairs.sym_size(0)});
+    Tensor info = alloc(pairs, at::kLong, {kTransavgInfoWords});
+    if (meta) return {positions, registered, level, residual, scale, info};
     const int64_t Q = pairs.size(0);
-    Tensor positions = at::empty({cameras, 3}, like(pairs, at::kDouble));
-    Tensor registered = at::empty({cameras}, like(pairs, at::kByte));
-    Tensor level = at::empty({cameras}, like(pairs, at::kInt));
-    Tensor residual = at::empty({Q}, like(pairs, at::kDouble));
-    Tensor scale = at::empty({Q}, like(pairs, at::kDouble));
-    Tensor info = at::empty({kTransavgInfoWords}, like(pairs, at::kLong));
     const int64_t bytes = sfm_average_translations_workspace_bytes(cameras, Q);
     TORCH_CHECK(bytes >= 0, "sfm_hip: average_translations: ", cameras, " cameras, ", Q, " edges exceed the limits");
     Tensor ws = at::empty({bytes}, like(pairs, at::kByte));
@@ -1952,20 +1771,6 @@ TransavgResult average_translations(const Tensor& pairs, const Tensor& direction
                                 reinterpret_cast<sfm_transavg_info*>(ptr<int64_t>(info)), ws.data_ptr(), bytes, current_stream()),
        "sfm_average_translations");
     return {positions, registered, level, residual, scale, info};
-}
-
-TransavgResult average_translations_meta(const Tensor& pairs, const Tensor& directions, const std::optional<Tensor>& rotations,
-                                         const Tensor& weights, int64_t cameras, int64_t root,
-                                         const std::optional<Tensor>& initial, int64_t loss, double loss_scale,
-                                         int64_t warmup_steps, int64_t max_steps, int64_t max_cg_iterations,
-                                         double cg_tolerance, double step_tolerance) {
-    transavg_check(pairs, directions, rotations, weights, cameras, root, initial, loss, loss_scale, warmup_steps, max_steps,
-                   max_cg_iterations, cg_tolerance, step_tolerance);
-    const c10::SymInt C(cameras);
-    return {at::empty_symint({C, c10::SymInt(3)}, like(pairs, at::kDouble)), at::empty_symint({C}, like(pairs, at::kByte)),
-            at::empty_symint({C}, like(pairs, at::kInt)), at::empty_symint({pairs.sym_size(0)}, like(pairs, at::kDouble)),
-            at::empty_symint({pairs.sym_size(0)}, like(pairs, at::kDouble)),
-            at::empty_symint({c10::SymInt(kTransavgInfoWords)}, like(pairs, at::kLong))};
 }
 }  // namespace
 
@@ -2123,211 +1928,153 @@ TORCH_LIBRARY(sfm_hip, m) {
 
 // ROCm devices dispatch under torch's "CUDA" key (the name of the dispatch key, not a CUDA code path)
 TORCH_LIBRARY_IMPL(sfm_hip, CUDA, m) {
-    m.impl("normalize_coords", &normalize_coords);
+    m.impl("normalize_coords", &Forms<&normalize_coords_new>::call<false>);
     m.impl("normalize_coords_", &normalize_coords_out);
-    m.impl("fit_eight_point", &essential_fit_new<fit_eight_point_out>);
-    m.impl("five_point_fit", &essential_fit_new<five_point_fit_out>);
+    m.impl("fit_eight_point", &Forms<&essential_fit_new<fit_eight_point_out>>::call<false>);
+    m.impl("five_point_fit", &Forms<&essential_fit_new<five_point_fit_out>>::call<false>);
     m.impl("five_point_fit_", &five_point_fit_out);
     m.impl("five_point_ransac_pass_", &five_point_ransac_pass_out);
     m.impl("fit_eight_point_", &fit_eight_point_out);
     m.impl("sample_fit_philox_", &sample_fit_philox_out);
-    m.impl("score_sed", &score_sed);
+    m.impl("score_sed", &Forms<&score_sed_new>::call<false>);
     m.impl("score_sed_", &score_sed_out);
     m.impl("ransac_pass_small_", &ransac_pass_small_out);
     m.impl("ransac_pass_large_", &ransac_pass_large_out);
-    m.impl("select_best", &select_best);
+    m.impl("select_best", &Forms<&select_best_new>::call<false>);
     m.impl("select_best_", &select_best_out);
-    m.impl("inlier_mask", &inlier_mask);
+    m.impl("inlier_mask", &Forms<&inlier_mask_new>::call<false>);
     m.impl("inlier_mask_", &inlier_mask_out);
-    m.impl("cheirality", &cheirality);
-    m.impl("triangulate", &triangulate);
-    m.impl("homography_fit", &essential_fit_new<homography_fit_out>);
-    m.impl("homography_score", &homography_score);
-    m.impl("homography_inlier_mask", &homography_inlier_mask);
+    m.impl("cheirality", &Forms<&cheirality_new>::call<false>);
+    m.impl("triangulate", &Forms<&triangulate_new>::call<false>);
+    m.impl("homography_fit", &Forms<&essential_fit_new<homography_fit_out>>::call<false>);
+    m.impl("homography_score", &Forms<&homography_score_new>::call<false>);
+    m.impl("homography_inlier_mask", &Forms<&homography_inlier_mask_new>::call<false>);
     m.impl("homography_ransac_pass_", &homography_ransac_pass_out);
     m.impl("verify_pairs_", &verify_pairs_out);
-    m.impl("pair_poses", &pair_poses);
-    m.impl("refine_pair_poses", &refine_pair_poses);
-    m.impl("pnp_fit", &pose_fit_new<pnp_fit_out>);
+    m.impl("pair_poses", &Forms<&pair_poses_new>::call<false>);
+    m.impl("refine_pair_poses", &Forms<&refine_pair_poses_new>::call<false>);
+    m.impl("pnp_fit", &Forms<&pose_fit_new<pnp_fit_out>>::call<false>);
     m.impl("pnp_fit_", &pnp_fit_out);
-    m.impl("pnp_score", &pnp_score);
+    m.impl("pnp_score", &Forms<&pnp_score_new>::call<false>);
     m.impl("pnp_score_", &pnp_score_out);
     m.impl("pnp_ransac_pass_", &pnp_ransac_pass_out);
-    m.impl("p3p_fit", &pose_fit_new<p3p_fit_out>);
+    m.impl("p3p_fit", &Forms<&pose_fit_new<p3p_fit_out>>::call<false>);
     m.impl("p3p_fit_", &p3p_fit_out);
     m.impl("p3p_ransac_pass_", &p3p_ransac_pass_out);
-    m.impl("pnp_refine", &pnp_refine);
+    m.impl("pnp_refine", &Forms<&pnp_refine_new>::call<false>);
     m.impl("pnp_refine_", &pnp_refine_out);
-    m.impl("register_views", &register_views);
+    m.impl("register_views", &Forms<&register_views_new>::call<false>);
     m.impl("register_views_", &register_views_out);
-    m.impl("similarity_ransac_pass", &similarity_ransac_pass);
+    m.impl("similarity_ransac_pass", &Forms<&similarity_ransac_pass_new>::call<false>);
     m.impl("similarity_ransac_pass_", &similarity_ransac_pass_out);
-    m.impl("similarity_fit", &similarity_fit);
+    m.impl("similarity_fit", &Forms<&similarity_fit_new>::call<false>);
     m.impl("similarity_fit_", &similarity_fit_out);
-    m.impl("similarity_refine", &similarity_refine);
+    m.impl("similarity_refine", &Forms<&similarity_refine_new>::call<false>);
     m.impl("similarity_refine_", &similarity_refine_out);
-    m.impl("align_models", &align_models);
+    m.impl("align_models", &Forms<&align_models_new>::call<false>);
     m.impl("align_models_", &align_models_out);
-    m.impl("plane_sweep", &plane_sweep);
+    m.impl("plane_sweep", &Forms<&plane_sweep_new>::call<false>);
     m.impl("plane_sweep_", &plane_sweep_out);
-    m.impl("filter_depth_maps", &filter_depth_maps);
+    m.impl("filter_depth_maps", &Forms<&filter_depth_maps_new>::call<false>);
     m.impl("filter_depth_maps_", &filter_depth_maps_out);
-    m.impl("sgm_aggregate", &sgm_aggregate);
+    m.impl("sgm_aggregate", &Forms<&sgm_aggregate_new>::call<false>);
     m.impl("sgm_aggregate_", &sgm_aggregate_out);
-    m.impl("tsdf_integrate", &tsdf_integrate);
+    m.impl("tsdf_integrate", &Forms<&tsdf_integrate_new>::call<false>);
     m.impl("tsdf_integrate_", &tsdf_integrate_out);
-    m.impl("tsdf_extract_mesh", &tsdf_extract_mesh);
+    m.impl("tsdf_extract_mesh", &Forms<&tsdf_extract_mesh_new>::call<false>);
     m.impl("tsdf_extract_mesh_", &tsdf_extract_mesh_out);
-    m.impl("bundle_adjust", &bundle_adjust);
-    m.impl("bundle_adjust_", &bundle_adjust_inplace);
-    m.impl("bundle_adjust_pcg", &bundle_adjust_pcg);
-    m.impl("bundle_adjust_pcg_", &bundle_adjust_pcg_inplace);
-    m.impl("bundle_adjust_robust", &bundle_adjust_robust);
-    m.impl("bundle_adjust_robust_", &bundle_adjust_robust_inplace);
-    m.impl("bundle_adjust_pcg_robust", &bundle_adjust_pcg_robust);
-    m.impl("bundle_adjust_pcg_robust_", &bundle_adjust_pcg_robust_inplace);
-    m.impl("bundle_adjust_calibrated", &bundle_adjust_calibrated);
-    m.impl("bundle_adjust_calibrated_", &bundle_adjust_calibrated_inplace);
-    m.impl("triangulate_tracks", &triangulate_tracks);
+    m.impl("bundle_adjust", &Forms<&bundle_adjust_new>::call<false>);
+    m.impl("bundle_adjust_", &bundle_adjust_out);
+    m.impl("bundle_adjust_pcg", &Forms<&bundle_adjust_pcg_new>::call<false>);
+    m.impl("bundle_adjust_pcg_", &bundle_adjust_pcg_out);
+    m.impl("bundle_adjust_robust", &Forms<&bundle_adjust_robust_new>::call<false>);
+    m.impl("bundle_adjust_robust_", &bundle_adjust_robust_out);
+    m.impl("bundle_adjust_pcg_robust", &Forms<&bundle_adjust_pcg_robust_new>::call<false>);
+    m.impl("bundle_adjust_pcg_robust_", &bundle_adjust_pcg_robust_out);
+    m.impl("bundle_adjust_calibrated", &Forms<&bundle_calibrated_new>::call<false>);
+    m.impl("bundle_adjust_calibrated_", &bundle_adjust_calibrated_out);
+    m.impl("triangulate_tracks", &Forms<&triangulate_tracks_new>::call<false>);
     m.impl("triangulate_tracks_", &triangulate_tracks_out);
-    m.impl("build_tracks", &build_tracks);
+    m.impl("build_tracks", &Forms<&build_tracks_new>::call<false>);
     m.impl("build_tracks_", &build_tracks_out);
-    m.impl("average_rotations", &average_rotations);
-    m.impl("average_translations", &average_translations);
+    m.impl("average_rotations", &Forms<&average_rotations_new>::call<false>);
+    m.impl("average_translations", &Forms<&average_translations_new>::call<false>);
 }
 
 // sample_philox has no tensor argument to dispatch on: registered for every backend, it checks its device itself
 TORCH_LIBRARY_IMPL(sfm_hip, CompositeExplicitAutograd, m) { m.impl("sample_philox", &sample_philox); }
 
-// in-place forms under fake tensors: shapes are fixed by the caller's buffers, nothing to compute
-void normalize_coords_out_meta(const Tensor&, const Tensor&, double, double, double, double, Tensor&) {}
-void fit_eight_point_out_meta(const Tensor&, const Tensor&, Tensor&, Tensor&) {}
-void five_point_ransac_pass_out_meta(const Tensor&, int64_t, int64_t, bool, int64_t, double, double, int64_t, Tensor&, Tensor&, Tensor&,
-                                     Tensor&, Tensor&, Tensor&, Tensor&, const std::optional<Tensor>&) {}
-void verify_pairs_out_meta(const Tensor&, const Tensor&, const Tensor&, int64_t, int64_t, int64_t, double, int64_t, double, Tensor&,
-                           Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&,
-                           Tensor&, Tensor&, Tensor&) {}
-void sample_fit_philox_out_meta(const Tensor&, int64_t, const std::optional<Tensor>&, int64_t, int64_t, Tensor&, Tensor&,
-                                Tensor&) {}
-void score_sed_out_meta(const Tensor&, const Tensor&, const Tensor&, double, Tensor&, Tensor&, Tensor&,
-                        const std::optional<Tensor>&) {}
-void ransac_pass_small_out_meta(const Tensor&, int64_t, const std::optional<Tensor>&, bool, int64_t, double, double, int64_t,
-                                int64_t, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&,
-                                const std::optional<Tensor>&, Tensor&) {}
-void select_best_out_meta(const Tensor&, const Tensor&, const Tensor&, const std::optional<Tensor>&, double, int64_t,
-                          int64_t, Tensor&, int64_t) {}
-void inlier_mask_out_meta(const Tensor&, const Tensor&, const Tensor&, const Tensor&, double, Tensor&, int64_t) {}
-void pnp_fit_out_meta(const Tensor&, const Tensor&, at::ArrayRef<double>, Tensor&, Tensor&) {}
-void pnp_score_out_meta(const Tensor&, const Tensor&, const Tensor&, at::ArrayRef<double>, double, Tensor&, Tensor&, Tensor&,
-                        int64_t) {}
-void pnp_ransac_pass_out_meta(const Tensor&, int64_t, int64_t, bool, int64_t, at::ArrayRef<double>, double, double, int64_t, Tensor&,
-                              Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, const std::optional<Tensor>&) {}
-void pnp_refine_out_meta(const Tensor&, const Tensor&, const Tensor&, const Tensor&, at::ArrayRef<double>, double, int64_t, int64_t,
-                         int64_t, Tensor&, Tensor&, Tensor&) {}
-void register_views_out_meta(const Tensor&, const Tensor&, const Tensor&, at::ArrayRef<double>, int64_t, int64_t, int64_t, double, int64_t,
-                             int64_t, int64_t, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&,
-                             Tensor&, Tensor&) {}
-void align_models_out_meta(const Tensor&, const Tensor&, const Tensor&, const Tensor&, int64_t, int64_t, int64_t, int64_t, int64_t,
-                           int64_t, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&,
-                           Tensor&) {}
-void plane_sweep_out_meta(const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, int64_t, int64_t, int64_t,
-                          double, Tensor&, Tensor&, Tensor&, Tensor&, const std::optional<Tensor>&) {}
-void filter_depth_maps_out_meta(const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, double, double, int64_t, Tensor&,
-                                Tensor&, Tensor&, Tensor&) {}
-void sgm_aggregate_out_meta(const Tensor&, const Tensor&, double, double, double, int64_t, Tensor&, Tensor&, Tensor&,
-                            const std::optional<Tensor>&) {}
-void tsdf_integrate_out_meta(Tensor&, Tensor&, const std::optional<Tensor>&, const Tensor&, const std::optional<Tensor>&, const Tensor&,
-                             const Tensor&, const Tensor&, double, double, double, double, double, Tensor&) {}
-void tsdf_extract_mesh_out_meta(const Tensor&, const Tensor&, const std::optional<Tensor>&, double, double, double, double, int64_t, Tensor&,
-                                const std::optional<Tensor>&, Tensor&) {}
-void similarity_fit_out_meta(const Tensor&, const std::optional<Tensor>&, Tensor&, Tensor&) {}
-void similarity_refine_out_meta(const Tensor&, const Tensor&, const Tensor&, const Tensor&, double, int64_t, int64_t, Tensor&, Tensor&,
-                                Tensor&) {}
-void bundle_adjust_out_meta(Tensor&, Tensor&, const Tensor&, const Tensor&, const Tensor&, at::ArrayRef<double>, at::ArrayRef<int64_t>,
-                            int64_t, Tensor&) {}
-void bundle_adjust_pcg_out_meta(Tensor&, Tensor&, const Tensor&, const Tensor&, const Tensor&, at::ArrayRef<double>,
-                                at::ArrayRef<int64_t>, int64_t, int64_t, double, Tensor&) {}
-void bundle_adjust_robust_out_meta(Tensor&, Tensor&, const Tensor&, const Tensor&, const Tensor&, at::ArrayRef<double>,
-                                   at::ArrayRef<int64_t>, int64_t, int64_t, double, Tensor&) {}
-void bundle_adjust_pcg_robust_out_meta(Tensor&, Tensor&, const Tensor&, const Tensor&, const Tensor&, at::ArrayRef<double>,
-                                       at::ArrayRef<int64_t>, int64_t, int64_t, double, int64_t, double, Tensor&) {}
-void bundle_adjust_calibrated_out_meta(Tensor&, Tensor&, const Tensor&, const Tensor&, const Tensor&, at::ArrayRef<double>,
-                                       at::ArrayRef<int64_t>, int64_t, int64_t, double, int64_t, Tensor&, Tensor&) {}
-void triangulate_tracks_out_meta(const Tensor&, const Tensor&, const Tensor&, const Tensor&, int64_t, at::ArrayRef<double>, int64_t,
-                                 double, double, int64_t, Tensor&, Tensor&, Tensor&, Tensor&, Tensor&) {}
-void build_tracks_out_meta(const Tensor&, const Tensor&, const Tensor&, const Tensor&, int64_t, Tensor&, Tensor&, Tensor&, Tensor&,
-                           Tensor&, Tensor&, Tensor&) {}
-
+// Under fake tensors a functional form gives its outputs' shapes; an in-place form has nothing to compute
 TORCH_LIBRARY_IMPL(sfm_hip, Meta, m) {
-    m.impl("normalize_coords_", &normalize_coords_out_meta);
-    m.impl("fit_eight_point_", &fit_eight_point_out_meta);
-    m.impl("five_point_fit_", &fit_eight_point_out_meta);
-    m.impl("five_point_ransac_pass_", &five_point_ransac_pass_out_meta);
-    m.impl("sample_fit_philox_", &sample_fit_philox_out_meta);
-    m.impl("score_sed_", &score_sed_out_meta);
-    m.impl("ransac_pass_small_", &ransac_pass_small_out_meta);
-    m.impl("ransac_pass_large_", &ransac_pass_small_out_meta);
-    m.impl("select_best_", &select_best_out_meta);
-    m.impl("inlier_mask_", &inlier_mask_out_meta);
-    m.impl("normalize_coords", &normalize_coords_meta);
-    m.impl("fit_eight_point", &fit_eight_point_meta);
-    m.impl("five_point_fit", &fit_eight_point_meta);
-    m.impl("score_sed", &score_sed_meta);
-    m.impl("select_best", &select_best_meta);
-    m.impl("inlier_mask", &inlier_mask_meta);
-    m.impl("cheirality", &cheirality_meta);
-    m.impl("triangulate", &triangulate_meta);
-    m.impl("homography_fit", &fit_eight_point_meta);
-    m.impl("homography_score", &homography_score_meta);
-    m.impl("homography_inlier_mask", &homography_inlier_mask_meta);
-    m.impl("homography_ransac_pass_", &five_point_ransac_pass_out_meta);
-    m.impl("verify_pairs_", &verify_pairs_out_meta);
-    m.impl("pair_poses", &pair_poses_meta);
-    m.impl("refine_pair_poses", &refine_pair_poses_meta);
-    m.impl("pnp_fit", &pnp_fit_meta);
-    m.impl("pnp_score", &pnp_score_meta);
-    m.impl("pnp_fit_", &pnp_fit_out_meta);
-    m.impl("pnp_score_", &pnp_score_out_meta);
-    m.impl("pnp_ransac_pass_", &pnp_ransac_pass_out_meta);
-    m.impl("p3p_fit", &pnp_fit_meta);
-    m.impl("p3p_fit_", &pnp_fit_out_meta);
-    m.impl("p3p_ransac_pass_", &pnp_ransac_pass_out_meta);
-    m.impl("pnp_refine", &pnp_refine_meta);
-    m.impl("pnp_refine_", &pnp_refine_out_meta);
-    m.impl("register_views", &register_views_meta);
-    m.impl("register_views_", &register_views_out_meta);
-    m.impl("similarity_ransac_pass", &similarity_ransac_pass_meta);
-    m.impl("similarity_ransac_pass_", &five_point_ransac_pass_out_meta);
-    m.impl("similarity_fit", &similarity_fit_meta);
-    m.impl("similarity_fit_", &similarity_fit_out_meta);
-    m.impl("similarity_refine", &similarity_refine_meta);
-    m.impl("similarity_refine_", &similarity_refine_out_meta);
-    m.impl("align_models", &align_models_meta);
-    m.impl("align_models_", &align_models_out_meta);
-    m.impl("plane_sweep", &plane_sweep_meta);
-    m.impl("plane_sweep_", &plane_sweep_out_meta);
-    m.impl("filter_depth_maps", &filter_depth_maps_meta);
-    m.impl("filter_depth_maps_", &filter_depth_maps_out_meta);
-    m.impl("sgm_aggregate", &sgm_aggregate_meta);
-    m.impl("sgm_aggregate_", &sgm_aggregate_out_meta);
-    m.impl("tsdf_integrate", &tsdf_integrate_meta);
-    m.impl("tsdf_integrate_", &tsdf_integrate_out_meta);
-    m.impl("tsdf_extract_mesh", &tsdf_extract_mesh_meta);
-    m.impl("tsdf_extract_mesh_", &tsdf_extract_mesh_out_meta);
-    m.impl("bundle_adjust", &bundle_adjust_meta);
-    m.impl("bundle_adjust_", &bundle_adjust_out_meta);
-    m.impl("bundle_adjust_pcg", &bundle_adjust_pcg_meta);
-    m.impl("bundle_adjust_pcg_", &bundle_adjust_pcg_out_meta);
-    m.impl("bundle_adjust_robust", &bundle_adjust_robust_meta);
-    m.impl("bundle_adjust_robust_", &bundle_adjust_robust_out_meta);
-    m.impl("bundle_adjust_pcg_robust", &bundle_adjust_pcg_robust_meta);
-    m.impl("bundle_adjust_pcg_robust_", &bundle_adjust_pcg_robust_out_meta);
-    m.impl("bundle_adjust_calibrated", &bundle_adjust_calibrated_meta);
-    m.impl("bundle_adjust_calibrated_", &bundle_adjust_calibrated_out_meta);
-    m.impl("triangulate_tracks", &triangulate_tracks_meta);
-    m.impl("triangulate_tracks_", &triangulate_tracks_out_meta);
-    m.impl("build_tracks", &build_tracks_meta);
-    m.impl("build_tracks_", &build_tracks_out_meta);
-    m.impl("average_rotations", &average_rotations_meta);
-    m.impl("average_translations", &average_translations_meta);
+    m.impl("normalize_coords", &Forms<&normalize_coords_new>::call<true>);
+    m.impl("normalize_coords_", &Noop<&normalize_coords_out>::call);
+    m.impl("fit_eight_point", &Forms<&essential_fit_new<fit_eight_point_out>>::call<true>);
+    m.impl("five_point_fit", &Forms<&essential_fit_new<five_point_fit_out>>::call<true>);
+    m.impl("five_point_fit_", &Noop<&five_point_fit_out>::call);
+    m.impl("five_point_ransac_pass_", &Noop<&five_point_ransac_pass_out>::call);
+    m.impl("fit_eight_point_", &Noop<&fit_eight_point_out>::call);
+    m.impl("sample_fit_philox_", &Noop<&sample_fit_philox_out>::call);
+    m.impl("score_sed", &Forms<&score_sed_new>::call<true>);
+    m.impl("score_sed_", &Noop<&score_sed_out>::call);
+    m.impl("ransac_pass_small_", &Noop<&ransac_pass_small_out>::call);
+    m.impl("ransac_pass_large_", &Noop<&ransac_pass_large_out>::call);
+    m.impl("select_best", &Forms<&select_best_new>::call<true>);
+    m.impl("select_best_", &Noop<&select_best_out>::call);
+    m.impl("inlier_mask", &Forms<&inlier_mask_new>::call<true>);
+    m.impl("inlier_mask_", &Noop<&inlier_mask_out>::call);
+    m.impl("cheirality", &Forms<&cheirality_new>::call<true>);
+    m.impl("triangulate", &Forms<&triangulate_new>::call<true>);
+    m.impl("homography_fit", &Forms<&essential_fit_new<homography_fit_out>>::call<true>);
+    m.impl("homography_score", &Forms<&homography_score_new>::call<true>);
+    m.impl("homography_inlier_mask", &Forms<&homography_inlier_mask_new>::call<true>);
+    m.impl("homography_ransac_pass_", &Noop<&homography_ransac_pass_out>::call);
+    m.impl("verify_pairs_", &Noop<&verify_pairs_out>::call);
+    m.impl("pair_poses", &Forms<&pair_poses_new>::call<true>);
+    m.impl("refine_pair_poses", &Forms<&refine_pair_poses_new>::call<true>);
+    m.impl("pnp_fit", &Forms<&pose_fit_new<pnp_fit_out>>::call<true>);
+    m.impl("pnp_fit_", &Noop<&pnp_fit_out>::call);
+    m.impl("pnp_score", &Forms<&pnp_score_new>::call<true>);
+    m.impl("pnp_score_", &Noop<&pnp_score_out>::call);
+    m.impl("pnp_ransac_pass_", &Noop<&pnp_ransac_pass_out>::call);
+    m.impl("p3p_fit", &Forms<&pose_fit_new<p3p_fit_out>>::call<true>);
+    m.impl("p3p_fit_", &Noop<&p3p_fit_out>::call);
+    m.impl("p3p_ransac_pass_", &Noop<&p3p_ransac_pass_out>::call);
+    m.impl("pnp_refine", &Forms<&pnp_refine_new>::call<true>);
+    m.impl("pnp_refine_", &Noop<&pnp_refine_out>::call);
+    m.impl("register_views", &Forms<&register_views_new>::call<true>);
+    m.impl("register_views_", &Noop<&register_views_out>::call);
+    m.impl("similarity_ransac_pass", &Forms<&similarity_ransac_pass_new>::call<true>);
+    m.impl("similarity_ransac_pass_", &Noop<&similarity_ransac_pass_out>::call);
+    m.impl("similarity_fit", &Forms<&similarity_fit_new>::call<true>);
+    m.impl("similarity_fit_", &Noop<&similarity_fit_out>::call);
+    m.impl("similarity_refine", &Forms<&similarity_refine_new>::call<true>);
+    m.impl("similarity_refine_", &Noop<&similarity_refine_out>::call);
+    m.impl("align_models", &Forms<&align_models_new>::call<true>);
+    m.impl("align_models_", &Noop<&align_models_out>::call);
+    m.impl("plane_sweep", &Forms<&plane_sweep_new>::call<true>);
+    m.impl("plane_sweep_", &Noop<&plane_sweep_out>::call);
+    m.impl("filter_depth_maps", &Forms<&filter_depth_maps_new>::call<true>);
+    m.impl("filter_depth_maps_", &Noop<&filter_depth_maps_out>::call);
+    m.impl("sgm_aggregate", &Forms<&sgm_aggregate_new>::call<true>);
+    m.impl("sgm_aggregate_", &Noop<&sgm_aggregate_out>::call);
+    m.impl("tsdf_integrate", &Forms<&tsdf_integrate_new>::call<true>);
+    m.impl("tsdf_integrate_", &Noop<&tsdf_integrate_out>::call);
+    m.impl("tsdf_extract_mesh", &Forms<&tsdf_extract_mesh_new>::call<true>);
+    m.impl("tsdf_extract_mesh_", &Noop<&tsdf_extract_mesh_out>::call);
+    m.impl("bundle_adjust", &Forms<&bundle_adjust_new>::call<true>);
+    m.impl("bundle_adjust_", &Noop<&bundle_adjust_out>::call);
+    m.impl("bundle_adjust_pcg", &Forms<&bundle_adjust_pcg_new>::call<true>);
+    m.impl("bundle_adjust_pcg_", &Noop<&bundle_adjust_pcg_out>::call);
+    m.impl("bundle_adjust_robust", &Forms<&bundle_adjust_robust_new>::call<true>);
+    m.impl("bundle_adjust_robust_", &Noop<&bundle_adjust_robust_out>::call);
+    m.impl("bundle_adjust_pcg_robust", &Forms<&bundle_adjust_pcg_robust_new>::call<true>);
+    m.impl("bundle_adjust_pcg_robust_", &Noop<&bundle_adjust_pcg_robust_out>::call);
+    m.impl("bundle_adjust_calibrated", &Forms<&bundle_calibrated_new>::call<true>);
+    m.impl("bundle_adjust_calibrated_", &Noop<&bundle_adjust_calibrated_out>::call);
+    m.impl("triangulate_tracks", &Forms<&triangulate_tracks_new>::call<true>);
+    m.impl("triangulate_tracks_", &Noop<&triangulate_tracks_out>::call);
+    m.impl("build_tracks", &Forms<&build_tracks_new>::call<true>);
+    m.impl("build_tracks_", &Noop<&build_tracks_out>::call);
+    m.impl("average_rotations", &Forms<&average_rotations_new>::call<true>);
+    m.impl("average_translations", &Forms<&average_translations_new>::call<true>);
 }

@@ -1,10 +1,10 @@
 """``torch.ops.sfm_hip.*`` — the hot-path kernels as PyTorch-ROCm custom ops (csrc/sfm_torch_ops.cpp, a
 ``TORCH_LIBRARY`` above the C ABI of include/sfm_hip.h).
 
-Op set: ``normalize_coords, sample_philox, fit_eight_point, score_sed, select_best, inlier_mask,
-cheirality, triangulate``, the five-point ops ``five_point_fit``, the homography ops ``homography_fit, homography_score, homography_inlier_mask``, the ragged two-view pass ``verify_pairs_`` (in-place only) and the poses behind it ``pair_poses`` and their refinement ``refine_pair_poses``, the PnP ops ``pnp_fit, p3p_fit, pnp_score, pnp_refine``, the ragged absolute-pose call ``register_views``, the similarity alignment ``similarity_ransac_pass, similarity_fit, similarity_refine``, the ragged alignment of sub-model pairs ``align_models``, the dense stage ``plane_sweep`` and ``filter_depth_maps``, the fusion ``tsdf_integrate`` and ``tsdf_extract_mesh``, the cost-volume smoothing ``sgm_aggregate``, ``bundle_adjust``, ``bundle_adjust_pcg``, their robust-loss forms ``bundle_adjust_robust`` and ``bundle_adjust_pcg_robust``, the calibrating ``bundle_adjust_calibrated``, ``triangulate_tracks``, ``build_tracks``, ``average_rotations`` and ``average_translations`` — functional forms with Meta kernels (fake tensors, ``torch.compile``,
-``torch.library.opcheck``) — and the in-place ``*_`` forms the pre-allocated engine uses.  ``device.py`` dispatches
-through them; ``load()`` must have run before ``torch.ops.sfm_hip`` is touched.
+The ``TORCH_LIBRARY(sfm_hip, m)`` block of that file is the list of ops and their schemas.  A functional op allocates its
+outputs and has a Meta form (fake tensors, ``torch.compile``, ``torch.library.opcheck``); an in-place ``*_`` op writes the
+buffers the pre-allocating engine hands it.  ``device.py`` dispatches through them; ``load()`` must have run before
+``torch.ops.sfm_hip`` is touched.
 """
 from __future__ import annotations
 
